@@ -13,6 +13,14 @@ own random restart (restart i on rank i; no data-path collective -> weak scaling
 job ends with one all-reduce (RCCL) that picks the maximum-likelihood restart.  Rank 0 prints
 ONE JSON line.
 
+A plain run sets up, warms up, times the K steps and prints the headline (`metric`, `value`, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step`, the workload and the library's build id); `--dump-outputs DIR` also
+writes what the last timed step left for a caller (theta, eta, pr of restart 0) as DIR/<name>.npy.  Everything
+else -- the CPU baseline, the one-rank RCCL group at N = 1, the job's wall clock by stage, per-rank records,
+steady-state and median-of-5 rates, per-kernel profile, roofline, batched restarts -- runs with `--full` only:
+
+    python bench.py --gpus 1 --steps 200 --warmup 20 --full
+
 `roofline` is for the dominant kernel: `achieved` = SURVEY 8(d)'s algorithmic bytes that launch
 serves / its mean duration from HIP events on the library's stream; the `rocprofv3 --kernel-trace
 --stats` duration and the PMC traffic of the same command come from profiles/ (tracked).
@@ -41,6 +49,13 @@ def parse_args():
     ap.add_argument("--steps", type=int, default=1000)
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--config", default="c3", choices=["c1", "c2", "c3", "c5"])
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, everything else the benchmark measures and checks (CPU baseline, "
+                         "one-rank RCCL group, job stages, steady-state and median-of-5 rates, per-kernel profile, "
+                         "roofline, --batched-restarts); the options below that tune those act with --full only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what they computed (theta, eta, pr of restart 0, float64) as "
+                         "DIR/<name>.npy, at most 64 MB in all (a fixed, seeded row sample of larger tables)")
     ap.add_argument("--profile-iters", type=int, default=20)
     ap.add_argument("--cpu-sample-rows", type=int, default=0,
                     help="rows of the workload the CPU baseline is timed on (0 = all of them where the "
@@ -70,7 +85,17 @@ def parse_args():
     ap.add_argument("--no-collective-at-1", action="store_true",
                     help="with one GPU skip the one-rank process group (by default the end-of-job pick "
                          "goes through RCCL even at N=1, so that path is exercised on every run)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if not args.full and not args.cpu_worker:
+        # options of what --full adds: silently ignoring one would print a line that lacks what was asked for
+        given = [f"--{nm.replace('_', '-')}" for nm in FULL_ONLY if getattr(args, nm) != ap.get_default(nm)]
+        if given:
+            ap.error(f"{', '.join(given)} act(s) with --full only")
+    return args
+
+
+FULL_ONLY = ("profile_iters", "cpu_sample_rows", "cpu_iters", "no_cpu_baseline", "batched_restarts", "steady_steps",
+             "no_collective_at_1")
 
 
 def self_launch(args):
@@ -83,7 +108,7 @@ def self_launch(args):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
-    if not args.no_cpu_baseline and CPU_BASELINE_ENV not in env:
+    if args.full and not args.no_cpu_baseline and CPU_BASELINE_ENV not in env:
         # the reference's side of an N-GPU number: `sampling` = N processes, one restart each (src/mmsbm.py:182-185),
         # timed HERE -- this parent never touches the GPU -- before the ranks exist, and handed to rank 0
         env[CPU_BASELINE_ENV] = json.dumps(cpu_baseline_processes(args, args.gpus))
@@ -274,6 +299,34 @@ def batched_rate(model, train, device, slots, iters):
             "value": slots * iters / (ms * 1e-3), "unit": "restart-iterations/s on one GPU (HIP events)"}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, limit=DUMP_LIMIT_BYTES):
+    """`arrays` ({name: float64 array}) -> out_dir/<name>.npy; returns {file stem: shape}.  When they would take more
+    than `limit` bytes in all, the 2-d tables keep a sample of their rows -- the same fraction of each, chosen by a
+    fixed seed, so that every run and every build dumps the same entries -- and the chosen row numbers go beside them
+    as <name>_rows.npy (float64, exact)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {nm: np.ascontiguousarray(a, dtype=np.float64) for nm, a in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > limit:
+        big = [nm for nm, a in arrays.items() if a.ndim == 2]
+        rest = sum(a.nbytes for nm, a in arrays.items() if nm not in big)
+        per_all_rows = sum(arrays[nm].shape[0] * (arrays[nm].shape[1] + 1) * 8 for nm in big)
+        frac = (limit - rest) / per_all_rows
+        for j, nm in enumerate(big):
+            a = arrays[nm]
+            keep = max(1, int(a.shape[0] * frac))
+            rows = np.sort(np.random.default_rng([0, j]).choice(a.shape[0], size=keep, replace=False))
+            arrays[nm] = np.ascontiguousarray(a[rows])
+            arrays[nm + "_rows"] = rows.astype(np.float64)
+    for nm, a in arrays.items():
+        np.save(os.path.join(out_dir, nm + ".npy"), a)
+    return {nm: list(a.shape) for nm, a in arrays.items()}
+
+
 def _config_groups(config):
     from mmsbm_amd.synthetic import CONFIGS
     k, l = CONFIGS[config][4:6]
@@ -352,7 +405,7 @@ def main():
     cpu_pre = None
     if os.environ.get(CPU_BASELINE_ENV):
         cpu_pre = json.loads(os.environ[CPU_BASELINE_ENV])
-    elif args.gpus > 1 and int(os.environ.get("RANK", "0")) == 0 and not args.no_cpu_baseline:
+    elif args.full and args.gpus > 1 and int(os.environ.get("RANK", "0")) == 0 and not args.no_cpu_baseline:
         cpu_pre = cpu_baseline_processes(args, args.gpus)
     # stdout carries exactly ONE line (rank 0's JSON): whatever libraries print while the job runs
     # (RCCL's version banner, for one) goes to stderr instead
@@ -447,6 +500,45 @@ def main():
     # MMSBM_HIP_LIBRARY may point elsewhere): recorded, and `traffic` is dropped when it is not
     from mmsbm_amd import _lib
     build_id = _lib.build_id()
+    # what the last timed step left for a caller, before anything below advances the parameters further
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        theta_d, eta_d, pr_d = ctx.get_params()
+        dumped = dump_outputs(args.dump_outputs, {"theta": theta_d, "eta": eta_d, "pr": pr_d})
+
+    # the headline: what a plain run prints, and the first fields of a --full line
+    head = None
+    if rank == 0:
+        head = {
+            "metric": "EM iterations/sec (1M ratings, K=L=20)" if (args.config == "c3" and args.groups in (0, 20))
+                      else f"EM iterations/sec ({args.config}" + (f", K=L={args.groups})" if args.groups else ")"),
+            "value": world * args.steps / elapsed_max, "unit": "it/s", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": 1000.0 * elapsed_max / args.steps,
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "f64", "data": "synthetic",
+            "config": {"workload": f"{args.config.upper()}: {n} synthetic ratings, {model.p + 1} users x "
+                                   f"{model.m + 1} items, R={r}, K={k}, L={l}, one restart per GPU "
+                                   f"(sampling={world}), uniform generator seed 0, model seed 0",
+                       "launch": "hipGraph replay" if args.graph else "eager",
+                       "pairs": ctx.n_pairs,
+                       "launches_per_iteration": int(ctx.get_option("launches")),
+                       "pair_stage": {0.0: "vector ALUs (pair_block_kernel)", 1.0: "matrix cores (pair_mfma_kernel)",
+                                      2.0: "matrix cores, blocked (mfma_rows_kernel + mfma_slab_kernel)"}[ctx.get_option("mfma")]},
+        }
+        if dumped is not None:
+            head["outputs"] = {"dir": args.dump_outputs, "arrays": dumped,
+                               "what": "theta, eta, pr of restart 0 after warmup + steps iterations"}
+    if not args.full:
+        if rank == 0:
+            head["library"] = {"build_id": build_id}
+        fence()
+        if rank == 0:
+            sys.stdout.flush()
+            os.write(json_fd, (json.dumps(head) + "\n").encode())
+        os.close(json_fd)
+        if dist.is_initialized():
+            dist.destroy_process_group()
+        return
 
     # end of the job: likelihood of this rank's restart + ONE all-reduce to pick the best + the winner's theta / eta /
     # pr from the rank that ran it to everyone (three tensor broadcasts) -- evaluated on the parameters after
@@ -525,20 +617,7 @@ def main():
         if coll_error:
             coll["error"] = coll_error
         out = {
-            "metric": "EM iterations/sec (1M ratings, K=L=20)" if (args.config == "c3" and args.groups in (0, 20))
-                      else f"EM iterations/sec ({args.config}" + (f", K=L={args.groups})" if args.groups else ")"),
-            "value": its, "unit": "it/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": 1000.0 * elapsed_max / args.steps,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f64", "data": "synthetic",
-            "config": {"workload": f"{args.config.upper()}: {n} synthetic ratings, {model.p + 1} users x "
-                                   f"{model.m + 1} items, R={r}, K={k}, L={l}, one restart per GPU "
-                                   f"(sampling={world}), uniform generator seed 0, model seed 0",
-                       "launch": "hipGraph replay" if args.graph else "eager",
-                       "pairs": ctx.n_pairs,
-                       "launches_per_iteration": int(ctx.get_option("launches")),
-                       "pair_stage": {0.0: "vector ALUs (pair_block_kernel)", 1.0: "matrix cores (pair_mfma_kernel)",
-                                      2.0: "matrix cores, blocked (mfma_rows_kernel + mfma_slab_kernel)"}[ctx.get_option("mfma")]},
+            **head,
             "collective": coll,
             "ranks": ranks,
             "distinct_devices": len({(r["hostname"], r["pci_bus_id"]) for r in ranks}),

@@ -44,14 +44,14 @@ ROWS = [
 
 
 def run_row(args_list, timeout):
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1"] + args_list
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--full"] + args_list
     t0 = time.time()
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout)
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
     if res.returncode != 0 or not lines:
         raise RuntimeError(f"{' '.join(cmd)} failed (rc {res.returncode}):\n{res.stderr[-2000:]}")
     out = json.loads(lines[-1])
-    out["_command"] = "python bench.py --gpus 1 " + " ".join(args_list)
+    out["_command"] = "python bench.py --gpus 1 --full " + " ".join(args_list)
     out["_wall_s"] = round(time.time() - t0, 1)
     return out
 

@@ -1,8 +1,8 @@
-"""TEST INFRASTRUCTURE (build container only).  With this directory on PYTHONPATH every Python process of the
-environment -- the spawned Pool workers of the reference's ``MMSBM.fit`` (src/mmsbm.py:182-185) included -- starts
-with ``tests.fake_device.FakeHipEM`` (the oracle behind the device interface) standing in for the HIP library's
-handle, so that the REAL reference caller can drive ``mmsbm_amd/plugin/kernels_hip.py`` on a machine without a GPU
-(``tests/test_reference_caller_cpu.py``).  Nothing under ``mmsbm_amd/`` knows about this file."""
+"""TEST INFRASTRUCTURE.  With this directory on PYTHONPATH every Python process of the environment -- the spawned
+Pool workers of a caller that runs each restart in one, as the reference's ``MMSBM.fit`` does (src/mmsbm.py:182-185),
+included -- starts with ``tests.fake_device.FakeHipEM`` (the oracle behind the device interface) standing in for the
+HIP library's handle, so that such a caller can drive ``mmsbm_amd/plugin/kernels_hip.py`` on a machine without a GPU
+(``tests/test_plugin_caller_cpu.py``).  Nothing under ``mmsbm_amd/`` knows about this file."""
 import os
 import sys
 

@@ -75,7 +75,7 @@ def test_self_launch_starts_torch_distributed_run_as_a_child(monkeypatch):
     monkeypatch.setattr(bench.subprocess, "run", fake_run)
     monkeypatch.setattr(bench, "cpu_baseline_processes", lambda args, procs: {"value": 1.5, "cores": procs, "kind": "port"})
     monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "4", "--steps", "20", "--warmup", "5"])
-    rc = bench.self_launch(types.SimpleNamespace(gpus=4, no_cpu_baseline=False))
+    rc = bench.self_launch(types.SimpleNamespace(gpus=4, full=True, no_cpu_baseline=False))
     assert rc == 7
     # the GPU-free parent times the CPU side on N processes BEFORE the ranks exist and hands it to rank 0
     assert json.loads(seen["env"][bench.CPU_BASELINE_ENV]) == {"value": 1.5, "cores": 4, "kind": "port"}
@@ -106,6 +106,63 @@ def test_argument_defaults(monkeypatch):
     monkeypatch.setattr(sys, "argv", ["bench.py"])
     a = bench.parse_args()
     assert (a.gpus, a.config, a.no_cpu_baseline, a.batched_restarts) == (1, "c3", False, 0) and a.steps >= 100
+    assert a.full is False and a.dump_outputs is None
+
+
+@pytest.mark.parametrize("extra", [["--batched-restarts", "8"], ["--steady-steps", "0"], ["--no-cpu-baseline"],
+                                   ["--cpu-iters", "1"], ["--profile-iters", "2"], ["--no-collective-at-1"]])
+def test_what_full_adds_is_refused_on_a_plain_run(monkeypatch, capsys, extra):
+    """A plain run prints the headline only: an option that tunes what --full adds is an error there, not ignored."""
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "20"] + extra)
+    with pytest.raises(SystemExit) as exc:
+        bench.parse_args()
+    assert exc.value.code == 2 and "--full only" in capsys.readouterr().err
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "20", "--full"] + extra)
+    assert bench.parse_args().full
+
+
+def test_plain_self_launch_times_no_cpu_baseline(monkeypatch):
+    seen = {}
+    monkeypatch.setattr(bench.subprocess, "run", lambda cmd, env=None: seen.update(env=env) or types.SimpleNamespace(returncode=0))
+    monkeypatch.setattr(bench, "cpu_baseline_processes", lambda args, procs: pytest.fail("timed a CPU baseline"))
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "2"])
+    monkeypatch.delenv(bench.CPU_BASELINE_ENV, raising=False)
+    assert bench.self_launch(types.SimpleNamespace(gpus=2, full=False, no_cpu_baseline=False)) == 0
+    assert bench.CPU_BASELINE_ENV not in seen["env"]
+
+
+def test_dump_outputs_writes_float64_arrays_whole_when_they_fit(tmp_path):
+    import numpy as np
+    rng = np.random.default_rng(1)
+    arrays = {"theta": rng.random((50, 4)), "eta": rng.random((30, 3)), "pr": rng.random((4, 3, 5))}
+    got = bench.dump_outputs(str(tmp_path), arrays)
+    assert got == {"theta": [50, 4], "eta": [30, 3], "pr": [4, 3, 5]}
+    for nm, a in arrays.items():
+        back = np.load(tmp_path / f"{nm}.npy")
+        assert back.dtype == np.float64 and np.array_equal(back, a)
+
+
+def test_dump_outputs_samples_the_same_rows_when_too_big(tmp_path):
+    """Over the limit the tables keep a seeded sample of their rows (the same in every run), row numbers beside them;
+    the small arrays stay whole, and the files together stay inside the limit."""
+    import numpy as np
+    rng = np.random.default_rng(2)
+    arrays = {"theta": rng.random((10_000, 20)), "eta": rng.random((2_000, 20)), "pr": rng.random((20, 20, 5))}
+    limit = 400_000
+    runs = []
+    for j in range(2):
+        out = tmp_path / str(j)
+        got = bench.dump_outputs(str(out), arrays, limit=limit)
+        assert set(got) == {"theta", "eta", "pr", "theta_rows", "eta_rows"}
+        assert sum(np.load(f).nbytes for f in out.iterdir()) <= limit
+        runs.append({nm: np.load(out / f"{nm}.npy") for nm in got})
+    for nm in runs[0]:
+        assert runs[0][nm].dtype == np.float64 and np.array_equal(runs[0][nm], runs[1][nm]), nm
+    for nm in ("theta", "eta"):
+        rows = runs[0][nm + "_rows"].astype(np.int64)
+        assert len(rows) > 100 and np.all(np.diff(rows) > 0) and rows[-1] < len(arrays[nm])
+        assert np.array_equal(runs[0][nm], arrays[nm][rows])
+    assert np.array_equal(runs[0]["pr"], arrays["pr"])
 
 
 GATHER_WORKER = """
@@ -170,7 +227,7 @@ def test_bench_refuses_ranks_without_local_rank():
     env = {k: v for k, v in os.environ.items() if k not in ("LOCAL_RANK",)}
     env.update(WORLD_SIZE="2", RANK="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="1", MMSBM_HIP_LAUNCH_LOG="")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                        "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=300)
+                        "--full", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode != 0 and r.stdout.strip() == "" and "LOCAL_RANK" in r.stderr, (r.returncode, r.stderr[-800:])
 
 

@@ -91,7 +91,7 @@ def test_bench_one_gpu_line_has_roofline_cpu_baseline_and_rccl_collective():
     """The default shape of the driver's command on a small workload (C2): ONE JSON line with the
     contract's keys; at N=1 the end-of-job pick still goes through a one-rank RCCL group."""
     res = _run([sys.executable, "bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5", "--config", "c2",
-                "--cpu-iters", "2"])
+                "--full", "--cpu-iters", "2"])
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
     out = _json_line(res.stdout)
     assert out["n_gpus"] == 1 and out["steps"] == 20 and out["unit"] == "it/s" and out["dtype"] == "f64"
@@ -120,13 +120,36 @@ def test_bench_one_gpu_line_has_roofline_cpu_baseline_and_rccl_collective():
     assert ss["value"] == pytest.approx(1000.0 / ss["ms_per_step"], rel=1e-9)
 
 
+def test_bench_plain_line_is_the_headline_and_dumps_the_oracles_parameters(tmp_path):
+    """A plain run (no --full): the headline alone, and with --dump-outputs the parameters the timed steps left --
+    restart 0 of model seed 0 after warmup + steps iterations, which the oracle reproduces from the same start."""
+    from mmsbm_amd.synthetic import CONFIGS
+    from oracle import mmsbm_oracle as orc
+    dump = tmp_path / "out"
+    res = _run([sys.executable, "bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5", "--config", "c1",
+                "--dump-outputs", str(dump)])
+    assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
+    out = _json_line(res.stdout)
+    assert out["steps"] == 20 and out["unit"] == "it/s" and out["dtype"] == "f64" and out["higher_is_better"] is True
+    assert out["value"] == pytest.approx(1000.0 / out["ms_per_step"], rel=1e-6) and "c1" in out["metric"]
+    assert not {"cpu_baseline", "roofline", "steady_state", "median_of_5", "collective", "job", "ranks"} & set(out)
+    assert out["outputs"]["arrays"] == {"theta": [5, 2], "eta": [10, 4], "pr": [2, 4, 5]}
+    n, u, i, r, k, l = CONFIGS["c1"]
+    train = orc.synthetic_triples(n, u, i, r, seed=0)
+    want = orc.run_one_sampling(train, orc.child_seeds(0, 1)[0], k, l, 25)
+    for nm in ("theta", "eta", "pr"):
+        got = np.load(dump / f"{nm}.npy")
+        assert got.dtype == np.float64 and got.shape == want[nm].shape, nm
+        assert np.max(np.abs(got - want[nm])) <= 1e-9 * np.max(np.abs(want[nm])), nm
+
+
 def test_bench_gpus2_starts_its_own_ranks():
     """`python bench.py --gpus 2 --share-gpu --dist-backend gloo` with no launcher around it (VERDICT r1
     item 1c): the parent starts torch.distributed.run as a child, rank 0's line comes back, two ranks
     (two restarts) were timed.  Both ranks share GPU 0 here -- a rehearsal of the launch and collective
     plumbing, not a scaling measurement."""
     res = _run([sys.executable, "bench.py", "--gpus", "2", "--share-gpu", "--dist-backend", "gloo", "--steps", "20",
-                "--warmup", "5", "--config", "c2"])
+                "--warmup", "5", "--config", "c2", "--full"])
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
     out = _json_line(res.stdout)
     assert out["n_gpus"] == 2 and out["collective"] == {"backend": "gloo", "world_size": 2}
@@ -169,7 +192,7 @@ def test_bench_under_the_drivers_launcher_times_the_cpu_side_before_touching_the
         port = sock.getsockname()[1]
     res = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr",
                 "127.0.0.1", "--master-port", str(port), "bench.py", "--gpus", "2", "--share-gpu", "--dist-backend",
-                "gloo", "--steps", "20", "--warmup", "5", "--config", "c2", "--steady-steps", "100", "--cpu-iters", "1"])
+                "gloo", "--steps", "20", "--warmup", "5", "--config", "c2", "--full", "--steady-steps", "100", "--cpu-iters", "1"])
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
     out = _json_line(res.stdout)
     assert out["n_gpus"] == 2 and out["cpu_baseline"]["cores"] == 2 and "roofline" in out and "job" in out
