@@ -169,6 +169,28 @@ int mmsbm_hip_predict_begin(mmsbm_hip_ctx *ctx, int64_t n_rows, const int32_t *u
 int mmsbm_hip_predict_add(mmsbm_hip_ctx *ctx, double stats[6]);
 int mmsbm_hip_predict_finish(mmsbm_hip_ctx *ctx, double *mean_dist, double stats[6]);
 
+/* ---- top-N recommendation: the best n items per user (mmsbm_amd/csrc/recommend.hpp) ---------------------------- */
+/* A session shaped like predict's:
+ *   begin  rating_weights: R finite doubles w (the reference's `self.ratings` for the expected rating, one-hot for
+ *          P(rating = r)); exclude_train != 0 leaves out the items a user has in the training triples (a pair that
+ *          occurs several times counts once).  Closes any earlier recommend session; a predict session is untouched.
+ *   add    folds the SELECTED slot's current parameters into the session (the slot itself is left unchanged);
+ *   query  for n_users external user ids: score_w(u, i) = (1/S) sum_s sum_r w_r P_s(r | u, i) over the S added slots,
+ *          every training item i a candidate, and per user the n best -- score descending, equal scores (exact
+ *          fp64 equality) by ascending item id.  items / scores: n_users x n, row b holding counts[b] entries followed
+ *          by item -1 / score -inf (scores and counts may be NULL).  A user's scores depend on that user and the items
+ *          only: bitwise the same whatever the other users of the call and from call to call.  May be repeated;
+ *   end    releases the session's device memory.
+ * mmsbm_hip_get_option(ctx, "recommend_ms") reads the device time of the last query's kernels (HIP events).
+ * 1 <= n <= MMSBM_HIP_RECOMMEND_MAX_N (larger n: MMSBM_E_UNSUPPORTED).  MMSBM_E_TOOLARGE where the device memory
+ * the session needs is not free.  These launches are not part of an EM iteration (mmsbm_hip_kernel_count). */
+#define MMSBM_HIP_RECOMMEND_MAX_N 1024
+int mmsbm_hip_recommend_begin(mmsbm_hip_ctx *ctx, const double *rating_weights, int exclude_train);
+int mmsbm_hip_recommend_add(mmsbm_hip_ctx *ctx);
+int mmsbm_hip_recommend_query(mmsbm_hip_ctx *ctx, int64_t n_users, const int32_t *users, int32_t n, int32_t *items,
+                              double *scores, int32_t *counts);
+int mmsbm_hip_recommend_end(mmsbm_hip_ctx *ctx);
+
 /* ---- measurement ------------------------------------------------------------------ */
 /* Runs n_iters EM iterations bracketed by HIP events on the context's stream; returns
  * the elapsed device time of the whole region in milliseconds (synchronises). */

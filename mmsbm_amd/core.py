@@ -305,6 +305,34 @@ class HipEM:
                   _p(out, C.c_double) if want_matrix else None, _p(st, C.c_double))
         return out, st
 
+    # -- top-N recommendation on the device (include/mmsbm_hip.h: mmsbm_hip_recommend_*) --------------
+    MAX_RECOMMEND = 1024
+
+    def recommend_begin(self, rating_weights, exclude_seen=True):
+        """Open a recommend session: score = sum_r w_r P(r | u, i), averaged over the slots added to it."""
+        w = _f64(rating_weights)
+        if w.shape != (self.n_ratings,):
+            raise ValueError(f"rating_weights has shape {w.shape}, expected ({self.n_ratings},)")
+        _lib.call("mmsbm_hip_recommend_begin", self._h, _p(w, C.c_double), int(bool(exclude_seen)))
+
+    def recommend_add(self):
+        """Fold the selected slot's current parameters into the session (the slot is left unchanged)."""
+        _lib.call("mmsbm_hip_recommend_add", self._h)
+
+    def recommend_query(self, users, n):
+        """(items (M,n) int32 padded with -1, scores (M,n) padded with -inf, counts (M,)) for encoded user ids."""
+        u = _i32(users)
+        n = int(n)
+        items = np.empty((len(u), max(n, 0)), dtype=np.int32)
+        scores = np.empty((len(u), max(n, 0)), dtype=np.float64)
+        counts = np.empty(len(u), dtype=np.int32)
+        _lib.call("mmsbm_hip_recommend_query", self._h, len(u), _p(u, C.c_int32), n, _p(items, C.c_int32),
+                  _p(scores, C.c_double), _p(counts, C.c_int32))
+        return items, scores, counts
+
+    def recommend_end(self):
+        _lib.call("mmsbm_hip_recommend_end", self._h)
+
     # -- measurement -------------------------------------------------------------------------
     def time_iterations(self, n_iters):
         """Device milliseconds for n_iters EM iterations (HIP events on the context stream)."""

@@ -220,6 +220,13 @@ struct mmsbm_hip_ctx {
   DevBuf<double> ps_sum, ps_w, ps_part;
   int64_t ps_rows = -1;  // -1: no session open
   int ps_added = 0;
+  // recommend session (mmsbm_hip_recommend_begin .. end; recommend.hpp): the slots' folded factors, external sides
+  DevBuf<double> rc_x, rc_y, rc_w;          // [slot][U][rank], [slot][I][rank], the R rating weights
+  DevBuf<int32_t> rc_seen_off, rc_seen;     // per external user: its distinct training items, ascending (exclude_train)
+  int rc_slots = -1;                        // slots added; -1: no session open
+  int rc_rank = 0;
+  bool rc_excl = false;
+  float rc_last_ms = 0.f;                   // device time of the last query's kernels (option "recommend_ms")
   int cur = 0;
   std::vector<char> have;  // per slot: set_params has been called
   bool graph_mode = false;  // replay a captured two-iteration hipGraph instead of eager launches

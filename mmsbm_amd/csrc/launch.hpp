@@ -35,6 +35,13 @@ int rows_launch(mmsbm_hip_ctx *c, int mode, const int32_t *pu, const int32_t *pi
 int score_rows_launch(mmsbm_hip_ctx *c, bool finish);  // the per-row scoring kernels; returns the number of workgroups
 int score_stats_count();
 
+// tu_recommend.hip -- top-N recommendation (recommend.hpp): the session of mmsbm_hip_recommend_*, arguments checked
+void recommend_begin(mmsbm_hip_ctx *c, const double *weights, int exclude_train);
+void recommend_add(mmsbm_hip_ctx *c);  // the selected slot (the caller holds a OneSlot)
+void recommend_query(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, int n, int32_t *items, double *scores,
+                     int32_t *counts);
+void recommend_end(mmsbm_hip_ctx *c);
+
 // dispatchers (mmsbm_hip.hip): the form the context's shape and options select
 void stage_dense(mmsbm_hip_ctx *c);
 void stage_matvec_a(mmsbm_hip_ctx *c, int slot, int a_slot, bool grid = false);

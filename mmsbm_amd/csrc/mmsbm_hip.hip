@@ -1267,6 +1267,53 @@ int mmsbm_hip_predict_finish(mmsbm_hip_ctx *ctx, double *mean_dist, double stats
   });
 }
 
+int mmsbm_hip_recommend_begin(mmsbm_hip_ctx *ctx, const double *rating_weights, int exclude_train) {
+  return guarded([&] {
+    if (!ctx || !rating_weights) throw std::invalid_argument("null argument");
+    for (int r = 0; r < ctx->n_ratings; ++r)  // (a NaN score has no place in the order; +-inf is not a score)
+      if (!std::isfinite(rating_weights[r]))
+        throw std::invalid_argument("recommend: rating weight " + std::to_string(r) + " is not finite");
+    recommend_begin(ctx, rating_weights, exclude_train);
+  });
+}
+
+int mmsbm_hip_recommend_add(mmsbm_hip_ctx *ctx) {
+  return guarded([&] {
+    require_params(ctx);
+    if (ctx->rc_slots < 0) throw std::invalid_argument("recommend_begin has not been called");
+    OneSlot one(ctx);
+    recommend_add(ctx);
+  });
+}
+
+int mmsbm_hip_recommend_query(mmsbm_hip_ctx *ctx, int64_t n_users, const int32_t *users, int32_t n, int32_t *items,
+                              double *scores, int32_t *counts) {
+  return guarded([&] {
+    if (!ctx) throw std::invalid_argument("null context");
+    if (ctx->rc_slots < 0) throw std::invalid_argument("recommend_begin has not been called");
+    if (ctx->rc_slots == 0) throw std::invalid_argument("recommend_query before any recommend_add");
+    if (n_users < 0) throw std::invalid_argument("negative n_users");
+    if (n < 1) throw std::invalid_argument("recommend: n must be at least 1");
+    if (n > MMSBM_HIP_RECOMMEND_MAX_N)
+      throw ApiError(MMSBM_E_UNSUPPORTED, "recommend: n = " + std::to_string(n) + " is beyond the " +
+                                              std::to_string(MMSBM_HIP_RECOMMEND_MAX_N) + " items a query returns at most");
+    if (n_users > 0 && (!users || !items)) throw std::invalid_argument("null argument");
+    for (int64_t m = 0; m < n_users; ++m)
+      if (users[m] < 0 || users[m] >= ctx->ext_users)
+        throw std::invalid_argument("recommend: user id out of range at row " + std::to_string(m));
+    recommend_query(ctx, n_users, users, n, items, scores, counts);
+  });
+}
+
+int mmsbm_hip_recommend_end(mmsbm_hip_ctx *ctx) {
+  return guarded([&] {
+    if (!ctx) throw std::invalid_argument("null context");
+    use_device(ctx);
+    HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    recommend_end(ctx);
+  });
+}
+
 int mmsbm_hip_time_iterations(mmsbm_hip_ctx *ctx, int n_iters, float *elapsed_ms) {
   return guarded([&] {
     require_all_params(ctx);
@@ -1443,6 +1490,7 @@ int mmsbm_hip_get_option(const mmsbm_hip_ctx *ctx, const char *name, double *val
     else if (key == "predict_fast") *value = ctx->predict_fast;
     else if (key == "fused") *value = ctx->fused;
     else if (key == "nt_out") *value = nt_on(ctx);
+    else if (key == "recommend_ms") *value = ctx->rc_last_ms;  // read-only: device time of the last recommend_query
     else if (key == "launches") *value = use_fused(ctx) ? 2 : 4;  // read-only: launches per iteration at the current slot count
     else if (key == "wide") *value = ctx->wide;
     else if (key == "lik_fast") *value = ctx->lik_mode;

@@ -1,0 +1,255 @@
+// recommend.hpp -- top-N item recommendation (mmsbm_hip_recommend_*): the expected score of every (user, item) pair
+// of a request and the N best items per user, on the device.
+//
+//   score_w(u, i) = (1/S) sum_s sum_r w_r P_s(r | u, i) = (1/S) sum_s theta_s[u,:] W_s eta_s[i,:]^T,
+//   W_s[k,l]      = sum_r w_r p_s[k,l,r]                                           (K x L, external sides)
+//
+// Per restart slot a small prologue folds W_s into the side with the larger group count, so that the product has
+// rank min(K, L): x_s = theta_s (U x K) and y_s = eta_s W_s^T (I x K) when K <= L, else x_s = theta_s W_s (U x L) and
+// y_s = eta_s.  The slots' factors are concatenated along the rank, f = s * rank + j, and a score is ONE fma chain
+// over f in ascending order, divided by S at the end -- the same operations in the same order whatever the tile, the
+// launch shape or the other users of the request (bitwise request independence; identical eta rows tie exactly).
+// Everything is stated in EXTERNAL terms (user side = the caller's users, whichever internal side holds them), so a
+// swapped context gives bitwise the same scores as an unswapped one.
+//
+// Then, per batch of users:
+//   rec_score_kernel    the score tile (128 users x 128 items per workgroup, 8 x 8 fp64 FMA per thread on the
+//                       vector ALU: users 8 in a row, items 16 apart; rank staged through LDS 16 at a time) into a
+//                       batch buffer [users][items];
+//   rec_exclude_kernel  -inf over the items each user has in the training triples (exclude_seen);
+//   rec_select_kernel   one wave per (user, item range): a running candidate list in LDS, filtered against the current
+//                       N-th best, compacted by ballot (no atomics) and re-sorted (bitonic) when it fills; the same
+//                       kernel then merges the ranges' lists when the items were split across waves.
+// Order: score descending, equal scores (exact fp64 equality) by ascending item id -- a strict total order, so the
+// top N is unique and the split into ranges cannot change it.  N is bounded by kRecMaxN (larger N: the C ABI answers
+// MMSBM_E_UNSUPPORTED); the candidate list holds the next power of two >= N + 256 entries (<= 2,048).
+#pragma once
+
+namespace {
+
+constexpr int kRecMaxN = MMSBM_HIP_RECOMMEND_MAX_N;  // largest N a query may ask for (include/mmsbm_hip.h)
+constexpr int kRecTile = 128;       // users x items of one score workgroup
+constexpr int kRecTm = 8;           // outputs per thread along each side (16 x 16 threads)
+constexpr int kRecKc = 16;          // rank entries staged in LDS per step
+constexpr int kRecLdsRow = kRecTile + 2;  // (padded LDS row: fewer bank conflicts, 16-byte aligned rows)
+constexpr int kRecWave = 64;        // rec_select_kernel: one wave per workgroup
+constexpr int kRecPerLane = 4;      // elements a lane examines per round
+
+// W[k * L + l] = sum_r w[r] p[r][k, l] in external (k, l); p of one slot in the device layout [R][kp][lp], internal
+// (k, l) = external (k, l) or (l, k) when swapped: element (k, l) at p + r * rs + k * ks + l * ls.
+__global__ __launch_bounds__(kBlock) void rec_w_kernel(const double *__restrict__ p, const double *__restrict__ w,
+                                                       double *__restrict__ wout, int K, int L, int R, size_t rs,
+                                                       int ks, int ls) {
+  const int e = blockIdx.x * kBlock + threadIdx.x;
+  if (e >= K * L) return;
+  const int k = e / L, l = e % L;
+  double acc = 0.0;
+  for (int r = 0; r < R; ++r) acc = fma(w[r], p[static_cast<size_t>(r) * rs + static_cast<size_t>(k) * ks + static_cast<size_t>(l) * ls], acc);
+  wout[e] = acc;
+}
+
+// out[row * rank + j] = src(row, j)                                (m == nullptr)
+//                     = sum_t src(row, t) m[t * mt + j * mj]       (t < d, ascending)
+__global__ __launch_bounds__(kBlock) void rec_fold_kernel(RowTab src, int d, const double *__restrict__ m, int mt,
+                                                          int mj, double *__restrict__ out, int rows, int rank) {
+  const size_t e = static_cast<size_t>(blockIdx.x) * kBlock + threadIdx.x;
+  if (e >= static_cast<size_t>(rows) * rank) return;
+  const size_t row = e / rank;
+  const int j = static_cast<int>(e % rank);
+  if (!m) {
+    out[e] = *rowtab_ptr(src, row, j);
+    return;
+  }
+  double acc = 0.0;
+  for (int t = 0; t < d; ++t) acc = fma(*rowtab_ptr(src, row, t), m[static_cast<size_t>(t) * mt + static_cast<size_t>(j) * mj], acc);
+  out[e] = acc;
+}
+
+// scores[b * ld + i] = (1/S) sum_f x[users[b], f] y[i, f] for b < nb, i < ni; x / y: `slots` tables [rows][rank]
+// one after the other (x: xs doubles apart, y: ys).  grid (item tiles, user tiles).
+__global__ __launch_bounds__(kBlock) void rec_score_kernel(const double *__restrict__ x, size_t xs,
+                                                           const double *__restrict__ y, size_t ys,
+                                                           const int32_t *__restrict__ users, int nb, int ni,
+                                                           int rank, int slots, double *__restrict__ scores, size_t ld) {
+  __shared__ double xt[kRecKc][kRecLdsRow];
+  __shared__ double yt[kRecKc][kRecLdsRow];
+  const int tid = threadIdx.x, tx = tid % 16, ty = tid / 16;
+  const int i0 = blockIdx.x * kRecTile, b0 = blockIdx.y * kRecTile;
+  double acc[kRecTm][kRecTm];
+#pragma unroll
+  for (int a = 0; a < kRecTm; ++a)
+#pragma unroll
+    for (int c = 0; c < kRecTm; ++c) acc[a][c] = 0.0;
+  // the rows this thread stages: (kk, r) = (e % 16, e / 16) for e = tid + 256 m
+  const int F = rank * slots;
+  for (int f0 = 0; f0 < F; f0 += kRecKc) {
+    const int kc = min(kRecKc, F - f0);
+#pragma unroll
+    for (int m = 0; m < kRecTile * kRecKc / kBlock; ++m) {
+      const int e = tid + kBlock * m, kk = e % kRecKc, r = e / kRecKc;
+      const int f = f0 + kk, s = f / rank, j = f - s * rank;
+      double xv = 0.0, yv = 0.0;
+      if (f < F) {
+        if (b0 + r < nb) xv = x[static_cast<size_t>(s) * xs + static_cast<size_t>(users[b0 + r]) * rank + j];
+        if (i0 + r < ni) yv = y[static_cast<size_t>(s) * ys + static_cast<size_t>(i0 + r) * rank + j];
+      }
+      xt[kk][r] = xv;
+      yt[kk][r] = yv;
+    }
+    __syncthreads();
+    for (int kk = 0; kk < kc; ++kk) {
+      double xa[kRecTm], yc[kRecTm];
+#pragma unroll
+      for (int a = 0; a < kRecTm; ++a) xa[a] = xt[kk][ty * kRecTm + a];
+#pragma unroll
+      for (int c = 0; c < kRecTm; ++c) yc[c] = yt[kk][tx + 16 * c];  // (neighbouring lanes: neighbouring items)
+#pragma unroll
+      for (int a = 0; a < kRecTm; ++a)
+#pragma unroll
+        for (int c = 0; c < kRecTm; ++c) acc[a][c] = fma(xa[a], yc[c], acc[a][c]);
+    }
+    __syncthreads();
+  }
+  const double n_slots = static_cast<double>(slots);
+#pragma unroll
+  for (int a = 0; a < kRecTm; ++a) {
+    const int b = b0 + ty * kRecTm + a;
+    if (b >= nb) continue;
+    double *row = scores + static_cast<size_t>(b) * ld;
+#pragma unroll
+    for (int c = 0; c < kRecTm; ++c) {
+      const int i = i0 + tx + 16 * c;
+      if (i < ni) row[i] = acc[a][c] / n_slots;
+    }
+  }
+}
+
+// scores[b * ld + item] = -inf for every item user users[b] has in the training triples (one workgroup per user)
+__global__ __launch_bounds__(kBlock) void rec_exclude_kernel(const int32_t *__restrict__ users,
+                                                             const int32_t *__restrict__ seen_off,
+                                                             const int32_t *__restrict__ seen_item,
+                                                             double *__restrict__ scores, size_t ld) {
+  const int b = blockIdx.x;
+  const int u = users[b];
+  double *row = scores + static_cast<size_t>(b) * ld;
+  for (int e = seen_off[u] + threadIdx.x; e < seen_off[u + 1]; e += kBlock) row[seen_item[e]] = -INFINITY;
+}
+
+__device__ __forceinline__ bool rec_better(double sa, int ia, double sb, int ib) {
+  return sa > sb || (sa == sb && ia < ib);
+}
+
+// Sorts the first `cnt` entries of (ks, ki) best first (entries up to the next power of two are padded with the
+// sentinel (-inf, INT_MAX), worse than any candidate).  One wave; cap = room of the arrays (a power of two).
+__device__ void rec_sort(double *ks, int *ki, int cnt) {
+  int sz = 2;
+  while (sz < cnt) sz <<= 1;
+  for (int t = cnt + threadIdx.x; t < sz; t += kRecWave) { ks[t] = -INFINITY; ki[t] = INT_MAX; }
+  __syncthreads();
+  for (int k = 2; k <= sz; k <<= 1) {
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      for (int t = threadIdx.x; t < sz / 2; t += kRecWave) {
+        const int i = (t / j) * 2 * j + (t % j), q = i + j;
+        const double si = ks[i], sq = ks[q];
+        const int ii = ki[i], iq = ki[q];
+        const bool up = (i & k) == 0;  // this half: best first
+        if (up ? rec_better(sq, iq, si, ii) : rec_better(si, ii, sq, iq)) {
+          ks[i] = sq; ki[i] = iq; ks[q] = si; ki[q] = ii;
+        }
+      }
+      __syncthreads();
+    }
+  }
+}
+
+// The N best of one (user, range).  One wave per workgroup; grid (parts, users).
+// !MERGE: the candidates are scores[b * ld + i] for i in the part's slice [part * per, min(ni, part * per + per)),
+//         excluded items (-inf) are never candidates.
+// MERGE:  the candidates are the lists of `in_parts` earlier parts: in_s / in_i [(b * in_parts + p) * n + k] for
+//         k < in_n[b * in_parts + p].
+// Output: out_s / out_i [(b * gridDim.x + part) * n + k], k < out_n[b * gridDim.x + part].
+template <bool MERGE>
+__global__ __launch_bounds__(kRecWave) void rec_select_kernel(const double *__restrict__ scores, size_t ld, int ni,
+                                                              int per, const double *__restrict__ in_s,
+                                                              const int32_t *__restrict__ in_i,
+                                                              const int32_t *__restrict__ in_n, int in_parts, int n,
+                                                              int cap, double *__restrict__ out_s,
+                                                              int32_t *__restrict__ out_i, int32_t *__restrict__ out_n) {
+  extern __shared__ double rec_lds[];
+  double *ks = rec_lds;
+  int *ki = reinterpret_cast<int *>(rec_lds + cap);
+  const int lane = threadIdx.x, part = blockIdx.x, b = blockIdx.y;
+  int lo, hi;
+  if (MERGE) {
+    lo = 0;
+    hi = in_parts * n;
+  } else {
+    lo = part * per;
+    hi = min(ni, lo + per);
+  }
+  int cnt = 0;
+  bool have_thr = false;
+  double thr_s = 0.0;
+  int thr_i = 0;
+  const double *row = MERGE ? nullptr : scores + static_cast<size_t>(b) * ld;
+  for (int base = lo; base < hi; base += kRecWave * kRecPerLane) {
+    if (cnt + kRecWave * kRecPerLane > cap) {  // no room for a whole round: keep the N best, raise the threshold
+      rec_sort(ks, ki, cnt);
+      cnt = min(cnt, n);
+      if (cnt == n) {
+        thr_s = ks[n - 1];
+        thr_i = ki[n - 1];
+        have_thr = true;
+      }
+      __syncthreads();
+    }
+    double sv[kRecPerLane];
+    int iv[kRecPerLane];
+    bool ok[kRecPerLane];
+#pragma unroll
+    for (int e = 0; e < kRecPerLane; ++e) {
+      const int pos = base + e * kRecWave + lane;
+      ok[e] = false;
+      sv[e] = -INFINITY;
+      iv[e] = INT_MAX;
+      if (pos < hi) {
+        if (MERGE) {
+          const int p = pos / n, k = pos - p * n;
+          const size_t at = static_cast<size_t>(b) * in_parts + p;
+          if (k < in_n[at]) {
+            sv[e] = in_s[at * n + k];
+            iv[e] = in_i[at * n + k];
+            ok[e] = true;
+          }
+        } else {
+          sv[e] = row[pos];
+          iv[e] = pos;
+          ok[e] = sv[e] != -INFINITY;
+        }
+      }
+    }
+#pragma unroll
+    for (int e = 0; e < kRecPerLane; ++e) {
+      const bool q = ok[e] && (!have_thr || rec_better(sv[e], iv[e], thr_s, thr_i));
+      const uint64_t mask = __ballot(q);
+      const uint64_t below = lane == 0 ? 0 : (mask & ((~uint64_t(0)) >> (64 - lane)));
+      if (q) {
+        const int at = cnt + __popcll(below);
+        ks[at] = sv[e];
+        ki[at] = iv[e];
+      }
+      cnt += __popcll(mask);
+    }
+    __syncthreads();
+  }
+  rec_sort(ks, ki, cnt);
+  cnt = min(cnt, n);
+  const size_t o = (static_cast<size_t>(b) * gridDim.x + part);
+  for (int k = lane; k < cnt; k += kRecWave) {
+    out_s[o * n + k] = ks[k];
+    out_i[o * n + k] = ki[k];
+  }
+  if (lane == 0) out_n[o] = cnt;
+}
+
+}  // namespace

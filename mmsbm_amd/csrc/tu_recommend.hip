@@ -1,0 +1,220 @@
+// tu_recommend.hip -- translation unit of top-N recommendation (recommend.hpp): the session's host side -- the
+// training items of every user, the per-slot prologue, the batches of a query and the choice of the item split
+#include "prelude.hpp"
+#include "recommend.hpp"
+
+#include <climits>
+
+namespace mmsbm_hip_impl {
+
+namespace {
+
+constexpr size_t kRecBatchBytes = size_t(128) << 20;  // score buffer of one batch of users (stays in the 256 MB MALL)
+constexpr int kRecMinPerPart = 1024;                   // items a selecting wave gets at least
+
+void rec_require_mem(size_t bytes, const char *what) {
+  size_t free_b = 0, total_b = 0;
+  HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
+  if (bytes + (size_t(64) << 20) > free_b)
+    throw ApiError(MMSBM_E_TOOLARGE, std::string("recommend: ") + what + " needs " + std::to_string(bytes >> 20) +
+                                         " MB of device memory, " + std::to_string(free_b >> 20) + " MB free");
+}
+
+int rec_rank(const mmsbm_hip_ctx *c) { return std::min(c->ext_k, c->ext_l); }
+
+}  // namespace
+
+void recommend_begin(mmsbm_hip_ctx *c, const double *weights, int exclude_train) {
+  use_device(c);
+  c->rc_slots = -1;  // (from here on the previous session is gone)
+  c->rc_x.release();
+  c->rc_y.release();
+  c->rc_seen_off.release();
+  c->rc_seen.release();
+  hipStream_t s = c->stream;
+  c->rc_w.alloc(c->n_ratings);
+  HIP_CHECK(hipMemcpyAsync(c->rc_w.ptr, weights, sizeof(double) * c->n_ratings, hipMemcpyHostToDevice, s));
+  c->rc_excl = exclude_train != 0;
+  if (c->rc_excl) {
+    // every external user's distinct training items, ascending: from the id columns in their original order
+    const size_t n = static_cast<size_t>(c->n_obs);
+    std::vector<int32_t> ou(n), oi(n);
+    if (n > 0) {
+      HIP_CHECK(hipMemcpyAsync(ou.data(), c->orig_u.ptr, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s));
+      HIP_CHECK(hipMemcpyAsync(oi.data(), c->orig_i.ptr, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s));
+    }
+    HIP_CHECK(hipStreamSynchronize(s));
+    const std::vector<int32_t> &eu = c->swapped ? oi : ou, &ei = c->swapped ? ou : oi;  // (internal users = external items)
+    const int U = c->ext_users;
+    std::vector<int32_t> off(static_cast<size_t>(U) + 1, 0), item(n);
+    for (size_t m = 0; m < n; ++m) off[static_cast<size_t>(eu[m]) + 1]++;
+    for (int u = 0; u < U; ++u) off[u + 1] += off[u];
+    std::vector<int32_t> pos(off.begin(), off.end() - 1);
+    for (size_t m = 0; m < n; ++m) item[static_cast<size_t>(pos[eu[m]]++)] = ei[m];
+    int32_t w = 0;  // sort + drop duplicate pairs, in place
+    for (int u = 0; u < U; ++u) {
+      const int32_t a = off[u], b = off[u + 1];
+      std::sort(item.begin() + a, item.begin() + b);
+      off[u] = w;
+      for (int32_t e = a; e < b; ++e)
+        if (e == a || item[e] != item[e - 1]) item[w++] = item[e];
+    }
+    off[U] = w;
+    item.resize(static_cast<size_t>(w));
+    c->rc_seen_off.upload(off, s);
+    c->rc_seen.upload(item, s);
+    HIP_CHECK(hipStreamSynchronize(s));  // (host vectors are locals)
+  }
+  HIP_CHECK(hipStreamSynchronize(s));
+  c->rc_rank = rec_rank(c);
+  c->rc_slots = 0;
+}
+
+void recommend_add(mmsbm_hip_ctx *c) {  // the selected slot (the caller holds a OneSlot)
+  use_device(c);
+  const int U = c->ext_users, I = c->ext_items, K = c->ext_k, L = c->ext_l, R = c->n_ratings, rank = c->rc_rank;
+  const int S = c->rc_slots;
+  const size_t xs = static_cast<size_t>(U) * rank, ys = static_cast<size_t>(I) * rank;
+  rec_require_mem(((S + 1) * (xs + ys) + static_cast<size_t>(K) * L) * sizeof(double), "the slots' factors");
+  hipStream_t st = c->stream;
+  // grow the two tables by one slot (the earlier slots' factors are kept as they are)
+  DevBuf<double> nx, ny, w;
+  nx.alloc((S + 1) * xs);
+  ny.alloc((S + 1) * ys);
+  w.alloc(static_cast<size_t>(K) * L);
+  if (S > 0) {
+    HIP_CHECK(hipMemcpyAsync(nx.ptr, c->rc_x.ptr, sizeof(double) * S * xs, hipMemcpyDeviceToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(ny.ptr, c->rc_y.ptr, sizeof(double) * S * ys, hipMemcpyDeviceToDevice, st));
+  }
+  const int cur = c->cur, sl = c->sel;
+  // external (k, l) of the slot's p: internal (k, l), or (l, k) when the context is swapped
+  const int ks = c->swapped ? 1 : c->lp, ls = c->swapped ? c->lp : 1;
+  const size_t rs = static_cast<size_t>(c->kp) * c->lp;
+  LAUNCH(rec_w_kernel, static_cast<unsigned>((K * L + kBlock - 1) / kBlock), kBlock, 0, st, c->p[cur].at(sl),
+         c->rc_w.ptr, w.ptr, K, L, R, rs, ks, ls);
+  // the caller's users / items: internal users / items, or the other way round when swapped
+  const RowTab th = theta_tab(c, cur), et = plain_tab(c->eta[cur].at(sl), c->lp);
+  const RowTab ut = c->swapped ? et : th, it = c->swapped ? th : et;
+  auto fold = [&](const RowTab &src, int d, const double *m, int mt, int mj, double *out, int rows) {
+    const size_t e = static_cast<size_t>(rows) * rank;
+    if (e == 0) return;
+    LAUNCH(rec_fold_kernel, static_cast<unsigned>((e + kBlock - 1) / kBlock), kBlock, 0, st, src, d, m, mt, mj, out,
+           rows, rank);
+  };
+  double *xo = nx.ptr + S * xs, *yo = ny.ptr + S * ys;
+  if (K <= L) {  // x = theta, y = eta W^T: y[i, k] = sum_l eta[i, l] W[k, l]
+    fold(ut, K, nullptr, 0, 0, xo, U);
+    fold(it, L, w.ptr, 1, L, yo, I);
+  } else {       // x = theta W: x[u, l] = sum_k theta[u, k] W[k, l], y = eta
+    fold(ut, K, w.ptr, L, 1, xo, U);
+    fold(it, L, nullptr, 0, 0, yo, I);
+  }
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipStreamSynchronize(st));
+  std::swap(c->rc_x.ptr, nx.ptr); std::swap(c->rc_x.count, nx.count);
+  std::swap(c->rc_y.ptr, ny.ptr); std::swap(c->rc_y.count, ny.count);
+  c->rc_slots = S + 1;
+}
+
+void recommend_query(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, int n, int32_t *items, double *scores,
+                     int32_t *counts) {
+  use_device(c);
+  for (int64_t b = 0; b < n_users; ++b) {
+    if (counts) counts[b] = 0;
+    for (int k = 0; k < n; ++k) {
+      items[static_cast<size_t>(b) * n + k] = -1;
+      if (scores) scores[static_cast<size_t>(b) * n + k] = -INFINITY;
+    }
+  }
+  if (n_users == 0) return;
+  const int I = c->ext_items, rank = c->rc_rank, S = c->rc_slots;
+  hipStream_t st = c->stream;
+  // users per batch: a score buffer of ~128 MB, whole 128-user tiles where that allows
+  int64_t bu = std::max<int64_t>(1, static_cast<int64_t>(kRecBatchBytes / (static_cast<size_t>(I) * sizeof(double))));
+  bu = std::min<int64_t>(bu, 32768);
+  if (bu >= kRecTile) bu = bu / kRecTile * kRecTile;
+  bu = std::min(bu, n_users);
+  // items split across waves until about 32 selecting waves per CU are in flight (the selection waits on its loads;
+  // few users: a single user over 100k items)
+  const int64_t target = 32LL * c->n_cus;
+  int parts = 1;
+  if (bu < target) parts = static_cast<int>(std::min<int64_t>((target + bu - 1) / bu, (I + kRecMinPerPart - 1) / kRecMinPerPart));
+  parts = std::max(parts, 1);
+  const int per = (I + parts - 1) / parts;
+  parts = I > 0 ? (I + per - 1) / per : 1;
+  int cap = 1;
+  while (cap < n + kRecWave * kRecPerLane) cap <<= 1;
+  const size_t lds = static_cast<size_t>(cap) * (sizeof(double) + sizeof(int32_t));
+  const size_t cand = parts > 1 ? static_cast<size_t>(bu) * parts * n : 0;
+  const size_t outs = static_cast<size_t>(n_users) * n;
+  rec_require_mem(static_cast<size_t>(bu) * I * sizeof(double) + cand * 12 + outs * 12 + static_cast<size_t>(n_users) * 8,
+                  "a batch of users");
+  DevBuf<int32_t> du, ci, cn, oi, on;
+  DevBuf<double> sc, cs, os;
+  du.alloc(n_users);
+  sc.alloc(static_cast<size_t>(bu) * I);
+  if (parts > 1) {
+    cs.alloc(cand); ci.alloc(cand); cn.alloc(static_cast<size_t>(bu) * parts);
+  }
+  os.alloc(outs); oi.alloc(outs); on.alloc(n_users);  // every user's result stays on the device until the end
+  HIP_CHECK(hipMemcpyAsync(du.ptr, users, sizeof(int32_t) * n_users, hipMemcpyHostToDevice, st));
+  hipEvent_t e0, e1;  // device time of the query's kernels (option "recommend_ms")
+  HIP_CHECK(hipEventCreate(&e0));
+  HIP_CHECK(hipEventCreate(&e1));
+  HIP_CHECK(hipEventRecord(e0, st));
+  for (int64_t b0 = 0; b0 < n_users; b0 += bu) {  // (batches follow each other on the stream: no host wait in between)
+    const int nb = static_cast<int>(std::min(bu, n_users - b0));
+    const int32_t *ub = du.ptr + b0;
+    double *obs = os.ptr + b0 * n;
+    int32_t *obi = oi.ptr + b0 * n, *obn = on.ptr + b0;
+    if (I > 0) {
+      const dim3 g(static_cast<unsigned>((I + kRecTile - 1) / kRecTile), static_cast<unsigned>((nb + kRecTile - 1) / kRecTile));
+      LAUNCH(rec_score_kernel, g, kBlock, 0, st, c->rc_x.ptr, static_cast<size_t>(c->ext_users) * rank, c->rc_y.ptr,
+             static_cast<size_t>(I) * rank, ub, nb, I, rank, S, sc.ptr, static_cast<size_t>(I));
+      if (c->rc_excl)
+        LAUNCH(rec_exclude_kernel, nb, kBlock, 0, st, ub, c->rc_seen_off.ptr, c->rc_seen.ptr, sc.ptr, static_cast<size_t>(I));
+    }
+    if (parts > 1) {
+      LAUNCH(rec_select_kernel<false>, dim3(parts, nb), kRecWave, lds, st, sc.ptr, static_cast<size_t>(I), I, per,
+             nullptr, nullptr, nullptr, 0, n, cap, cs.ptr, ci.ptr, cn.ptr);
+      LAUNCH(rec_select_kernel<true>, dim3(1, nb), kRecWave, lds, st, nullptr, 0, I, 0, cs.ptr, ci.ptr, cn.ptr, parts,
+             n, cap, obs, obi, obn);
+    } else {
+      LAUNCH(rec_select_kernel<false>, dim3(1, nb), kRecWave, lds, st, sc.ptr, static_cast<size_t>(I), I, I, nullptr,
+             nullptr, nullptr, 0, n, cap, obs, obi, obn);
+    }
+    HIP_CHECK(hipGetLastError());
+  }
+  HIP_CHECK(hipEventRecord(e1, st));
+  std::vector<double> hs(outs);
+  std::vector<int32_t> hi(outs), hn(static_cast<size_t>(n_users));
+  HIP_CHECK(hipMemcpyAsync(hs.data(), os.ptr, sizeof(double) * outs, hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipMemcpyAsync(hi.data(), oi.ptr, sizeof(int32_t) * outs, hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipMemcpyAsync(hn.data(), on.ptr, sizeof(int32_t) * n_users, hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipStreamSynchronize(st));
+  float ms = 0.f;
+  HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
+  c->rc_last_ms = ms;
+  (void)hipEventDestroy(e0);
+  (void)hipEventDestroy(e1);
+  for (int64_t b = 0; b < n_users; ++b) {
+    const size_t o = static_cast<size_t>(b) * n;
+    const int cnt = hn[static_cast<size_t>(b)];
+    if (counts) counts[b] = cnt;
+    for (int k = 0; k < cnt; ++k) {
+      items[o + k] = hi[o + k];
+      if (scores) scores[o + k] = hs[o + k];
+    }
+  }
+}
+
+void recommend_end(mmsbm_hip_ctx *c) {
+  c->rc_slots = -1;
+  c->rc_x.release();
+  c->rc_y.release();
+  c->rc_w.release();
+  c->rc_seen_off.release();
+  c->rc_seen.release();
+}
+
+}  // namespace mmsbm_hip_impl

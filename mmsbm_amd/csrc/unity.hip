@@ -13,3 +13,4 @@
 #include "tu_fused.hip"
 #include "tu_once.hip"
 #include "tu_layout.hip"
+#include "tu_recommend.hip"

@@ -279,6 +279,85 @@ class MMSBM:
         self._raw_per_run = per_run                  # the six sums of each scored restart (restarts.predict_distributed)
         return matrix, raw, [ctx.final_stats(st) for st in per_run]
 
+    # ------------------------------------------------------------------ recommendation (not in the reference)
+    RECOMMEND_BATCH_ROWS = 1 << 22   # result rows (users x n) fetched from the device per query call
+
+    def recommend(self, users=None, n=10, exclude_seen=True, weights=None):
+        """The ``n`` best items per user, scored on the device: score(u, i) = sum_r weights[r] P(r | u, i), mean over
+        the restarts the model holds -- with the default weights (the rating values, ``self.ratings``) the expected
+        rating that ``predict`` + ``score`` use.  Candidates are all training items, without the user's own training
+        items when ``exclude_seen``.  Order: score descending, equal scores by ascending encoded item id.
+
+        Returns a DataFrame with columns ``users``, ``items``, ``score``, ``rank`` (1 = best), users in request order
+        (``users=None``: every training user), users and items as the encoder's labels (``theta`` / ``eta``'s index).  The model's stored predictions and
+        ``score()`` are left as they are."""
+        import pandas as pd
+        self._check_is_fitted()
+        if len(self._restart_ids) != self.sampling:
+            raise RuntimeError(
+                f"this model holds {len(self._restart_ids)} of its {self.sampling} restarts (restarts.fit_distributed "
+                "without gather=True): fit with gather=True to recommend from all of them")
+        if isinstance(n, (bool, np.bool_)) or not isinstance(n, (int, np.integer)) or n < 1:
+            raise ValueError(f"n must be a positive integer, got {n!r}")
+        n = int(n)
+        w = np.asarray(self.ratings if weights is None else weights, dtype=np.float64)
+        if w.shape != (len(self.ratings),):
+            raise ValueError(f"weights has shape {w.shape}, expected ({len(self.ratings)},): one per rating value")
+        if not np.isfinite(w).all():
+            raise ValueError(f"weights must be finite, got {w.tolist()}")
+        enc = self.data_handler
+        n_users = self.p + 1
+        if users is None:
+            ids = np.arange(n_users, dtype=np.int32)
+            labels = np.asarray(enc.user_labels(), dtype=object) if enc else ids
+        else:
+            labels = np.asarray(list(users), dtype=object)
+            if enc:
+                index = {lab: j for j, lab in enumerate(enc.user_labels())}
+                found = [index.get(str(x), -1) for x in labels]
+            else:
+                found = [int(x) if isinstance(x, (int, np.integer)) and 0 <= int(x) < n_users else -1 for x in labels]
+            ids = np.asarray(found, dtype=np.int32)
+            if (ids < 0).any():
+                missing = list(dict.fromkeys(labels[ids < 0].tolist()))
+                raise KeyError(f"users not in the training data: {missing}")
+            if enc:  # the encoder's labels, as with users=None (7 and "7" are one user; the frames join on "users")
+                labels = np.asarray(enc.user_labels(), dtype=object)[ids]
+        item_labels = np.asarray(enc.item_labels(), dtype=object) if enc else None
+
+        dev = self._device_list()[0]
+        ctx = self._ctx(dev)
+        # restarts whose final parameters still sit in this context's slots need no upload (as in _predict_runs)
+        resident = self._resident.get((dev, 0)) == list(self._restart_ids) and ctx.slots == len(self.results)
+        if not resident:
+            ctx.set_slots(1)
+            self._resident.pop((dev, 0), None)
+        parts = []
+        ctx.recommend_begin(w, exclude_seen)
+        try:
+            for j, a in enumerate(self.results):
+                if resident:
+                    ctx.select(j)
+                else:
+                    ctx.set_params(a["theta"], a["eta"], a["pr"])
+                ctx.recommend_add()
+            step = max(1, self.RECOMMEND_BATCH_ROWS // n)   # bounded host memory at a million users
+            for b in range(0, len(ids), step):
+                items, scores, counts = ctx.recommend_query(ids[b:b + step], n)
+                keep = np.arange(n)[None, :] < counts[:, None]
+                rows = np.repeat(np.arange(b, b + len(counts)), counts)
+                it = items[keep]
+                parts.append(pd.DataFrame({
+                    "users": labels[rows] if len(rows) else np.empty(0, dtype=object),
+                    "items": item_labels[it] if item_labels is not None else it.astype(np.int64),
+                    "score": scores[keep],
+                    "rank": np.nonzero(keep)[1].astype(np.int64) + 1}))
+        finally:
+            ctx.recommend_end()
+        if not parts:
+            return pd.DataFrame({"users": [], "items": [], "score": np.zeros(0), "rank": np.zeros(0, dtype=np.int64)})
+        return pd.concat(parts, ignore_index=True)
+
     def _keep_best_run(self, best, res=None):
         """theta / eta / pr / likelihood of restart ``best`` become the model's stored objects
         (src/mmsbm.py:303-311); ``res``: its result dict when it is not in self.results."""
