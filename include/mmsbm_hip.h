@@ -190,6 +190,31 @@ int mmsbm_hip_recommend_add(mmsbm_hip_ctx *ctx);
 int mmsbm_hip_recommend_query(mmsbm_hip_ctx *ctx, int64_t n_users, const int32_t *users, int32_t n, int32_t *items,
                               double *scores, int32_t *counts);
 int mmsbm_hip_recommend_end(mmsbm_hip_ctx *ctx);
+/* Like query, but the users are caller-given theta rows: theta [S][n_users][K] (external K) for the S added slots in
+ * add order, folded with each slot's p and the session's weights exactly as add folds the slot's own theta -- so a
+ * slot's own row gives bitwise the scores query gives for that user.  Excluded items come from a CSR list: user b
+ * leaves out seen_items[seen_offsets[b] .. seen_offsets[b + 1]) (item ids in [0, I), repeats allowed);
+ * seen_offsets NULL: nothing excluded (the session's exclude_train does not apply to these users). */
+int mmsbm_hip_recommend_query_theta(mmsbm_hip_ctx *ctx, int64_t n_users, const double *theta,
+                                    const int64_t *seen_offsets, const int32_t *seen_items, int32_t n,
+                                    int32_t *items, double *scores, int32_t *counts);
+
+/* ---- fold-in: theta of new users under the fitted eta and p (mmsbm_amd/csrc/fold_in.hpp) ----------------------- */
+/* The SELECTED slot's eta and p stay fixed; for new users 0 .. n_new-1, given their rows (user in [0, n_new), item in
+ * [0, I), rating in [0, R), external ids), n_iters times
+ *   theta'_u[k] = (1/d_u) sum_{rows j of u} theta_u[k] v_j[k] / max(theta_u . v_j, eps),
+ *   v_j[k] = sum_l p[k, l, r_j] eta[i_j, l]
+ * -- the theta half of the M-step.  theta0 (n_new x K) may be NULL: uniform 1/K.  tol > 0: a user stops after the
+ * first iteration whose max_k |theta' - theta| <= tol; tol <= 0: all n_iters.  theta: n_new x K out; iters (may be
+ * NULL): the iterations each user ran.  A user without rows gets theta0 and 0 iterations.  A user's rows are taken in
+ * request order; its theta depends on its own rows only (bitwise, whatever the other users of the call).  Touches no
+ * slot, no EM state and no predict / recommend session.  K <= MMSBM_HIP_FOLD_IN_MAX_K (larger: MMSBM_E_UNSUPPORTED);
+ * MMSBM_E_TOOLARGE where the device memory a batch of users needs is not free.
+ * mmsbm_hip_get_option(ctx, "fold_in_ms") reads the device time of the last fold-in's kernels (HIP events). */
+#define MMSBM_HIP_FOLD_IN_MAX_K 1024
+int mmsbm_hip_fold_in(mmsbm_hip_ctx *ctx, int64_t n_rows, const int32_t *user, const int32_t *item,
+                      const int32_t *rating, int32_t n_new, int32_t n_iters, double tol,
+                      const double *theta0, double *theta, int32_t *iters);
 
 /* ---- measurement ------------------------------------------------------------------ */
 /* Runs n_iters EM iterations bracketed by HIP events on the context's stream; returns

@@ -314,10 +314,12 @@ class HipEM:
         if w.shape != (self.n_ratings,):
             raise ValueError(f"rating_weights has shape {w.shape}, expected ({self.n_ratings},)")
         _lib.call("mmsbm_hip_recommend_begin", self._h, _p(w, C.c_double), int(bool(exclude_seen)))
+        self._rc_added = 0
 
     def recommend_add(self):
         """Fold the selected slot's current parameters into the session (the slot is left unchanged)."""
         _lib.call("mmsbm_hip_recommend_add", self._h)
+        self._rc_added += 1
 
     def recommend_query(self, users, n):
         """(items (M,n) int32 padded with -1, scores (M,n) padded with -inf, counts (M,)) for encoded user ids."""
@@ -330,8 +332,53 @@ class HipEM:
                   _p(scores, C.c_double), _p(counts, C.c_int32))
         return items, scores, counts
 
+    def recommend_query_theta(self, theta, n, seen=None):
+        """recommend_query for caller-given users: theta (S, M, K), one (M, K) block per added slot in add order.
+        seen: None (nothing excluded) or (offsets (M+1,) int64, items int32): user b leaves out
+        items[offsets[b]:offsets[b + 1]]."""
+        t = _f64(theta)
+        if t.ndim != 3 or t.shape[2] != self.k:
+            raise ValueError(f"theta has shape {t.shape}, expected (slots, users, {self.k})")
+        if t.shape[0] != getattr(self, "_rc_added", 0):
+            raise ValueError(f"theta holds {t.shape[0]} blocks, the session {getattr(self, '_rc_added', 0)} added slots")
+        m, n = t.shape[1], int(n)
+        off = it = None
+        if seen is not None:
+            off = np.ascontiguousarray(seen[0], dtype=np.int64)
+            it = _i32(seen[1])
+            if off.shape != (m + 1,):
+                raise ValueError(f"seen offsets have shape {off.shape}, expected ({m + 1},)")
+        items = np.empty((m, max(n, 0)), dtype=np.int32)
+        scores = np.empty((m, max(n, 0)), dtype=np.float64)
+        counts = np.empty(m, dtype=np.int32)
+        _lib.call("mmsbm_hip_recommend_query_theta", self._h, m, _p(t, C.c_double),
+                  None if off is None else _p(off, C.c_int64), None if it is None else _p(it, C.c_int32), n,
+                  _p(items, C.c_int32), _p(scores, C.c_double), _p(counts, C.c_int32))
+        return items, scores, counts
+
     def recommend_end(self):
         _lib.call("mmsbm_hip_recommend_end", self._h)
+
+    # -- fold-in of new users (include/mmsbm_hip.h: mmsbm_hip_fold_in) ---------------------------------
+    MAX_FOLD_IN_K = 1024
+
+    def fold_in(self, rows, n_new, iterations, tol=None, theta0=None):
+        """theta (n_new, K) of new users 0 .. n_new-1 under the selected slot's eta and p, and the iterations each ran
+        (n_new,).  rows: (N, 3) [new user, item, rating] (encoded item and rating ids).  tol None: all iterations;
+        theta0 None: uniform 1/K.  The slot is left unchanged."""
+        u, i, r = split_triples(rows)
+        n_new = int(n_new)
+        t0 = None
+        if theta0 is not None:
+            t0 = _f64(theta0)
+            if t0.shape != (n_new, self.k):
+                raise ValueError(f"theta0 has shape {t0.shape}, expected ({n_new}, {self.k})")
+        theta = np.empty((n_new, self.k), dtype=np.float64)
+        iters = np.empty(n_new, dtype=np.int32)
+        _lib.call("mmsbm_hip_fold_in", self._h, len(u), _p(u, C.c_int32), _p(i, C.c_int32), _p(r, C.c_int32),
+                  n_new, int(iterations), -1.0 if tol is None else float(tol),
+                  None if t0 is None else _p(t0, C.c_double), _p(theta, C.c_double), _p(iters, C.c_int32))
+        return theta, iters
 
     # -- measurement -------------------------------------------------------------------------
     def time_iterations(self, n_iters):

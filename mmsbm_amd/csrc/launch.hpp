@@ -40,7 +40,13 @@ void recommend_begin(mmsbm_hip_ctx *c, const double *weights, int exclude_train)
 void recommend_add(mmsbm_hip_ctx *c);  // the selected slot (the caller holds a OneSlot)
 void recommend_query(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, int n, int32_t *items, double *scores,
                      int32_t *counts);
+void recommend_query_theta(mmsbm_hip_ctx *c, int64_t n_users, const double *theta, const int64_t *seen_offsets,
+                           const int32_t *seen_items, int n, int32_t *items, double *scores, int32_t *counts);
 void recommend_end(mmsbm_hip_ctx *c);
+
+// tu_fold_in.hip -- fold new users into the selected slot's fitted eta and p (fold_in.hpp), arguments checked
+void fold_in(mmsbm_hip_ctx *c, int64_t n_rows, const int32_t *user, const int32_t *item, const int32_t *rating,
+             int32_t n_new, int32_t n_iters, double tol, const double *theta0, double *theta, int32_t *iters);
 
 // dispatchers (mmsbm_hip.hip): the form the context's shape and options select
 void stage_dense(mmsbm_hip_ctx *c);

@@ -1314,6 +1314,62 @@ int mmsbm_hip_recommend_end(mmsbm_hip_ctx *ctx) {
   });
 }
 
+int mmsbm_hip_recommend_query_theta(mmsbm_hip_ctx *ctx, int64_t n_users, const double *theta,
+                                    const int64_t *seen_offsets, const int32_t *seen_items, int32_t n,
+                                    int32_t *items, double *scores, int32_t *counts) {
+  return guarded([&] {
+    if (!ctx) throw std::invalid_argument("null context");
+    if (ctx->rc_slots < 0) throw std::invalid_argument("recommend_begin has not been called");
+    if (ctx->rc_slots == 0) throw std::invalid_argument("recommend_query_theta before any recommend_add");
+    if (n_users < 0) throw std::invalid_argument("negative n_users");
+    if (n < 1) throw std::invalid_argument("recommend: n must be at least 1");
+    if (n > MMSBM_HIP_RECOMMEND_MAX_N)
+      throw ApiError(MMSBM_E_UNSUPPORTED, "recommend: n = " + std::to_string(n) + " is beyond the " +
+                                              std::to_string(MMSBM_HIP_RECOMMEND_MAX_N) + " items a query returns at most");
+    if (n_users > 0 && (!theta || !items)) throw std::invalid_argument("null argument");
+    if (seen_offsets && n_users > 0) {
+      if (seen_offsets[0] != 0) throw std::invalid_argument("recommend: seen_offsets[0] must be 0");
+      for (int64_t b = 0; b < n_users; ++b)
+        if (seen_offsets[b + 1] < seen_offsets[b])
+          throw std::invalid_argument("recommend: seen_offsets decrease at user " + std::to_string(b));
+      const int64_t total = seen_offsets[n_users];
+      if (total > INT32_MAX) throw std::invalid_argument("recommend: more than 2^31 - 1 seen items");
+      if (total > 0 && !seen_items) throw std::invalid_argument("null argument");
+      for (int64_t e = 0; e < total; ++e)
+        if (seen_items[e] < 0 || seen_items[e] >= ctx->ext_items)
+          throw std::invalid_argument("recommend: seen item out of range at entry " + std::to_string(e));
+    }
+    recommend_query_theta(ctx, n_users, theta, seen_offsets, seen_items, n, items, scores, counts);
+  });
+}
+
+int mmsbm_hip_fold_in(mmsbm_hip_ctx *ctx, int64_t n_rows, const int32_t *user, const int32_t *item,
+                      const int32_t *rating, int32_t n_new, int32_t n_iters, double tol,
+                      const double *theta0, double *theta, int32_t *iters) {
+  return guarded([&] {
+    require_params(ctx);
+    if (n_rows < 0 || n_rows > INT32_MAX) throw std::invalid_argument("fold_in: n_rows outside [0, 2^31)");
+    if (n_new < 0) throw std::invalid_argument("fold_in: negative n_new");
+    if (n_iters < 0) throw std::invalid_argument("fold_in: negative n_iters");
+    if (ctx->ext_k > MMSBM_HIP_FOLD_IN_MAX_K)
+      throw ApiError(MMSBM_E_UNSUPPORTED, "fold_in: K = " + std::to_string(ctx->ext_k) + " is beyond the " +
+                                              std::to_string(MMSBM_HIP_FOLD_IN_MAX_K) + " groups it is built for");
+    if (n_rows > 0 && (!user || !item || !rating)) throw std::invalid_argument("null argument");
+    if (n_new > 0 && !theta) throw std::invalid_argument("null argument");
+    for (int64_t m = 0; m < n_rows; ++m) {
+      if (user[m] < 0 || user[m] >= n_new)
+        throw std::invalid_argument("fold_in: user id out of range at row " + std::to_string(m));
+      if (item[m] < 0 || item[m] >= ctx->ext_items)
+        throw std::invalid_argument("fold_in: item id out of range at row " + std::to_string(m));
+      if (rating[m] < 0 || rating[m] >= ctx->n_ratings)
+        throw std::invalid_argument("fold_in: rating id out of range at row " + std::to_string(m));
+    }
+    use_device(ctx);
+    OneSlot one(ctx);
+    fold_in(ctx, n_rows, user, item, rating, n_new, n_iters, tol, theta0, theta, iters);
+  });
+}
+
 int mmsbm_hip_time_iterations(mmsbm_hip_ctx *ctx, int n_iters, float *elapsed_ms) {
   return guarded([&] {
     require_all_params(ctx);
@@ -1491,6 +1547,7 @@ int mmsbm_hip_get_option(const mmsbm_hip_ctx *ctx, const char *name, double *val
     else if (key == "fused") *value = ctx->fused;
     else if (key == "nt_out") *value = nt_on(ctx);
     else if (key == "recommend_ms") *value = ctx->rc_last_ms;  // read-only: device time of the last recommend_query
+    else if (key == "fold_in_ms") *value = ctx->fold_last_ms;  // read-only: device time of the last fold_in
     else if (key == "launches") *value = use_fused(ctx) ? 2 : 4;  // read-only: launches per iteration at the current slot count
     else if (key == "wide") *value = ctx->wide;
     else if (key == "lik_fast") *value = ctx->lik_mode;

@@ -11,6 +11,7 @@
 //   tu_once.hip    once-per-run kernels: likelihood, prod_dist / predict, omegas, the random start
 //   tu_layout.hip  the layout's sorts on the device (rocPRIM)
 //   tu_recommend.hip  top-N recommendation (recommend.hpp)
+//   tu_fold_in.hip    fold new users into a fitted model (fold_in.hpp)
 // unity.hip includes them all into ONE unit: the diagnostic builds (-DMMSBM_STAMPS, -DMMSBM_ABLATE) and
 // scripts/kernel_resources.sh use it.
 #pragma once

@@ -29,6 +29,7 @@ void recommend_begin(mmsbm_hip_ctx *c, const double *weights, int exclude_train)
   c->rc_slots = -1;  // (from here on the previous session is gone)
   c->rc_x.release();
   c->rc_y.release();
+  c->rc_wk.release();
   c->rc_seen_off.release();
   c->rc_seen.release();
   hipStream_t s = c->stream;
@@ -75,23 +76,26 @@ void recommend_add(mmsbm_hip_ctx *c) {  // the selected slot (the caller holds a
   const int U = c->ext_users, I = c->ext_items, K = c->ext_k, L = c->ext_l, R = c->n_ratings, rank = c->rc_rank;
   const int S = c->rc_slots;
   const size_t xs = static_cast<size_t>(U) * rank, ys = static_cast<size_t>(I) * rank;
-  rec_require_mem(((S + 1) * (xs + ys) + static_cast<size_t>(K) * L) * sizeof(double), "the slots' factors");
+  rec_require_mem(((S + 1) * (xs + ys + static_cast<size_t>(K) * L)) * sizeof(double), "the slots' factors");
   hipStream_t st = c->stream;
   // grow the two tables by one slot (the earlier slots' factors are kept as they are)
-  DevBuf<double> nx, ny, w;
+  const size_t kl = static_cast<size_t>(K) * L;
+  DevBuf<double> nx, ny, nw;  // (W of every slot is kept: recommend_query_theta folds the caller's rows with it)
   nx.alloc((S + 1) * xs);
   ny.alloc((S + 1) * ys);
-  w.alloc(static_cast<size_t>(K) * L);
+  nw.alloc((S + 1) * kl);
   if (S > 0) {
     HIP_CHECK(hipMemcpyAsync(nx.ptr, c->rc_x.ptr, sizeof(double) * S * xs, hipMemcpyDeviceToDevice, st));
     HIP_CHECK(hipMemcpyAsync(ny.ptr, c->rc_y.ptr, sizeof(double) * S * ys, hipMemcpyDeviceToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(nw.ptr, c->rc_wk.ptr, sizeof(double) * S * kl, hipMemcpyDeviceToDevice, st));
   }
+  double *wo = nw.ptr + S * kl;
   const int cur = c->cur, sl = c->sel;
   // external (k, l) of the slot's p: internal (k, l), or (l, k) when the context is swapped
   const int ks = c->swapped ? 1 : c->lp, ls = c->swapped ? c->lp : 1;
   const size_t rs = static_cast<size_t>(c->kp) * c->lp;
   LAUNCH(rec_w_kernel, static_cast<unsigned>((K * L + kBlock - 1) / kBlock), kBlock, 0, st, c->p[cur].at(sl),
-         c->rc_w.ptr, w.ptr, K, L, R, rs, ks, ls);
+         c->rc_w.ptr, wo, K, L, R, rs, ks, ls);
   // the caller's users / items: internal users / items, or the other way round when swapped
   const RowTab th = theta_tab(c, cur), et = plain_tab(c->eta[cur].at(sl), c->lp);
   const RowTab ut = c->swapped ? et : th, it = c->swapped ? th : et;
@@ -104,21 +108,25 @@ void recommend_add(mmsbm_hip_ctx *c) {  // the selected slot (the caller holds a
   double *xo = nx.ptr + S * xs, *yo = ny.ptr + S * ys;
   if (K <= L) {  // x = theta, y = eta W^T: y[i, k] = sum_l eta[i, l] W[k, l]
     fold(ut, K, nullptr, 0, 0, xo, U);
-    fold(it, L, w.ptr, 1, L, yo, I);
+    fold(it, L, wo, 1, L, yo, I);
   } else {       // x = theta W: x[u, l] = sum_k theta[u, k] W[k, l], y = eta
-    fold(ut, K, w.ptr, L, 1, xo, U);
+    fold(ut, K, wo, L, 1, xo, U);
     fold(it, L, nullptr, 0, 0, yo, I);
   }
   HIP_CHECK(hipGetLastError());
   HIP_CHECK(hipStreamSynchronize(st));
   std::swap(c->rc_x.ptr, nx.ptr); std::swap(c->rc_x.count, nx.count);
   std::swap(c->rc_y.ptr, ny.ptr); std::swap(c->rc_y.count, ny.count);
+  std::swap(c->rc_wk.ptr, nw.ptr); std::swap(c->rc_wk.count, nw.count);
   c->rc_slots = S + 1;
 }
 
-void recommend_query(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, int n, int32_t *items, double *scores,
-                     int32_t *counts) {
-  use_device(c);
+namespace {
+
+// The batches of a query: users users[0 .. n_users) (host ids, rows of x: `slots` tables of xs doubles, [row][rank]),
+// scored against the session's items; seen_off / seen (device, indexed by those ids): the items left out, or null.
+void rec_run(mmsbm_hip_ctx *c, const double *x, size_t xs, int64_t n_users, const int32_t *users,
+             const int32_t *seen_off, const int32_t *seen, int n, int32_t *items, double *scores, int32_t *counts) {
   for (int64_t b = 0; b < n_users; ++b) {
     if (counts) counts[b] = 0;
     for (int k = 0; k < n; ++k) {
@@ -129,6 +137,7 @@ void recommend_query(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, in
   if (n_users == 0) return;
   const int I = c->ext_items, rank = c->rc_rank, S = c->rc_slots;
   hipStream_t st = c->stream;
+
   // users per batch: a score buffer of ~128 MB, whole 128-user tiles where that allows
   int64_t bu = std::max<int64_t>(1, static_cast<int64_t>(kRecBatchBytes / (static_cast<size_t>(I) * sizeof(double))));
   bu = std::min<int64_t>(bu, 32768);
@@ -169,10 +178,10 @@ void recommend_query(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, in
     int32_t *obi = oi.ptr + b0 * n, *obn = on.ptr + b0;
     if (I > 0) {
       const dim3 g(static_cast<unsigned>((I + kRecTile - 1) / kRecTile), static_cast<unsigned>((nb + kRecTile - 1) / kRecTile));
-      LAUNCH(rec_score_kernel, g, kBlock, 0, st, c->rc_x.ptr, static_cast<size_t>(c->ext_users) * rank, c->rc_y.ptr,
-             static_cast<size_t>(I) * rank, ub, nb, I, rank, S, sc.ptr, static_cast<size_t>(I));
-      if (c->rc_excl)
-        LAUNCH(rec_exclude_kernel, nb, kBlock, 0, st, ub, c->rc_seen_off.ptr, c->rc_seen.ptr, sc.ptr, static_cast<size_t>(I));
+      LAUNCH(rec_score_kernel, g, kBlock, 0, st, x, xs, c->rc_y.ptr, static_cast<size_t>(I) * rank, ub, nb, I, rank, S,
+             sc.ptr, static_cast<size_t>(I));
+      if (seen_off)
+        LAUNCH(rec_exclude_kernel, nb, kBlock, 0, st, ub, seen_off, seen, sc.ptr, static_cast<size_t>(I));
     }
     if (parts > 1) {
       LAUNCH(rec_select_kernel<false>, dim3(parts, nb), kRecWave, lds, st, sc.ptr, static_cast<size_t>(I), I, per,
@@ -206,6 +215,50 @@ void recommend_query(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, in
       if (scores) scores[o + k] = hs[o + k];
     }
   }
+}
+
+}  // namespace
+
+void recommend_query(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, int n, int32_t *items, double *scores,
+                     int32_t *counts) {
+  use_device(c);
+  rec_run(c, c->rc_x.ptr, static_cast<size_t>(c->ext_users) * c->rc_rank, n_users, users,
+          c->rc_excl ? c->rc_seen_off.ptr : nullptr, c->rc_seen.ptr, n, items, scores, counts);
+}
+
+void recommend_query_theta(mmsbm_hip_ctx *c, int64_t n_users, const double *theta, const int64_t *seen_offsets,
+                           const int32_t *seen_items, int n, int32_t *items, double *scores, int32_t *counts) {
+  use_device(c);
+  const int K = c->ext_k, L = c->ext_l, rank = c->rc_rank, S = c->rc_slots;
+  const size_t tk = static_cast<size_t>(n_users) * K, xs = static_cast<size_t>(n_users) * rank;
+  const int64_t n_seen = seen_offsets && n_users > 0 ? seen_offsets[n_users] : 0;
+  rec_require_mem(S * (tk + xs) * sizeof(double) + (static_cast<size_t>(n_users) + 1 + n_seen) * 4,
+                  "the caller's theta rows");
+  hipStream_t st = c->stream;
+  // every slot's rows folded exactly as recommend_add folds the slot's own theta: x = theta, or theta W when K > L
+  DevBuf<double> th, x;
+  DevBuf<int32_t> soff, sit;
+  th.alloc(S * tk);
+  x.alloc(S * xs);
+  if (S * tk > 0) HIP_CHECK(hipMemcpyAsync(th.ptr, theta, sizeof(double) * S * tk, hipMemcpyHostToDevice, st));
+  std::vector<int32_t> hid(static_cast<size_t>(n_users)), hoff;
+  for (int64_t b = 0; b < n_users; ++b) hid[static_cast<size_t>(b)] = static_cast<int32_t>(b);
+  if (seen_offsets) {
+    hoff.assign(seen_offsets, seen_offsets + n_users + 1);  // (checked: below 2^31)
+    soff.upload(hoff, st);
+    sit.alloc(static_cast<size_t>(n_seen));
+    if (n_seen > 0)
+      HIP_CHECK(hipMemcpyAsync(sit.ptr, seen_items, sizeof(int32_t) * n_seen, hipMemcpyHostToDevice, st));
+  }
+  const size_t kl = static_cast<size_t>(K) * L;
+  for (int s = 0; s < S && xs > 0; ++s) {
+    const RowTab src = plain_tab(th.ptr + s * tk, K);
+    const double *m = K <= L ? nullptr : c->rc_wk.ptr + s * kl;
+    LAUNCH(rec_fold_kernel, static_cast<unsigned>((xs + kBlock - 1) / kBlock), kBlock, 0, st, src, K, m, L, 1,
+           x.ptr + s * xs, static_cast<int>(n_users), rank);
+  }
+  HIP_CHECK(hipGetLastError());
+  rec_run(c, x.ptr, xs, n_users, hid.data(), seen_offsets ? soff.ptr : nullptr, sit.ptr, n, items, scores, counts);
 }
 
 void recommend_end(mmsbm_hip_ctx *c) {

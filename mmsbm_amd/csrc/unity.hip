@@ -14,3 +14,4 @@
 #include "tu_once.hip"
 #include "tu_layout.hip"
 #include "tu_recommend.hip"
+#include "tu_fold_in.hip"

@@ -140,10 +140,32 @@ class Encoder:
         if self.labels is None:
             raise AssertionError("encoder has not seen training data")
         cols, names = _columns(data)
+        ids, keep = self._encode(cols, (0, 1, 2), logger)
+        out = np.empty((int(keep.sum()), 3), dtype=np.int32, order="F")
+        for j in range(3):
+            out[:, j] = ids[j][keep]
+        return out
+
+    def transform_items(self, data, logger=None):
+        """transform for the item and rating columns alone (the user column is not looked at): ((M, 2) int32 ids of
+        the rows kept, the (N,) mask of those rows).  Rows with an unseen item or rating are dropped with transform's
+        warning."""
+        if self.labels is None:
+            raise AssertionError("encoder has not seen training data")
+        cols, _ = _columns(data)
+        ids, keep = self._encode(cols, (1, 2), logger)
+        out = np.empty((int(keep.sum()), 2), dtype=np.int32)
+        out[:, 0], out[:, 1] = ids[0][keep], ids[1][keep]
+        return out, keep
+
+    def _encode(self, cols, which, logger):
+        """ids of columns `which` against the training dictionaries, and the mask of the rows all of them know"""
         keep = np.ones(len(cols[0]), dtype=bool)
         ids = []
         log = logger or logging.getLogger("MMSBM")
-        for j, (name, col, lab) in enumerate(zip(("users", "items", "ratings"), cols, self.labels)):
+        names = ("users", "items", "ratings")
+        for j in which:
+            name, col, lab = names[j], cols[j], self.labels[j]
             col = np.asarray(col)
             imap = self._int_maps[j]
             if imap is not None and col.dtype.kind in "iu" and len(col) and int(col.min()) >= 0 and int(col.max()) < 2 ** 62:
@@ -178,10 +200,7 @@ class Encoder:
                             f"the train set so I'll remove them.")
             keep &= hit
             ids.append(pos.astype(np.int32))
-        out = np.empty((int(keep.sum()), 3), dtype=np.int32, order="F")
-        for j in range(3):
-            out[:, j] = ids[j][keep]
-        return out
+        return ids, keep
 
     # decoding helpers (data_handler.py:74-99)
     def user_labels(self):

@@ -292,19 +292,8 @@ class MMSBM:
         (``users=None``: every training user), users and items as the encoder's labels (``theta`` / ``eta``'s index).  The model's stored predictions and
         ``score()`` are left as they are."""
         import pandas as pd
-        self._check_is_fitted()
-        if len(self._restart_ids) != self.sampling:
-            raise RuntimeError(
-                f"this model holds {len(self._restart_ids)} of its {self.sampling} restarts (restarts.fit_distributed "
-                "without gather=True): fit with gather=True to recommend from all of them")
-        if isinstance(n, (bool, np.bool_)) or not isinstance(n, (int, np.integer)) or n < 1:
-            raise ValueError(f"n must be a positive integer, got {n!r}")
-        n = int(n)
-        w = np.asarray(self.ratings if weights is None else weights, dtype=np.float64)
-        if w.shape != (len(self.ratings),):
-            raise ValueError(f"weights has shape {w.shape}, expected ({len(self.ratings)},): one per rating value")
-        if not np.isfinite(w).all():
-            raise ValueError(f"weights must be finite, got {w.tolist()}")
+        self._check_whole_model()
+        n, w = self._recommend_args(n, weights)
         enc = self.data_handler
         n_users = self.p + 1
         if users is None:
@@ -349,6 +338,161 @@ class MMSBM:
                 it = items[keep]
                 parts.append(pd.DataFrame({
                     "users": labels[rows] if len(rows) else np.empty(0, dtype=object),
+                    "items": item_labels[it] if item_labels is not None else it.astype(np.int64),
+                    "score": scores[keep],
+                    "rank": np.nonzero(keep)[1].astype(np.int64) + 1}))
+        finally:
+            ctx.recommend_end()
+        if not parts:
+            return pd.DataFrame({"users": [], "items": [], "score": np.zeros(0), "rank": np.zeros(0, dtype=np.int64)})
+        return pd.concat(parts, ignore_index=True)
+
+    def _check_whole_model(self):
+        self._check_is_fitted()
+        if len(self._restart_ids) != self.sampling:
+            raise RuntimeError(
+                f"this model holds {len(self._restart_ids)} of its {self.sampling} restarts (restarts.fit_distributed "
+                "without gather=True): fit with gather=True to recommend from all of them")
+
+    def _recommend_args(self, n, weights):
+        if isinstance(n, (bool, np.bool_)) or not isinstance(n, (int, np.integer)) or n < 1:
+            raise ValueError(f"n must be a positive integer, got {n!r}")
+        w = np.asarray(self.ratings if weights is None else weights, dtype=np.float64)
+        if w.shape != (len(self.ratings),):
+            raise ValueError(f"weights has shape {w.shape}, expected ({len(self.ratings)},): one per rating value")
+        if not np.isfinite(w).all():
+            raise ValueError(f"weights must be finite, got {w.tolist()}")
+        return int(n), w
+
+    # ------------------------------------------------------------------ fold-in of new users (not in the reference)
+    def _encode_new_users(self, data):
+        """(rows (N, 3) int32 [new user, item, rating], user labels in order of first appearance).  Every user of
+        ``data`` is new (the training theta is never consulted); items and ratings are encoded against the training
+        dictionaries, and rows with an unseen item or rating are dropped with ``Encoder.transform``'s warning.  A user
+        whose rows are all dropped keeps its place (uniform theta, no iterations)."""
+        import pandas as pd
+        from .encode import _columns
+        cols, _ = _columns(data)
+        users = np.asarray(cols[0])
+        enc = self.data_handler
+        if enc:  # labels as the encoder makes them: str(value)
+            if users.dtype.kind in "iu":
+                codes, uniq = pd.factorize(users)
+            else:
+                if any(v is None or (isinstance(v, float) and v != v) for v in users.tolist()):
+                    raise AssertionError("Data contains missing values. Aborting.")
+                codes, uniq = pd.factorize(np.array([str(v) for v in users.tolist()], dtype=object))
+            labels = np.array([str(v) for v in np.asarray(uniq).tolist()], dtype=object)
+            rows, keep = enc.transform_items(data, self.logger)
+        else:
+            if len(users) and (not np.issubdtype(users.dtype, np.integer) or users.min() < 0):
+                raise ValueError("after fit_encoded the user column holds non-negative integer ids")
+            codes, uniq = pd.factorize(users.astype(np.int64))
+            labels = np.asarray(uniq, dtype=np.int64)
+            item, rating = (np.asarray(c) for c in cols[1:])
+            for name, col in (("items", item), ("ratings", rating)):
+                if len(col) and not np.issubdtype(col.dtype, np.integer):
+                    raise ValueError(f"after fit_encoded the {name} column holds encoded integer ids")
+            keep = np.ones(len(users), dtype=bool)
+            for name, col, top in (("items", item, self.m + 1), ("ratings", rating, len(self.ratings))):
+                bad = keep & ((col < 0) | (col >= top))
+                unseen = np.unique(col[bad])
+                if len(unseen):
+                    self.logger.warning(f"The {name} {', '.join(str(v) for v in unseen.tolist())} are in the test set "
+                                        f"but weren't in the train set so I'll remove them.")
+                keep &= ~bad
+            rows = np.stack([item[keep], rating[keep]], 1).astype(np.int32)
+        out = np.empty((int(keep.sum()), 3), dtype=np.int32)
+        out[:, 0] = np.asarray(codes)[keep]
+        out[:, 1:] = rows
+        return out, labels
+
+    def _fold_runs(self, rows, n_new, iterations, tol, each=None):
+        """theta (n_new, K) and the iterations used of every restart, in ``self.results`` order; ``each(ctx)`` runs
+        after each restart's fold-in while its parameters are selected (recommend_new adds the slot there)."""
+        dev = self._device_list()[0]
+        ctx = self._ctx(dev)
+        resident = self._resident.get((dev, 0)) == list(self._restart_ids) and ctx.slots == len(self.results)
+        if not resident:
+            ctx.set_slots(1)
+            self._resident.pop((dev, 0), None)
+        thetas, iters = [], []
+        for j, a in enumerate(self.results):
+            if resident:
+                ctx.select(j)
+            else:
+                ctx.set_params(a["theta"], a["eta"], a["pr"])
+            t, it = ctx.fold_in(rows, n_new, iterations, tol)
+            thetas.append(t)
+            iters.append(it)
+            if each is not None:
+                each(ctx)
+        return ctx, thetas, iters
+
+    @staticmethod
+    def _fold_args(iterations, tol):
+        if isinstance(iterations, (bool, np.bool_)) or not isinstance(iterations, (int, np.integer)) or iterations < 0:
+            raise ValueError(f"iterations must be a non-negative integer, got {iterations!r}")
+        if tol is not None and not (isinstance(tol, (int, float, np.integer, np.floating)) and np.isfinite(tol)):
+            raise ValueError(f"tol must be None or a finite number, got {tol!r}")
+        return int(iterations), (None if tol is None else float(tol))
+
+    def fold_in(self, data, iterations=100, tol=None):
+        """theta of users that were not in the training data, from their ratings: ``iterations`` steps of the theta
+        half of the M-step with every restart's eta and p held fixed, from a uniform start (``tol``: a user stops once
+        no entry of its theta moves by more than ``tol``).  ``data``: users, items, ratings like ``fit``'s (after
+        ``fit_encoded``: integer triples, users as any non-negative ids, items and ratings encoded).
+
+        Returns a list of DataFrames, one per restart in ``self.results`` order, each (new users x K) indexed by the
+        user labels in order of first appearance in ``data``.  ``self.fold_in_iterations``: a DataFrame (new users x
+        restarts) of the iterations each user ran.  The model itself is left as it is."""
+        import pandas as pd
+        self._check_whole_model()
+        iterations, tol = self._fold_args(iterations, tol)
+        rows, labels = self._encode_new_users(data)
+        _, thetas, iters = self._fold_runs(rows, len(labels), iterations, tol)
+        index = pd.Index(labels, name="users") if len(labels) else pd.Index([], name="users")
+        self.fold_in_iterations = pd.DataFrame(np.stack(iters, 1) if iters else np.zeros((len(labels), 0)),
+                                               index=index)
+        return [pd.DataFrame(t, index=index) for t in thetas]
+
+    def recommend_new(self, data, n=10, exclude_seen=True, weights=None, iterations=100, tol=None):
+        """``recommend`` for users that were not in the training data: each restart scores with the theta its own
+        ``fold_in`` gives them (same arguments as ``fold_in``), the scores are averaged over the restarts.  Returns
+        the frame ``recommend`` returns (users, items, score, rank), users in order of first appearance in ``data``;
+        ``exclude_seen`` leaves out the items a user has in ``data``."""
+        import pandas as pd
+        self._check_whole_model()
+        n, w = self._recommend_args(n, weights)
+        iterations, tol = self._fold_args(iterations, tol)
+        rows, labels = self._encode_new_users(data)
+        enc = self.data_handler
+        item_labels = np.asarray(enc.item_labels(), dtype=object) if enc else None
+        n_new = len(labels)
+        ctx = self._ctx(self._device_list()[0])
+        parts = []
+        ctx.recommend_begin(w, False)
+        try:
+            _, thetas, iters = self._fold_runs(rows, n_new, iterations, tol, each=lambda c: c.recommend_add())
+            self.fold_in_iterations = pd.DataFrame(np.stack(iters, 1), index=pd.Index(labels, name="users"))
+            theta = np.stack(thetas)                                  # (restarts, new users, K)
+            if exclude_seen:
+                order = np.lexsort((rows[:, 1], rows[:, 0]))
+                counts = np.bincount(rows[:, 0], minlength=n_new)
+                seen_off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+                seen_items = rows[order, 1]
+            step = max(1, self.RECOMMEND_BATCH_ROWS // n)
+            for b in range(0, n_new, step):
+                e = min(n_new, b + step)
+                seen = None
+                if exclude_seen:
+                    seen = (seen_off[b:e + 1] - seen_off[b], seen_items[seen_off[b]:seen_off[e]])
+                items, scores, counts = ctx.recommend_query_theta(theta[:, b:e], n, seen)
+                keep = np.arange(n)[None, :] < counts[:, None]
+                at = np.repeat(np.arange(b, e), counts)
+                it = items[keep]
+                parts.append(pd.DataFrame({
+                    "users": labels[at] if len(at) else np.empty(0, dtype=object),
                     "items": item_labels[it] if item_labels is not None else it.astype(np.int64),
                     "score": scores[keep],
                     "rank": np.nonzero(keep)[1].astype(np.int64) + 1}))
