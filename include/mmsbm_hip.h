@@ -198,6 +198,18 @@ int mmsbm_hip_recommend_end(mmsbm_hip_ctx *ctx);
 int mmsbm_hip_recommend_query_theta(mmsbm_hip_ctx *ctx, int64_t n_users, const double *theta,
                                     const int64_t *seen_offsets, const int32_t *seen_items, int32_t n,
                                     int32_t *items, double *scores, int32_t *counts);
+/* Positions of caller-given items in each user's full recommendation order, within the open recommend session.
+ * user b's items: items[offsets[b] .. offsets[b+1]) (ids in [0, I), repeats allowed, any order).
+ * positions: offsets[n_users] int32 out, 0 = not a candidate.  candidates (may be NULL): n_users int32 out.
+ * With the scores and candidates of query: position(u, t) = 1 + #{candidates j : score(u, j) > score(u, t), or
+ * score(u, j) == score(u, t) and j < t} for a candidate t, 0 for a training item of u while exclude_train is set;
+ * candidates(u) = I - |distinct training items of u| when excluding, else I.  So a candidate at position p <= n is
+ * item p - 1 of query's row for n.  Bitwise independent of the other users of the call; only users holding items are
+ * scored; touches no slot and no session.  MMSBM_E_TOOLARGE where the device memory a batch needs is not free.
+ * mmsbm_hip_get_option(ctx, "position_ms") reads the device time of the last call's kernels (HIP events). */
+int mmsbm_hip_recommend_positions(mmsbm_hip_ctx *ctx, int64_t n_users, const int32_t *users,
+                                  const int64_t *offsets, const int32_t *items,
+                                  int32_t *positions, int32_t *candidates);
 
 /* ---- fold-in: theta of new users under the fitted eta and p (mmsbm_amd/csrc/fold_in.hpp) ----------------------- */
 /* The SELECTED slot's eta and p stay fixed; for new users 0 .. n_new-1, given their rows (user in [0, n_new), item in

@@ -356,6 +356,23 @@ class HipEM:
                   _p(items, C.c_int32), _p(scores, C.c_double), _p(counts, C.c_int32))
         return items, scores, counts
 
+    def recommend_positions(self, users, offsets, items):
+        """(positions, candidates): the position (1 = best, 0 = not a candidate) of each item in its user's full
+        order within the open session -- user b's items are items[offsets[b]:offsets[b + 1]] -- and each user's
+        number of candidates.  positions: (offsets[-1],) int32; candidates: (len(users),) int32."""
+        u = _i32(users)
+        off = np.ascontiguousarray(offsets, dtype=np.int64)
+        it = _i32(items)
+        if off.shape != (len(u) + 1,):
+            raise ValueError(f"offsets have shape {off.shape}, expected ({len(u) + 1},)")
+        if off[-1] != len(it):
+            raise ValueError(f"offsets end at {int(off[-1])}, items holds {len(it)}")
+        positions = np.empty(len(it), dtype=np.int32)
+        candidates = np.empty(len(u), dtype=np.int32)
+        _lib.call("mmsbm_hip_recommend_positions", self._h, len(u), _p(u, C.c_int32), _p(off, C.c_int64),
+                  _p(it, C.c_int32), _p(positions, C.c_int32), _p(candidates, C.c_int32))
+        return positions, candidates
+
     def recommend_end(self):
         _lib.call("mmsbm_hip_recommend_end", self._h)
 

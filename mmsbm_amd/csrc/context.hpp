@@ -224,11 +224,13 @@ struct mmsbm_hip_ctx {
   DevBuf<double> rc_x, rc_y, rc_w;          // [slot][U][rank], [slot][I][rank], the R rating weights
   DevBuf<double> rc_wk;                     // [slot][K][L]: each slot's W (recommend_query_theta folds caller rows)
   DevBuf<int32_t> rc_seen_off, rc_seen;     // per external user: its distinct training items, ascending (exclude_train)
+  std::vector<int32_t> rc_seen_off_h;       // rc_seen_off on the host (candidate counts of recommend_positions)
   int rc_slots = -1;                        // slots added; -1: no session open
   int rc_rank = 0;
   bool rc_excl = false;
   float rc_last_ms = 0.f;                   // device time of the last query's kernels (option "recommend_ms")
   float fold_last_ms = 0.f;                 // device time of the last fold-in's kernels (option "fold_in_ms")
+  float pos_last_ms = 0.f;                  // device time of the last recommend_positions (option "position_ms")
   int cur = 0;
   std::vector<char> have;  // per slot: set_params has been called
   bool graph_mode = false;  // replay a captured two-iteration hipGraph instead of eager launches

@@ -42,6 +42,8 @@ void recommend_query(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, in
                      int32_t *counts);
 void recommend_query_theta(mmsbm_hip_ctx *c, int64_t n_users, const double *theta, const int64_t *seen_offsets,
                            const int32_t *seen_items, int n, int32_t *items, double *scores, int32_t *counts);
+void recommend_positions(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, const int64_t *offsets,
+                         const int32_t *items, int32_t *positions, int32_t *candidates);
 void recommend_end(mmsbm_hip_ctx *c);
 
 // tu_fold_in.hip -- fold new users into the selected slot's fitted eta and p (fold_in.hpp), arguments checked

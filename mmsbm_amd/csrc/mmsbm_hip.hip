@@ -1343,6 +1343,34 @@ int mmsbm_hip_recommend_query_theta(mmsbm_hip_ctx *ctx, int64_t n_users, const d
   });
 }
 
+int mmsbm_hip_recommend_positions(mmsbm_hip_ctx *ctx, int64_t n_users, const int32_t *users,
+                                  const int64_t *offsets, const int32_t *items, int32_t *positions,
+                                  int32_t *candidates) {
+  return guarded([&] {
+    if (!ctx) throw std::invalid_argument("null context");
+    if (ctx->rc_slots < 0) throw std::invalid_argument("recommend_begin has not been called");
+    if (ctx->rc_slots == 0) throw std::invalid_argument("recommend_positions before any recommend_add");
+    if (n_users < 0) throw std::invalid_argument("negative n_users");
+    if (n_users > 0 && (!users || !offsets)) throw std::invalid_argument("null argument");
+    for (int64_t m = 0; m < n_users; ++m)
+      if (users[m] < 0 || users[m] >= ctx->ext_users)
+        throw std::invalid_argument("recommend_positions: user id out of range at row " + std::to_string(m));
+    if (n_users > 0) {
+      if (offsets[0] != 0) throw std::invalid_argument("recommend_positions: offsets[0] must be 0");
+      for (int64_t b = 0; b < n_users; ++b)
+        if (offsets[b + 1] < offsets[b])
+          throw std::invalid_argument("recommend_positions: offsets decrease at user " + std::to_string(b));
+      const int64_t total = offsets[n_users];
+      if (total > INT32_MAX) throw std::invalid_argument("recommend_positions: more than 2^31 - 1 items");
+      if (total > 0 && (!items || !positions)) throw std::invalid_argument("null argument");
+      for (int64_t e = 0; e < total; ++e)
+        if (items[e] < 0 || items[e] >= ctx->ext_items)
+          throw std::invalid_argument("recommend_positions: item id out of range at entry " + std::to_string(e));
+    }
+    recommend_positions(ctx, n_users, users, offsets, items, positions, candidates);
+  });
+}
+
 int mmsbm_hip_fold_in(mmsbm_hip_ctx *ctx, int64_t n_rows, const int32_t *user, const int32_t *item,
                       const int32_t *rating, int32_t n_new, int32_t n_iters, double tol,
                       const double *theta0, double *theta, int32_t *iters) {
@@ -1548,6 +1576,7 @@ int mmsbm_hip_get_option(const mmsbm_hip_ctx *ctx, const char *name, double *val
     else if (key == "nt_out") *value = nt_on(ctx);
     else if (key == "recommend_ms") *value = ctx->rc_last_ms;  // read-only: device time of the last recommend_query
     else if (key == "fold_in_ms") *value = ctx->fold_last_ms;  // read-only: device time of the last fold_in
+    else if (key == "position_ms") *value = ctx->pos_last_ms;  // read-only: device time of the last recommend_positions
     else if (key == "launches") *value = use_fused(ctx) ? 2 : 4;  // read-only: launches per iteration at the current slot count
     else if (key == "wide") *value = ctx->wide;
     else if (key == "lik_fast") *value = ctx->lik_mode;

@@ -20,6 +20,10 @@
 //   rec_select_kernel   one wave per (user, item range): a running candidate list in LDS, filtered against the current
 //                       N-th best, compacted by ballot (no atomics) and re-sorted (bitonic) when it fills; the same
 //                       kernel then merges the ranges' lists when the items were split across waves.
+//   rec_position_kernel / rec_position_sum_kernel  (mmsbm_hip_recommend_positions) the position of caller-given items
+//                       in a user's full order: per (user, item range) the items of the range that beat each test
+//                       item, counted as integers with up to kPosKeys test keys in registers per pass over the row;
+//                       the ranges' counts are then summed in range order (no atomics).
 // Order: score descending, equal scores (exact fp64 equality) by ascending item id -- a strict total order, so the
 // top N is unique and the split into ranges cannot change it.  N is bounded by kRecMaxN (larger N: the C ABI answers
 // MMSBM_E_UNSUPPORTED); the candidate list holds the next power of two >= N + 256 entries (<= 2,048).
@@ -250,6 +254,98 @@ __global__ __launch_bounds__(kRecWave) void rec_select_kernel(const double *__re
     out_i[o * n + k] = ki[k];
   }
   if (lane == 0) out_n[o] = cnt;
+}
+
+// ---- positions of test items (mmsbm_hip_recommend_positions) --------------------------------------------------------
+constexpr int kPosKeys = 16;   // test keys held in registers per pass over a row (TQ)
+constexpr int kPosSmall = 4;   // a chunk of at most this many keys takes the narrow pass (most users hold 1-2)
+
+// Adds to cnt[q] the items j of [lo, hi) this thread visits that come before key q in the order:
+// score(j) > ks[q], or score(j) == ks[q] and j < ki[q].  Padding keys (+inf, -1) are beaten by nothing; excluded
+// items (-inf) beat no finite key.
+template <int Q>
+__device__ __forceinline__ void rec_count_pass(const double *__restrict__ row, int lo, int hi, const double *ks,
+                                               const int *ki, int *cnt) {
+  for (int j = lo + static_cast<int>(threadIdx.x); j < hi; j += kBlock) {
+    const double s = row[j];
+#pragma unroll
+    for (int q = 0; q < Q; ++q) cnt[q] += (s > ks[q]) | ((s == ks[q]) & (j < ki[q]));
+  }
+}
+
+// One chunk of keys: test entries c0 .. c0 + nq of the row; the workgroup's counts over [lo, hi) go to
+// out[(c0 + q) * parts + part] (entries relative to the batch's first).
+template <int Q>
+__device__ __forceinline__ void rec_count_chunk(const double *__restrict__ row, int lo, int hi,
+                                                const int32_t *__restrict__ titem, int c0, int nq, int parts,
+                                                int part, int32_t *__restrict__ out, int (*red)[kPosKeys]) {
+  double ks[Q];
+  int ki[Q], cnt[Q];
+#pragma unroll
+  for (int q = 0; q < Q; ++q) {
+    ki[q] = -1;
+    ks[q] = INFINITY;
+    if (q < nq) {
+      ki[q] = titem[c0 + q];
+      ks[q] = row[ki[q]];
+    }
+    cnt[q] = 0;
+  }
+  rec_count_pass<Q>(row, lo, hi, ks, ki, cnt);
+  const int lane = threadIdx.x % kRecWave, wave = threadIdx.x / kRecWave;
+#pragma unroll
+  for (int q = 0; q < Q; ++q) {
+    int v = cnt[q];
+    for (int o = kRecWave / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, kRecWave);
+    if (lane == 0) red[wave][q] = v;
+  }
+  __syncthreads();
+  if (static_cast<int>(threadIdx.x) < nq) {
+    int v = 0;
+    for (int w = 0; w < kBlock / kRecWave; ++w) v += red[w][threadIdx.x];
+    out[static_cast<size_t>(c0 + threadIdx.x) * parts + part] = v;
+  }
+  __syncthreads();  // (red is reused by the next chunk)
+}
+
+// grid (parts, rows of the batch).  Row b scores[b * ld ...] holds the test entries toff[b] .. toff[b + 1) (item ids
+// titem[e]; entries counted from toff[0], the batch's first); the workgroup counts over items [part * per, + per).
+__global__ __launch_bounds__(kBlock) void rec_position_kernel(const double *__restrict__ scores, size_t ld, int ni,
+                                                              int per, const int32_t *__restrict__ toff,
+                                                              const int32_t *__restrict__ titem,
+                                                              int32_t *__restrict__ part_cnt) {
+  __shared__ int red[kBlock / kRecWave][kPosKeys];
+  const int part = blockIdx.x, parts = gridDim.x, b = blockIdx.y;
+  const int lo = part * per, hi = min(ni, lo + per);
+  const double *row = scores + static_cast<size_t>(b) * ld;
+  const int base = toff[0], e1 = toff[b + 1] - base;
+  const int32_t *it = titem + base;
+  for (int c0 = toff[b] - base; c0 < e1; c0 += kPosKeys) {
+    const int nq = min(kPosKeys, e1 - c0);
+    if (nq <= kPosSmall)
+      rec_count_chunk<kPosSmall>(row, lo, hi, it, c0, nq, parts, part, part_cnt, red);
+    else
+      rec_count_chunk<kPosKeys>(row, lo, hi, it, c0, nq, parts, part, part_cnt, red);
+  }
+}
+
+// positions[e] = 0 when the test item's score is -inf (excluded: not a candidate), else 1 + the ranges' counts summed
+// in range order.  One workgroup per row of the batch; e is the global entry (toff as in rec_position_kernel).
+__global__ __launch_bounds__(kBlock) void rec_position_sum_kernel(const double *__restrict__ scores, size_t ld,
+                                                                  const int32_t *__restrict__ toff,
+                                                                  const int32_t *__restrict__ titem,
+                                                                  const int32_t *__restrict__ part_cnt, int parts,
+                                                                  int32_t *__restrict__ positions) {
+  const int b = blockIdx.x, base = toff[0];
+  const double *row = scores + static_cast<size_t>(b) * ld;
+  for (int e = toff[b] + threadIdx.x; e < toff[b + 1]; e += kBlock) {
+    int pos = 0;
+    if (row[titem[e]] != -INFINITY) {
+      pos = 1;
+      for (int p = 0; p < parts; ++p) pos += part_cnt[static_cast<size_t>(e - base) * parts + p];
+    }
+    positions[e] = pos;
+  }
 }
 
 }  // namespace

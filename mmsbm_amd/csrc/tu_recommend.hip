@@ -11,6 +11,7 @@ namespace {
 
 constexpr size_t kRecBatchBytes = size_t(128) << 20;  // score buffer of one batch of users (stays in the 256 MB MALL)
 constexpr int kRecMinPerPart = 1024;                   // items a selecting wave gets at least
+constexpr int kPosMinPerPart = 2048;                   // items a counting workgroup gets at least
 
 void rec_require_mem(size_t bytes, const char *what) {
   size_t free_b = 0, total_b = 0;
@@ -32,6 +33,7 @@ void recommend_begin(mmsbm_hip_ctx *c, const double *weights, int exclude_train)
   c->rc_wk.release();
   c->rc_seen_off.release();
   c->rc_seen.release();
+  c->rc_seen_off_h.clear();
   hipStream_t s = c->stream;
   c->rc_w.alloc(c->n_ratings);
   HIP_CHECK(hipMemcpyAsync(c->rc_w.ptr, weights, sizeof(double) * c->n_ratings, hipMemcpyHostToDevice, s));
@@ -63,6 +65,7 @@ void recommend_begin(mmsbm_hip_ctx *c, const double *weights, int exclude_train)
     off[U] = w;
     item.resize(static_cast<size_t>(w));
     c->rc_seen_off.upload(off, s);
+    c->rc_seen_off_h = off;  // (candidate counts of recommend_positions)
     c->rc_seen.upload(item, s);
     HIP_CHECK(hipStreamSynchronize(s));  // (host vectors are locals)
   }
@@ -123,6 +126,27 @@ void recommend_add(mmsbm_hip_ctx *c) {  // the selected slot (the caller holds a
 
 namespace {
 
+// users per batch: a score buffer of ~128 MB, whole 128-user tiles where that allows
+int64_t rec_batch_users(int I, int64_t n_users) {
+  int64_t bu = std::max<int64_t>(1, static_cast<int64_t>(kRecBatchBytes / (static_cast<size_t>(I) * sizeof(double))));
+  bu = std::min<int64_t>(bu, 32768);
+  if (bu >= kRecTile) bu = bu / kRecTile * kRecTile;
+  return std::min(bu, n_users);
+}
+
+// The scores of one batch of nb users ub (device ids, rows of x) into sc [nb][I]; seen_off / seen (device, indexed by
+// those ids): the items set to -inf, or null.  Shared by the selection (rec_run) and the positions.
+void rec_score_batch(mmsbm_hip_ctx *c, const double *x, size_t xs, const int32_t *ub, int nb, const int32_t *seen_off,
+                     const int32_t *seen, double *sc) {
+  const int I = c->ext_items, rank = c->rc_rank, S = c->rc_slots;
+  if (I == 0) return;
+  hipStream_t st = c->stream;
+  const dim3 g(static_cast<unsigned>((I + kRecTile - 1) / kRecTile), static_cast<unsigned>((nb + kRecTile - 1) / kRecTile));
+  LAUNCH(rec_score_kernel, g, kBlock, 0, st, x, xs, c->rc_y.ptr, static_cast<size_t>(I) * rank, ub, nb, I, rank, S,
+         sc, static_cast<size_t>(I));
+  if (seen_off) LAUNCH(rec_exclude_kernel, nb, kBlock, 0, st, ub, seen_off, seen, sc, static_cast<size_t>(I));
+}
+
 // The batches of a query: users users[0 .. n_users) (host ids, rows of x: `slots` tables of xs doubles, [row][rank]),
 // scored against the session's items; seen_off / seen (device, indexed by those ids): the items left out, or null.
 void rec_run(mmsbm_hip_ctx *c, const double *x, size_t xs, int64_t n_users, const int32_t *users,
@@ -135,14 +159,10 @@ void rec_run(mmsbm_hip_ctx *c, const double *x, size_t xs, int64_t n_users, cons
     }
   }
   if (n_users == 0) return;
-  const int I = c->ext_items, rank = c->rc_rank, S = c->rc_slots;
+  const int I = c->ext_items;
   hipStream_t st = c->stream;
 
-  // users per batch: a score buffer of ~128 MB, whole 128-user tiles where that allows
-  int64_t bu = std::max<int64_t>(1, static_cast<int64_t>(kRecBatchBytes / (static_cast<size_t>(I) * sizeof(double))));
-  bu = std::min<int64_t>(bu, 32768);
-  if (bu >= kRecTile) bu = bu / kRecTile * kRecTile;
-  bu = std::min(bu, n_users);
+  const int64_t bu = rec_batch_users(I, n_users);
   // items split across waves until about 32 selecting waves per CU are in flight (the selection waits on its loads;
   // few users: a single user over 100k items)
   const int64_t target = 32LL * c->n_cus;
@@ -176,13 +196,7 @@ void rec_run(mmsbm_hip_ctx *c, const double *x, size_t xs, int64_t n_users, cons
     const int32_t *ub = du.ptr + b0;
     double *obs = os.ptr + b0 * n;
     int32_t *obi = oi.ptr + b0 * n, *obn = on.ptr + b0;
-    if (I > 0) {
-      const dim3 g(static_cast<unsigned>((I + kRecTile - 1) / kRecTile), static_cast<unsigned>((nb + kRecTile - 1) / kRecTile));
-      LAUNCH(rec_score_kernel, g, kBlock, 0, st, x, xs, c->rc_y.ptr, static_cast<size_t>(I) * rank, ub, nb, I, rank, S,
-             sc.ptr, static_cast<size_t>(I));
-      if (seen_off)
-        LAUNCH(rec_exclude_kernel, nb, kBlock, 0, st, ub, seen_off, seen, sc.ptr, static_cast<size_t>(I));
-    }
+    rec_score_batch(c, x, xs, ub, nb, seen_off, seen, sc.ptr);
     if (parts > 1) {
       LAUNCH(rec_select_kernel<false>, dim3(parts, nb), kRecWave, lds, st, sc.ptr, static_cast<size_t>(I), I, per,
              nullptr, nullptr, nullptr, 0, n, cap, cs.ptr, ci.ptr, cn.ptr);
@@ -261,6 +275,78 @@ void recommend_query_theta(mmsbm_hip_ctx *c, int64_t n_users, const double *thet
   rec_run(c, x.ptr, xs, n_users, hid.data(), seen_offsets ? soff.ptr : nullptr, sit.ptr, n, items, scores, counts);
 }
 
+void recommend_positions(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, const int64_t *offsets,
+                         const int32_t *items, int32_t *positions, int32_t *candidates) {
+  use_device(c);
+  const int I = c->ext_items, rank = c->rc_rank;
+  const int64_t total = n_users > 0 ? offsets[n_users] : 0;  // (checked: below 2^31)
+  for (int64_t b = 0; b < n_users && candidates; ++b) {
+    const int32_t u = users[b];
+    candidates[b] = c->rc_excl ? I - (c->rc_seen_off_h[u + 1] - c->rc_seen_off_h[u]) : I;
+  }
+  // only the users that hold test items are scored: the others' ranges are empty, so the ranges of the rows kept
+  // follow each other and toff[k] = offsets[row k] (toff[na] = total)
+  std::vector<int32_t> hu, toff;
+  for (int64_t b = 0; b < n_users; ++b)
+    if (offsets[b + 1] > offsets[b]) {
+      hu.push_back(users[b]);
+      toff.push_back(static_cast<int32_t>(offsets[b]));
+    }
+  toff.push_back(static_cast<int32_t>(total));
+  const int64_t na = static_cast<int64_t>(hu.size());
+  if (na == 0) {
+    c->pos_last_ms = 0.f;
+    return;
+  }
+  hipStream_t st = c->stream;
+  const int64_t bu = rec_batch_users(I, na);
+  // items split across workgroups until about 8 counting workgroups per CU are in flight (few users: one user over
+  // 100k items); the counts are integers, so the split cannot change a position
+  const int64_t target = 8LL * c->n_cus;
+  int parts = 1;
+  if (bu < target) parts = static_cast<int>(std::min<int64_t>((target + bu - 1) / bu, (I + kPosMinPerPart - 1) / kPosMinPerPart));
+  parts = std::max(parts, 1);
+  const int per = (I + parts - 1) / parts;
+  parts = I > 0 ? (I + per - 1) / per : 1;
+  int64_t most = 0;  // test entries of the largest batch
+  for (int64_t b0 = 0; b0 < na; b0 += bu) most = std::max<int64_t>(most, toff[std::min(na, b0 + bu)] - toff[b0]);
+  rec_require_mem(static_cast<size_t>(bu) * I * sizeof(double) + static_cast<size_t>(most) * parts * 4 +
+                      static_cast<size_t>(total) * 8 + static_cast<size_t>(na) * 8,
+                  "the positions of a batch of users");
+  DevBuf<int32_t> du, dto, dit, dpos, pc;
+  DevBuf<double> sc;
+  du.upload(hu, st);
+  dto.upload(toff, st);
+  dit.alloc(static_cast<size_t>(total));
+  dpos.alloc(static_cast<size_t>(total));
+  pc.alloc(static_cast<size_t>(most) * parts);
+  sc.alloc(static_cast<size_t>(bu) * I);
+  HIP_CHECK(hipMemcpyAsync(dit.ptr, items, sizeof(int32_t) * total, hipMemcpyHostToDevice, st));
+  hipEvent_t e0, e1;  // device time of the call's kernels (option "position_ms")
+  HIP_CHECK(hipEventCreate(&e0));
+  HIP_CHECK(hipEventCreate(&e1));
+  HIP_CHECK(hipEventRecord(e0, st));
+  const size_t xs = static_cast<size_t>(c->ext_users) * rank;
+  for (int64_t b0 = 0; b0 < na; b0 += bu) {  // (batches follow each other on the stream)
+    const int nb = static_cast<int>(std::min(bu, na - b0));
+    rec_score_batch(c, c->rc_x.ptr, xs, du.ptr + b0, nb, c->rc_excl ? c->rc_seen_off.ptr : nullptr, c->rc_seen.ptr,
+                    sc.ptr);
+    LAUNCH(rec_position_kernel, dim3(parts, nb), kBlock, 0, st, sc.ptr, static_cast<size_t>(I), I, per, dto.ptr + b0,
+           dit.ptr, pc.ptr);
+    LAUNCH(rec_position_sum_kernel, nb, kBlock, 0, st, sc.ptr, static_cast<size_t>(I), dto.ptr + b0, dit.ptr, pc.ptr,
+           parts, dpos.ptr);
+    HIP_CHECK(hipGetLastError());
+  }
+  HIP_CHECK(hipEventRecord(e1, st));
+  HIP_CHECK(hipMemcpyAsync(positions, dpos.ptr, sizeof(int32_t) * total, hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipStreamSynchronize(st));
+  float ms = 0.f;
+  HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
+  c->pos_last_ms = ms;
+  (void)hipEventDestroy(e0);
+  (void)hipEventDestroy(e1);
+}
+
 void recommend_end(mmsbm_hip_ctx *c) {
   c->rc_slots = -1;
   c->rc_x.release();
@@ -268,6 +354,7 @@ void recommend_end(mmsbm_hip_ctx *c) {
   c->rc_w.release();
   c->rc_seen_off.release();
   c->rc_seen.release();
+  c->rc_seen_off_h.clear();
 }
 
 }  // namespace mmsbm_hip_impl

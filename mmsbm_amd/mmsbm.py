@@ -357,12 +357,139 @@ class MMSBM:
     def _recommend_args(self, n, weights):
         if isinstance(n, (bool, np.bool_)) or not isinstance(n, (int, np.integer)) or n < 1:
             raise ValueError(f"n must be a positive integer, got {n!r}")
+        return int(n), self._rating_weights(weights)
+
+    def _rating_weights(self, weights):
         w = np.asarray(self.ratings if weights is None else weights, dtype=np.float64)
         if w.shape != (len(self.ratings),):
             raise ValueError(f"weights has shape {w.shape}, expected ({len(self.ratings)},): one per rating value")
         if not np.isfinite(w).all():
             raise ValueError(f"weights must be finite, got {w.tolist()}")
-        return int(n), w
+        return w
+
+    # ------------------------------------------------------------------ ranking evaluation (not in the reference)
+    def _encode_heldout(self, data):
+        """Encoded (N, 3) int32 rows of ``data`` in input order, rows with a user, item or rating unseen in training
+        dropped with ``Encoder.transform``'s warning (after ``fit_encoded``: ids outside the training ones)."""
+        if self.data_handler:
+            return self.data_handler.transform(data, self.logger)
+        from .encode import _columns
+        cols, _ = _columns(data)
+        keep = np.ones(len(cols[0]), dtype=bool)
+        ids = []
+        for name, col, known in (("users", cols[0], np.arange(self.p + 1)), ("items", cols[1], np.arange(self.m + 1)),
+                                 ("ratings", cols[2], np.asarray(self.ratings))):
+            col = np.asarray(col)
+            if len(col) and not np.issubdtype(col.dtype, np.integer):
+                raise ValueError(f"after fit_encoded the {name} column holds encoded integer ids")
+            hit = np.isin(col, known)
+            unseen = np.unique(col[keep & ~hit])
+            if len(unseen):
+                self.logger.warning(f"The {name} {', '.join(str(v) for v in unseen.tolist())} are in the test set "
+                                    f"but weren't in the train set so I'll remove them.")
+            keep &= hit
+            ids.append(col)
+        out = np.empty((int(keep.sum()), 3), dtype=np.int32)
+        for j in range(3):
+            out[:, j] = ids[j][keep]
+        return out
+
+    def _heldout(self, data, exclude_seen, weights):
+        """(encoded rows (N, 3), position (N,), candidates (N,)) of every row of ``data`` that survives encoding."""
+        self._check_whole_model()
+        w = self._rating_weights(weights)
+        rows = self._encode_heldout(data)
+        users = rows[:, 0]
+        order = np.argsort(users, kind="stable")                      # one request entry per user holding rows
+        uniq, counts = np.unique(users[order], return_counts=True)
+        offsets = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+        dev = self._device_list()[0]
+        ctx = self._ctx(dev)
+        # restarts whose final parameters still sit in this context's slots need no upload (as in recommend)
+        resident = self._resident.get((dev, 0)) == list(self._restart_ids) and ctx.slots == len(self.results)
+        if not resident:
+            ctx.set_slots(1)
+            self._resident.pop((dev, 0), None)
+        ctx.recommend_begin(w, exclude_seen)
+        try:
+            for j, a in enumerate(self.results):
+                if resident:
+                    ctx.select(j)
+                else:
+                    ctx.set_params(a["theta"], a["eta"], a["pr"])
+                ctx.recommend_add()
+            pos, cand = ctx.recommend_positions(uniq.astype(np.int32), offsets, rows[order, 1])
+        finally:
+            ctx.recommend_end()
+        position = np.empty(len(rows), dtype=np.int64)
+        position[order] = pos
+        candidates = np.empty(len(rows), dtype=np.int64)
+        candidates[order] = np.repeat(cand.astype(np.int64), counts)
+        return rows, position, candidates
+
+    def heldout_positions(self, data, exclude_seen=True, weights=None):
+        """Where each held-out row's item falls in its user's full recommendation order, on the device: one row per
+        row of ``data`` that survives encoding (rows whose user, item or rating is not in the training data are dropped
+        with ``predict``'s warning), in input order.  Scores and candidates are those of ``recommend(users, n,
+        exclude_seen, weights)``; ``position`` = 1 + the candidates that come before the item (score descending, equal
+        scores by ascending encoded item id), 0 when the item is not a candidate (a training item of the user while
+        ``exclude_seen``); ``candidates`` = the user's number of candidates.
+
+        Returns a DataFrame with columns ``users``, ``items``, ``ratings`` (the encoder's labels), ``position`` and
+        ``candidates``.  The model's stored objects are left as they are."""
+        import pandas as pd
+        rows, position, candidates = self._heldout(data, exclude_seen, weights)
+        enc = self.data_handler
+        cols = {}
+        for j, name in enumerate(("users", "items", "ratings")):
+            if enc:
+                cols[name] = np.asarray(enc.labels[j], dtype=object)[rows[:, j]] if len(rows) else np.empty(0, dtype=object)
+            else:
+                cols[name] = rows[:, j].astype(np.int64)
+        return pd.DataFrame({**cols, "position": position, "candidates": candidates})
+
+    def _ranking_args(self, k, relevant):
+        ks = [k] if isinstance(k, (int, np.integer)) and not isinstance(k, (bool, np.bool_)) else k
+        if isinstance(ks, (str, bytes)) or not hasattr(ks, "__iter__"):
+            raise ValueError(f"k must be a positive integer or a list of them, got {k!r}")
+        ks = list(ks)
+        if not ks or any(isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, np.integer)) or x < 1 for x in ks):
+            raise ValueError(f"k must be a positive integer or a list of them, got {k!r}")
+        ks = list(dict.fromkeys(int(x) for x in ks))
+        if relevant is None:
+            return ks, None
+        if isinstance(relevant, (str, bytes)) or not hasattr(relevant, "__iter__"):
+            raise ValueError(f"relevant must be a collection of rating values, got {relevant!r}")
+        enc = self.data_handler
+        index = {lab: j for j, lab in enumerate(enc.rating_labels())} if enc else None
+        ids = set()
+        for v in relevant:
+            if enc:  # the encoder's labels: str(value), whatever the order of the labels
+                j = index.get(str(v), -1)
+            else:
+                j = int(v) if isinstance(v, (int, np.integer)) and int(v) in self.ratings else -1
+            if j < 0:
+                raise ValueError(f"relevant rating {v!r} is not a rating of the training data")
+            ids.add(j)
+        return ks, ids
+
+    def ranking_score(self, data, k=10, relevant=None, exclude_seen=True, weights=None):
+        """Top-N ranking metrics of the held-out rows ``data`` (users, items, ratings like ``predict``'s), from
+        ``heldout_positions(data, exclude_seen, weights)``.  Each distinct (user, item) pair counts once; it is
+        relevant when any of its rows has a rating in ``relevant`` (rating values as in the data, e.g. ``{4, 5}``;
+        None: every pair).  Pairs that are not candidates (position 0) are left out and counted.  Per user with m >= 1
+        relevant candidate pairs at positions p_t among C candidates: hits(k) = #{p_t <= k}, precision@k = hits / k,
+        recall@k = hits / m, hit_rate@k = [hits > 0], ndcg@k (binary gains), mrr = 1 / min p_t and
+        auc = sum_t (C - m - (p_t - 1 - a_t)) / (m (C - m)) with a_t the relevant pairs before t (not defined for
+        C == m).  Each metric is the mean over those users (NaN without any).  ``k``: an int or a list of ints >= 1.
+
+        Returns a dict: ``users`` (evaluated), ``skipped_users`` (users with rows but no relevant candidate pair),
+        ``pairs`` (distinct pairs), ``not_candidates`` (pairs at position 0), ``mrr``, ``auc`` and ``precision@k``,
+        ``recall@k``, ``ndcg@k``, ``hit_rate@k`` for each k."""
+        self._check_whole_model()
+        ks, rel_ids = self._ranking_args(k, relevant)
+        rows, position, candidates = self._heldout(data, exclude_seen, weights)
+        return ranking_metrics(rows[:, 0], rows[:, 1], rows[:, 2], position, candidates, ks, rel_ids)
 
     # ------------------------------------------------------------------ fold-in of new users (not in the reference)
     def _encode_new_users(self, data):
@@ -639,3 +766,53 @@ class MMSBM:
         child.child_states = self.child_states  # every fold restarts from the same seeds (src/mmsbm.py:441)
         child.logger = self.logger
         return child
+
+
+def ranking_metrics(users, items, ratings, position, candidates, ks, relevant=None):
+    """The dict of ``MMSBM.ranking_score`` from per-row encoded ids, positions and candidate counts (work in
+    proportion to the rows).  ``relevant``: a set of rating ids, or None (every pair relevant)."""
+    users, items, ratings = (np.asarray(a, dtype=np.int64) for a in (users, items, ratings))
+    position, candidates = np.asarray(position, dtype=np.int64), np.asarray(candidates, dtype=np.int64)
+    rel_row = np.ones(len(users), dtype=bool) if relevant is None else np.isin(ratings, sorted(relevant))
+    # distinct (user, item) pairs: relevant when any of their rows is (the position is the same for every row)
+    order = np.lexsort((items, users))
+    u, i = users[order], items[order]
+    start = np.ones(len(u), dtype=bool)
+    start[1:] = (u[1:] != u[:-1]) | (i[1:] != i[:-1])
+    pair = np.cumsum(start) - 1
+    n_pairs = int(start.sum())
+    pu, pp, pc = u[start], position[order][start], candidates[order][start]
+    prel = np.zeros(n_pairs, dtype=bool)
+    np.logical_or.at(prel, pair, rel_row[order])
+    out = {"users": 0, "skipped_users": 0, "pairs": n_pairs, "not_candidates": int((pp == 0).sum())}
+    # per user: its relevant candidate pairs sorted by position
+    keep = prel & (pp > 0)
+    tu, tp, tc = pu[keep], pp[keep], pc[keep]
+    o = np.lexsort((tp, tu))
+    tu, tp, tc = tu[o], tp[o], tc[o]
+    all_users = np.unique(pu)
+    ev, first, m = np.unique(tu, return_index=True, return_counts=True)
+    n_ev = len(ev)
+    out["users"], out["skipped_users"] = n_ev, int(len(all_users) - n_ev)
+    grp = np.repeat(np.arange(n_ev), m)
+    a = np.arange(len(tu)) - np.repeat(first, m)                   # relevant pairs before each one
+    C = tc[first]
+    nan = float("nan")
+    mean = (lambda v: float(np.mean(v))) if n_ev else (lambda v: nan)
+    out["mrr"] = mean(1.0 / tp[first])
+    neg = C - m
+    ok = neg > 0
+    above = np.bincount(grp, weights=(np.repeat(neg, m) - (tp - 1 - a)).astype(np.float64), minlength=n_ev)
+    out["auc"] = float(np.mean(above[ok] / (m[ok] * neg[ok]).astype(np.float64))) if ok.any() else nan
+    gain = 1.0 / np.log2(tp + 1.0)
+    for k in ks:
+        inside = tp <= k
+        hits = np.bincount(grp, weights=inside.astype(np.float64), minlength=n_ev)
+        dcg = np.bincount(grp, weights=np.where(inside, gain, 0.0), minlength=n_ev)
+        ideal = np.cumsum(1.0 / np.log2(np.arange(1, max(int(m.max()) if n_ev else 0, 1) + 1) + 1.0))
+        idcg = ideal[np.minimum(m, k) - 1] if n_ev else np.zeros(0)
+        out[f"precision@{k}"] = mean(hits / k)
+        out[f"recall@{k}"] = mean(hits / m)
+        out[f"ndcg@{k}"] = mean(dcg / idcg)
+        out[f"hit_rate@{k}"] = mean((hits > 0).astype(np.float64))
+    return out
