@@ -193,23 +193,35 @@ int mmsbm_hip_recommend_end(mmsbm_hip_ctx *ctx);
 /* Like query, but the users are caller-given theta rows: theta [S][n_users][K] (external K) for the S added slots in
  * add order, folded with each slot's p and the session's weights exactly as add folds the slot's own theta -- so a
  * slot's own row gives bitwise the scores query gives for that user.  Excluded items come from a CSR list: user b
- * leaves out seen_items[seen_offsets[b] .. seen_offsets[b + 1]) (item ids in [0, I), repeats allowed);
+ * leaves out seen_items[seen_offsets[b] .. seen_offsets[b + 1]) (item ids in the session's catalogue [0, I) -- [0, I +
+ * n_new) after recommend_add_items -- repeats allowed);
  * seen_offsets NULL: nothing excluded (the session's exclude_train does not apply to these users). */
 int mmsbm_hip_recommend_query_theta(mmsbm_hip_ctx *ctx, int64_t n_users, const double *theta,
                                     const int64_t *seen_offsets, const int32_t *seen_items, int32_t n,
                                     int32_t *items, double *scores, int32_t *counts);
 /* Positions of caller-given items in each user's full recommendation order, within the open recommend session.
- * user b's items: items[offsets[b] .. offsets[b+1]) (ids in [0, I), repeats allowed, any order).
+ * user b's items: items[offsets[b] .. offsets[b+1]) (ids in the session's catalogue, repeats allowed, any order).
  * positions: offsets[n_users] int32 out, 0 = not a candidate.  candidates (may be NULL): n_users int32 out.
  * With the scores and candidates of query: position(u, t) = 1 + #{candidates j : score(u, j) > score(u, t), or
- * score(u, j) == score(u, t) and j < t} for a candidate t, 0 for a training item of u while exclude_train is set;
- * candidates(u) = I - |distinct training items of u| when excluding, else I.  So a candidate at position p <= n is
+ * score(u, j) == score(u, t) and j < t} for a candidate t, 0 for an excluded item of u;
+ * candidates(u) = I - |distinct excluded items of u| (I: the session's catalogue, I + n_new after
+ * recommend_add_items; excluded: the training items while exclude_train is set, plus the added items whose seen list
+ * names u).  So a candidate at position p <= n is
  * item p - 1 of query's row for n.  Bitwise independent of the other users of the call; only users holding items are
  * scored; touches no slot and no session.  MMSBM_E_TOOLARGE where the device memory a batch needs is not free.
  * mmsbm_hip_get_option(ctx, "position_ms") reads the device time of the last call's kernels (HIP events). */
 int mmsbm_hip_recommend_positions(mmsbm_hip_ctx *ctx, int64_t n_users, const int32_t *users,
                                   const int64_t *offsets, const int32_t *items,
                                   int32_t *positions, int32_t *candidates);
+/* Appends n_new items to the open session's catalogue, after every recommend_add: eta [S][n_new][L] (external L) for
+ * the S added slots in add order, folded with each slot's W exactly as add folds the slot's own eta.  New item j gets
+ * id I + j.  seen_offsets / seen_users (CSR over the new items, user ids in [0, U), repeats allowed; NULL: none):
+ * the training users that have rated new item j -- that (user, item) pair is then left out like a training pair
+ * (also when exclude_train is 0).  From here on query, query_theta and positions rank all I + n_new items; a training
+ * item's score is bitwise what it was before the call.  Once per session, after the first add and before any further
+ * add (otherwise MMSBM_E_INVALID); n_new == 0 changes nothing. */
+int mmsbm_hip_recommend_add_items(mmsbm_hip_ctx *ctx, int32_t n_new, const double *eta,
+                                  const int64_t *seen_offsets, const int32_t *seen_users);
 
 /* ---- fold-in: theta of new users under the fitted eta and p (mmsbm_amd/csrc/fold_in.hpp) ----------------------- */
 /* The SELECTED slot's eta and p stay fixed; for new users 0 .. n_new-1, given their rows (user in [0, n_new), item in
@@ -227,6 +239,17 @@ int mmsbm_hip_recommend_positions(mmsbm_hip_ctx *ctx, int64_t n_users, const int
 int mmsbm_hip_fold_in(mmsbm_hip_ctx *ctx, int64_t n_rows, const int32_t *user, const int32_t *item,
                       const int32_t *rating, int32_t n_new, int32_t n_iters, double tol,
                       const double *theta0, double *theta, int32_t *iters);
+/* The same for new ITEMS: the SELECTED slot's theta and p stay fixed; for new items 0 .. n_new-1, given their rows
+ * (user in [0, U), item in [0, n_new), rating in [0, R), external ids), n_iters times
+ *   eta'_i[l] = (1/d_i) sum_{rows j of i} eta_i[l] v_j[l] / max(eta_i . v_j, eps),
+ *   v_j[l]    = sum_k p[k, l, r_j] theta[u_j, k]                                  (k ascending)
+ * -- the eta half of the M-step.  eta0 (n_new x L) may be NULL: uniform 1/L.  tol, iters, rows without an item, request
+ * order and independence, side effects, MMSBM_E_TOOLARGE and "fold_in_ms" as mmsbm_hip_fold_in;
+ * L <= MMSBM_HIP_FOLD_IN_MAX_K (larger: MMSBM_E_UNSUPPORTED).  Bitwise equal to mmsbm_hip_fold_in on a context over
+ * the transposed problem (users and items exchanged, theta and eta exchanged, p transposed in (k, l)). */
+int mmsbm_hip_fold_in_items(mmsbm_hip_ctx *ctx, int64_t n_rows, const int32_t *user, const int32_t *item,
+                            const int32_t *rating, int32_t n_new, int32_t n_iters, double tol,
+                            const double *eta0, double *eta, int32_t *iters);
 
 /* ---- measurement ------------------------------------------------------------------ */
 /* Runs n_iters EM iterations bracketed by HIP events on the context's stream; returns

@@ -373,6 +373,28 @@ class HipEM:
                   _p(it, C.c_int32), _p(positions, C.c_int32), _p(candidates, C.c_int32))
         return positions, candidates
 
+    def recommend_add_items(self, eta, seen=None):
+        """Append new items to the open session's catalogue: eta (S, n_new, L), one (n_new, L) block per added slot in
+        add order; new item j gets id n_items + j.  seen: None or (offsets (n_new+1,) int64, users int32): the training
+        users that rated new item j are users[offsets[j]:offsets[j + 1]], and that pair is left out of their lists.
+        Once per session, after every recommend_add."""
+        e = _f64(eta)
+        if e.ndim != 3 or e.shape[2] != self.l:
+            raise ValueError(f"eta has shape {e.shape}, expected (slots, items, {self.l})")
+        if e.shape[0] != getattr(self, "_rc_added", 0):
+            raise ValueError(f"eta holds {e.shape[0]} blocks, the session {getattr(self, '_rc_added', 0)} added slots")
+        n_new = e.shape[1]
+        off = us = None
+        if seen is not None:
+            off = np.ascontiguousarray(seen[0], dtype=np.int64)
+            us = _i32(seen[1])
+            if off.shape != (n_new + 1,):
+                raise ValueError(f"seen offsets have shape {off.shape}, expected ({n_new + 1},)")
+            if off[-1] != len(us):
+                raise ValueError(f"seen offsets end at {int(off[-1])}, users holds {len(us)}")
+        _lib.call("mmsbm_hip_recommend_add_items", self._h, n_new, _p(e, C.c_double),
+                  None if off is None else _p(off, C.c_int64), None if us is None else _p(us, C.c_int32))
+
     def recommend_end(self):
         _lib.call("mmsbm_hip_recommend_end", self._h)
 
@@ -396,6 +418,24 @@ class HipEM:
                   n_new, int(iterations), -1.0 if tol is None else float(tol),
                   None if t0 is None else _p(t0, C.c_double), _p(theta, C.c_double), _p(iters, C.c_int32))
         return theta, iters
+
+    def fold_in_items(self, rows, n_new, iterations, tol=None, eta0=None):
+        """eta (n_new, L) of new items 0 .. n_new-1 under the selected slot's theta and p, and the iterations each ran
+        (n_new,).  rows: (N, 3) [user, new item, rating] (encoded user and rating ids, training data's column order).
+        tol None: all iterations; eta0 None: uniform 1/L.  The slot is left unchanged."""
+        u, i, r = split_triples(rows)
+        n_new = int(n_new)
+        e0 = None
+        if eta0 is not None:
+            e0 = _f64(eta0)
+            if e0.shape != (n_new, self.l):
+                raise ValueError(f"eta0 has shape {e0.shape}, expected ({n_new}, {self.l})")
+        eta = np.empty((n_new, self.l), dtype=np.float64)
+        iters = np.empty(n_new, dtype=np.int32)
+        _lib.call("mmsbm_hip_fold_in_items", self._h, len(u), _p(u, C.c_int32), _p(i, C.c_int32), _p(r, C.c_int32),
+                  n_new, int(iterations), -1.0 if tol is None else float(tol),
+                  None if e0 is None else _p(e0, C.c_double), _p(eta, C.c_double), _p(iters, C.c_int32))
+        return eta, iters
 
     # -- measurement -------------------------------------------------------------------------
     def time_iterations(self, n_iters):

@@ -221,15 +221,16 @@ struct mmsbm_hip_ctx {
   int64_t ps_rows = -1;  // -1: no session open
   int ps_added = 0;
   // recommend session (mmsbm_hip_recommend_begin .. end; recommend.hpp): the slots' folded factors, external sides
-  DevBuf<double> rc_x, rc_y, rc_w;          // [slot][U][rank], [slot][I][rank], the R rating weights
+  DevBuf<double> rc_x, rc_y, rc_w;          // [slot][U][rank], [slot][rc_items][rank], the R rating weights
   DevBuf<double> rc_wk;                     // [slot][K][L]: each slot's W (recommend_query_theta folds caller rows)
-  DevBuf<int32_t> rc_seen_off, rc_seen;     // per external user: its distinct training items, ascending (exclude_train)
+  DevBuf<int32_t> rc_seen_off, rc_seen;     // per external user: its distinct excluded items, ascending (rc_excl)
   std::vector<int32_t> rc_seen_off_h;       // rc_seen_off on the host (candidate counts of recommend_positions)
   int rc_slots = -1;                        // slots added; -1: no session open
+  int rc_items = 0;                         // the session's catalogue: I, or I + n_new after recommend_add_items
   int rc_rank = 0;
-  bool rc_excl = false;
+  bool rc_excl = false;                     // rc_seen_* in use: exclude_train, or seen lists of recommend_add_items
   float rc_last_ms = 0.f;                   // device time of the last query's kernels (option "recommend_ms")
-  float fold_last_ms = 0.f;                 // device time of the last fold-in's kernels (option "fold_in_ms")
+  float fold_last_ms = 0.f;                 // device time of the last fold-in's kernels, either side ("fold_in_ms")
   float pos_last_ms = 0.f;                  // device time of the last recommend_positions (option "position_ms")
   int cur = 0;
   std::vector<char> have;  // per slot: set_params has been called

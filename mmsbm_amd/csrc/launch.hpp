@@ -44,11 +44,16 @@ void recommend_query_theta(mmsbm_hip_ctx *c, int64_t n_users, const double *thet
                            const int32_t *seen_items, int n, int32_t *items, double *scores, int32_t *counts);
 void recommend_positions(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, const int64_t *offsets,
                          const int32_t *items, int32_t *positions, int32_t *candidates);
+void recommend_add_items(mmsbm_hip_ctx *c, int32_t n_new, const double *eta, const int64_t *seen_offsets,
+                         const int32_t *seen_users);
 void recommend_end(mmsbm_hip_ctx *c);
 
-// tu_fold_in.hip -- fold new users into the selected slot's fitted eta and p (fold_in.hpp), arguments checked
+// tu_fold_in.hip -- fold new users (new items) into the selected slot's fitted eta (theta) and p (fold_in.hpp),
+// arguments checked; fold_in_items: item[m] in [0, n_new), user[m] in [0, U)
 void fold_in(mmsbm_hip_ctx *c, int64_t n_rows, const int32_t *user, const int32_t *item, const int32_t *rating,
              int32_t n_new, int32_t n_iters, double tol, const double *theta0, double *theta, int32_t *iters);
+void fold_in_items(mmsbm_hip_ctx *c, int64_t n_rows, const int32_t *user, const int32_t *item, const int32_t *rating,
+                   int32_t n_new, int32_t n_iters, double tol, const double *eta0, double *eta, int32_t *iters);
 
 // dispatchers (mmsbm_hip.hip): the form the context's shape and options select
 void stage_dense(mmsbm_hip_ctx *c);

@@ -1281,6 +1281,8 @@ int mmsbm_hip_recommend_add(mmsbm_hip_ctx *ctx) {
   return guarded([&] {
     require_params(ctx);
     if (ctx->rc_slots < 0) throw std::invalid_argument("recommend_begin has not been called");
+    if (ctx->rc_items != ctx->ext_items)
+      throw std::invalid_argument("recommend_add after recommend_add_items: the added items hold no row of this slot");
     OneSlot one(ctx);
     recommend_add(ctx);
   });
@@ -1336,7 +1338,7 @@ int mmsbm_hip_recommend_query_theta(mmsbm_hip_ctx *ctx, int64_t n_users, const d
       if (total > INT32_MAX) throw std::invalid_argument("recommend: more than 2^31 - 1 seen items");
       if (total > 0 && !seen_items) throw std::invalid_argument("null argument");
       for (int64_t e = 0; e < total; ++e)
-        if (seen_items[e] < 0 || seen_items[e] >= ctx->ext_items)
+        if (seen_items[e] < 0 || seen_items[e] >= ctx->rc_items)
           throw std::invalid_argument("recommend: seen item out of range at entry " + std::to_string(e));
     }
     recommend_query_theta(ctx, n_users, theta, seen_offsets, seen_items, n, items, scores, counts);
@@ -1364,10 +1366,38 @@ int mmsbm_hip_recommend_positions(mmsbm_hip_ctx *ctx, int64_t n_users, const int
       if (total > INT32_MAX) throw std::invalid_argument("recommend_positions: more than 2^31 - 1 items");
       if (total > 0 && (!items || !positions)) throw std::invalid_argument("null argument");
       for (int64_t e = 0; e < total; ++e)
-        if (items[e] < 0 || items[e] >= ctx->ext_items)
+        if (items[e] < 0 || items[e] >= ctx->rc_items)
           throw std::invalid_argument("recommend_positions: item id out of range at entry " + std::to_string(e));
     }
     recommend_positions(ctx, n_users, users, offsets, items, positions, candidates);
+  });
+}
+
+int mmsbm_hip_recommend_add_items(mmsbm_hip_ctx *ctx, int32_t n_new, const double *eta,
+                                  const int64_t *seen_offsets, const int32_t *seen_users) {
+  return guarded([&] {
+    if (!ctx) throw std::invalid_argument("null context");
+    if (ctx->rc_slots < 0) throw std::invalid_argument("recommend_begin has not been called");
+    if (ctx->rc_slots == 0) throw std::invalid_argument("recommend_add_items before any recommend_add");
+    if (ctx->rc_items != ctx->ext_items)
+      throw std::invalid_argument("recommend_add_items: the session already holds added items");
+    if (n_new < 0) throw std::invalid_argument("recommend_add_items: negative n_new");
+    if (static_cast<int64_t>(ctx->ext_items) + n_new > INT32_MAX)
+      throw std::invalid_argument("recommend_add_items: more than 2^31 - 1 items in the catalogue");
+    if (n_new > 0 && !eta) throw std::invalid_argument("null argument");
+    if (seen_offsets && n_new > 0) {
+      if (seen_offsets[0] != 0) throw std::invalid_argument("recommend_add_items: seen_offsets[0] must be 0");
+      for (int32_t j = 0; j < n_new; ++j)
+        if (seen_offsets[j + 1] < seen_offsets[j])
+          throw std::invalid_argument("recommend_add_items: seen_offsets decrease at item " + std::to_string(j));
+      const int64_t total = seen_offsets[n_new];
+      if (total > INT32_MAX) throw std::invalid_argument("recommend_add_items: more than 2^31 - 1 seen users");
+      if (total > 0 && !seen_users) throw std::invalid_argument("null argument");
+      for (int64_t e = 0; e < total; ++e)
+        if (seen_users[e] < 0 || seen_users[e] >= ctx->ext_users)
+          throw std::invalid_argument("recommend_add_items: seen user out of range at entry " + std::to_string(e));
+    }
+    recommend_add_items(ctx, n_new, eta, seen_offsets, seen_users);
   });
 }
 
@@ -1395,6 +1425,33 @@ int mmsbm_hip_fold_in(mmsbm_hip_ctx *ctx, int64_t n_rows, const int32_t *user, c
     use_device(ctx);
     OneSlot one(ctx);
     fold_in(ctx, n_rows, user, item, rating, n_new, n_iters, tol, theta0, theta, iters);
+  });
+}
+
+int mmsbm_hip_fold_in_items(mmsbm_hip_ctx *ctx, int64_t n_rows, const int32_t *user, const int32_t *item,
+                            const int32_t *rating, int32_t n_new, int32_t n_iters, double tol,
+                            const double *eta0, double *eta, int32_t *iters) {
+  return guarded([&] {
+    require_params(ctx);
+    if (n_rows < 0 || n_rows > INT32_MAX) throw std::invalid_argument("fold_in_items: n_rows outside [0, 2^31)");
+    if (n_new < 0) throw std::invalid_argument("fold_in_items: negative n_new");
+    if (n_iters < 0) throw std::invalid_argument("fold_in_items: negative n_iters");
+    if (ctx->ext_l > MMSBM_HIP_FOLD_IN_MAX_K)
+      throw ApiError(MMSBM_E_UNSUPPORTED, "fold_in_items: L = " + std::to_string(ctx->ext_l) + " is beyond the " +
+                                              std::to_string(MMSBM_HIP_FOLD_IN_MAX_K) + " groups it is built for");
+    if (n_rows > 0 && (!user || !item || !rating)) throw std::invalid_argument("null argument");
+    if (n_new > 0 && !eta) throw std::invalid_argument("null argument");
+    for (int64_t m = 0; m < n_rows; ++m) {
+      if (user[m] < 0 || user[m] >= ctx->ext_users)
+        throw std::invalid_argument("fold_in_items: user id out of range at row " + std::to_string(m));
+      if (item[m] < 0 || item[m] >= n_new)
+        throw std::invalid_argument("fold_in_items: item id out of range at row " + std::to_string(m));
+      if (rating[m] < 0 || rating[m] >= ctx->n_ratings)
+        throw std::invalid_argument("fold_in_items: rating id out of range at row " + std::to_string(m));
+    }
+    use_device(ctx);
+    OneSlot one(ctx);
+    fold_in_items(ctx, n_rows, user, item, rating, n_new, n_iters, tol, eta0, eta, iters);
   });
 }
 
@@ -1575,7 +1632,7 @@ int mmsbm_hip_get_option(const mmsbm_hip_ctx *ctx, const char *name, double *val
     else if (key == "fused") *value = ctx->fused;
     else if (key == "nt_out") *value = nt_on(ctx);
     else if (key == "recommend_ms") *value = ctx->rc_last_ms;  // read-only: device time of the last recommend_query
-    else if (key == "fold_in_ms") *value = ctx->fold_last_ms;  // read-only: device time of the last fold_in
+    else if (key == "fold_in_ms") *value = ctx->fold_last_ms;  // read-only: device time of the last fold-in (either side)
     else if (key == "position_ms") *value = ctx->pos_last_ms;  // read-only: device time of the last recommend_positions
     else if (key == "launches") *value = use_fused(ctx) ? 2 : 4;  // read-only: launches per iteration at the current slot count
     else if (key == "wide") *value = ctx->wide;

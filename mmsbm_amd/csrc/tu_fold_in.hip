@@ -1,5 +1,5 @@
-// tu_fold_in.hip -- translation unit of fold-in (fold_in.hpp): the request's rows grouped by user, batches of users
-// within the scratch budget, the jobs of the two forms and their launches
+// tu_fold_in.hip -- translation unit of fold-in (fold_in.hpp), new users and new items alike: the request's rows grouped
+// by new user (item), batches within the scratch budget, the jobs of the two forms and their launches
 #include "prelude.hpp"
 #include "fold_in.hpp"
 
@@ -24,26 +24,34 @@ void fold_upload(DevBuf<T> &b, const T *h, size_t n, hipStream_t s) {
 
 }  // namespace
 
-void fold_in(mmsbm_hip_ctx *c, int64_t n_rows, const int32_t *user, const int32_t *item, const int32_t *rating,
-             int32_t n_new, int32_t n_iters, double tol, const double *theta0, double *theta, int32_t *iters) {
+namespace {
+
+// Both sides of fold-in (mmsbm_hip_fold_in / mmsbm_hip_fold_in_items): the new rows' own ids `own` in [0, n_new), the
+// fitted side's ids `other`.  Users: groups K, fixed rows the external items' eta, p as (k, l).  Items: groups L, fixed
+// rows the external users' theta, p read as (l, k) -- v_j[l] = sum_k p[k, l, r_j] theta[u_j, k] is fold_v_kernel with
+// the strides and the group counts exchanged.  Everything below is the same for both.
+void fold_side(mmsbm_hip_ctx *c, bool items_side, int64_t n_rows, const int32_t *own, const int32_t *other,
+               const int32_t *rating, int32_t n_new, int32_t n_iters, double tol, const double *x0, double *x,
+               int32_t *iters) {
   use_device(c);
-  const int K = c->ext_k, L = c->ext_l, code = fold_code(K), G = fold_lanes(code);
-  // rows grouped by user (counting sort; a user's rows keep the order of the request)
+  const int K = items_side ? c->ext_l : c->ext_k, L = items_side ? c->ext_k : c->ext_l;  // (own, fixed) group counts
+  const int code = fold_code(K), G = fold_lanes(code);
+  // rows grouped by new user / item ("user" below; counting sort; a user's rows keep the order of the request)
   std::vector<int64_t> off(static_cast<size_t>(n_new) + 1, 0);
-  for (int64_t m = 0; m < n_rows; ++m) off[static_cast<size_t>(user[m]) + 1]++;
+  for (int64_t m = 0; m < n_rows; ++m) off[static_cast<size_t>(own[m]) + 1]++;
   for (int32_t u = 0; u < n_new; ++u) off[u + 1] += off[u];
   std::vector<int32_t> it(static_cast<size_t>(n_rows)), rt(static_cast<size_t>(n_rows));
   {
     std::vector<int64_t> pos(off.begin(), off.end() - 1);
     for (int64_t m = 0; m < n_rows; ++m) {
-      const int64_t at = pos[user[m]]++;
-      it[at] = item[m];
+      const int64_t at = pos[own[m]]++;
+      it[at] = other[m];
       rt[at] = rating[m];
     }
   }
   const size_t nk = static_cast<size_t>(n_new) * K;
   std::vector<double> th0(nk);
-  if (theta0) std::copy(theta0, theta0 + nk, th0.begin());
+  if (x0) std::copy(x0, x0 + nk, th0.begin());
   else std::fill(th0.begin(), th0.end(), 1.0 / K);
   // batches: consecutive users whose v rows fit kFoldBatchBytes (a user beyond it: a batch of its own)
   const size_t row_b = static_cast<size_t>(K) * sizeof(double);
@@ -73,11 +81,15 @@ void fold_in(mmsbm_hip_ctx *c, int64_t n_rows, const int32_t *user, const int32_
   di.alloc(max_rows); dr.alloc(max_rows); dv.alloc(max_rows * K);
   doff.alloc(max_users + 1); dt0.alloc(max_users * K); dt.alloc(max_users * K); dn.alloc(max_users);
   jon.alloc(max_jobs); jst.alloc(max_jobs);
-  // external (k, l, r) of the slot's p, the external items' rows (internal users when swapped)
+  // external (k, l, r) of the slot's p (exchanged for items), the fixed side's external rows: the external items'
+  // (internal users when swapped) for users, the external users' (internal items when swapped) for items
   const int cur = c->cur, sl = c->sel;
-  const int ks = c->swapped ? 1 : c->lp, ls = c->swapped ? c->lp : 1;
+  const int pk = c->swapped ? 1 : c->lp, pl = c->swapped ? c->lp : 1;
+  const int ks = items_side ? pl : pk, ls = items_side ? pk : pl;
   const size_t prs = static_cast<size_t>(c->kp) * c->lp;
-  const RowTab et = c->swapped ? theta_tab(c, cur) : plain_tab(c->eta[cur].at(sl), c->lp);
+  const RowTab ut = c->swapped ? plain_tab(c->eta[cur].at(sl), c->lp) : theta_tab(c, cur);
+  const RowTab itab = c->swapped ? theta_tab(c, cur) : plain_tab(c->eta[cur].at(sl), c->lp);
+  const RowTab et = items_side ? ut : itab;
   float total_ms = 0.f;
   hipEvent_t e0, e1;
   HIP_CHECK(hipEventCreate(&e0));
@@ -148,7 +160,7 @@ void fold_in(mmsbm_hip_ctx *c, int64_t n_rows, const int32_t *user, const int32_
       for (int32_t b = 0; b < nb; ++b) {  // a user without rows: theta0 and 0 iterations
         const bool empty = boff[b + 1] == boff[b];
         const double *src = empty ? th0.data() + static_cast<size_t>(u0 + b) * K : ht.data() + static_cast<size_t>(b) * K;
-        std::copy(src, src + K, theta + static_cast<size_t>(u0 + b) * K);
+        std::copy(src, src + K, x + static_cast<size_t>(u0 + b) * K);
         if (iters) iters[u0 + b] = empty ? 0 : hn[b];
       }
     }
@@ -160,6 +172,18 @@ void fold_in(mmsbm_hip_ctx *c, int64_t n_rows, const int32_t *user, const int32_
   (void)hipEventDestroy(e0);
   (void)hipEventDestroy(e1);
   c->fold_last_ms = total_ms;
+}
+
+}  // namespace
+
+void fold_in(mmsbm_hip_ctx *c, int64_t n_rows, const int32_t *user, const int32_t *item, const int32_t *rating,
+             int32_t n_new, int32_t n_iters, double tol, const double *theta0, double *theta, int32_t *iters) {
+  fold_side(c, false, n_rows, user, item, rating, n_new, n_iters, tol, theta0, theta, iters);
+}
+
+void fold_in_items(mmsbm_hip_ctx *c, int64_t n_rows, const int32_t *user, const int32_t *item, const int32_t *rating,
+                   int32_t n_new, int32_t n_iters, double tol, const double *eta0, double *eta, int32_t *iters) {
+  fold_side(c, true, n_rows, item, user, rating, n_new, n_iters, tol, eta0, eta, iters);
 }
 
 }  // namespace mmsbm_hip_impl

@@ -71,6 +71,7 @@ void recommend_begin(mmsbm_hip_ctx *c, const double *weights, int exclude_train)
   }
   HIP_CHECK(hipStreamSynchronize(s));
   c->rc_rank = rec_rank(c);
+  c->rc_items = c->ext_items;
   c->rc_slots = 0;
 }
 
@@ -124,6 +125,74 @@ void recommend_add(mmsbm_hip_ctx *c) {  // the selected slot (the caller holds a
   c->rc_slots = S + 1;
 }
 
+void recommend_add_items(mmsbm_hip_ctx *c, int32_t n_new, const double *eta, const int64_t *seen_offsets,
+                         const int32_t *seen_users) {
+  use_device(c);
+  if (n_new == 0) return;
+  const int U = c->ext_users, I = c->ext_items, K = c->ext_k, L = c->ext_l, rank = c->rc_rank, S = c->rc_slots;
+  const int NI = I + n_new;
+  const size_t ys = static_cast<size_t>(I) * rank, nys = static_cast<size_t>(NI) * rank;
+  const size_t el = static_cast<size_t>(n_new) * L, kl = static_cast<size_t>(K) * L;
+  rec_require_mem(S * (nys + el) * sizeof(double), "the added items' factors");
+  hipStream_t st = c->stream;
+  // every slot's table grows from I to I + n_new rows: the training rows copied as they are, the new rows folded with
+  // the slot's W exactly as recommend_add folds the slot's own eta (y = eta W^T when K <= L, else y = eta)
+  DevBuf<double> ny, de;
+  DevBuf<int32_t> so, si;
+  ny.alloc(S * nys);
+  de.alloc(S * el);
+  HIP_CHECK(hipMemcpyAsync(de.ptr, eta, sizeof(double) * S * el, hipMemcpyHostToDevice, st));
+  const size_t nr = static_cast<size_t>(n_new) * rank;
+  for (int s = 0; s < S; ++s) {
+    if (ys > 0)
+      HIP_CHECK(hipMemcpyAsync(ny.ptr + s * nys, c->rc_y.ptr + s * ys, sizeof(double) * ys, hipMemcpyDeviceToDevice, st));
+    const double *m = K <= L ? c->rc_wk.ptr + s * kl : nullptr;
+    LAUNCH(rec_fold_kernel, static_cast<unsigned>((nr + kBlock - 1) / kBlock), kBlock, 0, st,
+           plain_tab(de.ptr + s * el, L), L, m, 1, L, ny.ptr + s * nys + ys, n_new, rank);
+  }
+  HIP_CHECK(hipGetLastError());
+  // the seen pairs: user u also leaves out the new items whose list names it.  A user's list stays ascending and
+  // distinct: its training items (< I) first, then its new items (>= I), sorted and de-duplicated.
+  const int64_t n_seen = seen_offsets ? seen_offsets[n_new] : 0;  // (checked: below 2^31)
+  if (n_seen > 0) {
+    std::vector<int32_t> old_off = c->rc_excl ? c->rc_seen_off_h : std::vector<int32_t>(static_cast<size_t>(U) + 1, 0);
+    std::vector<int32_t> old(static_cast<size_t>(old_off[U]));
+    if (!old.empty())
+      HIP_CHECK(hipMemcpyAsync(old.data(), c->rc_seen.ptr, sizeof(int32_t) * old.size(), hipMemcpyDeviceToHost, st));
+    // the new pairs grouped by user (counting sort)
+    std::vector<int32_t> noff(static_cast<size_t>(U) + 1, 0), nit(static_cast<size_t>(n_seen));
+    for (int64_t e = 0; e < n_seen; ++e) noff[static_cast<size_t>(seen_users[e]) + 1]++;
+    for (int u = 0; u < U; ++u) noff[u + 1] += noff[u];
+    {
+      std::vector<int32_t> pos(noff.begin(), noff.end() - 1);
+      for (int32_t j = 0; j < n_new; ++j)
+        for (int64_t e = seen_offsets[j]; e < seen_offsets[j + 1]; ++e) nit[static_cast<size_t>(pos[seen_users[e]]++)] = I + j;
+    }
+    HIP_CHECK(hipStreamSynchronize(st));
+    std::vector<int32_t> off(static_cast<size_t>(U) + 1, 0), item;
+    item.reserve(old.size() + static_cast<size_t>(n_seen));
+    for (int u = 0; u < U; ++u) {
+      off[u] = static_cast<int32_t>(item.size());
+      item.insert(item.end(), old.begin() + old_off[u], old.begin() + old_off[u + 1]);
+      const size_t a = item.size();
+      item.insert(item.end(), nit.begin() + noff[u], nit.begin() + noff[u + 1]);
+      std::sort(item.begin() + a, item.end());
+      item.erase(std::unique(item.begin() + a, item.end()), item.end());
+    }
+    off[U] = static_cast<int32_t>(item.size());
+    so.upload(off, st);
+    si.upload(item, st);
+    HIP_CHECK(hipStreamSynchronize(st));  // (host vectors are locals)
+    std::swap(c->rc_seen_off.ptr, so.ptr); std::swap(c->rc_seen_off.count, so.count);
+    std::swap(c->rc_seen.ptr, si.ptr); std::swap(c->rc_seen.count, si.count);
+    c->rc_seen_off_h = off;
+    c->rc_excl = true;
+  }
+  HIP_CHECK(hipStreamSynchronize(st));
+  std::swap(c->rc_y.ptr, ny.ptr); std::swap(c->rc_y.count, ny.count);
+  c->rc_items = NI;
+}
+
 namespace {
 
 // users per batch: a score buffer of ~128 MB, whole 128-user tiles where that allows
@@ -134,11 +203,11 @@ int64_t rec_batch_users(int I, int64_t n_users) {
   return std::min(bu, n_users);
 }
 
-// The scores of one batch of nb users ub (device ids, rows of x) into sc [nb][I]; seen_off / seen (device, indexed by
+// The scores of one batch of nb users ub (device ids, rows of x) into sc [nb][I] (I: the session's catalogue); seen_off / seen (device, indexed by
 // those ids): the items set to -inf, or null.  Shared by the selection (rec_run) and the positions.
 void rec_score_batch(mmsbm_hip_ctx *c, const double *x, size_t xs, const int32_t *ub, int nb, const int32_t *seen_off,
                      const int32_t *seen, double *sc) {
-  const int I = c->ext_items, rank = c->rc_rank, S = c->rc_slots;
+  const int I = c->rc_items, rank = c->rc_rank, S = c->rc_slots;
   if (I == 0) return;
   hipStream_t st = c->stream;
   const dim3 g(static_cast<unsigned>((I + kRecTile - 1) / kRecTile), static_cast<unsigned>((nb + kRecTile - 1) / kRecTile));
@@ -159,7 +228,7 @@ void rec_run(mmsbm_hip_ctx *c, const double *x, size_t xs, int64_t n_users, cons
     }
   }
   if (n_users == 0) return;
-  const int I = c->ext_items;
+  const int I = c->rc_items;
   hipStream_t st = c->stream;
 
   const int64_t bu = rec_batch_users(I, n_users);
@@ -278,7 +347,7 @@ void recommend_query_theta(mmsbm_hip_ctx *c, int64_t n_users, const double *thet
 void recommend_positions(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, const int64_t *offsets,
                          const int32_t *items, int32_t *positions, int32_t *candidates) {
   use_device(c);
-  const int I = c->ext_items, rank = c->rc_rank;
+  const int I = c->rc_items, rank = c->rc_rank;
   const int64_t total = n_users > 0 ? offsets[n_users] : 0;  // (checked: below 2^31)
   for (int64_t b = 0; b < n_users && candidates; ++b) {
     const int32_t u = users[b];

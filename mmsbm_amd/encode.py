@@ -158,6 +158,18 @@ class Encoder:
         out[:, 0], out[:, 1] = ids[0][keep], ids[1][keep]
         return out, keep
 
+    def transform_users(self, data, logger=None):
+        """transform for the user and rating columns alone (the item column is not looked at): ((M, 2) int32 ids
+        [user, rating] of the rows kept, the (N,) mask of those rows).  Rows with an unseen user or rating are dropped
+        with transform's warning."""
+        if self.labels is None:
+            raise AssertionError("encoder has not seen training data")
+        cols, _ = _columns(data)
+        ids, keep = self._encode(cols, (0, 2), logger)
+        out = np.empty((int(keep.sum()), 2), dtype=np.int32)
+        out[:, 0], out[:, 1] = ids[0][keep], ids[1][keep]
+        return out, keep
+
     def _encode(self, cols, which, logger):
         """ids of columns `which` against the training dictionaries, and the mask of the rows all of them know"""
         keep = np.ones(len(cols[0]), dtype=bool)

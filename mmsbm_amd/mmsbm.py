@@ -295,23 +295,7 @@ class MMSBM:
         self._check_whole_model()
         n, w = self._recommend_args(n, weights)
         enc = self.data_handler
-        n_users = self.p + 1
-        if users is None:
-            ids = np.arange(n_users, dtype=np.int32)
-            labels = np.asarray(enc.user_labels(), dtype=object) if enc else ids
-        else:
-            labels = np.asarray(list(users), dtype=object)
-            if enc:
-                index = {lab: j for j, lab in enumerate(enc.user_labels())}
-                found = [index.get(str(x), -1) for x in labels]
-            else:
-                found = [int(x) if isinstance(x, (int, np.integer)) and 0 <= int(x) < n_users else -1 for x in labels]
-            ids = np.asarray(found, dtype=np.int32)
-            if (ids < 0).any():
-                missing = list(dict.fromkeys(labels[ids < 0].tolist()))
-                raise KeyError(f"users not in the training data: {missing}")
-            if enc:  # the encoder's labels, as with users=None (7 and "7" are one user; the frames join on "users")
-                labels = np.asarray(enc.user_labels(), dtype=object)[ids]
+        ids, labels = self._training_users(users)
         item_labels = np.asarray(enc.item_labels(), dtype=object) if enc else None
 
         dev = self._device_list()[0]
@@ -346,6 +330,28 @@ class MMSBM:
         if not parts:
             return pd.DataFrame({"users": [], "items": [], "score": np.zeros(0), "rank": np.zeros(0, dtype=np.int64)})
         return pd.concat(parts, ignore_index=True)
+
+    def _training_users(self, users):
+        """(encoded ids int32, labels) of recommend's ``users`` argument (None: every training user)."""
+        enc = self.data_handler
+        n_users = self.p + 1
+        if users is None:
+            ids = np.arange(n_users, dtype=np.int32)
+            labels = np.asarray(enc.user_labels(), dtype=object) if enc else ids
+        else:
+            labels = np.asarray(list(users), dtype=object)
+            if enc:
+                index = {lab: j for j, lab in enumerate(enc.user_labels())}
+                found = [index.get(str(x), -1) for x in labels]
+            else:
+                found = [int(x) if isinstance(x, (int, np.integer)) and 0 <= int(x) < n_users else -1 for x in labels]
+            ids = np.asarray(found, dtype=np.int32)
+            if (ids < 0).any():
+                missing = list(dict.fromkeys(labels[ids < 0].tolist()))
+                raise KeyError(f"users not in the training data: {missing}")
+            if enc:  # the encoder's labels, as with users=None (7 and "7" are one user; the frames join on "users")
+                labels = np.asarray(enc.user_labels(), dtype=object)[ids]
+        return ids, labels
 
     def _check_whole_model(self):
         self._check_is_fitted()
@@ -497,46 +503,61 @@ class MMSBM:
         ``data`` is new (the training theta is never consulted); items and ratings are encoded against the training
         dictionaries, and rows with an unseen item or rating are dropped with ``Encoder.transform``'s warning.  A user
         whose rows are all dropped keeps its place (uniform theta, no iterations)."""
+        return self._encode_new(data, 0)
+
+    def _encode_new_items(self, data):
+        """(rows (N, 3) int32 [user, new item, rating], item labels in order of first appearance): _encode_new_users
+        with the roles of users and items exchanged (the training eta is never consulted)."""
+        return self._encode_new(data, 1)
+
+    def _encode_new(self, data, side):
+        """Column ``side`` (0: users, 1: items) of ``data`` holds new entities, numbered by first appearance; the other
+        two columns are encoded against the training dictionaries."""
         import pandas as pd
         from .encode import _columns
         cols, _ = _columns(data)
-        users = np.asarray(cols[0])
+        own = np.asarray(cols[side])
+        fixed = 1 - side
+        names = ("users", "items")
         enc = self.data_handler
         if enc:  # labels as the encoder makes them: str(value)
-            if users.dtype.kind in "iu":
-                codes, uniq = pd.factorize(users)
+            if own.dtype.kind in "iu":
+                codes, uniq = pd.factorize(own)
             else:
-                if any(v is None or (isinstance(v, float) and v != v) for v in users.tolist()):
+                if any(v is None or (isinstance(v, float) and v != v) for v in own.tolist()):
                     raise AssertionError("Data contains missing values. Aborting.")
-                codes, uniq = pd.factorize(np.array([str(v) for v in users.tolist()], dtype=object))
+                codes, uniq = pd.factorize(np.array([str(v) for v in own.tolist()], dtype=object))
             labels = np.array([str(v) for v in np.asarray(uniq).tolist()], dtype=object)
-            rows, keep = enc.transform_items(data, self.logger)
+            rows, keep = (enc.transform_items if side == 0 else enc.transform_users)(data, self.logger)
         else:
-            if len(users) and (not np.issubdtype(users.dtype, np.integer) or users.min() < 0):
-                raise ValueError("after fit_encoded the user column holds non-negative integer ids")
-            codes, uniq = pd.factorize(users.astype(np.int64))
+            if len(own) and (not np.issubdtype(own.dtype, np.integer) or own.min() < 0):
+                raise ValueError(f"after fit_encoded the {names[side][:-1]} column holds non-negative integer ids")
+            codes, uniq = pd.factorize(own.astype(np.int64))
             labels = np.asarray(uniq, dtype=np.int64)
-            item, rating = (np.asarray(c) for c in cols[1:])
-            for name, col in (("items", item), ("ratings", rating)):
+            other, rating = np.asarray(cols[fixed]), np.asarray(cols[2])
+            for name, col in ((names[fixed], other), ("ratings", rating)):
                 if len(col) and not np.issubdtype(col.dtype, np.integer):
                     raise ValueError(f"after fit_encoded the {name} column holds encoded integer ids")
-            keep = np.ones(len(users), dtype=bool)
-            for name, col, top in (("items", item, self.m + 1), ("ratings", rating, len(self.ratings))):
+            keep = np.ones(len(own), dtype=bool)
+            tops = (self.m + 1, self.p + 1)
+            for name, col, top in ((names[fixed], other, tops[side]), ("ratings", rating, len(self.ratings))):
                 bad = keep & ((col < 0) | (col >= top))
                 unseen = np.unique(col[bad])
                 if len(unseen):
                     self.logger.warning(f"The {name} {', '.join(str(v) for v in unseen.tolist())} are in the test set "
                                         f"but weren't in the train set so I'll remove them.")
                 keep &= ~bad
-            rows = np.stack([item[keep], rating[keep]], 1).astype(np.int32)
+            rows = np.stack([other[keep], rating[keep]], 1).astype(np.int32)
         out = np.empty((int(keep.sum()), 3), dtype=np.int32)
-        out[:, 0] = np.asarray(codes)[keep]
-        out[:, 1:] = rows
+        out[:, side] = np.asarray(codes)[keep]
+        out[:, fixed] = rows[:, 0]
+        out[:, 2] = rows[:, 1]
         return out, labels
 
-    def _fold_runs(self, rows, n_new, iterations, tol, each=None):
-        """theta (n_new, K) and the iterations used of every restart, in ``self.results`` order; ``each(ctx)`` runs
-        after each restart's fold-in while its parameters are selected (recommend_new adds the slot there)."""
+    def _fold_runs(self, rows, n_new, iterations, tol, each=None, items=False):
+        """theta (n_new, K) -- eta (n_new, L) with ``items`` -- and the iterations used of every restart, in
+        ``self.results`` order; ``each(ctx)`` runs after each restart's fold-in while its parameters are selected
+        (recommend_new adds the slot there)."""
         dev = self._device_list()[0]
         ctx = self._ctx(dev)
         resident = self._resident.get((dev, 0)) == list(self._restart_ids) and ctx.slots == len(self.results)
@@ -549,7 +570,7 @@ class MMSBM:
                 ctx.select(j)
             else:
                 ctx.set_params(a["theta"], a["eta"], a["pr"])
-            t, it = ctx.fold_in(rows, n_new, iterations, tol)
+            t, it = (ctx.fold_in_items if items else ctx.fold_in)(rows, n_new, iterations, tol)
             thetas.append(t)
             iters.append(it)
             if each is not None:
@@ -621,6 +642,81 @@ class MMSBM:
                 parts.append(pd.DataFrame({
                     "users": labels[at] if len(at) else np.empty(0, dtype=object),
                     "items": item_labels[it] if item_labels is not None else it.astype(np.int64),
+                    "score": scores[keep],
+                    "rank": np.nonzero(keep)[1].astype(np.int64) + 1}))
+        finally:
+            ctx.recommend_end()
+        if not parts:
+            return pd.DataFrame({"users": [], "items": [], "score": np.zeros(0), "rank": np.zeros(0, dtype=np.int64)})
+        return pd.concat(parts, ignore_index=True)
+
+    def fold_in_items(self, data, iterations=100, tol=None):
+        """eta of items that were not in the training data, from their ratings: ``iterations`` steps of the eta half of
+        the M-step with every restart's theta and p held fixed, from a uniform start (``tol`` as in ``fold_in``).
+        ``data``: users, items, ratings like ``fit``'s; every item of it is new (the training eta is never consulted),
+        users and ratings are encoded against the training dictionaries and rows with an unseen user or rating are
+        dropped with ``predict``'s warning (after ``fit_encoded``: integer triples, items as any non-negative ids, users
+        and ratings encoded).
+
+        Returns a list of DataFrames, one per restart in ``self.results`` order, each (new items x L) indexed by the
+        item labels in order of first appearance in ``data``.  ``self.fold_in_items_iterations``: a DataFrame (new
+        items x restarts) of the iterations each item ran.  The model itself is left as it is."""
+        import pandas as pd
+        self._check_whole_model()
+        iterations, tol = self._fold_args(iterations, tol)
+        rows, labels = self._encode_new_items(data)
+        _, etas, iters = self._fold_runs(rows, len(labels), iterations, tol, items=True)
+        index = pd.Index(labels, name="items") if len(labels) else pd.Index([], name="items")
+        self.fold_in_items_iterations = pd.DataFrame(np.stack(iters, 1) if iters else np.zeros((len(labels), 0)),
+                                                     index=index)
+        return [pd.DataFrame(e, index=index) for e in etas]
+
+    def recommend_with_new_items(self, data, users=None, n=10, exclude_seen=True, weights=None, iterations=100,
+                                 tol=None):
+        """``recommend`` over the training items plus the new items of ``data``: each restart scores the new items with
+        the eta its own ``fold_in_items`` gives them (same arguments), the scores are averaged over the restarts.
+        Returns the frame ``recommend`` returns (users, items, score, rank) for training users (``users`` as in
+        ``recommend``); ``exclude_seen`` leaves out a user's training items and the new items the user rated in
+        ``data``.  An item label of ``data`` that is also a training item is refused (ValueError)."""
+        import pandas as pd
+        self._check_whole_model()
+        n, w = self._recommend_args(n, weights)
+        iterations, tol = self._fold_args(iterations, tol)
+        rows, labels = self._encode_new_items(data)
+        enc = self.data_handler
+        n_items = self.m + 1
+        if enc:
+            train_items = np.asarray(enc.item_labels(), dtype=object)
+            known = set(train_items.tolist())
+            clash = [x for x in labels.tolist() if x in known]
+            item_labels = np.concatenate([train_items, labels]).astype(object)
+        else:
+            clash = [x for x in labels.tolist() if x < n_items]
+            item_labels = np.concatenate([np.arange(n_items, dtype=np.int64), labels]).astype(np.int64)
+        if clash:
+            raise ValueError(f"items of data are training items, so the frame would be ambiguous: {clash[:10]}")
+        ids, user_labels = self._training_users(users)
+        n_new = len(labels)
+        ctx = self._ctx(self._device_list()[0])
+        parts = []
+        ctx.recommend_begin(w, exclude_seen)
+        try:
+            _, etas, iters = self._fold_runs(rows, n_new, iterations, tol, each=lambda c: c.recommend_add(), items=True)
+            self.fold_in_items_iterations = pd.DataFrame(np.stack(iters, 1), index=pd.Index(labels, name="items"))
+            seen = None
+            if exclude_seen:  # the training users that rated each new item
+                order = np.argsort(rows[:, 1], kind="stable")
+                counts = np.bincount(rows[:, 1], minlength=n_new)
+                seen = (np.concatenate([[0], np.cumsum(counts)]).astype(np.int64), rows[order, 0])
+            ctx.recommend_add_items(np.stack(etas), seen)
+            step = max(1, self.RECOMMEND_BATCH_ROWS // n)
+            for b in range(0, len(ids), step):
+                items, scores, counts = ctx.recommend_query(ids[b:b + step], n)
+                keep = np.arange(n)[None, :] < counts[:, None]
+                at = np.repeat(np.arange(b, b + len(counts)), counts)
+                parts.append(pd.DataFrame({
+                    "users": user_labels[at] if len(at) else np.empty(0, dtype=object),
+                    "items": item_labels[items[keep]],
                     "score": scores[keep],
                     "rank": np.nonzero(keep)[1].astype(np.int64) + 1}))
         finally:
