@@ -25,6 +25,18 @@ def _p(a, ctype):
     return a.ctypes.data_as(C.POINTER(ctype))
 
 
+def _csr(offsets, values, rows, name, noun):
+    """(offsets int64, values int32) of a CSR argument over ``rows`` rows, its ``name`` and the ``noun`` of its values
+    in the shape and end checks."""
+    off = np.ascontiguousarray(offsets, dtype=np.int64)
+    val = _i32(values)
+    if off.shape != (rows + 1,):
+        raise ValueError(f"{name} have shape {off.shape}, expected ({rows + 1},)")
+    if off[-1] != len(val):
+        raise ValueError(f"{name} end at {int(off[-1])}, {noun} holds {len(val)}")
+    return off, val
+
+
 def normalize_with_self(p):
     """p[k,l,:] /= sum_r p[k,l,r]; zero rows stay zero (src/expectation_maximization.py:152-155).
     Host-side, used for the random initialisation only."""
@@ -113,6 +125,7 @@ class HipEM:
         _lib.call("mmsbm_hip_dims", self._h, dims)
         self.n_pairs, self.swapped = int(dims[6]), bool(dims[7])
         self.slots = 1
+        self._rc_added = 0
         if int(slots) != 1:
             self.set_slots(slots)
 
@@ -321,13 +334,17 @@ class HipEM:
         _lib.call("mmsbm_hip_recommend_add", self._h)
         self._rc_added += 1
 
+    @staticmethod
+    def _query_out(m, n):
+        """Empty (items, scores, counts) of a query of m users."""
+        return (np.empty((m, max(n, 0)), dtype=np.int32), np.empty((m, max(n, 0)), dtype=np.float64),
+                np.empty(m, dtype=np.int32))
+
     def recommend_query(self, users, n):
         """(items (M,n) int32 padded with -1, scores (M,n) padded with -inf, counts (M,)) for encoded user ids."""
         u = _i32(users)
         n = int(n)
-        items = np.empty((len(u), max(n, 0)), dtype=np.int32)
-        scores = np.empty((len(u), max(n, 0)), dtype=np.float64)
-        counts = np.empty(len(u), dtype=np.int32)
+        items, scores, counts = self._query_out(len(u), n)
         _lib.call("mmsbm_hip_recommend_query", self._h, len(u), _p(u, C.c_int32), n, _p(items, C.c_int32),
                   _p(scores, C.c_double), _p(counts, C.c_int32))
         return items, scores, counts
@@ -339,18 +356,11 @@ class HipEM:
         t = _f64(theta)
         if t.ndim != 3 or t.shape[2] != self.k:
             raise ValueError(f"theta has shape {t.shape}, expected (slots, users, {self.k})")
-        if t.shape[0] != getattr(self, "_rc_added", 0):
-            raise ValueError(f"theta holds {t.shape[0]} blocks, the session {getattr(self, '_rc_added', 0)} added slots")
+        if t.shape[0] != self._rc_added:
+            raise ValueError(f"theta holds {t.shape[0]} blocks, the session {self._rc_added} added slots")
         m, n = t.shape[1], int(n)
-        off = it = None
-        if seen is not None:
-            off = np.ascontiguousarray(seen[0], dtype=np.int64)
-            it = _i32(seen[1])
-            if off.shape != (m + 1,):
-                raise ValueError(f"seen offsets have shape {off.shape}, expected ({m + 1},)")
-        items = np.empty((m, max(n, 0)), dtype=np.int32)
-        scores = np.empty((m, max(n, 0)), dtype=np.float64)
-        counts = np.empty(m, dtype=np.int32)
+        off, it = (None, None) if seen is None else _csr(seen[0], seen[1], m, "seen offsets", "items")
+        items, scores, counts = self._query_out(m, n)
         _lib.call("mmsbm_hip_recommend_query_theta", self._h, m, _p(t, C.c_double),
                   None if off is None else _p(off, C.c_int64), None if it is None else _p(it, C.c_int32), n,
                   _p(items, C.c_int32), _p(scores, C.c_double), _p(counts, C.c_int32))
@@ -361,12 +371,7 @@ class HipEM:
         order within the open session -- user b's items are items[offsets[b]:offsets[b + 1]] -- and each user's
         number of candidates.  positions: (offsets[-1],) int32; candidates: (len(users),) int32."""
         u = _i32(users)
-        off = np.ascontiguousarray(offsets, dtype=np.int64)
-        it = _i32(items)
-        if off.shape != (len(u) + 1,):
-            raise ValueError(f"offsets have shape {off.shape}, expected ({len(u) + 1},)")
-        if off[-1] != len(it):
-            raise ValueError(f"offsets end at {int(off[-1])}, items holds {len(it)}")
+        off, it = _csr(offsets, items, len(u), "offsets", "items")
         positions = np.empty(len(it), dtype=np.int32)
         candidates = np.empty(len(u), dtype=np.int32)
         _lib.call("mmsbm_hip_recommend_positions", self._h, len(u), _p(u, C.c_int32), _p(off, C.c_int64),
@@ -381,17 +386,10 @@ class HipEM:
         e = _f64(eta)
         if e.ndim != 3 or e.shape[2] != self.l:
             raise ValueError(f"eta has shape {e.shape}, expected (slots, items, {self.l})")
-        if e.shape[0] != getattr(self, "_rc_added", 0):
-            raise ValueError(f"eta holds {e.shape[0]} blocks, the session {getattr(self, '_rc_added', 0)} added slots")
+        if e.shape[0] != self._rc_added:
+            raise ValueError(f"eta holds {e.shape[0]} blocks, the session {self._rc_added} added slots")
         n_new = e.shape[1]
-        off = us = None
-        if seen is not None:
-            off = np.ascontiguousarray(seen[0], dtype=np.int64)
-            us = _i32(seen[1])
-            if off.shape != (n_new + 1,):
-                raise ValueError(f"seen offsets have shape {off.shape}, expected ({n_new + 1},)")
-            if off[-1] != len(us):
-                raise ValueError(f"seen offsets end at {int(off[-1])}, users holds {len(us)}")
+        off, us = (None, None) if seen is None else _csr(seen[0], seen[1], n_new, "seen offsets", "users")
         _lib.call("mmsbm_hip_recommend_add_items", self._h, n_new, _p(e, C.c_double),
                   None if off is None else _p(off, C.c_int64), None if us is None else _p(us, C.c_int32))
 
@@ -405,37 +403,29 @@ class HipEM:
         """theta (n_new, K) of new users 0 .. n_new-1 under the selected slot's eta and p, and the iterations each ran
         (n_new,).  rows: (N, 3) [new user, item, rating] (encoded item and rating ids).  tol None: all iterations;
         theta0 None: uniform 1/K.  The slot is left unchanged."""
-        u, i, r = split_triples(rows)
-        n_new = int(n_new)
-        t0 = None
-        if theta0 is not None:
-            t0 = _f64(theta0)
-            if t0.shape != (n_new, self.k):
-                raise ValueError(f"theta0 has shape {t0.shape}, expected ({n_new}, {self.k})")
-        theta = np.empty((n_new, self.k), dtype=np.float64)
-        iters = np.empty(n_new, dtype=np.int32)
-        _lib.call("mmsbm_hip_fold_in", self._h, len(u), _p(u, C.c_int32), _p(i, C.c_int32), _p(r, C.c_int32),
-                  n_new, int(iterations), -1.0 if tol is None else float(tol),
-                  None if t0 is None else _p(t0, C.c_double), _p(theta, C.c_double), _p(iters, C.c_int32))
-        return theta, iters
+        return self._fold("mmsbm_hip_fold_in", self.k, "theta0", rows, n_new, iterations, tol, theta0)
 
     def fold_in_items(self, rows, n_new, iterations, tol=None, eta0=None):
         """eta (n_new, L) of new items 0 .. n_new-1 under the selected slot's theta and p, and the iterations each ran
         (n_new,).  rows: (N, 3) [user, new item, rating] (encoded user and rating ids, training data's column order).
         tol None: all iterations; eta0 None: uniform 1/L.  The slot is left unchanged."""
+        return self._fold("mmsbm_hip_fold_in_items", self.l, "eta0", rows, n_new, iterations, tol, eta0)
+
+    def _fold(self, symbol, groups, start_name, rows, n_new, iterations, tol, start):
+        """fold_in / fold_in_items through ABI entry ``symbol``: rows of ``groups`` columns, ``start`` (named
+        ``start_name``) or None."""
         u, i, r = split_triples(rows)
         n_new = int(n_new)
-        e0 = None
-        if eta0 is not None:
-            e0 = _f64(eta0)
-            if e0.shape != (n_new, self.l):
-                raise ValueError(f"eta0 has shape {e0.shape}, expected ({n_new}, {self.l})")
-        eta = np.empty((n_new, self.l), dtype=np.float64)
+        if start is not None:
+            start = _f64(start)
+            if start.shape != (n_new, groups):
+                raise ValueError(f"{start_name} has shape {start.shape}, expected ({n_new}, {groups})")
+        out = np.empty((n_new, groups), dtype=np.float64)
         iters = np.empty(n_new, dtype=np.int32)
-        _lib.call("mmsbm_hip_fold_in_items", self._h, len(u), _p(u, C.c_int32), _p(i, C.c_int32), _p(r, C.c_int32),
+        _lib.call(symbol, self._h, len(u), _p(u, C.c_int32), _p(i, C.c_int32), _p(r, C.c_int32),
                   n_new, int(iterations), -1.0 if tol is None else float(tol),
-                  None if e0 is None else _p(e0, C.c_double), _p(eta, C.c_double), _p(iters, C.c_int32))
-        return eta, iters
+                  None if start is None else _p(start, C.c_double), _p(out, C.c_double), _p(iters, C.c_int32))
+        return out, iters
 
     # -- measurement -------------------------------------------------------------------------
     def time_iterations(self, n_iters):

@@ -70,6 +70,11 @@ struct DevBuf {
     if (!h.empty())
       HIP_CHECK(hipMemcpyAsync(ptr, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, s));
   }
+  void swap(DevBuf &o) {
+    using std::swap;
+    swap(ptr, o.ptr);
+    swap(count, o.count);
+  }
 };
 
 // A per-restart table: `slots` copies, `stride` doubles apart (whole 128-byte lines, so every
@@ -109,6 +114,19 @@ struct PinBuf {
     used += n;
     return r;
   }
+};
+
+// The recommend session (mmsbm_hip_recommend_begin .. end; recommend.hpp): the slots' folded factors, external sides.
+// Created by recommend_begin, dropped whole by recommend_begin and recommend_end.
+struct RecSession {
+  DevBuf<double> x, y, w;               // [slot][U][rank], [slot][items][rank], the R rating weights
+  DevBuf<double> wk;                    // [slot][K][L]: each slot's W (recommend_query_theta folds caller rows)
+  DevBuf<int32_t> seen_off, seen;       // per external user: its distinct excluded items, ascending (excl)
+  std::vector<int32_t> seen_off_h;      // seen_off on the host (candidate counts of recommend_positions)
+  int slots = 0;                        // slots added
+  int items = 0;                        // the session's catalogue: I, or I + n_new after recommend_add_items
+  int rank = 0;
+  bool excl = false;                    // seen_* in use: exclude_train, or seen lists of recommend_add_items
 };
 
 }  // namespace mmsbm_hip_impl
@@ -220,15 +238,7 @@ struct mmsbm_hip_ctx {
   DevBuf<double> ps_sum, ps_w, ps_part;
   int64_t ps_rows = -1;  // -1: no session open
   int ps_added = 0;
-  // recommend session (mmsbm_hip_recommend_begin .. end; recommend.hpp): the slots' folded factors, external sides
-  DevBuf<double> rc_x, rc_y, rc_w;          // [slot][U][rank], [slot][rc_items][rank], the R rating weights
-  DevBuf<double> rc_wk;                     // [slot][K][L]: each slot's W (recommend_query_theta folds caller rows)
-  DevBuf<int32_t> rc_seen_off, rc_seen;     // per external user: its distinct excluded items, ascending (rc_excl)
-  std::vector<int32_t> rc_seen_off_h;       // rc_seen_off on the host (candidate counts of recommend_positions)
-  int rc_slots = -1;                        // slots added; -1: no session open
-  int rc_items = 0;                         // the session's catalogue: I, or I + n_new after recommend_add_items
-  int rc_rank = 0;
-  bool rc_excl = false;                     // rc_seen_* in use: exclude_train, or seen lists of recommend_add_items
+  std::unique_ptr<mmsbm_hip_impl::RecSession> rc;  // the open recommend session; null: none
   float rc_last_ms = 0.f;                   // device time of the last query's kernels (option "recommend_ms")
   float fold_last_ms = 0.f;                 // device time of the last fold-in's kernels, either side ("fold_in_ms")
   float pos_last_ms = 0.f;                  // device time of the last recommend_positions (option "position_ms")
@@ -288,6 +298,25 @@ struct LaunchScope {
 };
 
 void use_device(const mmsbm_hip_ctx *c) { HIP_CHECK(hipSetDevice(c->device)); }
+
+// Device time between two points of a stream: start() and stop() record, ms() reads it once the stream has passed
+// stop().  The events are destroyed on every way out of the scope.
+struct EventPair {
+  struct Event {
+    hipEvent_t e = nullptr;
+    Event() { HIP_CHECK(hipEventCreate(&e)); }
+    Event(const Event &) = delete;
+    Event &operator=(const Event &) = delete;
+    ~Event() { (void)hipEventDestroy(e); }
+  } e0, e1;
+  void start(hipStream_t s) { HIP_CHECK(hipEventRecord(e0.e, s)); }
+  void stop(hipStream_t s) { HIP_CHECK(hipEventRecord(e1.e, s)); }
+  float ms() const {
+    float v = 0.f;
+    HIP_CHECK(hipEventElapsedTime(&v, e0.e, e1.e));
+    return v;
+  }
+};
 
 
 }  // namespace

@@ -36,6 +36,8 @@ int score_rows_launch(mmsbm_hip_ctx *c, bool finish);  // the per-row scoring ke
 int score_stats_count();
 
 // tu_recommend.hip -- top-N recommendation (recommend.hpp): the session of mmsbm_hip_recommend_*, arguments checked
+// MMSBM_E_TOOLARGE "<what> needs ... MB of device memory" unless `bytes` (plus 64 MB) are free (fold-in too)
+void require_free_mem(size_t bytes, const std::string &what);
 void recommend_begin(mmsbm_hip_ctx *c, const double *weights, int exclude_train);
 void recommend_add(mmsbm_hip_ctx *c);  // the selected slot (the caller holds a OneSlot)
 void recommend_query(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, int n, int32_t *items, double *scores,
@@ -48,12 +50,11 @@ void recommend_add_items(mmsbm_hip_ctx *c, int32_t n_new, const double *eta, con
                          const int32_t *seen_users);
 void recommend_end(mmsbm_hip_ctx *c);
 
-// tu_fold_in.hip -- fold new users (new items) into the selected slot's fitted eta (theta) and p (fold_in.hpp),
-// arguments checked; fold_in_items: item[m] in [0, n_new), user[m] in [0, U)
-void fold_in(mmsbm_hip_ctx *c, int64_t n_rows, const int32_t *user, const int32_t *item, const int32_t *rating,
-             int32_t n_new, int32_t n_iters, double tol, const double *theta0, double *theta, int32_t *iters);
-void fold_in_items(mmsbm_hip_ctx *c, int64_t n_rows, const int32_t *user, const int32_t *item, const int32_t *rating,
-                   int32_t n_new, int32_t n_iters, double tol, const double *eta0, double *eta, int32_t *iters);
+// tu_fold_in.hip -- fold new users (items_side: new items) into the selected slot's fitted eta (theta) and p
+// (fold_in.hpp), arguments checked; x0, x: theta0, theta (eta0, eta); items_side: item[m] in [0, n_new), user[m] in [0, U)
+void fold_in(mmsbm_hip_ctx *c, bool items_side, int64_t n_rows, const int32_t *user, const int32_t *item,
+             const int32_t *rating, int32_t n_new, int32_t n_iters, double tol, const double *x0, double *x,
+             int32_t *iters);
 
 // dispatchers (mmsbm_hip.hip): the form the context's shape and options select
 void stage_dense(mmsbm_hip_ctx *c);

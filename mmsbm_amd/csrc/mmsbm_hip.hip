@@ -1267,6 +1267,73 @@ int mmsbm_hip_predict_finish(mmsbm_hip_ctx *ctx, double *mean_dist, double stats
   });
 }
 
+namespace {
+// The open recommend session; with `what` (the entry asking) also at least one slot added to it
+void require_session(const mmsbm_hip_ctx *ctx, const char *what) {
+  if (!ctx) throw std::invalid_argument("null context");
+  if (!ctx->rc) throw std::invalid_argument("recommend_begin has not been called");
+  if (what && ctx->rc->slots == 0) throw std::invalid_argument(std::string(what) + " before any recommend_add");
+}
+
+void require_n(int32_t n) {  // the n of a top-N query
+  if (n < 1) throw std::invalid_argument("recommend: n must be at least 1");
+  if (n > MMSBM_HIP_RECOMMEND_MAX_N)
+    throw ApiError(MMSBM_E_UNSUPPORTED, "recommend: n = " + std::to_string(n) + " is beyond the " +
+                                            std::to_string(MMSBM_HIP_RECOMMEND_MAX_N) + " items a query returns at most");
+}
+
+// A CSR argument of `rows` ranges (none when off is null): off[0] == 0, never decreasing, a total below 2^31 and
+// val[0 .. total) in [0, top).  Messages "<who>: <off_name>[0] must be 0", "<who>: <off_name> decrease at <row> b",
+// "<who>: more than 2^31 - 1 <vals>", "<who>: <val_name> out of range at entry e".
+void check_csr(const int64_t *off, const int32_t *val, int64_t rows, int32_t top, const char *who,
+               const char *off_name, const char *row, const char *vals, const char *val_name) {
+  if (!off || rows == 0) return;
+  const std::string w = std::string(who) + ": ";
+  if (off[0] != 0) throw std::invalid_argument(w + off_name + "[0] must be 0");
+  for (int64_t b = 0; b < rows; ++b)
+    if (off[b + 1] < off[b])
+      throw std::invalid_argument(w + off_name + " decrease at " + row + " " + std::to_string(b));
+  const int64_t total = off[rows];
+  if (total > INT32_MAX) throw std::invalid_argument(w + "more than 2^31 - 1 " + vals);
+  if (total > 0 && !val) throw std::invalid_argument("null argument");
+  for (int64_t e = 0; e < total; ++e)
+    if (val[e] < 0 || val[e] >= top)
+      throw std::invalid_argument(w + val_name + " out of range at entry " + std::to_string(e));
+}
+
+// Both fold-in entries: new users (user[m] in [0, n_new), K groups) or, items_side, new items (item[m], L groups)
+int fold_entry(mmsbm_hip_ctx *ctx, bool items_side, int64_t n_rows, const int32_t *user, const int32_t *item,
+               const int32_t *rating, int32_t n_new, int32_t n_iters, double tol, const double *x0, double *x,
+               int32_t *iters) {
+  return guarded([&] {
+    require_params(ctx);
+    const std::string what = items_side ? "fold_in_items" : "fold_in";
+    if (n_rows < 0 || n_rows > INT32_MAX) throw std::invalid_argument(what + ": n_rows outside [0, 2^31)");
+    if (n_new < 0) throw std::invalid_argument(what + ": negative n_new");
+    if (n_iters < 0) throw std::invalid_argument(what + ": negative n_iters");
+    const int groups = items_side ? ctx->ext_l : ctx->ext_k;
+    if (groups > MMSBM_HIP_FOLD_IN_MAX_K)
+      throw ApiError(MMSBM_E_UNSUPPORTED, what + (items_side ? ": L = " : ": K = ") + std::to_string(groups) +
+                                              " is beyond the " + std::to_string(MMSBM_HIP_FOLD_IN_MAX_K) +
+                                              " groups it is built for");
+    if (n_rows > 0 && (!user || !item || !rating)) throw std::invalid_argument("null argument");
+    if (n_new > 0 && !x) throw std::invalid_argument("null argument");
+    const int32_t n_users = items_side ? ctx->ext_users : n_new, n_items = items_side ? n_new : ctx->ext_items;
+    for (int64_t m = 0; m < n_rows; ++m) {
+      if (user[m] < 0 || user[m] >= n_users)
+        throw std::invalid_argument(what + ": user id out of range at row " + std::to_string(m));
+      if (item[m] < 0 || item[m] >= n_items)
+        throw std::invalid_argument(what + ": item id out of range at row " + std::to_string(m));
+      if (rating[m] < 0 || rating[m] >= ctx->n_ratings)
+        throw std::invalid_argument(what + ": rating id out of range at row " + std::to_string(m));
+    }
+    use_device(ctx);
+    OneSlot one(ctx);
+    fold_in(ctx, items_side, n_rows, user, item, rating, n_new, n_iters, tol, x0, x, iters);
+  });
+}
+}  // namespace
+
 int mmsbm_hip_recommend_begin(mmsbm_hip_ctx *ctx, const double *rating_weights, int exclude_train) {
   return guarded([&] {
     if (!ctx || !rating_weights) throw std::invalid_argument("null argument");
@@ -1280,8 +1347,8 @@ int mmsbm_hip_recommend_begin(mmsbm_hip_ctx *ctx, const double *rating_weights, 
 int mmsbm_hip_recommend_add(mmsbm_hip_ctx *ctx) {
   return guarded([&] {
     require_params(ctx);
-    if (ctx->rc_slots < 0) throw std::invalid_argument("recommend_begin has not been called");
-    if (ctx->rc_items != ctx->ext_items)
+    require_session(ctx, nullptr);
+    if (ctx->rc->items != ctx->ext_items)
       throw std::invalid_argument("recommend_add after recommend_add_items: the added items hold no row of this slot");
     OneSlot one(ctx);
     recommend_add(ctx);
@@ -1291,14 +1358,9 @@ int mmsbm_hip_recommend_add(mmsbm_hip_ctx *ctx) {
 int mmsbm_hip_recommend_query(mmsbm_hip_ctx *ctx, int64_t n_users, const int32_t *users, int32_t n, int32_t *items,
                               double *scores, int32_t *counts) {
   return guarded([&] {
-    if (!ctx) throw std::invalid_argument("null context");
-    if (ctx->rc_slots < 0) throw std::invalid_argument("recommend_begin has not been called");
-    if (ctx->rc_slots == 0) throw std::invalid_argument("recommend_query before any recommend_add");
+    require_session(ctx, "recommend_query");
     if (n_users < 0) throw std::invalid_argument("negative n_users");
-    if (n < 1) throw std::invalid_argument("recommend: n must be at least 1");
-    if (n > MMSBM_HIP_RECOMMEND_MAX_N)
-      throw ApiError(MMSBM_E_UNSUPPORTED, "recommend: n = " + std::to_string(n) + " is beyond the " +
-                                              std::to_string(MMSBM_HIP_RECOMMEND_MAX_N) + " items a query returns at most");
+    require_n(n);
     if (n_users > 0 && (!users || !items)) throw std::invalid_argument("null argument");
     for (int64_t m = 0; m < n_users; ++m)
       if (users[m] < 0 || users[m] >= ctx->ext_users)
@@ -1320,27 +1382,12 @@ int mmsbm_hip_recommend_query_theta(mmsbm_hip_ctx *ctx, int64_t n_users, const d
                                     const int64_t *seen_offsets, const int32_t *seen_items, int32_t n,
                                     int32_t *items, double *scores, int32_t *counts) {
   return guarded([&] {
-    if (!ctx) throw std::invalid_argument("null context");
-    if (ctx->rc_slots < 0) throw std::invalid_argument("recommend_begin has not been called");
-    if (ctx->rc_slots == 0) throw std::invalid_argument("recommend_query_theta before any recommend_add");
+    require_session(ctx, "recommend_query_theta");
     if (n_users < 0) throw std::invalid_argument("negative n_users");
-    if (n < 1) throw std::invalid_argument("recommend: n must be at least 1");
-    if (n > MMSBM_HIP_RECOMMEND_MAX_N)
-      throw ApiError(MMSBM_E_UNSUPPORTED, "recommend: n = " + std::to_string(n) + " is beyond the " +
-                                              std::to_string(MMSBM_HIP_RECOMMEND_MAX_N) + " items a query returns at most");
+    require_n(n);
     if (n_users > 0 && (!theta || !items)) throw std::invalid_argument("null argument");
-    if (seen_offsets && n_users > 0) {
-      if (seen_offsets[0] != 0) throw std::invalid_argument("recommend: seen_offsets[0] must be 0");
-      for (int64_t b = 0; b < n_users; ++b)
-        if (seen_offsets[b + 1] < seen_offsets[b])
-          throw std::invalid_argument("recommend: seen_offsets decrease at user " + std::to_string(b));
-      const int64_t total = seen_offsets[n_users];
-      if (total > INT32_MAX) throw std::invalid_argument("recommend: more than 2^31 - 1 seen items");
-      if (total > 0 && !seen_items) throw std::invalid_argument("null argument");
-      for (int64_t e = 0; e < total; ++e)
-        if (seen_items[e] < 0 || seen_items[e] >= ctx->rc_items)
-          throw std::invalid_argument("recommend: seen item out of range at entry " + std::to_string(e));
-    }
+    check_csr(seen_offsets, seen_items, n_users, ctx->rc->items, "recommend", "seen_offsets", "user", "seen items",
+              "seen item");
     recommend_query_theta(ctx, n_users, theta, seen_offsets, seen_items, n, items, scores, counts);
   });
 }
@@ -1349,26 +1396,14 @@ int mmsbm_hip_recommend_positions(mmsbm_hip_ctx *ctx, int64_t n_users, const int
                                   const int64_t *offsets, const int32_t *items, int32_t *positions,
                                   int32_t *candidates) {
   return guarded([&] {
-    if (!ctx) throw std::invalid_argument("null context");
-    if (ctx->rc_slots < 0) throw std::invalid_argument("recommend_begin has not been called");
-    if (ctx->rc_slots == 0) throw std::invalid_argument("recommend_positions before any recommend_add");
+    require_session(ctx, "recommend_positions");
     if (n_users < 0) throw std::invalid_argument("negative n_users");
     if (n_users > 0 && (!users || !offsets)) throw std::invalid_argument("null argument");
     for (int64_t m = 0; m < n_users; ++m)
       if (users[m] < 0 || users[m] >= ctx->ext_users)
         throw std::invalid_argument("recommend_positions: user id out of range at row " + std::to_string(m));
-    if (n_users > 0) {
-      if (offsets[0] != 0) throw std::invalid_argument("recommend_positions: offsets[0] must be 0");
-      for (int64_t b = 0; b < n_users; ++b)
-        if (offsets[b + 1] < offsets[b])
-          throw std::invalid_argument("recommend_positions: offsets decrease at user " + std::to_string(b));
-      const int64_t total = offsets[n_users];
-      if (total > INT32_MAX) throw std::invalid_argument("recommend_positions: more than 2^31 - 1 items");
-      if (total > 0 && (!items || !positions)) throw std::invalid_argument("null argument");
-      for (int64_t e = 0; e < total; ++e)
-        if (items[e] < 0 || items[e] >= ctx->rc_items)
-          throw std::invalid_argument("recommend_positions: item id out of range at entry " + std::to_string(e));
-    }
+    check_csr(offsets, items, n_users, ctx->rc->items, "recommend_positions", "offsets", "user", "items", "item id");
+    if (n_users > 0 && offsets[n_users] > 0 && !positions) throw std::invalid_argument("null argument");
     recommend_positions(ctx, n_users, users, offsets, items, positions, candidates);
   });
 }
@@ -1376,27 +1411,15 @@ int mmsbm_hip_recommend_positions(mmsbm_hip_ctx *ctx, int64_t n_users, const int
 int mmsbm_hip_recommend_add_items(mmsbm_hip_ctx *ctx, int32_t n_new, const double *eta,
                                   const int64_t *seen_offsets, const int32_t *seen_users) {
   return guarded([&] {
-    if (!ctx) throw std::invalid_argument("null context");
-    if (ctx->rc_slots < 0) throw std::invalid_argument("recommend_begin has not been called");
-    if (ctx->rc_slots == 0) throw std::invalid_argument("recommend_add_items before any recommend_add");
-    if (ctx->rc_items != ctx->ext_items)
+    require_session(ctx, "recommend_add_items");
+    if (ctx->rc->items != ctx->ext_items)
       throw std::invalid_argument("recommend_add_items: the session already holds added items");
     if (n_new < 0) throw std::invalid_argument("recommend_add_items: negative n_new");
     if (static_cast<int64_t>(ctx->ext_items) + n_new > INT32_MAX)
       throw std::invalid_argument("recommend_add_items: more than 2^31 - 1 items in the catalogue");
     if (n_new > 0 && !eta) throw std::invalid_argument("null argument");
-    if (seen_offsets && n_new > 0) {
-      if (seen_offsets[0] != 0) throw std::invalid_argument("recommend_add_items: seen_offsets[0] must be 0");
-      for (int32_t j = 0; j < n_new; ++j)
-        if (seen_offsets[j + 1] < seen_offsets[j])
-          throw std::invalid_argument("recommend_add_items: seen_offsets decrease at item " + std::to_string(j));
-      const int64_t total = seen_offsets[n_new];
-      if (total > INT32_MAX) throw std::invalid_argument("recommend_add_items: more than 2^31 - 1 seen users");
-      if (total > 0 && !seen_users) throw std::invalid_argument("null argument");
-      for (int64_t e = 0; e < total; ++e)
-        if (seen_users[e] < 0 || seen_users[e] >= ctx->ext_users)
-          throw std::invalid_argument("recommend_add_items: seen user out of range at entry " + std::to_string(e));
-    }
+    check_csr(seen_offsets, seen_users, n_new, ctx->ext_users, "recommend_add_items", "seen_offsets", "item",
+              "seen users", "seen user");
     recommend_add_items(ctx, n_new, eta, seen_offsets, seen_users);
   });
 }
@@ -1404,55 +1427,13 @@ int mmsbm_hip_recommend_add_items(mmsbm_hip_ctx *ctx, int32_t n_new, const doubl
 int mmsbm_hip_fold_in(mmsbm_hip_ctx *ctx, int64_t n_rows, const int32_t *user, const int32_t *item,
                       const int32_t *rating, int32_t n_new, int32_t n_iters, double tol,
                       const double *theta0, double *theta, int32_t *iters) {
-  return guarded([&] {
-    require_params(ctx);
-    if (n_rows < 0 || n_rows > INT32_MAX) throw std::invalid_argument("fold_in: n_rows outside [0, 2^31)");
-    if (n_new < 0) throw std::invalid_argument("fold_in: negative n_new");
-    if (n_iters < 0) throw std::invalid_argument("fold_in: negative n_iters");
-    if (ctx->ext_k > MMSBM_HIP_FOLD_IN_MAX_K)
-      throw ApiError(MMSBM_E_UNSUPPORTED, "fold_in: K = " + std::to_string(ctx->ext_k) + " is beyond the " +
-                                              std::to_string(MMSBM_HIP_FOLD_IN_MAX_K) + " groups it is built for");
-    if (n_rows > 0 && (!user || !item || !rating)) throw std::invalid_argument("null argument");
-    if (n_new > 0 && !theta) throw std::invalid_argument("null argument");
-    for (int64_t m = 0; m < n_rows; ++m) {
-      if (user[m] < 0 || user[m] >= n_new)
-        throw std::invalid_argument("fold_in: user id out of range at row " + std::to_string(m));
-      if (item[m] < 0 || item[m] >= ctx->ext_items)
-        throw std::invalid_argument("fold_in: item id out of range at row " + std::to_string(m));
-      if (rating[m] < 0 || rating[m] >= ctx->n_ratings)
-        throw std::invalid_argument("fold_in: rating id out of range at row " + std::to_string(m));
-    }
-    use_device(ctx);
-    OneSlot one(ctx);
-    fold_in(ctx, n_rows, user, item, rating, n_new, n_iters, tol, theta0, theta, iters);
-  });
+  return fold_entry(ctx, false, n_rows, user, item, rating, n_new, n_iters, tol, theta0, theta, iters);
 }
 
 int mmsbm_hip_fold_in_items(mmsbm_hip_ctx *ctx, int64_t n_rows, const int32_t *user, const int32_t *item,
                             const int32_t *rating, int32_t n_new, int32_t n_iters, double tol,
                             const double *eta0, double *eta, int32_t *iters) {
-  return guarded([&] {
-    require_params(ctx);
-    if (n_rows < 0 || n_rows > INT32_MAX) throw std::invalid_argument("fold_in_items: n_rows outside [0, 2^31)");
-    if (n_new < 0) throw std::invalid_argument("fold_in_items: negative n_new");
-    if (n_iters < 0) throw std::invalid_argument("fold_in_items: negative n_iters");
-    if (ctx->ext_l > MMSBM_HIP_FOLD_IN_MAX_K)
-      throw ApiError(MMSBM_E_UNSUPPORTED, "fold_in_items: L = " + std::to_string(ctx->ext_l) + " is beyond the " +
-                                              std::to_string(MMSBM_HIP_FOLD_IN_MAX_K) + " groups it is built for");
-    if (n_rows > 0 && (!user || !item || !rating)) throw std::invalid_argument("null argument");
-    if (n_new > 0 && !eta) throw std::invalid_argument("null argument");
-    for (int64_t m = 0; m < n_rows; ++m) {
-      if (user[m] < 0 || user[m] >= ctx->ext_users)
-        throw std::invalid_argument("fold_in_items: user id out of range at row " + std::to_string(m));
-      if (item[m] < 0 || item[m] >= n_new)
-        throw std::invalid_argument("fold_in_items: item id out of range at row " + std::to_string(m));
-      if (rating[m] < 0 || rating[m] >= ctx->n_ratings)
-        throw std::invalid_argument("fold_in_items: rating id out of range at row " + std::to_string(m));
-    }
-    use_device(ctx);
-    OneSlot one(ctx);
-    fold_in_items(ctx, n_rows, user, item, rating, n_new, n_iters, tol, eta0, eta, iters);
-  });
+  return fold_entry(ctx, true, n_rows, user, item, rating, n_new, n_iters, tol, eta0, eta, iters);
 }
 
 int mmsbm_hip_time_iterations(mmsbm_hip_ctx *ctx, int n_iters, float *elapsed_ms) {

@@ -13,32 +13,25 @@ constexpr size_t kRecBatchBytes = size_t(128) << 20;  // score buffer of one bat
 constexpr int kRecMinPerPart = 1024;                   // items a selecting wave gets at least
 constexpr int kPosMinPerPart = 2048;                   // items a counting workgroup gets at least
 
-void rec_require_mem(size_t bytes, const char *what) {
+}  // namespace
+
+void require_free_mem(size_t bytes, const std::string &what) {
   size_t free_b = 0, total_b = 0;
   HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
   if (bytes + (size_t(64) << 20) > free_b)
-    throw ApiError(MMSBM_E_TOOLARGE, std::string("recommend: ") + what + " needs " + std::to_string(bytes >> 20) +
-                                         " MB of device memory, " + std::to_string(free_b >> 20) + " MB free");
+    throw ApiError(MMSBM_E_TOOLARGE, what + " needs " + std::to_string(bytes >> 20) + " MB of device memory, " +
+                                         std::to_string(free_b >> 20) + " MB free");
 }
-
-int rec_rank(const mmsbm_hip_ctx *c) { return std::min(c->ext_k, c->ext_l); }
-
-}  // namespace
 
 void recommend_begin(mmsbm_hip_ctx *c, const double *weights, int exclude_train) {
   use_device(c);
-  c->rc_slots = -1;  // (from here on the previous session is gone)
-  c->rc_x.release();
-  c->rc_y.release();
-  c->rc_wk.release();
-  c->rc_seen_off.release();
-  c->rc_seen.release();
-  c->rc_seen_off_h.clear();
+  c->rc.reset();  // (from here on the previous session is gone)
+  auto rc = std::make_unique<RecSession>();
   hipStream_t s = c->stream;
-  c->rc_w.alloc(c->n_ratings);
-  HIP_CHECK(hipMemcpyAsync(c->rc_w.ptr, weights, sizeof(double) * c->n_ratings, hipMemcpyHostToDevice, s));
-  c->rc_excl = exclude_train != 0;
-  if (c->rc_excl) {
+  rc->w.alloc(c->n_ratings);
+  HIP_CHECK(hipMemcpyAsync(rc->w.ptr, weights, sizeof(double) * c->n_ratings, hipMemcpyHostToDevice, s));
+  rc->excl = exclude_train != 0;
+  if (rc->excl) {
     // every external user's distinct training items, ascending: from the id columns in their original order
     const size_t n = static_cast<size_t>(c->n_obs);
     std::vector<int32_t> ou(n), oi(n);
@@ -64,23 +57,24 @@ void recommend_begin(mmsbm_hip_ctx *c, const double *weights, int exclude_train)
     }
     off[U] = w;
     item.resize(static_cast<size_t>(w));
-    c->rc_seen_off.upload(off, s);
-    c->rc_seen_off_h = off;  // (candidate counts of recommend_positions)
-    c->rc_seen.upload(item, s);
+    rc->seen_off.upload(off, s);
+    rc->seen_off_h = off;  // (candidate counts of recommend_positions)
+    rc->seen.upload(item, s);
     HIP_CHECK(hipStreamSynchronize(s));  // (host vectors are locals)
   }
   HIP_CHECK(hipStreamSynchronize(s));
-  c->rc_rank = rec_rank(c);
-  c->rc_items = c->ext_items;
-  c->rc_slots = 0;
+  rc->rank = std::min(c->ext_k, c->ext_l);
+  rc->items = c->ext_items;
+  c->rc = std::move(rc);
 }
 
 void recommend_add(mmsbm_hip_ctx *c) {  // the selected slot (the caller holds a OneSlot)
   use_device(c);
-  const int U = c->ext_users, I = c->ext_items, K = c->ext_k, L = c->ext_l, R = c->n_ratings, rank = c->rc_rank;
-  const int S = c->rc_slots;
+  RecSession &rc = *c->rc;
+  const int U = c->ext_users, I = c->ext_items, K = c->ext_k, L = c->ext_l, R = c->n_ratings, rank = rc.rank;
+  const int S = rc.slots;
   const size_t xs = static_cast<size_t>(U) * rank, ys = static_cast<size_t>(I) * rank;
-  rec_require_mem(((S + 1) * (xs + ys + static_cast<size_t>(K) * L)) * sizeof(double), "the slots' factors");
+  require_free_mem(((S + 1) * (xs + ys + static_cast<size_t>(K) * L)) * sizeof(double), "recommend: the slots' factors");
   hipStream_t st = c->stream;
   // grow the two tables by one slot (the earlier slots' factors are kept as they are)
   const size_t kl = static_cast<size_t>(K) * L;
@@ -89,9 +83,9 @@ void recommend_add(mmsbm_hip_ctx *c) {  // the selected slot (the caller holds a
   ny.alloc((S + 1) * ys);
   nw.alloc((S + 1) * kl);
   if (S > 0) {
-    HIP_CHECK(hipMemcpyAsync(nx.ptr, c->rc_x.ptr, sizeof(double) * S * xs, hipMemcpyDeviceToDevice, st));
-    HIP_CHECK(hipMemcpyAsync(ny.ptr, c->rc_y.ptr, sizeof(double) * S * ys, hipMemcpyDeviceToDevice, st));
-    HIP_CHECK(hipMemcpyAsync(nw.ptr, c->rc_wk.ptr, sizeof(double) * S * kl, hipMemcpyDeviceToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(nx.ptr, rc.x.ptr, sizeof(double) * S * xs, hipMemcpyDeviceToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(ny.ptr, rc.y.ptr, sizeof(double) * S * ys, hipMemcpyDeviceToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(nw.ptr, rc.wk.ptr, sizeof(double) * S * kl, hipMemcpyDeviceToDevice, st));
   }
   double *wo = nw.ptr + S * kl;
   const int cur = c->cur, sl = c->sel;
@@ -99,7 +93,7 @@ void recommend_add(mmsbm_hip_ctx *c) {  // the selected slot (the caller holds a
   const int ks = c->swapped ? 1 : c->lp, ls = c->swapped ? c->lp : 1;
   const size_t rs = static_cast<size_t>(c->kp) * c->lp;
   LAUNCH(rec_w_kernel, static_cast<unsigned>((K * L + kBlock - 1) / kBlock), kBlock, 0, st, c->p[cur].at(sl),
-         c->rc_w.ptr, wo, K, L, R, rs, ks, ls);
+         rc.w.ptr, wo, K, L, R, rs, ks, ls);
   // the caller's users / items: internal users / items, or the other way round when swapped
   const RowTab th = theta_tab(c, cur), et = plain_tab(c->eta[cur].at(sl), c->lp);
   const RowTab ut = c->swapped ? et : th, it = c->swapped ? th : et;
@@ -119,21 +113,22 @@ void recommend_add(mmsbm_hip_ctx *c) {  // the selected slot (the caller holds a
   }
   HIP_CHECK(hipGetLastError());
   HIP_CHECK(hipStreamSynchronize(st));
-  std::swap(c->rc_x.ptr, nx.ptr); std::swap(c->rc_x.count, nx.count);
-  std::swap(c->rc_y.ptr, ny.ptr); std::swap(c->rc_y.count, ny.count);
-  std::swap(c->rc_wk.ptr, nw.ptr); std::swap(c->rc_wk.count, nw.count);
-  c->rc_slots = S + 1;
+  rc.x.swap(nx);
+  rc.y.swap(ny);
+  rc.wk.swap(nw);
+  rc.slots = S + 1;
 }
 
 void recommend_add_items(mmsbm_hip_ctx *c, int32_t n_new, const double *eta, const int64_t *seen_offsets,
                          const int32_t *seen_users) {
   use_device(c);
   if (n_new == 0) return;
-  const int U = c->ext_users, I = c->ext_items, K = c->ext_k, L = c->ext_l, rank = c->rc_rank, S = c->rc_slots;
+  RecSession &rc = *c->rc;
+  const int U = c->ext_users, I = c->ext_items, K = c->ext_k, L = c->ext_l, rank = rc.rank, S = rc.slots;
   const int NI = I + n_new;
   const size_t ys = static_cast<size_t>(I) * rank, nys = static_cast<size_t>(NI) * rank;
   const size_t el = static_cast<size_t>(n_new) * L, kl = static_cast<size_t>(K) * L;
-  rec_require_mem(S * (nys + el) * sizeof(double), "the added items' factors");
+  require_free_mem(S * (nys + el) * sizeof(double), "recommend: the added items' factors");
   hipStream_t st = c->stream;
   // every slot's table grows from I to I + n_new rows: the training rows copied as they are, the new rows folded with
   // the slot's W exactly as recommend_add folds the slot's own eta (y = eta W^T when K <= L, else y = eta)
@@ -145,8 +140,8 @@ void recommend_add_items(mmsbm_hip_ctx *c, int32_t n_new, const double *eta, con
   const size_t nr = static_cast<size_t>(n_new) * rank;
   for (int s = 0; s < S; ++s) {
     if (ys > 0)
-      HIP_CHECK(hipMemcpyAsync(ny.ptr + s * nys, c->rc_y.ptr + s * ys, sizeof(double) * ys, hipMemcpyDeviceToDevice, st));
-    const double *m = K <= L ? c->rc_wk.ptr + s * kl : nullptr;
+      HIP_CHECK(hipMemcpyAsync(ny.ptr + s * nys, rc.y.ptr + s * ys, sizeof(double) * ys, hipMemcpyDeviceToDevice, st));
+    const double *m = K <= L ? rc.wk.ptr + s * kl : nullptr;
     LAUNCH(rec_fold_kernel, static_cast<unsigned>((nr + kBlock - 1) / kBlock), kBlock, 0, st,
            plain_tab(de.ptr + s * el, L), L, m, 1, L, ny.ptr + s * nys + ys, n_new, rank);
   }
@@ -155,10 +150,10 @@ void recommend_add_items(mmsbm_hip_ctx *c, int32_t n_new, const double *eta, con
   // distinct: its training items (< I) first, then its new items (>= I), sorted and de-duplicated.
   const int64_t n_seen = seen_offsets ? seen_offsets[n_new] : 0;  // (checked: below 2^31)
   if (n_seen > 0) {
-    std::vector<int32_t> old_off = c->rc_excl ? c->rc_seen_off_h : std::vector<int32_t>(static_cast<size_t>(U) + 1, 0);
+    std::vector<int32_t> old_off = rc.excl ? rc.seen_off_h : std::vector<int32_t>(static_cast<size_t>(U) + 1, 0);
     std::vector<int32_t> old(static_cast<size_t>(old_off[U]));
     if (!old.empty())
-      HIP_CHECK(hipMemcpyAsync(old.data(), c->rc_seen.ptr, sizeof(int32_t) * old.size(), hipMemcpyDeviceToHost, st));
+      HIP_CHECK(hipMemcpyAsync(old.data(), rc.seen.ptr, sizeof(int32_t) * old.size(), hipMemcpyDeviceToHost, st));
     // the new pairs grouped by user (counting sort)
     std::vector<int32_t> noff(static_cast<size_t>(U) + 1, 0), nit(static_cast<size_t>(n_seen));
     for (int64_t e = 0; e < n_seen; ++e) noff[static_cast<size_t>(seen_users[e]) + 1]++;
@@ -183,14 +178,14 @@ void recommend_add_items(mmsbm_hip_ctx *c, int32_t n_new, const double *eta, con
     so.upload(off, st);
     si.upload(item, st);
     HIP_CHECK(hipStreamSynchronize(st));  // (host vectors are locals)
-    std::swap(c->rc_seen_off.ptr, so.ptr); std::swap(c->rc_seen_off.count, so.count);
-    std::swap(c->rc_seen.ptr, si.ptr); std::swap(c->rc_seen.count, si.count);
-    c->rc_seen_off_h = off;
-    c->rc_excl = true;
+    rc.seen_off.swap(so);
+    rc.seen.swap(si);
+    rc.seen_off_h = off;
+    rc.excl = true;
   }
   HIP_CHECK(hipStreamSynchronize(st));
-  std::swap(c->rc_y.ptr, ny.ptr); std::swap(c->rc_y.count, ny.count);
-  c->rc_items = NI;
+  rc.y.swap(ny);
+  rc.items = NI;
 }
 
 namespace {
@@ -203,15 +198,25 @@ int64_t rec_batch_users(int I, int64_t n_users) {
   return std::min(bu, n_users);
 }
 
+// (parts, per): the I items split into parts of at least min_per items each until about `target` (batch rows x
+// parts) are in flight; few users: one user over 100k items
+std::pair<int, int> item_parts(int I, int64_t bu, int64_t target, int min_per) {
+  int parts = 1;
+  if (bu < target) parts = static_cast<int>(std::min<int64_t>((target + bu - 1) / bu, (I + min_per - 1) / min_per));
+  parts = std::max(parts, 1);
+  const int per = (I + parts - 1) / parts;
+  return {I > 0 ? (I + per - 1) / per : 1, per};
+}
+
 // The scores of one batch of nb users ub (device ids, rows of x) into sc [nb][I] (I: the session's catalogue); seen_off / seen (device, indexed by
 // those ids): the items set to -inf, or null.  Shared by the selection (rec_run) and the positions.
 void rec_score_batch(mmsbm_hip_ctx *c, const double *x, size_t xs, const int32_t *ub, int nb, const int32_t *seen_off,
                      const int32_t *seen, double *sc) {
-  const int I = c->rc_items, rank = c->rc_rank, S = c->rc_slots;
+  const int I = c->rc->items, rank = c->rc->rank, S = c->rc->slots;
   if (I == 0) return;
   hipStream_t st = c->stream;
   const dim3 g(static_cast<unsigned>((I + kRecTile - 1) / kRecTile), static_cast<unsigned>((nb + kRecTile - 1) / kRecTile));
-  LAUNCH(rec_score_kernel, g, kBlock, 0, st, x, xs, c->rc_y.ptr, static_cast<size_t>(I) * rank, ub, nb, I, rank, S,
+  LAUNCH(rec_score_kernel, g, kBlock, 0, st, x, xs, c->rc->y.ptr, static_cast<size_t>(I) * rank, ub, nb, I, rank, S,
          sc, static_cast<size_t>(I));
   if (seen_off) LAUNCH(rec_exclude_kernel, nb, kBlock, 0, st, ub, seen_off, seen, sc, static_cast<size_t>(I));
 }
@@ -228,25 +233,19 @@ void rec_run(mmsbm_hip_ctx *c, const double *x, size_t xs, int64_t n_users, cons
     }
   }
   if (n_users == 0) return;
-  const int I = c->rc_items;
+  const int I = c->rc->items;
   hipStream_t st = c->stream;
 
   const int64_t bu = rec_batch_users(I, n_users);
-  // items split across waves until about 32 selecting waves per CU are in flight (the selection waits on its loads;
-  // few users: a single user over 100k items)
-  const int64_t target = 32LL * c->n_cus;
-  int parts = 1;
-  if (bu < target) parts = static_cast<int>(std::min<int64_t>((target + bu - 1) / bu, (I + kRecMinPerPart - 1) / kRecMinPerPart));
-  parts = std::max(parts, 1);
-  const int per = (I + parts - 1) / parts;
-  parts = I > 0 ? (I + per - 1) / per : 1;
+  // items split across waves until about 32 selecting waves per CU are in flight (the selection waits on its loads)
+  const auto [parts, per] = item_parts(I, bu, 32LL * c->n_cus, kRecMinPerPart);
   int cap = 1;
   while (cap < n + kRecWave * kRecPerLane) cap <<= 1;
   const size_t lds = static_cast<size_t>(cap) * (sizeof(double) + sizeof(int32_t));
   const size_t cand = parts > 1 ? static_cast<size_t>(bu) * parts * n : 0;
   const size_t outs = static_cast<size_t>(n_users) * n;
-  rec_require_mem(static_cast<size_t>(bu) * I * sizeof(double) + cand * 12 + outs * 12 + static_cast<size_t>(n_users) * 8,
-                  "a batch of users");
+  require_free_mem(static_cast<size_t>(bu) * I * sizeof(double) + cand * 12 + outs * 12 + static_cast<size_t>(n_users) * 8,
+                   "recommend: a batch of users");
   DevBuf<int32_t> du, ci, cn, oi, on;
   DevBuf<double> sc, cs, os;
   du.alloc(n_users);
@@ -256,10 +255,8 @@ void rec_run(mmsbm_hip_ctx *c, const double *x, size_t xs, int64_t n_users, cons
   }
   os.alloc(outs); oi.alloc(outs); on.alloc(n_users);  // every user's result stays on the device until the end
   HIP_CHECK(hipMemcpyAsync(du.ptr, users, sizeof(int32_t) * n_users, hipMemcpyHostToDevice, st));
-  hipEvent_t e0, e1;  // device time of the query's kernels (option "recommend_ms")
-  HIP_CHECK(hipEventCreate(&e0));
-  HIP_CHECK(hipEventCreate(&e1));
-  HIP_CHECK(hipEventRecord(e0, st));
+  EventPair ev;  // device time of the query's kernels (option "recommend_ms")
+  ev.start(st);
   for (int64_t b0 = 0; b0 < n_users; b0 += bu) {  // (batches follow each other on the stream: no host wait in between)
     const int nb = static_cast<int>(std::min(bu, n_users - b0));
     const int32_t *ub = du.ptr + b0;
@@ -277,18 +274,14 @@ void rec_run(mmsbm_hip_ctx *c, const double *x, size_t xs, int64_t n_users, cons
     }
     HIP_CHECK(hipGetLastError());
   }
-  HIP_CHECK(hipEventRecord(e1, st));
+  ev.stop(st);
   std::vector<double> hs(outs);
   std::vector<int32_t> hi(outs), hn(static_cast<size_t>(n_users));
   HIP_CHECK(hipMemcpyAsync(hs.data(), os.ptr, sizeof(double) * outs, hipMemcpyDeviceToHost, st));
   HIP_CHECK(hipMemcpyAsync(hi.data(), oi.ptr, sizeof(int32_t) * outs, hipMemcpyDeviceToHost, st));
   HIP_CHECK(hipMemcpyAsync(hn.data(), on.ptr, sizeof(int32_t) * n_users, hipMemcpyDeviceToHost, st));
   HIP_CHECK(hipStreamSynchronize(st));
-  float ms = 0.f;
-  HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-  c->rc_last_ms = ms;
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
+  c->rc_last_ms = ev.ms();
   for (int64_t b = 0; b < n_users; ++b) {
     const size_t o = static_cast<size_t>(b) * n;
     const int cnt = hn[static_cast<size_t>(b)];
@@ -305,18 +298,19 @@ void rec_run(mmsbm_hip_ctx *c, const double *x, size_t xs, int64_t n_users, cons
 void recommend_query(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, int n, int32_t *items, double *scores,
                      int32_t *counts) {
   use_device(c);
-  rec_run(c, c->rc_x.ptr, static_cast<size_t>(c->ext_users) * c->rc_rank, n_users, users,
-          c->rc_excl ? c->rc_seen_off.ptr : nullptr, c->rc_seen.ptr, n, items, scores, counts);
+  const RecSession &rc = *c->rc;
+  rec_run(c, rc.x.ptr, static_cast<size_t>(c->ext_users) * rc.rank, n_users, users, rc.excl ? rc.seen_off.ptr : nullptr,
+          rc.seen.ptr, n, items, scores, counts);
 }
 
 void recommend_query_theta(mmsbm_hip_ctx *c, int64_t n_users, const double *theta, const int64_t *seen_offsets,
                            const int32_t *seen_items, int n, int32_t *items, double *scores, int32_t *counts) {
   use_device(c);
-  const int K = c->ext_k, L = c->ext_l, rank = c->rc_rank, S = c->rc_slots;
+  const int K = c->ext_k, L = c->ext_l, rank = c->rc->rank, S = c->rc->slots;
   const size_t tk = static_cast<size_t>(n_users) * K, xs = static_cast<size_t>(n_users) * rank;
   const int64_t n_seen = seen_offsets && n_users > 0 ? seen_offsets[n_users] : 0;
-  rec_require_mem(S * (tk + xs) * sizeof(double) + (static_cast<size_t>(n_users) + 1 + n_seen) * 4,
-                  "the caller's theta rows");
+  require_free_mem(S * (tk + xs) * sizeof(double) + (static_cast<size_t>(n_users) + 1 + n_seen) * 4,
+                   "recommend: the caller's theta rows");
   hipStream_t st = c->stream;
   // every slot's rows folded exactly as recommend_add folds the slot's own theta: x = theta, or theta W when K > L
   DevBuf<double> th, x;
@@ -336,7 +330,7 @@ void recommend_query_theta(mmsbm_hip_ctx *c, int64_t n_users, const double *thet
   const size_t kl = static_cast<size_t>(K) * L;
   for (int s = 0; s < S && xs > 0; ++s) {
     const RowTab src = plain_tab(th.ptr + s * tk, K);
-    const double *m = K <= L ? nullptr : c->rc_wk.ptr + s * kl;
+    const double *m = K <= L ? nullptr : c->rc->wk.ptr + s * kl;
     LAUNCH(rec_fold_kernel, static_cast<unsigned>((xs + kBlock - 1) / kBlock), kBlock, 0, st, src, K, m, L, 1,
            x.ptr + s * xs, static_cast<int>(n_users), rank);
   }
@@ -347,11 +341,12 @@ void recommend_query_theta(mmsbm_hip_ctx *c, int64_t n_users, const double *thet
 void recommend_positions(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, const int64_t *offsets,
                          const int32_t *items, int32_t *positions, int32_t *candidates) {
   use_device(c);
-  const int I = c->rc_items, rank = c->rc_rank;
+  const RecSession &rc = *c->rc;
+  const int I = rc.items, rank = rc.rank;
   const int64_t total = n_users > 0 ? offsets[n_users] : 0;  // (checked: below 2^31)
   for (int64_t b = 0; b < n_users && candidates; ++b) {
     const int32_t u = users[b];
-    candidates[b] = c->rc_excl ? I - (c->rc_seen_off_h[u + 1] - c->rc_seen_off_h[u]) : I;
+    candidates[b] = rc.excl ? I - (rc.seen_off_h[u + 1] - rc.seen_off_h[u]) : I;
   }
   // only the users that hold test items are scored: the others' ranges are empty, so the ranges of the rows kept
   // follow each other and toff[k] = offsets[row k] (toff[na] = total)
@@ -369,19 +364,14 @@ void recommend_positions(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users
   }
   hipStream_t st = c->stream;
   const int64_t bu = rec_batch_users(I, na);
-  // items split across workgroups until about 8 counting workgroups per CU are in flight (few users: one user over
-  // 100k items); the counts are integers, so the split cannot change a position
-  const int64_t target = 8LL * c->n_cus;
-  int parts = 1;
-  if (bu < target) parts = static_cast<int>(std::min<int64_t>((target + bu - 1) / bu, (I + kPosMinPerPart - 1) / kPosMinPerPart));
-  parts = std::max(parts, 1);
-  const int per = (I + parts - 1) / parts;
-  parts = I > 0 ? (I + per - 1) / per : 1;
+  // items split across workgroups until about 8 counting workgroups per CU are in flight; the counts are integers,
+  // so the split cannot change a position
+  const auto [parts, per] = item_parts(I, bu, 8LL * c->n_cus, kPosMinPerPart);
   int64_t most = 0;  // test entries of the largest batch
   for (int64_t b0 = 0; b0 < na; b0 += bu) most = std::max<int64_t>(most, toff[std::min(na, b0 + bu)] - toff[b0]);
-  rec_require_mem(static_cast<size_t>(bu) * I * sizeof(double) + static_cast<size_t>(most) * parts * 4 +
-                      static_cast<size_t>(total) * 8 + static_cast<size_t>(na) * 8,
-                  "the positions of a batch of users");
+  require_free_mem(static_cast<size_t>(bu) * I * sizeof(double) + static_cast<size_t>(most) * parts * 4 +
+                       static_cast<size_t>(total) * 8 + static_cast<size_t>(na) * 8,
+                   "recommend: the positions of a batch of users");
   DevBuf<int32_t> du, dto, dit, dpos, pc;
   DevBuf<double> sc;
   du.upload(hu, st);
@@ -391,39 +381,24 @@ void recommend_positions(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users
   pc.alloc(static_cast<size_t>(most) * parts);
   sc.alloc(static_cast<size_t>(bu) * I);
   HIP_CHECK(hipMemcpyAsync(dit.ptr, items, sizeof(int32_t) * total, hipMemcpyHostToDevice, st));
-  hipEvent_t e0, e1;  // device time of the call's kernels (option "position_ms")
-  HIP_CHECK(hipEventCreate(&e0));
-  HIP_CHECK(hipEventCreate(&e1));
-  HIP_CHECK(hipEventRecord(e0, st));
+  EventPair ev;  // device time of the call's kernels (option "position_ms")
+  ev.start(st);
   const size_t xs = static_cast<size_t>(c->ext_users) * rank;
   for (int64_t b0 = 0; b0 < na; b0 += bu) {  // (batches follow each other on the stream)
     const int nb = static_cast<int>(std::min(bu, na - b0));
-    rec_score_batch(c, c->rc_x.ptr, xs, du.ptr + b0, nb, c->rc_excl ? c->rc_seen_off.ptr : nullptr, c->rc_seen.ptr,
-                    sc.ptr);
+    rec_score_batch(c, rc.x.ptr, xs, du.ptr + b0, nb, rc.excl ? rc.seen_off.ptr : nullptr, rc.seen.ptr, sc.ptr);
     LAUNCH(rec_position_kernel, dim3(parts, nb), kBlock, 0, st, sc.ptr, static_cast<size_t>(I), I, per, dto.ptr + b0,
            dit.ptr, pc.ptr);
     LAUNCH(rec_position_sum_kernel, nb, kBlock, 0, st, sc.ptr, static_cast<size_t>(I), dto.ptr + b0, dit.ptr, pc.ptr,
            parts, dpos.ptr);
     HIP_CHECK(hipGetLastError());
   }
-  HIP_CHECK(hipEventRecord(e1, st));
+  ev.stop(st);
   HIP_CHECK(hipMemcpyAsync(positions, dpos.ptr, sizeof(int32_t) * total, hipMemcpyDeviceToHost, st));
   HIP_CHECK(hipStreamSynchronize(st));
-  float ms = 0.f;
-  HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-  c->pos_last_ms = ms;
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
+  c->pos_last_ms = ev.ms();
 }
 
-void recommend_end(mmsbm_hip_ctx *c) {
-  c->rc_slots = -1;
-  c->rc_x.release();
-  c->rc_y.release();
-  c->rc_w.release();
-  c->rc_seen_off.release();
-  c->rc_seen.release();
-  c->rc_seen_off_h.clear();
-}
+void recommend_end(mmsbm_hip_ctx *c) { c->rc.reset(); }
 
 }  // namespace mmsbm_hip_impl

@@ -15,6 +15,7 @@ which GPU ran it.
 """
 from __future__ import annotations
 
+import contextlib
 import logging
 from concurrent.futures import ThreadPoolExecutor
 from datetime import datetime
@@ -258,26 +259,35 @@ class MMSBM:
         (mean distribution over them, its six sums, the five scores of every restart).  ``subset``:
         positions in ``self.results`` to score instead of all of them (restarts.predict_distributed)."""
         self.test = test
+        ctx, restarts = self._restarts(subset)
+        ctx.predict_begin(test, np.asarray(self.ratings, dtype=np.float64))
+        per_run = [ctx.predict_add() for _ in restarts]
+        matrix, raw = ctx.predict_finish()
+        self._raw_per_run = per_run                  # the six sums of each scored restart (restarts.predict_distributed)
+        return matrix, raw, [ctx.final_stats(st) for st in per_run]
+
+    def _restarts(self, subset=None):
+        """(ctx, restarts): this model's context on its first device, and an iterator over the positions ``subset`` in
+        ``self.results`` (None: all of them) that selects each restart's parameters in the context before it yields
+        the position.  Restarts whose final parameters still sit in the context's slots are selected there and need no
+        upload; otherwise the context drops to one slot here and each restart is uploaded in its turn."""
         dev = self._device_list()[0]
         ctx = self._ctx(dev)
-        picked = list(range(len(self.results))) if subset is None else list(subset)
-        # restarts whose final parameters still sit in this context's slots need no upload
+        picked = range(len(self.results)) if subset is None else list(subset)
         resident = self._resident.get((dev, 0)) == list(self._restart_ids) and ctx.slots == len(self.results)
         if not resident:
             ctx.set_slots(1)
             self._resident.pop((dev, 0), None)
-        ctx.predict_begin(test, np.asarray(self.ratings, dtype=np.float64))
-        per_run = []
-        for j in picked:
-            a = self.results[j]
-            if resident:
-                ctx.select(j)
-            else:
-                ctx.set_params(a["theta"], a["eta"], a["pr"])
-            per_run.append(ctx.predict_add())
-        matrix, raw = ctx.predict_finish()
-        self._raw_per_run = per_run                  # the six sums of each scored restart (restarts.predict_distributed)
-        return matrix, raw, [ctx.final_stats(st) for st in per_run]
+
+        def each():
+            for j in picked:
+                if resident:
+                    ctx.select(j)
+                else:
+                    a = self.results[j]
+                    ctx.set_params(a["theta"], a["eta"], a["pr"])
+                yield j
+        return ctx, each()
 
     # ------------------------------------------------------------------ recommendation (not in the reference)
     RECOMMEND_BATCH_ROWS = 1 << 22   # result rows (users x n) fetched from the device per query call
@@ -291,42 +301,45 @@ class MMSBM:
         Returns a DataFrame with columns ``users``, ``items``, ``score``, ``rank`` (1 = best), users in request order
         (``users=None``: every training user), users and items as the encoder's labels (``theta`` / ``eta``'s index).  The model's stored predictions and
         ``score()`` are left as they are."""
-        import pandas as pd
         self._check_whole_model()
         n, w = self._recommend_args(n, weights)
         enc = self.data_handler
         ids, labels = self._training_users(users)
         item_labels = np.asarray(enc.item_labels(), dtype=object) if enc else None
-
-        dev = self._device_list()[0]
-        ctx = self._ctx(dev)
-        # restarts whose final parameters still sit in this context's slots need no upload (as in _predict_runs)
-        resident = self._resident.get((dev, 0)) == list(self._restart_ids) and ctx.slots == len(self.results)
-        if not resident:
-            ctx.set_slots(1)
-            self._resident.pop((dev, 0), None)
-        parts = []
-        ctx.recommend_begin(w, exclude_seen)
-        try:
-            for j, a in enumerate(self.results):
-                if resident:
-                    ctx.select(j)
-                else:
-                    ctx.set_params(a["theta"], a["eta"], a["pr"])
+        ctx, restarts = self._restarts()
+        with self._recommend_session(ctx, w, exclude_seen):
+            for _ in restarts:
                 ctx.recommend_add()
-            step = max(1, self.RECOMMEND_BATCH_ROWS // n)   # bounded host memory at a million users
-            for b in range(0, len(ids), step):
-                items, scores, counts = ctx.recommend_query(ids[b:b + step], n)
-                keep = np.arange(n)[None, :] < counts[:, None]
-                rows = np.repeat(np.arange(b, b + len(counts)), counts)
-                it = items[keep]
-                parts.append(pd.DataFrame({
-                    "users": labels[rows] if len(rows) else np.empty(0, dtype=object),
-                    "items": item_labels[it] if item_labels is not None else it.astype(np.int64),
-                    "score": scores[keep],
-                    "rank": np.nonzero(keep)[1].astype(np.int64) + 1}))
+            return self._top_n_frame(lambda b, e: ctx.recommend_query(ids[b:e], n), n, labels, item_labels)
+
+    @staticmethod
+    @contextlib.contextmanager
+    def _recommend_session(ctx, weights, exclude_seen):
+        """ctx's recommend session around the block, ended however the block ends."""
+        ctx.recommend_begin(weights, exclude_seen)
+        try:
+            yield
         finally:
             ctx.recommend_end()
+
+    def _top_n_frame(self, query, n, row_labels, item_labels):
+        """The top-``n`` frame (users, items, score, rank) of rows [0, len(row_labels)), fetched in calls of at most
+        RECOMMEND_BATCH_ROWS result rows (bounded host memory at a million users): ``query(b, e)`` -> (items, scores,
+        counts) of rows [b, e).  ``item_labels``: the label of each item id, or None (the ids themselves)."""
+        import pandas as pd
+        n_rows = len(row_labels)
+        step = max(1, self.RECOMMEND_BATCH_ROWS // n)
+        parts = []
+        for b in range(0, n_rows, step):
+            items, scores, counts = query(b, min(n_rows, b + step))
+            keep = np.arange(n)[None, :] < counts[:, None]
+            at = np.repeat(np.arange(b, b + len(counts)), counts)
+            it = items[keep]
+            parts.append(pd.DataFrame({
+                "users": row_labels[at] if len(at) else np.empty(0, dtype=object),
+                "items": item_labels[it] if item_labels is not None else it.astype(np.int64),
+                "score": scores[keep],
+                "rank": np.nonzero(keep)[1].astype(np.int64) + 1}))
         if not parts:
             return pd.DataFrame({"users": [], "items": [], "score": np.zeros(0), "rank": np.zeros(0, dtype=np.int64)})
         return pd.concat(parts, ignore_index=True)
@@ -409,24 +422,11 @@ class MMSBM:
         order = np.argsort(users, kind="stable")                      # one request entry per user holding rows
         uniq, counts = np.unique(users[order], return_counts=True)
         offsets = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
-        dev = self._device_list()[0]
-        ctx = self._ctx(dev)
-        # restarts whose final parameters still sit in this context's slots need no upload (as in recommend)
-        resident = self._resident.get((dev, 0)) == list(self._restart_ids) and ctx.slots == len(self.results)
-        if not resident:
-            ctx.set_slots(1)
-            self._resident.pop((dev, 0), None)
-        ctx.recommend_begin(w, exclude_seen)
-        try:
-            for j, a in enumerate(self.results):
-                if resident:
-                    ctx.select(j)
-                else:
-                    ctx.set_params(a["theta"], a["eta"], a["pr"])
+        ctx, restarts = self._restarts()
+        with self._recommend_session(ctx, w, exclude_seen):
+            for _ in restarts:
                 ctx.recommend_add()
             pos, cand = ctx.recommend_positions(uniq.astype(np.int32), offsets, rows[order, 1])
-        finally:
-            ctx.recommend_end()
         position = np.empty(len(rows), dtype=np.int64)
         position[order] = pos
         candidates = np.empty(len(rows), dtype=np.int64)
@@ -498,21 +498,12 @@ class MMSBM:
         return ranking_metrics(rows[:, 0], rows[:, 1], rows[:, 2], position, candidates, ks, rel_ids)
 
     # ------------------------------------------------------------------ fold-in of new users (not in the reference)
-    def _encode_new_users(self, data):
-        """(rows (N, 3) int32 [new user, item, rating], user labels in order of first appearance).  Every user of
-        ``data`` is new (the training theta is never consulted); items and ratings are encoded against the training
-        dictionaries, and rows with an unseen item or rating are dropped with ``Encoder.transform``'s warning.  A user
-        whose rows are all dropped keeps its place (uniform theta, no iterations)."""
-        return self._encode_new(data, 0)
-
-    def _encode_new_items(self, data):
-        """(rows (N, 3) int32 [user, new item, rating], item labels in order of first appearance): _encode_new_users
-        with the roles of users and items exchanged (the training eta is never consulted)."""
-        return self._encode_new(data, 1)
-
     def _encode_new(self, data, side):
-        """Column ``side`` (0: users, 1: items) of ``data`` holds new entities, numbered by first appearance; the other
-        two columns are encoded against the training dictionaries."""
+        """(rows (N, 3) int32 in the training column order, labels of the new entities in order of first appearance).
+        Column ``side`` (0: users, 1: items) of ``data`` holds new entities, numbered by first appearance (the training
+        theta / eta is never consulted); the other two columns are encoded against the training dictionaries, and rows
+        with an unseen entry are dropped with ``Encoder.transform``'s warning.  An entity whose rows are all dropped
+        keeps its place (uniform start, no iterations)."""
         import pandas as pd
         from .encode import _columns
         cols, _ = _columns(data)
@@ -555,27 +546,18 @@ class MMSBM:
         return out, labels
 
     def _fold_runs(self, rows, n_new, iterations, tol, each=None, items=False):
-        """theta (n_new, K) -- eta (n_new, L) with ``items`` -- and the iterations used of every restart, in
-        ``self.results`` order; ``each(ctx)`` runs after each restart's fold-in while its parameters are selected
-        (recommend_new adds the slot there)."""
-        dev = self._device_list()[0]
-        ctx = self._ctx(dev)
-        resident = self._resident.get((dev, 0)) == list(self._restart_ids) and ctx.slots == len(self.results)
-        if not resident:
-            ctx.set_slots(1)
-            self._resident.pop((dev, 0), None)
+        """(thetas, iterations): theta (n_new, K) -- eta (n_new, L) with ``items`` -- and the iterations used of every
+        restart, in ``self.results`` order; ``each(ctx)`` runs after each restart's fold-in while its parameters are
+        selected (recommend_new adds the slot there)."""
+        ctx, restarts = self._restarts()
         thetas, iters = [], []
-        for j, a in enumerate(self.results):
-            if resident:
-                ctx.select(j)
-            else:
-                ctx.set_params(a["theta"], a["eta"], a["pr"])
+        for _ in restarts:
             t, it = (ctx.fold_in_items if items else ctx.fold_in)(rows, n_new, iterations, tol)
             thetas.append(t)
             iters.append(it)
             if each is not None:
                 each(ctx)
-        return ctx, thetas, iters
+        return thetas, iters
 
     @staticmethod
     def _fold_args(iterations, tol):
@@ -597,8 +579,8 @@ class MMSBM:
         import pandas as pd
         self._check_whole_model()
         iterations, tol = self._fold_args(iterations, tol)
-        rows, labels = self._encode_new_users(data)
-        _, thetas, iters = self._fold_runs(rows, len(labels), iterations, tol)
+        rows, labels = self._encode_new(data, 0)
+        thetas, iters = self._fold_runs(rows, len(labels), iterations, tol)
         index = pd.Index(labels, name="users") if len(labels) else pd.Index([], name="users")
         self.fold_in_iterations = pd.DataFrame(np.stack(iters, 1) if iters else np.zeros((len(labels), 0)),
                                                index=index)
@@ -613,15 +595,13 @@ class MMSBM:
         self._check_whole_model()
         n, w = self._recommend_args(n, weights)
         iterations, tol = self._fold_args(iterations, tol)
-        rows, labels = self._encode_new_users(data)
+        rows, labels = self._encode_new(data, 0)
         enc = self.data_handler
         item_labels = np.asarray(enc.item_labels(), dtype=object) if enc else None
         n_new = len(labels)
         ctx = self._ctx(self._device_list()[0])
-        parts = []
-        ctx.recommend_begin(w, False)
-        try:
-            _, thetas, iters = self._fold_runs(rows, n_new, iterations, tol, each=lambda c: c.recommend_add())
+        with self._recommend_session(ctx, w, False):
+            thetas, iters = self._fold_runs(rows, n_new, iterations, tol, each=lambda c: c.recommend_add())
             self.fold_in_iterations = pd.DataFrame(np.stack(iters, 1), index=pd.Index(labels, name="users"))
             theta = np.stack(thetas)                                  # (restarts, new users, K)
             if exclude_seen:
@@ -629,26 +609,11 @@ class MMSBM:
                 counts = np.bincount(rows[:, 0], minlength=n_new)
                 seen_off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
                 seen_items = rows[order, 1]
-            step = max(1, self.RECOMMEND_BATCH_ROWS // n)
-            for b in range(0, n_new, step):
-                e = min(n_new, b + step)
-                seen = None
-                if exclude_seen:
-                    seen = (seen_off[b:e + 1] - seen_off[b], seen_items[seen_off[b]:seen_off[e]])
-                items, scores, counts = ctx.recommend_query_theta(theta[:, b:e], n, seen)
-                keep = np.arange(n)[None, :] < counts[:, None]
-                at = np.repeat(np.arange(b, e), counts)
-                it = items[keep]
-                parts.append(pd.DataFrame({
-                    "users": labels[at] if len(at) else np.empty(0, dtype=object),
-                    "items": item_labels[it] if item_labels is not None else it.astype(np.int64),
-                    "score": scores[keep],
-                    "rank": np.nonzero(keep)[1].astype(np.int64) + 1}))
-        finally:
-            ctx.recommend_end()
-        if not parts:
-            return pd.DataFrame({"users": [], "items": [], "score": np.zeros(0), "rank": np.zeros(0, dtype=np.int64)})
-        return pd.concat(parts, ignore_index=True)
+
+            def query(b, e):
+                seen = (seen_off[b:e + 1] - seen_off[b], seen_items[seen_off[b]:seen_off[e]]) if exclude_seen else None
+                return ctx.recommend_query_theta(theta[:, b:e], n, seen)
+            return self._top_n_frame(query, n, labels, item_labels)
 
     def fold_in_items(self, data, iterations=100, tol=None):
         """eta of items that were not in the training data, from their ratings: ``iterations`` steps of the eta half of
@@ -664,8 +629,8 @@ class MMSBM:
         import pandas as pd
         self._check_whole_model()
         iterations, tol = self._fold_args(iterations, tol)
-        rows, labels = self._encode_new_items(data)
-        _, etas, iters = self._fold_runs(rows, len(labels), iterations, tol, items=True)
+        rows, labels = self._encode_new(data, 1)
+        etas, iters = self._fold_runs(rows, len(labels), iterations, tol, items=True)
         index = pd.Index(labels, name="items") if len(labels) else pd.Index([], name="items")
         self.fold_in_items_iterations = pd.DataFrame(np.stack(iters, 1) if iters else np.zeros((len(labels), 0)),
                                                      index=index)
@@ -682,7 +647,7 @@ class MMSBM:
         self._check_whole_model()
         n, w = self._recommend_args(n, weights)
         iterations, tol = self._fold_args(iterations, tol)
-        rows, labels = self._encode_new_items(data)
+        rows, labels = self._encode_new(data, 1)
         enc = self.data_handler
         n_items = self.m + 1
         if enc:
@@ -698,10 +663,8 @@ class MMSBM:
         ids, user_labels = self._training_users(users)
         n_new = len(labels)
         ctx = self._ctx(self._device_list()[0])
-        parts = []
-        ctx.recommend_begin(w, exclude_seen)
-        try:
-            _, etas, iters = self._fold_runs(rows, n_new, iterations, tol, each=lambda c: c.recommend_add(), items=True)
+        with self._recommend_session(ctx, w, exclude_seen):
+            etas, iters = self._fold_runs(rows, n_new, iterations, tol, each=lambda c: c.recommend_add(), items=True)
             self.fold_in_items_iterations = pd.DataFrame(np.stack(iters, 1), index=pd.Index(labels, name="items"))
             seen = None
             if exclude_seen:  # the training users that rated each new item
@@ -709,21 +672,7 @@ class MMSBM:
                 counts = np.bincount(rows[:, 1], minlength=n_new)
                 seen = (np.concatenate([[0], np.cumsum(counts)]).astype(np.int64), rows[order, 0])
             ctx.recommend_add_items(np.stack(etas), seen)
-            step = max(1, self.RECOMMEND_BATCH_ROWS // n)
-            for b in range(0, len(ids), step):
-                items, scores, counts = ctx.recommend_query(ids[b:b + step], n)
-                keep = np.arange(n)[None, :] < counts[:, None]
-                at = np.repeat(np.arange(b, b + len(counts)), counts)
-                parts.append(pd.DataFrame({
-                    "users": user_labels[at] if len(at) else np.empty(0, dtype=object),
-                    "items": item_labels[items[keep]],
-                    "score": scores[keep],
-                    "rank": np.nonzero(keep)[1].astype(np.int64) + 1}))
-        finally:
-            ctx.recommend_end()
-        if not parts:
-            return pd.DataFrame({"users": [], "items": [], "score": np.zeros(0), "rank": np.zeros(0, dtype=np.int64)})
-        return pd.concat(parts, ignore_index=True)
+            return self._top_n_frame(lambda b, e: ctx.recommend_query(ids[b:e], n), n, user_labels, item_labels)
 
     def _keep_best_run(self, best, res=None):
         """theta / eta / pr / likelihood of restart ``best`` become the model's stored objects
