@@ -322,9 +322,9 @@ int mmsbm_hip_layout_free(mmsbm_hip_layout *layout);
  * launch.  side 0: pair segments, the 64-pair units rebuilt with at most cap_items work items each; side 1: user
  * segments, workgroups of at most cap_items items (a longer segment gets a workgroup of its own).  which: 0 units
  * (items begin, end, splits begin, end), 1 work items in (segment, piece) order (segment, begin, end, workgroup-local
- * partial row or -1), 2 split segments (segment, first local partial row, pieces, 1 = combined in the strided order of
- * seg_combine_kernel), 3 the rebuilt unit list as (rating, q_begin, q_end, 0) (side 0), 4 { most partial rows a
- * workgroup holds, 1 if the lists could be built }.  Pass out == NULL to query count. */
+ * partial row or -1), 2 split segments (segment, first local partial row, pieces, 1 = combined in the strided order
+ * seg_combine_both_kernel adds splits of many pieces in), 3 the rebuilt unit list as (rating, q_begin, q_end, 0)
+ * (side 0), 4 { most partial rows a workgroup holds, 1 if the lists could be built }.  Pass out == NULL to query count. */
 int mmsbm_hip_layout_fused(const mmsbm_hip_layout *layout, int side, int32_t cap_items, int which, int32_t *out,
                            int64_t capacity, int64_t *count);
 /* No exception ever crosses this ABI: every entry point runs inside one handler that turns whatever is thrown

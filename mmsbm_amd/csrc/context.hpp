@@ -206,7 +206,7 @@ struct mmsbm_hip_ctx {
   size_t lds_mt = 0, lds_ma = 0;
   bool mfma_big = false;  // K or L beyond 64: the blocked forms (mfma_rows_kernel + mfma_slab_kernel)
   bool wide = false;    // K, L beyond the LDS stage: wide_matvec / wide_slab kernels (any size)
-  int nt_out = 7;          // option "nt_out" (bits: 1 T and A rows, 2 theta' rows as non-temporal stores, 4 the segments' own rows as non-temporal loads) where that pays (nt_on, stages.hpp)
+  int nt_out = 7;          // option "nt_out" (bits: 1 T and A rows, 2 theta' rows as non-temporal stores, 4 the segments' own rows as non-temporal loads) where that pays (nt_on, launch.hpp)
   int ranges_pairs = 1, ranges_users = 1;  // XCD-local work lists: ranges the gathered table is cut into
   int n_cus = 256;
   size_t lds_qa = 0;
@@ -216,7 +216,7 @@ struct mmsbm_hip_ctx {
   DevBuf<int32_t> item_grid;  // [n_items][n_ratings] pair ids (-1: none); only for dense (item, rating) grids
   DevBuf<mmsbm::Chunk> mv_chunks;
   DevBuf<mmsbm::Chunk> lik_units;  // 64-pair units for the likelihood kernel (mv_chunks may hold 256)
-  DevBuf<mmsbm::Chunk> a_chunks;   // matrix-core A launch: its own runs of units (balanced_run_units, stages.hpp), when they differ from mv_chunks
+  DevBuf<mmsbm::Chunk> a_chunks;   // matrix-core A launch: its own runs of units (balanced_run_units, mmsbm_hip.hip), when they differ from mv_chunks
   int n_a_chunks = 0, a_units = 0;   // (a_units: 64-pair units per workgroup of that launch; option "a_units")
   int n_lik_units = 0;
   DevBuf<mmsbm::WorkItem> pair_items, user_items;   // only when some segment is long

@@ -157,5 +157,13 @@ inline int nt_on(const mmsbm_hip_ctx *c) {
 inline bool mfma_possible(const mmsbm_hip_ctx *c) {
   return !c->wide && c->kp <= kMfmaMaxDim && c->lp <= kMfmaMaxDim && c->lds_mt <= kLdsMax && c->lds_ma <= kLdsMax;
 }
+// The pair stage runs on the matrix cores.  (`mfma` is never set while `wide` is: create() and option "mfma" both set it
+// through mfma_possible, and `wide` is decided once, before either.  `mfma_big` may be, and then takes wide shapes too.)
+inline bool pair_stage_on_mfma(const mmsbm_hip_ctx *c) { return c->mfma || c->mfma_big; }
+// The A launch as pair_quad_a_kernel: the tile in LDS, 512-thread workgroups, four units' rows and the tile inside the LDS
+inline bool quad_possible(const mmsbm_hip_ctx *c) {
+  return !c->wide && tile_beyond_scalar_cache(c->kp, c->lp) && c->tl_a && c->pb_threads_a == kPairBlockMax &&
+         c->lds_qa <= kLdsMax - 2048 && c->lp <= kQuadMaxL;
+}
 
 }  // namespace

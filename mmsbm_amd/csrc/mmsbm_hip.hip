@@ -123,11 +123,11 @@ void launch_log_note(const void *host_fn) { launch_log().note(host_fn); }
 // ---- the form of the pair stage the context's shape and options select ------------------------------------------------
 void stage_dense(mmsbm_hip_ctx *c) {  // T = P^T C  and the K x L slabs for p
   if (c->n_chunks == 0) return;
-  if (c->mfma_big || (!c->wide && c->mfma)) stage_dense_mfma(c);
+  if (pair_stage_on_mfma(c)) stage_dense_mfma(c);
   else stage_dense_valu(c);
 }
 void stage_matvec_a(mmsbm_hip_ctx *c, int slot, int a_slot, bool grid) {
-  if (c->mfma_big || (!c->wide && c->mfma)) stage_matvec_a_mfma(c, slot, a_slot, grid);
+  if (pair_stage_on_mfma(c)) stage_matvec_a_mfma(c, slot, a_slot, grid);
   else stage_matvec_a_valu(c, slot, a_slot, grid);
 }
 
@@ -477,6 +477,337 @@ void collect_profile(mmsbm_hip_ctx *c, float *mean_us, int *launches, int n_iter
   }
 }
 
+// ---- building a context: the steps of mmsbm_hip_create, in the order it calls them ---------------------------------------
+
+// The create-time tuning switches.  Read from the environment by every mmsbm_hip_create call (not when the library is
+// loaded: callers set and unset them between contexts), here and nowhere else.
+struct CreateKnobs {
+  bool force_wide = false;      // the wide-row kernels whatever the shape
+  int gpu_layout = -1;          // 0 / 1: the layout's sorts on the host / on the device whatever the size (-1: by size)
+  bool no_mfma = false;         // the pair stage of big tiles stays on the vector ALUs
+  int mfma_chunk = 0;           // tuning: pairs per workgroup of big tiles, a multiple of 64 in 64 .. 1,024 (0: not set)
+  bool no_ranges = false;       // no XCD-local work lists
+  int ranges_pairs = 0, ranges_users = 0;  // tuning: "pairs,users" forced range counts, 1 .. 512 each (0: not set)
+  bool no_fused_split = false;  // no whole-segment lists for the two-launch form
+  int fused_ucap = 0;           // tuning: work items per workgroup of its user side (0: not set)
+  bool no_fused = false;        // four launches per iteration whatever the size
+  bool no_itemgrid = false;     // no fixed-width grid of pair ids
+  bool timing = false;          // where the time of building a context goes (stderr)
+};
+CreateKnobs read_create_knobs() {
+  CreateKnobs k;
+  auto is_set = [](const char *name) { return std::getenv(name) != nullptr; };
+  k.force_wide = is_set("MMSBM_HIP_FORCE_WIDE");
+  if (const char *g = std::getenv("MMSBM_HIP_GPU_LAYOUT")) k.gpu_layout = std::atoi(g) != 0;
+  k.no_mfma = is_set("MMSBM_HIP_NO_MFMA");
+  if (const char *e = std::getenv("MMSBM_HIP_MFMA_CHUNK")) k.mfma_chunk = std::min(std::max(std::atoi(e) / 64 * 64, 64), kMfmaChunkPairs);
+  k.no_ranges = is_set("MMSBM_HIP_NO_RANGES");
+  if (const char *f = std::getenv("MMSBM_HIP_RANGES")) {
+    int a = 0, b = 0;
+    if (std::sscanf(f, "%d,%d", &a, &b) == 2 && a >= 1 && b >= 1 && a <= 512 && b <= 512) { k.ranges_pairs = a; k.ranges_users = b; }
+  }
+  k.no_fused_split = is_set("MMSBM_HIP_NO_FUSED_SPLIT");
+  if (const char *e = std::getenv("MMSBM_HIP_FUSED_UCAP")) k.fused_ucap = std::max(1, std::atoi(e));
+  k.no_fused = is_set("MMSBM_HIP_NO_FUSED");
+  k.no_itemgrid = is_set("MMSBM_HIP_NO_ITEMGRID");
+  k.timing = is_set("MMSBM_HIP_TIMING");
+  return k;
+}
+
+struct CreateLaps {  // (CreateKnobs::timing) one line per step: the time since the line before
+  bool on;
+  std::chrono::steady_clock::time_point clk = std::chrono::steady_clock::now();
+  void operator()(const char *what) {
+    if (!on) return;
+    const auto now = std::chrono::steady_clock::now();
+    std::fprintf(stderr, "[mmsbm_hip_create] %-28s %8.2f ms\n", what,
+                 std::chrono::duration<double, std::milli>(now - clk).count());
+    clk = now;
+  }
+};
+
+// Which side is paired with the rating, the internal dims, their padding and group codes
+void plan_sides(mmsbm_hip_ctx *c, int device, int64_t n_obs, int32_t n_users, int32_t n_items, int32_t n_ratings,
+                int32_t k_groups, int32_t l_groups, int swap_sides) {
+  c->device = device;
+  c->swapped = swap_sides > 0 || (swap_sides < 0 && n_users < n_items);
+  c->n_obs = n_obs;
+  c->ext_users = n_users; c->ext_items = n_items; c->ext_k = k_groups; c->ext_l = l_groups;
+  c->n_ratings = n_ratings;
+  if (c->swapped) {
+    c->n_users = n_items; c->n_items = n_users; c->k = l_groups; c->l = k_groups;
+  } else {
+    c->n_users = n_users; c->n_items = n_items; c->k = k_groups; c->l = l_groups;
+  }
+  c->kp = pad_dim(c->k); c->lp = pad_dim(c->l);
+  c->code_k = group_code(c->kp); c->code_l = group_code(c->lp);
+}
+
+// The geometry of the lane-per-pair stage, and whether the shape has outgrown it: arithmetic on kp, lp and n_obs only
+void plan_pair_stage(mmsbm_hip_ctx *c, const CreateKnobs &knobs) {
+  // four waves share the chunks of 4 outputs of a short row; long rows get up to 8 waves
+  // (measured: 320 threads do not beat 256 at L = 20, 512 beat 256 by 15 % at L = 50)
+  auto threads_for = [](int nch) { return nch <= 6 ? kBlock : kPairBlockMax; };
+  c->pb_threads_t = threads_for(c->lp / 4);
+  c->pb_threads_a = threads_for(c->kp / 4);
+  const int nthr = c->pb_threads_t;
+  c->pb_kt = ((c->kp / 2) * (c->lp / 4) <= kBlock / 2) ? 2 : 4;
+  const int nslot = (c->kp / c->pb_kt) * (c->lp / 4);
+  if (nslot <= nthr / 2) {
+    c->pb_spb = nslot; c->pb_nacc = 1;
+    const int room = (c->kp * (kUnitPairs + 1) + kUnitPairs * c->lp) /
+                     (nslot * 4 * c->pb_kt);  // hand-over area
+    c->pb_nsub = std::max(1, std::min(std::min(nthr / nslot, 8), 1 + room));
+  }
+  else { c->pb_spb = nthr; int n = 1; while (n * nthr < nslot) n *= 2; c->pb_nacc = n; }
+  // the rating tile sits in LDS when it is too big for the scalar cache -- unless that does not
+  // fit beside the rows, then it is read through scalar loads after all (slower, but it runs)
+  c->tl_t = tile_in_lds(c->kp, c->lp);
+  c->tl_a = tile_in_lds(c->lp, c->kp);
+  c->lds_t = pair_block_lds(c->kp, c->lp, c->tl_t);
+  c->lds_a = pair_block_lds(c->lp, c->kp, c->tl_a);
+  if (c->lds_t > kLdsMax) { c->tl_t = false; c->lds_t = pair_block_lds(c->kp, c->lp, false); }
+  if (c->lds_a > kLdsMax) { c->tl_a = false; c->lds_a = pair_block_lds(c->lp, c->kp, false); }
+  // still too large for the 64-pair LDS stage (roughly K + L > 300): the plain wide-row kernels
+  c->wide = c->lds_t > kLdsMax || c->lds_a > kLdsMax || c->pb_nacc > 4 || knobs.force_wide;
+  c->split_rows = true;
+  // small problems leave most CUs a couple of workgroups: the triple passes are then bound by the rounds of
+  // dependent gathers per segment, and eight rows in flight per group beat four (C1 16.8 -> 16.1 us, C2 29.7 ->
+  // 29.1 us per iteration); at C3 four are better (95.3 vs 97.3 us)
+  c->seg_batch = c->n_obs <= 300000 ? 8 : 4;
+}
+
+// The device, its CU count (chunk lengths and persistent grids are sized from it) and the two streams
+void open_device(mmsbm_hip_ctx *c) {
+  HIP_CHECK(hipSetDevice(c->device));
+  int cus = 0;
+  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device) == hipSuccess && cus > 0)
+    c->n_cus = cus;
+  HIP_CHECK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+  HIP_CHECK(hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
+}
+
+// The id columns in the caller's order (the element-wise kernels keep them so), internal sides: enqueued on c->stream
+void upload_ids(mmsbm_hip_ctx *c, const int32_t *iu, const int32_t *ii, const int32_t *rating) {
+  const size_t bytes = sizeof(int32_t) * static_cast<size_t>(c->n_obs);
+  HIP_CHECK(hipMemcpyAsync(c->orig_u.ptr, iu, bytes, hipMemcpyHostToDevice, c->stream));
+  HIP_CHECK(hipMemcpyAsync(c->orig_i.ptr, ii, bytes, hipMemcpyHostToDevice, c->stream));
+  HIP_CHECK(hipMemcpyAsync(c->orig_r.ptr, rating, bytes, hipMemcpyHostToDevice, c->stream));
+}
+
+// The sorts: on the host for small inputs (14 ms at 1M ratings), on the device beyond kGpuLayoutMin triples
+// (layout_gpu.hpp; CreateKnobs::gpu_layout forces either).  Returns whether they ran on the device: pair_user and
+// user_pair then stay where they were built (owned by the context's buffers from here on) and the id columns are
+// uploaded already; after the host's sorts upload_index() sends all of them.
+bool build_index(mmsbm_hip_ctx *c, const CreateKnobs &knobs, const int32_t *iu, const int32_t *ii, const int32_t *rating,
+                 CreateLaps &lap) {
+  const int64_t n_obs = c->n_obs;
+  bool gpu_layout = knobs.gpu_layout >= 0 ? knobs.gpu_layout != 0 : n_obs >= kGpuLayoutMin;
+  // (the device sort packs (rating, item) into 31 bits; sparser key spaces stay on the host)
+  if (static_cast<uint64_t>(c->n_ratings) * static_cast<uint64_t>(c->n_items) >= (uint64_t(1) << 31)) gpu_layout = false;
+  if (gpu_layout) {  // (the host's sorts check the ids themselves)
+    mmsbm::validate_triples(n_obs, c->n_users, c->n_items, c->n_ratings, iu, ii, rating);
+    lap("id checks");
+  }
+  c->orig_u.alloc(n_obs); c->orig_i.alloc(n_obs); c->orig_r.alloc(n_obs);
+  if (!gpu_layout) {
+    mmsbm::build_layout(n_obs, c->n_users, c->n_items, c->n_ratings, iu, ii, rating, 512, c->lay);
+    lap("host layout (sorts)");
+    return false;
+  }
+  if (n_obs > 0) {
+    upload_ids(c, iu, ii, rating);
+    HIP_CHECK(hipStreamSynchronize(c->stream));  // the caller's buffers are free again
+    lap("id upload");
+  }
+  mmsbm::gpu_layout::DeviceArrays dev_idx;
+  try {
+    mmsbm::gpu_layout::sort_stage(c->stream, n_obs, c->n_users, c->n_items, c->n_ratings, c->orig_u.ptr,
+                                  c->orig_i.ptr, c->orig_r.ptr, c->lay, dev_idx);
+  } catch (const std::invalid_argument &) {
+    throw;
+  } catch (const std::exception &e) {
+    throw ApiError(MMSBM_E_HIP, std::string("device layout: ") + e.what());
+  } catch (...) {
+    throw ApiError(MMSBM_E_INTERNAL, "device layout: unknown exception (not derived from std::exception)");
+  }
+  c->pair_user.ptr = dev_idx.pair_user; c->pair_user.count = static_cast<size_t>(n_obs);
+  c->user_pair.ptr = dev_idx.user_pair; c->user_pair.count = static_cast<size_t>(n_obs);
+  mmsbm::finish_layout(c->lay, 512);
+  lap("device layout (sorts)");
+  return true;
+}
+
+// Which form of the pair stage the shape gets and how many pairs a workgroup of it takes; rebuilds the unit list to
+// that length.  Returns the 64-pair units as the layout built them: the likelihood (likelihood_units_kernel: <= 64 pairs)
+// keeps that list whatever replaces it here or in build_fused_lists().
+std::vector<mmsbm::Chunk> plan_dense_forms(mmsbm_hip_ctx *c, const CreateKnobs &knobs) {
+  std::vector<mmsbm::Chunk> units64 = c->lay.mv_chunks;
+  c->n_lik_units = static_cast<int>(units64.size());
+  const bool big_tile = tile_beyond_scalar_cache(c->kp, c->lp);
+  // both launches on the matrix cores where the tile has left the scalar cache (pair_mfma_kernel)
+  c->lds_mt = pair_mfma_lds(c->kp, c->lp, true);
+  c->lds_ma = pair_mfma_lds(c->lp, c->kp, false);
+  c->mfma = mfma_possible(c) && big_tile && !knobs.no_mfma;
+  // K or L beyond 64: the blocked matrix-core kernels take over from the lane-per-pair stage with its tile in
+  // scalar loads and from the wide-row kernels
+  // Skinny tiles too (a side below 16 groups, e.g. 600 x 5 or 3 x 1,024): three quarters of a 16-wide tile are
+  // padding there, and it is still several times faster than the alternatives -- the wide-row kernels have one
+  // thread per output column (8 of 256 threads busy at L = 5), the lane-per-pair stage streams a 38 KB tile
+  // through the scalar cache.  1M ratings, T+S / A launch: 600 x 5 2,336 / 124 -> 380 / 115 us, 1,024 x 3
+  // 5,822 / 152 -> 621 / 171, 8 x 520 471 / 927 -> 247 / 191, 3 x 1,024 470 / 3,219 -> 430 / 346, 300 x 8
+  // 310 / 91 -> 197 / 53 (scripts/skinny_time.py, round 3).
+  c->mfma_big = !c->mfma && big_tile && !knobs.no_mfma;
+  // big K x L tiles: four 64-pair units per pair_block workgroup (4x fewer slabs to write + add); on the matrix cores
+  // eight while that still leaves every CU a few rounds of workgroups (C5: T+S 358 -> 342 us, half the slabs for
+  // eta_p: 123 -> 111 us; 768 or 1,024 pairs per workgroup are slower)
+  int big_chunk = 4 * mmsbm::kMvChunkPairs;
+  if (c->mfma && c->lay.n_pairs >= 2 * big_chunk * 4 * c->n_cus) big_chunk *= 2;
+  if (knobs.mfma_chunk > 0) big_chunk = knobs.mfma_chunk;
+  c->mv_chunk_pairs = c->wide ? kWideChunkPairs : (big_tile ? big_chunk : mmsbm::kMvChunkPairs);
+  if (c->wide || big_tile) mmsbm::build_mv_chunks(c->lay, c->mv_chunk_pairs);
+  // long rows: the mat-vec's outputs go to memory straight from registers (C5: -6 % on both
+  // pair_block launches); short rows are cheaper transposed through LDS and copied out flat
+  // (C3: direct stores cost +1.1 / +1.7 us)
+  c->direct_out = big_tile;
+  // ... and the A launch as a persistent four-unit pipeline where the tile sits in LDS and
+  // everything fits (C5: 312 -> 259 us)
+  c->lds_qa = (static_cast<size_t>(kQuadUnits) * c->lp * (kUnitPairs + 1) + static_cast<size_t>(c->lp) * c->kp) *
+              sizeof(double);
+  c->quad_a = quad_possible(c) && big_chunk == 4 * mmsbm::kMvChunkPairs;
+  c->n_pairs = c->lay.n_pairs;
+  c->n_chunks = static_cast<int>(c->lay.mv_chunks.size());
+  return units64;
+}
+
+// Dense data: XCD-local work lists (layout.hpp) -- every segment cut at fixed borders of the gathered index, each
+// range's work on one XCD, whose L2 then holds that slice of the table
+void build_range_worklists(mmsbm_hip_ctx *c, const CreateKnobs &knobs, bool gpu_layout) {
+  if (c->kp > kMaxGroupRow) {  // rows beyond the widest group-of-lanes instantiation: seg_wide_kernel, whole segments
+    c->lay.pair_work = mmsbm::WorkList();
+    c->lay.user_work = mmsbm::WorkList();
+    return;
+  }
+  if (knobs.no_ranges) return;
+  const int64_t n_obs = c->n_obs;
+  const int per = kBlock / group_lanes(c->code_k);
+  const size_t row_bytes = static_cast<size_t>(c->kp) * sizeof(double);
+  const int64_t mean_p = c->n_pairs > 0 ? n_obs / c->n_pairs : 0, mean_u = n_obs / std::max(c->n_users, 1);
+  int rp = mmsbm::range_count(static_cast<size_t>(c->n_users) * row_bytes, mean_p);   // pair pass gathers theta
+  int ru = mmsbm::range_count(static_cast<size_t>(c->n_pairs) * row_bytes, mean_u);   // user pass gathers A
+  // ... unless the table's hot rows (what one L2 keeps by itself) already take most of the gathers:
+  // theta rows are gathered once per triple of that user, A rows once per triple of that pair
+  // Where the rows one L2 keeps by itself already take half of the gathers (heavy-tailed gather
+  // counts, or a table only a few times an L2) there is little left to win: measured +16 % (50M
+  // ratings, log-normal item popularity, 8.5 MB table) and +24 % (Zipf(1.2) degrees) if cut anyway.
+  const int64_t fit = static_cast<int64_t>(mmsbm::kRangeSliceBytes / row_bytes);
+  if (rp > 1 && mmsbm::hot_fraction(c->lay.user_off, fit) > 0.5) rp = 1;
+  if (ru > 1 && mmsbm::hot_fraction(c->lay.pair_off, fit) > 0.5) ru = 1;
+  if (knobs.ranges_pairs > 0) { rp = knobs.ranges_pairs; ru = knobs.ranges_users; }
+  // (device layout: the index arrays live on the device, so the borders are found there and only the
+  // cut positions -- segments x (ranges + 1) integers -- come back)
+  std::vector<int32_t> cuts_p, cuts_u;
+  if (gpu_layout && rp > 1) cuts_p = mmsbm::gpu_layout::range_cuts(c->stream, c->lay.pair_off, c->pair_user.ptr, c->n_users, rp);
+  if (gpu_layout && ru > 1) cuts_u = mmsbm::gpu_layout::range_cuts(c->stream, c->lay.user_off, c->user_pair.ptr, c->n_pairs, ru);
+  if (rp > 1)
+    mmsbm::build_worklist_ranges(c->lay.pair_off, c->lay.pair_user.data(), c->n_users, rp,
+                                 mmsbm::item_length(n_obs, c->n_pairs), per, c->lay.pair_work,
+                                 gpu_layout ? cuts_p.data() : nullptr);
+  if (ru > 1)
+    mmsbm::build_worklist_ranges(c->lay.user_off, c->lay.user_pair.data(), c->n_pairs, ru,
+                                 mmsbm::item_length(n_obs, c->n_users), per, c->lay.user_work,
+                                 gpu_layout ? cuts_u.data() : nullptr);
+  c->ranges_pairs = rp;
+  c->ranges_users = ru;
+}
+
+// Whole pair segments for the workgroups of the two-launch form: the 64-pair units rebuilt with at most 64 work items
+// each.  The capped unit list REPLACES the plain one -- both forms of the iteration then run it, so that their S sums
+// associate the same way -- but only once it is certain that the two-launch form can use it: a pair of more than 64
+// pieces, or partial rows beyond the LDS, and the plain list is back.
+void build_fused_pair_lists(mmsbm_hip_ctx *c) {
+  const mmsbm::SegPieces sp = mmsbm::segment_pieces(c->lay.pair_off, c->lay.pair_work);
+  const std::vector<mmsbm::Chunk> plain_chunks = c->lay.mv_chunks;
+  const std::vector<int32_t> plain_off = c->lay.mv_chunk_off;
+  if (mmsbm::build_mv_chunks_capped(c->lay, sp, mmsbm::kMvChunkPairs, kUnitPairs)) {
+    const mmsbm::FusedLists fl = mmsbm::build_fused_pairs(c->lay, sp);
+    if (pairs_fused_lds(c->kp, c->lp, fl.max_parts) <= kLdsMax) {
+      c->fp_units.upload(fl.units, c->stream); c->fp_items.upload(fl.items, c->stream);
+      c->fp_splits.upload(fl.splits, c->stream);
+      HIP_CHECK(hipStreamSynchronize(c->stream));  // (`fl` is a local)
+      c->fp_max_parts = fl.max_parts;
+      c->fs_pairs = true;
+    }
+  }
+  if (!c->fs_pairs) { c->lay.mv_chunks = plain_chunks; c->lay.mv_chunk_off = plain_off; }
+  c->n_chunks = static_cast<int>(c->lay.mv_chunks.size());  // (either list)
+}
+// ... and whole user segments: a user whose pieces' partial rows exceed the LDS budget leaves the data with the
+// separate launches
+void build_fused_user_lists(mmsbm_hip_ctx *c, const CreateKnobs &knobs) {
+  const mmsbm::SegPieces sp = mmsbm::segment_pieces(c->lay.user_off, c->lay.user_work);
+  // work items per workgroup: one round of its groups of lanes
+  const int ucap = knobs.fused_ucap > 0 ? knobs.fused_ucap : kBlock / group_lanes(c->code_k);
+  const mmsbm::FusedLists fl = mmsbm::build_fused_users(sp, ucap);
+  if (static_cast<size_t>(fl.max_parts) * c->kp * sizeof(double) > kFusedSplitLds) return;
+  c->fu_units.upload(fl.units, c->stream); c->fu_items.upload(fl.items, c->stream);
+  c->fu_splits.upload(fl.splits, c->stream);
+  HIP_CHECK(hipStreamSynchronize(c->stream));  // (`fl` is a local)
+  c->fu_max_parts = fl.max_parts;
+  c->fu_blocks = static_cast<int>(fl.units.size());
+  c->fs_users = true;
+}
+// Small problems with uneven degrees (round 4): their segments are cut into pieces by build_range_worklists(); give
+// every workgroup of the two-launch form WHOLE segments (layout.hpp: FusedLists) so that the pieces' partial rows meet
+// in its LDS instead of in a combine launch.
+void build_fused_lists(mmsbm_hip_ctx *c, const CreateKnobs &knobs, CreateLaps &lap) {
+  const bool cut_p = !c->lay.pair_work.splits.empty(), cut_u = !c->lay.user_work.splits.empty();
+  if (c->n_obs > kFusedRatingsMax || !fused_shape_ok(c) || knobs.no_fused_split || !(cut_p || cut_u)) return;
+  if (cut_p) build_fused_pair_lists(c);
+  if (cut_u) build_fused_user_lists(c, knobs);
+  lap("whole-segment lists (two launches)");
+}
+
+// At least half of all (item, rating) combinations occur and R is small: a fixed-width grid of pair ids
+void upload_item_grid(mmsbm_hip_ctx *c) {
+  const int n_ratings = c->n_ratings;
+  if (n_ratings > 16 || static_cast<int64_t>(c->n_pairs) * 2 < static_cast<int64_t>(c->n_items) * n_ratings) return;
+  std::vector<int32_t> grid(static_cast<size_t>(c->n_items) * n_ratings, -1);
+  for (int r = 0; r < n_ratings; ++r)
+    for (int32_t q = c->lay.rating_off[static_cast<size_t>(r)]; q < c->lay.rating_off[static_cast<size_t>(r) + 1]; ++q)
+      grid[static_cast<size_t>(c->lay.pair_item[static_cast<size_t>(q)]) * n_ratings + r] = q;
+  c->item_grid.upload(grid, c->stream);
+  HIP_CHECK(hipStreamSynchronize(c->stream));  // `grid` is a local
+}
+
+// Everything the kernels index by, onto the device.  After the host's sorts (`gpu_layout` false) that includes
+// pair_user, user_pair and the id columns; the device's sorts left all five in place (build_index).
+void upload_index(mmsbm_hip_ctx *c, const CreateKnobs &knobs, bool gpu_layout, const std::vector<mmsbm::Chunk> &units64,
+                  const int32_t *iu, const int32_t *ii, const int32_t *rating) {
+  hipStream_t s = c->stream;
+  c->pair_off.upload(c->lay.pair_off, s);
+  c->pair_item.upload(c->lay.pair_item, s);
+  c->user_off.upload(c->lay.user_off, s);
+  if (!gpu_layout) {
+    c->pair_user.upload(c->lay.pair_user, s);
+    c->user_pair.upload(c->lay.user_pair, s);
+  }
+  c->item_off.upload(c->lay.item_off, s);
+  c->item_pairs.upload(c->lay.item_pairs, s);
+  c->item_deg.upload(c->lay.item_deg, s);
+  if (!knobs.no_itemgrid) upload_item_grid(c);
+  c->mv_chunks.upload(c->lay.mv_chunks, s);
+  build_a_runs(c, 0);
+  c->lik_units.upload(units64, s);
+  c->mv_chunk_off.upload(c->lay.mv_chunk_off, s);
+  c->pair_items.upload(c->lay.pair_work.items, s);
+  c->user_items.upload(c->lay.user_work.items, s);
+  c->pair_splits.upload(c->lay.pair_work.splits, s);
+  c->user_splits.upload(c->lay.user_work.splits, s);
+  if (!gpu_layout && c->n_obs > 0) upload_ids(c, iu, ii, rating);
+  HIP_CHECK(hipStreamSynchronize(s));  // nothing of the caller's (or create's) host memory is still being read
+}
+
 }  // namespace
 
 
@@ -564,278 +895,28 @@ int mmsbm_hip_create(int device, int64_t n_obs, int32_t n_users, int32_t n_items
       throw ApiError(MMSBM_E_NODEVICE, "no HIP device available (this library has no CPU path)");
     if (device < 0 || device >= ndev) throw std::invalid_argument("device index out of range");
 
-    // MMSBM_HIP_TIMING=1: where the time of building a context goes (stderr)
-    const bool timing = std::getenv("MMSBM_HIP_TIMING") != nullptr;
-    auto clk = std::chrono::steady_clock::now();
-    auto lap = [&](const char *what) {
-      if (!timing) return;
-      const auto now = std::chrono::steady_clock::now();
-      std::fprintf(stderr, "[mmsbm_hip_create] %-28s %8.2f ms\n", what,
-                   std::chrono::duration<double, std::milli>(now - clk).count());
-      clk = now;
-    };
+    const CreateKnobs knobs = read_create_knobs();
+    CreateLaps lap{knobs.timing};
     std::unique_ptr<mmsbm_hip_ctx> c(new mmsbm_hip_ctx());
-    c->device = device;
-    c->swapped = swap_sides > 0 || (swap_sides < 0 && n_users < n_items);
-    c->n_obs = n_obs;
-    c->ext_users = n_users; c->ext_items = n_items; c->ext_k = k_groups; c->ext_l = l_groups;
-    c->n_ratings = n_ratings;
-    const int32_t *iu = user, *ii = item;
-    if (c->swapped) {
-      c->n_users = n_items; c->n_items = n_users; c->k = l_groups; c->l = k_groups;
-      iu = item; ii = user;
-    } else {
-      c->n_users = n_users; c->n_items = n_items; c->k = k_groups; c->l = l_groups;
-    }
-    c->kp = pad_dim(c->k); c->lp = pad_dim(c->l);
-    c->code_k = group_code(c->kp); c->code_l = group_code(c->lp);
-    {
-      // four waves share the chunks of 4 outputs of a short row; long rows get up to 8 waves
-      // (measured: 320 threads do not beat 256 at L = 20, 512 beat 256 by 15 % at L = 50)
-      auto threads_for = [](int nch) { return nch <= 6 ? kBlock : kPairBlockMax; };
-      c->pb_threads_t = threads_for(c->lp / 4);
-      c->pb_threads_a = threads_for(c->kp / 4);
-      const int nthr = c->pb_threads_t;
-      c->pb_kt = ((c->kp / 2) * (c->lp / 4) <= kBlock / 2) ? 2 : 4;
-      const int nslot = (c->kp / c->pb_kt) * (c->lp / 4);
-      if (nslot <= nthr / 2) {
-        c->pb_spb = nslot; c->pb_nacc = 1;
-        const int room = (c->kp * (kUnitPairs + 1) + kUnitPairs * c->lp) /
-                         (nslot * 4 * c->pb_kt);  // hand-over area
-        c->pb_nsub = std::max(1, std::min(std::min(nthr / nslot, 8), 1 + room));
-      }
-      else { c->pb_spb = nthr; int n = 1; while (n * nthr < nslot) n *= 2; c->pb_nacc = n; }
-    }
-    // the rating tile sits in LDS when it is too big for the scalar cache -- unless that does not
-    // fit beside the rows, then it is read through scalar loads after all (slower, but it runs)
-    c->tl_t = tile_in_lds(c->kp, c->lp);
-    c->tl_a = tile_in_lds(c->lp, c->kp);
-    c->lds_t = pair_block_lds(c->kp, c->lp, c->tl_t);
-    c->lds_a = pair_block_lds(c->lp, c->kp, c->tl_a);
-    if (c->lds_t > kLdsMax) { c->tl_t = false; c->lds_t = pair_block_lds(c->kp, c->lp, false); }
-    if (c->lds_a > kLdsMax) { c->tl_a = false; c->lds_a = pair_block_lds(c->lp, c->kp, false); }
-    // still too large for the 64-pair LDS stage (roughly K + L > 300): the plain wide-row kernels
-    c->wide = c->lds_t > kLdsMax || c->lds_a > kLdsMax || c->pb_nacc > 4 ||
-              std::getenv("MMSBM_HIP_FORCE_WIDE") != nullptr;
-    c->split_rows = true;
-    // small problems leave most CUs a couple of workgroups: the triple passes are then bound by the rounds of
-    // dependent gathers per segment, and eight rows in flight per group beat four (C1 16.8 -> 16.1 us, C2 29.7 ->
-    // 29.1 us per iteration); at C3 four are better (95.3 vs 97.3 us)
-    c->seg_batch = n_obs <= 300000 ? 8 : 4;
-
+    plan_sides(c.get(), device, n_obs, n_users, n_items, n_ratings, k_groups, l_groups, swap_sides);
+    const int32_t *iu = c->swapped ? item : user, *ii = c->swapped ? user : item;  // the id columns of the internal sides
+    plan_pair_stage(c.get(), knobs);
     lap("checks");
-    // The sorts: on the host for small inputs (14 ms at 1M ratings), on the device beyond
-    // kGpuLayoutMin triples (layout_gpu.hpp; MMSBM_HIP_GPU_LAYOUT=0/1 forces either).  The id columns
-    // are uploaded first in both cases (the element-wise kernels keep them in the original order).
-    HIP_CHECK(hipSetDevice(device));
-    {  // (before anything is sized from it: chunk lengths, persistent grids)
-      int cus = 0;
-      if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0)
-        c->n_cus = cus;
-    }
-    HIP_CHECK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-    HIP_CHECK(hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
-    bool gpu_layout = n_obs >= kGpuLayoutMin;
-    if (const char *g = std::getenv("MMSBM_HIP_GPU_LAYOUT")) gpu_layout = std::atoi(g) != 0;
-    // (the device sort packs (rating, item) into 31 bits; sparser key spaces stay on the host)
-    if (static_cast<uint64_t>(n_ratings) * static_cast<uint64_t>(c->n_items) >= (uint64_t(1) << 31)) gpu_layout = false;
-    mmsbm::gpu_layout::DeviceArrays dev_idx;
-    if (gpu_layout) {
-      mmsbm::validate_triples(n_obs, c->n_users, c->n_items, n_ratings, iu, ii, rating);
-      lap("id checks");
-    }
-    {
-      const size_t bytes = sizeof(int32_t) * static_cast<size_t>(n_obs);
-      c->orig_u.alloc(n_obs); c->orig_i.alloc(n_obs); c->orig_r.alloc(n_obs);
-      if (n_obs > 0 && gpu_layout) {  // (host layout: uploaded after its own id checks, below)
-        HIP_CHECK(hipMemcpyAsync(c->orig_u.ptr, iu, bytes, hipMemcpyHostToDevice, c->stream));
-        HIP_CHECK(hipMemcpyAsync(c->orig_i.ptr, ii, bytes, hipMemcpyHostToDevice, c->stream));
-        HIP_CHECK(hipMemcpyAsync(c->orig_r.ptr, rating, bytes, hipMemcpyHostToDevice, c->stream));
-        HIP_CHECK(hipStreamSynchronize(c->stream));  // the caller's buffers are free again
-        lap("id upload");
-      }
-    }
-    if (gpu_layout) {
-      try {
-        mmsbm::gpu_layout::sort_stage(c->stream, n_obs, c->n_users, c->n_items, n_ratings, c->orig_u.ptr,
-                                      c->orig_i.ptr, c->orig_r.ptr, c->lay, dev_idx);
-      } catch (const std::invalid_argument &) {
-        throw;
-      } catch (const std::exception &e) {
-        throw ApiError(MMSBM_E_HIP, std::string("device layout: ") + e.what());
-      } catch (...) {
-        throw ApiError(MMSBM_E_INTERNAL, "device layout: unknown exception (not derived from std::exception)");
-      }
-      c->pair_user.ptr = dev_idx.pair_user; c->pair_user.count = static_cast<size_t>(n_obs);
-      c->user_pair.ptr = dev_idx.user_pair; c->user_pair.count = static_cast<size_t>(n_obs);
-      mmsbm::finish_layout(c->lay, 512);
-      lap("device layout (sorts)");
-    } else {
-      mmsbm::build_layout(n_obs, c->n_users, c->n_items, n_ratings, iu, ii, rating, 512, c->lay);
-      lap("host layout (sorts)");
-    }
-    // big K x L tiles: four 64-pair units per pair_block workgroup (4x fewer slabs to write + add)
-    const std::vector<mmsbm::Chunk> units64 = c->lay.mv_chunks;  // likelihood_units_kernel: <= 64 pairs
-    c->n_lik_units = static_cast<int>(units64.size());
-    // ... and both launches on the matrix cores where the tile has left the scalar cache (pair_mfma_kernel),
-    // with eight units per workgroup while that still leaves every CU a few rounds of workgroups (C5: T+S
-    // 358 -> 342 us, half the slabs for eta_p: 123 -> 111 us; 768 or 1,024 pairs per workgroup are slower)
-    c->lds_mt = pair_mfma_lds(c->kp, c->lp, true);
-    c->lds_ma = pair_mfma_lds(c->lp, c->kp, false);
-    c->mfma = mfma_possible(c.get()) && c->kp * c->lp > 1024 && std::getenv("MMSBM_HIP_NO_MFMA") == nullptr;
-    // K or L beyond 64: the blocked matrix-core kernels take over from the lane-per-pair stage with its tile in
-    // scalar loads and from the wide-row kernels
-    // Skinny tiles too (a side below 16 groups, e.g. 600 x 5 or 3 x 1,024): three quarters of a 16-wide tile are
-    // padding there, and it is still several times faster than the alternatives -- the wide-row kernels have one
-    // thread per output column (8 of 256 threads busy at L = 5), the lane-per-pair stage streams a 38 KB tile
-    // through the scalar cache.  1M ratings, T+S / A launch: 600 x 5 2,336 / 124 -> 380 / 115 us, 1,024 x 3
-    // 5,822 / 152 -> 621 / 171, 8 x 520 471 / 927 -> 247 / 191, 3 x 1,024 470 / 3,219 -> 430 / 346, 300 x 8
-    // 310 / 91 -> 197 / 53 (scripts/skinny_time.py, round 3).
-    c->mfma_big = !c->mfma && c->kp * c->lp > 1024 && std::getenv("MMSBM_HIP_NO_MFMA") == nullptr;
-    int big_chunk = 4 * mmsbm::kMvChunkPairs;
-    if (c->mfma && c->lay.n_pairs >= 2 * big_chunk * 4 * c->n_cus) big_chunk *= 2;
-    if (const char *e = std::getenv("MMSBM_HIP_MFMA_CHUNK")) big_chunk = std::min(std::max(std::atoi(e) / 64 * 64, 64), kMfmaChunkPairs);  // (tuning)
-    if (c->wide) mmsbm::build_mv_chunks(c->lay, kWideChunkPairs);
-    else if (c->kp * c->lp > 1024) mmsbm::build_mv_chunks(c->lay, big_chunk);
-    c->mv_chunk_pairs = c->wide ? kWideChunkPairs : (c->kp * c->lp > 1024 ? big_chunk : mmsbm::kMvChunkPairs);
-    // long rows: the mat-vec's outputs go to memory straight from registers (C5: -6 % on both
-    // pair_block launches); short rows are cheaper transposed through LDS and copied out flat
-    // (C3: direct stores cost +1.1 / +1.7 us)
-    c->direct_out = c->kp * c->lp > 1024;
-    // ... and the A launch as a persistent four-unit pipeline where the tile sits in LDS and
-    // everything fits (C5: 312 -> 259 us)
-    c->lds_qa = (static_cast<size_t>(kQuadUnits) * c->lp * (kUnitPairs + 1) + static_cast<size_t>(c->lp) * c->kp) *
-                sizeof(double);
-    c->quad_a = !c->wide && c->kp * c->lp > 1024 && c->tl_a && c->pb_threads_a == kPairBlockMax &&
-                c->lds_qa <= kLdsMax - 2048 && c->lp <= kQuadMaxL && big_chunk == 4 * mmsbm::kMvChunkPairs;
-    c->n_pairs = c->lay.n_pairs;
-    c->n_chunks = static_cast<int>(c->lay.mv_chunks.size());
-    // dense data: XCD-local work lists (layout.hpp) -- every segment cut at fixed borders of the
-    // gathered index, each range's work on one XCD, whose L2 then holds that slice of the table
-    if (c->kp > kMaxGroupRow) {  // rows beyond the widest group-of-lanes instantiation: seg_wide_kernel, whole segments
-      c->lay.pair_work = mmsbm::WorkList();
-      c->lay.user_work = mmsbm::WorkList();
-    } else if (std::getenv("MMSBM_HIP_NO_RANGES") == nullptr) {
-      const int per = kBlock / group_lanes(c->code_k);
-      const size_t row_bytes = static_cast<size_t>(c->kp) * sizeof(double);
-      const int64_t mean_p = c->n_pairs > 0 ? n_obs / c->n_pairs : 0, mean_u = n_obs / std::max(c->n_users, 1);
-      int rp = mmsbm::range_count(static_cast<size_t>(c->n_users) * row_bytes, mean_p);   // pair pass gathers theta
-      int ru = mmsbm::range_count(static_cast<size_t>(c->n_pairs) * row_bytes, mean_u);   // user pass gathers A
-      // ... unless the table's hot rows (what one L2 keeps by itself) already take most of the gathers:
-      // theta rows are gathered once per triple of that user, A rows once per triple of that pair
-      // Where the rows one L2 keeps by itself already take half of the gathers (heavy-tailed gather
-      // counts, or a table only a few times an L2) there is little left to win: measured +16 % (50M
-      // ratings, log-normal item popularity, 8.5 MB table) and +24 % (Zipf(1.2) degrees) if cut anyway.
-      const int64_t fit = static_cast<int64_t>(mmsbm::kRangeSliceBytes / row_bytes);
-      if (rp > 1 && mmsbm::hot_fraction(c->lay.user_off, fit) > 0.5) rp = 1;
-      if (ru > 1 && mmsbm::hot_fraction(c->lay.pair_off, fit) > 0.5) ru = 1;
-      if (const char *f = std::getenv("MMSBM_HIP_RANGES")) {  // tuning: "pairs,users" forced range counts
-        int a = 0, b = 0;
-        if (std::sscanf(f, "%d,%d", &a, &b) == 2 && a >= 1 && b >= 1 && a <= 512 && b <= 512) { rp = a; ru = b; }
-      }
-      // (device layout: the index arrays live on the device, so the borders are found there and only the
-      // cut positions -- segments x (ranges + 1) integers -- come back)
-      std::vector<int32_t> cuts_p, cuts_u;
-      if (gpu_layout && rp > 1) cuts_p = mmsbm::gpu_layout::range_cuts(c->stream, c->lay.pair_off, c->pair_user.ptr, c->n_users, rp);
-      if (gpu_layout && ru > 1) cuts_u = mmsbm::gpu_layout::range_cuts(c->stream, c->lay.user_off, c->user_pair.ptr, c->n_pairs, ru);
-      if (rp > 1)
-        mmsbm::build_worklist_ranges(c->lay.pair_off, c->lay.pair_user.data(), c->n_users, rp,
-                                     mmsbm::item_length(n_obs, c->n_pairs), per, c->lay.pair_work,
-                                     gpu_layout ? cuts_p.data() : nullptr);
-      if (ru > 1)
-        mmsbm::build_worklist_ranges(c->lay.user_off, c->lay.user_pair.data(), c->n_pairs, ru,
-                                     mmsbm::item_length(n_obs, c->n_users), per, c->lay.user_work,
-                                     gpu_layout ? cuts_u.data() : nullptr);
-      c->ranges_pairs = rp;
-      c->ranges_users = ru;
-    }
+    open_device(c.get());
+    const bool gpu_layout = build_index(c.get(), knobs, iu, ii, rating, lap);
+    // (after open_device: chunk lengths are sized from the CU count.  After plan_pair_stage: `wide` decides first.)
+    const std::vector<mmsbm::Chunk> units64 = plan_dense_forms(c.get(), knobs);
+    build_range_worklists(c.get(), knobs, gpu_layout);
     lap("xcd-local work lists");
-    // Small problems with uneven degrees (round 4): segments are cut into pieces above; give every workgroup of the
-    // two-launch form WHOLE segments (layout.hpp: FusedLists) so that the pieces' partial rows meet in its LDS instead
-    // of in a combine launch.  Pair side: the 64-pair units are rebuilt with at most 64 work items each (both forms
-    // of the iteration then use these units: their S sums associate the same way); a pair of more than 64 pieces, or a
-    // user whose pieces' partial rows exceed the LDS budget, leaves the data with the separate launches.
-    if (n_obs <= kFusedRatingsMax && fused_shape_ok(c.get()) && std::getenv("MMSBM_HIP_NO_FUSED_SPLIT") == nullptr &&
-        (!c->lay.pair_work.splits.empty() || !c->lay.user_work.splits.empty())) {
-      const int lanes = group_lanes(c->code_k);
-      if (!c->lay.pair_work.splits.empty()) {
-        const mmsbm::SegPieces sp = mmsbm::segment_pieces(c->lay.pair_off, c->lay.pair_work);
-        // (the capped unit list REPLACES the plain one -- both forms of the iteration then run it, so that their S sums
-        // associate the same way -- but only once it is certain that the two-launch form can use it: kept aside until then)
-        const std::vector<mmsbm::Chunk> plain_chunks = c->lay.mv_chunks;
-        const std::vector<int32_t> plain_off = c->lay.mv_chunk_off;
-        if (mmsbm::build_mv_chunks_capped(c->lay, sp, mmsbm::kMvChunkPairs, kUnitPairs)) {
-          const mmsbm::FusedLists fl = mmsbm::build_fused_pairs(c->lay, sp);
-          if (pairs_fused_lds(c->kp, c->lp, fl.max_parts) <= kLdsMax) {
-            c->fp_units.upload(fl.units, c->stream); c->fp_items.upload(fl.items, c->stream);
-            c->fp_splits.upload(fl.splits, c->stream);
-            HIP_CHECK(hipStreamSynchronize(c->stream));  // (`fl` is a local)
-            c->fp_max_parts = fl.max_parts;
-            c->fs_pairs = true;
-          }
-        }
-        if (!c->fs_pairs) { c->lay.mv_chunks = plain_chunks; c->lay.mv_chunk_off = plain_off; }
-        c->n_chunks = static_cast<int>(c->lay.mv_chunks.size());
-      }
-      if (!c->lay.user_work.splits.empty()) {
-        const mmsbm::SegPieces sp = mmsbm::segment_pieces(c->lay.user_off, c->lay.user_work);
-        int ucap = kBlock / lanes;  // work items per workgroup: one round of its groups of lanes
-        if (const char *e = std::getenv("MMSBM_HIP_FUSED_UCAP")) ucap = std::max(1, std::atoi(e));  // (tuning)
-        const mmsbm::FusedLists fl = mmsbm::build_fused_users(sp, ucap);
-        if (static_cast<size_t>(fl.max_parts) * c->kp * sizeof(double) <= kFusedSplitLds) {
-          c->fu_units.upload(fl.units, c->stream); c->fu_items.upload(fl.items, c->stream);
-          c->fu_splits.upload(fl.splits, c->stream);
-          HIP_CHECK(hipStreamSynchronize(c->stream));
-          c->fu_max_parts = fl.max_parts;
-          c->fu_blocks = static_cast<int>(fl.units.size());
-          c->fs_users = true;
-        }
-      }
-      lap("whole-segment lists (two launches)");
-    }
-    // small problems (where eight rows in flight pay, above): two launches per iteration instead of four
-    c->fused = n_obs <= kFusedRatingsMax && fused_possible(c.get()) && std::getenv("MMSBM_HIP_NO_FUSED") == nullptr;
-
-    hipStream_t s = c->stream;
-    c->pair_off.upload(c->lay.pair_off, s);
-    c->pair_item.upload(c->lay.pair_item, s);
-    c->user_off.upload(c->lay.user_off, s);
-    if (!gpu_layout) {  // (the device layout left these two where they were built)
-      c->pair_user.upload(c->lay.pair_user, s);
-      c->user_pair.upload(c->lay.user_pair, s);
-    }
-    c->item_off.upload(c->lay.item_off, s);
-    c->item_pairs.upload(c->lay.item_pairs, s);
-    c->item_deg.upload(c->lay.item_deg, s);
-    // at least half of all (item, rating) combinations occur and R is small: fixed-width grid of pair ids
-    if (n_ratings <= 16 && static_cast<int64_t>(c->n_pairs) * 2 >= static_cast<int64_t>(c->n_items) * n_ratings &&
-        std::getenv("MMSBM_HIP_NO_ITEMGRID") == nullptr) {
-      std::vector<int32_t> grid(static_cast<size_t>(c->n_items) * n_ratings, -1);
-      for (int r = 0; r < n_ratings; ++r)
-        for (int32_t q = c->lay.rating_off[static_cast<size_t>(r)]; q < c->lay.rating_off[static_cast<size_t>(r) + 1]; ++q)
-          grid[static_cast<size_t>(c->lay.pair_item[static_cast<size_t>(q)]) * n_ratings + r] = q;
-      c->item_grid.upload(grid, s);
-      HIP_CHECK(hipStreamSynchronize(s));  // `grid` is a local
-    }
-    c->mv_chunks.upload(c->lay.mv_chunks, s);
-    build_a_runs(c.get(), 0);
-    c->lik_units.upload(units64, s);
-    c->mv_chunk_off.upload(c->lay.mv_chunk_off, s);
-    c->pair_items.upload(c->lay.pair_work.items, s);
-    c->user_items.upload(c->lay.user_work.items, s);
-    c->pair_splits.upload(c->lay.pair_work.splits, s);
-    c->user_splits.upload(c->lay.user_work.splits, s);
-    if (!gpu_layout && n_obs > 0) {
-      const size_t bytes = sizeof(int32_t) * static_cast<size_t>(n_obs);
-      HIP_CHECK(hipMemcpyAsync(c->orig_u.ptr, iu, bytes, hipMemcpyHostToDevice, s));
-      HIP_CHECK(hipMemcpyAsync(c->orig_i.ptr, ii, bytes, hipMemcpyHostToDevice, s));
-      HIP_CHECK(hipMemcpyAsync(c->orig_r.ptr, rating, bytes, hipMemcpyHostToDevice, s));
-    }
-    HIP_CHECK(hipStreamSynchronize(s));  // nothing of the caller's (or this function's) host memory is still being read
+    // (after plan_dense_forms: fused_shape_ok reads n_chunks, mfma, direct_out and mv_chunk_pairs)
+    build_fused_lists(c.get(), knobs, lap);
+    // small problems (where eight rows in flight pay, plan_pair_stage): two launches per iteration instead of four
+    c->fused = n_obs <= kFusedRatingsMax && fused_possible(c.get()) && !knobs.no_fused;
+    upload_index(c.get(), knobs, gpu_layout, units64, iu, ii, rating);
     lap("index uploads");
     alloc_state(c.get(), 1);
     c->lik_part.alloc(4096);
-    HIP_CHECK(hipStreamSynchronize(s));
+    HIP_CHECK(hipStreamSynchronize(c->stream));
     lap("state allocation");
     *out = c.release();
   });
@@ -1575,8 +1656,9 @@ int mmsbm_hip_set_option(mmsbm_hip_ctx *ctx, const char *name, double value) {
       if (g != 0 && g != 1 && g != 2 && g != 4 && g != 8) throw std::invalid_argument("lik_g: 0, 1, 2, 4 or 8");
       ctx->lik_g = g;
     } else if (key == "quad") {  // 0: the A launch through pair_block like every other shape
-      ctx->quad_a = value != 0.0 && !ctx->wide && ctx->kp * ctx->lp > 1024 && ctx->tl_a &&
-                    ctx->pb_threads_a == kPairBlockMax && ctx->lds_qa <= kLdsMax - 2048 && ctx->lp <= kQuadMaxL;
+      // (create() also requires unit runs of four -- big_chunk == 4 * kMvChunkPairs, plan_dense_forms -- and this option
+      // never has: with longer runs it turns on what create() left off.  Whether that is meant is open; both are as they were)
+      ctx->quad_a = value != 0.0 && quad_possible(ctx);
     } else if (key == "fused") {  // two launches per iteration (small tiles, unsplit segments); any problem size
       if (value != 0.0 && !fused_possible(ctx)) throw std::invalid_argument("fused: not available for this shape / data");
       ctx->fused = value != 0.0;

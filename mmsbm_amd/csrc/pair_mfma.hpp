@@ -228,7 +228,7 @@ __global__ __launch_bounds__(NT, NT == 512 ? MMSBM_MFMA_WPE : 2) void pair_mfma_
           const int r = trow0 + lk + 4 * g;
           if (r < np) {
             double *dst = pair_out_ptr(pa, out, out_tail, static_cast<size_t>(q0 + r), col);
-            if (GATHER && (pa.nt & 2)) __builtin_nontemporal_store(acc_t[n][g], dst);  // (A rows: stages.hpp, nt_on)
+            if (GATHER && (pa.nt & 2)) __builtin_nontemporal_store(acc_t[n][g], dst);  // (A rows: launch.hpp, nt_on)
             else *dst = acc_t[n][g];
           }
         }

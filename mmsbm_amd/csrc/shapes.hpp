@@ -18,6 +18,9 @@ constexpr size_t kScalarTileBytes = 8 * 1024;  // larger tiles thrash the scalar
 inline bool tile_in_lds(int dinp, int doutp) {
   return static_cast<size_t>(dinp) * doutp * sizeof(double) > kScalarTileBytes;
 }
+// A rating tile beyond the scalar cache (kp * lp > 1024: 1,024 doubles are kScalarTileBytes): the shapes whose pair stage
+// leaves the lane-per-pair form with its tile in scalar loads -- matrix cores, longer unit runs, direct stores, the quad A launch
+inline bool tile_beyond_scalar_cache(int kp, int lp) { return static_cast<size_t>(kp) * lp * sizeof(double) > kScalarTileBytes; }
 inline size_t pair_block_lds(int dinp, int doutp, bool tile_lds) {
   // transposed input rows + one region shared by the eta rows and the output rows [+ the tile]
   const size_t d = static_cast<size_t>(dinp) * (kUnitPairs + 1) + static_cast<size_t>(kUnitPairs) * doutp +

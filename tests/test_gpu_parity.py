@@ -591,7 +591,7 @@ def test_two_launch_iteration_is_chosen_by_size_and_refused_where_it_does_not_ap
 
 def test_non_temporal_output_rows_change_nothing_but_the_cache_policy(hip):
     """T, A and theta' rows go out as non-temporal stores for one restart per launch and rows of up to 32 groups
-    (stages.hpp: nt_on): the same bits as with plain stores, in the four-launch and in the two-launch form."""
+    (launch.hpp: nt_on): the same bits as with plain stores, in the four-launch and in the two-launch form."""
     data = orc.synthetic_triples(30_000, 3_000, 700, 5, seed=3)
     for k, l, fused in ((20, 20, 0), (20, 20, 1), (10, 7, 1), (32, 9, 0)):
         runs = []
