@@ -1,11 +1,15 @@
 """Randomised parity fuzz (not part of the test suite): random shapes, degrees, slot counts and kernel-family
 options against the dense oracle -- numerators after one step, parameters after a few iterations, likelihood in all
-three device forms, prod_dist.  usage: python scripts/fuzz_parity.py [seconds] [seed]"""
+three device forms, prod_dist; and, one case in four, the serving kernels on a model family of tests/exact_models.py at
+random sizes -- top-N lists, scores (by their bits), counts and positions EQUAL to the exact reference.
+usage: python scripts/fuzz_parity.py [seconds] [seed]"""
 import os, sys, time
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 import numpy as np
 from mmsbm_amd import HipEM
 from oracle import mmsbm_oracle as orc
+import exact_models as xm
 
 budget = float(sys.argv[1]) if len(sys.argv) > 1 else 240.0
 rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 0)
@@ -16,8 +20,49 @@ def rel(a, b):
     return float(np.max(np.abs(a - b)) / (m if m > 0 else 1.0))
 
 
-t0, cases, worst = time.time(), 0, 0.0
+def serving_case(rng):
+    """One exact-model session: None when the device equals the exact reference, else what differs."""
+    family, kind = xm.FAMILIES[rng.integers(len(xm.FAMILIES))], xm.WEIGHT_KINDS[rng.integers(len(xm.WEIGHT_KINDS))]
+    few = rng.random() < 0.3                           # few users over many items: the split across waves + the merge
+    U, I = (int(rng.integers(1, 4)), int(rng.integers(1100, 30000))) if few else (int(rng.integers(1, 400)), int(rng.integers(20, 3000)))
+    shape = (U, I, int(rng.integers(2, 10)), int(rng.integers(2, 10)), int(rng.integers(2, 7)), int(rng.integers(1, 5)))
+    case = xm.make_case(family, kind, shape, n_random=int(rng.integers(1, 30 * U + 2)))
+    swap, exclude = int(rng.integers(-1, 2)), bool(rng.integers(0, 2))
+    tag = f"serving {family}/{kind} U={U} I={I} K={shape[2]} L={shape[3]} R={shape[4]} S={shape[5]} swap={swap} exclude={exclude}"
+    seen = case["seen"] if exclude else None
+    off, items = xm.position_lists(rng, case["scores"], seen, lengths=tuple(int(x) for x in rng.choice([0, 1, 4, 5, 16, 17, 33, 200], 3)))
+    ns = sorted({1, int(rng.integers(1, 1025)), int(rng.integers(1, 1025)), 1024})
+    with HipEM(case["data"], shape[2], shape[3], U, I, shape[4], slots=shape[5], swap_sides=swap) as em:
+        for s, p in enumerate(case["params"]):
+            em.select(s).set_params(*p)
+        em.recommend_begin(case["w"], exclude)
+        for s in range(shape[5]):
+            em.select(s).recommend_add()
+        got = {n: em.recommend_query(case["users"], n) for n in ns}
+        pos = em.recommend_positions(case["users"], off, items)
+        em.recommend_end()
+    top = xm.exact_top_n(case["scores"], case["users"], 1024, seen)
+    for n in ns:
+        wi, ws, wc = xm.first_n(top, n)
+        gi, gs, gc = got[n]
+        if not (np.array_equal(gi, wi) and np.array_equal(xm.bits(gs), xm.bits(ws)) and np.array_equal(gc, wc)):
+            return tag, f"top-{n} differs"
+    want = xm.exact_positions(case["scores"], off, items, case["users"].tolist(), seen)
+    if not (np.array_equal(pos[0], want[0]) and np.array_equal(pos[1], want[1])):
+        return tag, "positions differ"
+    return tag, None
+
+
+t0, cases, serving, worst = time.time(), 0, 0, 0.0
 while time.time() - t0 < budget:
+    if rng.random() < 0.25:
+        tag, bad = serving_case(rng)
+        cases += 1
+        serving += 1
+        if bad:
+            print(f"MISMATCH {tag}: {bad}", flush=True)
+            sys.exit(1)
+        continue
     kind = rng.integers(0, 10)
     if kind < 6:
         k, l = int(rng.integers(1, 26)), int(rng.integers(1, 26))
@@ -78,4 +123,4 @@ while time.time() - t0 < budget:
         sys.exit(1)
     if cases % 50 == 0:
         print(f"{cases} cases, worst relative error {worst:.2e}  [{time.time() - t0:.0f}s]  last: {tag}", flush=True)
-print(f"done: {cases} cases, worst relative error {worst:.2e}")
+print(f"done: {cases} cases ({serving} of them serving sessions, each equal to the exact reference), worst relative error {worst:.2e}")

@@ -11,7 +11,8 @@ mmsbm_amd/restarts.py -- and restart i does not depend on where it runs).
 import numpy as np
 import pytest
 
-from conftest import assert_elementwise, rel_err
+from argmax_rule import assert_unclear_rows_near_max
+from conftest import assert_elementwise, elem_rel_err, rel_err
 from oracle import mmsbm_factorised as fac
 from oracle import mmsbm_oracle as orc
 
@@ -88,15 +89,20 @@ def _check_against(hip, train, case, options=()):
         assert rel_err(g, w) < TOL_STEP, (nm, rel_err(g, w))
         assert_elementwise(g, w, nm)
     ctx.iterate(case["iters"])
+    drift = 0.0
     for g, w, nm in zip(ctx.get_params(), case["params"], ("theta", "eta", "pr")):
         assert rel_err(g, w) < TOL_FEW, (nm, rel_err(g, w))
         assert_elementwise(g, w, nm)
+        drift = max(drift, elem_rel_err(g, w))
     lik = ctx.likelihood()
     assert abs(lik - case["lik"]) <= 1e-11 * abs(case["lik"]), (lik, case["lik"])
     pd_h = ctx.prod_dist(train)
     assert rel_err(pd_h, case["pd"]) < TOL_FEW
     agree, clear = _argmax_agreement(pd_h, case["pd"])
     assert agree == 1.0 and clear > 0.99, (agree, clear)
+    srt = np.sort(case["pd"], axis=1)                 # the rows that are not clear: the reference's argmax is a near-maximum
+    assert_unclear_rows_near_max(pd_h, np.argmax(case["pd"], 1), (srt[:, -1] - srt[:, -2]) > 1e-9, drift,
+                                 f"K={case['k']} L={case['l']}, {len(train)} ratings, {case['iters']} iterations")
     info = {nm: ctx.get_option(nm) for nm in ("mfma", "quad", "chunk_pairs", "n_chunks")}
     mm._release()
     return info
@@ -338,7 +344,9 @@ def _long_run_against_the_reference(hip, name, expect, min_clear=0.99):
         assert ctx.likelihood() == pytest.approx(float(g["likelihood_at"][j]), rel=1e-9)
         clear = np.unpackbits(g[f"clear_{it}"])[:len(train)].astype(bool)
         assert clear.mean() > min_clear, clear.mean()
-        assert np.array_equal(np.argmax(ctx.prod_dist(train), 1)[clear], g[f"argmax_{it}"][clear]), it
+        pd_h = ctx.prod_dist(train)
+        assert np.array_equal(np.argmax(pd_h, 1)[clear], g[f"argmax_{it}"][clear]), it
+        assert_unclear_rows_near_max(pd_h, g[f"argmax_{it}"], clear, max(errs), f"{name} after {it} iterations")
         worst[it] = max(errs)
     print(f"{name}: worst element-wise relative error vs the reference after {' / '.join(map(str, snaps))} iterations: "
           + " / ".join(f"{worst[it]:.1e}" for it in snaps))

@@ -3,7 +3,8 @@ golden vectors.  Needs a real MI355X: run with ``-m gpu``."""
 import numpy as np
 import pytest
 
-from conftest import assert_elementwise, load_golden, rel_err
+from argmax_rule import assert_unclear_rows_near_max
+from conftest import assert_elementwise, elem_rel_err, load_golden, rel_err
 from oracle import mmsbm_oracle as orc
 
 pytestmark = pytest.mark.gpu
@@ -244,10 +245,12 @@ def test_host_class_on_a_rating_table_with_string_ids_and_uneven_degrees(hip):
     ctx = mm._ctx(0)
     assert ctx.get_option("splits_pairs") > 0 and ctx.get_option("splits_users") > 0
     assert ctx.get_option("fused_split") == 3.0 and ctx.get_option("launches") == 2.0
+    drift = 0.0
     for s_, got in enumerate(mm.results):
         for nm in ("theta", "eta", "pr"):
             assert rel_err(got[nm], g[f"{nm}_{s_}"]) < TOL_LOOP, (s_, nm)
             assert_elementwise(got[nm], g[f"{nm}_{s_}"], f"{nm} of restart {s_}")
+            drift = max(drift, elem_rel_err(got[nm], g[f"{nm}_{s_}"]))
         assert float(got["likelihood"]) == pytest.approx(float(g["likelihoods"][s_]), rel=1e-10)
     pm = mm.predict(frame("test_raw", index=g["test_index"]))
     assert np.array_equal(mm.test, g["test"])
@@ -256,6 +259,7 @@ def test_host_class_on_a_rating_table_with_string_ids_and_uneven_degrees(hip):
     srt = np.sort(ref, axis=1)
     clear = srt[:, -1] - srt[:, -2] > 1e-9
     assert clear.mean() > 0.99 and np.array_equal(np.argmax(pm, 1)[clear], np.argmax(ref, 1)[clear])
+    assert_unclear_rows_near_max(pm, np.argmax(ref, 1), clear, drift, "g7_uneven_strings prediction matrix")
     want = dict(zip(g["stats_keys"].tolist(), g["stats_vals"].tolist()))
     st = mm.score(silent=True)["stats"]
     assert st["accuracy"] == pytest.approx(want["accuracy"], abs=1e-12) and st["s2"] == want["s2"]
@@ -299,12 +303,15 @@ def test_c2_50_iterations_sampled_entries_and_argmax(hip):
         assert_elementwise(t[g["ut"], g["kt"]], g[f"theta_s_{it}"], f"theta entries after {it}")
         assert_elementwise(e[g["ie"], g["le"]], g[f"eta_s_{it}"], f"eta entries after {it}")
         assert_elementwise(p, g[f"pr_{it}"], f"p after {it}")
+        drift = max(elem_rel_err(t[g["ut"], g["kt"]], g[f"theta_s_{it}"]), elem_rel_err(e[g["ie"], g["le"]], g[f"eta_s_{it}"]),
+                    elem_rel_err(p, g[f"pr_{it}"]))                     # (of the last snapshot: the one P is taken at)
         assert rel_err(t.sum(0), g[f"theta_colsum_{it}"]) < TOL_LOOP
         assert ctx.likelihood() == pytest.approx(float(g["likelihood_at"][(1, 10, 50).index(it)]), rel=1e-9)
     pdist = ctx.prod_dist(train)
     clear = g["gap_50"] > 1e-9
     assert np.array_equal(np.argmax(pdist, 1)[clear], g["argmax_50"][clear])
     assert clear.mean() > 0.99
+    assert_unclear_rows_near_max(pdist, g["argmax_50"], clear, drift, "g5_c2_sampled after 50 iterations")
 
 
 def test_c2_400_iterations_the_references_default_run_length(hip):
@@ -329,15 +336,19 @@ def test_c2_400_iterations_the_references_default_run_length(hip):
         ctx.iterate(it - done)
         done = it
         t, e, p = ctx.get_params()
+        drift = 0.0
         for got, want, nm in ((t[g["ut"], g["kt"]], g[f"theta_s_{it}"], "theta entries"),
                               (e[g["ie"], g["le"]], g[f"eta_s_{it}"], "eta entries"), (p, g[f"pr_{it}"], "p")):
             assert rel_err(got, want) < TOL_LOOP, (nm, it)
             assert_elementwise(got, want, f"{nm} after {it} iterations", rtol=1e-6)
+            drift = max(drift, elem_rel_err(got, want))
         assert rel_err(t.sum(0), g[f"theta_colsum_{it}"]) < TOL_LOOP and rel_err(e.sum(0), g[f"eta_colsum_{it}"]) < TOL_LOOP
         assert ctx.likelihood() == pytest.approx(float(g["likelihood_at"][j]), rel=1e-9)
         clear = np.unpackbits(g[f"clear_{it}"])[:len(train)].astype(bool)
         assert clear.mean() > 0.99
-        assert np.array_equal(np.argmax(ctx.prod_dist(train), 1)[clear], g[f"argmax_{it}"][clear]), it
+        pdist = ctx.prod_dist(train)
+        assert np.array_equal(np.argmax(pdist, 1)[clear], g[f"argmax_{it}"][clear]), it
+        assert_unclear_rows_near_max(pdist, g[f"argmax_{it}"], clear, drift, f"g5_c2_400 after {it} iterations")
     assert float(g["likelihood_at"][2]) == float(g["likelihood_400"])
 
 

@@ -5,7 +5,8 @@ Positions and candidate counts are integers and are compared exactly.  The resta
 differ from the device's in the last bits, so an item whose restated score lies within TOL x max|score| of another
 item's without being equal to it (a near tie, absent from these seeded problems in practice) may move by at most the
 number of such neighbours; every other position must be equal.  What holds on the device alone -- consistency with
-recommend_query, request independence, swapped contexts, no side effects -- is checked bit for bit.
+recommend_query, request independence, swapped contexts, no side effects -- is checked bit for bit.  Positions inside
+large tie groups are compared without any band in test_gpu_serving_exact.py, on models whose scores carry no rounding.
 """
 import numpy as np
 import pandas as pd

@@ -5,7 +5,8 @@ restatement of test_recommend_cpu.py: mean over restarts of oracle prod_dist, ti
 Scores agree within TOL x max|score|; the returned items agree outside the tie band: with tau = TOL x max|score| and
 s* the restatement's n-th score, every item scoring above s* + tau is returned and none below s* - tau.  What the
 kernels promise beyond that -- bitwise the same scores whatever the request, the launch shape or the side layout,
-exact ties by item id, no change to any slot -- is checked bit for bit.
+exact ties by item id, no change to any slot -- is checked bit for bit.  The band-free checks (mass ties, every
+member of a tie group, scores compared by their bits) live in test_gpu_serving_exact.py, on models without rounding.
 """
 import os
 import sys
