@@ -223,6 +223,31 @@ int mmsbm_hip_recommend_positions(mmsbm_hip_ctx *ctx, int64_t n_users, const int
 int mmsbm_hip_recommend_add_items(mmsbm_hip_ctx *ctx, int32_t n_new, const double *eta,
                                   const int64_t *seen_offsets, const int32_t *seen_users);
 
+/* ---- nearest items / users: the n most similar rows of one side (mmsbm_amd/csrc/similar.hpp) -------------------- */
+/* A session of its own beside the recommend session (either may be open while the other is):
+ *   begin  side 0: items, 1: users (external sides).  Closes any earlier similarity session;
+ *   add    the SELECTED slot's rating profiles and group masses join the session (the slot itself is left unchanged):
+ *          items  q_s[i, k, r] = sum_l eta_s[i, l] p_s[k, l, r],    m_s[k] = sum_u theta_s[u, k];
+ *          users  q_s[u, l, r] = sum_k theta_s[u, k] p_s[k, l, r],  m_s[l] = sum_i eta_s[i, l];
+ *   query  for n_rows ids of the side (repeats allowed, any order): over the S added slots
+ *          D(i, j) = ( sum_s sum_k sum_r m_s[k] (q_s[i,k,r] - q_s[j,k,r])^2 ) / (S U)        (users: / (S I))
+ *          in the direct form (subtract, square, accumulate: D(i, i) = 0 and identical rows are at distance exactly 0),
+ *          and per id the n nearest OTHER rows -- D ascending, equal D (exact fp64 equality) by ascending id.
+ *          out_ids / distance: n_rows x n, row b holding counts[b] = min(n, rows - 1) entries followed by id -1 /
+ *          distance +inf (distance and counts may be NULL).  A row's answer depends on that id only: bitwise the same
+ *          whatever the other ids of the call, the slots the context holds beyond those added, and the side layout;
+ *   end    releases the session's device memory (so does mmsbm_hip_destroy).
+ * mmsbm_hip_get_option(ctx, "similar_ms") reads the device time of the last query's kernels (HIP events).
+ * MMSBM_E_INVALID: side not 0 / 1, add or query without begin, query before the first add, an id outside the side's
+ * range, n < 1; n > MMSBM_HIP_RECOMMEND_MAX_N: MMSBM_E_UNSUPPORTED; MMSBM_E_TOOLARGE where the device memory of the
+ * profile tables (rows x groups x R doubles per slot) or of a batch is not free.  Touches no slot, no EM state and no
+ * predict / recommend session. */
+int mmsbm_hip_similar_begin(mmsbm_hip_ctx *ctx, int side);
+int mmsbm_hip_similar_add(mmsbm_hip_ctx *ctx);
+int mmsbm_hip_similar_query(mmsbm_hip_ctx *ctx, int64_t n_rows, const int32_t *ids, int32_t n, int32_t *out_ids,
+                            double *distance, int32_t *counts);
+int mmsbm_hip_similar_end(mmsbm_hip_ctx *ctx);
+
 /* ---- fold-in: theta of new users under the fitted eta and p (mmsbm_amd/csrc/fold_in.hpp) ----------------------- */
 /* The SELECTED slot's eta and p stay fixed; for new users 0 .. n_new-1, given their rows (user in [0, n_new), item in
  * [0, I), rating in [0, R), external ids), n_iters times

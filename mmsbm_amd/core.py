@@ -396,6 +396,29 @@ class HipEM:
     def recommend_end(self):
         _lib.call("mmsbm_hip_recommend_end", self._h)
 
+    # -- nearest items / users on the device (include/mmsbm_hip.h: mmsbm_hip_similar_*) -----------------
+    def similar_begin(self, side):
+        """Open a similarity session over one side: 0 (or "items") the items, 1 (or "users") the users."""
+        side = {"items": 0, "users": 1}.get(side, side)
+        _lib.call("mmsbm_hip_similar_begin", self._h, int(side))
+
+    def similar_add(self):
+        """Add the selected slot's rating profiles and group masses to the session (the slot is left unchanged)."""
+        _lib.call("mmsbm_hip_similar_add", self._h)
+
+    def similar_query(self, ids, n):
+        """(ids (M,n) int32 padded with -1, distance (M,n) padded with +inf, counts (M,)) for encoded ids of the
+        session's side: the n nearest other rows of each, distance ascending, equal distances by ascending id."""
+        q = _i32(ids)
+        n = int(n)
+        out, dist, counts = self._query_out(len(q), n)
+        _lib.call("mmsbm_hip_similar_query", self._h, len(q), _p(q, C.c_int32), n, _p(out, C.c_int32),
+                  _p(dist, C.c_double), _p(counts, C.c_int32))
+        return out, dist, counts
+
+    def similar_end(self):
+        _lib.call("mmsbm_hip_similar_end", self._h)
+
     # -- fold-in of new users (include/mmsbm_hip.h: mmsbm_hip_fold_in) ---------------------------------
     MAX_FOLD_IN_K = 1024
 

@@ -129,6 +129,18 @@ struct RecSession {
   bool excl = false;                    // seen_* in use: exclude_train, or seen lists of recommend_add_items
 };
 
+// The similarity session (mmsbm_hip_similar_begin .. end; similar.hpp): the added slots' profiles and group masses of
+// one external side.  Created by similar_begin, dropped whole by similar_begin and similar_end.
+struct SimSession {
+  DevBuf<double> q;                     // [slot][rows][width]: the rating profiles
+  DevBuf<double> mf;                    // [slot][width]: the mass of the group each profile entry belongs to
+  int side = 0;                         // 0: items, 1: users (external sides)
+  int slots = 0;                        // slots added
+  int rows = 0;                         // rows of the side: I, or U
+  int others = 0;                       // rows of the other side (the masses sum to it): U, or I
+  int width = 0;                        // profile entries per row: K R, or L R
+};
+
 }  // namespace mmsbm_hip_impl
 
 namespace {
@@ -242,6 +254,8 @@ struct mmsbm_hip_ctx {
   float rc_last_ms = 0.f;                   // device time of the last query's kernels (option "recommend_ms")
   float fold_last_ms = 0.f;                 // device time of the last fold-in's kernels, either side ("fold_in_ms")
   float pos_last_ms = 0.f;                  // device time of the last recommend_positions (option "position_ms")
+  std::unique_ptr<mmsbm_hip_impl::SimSession> sm;  // the open similarity session; null: none
+  float sim_last_ms = 0.f;                  // device time of the last similar_query's kernels (option "similar_ms")
   int cur = 0;
   std::vector<char> have;  // per slot: set_params has been called
   bool graph_mode = false;  // replay a captured two-iteration hipGraph instead of eager launches

@@ -49,6 +49,12 @@ void recommend_positions(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users
 void recommend_add_items(mmsbm_hip_ctx *c, int32_t n_new, const double *eta, const int64_t *seen_offsets,
                          const int32_t *seen_users);
 void recommend_end(mmsbm_hip_ctx *c);
+// ... and nearest items / users (similar.hpp): the session of mmsbm_hip_similar_*, arguments checked
+void similar_begin(mmsbm_hip_ctx *c, int side);
+void similar_add(mmsbm_hip_ctx *c);  // the selected slot (the caller holds a OneSlot)
+void similar_query(mmsbm_hip_ctx *c, int64_t n_rows, const int32_t *ids, int n, int32_t *out_ids, double *distance,
+                   int32_t *counts);
+void similar_end(mmsbm_hip_ctx *c);
 
 // tu_fold_in.hip -- fold new users (items_side: new items) into the selected slot's fitted eta (theta) and p
 // (fold_in.hpp), arguments checked; x0, x: theta0, theta (eta0, eta); items_side: item[m] in [0, n_new), user[m] in [0, U)

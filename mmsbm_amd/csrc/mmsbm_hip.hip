@@ -1505,6 +1505,52 @@ int mmsbm_hip_recommend_add_items(mmsbm_hip_ctx *ctx, int32_t n_new, const doubl
   });
 }
 
+int mmsbm_hip_similar_begin(mmsbm_hip_ctx *ctx, int side) {
+  return guarded([&] {
+    if (!ctx) throw std::invalid_argument("null context");
+    if (side != 0 && side != 1) throw std::invalid_argument("similar: side must be 0 (items) or 1 (users)");
+    similar_begin(ctx, side);
+  });
+}
+
+int mmsbm_hip_similar_add(mmsbm_hip_ctx *ctx) {
+  return guarded([&] {
+    require_params(ctx);
+    if (!ctx->sm) throw std::invalid_argument("similar_begin has not been called");
+    OneSlot one(ctx);
+    similar_add(ctx);
+  });
+}
+
+int mmsbm_hip_similar_query(mmsbm_hip_ctx *ctx, int64_t n_rows, const int32_t *ids, int32_t n, int32_t *out_ids,
+                            double *distance, int32_t *counts) {
+  return guarded([&] {
+    if (!ctx) throw std::invalid_argument("null context");
+    if (!ctx->sm) throw std::invalid_argument("similar_begin has not been called");
+    if (ctx->sm->slots == 0) throw std::invalid_argument("similar_query before any similar_add");
+    if (n_rows < 0) throw std::invalid_argument("negative n_rows");
+    if (n < 1) throw std::invalid_argument("similar: n must be at least 1");
+    if (n > MMSBM_HIP_RECOMMEND_MAX_N)
+      throw ApiError(MMSBM_E_UNSUPPORTED, "similar: n = " + std::to_string(n) + " is beyond the " +
+                                              std::to_string(MMSBM_HIP_RECOMMEND_MAX_N) + " rows a query returns at most");
+    if (n_rows > 0 && (!ids || !out_ids)) throw std::invalid_argument("null argument");
+    for (int64_t m = 0; m < n_rows; ++m)
+      if (ids[m] < 0 || ids[m] >= ctx->sm->rows)
+        throw std::invalid_argument(std::string("similar: ") + (ctx->sm->side == 0 ? "item" : "user") +
+                                    " id out of range at row " + std::to_string(m));
+    similar_query(ctx, n_rows, ids, n, out_ids, distance, counts);
+  });
+}
+
+int mmsbm_hip_similar_end(mmsbm_hip_ctx *ctx) {
+  return guarded([&] {
+    if (!ctx) throw std::invalid_argument("null context");
+    use_device(ctx);
+    HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    similar_end(ctx);
+  });
+}
+
 int mmsbm_hip_fold_in(mmsbm_hip_ctx *ctx, int64_t n_rows, const int32_t *user, const int32_t *item,
                       const int32_t *rating, int32_t n_new, int32_t n_iters, double tol,
                       const double *theta0, double *theta, int32_t *iters) {
@@ -1697,6 +1743,7 @@ int mmsbm_hip_get_option(const mmsbm_hip_ctx *ctx, const char *name, double *val
     else if (key == "recommend_ms") *value = ctx->rc_last_ms;  // read-only: device time of the last recommend_query
     else if (key == "fold_in_ms") *value = ctx->fold_last_ms;  // read-only: device time of the last fold-in (either side)
     else if (key == "position_ms") *value = ctx->pos_last_ms;  // read-only: device time of the last recommend_positions
+    else if (key == "similar_ms") *value = ctx->sim_last_ms;   // read-only: device time of the last similar_query
     else if (key == "launches") *value = use_fused(ctx) ? 2 : 4;  // read-only: launches per iteration at the current slot count
     else if (key == "wide") *value = ctx->wide;
     else if (key == "lik_fast") *value = ctx->lik_mode;

@@ -1,7 +1,9 @@
 // tu_recommend.hip -- translation unit of top-N recommendation (recommend.hpp): the session's host side -- the
-// training items of every user, the per-slot prologue, the batches of a query and the choice of the item split
+// training items of every user, the per-slot prologue, the batches of a query and the choice of the item split -- and
+// of nearest items / users (similar.hpp), whose queries share the batches and the selection
 #include "prelude.hpp"
 #include "recommend.hpp"
+#include "similar.hpp"
 
 #include <climits>
 
@@ -221,10 +223,13 @@ void rec_score_batch(mmsbm_hip_ctx *c, const double *x, size_t xs, const int32_t
   if (seen_off) LAUNCH(rec_exclude_kernel, nb, kBlock, 0, st, ub, seen_off, seen, sc, static_cast<size_t>(I));
 }
 
-// The batches of a query: users users[0 .. n_users) (host ids, rows of x: `slots` tables of xs doubles, [row][rank]),
-// scored against the session's items; seen_off / seen (device, indexed by those ids): the items left out, or null.
-void rec_run(mmsbm_hip_ctx *c, const double *x, size_t xs, int64_t n_users, const int32_t *users,
-             const int32_t *seen_off, const int32_t *seen, int n, int32_t *items, double *scores, int32_t *counts) {
+// The batches of a top-N query over a buffer of `I` columns: rows ids[0 .. n_rows) (host ids); `fill(ub, nb, sc)`
+// enqueues the kernels that write the batch's values sc [nb][I] for the device ids ub (-inf: no candidate), then the
+// N best of every row are selected (and merged when the columns are split across waves).  `what` names the query in
+// MMSBM_E_TOOLARGE; *ms: device time of the query's kernels.
+template <class Fill>
+void top_n_run(mmsbm_hip_ctx *c, int I, int64_t n_users, const int32_t *users, int n, const char *what, Fill &&fill,
+               float *ms, int32_t *items, double *scores, int32_t *counts) {
   for (int64_t b = 0; b < n_users; ++b) {
     if (counts) counts[b] = 0;
     for (int k = 0; k < n; ++k) {
@@ -233,7 +238,6 @@ void rec_run(mmsbm_hip_ctx *c, const double *x, size_t xs, int64_t n_users, cons
     }
   }
   if (n_users == 0) return;
-  const int I = c->rc->items;
   hipStream_t st = c->stream;
 
   const int64_t bu = rec_batch_users(I, n_users);
@@ -245,7 +249,7 @@ void rec_run(mmsbm_hip_ctx *c, const double *x, size_t xs, int64_t n_users, cons
   const size_t cand = parts > 1 ? static_cast<size_t>(bu) * parts * n : 0;
   const size_t outs = static_cast<size_t>(n_users) * n;
   require_free_mem(static_cast<size_t>(bu) * I * sizeof(double) + cand * 12 + outs * 12 + static_cast<size_t>(n_users) * 8,
-                   "recommend: a batch of users");
+                   what);
   DevBuf<int32_t> du, ci, cn, oi, on;
   DevBuf<double> sc, cs, os;
   du.alloc(n_users);
@@ -255,14 +259,14 @@ void rec_run(mmsbm_hip_ctx *c, const double *x, size_t xs, int64_t n_users, cons
   }
   os.alloc(outs); oi.alloc(outs); on.alloc(n_users);  // every user's result stays on the device until the end
   HIP_CHECK(hipMemcpyAsync(du.ptr, users, sizeof(int32_t) * n_users, hipMemcpyHostToDevice, st));
-  EventPair ev;  // device time of the query's kernels (option "recommend_ms")
+  EventPair ev;  // device time of the query's kernels (options "recommend_ms", "similar_ms")
   ev.start(st);
   for (int64_t b0 = 0; b0 < n_users; b0 += bu) {  // (batches follow each other on the stream: no host wait in between)
     const int nb = static_cast<int>(std::min(bu, n_users - b0));
     const int32_t *ub = du.ptr + b0;
     double *obs = os.ptr + b0 * n;
     int32_t *obi = oi.ptr + b0 * n, *obn = on.ptr + b0;
-    rec_score_batch(c, x, xs, ub, nb, seen_off, seen, sc.ptr);
+    fill(ub, nb, sc.ptr);
     if (parts > 1) {
       LAUNCH(rec_select_kernel<false>, dim3(parts, nb), kRecWave, lds, st, sc.ptr, static_cast<size_t>(I), I, per,
              nullptr, nullptr, nullptr, 0, n, cap, cs.ptr, ci.ptr, cn.ptr);
@@ -281,7 +285,7 @@ void rec_run(mmsbm_hip_ctx *c, const double *x, size_t xs, int64_t n_users, cons
   HIP_CHECK(hipMemcpyAsync(hi.data(), oi.ptr, sizeof(int32_t) * outs, hipMemcpyDeviceToHost, st));
   HIP_CHECK(hipMemcpyAsync(hn.data(), on.ptr, sizeof(int32_t) * n_users, hipMemcpyDeviceToHost, st));
   HIP_CHECK(hipStreamSynchronize(st));
-  c->rc_last_ms = ev.ms();
+  *ms = ev.ms();
   for (int64_t b = 0; b < n_users; ++b) {
     const size_t o = static_cast<size_t>(b) * n;
     const int cnt = hn[static_cast<size_t>(b)];
@@ -291,6 +295,15 @@ void rec_run(mmsbm_hip_ctx *c, const double *x, size_t xs, int64_t n_users, cons
       if (scores) scores[o + k] = hs[o + k];
     }
   }
+}
+
+// A recommend query: users users[0 .. n_users) (host ids, rows of x: `slots` tables of xs doubles, [row][rank]),
+// scored against the session's items; seen_off / seen (device, indexed by those ids): the items left out, or null.
+void rec_run(mmsbm_hip_ctx *c, const double *x, size_t xs, int64_t n_users, const int32_t *users,
+             const int32_t *seen_off, const int32_t *seen, int n, int32_t *items, double *scores, int32_t *counts) {
+  top_n_run(c, c->rc->items, n_users, users, n, "recommend: a batch of users",
+            [&](const int32_t *ub, int nb, double *sc) { rec_score_batch(c, x, xs, ub, nb, seen_off, seen, sc); },
+            &c->rc_last_ms, items, scores, counts);
 }
 
 }  // namespace
@@ -400,5 +413,74 @@ void recommend_positions(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users
 }
 
 void recommend_end(mmsbm_hip_ctx *c) { c->rc.reset(); }
+
+// ---- nearest items / users (similar.hpp) ------------------------------------------------------------------------------
+void similar_begin(mmsbm_hip_ctx *c, int side) {
+  use_device(c);
+  c->sm.reset();  // (from here on the previous session is gone)
+  auto sm = std::make_unique<SimSession>();
+  sm->side = side;
+  sm->rows = side == 0 ? c->ext_items : c->ext_users;
+  sm->others = side == 0 ? c->ext_users : c->ext_items;
+  sm->width = (side == 0 ? c->ext_k : c->ext_l) * c->n_ratings;
+  c->sm = std::move(sm);
+}
+
+void similar_add(mmsbm_hip_ctx *c) {  // the selected slot (the caller holds a OneSlot)
+  use_device(c);
+  SimSession &sm = *c->sm;
+  const int R = c->n_ratings, S = sm.slots, W = sm.width, rows = sm.rows;
+  const size_t qs = static_cast<size_t>(rows) * W;
+  require_free_mem((S + 1) * (qs + W) * sizeof(double), "similar: the slots' profiles");
+  hipStream_t st = c->stream;
+  // grow the two tables by one slot (the earlier slots' profiles are kept as they are)
+  DevBuf<double> nq, nm;
+  nq.alloc((S + 1) * qs);
+  nm.alloc(static_cast<size_t>(S + 1) * W);
+  if (S > 0) {
+    HIP_CHECK(hipMemcpyAsync(nq.ptr, sm.q.ptr, sizeof(double) * S * qs, hipMemcpyDeviceToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(nm.ptr, sm.mf.ptr, sizeof(double) * S * W, hipMemcpyDeviceToDevice, st));
+  }
+  const int cur = c->cur, sl = c->sel;
+  // external (k, l) of the slot's p and the caller's users / items, as recommend_add reads them
+  const int ks = c->swapped ? 1 : c->lp, ls = c->swapped ? c->lp : 1;
+  const size_t rs = static_cast<size_t>(c->kp) * c->lp;
+  const RowTab th = theta_tab(c, cur), et = plain_tab(c->eta[cur].at(sl), c->lp);
+  const RowTab ut = c->swapped ? et : th, it = c->swapped ? th : et;
+  // items: profiles over the user groups (g = k) from eta (t = l), masses of theta; users: the other way round
+  const bool items = sm.side == 0;
+  const int G = items ? c->ext_k : c->ext_l, T = items ? c->ext_l : c->ext_k;
+  LAUNCH(sim_mass_kernel, static_cast<unsigned>(G), kBlock, 0, st, items ? ut : it, sm.others, R,
+         nm.ptr + static_cast<size_t>(S) * W);
+  if (qs > 0)
+    LAUNCH(sim_profile_kernel, static_cast<unsigned>((qs + kBlock - 1) / kBlock), kBlock, 0, st, items ? it : ut, T,
+           c->p[cur].at(sl), rs, items ? ks : ls, items ? ls : ks, nq.ptr + S * qs, rows, G, R);
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipStreamSynchronize(st));
+  sm.q.swap(nq);
+  sm.mf.swap(nm);
+  sm.slots = S + 1;
+}
+
+void similar_query(mmsbm_hip_ctx *c, int64_t n_rows, const int32_t *ids, int n, int32_t *out_ids, double *distance,
+                   int32_t *counts) {
+  use_device(c);
+  const SimSession &sm = *c->sm;
+  const int rows = sm.rows, W = sm.width, S = sm.slots;
+  const double denom = static_cast<double>(S) * static_cast<double>(sm.others);
+  hipStream_t st = c->stream;
+  top_n_run(c, rows, n_rows, ids, n, "similar: a batch of query rows",
+            [&](const int32_t *ub, int nb, double *sc) {
+              const dim3 g(static_cast<unsigned>((rows + kSimTile - 1) / kSimTile),
+                           static_cast<unsigned>((nb + kSimTile - 1) / kSimTile));
+              LAUNCH(sim_dist_kernel, g, kBlock, 0, st, sm.q.ptr, static_cast<size_t>(rows) * W, sm.mf.ptr, ub, nb, rows,
+                     W, S, denom, sc, static_cast<size_t>(rows));
+            },
+            &c->sim_last_ms, out_ids, distance, counts);
+  // the buffer held -D (the selection's order): the distances, +inf behind the last one (a zero leaves as +0.0)
+  for (size_t e = 0; distance && e < static_cast<size_t>(n_rows) * n; ++e) distance[e] = -distance[e];
+}
+
+void similar_end(mmsbm_hip_ctx *c) { c->sm.reset(); }
 
 }  // namespace mmsbm_hip_impl

@@ -322,11 +322,13 @@ class MMSBM:
         finally:
             ctx.recommend_end()
 
-    def _top_n_frame(self, query, n, row_labels, item_labels):
+    def _top_n_frame(self, query, n, row_labels, item_labels, columns=("users", "items", "score")):
         """The top-``n`` frame (users, items, score, rank) of rows [0, len(row_labels)), fetched in calls of at most
         RECOMMEND_BATCH_ROWS result rows (bounded host memory at a million users): ``query(b, e)`` -> (items, scores,
-        counts) of rows [b, e).  ``item_labels``: the label of each item id, or None (the ids themselves)."""
+        counts) of rows [b, e).  ``item_labels``: the label of each item id, or None (the ids themselves).
+        ``columns``: the names of the row, the returned-id and the value column (similar_items / similar_users)."""
         import pandas as pd
+        rows_col, ids_col, value_col = columns
         n_rows = len(row_labels)
         step = max(1, self.RECOMMEND_BATCH_ROWS // n)
         parts = []
@@ -336,34 +338,39 @@ class MMSBM:
             at = np.repeat(np.arange(b, b + len(counts)), counts)
             it = items[keep]
             parts.append(pd.DataFrame({
-                "users": row_labels[at] if len(at) else np.empty(0, dtype=object),
-                "items": item_labels[it] if item_labels is not None else it.astype(np.int64),
-                "score": scores[keep],
+                rows_col: row_labels[at] if len(at) else np.empty(0, dtype=object),
+                ids_col: item_labels[it] if item_labels is not None else it.astype(np.int64),
+                value_col: scores[keep],
                 "rank": np.nonzero(keep)[1].astype(np.int64) + 1}))
         if not parts:
-            return pd.DataFrame({"users": [], "items": [], "score": np.zeros(0), "rank": np.zeros(0, dtype=np.int64)})
+            return pd.DataFrame({rows_col: [], ids_col: [], value_col: np.zeros(0), "rank": np.zeros(0, dtype=np.int64)})
         return pd.concat(parts, ignore_index=True)
 
     def _training_users(self, users):
         """(encoded ids int32, labels) of recommend's ``users`` argument (None: every training user)."""
+        return self._training_ids(users, "users")
+
+    def _training_ids(self, wanted, side):
+        """(encoded ids int32, labels) of a request for training users or items (``side``; None: all of them)."""
         enc = self.data_handler
-        n_users = self.p + 1
-        if users is None:
-            ids = np.arange(n_users, dtype=np.int32)
-            labels = np.asarray(enc.user_labels(), dtype=object) if enc else ids
+        n_side = (self.p if side == "users" else self.m) + 1
+        side_labels = (lambda: enc.user_labels()) if side == "users" else (lambda: enc.item_labels())
+        if wanted is None:
+            ids = np.arange(n_side, dtype=np.int32)
+            labels = np.asarray(side_labels(), dtype=object) if enc else ids
         else:
-            labels = np.asarray(list(users), dtype=object)
+            labels = np.asarray(list(wanted), dtype=object)
             if enc:
-                index = {lab: j for j, lab in enumerate(enc.user_labels())}
+                index = {lab: j for j, lab in enumerate(side_labels())}
                 found = [index.get(str(x), -1) for x in labels]
             else:
-                found = [int(x) if isinstance(x, (int, np.integer)) and 0 <= int(x) < n_users else -1 for x in labels]
+                found = [int(x) if isinstance(x, (int, np.integer)) and 0 <= int(x) < n_side else -1 for x in labels]
             ids = np.asarray(found, dtype=np.int32)
             if (ids < 0).any():
                 missing = list(dict.fromkeys(labels[ids < 0].tolist()))
-                raise KeyError(f"users not in the training data: {missing}")
-            if enc:  # the encoder's labels, as with users=None (7 and "7" are one user; the frames join on "users")
-                labels = np.asarray(enc.user_labels(), dtype=object)[ids]
+                raise KeyError(f"{side} not in the training data: {missing}")
+            if enc:  # the encoder's labels, as with None (7 and "7" are one user; the frames join on this column)
+                labels = np.asarray(side_labels(), dtype=object)[ids]
         return ids, labels
 
     def _check_whole_model(self):
@@ -385,6 +392,44 @@ class MMSBM:
         if not np.isfinite(w).all():
             raise ValueError(f"weights must be finite, got {w.tolist()}")
         return w
+
+    # ------------------------------------------------------------------ nearest items / users (not in the reference)
+    def similar_items(self, items=None, n=10):
+        """The ``n`` training items most similar to each of ``items`` (None: every training item), on the device.
+
+        An item's rating profile is the rating distribution a member of each user group gives it,
+        q[i, k, :] = sum_l eta[i, l] p[k, l, :]; the distance of two items is
+        D(i, j) = sum_k m[k] |q[i, k, :] - q[j, k, :]|^2 / U with m[k] = sum_u theta[u, k] the users in group k: how
+        differently a user drawn from the training population rates the two, in [0, 2], mean over the restarts the
+        model holds.  It does not depend on how a restart happens to label its groups.
+
+        Returns a DataFrame with columns ``items``, ``similar``, ``distance``, ``rank`` (1 = nearest), rows in request
+        order, both id columns as the encoder's labels (``eta``'s index).  Order: distance ascending, equal distances
+        by ascending encoded id; an item is never its own neighbour.  The model's stored predictions and ``score()``
+        are left as they are."""
+        return self._similar("items", items, n)
+
+    def similar_users(self, users=None, n=10):
+        """The ``n`` training users most similar to each of ``users`` (None: every training user): ``similar_items``
+        with the sides exchanged -- q[u, l, :] = sum_k theta[u, k] p[k, l, :], weighted by the items in each item
+        group.  Columns ``users``, ``similar``, ``distance``, ``rank``."""
+        return self._similar("users", users, n)
+
+    def _similar(self, side, wanted, n):
+        self._check_whole_model()
+        n, _ = self._recommend_args(n, None)
+        ids, labels = self._training_ids(wanted, side)
+        enc = self.data_handler
+        side_labels = np.asarray(enc.user_labels() if side == "users" else enc.item_labels(), dtype=object) if enc else None
+        ctx, restarts = self._restarts()
+        ctx.similar_begin(side)
+        try:
+            for _ in restarts:
+                ctx.similar_add()
+            return self._top_n_frame(lambda b, e: ctx.similar_query(ids[b:e], n), n, labels, side_labels,
+                                     columns=(side, "similar", "distance"))
+        finally:
+            ctx.similar_end()
 
     # ------------------------------------------------------------------ ranking evaluation (not in the reference)
     def _encode_heldout(self, data):
