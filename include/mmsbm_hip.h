@@ -223,6 +223,22 @@ int mmsbm_hip_recommend_positions(mmsbm_hip_ctx *ctx, int64_t n_users, const int
 int mmsbm_hip_recommend_add_items(mmsbm_hip_ctx *ctx, int32_t n_new, const double *eta,
                                   const int64_t *seen_offsets, const int32_t *seen_users);
 
+/* The m best (user, item) pairs of the whole request, within the open recommend session (mmsbm_amd/csrc/top_pairs.hpp):
+ * candidates are all pairs (u, i), u in users[0 .. n_users) (distinct external ids, any order; users NULL: every
+ * training user, n_users ignored), i in the session's catalogue, without the pairs the session leaves out for u;
+ * score_w(u, i) bit for bit what query returns for the pair; order: score descending, equal scores (exact fp64
+ * equality) by ascending user id, then ascending item id.  out_users / out_items / out_scores: m entries each, the first
+ * *count = min(m, candidates) hold the answer, the rest -1 / -1 / -inf.  The answer does not depend on how the work is
+ * split: option "top_pairs_groups" (0: the library's choice, else the number of workgroups, at most 4096) changes the
+ * time only.  No buffer of n_users x items exists: device memory is O(groups x m + n_users), the launches of a query
+ * do not depend on the sizes.  mmsbm_hip_get_option(ctx, "top_pairs_ms") reads the device time of the last call's
+ * kernels (HIP events).  MMSBM_E_INVALID: no session, no slot added, an id out of range, a repeated id, m < 1;
+ * m > MMSBM_HIP_TOP_PAIRS_MAX_M: MMSBM_E_UNSUPPORTED; MMSBM_E_TOOLARGE where the device memory of the lists is not
+ * free.  Touches no slot, no EM state and no predict / similar session; the recommend session stays open. */
+#define MMSBM_HIP_TOP_PAIRS_MAX_M 1024
+int mmsbm_hip_recommend_top_pairs(mmsbm_hip_ctx *ctx, int64_t n_users, const int32_t *users, int32_t m,
+                                  int32_t *out_users, int32_t *out_items, double *out_scores, int32_t *count);
+
 /* ---- nearest items / users: the n most similar rows of one side (mmsbm_amd/csrc/similar.hpp) -------------------- */
 /* A session of its own beside the recommend session (either may be open while the other is):
  *   begin  side 0: items, 1: users (external sides).  Closes any earlier similarity session;

@@ -57,6 +57,7 @@ SIGNATURES = {
                                                   c_f64p, c_i32p]),
     "mmsbm_hip_recommend_positions": (C.c_int, [C.c_void_p, C.c_int64, c_i32p, c_i64p, c_i32p, c_i32p, c_i32p]),
     "mmsbm_hip_recommend_add_items": (C.c_int, [C.c_void_p, C.c_int32, c_f64p, c_i64p, c_i32p]),
+    "mmsbm_hip_recommend_top_pairs": (C.c_int, [C.c_void_p, C.c_int64, c_i32p, C.c_int32, c_i32p, c_i32p, c_f64p, c_i32p]),
     "mmsbm_hip_similar_begin": (C.c_int, [C.c_void_p, C.c_int]),
     "mmsbm_hip_similar_add": (C.c_int, [C.c_void_p]),
     "mmsbm_hip_similar_query": (C.c_int, [C.c_void_p, C.c_int64, c_i32p, C.c_int32, c_i32p, c_f64p, c_i32p]),

@@ -393,6 +393,22 @@ class HipEM:
         _lib.call("mmsbm_hip_recommend_add_items", self._h, n_new, _p(e, C.c_double),
                   None if off is None else _p(off, C.c_int64), None if us is None else _p(us, C.c_int32))
 
+    MAX_TOP_PAIRS = 1024
+
+    def recommend_top_pairs(self, m, users=None):
+        """(users (m,) int32, items (m,) int32, scores (m,), count): the m best (user, item) pairs of the open session
+        over the encoded user ids ``users`` (distinct; None: every training user) -- score descending, equal scores
+        by ascending user id, then item id; entries behind ``count`` are -1 / -1 / -inf."""
+        u = None if users is None else _i32(users)
+        m = int(m)
+        ou, oi = np.empty(max(m, 0), dtype=np.int32), np.empty(max(m, 0), dtype=np.int32)
+        sc = np.empty(max(m, 0), dtype=np.float64)
+        count = C.c_int32(0)
+        _lib.call("mmsbm_hip_recommend_top_pairs", self._h, 0 if u is None else len(u),
+                  None if u is None else _p(u, C.c_int32), m, _p(ou, C.c_int32), _p(oi, C.c_int32),
+                  _p(sc, C.c_double), C.byref(count))
+        return ou, oi, sc, int(count.value)
+
     def recommend_end(self):
         _lib.call("mmsbm_hip_recommend_end", self._h)
 

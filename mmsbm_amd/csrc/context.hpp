@@ -254,6 +254,8 @@ struct mmsbm_hip_ctx {
   float rc_last_ms = 0.f;                   // device time of the last query's kernels (option "recommend_ms")
   float fold_last_ms = 0.f;                 // device time of the last fold-in's kernels, either side ("fold_in_ms")
   float pos_last_ms = 0.f;                  // device time of the last recommend_positions (option "position_ms")
+  float top_last_ms = 0.f;                  // device time of the last recommend_top_pairs (option "top_pairs_ms")
+  int top_groups = 0;                       // option "top_pairs_groups": workgroups of gtop_fused_kernel (0: 2 per CU)
   std::unique_ptr<mmsbm_hip_impl::SimSession> sm;  // the open similarity session; null: none
   float sim_last_ms = 0.f;                  // device time of the last similar_query's kernels (option "similar_ms")
   int cur = 0;

@@ -48,6 +48,9 @@ void recommend_positions(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users
                          const int32_t *items, int32_t *positions, int32_t *candidates);
 void recommend_add_items(mmsbm_hip_ctx *c, int32_t n_new, const double *eta, const int64_t *seen_offsets,
                          const int32_t *seen_users);
+// ... the m best pairs of the whole model (top_pairs.hpp): users ascending and distinct
+void recommend_top_pairs(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, int m, int32_t *out_users,
+                         int32_t *out_items, double *out_scores, int32_t *count);
 void recommend_end(mmsbm_hip_ctx *c);
 // ... and nearest items / users (similar.hpp): the session of mmsbm_hip_similar_*, arguments checked
 void similar_begin(mmsbm_hip_ctx *c, int side);

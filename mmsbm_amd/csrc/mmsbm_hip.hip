@@ -1505,6 +1505,35 @@ int mmsbm_hip_recommend_add_items(mmsbm_hip_ctx *ctx, int32_t n_new, const doubl
   });
 }
 
+int mmsbm_hip_recommend_top_pairs(mmsbm_hip_ctx *ctx, int64_t n_users, const int32_t *users, int32_t m,
+                                  int32_t *out_users, int32_t *out_items, double *out_scores, int32_t *count) {
+  return guarded([&] {
+    require_session(ctx, "recommend_top_pairs");
+    if (n_users < 0) throw std::invalid_argument("negative n_users");
+    if (m < 1) throw std::invalid_argument("top_pairs: m must be at least 1");
+    if (m > MMSBM_HIP_TOP_PAIRS_MAX_M)
+      throw ApiError(MMSBM_E_UNSUPPORTED, "top_pairs: m = " + std::to_string(m) + " is beyond the " +
+                                              std::to_string(MMSBM_HIP_TOP_PAIRS_MAX_M) + " pairs a query returns at most");
+    if (!out_users || !out_items || !out_scores || !count) throw std::invalid_argument("null argument");
+    // the request in id order (ties go by user id; the kernel walks the users in this order), every training user
+    // when `users` is null; a repeated id would put its pairs into the order twice
+    std::vector<int32_t> ids;
+    if (users) {
+      for (int64_t b = 0; b < n_users; ++b)
+        if (users[b] < 0 || users[b] >= ctx->ext_users)
+          throw std::invalid_argument("top_pairs: user id out of range at row " + std::to_string(b));
+      ids.assign(users, users + n_users);
+      std::sort(ids.begin(), ids.end());
+      const auto twice = std::adjacent_find(ids.begin(), ids.end());
+      if (twice != ids.end()) throw std::invalid_argument("top_pairs: user id " + std::to_string(*twice) + " is repeated");
+    } else {
+      ids.resize(static_cast<size_t>(ctx->ext_users));
+      for (int32_t u = 0; u < ctx->ext_users; ++u) ids[static_cast<size_t>(u)] = u;
+    }
+    recommend_top_pairs(ctx, static_cast<int64_t>(ids.size()), ids.data(), m, out_users, out_items, out_scores, count);
+  });
+}
+
 int mmsbm_hip_similar_begin(mmsbm_hip_ctx *ctx, int side) {
   return guarded([&] {
     if (!ctx) throw std::invalid_argument("null context");
@@ -1714,6 +1743,9 @@ int mmsbm_hip_set_option(mmsbm_hip_ctx *ctx, const char *name, double value) {
       ctx->nt_out = static_cast<int>(value);
     } else if (key == "predict_fast") {  // 0: prod_dist / predict through the per-row kernels (R K L multiply-adds per row)
       ctx->predict_fast = value != 0.0;
+    } else if (key == "top_pairs_groups") {  // workgroups of gtop_fused_kernel (top_pairs.hpp); 0: the library's choice
+      if (value < 0 || value > 4096 || value != std::floor(value)) throw std::invalid_argument("top_pairs_groups: 0 .. 4096");
+      ctx->top_groups = static_cast<int>(value);
     } else if (key == "a_units") {  // 64-pair units per workgroup of the matrix-core A launch; 0: the library's own balance
       if (value < 0 || value > kMfmaChunkPairs / kUnitPairs) throw std::invalid_argument("a_units: 0 .. 16");
       use_device(ctx);
@@ -1744,6 +1776,8 @@ int mmsbm_hip_get_option(const mmsbm_hip_ctx *ctx, const char *name, double *val
     else if (key == "fold_in_ms") *value = ctx->fold_last_ms;  // read-only: device time of the last fold-in (either side)
     else if (key == "position_ms") *value = ctx->pos_last_ms;  // read-only: device time of the last recommend_positions
     else if (key == "similar_ms") *value = ctx->sim_last_ms;   // read-only: device time of the last similar_query
+    else if (key == "top_pairs_ms") *value = ctx->top_last_ms; // read-only: device time of the last recommend_top_pairs
+    else if (key == "top_pairs_groups") *value = ctx->top_groups;
     else if (key == "launches") *value = use_fused(ctx) ? 2 : 4;  // read-only: launches per iteration at the current slot count
     else if (key == "wide") *value = ctx->wide;
     else if (key == "lik_fast") *value = ctx->lik_mode;

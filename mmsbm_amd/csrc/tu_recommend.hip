@@ -1,9 +1,11 @@
 // tu_recommend.hip -- translation unit of top-N recommendation (recommend.hpp): the session's host side -- the
 // training items of every user, the per-slot prologue, the batches of a query and the choice of the item split -- and
-// of nearest items / users (similar.hpp), whose queries share the batches and the selection
+// of nearest items / users (similar.hpp), whose queries share the batches and the selection; and the m best pairs of
+// the whole model (top_pairs.hpp), a query of the recommend session with kernels of its own
 #include "prelude.hpp"
 #include "recommend.hpp"
 #include "similar.hpp"
+#include "top_pairs.hpp"
 
 #include <climits>
 
@@ -410,6 +412,71 @@ void recommend_positions(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users
   HIP_CHECK(hipMemcpyAsync(positions, dpos.ptr, sizeof(int32_t) * total, hipMemcpyDeviceToHost, st));
   HIP_CHECK(hipStreamSynchronize(st));
   c->pos_last_ms = ev.ms();
+}
+
+// The m best pairs over users[0 .. n_users) (host ids, ascending and distinct) x the session's catalogue
+// (top_pairs.hpp).  The launches of a query: one fused launch and the merge levels of G lists -- whatever U and I.
+void recommend_top_pairs(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, int m, int32_t *out_users,
+                         int32_t *out_items, double *out_scores, int32_t *count) {
+  use_device(c);
+  const RecSession &rc = *c->rc;
+  const int I = rc.items, rank = rc.rank;
+  for (int k = 0; k < m; ++k) {
+    out_users[k] = -1;
+    out_items[k] = -1;
+    out_scores[k] = -INFINITY;
+  }
+  *count = 0;
+  c->top_last_ms = 0.f;
+  if (n_users == 0 || I == 0) return;
+  hipStream_t st = c->stream;
+  const int64_t tiles = ((n_users + kRecTile - 1) / kRecTile) * ((static_cast<int64_t>(I) + kRecTile - 1) / kRecTile);
+  // G: two workgroups per CU (what the LDS of gtop_fused_kernel allows), one resident set that walks all tiles
+  const int G = static_cast<int>(std::min<int64_t>(c->top_groups > 0 ? c->top_groups : 2 * c->n_cus, tiles));
+  const size_t per_list = static_cast<size_t>(m) * (sizeof(double) + sizeof(uint64_t)) + sizeof(int32_t);
+  const int G1 = (G + kTopFan - 1) / kTopFan;  // lists after the first merge level
+  require_free_mem((static_cast<size_t>(G) + G1) * per_list + static_cast<size_t>(n_users) * 4, "top_pairs: the workgroups' lists");
+  DevBuf<int32_t> du, na, nb2;
+  DevBuf<double> sa, sb;
+  DevBuf<uint64_t> ka, kb;
+  du.alloc(n_users);
+  sa.alloc(static_cast<size_t>(G) * m); ka.alloc(static_cast<size_t>(G) * m); na.alloc(G);
+  sb.alloc(static_cast<size_t>(G1) * m); kb.alloc(static_cast<size_t>(G1) * m); nb2.alloc(G1);
+  HIP_CHECK(hipMemcpyAsync(du.ptr, users, sizeof(int32_t) * n_users, hipMemcpyHostToDevice, st));
+  EventPair ev;  // device time of the query's kernels (option "top_pairs_ms")
+  ev.start(st);
+  LAUNCH(gtop_fused_kernel, G, kBlock, 0, st, rc.x.ptr, static_cast<size_t>(c->ext_users) * rank, rc.y.ptr,
+         static_cast<size_t>(I) * rank, du.ptr, static_cast<int>(n_users), I, rank, rc.slots,
+         rc.excl ? rc.seen_off.ptr : nullptr, rc.seen.ptr, m, sa.ptr, ka.ptr, na.ptr);
+  // merge levels: a -> b -> a ... until one list is left (G = 1: one level, so that the merge is always part of a query)
+  double *is = sa.ptr, *os = sb.ptr;
+  uint64_t *ik = ka.ptr, *ok = kb.ptr;
+  int32_t *in = na.ptr, *on = nb2.ptr;
+  int lists = G;
+  do {
+    const int out_lists = (lists + kTopFan - 1) / kTopFan;
+    LAUNCH(gtop_merge_kernel, out_lists, kBlock, 0, st, is, ik, in, lists, kTopFan, m, os, ok, on);
+    std::swap(is, os);
+    std::swap(ik, ok);
+    std::swap(in, on);
+    lists = out_lists;
+  } while (lists > 1);
+  HIP_CHECK(hipGetLastError());
+  ev.stop(st);
+  std::vector<double> hs(static_cast<size_t>(m));
+  std::vector<uint64_t> hk(static_cast<size_t>(m));
+  int32_t hn = 0;
+  HIP_CHECK(hipMemcpyAsync(hs.data(), is, sizeof(double) * m, hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipMemcpyAsync(hk.data(), ik, sizeof(uint64_t) * m, hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipMemcpyAsync(&hn, in, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipStreamSynchronize(st));
+  c->top_last_ms = ev.ms();
+  *count = hn;
+  for (int k = 0; k < hn; ++k) {
+    out_users[k] = static_cast<int32_t>(hk[static_cast<size_t>(k)] >> 32);
+    out_items[k] = static_cast<int32_t>(hk[static_cast<size_t>(k)] & 0xffffffffu);
+    out_scores[k] = hs[static_cast<size_t>(k)];
+  }
 }
 
 void recommend_end(mmsbm_hip_ctx *c) { c->rc.reset(); }

@@ -312,6 +312,44 @@ class MMSBM:
                 ctx.recommend_add()
             return self._top_n_frame(lambda b, e: ctx.recommend_query(ids[b:e], n), n, labels, item_labels)
 
+    TOP_PAIRS_MAX = 1024             # largest m of top_pairs (MMSBM_HIP_TOP_PAIRS_MAX_M)
+
+    def top_pairs(self, m=100, users=None, exclude_seen=True, weights=None):
+        """The ``m`` best (user, item) pairs of the whole model, ranked on the device in ONE order over all pairs of
+        ``users`` (None: every training user) and the training items -- the most probable missing links of a network,
+        the strongest matches of a catalogue.  Scores as in ``recommend`` (the same numbers, bit for bit); candidates
+        are all pairs, without the training pairs when ``exclude_seen``.  Order: score descending, equal scores by
+        ascending encoded user id, then encoded item id; the order in which ``users`` are named does not matter.
+
+        Returns a DataFrame with columns ``users``, ``items``, ``score``, ``rank`` (1 = best of all), at most ``m``
+        rows, labels as ``recommend`` returns them.  The model's stored predictions and ``score()`` are left as they
+        are."""
+        import pandas as pd
+        self._check_whole_model()
+        if isinstance(m, (bool, np.bool_)) or not isinstance(m, (int, np.integer)) or m < 1:
+            raise ValueError(f"m must be a positive integer, got {m!r}")
+        if m > self.TOP_PAIRS_MAX:
+            raise ValueError(f"m = {m} is beyond the {self.TOP_PAIRS_MAX} pairs a query returns at most")
+        m, w = int(m), self._rating_weights(weights)
+        enc = self.data_handler
+        ids = None
+        if users is not None:
+            ids, labels = self._training_users(users)
+            if len(np.unique(ids)) != len(ids):
+                twice = list(dict.fromkeys(labels[np.isin(ids, ids[np.bincount(ids)[ids] > 1])].tolist()))
+                raise ValueError(f"users named more than once: {twice}")
+        ctx, restarts = self._restarts()
+        with self._recommend_session(ctx, w, exclude_seen):
+            for _ in restarts:
+                ctx.recommend_add()
+            us, its, scores, count = ctx.recommend_top_pairs(m, ids)
+        us, its = us[:count].astype(np.int64), its[:count].astype(np.int64)
+        return pd.DataFrame({
+            "users": np.asarray(enc.user_labels(), dtype=object)[us] if enc else us,
+            "items": np.asarray(enc.item_labels(), dtype=object)[its] if enc else its,
+            "score": scores[:count],
+            "rank": np.arange(1, count + 1, dtype=np.int64)})
+
     @staticmethod
     @contextlib.contextmanager
     def _recommend_session(ctx, weights, exclude_seen):
