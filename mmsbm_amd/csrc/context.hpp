@@ -77,6 +77,16 @@ struct DevBuf {
   }
 };
 
+// A session table of `slots` slots, `per_slot` doubles each, grown by one slot: `next` becomes the table of slots + 1 with
+// the earlier slots copied as they are (device to device, on `s`); returns the new slot.  The caller checks the memory
+// first, fills the new slot, and swaps `next` in once its kernels have run.
+inline double *grow_by_slot(const DevBuf<double> &tab, size_t per_slot, int slots, hipStream_t s, DevBuf<double> &next) {
+  next.alloc((static_cast<size_t>(slots) + 1) * per_slot);
+  if (slots > 0)
+    HIP_CHECK(hipMemcpyAsync(next.ptr, tab.ptr, sizeof(double) * slots * per_slot, hipMemcpyDeviceToDevice, s));
+  return next.ptr + static_cast<size_t>(slots) * per_slot;
+}
+
 // A per-restart table: `slots` copies, `stride` doubles apart (whole 128-byte lines, so every
 // copy keeps the alignment of the first).
 struct SlotBuf : DevBuf<double> {
@@ -161,6 +171,32 @@ void for_row_blocks(int rows, size_t row_doubles, F &&fn) {
     if (a < b) th.emplace_back([&fn, a, b] { fn(a, b); });
   }
   for (auto &x : th) x.join();
+}
+
+// The n pairs (key[m], value m) grouped by key < n_keys (counting sort): returns off [n_keys + 1], and put(m, at) is told
+// the place `at` in [off[key[m]], off[key[m] + 1]) of pair m -- a key's pairs keep the order of the request.
+template <class Off, class Put>
+std::vector<Off> group_by_key(const int32_t *key, int64_t n, int n_keys, Put &&put) {
+  std::vector<Off> off(static_cast<size_t>(n_keys) + 1, 0);
+  for (int64_t m = 0; m < n; ++m) off[static_cast<size_t>(key[m]) + 1]++;
+  for (int k = 0; k < n_keys; ++k) off[k + 1] += off[k];
+  std::vector<Off> pos(off.begin(), off.end() - 1);
+  for (int64_t m = 0; m < n; ++m) put(m, pos[key[m]]++);
+  return off;
+}
+
+// Every group of (off, val) ascending and distinct, in place (off and val shrink to what is kept)
+inline void sort_unique_groups(std::vector<int32_t> &off, std::vector<int32_t> &val) {
+  int32_t w = 0;
+  for (size_t g = 0; g + 1 < off.size(); ++g) {
+    const int32_t a = off[g], b = off[g + 1];
+    std::sort(val.begin() + a, val.begin() + b);
+    off[g] = w;
+    for (int32_t e = a; e < b; ++e)
+      if (e == a || val[e] != val[e - 1]) val[w++] = val[e];
+  }
+  off.back() = w;
+  val.resize(static_cast<size_t>(w));
 }
 
 enum KernelId { K_SEG = 0, K_DENSE, K_ETAP, K_MATVEC_A, K_FUSED_PAIRS, K_FUSED_TAIL, K_COUNT };

@@ -129,6 +129,8 @@ inline RowTab gather_tab(const mmsbm_hip_ctx *c, double *base, size_t rows, int 
 inline RowTab theta_tab(const mmsbm_hip_ctx *c, int b) {
   return gather_tab(c, c->theta[b].ptr, static_cast<size_t>(c->n_users), c->base_slot);
 }
+// eta streams: one plain table per slot.  Of the SELECTED slot (single-restart entry points)
+inline RowTab eta_tab(const mmsbm_hip_ctx *c, int b) { return plain_tab(c->eta[b].at(c->sel), c->lp); }
 inline RowTab a_tab(const mmsbm_hip_ctx *c, int b) {
   return gather_tab(c, c->atab[b].ptr, static_cast<size_t>(c->n_pairs), c->base_slot);
 }
@@ -145,6 +147,23 @@ struct OneSlot {
   }
   ~OneSlot() { c->base_slot = b; c->launch_slots = n; }
 };
+
+// The selected slot's current parameters in EXTERNAL terms (the caller holds a OneSlot), whichever internal side holds
+// the caller's users: element (k, l, r) of p at p[r * rs + k * ks + l * ls] -- internal (k, l), or (l, k) when the
+// context is swapped -- and the caller's users' / items' rows (theta / eta, or eta / theta when swapped).  The serving
+// paths (recommend, similar, fold-in) read the model through this and nothing else, so a swapped context gives them
+// the same values in the same order.
+struct ExtSlot {
+  const double *p;
+  size_t rs;
+  int ks, ls;
+  RowTab users, items;
+};
+inline ExtSlot ext_slot(const mmsbm_hip_ctx *c) {
+  const RowTab th = theta_tab(c, c->cur), et = eta_tab(c, c->cur);
+  return ExtSlot{c->p[c->cur].at(c->sel), static_cast<size_t>(c->kp) * c->lp, c->swapped ? 1 : c->lp,
+                 c->swapped ? c->lp : 1, c->swapped ? et : th, c->swapped ? th : et};
+}
 
 // Non-temporal stores for the rows the next launch gathers (T, A, theta'): one restart per launch and rows of up to
 // 32 groups.  Measured per iteration, plain -> non-temporal (scripts/ab_fused.sh, variants side by side on one box): C1

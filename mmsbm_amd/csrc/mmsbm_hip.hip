@@ -967,7 +967,7 @@ int mmsbm_hip_set_params(mmsbm_hip_ctx *ctx, const double *theta, const double *
     HIP_CHECK(hipStreamSynchronize(ctx->stream));  // nothing in flight still reads the staging area
     ctx->pin.reset(rows_doubles(ctx));
     upload_rows(ctx, theta_tab(ctx, cur), it, ctx->n_users, ctx->k);
-    upload_rows(ctx, plain_tab(ctx->eta[cur].at(sl), ctx->lp), ie, ctx->n_items, ctx->l);
+    upload_rows(ctx, eta_tab(ctx, cur), ie, ctx->n_items, ctx->l);
     const size_t klr = static_cast<size_t>(ctx->n_ratings) * ctx->kp * ctx->lp;
     double *p = ctx->pin.take(klr), *pt = ctx->pin.take(klr);
     p_host_to_dev(ctx, pr, p, pt);
@@ -996,7 +996,7 @@ int mmsbm_hip_init_params(mmsbm_hip_ctx *ctx, const uint64_t pcg64_state[4], con
     HIP_CHECK(hipMemcpyAsync(ctx->p[cur].at(sl), p, sizeof(double) * klr, hipMemcpyHostToDevice, ctx->stream));
     HIP_CHECK(hipMemcpyAsync(ctx->pt[cur].at(sl), pt, sizeof(double) * klr, hipMemcpyHostToDevice, ctx->stream));
     zero_rows(ctx, theta_tab(ctx, cur), ctx->n_users);  // padding columns
-    zero_rows(ctx, plain_tab(ctx->eta[cur].at(sl), ctx->lp), ctx->n_items);
+    zero_rows(ctx, eta_tab(ctx, cur), ctx->n_items);
     init_rows_launch(ctx, pcg64_state);
     stage_matvec_a(ctx, cur, cur);
     HIP_CHECK(hipStreamSynchronize(ctx->stream));
@@ -1022,7 +1022,7 @@ int mmsbm_hip_get_params(mmsbm_hip_ctx *ctx, double *theta, double *eta, double 
     double *it = ctx->swapped ? eta : theta;
     double *ie = ctx->swapped ? theta : eta;
     const int cur = ctx->cur, sl = ctx->sel;
-    fetch_params(ctx, theta_tab(ctx, cur), plain_tab(ctx->eta[cur].at(sl), ctx->lp),
+    fetch_params(ctx, theta_tab(ctx, cur), eta_tab(ctx, cur),
                  ctx->p[cur].at(sl), it, ie, pr);
   });
 }
@@ -1112,7 +1112,7 @@ int mmsbm_hip_update_coefficients(mmsbm_hip_ctx *ctx, double *n_theta, double *n
     const int nxt = ctx->cur ^ 1, sl = ctx->sel;
     double *it = ctx->swapped ? n_eta : n_theta;
     double *ie = ctx->swapped ? n_theta : n_eta;
-    fetch_params(ctx, theta_tab(ctx, nxt), plain_tab(ctx->eta[nxt].at(sl), ctx->lp),
+    fetch_params(ctx, theta_tab(ctx, nxt), eta_tab(ctx, nxt),
                  ctx->npr.at(sl), it, ie, n_pr);
   });
 }
@@ -1155,7 +1155,7 @@ int mmsbm_hip_result(mmsbm_hip_ctx *ctx, double *theta, double *eta, double *pr,
       Xfer on(ctx);
       double *it = ctx->swapped ? eta : theta;
       double *ie = ctx->swapped ? theta : eta;
-      fetch_params(ctx, theta_tab(ctx, ctx->cur), plain_tab(ctx->eta[ctx->cur].at(ctx->sel), ctx->lp),
+      fetch_params(ctx, theta_tab(ctx, ctx->cur), eta_tab(ctx, ctx->cur),
                    ctx->p[ctx->cur].at(ctx->sel), it, ie, pr);
     }
     *likelihood = likelihood_finish(ctx, nb);

@@ -24,6 +24,11 @@
 //                       in a user's full order: per (user, item range) the items of the range that beat each test
 //                       item, counted as integers with up to kPosKeys test keys in registers per pass over the row;
 //                       the ranges' counts are then summed in range order (no atomics).
+// Shared with top_pairs.hpp, which holds no copy of either: the tile's accumulation (rec_tile_acc: staging + the 8 x 8
+// fma loop; rec_score_kernel stores the tile, gtop_fused_kernel filters it in registers) and the candidate list
+// (RecList, rec_better, rec_sort, rec_sort_cut: one order, one bitonic network, one "sort, cut to n, take the n-th as
+// threshold", by key type and workgroup width).  How survivors are appended stays with each kernel: a one-wave ballot
+// here, a workgroup prefix sum there.
 // Order: score descending, equal scores (exact fp64 equality) by ascending item id -- a strict total order, so the
 // top N is unique and the split into ranges cannot change it.  N is bounded by kRecMaxN (larger N: the C ABI answers
 // MMSBM_E_UNSUPPORTED); the candidate list holds the next power of two >= N + 256 entries (<= 2,048).
@@ -69,17 +74,18 @@ __global__ __launch_bounds__(kBlock) void rec_fold_kernel(RowTab src, int d, con
   out[e] = acc;
 }
 
-// scores[b * ld + i] = (1/S) sum_f x[users[b], f] y[i, f] for b < nb, i < ni; x / y: `slots` tables [rows][rank]
-// one after the other (x: xs doubles apart, y: ys).  grid (item tiles, user tiles).
-__global__ __launch_bounds__(kBlock) void rec_score_kernel(const double *__restrict__ x, size_t xs,
-                                                           const double *__restrict__ y, size_t ys,
-                                                           const int32_t *__restrict__ users, int nb, int ni,
-                                                           int rank, int slots, double *__restrict__ scores, size_t ld) {
-  __shared__ double xt[kRecKc][kRecLdsRow];
-  __shared__ double yt[kRecKc][kRecLdsRow];
-  const int tid = threadIdx.x, tx = tid % 16, ty = tid / 16;
-  const int i0 = blockIdx.x * kRecTile, b0 = blockIdx.y * kRecTile;
-  double acc[kRecTm][kRecTm];
+// THE score tile (the one copy: rec_score_kernel and gtop_fused_kernel of top_pairs.hpp both call it, so a pair's score
+// is the same bits in both).  acc[a][c] = sum_f x[users[b0 + ty * 8 + a], f] y[i0 + tx + 16 * c, f]: ONE fma chain per
+// output over f = s * rank + j ascending from +0.0, rows beyond nb / ni as 0.0; the caller divides once by S.
+// x / y: `slots` tables [rows][rank] one after the other (x: xs doubles apart, y: ys).  All 256 threads; (tx, ty) =
+// (tid % 16, tid / 16) is the caller's, which reads acc by it (derived again in here, the compiler no longer proves the
+// 16-byte alignment of a thread's eight x entries and narrows their LDS reads); xt / yt: the workgroup's two staging
+// tiles, free again on return.
+__device__ __forceinline__ void rec_tile_acc(const double *__restrict__ x, size_t xs, const double *__restrict__ y,
+                                             size_t ys, const int32_t *__restrict__ users, int nb, int ni, int rank,
+                                             int slots, int b0, int i0, int tx, int ty, double (&xt)[kRecKc][kRecLdsRow],
+                                             double (&yt)[kRecKc][kRecLdsRow], double (&acc)[kRecTm][kRecTm]) {
+  const int tid = threadIdx.x;
 #pragma unroll
   for (int a = 0; a < kRecTm; ++a)
 #pragma unroll
@@ -114,6 +120,20 @@ __global__ __launch_bounds__(kBlock) void rec_score_kernel(const double *__restr
     }
     __syncthreads();
   }
+}
+
+// scores[b * ld + i] = (1/S) sum_f x[users[b], f] y[i, f] for b < nb, i < ni (rec_tile_acc).  grid (item tiles, user
+// tiles).
+__global__ __launch_bounds__(kBlock) void rec_score_kernel(const double *__restrict__ x, size_t xs,
+                                                           const double *__restrict__ y, size_t ys,
+                                                           const int32_t *__restrict__ users, int nb, int ni,
+                                                           int rank, int slots, double *__restrict__ scores, size_t ld) {
+  __shared__ double xt[kRecKc][kRecLdsRow];
+  __shared__ double yt[kRecKc][kRecLdsRow];
+  const int tid = threadIdx.x, tx = tid % 16, ty = tid / 16;
+  const int i0 = blockIdx.x * kRecTile, b0 = blockIdx.y * kRecTile;
+  double acc[kRecTm][kRecTm];
+  rec_tile_acc(x, xs, y, ys, users, nb, ni, rank, slots, b0, i0, tx, ty, xt, yt, acc);
   const double n_slots = static_cast<double>(slots);
 #pragma unroll
   for (int a = 0; a < kRecTm; ++a) {
@@ -139,31 +159,62 @@ __global__ __launch_bounds__(kBlock) void rec_exclude_kernel(const int32_t *__re
   for (int e = seen_off[u] + threadIdx.x; e < seen_off[u + 1]; e += kBlock) row[seen_item[e]] = -INFINITY;
 }
 
-__device__ __forceinline__ bool rec_better(double sa, int ia, double sb, int ib) {
-  return sa > sb || (sa == sb && ia < ib);
+// THE order of every candidate list (the one definition): score descending, equal scores by ascending key.  Key: the
+// item id (int) of a top-N query, (user << 32 | item) (uint64_t) of top_pairs.hpp.
+template <class Key>
+__device__ __forceinline__ bool rec_better(double sa, Key ka, double sb, Key kb) {
+  return sa > sb || (sa == sb && ka < kb);
 }
 
-// Sorts the first `cnt` entries of (ks, ki) best first (entries up to the next power of two are padded with the
-// sentinel (-inf, INT_MAX), worse than any candidate).  One wave; cap = room of the arrays (a power of two).
-__device__ void rec_sort(double *ks, int *ki, int cnt) {
+// A candidate list in LDS: entries [0, cnt) of (ks, kk), and the threshold -- the n-th best -- once n entries were
+// accepted.  Everything but the arrays is uniform over the workgroup.
+template <class Key>
+struct RecList {
+  double *ks;
+  Key *kk;
+  int cnt = 0;
+  bool have_thr = false;
+  double thr_s = 0.0;
+  Key thr_k = 0;
+  __device__ bool admits(double s, Key k) const { return !have_thr || rec_better(s, k, thr_s, thr_k); }
+};
+
+// Sorts the first `cnt` entries of (ks, kk) best first (THE bitonic network; entries up to the next power of two are
+// padded with the sentinel (-inf, largest key), worse than any candidate: the arrays hold a power of two).  All THREADS
+// threads of the workgroup; what they wrote to the list before is ordered by the first barrier in here.
+template <int THREADS, class Key>
+__device__ void rec_sort(double *ks, Key *kk, int cnt) {
   int sz = 2;
   while (sz < cnt) sz <<= 1;
-  for (int t = cnt + threadIdx.x; t < sz; t += kRecWave) { ks[t] = -INFINITY; ki[t] = INT_MAX; }
+  for (int t = cnt + threadIdx.x; t < sz; t += THREADS) { ks[t] = -INFINITY; kk[t] = std::numeric_limits<Key>::max(); }
   __syncthreads();
   for (int k = 2; k <= sz; k <<= 1) {
     for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int t = threadIdx.x; t < sz / 2; t += kRecWave) {
+      for (int t = threadIdx.x; t < sz / 2; t += THREADS) {
         const int i = (t / j) * 2 * j + (t % j), q = i + j;
         const double si = ks[i], sq = ks[q];
-        const int ii = ki[i], iq = ki[q];
+        const Key ki = kk[i], kq = kk[q];
         const bool up = (i & k) == 0;  // this half: best first
-        if (up ? rec_better(sq, iq, si, ii) : rec_better(si, ii, sq, iq)) {
-          ks[i] = sq; ki[i] = iq; ks[q] = si; ki[q] = ii;
+        if (up ? rec_better(sq, kq, si, ki) : rec_better(si, ki, sq, kq)) {
+          ks[i] = sq; kk[i] = kq; ks[q] = si; kk[q] = ki;
         }
       }
       __syncthreads();
     }
   }
+}
+
+// Sorts the list best first, cuts it to n and takes the n-th as the threshold.  All THREADS threads.
+template <int THREADS, class Key>
+__device__ void rec_sort_cut(RecList<Key> &L, int n) {
+  rec_sort<THREADS>(L.ks, L.kk, L.cnt);
+  L.cnt = min(L.cnt, n);
+  if (L.cnt == n) {
+    L.thr_s = L.ks[n - 1];
+    L.thr_k = L.kk[n - 1];
+    L.have_thr = true;
+  }
+  __syncthreads();  // (the threshold is read before the list is written again)
 }
 
 // The N best of one (user, range).  One wave per workgroup; grid (parts, users).
@@ -180,8 +231,7 @@ __global__ __launch_bounds__(kRecWave) void rec_select_kernel(const double *__re
                                                               int cap, double *__restrict__ out_s,
                                                               int32_t *__restrict__ out_i, int32_t *__restrict__ out_n) {
   extern __shared__ double rec_lds[];
-  double *ks = rec_lds;
-  int *ki = reinterpret_cast<int *>(rec_lds + cap);
+  RecList<int> L{rec_lds, reinterpret_cast<int *>(rec_lds + cap)};
   const int lane = threadIdx.x, part = blockIdx.x, b = blockIdx.y;
   int lo, hi;
   if (MERGE) {
@@ -191,22 +241,10 @@ __global__ __launch_bounds__(kRecWave) void rec_select_kernel(const double *__re
     lo = part * per;
     hi = min(ni, lo + per);
   }
-  int cnt = 0;
-  bool have_thr = false;
-  double thr_s = 0.0;
-  int thr_i = 0;
   const double *row = MERGE ? nullptr : scores + static_cast<size_t>(b) * ld;
   for (int base = lo; base < hi; base += kRecWave * kRecPerLane) {
-    if (cnt + kRecWave * kRecPerLane > cap) {  // no room for a whole round: keep the N best, raise the threshold
-      rec_sort(ks, ki, cnt);
-      cnt = min(cnt, n);
-      if (cnt == n) {
-        thr_s = ks[n - 1];
-        thr_i = ki[n - 1];
-        have_thr = true;
-      }
-      __syncthreads();
-    }
+    // no room for a whole round: keep the N best, raise the threshold
+    if (L.cnt + kRecWave * kRecPerLane > cap) rec_sort_cut<kRecWave>(L, n);
     double sv[kRecPerLane];
     int iv[kRecPerLane];
     bool ok[kRecPerLane];
@@ -234,26 +272,25 @@ __global__ __launch_bounds__(kRecWave) void rec_select_kernel(const double *__re
     }
 #pragma unroll
     for (int e = 0; e < kRecPerLane; ++e) {
-      const bool q = ok[e] && (!have_thr || rec_better(sv[e], iv[e], thr_s, thr_i));
+      const bool q = ok[e] && L.admits(sv[e], iv[e]);
       const uint64_t mask = __ballot(q);
       const uint64_t below = lane == 0 ? 0 : (mask & ((~uint64_t(0)) >> (64 - lane)));
       if (q) {
-        const int at = cnt + __popcll(below);
-        ks[at] = sv[e];
-        ki[at] = iv[e];
+        const int at = L.cnt + __popcll(below);
+        L.ks[at] = sv[e];
+        L.kk[at] = iv[e];
       }
-      cnt += __popcll(mask);
+      L.cnt += __popcll(mask);
     }
     __syncthreads();
   }
-  rec_sort(ks, ki, cnt);
-  cnt = min(cnt, n);
+  rec_sort_cut<kRecWave>(L, n);
   const size_t o = (static_cast<size_t>(b) * gridDim.x + part);
-  for (int k = lane; k < cnt; k += kRecWave) {
-    out_s[o * n + k] = ks[k];
-    out_i[o * n + k] = ki[k];
+  for (int k = lane; k < L.cnt; k += kRecWave) {
+    out_s[o * n + k] = L.ks[k];
+    out_i[o * n + k] = L.kk[k];
   }
-  if (lane == 0) out_n[o] = cnt;
+  if (lane == 0) out_n[o] = L.cnt;
 }
 
 // ---- positions of test items (mmsbm_hip_recommend_positions) --------------------------------------------------------

@@ -71,7 +71,9 @@ __global__ __launch_bounds__(kBlock) void sim_profile_kernel(RowTab src, int T, 
 
 // out[b * ld + i] = -( sum_f mf[f] (q[ids[b], f] - q[i, f])^2 / denom ) for b < nb, i < rows, -inf where i == ids[b];
 // q: `slots` tables [rows][width] qs doubles apart, mf: [slots][width], f = s * width + j.
-// grid (row tiles, query tiles).
+// grid (row tiles, query tiles).  A tile loop of its own, not rec_tile_acc (recommend.hpp): 64 x 64 with 4 x 4 outputs,
+// the step d = x - y, acc = fma(w * d, d, acc) with the masses staged beside the rows -- a template wide enough for
+// both would be more machinery than the two loops.
 __global__ __launch_bounds__(kBlock) void sim_dist_kernel(const double *__restrict__ q, size_t qs,
                                                           const double *__restrict__ mf,
                                                           const int32_t *__restrict__ ids, int nb, int rows, int width,

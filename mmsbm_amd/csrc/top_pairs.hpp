@@ -7,9 +7,9 @@
 //
 //   gtop_fused_kernel   G workgroups, each owning a contiguous run of 128 x 128 (user, item) tiles (tile t = user tile
 //                       t / item tiles, item tile t % item tiles; 64-bit tile numbers).  Per tile the 8 x 8 accumulators
-//                       per thread are formed by the loop of rec_score_kernel (copied: the same fma chain over
-//                       f = s * rank + j from +0.0, then one division by S, so a pair's score is bit for bit
-//                       recommend_query's) and stay in registers:
+//                       per thread are formed by rec_tile_acc (recommend.hpp), the function rec_score_kernel calls:
+//                       the same fma chain over f = s * rank + j from +0.0, then one division by S, so a pair's score
+//                       is bit for bit recommend_query's -- by construction -- and stay in registers:
 //                         1. pre-filter, 64 compares per thread: acc >= lo, where lo is the smallest accumulator whose
 //                            QUOTIENT reaches the threshold score (the correctly rounded division by S is monotone, so
 //                            acc < lo implies acc / S < threshold; lo is searched among the neighbours of threshold * S
@@ -19,7 +19,7 @@
 //                            its m-th best accepted pair so far -- and only then search the user's ascending seen list;
 //                         3. survivors are appended to the candidate list in LDS at positions from a workgroup prefix
 //                            sum of the per-thread counts (no atomics); what does not fit waits in the thread's bit mask
-//                            while the list is sorted (bitonic, 256 threads) and cut to m, which raises the threshold,
+//                            while the list is sorted and cut to m (rec_sort_cut, 256 threads), which raises the threshold,
 //                            and is then judged again.  The first tile (no threshold, 16,384 candidates) goes through
 //                            the same loop in pieces of at most kTopCap - m.
 //                       The workgroup writes its <= m best (score, user << 32 | item), best first.
@@ -43,10 +43,6 @@ static_assert(kTopFan <= kBlock, "a round of the merge visits every list");
 
 __device__ __forceinline__ uint64_t gtop_key(int u, int i) {
   return (static_cast<uint64_t>(static_cast<uint32_t>(u)) << 32) | static_cast<uint32_t>(i);
-}
-
-__device__ __forceinline__ bool gtop_better(double sa, uint64_t ka, double sb, uint64_t kb) {
-  return sa > sb || (sa == sb && ka < kb);
 }
 
 // The neighbour of x towards +inf (up) or -inf
@@ -82,48 +78,8 @@ __device__ __forceinline__ double gtop_pick(const double (&row)[kRecTm], int c) 
   return b2 ? q1 : q0;
 }
 
-// The candidate list of a workgroup: entries [0, cnt) of (ks, kk) in LDS, the threshold once m entries were accepted.
-struct GtopList {
-  double *ks;
-  uint64_t *kk;
-  int *wtot;          // [kTopWaves + 1]
-  int cnt;            // (workgroup-uniform, like everything below)
-  bool have_thr;
-  double thr_s;
-  uint64_t thr_k;
-};
-
-// Sorts the list best first, cuts it to m and takes the threshold.  All 256 threads.
-__device__ void gtop_sort_cut(GtopList &L, int m) {
-  double *ks = L.ks;
-  uint64_t *kk = L.kk;
-  const int cnt = L.cnt;
-  int sz = 2;
-  while (sz < cnt) sz <<= 1;
-  for (int t = cnt + threadIdx.x; t < sz; t += kBlock) { ks[t] = -INFINITY; kk[t] = ~uint64_t(0); }
-  __syncthreads();
-  for (int k = 2; k <= sz; k <<= 1) {
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int t = threadIdx.x; t < sz / 2; t += kBlock) {
-        const int i = (t / j) * 2 * j + (t % j), q = i + j;
-        const double si = ks[i], sq = ks[q];
-        const uint64_t ki = kk[i], kq = kk[q];
-        const bool up = (i & k) == 0;  // this half: best first
-        if (up ? gtop_better(sq, kq, si, ki) : gtop_better(si, ki, sq, kq)) {
-          ks[i] = sq; kk[i] = kq; ks[q] = si; kk[q] = ki;
-        }
-      }
-      __syncthreads();
-    }
-  }
-  L.cnt = min(cnt, m);
-  if (L.cnt == m) {
-    L.thr_s = ks[m - 1];
-    L.thr_k = kk[m - 1];
-    L.have_thr = true;
-  }
-  __syncthreads();
-}
+// The candidate list of a workgroup: recommend.hpp's list, order and sort with the pair key (user << 32 | item)
+using GtopList = RecList<uint64_t>;
 
 // Exclusive prefix of k over the workgroup's threads (thread order) and the total.  All 256 threads.
 __device__ __forceinline__ int gtop_scan(int k, int *wtot, int &total) {
@@ -173,10 +129,9 @@ __global__ __launch_bounds__(kBlock) void gtop_fused_kernel(const double *__rest
   __shared__ uint64_t list_k[kTopCap];
   __shared__ int wtot[kTopWaves + 1];
   const int tid = threadIdx.x, tx = tid % 16, ty = tid / 16;
-  GtopList L{list_s, list_k, wtot, 0, false, 0.0, 0};
+  GtopList L{list_s, list_k};
   double lo = -INFINITY;  // the pre-filter's bound on the accumulator
   const double n_slots = static_cast<double>(slots);
-  const int F = rank * slots;
   // this workgroup's tiles: [t0, t1) of n_ut * n_it, the first T % G workgroups one more than the others
   const long long n_it = (ni + kRecTile - 1) / kRecTile, n_ut = (nb + kRecTile - 1) / kRecTile;
   const long long T = n_it * n_ut, G = gridDim.x, g = blockIdx.x;
@@ -184,39 +139,7 @@ __global__ __launch_bounds__(kBlock) void gtop_fused_kernel(const double *__rest
   for (long long t = t0; t < t1; ++t) {
     const int b0 = static_cast<int>(t / n_it) * kRecTile, i0 = static_cast<int>(t % n_it) * kRecTile;
     double acc[kRecTm][kRecTm];
-#pragma unroll
-    for (int a = 0; a < kRecTm; ++a)
-#pragma unroll
-      for (int c = 0; c < kRecTm; ++c) acc[a][c] = 0.0;
-    // ---- the accumulation of rec_score_kernel ----
-    for (int f0 = 0; f0 < F; f0 += kRecKc) {
-      const int kc = min(kRecKc, F - f0);
-#pragma unroll
-      for (int mm = 0; mm < kRecTile * kRecKc / kBlock; ++mm) {
-        const int e = tid + kBlock * mm, kk = e % kRecKc, r = e / kRecKc;
-        const int f = f0 + kk, s = f / rank, j = f - s * rank;
-        double xv = 0.0, yv = 0.0;
-        if (f < F) {
-          if (b0 + r < nb) xv = x[static_cast<size_t>(s) * xs + static_cast<size_t>(users[b0 + r]) * rank + j];
-          if (i0 + r < ni) yv = y[static_cast<size_t>(s) * ys + static_cast<size_t>(i0 + r) * rank + j];
-        }
-        xt[kk][r] = xv;
-        yt[kk][r] = yv;
-      }
-      __syncthreads();
-      for (int kk = 0; kk < kc; ++kk) {
-        double xa[kRecTm], yc[kRecTm];
-#pragma unroll
-        for (int a = 0; a < kRecTm; ++a) xa[a] = xt[kk][ty * kRecTm + a];
-#pragma unroll
-        for (int c = 0; c < kRecTm; ++c) yc[c] = yt[kk][tx + 16 * c];
-#pragma unroll
-        for (int a = 0; a < kRecTm; ++a)
-#pragma unroll
-          for (int c = 0; c < kRecTm; ++c) acc[a][c] = fma(xa[a], yc[c], acc[a][c]);
-      }
-      __syncthreads();
-    }
+    rec_tile_acc(x, xs, y, ys, users, nb, ni, rank, slots, b0, i0, tx, ty, xt, yt, acc);
     // ---- bit e = a * 8 + c of `todo`: the pairs of this thread still to be judged; lanes outside the request
     // (b >= nb, i >= ni: accumulators of 0.0) are masked by index ----
     uint32_t cols = 0;
@@ -249,7 +172,7 @@ __global__ __launch_bounds__(kBlock) void gtop_fused_kernel(const double *__rest
         for (; rb != 0; rb &= rb - 1) {
           const int c = __ffs(static_cast<int>(rb)) - 1, i = i0 + tx + 16 * c;
           const double sc = gtop_pick(acc[a], c) / n_slots;
-          bool ok = !L.have_thr || gtop_better(sc, gtop_key(u, i), L.thr_s, L.thr_k);
+          bool ok = L.admits(sc, gtop_key(u, i));
           if (ok && first && seen_off) {  // survivors only: binary search in the user's ascending list
             const int end = seen_off[u + 1];
             int p = seen_off[u], q = end;
@@ -289,18 +212,18 @@ __global__ __launch_bounds__(kBlock) void gtop_fused_kernel(const double *__rest
       L.cnt += min(total, room);
       if (total <= room) break;
       __syncthreads();
-      gtop_sort_cut(L, m);
+      rec_sort_cut<kBlock>(L, m);
       if (L.have_thr) lo = gtop_floor_acc(L.thr_s, n_slots);
     }
     // the threshold as early as m candidates exist: the next tile is filtered against it
     if (!L.have_thr && L.cnt >= m) {
       __syncthreads();
-      gtop_sort_cut(L, m);
+      rec_sort_cut<kBlock>(L, m);
       if (L.have_thr) lo = gtop_floor_acc(L.thr_s, n_slots);
     }
   }
   __syncthreads();
-  gtop_sort_cut(L, m);
+  rec_sort_cut<kBlock>(L, m);
   gtop_write(L, m, blockIdx.x, out_s, out_k, out_n);
 }
 
@@ -314,13 +237,13 @@ __global__ __launch_bounds__(kBlock) void gtop_merge_kernel(const double *__rest
   __shared__ double list_s[kTopCap];
   __shared__ uint64_t list_k[kTopCap];
   __shared__ int wtot[kTopWaves + 1];
-  GtopList L{list_s, list_k, wtot, 0, false, 0.0, 0};
+  GtopList L{list_s, list_k};
   const int l0 = blockIdx.x * fan, nl = min(fan, n_lists - l0);
   const int n_pos = nl * m;  // (<= kTopFan * kTopMaxM)
   for (int base = 0; base < n_pos; base += kBlock) {
     if (L.cnt + kBlock > kTopCap) {  // no room for a whole round
       __syncthreads();
-      gtop_sort_cut(L, m);
+      rec_sort_cut<kBlock>(L, m);
     }
     const int pos = base + static_cast<int>(threadIdx.x);
     bool ok = false;
@@ -332,7 +255,7 @@ __global__ __launch_bounds__(kBlock) void gtop_merge_kernel(const double *__rest
       if (k < in_n[list]) {
         sc = in_s[list * m + k];
         key = in_k[list * m + k];
-        ok = !L.have_thr || gtop_better(sc, key, L.thr_s, L.thr_k);
+        ok = L.admits(sc, key);
       }
     }
     int total;
@@ -345,7 +268,7 @@ __global__ __launch_bounds__(kBlock) void gtop_merge_kernel(const double *__rest
     L.cnt += total;
   }
   __syncthreads();
-  gtop_sort_cut(L, m);
+  rec_sort_cut<kBlock>(L, m);
   gtop_write(L, m, blockIdx.x, out_s, out_k, out_n);
 }
 

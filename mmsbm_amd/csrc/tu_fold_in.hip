@@ -27,19 +27,12 @@ void fold_in(mmsbm_hip_ctx *c, bool items_side, int64_t n_rows, const int32_t *u
   const int32_t *own = items_side ? item : user, *other = items_side ? user : item;
   const int K = items_side ? c->ext_l : c->ext_k, L = items_side ? c->ext_k : c->ext_l;  // (own, fixed) group counts
   const int code = fold_code(K), G = fold_lanes(code);
-  // rows grouped by new user / item ("user" below; counting sort; a user's rows keep the order of the request)
-  std::vector<int64_t> off(static_cast<size_t>(n_new) + 1, 0);
-  for (int64_t m = 0; m < n_rows; ++m) off[static_cast<size_t>(own[m]) + 1]++;
-  for (int32_t u = 0; u < n_new; ++u) off[u + 1] += off[u];
+  // rows grouped by new user / item ("user" below; a user's rows keep the order of the request)
   std::vector<int32_t> it(static_cast<size_t>(n_rows)), rt(static_cast<size_t>(n_rows));
-  {
-    std::vector<int64_t> pos(off.begin(), off.end() - 1);
-    for (int64_t m = 0; m < n_rows; ++m) {
-      const int64_t at = pos[own[m]]++;
-      it[at] = other[m];
-      rt[at] = rating[m];
-    }
-  }
+  const std::vector<int64_t> off = group_by_key<int64_t>(own, n_rows, n_new, [&](int64_t m, int64_t at) {
+    it[at] = other[m];
+    rt[at] = rating[m];
+  });
   const size_t nk = static_cast<size_t>(n_new) * K;
   std::vector<double> th0(nk);
   if (x0) std::copy(x0, x0 + nk, th0.begin());
@@ -75,13 +68,9 @@ void fold_in(mmsbm_hip_ctx *c, bool items_side, int64_t n_rows, const int32_t *u
   jon.alloc(max_jobs); jst.alloc(max_jobs);
   // external (k, l, r) of the slot's p (exchanged for items), the fixed side's external rows: the external items'
   // (internal users when swapped) for users, the external users' (internal items when swapped) for items
-  const int cur = c->cur, sl = c->sel;
-  const int pk = c->swapped ? 1 : c->lp, pl = c->swapped ? c->lp : 1;
-  const int ks = items_side ? pl : pk, ls = items_side ? pk : pl;
-  const size_t prs = static_cast<size_t>(c->kp) * c->lp;
-  const RowTab ut = c->swapped ? plain_tab(c->eta[cur].at(sl), c->lp) : theta_tab(c, cur);
-  const RowTab itab = c->swapped ? theta_tab(c, cur) : plain_tab(c->eta[cur].at(sl), c->lp);
-  const RowTab et = items_side ? ut : itab;
+  const ExtSlot e = ext_slot(c);
+  const int ks = items_side ? e.ls : e.ks, ls = items_side ? e.ks : e.ls;
+  const RowTab et = items_side ? e.users : e.items;
   float total_ms = 0.f;
   EventPair ev;
   for (size_t bi = 0; bi + 1 < cut.size(); ++bi) {
@@ -121,8 +110,8 @@ void fold_in(mmsbm_hip_ctx *c, bool items_side, int64_t n_rows, const int32_t *u
     ev.start(st);
     const size_t ve = static_cast<size_t>(nr) * K;
     if (ve > 0)
-      LAUNCH(fold_v_kernel, static_cast<unsigned>((ve + kBlock - 1) / kBlock), kBlock, 0, st, et, c->p[cur].at(sl),
-             prs, ks, ls, di.ptr, dr.ptr, nr, K, L, dv.ptr);
+      LAUNCH(fold_v_kernel, static_cast<unsigned>((ve + kBlock - 1) / kBlock), kBlock, 0, st, et, e.p, e.rs,
+             ks, ls, di.ptr, dr.ptr, nr, K, L, dv.ptr);
     const unsigned n_on = static_cast<unsigned>(on.size() / gpw), n_st = static_cast<unsigned>(str.size());
     const size_t lds = static_cast<size_t>(lds_max) * sizeof(double);
 #define FOLD_CALL(GG, NT)                                                                                            \

@@ -134,7 +134,7 @@ int likelihood_lanes(mmsbm_hip_ctx *c) {
   double2 *tl = reinterpret_cast<double2 *>(c->lg_theta.ptr), *el = reinterpret_cast<double2 *>(c->lg_eta.ptr);
   double2 *ptl = reinterpret_cast<double2 *>(c->lg_p.ptr);
   if (nt > 0) LAUNCH(theta_log_pairs_kernel, blocks(nt), kBlock, 0, st, theta_tab(c, cur), tl, static_cast<size_t>(c->n_users), c->kp);
-  if (ne > 0) LAUNCH(theta_log_pairs_kernel, blocks(ne), kBlock, 0, st, plain_tab(c->eta[cur].at(sl), c->lp), el, static_cast<size_t>(c->n_items), c->lp);
+  if (ne > 0) LAUNCH(theta_log_pairs_kernel, blocks(ne), kBlock, 0, st, eta_tab(c, cur), el, static_cast<size_t>(c->n_items), c->lp);
   LAUNCH(theta_log_pairs_kernel, blocks(np), kBlock, 0, st, plain_tab(c->pt[cur].at(sl), c->kp), ptl,
          static_cast<size_t>(c->n_ratings) * c->lp, c->kp);   // pT: [R][lp][kp]
   const int nb = c->n_lik_units;
@@ -242,13 +242,13 @@ int score_stats_count() { return kScoreStats; }
 
 // theta0 / eta0 of the selected slot drawn on the device from the restart's PCG64 stream (pcg64.hpp)
 void init_rows_launch(mmsbm_hip_ctx *ctx, const uint64_t pcg64_state[4]) {
-  const int cur = ctx->cur, sl = ctx->sel;
+  const int cur = ctx->cur;
   // the reference draws theta (external users x K) first, then eta; internally the two sides
   // may be swapped, the stream offsets are not
   const uint64_t n_theta_ext = static_cast<uint64_t>(ctx->ext_users) * ctx->ext_k;
   const uint64_t off_users = ctx->swapped ? n_theta_ext : 0;  // internal users' table
   const uint64_t off_items = ctx->swapped ? 0 : n_theta_ext;
-  const RowTab tt = theta_tab(ctx, cur), et = plain_tab(ctx->eta[cur].at(sl), ctx->lp);
+  const RowTab tt = theta_tab(ctx, cur), et = eta_tab(ctx, cur);
   auto blocks = [](uint64_t total) {
     return static_cast<unsigned>((total + uint64_t(kBlock) * kDrawsPerThread - 1) / (uint64_t(kBlock) * kDrawsPerThread));
   };

@@ -45,22 +45,10 @@ void recommend_begin(mmsbm_hip_ctx *c, const double *weights, int exclude_train)
     }
     HIP_CHECK(hipStreamSynchronize(s));
     const std::vector<int32_t> &eu = c->swapped ? oi : ou, &ei = c->swapped ? ou : oi;  // (internal users = external items)
-    const int U = c->ext_users;
-    std::vector<int32_t> off(static_cast<size_t>(U) + 1, 0), item(n);
-    for (size_t m = 0; m < n; ++m) off[static_cast<size_t>(eu[m]) + 1]++;
-    for (int u = 0; u < U; ++u) off[u + 1] += off[u];
-    std::vector<int32_t> pos(off.begin(), off.end() - 1);
-    for (size_t m = 0; m < n; ++m) item[static_cast<size_t>(pos[eu[m]]++)] = ei[m];
-    int32_t w = 0;  // sort + drop duplicate pairs, in place
-    for (int u = 0; u < U; ++u) {
-      const int32_t a = off[u], b = off[u + 1];
-      std::sort(item.begin() + a, item.begin() + b);
-      off[u] = w;
-      for (int32_t e = a; e < b; ++e)
-        if (e == a || item[e] != item[e - 1]) item[w++] = item[e];
-    }
-    off[U] = w;
-    item.resize(static_cast<size_t>(w));
+    std::vector<int32_t> item(n);
+    std::vector<int32_t> off = group_by_key<int32_t>(eu.data(), static_cast<int64_t>(n), c->ext_users,
+                                                     [&](int64_t m, int32_t at) { item[at] = ei[m]; });
+    sort_unique_groups(off, item);  // (duplicate pairs dropped)
     rc->seen_off.upload(off, s);
     rc->seen_off_h = off;  // (candidate counts of recommend_positions)
     rc->seen.upload(item, s);
@@ -80,40 +68,25 @@ void recommend_add(mmsbm_hip_ctx *c) {  // the selected slot (the caller holds a
   const size_t xs = static_cast<size_t>(U) * rank, ys = static_cast<size_t>(I) * rank;
   require_free_mem(((S + 1) * (xs + ys + static_cast<size_t>(K) * L)) * sizeof(double), "recommend: the slots' factors");
   hipStream_t st = c->stream;
-  // grow the two tables by one slot (the earlier slots' factors are kept as they are)
-  const size_t kl = static_cast<size_t>(K) * L;
-  DevBuf<double> nx, ny, nw;  // (W of every slot is kept: recommend_query_theta folds the caller's rows with it)
-  nx.alloc((S + 1) * xs);
-  ny.alloc((S + 1) * ys);
-  nw.alloc((S + 1) * kl);
-  if (S > 0) {
-    HIP_CHECK(hipMemcpyAsync(nx.ptr, rc.x.ptr, sizeof(double) * S * xs, hipMemcpyDeviceToDevice, st));
-    HIP_CHECK(hipMemcpyAsync(ny.ptr, rc.y.ptr, sizeof(double) * S * ys, hipMemcpyDeviceToDevice, st));
-    HIP_CHECK(hipMemcpyAsync(nw.ptr, rc.wk.ptr, sizeof(double) * S * kl, hipMemcpyDeviceToDevice, st));
-  }
-  double *wo = nw.ptr + S * kl;
-  const int cur = c->cur, sl = c->sel;
-  // external (k, l) of the slot's p: internal (k, l), or (l, k) when the context is swapped
-  const int ks = c->swapped ? 1 : c->lp, ls = c->swapped ? c->lp : 1;
-  const size_t rs = static_cast<size_t>(c->kp) * c->lp;
-  LAUNCH(rec_w_kernel, static_cast<unsigned>((K * L + kBlock - 1) / kBlock), kBlock, 0, st, c->p[cur].at(sl),
-         rc.w.ptr, wo, K, L, R, rs, ks, ls);
-  // the caller's users / items: internal users / items, or the other way round when swapped
-  const RowTab th = theta_tab(c, cur), et = plain_tab(c->eta[cur].at(sl), c->lp);
-  const RowTab ut = c->swapped ? et : th, it = c->swapped ? th : et;
+  // the three tables grow by one slot (W of every slot is kept: recommend_query_theta folds the caller's rows with it)
+  DevBuf<double> nx, ny, nw;
+  double *xo = grow_by_slot(rc.x, xs, S, st, nx), *yo = grow_by_slot(rc.y, ys, S, st, ny);
+  double *wo = grow_by_slot(rc.wk, static_cast<size_t>(K) * L, S, st, nw);
+  const ExtSlot e = ext_slot(c);
+  LAUNCH(rec_w_kernel, static_cast<unsigned>((K * L + kBlock - 1) / kBlock), kBlock, 0, st, e.p, rc.w.ptr, wo, K, L, R,
+         e.rs, e.ks, e.ls);
   auto fold = [&](const RowTab &src, int d, const double *m, int mt, int mj, double *out, int rows) {
-    const size_t e = static_cast<size_t>(rows) * rank;
-    if (e == 0) return;
-    LAUNCH(rec_fold_kernel, static_cast<unsigned>((e + kBlock - 1) / kBlock), kBlock, 0, st, src, d, m, mt, mj, out,
+    const size_t n = static_cast<size_t>(rows) * rank;
+    if (n == 0) return;
+    LAUNCH(rec_fold_kernel, static_cast<unsigned>((n + kBlock - 1) / kBlock), kBlock, 0, st, src, d, m, mt, mj, out,
            rows, rank);
   };
-  double *xo = nx.ptr + S * xs, *yo = ny.ptr + S * ys;
   if (K <= L) {  // x = theta, y = eta W^T: y[i, k] = sum_l eta[i, l] W[k, l]
-    fold(ut, K, nullptr, 0, 0, xo, U);
-    fold(it, L, wo, 1, L, yo, I);
+    fold(e.users, K, nullptr, 0, 0, xo, U);
+    fold(e.items, L, wo, 1, L, yo, I);
   } else {       // x = theta W: x[u, l] = sum_k theta[u, k] W[k, l], y = eta
-    fold(ut, K, wo, L, 1, xo, U);
-    fold(it, L, nullptr, 0, 0, yo, I);
+    fold(e.users, K, wo, L, 1, xo, U);
+    fold(e.items, L, nullptr, 0, 0, yo, I);
   }
   HIP_CHECK(hipGetLastError());
   HIP_CHECK(hipStreamSynchronize(st));
@@ -158,25 +131,18 @@ void recommend_add_items(mmsbm_hip_ctx *c, int32_t n_new, const double *eta, con
     std::vector<int32_t> old(static_cast<size_t>(old_off[U]));
     if (!old.empty())
       HIP_CHECK(hipMemcpyAsync(old.data(), rc.seen.ptr, sizeof(int32_t) * old.size(), hipMemcpyDeviceToHost, st));
-    // the new pairs grouped by user (counting sort)
-    std::vector<int32_t> noff(static_cast<size_t>(U) + 1, 0), nit(static_cast<size_t>(n_seen));
-    for (int64_t e = 0; e < n_seen; ++e) noff[static_cast<size_t>(seen_users[e]) + 1]++;
-    for (int u = 0; u < U; ++u) noff[u + 1] += noff[u];
-    {
-      std::vector<int32_t> pos(noff.begin(), noff.end() - 1);
-      for (int32_t j = 0; j < n_new; ++j)
-        for (int64_t e = seen_offsets[j]; e < seen_offsets[j + 1]; ++e) nit[static_cast<size_t>(pos[seen_users[e]]++)] = I + j;
-    }
+    // the new pairs (user seen_users[e], item I + j for e in item j's range) grouped by user
+    std::vector<int32_t> pit(static_cast<size_t>(n_seen)), nit(static_cast<size_t>(n_seen));
+    for (int32_t j = 0; j < n_new; ++j) std::fill(pit.begin() + seen_offsets[j], pit.begin() + seen_offsets[j + 1], I + j);
+    std::vector<int32_t> noff = group_by_key<int32_t>(seen_users, n_seen, U, [&](int64_t e, int32_t at) { nit[at] = pit[e]; });
+    sort_unique_groups(noff, nit);
     HIP_CHECK(hipStreamSynchronize(st));
     std::vector<int32_t> off(static_cast<size_t>(U) + 1, 0), item;
     item.reserve(old.size() + static_cast<size_t>(n_seen));
     for (int u = 0; u < U; ++u) {
       off[u] = static_cast<int32_t>(item.size());
       item.insert(item.end(), old.begin() + old_off[u], old.begin() + old_off[u + 1]);
-      const size_t a = item.size();
       item.insert(item.end(), nit.begin() + noff[u], nit.begin() + noff[u + 1]);
-      std::sort(item.begin() + a, item.end());
-      item.erase(std::unique(item.begin() + a, item.end()), item.end());
     }
     off[U] = static_cast<int32_t>(item.size());
     so.upload(off, st);
@@ -500,28 +466,16 @@ void similar_add(mmsbm_hip_ctx *c) {  // the selected slot (the caller holds a O
   const size_t qs = static_cast<size_t>(rows) * W;
   require_free_mem((S + 1) * (qs + W) * sizeof(double), "similar: the slots' profiles");
   hipStream_t st = c->stream;
-  // grow the two tables by one slot (the earlier slots' profiles are kept as they are)
-  DevBuf<double> nq, nm;
-  nq.alloc((S + 1) * qs);
-  nm.alloc(static_cast<size_t>(S + 1) * W);
-  if (S > 0) {
-    HIP_CHECK(hipMemcpyAsync(nq.ptr, sm.q.ptr, sizeof(double) * S * qs, hipMemcpyDeviceToDevice, st));
-    HIP_CHECK(hipMemcpyAsync(nm.ptr, sm.mf.ptr, sizeof(double) * S * W, hipMemcpyDeviceToDevice, st));
-  }
-  const int cur = c->cur, sl = c->sel;
-  // external (k, l) of the slot's p and the caller's users / items, as recommend_add reads them
-  const int ks = c->swapped ? 1 : c->lp, ls = c->swapped ? c->lp : 1;
-  const size_t rs = static_cast<size_t>(c->kp) * c->lp;
-  const RowTab th = theta_tab(c, cur), et = plain_tab(c->eta[cur].at(sl), c->lp);
-  const RowTab ut = c->swapped ? et : th, it = c->swapped ? th : et;
+  DevBuf<double> nq, nm;  // the two tables grow by one slot
+  double *qo = grow_by_slot(sm.q, qs, S, st, nq), *mo = grow_by_slot(sm.mf, static_cast<size_t>(W), S, st, nm);
+  const ExtSlot e = ext_slot(c);
   // items: profiles over the user groups (g = k) from eta (t = l), masses of theta; users: the other way round
   const bool items = sm.side == 0;
   const int G = items ? c->ext_k : c->ext_l, T = items ? c->ext_l : c->ext_k;
-  LAUNCH(sim_mass_kernel, static_cast<unsigned>(G), kBlock, 0, st, items ? ut : it, sm.others, R,
-         nm.ptr + static_cast<size_t>(S) * W);
+  LAUNCH(sim_mass_kernel, static_cast<unsigned>(G), kBlock, 0, st, items ? e.users : e.items, sm.others, R, mo);
   if (qs > 0)
-    LAUNCH(sim_profile_kernel, static_cast<unsigned>((qs + kBlock - 1) / kBlock), kBlock, 0, st, items ? it : ut, T,
-           c->p[cur].at(sl), rs, items ? ks : ls, items ? ls : ks, nq.ptr + S * qs, rows, G, R);
+    LAUNCH(sim_profile_kernel, static_cast<unsigned>((qs + kBlock - 1) / kBlock), kBlock, 0, st,
+           items ? e.items : e.users, T, e.p, e.rs, items ? e.ks : e.ls, items ? e.ls : e.ks, qo, rows, G, R);
   HIP_CHECK(hipGetLastError());
   HIP_CHECK(hipStreamSynchronize(st));
   sm.q.swap(nq);
