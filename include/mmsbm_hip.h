@@ -264,6 +264,44 @@ int mmsbm_hip_similar_query(mmsbm_hip_ctx *ctx, int64_t n_rows, const int32_t *i
                             double *distance, int32_t *counts);
 int mmsbm_hip_similar_end(mmsbm_hip_ctx *ctx);
 
+/* ---- held-out log-likelihood of every restart slot, and parameter snapshots (mmsbm_amd/csrc/heldout.hpp) ------------ */
+/* For a row m = (u, i, r) (external ids) and the parameters of slot s:
+ *   t_s[k] = sum_l p_s[k, l, r] eta_s[i, l]     one fma chain over l ascending, from +0.0
+ *   P_s(m) = sum_k theta_s[u, k] t_s[k]         one fma chain over k ascending, from +0.0
+ *   ll_s   = sum_m log(max(P_s(m), eps))        eps = DBL_EPSILON, the clamp of mmsbm_hip_likelihood
+ * -- the predictive log-likelihood of rows the fit has not seen, not the omega form of mmsbm_hip_likelihood.  A session
+ * of its own beside the predict, recommend and similar sessions (any of them may be open meanwhile):
+ *   begin  n_rows rows, ids as in create(); the rows are ordered by rating once and stay on the device.  Closes any
+ *          earlier held-out session -- once its own arguments are accepted: a refused begin (an id out of range,
+ *          n_rows >= 2^31) changes nothing and an earlier session stays open.  n_rows == 0 is valid (every ll is 0.0);
+ *   eval   loglik[s] = ll_s of the CURRENT parameters of EVERY slot s < n_slots, in one set of launches (two, whatever
+ *          the number of slots).  Changes nothing: the monitor of a fit, called between two mmsbm_hip_em_iterate;
+ *   add    the SELECTED slot: *loglik = ll_s, and P_s(m) is added to the running per-row sum (in call order);
+ *   mean   over the S adds so far: mean_p[m] = (sum_s P_s(m)) / S -- one division --, n_rows doubles in REQUEST order
+ *          (may be NULL), and *loglik = sum_m log(max(mean_p[m], eps)): the log-likelihood of the ensemble predict uses;
+ *   end    releases the session's device memory (so does mmsbm_hip_destroy).
+ * P_s(m) depends on that row's theta row, eta row and p_r only, bit for bit: not on the other rows, the number of
+ * slots, which slot, the launch shape or the side layout.  The sum over the rows runs in an order fixed by the
+ * session's rows alone (blocks of 256 rows of one rating, a fixed tree inside a block and over the blocks, no atomics):
+ * ll_s is bitwise the same from call to call and from slot count to slot count.
+ * mmsbm_hip_get_option(ctx, "heldout_ms") reads the device time of the last eval or add: HIP events around its two launches,
+ * without the copy of the results.  MMSBM_E_INVALID: no session open, an id or rating out of range, a slot without parameters (eval: any slot; add: the
+ * selected one), mean before any add; n_rows >= 2^31: MMSBM_E_UNSUPPORTED; MMSBM_E_TOOLARGE where the device memory of
+ * the session is not free.  Touches no slot, no EM state and no other session; set_slots keeps the session's rows. */
+int mmsbm_hip_heldout_begin(mmsbm_hip_ctx *ctx, int64_t n_rows, const int32_t *user, const int32_t *item,
+                            const int32_t *rating);
+int mmsbm_hip_heldout_eval(mmsbm_hip_ctx *ctx, double *loglik);
+int mmsbm_hip_heldout_add(mmsbm_hip_ctx *ctx, double *loglik);
+int mmsbm_hip_heldout_mean(mmsbm_hip_ctx *ctx, double *mean_p, double *loglik);
+int mmsbm_hip_heldout_end(mmsbm_hip_ctx *ctx);
+/* A slot's best parameters so far, kept on the device: save copies the SELECTED slot's current theta, eta and p into
+ * that slot's snapshot (device to device, enqueued on the context's stream, no wait; a later save replaces it); get
+ * returns the selected slot's snapshot as mmsbm_hip_get_params returns parameters (any output may be NULL).  The first
+ * save allocates room for every slot (MMSBM_E_TOOLARGE where it is not free); set_slots drops all snapshots.
+ * MMSBM_E_INVALID: save on a slot without parameters, get with nothing saved for the selected slot. */
+int mmsbm_hip_snapshot_save(mmsbm_hip_ctx *ctx);
+int mmsbm_hip_snapshot_get(mmsbm_hip_ctx *ctx, double *theta, double *eta, double *pr);
+
 /* ---- fold-in: theta of new users under the fitted eta and p (mmsbm_amd/csrc/fold_in.hpp) ----------------------- */
 /* The SELECTED slot's eta and p stay fixed; for new users 0 .. n_new-1, given their rows (user in [0, n_new), item in
  * [0, I), rating in [0, R), external ids), n_iters times

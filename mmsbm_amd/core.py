@@ -126,6 +126,7 @@ class HipEM:
         self.n_pairs, self.swapped = int(dims[6]), bool(dims[7])
         self.slots = 1
         self._rc_added = 0
+        self._ho_rows = 0
         if int(slots) != 1:
             self.set_slots(slots)
 
@@ -434,6 +435,46 @@ class HipEM:
 
     def similar_end(self):
         _lib.call("mmsbm_hip_similar_end", self._h)
+
+    # -- held-out log-likelihood and snapshots on the device (include/mmsbm_hip.h: mmsbm_hip_heldout_*) ----
+    def heldout_begin(self, rows):
+        """Open a held-out session over (M,3) triples [user, item, observed rating index] (encoded ids)."""
+        u, i, r = split_triples(rows)
+        _lib.call("mmsbm_hip_heldout_begin", self._h, len(u), _p(u, C.c_int32), _p(i, C.c_int32), _p(r, C.c_int32))
+        self._ho_rows = len(u)   # (only now: a refused begin leaves an earlier session, and its row count, as they are)
+
+    def heldout_eval(self):
+        """(slots,) sum over the rows of log P(observed rating | user, item) under EVERY slot's current parameters,
+        in one set of launches; changes nothing."""
+        out = np.zeros(self.slots, dtype=np.float64)
+        _lib.call("mmsbm_hip_heldout_eval", self._h, _p(out, C.c_double))
+        return out
+
+    def heldout_add(self):
+        """The selected slot's held-out log-likelihood; its row probabilities join the session's running sum."""
+        out = C.c_double(0.0)
+        _lib.call("mmsbm_hip_heldout_add", self._h, C.byref(out))
+        return np.float64(out.value)
+
+    def heldout_mean(self, want_rows=True):
+        """(mean row probability over the slots added (M,) in request order or None, its log-likelihood)."""
+        out = C.c_double(0.0)
+        mean = np.empty(self._ho_rows, dtype=np.float64) if want_rows else None
+        _lib.call("mmsbm_hip_heldout_mean", self._h, _p(mean, C.c_double) if want_rows else None, C.byref(out))
+        return mean, np.float64(out.value)
+
+    def heldout_end(self):
+        _lib.call("mmsbm_hip_heldout_end", self._h)
+
+    def snapshot_save(self):
+        """Keep the selected slot's current parameters on the device (replaces that slot's earlier snapshot)."""
+        _lib.call("mmsbm_hip_snapshot_save", self._h)
+
+    def snapshot_get(self):
+        """(theta, eta, pr) of the selected slot's snapshot."""
+        theta, eta, pr = (np.empty(s, dtype=np.float64) for s in self._shapes())
+        _lib.call("mmsbm_hip_snapshot_get", self._h, _p(theta, C.c_double), _p(eta, C.c_double), _p(pr, C.c_double))
+        return theta, eta, pr
 
     # -- fold-in of new users (include/mmsbm_hip.h: mmsbm_hip_fold_in) ---------------------------------
     MAX_FOLD_IN_K = 1024

@@ -151,6 +151,20 @@ struct SimSession {
   int width = 0;                        // profile entries per row: K R, or L R
 };
 
+// The held-out session (mmsbm_hip_heldout_begin .. end; heldout.hpp): the request's rows rating-major, cut into blocks
+// of one rating, and the running per-row sum of the slots added.  Created by heldout_begin, dropped whole by
+// heldout_begin and heldout_end; set_slots leaves it alone (it holds rows, no parameters).
+struct HoldSession {
+  DevBuf<int32_t> user, item, orig;     // external ids in session order, and each row's place in the request
+  DevBuf<int4> blocks;                  // (rating, first row, rows, 0)
+  DevBuf<double> sum;                   // [rows], request order: P added by every heldout_add
+  DevBuf<double> part, out, mean;       // [slots][blocks] block sums, [slots] results, [rows] of heldout_mean
+  int64_t rows = 0;
+  int n_blocks = 0;
+  int part_slots = 0;                   // slots `part` and `out` are sized for
+  int added = 0;                        // heldout_add calls so far
+};
+
 }  // namespace mmsbm_hip_impl
 
 namespace {
@@ -294,6 +308,13 @@ struct mmsbm_hip_ctx {
   int top_groups = 0;                       // option "top_pairs_groups": workgroups of gtop_fused_kernel (0: 2 per CU)
   std::unique_ptr<mmsbm_hip_impl::SimSession> sm;  // the open similarity session; null: none
   float sim_last_ms = 0.f;                  // device time of the last similar_query's kernels (option "similar_ms")
+  std::unique_ptr<mmsbm_hip_impl::HoldSession> ho;  // the open held-out session; null: none
+  float hold_last_ms = 0.f;                 // device time of the last heldout_eval / heldout_add (option "heldout_ms")
+  // snapshots (mmsbm_hip_snapshot_save / get): a second copy of theta, eta and p in the layout of theta[cur], eta[cur]
+  // and p[cur], every slot's place in it filled by that slot's last save; allocated by the first save, dropped by set_slots
+  DevBuf<double> snap_theta;
+  SlotBuf snap_eta, snap_p;
+  std::vector<char> snap_have;              // per slot: a snapshot has been saved
   int cur = 0;
   std::vector<char> have;  // per slot: set_params has been called
   bool graph_mode = false;  // replay a captured two-iteration hipGraph instead of eager launches
@@ -307,6 +328,12 @@ struct mmsbm_hip_ctx {
       if (g) (void)hipGraphExecDestroy(g);
       g = nullptr;
     }
+  }
+  void drop_snapshots() {
+    snap_theta.release();
+    snap_eta.release();
+    snap_p.release();
+    snap_have.clear();
   }
   ~mmsbm_hip_ctx() {
     drop_graphs();

@@ -65,6 +65,13 @@ void fold_in(mmsbm_hip_ctx *c, bool items_side, int64_t n_rows, const int32_t *u
              const int32_t *rating, int32_t n_new, int32_t n_iters, double tol, const double *x0, double *x,
              int32_t *iters);
 
+// tu_heldout.hip -- held-out log-likelihood (heldout.hpp): the session of mmsbm_hip_heldout_*, arguments checked
+void heldout_begin(mmsbm_hip_ctx *c, int64_t n_rows, const int32_t *user, const int32_t *item, const int32_t *rating);
+// the slots [first, first + n_slots): loglik[s] of each; add: also P into the running per-row sum (one slot)
+void heldout_eval(mmsbm_hip_ctx *c, int first, int n_slots, bool add, double *loglik);
+void heldout_mean(mmsbm_hip_ctx *c, double *mean_p, double *loglik);
+void heldout_end(mmsbm_hip_ctx *c);
+
 // dispatchers (mmsbm_hip.hip): the form the context's shape and options select
 void stage_dense(mmsbm_hip_ctx *c);
 void stage_matvec_a(mmsbm_hip_ctx *c, int slot, int a_slot, bool grid = false);
@@ -162,6 +169,14 @@ struct ExtSlot {
 inline ExtSlot ext_slot(const mmsbm_hip_ctx *c) {
   const RowTab th = theta_tab(c, c->cur), et = eta_tab(c, c->cur);
   return ExtSlot{c->p[c->cur].at(c->sel), static_cast<size_t>(c->kp) * c->lp, c->swapped ? 1 : c->lp,
+                 c->swapped ? c->lp : 1, c->swapped ? et : th, c->swapped ? th : et};
+}
+// ... and those of a given slot, no OneSlot needed, with the distance to the next slot's copy in both tables (RowTab
+// so_m / so_t; p: the SlotBuf's stride) -- a launch that covers several slots steps from this one with slot_tab
+inline ExtSlot ext_slot(const mmsbm_hip_ctx *c, int slot) {
+  const RowTab th = gather_tab(c, c->theta[c->cur].ptr, static_cast<size_t>(c->n_users), slot);
+  const RowTab et = plain_tab(c->eta[c->cur].at(slot), c->lp, c->eta[c->cur].stride);
+  return ExtSlot{c->p[c->cur].at(slot), static_cast<size_t>(c->kp) * c->lp, c->swapped ? 1 : c->lp,
                  c->swapped ? c->lp : 1, c->swapped ? et : th, c->swapped ? th : et};
 }
 

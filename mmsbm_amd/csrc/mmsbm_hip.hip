@@ -1032,6 +1032,8 @@ int mmsbm_hip_set_slots(mmsbm_hip_ctx *ctx, int n_slots) {
     if (!ctx) throw std::invalid_argument("null context");
     if (n_slots < 1 || n_slots > 65535) throw std::invalid_argument("n_slots must be in [1, 65535]");
     use_device(ctx);
+    HIP_CHECK(hipStreamSynchronize(ctx->stream));  // (a snapshot copy may still be on its way)
+    ctx->drop_snapshots();
     if (n_slots == ctx->n_slots) {
       ctx->have.assign(static_cast<size_t>(n_slots), 0);
       ctx->a_ok.assign(static_cast<size_t>(n_slots), 0);
@@ -1580,6 +1582,115 @@ int mmsbm_hip_similar_end(mmsbm_hip_ctx *ctx) {
   });
 }
 
+int mmsbm_hip_heldout_begin(mmsbm_hip_ctx *ctx, int64_t n_rows, const int32_t *user, const int32_t *item,
+                            const int32_t *rating) {
+  return guarded([&] {
+    if (!ctx) throw std::invalid_argument("null context");
+    if (n_rows < 0) throw std::invalid_argument("heldout: negative n_rows");
+    if (n_rows > INT32_MAX) throw ApiError(MMSBM_E_UNSUPPORTED, "heldout: n_rows must be below 2^31");
+    if (n_rows > 0 && (!user || !item || !rating)) throw std::invalid_argument("null argument");
+    for (int64_t m = 0; m < n_rows; ++m)
+      if (user[m] < 0 || user[m] >= ctx->ext_users || item[m] < 0 || item[m] >= ctx->ext_items || rating[m] < 0 ||
+          rating[m] >= ctx->n_ratings)
+        throw std::invalid_argument("heldout: id out of range at row " + std::to_string(m));
+    heldout_begin(ctx, n_rows, user, item, rating);
+  });
+}
+
+int mmsbm_hip_heldout_eval(mmsbm_hip_ctx *ctx, double *loglik) {
+  return guarded([&] {
+    require_all_params(ctx);
+    if (!loglik) throw std::invalid_argument("null loglik");
+    if (!ctx->ho) throw std::invalid_argument("heldout_begin has not been called");
+    heldout_eval(ctx, 0, ctx->n_slots, false, loglik);
+  });
+}
+
+int mmsbm_hip_heldout_add(mmsbm_hip_ctx *ctx, double *loglik) {
+  return guarded([&] {
+    require_params(ctx);
+    if (!loglik) throw std::invalid_argument("null loglik");
+    if (!ctx->ho) throw std::invalid_argument("heldout_begin has not been called");
+    heldout_eval(ctx, ctx->sel, 1, true, loglik);
+  });
+}
+
+int mmsbm_hip_heldout_mean(mmsbm_hip_ctx *ctx, double *mean_p, double *loglik) {
+  return guarded([&] {
+    if (!ctx || !loglik) throw std::invalid_argument("null argument");
+    if (!ctx->ho) throw std::invalid_argument("heldout_begin has not been called");
+    if (ctx->ho->added < 1) throw std::invalid_argument("heldout_mean before any heldout_add");
+    heldout_mean(ctx, mean_p, loglik);
+  });
+}
+
+int mmsbm_hip_heldout_end(mmsbm_hip_ctx *ctx) {
+  return guarded([&] {
+    if (!ctx) throw std::invalid_argument("null context");
+    if (!ctx->ho) throw std::invalid_argument("heldout_begin has not been called");
+    use_device(ctx);
+    HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    heldout_end(ctx);
+  });
+}
+
+namespace {
+// the snapshot tables as theta_tab / eta_tab see the parameters of slot `slot`
+RowTab snap_theta_tab(const mmsbm_hip_ctx *c, int slot) {
+  return gather_tab(c, c->snap_theta.ptr, static_cast<size_t>(c->n_users), slot);
+}
+}  // namespace
+
+int mmsbm_hip_snapshot_save(mmsbm_hip_ctx *ctx) {
+  return guarded([&] {
+    require_params(ctx);
+    use_device(ctx);
+    mmsbm_hip_ctx *c = ctx;
+    const int cur = c->cur, sl = c->sel;
+    const size_t klr = static_cast<size_t>(c->n_ratings) * c->kp * c->lp;
+    if (c->snap_have.empty()) {
+      const size_t doubles = c->theta[cur].count + c->eta[cur].count + c->p[cur].count;
+      require_free_mem(doubles * sizeof(double), "snapshot: a copy of every slot's parameters");
+      try {
+        c->snap_theta.alloc(c->theta[cur].count);
+        c->snap_eta.alloc_slots(static_cast<size_t>(c->n_items) * c->lp, c->n_slots);
+        c->snap_p.alloc_slots(klr, c->n_slots);
+      } catch (...) {
+        c->drop_snapshots();
+        throw;
+      }
+      c->snap_have.assign(static_cast<size_t>(c->n_slots), 0);
+    }
+    hipStream_t s = c->stream;
+    const size_t e = sizeof(double);
+    const RowTab src = gather_tab(c, c->theta[cur].ptr, static_cast<size_t>(c->n_users), sl), dst = snap_theta_tab(c, sl);
+    if (c->n_users > 0) {  // the slot's columns of the interleaved rows: main parts, then tail parts
+      HIP_CHECK(hipMemcpy2DAsync(dst.main, e * dst.rs_m, src.main, e * src.rs_m, e * src.mw, c->n_users,
+                                 hipMemcpyDeviceToDevice, s));
+      if (src.tw > 0)
+        HIP_CHECK(hipMemcpy2DAsync(dst.tail, e * dst.rs_t, src.tail, e * src.rs_t, e * src.tw, c->n_users,
+                                   hipMemcpyDeviceToDevice, s));
+    }
+    HIP_CHECK(hipMemcpyAsync(c->snap_eta.at(sl), c->eta[cur].at(sl), e * static_cast<size_t>(c->n_items) * c->lp,
+                             hipMemcpyDeviceToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(c->snap_p.at(sl), c->p[cur].at(sl), e * klr, hipMemcpyDeviceToDevice, s));
+    c->snap_have[sl] = 1;
+  });
+}
+
+int mmsbm_hip_snapshot_get(mmsbm_hip_ctx *ctx, double *theta, double *eta, double *pr) {
+  return guarded([&] {
+    if (!ctx) throw std::invalid_argument("null context");
+    if (ctx->snap_have.empty() || !ctx->snap_have[ctx->sel])
+      throw std::invalid_argument("snapshot_get: nothing saved for the selected slot");
+    use_device(ctx);
+    double *it = ctx->swapped ? eta : theta;
+    double *ie = ctx->swapped ? theta : eta;
+    const int sl = ctx->sel;
+    fetch_params(ctx, snap_theta_tab(ctx, sl), plain_tab(ctx->snap_eta.at(sl), ctx->lp), ctx->snap_p.at(sl), it, ie, pr);
+  });
+}
+
 int mmsbm_hip_fold_in(mmsbm_hip_ctx *ctx, int64_t n_rows, const int32_t *user, const int32_t *item,
                       const int32_t *rating, int32_t n_new, int32_t n_iters, double tol,
                       const double *theta0, double *theta, int32_t *iters) {
@@ -1777,6 +1888,7 @@ int mmsbm_hip_get_option(const mmsbm_hip_ctx *ctx, const char *name, double *val
     else if (key == "position_ms") *value = ctx->pos_last_ms;  // read-only: device time of the last recommend_positions
     else if (key == "similar_ms") *value = ctx->sim_last_ms;   // read-only: device time of the last similar_query
     else if (key == "top_pairs_ms") *value = ctx->top_last_ms; // read-only: device time of the last recommend_top_pairs
+    else if (key == "heldout_ms") *value = ctx->hold_last_ms;  // read-only: device time of the last heldout_eval / heldout_add
     else if (key == "top_pairs_groups") *value = ctx->top_groups;
     else if (key == "launches") *value = use_fused(ctx) ? 2 : 4;  // read-only: launches per iteration at the current slot count
     else if (key == "wide") *value = ctx->wide;

@@ -12,6 +12,7 @@
 //   tu_layout.hip  the layout's sorts on the device (rocPRIM)
 //   tu_recommend.hip  top-N recommendation (recommend.hpp), nearest items / users (similar.hpp) and the m best pairs (top_pairs.hpp)
 //   tu_fold_in.hip    fold new users into a fitted model (fold_in.hpp)
+//   tu_heldout.hip    held-out log-likelihood of every restart slot (heldout.hpp)
 // unity.hip includes them all into ONE unit: the diagnostic builds (-DMMSBM_STAMPS, -DMMSBM_ABLATE) and
 // scripts/kernel_resources.sh use it.
 #pragma once

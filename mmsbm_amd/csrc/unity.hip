@@ -15,3 +15,4 @@
 #include "tu_layout.hip"
 #include "tu_recommend.hip"
 #include "tu_fold_in.hip"
+#include "tu_heldout.hip"

@@ -64,6 +64,11 @@ class MMSBM:
         self.tol = tol
         self.check_every = max(1, int(check_every))
         self.iterations_run = {}
+        # Validation monitor (fit(..., validation=...)): per restart the held-out log-likelihood at every check as
+        # [(iterations done, value), ...] and the iteration count of its best check, whose parameters `results` holds
+        self.validation_curve = {}
+        self.best_iteration = {}
+        self._monitor = None     # (encoded validation rows, patience) while a monitored fit runs
         # src/mmsbm.py:81-85
         self.rng = np.random.default_rng(seed)
         self.child_states = self.rng.bit_generator._seed_seq.spawn(sampling)
@@ -116,16 +121,60 @@ class MMSBM:
         self._resident = {}
 
     # ------------------------------------------------------------------ training
-    def fit(self, data, silent=False):
+    def fit(self, data, silent=False, validation=None, patience=None):
+        """``validation``: rows the fit does not train on (same columns as ``data``; users, items and ratings unseen in
+        ``data`` are dropped with ``predict``'s warning).  Every ``check_every`` iterations, and after the last one,
+        the held-out log-likelihood sum log P(observed rating | user, item) of every restart is evaluated on the
+        device; a restart's parameters at its best check (the first one with the highest value) are kept there and are
+        what ``results`` holds -- with ``"likelihood"`` the training likelihood of exactly those parameters and
+        ``"validation"`` the value at that check.  ``validation_curve[i]`` and ``best_iteration[i]`` record restart
+        i's checks.  ``patience=p`` stops a batch of restarts after a check at which each of them has had p
+        consecutive checks without a new best; None runs all iterations."""
+        self._check_monitor_args(validation, patience)
         if not silent:
             self.logger.info(f"Running {self.sampling} runs of {self.iterations} iterations.")
-        self.data_handler = Encoder()
-        train = self.data_handler.fit_transform(data)
-        self.fit_encoded(train)
+        encoder = Encoder()
+        train = encoder.fit_transform(data)
+        if validation is not None:
+            validation = encoder.transform(validation, self.logger)
+            if len(validation) == 0:
+                raise ValueError(self._NO_VALIDATION_ROW)
+        self.data_handler = encoder   # (only now: a refused fit leaves a fitted model, its encoder included, as it was)
+        self.fit_encoded(train, validation=validation, patience=patience)
 
-    def fit_encoded(self, train, restarts=None):
+    _NO_VALIDATION_ROW = ("the validation set has no row left after encoding: every row names a user, an item or a "
+                          "rating that is not in the training data")
+
+    def _check_monitor_args(self, validation, patience):
+        """The refusals of a monitored fit that need no data (before anything is encoded or sent to a device)."""
+        if patience is not None:
+            if isinstance(patience, (bool, np.bool_)) or not isinstance(patience, (int, np.integer)) or patience < 1:
+                raise ValueError(f"patience must be a positive integer, got {patience!r}")
+            if validation is None:
+                raise ValueError("patience needs a validation set: it counts checks without a new best on it")
+        if validation is not None and self.tol is not None:
+            raise ValueError("validation and tol are two stop rules with no defined way to combine them: "
+                             "construct the model with tol=None to monitor a validation set")
+
+    def fit_encoded(self, train, restarts=None, validation=None, patience=None):
         """fit() on already encoded (N,3) triples.  ``restarts``: subset of restart indices to
-        run here (used by the multi-GPU driver); default all."""
+        run here (used by the multi-GPU driver); default all.  ``validation`` / ``patience``: as in ``fit``, encoded
+        (M,3) triples; rows with an id outside the training ones are dropped with a warning."""
+        self._check_monitor_args(validation, patience)
+        if validation is not None:
+            t = np.asarray(train)
+            validation = self._known_rows(validation, int(t[:, 0].max()) + 1, int(t[:, 1].max()) + 1,
+                                          np.flatnonzero(np.bincount(t[:, 2])))
+            if len(validation) == 0:
+                raise ValueError(self._NO_VALIDATION_ROW)
+        self.validation_curve, self.best_iteration = {}, {}
+        self._monitor = None if validation is None else (validation, None if patience is None else int(patience))
+        try:
+            return self._fit_prepared(train, restarts)
+        finally:
+            self._monitor = None
+
+    def _fit_prepared(self, train, restarts):
         self._prepare_objects(train)
         todo = list(range(self.sampling)) if restarts is None else list(restarts)
         # workers = (GPU, context slot); restart j of `todo` goes to worker j mod #workers
@@ -187,6 +236,21 @@ class MMSBM:
                     self.run_samplings(ids[half:], device, slot, seeds[half:]))
         for s, seed in enumerate(seeds):  # theta0, eta0 are drawn on the device (same PCG64 stream)
             ctx.select(s).init_params(seed)
+        if self._monitor is not None:
+            # The snapshot tables -- a further theta + eta + p for every slot, which max_slots() does not count -- are
+            # allocated by the first save: make it now, before any iteration, so that a batch they do not fit beside
+            # is halved like one whose slots do not fit.  (The start it saves is replaced by the first check.)
+            try:
+                ctx.select(0).snapshot_save()
+            except HipLibraryError:
+                if len(ids) == 1:
+                    raise
+                half = len(ids) // 2
+                return (self.run_samplings(ids[:half], device, slot, seeds[:half]) +
+                        self.run_samplings(ids[half:], device, slot, seeds[half:]))
+            out = self._run_monitored(ctx, ids)
+            self._resident[(device, slot)] = ids
+            return out
         done = 0
         if self.debug or self.tol is not None:
             # src/mmsbm.py:252-254 evaluates the likelihood inside the loop when j % 50 == 0, i.e.
@@ -220,6 +284,51 @@ class MMSBM:
             likelihood, theta, eta, pr = ctx.select(s).result()
             out.append({"likelihood": likelihood, "pr": pr, "theta": theta, "eta": eta})
         self._resident[(device, slot)] = ids
+        return out
+
+    def _run_monitored(self, ctx, ids):
+        """The iterations of the restarts in ctx's slots with the validation monitor of ``fit``: a check is ONE
+        heldout_eval for the whole batch; a restart's new best (strictly greater: the first of equal values stays)
+        saves its slot's parameters on the device.  Returns the result dicts of the kept parameters; the slots hold
+        them afterwards."""
+        validation, patience = self._monitor
+        n = len(ids)
+        best, best_it, stale = [None] * n, [0] * n, [0] * n
+        curves = [[] for _ in range(n)]
+        done = 0
+        ctx.heldout_begin(validation)
+        try:
+            while True:
+                step = min(self.check_every, self.iterations - done)
+                if step > 0:
+                    ctx.iterate(step)
+                    done += step
+                values = ctx.heldout_eval()
+                for s in range(n):
+                    v = float(values[s])
+                    curves[s].append((done, v))
+                    if best[s] is None or v > best[s]:
+                        best[s], best_it[s], stale[s] = v, done, 0
+                        ctx.select(s).snapshot_save()
+                    else:
+                        stale[s] += 1
+                if self.debug:
+                    for i, v in zip(ids, values):
+                        self.logger.debug(f"\nHeld-out log-likelihood at run {i} after {done} iterations is {v:.0f}")
+                if done >= self.iterations or (patience is not None and all(c >= patience for c in stale)):
+                    break
+        finally:
+            ctx.heldout_end()
+        out = []
+        for s, i in enumerate(ids):
+            self.iterations_run[i] = done
+            self.validation_curve[i] = curves[s]
+            self.best_iteration[i] = best_it[s]
+            ctx.select(s)
+            if best_it[s] != done:  # the kept parameters go back into the slot (through the host, once per restart)
+                ctx.set_params(*ctx.snapshot_get())
+            likelihood, theta, eta, pr = ctx.result()
+            out.append({"likelihood": likelihood, "pr": pr, "theta": theta, "eta": eta, "validation": best[s]})
         return out
 
     def run_one_sampling(self, data, seed, i, device=0, slot=0):
@@ -470,17 +579,44 @@ class MMSBM:
             ctx.similar_end()
 
     # ------------------------------------------------------------------ ranking evaluation (not in the reference)
+    def log_likelihood(self, data):
+        """The held-out predictive log-likelihood of ``data`` (same columns as the training data), on the device:
+        sum over the rows of log max(P(observed rating | user, item), eps) -- the quantity a probabilistic model is
+        judged by, where ``score()`` reports the accuracy of the argmax.  Rows with a user, item or rating unseen in
+        training are dropped with ``predict``'s warning.
+
+        Returns {"rows": rows scored, "log_likelihood": that of the model's predictive distribution, the mean over the
+        restarts as ``predict`` uses it, "per_restart": [that of each restart alone], "perplexity":
+        exp(-log_likelihood / rows)}.  The model's stored predictions and ``score()`` are left as they are."""
+        self._check_whole_model()
+        rows = self._encode_heldout(data)
+        ctx, restarts = self._restarts()
+        ctx.heldout_begin(rows)
+        try:
+            per_restart = [float(ctx.heldout_add()) for _ in restarts]
+            _, mean = ctx.heldout_mean(want_rows=False)
+        finally:
+            ctx.heldout_end()
+        n, mean = len(rows), float(mean)
+        return {"rows": n, "log_likelihood": mean, "per_restart": per_restart,
+                "perplexity": float(np.exp(-mean / n)) if n else float("nan")}
+
     def _encode_heldout(self, data):
         """Encoded (N, 3) int32 rows of ``data`` in input order, rows with a user, item or rating unseen in training
         dropped with ``Encoder.transform``'s warning (after ``fit_encoded``: ids outside the training ones)."""
         if self.data_handler:
             return self.data_handler.transform(data, self.logger)
+        return self._known_rows(data, self.p + 1, self.m + 1, self.ratings)
+
+    def _known_rows(self, data, n_users, n_items, ratings):
+        """The rows of encoded ``data`` whose ids are training ones (users below n_users, items below n_items, ratings
+        among ``ratings``), (N, 3) int32 in input order; the others are dropped with ``Encoder.transform``'s warning."""
         from .encode import _columns
         cols, _ = _columns(data)
         keep = np.ones(len(cols[0]), dtype=bool)
         ids = []
-        for name, col, known in (("users", cols[0], np.arange(self.p + 1)), ("items", cols[1], np.arange(self.m + 1)),
-                                 ("ratings", cols[2], np.asarray(self.ratings))):
+        for name, col, known in (("users", cols[0], np.arange(n_users)), ("items", cols[1], np.arange(n_items)),
+                                 ("ratings", cols[2], np.asarray(ratings))):
             col = np.asarray(col)
             if len(col) and not np.issubdtype(col.dtype, np.integer):
                 raise ValueError(f"after fit_encoded the {name} column holds encoded integer ids")
