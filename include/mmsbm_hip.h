@@ -111,8 +111,10 @@ int mmsbm_hip_pcg64_doubles(const uint64_t pcg64_state[4], uint64_t offset, int6
  * gather for every restart), every other entry point (set/get_params, update_coefficients, likelihood,
  * compute_omegas, prod_dist) acts on the SELECTED slot.  Slots never interact: slot s holds
  * exactly what a one-slot context given the same parameters would hold, bit for bit.
- * set_slots drops all parameters (set_params must follow for every slot) and selects slot 0;
- * a new context has one slot. */
+ * set_slots drops all parameters (set_params must follow for every slot) and selects slot 0 -- also when n_slots is
+ * the count the context already has; a new context has one slot.  It leaves every open session (predict, recommend,
+ * similar, held-out) as it is: a session holds its own copy of what each add took from a slot, so what was added
+ * stays, and slots given parameters afterwards can be added to the same session. */
 int mmsbm_hip_set_slots(mmsbm_hip_ctx *ctx, int n_slots);
 int mmsbm_hip_select_slot(mmsbm_hip_ctx *ctx, int slot);
 /* Any output may be NULL.  bytes_per_slot: device memory one more slot costs (a failed
@@ -153,7 +155,7 @@ int mmsbm_hip_prod_dist(mmsbm_hip_ctx *ctx, int64_t n_pairs, const int32_t *user
 /* A session over n_rows test triples (ids as in create(); rating = the true rating index;
  * rating_weights: R doubles, the values the reference multiplies the distribution with --
  * its `self.ratings`, src/mmsbm.py:95,518):
- *   begin  uploads the rows;
+ *   begin  uploads the rows; closes any earlier predict session, once its own arguments are accepted;
  *   add    evaluates prod_dist for the SELECTED slot's current parameters, adds it to the
  *          running sum over restarts (in call order, which is numpy's order for
  *          np.array(rats).mean(axis=0)) and returns that restart's indicators;

@@ -132,3 +132,132 @@ class FakeHipEM:
 
     def close(self):
         self.closed = True
+
+
+# ---- every session in one stand-in -------------------------------------------------------------------------------------
+_FULL = []
+
+
+def full_fake():
+    """The stand-in with EVERY session of ``HipEM``: the recommend, positions, top_pairs, fold-in, similar and held-out
+    stand-ins of the ``*_cpu.py`` files (each answered by that file's restatement) in one class, plus the switches and
+    the refusals tests/api_walk.py drives -- a refused call raises ``HipLibraryError`` with ``E_INVALID`` as the library
+    does.  Built on first use: those files import this module."""
+    if _FULL:
+        return _FULL[0]
+    from mmsbm_amd._lib import E_INVALID, HipLibraryError
+    from test_fold_in_items_cpu import ItemsFakeHipEM
+    from test_heldout_cpu import HeldoutFakeHipEM
+    from test_ranking_cpu import RankingFakeHipEM
+    from test_similar_cpu import SimilarFakeHipEM
+    from test_top_pairs_cpu import TopPairsFakeHipEM
+
+    def refuse(func, why):
+        raise HipLibraryError(func, E_INVALID, why)
+
+    class FullFakeHipEM(ItemsFakeHipEM, RankingFakeHipEM, TopPairsFakeHipEM, SimilarFakeHipEM, HeldoutFakeHipEM):
+        _rc = _sm = _ho = None
+
+        def __init__(self, data, k_groups, l_groups, n_users=None, n_items=None, n_ratings=None, device=0,
+                     swap_sides=-1, slots=1):
+            self._options = {"fused": 1.0, "nt_out": 7.0, "top_pairs_groups": 0.0, "graph": 0.0}
+            self.swapped = swap_sides == 1
+            super().__init__(data, k_groups, l_groups, n_users, n_items, n_ratings, device, swap_sides, slots)
+
+        # -- switches: the stand-in has one form of everything
+        def set_option(self, name, value):
+            if name not in self._options:
+                refuse("set_option", f"unknown option: {name}")
+            self._options[name] = float(value)
+
+        def get_option(self, name):
+            if name == "launches":
+                return 2.0 if self._options["fused"] else 4.0
+            if name == "mfma":
+                return float(self.k * self.l > 1024)
+            if name in ("splits_users", "fused_split"):
+                return 2.0
+            return self._options[name]
+
+        def set_graph_mode(self, mode):
+            self._options["graph"] = float(mode)
+
+        # -- refusals
+        def _need_params(self, func, every=False):
+            if any(self._params[s] is None for s in (range(self.slots) if every else [self._sel])):
+                refuse(func, "set_params has not been called")
+
+        def select(self, s):
+            if not 0 <= s < self.slots:
+                refuse("select_slot", f"slot {s} out of range")
+            return super().select(s)
+
+        def iterate(self, n, sync=True):
+            self._need_params("em_iterate", every=True)
+            super().iterate(n, sync)
+
+        def get_params(self):
+            self._need_params("get_params")
+            return super().get_params()
+
+        def recommend_query(self, users, n):
+            if self._rc is None or not self._rc["params"]:
+                refuse("recommend_query", "no session, or no slot added")
+            return super().recommend_query(users, n)
+
+        def recommend_positions(self, users, offsets, items):
+            if self._rc is None or not self._rc["params"]:
+                refuse("recommend_positions", "no session, or no slot added")
+            return super().recommend_positions(users, offsets, items)
+
+        def recommend_top_pairs(self, m, users=None):
+            if self._rc is None or not self._rc["params"]:
+                refuse("recommend_top_pairs", "no session, or no slot added")
+            return super().recommend_top_pairs(m, users)
+
+        def similar_query(self, ids, n):
+            if self._sm is None or not self._sm["params"]:
+                refuse("similar_query", "no session, or no slot added")
+            return super().similar_query(ids, n)
+
+        def heldout_eval(self):
+            self._need_params("heldout_eval", every=True)
+            if self._ho is None:
+                refuse("heldout_eval", "heldout_begin has not been called")
+            return super().heldout_eval()
+
+        def heldout_add(self):
+            self._need_params("heldout_add")
+            if self._ho is None:
+                refuse("heldout_add", "heldout_begin has not been called")
+            return super().heldout_add()
+
+        def heldout_mean(self, want_rows=True):
+            if self._ho is None or not self._ho["added"]:
+                refuse("heldout_mean", "no session, or before any heldout_add")
+            return super().heldout_mean(want_rows)
+
+        def heldout_end(self):
+            if self._ho is None:
+                refuse("heldout_end", "heldout_begin has not been called")
+            super().heldout_end()
+
+        def snapshot_save(self):
+            self._need_params("snapshot_save")
+            super().snapshot_save()
+
+        def snapshot_get(self):
+            if self._snap[self._sel] is None:
+                refuse("snapshot_get", "nothing saved for the selected slot")
+            return super().snapshot_get()
+
+    _FULL.append(FullFakeHipEM)
+    return FullFakeHipEM
+
+
+def full_fake_module(cls=None):
+    """What tests/api_walk.py takes for the ``mmsbm_amd`` module: ``HipEM`` (``cls`` or the full stand-in) and ``_lib``."""
+    import types
+
+    from mmsbm_amd import _lib
+    return types.SimpleNamespace(HipEM=cls or full_fake(), _lib=_lib)

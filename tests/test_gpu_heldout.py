@@ -127,6 +127,39 @@ def test_log_likelihood_within_the_derived_bound(hip, shape):
         assert abs(mean_ll - want["mean_ll"]) <= ll_bound(K, L, want["mean_p"])
 
 
+def test_more_than_256_blocks_take_the_second_trip_of_the_final_sum(hip):
+    """hold_sum_kernel: thread t adds the block sums t, t + 256, ... -- a second trip only beyond 256 blocks, which the
+    2,513 rows above (about 14 blocks) never reach.  70,001 rows at R = 4: every rating's run is longer than a block
+    and there are more than 256 blocks."""
+    shape = SHAPES[SHAPE_IDS.index("four_launch")]
+    name, U, I, R, K, L, fused, swap = shape
+    S, M = 3, 70_001
+    data, params, rows = shape_problem(shape, S, M)
+    runs = np.bincount(rows[:, 2], minlength=R)
+    assert runs.min() > 256 and int(np.ceil(runs / 256).sum()) > 256
+    want = restate_heldout(params, rows)
+    em = shape_context(hip, shape, data, params)
+    try:
+        ev, adds, mean_p, mean_ll = evaluate(em, rows, range(S))
+    finally:
+        em.close()
+    for s in range(S):
+        bound = ll_bound(K, L, want["p"][s])
+        print(f"{name} M={M} slot {s}: |delta| = {abs(ev[s] - want['ll'][s]):.3e}, bound {bound:.3e}")
+        assert abs(ev[s] - want["ll"][s]) <= bound
+        assert bits(adds[s]) == bits(ev[s])
+    assert np.allclose(mean_p, want["mean_p"], rtol=(K * L + 4) * 2.0 ** -52, atol=0)
+    assert abs(mean_ll - want["mean_ll"]) <= ll_bound(K, L, want["mean_p"])
+    for s in range(S):                                     # a parameter set alone in a one-slot context == slot s of 3
+        one = shape_context(hip, shape, data, [params[s]])
+        try:
+            ev1, adds1, p1, ll1 = evaluate(one, rows, [0])
+        finally:
+            one.close()
+        assert bits(ev1[0]) == bits(ev[s]) == bits(adds1[0])
+        assert abs(ll1 - ev1[0]) <= ll_bound(K, L, p1)     # (the mean of one add: the same logs summed in request order)
+
+
 # ---- 3. the clamp ----------------------------------------------------------------------------------------------------
 def test_impossible_ratings_are_clamped_and_their_mean_p_is_zero(hip):
     U, I, K, L, R = 40, 50, 6, 5, 4
