@@ -266,6 +266,31 @@ int mmsbm_hip_similar_query(mmsbm_hip_ctx *ctx, int64_t n_rows, const int32_t *i
                             double *distance, int32_t *counts);
 int mmsbm_hip_similar_end(mmsbm_hip_ctx *ctx);
 
+/* ---- the overlap of the restarts' groups: the Gram matrix of the membership tables (mmsbm_amd/csrc/overlap.hpp) ---- */
+/* A session of its own beside the predict, recommend, similar and held-out sessions (any of them may be open meanwhile):
+ *   begin  side 0: items (eta, G = L groups), 1: users (theta, G = K groups); external sides.  Closes any earlier
+ *          overlap session;
+ *   add    the SELECTED slot's table of that side joins the session as slot s = the number of adds so far, copied in
+ *          external terms (the caller's rows and the caller's group order; the slot itself is left unchanged);
+ *   query  over the S added slots, F = S G: out is F x F doubles, row-major,
+ *          out[(s G + a) F + (t G + b)] = sum_row x_s[row, a] x_t[row, b]
+ *          -- how much of the population group a of slot s and group b of slot t share;
+ *   end    releases the session's device memory (so does mmsbm_hip_destroy).
+ * Operation order: the rows are cut into slabs of a fixed length (2,048); inside a slab an output is one fma chain over
+ * the rows in ascending order from +0.0; the slabs' partial results are combined in a fixed pairwise tree in slab order;
+ * no atomics.  An output depends on its two columns and on the number of rows only, bit for bit: not on S, on the
+ * other slots, on the launch shape, on the side layout or on slots the context holds beyond those added; out[a][b] and
+ * out[b][a] are the same bits.
+ * mmsbm_hip_get_option(ctx, "overlap_ms") reads the device time of the last query's kernels (HIP events).
+ * MMSBM_E_INVALID: side not 0 / 1, add or query without begin, query before the first add, a selected slot without
+ * parameters, out == NULL; MMSBM_E_TOOLARGE where the device memory of the session tables (rows x G doubles per slot),
+ * of the slabs' partial results or of the F x F result is not free.  Touches no slot, no EM state and no other session;
+ * set_slots keeps the session's tables. */
+int mmsbm_hip_overlap_begin(mmsbm_hip_ctx *ctx, int side);
+int mmsbm_hip_overlap_add(mmsbm_hip_ctx *ctx);
+int mmsbm_hip_overlap_query(mmsbm_hip_ctx *ctx, double *out);
+int mmsbm_hip_overlap_end(mmsbm_hip_ctx *ctx);
+
 /* ---- held-out log-likelihood of every restart slot, and parameter snapshots (mmsbm_amd/csrc/heldout.hpp) ------------ */
 /* For a row m = (u, i, r) (external ids) and the parameters of slot s:
  *   t_s[k] = sum_l p_s[k, l, r] eta_s[i, l]     one fma chain over l ascending, from +0.0

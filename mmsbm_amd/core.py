@@ -436,6 +436,31 @@ class HipEM:
     def similar_end(self):
         _lib.call("mmsbm_hip_similar_end", self._h)
 
+    # -- the overlap of the restarts' groups on the device (include/mmsbm_hip.h: mmsbm_hip_overlap_*) ----
+    def overlap_begin(self, side):
+        """Open an overlap session over one side: 0 (or "items") eta's L groups, 1 (or "users") theta's K groups."""
+        side = {"items": 0, "users": 1}.get(side, side)
+        _lib.call("mmsbm_hip_overlap_begin", self._h, int(side))
+        self._ov = [self.l if int(side) == 0 else self.k, 0]   # (groups, slots added)
+
+    def overlap_add(self):
+        """Add the selected slot's membership table of the session's side (the slot is left unchanged)."""
+        _lib.call("mmsbm_hip_overlap_add", self._h)
+        self._ov[1] += 1
+
+    def overlap_query(self):
+        """(F, F) with F = slots added x groups: entry (s G + a, t G + b) is the sum over the rows of
+        x_s[row, a] x_t[row, b]."""
+        groups, slots = getattr(self, "_ov", None) or (0, 0)
+        f = groups * slots
+        out = np.empty((f, f), dtype=np.float64)
+        _lib.call("mmsbm_hip_overlap_query", self._h, _p(out, C.c_double) if f else None)
+        return out
+
+    def overlap_end(self):
+        _lib.call("mmsbm_hip_overlap_end", self._h)
+        self._ov = None
+
     # -- held-out log-likelihood and snapshots on the device (include/mmsbm_hip.h: mmsbm_hip_heldout_*) ----
     def heldout_begin(self, rows):
         """Open a held-out session over (M,3) triples [user, item, observed rating index] (encoded ids)."""

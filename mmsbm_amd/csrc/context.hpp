@@ -151,6 +151,17 @@ struct SimSession {
   int width = 0;                        // profile entries per row: K R, or L R
 };
 
+// The overlap session (mmsbm_hip_overlap_begin .. end; overlap.hpp): the added slots' membership tables of one external
+// side.  Created by overlap_begin, dropped whole by overlap_begin and overlap_end; set_slots leaves it alone (it holds
+// copies of the rows, nothing of a slot).
+struct OvlSession {
+  DevBuf<double> x;                     // [slot][rows][groups]
+  int side = 0;                         // 0: items (eta, L groups), 1: users (theta, K groups); external sides
+  int slots = 0;                        // slots added
+  int rows = 0;                         // rows of the side: I, or U
+  int groups = 0;                       // G: L, or K
+};
+
 // The held-out session (mmsbm_hip_heldout_begin .. end; heldout.hpp): the request's rows rating-major, cut into blocks
 // of one rating, and the running per-row sum of the slots added.  Created by heldout_begin, dropped whole by
 // heldout_begin and heldout_end; set_slots leaves it alone (it holds rows, no parameters).
@@ -308,6 +319,8 @@ struct mmsbm_hip_ctx {
   int top_groups = 0;                       // option "top_pairs_groups": workgroups of gtop_fused_kernel (0: 2 per CU)
   std::unique_ptr<mmsbm_hip_impl::SimSession> sm;  // the open similarity session; null: none
   float sim_last_ms = 0.f;                  // device time of the last similar_query's kernels (option "similar_ms")
+  std::unique_ptr<mmsbm_hip_impl::OvlSession> ov;  // the open overlap session; null: none
+  float ovl_last_ms = 0.f;                  // device time of the last overlap_query's kernels (option "overlap_ms")
   std::unique_ptr<mmsbm_hip_impl::HoldSession> ho;  // the open held-out session; null: none
   float hold_last_ms = 0.f;                 // device time of the last heldout_eval / heldout_add (option "heldout_ms")
   // snapshots (mmsbm_hip_snapshot_save / get): a second copy of theta, eta and p in the layout of theta[cur], eta[cur]

@@ -58,6 +58,11 @@ void similar_add(mmsbm_hip_ctx *c);  // the selected slot (the caller holds a On
 void similar_query(mmsbm_hip_ctx *c, int64_t n_rows, const int32_t *ids, int n, int32_t *out_ids, double *distance,
                    int32_t *counts);
 void similar_end(mmsbm_hip_ctx *c);
+// ... and the overlap of the restarts' groups (overlap.hpp): the session of mmsbm_hip_overlap_*, arguments checked
+void overlap_begin(mmsbm_hip_ctx *c, int side);
+void overlap_add(mmsbm_hip_ctx *c);  // the selected slot (the caller holds a OneSlot)
+void overlap_query(mmsbm_hip_ctx *c, double *out);
+void overlap_end(mmsbm_hip_ctx *c);
 
 // tu_fold_in.hip -- fold new users (items_side: new items) into the selected slot's fitted eta (theta) and p
 // (fold_in.hpp), arguments checked; x0, x: theta0, theta (eta0, eta); items_side: item[m] in [0, n_new), user[m] in [0, U)

@@ -1582,6 +1582,43 @@ int mmsbm_hip_similar_end(mmsbm_hip_ctx *ctx) {
   });
 }
 
+int mmsbm_hip_overlap_begin(mmsbm_hip_ctx *ctx, int side) {
+  return guarded([&] {
+    if (!ctx) throw std::invalid_argument("null context");
+    if (side != 0 && side != 1) throw std::invalid_argument("overlap: side must be 0 (items) or 1 (users)");
+    overlap_begin(ctx, side);
+  });
+}
+
+int mmsbm_hip_overlap_add(mmsbm_hip_ctx *ctx) {
+  return guarded([&] {
+    if (!ctx) throw std::invalid_argument("null context");
+    if (!ctx->ov) throw std::invalid_argument("overlap_begin has not been called");
+    require_params(ctx);
+    OneSlot one(ctx);
+    overlap_add(ctx);
+  });
+}
+
+int mmsbm_hip_overlap_query(mmsbm_hip_ctx *ctx, double *out) {
+  return guarded([&] {
+    if (!ctx) throw std::invalid_argument("null context");
+    if (!ctx->ov) throw std::invalid_argument("overlap_begin has not been called");
+    if (ctx->ov->slots == 0) throw std::invalid_argument("overlap_query before any overlap_add");
+    if (!out) throw std::invalid_argument("null out");
+    overlap_query(ctx, out);
+  });
+}
+
+int mmsbm_hip_overlap_end(mmsbm_hip_ctx *ctx) {
+  return guarded([&] {
+    if (!ctx) throw std::invalid_argument("null context");
+    use_device(ctx);
+    HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    overlap_end(ctx);
+  });
+}
+
 int mmsbm_hip_heldout_begin(mmsbm_hip_ctx *ctx, int64_t n_rows, const int32_t *user, const int32_t *item,
                             const int32_t *rating) {
   return guarded([&] {
@@ -1888,6 +1925,7 @@ int mmsbm_hip_get_option(const mmsbm_hip_ctx *ctx, const char *name, double *val
     else if (key == "position_ms") *value = ctx->pos_last_ms;  // read-only: device time of the last recommend_positions
     else if (key == "similar_ms") *value = ctx->sim_last_ms;   // read-only: device time of the last similar_query
     else if (key == "top_pairs_ms") *value = ctx->top_last_ms; // read-only: device time of the last recommend_top_pairs
+    else if (key == "overlap_ms") *value = ctx->ovl_last_ms;   // read-only: device time of the last overlap_query
     else if (key == "heldout_ms") *value = ctx->hold_last_ms;  // read-only: device time of the last heldout_eval / heldout_add
     else if (key == "top_pairs_groups") *value = ctx->top_groups;
     else if (key == "launches") *value = use_fused(ctx) ? 2 : 4;  // read-only: launches per iteration at the current slot count

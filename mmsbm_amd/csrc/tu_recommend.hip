@@ -1,10 +1,12 @@
 // tu_recommend.hip -- translation unit of top-N recommendation (recommend.hpp): the session's host side -- the
 // training items of every user, the per-slot prologue, the batches of a query and the choice of the item split -- and
 // of nearest items / users (similar.hpp), whose queries share the batches and the selection; and the m best pairs of
-// the whole model (top_pairs.hpp), a query of the recommend session with kernels of its own
+// the whole model (top_pairs.hpp), a query of the recommend session with kernels of its own; and the overlap of the
+// restarts' groups (overlap.hpp), whose session copies a slot's rows with the recommend session's rec_fold_kernel
 #include "prelude.hpp"
 #include "recommend.hpp"
 #include "similar.hpp"
+#include "overlap.hpp"
 #include "top_pairs.hpp"
 
 #include <climits>
@@ -503,5 +505,65 @@ void similar_query(mmsbm_hip_ctx *c, int64_t n_rows, const int32_t *ids, int n, 
 }
 
 void similar_end(mmsbm_hip_ctx *c) { c->sm.reset(); }
+
+// ---- the overlap of the restarts' groups (overlap.hpp) ---------------------------------------------------------------
+void overlap_begin(mmsbm_hip_ctx *c, int side) {
+  use_device(c);
+  c->ov.reset();  // (from here on the previous session is gone)
+  auto ov = std::make_unique<OvlSession>();
+  ov->side = side;
+  ov->rows = side == 0 ? c->ext_items : c->ext_users;
+  ov->groups = side == 0 ? c->ext_l : c->ext_k;
+  c->ov = std::move(ov);
+}
+
+void overlap_add(mmsbm_hip_ctx *c) {  // the selected slot (the caller holds a OneSlot)
+  use_device(c);
+  OvlSession &ov = *c->ov;
+  const int S = ov.slots, G = ov.groups, rows = ov.rows;
+  const size_t qs = static_cast<size_t>(rows) * G;
+  require_free_mem((S + 1) * qs * sizeof(double), "overlap: the slots' membership tables");
+  hipStream_t st = c->stream;
+  DevBuf<double> nx;  // the table grows by one slot
+  double *xo = grow_by_slot(ov.x, qs, S, st, nx);
+  const ExtSlot e = ext_slot(c);
+  if (qs > 0)  // the slot's rows as they are, external sides (rec_fold_kernel without a matrix)
+    LAUNCH(rec_fold_kernel, static_cast<unsigned>((qs + kBlock - 1) / kBlock), kBlock, 0, st,
+           ov.side == 0 ? e.items : e.users, G, nullptr, 0, 0, xo, rows, G);
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipStreamSynchronize(st));
+  ov.x.swap(nx);
+  ov.slots = S + 1;
+}
+
+void overlap_query(mmsbm_hip_ctx *c, double *out) {
+  use_device(c);
+  const OvlSession &ov = *c->ov;
+  const int rows = ov.rows, G = ov.groups;
+  const size_t F = static_cast<size_t>(ov.slots) * G, nt = (F + kOvlTile - 1) / kOvlTile, pairs = nt * (nt + 1) / 2;
+  // B is a constant, so the number of slabs -- and with it the size of the partials -- follows from the rows alone
+  const size_t slabs = static_cast<size_t>(std::max(1, (rows + kOvlSlab - 1) / kOvlSlab));
+  const size_t tile = static_cast<size_t>(kOvlTile) * kOvlTile, outs = F * F;
+  require_free_mem((slabs * pairs * tile + outs) * sizeof(double), "overlap: the slabs' partial results and the result");
+  if (slabs * pairs > (size_t(1) << 26))  // (the grid: 2^26 tiles are 2 TB of partial results)
+    throw ApiError(MMSBM_E_TOOLARGE, "overlap: " + std::to_string(slabs * pairs) + " partial tiles in one query");
+  hipStream_t st = c->stream;
+  DevBuf<double> part, res;
+  part.alloc(slabs * pairs * tile);
+  res.alloc(outs);
+  EventPair ev;  // device time of the query's kernels (option "overlap_ms")
+  ev.start(st);
+  LAUNCH(ovl_gram_kernel, static_cast<unsigned>(slabs * pairs), kBlock, 0, st, ov.x.ptr, static_cast<size_t>(rows) * G,
+         rows, G, static_cast<int>(F), static_cast<int>(nt), static_cast<int>(pairs), part.ptr);
+  LAUNCH(ovl_combine_kernel, static_cast<unsigned>(pairs * (tile / kBlock)), kBlock, 0, st, part.ptr,
+         static_cast<int>(slabs), static_cast<int>(F), static_cast<int>(nt), static_cast<int>(pairs), res.ptr);
+  HIP_CHECK(hipGetLastError());
+  ev.stop(st);
+  HIP_CHECK(hipMemcpyAsync(out, res.ptr, sizeof(double) * outs, hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipStreamSynchronize(st));
+  c->ovl_last_ms = ev.ms();
+}
+
+void overlap_end(mmsbm_hip_ctx *c) { c->ov.reset(); }
 
 }  // namespace mmsbm_hip_impl

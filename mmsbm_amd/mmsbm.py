@@ -578,6 +578,73 @@ class MMSBM:
         finally:
             ctx.similar_end()
 
+    # ------------------------------------------------------------------ matching the restarts' groups (not in the reference)
+    def align_restarts(self, reference=None):
+        """Which group of each restart is which group of restart ``reference``, and how well the restarts agree.
+
+        Every restart labels its groups in an order of its own.  The overlap of two groups is the population they
+        share, O[a, b] = sum_u theta_s[u, a] theta_t[u, b] (items: eta); the device computes it for all pairs of
+        restarts at once, and each restart's groups are matched to the reference's by the assignment of the largest
+        total overlap.  ``reference``: a position in ``self.results``; None: the restart of the highest training
+        likelihood (the first of them).
+
+        Returns a dict:
+          ``reference``        the position used;
+          ``user_groups``      (S, K) int64, ``[s, k]`` = the group of restart s matched to group k of the reference
+                               (the identity for the reference itself);  ``item_groups`` (S, L) likewise;
+          ``user_similarity``  (S, K), the cosine of each matched pair of theta columns, in [0, 1], 1 for the
+                               reference; a column near 0 across the restarts is a group they do not reproduce -- the
+                               usual sign of too large a K.  ``item_similarity`` (S, L) likewise;
+          ``user_agreement``   (S, S), the largest assignment total of restarts s and t divided by the number of
+                               users: the expected share of users the two put into matched groups; symmetric.
+                               ``item_agreement`` likewise.
+        ``self.results``, the stored predictions and ``score()`` are left as they are."""
+        from . import align
+        self._check_whole_model()
+        S = len(self.results)
+        if reference is None:
+            reference = int(np.argmax([float(a["likelihood"]) for a in self.results]))   # (the first of the highest)
+        elif isinstance(reference, (bool, np.bool_)) or not isinstance(reference, (int, np.integer)):
+            raise ValueError(f"reference must be a position in self.results (an int) or None, got {reference!r}")
+        elif not 0 <= reference < S:
+            raise ValueError(f"reference = {reference} is not a position in self.results (0 .. {S - 1})")
+        reference = int(reference)
+        out = {"reference": reference}
+        for side, groups, n_rows in (("user", self.user_groups, self.p + 1), ("item", self.item_groups, self.m + 1)):
+            ctx, restarts = self._restarts()
+            ctx.overlap_begin(side + "s")
+            try:
+                for _ in restarts:
+                    ctx.overlap_add()
+                gram = ctx.overlap_query()
+            finally:
+                ctx.overlap_end()
+            out[side + "_groups"], out[side + "_similarity"], out[side + "_agreement"] = align.align_side(
+                gram, groups, n_rows, reference)
+        return out
+
+    def consensus(self, reference=None):
+        """theta, eta and pr averaged over the restarts once their groups are matched (``align_restarts``).
+
+        This is a DESCRIPTIVE summary, written in the group labels of restart ``reference`` (None: the restart of the
+        highest training likelihood): what the restarts say about the groups on average, for reading memberships and
+        judging which groups are reproducible.  It is not what the model predicts with: the predictive ensemble remains
+        the mean over the restarts' own predictions that ``predict`` and ``recommend`` use, which needs no matching.
+
+        Returns {"theta": DataFrame (user labels x K), "eta": DataFrame (item labels x L), "pr": {rating label: K x L
+        DataFrame} (shaped as ``self.theta`` / ``self.eta`` / ``self.pr``), "alignment": the dict of
+        ``align_restarts``}.  ``self.results`` and the stored objects are left as they are."""
+        import pandas as pd
+        from . import align
+        alignment = self.align_restarts(reference)
+        theta, eta, pr = align.consensus_params(self.results, alignment["user_groups"], alignment["item_groups"])
+        enc = self.data_handler
+        labels = enc.rating_labels() if enc else range(pr.shape[2])
+        return {"theta": pd.DataFrame(theta, index=enc.user_labels() if enc else None),
+                "eta": pd.DataFrame(eta, index=enc.item_labels() if enc else None),
+                "pr": {lab: pd.DataFrame(pr[:, :, j]) for j, lab in enumerate(labels)},
+                "alignment": alignment}
+
     # ------------------------------------------------------------------ ranking evaluation (not in the reference)
     def log_likelihood(self, data):
         """The held-out predictive log-likelihood of ``data`` (same columns as the training data), on the device:
