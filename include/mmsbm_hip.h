@@ -398,7 +398,8 @@ int mmsbm_hip_set_option(mmsbm_hip_ctx *ctx, const char *name, double value);
 /* Reads a switch back; also the read-only "launches" (2 or 4: what the next iteration takes), "ranges_pairs" / "ranges_users" (ranges the XCD-local work
  * list of that pass uses, 1 = off), "items_pairs" / "items_users" (work items, 0 = segments as
  * they are), "splits_pairs" / "splits_users" (segments cut into pieces), "fused_split" (bit 0 / 1: whole-segment lists of
- * the two-launch form built for the pair / user side), "chunk_pairs" (pairs per pair-stage workgroup at most), "n_chunks"
+ * the two-launch form built for the pair / user side), "item_grid" (1: at least half of the (item, rating) combinations
+ * occur and R <= 16, so the item sums walk a fixed-width grid of pair ids; 0: the items' pair lists), "chunk_pairs" (pairs per pair-stage workgroup at most), "n_chunks"
  * (pair-stage workgroups = slabs, padding included), "a_chunks" (workgroups of the matrix-core A launch when it walks
  * runs of its own; 0: the T + S launch's list serves) and "wide" (1: K, L beyond the 64-pair LDS stage -- the vector form of the pair stage is then the plain
  * wide-row kernels; they run when "mfma" reads 0, the blocked matrix-core kernels when it reads 2). */

@@ -1943,6 +1943,7 @@ int mmsbm_hip_get_option(const mmsbm_hip_ctx *ctx, const char *name, double *val
     else if (key == "splits_pairs") *value = static_cast<double>(ctx->lay.pair_work.splits.size());  // read-only: segments cut into pieces
     else if (key == "splits_users") *value = static_cast<double>(ctx->lay.user_work.splits.size());
     else if (key == "fused_split") *value = (ctx->fs_pairs ? 1 : 0) + (ctx->fs_users ? 2 : 0);  // read-only: whole-segment lists built (1 pair side, 2 user side)
+    else if (key == "item_grid") *value = ctx->item_grid.count ? 1 : 0;  // read-only: item_sum walks the fixed-width grid of pair ids (upload_item_grid)
     else throw std::invalid_argument("unknown option: " + key);
   });
 }

@@ -12,6 +12,7 @@ inputs, never another bar.
 import numpy as np
 import pytest
 
+from border_tables import longdouble_step    # (the np.longdouble restatement of one M-step: shared with the border tables)
 from conftest import ELEMENT_FLOOR, elem_rel_err
 from oracle import mmsbm_factorised as fact
 from oracle import mmsbm_oracle as orc
@@ -20,24 +21,6 @@ from staged_params import FAMILIES, clamped_elements, clamped_rows, staged, unif
 SHAPES = [(7, 13), (36, 30)]          # K L = 91 and 1,080: either side of the 1,024 at which the pair stage changes family
 N_U, N_I, N_R, N_ROWS = 120, 80, 5, 3000
 AGREE = 1e-13
-
-
-def longdouble_step(data, theta, eta, pr, d_u, d_i):
-    """update_coefficients and the normalisations of em_step in np.longdouble: the same max(s, eps), the same zero-row
-    guard of p.  Returns (numerators, parameters), rounded to float64."""
-    ld = np.longdouble
-    u, i, r = data[:, 0], data[:, 1], data[:, 2]
-    th, et, p = theta.astype(ld), eta.astype(ld), pr.astype(ld)
-    om = th[u][:, :, None] * et[i][:, None, :] * np.moveaxis(p, 2, 0)[r]
-    inc = om / np.maximum(om.sum(axis=(1, 2)), ld(orc.EPS))[:, None, None]
-    n_theta, n_eta, n_pr = np.zeros_like(th), np.zeros_like(et), np.zeros_like(p)
-    np.add.at(n_theta, u, inc.sum(axis=2))
-    np.add.at(n_eta, i, inc.sum(axis=1))
-    for rr in range(p.shape[2]):
-        n_pr[:, :, rr] = inc[r == rr].sum(axis=0)
-    tot = n_pr.sum(axis=2, keepdims=True)
-    params = (n_theta / d_u[:, None].astype(ld), n_eta / d_i[:, None].astype(ld), n_pr / np.where(tot == 0, ld(1), tot))
-    return tuple(a.astype(np.float64) for a in (n_theta, n_eta, n_pr)), tuple(a.astype(np.float64) for a in params)
 
 
 def below_floor_share(arrays):
