@@ -29,7 +29,6 @@ namespace {
 
 constexpr double kEps = 2.220446049250313e-16;  // np.finfo(float).eps, src/kernels_numpy.py:51
 constexpr int64_t kGpuLayoutMin = 100'000;       // triples from which the layout's sorts run on the device
-constexpr int kBlock = 256;
 
 // ======================================================================================
 // device helpers

@@ -1,4 +1,4 @@
-// context.hpp -- host side: padding rules, device buffers, the context (mmsbm_hip_ctx), launch bookkeeping
+// context.hpp -- host side: device buffers, the context (mmsbm_hip_ctx), launch bookkeeping
 // Included by every translation unit of the library (prelude.hpp).
 #pragma once
 
@@ -7,31 +7,7 @@ namespace {
 // ======================================================================================
 // host side
 // ======================================================================================
-int pad_dim(int d) {  // multiples of 4: 32-byte row granules, whole chunks of 4 outputs
-  if (d <= 256) return (d + 3) / 4 * 4;
-  if (d <= 512) return (d + 7) / 8 * 8;
-  if (d <= 1024) return (d + 15) / 16 * 16;
-  return (d + 31) / 32 * 32;  // (whole lanes of the 64 x 32 instantiation of the triple passes)
-}
-
-// (G, VEC) instantiation for a padded row length: code 0..6
-// Four doubles (32 bytes) per lane: fewer lanes per row means more rows per wave instruction,
-// i.e. less vector-ALU work (dot product, DPP reduction, division) per triple.
-int group_code(int dp) {
-  if (dp <= 16) return 0;   // G=4  VEC=4
-  if (dp <= 32) return 1;   // G=8  VEC=4
-  if (dp <= 64) return 2;   // G=16 VEC=4
-  if (dp <= 128) return 3;  // G=32 VEC=4
-  if (dp <= 256) return 4;  // G=64 VEC=4
-  if (dp <= 512) return 5;  // G=64 VEC=8
-  return 6;                 // G=64 VEC=16 (up to 1,024 groups)
-}
-constexpr int kMaxGroupRow = 1024;  // columns the widest (G, VEC) covers; wider rows: seg_wide_kernel / block loops
-int group_lanes(int code) {
-  static const int g[7] = {4, 8, 16, 32, 64, 64, 64};
-  return g[code];
-}
-
+// one (G, VEC) instantiation per group_code (shapes.hpp)
 #define DISPATCH_GV(code, CALL)                                   \
   switch (code) {                                                 \
     case 0: CALL(4, 4); break;                                    \
@@ -246,21 +222,14 @@ struct mmsbm_hip_ctx {
   int n_users = 0, n_items = 0, n_ratings = 0, k = 0, l = 0, kp = 0, lp = 0;
   int n_pairs = 0, n_chunks = 0;
   int code_k = 0, code_l = 0;
-  bool direct_out = false;  // pair_block: output rows stored straight from registers (no LDS transpose)
 #ifdef MMSBM_ABLATE
   int ablate = 0;           // diagnostic build (-DMMSBM_ABLATE): phases the pair stage / eta_p skip, set by mmsbm_hip_time_stage
 #endif
-  bool split_rows = false;  // theta and A kept as 128-byte main lines + tail rows (RowTab)
-  int pb_threads_t = kBlock, pb_threads_a = kBlock;  // pair_block workgroup sizes (T+S mode, A mode)
-  int pb_kt = 4;  // pair_block S phase: k-rows per register tile (2 when K x L is small)
-  int pb_spb = kBlock, pb_nacc = 1, pb_nsub = 1;  // pair_block S phase: threads per slot-grid copy, slots per thread
-  size_t lds_t = 0, lds_a = 0;
-  bool tl_t = false, tl_a = false;  // rating tile staged in LDS (T+S launch / A launch)
-  bool quad_a = false;  // the A launch runs pair_quad_a_kernel (long rows)
+  PairPlan pp;  // the pair stage's launch plan: its form and geometry (pair_plan.hpp)
   // prod_dist / predict through B[(item, rating), :] = p_r eta_i (predict_rows_kernel)
   DevBuf<int32_t> grid_item;          // item of pair q = r * I + i, every (item, rating) combination
   DevBuf<mmsbm::Chunk> grid_chunks;   // its rating-homogeneous chunks
-  int grid_n_chunks = 0, mv_chunk_pairs = mmsbm::kMvChunkPairs;
+  int grid_n_chunks = 0;
   DevBuf<double> btab;                // [I * R][kp], of the slot being scored
   bool predict_fast = true;
   int seg_batch = 4;  // row gathers a group of seg_pass keeps in flight (4, or 8)
@@ -275,14 +244,9 @@ struct mmsbm_hip_ctx {
   int fp_max_parts = 0, fu_max_parts = 0, fu_blocks = 0;
   std::vector<char> a_ok;      // per slot: atab[cur] holds A of the CURRENT parameters (the fused form computes A at
                                // the start of an iteration, so after a committed fused iteration it does not)
-  bool mfma = false;    // both pair-stage launches run pair_mfma_kernel (tiles beyond the scalar cache, K, L <= 64)
-  size_t lds_mt = 0, lds_ma = 0;
-  bool mfma_big = false;  // K or L beyond 64: the blocked forms (mfma_rows_kernel + mfma_slab_kernel)
-  bool wide = false;    // K, L beyond the LDS stage: wide_matvec / wide_slab kernels (any size)
   int nt_out = 7;          // option "nt_out" (bits: 1 T and A rows, 2 theta' rows as non-temporal stores, 4 the segments' own rows as non-temporal loads) where that pays (nt_on, launch.hpp)
   int ranges_pairs = 1, ranges_users = 1;  // XCD-local work lists: ranges the gathered table is cut into
   int n_cus = 256;
-  size_t lds_qa = 0;
   mmsbm::Layout lay;  // host copy (degrees, sizes)
   DevBuf<int32_t> pair_off, pair_user, pair_item, user_off, user_pair, item_off, item_pairs,
       item_deg, mv_chunk_off, orig_u, orig_i, orig_r;

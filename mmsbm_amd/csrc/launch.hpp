@@ -130,7 +130,7 @@ inline RowTab plain_tab(double *base, int width, size_t slot_stride = 0) {
 // A gathered table (theta, A) as seen from restart slot `slot`: the n_slots copies of every row are
 // interleaved (RowTab), main parts of all rows first, then the tail parts.
 inline RowTab gather_tab(const mmsbm_hip_ctx *c, double *base, size_t rows, int slot) {
-  int mw = c->split_rows ? (c->kp / 16) * 16 : c->kp;  // (split_rows is always on today)
+  int mw = (c->kp / 16) * 16;  // whole 128-byte main lines + a tail row
   if (mw == 0) mw = c->kp;
   const int tw = c->kp - mw, ns = c->n_slots;
   return RowTab{base + static_cast<size_t>(slot) * mw,
@@ -200,18 +200,6 @@ inline ExtSlot ext_slot(const mmsbm_hip_ctx *c, int slot) {
 inline int nt_on(const mmsbm_hip_ctx *c) {
   const bool plain_data = (c->lay.pair_work.items.empty() && c->lay.user_work.items.empty()) || (c->nt_out & 8);  // (8: tuning, whatever the data)
   return (plain_data && c->launch_slots == 1 && c->kp <= 32 && c->lp <= 32) ? (c->nt_out & 7) : 0;
-}
-
-inline bool mfma_possible(const mmsbm_hip_ctx *c) {
-  return !c->wide && c->kp <= kMfmaMaxDim && c->lp <= kMfmaMaxDim && c->lds_mt <= kLdsMax && c->lds_ma <= kLdsMax;
-}
-// The pair stage runs on the matrix cores.  (`mfma` is never set while `wide` is: create() and option "mfma" both set it
-// through mfma_possible, and `wide` is decided once, before either.  `mfma_big` may be, and then takes wide shapes too.)
-inline bool pair_stage_on_mfma(const mmsbm_hip_ctx *c) { return c->mfma || c->mfma_big; }
-// The A launch as pair_quad_a_kernel: the tile in LDS, 512-thread workgroups, four units' rows and the tile inside the LDS
-inline bool quad_possible(const mmsbm_hip_ctx *c) {
-  return !c->wide && tile_beyond_scalar_cache(c->kp, c->lp) && c->tl_a && c->pb_threads_a == kPairBlockMax &&
-         c->lds_qa <= kLdsMax - 2048 && c->lp <= kQuadMaxL;
 }
 
 }  // namespace

@@ -123,11 +123,11 @@ void launch_log_note(const void *host_fn) { launch_log().note(host_fn); }
 // ---- the form of the pair stage the context's shape and options select ------------------------------------------------
 void stage_dense(mmsbm_hip_ctx *c) {  // T = P^T C  and the K x L slabs for p
   if (c->n_chunks == 0) return;
-  if (pair_stage_on_mfma(c)) stage_dense_mfma(c);
+  if (c->pp.on_mfma()) stage_dense_mfma(c);
   else stage_dense_valu(c);
 }
 void stage_matvec_a(mmsbm_hip_ctx *c, int slot, int a_slot, bool grid) {
-  if (pair_stage_on_mfma(c)) stage_matvec_a_mfma(c, slot, a_slot, grid);
+  if (c->pp.on_mfma()) stage_matvec_a_mfma(c, slot, a_slot, grid);
   else stage_matvec_a_valu(c, slot, a_slot, grid);
 }
 
@@ -175,8 +175,8 @@ inline int balanced_run_units(const std::vector<int32_t> &rating_off, int slots,
 void build_a_runs(mmsbm_hip_ctx *c, int units) {
   c->n_a_chunks = 0;
   c->a_chunks.release();
-  if (!c->mfma || c->n_pairs <= 0) return;
-  const int now = c->mv_chunk_pairs / kUnitPairs, most = kMfmaChunkPairs / kUnitPairs;
+  if (!c->pp.mfma || c->n_pairs <= 0) return;
+  const int now = c->pp.chunk_pairs / kUnitPairs, most = kMfmaChunkPairs / kUnitPairs;
   int a_units = units > 0 ? std::min(units, most)
                           : balanced_run_units(c->lay.rating_off, mfma_a_blocks_per_cu(c) * c->n_cus, std::max(2, now / 2),
                                                std::min(2 * now, most));
@@ -192,12 +192,7 @@ void build_a_runs(mmsbm_hip_ctx *c, int units) {
 
 // ---- small problems: the iteration in two launches (fused_small.hpp) -------------------------------------
 bool fused_shape_ok(const mmsbm_hip_ctx *c) {  // (everything but the data: the kernels exist for this shape)
-  // (rows of up to 24 groups: beyond that the four-launch pair stage runs 512-thread workgroups, whose split of a
-  // unit's pairs among the copies of the slab grid -- hence the association order of S -- 256 threads cannot mirror)
-  return c->code_k <= 1 && c->code_l <= 1 && c->pb_threads_t == kBlock && c->pb_threads_a == kBlock && !c->tl_t &&
-         !c->tl_a && c->pb_nacc == 1 && c->pb_kt == 2 && c->pb_spb * c->pb_nsub <= kBlock && !c->wide &&
-         !c->mfma && !c->mfma_big && !c->direct_out && c->mv_chunk_pairs == mmsbm::kMvChunkPairs && c->n_chunks > 0 &&
-         pairs_fused_lds(c->kp, c->lp) <= kLdsBudget;
+  return c->code_k <= 1 && c->code_l <= 1 && c->n_chunks > 0 && c->pp.fused_shape_ok();
 }
 bool fused_possible(const mmsbm_hip_ctx *c) {
   // A work list that only ORDERS whole segments is fine (the pair units ignore it -- every segment's result is its
@@ -541,36 +536,6 @@ void plan_sides(mmsbm_hip_ctx *c, int device, int64_t n_obs, int32_t n_users, in
   }
   c->kp = pad_dim(c->k); c->lp = pad_dim(c->l);
   c->code_k = group_code(c->kp); c->code_l = group_code(c->lp);
-}
-
-// The geometry of the lane-per-pair stage, and whether the shape has outgrown it: arithmetic on kp, lp and n_obs only
-void plan_pair_stage(mmsbm_hip_ctx *c, const CreateKnobs &knobs) {
-  // four waves share the chunks of 4 outputs of a short row; long rows get up to 8 waves
-  // (measured: 320 threads do not beat 256 at L = 20, 512 beat 256 by 15 % at L = 50)
-  auto threads_for = [](int nch) { return nch <= 6 ? kBlock : kPairBlockMax; };
-  c->pb_threads_t = threads_for(c->lp / 4);
-  c->pb_threads_a = threads_for(c->kp / 4);
-  const int nthr = c->pb_threads_t;
-  c->pb_kt = ((c->kp / 2) * (c->lp / 4) <= kBlock / 2) ? 2 : 4;
-  const int nslot = (c->kp / c->pb_kt) * (c->lp / 4);
-  if (nslot <= nthr / 2) {
-    c->pb_spb = nslot; c->pb_nacc = 1;
-    const int room = (c->kp * (kUnitPairs + 1) + kUnitPairs * c->lp) /
-                     (nslot * 4 * c->pb_kt);  // hand-over area
-    c->pb_nsub = std::max(1, std::min(std::min(nthr / nslot, 8), 1 + room));
-  }
-  else { c->pb_spb = nthr; int n = 1; while (n * nthr < nslot) n *= 2; c->pb_nacc = n; }
-  // the rating tile sits in LDS when it is too big for the scalar cache -- unless that does not
-  // fit beside the rows, then it is read through scalar loads after all (slower, but it runs)
-  c->tl_t = tile_in_lds(c->kp, c->lp);
-  c->tl_a = tile_in_lds(c->lp, c->kp);
-  c->lds_t = pair_block_lds(c->kp, c->lp, c->tl_t);
-  c->lds_a = pair_block_lds(c->lp, c->kp, c->tl_a);
-  if (c->lds_t > kLdsMax) { c->tl_t = false; c->lds_t = pair_block_lds(c->kp, c->lp, false); }
-  if (c->lds_a > kLdsMax) { c->tl_a = false; c->lds_a = pair_block_lds(c->lp, c->kp, false); }
-  // still too large for the 64-pair LDS stage (roughly K + L > 300): the plain wide-row kernels
-  c->wide = c->lds_t > kLdsMax || c->lds_a > kLdsMax || c->pb_nacc > 4 || knobs.force_wide;
-  c->split_rows = true;
   // small problems leave most CUs a couple of workgroups: the triple passes are then bound by the rounds of
   // dependent gathers per segment, and eight rows in flight per group beat four (C1 16.8 -> 16.1 us, C2 29.7 ->
   // 29.1 us per iteration); at C3 four are better (95.3 vs 97.3 us)
@@ -638,43 +603,14 @@ bool build_index(mmsbm_hip_ctx *c, const CreateKnobs &knobs, const int32_t *iu, 
   return true;
 }
 
-// Which form of the pair stage the shape gets and how many pairs a workgroup of it takes; rebuilds the unit list to
-// that length.  Returns the 64-pair units as the layout built them: the likelihood (likelihood_units_kernel: <= 64 pairs)
-// keeps that list whatever replaces it here or in build_fused_lists().
-std::vector<mmsbm::Chunk> plan_dense_forms(mmsbm_hip_ctx *c, const CreateKnobs &knobs) {
+// The pair stage's plan applied to the index: the unit list rebuilt to the plan's chunk length.  Returns the 64-pair units
+// as the layout built them: the likelihood (likelihood_units_kernel: <= 64 pairs) keeps that list whatever replaces it
+// here or in build_fused_lists().
+std::vector<mmsbm::Chunk> apply_pair_plan(mmsbm_hip_ctx *c, const PairPlan &plan) {
   std::vector<mmsbm::Chunk> units64 = c->lay.mv_chunks;
   c->n_lik_units = static_cast<int>(units64.size());
-  const bool big_tile = tile_beyond_scalar_cache(c->kp, c->lp);
-  // both launches on the matrix cores where the tile has left the scalar cache (pair_mfma_kernel)
-  c->lds_mt = pair_mfma_lds(c->kp, c->lp, true);
-  c->lds_ma = pair_mfma_lds(c->lp, c->kp, false);
-  c->mfma = mfma_possible(c) && big_tile && !knobs.no_mfma;
-  // K or L beyond 64: the blocked matrix-core kernels take over from the lane-per-pair stage with its tile in
-  // scalar loads and from the wide-row kernels
-  // Skinny tiles too (a side below 16 groups, e.g. 600 x 5 or 3 x 1,024): three quarters of a 16-wide tile are
-  // padding there, and it is still several times faster than the alternatives -- the wide-row kernels have one
-  // thread per output column (8 of 256 threads busy at L = 5), the lane-per-pair stage streams a 38 KB tile
-  // through the scalar cache.  1M ratings, T+S / A launch: 600 x 5 2,336 / 124 -> 380 / 115 us, 1,024 x 3
-  // 5,822 / 152 -> 621 / 171, 8 x 520 471 / 927 -> 247 / 191, 3 x 1,024 470 / 3,219 -> 430 / 346, 300 x 8
-  // 310 / 91 -> 197 / 53 (scripts/skinny_time.py, round 3).
-  c->mfma_big = !c->mfma && big_tile && !knobs.no_mfma;
-  // big K x L tiles: four 64-pair units per pair_block workgroup (4x fewer slabs to write + add); on the matrix cores
-  // eight while that still leaves every CU a few rounds of workgroups (C5: T+S 358 -> 342 us, half the slabs for
-  // eta_p: 123 -> 111 us; 768 or 1,024 pairs per workgroup are slower)
-  int big_chunk = 4 * mmsbm::kMvChunkPairs;
-  if (c->mfma && c->lay.n_pairs >= 2 * big_chunk * 4 * c->n_cus) big_chunk *= 2;
-  if (knobs.mfma_chunk > 0) big_chunk = knobs.mfma_chunk;
-  c->mv_chunk_pairs = c->wide ? kWideChunkPairs : (big_tile ? big_chunk : mmsbm::kMvChunkPairs);
-  if (c->wide || big_tile) mmsbm::build_mv_chunks(c->lay, c->mv_chunk_pairs);
-  // long rows: the mat-vec's outputs go to memory straight from registers (C5: -6 % on both
-  // pair_block launches); short rows are cheaper transposed through LDS and copied out flat
-  // (C3: direct stores cost +1.1 / +1.7 us)
-  c->direct_out = big_tile;
-  // ... and the A launch as a persistent four-unit pipeline where the tile sits in LDS and
-  // everything fits (C5: 312 -> 259 us)
-  c->lds_qa = (static_cast<size_t>(kQuadUnits) * c->lp * (kUnitPairs + 1) + static_cast<size_t>(c->lp) * c->kp) *
-              sizeof(double);
-  c->quad_a = quad_possible(c) && big_chunk == 4 * mmsbm::kMvChunkPairs;
+  c->pp = plan;
+  if (plan.wide || plan.big_tile()) mmsbm::build_mv_chunks(c->lay, plan.chunk_pairs);
   c->n_pairs = c->lay.n_pairs;
   c->n_chunks = static_cast<int>(c->lay.mv_chunks.size());
   return units64;
@@ -900,17 +836,16 @@ int mmsbm_hip_create(int device, int64_t n_obs, int32_t n_users, int32_t n_items
     std::unique_ptr<mmsbm_hip_ctx> c(new mmsbm_hip_ctx());
     plan_sides(c.get(), device, n_obs, n_users, n_items, n_ratings, k_groups, l_groups, swap_sides);
     const int32_t *iu = c->swapped ? item : user, *ii = c->swapped ? user : item;  // the id columns of the internal sides
-    plan_pair_stage(c.get(), knobs);
+    const PairPlan shape = plan_pair_shape(c->kp, c->lp, knobs.force_wide);
     lap("checks");
     open_device(c.get());
     const bool gpu_layout = build_index(c.get(), knobs, iu, ii, rating, lap);
-    // (after open_device: chunk lengths are sized from the CU count.  After plan_pair_stage: `wide` decides first.)
-    const std::vector<mmsbm::Chunk> units64 = plan_dense_forms(c.get(), knobs);
+    const std::vector<mmsbm::Chunk> units64 =
+        apply_pair_plan(c.get(), plan_pair_forms(shape, c->lay.n_pairs, c->n_cus, knobs.no_mfma, knobs.mfma_chunk));
     build_range_worklists(c.get(), knobs, gpu_layout);
     lap("xcd-local work lists");
-    // (after plan_dense_forms: fused_shape_ok reads n_chunks, mfma, direct_out and mv_chunk_pairs)
     build_fused_lists(c.get(), knobs, lap);
-    // small problems (where eight rows in flight pay, plan_pair_stage): two launches per iteration instead of four
+    // small problems (where eight rows in flight pay, plan_sides): two launches per iteration instead of four
     c->fused = n_obs <= kFusedRatingsMax && fused_possible(c.get()) && !knobs.no_fused;
     upload_index(c.get(), knobs, gpu_layout, units64, iu, ii, rating);
     lap("index uploads");
@@ -1206,8 +1141,8 @@ void ensure_pair_grid(mmsbm_hip_ctx *c) {  // q = r * I + i, chunks of the pair 
     for (int r = 0; r < c->n_ratings; ++r) {
       const int32_t base = static_cast<int32_t>(static_cast<size_t>(r) * c->n_items);
       for (int i = 0; i < c->n_items; ++i) item[static_cast<size_t>(base) + i] = i;
-      for (int i = 0; i < c->n_items; i += c->mv_chunk_pairs)
-        chunks.push_back(mmsbm::Chunk{r, base + i, base + std::min(i + c->mv_chunk_pairs, c->n_items), 0});
+      for (int i = 0; i < c->n_items; i += c->pp.chunk_pairs)
+        chunks.push_back(mmsbm::Chunk{r, base + i, base + std::min(i + c->pp.chunk_pairs, c->n_items), 0});
     }
     c->grid_item.upload(item, c->stream);
     c->grid_chunks.upload(chunks, c->stream);
@@ -1879,9 +1814,9 @@ int mmsbm_hip_set_option(mmsbm_hip_ctx *ctx, const char *name, double value) {
       if (g != 0 && g != 1 && g != 2 && g != 4 && g != 8) throw std::invalid_argument("lik_g: 0, 1, 2, 4 or 8");
       ctx->lik_g = g;
     } else if (key == "quad") {  // 0: the A launch through pair_block like every other shape
-      // (create() also requires unit runs of four -- big_chunk == 4 * kMvChunkPairs, plan_dense_forms -- and this option
+      // (create() also requires unit runs of four -- big_chunk == 4 * kMvChunkPairs, plan_pair_forms -- and this option
       // never has: with longer runs it turns on what create() left off.  Whether that is meant is open; both are as they were)
-      ctx->quad_a = value != 0.0 && quad_possible(ctx);
+      ctx->pp.set_quad(value != 0.0);
     } else if (key == "fused") {  // two launches per iteration (small tiles, unsplit segments); any problem size
       if (value != 0.0 && !fused_possible(ctx)) throw std::invalid_argument("fused: not available for this shape / data");
       ctx->fused = value != 0.0;
@@ -1901,12 +1836,11 @@ int mmsbm_hip_set_option(mmsbm_hip_ctx *ctx, const char *name, double value) {
       build_a_runs(ctx, static_cast<int>(value));
     } else if (key == "mfma") {  // the pair stage on the matrix cores: 0 off, 1 on (one-block form if K, L <= 64,
                                  // else the blocked form), 2 the blocked form whatever the shape
-      ctx->mfma = value == 1.0 && mfma_possible(ctx);
-      ctx->mfma_big = value != 0.0 && !ctx->mfma && ctx->mv_chunk_pairs <= kMfmaChunkPairs;
+      ctx->pp.set_mfma(value);
     } else {
       throw std::invalid_argument("unknown option: " + key);
     }
-    ctx->drop_graphs();
+    ctx->drop_graphs();  // (after every option: a captured graph holds the launches of the plan it was captured under)
   });
 }
 
@@ -1915,8 +1849,8 @@ int mmsbm_hip_get_option(const mmsbm_hip_ctx *ctx, const char *name, double *val
     if (!ctx || !name || !value) throw std::invalid_argument("null argument");
     const std::string key(name);
     if (key == "graph") *value = ctx->graph_mode;
-    else if (key == "quad") *value = ctx->quad_a;
-    else if (key == "mfma") *value = ctx->mfma ? 1.0 : (ctx->mfma_big ? 2.0 : 0.0);
+    else if (key == "quad") *value = ctx->pp.quad_a;
+    else if (key == "mfma") *value = ctx->pp.mfma ? 1.0 : (ctx->pp.mfma_big ? 2.0 : 0.0);
     else if (key == "predict_fast") *value = ctx->predict_fast;
     else if (key == "fused") *value = ctx->fused;
     else if (key == "nt_out") *value = nt_on(ctx);
@@ -1929,12 +1863,12 @@ int mmsbm_hip_get_option(const mmsbm_hip_ctx *ctx, const char *name, double *val
     else if (key == "heldout_ms") *value = ctx->hold_last_ms;  // read-only: device time of the last heldout_eval / heldout_add
     else if (key == "top_pairs_groups") *value = ctx->top_groups;
     else if (key == "launches") *value = use_fused(ctx) ? 2 : 4;  // read-only: launches per iteration at the current slot count
-    else if (key == "wide") *value = ctx->wide;
+    else if (key == "wide") *value = ctx->pp.wide;
     else if (key == "lik_fast") *value = ctx->lik_mode;
     else if (key == "lik_g") *value = ctx->lik_g;
     else if (key == "ranges_pairs") *value = ctx->ranges_pairs;   // read-only: XCD-local work lists,
     else if (key == "ranges_users") *value = ctx->ranges_users;   // ranges per pass (1 = off)
-    else if (key == "chunk_pairs") *value = ctx->mv_chunk_pairs;   // read-only: pairs per pair-stage workgroup at most
+    else if (key == "chunk_pairs") *value = ctx->pp.chunk_pairs;   // read-only: pairs per pair-stage workgroup at most
     else if (key == "n_chunks") *value = ctx->n_chunks;            // read-only: pair-stage workgroups (= slabs), padding included
     else if (key == "a_units") *value = ctx->a_units;     // 64-pair units per workgroup of the matrix-core A launch (0: not on the matrix cores)
     else if (key == "a_chunks") *value = ctx->n_a_chunks;   // read-only: workgroups of the matrix-core A launch when it walks runs of its own (0: the T + S launch's)

@@ -307,7 +307,7 @@ PairBlockArgs pair_block_t_args(const mmsbm_hip_ctx *c) {
   pa.tiles = c->p[c->cur].at(s); pa.in_tab = c->ctab.at(s); pa.e_tab = c->eta[c->cur].at(s);
   pa.pair_item = c->pair_item.ptr; pa.chunks = c->mv_chunks.ptr;
   pa.out = c->ttab.at(s); pa.partial = c->partial.at(s);
-  pa.din = c->k; pa.dinp = c->kp; pa.doutp = c->lp; pa.spb = c->pb_spb; pa.nsub = c->pb_nsub;
+  pa.din = c->k; pa.dinp = c->kp; pa.doutp = c->lp; pa.spb = c->pp.spb; pa.nsub = c->pp.nsub;
 #ifdef MMSBM_ABLATE
   pa.abl = c->ablate;
 #endif
@@ -341,7 +341,8 @@ PairBlockArgs pair_block_a_args(const mmsbm_hip_ctx *c, int param_slot, int a_sl
 PairBlockArgs matvec_a_args(const mmsbm_hip_ctx *c, int slot, int a_slot, bool grid, int *n_blocks) {
   int nb = grid ? c->grid_n_chunks : static_cast<int>(c->lay.mv_chunks.size());
   PairBlockArgs pa = pair_block_a_args(c, slot, a_slot);
-  if (!grid && c->mfma && c->n_a_chunks > 0) {  // the same units in runs of its own (create(): balanced_run_units)
+  // (option "mfma" does not rebuild a_chunks: the runs of create() or of option "a_units" serve whenever `mfma` is on)
+  if (!grid && c->pp.mfma && c->n_a_chunks > 0) {  // the same units in runs of its own (create(): balanced_run_units)
     pa.chunks = c->a_chunks.ptr;
     nb = c->n_a_chunks;
   }

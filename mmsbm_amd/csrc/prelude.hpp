@@ -39,6 +39,7 @@
 #include "layout.hpp"
 #include "common.hpp"
 #include "shapes.hpp"
+#include "pair_plan.hpp"
 #include "stamps.hpp"
 #include "rowtab.hpp"
 #include "context.hpp"

@@ -1,10 +1,36 @@
-// shapes.hpp -- sizes and limits every translation unit of the library agrees on: workgroup sizes, unit lengths and the
-// LDS footprints the kernels are launched with (host constants only; no kernels)
+// shapes.hpp -- sizes and limits every translation unit of the library agrees on: the padding of K and L, workgroup
+// sizes, unit lengths and the LDS footprints the kernels are launched with (host arithmetic only: no kernels, no HIP type)
 #pragma once
 
 namespace {
 
-constexpr int kUnitPairs = 64;       // pairs of one rating a pair-stage workgroup multiplies at a time
+inline int pad_dim(int d) {  // multiples of 4: 32-byte row granules, whole chunks of 4 outputs
+  if (d <= 256) return (d + 3) / 4 * 4;
+  if (d <= 512) return (d + 7) / 8 * 8;
+  if (d <= 1024) return (d + 15) / 16 * 16;
+  return (d + 31) / 32 * 32;  // (whole lanes of the 64 x 32 instantiation of the triple passes)
+}
+
+// (G, VEC) instantiation for a padded row length: code 0..6
+// Four doubles (32 bytes) per lane: fewer lanes per row means more rows per wave instruction,
+// i.e. less vector-ALU work (dot product, DPP reduction, division) per triple.
+inline int group_code(int dp) {
+  if (dp <= 16) return 0;   // G=4  VEC=4
+  if (dp <= 32) return 1;   // G=8  VEC=4
+  if (dp <= 64) return 2;   // G=16 VEC=4
+  if (dp <= 128) return 3;  // G=32 VEC=4
+  if (dp <= 256) return 4;  // G=64 VEC=4
+  if (dp <= 512) return 5;  // G=64 VEC=8
+  return 6;                 // G=64 VEC=16 (up to 1,024 groups)
+}
+constexpr int kMaxGroupRow = 1024;  // columns the widest (G, VEC) covers; wider rows: seg_wide_kernel / block loops
+inline int group_lanes(int code) {
+  static const int g[7] = {4, 8, 16, 32, 64, 64, 64};
+  return g[code];
+}
+
+constexpr int kBlock = 256;          // threads of a workgroup, where nothing else is said
+constexpr int kUnitPairs = 64;      // pairs of one rating a pair-stage workgroup multiplies at a time
 constexpr int kPairBlockMax = 512;   // threads of the pair stage's big workgroups
 
 constexpr int kQuadUnits = 4;  // 64-pair units a workgroup of pair_quad_a_kernel multiplies jointly
@@ -56,6 +82,7 @@ inline void mfma_geometry(int dinp, int doutp, int *mg0, int *mg1) {
 // ---- wide rows (pair_quad.hpp: wide_matvec_kernel, wide_slab_kernel) ----
 constexpr int kWidePairs = 8, kWideChunkPairs = 1024;
 constexpr int kWideKG = 8;  // (16: the C values no longer fit the scalar registers, 921 vs 477 us)
+inline size_t wide_matvec_lds(int dinp) { return static_cast<size_t>(kWidePairs) * dinp * sizeof(double); }
 
 // ---- small problems: the two-launch iteration (fused_small.hpp) ----
 inline size_t pairs_fused_lds(int kp, int lp, int split_parts = 0) {  // split_parts: partial rows of a unit's split pairs

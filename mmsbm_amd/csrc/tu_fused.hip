@@ -16,7 +16,7 @@ void stage_fused_pairs(mmsbm_hip_ctx *c) {
   fa.theta = theta_tab(c, cur); fa.a_out = a_tab(c, cur);
   fa.pair_off = c->pair_off.ptr; fa.pair_user = c->pair_user.ptr; fa.pair_item = c->pair_item.ptr;
   fa.chunks = c->mv_chunks.ptr; fa.t_out = c->ttab.at(s); fa.partial = c->partial.at(s);
-  fa.kp = c->kp; fa.lp = c->lp; fa.spb = c->pb_spb; fa.nsub = c->pb_nsub; fa.nt = nt_on(c) & 1;
+  fa.kp = c->kp; fa.lp = c->lp; fa.spb = c->pp.spb; fa.nsub = c->pp.nsub; fa.nt = nt_on(c) & 1;
   fa.bs_tiles = c->p[0].stride; fa.bs_eta = c->eta[0].stride; fa.bs_t = c->ttab.stride; fa.bs_partial = c->partial.stride;
   const bool split = c->fs_pairs && !c->lay.pair_work.splits.empty();
   fa.units = split ? c->fp_units.ptr : nullptr; fa.items = split ? c->fp_items.ptr : nullptr;

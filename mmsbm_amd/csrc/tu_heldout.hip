@@ -7,7 +7,7 @@ namespace mmsbm_hip_impl {
 
 namespace {
 
-// (G, tile in LDS) for the shape: G lanes per row follow the wider of the two rows (group_code, context.hpp); the
+// (G, tile in LDS) for the shape: G lanes per row follow the wider of the two rows (group_code, shapes.hpp); the
 // rating's tile is staged where the launch's LDS holds it
 struct HoldForm {
   int lanes;

@@ -24,7 +24,7 @@ def short(name):
                     ("lik_wave_kernel", "lik_wave_kernel"), ("lik_lane_kernel", "lik_lane_kernel"),
                     ("seg_combine_both_kernel", "seg_combine_both_kernel"), ("theta_log_pairs_kernel", "theta_log_pairs_kernel"),
                     ("seg_combine_small_kernel", "seg_combine_small_kernel"),
-                    ("seg_combine_kernel", "seg_combine_kernel"), ("likelihood_fast_kernel", "likelihood_fast_kernel"), ("log_table_kernel", "log_table_kernel"),
+                    ("likelihood_fast_kernel", "likelihood_fast_kernel"), ("log_table_kernel", "log_table_kernel"),
                     ("init_rows_kernel", "init_rows_kernel"), ("likelihood_units_kernel", "likelihood_units_kernel"),
                     ("likelihood_kernel", "likelihood_kernel"), ("prod_dist_kernel", "prod_dist_kernel")):
         if key in name:

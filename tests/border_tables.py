@@ -414,7 +414,7 @@ def reference_step(data, theta, eta, pr, d_u, d_i):
 
 
 # ---- the registry the CPU and the GPU module share ----
-# (item_len, g, K, L): the internal row length K (padded to a multiple of 4) selects the group of g lanes (context.hpp: group_code)
+# (item_len, g, K, L): the internal row length K (padded to a multiple of 4) selects the group of g lanes (shapes.hpp: group_code)
 SEGMENT_CASES = [(64, 4, 10, 10), (16, 4, 10, 10), (64, 8, 20, 12), (16, 16, 50, 50), (16, 32, 80, 80)]
 GRID_R = tuple(range(1, 18))
 FULL_R = (1, 7, 11, 16)         # R of the tables with every (item, rating) combination: one round at B = 8, 8 + 2 + 1, two full rounds

@@ -243,7 +243,7 @@ def required(family, R):
 
 # ---- the cases both test files run -------------------------------------------------------------------------------------
 # name -> (family, weight kind, (U, I, K, L, R, S), swap_sides).  K and L are the caller's; with swap_sides = 0 they are
-# the internal ones too, and group_code (context.hpp) goes by the padded internal K: <= 16, 32, 64, 128, 256, 512, more.
+# the internal ones too, and group_code (shapes.hpp) goes by the padded internal K: <= 16, 32, 64, 128, 256, 512, more.
 FORM_KS = (16, 17, 32, 33, 64, 65, 128, 129, 256, 257, 512, 513, 1040)
 GROUPS_OF_K = {16: (4, 4), 17: (8, 4), 32: (8, 4), 33: (16, 4), 64: (16, 4), 65: (32, 4), 128: (32, 4), 129: (64, 4),
                256: (64, 4), 257: (64, 8), 512: (64, 8), 513: (64, 16), 1040: (64, 16)}    # K -> (G, VEC)
