@@ -85,6 +85,17 @@ int mmsbm_hip_destroy(mmsbm_hip_ctx *ctx);
 int mmsbm_hip_dims(const mmsbm_hip_ctx *ctx, int64_t dims[8]);
 /* d_u (U) and d_i (I): rows per user / item, floored at 1 (src/mmsbm.py:106-111). */
 int mmsbm_hip_degrees(const mmsbm_hip_ctx *ctx, int64_t *d_user, int64_t *d_item);
+/* The index this context's kernels read, for tests: which 0 .. 15 as mmsbm_hip_layout_array below (the 4-int records
+ * flattened; out == NULL queries *count), 16 item_grid ([I][R] pair ids, -1: none; empty when the context has no grid),
+ * 17 lik_units (the likelihood's 64-pair units, records like mv_chunks), 18 mv_chunk_off.  Every array that has a device
+ * buffer -- pair_off, pair_user, pair_item, user_off, user_pair, item_off, item_pairs, item_deg, mv_chunks, the work
+ * items and split segments of both sides, item_grid, lik_units, mv_chunk_off -- is copied from that buffer, device to
+ * host, after the context's stream has been synchronised; rating_off, chunk_off and chunks are the context's host copy
+ * (it keeps them nowhere else).  All in INTERNAL terms: in a swapped context (dims[7]) the "users" are the caller's items
+ * and the pairs are (user, rating) combinations.  Read-only: touches no slot, no session and no EM state.
+ * MMSBM_E_INVALID: null context or count, unknown which, capacity below the count.
+ * mmsbm_hip_get_option(ctx, "gpu_layout") reads which builder sorted this index: 1 the device, 0 the host. */
+int mmsbm_hip_index_array(mmsbm_hip_ctx *ctx, int which, int32_t *out, int64_t capacity, int64_t *count);
 
 /* ---- parameters (device resident between calls) ---------------------------------- */
 int mmsbm_hip_set_params(mmsbm_hip_ctx *ctx, const double *theta, const double *eta,
@@ -399,7 +410,8 @@ int mmsbm_hip_set_option(mmsbm_hip_ctx *ctx, const char *name, double value);
  * list of that pass uses, 1 = off), "items_pairs" / "items_users" (work items, 0 = segments as
  * they are), "splits_pairs" / "splits_users" (segments cut into pieces), "fused_split" (bit 0 / 1: whole-segment lists of
  * the two-launch form built for the pair / user side), "item_grid" (1: at least half of the (item, rating) combinations
- * occur and R <= 16, so the item sums walk a fixed-width grid of pair ids; 0: the items' pair lists), "chunk_pairs" (pairs per pair-stage workgroup at most), "n_chunks"
+ * occur and R <= 16, so the item sums walk a fixed-width grid of pair ids; 0: the items' pair lists), "gpu_layout" (1: the
+ * index's sorts ran on the device -- 100,000 triples and more, or MMSBM_HIP_GPU_LAYOUT=1, and ratings x items below 2^31 --, 0: on the host), "chunk_pairs" (pairs per pair-stage workgroup at most), "n_chunks"
  * (pair-stage workgroups = slabs, padding included), "a_chunks" (workgroups of the matrix-core A launch when it walks
  * runs of its own; 0: the T + S launch's list serves) and "wide" (1: K, L beyond the 64-pair LDS stage -- the vector form of the pair stage is then the plain
  * wide-row kernels; they run when "mfma" reads 0, the blocked matrix-core kernels when it reads 2). */

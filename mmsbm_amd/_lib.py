@@ -32,6 +32,7 @@ SIGNATURES = {
     "mmsbm_hip_destroy": (C.c_int, [C.c_void_p]),
     "mmsbm_hip_dims": (C.c_int, [C.c_void_p, c_i64p]),
     "mmsbm_hip_degrees": (C.c_int, [C.c_void_p, c_i64p, c_i64p]),
+    "mmsbm_hip_index_array": (C.c_int, [C.c_void_p, C.c_int, c_i32p, C.c_int64, c_i64p]),
     "mmsbm_hip_set_params": (C.c_int, [C.c_void_p, c_f64p, c_f64p, c_f64p]),
     "mmsbm_hip_get_params": (C.c_int, [C.c_void_p, c_f64p, c_f64p, c_f64p]),
     "mmsbm_hip_init_params": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), c_f64p]),

@@ -104,6 +104,13 @@ def data_key(data):
     return (d.shape, d.dtype.str, _digest128(memoryview(d).cast("B")).hexdigest())
 
 
+LAYOUT_NAMES = ["pair_off", "pair_user", "pair_item", "rating_off", "user_off", "user_pair",
+                "item_off", "item_pairs", "item_deg", "chunk_off", "chunks", "mv_chunks",
+                "pair_items", "user_items", "pair_splits", "user_splits"]       # mmsbm_hip_layout_array: which = position
+INDEX_ONLY_NAMES = ["item_grid", "lik_units", "mv_chunk_off"]                   # mmsbm_hip_index_array: 16, 17, 18
+RECORD_NAMES = frozenset(LAYOUT_NAMES[10:] + ["lik_units"])                     # arrays of 4-int records
+
+
 class HipEM:
     """Device-resident EM state for one (GPU, training set, K, L)."""
 
@@ -574,6 +581,20 @@ class HipEM:
         """0 eager launches (default), 1 replay a captured hipGraph of two iterations."""
         _lib.call("mmsbm_hip_set_graph_mode", self._h, int(mode))
 
+    def index_arrays(self):
+        """The index this context's kernels read (mmsbm_hip_index_array), read back from the device where it lives
+        there: the names of ``build_layout`` plus ``item_grid``, ``lik_units`` and ``mv_chunk_off``.  Internal terms:
+        in a swapped context the "users" are the caller's items."""
+        out = {}
+        for which, nm in enumerate(LAYOUT_NAMES + INDEX_ONLY_NAMES):
+            cnt = C.c_int64(0)
+            _lib.call("mmsbm_hip_index_array", self._h, which, None, 0, C.byref(cnt))
+            arr = np.empty(cnt.value, dtype=np.int32)
+            if cnt.value:
+                _lib.call("mmsbm_hip_index_array", self._h, which, _p(arr, C.c_int32), arr.size, C.byref(cnt))
+            out[nm] = arr.reshape(-1, 4) if nm in RECORD_NAMES else arr
+        return out
+
 
 def build_layout(data, n_users, n_items, n_ratings, target_chunks=1024, fused_caps=None):
     """Host-only: the sorted CSR layout the library uploads (dict of int32 arrays).  ``fused_caps = (pair cap, user
@@ -583,12 +604,9 @@ def build_layout(data, n_users, n_items, n_ratings, target_chunks=1024, fused_ca
     h = C.c_void_p()
     _lib.call("mmsbm_hip_layout_build", len(u), int(n_users), int(n_items), int(n_ratings),
               _p(u, C.c_int32), _p(i, C.c_int32), _p(r, C.c_int32), int(target_chunks), C.byref(h))
-    names = ["pair_off", "pair_user", "pair_item", "rating_off", "user_off", "user_pair",
-             "item_off", "item_pairs", "item_deg", "chunk_off", "chunks", "mv_chunks",
-             "pair_items", "user_items", "pair_splits", "user_splits"]
     out = {}
     try:
-        for which, nm in enumerate(names):
+        for which, nm in enumerate(LAYOUT_NAMES):
             cnt = C.c_int64(0)
             _lib.call("mmsbm_hip_layout_array", h, which, None, 0, C.byref(cnt))
             arr = np.empty(cnt.value, dtype=np.int32)

@@ -247,6 +247,7 @@ struct mmsbm_hip_ctx {
   int nt_out = 7;          // option "nt_out" (bits: 1 T and A rows, 2 theta' rows as non-temporal stores, 4 the segments' own rows as non-temporal loads) where that pays (nt_on, launch.hpp)
   int ranges_pairs = 1, ranges_users = 1;  // XCD-local work lists: ranges the gathered table is cut into
   int n_cus = 256;
+  bool gpu_layout = false;  // the index's sorts ran on the device (build_index; option "gpu_layout")
   mmsbm::Layout lay;  // host copy (degrees, sizes)
   DevBuf<int32_t> pair_off, pair_user, pair_item, user_off, user_pair, item_off, item_pairs,
       item_deg, mv_chunk_off, orig_u, orig_i, orig_r;

@@ -15,7 +15,7 @@
 // The radix sorts and the scan are rocPRIM device primitives (rocprim::radix_sort_keys / _pairs,
 // rocprim::inclusive_scan: library calls for a library job -- this is set-up work outside the EM loop,
 // not one of the hot kernels); the kernels around them are below.  The result is IDENTICAL to layout.hpp's (same orders, same tie rules: both
-// sorts are stable), checked by tests on the GPU box.
+// sorts are stable), checked array by array on the GPU by tests/test_gpu_index.py.
 #pragma once
 #include <hip/hip_runtime.h>
 

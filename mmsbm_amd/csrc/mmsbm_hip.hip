@@ -840,6 +840,7 @@ int mmsbm_hip_create(int device, int64_t n_obs, int32_t n_users, int32_t n_items
     lap("checks");
     open_device(c.get());
     const bool gpu_layout = build_index(c.get(), knobs, iu, ii, rating, lap);
+    c->gpu_layout = gpu_layout;
     const std::vector<mmsbm::Chunk> units64 =
         apply_pair_plan(c.get(), plan_pair_forms(shape, c->lay.n_pairs, c->n_cus, knobs.no_mfma, knobs.mfma_chunk));
     build_range_worklists(c.get(), knobs, gpu_layout);
@@ -887,6 +888,56 @@ int mmsbm_hip_degrees(const mmsbm_hip_ctx *ctx, int64_t *d_user, int64_t *d_item
         du[u] = std::max<int64_t>(L.user_off[u + 1] - L.user_off[u], 1);
     if (di)
       for (int i = 0; i < L.n_items; ++i) di[i] = std::max<int64_t>(L.item_deg[i], 1);
+  });
+}
+
+// which: 0 .. 15 as mmsbm_hip_layout_array, 16 item_grid, 17 lik_units, 18 mv_chunk_off.  What has a device buffer is
+// read back from it (the device-built pair_user / user_pair exist nowhere else); rating_off, chunk_off and chunks are
+// host-only members of the context.
+int mmsbm_hip_index_array(mmsbm_hip_ctx *ctx, int which, int32_t *out, int64_t capacity, int64_t *count) {
+  return guarded([&] {
+    if (!ctx || !count) throw std::invalid_argument("null argument");
+    const mmsbm::Layout &L = ctx->lay;
+    const int32_t *host = nullptr;
+    const void *dev = nullptr;
+    size_t n = 0;  // in int32
+    auto from_dev = [&](const auto &buf) {
+      dev = buf.ptr;
+      n = buf.count * (sizeof(*buf.ptr) / sizeof(int32_t));
+    };
+    switch (which) {
+      case 0: from_dev(ctx->pair_off); break;
+      case 1: from_dev(ctx->pair_user); break;
+      case 2: from_dev(ctx->pair_item); break;
+      case 3: host = L.rating_off.data(); n = L.rating_off.size(); break;
+      case 4: from_dev(ctx->user_off); break;
+      case 5: from_dev(ctx->user_pair); break;
+      case 6: from_dev(ctx->item_off); break;
+      case 7: from_dev(ctx->item_pairs); break;
+      case 8: from_dev(ctx->item_deg); break;
+      case 9: host = L.chunk_off.data(); n = L.chunk_off.size(); break;
+      case 10: host = reinterpret_cast<const int32_t *>(L.chunks.data()); n = L.chunks.size() * 4; break;
+      case 11: from_dev(ctx->mv_chunks); break;
+      case 12: from_dev(ctx->pair_items); break;
+      case 13: from_dev(ctx->user_items); break;
+      case 14: from_dev(ctx->pair_splits); break;
+      case 15: from_dev(ctx->user_splits); break;
+      case 16: from_dev(ctx->item_grid); break;
+      case 17: from_dev(ctx->lik_units); break;
+      case 18: from_dev(ctx->mv_chunk_off); break;
+      default: throw std::invalid_argument("unknown index array");
+    }
+    *count = static_cast<int64_t>(n);
+    if (!out) return;
+    if (capacity < *count) throw std::invalid_argument("buffer too small");
+    if (n == 0) return;
+    if (host) {
+      std::memcpy(out, host, sizeof(int32_t) * n);
+      return;
+    }
+    use_device(ctx);
+    HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    HIP_CHECK(hipMemcpy(out, dev, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
   });
 }
 
@@ -1878,6 +1929,7 @@ int mmsbm_hip_get_option(const mmsbm_hip_ctx *ctx, const char *name, double *val
     else if (key == "splits_users") *value = static_cast<double>(ctx->lay.user_work.splits.size());
     else if (key == "fused_split") *value = (ctx->fs_pairs ? 1 : 0) + (ctx->fs_users ? 2 : 0);  // read-only: whole-segment lists built (1 pair side, 2 user side)
     else if (key == "item_grid") *value = ctx->item_grid.count ? 1 : 0;  // read-only: item_sum walks the fixed-width grid of pair ids (upload_item_grid)
+    else if (key == "gpu_layout") *value = ctx->gpu_layout ? 1 : 0;  // read-only: the index's sorts ran on the device (build_index)
     else throw std::invalid_argument("unknown option: " + key);
   });
 }

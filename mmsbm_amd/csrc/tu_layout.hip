@@ -133,6 +133,19 @@ void sort_stage(hipStream_t s, int64_t n_obs, int32_t n_users, int32_t n_items, 
   const int64_t n = n_obs;
   const uint64_t key_space = static_cast<uint64_t>(n_ratings) * static_cast<uint64_t>(n_items);
   if (key_space >= (uint64_t(1) << 31)) throw std::invalid_argument("ratings x items must be below 2^31");
+  if (n == 0) {
+    // an empty training set: a grid of zero workgroups is no launch but an error, so nothing is launched; the
+    // offsets are those of layout.hpp's builder (all zero, the right lengths)
+    L.pair_off.assign(1, 0);
+    L.rating_off.assign(static_cast<size_t>(n_ratings) + 1, 0);
+    L.user_off.assign(static_cast<size_t>(n_users) + 1, 0);
+    L.item_off.assign(static_cast<size_t>(n_items) + 1, 0);
+    L.item_deg.assign(static_cast<size_t>(n_items), 0);
+    Buf<int32_t> pair_user(0), user_pair(0);
+    dev.pair_user = pair_user.release();
+    dev.user_pair = user_pair.release();
+    return;
+  }
   int pk_bits = 1;
   while ((uint64_t(1) << pk_bits) < key_space) ++pk_bits;
   int user_bits = 1;
@@ -217,7 +230,7 @@ std::vector<int32_t> range_cuts(hipStream_t s, const std::vector<int32_t> &off, 
   const int32_t n_seg = static_cast<int32_t>(off.size()) - 1;
   const int64_t total = static_cast<int64_t>(n_seg) * (n_ranges + 1);
   std::vector<int32_t> out;
-  if (total <= 0) return out;
+  if (n_seg <= 0 || n_ranges < 1) return out;  // (no segment -- no pair of an empty training set --: nothing to launch)
   Buf<int32_t> d_off(off.size()), d_cuts(static_cast<size_t>(total));
   check(hipMemcpyAsync(d_off.p, off.data(), off.size() * sizeof(int32_t), hipMemcpyHostToDevice, s), "offsets");
   LAUNCH(range_cuts_kernel, blocks_for(total), kThreads, 0, s, d_off.p, d_idx, n_seg, std::max(table_rows, 1), n_ranges, d_cuts.p);
