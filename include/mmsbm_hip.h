@@ -252,6 +252,36 @@ int mmsbm_hip_recommend_add_items(mmsbm_hip_ctx *ctx, int32_t n_new, const doubl
 int mmsbm_hip_recommend_top_pairs(mmsbm_hip_ctx *ctx, int64_t n_users, const int32_t *users, int32_t m,
                                   int32_t *out_users, int32_t *out_items, double *out_scores, int32_t *count);
 
+/* Item-side queries of the open recommend session (mmsbm_amd/csrc/audience.hpp): who should see an item.  items[0 ..
+ * n_items): ids in the session's catalogue (training items, and I .. I + n_new - 1 after recommend_add_items), any
+ * order, repeats allowed.  score_w(u, i) is bit for bit what query returns for the pair, in swapped and unswapped
+ * contexts; the pair (u, i) is left out exactly when query leaves i out for u (the training pairs while exclude_train
+ * is set, the seen lists of recommend_add_items always, a duplicate pair once), so candidates(i) = U - |distinct
+ * excluded users of i|.  The item -> users lists are the transpose of the session's lists, built by the first of these
+ * calls and again after recommend_add_items.  Both touch no slot, no EM state and no other session; the recommend
+ * session stays open and its later answers are bitwise unchanged.  MMSBM_E_INVALID: no session, no slot added, an id
+ * outside the catalogue, a null pointer where one is needed.
+ *
+ * query_items: the n best candidate users of each item; order: score descending, equal scores (exact fp64 equality)
+ * by ascending user id.  users / scores [n_items][n], row b holds counts[b] = min(n, candidates) entries, the rest
+ * -1 / -inf (scores, counts may be NULL).  A row depends on its item only.  n < 1: MMSBM_E_INVALID; n >
+ * MMSBM_HIP_RECOMMEND_MAX_N: MMSBM_E_UNSUPPORTED; MMSBM_E_TOOLARGE where the device memory a batch needs is not free.
+ * The kernels are query's own with the two tables exchanged; "recommend_ms" reads their device time. */
+int mmsbm_hip_recommend_query_items(mmsbm_hip_ctx *ctx, int64_t n_items, const int32_t *items, int32_t n,
+                                    int32_t *users, double *scores, int32_t *counts);
+/* audience: for each item every candidate user with score_w(u, i) >= min_score (finite; the comparison is made on the
+ * final score, the quotient by the number of slots), in ascending user id, as a CSR: offsets[n_items + 1] (always
+ * filled), item b's users[offsets[b] .. offsets[b + 1]) and their scores.  users == NULL: sizes only (scores ignored).
+ * users given and capacity < offsets[n_items]: MMSBM_E_TOOLARGE with offsets filled and nothing else written; the caller
+ * allocates and calls again.  No buffer of U x n_items scores exists: a fused kernel counts per (item, 128-user tile),
+ * a small kernel turns the counts into offsets, and the fused kernel runs again to write.  The result does not depend
+ * on how the work is split: options "audience_rows" (items per counting batch) and "audience_entries" (entries per
+ * writing batch at most; a larger item goes alone), 0: the library's choice, change time and memory only.
+ * "audience_ms" reads the device time of the call's kernels.  A non-finite min_score: MMSBM_E_INVALID;
+ * MMSBM_E_TOOLARGE also where the device memory of a batch is not free. */
+int mmsbm_hip_recommend_audience(mmsbm_hip_ctx *ctx, int64_t n_items, const int32_t *items, double min_score,
+                                 int64_t capacity, int64_t *offsets, int32_t *users, double *scores);
+
 /* ---- nearest items / users: the n most similar rows of one side (mmsbm_amd/csrc/similar.hpp) -------------------- */
 /* A session of its own beside the recommend session (either may be open while the other is):
  *   begin  side 0: items, 1: users (external sides).  Closes any earlier similarity session;

@@ -417,6 +417,35 @@ class HipEM:
                   _p(sc, C.c_double), C.byref(count))
         return ou, oi, sc, int(count.value)
 
+    def recommend_query_items(self, items, n):
+        """(users (M,n) int32 padded with -1, scores (M,n) padded with -inf, counts (M,)) for item ids of the open
+        session's catalogue: the n best candidate users of each -- score descending, equal scores by ascending user
+        id; the pair (u, i) is left out exactly when recommend_query leaves i out for u."""
+        i = _i32(items)
+        n = int(n)
+        users, scores, counts = self._query_out(len(i), n)
+        _lib.call("mmsbm_hip_recommend_query_items", self._h, len(i), _p(i, C.c_int32), n, _p(users, C.c_int32),
+                  _p(scores, C.c_double), _p(counts, C.c_int32))
+        return users, scores, counts
+
+    def recommend_audience(self, items, min_score, count_only=False, total=None):
+        """(offsets (M+1,) int64, users int32, scores): for each item id every candidate user whose score is >=
+        min_score, in ascending user id -- item b's are [offsets[b]:offsets[b + 1]].  A sizes call followed by a
+        filled call; with count_only only the first, and users / scores are None.  ``total``: offsets[-1] of an
+        earlier sizes call for the same request, which is then not made again."""
+        i = _i32(items)
+        offsets = np.zeros(len(i) + 1, dtype=np.int64)
+        args = (self._h, len(i), _p(i, C.c_int32), float(min_score))
+        if total is None or count_only:
+            _lib.call("mmsbm_hip_recommend_audience", *args, 0, _p(offsets, C.c_int64), None, None)
+            if count_only:
+                return offsets, None, None
+            total = int(offsets[-1])
+        users, scores = np.empty(total, dtype=np.int32), np.empty(total, dtype=np.float64)
+        _lib.call("mmsbm_hip_recommend_audience", *args, total, _p(offsets, C.c_int64), _p(users, C.c_int32),
+                  _p(scores, C.c_double))
+        return offsets, users, scores
+
     def recommend_end(self):
         _lib.call("mmsbm_hip_recommend_end", self._h)
 

@@ -109,6 +109,8 @@ struct RecSession {
   DevBuf<double> wk;                    // [slot][K][L]: each slot's W (recommend_query_theta folds caller rows)
   DevBuf<int32_t> seen_off, seen;       // per external user: its distinct excluded items, ascending (excl)
   std::vector<int32_t> seen_off_h;      // seen_off on the host (candidate counts of recommend_positions)
+  DevBuf<int32_t> by_item_off, by_item; // per item of the catalogue: its excluded users, ascending -- the transpose of
+  bool by_item_built = false;           // seen_off / seen, built by the first item-side query (audience.hpp)
   int slots = 0;                        // slots added
   int items = 0;                        // the session's catalogue: I, or I + n_new after recommend_add_items
   int rank = 0;
@@ -282,6 +284,9 @@ struct mmsbm_hip_ctx {
   float pos_last_ms = 0.f;                  // device time of the last recommend_positions (option "position_ms")
   float top_last_ms = 0.f;                  // device time of the last recommend_top_pairs (option "top_pairs_ms")
   int top_groups = 0;                       // option "top_pairs_groups": workgroups of gtop_fused_kernel (0: 2 per CU)
+  float aud_last_ms = 0.f;                  // device time of the last recommend_audience's kernels (option "audience_ms")
+  int64_t aud_rows = 0;                     // option "audience_rows": items per COUNT batch (0: the library's choice)
+  int64_t aud_entries = 0;                  // option "audience_entries": entries per WRITE batch at most (0: likewise)
   std::unique_ptr<mmsbm_hip_impl::SimSession> sm;  // the open similarity session; null: none
   float sim_last_ms = 0.f;                  // device time of the last similar_query's kernels (option "similar_ms")
   std::unique_ptr<mmsbm_hip_impl::OvlSession> ov;  // the open overlap session; null: none

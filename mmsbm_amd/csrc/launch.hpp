@@ -51,6 +51,11 @@ void recommend_add_items(mmsbm_hip_ctx *c, int32_t n_new, const double *eta, con
 // ... the m best pairs of the whole model (top_pairs.hpp): users ascending and distinct
 void recommend_top_pairs(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, int m, int32_t *out_users,
                          int32_t *out_items, double *out_scores, int32_t *count);
+// ... item-side queries of the session (audience.hpp): item ids inside the session's catalogue
+void recommend_query_items(mmsbm_hip_ctx *c, int64_t n_items, const int32_t *items, int n, int32_t *users,
+                           double *scores, int32_t *counts);
+void recommend_audience(mmsbm_hip_ctx *c, int64_t n_items, const int32_t *items, double min_score, int64_t capacity,
+                        int64_t *offsets, int32_t *users, double *scores);
 void recommend_end(mmsbm_hip_ctx *c);
 // ... and nearest items / users (similar.hpp): the session of mmsbm_hip_similar_*, arguments checked
 void similar_begin(mmsbm_hip_ctx *c, int side);

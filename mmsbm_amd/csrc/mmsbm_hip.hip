@@ -1522,6 +1522,35 @@ int mmsbm_hip_recommend_top_pairs(mmsbm_hip_ctx *ctx, int64_t n_users, const int
   });
 }
 
+int mmsbm_hip_recommend_query_items(mmsbm_hip_ctx *ctx, int64_t n_items, const int32_t *items, int32_t n,
+                                    int32_t *users, double *scores, int32_t *counts) {
+  return guarded([&] {
+    require_session(ctx, "recommend_query_items");
+    if (n_items < 0) throw std::invalid_argument("negative n_items");
+    require_n(n);
+    if (n_items > 0 && (!items || !users)) throw std::invalid_argument("null argument");
+    for (int64_t m = 0; m < n_items; ++m)
+      if (items[m] < 0 || items[m] >= ctx->rc->items)
+        throw std::invalid_argument("recommend_query_items: item id out of range at row " + std::to_string(m));
+    recommend_query_items(ctx, n_items, items, n, users, scores, counts);
+  });
+}
+
+int mmsbm_hip_recommend_audience(mmsbm_hip_ctx *ctx, int64_t n_items, const int32_t *items, double min_score,
+                                 int64_t capacity, int64_t *offsets, int32_t *users, double *scores) {
+  return guarded([&] {
+    require_session(ctx, "recommend_audience");
+    if (n_items < 0) throw std::invalid_argument("negative n_items");
+    if (!std::isfinite(min_score)) throw std::invalid_argument("audience: min_score is not finite");
+    if (!offsets || (n_items > 0 && !items) || (users && !scores)) throw std::invalid_argument("null argument");
+    if (users && capacity < 0) throw std::invalid_argument("audience: negative capacity");
+    for (int64_t m = 0; m < n_items; ++m)
+      if (items[m] < 0 || items[m] >= ctx->rc->items)
+        throw std::invalid_argument("audience: item id out of range at row " + std::to_string(m));
+    recommend_audience(ctx, n_items, items, min_score, capacity, offsets, users, scores);
+  });
+}
+
 int mmsbm_hip_similar_begin(mmsbm_hip_ctx *ctx, int side) {
   return guarded([&] {
     if (!ctx) throw std::invalid_argument("null context");
@@ -1880,6 +1909,10 @@ int mmsbm_hip_set_option(mmsbm_hip_ctx *ctx, const char *name, double value) {
     } else if (key == "top_pairs_groups") {  // workgroups of gtop_fused_kernel (top_pairs.hpp); 0: the library's choice
       if (value < 0 || value > 4096 || value != std::floor(value)) throw std::invalid_argument("top_pairs_groups: 0 .. 4096");
       ctx->top_groups = static_cast<int>(value);
+    } else if (key == "audience_rows" || key == "audience_entries") {  // recommend_audience (audience.hpp): items per COUNT
+      // batch, entries per WRITE batch at most; 0: the library's choice.  Neither changes the answer
+      if (value < 0 || value > 2147483647.0 || value != std::floor(value)) throw std::invalid_argument(key + ": 0 .. 2^31 - 1");
+      (key == "audience_rows" ? ctx->aud_rows : ctx->aud_entries) = static_cast<int64_t>(value);
     } else if (key == "a_units") {  // 64-pair units per workgroup of the matrix-core A launch; 0: the library's own balance
       if (value < 0 || value > kMfmaChunkPairs / kUnitPairs) throw std::invalid_argument("a_units: 0 .. 16");
       use_device(ctx);
@@ -1913,6 +1946,9 @@ int mmsbm_hip_get_option(const mmsbm_hip_ctx *ctx, const char *name, double *val
     else if (key == "overlap_ms") *value = ctx->ovl_last_ms;   // read-only: device time of the last overlap_query
     else if (key == "heldout_ms") *value = ctx->hold_last_ms;  // read-only: device time of the last heldout_eval / heldout_add
     else if (key == "top_pairs_groups") *value = ctx->top_groups;
+    else if (key == "audience_ms") *value = ctx->aud_last_ms;  // read-only: device time of the last recommend_audience
+    else if (key == "audience_rows") *value = static_cast<double>(ctx->aud_rows);
+    else if (key == "audience_entries") *value = static_cast<double>(ctx->aud_entries);
     else if (key == "launches") *value = use_fused(ctx) ? 2 : 4;  // read-only: launches per iteration at the current slot count
     else if (key == "wide") *value = ctx->pp.wide;
     else if (key == "lik_fast") *value = ctx->lik_mode;

@@ -2,12 +2,15 @@
 // training items of every user, the per-slot prologue, the batches of a query and the choice of the item split -- and
 // of nearest items / users (similar.hpp), whose queries share the batches and the selection; and the m best pairs of
 // the whole model (top_pairs.hpp), a query of the recommend session with kernels of its own; and the overlap of the
-// restarts' groups (overlap.hpp), whose session copies a slot's rows with the recommend session's rec_fold_kernel
+// restarts' groups (overlap.hpp), whose session copies a slot's rows with the recommend session's rec_fold_kernel; and
+// the item-side queries of the recommend session (audience.hpp): the n best users of an item through the same batches
+// and selection, and the audience of an item above a bar through a fused kernel of its own
 #include "prelude.hpp"
 #include "recommend.hpp"
 #include "similar.hpp"
 #include "overlap.hpp"
 #include "top_pairs.hpp"
+#include "audience.hpp"
 
 #include <climits>
 
@@ -18,6 +21,8 @@ namespace {
 constexpr size_t kRecBatchBytes = size_t(128) << 20;  // score buffer of one batch of users (stays in the 256 MB MALL)
 constexpr int kRecMinPerPart = 1024;                   // items a selecting wave gets at least
 constexpr int kPosMinPerPart = 2048;                   // items a counting workgroup gets at least
+constexpr size_t kAudTableBytes = size_t(64) << 20;    // recommend_audience: the (row, user tile) counts of one batch
+constexpr int64_t kAudEntries = int64_t(16) << 20;     // ... and the entries of one WRITE batch (12 bytes each)
 
 }  // namespace
 
@@ -158,6 +163,9 @@ void recommend_add_items(mmsbm_hip_ctx *c, int32_t n_new, const double *eta, con
   HIP_CHECK(hipStreamSynchronize(st));
   rc.y.swap(ny);
   rc.items = NI;
+  rc.by_item_off.release();  // (the item -> users lists follow the session's lists and catalogue: built again on use)
+  rc.by_item.release();
+  rc.by_item_built = false;
 }
 
 namespace {
@@ -445,6 +453,174 @@ void recommend_top_pairs(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users
     out_items[k] = static_cast<int32_t>(hk[static_cast<size_t>(k)] & 0xffffffffu);
     out_scores[k] = hs[static_cast<size_t>(k)];
   }
+}
+
+// ---- item-side queries (audience.hpp) -----------------------------------------------------------------------------------
+namespace {
+
+// The item -> users lists of the session: the transpose of seen_off / seen, so each item's users are ascending and
+// distinct by construction.  Built by the first item-side query, dropped by recommend_add_items.
+void rec_item_lists(mmsbm_hip_ctx *c) {
+  RecSession &rc = *c->rc;
+  if (!rc.excl || rc.by_item_built) return;
+  const int U = c->ext_users, NI = rc.items;
+  hipStream_t st = c->stream;
+  const size_t n = static_cast<size_t>(rc.seen_off_h[U]);
+  std::vector<int32_t> seen(n);
+  if (n > 0) HIP_CHECK(hipMemcpyAsync(seen.data(), rc.seen.ptr, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipStreamSynchronize(st));
+  std::vector<int32_t> off(static_cast<size_t>(NI) + 1, 0), user(n);
+  for (size_t e = 0; e < n; ++e) ++off[static_cast<size_t>(seen[e]) + 1];
+  for (int i = 0; i < NI; ++i) off[i + 1] += off[i];
+  std::vector<int32_t> at(off.begin(), off.end() - 1);
+  for (int u = 0; u < U; ++u)  // (users ascending: so is every item's list)
+    for (int32_t e = rc.seen_off_h[u]; e < rc.seen_off_h[u + 1]; ++e) user[static_cast<size_t>(at[seen[e]]++)] = u;
+  require_free_mem((off.size() + n) * sizeof(int32_t), "recommend: the items' excluded users");
+  DevBuf<int32_t> d_off, d_user;
+  d_off.upload(off, st);
+  d_user.upload(user, st);
+  HIP_CHECK(hipStreamSynchronize(st));  // (host vectors are locals)
+  rc.by_item_off.swap(d_off);
+  rc.by_item.swap(d_user);
+  rc.by_item_built = true;
+}
+
+// rec_score_batch with the sides exchanged: the scores of one batch of nb items ib (device ids, rows of the session's
+// item table) against every user into sc [nb][U]; ex_off / ex (device, indexed by item id): the users set to -inf, or
+// null.  fma is commutative in its factors: sc[b][u] is bit for bit the score rec_score_batch gives (u, ib[b]).
+void rec_score_items_batch(mmsbm_hip_ctx *c, const int32_t *ib, int nb, const int32_t *ex_off, const int32_t *ex,
+                           double *sc) {
+  const RecSession &rc = *c->rc;
+  const int U = c->ext_users, rank = rc.rank, S = rc.slots;
+  if (U == 0) return;
+  hipStream_t st = c->stream;
+  const dim3 g(static_cast<unsigned>((U + kRecTile - 1) / kRecTile), static_cast<unsigned>((nb + kRecTile - 1) / kRecTile));
+  LAUNCH(rec_score_kernel, g, kBlock, 0, st, rc.y.ptr, static_cast<size_t>(rc.items) * rank, rc.x.ptr,
+         static_cast<size_t>(U) * rank, ib, nb, U, rank, S, sc, static_cast<size_t>(U));
+  if (ex_off) LAUNCH(rec_exclude_kernel, nb, kBlock, 0, st, ib, ex_off, ex, sc, static_cast<size_t>(U));
+}
+
+}  // namespace
+
+void recommend_query_items(mmsbm_hip_ctx *c, int64_t n_items, const int32_t *items, int n, int32_t *users,
+                           double *scores, int32_t *counts) {
+  use_device(c);
+  rec_item_lists(c);
+  const RecSession &rc = *c->rc;
+  const int32_t *ex_off = rc.excl ? rc.by_item_off.ptr : nullptr, *ex = rc.by_item.ptr;
+  top_n_run(c, c->ext_users, n_items, items, n, "recommend: a batch of items",
+            [&](const int32_t *ib, int nb, double *sc) { rec_score_items_batch(c, ib, nb, ex_off, ex, sc); },
+            &c->rc_last_ms, users, scores, counts);
+}
+
+void recommend_audience(mmsbm_hip_ctx *c, int64_t n_items, const int32_t *items, double min_score, int64_t capacity,
+                        int64_t *offsets, int32_t *users, double *scores) {
+  use_device(c);
+  rec_item_lists(c);
+  const RecSession &rc = *c->rc;
+  std::fill(offsets, offsets + n_items + 1, int64_t(0));
+  c->aud_last_ms = 0.f;
+  const int U = c->ext_users, rank = rc.rank, S = rc.slots;
+  if (n_items == 0 || U == 0) return;
+  hipStream_t st = c->stream;
+  const int64_t n_ut = (static_cast<int64_t>(U) + kRecTile - 1) / kRecTile;
+  // items per COUNT batch: whole 128-row tiles while the batch's counts stay within kAudTableBytes
+  int64_t rb = c->aud_rows;
+  if (rb <= 0) rb = std::max<int64_t>(kRecTile, static_cast<int64_t>(kAudTableBytes / sizeof(int32_t)) / n_ut / kRecTile * kRecTile);
+  rb = std::min(rb, n_items);
+  const size_t table = static_cast<size_t>(rb) * n_ut;
+  require_free_mem(table * 4 + static_cast<size_t>(n_items) * 8 + static_cast<size_t>(rb) * 8,
+                   "audience: the counts of a batch of items");
+  DevBuf<int32_t> di, cnt, tot;
+  di.alloc(n_items);
+  cnt.alloc(table);
+  tot.alloc(n_items);
+  HIP_CHECK(hipMemcpyAsync(di.ptr, items, sizeof(int32_t) * n_items, hipMemcpyHostToDevice, st));
+  const int32_t *ex_off = rc.excl ? rc.by_item_off.ptr : nullptr, *ex = rc.by_item.ptr;
+  const size_t xs = static_cast<size_t>(rc.items) * rank, ys = static_cast<size_t>(U) * rank;
+  // tiles are dealt to at most 8 workgroups per CU (what the staging tiles' LDS allows twice over)
+  auto groups = [&](int nb) {
+    return static_cast<unsigned>(std::min<int64_t>(n_ut * ((nb + kRecTile - 1) / kRecTile), 8LL * c->n_cus));
+  };
+  // COUNT + offsets of rows [r0, r0 + nb): cnt [user tile][nb], tot[r0 ...]
+  auto count_batch = [&](int64_t r0, int nb) {
+    LAUNCH(aud_tile_kernel<false>, groups(nb), kBlock, 0, st, rc.y.ptr, xs, rc.x.ptr, ys, di.ptr + r0, nb, U, rank, S,
+           ex_off, ex, min_score, cnt.ptr, static_cast<size_t>(nb), nullptr, int64_t(0), nullptr, nullptr, int64_t(0));
+    LAUNCH(aud_offsets_kernel, static_cast<unsigned>((nb + kBlock - 1) / kBlock), kBlock, 0, st, cnt.ptr,
+           static_cast<size_t>(nb), static_cast<int>(n_ut), nb, tot.ptr + r0);
+  };
+  float ms = 0.f;  // device time of the call's kernels (option "audience_ms")
+  std::vector<int32_t> ht(static_cast<size_t>(n_items));
+  {
+    EventPair ev;
+    ev.start(st);
+    for (int64_t r0 = 0; r0 < n_items; r0 += rb) count_batch(r0, static_cast<int>(std::min(rb, n_items - r0)));
+    HIP_CHECK(hipGetLastError());
+    ev.stop(st);
+    HIP_CHECK(hipMemcpyAsync(ht.data(), tot.ptr, sizeof(int32_t) * n_items, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    ms += ev.ms();
+  }
+  int64_t largest = 0;
+  for (int64_t b = 0; b < n_items; ++b) {
+    offsets[b + 1] = offsets[b] + ht[static_cast<size_t>(b)];
+    largest = std::max<int64_t>(largest, ht[static_cast<size_t>(b)]);
+  }
+  c->aud_last_ms = ms;
+  const int64_t total = offsets[n_items];
+  if (!users || total == 0) return;
+  if (capacity < total)
+    throw ApiError(MMSBM_E_TOOLARGE, "audience: " + std::to_string(total) + " entries, room for " + std::to_string(capacity));
+  // WRITE: runs of rows whose entries stay under the cap (a larger row goes alone), inside the COUNT batches; a batch's
+  // counts are formed again unless the request was one batch, whose offsets are still there
+  const int64_t cap = c->aud_entries > 0 ? c->aud_entries : kAudEntries;
+  const int64_t out_cap = std::min(total, std::max(cap, largest));
+  require_free_mem(static_cast<size_t>(out_cap) * 12 + static_cast<size_t>(rb) * 8, "audience: the entries of a batch of items");
+  DevBuf<int32_t> ou;
+  DevBuf<double> os;
+  DevBuf<int64_t> rbase;
+  ou.alloc(static_cast<size_t>(out_cap));
+  os.alloc(static_cast<size_t>(out_cap));
+  rbase.alloc(static_cast<size_t>(rb));
+  const bool one_batch = rb >= n_items;
+  std::vector<int64_t> hb(static_cast<size_t>(rb));
+  for (int64_t r0 = 0; r0 < n_items; r0 += rb) {
+    const int nb = static_cast<int>(std::min(rb, n_items - r0));
+    if (offsets[r0 + nb] == offsets[r0]) continue;
+    for (int j = 0; j < nb; ++j) hb[static_cast<size_t>(j)] = offsets[r0 + j] - offsets[r0];
+    HIP_CHECK(hipMemcpyAsync(rbase.ptr, hb.data(), sizeof(int64_t) * nb, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipStreamSynchronize(st));  // (hb is written again for the next batch)
+    if (!one_batch) {
+      EventPair ev;
+      ev.start(st);
+      count_batch(r0, nb);
+      ev.stop(st);
+      HIP_CHECK(hipStreamSynchronize(st));
+      ms += ev.ms();
+    }
+    for (int s0 = 0; s0 < nb;) {
+      int64_t e = ht[static_cast<size_t>(r0 + s0)];
+      int s1 = s0 + 1;
+      while (s1 < nb && e + ht[static_cast<size_t>(r0 + s1)] <= cap) e += ht[static_cast<size_t>(r0 + s1++)];
+      if (e > 0) {
+        const int ns = s1 - s0;
+        EventPair ev;
+        ev.start(st);
+        LAUNCH(aud_tile_kernel<true>, groups(ns), kBlock, 0, st, rc.y.ptr, xs, rc.x.ptr, ys, di.ptr + r0 + s0, ns, U, rank,
+               S, ex_off, ex, min_score, cnt.ptr + s0, static_cast<size_t>(nb), rbase.ptr + s0, hb[static_cast<size_t>(s0)],
+               ou.ptr, os.ptr, out_cap);
+        HIP_CHECK(hipGetLastError());
+        ev.stop(st);
+        const int64_t o = offsets[r0 + s0];
+        HIP_CHECK(hipMemcpyAsync(users + o, ou.ptr, sizeof(int32_t) * e, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipMemcpyAsync(scores + o, os.ptr, sizeof(double) * e, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        ms += ev.ms();
+      }
+      s0 = s1;
+    }
+  }
+  c->aud_last_ms = ms;
 }
 
 void recommend_end(mmsbm_hip_ctx *c) { c->rc.reset(); }

@@ -421,6 +421,73 @@ class MMSBM:
                 ctx.recommend_add()
             return self._top_n_frame(lambda b, e: ctx.recommend_query(ids[b:e], n), n, labels, item_labels)
 
+    def recommend_users(self, items=None, n=10, exclude_seen=True, weights=None):
+        """The ``n`` best users per item -- who should see this item -- scored on the device: ``recommend`` from the
+        item's side.  Scores as in ``recommend`` (the same numbers, bit for bit); candidates are all training users,
+        without the users that have the item in the training data when ``exclude_seen``.  Order: score descending,
+        equal scores by ascending encoded user id.
+
+        Returns a DataFrame with columns ``items``, ``users``, ``score``, ``rank`` (1 = best), items in request order
+        (``items=None``: every training item), labels as ``recommend`` returns them.  The model's stored predictions
+        and ``score()`` are left as they are."""
+        self._check_whole_model()
+        n, w = self._recommend_args(n, weights)
+        enc = self.data_handler
+        ids, labels = self._training_ids(items, "items")
+        user_labels = np.asarray(enc.user_labels(), dtype=object) if enc else None
+        ctx, restarts = self._restarts()
+        with self._recommend_session(ctx, w, exclude_seen):
+            for _ in restarts:
+                ctx.recommend_add()
+            return self._top_n_frame(lambda b, e: ctx.recommend_query_items(ids[b:e], n), n, labels, user_labels,
+                                     columns=("items", "users", "score"))
+
+    def audience(self, items=None, min_score=None, exclude_seen=True, weights=None, count_only=False):
+        """Every user whose score for an item reaches ``min_score`` (required, finite) -- a mailing list, the reach of a
+        campaign -- found on the device without a users x items score matrix.  Scores and candidates as in
+        ``recommend_users``; the bar is compared with the final score.
+
+        Returns a DataFrame with columns ``items``, ``users``, ``score``, ``rank`` (1 = the item's best user): items in
+        request order (``items=None``: every training item), within an item score descending, equal scores by
+        ascending encoded user id.  ``count_only=True``: columns ``items``, ``count``, one row per requested item.  The
+        model's stored predictions and ``score()`` are left as they are."""
+        import pandas as pd
+        self._check_whole_model()
+        if (isinstance(min_score, (bool, np.bool_)) or not isinstance(min_score, (int, float, np.integer, np.floating))
+                or not np.isfinite(min_score)):
+            raise ValueError(f"min_score must be a finite number, got {min_score!r}")
+        min_score, w = float(min_score), self._rating_weights(weights)
+        enc = self.data_handler
+        ids, labels = self._training_ids(items, "items")
+        user_labels = np.asarray(enc.user_labels(), dtype=object) if enc else None
+        ctx, restarts = self._restarts()
+        with self._recommend_session(ctx, w, exclude_seen):
+            for _ in restarts:
+                ctx.recommend_add()
+            sizes = np.diff(ctx.recommend_audience(ids, min_score, count_only=True)[0])
+            if count_only:
+                return pd.DataFrame({"items": labels, "count": sizes.astype(np.int64)})
+            parts = []
+            b = 0
+            while b < len(ids):  # pieces of at most RECOMMEND_BATCH_ROWS entries (a larger item goes alone)
+                e, total = b + 1, int(sizes[b])
+                while e < len(ids) and total + int(sizes[e]) <= self.RECOMMEND_BATCH_ROWS:
+                    total += int(sizes[e])
+                    e += 1
+                off, us, sc = ctx.recommend_audience(ids[b:e], min_score, total=total)
+                at = np.repeat(np.arange(b, e), np.diff(off))
+                order = np.lexsort((us, -sc, at))
+                us, sc, at = us[order], sc[order], at[order]
+                parts.append(pd.DataFrame({
+                    "items": labels[at] if len(at) else np.empty(0, dtype=object),
+                    "users": user_labels[us] if user_labels is not None else us.astype(np.int64),
+                    "score": sc,
+                    "rank": (np.arange(len(at)) - off[:-1][at - b] + 1).astype(np.int64)}))
+                b = e
+        if not parts:
+            return pd.DataFrame({"items": [], "users": [], "score": np.zeros(0), "rank": np.zeros(0, dtype=np.int64)})
+        return pd.concat(parts, ignore_index=True)
+
     TOP_PAIRS_MAX = 1024             # largest m of top_pairs (MMSBM_HIP_TOP_PAIRS_MAX_M)
 
     def top_pairs(self, m=100, users=None, exclude_seen=True, weights=None):
@@ -959,6 +1026,43 @@ class MMSBM:
                 seen = (np.concatenate([[0], np.cumsum(counts)]).astype(np.int64), rows[order, 0])
             ctx.recommend_add_items(np.stack(etas), seen)
             return self._top_n_frame(lambda b, e: ctx.recommend_query(ids[b:e], n), n, user_labels, item_labels)
+
+    def recommend_users_new_items(self, data, n=10, exclude_seen=True, weights=None, iterations=100, tol=None):
+        """``recommend_users`` for items that were not in the training data -- the cold-start audience of new items:
+        each restart scores with the eta its own ``fold_in_items`` gives them (same arguments), the scores are averaged
+        over the restarts.  Returns the frame ``recommend_users`` returns (items, users, score, rank), items in order
+        of first appearance in ``data``; ``exclude_seen`` leaves out the users that rated the item in ``data``.  An
+        item label of ``data`` that is also a training item is refused (ValueError)."""
+        import pandas as pd
+        self._check_whole_model()
+        n, w = self._recommend_args(n, weights)
+        iterations, tol = self._fold_args(iterations, tol)
+        rows, labels = self._encode_new(data, 1)
+        enc = self.data_handler
+        n_items = self.m + 1
+        if enc:
+            known = set(enc.item_labels())
+            clash = [x for x in labels.tolist() if x in known]
+            user_labels = np.asarray(enc.user_labels(), dtype=object)
+        else:
+            clash = [x for x in labels.tolist() if x < n_items]
+            user_labels = None
+        if clash:
+            raise ValueError(f"items of data are training items, so the frame would be ambiguous: {clash[:10]}")
+        n_new = len(labels)
+        ids = np.arange(n_items, n_items + n_new, dtype=np.int32)
+        ctx = self._ctx(self._device_list()[0])
+        with self._recommend_session(ctx, w, exclude_seen):
+            etas, iters = self._fold_runs(rows, n_new, iterations, tol, each=lambda c: c.recommend_add(), items=True)
+            self.fold_in_items_iterations = pd.DataFrame(np.stack(iters, 1), index=pd.Index(labels, name="items"))
+            seen = None
+            if exclude_seen:  # the training users that rated each new item
+                order = np.argsort(rows[:, 1], kind="stable")
+                counts = np.bincount(rows[:, 1], minlength=n_new)
+                seen = (np.concatenate([[0], np.cumsum(counts)]).astype(np.int64), rows[order, 0])
+            ctx.recommend_add_items(np.stack(etas), seen)
+            return self._top_n_frame(lambda b, e: ctx.recommend_query_items(ids[b:e], n), n, labels, user_labels,
+                                     columns=("items", "users", "score"))
 
     def _keep_best_run(self, best, res=None):
         """theta / eta / pr / likelihood of restart ``best`` become the model's stored objects
