@@ -171,7 +171,8 @@ int mmsbm_hip_prod_dist(mmsbm_hip_ctx *ctx, int64_t n_pairs, const int32_t *user
  *          running sum over restarts (in call order, which is numpy's order for
  *          np.array(rats).mean(axis=0)) and returns that restart's indicators;
  *   finish divides by the number of adds, returns the mean distribution (n_rows x R, may be
- *          NULL) and ITS indicators, and closes the session.
+ *          NULL) and ITS indicators, and closes the session: its device buffers are freed,
+ *          whether finish succeeds or not.
  * stats[6] = { rows kept (distribution not all zero), argmax == real, |argmax - real| <= 1,
  *              sum |argmax - real|, real == round(P . w), sum |P . w - real| }, from which
  * accuracy = [1]/[0], one_off = [2]/[0], mae = 1 - [4]/[0], s2 = [3], s2pond = [5]

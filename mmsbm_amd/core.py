@@ -37,6 +37,17 @@ def _csr(offsets, values, rows, name, noun):
     return off, val
 
 
+def _fetch_i32(symbol, *head):
+    """The int32 array of count-then-fill entry ``symbol(*head, out, capacity, count)``: asked for its length, then, if
+    it has any, filled."""
+    cnt = C.c_int64(0)
+    _lib.call(symbol, *head, None, 0, C.byref(cnt))
+    arr = np.empty(cnt.value, dtype=np.int32)
+    if cnt.value:
+        _lib.call(symbol, *head, _p(arr, C.c_int32), arr.size, C.byref(cnt))
+    return arr
+
+
 def normalize_with_self(p):
     """p[k,l,:] /= sum_r p[k,l,r]; zero rows stay zero (src/expectation_maximization.py:152-155).
     Host-side, used for the random initialisation only."""
@@ -348,14 +359,17 @@ class HipEM:
         return (np.empty((m, max(n, 0)), dtype=np.int32), np.empty((m, max(n, 0)), dtype=np.float64),
                 np.empty(m, dtype=np.int32))
 
+    def _top_n(self, symbol, ids, n):
+        """(ids (M,n) int32, values (M,n), counts (M,)) of top-N entry ``symbol`` for the M encoded ids ``ids``."""
+        q, n = _i32(ids), int(n)
+        out, values, counts = self._query_out(len(q), n)
+        _lib.call(symbol, self._h, len(q), _p(q, C.c_int32), n, _p(out, C.c_int32), _p(values, C.c_double),
+                  _p(counts, C.c_int32))
+        return out, values, counts
+
     def recommend_query(self, users, n):
         """(items (M,n) int32 padded with -1, scores (M,n) padded with -inf, counts (M,)) for encoded user ids."""
-        u = _i32(users)
-        n = int(n)
-        items, scores, counts = self._query_out(len(u), n)
-        _lib.call("mmsbm_hip_recommend_query", self._h, len(u), _p(u, C.c_int32), n, _p(items, C.c_int32),
-                  _p(scores, C.c_double), _p(counts, C.c_int32))
-        return items, scores, counts
+        return self._top_n("mmsbm_hip_recommend_query", users, n)
 
     def recommend_query_theta(self, theta, n, seen=None):
         """recommend_query for caller-given users: theta (S, M, K), one (M, K) block per added slot in add order.
@@ -421,12 +435,7 @@ class HipEM:
         """(users (M,n) int32 padded with -1, scores (M,n) padded with -inf, counts (M,)) for item ids of the open
         session's catalogue: the n best candidate users of each -- score descending, equal scores by ascending user
         id; the pair (u, i) is left out exactly when recommend_query leaves i out for u."""
-        i = _i32(items)
-        n = int(n)
-        users, scores, counts = self._query_out(len(i), n)
-        _lib.call("mmsbm_hip_recommend_query_items", self._h, len(i), _p(i, C.c_int32), n, _p(users, C.c_int32),
-                  _p(scores, C.c_double), _p(counts, C.c_int32))
-        return users, scores, counts
+        return self._top_n("mmsbm_hip_recommend_query_items", items, n)
 
     def recommend_audience(self, items, min_score, count_only=False, total=None):
         """(offsets (M+1,) int64, users int32, scores): for each item id every candidate user whose score is >=
@@ -462,12 +471,7 @@ class HipEM:
     def similar_query(self, ids, n):
         """(ids (M,n) int32 padded with -1, distance (M,n) padded with +inf, counts (M,)) for encoded ids of the
         session's side: the n nearest other rows of each, distance ascending, equal distances by ascending id."""
-        q = _i32(ids)
-        n = int(n)
-        out, dist, counts = self._query_out(len(q), n)
-        _lib.call("mmsbm_hip_similar_query", self._h, len(q), _p(q, C.c_int32), n, _p(out, C.c_int32),
-                  _p(dist, C.c_double), _p(counts, C.c_int32))
-        return out, dist, counts
+        return self._top_n("mmsbm_hip_similar_query", ids, n)
 
     def similar_end(self):
         _lib.call("mmsbm_hip_similar_end", self._h)
@@ -598,7 +602,8 @@ class HipEM:
         return float(us.value)
 
     def set_option(self, name, value):
-        """Named tuning knob of the library (currently "graph")."""
+        """Set a named option of the library (mmsbm_hip_set_option in include/mmsbm_hip.h lists them); a name that can
+        only be read is refused like an unknown one."""
         _lib.call("mmsbm_hip_set_option", self._h, name.encode(), float(value))
 
     def get_option(self, name):
@@ -616,11 +621,7 @@ class HipEM:
         in a swapped context the "users" are the caller's items."""
         out = {}
         for which, nm in enumerate(LAYOUT_NAMES + INDEX_ONLY_NAMES):
-            cnt = C.c_int64(0)
-            _lib.call("mmsbm_hip_index_array", self._h, which, None, 0, C.byref(cnt))
-            arr = np.empty(cnt.value, dtype=np.int32)
-            if cnt.value:
-                _lib.call("mmsbm_hip_index_array", self._h, which, _p(arr, C.c_int32), arr.size, C.byref(cnt))
+            arr = _fetch_i32("mmsbm_hip_index_array", self._h, which)
             out[nm] = arr.reshape(-1, 4) if nm in RECORD_NAMES else arr
         return out
 
@@ -636,22 +637,13 @@ def build_layout(data, n_users, n_items, n_ratings, target_chunks=1024, fused_ca
     out = {}
     try:
         for which, nm in enumerate(LAYOUT_NAMES):
-            cnt = C.c_int64(0)
-            _lib.call("mmsbm_hip_layout_array", h, which, None, 0, C.byref(cnt))
-            arr = np.empty(cnt.value, dtype=np.int32)
-            if cnt.value:
-                _lib.call("mmsbm_hip_layout_array", h, which, _p(arr, C.c_int32), arr.size,
-                          C.byref(cnt))
+            arr = _fetch_i32("mmsbm_hip_layout_array", h, which)
             out[nm] = arr.reshape(-1, 4) if which >= 10 else arr
         if fused_caps is not None:
             for side, (key, cap) in enumerate(zip(("fused_pairs", "fused_users"), fused_caps)):
                 rec = {}
                 for which, nm in enumerate(("units", "items", "splits", "chunks", "info")):
-                    cnt = C.c_int64(0)
-                    _lib.call("mmsbm_hip_layout_fused", h, side, int(cap), which, None, 0, C.byref(cnt))
-                    arr = np.empty(cnt.value, dtype=np.int32)
-                    if cnt.value:
-                        _lib.call("mmsbm_hip_layout_fused", h, side, int(cap), which, _p(arr, C.c_int32), arr.size, C.byref(cnt))
+                    arr = _fetch_i32("mmsbm_hip_layout_fused", h, side, int(cap), which)
                     rec[nm] = arr.reshape(-1, 4) if which < 4 else arr
                 rec["max_parts"], rec["built"] = int(rec["info"][0]), bool(rec["info"][1])
                 out[key] = rec

@@ -151,7 +151,16 @@ struct HoldSession {
   int64_t rows = 0;
   int n_blocks = 0;
   int part_slots = 0;                   // slots `part` and `out` are sized for
-  int added = 0;                        // heldout_add calls so far
+  int slots = 0;                        // slots added: heldout_add calls so far
+};
+
+// The predict/score session (mmsbm_hip_predict_begin .. finish): the test rows, internal sides, and the running sum of
+// the added slots' rating distributions.  Created by predict_begin, dropped whole by predict_begin and predict_finish.
+struct PredictSession {
+  DevBuf<int32_t> u, i, r;              // [rows]: internal user, internal item, true rating
+  DevBuf<double> sum, w, part;          // [rows][R] distributions added so far, the R rating weights, sums per workgroup
+  int64_t rows = 0;
+  int slots = 0;                        // slots added: predict_add calls so far
 };
 
 }  // namespace mmsbm_hip_impl
@@ -201,6 +210,11 @@ inline void sort_unique_groups(std::vector<int32_t> &off, std::vector<int32_t> &
   off.back() = w;
   val.resize(static_cast<size_t>(w));
 }
+
+// The serving calls whose kernels are timed (mmsbm_hip_ctx::last_ms), in the order of their "<name>_ms" options:
+// recommend_query / recommend_query_items, fold_in / fold_in_items, recommend_positions, recommend_top_pairs,
+// recommend_audience, similar_query, overlap_query, heldout_eval / heldout_add
+enum TimedCall { T_RECOMMEND = 0, T_FOLD_IN, T_POSITIONS, T_TOP_PAIRS, T_AUDIENCE, T_SIMILAR, T_OVERLAP, T_HELDOUT, T_COUNT };
 
 enum KernelId { K_SEG = 0, K_DENSE, K_ETAP, K_MATVEC_A, K_FUSED_PAIRS, K_FUSED_TAIL, K_COUNT };
 // The four launches of an iteration -- or, for small problems, the two of fused_small.hpp.
@@ -273,26 +287,16 @@ struct mmsbm_hip_ctx {
   int lik_mode = 2;                       // option "lik_fast": 0 log per element, 1 log tables, 2 a wave per pair where it applies
   int lik_g = 0;                          // option "lik_g": lanes per triple (0 = automatic)
   PinBuf pin;  // host staging for set_params / get_params / update_coefficients
-  // predict/score session (mmsbm_hip_predict_begin .. finish)
-  DevBuf<int32_t> ps_u, ps_i, ps_r;
-  DevBuf<double> ps_sum, ps_w, ps_part;
-  int64_t ps_rows = -1;  // -1: no session open
-  int ps_added = 0;
-  std::unique_ptr<mmsbm_hip_impl::RecSession> rc;  // the open recommend session; null: none
-  float rc_last_ms = 0.f;                   // device time of the last query's kernels (option "recommend_ms")
-  float fold_last_ms = 0.f;                 // device time of the last fold-in's kernels, either side ("fold_in_ms")
-  float pos_last_ms = 0.f;                  // device time of the last recommend_positions (option "position_ms")
-  float top_last_ms = 0.f;                  // device time of the last recommend_top_pairs (option "top_pairs_ms")
+  // the open sessions; null: none
+  std::unique_ptr<mmsbm_hip_impl::PredictSession> ps;  // predict / score
+  std::unique_ptr<mmsbm_hip_impl::RecSession> rc;      // recommend
+  std::unique_ptr<mmsbm_hip_impl::SimSession> sm;      // similarity
+  std::unique_ptr<mmsbm_hip_impl::OvlSession> ov;      // overlap
+  std::unique_ptr<mmsbm_hip_impl::HoldSession> ho;     // held-out
+  float last_ms[T_COUNT] = {};              // device time of the last call's kernels, per TimedCall (options "<name>_ms")
   int top_groups = 0;                       // option "top_pairs_groups": workgroups of gtop_fused_kernel (0: 2 per CU)
-  float aud_last_ms = 0.f;                  // device time of the last recommend_audience's kernels (option "audience_ms")
   int64_t aud_rows = 0;                     // option "audience_rows": items per COUNT batch (0: the library's choice)
   int64_t aud_entries = 0;                  // option "audience_entries": entries per WRITE batch at most (0: likewise)
-  std::unique_ptr<mmsbm_hip_impl::SimSession> sm;  // the open similarity session; null: none
-  float sim_last_ms = 0.f;                  // device time of the last similar_query's kernels (option "similar_ms")
-  std::unique_ptr<mmsbm_hip_impl::OvlSession> ov;  // the open overlap session; null: none
-  float ovl_last_ms = 0.f;                  // device time of the last overlap_query's kernels (option "overlap_ms")
-  std::unique_ptr<mmsbm_hip_impl::HoldSession> ho;  // the open held-out session; null: none
-  float hold_last_ms = 0.f;                 // device time of the last heldout_eval / heldout_add (option "heldout_ms")
   // snapshots (mmsbm_hip_snapshot_save / get): a second copy of theta, eta and p in the layout of theta[cur], eta[cur]
   // and p[cur], every slot's place in it filled by that slot's last save; allocated by the first save, dropped by set_slots
   DevBuf<double> snap_theta;
@@ -373,6 +377,7 @@ struct EventPair {
   } e0, e1;
   void start(hipStream_t s) { HIP_CHECK(hipEventRecord(e0.e, s)); }
   void stop(hipStream_t s) { HIP_CHECK(hipEventRecord(e1.e, s)); }
+  void wait() { HIP_CHECK(hipEventSynchronize(e1.e)); }   // the host waits for stop()'s point of the stream
   float ms() const {
     float v = 0.f;
     HIP_CHECK(hipEventElapsedTime(&v, e0.e, e1.e));

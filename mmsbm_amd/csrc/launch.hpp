@@ -56,18 +56,15 @@ void recommend_query_items(mmsbm_hip_ctx *c, int64_t n_items, const int32_t *ite
                            double *scores, int32_t *counts);
 void recommend_audience(mmsbm_hip_ctx *c, int64_t n_items, const int32_t *items, double min_score, int64_t capacity,
                         int64_t *offsets, int32_t *users, double *scores);
-void recommend_end(mmsbm_hip_ctx *c);
 // ... and nearest items / users (similar.hpp): the session of mmsbm_hip_similar_*, arguments checked
 void similar_begin(mmsbm_hip_ctx *c, int side);
 void similar_add(mmsbm_hip_ctx *c);  // the selected slot (the caller holds a OneSlot)
 void similar_query(mmsbm_hip_ctx *c, int64_t n_rows, const int32_t *ids, int n, int32_t *out_ids, double *distance,
                    int32_t *counts);
-void similar_end(mmsbm_hip_ctx *c);
 // ... and the overlap of the restarts' groups (overlap.hpp): the session of mmsbm_hip_overlap_*, arguments checked
 void overlap_begin(mmsbm_hip_ctx *c, int side);
 void overlap_add(mmsbm_hip_ctx *c);  // the selected slot (the caller holds a OneSlot)
 void overlap_query(mmsbm_hip_ctx *c, double *out);
-void overlap_end(mmsbm_hip_ctx *c);
 
 // tu_fold_in.hip -- fold new users (items_side: new items) into the selected slot's fitted eta (theta) and p
 // (fold_in.hpp), arguments checked; x0, x: theta0, theta (eta0, eta); items_side: item[m] in [0, n_new), user[m] in [0, U)
@@ -80,7 +77,6 @@ void heldout_begin(mmsbm_hip_ctx *c, int64_t n_rows, const int32_t *user, const 
 // the slots [first, first + n_slots): loglik[s] of each; add: also P into the running per-row sum (one slot)
 void heldout_eval(mmsbm_hip_ctx *c, int first, int n_slots, bool add, double *loglik);
 void heldout_mean(mmsbm_hip_ctx *c, double *mean_p, double *loglik);
-void heldout_end(mmsbm_hip_ctx *c);
 
 // dispatchers (mmsbm_hip.hip): the form the context's shape and options select
 void stage_dense(mmsbm_hip_ctx *c);

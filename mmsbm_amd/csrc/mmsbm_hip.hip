@@ -744,6 +744,157 @@ void upload_index(mmsbm_hip_ctx *c, const CreateKnobs &knobs, bool gpu_layout, c
   HIP_CHECK(hipStreamSynchronize(s));  // nothing of the caller's (or create's) host memory is still being read
 }
 
+
+// ---- the sessions' guards: one per question ------------------------------------------------------------------------
+// The open session of one kind (`held`: where the context keeps it; `kind`: "recommend", "predict" ...), or
+// "<kind>_begin has not been called"; with `what` (the entry asking) also at least one slot added to it, or
+// "<what> before any <kind>_add"
+template <class S>
+S &require_open(mmsbm_hip_ctx *ctx, std::unique_ptr<S> mmsbm_hip_ctx::*held, const char *kind, const char *what = nullptr) {
+  if (!ctx) throw std::invalid_argument("null context");
+  S *s = (ctx->*held).get();
+  if (!s) throw std::invalid_argument(std::string(kind) + "_begin has not been called");
+  if (what && s->slots == 0) throw std::invalid_argument(std::string(what) + " before any " + kind + "_add");
+  return *s;
+}
+
+// The four *_end entries: wait for the session's work, drop it.  `kind`: refuse when none is open (heldout_end)
+template <class S>
+int end_session(mmsbm_hip_ctx *ctx, std::unique_ptr<S> mmsbm_hip_ctx::*held, const char *kind = nullptr) {
+  return guarded([&] {
+    if (!ctx) throw std::invalid_argument("null context");
+    if (kind) require_open(ctx, held, kind);
+    use_device(ctx);
+    HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    (ctx->*held).reset();
+  });
+}
+
+// ids[0 .. n) in [0, top), or "<prefix> id out of range at row m"
+void require_ids(const int32_t *ids, int64_t n, int32_t top, const std::string &prefix) {
+  for (int64_t m = 0; m < n; ++m)
+    if (ids[m] < 0 || ids[m] >= top) throw std::invalid_argument(prefix + " id out of range at row " + std::to_string(m));
+}
+
+// The n of a top-N query of `who` ("recommend", "similar"), which returns `noun` ("items", "rows")
+void require_n(int32_t n, const char *who, const char *noun) {
+  if (n < 1) throw std::invalid_argument(std::string(who) + ": n must be at least 1");
+  if (n > MMSBM_HIP_RECOMMEND_MAX_N)
+    throw ApiError(MMSBM_E_UNSUPPORTED, std::string(who) + ": n = " + std::to_string(n) + " is beyond the " +
+                                            std::to_string(MMSBM_HIP_RECOMMEND_MAX_N) + " " + noun + " a query returns at most");
+}
+
+// ---- the options: one row per name.  get: its value now; set: null for a read-only name, else the value's check and
+// what setting it does.  mmsbm_hip_get_option and mmsbm_hip_set_option both walk this table and nothing else.
+struct Option {
+  const char *name;
+  double (*get)(const mmsbm_hip_ctx *);
+  void (*set)(mmsbm_hip_ctx *, double);
+};
+using Ctx = mmsbm_hip_ctx;
+// "audience_rows" / "audience_entries": 0 .. 2^31 - 1, whole
+void set_audience(int64_t &field, const char *name, double v) {
+  if (v < 0 || v > 2147483647.0 || v != std::floor(v)) throw std::invalid_argument(std::string(name) + ": 0 .. 2^31 - 1");
+  field = static_cast<int64_t>(v);
+}
+const Option kOptions[] = {
+    {"graph", [](const Ctx *c) -> double { return c->graph_mode; }, [](Ctx *c, double v) { c->graph_mode = v != 0.0; }},
+    // 0: the A launch through pair_block like every other shape
+    // (create() also requires unit runs of four -- big_chunk == 4 * kMvChunkPairs, plan_pair_forms -- and this option
+    // never has: with longer runs it turns on what create() left off.  Whether that is meant is open; both are as they were)
+    {"quad", [](const Ctx *c) -> double { return c->pp.quad_a; }, [](Ctx *c, double v) { c->pp.set_quad(v != 0.0); }},
+    // the pair stage on the matrix cores: 0 off, 1 on (one-block form if K, L <= 64, else the blocked form), 2 the
+    // blocked form whatever the shape
+    {"mfma", [](const Ctx *c) -> double { return c->pp.mfma ? 1.0 : (c->pp.mfma_big ? 2.0 : 0.0); },
+     [](Ctx *c, double v) { c->pp.set_mfma(v); }},
+    // 0: prod_dist / predict through the per-row kernels (R K L multiply-adds per row)
+    {"predict_fast", [](const Ctx *c) -> double { return c->predict_fast; }, [](Ctx *c, double v) { c->predict_fast = v != 0.0; }},
+    // two launches per iteration (small tiles, unsplit segments); any problem size
+    {"fused", [](const Ctx *c) -> double { return c->fused; },
+     [](Ctx *c, double v) {
+       if (v != 0.0 && !fused_possible(c)) throw std::invalid_argument("fused: not available for this shape / data");
+       c->fused = c->fused_forced = v != 0.0;
+     }},
+    // 0: plain stores for every output row; bits: 1 T and A rows, 2 theta' rows, 4 own-row loads.  Reads as what is in use
+    {"nt_out", [](const Ctx *c) -> double { return nt_on(c); },
+     [](Ctx *c, double v) {
+       if (v < 0 || v > 15) throw std::invalid_argument("nt_out: 0 .. 15");
+       c->nt_out = static_cast<int>(v);
+     }},
+    // device time of the last call's kernels (TimedCall, context.hpp)
+    {"recommend_ms", [](const Ctx *c) -> double { return c->last_ms[T_RECOMMEND]; }, nullptr},
+    {"fold_in_ms", [](const Ctx *c) -> double { return c->last_ms[T_FOLD_IN]; }, nullptr},
+    {"position_ms", [](const Ctx *c) -> double { return c->last_ms[T_POSITIONS]; }, nullptr},
+    {"similar_ms", [](const Ctx *c) -> double { return c->last_ms[T_SIMILAR]; }, nullptr},
+    {"top_pairs_ms", [](const Ctx *c) -> double { return c->last_ms[T_TOP_PAIRS]; }, nullptr},
+    {"overlap_ms", [](const Ctx *c) -> double { return c->last_ms[T_OVERLAP]; }, nullptr},
+    {"heldout_ms", [](const Ctx *c) -> double { return c->last_ms[T_HELDOUT]; }, nullptr},
+    {"audience_ms", [](const Ctx *c) -> double { return c->last_ms[T_AUDIENCE]; }, nullptr},
+    // workgroups of gtop_fused_kernel (top_pairs.hpp); 0: the library's choice
+    {"top_pairs_groups", [](const Ctx *c) -> double { return c->top_groups; },
+     [](Ctx *c, double v) {
+       if (v < 0 || v > 4096 || v != std::floor(v)) throw std::invalid_argument("top_pairs_groups: 0 .. 4096");
+       c->top_groups = static_cast<int>(v);
+     }},
+    // recommend_audience (audience.hpp): items per COUNT batch, entries per WRITE batch at most; 0: the library's choice.
+    // Neither changes the answer
+    {"audience_rows", [](const Ctx *c) -> double { return static_cast<double>(c->aud_rows); },
+     [](Ctx *c, double v) { set_audience(c->aud_rows, "audience_rows", v); }},
+    {"audience_entries", [](const Ctx *c) -> double { return static_cast<double>(c->aud_entries); },
+     [](Ctx *c, double v) { set_audience(c->aud_entries, "audience_entries", v); }},
+    {"launches", [](const Ctx *c) -> double { return use_fused(c) ? 2 : 4; }, nullptr},  // per iteration at the current slot count
+    {"wide", [](const Ctx *c) -> double { return c->pp.wide; }, nullptr},
+    // 0: a logarithm per element; 1: logarithm tables, a group of lanes per triple; 2: where it applies a wave per pair
+    // (lik_fact.hpp), else as 1
+    {"lik_fast", [](const Ctx *c) -> double { return c->lik_mode; },
+     [](Ctx *c, double v) {
+       if (v != 0.0 && v != 1.0 && v != 2.0) throw std::invalid_argument("lik_fast: 0, 1 or 2");
+       c->lik_mode = static_cast<int>(v);
+     }},
+    {"lik_g", [](const Ctx *c) -> double { return c->lik_g; },
+     [](Ctx *c, double v) {
+       const int g = static_cast<int>(v);
+       if (g != 0 && g != 1 && g != 2 && g != 4 && g != 8) throw std::invalid_argument("lik_g: 0, 1, 2, 4 or 8");
+       c->lik_g = g;
+     }},
+    {"ranges_pairs", [](const Ctx *c) -> double { return c->ranges_pairs; }, nullptr},  // XCD-local work lists,
+    {"ranges_users", [](const Ctx *c) -> double { return c->ranges_users; }, nullptr},  // ranges per pass (1 = off)
+    {"chunk_pairs", [](const Ctx *c) -> double { return c->pp.chunk_pairs; }, nullptr},  // pairs per pair-stage workgroup at most
+    {"n_chunks", [](const Ctx *c) -> double { return c->n_chunks; }, nullptr},  // pair-stage workgroups (= slabs), padding included
+    // 64-pair units per workgroup of the matrix-core A launch (reads 0: not on the matrix cores; set 0: the library's own balance)
+    {"a_units", [](const Ctx *c) -> double { return c->a_units; },
+     [](Ctx *c, double v) {
+       if (v < 0 || v > kMfmaChunkPairs / kUnitPairs) throw std::invalid_argument("a_units: 0 .. 16");
+       use_device(c);
+       HIP_CHECK(hipStreamSynchronize(c->stream));
+       build_a_runs(c, static_cast<int>(v));
+     }},
+    // workgroups of the matrix-core A launch when it walks runs of its own (0: the T + S launch's)
+    {"a_chunks", [](const Ctx *c) -> double { return c->n_a_chunks; }, nullptr},
+    {"items_pairs", [](const Ctx *c) -> double { return static_cast<double>(c->lay.pair_work.items.size()); }, nullptr},
+    {"items_users", [](const Ctx *c) -> double { return static_cast<double>(c->lay.user_work.items.size()); }, nullptr},
+    // segments cut into pieces
+    {"splits_pairs", [](const Ctx *c) -> double { return static_cast<double>(c->lay.pair_work.splits.size()); }, nullptr},
+    {"splits_users", [](const Ctx *c) -> double { return static_cast<double>(c->lay.user_work.splits.size()); }, nullptr},
+    // whole-segment lists built (1 pair side, 2 user side)
+    {"fused_split", [](const Ctx *c) -> double { return (c->fs_pairs ? 1 : 0) + (c->fs_users ? 2 : 0); }, nullptr},
+    // item_sum walks the fixed-width grid of pair ids (upload_item_grid)
+    {"item_grid", [](const Ctx *c) -> double { return c->item_grid.count ? 1 : 0; }, nullptr},
+    // the index's sorts ran on the device (build_index)
+    {"gpu_layout", [](const Ctx *c) -> double { return c->gpu_layout ? 1 : 0; }, nullptr},
+};
+const Option *find_option(const std::string &name) {
+  for (const Option &o : kOptions)
+    if (name == o.name) return &o;
+  return nullptr;
+}
+// A successful set drops the captured graphs: they hold the launches of the plan they were captured under
+void set_option(mmsbm_hip_ctx *ctx, const std::string &name, double value) {
+  const Option *o = find_option(name);
+  if (!o || !o->set) throw std::invalid_argument("unknown option: " + name);
+  o->set(ctx, value);
+  ctx->drop_graphs();
+}
 }  // namespace
 
 
@@ -1249,20 +1400,18 @@ int mmsbm_hip_prod_dist(mmsbm_hip_ctx *ctx, int64_t n_pairs, const int32_t *user
 namespace {
 void score_launch(mmsbm_hip_ctx *ctx, bool finish, double *stats) {
   const int n_stats = score_stats_count();
-  const bool fast = !finish && rows_fast_prepare(ctx, ctx->ps_rows);
+  PredictSession &ps = *ctx->ps;
+  const bool fast = !finish && rows_fast_prepare(ctx, ps.rows);
   const int per_block = fast ? kBlock / group_lanes(ctx->code_k) : kBlock;
-  const int64_t nb64 = (ctx->ps_rows + per_block - 1) / per_block;
-  const int nb = static_cast<int>(nb64);
-  if (ctx->ps_part.count < static_cast<size_t>(nb) * n_stats) ctx->ps_part.alloc(static_cast<size_t>(nb) * n_stats);
+  const int nb = static_cast<int>((ps.rows + per_block - 1) / per_block);
+  if (ps.part.count < static_cast<size_t>(nb) * n_stats) ps.part.alloc(static_cast<size_t>(nb) * n_stats);
   if (nb > 0 && fast)
-    rows_launch(ctx, 1, ctx->ps_u.ptr, ctx->ps_i.ptr, ctx->ps_r.ptr, ctx->ps_w.ptr, ctx->ps_sum.ptr, ctx->ps_part.ptr,
-                ctx->ps_rows, ctx->ps_added == 0 ? 1 : 0);
+    rows_launch(ctx, 1, ps.u.ptr, ps.i.ptr, ps.r.ptr, ps.w.ptr, ps.sum.ptr, ps.part.ptr, ps.rows, ps.slots == 0 ? 1 : 0);
   else if (nb > 0)
     score_rows_launch(ctx, finish);
   std::vector<double> part(static_cast<size_t>(nb) * n_stats);
   if (nb > 0)
-    HIP_CHECK(hipMemcpyAsync(part.data(), ctx->ps_part.ptr, sizeof(double) * part.size(),
-                             hipMemcpyDeviceToHost, ctx->stream));
+    HIP_CHECK(hipMemcpyAsync(part.data(), ps.part.ptr, sizeof(double) * part.size(), hipMemcpyDeviceToHost, ctx->stream));
   HIP_CHECK(hipStreamSynchronize(ctx->stream));
   for (int j = 0; j < n_stats; ++j) stats[j] = 0.0;
   for (int b = 0; b < nb; ++b)
@@ -1284,24 +1433,24 @@ int mmsbm_hip_predict_begin(mmsbm_hip_ctx *ctx, int64_t n_rows, const int32_t *u
       if (user[m] < 0 || user[m] >= ctx->ext_users || item[m] < 0 || item[m] >= ctx->ext_items ||
           rating[m] < 0 || rating[m] >= ctx->n_ratings)
         throw std::invalid_argument("predict: id out of range at row " + std::to_string(m));
-    use_device(ctx);  // (arguments are fine: from here on the previous session is gone)
-    ctx->ps_rows = -1;
+    use_device(ctx);
+    ctx->ps.reset();  // (arguments are fine: from here on the previous session is gone)
+    auto ps = std::make_unique<PredictSession>();
     const int32_t *iu = ctx->swapped ? item : user;
     const int32_t *ii = ctx->swapped ? user : item;
     hipStream_t s = ctx->stream;
-    ctx->ps_u.alloc(n_rows); ctx->ps_i.alloc(n_rows); ctx->ps_r.alloc(n_rows);
-    ctx->ps_sum.alloc(static_cast<size_t>(n_rows) * ctx->n_ratings);
-    ctx->ps_w.alloc(ctx->n_ratings);
+    ps->u.alloc(n_rows); ps->i.alloc(n_rows); ps->r.alloc(n_rows);
+    ps->sum.alloc(static_cast<size_t>(n_rows) * ctx->n_ratings);
+    ps->w.alloc(ctx->n_ratings);
     if (n_rows > 0) {
-      HIP_CHECK(hipMemcpyAsync(ctx->ps_u.ptr, iu, sizeof(int32_t) * n_rows, hipMemcpyHostToDevice, s));
-      HIP_CHECK(hipMemcpyAsync(ctx->ps_i.ptr, ii, sizeof(int32_t) * n_rows, hipMemcpyHostToDevice, s));
-      HIP_CHECK(hipMemcpyAsync(ctx->ps_r.ptr, rating, sizeof(int32_t) * n_rows, hipMemcpyHostToDevice, s));
+      HIP_CHECK(hipMemcpyAsync(ps->u.ptr, iu, sizeof(int32_t) * n_rows, hipMemcpyHostToDevice, s));
+      HIP_CHECK(hipMemcpyAsync(ps->i.ptr, ii, sizeof(int32_t) * n_rows, hipMemcpyHostToDevice, s));
+      HIP_CHECK(hipMemcpyAsync(ps->r.ptr, rating, sizeof(int32_t) * n_rows, hipMemcpyHostToDevice, s));
     }
-    HIP_CHECK(hipMemcpyAsync(ctx->ps_w.ptr, rating_weights, sizeof(double) * ctx->n_ratings,
-                             hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(ps->w.ptr, rating_weights, sizeof(double) * ctx->n_ratings, hipMemcpyHostToDevice, s));
     HIP_CHECK(hipStreamSynchronize(s));  // the caller's buffers are free again
-    ctx->ps_rows = n_rows;
-    ctx->ps_added = 0;
+    ps->rows = n_rows;
+    ctx->ps = std::move(ps);
   });
 }
 
@@ -1309,48 +1458,33 @@ int mmsbm_hip_predict_add(mmsbm_hip_ctx *ctx, double stats[6]) {
   return guarded([&] {
     require_params(ctx);
     if (!stats) throw std::invalid_argument("null stats");
-    if (ctx->ps_rows < 0) throw std::invalid_argument("predict_begin has not been called");
+    PredictSession &ps = require_open(ctx, &mmsbm_hip_ctx::ps, "predict");
     use_device(ctx);
     OneSlot one(ctx);
     score_launch(ctx, false, stats);
-    ctx->ps_added++;
+    ps.slots++;
   });
 }
 
 int mmsbm_hip_predict_finish(mmsbm_hip_ctx *ctx, double *mean_dist, double stats[6]) {
   return guarded([&] {
     if (!ctx || !stats) throw std::invalid_argument("null argument");
-    if (ctx->ps_rows < 0) throw std::invalid_argument("predict_begin has not been called");
-    if (ctx->ps_added < 1) throw std::invalid_argument("predict_finish before any predict_add");
+    const PredictSession &ps = require_open(ctx, &mmsbm_hip_ctx::ps, "predict", "predict_finish");
     use_device(ctx);
     OneSlot one(ctx);
-    const int64_t rows = ctx->ps_rows;
+    // the session is over on every way out of here, and its buffers go back: restart slots are sized from the free memory
+    struct Drop { mmsbm_hip_ctx *c; ~Drop() { c->ps.reset(); } } drop{ctx};
     score_launch(ctx, true, stats);
-    ctx->ps_rows = -1;  // the session is over whatever happens next
     ctx->btab.release();
-    if (mean_dist && rows > 0) {
-      HIP_CHECK(hipMemcpyAsync(mean_dist, ctx->ps_sum.ptr, sizeof(double) * rows * ctx->n_ratings,
-                               hipMemcpyDeviceToHost, ctx->stream));
+    if (mean_dist && ps.rows > 0) {
+      HIP_CHECK(hipMemcpyAsync(mean_dist, ps.sum.ptr, sizeof(double) * ps.rows * ctx->n_ratings, hipMemcpyDeviceToHost,
+                               ctx->stream));
       HIP_CHECK(hipStreamSynchronize(ctx->stream));
     }
   });
 }
 
 namespace {
-// The open recommend session; with `what` (the entry asking) also at least one slot added to it
-void require_session(const mmsbm_hip_ctx *ctx, const char *what) {
-  if (!ctx) throw std::invalid_argument("null context");
-  if (!ctx->rc) throw std::invalid_argument("recommend_begin has not been called");
-  if (what && ctx->rc->slots == 0) throw std::invalid_argument(std::string(what) + " before any recommend_add");
-}
-
-void require_n(int32_t n) {  // the n of a top-N query
-  if (n < 1) throw std::invalid_argument("recommend: n must be at least 1");
-  if (n > MMSBM_HIP_RECOMMEND_MAX_N)
-    throw ApiError(MMSBM_E_UNSUPPORTED, "recommend: n = " + std::to_string(n) + " is beyond the " +
-                                            std::to_string(MMSBM_HIP_RECOMMEND_MAX_N) + " items a query returns at most");
-}
-
 // A CSR argument of `rows` ranges (none when off is null): off[0] == 0, never decreasing, a total below 2^31 and
 // val[0 .. total) in [0, top).  Messages "<who>: <off_name>[0] must be 0", "<who>: <off_name> decrease at <row> b",
 // "<who>: more than 2^31 - 1 <vals>", "<who>: <val_name> out of range at entry e".
@@ -1416,8 +1550,7 @@ int mmsbm_hip_recommend_begin(mmsbm_hip_ctx *ctx, const double *rating_weights, 
 int mmsbm_hip_recommend_add(mmsbm_hip_ctx *ctx) {
   return guarded([&] {
     require_params(ctx);
-    require_session(ctx, nullptr);
-    if (ctx->rc->items != ctx->ext_items)
+    if (require_open(ctx, &mmsbm_hip_ctx::rc, "recommend").items != ctx->ext_items)
       throw std::invalid_argument("recommend_add after recommend_add_items: the added items hold no row of this slot");
     OneSlot one(ctx);
     recommend_add(ctx);
@@ -1427,35 +1560,26 @@ int mmsbm_hip_recommend_add(mmsbm_hip_ctx *ctx) {
 int mmsbm_hip_recommend_query(mmsbm_hip_ctx *ctx, int64_t n_users, const int32_t *users, int32_t n, int32_t *items,
                               double *scores, int32_t *counts) {
   return guarded([&] {
-    require_session(ctx, "recommend_query");
+    require_open(ctx, &mmsbm_hip_ctx::rc, "recommend", "recommend_query");
     if (n_users < 0) throw std::invalid_argument("negative n_users");
-    require_n(n);
+    require_n(n, "recommend", "items");
     if (n_users > 0 && (!users || !items)) throw std::invalid_argument("null argument");
-    for (int64_t m = 0; m < n_users; ++m)
-      if (users[m] < 0 || users[m] >= ctx->ext_users)
-        throw std::invalid_argument("recommend: user id out of range at row " + std::to_string(m));
+    require_ids(users, n_users, ctx->ext_users, "recommend: user");
     recommend_query(ctx, n_users, users, n, items, scores, counts);
   });
 }
 
-int mmsbm_hip_recommend_end(mmsbm_hip_ctx *ctx) {
-  return guarded([&] {
-    if (!ctx) throw std::invalid_argument("null context");
-    use_device(ctx);
-    HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    recommend_end(ctx);
-  });
-}
+int mmsbm_hip_recommend_end(mmsbm_hip_ctx *ctx) { return end_session(ctx, &mmsbm_hip_ctx::rc); }
 
 int mmsbm_hip_recommend_query_theta(mmsbm_hip_ctx *ctx, int64_t n_users, const double *theta,
                                     const int64_t *seen_offsets, const int32_t *seen_items, int32_t n,
                                     int32_t *items, double *scores, int32_t *counts) {
   return guarded([&] {
-    require_session(ctx, "recommend_query_theta");
+    const RecSession &rc = require_open(ctx, &mmsbm_hip_ctx::rc, "recommend", "recommend_query_theta");
     if (n_users < 0) throw std::invalid_argument("negative n_users");
-    require_n(n);
+    require_n(n, "recommend", "items");
     if (n_users > 0 && (!theta || !items)) throw std::invalid_argument("null argument");
-    check_csr(seen_offsets, seen_items, n_users, ctx->rc->items, "recommend", "seen_offsets", "user", "seen items",
+    check_csr(seen_offsets, seen_items, n_users, rc.items, "recommend", "seen_offsets", "user", "seen items",
               "seen item");
     recommend_query_theta(ctx, n_users, theta, seen_offsets, seen_items, n, items, scores, counts);
   });
@@ -1465,13 +1589,11 @@ int mmsbm_hip_recommend_positions(mmsbm_hip_ctx *ctx, int64_t n_users, const int
                                   const int64_t *offsets, const int32_t *items, int32_t *positions,
                                   int32_t *candidates) {
   return guarded([&] {
-    require_session(ctx, "recommend_positions");
+    const RecSession &rc = require_open(ctx, &mmsbm_hip_ctx::rc, "recommend", "recommend_positions");
     if (n_users < 0) throw std::invalid_argument("negative n_users");
     if (n_users > 0 && (!users || !offsets)) throw std::invalid_argument("null argument");
-    for (int64_t m = 0; m < n_users; ++m)
-      if (users[m] < 0 || users[m] >= ctx->ext_users)
-        throw std::invalid_argument("recommend_positions: user id out of range at row " + std::to_string(m));
-    check_csr(offsets, items, n_users, ctx->rc->items, "recommend_positions", "offsets", "user", "items", "item id");
+    require_ids(users, n_users, ctx->ext_users, "recommend_positions: user");
+    check_csr(offsets, items, n_users, rc.items, "recommend_positions", "offsets", "user", "items", "item id");
     if (n_users > 0 && offsets[n_users] > 0 && !positions) throw std::invalid_argument("null argument");
     recommend_positions(ctx, n_users, users, offsets, items, positions, candidates);
   });
@@ -1480,8 +1602,8 @@ int mmsbm_hip_recommend_positions(mmsbm_hip_ctx *ctx, int64_t n_users, const int
 int mmsbm_hip_recommend_add_items(mmsbm_hip_ctx *ctx, int32_t n_new, const double *eta,
                                   const int64_t *seen_offsets, const int32_t *seen_users) {
   return guarded([&] {
-    require_session(ctx, "recommend_add_items");
-    if (ctx->rc->items != ctx->ext_items)
+    const RecSession &rc = require_open(ctx, &mmsbm_hip_ctx::rc, "recommend", "recommend_add_items");
+    if (rc.items != ctx->ext_items)
       throw std::invalid_argument("recommend_add_items: the session already holds added items");
     if (n_new < 0) throw std::invalid_argument("recommend_add_items: negative n_new");
     if (static_cast<int64_t>(ctx->ext_items) + n_new > INT32_MAX)
@@ -1496,7 +1618,7 @@ int mmsbm_hip_recommend_add_items(mmsbm_hip_ctx *ctx, int32_t n_new, const doubl
 int mmsbm_hip_recommend_top_pairs(mmsbm_hip_ctx *ctx, int64_t n_users, const int32_t *users, int32_t m,
                                   int32_t *out_users, int32_t *out_items, double *out_scores, int32_t *count) {
   return guarded([&] {
-    require_session(ctx, "recommend_top_pairs");
+    require_open(ctx, &mmsbm_hip_ctx::rc, "recommend", "recommend_top_pairs");
     if (n_users < 0) throw std::invalid_argument("negative n_users");
     if (m < 1) throw std::invalid_argument("top_pairs: m must be at least 1");
     if (m > MMSBM_HIP_TOP_PAIRS_MAX_M)
@@ -1507,9 +1629,7 @@ int mmsbm_hip_recommend_top_pairs(mmsbm_hip_ctx *ctx, int64_t n_users, const int
     // when `users` is null; a repeated id would put its pairs into the order twice
     std::vector<int32_t> ids;
     if (users) {
-      for (int64_t b = 0; b < n_users; ++b)
-        if (users[b] < 0 || users[b] >= ctx->ext_users)
-          throw std::invalid_argument("top_pairs: user id out of range at row " + std::to_string(b));
+      require_ids(users, n_users, ctx->ext_users, "top_pairs: user");
       ids.assign(users, users + n_users);
       std::sort(ids.begin(), ids.end());
       const auto twice = std::adjacent_find(ids.begin(), ids.end());
@@ -1525,13 +1645,11 @@ int mmsbm_hip_recommend_top_pairs(mmsbm_hip_ctx *ctx, int64_t n_users, const int
 int mmsbm_hip_recommend_query_items(mmsbm_hip_ctx *ctx, int64_t n_items, const int32_t *items, int32_t n,
                                     int32_t *users, double *scores, int32_t *counts) {
   return guarded([&] {
-    require_session(ctx, "recommend_query_items");
+    const RecSession &rc = require_open(ctx, &mmsbm_hip_ctx::rc, "recommend", "recommend_query_items");
     if (n_items < 0) throw std::invalid_argument("negative n_items");
-    require_n(n);
+    require_n(n, "recommend", "items");
     if (n_items > 0 && (!items || !users)) throw std::invalid_argument("null argument");
-    for (int64_t m = 0; m < n_items; ++m)
-      if (items[m] < 0 || items[m] >= ctx->rc->items)
-        throw std::invalid_argument("recommend_query_items: item id out of range at row " + std::to_string(m));
+    require_ids(items, n_items, rc.items, "recommend_query_items: item");
     recommend_query_items(ctx, n_items, items, n, users, scores, counts);
   });
 }
@@ -1539,14 +1657,12 @@ int mmsbm_hip_recommend_query_items(mmsbm_hip_ctx *ctx, int64_t n_items, const i
 int mmsbm_hip_recommend_audience(mmsbm_hip_ctx *ctx, int64_t n_items, const int32_t *items, double min_score,
                                  int64_t capacity, int64_t *offsets, int32_t *users, double *scores) {
   return guarded([&] {
-    require_session(ctx, "recommend_audience");
+    const RecSession &rc = require_open(ctx, &mmsbm_hip_ctx::rc, "recommend", "recommend_audience");
     if (n_items < 0) throw std::invalid_argument("negative n_items");
     if (!std::isfinite(min_score)) throw std::invalid_argument("audience: min_score is not finite");
     if (!offsets || (n_items > 0 && !items) || (users && !scores)) throw std::invalid_argument("null argument");
     if (users && capacity < 0) throw std::invalid_argument("audience: negative capacity");
-    for (int64_t m = 0; m < n_items; ++m)
-      if (items[m] < 0 || items[m] >= ctx->rc->items)
-        throw std::invalid_argument("audience: item id out of range at row " + std::to_string(m));
+    require_ids(items, n_items, rc.items, "audience: item");
     recommend_audience(ctx, n_items, items, min_score, capacity, offsets, users, scores);
   });
 }
@@ -1562,7 +1678,7 @@ int mmsbm_hip_similar_begin(mmsbm_hip_ctx *ctx, int side) {
 int mmsbm_hip_similar_add(mmsbm_hip_ctx *ctx) {
   return guarded([&] {
     require_params(ctx);
-    if (!ctx->sm) throw std::invalid_argument("similar_begin has not been called");
+    require_open(ctx, &mmsbm_hip_ctx::sm, "similar");
     OneSlot one(ctx);
     similar_add(ctx);
   });
@@ -1571,31 +1687,16 @@ int mmsbm_hip_similar_add(mmsbm_hip_ctx *ctx) {
 int mmsbm_hip_similar_query(mmsbm_hip_ctx *ctx, int64_t n_rows, const int32_t *ids, int32_t n, int32_t *out_ids,
                             double *distance, int32_t *counts) {
   return guarded([&] {
-    if (!ctx) throw std::invalid_argument("null context");
-    if (!ctx->sm) throw std::invalid_argument("similar_begin has not been called");
-    if (ctx->sm->slots == 0) throw std::invalid_argument("similar_query before any similar_add");
+    const SimSession &sm = require_open(ctx, &mmsbm_hip_ctx::sm, "similar", "similar_query");
     if (n_rows < 0) throw std::invalid_argument("negative n_rows");
-    if (n < 1) throw std::invalid_argument("similar: n must be at least 1");
-    if (n > MMSBM_HIP_RECOMMEND_MAX_N)
-      throw ApiError(MMSBM_E_UNSUPPORTED, "similar: n = " + std::to_string(n) + " is beyond the " +
-                                              std::to_string(MMSBM_HIP_RECOMMEND_MAX_N) + " rows a query returns at most");
+    require_n(n, "similar", "rows");
     if (n_rows > 0 && (!ids || !out_ids)) throw std::invalid_argument("null argument");
-    for (int64_t m = 0; m < n_rows; ++m)
-      if (ids[m] < 0 || ids[m] >= ctx->sm->rows)
-        throw std::invalid_argument(std::string("similar: ") + (ctx->sm->side == 0 ? "item" : "user") +
-                                    " id out of range at row " + std::to_string(m));
+    require_ids(ids, n_rows, sm.rows, sm.side == 0 ? "similar: item" : "similar: user");
     similar_query(ctx, n_rows, ids, n, out_ids, distance, counts);
   });
 }
 
-int mmsbm_hip_similar_end(mmsbm_hip_ctx *ctx) {
-  return guarded([&] {
-    if (!ctx) throw std::invalid_argument("null context");
-    use_device(ctx);
-    HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    similar_end(ctx);
-  });
-}
+int mmsbm_hip_similar_end(mmsbm_hip_ctx *ctx) { return end_session(ctx, &mmsbm_hip_ctx::sm); }
 
 int mmsbm_hip_overlap_begin(mmsbm_hip_ctx *ctx, int side) {
   return guarded([&] {
@@ -1607,9 +1708,8 @@ int mmsbm_hip_overlap_begin(mmsbm_hip_ctx *ctx, int side) {
 
 int mmsbm_hip_overlap_add(mmsbm_hip_ctx *ctx) {
   return guarded([&] {
-    if (!ctx) throw std::invalid_argument("null context");
-    if (!ctx->ov) throw std::invalid_argument("overlap_begin has not been called");
     require_params(ctx);
+    require_open(ctx, &mmsbm_hip_ctx::ov, "overlap");
     OneSlot one(ctx);
     overlap_add(ctx);
   });
@@ -1617,22 +1717,13 @@ int mmsbm_hip_overlap_add(mmsbm_hip_ctx *ctx) {
 
 int mmsbm_hip_overlap_query(mmsbm_hip_ctx *ctx, double *out) {
   return guarded([&] {
-    if (!ctx) throw std::invalid_argument("null context");
-    if (!ctx->ov) throw std::invalid_argument("overlap_begin has not been called");
-    if (ctx->ov->slots == 0) throw std::invalid_argument("overlap_query before any overlap_add");
+    require_open(ctx, &mmsbm_hip_ctx::ov, "overlap", "overlap_query");
     if (!out) throw std::invalid_argument("null out");
     overlap_query(ctx, out);
   });
 }
 
-int mmsbm_hip_overlap_end(mmsbm_hip_ctx *ctx) {
-  return guarded([&] {
-    if (!ctx) throw std::invalid_argument("null context");
-    use_device(ctx);
-    HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    overlap_end(ctx);
-  });
-}
+int mmsbm_hip_overlap_end(mmsbm_hip_ctx *ctx) { return end_session(ctx, &mmsbm_hip_ctx::ov); }
 
 int mmsbm_hip_heldout_begin(mmsbm_hip_ctx *ctx, int64_t n_rows, const int32_t *user, const int32_t *item,
                             const int32_t *rating) {
@@ -1653,7 +1744,7 @@ int mmsbm_hip_heldout_eval(mmsbm_hip_ctx *ctx, double *loglik) {
   return guarded([&] {
     require_all_params(ctx);
     if (!loglik) throw std::invalid_argument("null loglik");
-    if (!ctx->ho) throw std::invalid_argument("heldout_begin has not been called");
+    require_open(ctx, &mmsbm_hip_ctx::ho, "heldout");
     heldout_eval(ctx, 0, ctx->n_slots, false, loglik);
   });
 }
@@ -1662,7 +1753,7 @@ int mmsbm_hip_heldout_add(mmsbm_hip_ctx *ctx, double *loglik) {
   return guarded([&] {
     require_params(ctx);
     if (!loglik) throw std::invalid_argument("null loglik");
-    if (!ctx->ho) throw std::invalid_argument("heldout_begin has not been called");
+    require_open(ctx, &mmsbm_hip_ctx::ho, "heldout");
     heldout_eval(ctx, ctx->sel, 1, true, loglik);
   });
 }
@@ -1670,21 +1761,12 @@ int mmsbm_hip_heldout_add(mmsbm_hip_ctx *ctx, double *loglik) {
 int mmsbm_hip_heldout_mean(mmsbm_hip_ctx *ctx, double *mean_p, double *loglik) {
   return guarded([&] {
     if (!ctx || !loglik) throw std::invalid_argument("null argument");
-    if (!ctx->ho) throw std::invalid_argument("heldout_begin has not been called");
-    if (ctx->ho->added < 1) throw std::invalid_argument("heldout_mean before any heldout_add");
+    require_open(ctx, &mmsbm_hip_ctx::ho, "heldout", "heldout_mean");
     heldout_mean(ctx, mean_p, loglik);
   });
 }
 
-int mmsbm_hip_heldout_end(mmsbm_hip_ctx *ctx) {
-  return guarded([&] {
-    if (!ctx) throw std::invalid_argument("null context");
-    if (!ctx->ho) throw std::invalid_argument("heldout_begin has not been called");
-    use_device(ctx);
-    HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    heldout_end(ctx);
-  });
-}
+int mmsbm_hip_heldout_end(mmsbm_hip_ctx *ctx) { return end_session(ctx, &mmsbm_hip_ctx::ho, "heldout"); }
 
 namespace {
 // the snapshot tables as theta_tab / eta_tab see the parameters of slot `slot`
@@ -1760,16 +1842,12 @@ int mmsbm_hip_time_iterations(mmsbm_hip_ctx *ctx, int n_iters, float *elapsed_ms
     require_all_params(ctx);
     if (!elapsed_ms || n_iters < 0) throw std::invalid_argument("bad argument");
     use_device(ctx);
-    hipEvent_t e0, e1;
-    HIP_CHECK(hipEventCreate(&e0));
-    HIP_CHECK(hipEventCreate(&e1));
-    HIP_CHECK(hipEventRecord(e0, ctx->stream));
+    EventPair ev;
+    ev.start(ctx->stream);
     run_iterations(ctx, n_iters);
-    HIP_CHECK(hipEventRecord(e1, ctx->stream));
-    HIP_CHECK(hipEventSynchronize(e1));
-    HIP_CHECK(hipEventElapsedTime(elapsed_ms, e0, e1));
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
+    ev.stop(ctx->stream);
+    ev.wait();
+    *elapsed_ms = ev.ms();
   });
 }
 
@@ -1864,117 +1942,35 @@ int mmsbm_hip_time_stage(mmsbm_hip_ctx *ctx, int stage, int reps, float *mean_us
       }
     };
     for (int w = 0; w < 3; ++w) one();
-    hipEvent_t e0, e1;
-    HIP_CHECK(hipEventCreate(&e0));
-    HIP_CHECK(hipEventCreate(&e1));
-    HIP_CHECK(hipEventRecord(e0, ctx->stream));
+    EventPair ev;
+    ev.start(ctx->stream);
     for (int r = 0; r < reps; ++r) one();
-    HIP_CHECK(hipEventRecord(e1, ctx->stream));
-    HIP_CHECK(hipEventSynchronize(e1));
-    float ms = 0.f;
-    HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-    *mean_us = ms * 1000.f / reps;
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
+    ev.stop(ctx->stream);
+    ev.wait();
+    *mean_us = ev.ms() * 1000.f / reps;
   });
 }
 
 int mmsbm_hip_set_option(mmsbm_hip_ctx *ctx, const char *name, double value) {
   return guarded([&] {
     if (!ctx || !name) throw std::invalid_argument("null argument");
-    const std::string key(name);
-    if (key == "graph") {
-      ctx->graph_mode = value != 0.0;
-    } else if (key == "lik_fast") {  // 0: a logarithm per element; 1: logarithm tables, a group of lanes per triple
-                                     // (round 2); 2: where it applies a wave per pair (lik_fact.hpp), else as 1
-      if (value != 0.0 && value != 1.0 && value != 2.0) throw std::invalid_argument("lik_fast: 0, 1 or 2");
-      ctx->lik_mode = static_cast<int>(value);
-    } else if (key == "lik_g") {
-      const int g = static_cast<int>(value);
-      if (g != 0 && g != 1 && g != 2 && g != 4 && g != 8) throw std::invalid_argument("lik_g: 0, 1, 2, 4 or 8");
-      ctx->lik_g = g;
-    } else if (key == "quad") {  // 0: the A launch through pair_block like every other shape
-      // (create() also requires unit runs of four -- big_chunk == 4 * kMvChunkPairs, plan_pair_forms -- and this option
-      // never has: with longer runs it turns on what create() left off.  Whether that is meant is open; both are as they were)
-      ctx->pp.set_quad(value != 0.0);
-    } else if (key == "fused") {  // two launches per iteration (small tiles, unsplit segments); any problem size
-      if (value != 0.0 && !fused_possible(ctx)) throw std::invalid_argument("fused: not available for this shape / data");
-      ctx->fused = value != 0.0;
-      ctx->fused_forced = value != 0.0;
-    } else if (key == "nt_out") {  // 0: plain stores for every output row; bits: 1 T and A rows, 2 theta' rows, 4 own-row loads
-      if (value < 0 || value > 15) throw std::invalid_argument("nt_out: 0 .. 15");
-      ctx->nt_out = static_cast<int>(value);
-    } else if (key == "predict_fast") {  // 0: prod_dist / predict through the per-row kernels (R K L multiply-adds per row)
-      ctx->predict_fast = value != 0.0;
-    } else if (key == "top_pairs_groups") {  // workgroups of gtop_fused_kernel (top_pairs.hpp); 0: the library's choice
-      if (value < 0 || value > 4096 || value != std::floor(value)) throw std::invalid_argument("top_pairs_groups: 0 .. 4096");
-      ctx->top_groups = static_cast<int>(value);
-    } else if (key == "audience_rows" || key == "audience_entries") {  // recommend_audience (audience.hpp): items per COUNT
-      // batch, entries per WRITE batch at most; 0: the library's choice.  Neither changes the answer
-      if (value < 0 || value > 2147483647.0 || value != std::floor(value)) throw std::invalid_argument(key + ": 0 .. 2^31 - 1");
-      (key == "audience_rows" ? ctx->aud_rows : ctx->aud_entries) = static_cast<int64_t>(value);
-    } else if (key == "a_units") {  // 64-pair units per workgroup of the matrix-core A launch; 0: the library's own balance
-      if (value < 0 || value > kMfmaChunkPairs / kUnitPairs) throw std::invalid_argument("a_units: 0 .. 16");
-      use_device(ctx);
-      HIP_CHECK(hipStreamSynchronize(ctx->stream));
-      build_a_runs(ctx, static_cast<int>(value));
-    } else if (key == "mfma") {  // the pair stage on the matrix cores: 0 off, 1 on (one-block form if K, L <= 64,
-                                 // else the blocked form), 2 the blocked form whatever the shape
-      ctx->pp.set_mfma(value);
-    } else {
-      throw std::invalid_argument("unknown option: " + key);
-    }
-    ctx->drop_graphs();  // (after every option: a captured graph holds the launches of the plan it was captured under)
+    set_option(ctx, name, value);
   });
 }
 
 int mmsbm_hip_get_option(const mmsbm_hip_ctx *ctx, const char *name, double *value) {
   return guarded([&] {
     if (!ctx || !name || !value) throw std::invalid_argument("null argument");
-    const std::string key(name);
-    if (key == "graph") *value = ctx->graph_mode;
-    else if (key == "quad") *value = ctx->pp.quad_a;
-    else if (key == "mfma") *value = ctx->pp.mfma ? 1.0 : (ctx->pp.mfma_big ? 2.0 : 0.0);
-    else if (key == "predict_fast") *value = ctx->predict_fast;
-    else if (key == "fused") *value = ctx->fused;
-    else if (key == "nt_out") *value = nt_on(ctx);
-    else if (key == "recommend_ms") *value = ctx->rc_last_ms;  // read-only: device time of the last recommend_query
-    else if (key == "fold_in_ms") *value = ctx->fold_last_ms;  // read-only: device time of the last fold-in (either side)
-    else if (key == "position_ms") *value = ctx->pos_last_ms;  // read-only: device time of the last recommend_positions
-    else if (key == "similar_ms") *value = ctx->sim_last_ms;   // read-only: device time of the last similar_query
-    else if (key == "top_pairs_ms") *value = ctx->top_last_ms; // read-only: device time of the last recommend_top_pairs
-    else if (key == "overlap_ms") *value = ctx->ovl_last_ms;   // read-only: device time of the last overlap_query
-    else if (key == "heldout_ms") *value = ctx->hold_last_ms;  // read-only: device time of the last heldout_eval / heldout_add
-    else if (key == "top_pairs_groups") *value = ctx->top_groups;
-    else if (key == "audience_ms") *value = ctx->aud_last_ms;  // read-only: device time of the last recommend_audience
-    else if (key == "audience_rows") *value = static_cast<double>(ctx->aud_rows);
-    else if (key == "audience_entries") *value = static_cast<double>(ctx->aud_entries);
-    else if (key == "launches") *value = use_fused(ctx) ? 2 : 4;  // read-only: launches per iteration at the current slot count
-    else if (key == "wide") *value = ctx->pp.wide;
-    else if (key == "lik_fast") *value = ctx->lik_mode;
-    else if (key == "lik_g") *value = ctx->lik_g;
-    else if (key == "ranges_pairs") *value = ctx->ranges_pairs;   // read-only: XCD-local work lists,
-    else if (key == "ranges_users") *value = ctx->ranges_users;   // ranges per pass (1 = off)
-    else if (key == "chunk_pairs") *value = ctx->pp.chunk_pairs;   // read-only: pairs per pair-stage workgroup at most
-    else if (key == "n_chunks") *value = ctx->n_chunks;            // read-only: pair-stage workgroups (= slabs), padding included
-    else if (key == "a_units") *value = ctx->a_units;     // 64-pair units per workgroup of the matrix-core A launch (0: not on the matrix cores)
-    else if (key == "a_chunks") *value = ctx->n_a_chunks;   // read-only: workgroups of the matrix-core A launch when it walks runs of its own (0: the T + S launch's)
-    else if (key == "items_pairs") *value = static_cast<double>(ctx->lay.pair_work.items.size());
-    else if (key == "items_users") *value = static_cast<double>(ctx->lay.user_work.items.size());
-    else if (key == "splits_pairs") *value = static_cast<double>(ctx->lay.pair_work.splits.size());  // read-only: segments cut into pieces
-    else if (key == "splits_users") *value = static_cast<double>(ctx->lay.user_work.splits.size());
-    else if (key == "fused_split") *value = (ctx->fs_pairs ? 1 : 0) + (ctx->fs_users ? 2 : 0);  // read-only: whole-segment lists built (1 pair side, 2 user side)
-    else if (key == "item_grid") *value = ctx->item_grid.count ? 1 : 0;  // read-only: item_sum walks the fixed-width grid of pair ids (upload_item_grid)
-    else if (key == "gpu_layout") *value = ctx->gpu_layout ? 1 : 0;  // read-only: the index's sorts ran on the device (build_index)
-    else throw std::invalid_argument("unknown option: " + key);
+    const Option *o = find_option(name);
+    if (!o) throw std::invalid_argument(std::string("unknown option: ") + name);
+    *value = o->get(ctx);
   });
 }
 
 int mmsbm_hip_set_graph_mode(mmsbm_hip_ctx *ctx, int enabled) {
   return guarded([&] {
     if (!ctx) throw std::invalid_argument("null context");
-    ctx->graph_mode = enabled != 0;
-    ctx->drop_graphs();
+    set_option(ctx, "graph", enabled != 0);
   });
 }
 

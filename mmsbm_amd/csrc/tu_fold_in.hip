@@ -140,7 +140,7 @@ void fold_in(mmsbm_hip_ctx *c, bool items_side, int64_t n_rows, const int32_t *u
       if (iters) iters[u0 + b] = empty ? 0 : hn[b];
     }
   }
-  c->fold_last_ms = total_ms;
+  c->last_ms[T_FOLD_IN] = total_ms;
 }
 
 }  // namespace mmsbm_hip_impl

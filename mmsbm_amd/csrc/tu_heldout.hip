@@ -114,8 +114,8 @@ void heldout_eval(mmsbm_hip_ctx *c, int first, int n_slots, bool add, double *lo
   ev.stop(st);  // (the two launches: the copy of the results is not part of "heldout_ms")
   hold_fetch(c, h, n_slots, loglik);
   HIP_CHECK(hipStreamSynchronize(st));
-  c->hold_last_ms = ev.ms();
-  if (add) h.added++;
+  c->last_ms[T_HELDOUT] = ev.ms();
+  if (add) h.slots++;
 }
 
 void heldout_mean(mmsbm_hip_ctx *c, double *mean_p, double *loglik) {
@@ -124,7 +124,7 @@ void heldout_mean(mmsbm_hip_ctx *c, double *mean_p, double *loglik) {
   hipStream_t st = c->stream;
   const int nb = static_cast<int>((h.rows + kHoldRows - 1) / kHoldRows);  // (<= n_blocks: a block holds at most kHoldRows)
   if (nb > 0) {
-    LAUNCH(hold_mean_kernel, static_cast<unsigned>(nb), kBlock, 0, st, h.sum.ptr, h.rows, static_cast<double>(h.added),
+    LAUNCH(hold_mean_kernel, static_cast<unsigned>(nb), kBlock, 0, st, h.sum.ptr, h.rows, static_cast<double>(h.slots),
            h.mean.ptr, h.part.ptr);
     HIP_CHECK(hipGetLastError());
   }
@@ -134,7 +134,5 @@ void heldout_mean(mmsbm_hip_ctx *c, double *mean_p, double *loglik) {
     HIP_CHECK(hipMemcpyAsync(mean_p, h.mean.ptr, sizeof(double) * h.rows, hipMemcpyDeviceToHost, st));
   HIP_CHECK(hipStreamSynchronize(st));
 }
-
-void heldout_end(mmsbm_hip_ctx *c) { c->ho.reset(); }
 
 }  // namespace mmsbm_hip_impl

@@ -220,21 +220,22 @@ int rows_launch(mmsbm_hip_ctx *c, int mode, const int32_t *pu, const int32_t *pi
 }
 
 // the per-row scoring kernels (fewer rows than items, or predict_fast = 0) and the final pass over the mean; the six sums
-// per workgroup go to ps_part.  Returns the number of workgroups.
+// per workgroup go to the session's `part`.  Returns the number of workgroups.
 int score_rows_launch(mmsbm_hip_ctx *ctx, bool finish) {
-  const int nb = static_cast<int>((ctx->ps_rows + kBlock - 1) / kBlock);
+  const PredictSession &ps = *ctx->ps;
+  const int nb = static_cast<int>((ps.rows + kBlock - 1) / kBlock);
   if (nb <= 0) return 0;
   const int cur = ctx->cur, sl = ctx->sel;
   if (finish)
     LAUNCH(predict_score_kernel<true>, nb, kBlock, 0, ctx->stream,
-           ctx->ps_u.ptr, ctx->ps_i.ptr, ctx->ps_r.ptr, theta_tab(ctx, cur), ctx->eta[cur].at(sl),
-           ctx->p[cur].at(sl), ctx->ps_w.ptr, ctx->ps_sum.ptr, ctx->ps_part.ptr, ctx->ps_rows,
-           ctx->n_ratings, ctx->k, ctx->l, ctx->kp, ctx->lp, 0, static_cast<double>(ctx->ps_added));
+           ps.u.ptr, ps.i.ptr, ps.r.ptr, theta_tab(ctx, cur), ctx->eta[cur].at(sl),
+           ctx->p[cur].at(sl), ps.w.ptr, ps.sum.ptr, ps.part.ptr, ps.rows,
+           ctx->n_ratings, ctx->k, ctx->l, ctx->kp, ctx->lp, 0, static_cast<double>(ps.slots));
   else
     LAUNCH(predict_score_kernel<false>, nb, kBlock, 0, ctx->stream,
-           ctx->ps_u.ptr, ctx->ps_i.ptr, ctx->ps_r.ptr, theta_tab(ctx, cur), ctx->eta[cur].at(sl),
-           ctx->p[cur].at(sl), ctx->ps_w.ptr, ctx->ps_sum.ptr, ctx->ps_part.ptr, ctx->ps_rows,
-           ctx->n_ratings, ctx->k, ctx->l, ctx->kp, ctx->lp, ctx->ps_added == 0 ? 1 : 0, 1.0);
+           ps.u.ptr, ps.i.ptr, ps.r.ptr, theta_tab(ctx, cur), ctx->eta[cur].at(sl),
+           ctx->p[cur].at(sl), ps.w.ptr, ps.sum.ptr, ps.part.ptr, ps.rows,
+           ctx->n_ratings, ctx->k, ctx->l, ctx->kp, ctx->lp, ps.slots == 0 ? 1 : 0, 1.0);
   HIP_CHECK(hipGetLastError());
   return nb;
 }

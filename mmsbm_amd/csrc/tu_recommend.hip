@@ -204,10 +204,10 @@ void rec_score_batch(mmsbm_hip_ctx *c, const double *x, size_t xs, const int32_t
 // The batches of a top-N query over a buffer of `I` columns: rows ids[0 .. n_rows) (host ids); `fill(ub, nb, sc)`
 // enqueues the kernels that write the batch's values sc [nb][I] for the device ids ub (-inf: no candidate), then the
 // N best of every row are selected (and merged when the columns are split across waves).  `what` names the query in
-// MMSBM_E_TOOLARGE; *ms: device time of the query's kernels.
+// MMSBM_E_TOOLARGE; `timed`: the timer that takes the device time of the query's kernels.
 template <class Fill>
 void top_n_run(mmsbm_hip_ctx *c, int I, int64_t n_users, const int32_t *users, int n, const char *what, Fill &&fill,
-               float *ms, int32_t *items, double *scores, int32_t *counts) {
+               TimedCall timed, int32_t *items, double *scores, int32_t *counts) {
   for (int64_t b = 0; b < n_users; ++b) {
     if (counts) counts[b] = 0;
     for (int k = 0; k < n; ++k) {
@@ -263,7 +263,7 @@ void top_n_run(mmsbm_hip_ctx *c, int I, int64_t n_users, const int32_t *users, i
   HIP_CHECK(hipMemcpyAsync(hi.data(), oi.ptr, sizeof(int32_t) * outs, hipMemcpyDeviceToHost, st));
   HIP_CHECK(hipMemcpyAsync(hn.data(), on.ptr, sizeof(int32_t) * n_users, hipMemcpyDeviceToHost, st));
   HIP_CHECK(hipStreamSynchronize(st));
-  *ms = ev.ms();
+  c->last_ms[timed] = ev.ms();
   for (int64_t b = 0; b < n_users; ++b) {
     const size_t o = static_cast<size_t>(b) * n;
     const int cnt = hn[static_cast<size_t>(b)];
@@ -281,7 +281,7 @@ void rec_run(mmsbm_hip_ctx *c, const double *x, size_t xs, int64_t n_users, cons
              const int32_t *seen_off, const int32_t *seen, int n, int32_t *items, double *scores, int32_t *counts) {
   top_n_run(c, c->rc->items, n_users, users, n, "recommend: a batch of users",
             [&](const int32_t *ub, int nb, double *sc) { rec_score_batch(c, x, xs, ub, nb, seen_off, seen, sc); },
-            &c->rc_last_ms, items, scores, counts);
+            T_RECOMMEND, items, scores, counts);
 }
 
 }  // namespace
@@ -350,7 +350,7 @@ void recommend_positions(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users
   toff.push_back(static_cast<int32_t>(total));
   const int64_t na = static_cast<int64_t>(hu.size());
   if (na == 0) {
-    c->pos_last_ms = 0.f;
+    c->last_ms[T_POSITIONS] = 0.f;
     return;
   }
   hipStream_t st = c->stream;
@@ -387,7 +387,7 @@ void recommend_positions(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users
   ev.stop(st);
   HIP_CHECK(hipMemcpyAsync(positions, dpos.ptr, sizeof(int32_t) * total, hipMemcpyDeviceToHost, st));
   HIP_CHECK(hipStreamSynchronize(st));
-  c->pos_last_ms = ev.ms();
+  c->last_ms[T_POSITIONS] = ev.ms();
 }
 
 // The m best pairs over users[0 .. n_users) (host ids, ascending and distinct) x the session's catalogue
@@ -403,7 +403,7 @@ void recommend_top_pairs(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users
     out_scores[k] = -INFINITY;
   }
   *count = 0;
-  c->top_last_ms = 0.f;
+  c->last_ms[T_TOP_PAIRS] = 0.f;
   if (n_users == 0 || I == 0) return;
   hipStream_t st = c->stream;
   const int64_t tiles = ((n_users + kRecTile - 1) / kRecTile) * ((static_cast<int64_t>(I) + kRecTile - 1) / kRecTile);
@@ -446,7 +446,7 @@ void recommend_top_pairs(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users
   HIP_CHECK(hipMemcpyAsync(hk.data(), ik, sizeof(uint64_t) * m, hipMemcpyDeviceToHost, st));
   HIP_CHECK(hipMemcpyAsync(&hn, in, sizeof(int32_t), hipMemcpyDeviceToHost, st));
   HIP_CHECK(hipStreamSynchronize(st));
-  c->top_last_ms = ev.ms();
+  c->last_ms[T_TOP_PAIRS] = ev.ms();
   *count = hn;
   for (int k = 0; k < hn; ++k) {
     out_users[k] = static_cast<int32_t>(hk[static_cast<size_t>(k)] >> 32);
@@ -510,7 +510,7 @@ void recommend_query_items(mmsbm_hip_ctx *c, int64_t n_items, const int32_t *ite
   const int32_t *ex_off = rc.excl ? rc.by_item_off.ptr : nullptr, *ex = rc.by_item.ptr;
   top_n_run(c, c->ext_users, n_items, items, n, "recommend: a batch of items",
             [&](const int32_t *ib, int nb, double *sc) { rec_score_items_batch(c, ib, nb, ex_off, ex, sc); },
-            &c->rc_last_ms, users, scores, counts);
+            T_RECOMMEND, users, scores, counts);
 }
 
 void recommend_audience(mmsbm_hip_ctx *c, int64_t n_items, const int32_t *items, double min_score, int64_t capacity,
@@ -519,7 +519,7 @@ void recommend_audience(mmsbm_hip_ctx *c, int64_t n_items, const int32_t *items,
   rec_item_lists(c);
   const RecSession &rc = *c->rc;
   std::fill(offsets, offsets + n_items + 1, int64_t(0));
-  c->aud_last_ms = 0.f;
+  c->last_ms[T_AUDIENCE] = 0.f;
   const int U = c->ext_users, rank = rc.rank, S = rc.slots;
   if (n_items == 0 || U == 0) return;
   hipStream_t st = c->stream;
@@ -566,7 +566,7 @@ void recommend_audience(mmsbm_hip_ctx *c, int64_t n_items, const int32_t *items,
     offsets[b + 1] = offsets[b] + ht[static_cast<size_t>(b)];
     largest = std::max<int64_t>(largest, ht[static_cast<size_t>(b)]);
   }
-  c->aud_last_ms = ms;
+  c->last_ms[T_AUDIENCE] = ms;
   const int64_t total = offsets[n_items];
   if (!users || total == 0) return;
   if (capacity < total)
@@ -620,10 +620,8 @@ void recommend_audience(mmsbm_hip_ctx *c, int64_t n_items, const int32_t *items,
       s0 = s1;
     }
   }
-  c->aud_last_ms = ms;
+  c->last_ms[T_AUDIENCE] = ms;
 }
-
-void recommend_end(mmsbm_hip_ctx *c) { c->rc.reset(); }
 
 // ---- nearest items / users (similar.hpp) ------------------------------------------------------------------------------
 void similar_begin(mmsbm_hip_ctx *c, int side) {
@@ -675,12 +673,10 @@ void similar_query(mmsbm_hip_ctx *c, int64_t n_rows, const int32_t *ids, int n, 
               LAUNCH(sim_dist_kernel, g, kBlock, 0, st, sm.q.ptr, static_cast<size_t>(rows) * W, sm.mf.ptr, ub, nb, rows,
                      W, S, denom, sc, static_cast<size_t>(rows));
             },
-            &c->sim_last_ms, out_ids, distance, counts);
+            T_SIMILAR, out_ids, distance, counts);
   // the buffer held -D (the selection's order): the distances, +inf behind the last one (a zero leaves as +0.0)
   for (size_t e = 0; distance && e < static_cast<size_t>(n_rows) * n; ++e) distance[e] = -distance[e];
 }
-
-void similar_end(mmsbm_hip_ctx *c) { c->sm.reset(); }
 
 // ---- the overlap of the restarts' groups (overlap.hpp) ---------------------------------------------------------------
 void overlap_begin(mmsbm_hip_ctx *c, int side) {
@@ -737,9 +733,7 @@ void overlap_query(mmsbm_hip_ctx *c, double *out) {
   ev.stop(st);
   HIP_CHECK(hipMemcpyAsync(out, res.ptr, sizeof(double) * outs, hipMemcpyDeviceToHost, st));
   HIP_CHECK(hipStreamSynchronize(st));
-  c->ovl_last_ms = ev.ms();
+  c->last_ms[T_OVERLAP] = ev.ms();
 }
-
-void overlap_end(mmsbm_hip_ctx *c) { c->ov.reset(); }
 
 }  // namespace mmsbm_hip_impl

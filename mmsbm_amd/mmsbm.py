@@ -415,10 +415,7 @@ class MMSBM:
         enc = self.data_handler
         ids, labels = self._training_users(users)
         item_labels = np.asarray(enc.item_labels(), dtype=object) if enc else None
-        ctx, restarts = self._restarts()
-        with self._recommend_session(ctx, w, exclude_seen):
-            for _ in restarts:
-                ctx.recommend_add()
+        with self._session_of_restarts("recommend", w, exclude_seen) as ctx:
             return self._top_n_frame(lambda b, e: ctx.recommend_query(ids[b:e], n), n, labels, item_labels)
 
     def recommend_users(self, items=None, n=10, exclude_seen=True, weights=None):
@@ -435,10 +432,7 @@ class MMSBM:
         enc = self.data_handler
         ids, labels = self._training_ids(items, "items")
         user_labels = np.asarray(enc.user_labels(), dtype=object) if enc else None
-        ctx, restarts = self._restarts()
-        with self._recommend_session(ctx, w, exclude_seen):
-            for _ in restarts:
-                ctx.recommend_add()
+        with self._session_of_restarts("recommend", w, exclude_seen) as ctx:
             return self._top_n_frame(lambda b, e: ctx.recommend_query_items(ids[b:e], n), n, labels, user_labels,
                                      columns=("items", "users", "score"))
 
@@ -460,10 +454,7 @@ class MMSBM:
         enc = self.data_handler
         ids, labels = self._training_ids(items, "items")
         user_labels = np.asarray(enc.user_labels(), dtype=object) if enc else None
-        ctx, restarts = self._restarts()
-        with self._recommend_session(ctx, w, exclude_seen):
-            for _ in restarts:
-                ctx.recommend_add()
+        with self._session_of_restarts("recommend", w, exclude_seen) as ctx:
             sizes = np.diff(ctx.recommend_audience(ids, min_score, count_only=True)[0])
             if count_only:
                 return pd.DataFrame({"items": labels, "count": sizes.astype(np.int64)})
@@ -514,10 +505,7 @@ class MMSBM:
             if len(np.unique(ids)) != len(ids):
                 twice = list(dict.fromkeys(labels[np.isin(ids, ids[np.bincount(ids)[ids] > 1])].tolist()))
                 raise ValueError(f"users named more than once: {twice}")
-        ctx, restarts = self._restarts()
-        with self._recommend_session(ctx, w, exclude_seen):
-            for _ in restarts:
-                ctx.recommend_add()
+        with self._session_of_restarts("recommend", w, exclude_seen) as ctx:
             us, its, scores, count = ctx.recommend_top_pairs(m, ids)
         us, its = us[:count].astype(np.int64), its[:count].astype(np.int64)
         return pd.DataFrame({
@@ -535,6 +523,19 @@ class MMSBM:
             yield
         finally:
             ctx.recommend_end()
+
+    @contextlib.contextmanager
+    def _session_of_restarts(self, kind, *begin_args):
+        """The context, with its ``kind`` session ("recommend", "similar", "overlap") begun with ``begin_args`` and
+        every restart the model holds added to it, around the block; the session is ended however the block ends."""
+        ctx, restarts = self._restarts()
+        getattr(ctx, kind + "_begin")(*begin_args)
+        try:
+            for _ in restarts:
+                getattr(ctx, kind + "_add")()
+            yield ctx
+        finally:
+            getattr(ctx, kind + "_end")()
 
     def _top_n_frame(self, query, n, row_labels, item_labels, columns=("users", "items", "score")):
         """The top-``n`` frame (users, items, score, rank) of rows [0, len(row_labels)), fetched in calls of at most
@@ -635,15 +636,9 @@ class MMSBM:
         ids, labels = self._training_ids(wanted, side)
         enc = self.data_handler
         side_labels = np.asarray(enc.user_labels() if side == "users" else enc.item_labels(), dtype=object) if enc else None
-        ctx, restarts = self._restarts()
-        ctx.similar_begin(side)
-        try:
-            for _ in restarts:
-                ctx.similar_add()
+        with self._session_of_restarts("similar", side) as ctx:
             return self._top_n_frame(lambda b, e: ctx.similar_query(ids[b:e], n), n, labels, side_labels,
                                      columns=(side, "similar", "distance"))
-        finally:
-            ctx.similar_end()
 
     # ------------------------------------------------------------------ matching the restarts' groups (not in the reference)
     def align_restarts(self, reference=None):
@@ -678,14 +673,8 @@ class MMSBM:
         reference = int(reference)
         out = {"reference": reference}
         for side, groups, n_rows in (("user", self.user_groups, self.p + 1), ("item", self.item_groups, self.m + 1)):
-            ctx, restarts = self._restarts()
-            ctx.overlap_begin(side + "s")
-            try:
-                for _ in restarts:
-                    ctx.overlap_add()
+            with self._session_of_restarts("overlap", side + "s") as ctx:
                 gram = ctx.overlap_query()
-            finally:
-                ctx.overlap_end()
             out[side + "_groups"], out[side + "_similarity"], out[side + "_agreement"] = align.align_side(
                 gram, groups, n_rows, reference)
         return out
@@ -775,10 +764,7 @@ class MMSBM:
         order = np.argsort(users, kind="stable")                      # one request entry per user holding rows
         uniq, counts = np.unique(users[order], return_counts=True)
         offsets = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
-        ctx, restarts = self._restarts()
-        with self._recommend_session(ctx, w, exclude_seen):
-            for _ in restarts:
-                ctx.recommend_add()
+        with self._session_of_restarts("recommend", w, exclude_seen) as ctx:
             pos, cand = ctx.recommend_positions(uniq.astype(np.int32), offsets, rows[order, 1])
         position = np.empty(len(rows), dtype=np.int64)
         position[order] = pos
