@@ -333,6 +333,49 @@ int mmsbm_hip_overlap_add(mmsbm_hip_ctx *ctx);
 int mmsbm_hip_overlap_query(mmsbm_hip_ctx *ctx, double *out);
 int mmsbm_hip_overlap_end(mmsbm_hip_ctx *ctx);
 
+/* ---- why a recommendation: which of a user's training rows carry it (mmsbm_amd/csrc/explain.hpp) ------------------- */
+/* With eta and p fixed, the theta half of the M-step is an average over the user's training rows j = (u, i_j, r_j):
+ *   v_j[k] = sum_l p[k, l, r_j] eta[i_j, l],  c_j[k] = theta_u[k] v_j[k] / max(theta_u . v_j, eps),
+ *   theta'_u[k] = (1/d_u) sum_j c_j[k],
+ * and score_w(u, t) = sum_k theta_u[k] g_t[k] with g_t[k] = sum_l W[k, l] eta[t, l] is linear in theta.  So
+ *   a(u, t, j) = (1/d_u) sum_k c_j[k] g_t[k]
+ * is the part of the recommendation of t to u that training row j carries: over ALL rows of u the a add up to the score
+ * under one more theta update, which is score_w(u, t) itself at a fixed point of EM; d_u a(u, t, j) is the score u
+ * would have for t if judged from row j alone.  Over the S added slots a is the mean of the slots' a, as the score is.
+ * A session of its own beside the other five (any of them may be open meanwhile):
+ *   begin  the R rating weights (finite), and the training rows of every external user in the order they were given to
+ *          mmsbm_hip_create (duplicate triples are separate rows).  Closes any earlier explain session;
+ *   add    the SELECTED slot joins: external copies of its theta, G = eta W^T, p and eta (the slot is left unchanged);
+ *   query  occurrence b of the request is user users[b] with the candidate items items[offsets[b] .. offsets[b + 1])
+ *          (training item ids, any order, repeats allowed; a user may appear more than once; offsets ascending from 0).
+ *          Pair q, counted in that flattened order, gets row q of hist_items / hist_ratings / contribution (n entries
+ *          each): the counts[q] = min(n, d_u) rows of u with the largest a(u, t, j), as (item, rating id, a), followed
+ *          by -1 / -1 / -inf; order: a descending, exactly equal a (fp64 equality) by ascending history item id, then
+ *          ascending rating id.  explained[q] = the sum of a over all d_u rows, score[q] = score_w(u, t), degree[q] =
+ *          d_u.  Every output except hist_items may be NULL;
+ *   end    releases the session's device memory (so does mmsbm_hip_destroy).
+ * Operation order: v one fma chain over l ascending from +0.0 (fold-in's); theta . v one fma chain over k ascending;
+ * one division 1 / max(dot, eps), c[k] = (theta[k] v[k]) times it; per row ONE fma chain over f = s K + k ascending of
+ * c_s[k] G_s[t, k], divided once by the product S d_u formed in double; explained: row j is added to partial sum j mod
+ * 64 in ascending row order and the 64 partial sums are added by the butterfly 1, 2, 4 ... 32 (a tree fixed by d_u
+ * alone); score: one fma chain over f of theta_s[u, k] G_s[t, k], divided by S -- bit for bit recommend_query's score
+ * where K <= L, equal up to rounding where K > L (recommend folds W into theta there).  No atomics.  A pair's answer
+ * depends on its user, its item and the added slots only, bit for bit: not on the other pairs of the call, on the
+ * batches, on the side layout or on slots the context holds beyond those added.  The c rows (S K doubles per training
+ * row) exist per batch of requested users only: option "explain_rows" (training rows per batch, 0: the library's choice;
+ * a user with more rows is a batch of its own) changes time and memory, never the answer.  "explain_ms" reads the device
+ * time of the last query's kernels (HIP events).
+ * MMSBM_E_INVALID: add or query without begin, query before the first add, a selected slot without parameters, an id
+ * out of range, offsets not ascending from 0, n < 1, a non-finite weight, a null pointer where one is needed; n >
+ * MMSBM_HIP_RECOMMEND_MAX_N or K > MMSBM_HIP_FOLD_IN_MAX_K: MMSBM_E_UNSUPPORTED; MMSBM_E_TOOLARGE where the device
+ * memory of the session's tables or of a batch is not free.  Touches no slot, no EM state and no other session. */
+int mmsbm_hip_explain_begin(mmsbm_hip_ctx *ctx, const double *rating_weights);
+int mmsbm_hip_explain_add(mmsbm_hip_ctx *ctx);
+int mmsbm_hip_explain_query(mmsbm_hip_ctx *ctx, int64_t n_users, const int32_t *users, const int64_t *offsets,
+                            const int32_t *items, int32_t n, int32_t *hist_items, int32_t *hist_ratings,
+                            double *contribution, int32_t *counts, double *explained, double *score, int32_t *degree);
+int mmsbm_hip_explain_end(mmsbm_hip_ctx *ctx);
+
 /* ---- held-out log-likelihood of every restart slot, and parameter snapshots (mmsbm_amd/csrc/heldout.hpp) ------------ */
 /* For a row m = (u, i, r) (external ids) and the parameters of slot s:
  *   t_s[k] = sum_l p_s[k, l, r] eta_s[i, l]     one fma chain over l ascending, from +0.0

@@ -70,6 +70,11 @@ SIGNATURES = {
     "mmsbm_hip_overlap_add": (C.c_int, [C.c_void_p]),
     "mmsbm_hip_overlap_query": (C.c_int, [C.c_void_p, c_f64p]),
     "mmsbm_hip_overlap_end": (C.c_int, [C.c_void_p]),
+    "mmsbm_hip_explain_begin": (C.c_int, [C.c_void_p, c_f64p]),
+    "mmsbm_hip_explain_add": (C.c_int, [C.c_void_p]),
+    "mmsbm_hip_explain_query": (C.c_int, [C.c_void_p, C.c_int64, c_i32p, c_i64p, c_i32p, C.c_int32, c_i32p, c_i32p,
+                                         c_f64p, c_i32p, c_f64p, c_f64p, c_i32p]),
+    "mmsbm_hip_explain_end": (C.c_int, [C.c_void_p]),
     "mmsbm_hip_heldout_begin": (C.c_int, [C.c_void_p, C.c_int64, c_i32p, c_i32p, c_i32p]),
     "mmsbm_hip_heldout_eval": (C.c_int, [C.c_void_p, c_f64p]),
     "mmsbm_hip_heldout_add": (C.c_int, [C.c_void_p, c_f64p]),

@@ -14,7 +14,8 @@ from concurrent.futures import ThreadPoolExecutor
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG_DIR, "csrc")
 # the translation units, longest compile first (tu_layout.hip carries rocPRIM's sorts)
-UNITS = ("tu_layout", "tu_fused", "tu_once", "mmsbm_hip", "tu_seg", "tu_pair", "tu_etap", "tu_mfma", "tu_recommend", "tu_fold_in", "tu_heldout")
+UNITS = ("tu_layout", "tu_fused", "tu_once", "mmsbm_hip", "tu_seg", "tu_pair", "tu_etap", "tu_mfma", "tu_recommend", "tu_fold_in", "tu_heldout",
+         "tu_explain")
 OBJ_DIR = os.path.join(PKG_DIR, "_build")
 DEPS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".hpp"))) + [
     os.path.join(os.path.dirname(PKG_DIR), "include", "mmsbm_hip.h")]

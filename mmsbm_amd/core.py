@@ -501,6 +501,40 @@ class HipEM:
         _lib.call("mmsbm_hip_overlap_end", self._h)
         self._ov = None
 
+    # -- which of a user's training rows carry a recommendation (include/mmsbm_hip.h: mmsbm_hip_explain_*) ----
+    def explain_begin(self, rating_weights):
+        """Open an explain session: the attribution of score = sum_r w_r P(r | u, i), averaged over the slots added to
+        it, to the user's training rows."""
+        w = _f64(rating_weights)
+        if w.shape != (self.n_ratings,):
+            raise ValueError(f"rating_weights has shape {w.shape}, expected ({self.n_ratings},)")
+        _lib.call("mmsbm_hip_explain_begin", self._h, _p(w, C.c_double))
+
+    def explain_add(self):
+        """Add the selected slot's current parameters to the session (the slot is left unchanged)."""
+        _lib.call("mmsbm_hip_explain_add", self._h)
+
+    def explain_query(self, users, offsets, items, n):
+        """For encoded user ids, user b with the candidate items items[offsets[b]:offsets[b + 1]]; pair q counted in that
+        flattened order: (hist_items (Q,n) int32 padded with -1, hist_ratings (Q,n) int32 padded with -1, contribution
+        (Q,n) padded with -inf, counts (Q,), explained (Q,), score (Q,), degree (Q,)) -- the n training rows of the
+        pair's user that carry most of the pair's score, contribution descending, equal ones by ascending item id, then
+        rating id; explained: the sum over ALL the user's rows."""
+        u, n = _i32(users), int(n)
+        off, it = _csr(offsets, items, len(u), "offsets", "items")
+        q = len(it)
+        hi, hr = np.empty((q, max(n, 0)), dtype=np.int32), np.empty((q, max(n, 0)), dtype=np.int32)
+        co = np.empty((q, max(n, 0)), dtype=np.float64)
+        counts, degree = np.empty(q, dtype=np.int32), np.empty(q, dtype=np.int32)
+        explained, score = np.empty(q, dtype=np.float64), np.empty(q, dtype=np.float64)
+        _lib.call("mmsbm_hip_explain_query", self._h, len(u), _p(u, C.c_int32), _p(off, C.c_int64), _p(it, C.c_int32), n,
+                  _p(hi, C.c_int32), _p(hr, C.c_int32), _p(co, C.c_double), _p(counts, C.c_int32),
+                  _p(explained, C.c_double), _p(score, C.c_double), _p(degree, C.c_int32))
+        return hi, hr, co, counts, explained, score, degree
+
+    def explain_end(self):
+        _lib.call("mmsbm_hip_explain_end", self._h)
+
     # -- held-out log-likelihood and snapshots on the device (include/mmsbm_hip.h: mmsbm_hip_heldout_*) ----
     def heldout_begin(self, rows):
         """Open a held-out session over (M,3) triples [user, item, observed rating index] (encoded ids)."""

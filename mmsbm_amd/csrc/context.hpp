@@ -163,6 +163,19 @@ struct PredictSession {
   int slots = 0;                        // slots added: predict_add calls so far
 };
 
+// The explain session (mmsbm_hip_explain_begin .. end; explain.hpp): external copies of what the attribution of a score
+// to the user's training rows reads, per added slot, and the training rows per external user.  Created by explain_begin,
+// dropped whole by explain_begin and explain_end; set_slots leaves it alone (it holds copies, nothing of a slot).
+struct ExpSession {
+  DevBuf<double> w;                     // the R rating weights
+  DevBuf<double> th, g;                 // [slot][U][K] theta, [slot][I][K] G = eta W^T
+  DevBuf<double> p, eta;                // [slot][R][K][L] p in external (k, l), [slot][I][L] eta: what v needs
+  DevBuf<int64_t> off;                  // [U + 1]: the training rows of every external user, in the order given
+  DevBuf<int32_t> item, rating;         // [n_obs]: their items and ratings (duplicate triples are separate rows)
+  std::vector<int64_t> off_h;           // off on the host (degrees, batches)
+  int slots = 0;                        // slots added
+};
+
 }  // namespace mmsbm_hip_impl
 
 namespace {
@@ -213,8 +226,8 @@ inline void sort_unique_groups(std::vector<int32_t> &off, std::vector<int32_t> &
 
 // The serving calls whose kernels are timed (mmsbm_hip_ctx::last_ms), in the order of their "<name>_ms" options:
 // recommend_query / recommend_query_items, fold_in / fold_in_items, recommend_positions, recommend_top_pairs,
-// recommend_audience, similar_query, overlap_query, heldout_eval / heldout_add
-enum TimedCall { T_RECOMMEND = 0, T_FOLD_IN, T_POSITIONS, T_TOP_PAIRS, T_AUDIENCE, T_SIMILAR, T_OVERLAP, T_HELDOUT, T_COUNT };
+// recommend_audience, similar_query, overlap_query, heldout_eval / heldout_add, explain_query
+enum TimedCall { T_RECOMMEND = 0, T_FOLD_IN, T_POSITIONS, T_TOP_PAIRS, T_AUDIENCE, T_SIMILAR, T_OVERLAP, T_HELDOUT, T_EXPLAIN, T_COUNT };
 
 enum KernelId { K_SEG = 0, K_DENSE, K_ETAP, K_MATVEC_A, K_FUSED_PAIRS, K_FUSED_TAIL, K_COUNT };
 // The four launches of an iteration -- or, for small problems, the two of fused_small.hpp.
@@ -293,10 +306,12 @@ struct mmsbm_hip_ctx {
   std::unique_ptr<mmsbm_hip_impl::SimSession> sm;      // similarity
   std::unique_ptr<mmsbm_hip_impl::OvlSession> ov;      // overlap
   std::unique_ptr<mmsbm_hip_impl::HoldSession> ho;     // held-out
+  std::unique_ptr<mmsbm_hip_impl::ExpSession> ex;      // explain
   float last_ms[T_COUNT] = {};              // device time of the last call's kernels, per TimedCall (options "<name>_ms")
   int top_groups = 0;                       // option "top_pairs_groups": workgroups of gtop_fused_kernel (0: 2 per CU)
   int64_t aud_rows = 0;                     // option "audience_rows": items per COUNT batch (0: the library's choice)
   int64_t aud_entries = 0;                  // option "audience_entries": entries per WRITE batch at most (0: likewise)
+  int64_t exp_rows = 0;                     // option "explain_rows": training rows per batch of explain_query (0: likewise)
   // snapshots (mmsbm_hip_snapshot_save / get): a second copy of theta, eta and p in the layout of theta[cur], eta[cur]
   // and p[cur], every slot's place in it filled by that slot's last save; allocated by the first save, dropped by set_slots
   DevBuf<double> snap_theta;

@@ -57,8 +57,25 @@ inline bool fold_onchip(int64_t d, int K) { return d * K <= kFoldUserLds; }
     default: CALL(64, 16); break; \
   }
 
-// v[j * K + k] = sum_l p(k, l, rating[j]) eta(item[j], l), l ascending.  p of one slot in the device layout, element
-// (k, l, r) at p + r * rs + k * ks + l * ls in external (k, l); `et`: the external items' rows.
+// THE link of v's chain (the one copy: fold_v_at here and exp_row_kernel of explain.hpp, which keeps the eta row in
+// registers): acc + p(k, l, r) eta(item, l) as one fma, `pk` = p + r * rs + k * ks.
+__device__ __forceinline__ double fold_v_step(const double *__restrict__ pk, int ls, int l, double eta_l, double acc) {
+  return fma(pk[static_cast<size_t>(l) * ls], eta_l, acc);
+}
+
+// v[k] of a row (item, rating) = sum_l p(k, l, rating) eta(item, l): ONE chain of fold_v_step over l ascending from
+// +0.0.  p of one slot, element (k, l, r) at p + r * rs + k * ks + l * ls in external (k, l); `et`: the external items'
+// rows.
+__device__ __forceinline__ double fold_v_at(const RowTab &et, const double *__restrict__ p, size_t rs, int ks, int ls,
+                                            int32_t item, int32_t rating, int k, int L) {
+  const double *pk = p + static_cast<size_t>(rating) * rs + static_cast<size_t>(k) * ks;
+  const size_t i = static_cast<size_t>(item);
+  double acc = 0.0;
+  for (int l = 0; l < L; ++l) acc = fold_v_step(pk, ls, l, *rowtab_ptr(et, i, l), acc);
+  return acc;
+}
+
+// v[j * K + k] = fold_v_at(item[j], rating[j], k) for every row j of the request and every k.
 __global__ __launch_bounds__(kBlock) void fold_v_kernel(RowTab et, const double *__restrict__ p, size_t rs, int ks,
                                                         int ls, const int32_t *__restrict__ item,
                                                         const int32_t *__restrict__ rating, int64_t rows, int K, int L,
@@ -67,11 +84,7 @@ __global__ __launch_bounds__(kBlock) void fold_v_kernel(RowTab et, const double 
   if (e >= static_cast<size_t>(rows) * K) return;
   const size_t j = e / K;
   const int k = static_cast<int>(e % K);
-  const double *pk = p + static_cast<size_t>(rating[j]) * rs + static_cast<size_t>(k) * ks;
-  const size_t i = static_cast<size_t>(item[j]);
-  double acc = 0.0;
-  for (int l = 0; l < L; ++l) acc = fma(pk[static_cast<size_t>(l) * ls], *rowtab_ptr(et, i, l), acc);
-  v[e] = acc;
+  v[e] = fold_v_at(et, p, rs, ks, ls, item[j], rating[j], k, L);
 }
 
 // One job per group of G * RS lanes: int2 (user, LDS offset in doubles); user -1: no work.  Users are local to the batch:

@@ -78,6 +78,14 @@ void heldout_begin(mmsbm_hip_ctx *c, int64_t n_rows, const int32_t *user, const 
 void heldout_eval(mmsbm_hip_ctx *c, int first, int n_slots, bool add, double *loglik);
 void heldout_mean(mmsbm_hip_ctx *c, double *mean_p, double *loglik);
 
+// tu_explain.hip -- which of a user's training rows carry a recommendation (explain.hpp): the session of
+// mmsbm_hip_explain_*, arguments checked
+void explain_begin(mmsbm_hip_ctx *c, const double *weights);
+void explain_add(mmsbm_hip_ctx *c);  // the selected slot (the caller holds a OneSlot)
+void explain_query(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, const int64_t *offsets, const int32_t *items,
+                   int n, int32_t *hist_items, int32_t *hist_ratings, double *contribution, int32_t *counts,
+                   double *explained, double *score, int32_t *degree);
+
 // dispatchers (mmsbm_hip.hip): the form the context's shape and options select
 void stage_dense(mmsbm_hip_ctx *c);
 void stage_matvec_a(mmsbm_hip_ctx *c, int slot, int a_slot, bool grid = false);

@@ -792,7 +792,7 @@ struct Option {
   void (*set)(mmsbm_hip_ctx *, double);
 };
 using Ctx = mmsbm_hip_ctx;
-// "audience_rows" / "audience_entries": 0 .. 2^31 - 1, whole
+// "audience_rows" / "audience_entries" / "explain_rows": 0 .. 2^31 - 1, whole
 void set_audience(int64_t &field, const char *name, double v) {
   if (v < 0 || v > 2147483647.0 || v != std::floor(v)) throw std::invalid_argument(std::string(name) + ": 0 .. 2^31 - 1");
   field = static_cast<int64_t>(v);
@@ -830,6 +830,7 @@ const Option kOptions[] = {
     {"overlap_ms", [](const Ctx *c) -> double { return c->last_ms[T_OVERLAP]; }, nullptr},
     {"heldout_ms", [](const Ctx *c) -> double { return c->last_ms[T_HELDOUT]; }, nullptr},
     {"audience_ms", [](const Ctx *c) -> double { return c->last_ms[T_AUDIENCE]; }, nullptr},
+    {"explain_ms", [](const Ctx *c) -> double { return c->last_ms[T_EXPLAIN]; }, nullptr},
     // workgroups of gtop_fused_kernel (top_pairs.hpp); 0: the library's choice
     {"top_pairs_groups", [](const Ctx *c) -> double { return c->top_groups; },
      [](Ctx *c, double v) {
@@ -842,6 +843,9 @@ const Option kOptions[] = {
      [](Ctx *c, double v) { set_audience(c->aud_rows, "audience_rows", v); }},
     {"audience_entries", [](const Ctx *c) -> double { return static_cast<double>(c->aud_entries); },
      [](Ctx *c, double v) { set_audience(c->aud_entries, "audience_entries", v); }},
+    // explain_query (explain.hpp): training rows per batch; 0: the library's choice.  It does not change the answer
+    {"explain_rows", [](const Ctx *c) -> double { return static_cast<double>(c->exp_rows); },
+     [](Ctx *c, double v) { set_audience(c->exp_rows, "explain_rows", v); }},
     {"launches", [](const Ctx *c) -> double { return use_fused(c) ? 2 : 4; }, nullptr},  // per iteration at the current slot count
     {"wide", [](const Ctx *c) -> double { return c->pp.wide; }, nullptr},
     // 0: a logarithm per element; 1: logarithm tables, a group of lanes per triple; 2: where it applies a wave per pair
@@ -1724,6 +1728,48 @@ int mmsbm_hip_overlap_query(mmsbm_hip_ctx *ctx, double *out) {
 }
 
 int mmsbm_hip_overlap_end(mmsbm_hip_ctx *ctx) { return end_session(ctx, &mmsbm_hip_ctx::ov); }
+
+int mmsbm_hip_explain_begin(mmsbm_hip_ctx *ctx, const double *rating_weights) {
+  return guarded([&] {
+    if (!ctx || !rating_weights) throw std::invalid_argument("null argument");
+    for (int r = 0; r < ctx->n_ratings; ++r)
+      if (!std::isfinite(rating_weights[r]))
+        throw std::invalid_argument("explain: rating weight " + std::to_string(r) + " is not finite");
+    if (ctx->ext_k > MMSBM_HIP_FOLD_IN_MAX_K)
+      throw ApiError(MMSBM_E_UNSUPPORTED, "explain: K = " + std::to_string(ctx->ext_k) + " is beyond the " +
+                                              std::to_string(MMSBM_HIP_FOLD_IN_MAX_K) + " groups it is built for");
+    explain_begin(ctx, rating_weights);
+  });
+}
+
+int mmsbm_hip_explain_add(mmsbm_hip_ctx *ctx) {
+  return guarded([&] {
+    require_params(ctx);
+    require_open(ctx, &mmsbm_hip_ctx::ex, "explain");
+    OneSlot one(ctx);
+    explain_add(ctx);
+  });
+}
+
+int mmsbm_hip_explain_query(mmsbm_hip_ctx *ctx, int64_t n_users, const int32_t *users, const int64_t *offsets,
+                            const int32_t *items, int32_t n, int32_t *hist_items, int32_t *hist_ratings,
+                            double *contribution, int32_t *counts, double *explained, double *score, int32_t *degree) {
+  return guarded([&] {
+    require_open(ctx, &mmsbm_hip_ctx::ex, "explain", "explain_query");
+    if (n_users < 0) throw std::invalid_argument("negative n_users");
+    require_n(n, "explain", "rows");
+    if (n_users > 0 && (!users || !offsets)) throw std::invalid_argument("null argument");
+    require_ids(users, n_users, ctx->ext_users, "explain: user");
+    check_csr(offsets, items, n_users, ctx->ext_items, "explain", "offsets", "user", "pairs", "item id");
+    if (n_users > 0 && offsets[n_users] > 0 && !hist_items) throw std::invalid_argument("null argument");
+    if (n_users > 0 && offsets[n_users] * static_cast<int64_t>(n) > INT32_MAX)
+      throw std::invalid_argument("explain: more than 2^31 - 1 entries in one query");
+    explain_query(ctx, n_users, users, offsets, items, n, hist_items, hist_ratings, contribution, counts, explained,
+                  score, degree);
+  });
+}
+
+int mmsbm_hip_explain_end(mmsbm_hip_ctx *ctx) { return end_session(ctx, &mmsbm_hip_ctx::ex); }
 
 int mmsbm_hip_heldout_begin(mmsbm_hip_ctx *ctx, int64_t n_rows, const int32_t *user, const int32_t *item,
                             const int32_t *rating) {

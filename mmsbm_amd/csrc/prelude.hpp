@@ -15,6 +15,7 @@
 //                     and the overlap of the restarts' groups (overlap.hpp)
 //   tu_fold_in.hip    fold new users into a fitted model (fold_in.hpp)
 //   tu_heldout.hip    held-out log-likelihood of every restart slot (heldout.hpp)
+//   tu_explain.hip    which of a user's training rows carry a recommendation (explain.hpp)
 // unity.hip includes them all into ONE unit: the diagnostic builds (-DMMSBM_STAMPS, -DMMSBM_ABLATE) and
 // scripts/kernel_resources.sh use it.
 #pragma once

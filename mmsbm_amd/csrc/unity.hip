@@ -16,3 +16,4 @@
 #include "tu_recommend.hip"
 #include "tu_fold_in.hip"
 #include "tu_heldout.hip"
+#include "tu_explain.hip"

@@ -514,6 +514,75 @@ class MMSBM:
             "score": scores[:count],
             "rank": np.arange(1, count + 1, dtype=np.int64)})
 
+    def explain(self, pairs, n=5, weights=None):
+        """Why an item is recommended to a user: the ``n`` training rows of the user that carry most of the pair's
+        score -- the "because you rated ..." of a recommendation -- found on the device.
+
+        With eta and p fixed, the theta half of the M-step writes a user's membership as an average over the user's
+        d_u training rows j = (u, i_j, r_j): theta'_u[k] = (1/d_u) sum_j c_j[k], where c_j[k] = theta_u[k] v_j[k] /
+        (theta_u . v_j) is the share of row j that group k takes and v_j[k] = sum_l p[k, l, r_j] eta[i_j, l].  The score
+        is linear in theta, score(u, t) = sum_k theta_u[k] g_t[k] with g_t[k] = sum_l (sum_r weights[r] p[k, l, r])
+        eta[t, l], so contribution(u, t, j) = (1/d_u) sum_k c_j[k] g_t[k] is the part of the score that row j carries
+        (d_u times it: the score u would have for t if judged from row j alone).  The contributions of ALL the user's
+        rows, not only the ``n`` returned, sum to ``explained``, the score under one more theta update; ``explained``
+        equals ``score`` at a fixed point of EM, so ``score - explained`` is how far that user's theta is from one.
+        Everything is the mean over the restarts the model holds.
+
+        ``pairs``: a DataFrame whose first two columns are users and items (further columns are ignored, so
+        ``model.explain(model.recommend(users=[...]))`` works as is), or an iterable of (user, item) tuples; both must
+        be in the training data (KeyError).  Returns a DataFrame with columns ``users``, ``items``, ``because`` (the
+        history item), ``rating`` (the rating the user gave it), ``contribution``, ``share`` (contribution /
+        explained), ``rank`` (1 = the largest contribution), ``score``, ``explained`` (both repeated on a pair's rows):
+        pairs in request order, labels as ``recommend`` returns them; within a pair contribution descending, equal
+        ones by ascending encoded history item id, then rating id.  The model's stored predictions and ``score()`` are
+        left as they are."""
+        import pandas as pd
+        self._check_whole_model()
+        n, w = self._recommend_args(n, weights)
+        if hasattr(pairs, "iloc") and hasattr(pairs, "columns"):
+            if pairs.shape[1] < 2:
+                raise ValueError("pairs needs two columns: users and items")
+            us, its = pairs.iloc[:, 0].tolist(), pairs.iloc[:, 1].tolist()
+        else:
+            rows = [tuple(x) for x in pairs]
+            if any(len(x) != 2 for x in rows):
+                raise ValueError("pairs must be (user, item) tuples")
+            us, its = [x[0] for x in rows], [x[1] for x in rows]
+        uid, ulab = self._training_ids(us, "users")
+        iid, ilab = self._training_ids(its, "items")
+        enc = self.data_handler
+        item_labels = np.asarray(enc.item_labels(), dtype=object) if enc else None
+        rating_labels = np.asarray(enc.rating_labels(), dtype=object) if enc else None
+        q_all = len(uid)
+        step = max(1, self.RECOMMEND_BATCH_ROWS // n)
+        parts = []
+        with self._session_of_restarts("explain", w) as ctx:
+            for b in range(0, q_all, step):
+                e = min(q_all, b + step)
+                u = uid[b:e]
+                first = np.flatnonzero(np.concatenate([[True], u[1:] != u[:-1]]))   # runs of one user: one occurrence
+                off = np.concatenate([first, [e - b]]).astype(np.int64)
+                hi, hr, co, counts, explained, score, _ = ctx.explain_query(u[first], off, iid[b:e], n)
+                keep = np.arange(n)[None, :] < counts[:, None]
+                at = np.repeat(np.arange(b, e), counts)
+                it, rt, cv = hi[keep], hr[keep], co[keep]
+                ex = explained[at - b]
+                parts.append(pd.DataFrame({
+                    "users": ulab[at] if len(at) else np.empty(0, dtype=object),
+                    "items": ilab[at] if len(at) else np.empty(0, dtype=object),
+                    "because": item_labels[it] if item_labels is not None else it.astype(np.int64),
+                    "rating": rating_labels[rt] if rating_labels is not None else rt.astype(np.int64),
+                    "contribution": cv,
+                    "share": cv / ex,
+                    "rank": np.nonzero(keep)[1].astype(np.int64) + 1,
+                    "score": score[at - b],
+                    "explained": ex}))
+        if not parts:
+            return pd.DataFrame({"users": [], "items": [], "because": [], "rating": [], "contribution": np.zeros(0),
+                                 "share": np.zeros(0), "rank": np.zeros(0, dtype=np.int64), "score": np.zeros(0),
+                                 "explained": np.zeros(0)})
+        return pd.concat(parts, ignore_index=True)
+
     @staticmethod
     @contextlib.contextmanager
     def _recommend_session(ctx, weights, exclude_seen):
@@ -526,7 +595,7 @@ class MMSBM:
 
     @contextlib.contextmanager
     def _session_of_restarts(self, kind, *begin_args):
-        """The context, with its ``kind`` session ("recommend", "similar", "overlap") begun with ``begin_args`` and
+        """The context, with its ``kind`` session ("recommend", "similar", "overlap", "explain") begun with ``begin_args`` and
         every restart the model holds added to it, around the block; the session is ended however the block ends."""
         ctx, restarts = self._restarts()
         getattr(ctx, kind + "_begin")(*begin_args)
