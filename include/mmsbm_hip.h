@@ -283,6 +283,41 @@ int mmsbm_hip_recommend_query_items(mmsbm_hip_ctx *ctx, int64_t n_items, const i
 int mmsbm_hip_recommend_audience(mmsbm_hip_ctx *ctx, int64_t n_items, const int32_t *items, double min_score,
                                  int64_t capacity, int64_t *offsets, int32_t *users, double *scores);
 
+/* Queries within a part of the catalogue, inside the open recommend session (mmsbm_amd/csrc/catalogue.hpp): the items
+ * in stock, of one category, released this week; items a user has dismissed; the candidates a cheap retriever proposes.
+ * score_w(u, i) is bit for bit what query returns for the pair, in swapped and unswapped contexts, and the order is
+ * query's (score descending, equal scores by ascending item id) cut to the candidates: each answer is the user's row
+ * of query(n = all items), filtered to the candidates and cut to n.  Output as query's: items / scores [n_users][n],
+ * row b holding counts[b] = min(n, candidates left) entries, then -1 / -inf (scores, counts may be NULL).  All three
+ * touch no slot, no EM state, no other session and nothing of the recommend session: a later query answers as before.
+ * "recommend_ms" reads the device time of the call's kernels.  MMSBM_E_INVALID (before any launch): no session, no
+ * slot added, an id out of range, a candidate list that is not strictly ascending (a repeat included), a bad CSR,
+ * n < 1; n > MMSBM_HIP_RECOMMEND_MAX_N: MMSBM_E_UNSUPPORTED; MMSBM_E_TOOLARGE where the device memory is not free.
+ *
+ * query_within: the candidates are cand_items[0 .. n_cand), strictly ascending ids of the session's catalogue (ids of
+ * recommend_add_items included), shared by the users of the call; cand_items NULL: the whole catalogue (n_cand
+ * ignored) -- then, without excl_offsets, the call IS query.  Left out for row b: what query leaves out for users[b],
+ * and excl_items[excl_offsets[b] .. excl_offsets[b + 1]) (excl_offsets: int64 [n_users + 1] or NULL; ids of the
+ * catalogue, any order, repeats allowed, items outside the candidates are ignored).  The lists go by the row's place in
+ * the request: a user asked twice may carry two lists.  n_cand == 0: every count is 0.  The scores of n_users x n_cand
+ * pairs are formed, not n_users x items: the candidates' rows are gathered into a compact table first.
+ *
+ * query_theta_within: query_theta (caller-given theta rows, seen lists per row) within cand_items as above.
+ *
+ * rank: row b's candidates are cand_items[offsets[b] .. offsets[b + 1]) (offsets: int64 [n_users + 1]), each list
+ * strictly ascending, of any length; users may repeat.  What query leaves out for users[b] is left out.  One wave per
+ * row scores and selects its list; no buffer of scores exists. */
+int mmsbm_hip_recommend_query_within(mmsbm_hip_ctx *ctx, int64_t n_users, const int32_t *users, int32_t n_cand,
+                                     const int32_t *cand_items, const int64_t *excl_offsets,
+                                     const int32_t *excl_items, int32_t n, int32_t *items, double *scores,
+                                     int32_t *counts);
+int mmsbm_hip_recommend_query_theta_within(mmsbm_hip_ctx *ctx, int64_t n_users, const double *theta,
+                                           const int64_t *seen_offsets, const int32_t *seen_items, int32_t n_cand,
+                                           const int32_t *cand_items, int32_t n, int32_t *items, double *scores,
+                                           int32_t *counts);
+int mmsbm_hip_recommend_rank(mmsbm_hip_ctx *ctx, int64_t n_users, const int32_t *users, const int64_t *offsets,
+                             const int32_t *cand_items, int32_t n, int32_t *items, double *scores, int32_t *counts);
+
 /* ---- nearest items / users: the n most similar rows of one side (mmsbm_amd/csrc/similar.hpp) -------------------- */
 /* A session of its own beside the recommend session (either may be open while the other is):
  *   begin  side 0: items, 1: users (external sides).  Closes any earlier similarity session;

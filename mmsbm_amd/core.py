@@ -371,10 +371,11 @@ class HipEM:
         """(items (M,n) int32 padded with -1, scores (M,n) padded with -inf, counts (M,)) for encoded user ids."""
         return self._top_n("mmsbm_hip_recommend_query", users, n)
 
-    def recommend_query_theta(self, theta, n, seen=None):
+    def recommend_query_theta(self, theta, n, seen=None, candidates=None):
         """recommend_query for caller-given users: theta (S, M, K), one (M, K) block per added slot in add order.
         seen: None (nothing excluded) or (offsets (M+1,) int64, items int32): user b leaves out
-        items[offsets[b]:offsets[b + 1]]."""
+        items[offsets[b]:offsets[b + 1]].  candidates: None (the whole catalogue) or ascending, distinct item ids of
+        the session's catalogue, as in recommend_query_within."""
         t = _f64(theta)
         if t.ndim != 3 or t.shape[2] != self.k:
             raise ValueError(f"theta has shape {t.shape}, expected (slots, users, {self.k})")
@@ -383,10 +384,43 @@ class HipEM:
         m, n = t.shape[1], int(n)
         off, it = (None, None) if seen is None else _csr(seen[0], seen[1], m, "seen offsets", "items")
         items, scores, counts = self._query_out(m, n)
-        _lib.call("mmsbm_hip_recommend_query_theta", self._h, m, _p(t, C.c_double),
+        head = (self._h, m, _p(t, C.c_double), None if off is None else _p(off, C.c_int64),
+                None if it is None else _p(it, C.c_int32))
+        tail = (n, _p(items, C.c_int32), _p(scores, C.c_double), _p(counts, C.c_int32))
+        if candidates is None:
+            _lib.call("mmsbm_hip_recommend_query_theta", *head, *tail)
+        else:
+            cand = _i32(candidates)
+            _lib.call("mmsbm_hip_recommend_query_theta_within", *head, len(cand), _p(cand, C.c_int32), *tail)
+        return items, scores, counts
+
+    def recommend_query_within(self, users, n, candidates=None, exclude=None):
+        """recommend_query within a part of the catalogue: the n best of ``candidates`` (ascending, distinct item ids
+        of the session's catalogue; None: all of it) for each encoded user id, without what recommend_query leaves out
+        and without ``exclude``: None or (offsets (M+1,) int64, items int32), request row b also leaves out
+        items[offsets[b]:offsets[b + 1]] (any order; a user asked twice may carry two lists).  Scores and order are
+        recommend_query's: the answer is its row for n = all items, filtered and cut to n."""
+        u, n = _i32(users), int(n)
+        cand = None if candidates is None else _i32(candidates)
+        off, it = (None, None) if exclude is None else _csr(exclude[0], exclude[1], len(u), "exclude offsets", "items")
+        items, scores, counts = self._query_out(len(u), n)
+        _lib.call("mmsbm_hip_recommend_query_within", self._h, len(u), _p(u, C.c_int32),
+                  0 if cand is None else len(cand), None if cand is None else _p(cand, C.c_int32),
                   None if off is None else _p(off, C.c_int64), None if it is None else _p(it, C.c_int32), n,
                   _p(items, C.c_int32), _p(scores, C.c_double), _p(counts, C.c_int32))
         return items, scores, counts
+
+    def recommend_rank(self, users, offsets, items, n):
+        """The order of caller-given candidates, one list per request row: row b's candidates are
+        items[offsets[b]:offsets[b + 1]] (ascending, distinct item ids of the session's catalogue) for encoded user
+        users[b].  Returns recommend_query's triple: the n best of each list, without what recommend_query leaves
+        out for the user; scores and order are recommend_query's, bit for bit."""
+        u, n = _i32(users), int(n)
+        off, it = _csr(offsets, items, len(u), "offsets", "items")
+        out, scores, counts = self._query_out(len(u), n)
+        _lib.call("mmsbm_hip_recommend_rank", self._h, len(u), _p(u, C.c_int32), _p(off, C.c_int64),
+                  _p(it, C.c_int32), n, _p(out, C.c_int32), _p(scores, C.c_double), _p(counts, C.c_int32))
+        return out, scores, counts
 
     def recommend_positions(self, users, offsets, items):
         """(positions, candidates): the position (1 = best, 0 = not a candidate) of each item in its user's full

@@ -56,6 +56,17 @@ void recommend_query_items(mmsbm_hip_ctx *c, int64_t n_items, const int32_t *ite
                            double *scores, int32_t *counts);
 void recommend_audience(mmsbm_hip_ctx *c, int64_t n_items, const int32_t *items, double min_score, int64_t capacity,
                         int64_t *offsets, int32_t *users, double *scores);
+// ... queries within a part of the catalogue (catalogue.hpp): cand ascending, distinct ids of the session's catalogue
+// (null: all of it); excl_*: the query's own excluded items by request row (null: none); recommend_rank: one ascending,
+// distinct candidate list per request row
+void recommend_query_within(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, const int32_t *cand, int n_cand,
+                            const int64_t *excl_offsets, const int32_t *excl_items, int n, int32_t *items,
+                            double *scores, int32_t *counts);
+void recommend_query_theta_within(mmsbm_hip_ctx *c, int64_t n_users, const double *theta, const int64_t *seen_offsets,
+                                  const int32_t *seen_items, const int32_t *cand, int n_cand, int n, int32_t *items,
+                                  double *scores, int32_t *counts);
+void recommend_rank(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, const int64_t *offsets,
+                    const int32_t *cand, int n, int32_t *items, double *scores, int32_t *counts);
 // ... and nearest items / users (similar.hpp): the session of mmsbm_hip_similar_*, arguments checked
 void similar_begin(mmsbm_hip_ctx *c, int side);
 void similar_add(mmsbm_hip_ctx *c);  // the selected slot (the caller holds a OneSlot)

@@ -1671,6 +1671,77 @@ int mmsbm_hip_recommend_audience(mmsbm_hip_ctx *ctx, int64_t n_items, const int3
   });
 }
 
+namespace {
+// A candidate list of `who`: v[0 .. n) strictly ascending (so distinct) ids in [0, top)
+void require_candidates(const int32_t *v, int64_t first, int64_t n, int32_t top, const char *who) {
+  for (int64_t e = 0; e < n; ++e) {
+    if (v[e] < 0 || v[e] >= top)
+      throw std::invalid_argument(std::string(who) + ": candidate item id out of range at entry " + std::to_string(first + e));
+    if (e > 0 && v[e] <= v[e - 1])
+      throw std::invalid_argument(std::string(who) + ": candidate items must be ascending and distinct (entry " +
+                                  std::to_string(first + e) + ")");
+  }
+}
+// n_cand / cand_items of the two *_within entries (cand_items null: the whole catalogue, n_cand ignored)
+void require_subset(const int32_t *cand_items, int32_t n_cand, int32_t top, const char *who) {
+  if (!cand_items) return;
+  if (n_cand < 0 || n_cand > top)
+    throw std::invalid_argument(std::string(who) + ": n_cand outside [0, items of the catalogue]");
+  require_candidates(cand_items, 0, n_cand, top, who);
+}
+}  // namespace
+
+int mmsbm_hip_recommend_query_within(mmsbm_hip_ctx *ctx, int64_t n_users, const int32_t *users, int32_t n_cand,
+                                     const int32_t *cand_items, const int64_t *excl_offsets,
+                                     const int32_t *excl_items, int32_t n, int32_t *items, double *scores,
+                                     int32_t *counts) {
+  return guarded([&] {
+    const RecSession &rc = require_open(ctx, &mmsbm_hip_ctx::rc, "recommend", "recommend_query_within");
+    if (n_users < 0) throw std::invalid_argument("negative n_users");
+    require_n(n, "recommend", "items");
+    if (n_users > 0 && (!users || !items)) throw std::invalid_argument("null argument");
+    require_ids(users, n_users, ctx->ext_users, "recommend: user");
+    require_subset(cand_items, n_cand, rc.items, "recommend_query_within");
+    check_csr(excl_offsets, excl_items, n_users, rc.items, "recommend_query_within", "excl_offsets", "user",
+              "excluded items", "excluded item");
+    recommend_query_within(ctx, n_users, users, cand_items, n_cand, n_users > 0 ? excl_offsets : nullptr, excl_items, n,
+                           items, scores, counts);
+  });
+}
+
+int mmsbm_hip_recommend_query_theta_within(mmsbm_hip_ctx *ctx, int64_t n_users, const double *theta,
+                                           const int64_t *seen_offsets, const int32_t *seen_items, int32_t n_cand,
+                                           const int32_t *cand_items, int32_t n, int32_t *items, double *scores,
+                                           int32_t *counts) {
+  return guarded([&] {
+    const RecSession &rc = require_open(ctx, &mmsbm_hip_ctx::rc, "recommend", "recommend_query_theta_within");
+    if (n_users < 0) throw std::invalid_argument("negative n_users");
+    require_n(n, "recommend", "items");
+    if (n_users > 0 && (!theta || !items)) throw std::invalid_argument("null argument");
+    require_subset(cand_items, n_cand, rc.items, "recommend_query_theta_within");
+    check_csr(seen_offsets, seen_items, n_users, rc.items, "recommend", "seen_offsets", "user", "seen items",
+              "seen item");
+    recommend_query_theta_within(ctx, n_users, theta, seen_offsets, seen_items, cand_items, n_cand, n, items, scores,
+                                 counts);
+  });
+}
+
+int mmsbm_hip_recommend_rank(mmsbm_hip_ctx *ctx, int64_t n_users, const int32_t *users, const int64_t *offsets,
+                             const int32_t *cand_items, int32_t n, int32_t *items, double *scores, int32_t *counts) {
+  return guarded([&] {
+    const RecSession &rc = require_open(ctx, &mmsbm_hip_ctx::rc, "recommend", "recommend_rank");
+    if (n_users < 0) throw std::invalid_argument("negative n_users");
+    require_n(n, "recommend", "items");
+    if (n_users > 0 && (!users || !offsets || !items)) throw std::invalid_argument("null argument");
+    require_ids(users, n_users, ctx->ext_users, "recommend_rank: user");
+    check_csr(offsets, cand_items, n_users, rc.items, "recommend_rank", "offsets", "user", "candidate items",
+              "candidate item id");
+    for (int64_t b = 0; b < n_users; ++b)
+      require_candidates(cand_items + offsets[b], offsets[b], offsets[b + 1] - offsets[b], rc.items, "recommend_rank");
+    recommend_rank(ctx, n_users, users, offsets, cand_items, n, items, scores, counts);
+  });
+}
+
 int mmsbm_hip_similar_begin(mmsbm_hip_ctx *ctx, int side) {
   return guarded([&] {
     if (!ctx) throw std::invalid_argument("null context");

@@ -4,13 +4,16 @@
 // the whole model (top_pairs.hpp), a query of the recommend session with kernels of its own; and the overlap of the
 // restarts' groups (overlap.hpp), whose session copies a slot's rows with the recommend session's rec_fold_kernel; and
 // the item-side queries of the recommend session (audience.hpp): the n best users of an item through the same batches
-// and selection, and the audience of an item above a bar through a fused kernel of its own
+// and selection, and the audience of an item above a bar through a fused kernel of its own; and the queries within a
+// part of the catalogue (catalogue.hpp): a subset of the items through the same batches and selection over a compact
+// item table, and per-user candidate lists through a kernel of their own
 #include "prelude.hpp"
 #include "recommend.hpp"
 #include "similar.hpp"
 #include "overlap.hpp"
 #include "top_pairs.hpp"
 #include "audience.hpp"
+#include "catalogue.hpp"
 
 #include <climits>
 
@@ -284,19 +287,89 @@ void rec_run(mmsbm_hip_ctx *c, const double *x, size_t xs, int64_t n_users, cons
             T_RECOMMEND, items, scores, counts);
 }
 
-}  // namespace
-
-void recommend_query(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, int n, int32_t *items, double *scores,
-                     int32_t *counts) {
-  use_device(c);
+// rec_run within the candidates cand[0 .. n_cand) (host; ascending, distinct ids of the session's catalogue; null: the
+// whole catalogue), and with the query's own excluded items: row b of the request also leaves out xit[xoff[b] ..
+// xoff[b + 1]) (host, any order, repeats allowed; null: none).  catalogue.hpp.  Without either: rec_run.
+void rec_run_within(mmsbm_hip_ctx *c, const double *x, size_t xs, int64_t n_users, const int32_t *users,
+                    const int32_t *seen_off, const int32_t *seen, const int32_t *cand, int n_cand, const int64_t *xoff,
+                    const int32_t *xit, int n, int32_t *items, double *scores, int32_t *counts) {
   const RecSession &rc = *c->rc;
-  rec_run(c, rc.x.ptr, static_cast<size_t>(c->ext_users) * rc.rank, n_users, users, rc.excl ? rc.seen_off.ptr : nullptr,
-          rc.seen.ptr, n, items, scores, counts);
+  const int NI = rc.items, rank = rc.rank, S = rc.slots;
+  if (!cand && !xoff) {
+    rec_run(c, x, xs, n_users, users, seen_off, seen, n, items, scores, counts);
+    return;
+  }
+  const int C = cand ? n_cand : NI;
+  if (C == 0 || n_users == 0) {  // (no column to score: every row is empty)
+    for (int64_t b = 0; b < n_users; ++b) {
+      if (counts) counts[b] = 0;
+      for (int k = 0; k < n; ++k) {
+        items[static_cast<size_t>(b) * n + k] = -1;
+        if (scores) scores[static_cast<size_t>(b) * n + k] = -INFINITY;
+      }
+    }
+    c->last_ms[T_RECOMMEND] = 0.f;
+    return;
+  }
+  hipStream_t st = c->stream;
+  const int64_t n_x = xoff ? xoff[n_users] : 0;  // (checked: below 2^31)
+  const size_t ycs = static_cast<size_t>(C) * rank;
+  require_free_mem((cand ? S * ycs * sizeof(double) + (static_cast<size_t>(C) + NI) * 4 : 0) +
+                       (static_cast<size_t>(n_users) + 1 + n_x) * 4,
+                   "recommend: the candidates' rows and the query's excluded items");
+  DevBuf<int32_t> dxo, dxi, dcand, dcol;
+  DevBuf<double> yc;
+  std::vector<int32_t> hxo;
+  if (xoff) {
+    hxo.assign(xoff, xoff + n_users + 1);
+    dxo.upload(hxo, st);
+    dxi.alloc(static_cast<size_t>(n_x));
+    if (n_x > 0) HIP_CHECK(hipMemcpyAsync(dxi.ptr, xit, sizeof(int32_t) * n_x, hipMemcpyHostToDevice, st));
+  }
+  float prep_ms = 0.f;  // device time of the compact table and the columns (added to "recommend_ms")
+  if (cand) {
+    dcand.alloc(static_cast<size_t>(C));
+    dcol.alloc(static_cast<size_t>(NI));
+    yc.alloc(S * ycs);
+    HIP_CHECK(hipMemcpyAsync(dcand.ptr, cand, sizeof(int32_t) * C, hipMemcpyHostToDevice, st));
+    EventPair ev;
+    ev.start(st);
+    LAUNCH(cat_gather_kernel, static_cast<unsigned>((S * ycs + kBlock - 1) / kBlock), kBlock, 0, st, rc.y.ptr,
+           static_cast<size_t>(NI) * rank, dcand.ptr, C, rank, S, yc.ptr);
+    LAUNCH(cat_cols_kernel, static_cast<unsigned>((NI + kBlock - 1) / kBlock), kBlock, 0, st, dcand.ptr, C, NI, dcol.ptr);
+    HIP_CHECK(hipGetLastError());
+    ev.stop(st);
+    HIP_CHECK(hipStreamSynchronize(st));
+    prep_ms = ev.ms();
+  }
+  int64_t done = 0;  // rows of the request the earlier batches held (the batches follow each other)
+  top_n_run(c, C, n_users, users, n, "recommend: a batch of users within the candidates",
+            [&](const int32_t *ub, int nb, double *sc) {
+              if (cand) {
+                const dim3 g(static_cast<unsigned>((C + kRecTile - 1) / kRecTile), static_cast<unsigned>((nb + kRecTile - 1) / kRecTile));
+                LAUNCH(rec_score_kernel, g, kBlock, 0, st, x, xs, yc.ptr, ycs, ub, nb, C, rank, S, sc, static_cast<size_t>(C));
+                if (seen_off)
+                  LAUNCH(cat_exclude_kernel, nb, kBlock, 0, st, ub, 0, seen_off, seen, dcol.ptr, sc, static_cast<size_t>(C));
+              } else {
+                rec_score_batch(c, x, xs, ub, nb, seen_off, seen, sc);
+              }
+              if (xoff)
+                LAUNCH(cat_exclude_kernel, nb, kBlock, 0, st, static_cast<const int32_t *>(nullptr), static_cast<int>(done),
+                       dxo.ptr, dxi.ptr, cand ? dcol.ptr : static_cast<const int32_t *>(nullptr), sc, static_cast<size_t>(C));
+              done += nb;
+            },
+            T_RECOMMEND, items, scores, counts);
+  c->last_ms[T_RECOMMEND] += prep_ms;
+  if (cand)  // columns -> item ids
+    for (size_t e = 0; e < static_cast<size_t>(n_users) * n; ++e)
+      if (items[e] >= 0) items[e] = cand[items[e]];
 }
 
-void recommend_query_theta(mmsbm_hip_ctx *c, int64_t n_users, const double *theta, const int64_t *seen_offsets,
-                           const int32_t *seen_items, int n, int32_t *items, double *scores, int32_t *counts) {
-  use_device(c);
+// The caller's theta rows [S][n_users][K] folded exactly as recommend_add folds a slot's own theta (x = theta, or
+// theta W when K > L), then rec_run_within over the rows 0 .. n_users - 1 with the caller's seen lists
+void rec_theta_run(mmsbm_hip_ctx *c, int64_t n_users, const double *theta, const int64_t *seen_offsets,
+                   const int32_t *seen_items, const int32_t *cand, int n_cand, int n, int32_t *items, double *scores,
+                   int32_t *counts) {
   const int K = c->ext_k, L = c->ext_l, rank = c->rc->rank, S = c->rc->slots;
   const size_t tk = static_cast<size_t>(n_users) * K, xs = static_cast<size_t>(n_users) * rank;
   const int64_t n_seen = seen_offsets && n_users > 0 ? seen_offsets[n_users] : 0;
@@ -326,7 +399,97 @@ void recommend_query_theta(mmsbm_hip_ctx *c, int64_t n_users, const double *thet
            x.ptr + s * xs, static_cast<int>(n_users), rank);
   }
   HIP_CHECK(hipGetLastError());
-  rec_run(c, x.ptr, xs, n_users, hid.data(), seen_offsets ? soff.ptr : nullptr, sit.ptr, n, items, scores, counts);
+  rec_run_within(c, x.ptr, xs, n_users, hid.data(), seen_offsets ? soff.ptr : nullptr, sit.ptr, cand, n_cand, nullptr,
+                 nullptr, n, items, scores, counts);
+}
+
+}  // namespace
+
+void recommend_query(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, int n, int32_t *items, double *scores,
+                     int32_t *counts) {
+  use_device(c);
+  const RecSession &rc = *c->rc;
+  rec_run(c, rc.x.ptr, static_cast<size_t>(c->ext_users) * rc.rank, n_users, users, rc.excl ? rc.seen_off.ptr : nullptr,
+          rc.seen.ptr, n, items, scores, counts);
+}
+
+void recommend_query_theta(mmsbm_hip_ctx *c, int64_t n_users, const double *theta, const int64_t *seen_offsets,
+                           const int32_t *seen_items, int n, int32_t *items, double *scores, int32_t *counts) {
+  use_device(c);
+  rec_theta_run(c, n_users, theta, seen_offsets, seen_items, nullptr, 0, n, items, scores, counts);
+}
+
+void recommend_query_within(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, const int32_t *cand, int n_cand,
+                            const int64_t *excl_offsets, const int32_t *excl_items, int n, int32_t *items,
+                            double *scores, int32_t *counts) {
+  use_device(c);
+  const RecSession &rc = *c->rc;
+  rec_run_within(c, rc.x.ptr, static_cast<size_t>(c->ext_users) * rc.rank, n_users, users,
+                 rc.excl ? rc.seen_off.ptr : nullptr, rc.seen.ptr, cand, n_cand, excl_offsets, excl_items, n, items,
+                 scores, counts);
+}
+
+void recommend_query_theta_within(mmsbm_hip_ctx *c, int64_t n_users, const double *theta, const int64_t *seen_offsets,
+                                  const int32_t *seen_items, const int32_t *cand, int n_cand, int n, int32_t *items,
+                                  double *scores, int32_t *counts) {
+  use_device(c);
+  rec_theta_run(c, n_users, theta, seen_offsets, seen_items, cand, n_cand, n, items, scores, counts);
+}
+
+void recommend_rank(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, const int64_t *offsets,
+                    const int32_t *cand, int n, int32_t *items, double *scores, int32_t *counts) {
+  use_device(c);
+  const RecSession &rc = *c->rc;
+  for (int64_t b = 0; b < n_users; ++b) {
+    if (counts) counts[b] = 0;
+    for (int k = 0; k < n; ++k) {
+      items[static_cast<size_t>(b) * n + k] = -1;
+      if (scores) scores[static_cast<size_t>(b) * n + k] = -INFINITY;
+    }
+  }
+  c->last_ms[T_RECOMMEND] = 0.f;
+  if (n_users == 0) return;
+  hipStream_t st = c->stream;
+  const int64_t total = offsets[n_users];  // (checked: below 2^31)
+  int cap = 1;
+  while (cap < n + kRecWave * kRecPerLane) cap <<= 1;
+  const size_t lds = static_cast<size_t>(cap) * (sizeof(double) + sizeof(int32_t));
+  const size_t outs = static_cast<size_t>(n_users) * n;
+  require_free_mem(outs * 12 + (2 * static_cast<size_t>(n_users) + 1 + static_cast<size_t>(total)) * 4 +
+                       static_cast<size_t>(n_users) * 4,
+                   "recommend_rank: the users' lists and results");
+  std::vector<int32_t> hoff(offsets, offsets + n_users + 1);
+  DevBuf<int32_t> du, doff, dc, oi, on;
+  DevBuf<double> os;
+  du.alloc(static_cast<size_t>(n_users));
+  doff.upload(hoff, st);
+  dc.alloc(static_cast<size_t>(total));
+  os.alloc(outs); oi.alloc(outs); on.alloc(static_cast<size_t>(n_users));
+  HIP_CHECK(hipMemcpyAsync(du.ptr, users, sizeof(int32_t) * n_users, hipMemcpyHostToDevice, st));
+  if (total > 0) HIP_CHECK(hipMemcpyAsync(dc.ptr, cand, sizeof(int32_t) * total, hipMemcpyHostToDevice, st));
+  EventPair ev;  // device time of the query's kernel (option "recommend_ms")
+  ev.start(st);
+  LAUNCH(cat_rank_kernel, static_cast<unsigned>(n_users), kRecWave, lds, st, rc.x.ptr,
+         static_cast<size_t>(c->ext_users) * rc.rank, rc.y.ptr, static_cast<size_t>(rc.items) * rc.rank, rc.rank, rc.slots,
+         du.ptr, doff.ptr, dc.ptr, rc.excl ? rc.seen_off.ptr : nullptr, rc.seen.ptr, n, cap, os.ptr, oi.ptr, on.ptr);
+  HIP_CHECK(hipGetLastError());
+  ev.stop(st);
+  std::vector<double> hs(outs);
+  std::vector<int32_t> hi(outs), hn(static_cast<size_t>(n_users));
+  HIP_CHECK(hipMemcpyAsync(hs.data(), os.ptr, sizeof(double) * outs, hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipMemcpyAsync(hi.data(), oi.ptr, sizeof(int32_t) * outs, hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipMemcpyAsync(hn.data(), on.ptr, sizeof(int32_t) * n_users, hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipStreamSynchronize(st));
+  c->last_ms[T_RECOMMEND] = ev.ms();
+  for (int64_t b = 0; b < n_users; ++b) {
+    const size_t o = static_cast<size_t>(b) * n;
+    const int cnt = hn[static_cast<size_t>(b)];
+    if (counts) counts[b] = cnt;
+    for (int k = 0; k < cnt; ++k) {
+      items[o + k] = hi[o + k];
+      if (scores) scores[o + k] = hs[o + k];
+    }
+  }
 }
 
 void recommend_positions(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, const int64_t *offsets,

@@ -401,11 +401,18 @@ class MMSBM:
     # ------------------------------------------------------------------ recommendation (not in the reference)
     RECOMMEND_BATCH_ROWS = 1 << 22   # result rows (users x n) fetched from the device per query call
 
-    def recommend(self, users=None, n=10, exclude_seen=True, weights=None):
+    def recommend(self, users=None, n=10, exclude_seen=True, weights=None, candidates=None, exclude=None):
         """The ``n`` best items per user, scored on the device: score(u, i) = sum_r weights[r] P(r | u, i), mean over
         the restarts the model holds -- with the default weights (the rating values, ``self.ratings``) the expected
         rating that ``predict`` + ``score`` use.  Candidates are all training items, without the user's own training
         items when ``exclude_seen``.  Order: score descending, equal scores by ascending encoded item id.
+
+        ``candidates``: an iterable of item labels -- the items in stock, of one category, released this week; only
+        they are scored and ranked (duplicates count once; a label that is not in the training data: KeyError; an
+        empty one: an empty frame).  ``exclude``: further (user, item) pairs to leave out -- shown, dismissed, bought
+        elsewhere -- as a DataFrame whose first two columns are users and items or an iterable of (user, item) tuples;
+        pairs of users that are not requested, and pairs with a user or an item that is not in the training data, are
+        ignored.  Scores and order are those of the plain call: the answer is its list for n = all items, filtered.
 
         Returns a DataFrame with columns ``users``, ``items``, ``score``, ``rank`` (1 = best), users in request order
         (``users=None``: every training user), users and items as the encoder's labels (``theta`` / ``eta``'s index).  The model's stored predictions and
@@ -415,8 +422,93 @@ class MMSBM:
         enc = self.data_handler
         ids, labels = self._training_users(users)
         item_labels = np.asarray(enc.item_labels(), dtype=object) if enc else None
+        if candidates is None and exclude is None:
+            with self._session_of_restarts("recommend", w, exclude_seen) as ctx:
+                return self._top_n_frame(lambda b, e: ctx.recommend_query(ids[b:e], n), n, labels, item_labels)
+        cand = None if candidates is None else self._candidate_ids(candidates)
+        if cand is not None and len(cand) == 0:
+            return self._top_n_frame(None, n, labels[:0], item_labels)
+        off, its = (None, None) if exclude is None else self._exclusion_lists(exclude, ids)
         with self._session_of_restarts("recommend", w, exclude_seen) as ctx:
-            return self._top_n_frame(lambda b, e: ctx.recommend_query(ids[b:e], n), n, labels, item_labels)
+            def query(b, e):
+                extra = None if off is None else (off[b:e + 1] - off[b], its[off[b]:off[e]])
+                return ctx.recommend_query_within(ids[b:e], n, cand, extra)
+            return self._top_n_frame(query, n, labels, item_labels)
+
+    RECOMMEND_MAX = 1024             # largest n of a top-N query (MMSBM_HIP_RECOMMEND_MAX_N)
+
+    def rerank(self, pairs, n=None, exclude_seen=True, weights=None):
+        """The order of caller-given candidates per user -- the second stage of a two-stage system: a cheap retriever
+        proposes a few hundred items per user, the model orders them.  ``pairs``: a DataFrame whose first two columns
+        are users and items (further columns are ignored), or an iterable of (user, item) tuples; both must be in the
+        training data (KeyError).  A user's candidates are the items of its pairs (a repeated pair counts once),
+        without the user's own training items when ``exclude_seen``.  Scores and order are ``recommend``'s, bit for
+        bit, and everything runs on the device.
+
+        ``n``: the best ``n`` of each list; None: each user's whole list, provided the longest holds at most 1,024
+        items (a longer one needs an explicit ``n``).  Returns ``recommend``'s frame (``users``, ``items``, ``score``,
+        ``rank``), users in order of first appearance in ``pairs``.  The model's stored predictions and ``score()``
+        are left as they are."""
+        self._check_whole_model()
+        w = self._rating_weights(weights)
+        if n is not None:
+            n, _ = self._recommend_args(n, weights)
+        us, its = self._pair_columns(pairs)
+        uid, _ = self._training_ids(us, "users")
+        iid, _ = self._training_ids(its, "items")
+        enc = self.data_handler
+        item_labels = np.asarray(enc.item_labels(), dtype=object) if enc else None
+        users, first = np.unique(uid, return_index=True)
+        users = users[np.argsort(first, kind="stable")]                    # order of first appearance
+        place = np.empty((self.p + 1), dtype=np.int64)
+        place[users] = np.arange(len(users))
+        rows = np.unique(np.stack([place[uid], iid.astype(np.int64)], 1), axis=0) if len(uid) else np.zeros((0, 2), np.int64)
+        off = np.concatenate([[0], np.cumsum(np.bincount(rows[:, 0], minlength=len(users)))]).astype(np.int64)
+        items = rows[:, 1].astype(np.int32)                                 # per user ascending and distinct
+        users = users.astype(np.int32)
+        labels = np.asarray(enc.user_labels(), dtype=object)[users] if enc else users
+        if n is None:
+            longest = int(np.diff(off).max()) if len(users) else 1
+            if longest > self.RECOMMEND_MAX:
+                raise ValueError(f"the longest candidate list holds {longest} items: beyond {self.RECOMMEND_MAX} "
+                                 "an explicit n is needed")
+            n = max(longest, 1)
+        if len(users) == 0:
+            return self._top_n_frame(None, n, labels[:0], item_labels)
+        with self._session_of_restarts("recommend", w, exclude_seen) as ctx:
+            return self._top_n_frame(
+                lambda b, e: ctx.recommend_rank(users[b:e], off[b:e + 1] - off[b], items[off[b]:off[e]], n),
+                n, labels, item_labels)
+
+    def _candidate_ids(self, candidates):
+        """The encoded ids of ``candidates`` (item labels of the training data: KeyError otherwise), ascending and
+        distinct, int32."""
+        return np.unique(self._training_ids(list(candidates), "items")[0]).astype(np.int32)
+
+    @staticmethod
+    def _pair_columns(pairs):
+        """(users, items) of a ``pairs`` argument: the first two columns of a DataFrame, or (user, item) tuples."""
+        if hasattr(pairs, "iloc") and hasattr(pairs, "columns"):
+            if pairs.shape[1] < 2:
+                raise ValueError("pairs needs two columns: users and items")
+            return pairs.iloc[:, 0].tolist(), pairs.iloc[:, 1].tolist()
+        rows = [tuple(x) for x in pairs]
+        if any(len(x) != 2 for x in rows):
+            raise ValueError("pairs must be (user, item) tuples")
+        return [x[0] for x in rows], [x[1] for x in rows]
+
+    def _exclusion_lists(self, exclude, ids):
+        """(offsets (len(ids) + 1,) int64, items int32): for every requested row (encoded user ``ids``) the distinct
+        encoded items ``exclude`` names for that user, ascending; pairs of other users and unknown labels are dropped."""
+        us, its = self._pair_columns(exclude)
+        uid, iid = self._lookup_ids(us, "users"), self._lookup_ids(its, "items")
+        keep = (uid >= 0) & (iid >= 0) & np.isin(uid, ids)
+        rows = np.unique(np.stack([uid[keep], iid[keep]], 1).astype(np.int64), axis=0) if keep.any() else np.zeros((0, 2), np.int64)
+        start = np.searchsorted(rows[:, 0], ids, side="left")               # rows: by user, then item, both ascending
+        stop = np.searchsorted(rows[:, 0], ids, side="right")
+        off = np.concatenate([[0], np.cumsum(stop - start)]).astype(np.int64)
+        pick = np.concatenate([np.arange(a, b) for a, b in zip(start.tolist(), stop.tolist())]) if len(ids) else []
+        return off, rows[np.asarray(pick, dtype=np.int64), 1].astype(np.int32)
 
     def recommend_users(self, items=None, n=10, exclude_seen=True, weights=None):
         """The ``n`` best users per item -- who should see this item -- scored on the device: ``recommend`` from the
@@ -539,15 +631,7 @@ class MMSBM:
         import pandas as pd
         self._check_whole_model()
         n, w = self._recommend_args(n, weights)
-        if hasattr(pairs, "iloc") and hasattr(pairs, "columns"):
-            if pairs.shape[1] < 2:
-                raise ValueError("pairs needs two columns: users and items")
-            us, its = pairs.iloc[:, 0].tolist(), pairs.iloc[:, 1].tolist()
-        else:
-            rows = [tuple(x) for x in pairs]
-            if any(len(x) != 2 for x in rows):
-                raise ValueError("pairs must be (user, item) tuples")
-            us, its = [x[0] for x in rows], [x[1] for x in rows]
+        us, its = self._pair_columns(pairs)
         uid, ulab = self._training_ids(us, "users")
         iid, ilab = self._training_ids(its, "items")
         enc = self.data_handler
@@ -644,18 +728,24 @@ class MMSBM:
             labels = np.asarray(side_labels(), dtype=object) if enc else ids
         else:
             labels = np.asarray(list(wanted), dtype=object)
-            if enc:
-                index = {lab: j for j, lab in enumerate(side_labels())}
-                found = [index.get(str(x), -1) for x in labels]
-            else:
-                found = [int(x) if isinstance(x, (int, np.integer)) and 0 <= int(x) < n_side else -1 for x in labels]
-            ids = np.asarray(found, dtype=np.int32)
+            ids = self._lookup_ids(labels, side)
             if (ids < 0).any():
                 missing = list(dict.fromkeys(labels[ids < 0].tolist()))
                 raise KeyError(f"{side} not in the training data: {missing}")
             if enc:  # the encoder's labels, as with None (7 and "7" are one user; the frames join on this column)
                 labels = np.asarray(side_labels(), dtype=object)[ids]
         return ids, labels
+
+    def _lookup_ids(self, labels, side):
+        """The encoded id (int32) of every label of ``side`` ("users" / "items"), -1 where the training data has none."""
+        enc = self.data_handler
+        if enc:
+            index = {lab: j for j, lab in enumerate(enc.user_labels() if side == "users" else enc.item_labels())}
+            found = [index.get(str(x), -1) for x in labels]
+        else:
+            n_side = (self.p if side == "users" else self.m) + 1
+            found = [int(x) if isinstance(x, (int, np.integer)) and 0 <= int(x) < n_side else -1 for x in labels]
+        return np.asarray(found, dtype=np.int32)
 
     def _check_whole_model(self):
         self._check_is_fitted()
@@ -994,14 +1084,16 @@ class MMSBM:
                                                index=index)
         return [pd.DataFrame(t, index=index) for t in thetas]
 
-    def recommend_new(self, data, n=10, exclude_seen=True, weights=None, iterations=100, tol=None):
+    def recommend_new(self, data, n=10, exclude_seen=True, weights=None, iterations=100, tol=None, candidates=None):
         """``recommend`` for users that were not in the training data: each restart scores with the theta its own
         ``fold_in`` gives them (same arguments as ``fold_in``), the scores are averaged over the restarts.  Returns
         the frame ``recommend`` returns (users, items, score, rank), users in order of first appearance in ``data``;
-        ``exclude_seen`` leaves out the items a user has in ``data``."""
+        ``exclude_seen`` leaves out the items a user has in ``data``; ``candidates`` as in ``recommend``: only these
+        items are scored and ranked."""
         import pandas as pd
         self._check_whole_model()
         n, w = self._recommend_args(n, weights)
+        cand = None if candidates is None else self._candidate_ids(candidates)
         iterations, tol = self._fold_args(iterations, tol)
         rows, labels = self._encode_new(data, 0)
         enc = self.data_handler
@@ -1020,7 +1112,9 @@ class MMSBM:
 
             def query(b, e):
                 seen = (seen_off[b:e + 1] - seen_off[b], seen_items[seen_off[b]:seen_off[e]]) if exclude_seen else None
-                return ctx.recommend_query_theta(theta[:, b:e], n, seen)
+                if cand is None:
+                    return ctx.recommend_query_theta(theta[:, b:e], n, seen)
+                return ctx.recommend_query_theta(theta[:, b:e], n, seen, candidates=cand)
             return self._top_n_frame(query, n, labels, item_labels)
 
     def fold_in_items(self, data, iterations=100, tol=None):
