@@ -343,6 +343,42 @@ int mmsbm_hip_similar_query(mmsbm_hip_ctx *ctx, int64_t n_rows, const int32_t *i
                             double *distance, int32_t *counts);
 int mmsbm_hip_similar_end(mmsbm_hip_ctx *ctx);
 
+/* ---- diversified top-N and the distance of given pairs (mmsbm_amd/csrc/diverse.hpp) ------------------------------- */
+/* similar_pairs: distance[e] = D(a[e], b[e]) of the open similarity session (either side), e < n_pairs; ids of the
+ * session's side, any order, repeats allowed.  The number is query's for the pair, bit for bit, with a[e] as the query
+ * row: D(a, b) and D(b, a) have equal bits, D(a, a) and D between identical rows is +0.0.  MMSBM_E_INVALID: no session,
+ * no slot added, an id out of range, negative n_pairs.
+ *
+ * recommend_diverse: the greedy re-ranking of each user's `pool` best candidates, with score(u, i) of the open
+ * recommend session and D(i, j) of the open similarity session of side ITEMS.  For request row b:
+ *   pool   P = the row recommend_query_within(users, cand_items, excl_*, n = pool) returns: the same exclusions, the
+ *          same optional candidate subset, the same order and score bits; M = its count;
+ *   pick 1 t_1 = P[0];
+ *   pick j (j = 2 .. min(n, M)): over the i of P not picked yet, m_i = min over a < j of D(t_a, i),
+ *          v_i = fma(trade_off, m_i, score_i) (one rounding); t_j = the i with the largest v_i, equal v_i (exact fp64
+ *          equality) to the earlier place in P.
+ * items / scores / distances: [n_users][n]; row b holds counts[b] = min(n, M) picks -- the item, its score (the pool's
+ * bits) and m at the moment of the pick, the distance to the nearest earlier pick (+inf for pick 1) -- then -1 / -inf /
+ * +inf (scores, distances, counts may be NULL).  trade_off is in score units per unit of distance: at 0 the answer is
+ * recommend_query_within(n), bit for bit; as it grows the list tends to the farthest-point order inside the pool.  A
+ * row's answer depends on its user and the arguments only.  The pool never visits the host.
+ * THE CALLER'S CONTRACT: both sessions hold the same slots, added in the same order -- the library checks that their
+ * numbers agree and cannot check more.
+ * MMSBM_E_INVALID (before any launch): no recommend session or no slot added to it; no similarity session, one of side
+ * users, or no slot added to it; the two sessions' slot counts differ; the recommend session's catalogue was grown by
+ * recommend_add_items; an id out of range; cand_items not strictly ascending; a bad CSR; n < 1; pool < n; trade_off
+ * negative, NaN or infinite.  pool > MMSBM_HIP_RECOMMEND_MAX_N: MMSBM_E_UNSUPPORTED; MMSBM_E_TOOLARGE where the device
+ * memory is not free (the rows of a request are taken in parts while the pool lists, n_users x pool x 12 bytes, are
+ * not; option "diverse_rows": rows per part, 0 = the library's choice -- time and memory, never the answer).
+ *
+ * Both write nothing of any session, slot or predict session: a later query answers as before.  "diverse_ms" reads the
+ * device time of the last call's kernels. */
+int mmsbm_hip_similar_pairs(mmsbm_hip_ctx *ctx, int64_t n_pairs, const int32_t *a, const int32_t *b, double *distance);
+int mmsbm_hip_recommend_diverse(mmsbm_hip_ctx *ctx, int64_t n_users, const int32_t *users, int32_t n_cand,
+                                const int32_t *cand_items, const int64_t *excl_offsets, const int32_t *excl_items,
+                                int32_t n, int32_t pool, double trade_off, int32_t *items, double *scores,
+                                double *distances, int32_t *counts);
+
 /* ---- the overlap of the restarts' groups: the Gram matrix of the membership tables (mmsbm_amd/csrc/overlap.hpp) ---- */
 /* A session of its own beside the predict, recommend, similar and held-out sessions (any of them may be open meanwhile):
  *   begin  side 0: items (eta, G = L groups), 1: users (theta, G = K groups); external sides.  Closes any earlier

@@ -510,6 +510,35 @@ class HipEM:
     def similar_end(self):
         _lib.call("mmsbm_hip_similar_end", self._h)
 
+    def similar_pairs(self, a, b):
+        """distance (M,): D(a[e], b[e]) of the open similarity session for encoded ids of its side -- similar_query's
+        number for the pair, bit for bit; symmetric, +0.0 between a row and itself."""
+        a, b = _i32(a), _i32(b)
+        if a.shape != b.shape or a.ndim != 1:
+            raise ValueError(f"a and b must be two id columns of one length, got shapes {a.shape} and {b.shape}")
+        out = np.empty(len(a), dtype=np.float64)
+        _lib.call("mmsbm_hip_similar_pairs", self._h, len(a), _p(a, C.c_int32), _p(b, C.c_int32), _p(out, C.c_double))
+        return out
+
+    # -- diversified top-N on the device (include/mmsbm_hip.h: mmsbm_hip_recommend_diverse) -----------------
+    def recommend_diverse(self, users, n, pool, trade_off, candidates=None, exclude=None):
+        """(items (M,n) int32 padded with -1, scores (M,n) padded with -inf, distances (M,n) padded with +inf, counts
+        (M,)): the greedy re-ranking of each user's ``pool`` best candidates -- the row recommend_query_within(users,
+        pool, candidates, exclude) returns -- by score + trade_off x (distance to the nearest item picked so far), with
+        the open recommend session's scores and the distance of the open similarity session over the items (both must
+        hold the same slots, added in the same order).  distances: to the nearest earlier pick, +inf for the first."""
+        u, n, pool = _i32(users), int(n), int(pool)
+        cand = None if candidates is None else _i32(candidates)
+        off, it = (None, None) if exclude is None else _csr(exclude[0], exclude[1], len(u), "exclude offsets", "items")
+        items, scores, counts = self._query_out(len(u), n)
+        distances = np.empty((len(u), max(n, 0)), dtype=np.float64)
+        _lib.call("mmsbm_hip_recommend_diverse", self._h, len(u), _p(u, C.c_int32),
+                  0 if cand is None else len(cand), None if cand is None else _p(cand, C.c_int32),
+                  None if off is None else _p(off, C.c_int64), None if it is None else _p(it, C.c_int32), n, pool,
+                  float(trade_off), _p(items, C.c_int32), _p(scores, C.c_double), _p(distances, C.c_double),
+                  _p(counts, C.c_int32))
+        return items, scores, distances, counts
+
     # -- the overlap of the restarts' groups on the device (include/mmsbm_hip.h: mmsbm_hip_overlap_*) ----
     def overlap_begin(self, side):
         """Open an overlap session over one side: 0 (or "items") eta's L groups, 1 (or "users") theta's K groups."""

@@ -226,8 +226,9 @@ inline void sort_unique_groups(std::vector<int32_t> &off, std::vector<int32_t> &
 
 // The serving calls whose kernels are timed (mmsbm_hip_ctx::last_ms), in the order of their "<name>_ms" options:
 // recommend_query / recommend_query_items, fold_in / fold_in_items, recommend_positions, recommend_top_pairs,
-// recommend_audience, similar_query, overlap_query, heldout_eval / heldout_add, explain_query
-enum TimedCall { T_RECOMMEND = 0, T_FOLD_IN, T_POSITIONS, T_TOP_PAIRS, T_AUDIENCE, T_SIMILAR, T_OVERLAP, T_HELDOUT, T_EXPLAIN, T_COUNT };
+// recommend_audience, similar_query, overlap_query, heldout_eval / heldout_add, explain_query, recommend_diverse /
+// similar_pairs
+enum TimedCall { T_RECOMMEND = 0, T_FOLD_IN, T_POSITIONS, T_TOP_PAIRS, T_AUDIENCE, T_SIMILAR, T_OVERLAP, T_HELDOUT, T_EXPLAIN, T_DIVERSE, T_COUNT };
 
 enum KernelId { K_SEG = 0, K_DENSE, K_ETAP, K_MATVEC_A, K_FUSED_PAIRS, K_FUSED_TAIL, K_COUNT };
 // The four launches of an iteration -- or, for small problems, the two of fused_small.hpp.
@@ -312,6 +313,7 @@ struct mmsbm_hip_ctx {
   int64_t aud_rows = 0;                     // option "audience_rows": items per COUNT batch (0: the library's choice)
   int64_t aud_entries = 0;                  // option "audience_entries": entries per WRITE batch at most (0: likewise)
   int64_t exp_rows = 0;                     // option "explain_rows": training rows per batch of explain_query (0: likewise)
+  int64_t div_rows = 0;                     // option "diverse_rows": request rows per call of recommend_diverse (0: likewise)
   // snapshots (mmsbm_hip_snapshot_save / get): a second copy of theta, eta and p in the layout of theta[cur], eta[cur]
   // and p[cur], every slot's place in it filled by that slot's last save; allocated by the first save, dropped by set_slots
   DevBuf<double> snap_theta;

@@ -72,6 +72,12 @@ void similar_begin(mmsbm_hip_ctx *c, int side);
 void similar_add(mmsbm_hip_ctx *c);  // the selected slot (the caller holds a OneSlot)
 void similar_query(mmsbm_hip_ctx *c, int64_t n_rows, const int32_t *ids, int n, int32_t *out_ids, double *distance,
                    int32_t *counts);
+// ... and the two queries of diverse.hpp, arguments checked: the distance of given pairs of the similarity session's
+// side, and the diversified top-N, which reads the recommend session and the similarity session (side items)
+void similar_pairs(mmsbm_hip_ctx *c, int64_t n_pairs, const int32_t *a, const int32_t *b, double *distance);
+void recommend_diverse(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, const int32_t *cand, int n_cand,
+                       const int64_t *excl_offsets, const int32_t *excl_items, int n, int pool, double trade_off,
+                       int32_t *items, double *scores, double *distances, int32_t *counts);
 // ... and the overlap of the restarts' groups (overlap.hpp): the session of mmsbm_hip_overlap_*, arguments checked
 void overlap_begin(mmsbm_hip_ctx *c, int side);
 void overlap_add(mmsbm_hip_ctx *c);  // the selected slot (the caller holds a OneSlot)

@@ -792,7 +792,7 @@ struct Option {
   void (*set)(mmsbm_hip_ctx *, double);
 };
 using Ctx = mmsbm_hip_ctx;
-// "audience_rows" / "audience_entries" / "explain_rows": 0 .. 2^31 - 1, whole
+// "audience_rows" / "audience_entries" / "explain_rows" / "diverse_rows": 0 .. 2^31 - 1, whole
 void set_audience(int64_t &field, const char *name, double v) {
   if (v < 0 || v > 2147483647.0 || v != std::floor(v)) throw std::invalid_argument(std::string(name) + ": 0 .. 2^31 - 1");
   field = static_cast<int64_t>(v);
@@ -831,6 +831,7 @@ const Option kOptions[] = {
     {"heldout_ms", [](const Ctx *c) -> double { return c->last_ms[T_HELDOUT]; }, nullptr},
     {"audience_ms", [](const Ctx *c) -> double { return c->last_ms[T_AUDIENCE]; }, nullptr},
     {"explain_ms", [](const Ctx *c) -> double { return c->last_ms[T_EXPLAIN]; }, nullptr},
+    {"diverse_ms", [](const Ctx *c) -> double { return c->last_ms[T_DIVERSE]; }, nullptr},
     // workgroups of gtop_fused_kernel (top_pairs.hpp); 0: the library's choice
     {"top_pairs_groups", [](const Ctx *c) -> double { return c->top_groups; },
      [](Ctx *c, double v) {
@@ -846,6 +847,9 @@ const Option kOptions[] = {
     // explain_query (explain.hpp): training rows per batch; 0: the library's choice.  It does not change the answer
     {"explain_rows", [](const Ctx *c) -> double { return static_cast<double>(c->exp_rows); },
      [](Ctx *c, double v) { set_audience(c->exp_rows, "explain_rows", v); }},
+    // recommend_diverse (diverse.hpp): request rows per call; 0: the library's choice.  It does not change the answer
+    {"diverse_rows", [](const Ctx *c) -> double { return static_cast<double>(c->div_rows); },
+     [](Ctx *c, double v) { set_audience(c->div_rows, "diverse_rows", v); }},
     {"launches", [](const Ctx *c) -> double { return use_fused(c) ? 2 : 4; }, nullptr},  // per iteration at the current slot count
     {"wide", [](const Ctx *c) -> double { return c->pp.wide; }, nullptr},
     // 0: a logarithm per element; 1: logarithm tables, a group of lanes per triple; 2: where it applies a wave per pair
@@ -1772,6 +1776,47 @@ int mmsbm_hip_similar_query(mmsbm_hip_ctx *ctx, int64_t n_rows, const int32_t *i
 }
 
 int mmsbm_hip_similar_end(mmsbm_hip_ctx *ctx) { return end_session(ctx, &mmsbm_hip_ctx::sm); }
+
+int mmsbm_hip_similar_pairs(mmsbm_hip_ctx *ctx, int64_t n_pairs, const int32_t *a, const int32_t *b, double *distance) {
+  return guarded([&] {
+    const SimSession &sm = require_open(ctx, &mmsbm_hip_ctx::sm, "similar", "similar_pairs");
+    if (n_pairs < 0) throw std::invalid_argument("negative n_pairs");
+    if (n_pairs > 0 && (!a || !b || !distance)) throw std::invalid_argument("null argument");
+    const char *who = sm.side == 0 ? "similar_pairs: item" : "similar_pairs: user";
+    require_ids(a, n_pairs, sm.rows, who);
+    require_ids(b, n_pairs, sm.rows, who);
+    similar_pairs(ctx, n_pairs, a, b, distance);
+  });
+}
+
+int mmsbm_hip_recommend_diverse(mmsbm_hip_ctx *ctx, int64_t n_users, const int32_t *users, int32_t n_cand,
+                                const int32_t *cand_items, const int64_t *excl_offsets, const int32_t *excl_items,
+                                int32_t n, int32_t pool, double trade_off, int32_t *items, double *scores,
+                                double *distances, int32_t *counts) {
+  return guarded([&] {
+    const RecSession &rc = require_open(ctx, &mmsbm_hip_ctx::rc, "recommend", "recommend_diverse");
+    const SimSession &sm = require_open(ctx, &mmsbm_hip_ctx::sm, "similar", "recommend_diverse");
+    if (sm.side != 0) throw std::invalid_argument("recommend_diverse: the similarity session is over the users");
+    if (sm.slots != rc.slots)
+      throw std::invalid_argument("recommend_diverse: the recommend session holds " + std::to_string(rc.slots) +
+                                  " slots, the similarity session " + std::to_string(sm.slots));
+    if (rc.items != sm.rows)
+      throw std::invalid_argument("recommend_diverse: the recommend session's catalogue holds added items");
+    if (n_users < 0) throw std::invalid_argument("negative n_users");
+    if (n < 1) throw std::invalid_argument("recommend_diverse: n must be at least 1");
+    if (pool < n) throw std::invalid_argument("recommend_diverse: pool must be at least n");
+    if (!std::isfinite(trade_off) || trade_off < 0.0)
+      throw std::invalid_argument("recommend_diverse: trade_off must be finite and at least 0");
+    require_n(pool, "recommend_diverse", "pool entries");
+    if (n_users > 0 && (!users || !items)) throw std::invalid_argument("null argument");
+    require_ids(users, n_users, ctx->ext_users, "recommend_diverse: user");
+    require_subset(cand_items, n_cand, rc.items, "recommend_diverse");
+    check_csr(excl_offsets, excl_items, n_users, rc.items, "recommend_diverse", "excl_offsets", "user", "excluded items",
+              "excluded item");
+    recommend_diverse(ctx, n_users, users, cand_items, n_cand, n_users > 0 ? excl_offsets : nullptr, excl_items, n, pool,
+                      trade_off, items, scores, distances, counts);
+  });
+}
 
 int mmsbm_hip_overlap_begin(mmsbm_hip_ctx *ctx, int side) {
   return guarded([&] {

@@ -11,8 +11,8 @@
 //   tu_once.hip    once-per-run kernels: likelihood, prod_dist / predict, omegas, the random start
 //   tu_layout.hip  the layout's sorts on the device (rocPRIM)
 //   tu_recommend.hip  top-N recommendation (recommend.hpp), nearest items / users (similar.hpp), the m best pairs (top_pairs.hpp),
-//                     item-side queries (audience.hpp), queries within a part of the catalogue (catalogue.hpp)
-//                     and the overlap of the restarts' groups (overlap.hpp)
+//                     item-side queries (audience.hpp), queries within a part of the catalogue (catalogue.hpp),
+//                     the overlap of the restarts' groups (overlap.hpp) and the diversified top-N (diverse.hpp)
 //   tu_fold_in.hip    fold new users into a fitted model (fold_in.hpp)
 //   tu_heldout.hip    held-out log-likelihood of every restart slot (heldout.hpp)
 //   tu_explain.hip    which of a user's training rows carry a recommendation (explain.hpp)

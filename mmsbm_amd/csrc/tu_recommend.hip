@@ -6,7 +6,9 @@
 // the item-side queries of the recommend session (audience.hpp): the n best users of an item through the same batches
 // and selection, and the audience of an item above a bar through a fused kernel of its own; and the queries within a
 // part of the catalogue (catalogue.hpp): a subset of the items through the same batches and selection over a compact
-// item table, and per-user candidate lists through a kernel of their own
+// item table, and per-user candidate lists through a kernel of their own; and the diversified top-N (diverse.hpp), the
+// one query that reads the recommend and the similarity session at once: the pool through the same batches and
+// selection, kept on the device, then a greedy kernel of its own
 #include "prelude.hpp"
 #include "recommend.hpp"
 #include "similar.hpp"
@@ -14,6 +16,7 @@
 #include "top_pairs.hpp"
 #include "audience.hpp"
 #include "catalogue.hpp"
+#include "diverse.hpp"
 
 #include <climits>
 
@@ -204,21 +207,34 @@ void rec_score_batch(mmsbm_hip_ctx *c, const double *x, size_t xs, const int32_t
   if (seen_off) LAUNCH(rec_exclude_kernel, nb, kBlock, 0, st, ub, seen_off, seen, sc, static_cast<size_t>(I));
 }
 
-// The batches of a top-N query over a buffer of `I` columns: rows ids[0 .. n_rows) (host ids); `fill(ub, nb, sc)`
-// enqueues the kernels that write the batch's values sc [nb][I] for the device ids ub (-inf: no candidate), then the
-// N best of every row are selected (and merged when the columns are split across waves).  `what` names the query in
-// MMSBM_E_TOOLARGE; `timed`: the timer that takes the device time of the query's kernels.
-template <class Fill>
-void top_n_run(mmsbm_hip_ctx *c, int I, int64_t n_users, const int32_t *users, int n, const char *what, Fill &&fill,
-               TimedCall timed, int32_t *items, double *scores, int32_t *counts) {
-  for (int64_t b = 0; b < n_users; ++b) {
+// Every row of a top-N answer as "no candidate": counts 0, ids -1, values -inf
+void top_n_blank(int64_t n_rows, int n, int32_t *items, double *scores, int32_t *counts) {
+  for (int64_t b = 0; b < n_rows; ++b) {
     if (counts) counts[b] = 0;
     for (int k = 0; k < n; ++k) {
       items[static_cast<size_t>(b) * n + k] = -1;
       if (scores) scores[static_cast<size_t>(b) * n + k] = -INFINITY;
     }
   }
-  if (n_users == 0) return;
+}
+
+// What top_n_device leaves on the device: row b's os / oi [b * n + k], k < on[b] (the entries behind are not written)
+struct TopNDev {
+  const double *os;
+  int32_t *oi;        // (a following stage may map them in place: div_ids_kernel)
+  const int32_t *on;
+};
+
+// The batches of a top-N query over a buffer of `I` columns: rows ids[0 .. n_rows) (host ids); `fill(ub, nb, sc)`
+// enqueues the kernels that write the batch's values sc [nb][I] for the device ids ub (-inf: no candidate), then the
+// N best of every row are selected (and merged when the columns are split across waves).  `what` names the query in
+// MMSBM_E_TOOLARGE.  Every row's result stays on the device: `then(dev, ev)` is called once the last batch is
+// enqueued, with the result and the event pair around the query's kernels (recorded; not waited for) -- it copies the
+// result out (top_n_copy_out) or enqueues a stage that reads it there (diverse.hpp); `extra` bytes of device memory
+// are what it will allocate.  n_users > 0.
+template <class Fill, class Then>
+void top_n_device(mmsbm_hip_ctx *c, int I, int64_t n_users, const int32_t *users, int n, const char *what, size_t extra,
+                  Fill &&fill, Then &&then) {
   hipStream_t st = c->stream;
 
   const int64_t bu = rec_batch_users(I, n_users);
@@ -229,7 +245,8 @@ void top_n_run(mmsbm_hip_ctx *c, int I, int64_t n_users, const int32_t *users, i
   const size_t lds = static_cast<size_t>(cap) * (sizeof(double) + sizeof(int32_t));
   const size_t cand = parts > 1 ? static_cast<size_t>(bu) * parts * n : 0;
   const size_t outs = static_cast<size_t>(n_users) * n;
-  require_free_mem(static_cast<size_t>(bu) * I * sizeof(double) + cand * 12 + outs * 12 + static_cast<size_t>(n_users) * 8,
+  require_free_mem(static_cast<size_t>(bu) * I * sizeof(double) + cand * 12 + outs * 12 + static_cast<size_t>(n_users) * 8 +
+                       extra,
                    what);
   DevBuf<int32_t> du, ci, cn, oi, on;
   DevBuf<double> sc, cs, os;
@@ -240,7 +257,7 @@ void top_n_run(mmsbm_hip_ctx *c, int I, int64_t n_users, const int32_t *users, i
   }
   os.alloc(outs); oi.alloc(outs); on.alloc(n_users);  // every user's result stays on the device until the end
   HIP_CHECK(hipMemcpyAsync(du.ptr, users, sizeof(int32_t) * n_users, hipMemcpyHostToDevice, st));
-  EventPair ev;  // device time of the query's kernels (options "recommend_ms", "similar_ms")
+  EventPair ev;  // device time of the query's kernels (options "recommend_ms", "similar_ms", "diverse_ms")
   ev.start(st);
   for (int64_t b0 = 0; b0 < n_users; b0 += bu) {  // (batches follow each other on the stream: no host wait in between)
     const int nb = static_cast<int>(std::min(bu, n_users - b0));
@@ -260,11 +277,19 @@ void top_n_run(mmsbm_hip_ctx *c, int I, int64_t n_users, const int32_t *users, i
     HIP_CHECK(hipGetLastError());
   }
   ev.stop(st);
+  then(TopNDev{os.ptr, oi.ptr, on.ptr}, ev);
+}
+
+// The result of top_n_device to the host (rows blanked by top_n_blank), and the device time of its kernels to `timed`
+void top_n_copy_out(mmsbm_hip_ctx *c, const TopNDev &dev, EventPair &ev, int64_t n_users, int n, TimedCall timed,
+                    int32_t *items, double *scores, int32_t *counts) {
+  hipStream_t st = c->stream;
+  const size_t outs = static_cast<size_t>(n_users) * n;
   std::vector<double> hs(outs);
   std::vector<int32_t> hi(outs), hn(static_cast<size_t>(n_users));
-  HIP_CHECK(hipMemcpyAsync(hs.data(), os.ptr, sizeof(double) * outs, hipMemcpyDeviceToHost, st));
-  HIP_CHECK(hipMemcpyAsync(hi.data(), oi.ptr, sizeof(int32_t) * outs, hipMemcpyDeviceToHost, st));
-  HIP_CHECK(hipMemcpyAsync(hn.data(), on.ptr, sizeof(int32_t) * n_users, hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipMemcpyAsync(hs.data(), dev.os, sizeof(double) * outs, hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipMemcpyAsync(hi.data(), dev.oi, sizeof(int32_t) * outs, hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipMemcpyAsync(hn.data(), dev.on, sizeof(int32_t) * n_users, hipMemcpyDeviceToHost, st));
   HIP_CHECK(hipStreamSynchronize(st));
   c->last_ms[timed] = ev.ms();
   for (int64_t b = 0; b < n_users; ++b) {
@@ -278,6 +303,17 @@ void top_n_run(mmsbm_hip_ctx *c, int I, int64_t n_users, const int32_t *users, i
   }
 }
 
+// top_n_device with the result copied to the host; `timed`: the timer that takes the device time of the query's kernels
+template <class Fill>
+void top_n_run(mmsbm_hip_ctx *c, int I, int64_t n_users, const int32_t *users, int n, const char *what, Fill &&fill,
+               TimedCall timed, int32_t *items, double *scores, int32_t *counts) {
+  top_n_blank(n_users, n, items, scores, counts);
+  if (n_users == 0) return;
+  top_n_device(c, I, n_users, users, n, what, 0, fill, [&](const TopNDev &dev, EventPair &ev) {
+    top_n_copy_out(c, dev, ev, n_users, n, timed, items, scores, counts);
+  });
+}
+
 // A recommend query: users users[0 .. n_users) (host ids, rows of x: `slots` tables of xs doubles, [row][rank]),
 // scored against the session's items; seen_off / seen (device, indexed by those ids): the items left out, or null.
 void rec_run(mmsbm_hip_ctx *c, const double *x, size_t xs, int64_t n_users, const int32_t *users,
@@ -287,36 +323,26 @@ void rec_run(mmsbm_hip_ctx *c, const double *x, size_t xs, int64_t n_users, cons
             T_RECOMMEND, items, scores, counts);
 }
 
-// rec_run within the candidates cand[0 .. n_cand) (host; ascending, distinct ids of the session's catalogue; null: the
-// whole catalogue), and with the query's own excluded items: row b of the request also leaves out xit[xoff[b] ..
-// xoff[b + 1]) (host, any order, repeats allowed; null: none).  catalogue.hpp.  Without either: rec_run.
-void rec_run_within(mmsbm_hip_ctx *c, const double *x, size_t xs, int64_t n_users, const int32_t *users,
-                    const int32_t *seen_off, const int32_t *seen, const int32_t *cand, int n_cand, const int64_t *xoff,
-                    const int32_t *xit, int n, int32_t *items, double *scores, int32_t *counts) {
+// The device side of rec_run within the candidates cand[0 .. n_cand) (host; ascending, distinct ids of the session's
+// catalogue; null: the whole catalogue), and with the query's own excluded items: row b of the request also leaves out
+// xit[xoff[b] .. xoff[b + 1]) (host, any order, repeats allowed; null: none).  catalogue.hpp.  Without either: rec_run's
+// launches.  The result stays on the device (top_n_device): `then(dev, ev, dcand, prep_ms)` gets it -- as COLUMNS of
+// the candidate list when there is one --, the candidate list on the device (or null) and the device time of the
+// compact table and the columns.  n_users > 0 and at least one column.
+template <class Then>
+void rec_within_device(mmsbm_hip_ctx *c, const double *x, size_t xs, int64_t n_users, const int32_t *users,
+                       const int32_t *seen_off, const int32_t *seen, const int32_t *cand, int n_cand,
+                       const int64_t *xoff, const int32_t *xit, int n, size_t extra, Then &&then) {
   const RecSession &rc = *c->rc;
   const int NI = rc.items, rank = rc.rank, S = rc.slots;
-  if (!cand && !xoff) {
-    rec_run(c, x, xs, n_users, users, seen_off, seen, n, items, scores, counts);
-    return;
-  }
   const int C = cand ? n_cand : NI;
-  if (C == 0 || n_users == 0) {  // (no column to score: every row is empty)
-    for (int64_t b = 0; b < n_users; ++b) {
-      if (counts) counts[b] = 0;
-      for (int k = 0; k < n; ++k) {
-        items[static_cast<size_t>(b) * n + k] = -1;
-        if (scores) scores[static_cast<size_t>(b) * n + k] = -INFINITY;
-      }
-    }
-    c->last_ms[T_RECOMMEND] = 0.f;
-    return;
-  }
   hipStream_t st = c->stream;
   const int64_t n_x = xoff ? xoff[n_users] : 0;  // (checked: below 2^31)
   const size_t ycs = static_cast<size_t>(C) * rank;
-  require_free_mem((cand ? S * ycs * sizeof(double) + (static_cast<size_t>(C) + NI) * 4 : 0) +
-                       (static_cast<size_t>(n_users) + 1 + n_x) * 4,
-                   "recommend: the candidates' rows and the query's excluded items");
+  if (cand || xoff)
+    require_free_mem((cand ? S * ycs * sizeof(double) + (static_cast<size_t>(C) + NI) * 4 : 0) +
+                         (static_cast<size_t>(n_users) + 1 + n_x) * 4,
+                     "recommend: the candidates' rows and the query's excluded items");
   DevBuf<int32_t> dxo, dxi, dcand, dcol;
   DevBuf<double> yc;
   std::vector<int32_t> hxo;
@@ -343,23 +369,44 @@ void rec_run_within(mmsbm_hip_ctx *c, const double *x, size_t xs, int64_t n_user
     prep_ms = ev.ms();
   }
   int64_t done = 0;  // rows of the request the earlier batches held (the batches follow each other)
-  top_n_run(c, C, n_users, users, n, "recommend: a batch of users within the candidates",
-            [&](const int32_t *ub, int nb, double *sc) {
-              if (cand) {
-                const dim3 g(static_cast<unsigned>((C + kRecTile - 1) / kRecTile), static_cast<unsigned>((nb + kRecTile - 1) / kRecTile));
-                LAUNCH(rec_score_kernel, g, kBlock, 0, st, x, xs, yc.ptr, ycs, ub, nb, C, rank, S, sc, static_cast<size_t>(C));
-                if (seen_off)
-                  LAUNCH(cat_exclude_kernel, nb, kBlock, 0, st, ub, 0, seen_off, seen, dcol.ptr, sc, static_cast<size_t>(C));
-              } else {
-                rec_score_batch(c, x, xs, ub, nb, seen_off, seen, sc);
-              }
-              if (xoff)
-                LAUNCH(cat_exclude_kernel, nb, kBlock, 0, st, static_cast<const int32_t *>(nullptr), static_cast<int>(done),
-                       dxo.ptr, dxi.ptr, cand ? dcol.ptr : static_cast<const int32_t *>(nullptr), sc, static_cast<size_t>(C));
-              done += nb;
-            },
-            T_RECOMMEND, items, scores, counts);
-  c->last_ms[T_RECOMMEND] += prep_ms;
+  top_n_device(c, C, n_users, users, n,
+               cand || xoff ? "recommend: a batch of users within the candidates" : "recommend: a batch of users", extra,
+               [&](const int32_t *ub, int nb, double *sc) {
+                 if (cand) {
+                   const dim3 g(static_cast<unsigned>((C + kRecTile - 1) / kRecTile), static_cast<unsigned>((nb + kRecTile - 1) / kRecTile));
+                   LAUNCH(rec_score_kernel, g, kBlock, 0, st, x, xs, yc.ptr, ycs, ub, nb, C, rank, S, sc, static_cast<size_t>(C));
+                   if (seen_off)
+                     LAUNCH(cat_exclude_kernel, nb, kBlock, 0, st, ub, 0, seen_off, seen, dcol.ptr, sc, static_cast<size_t>(C));
+                 } else {
+                   rec_score_batch(c, x, xs, ub, nb, seen_off, seen, sc);
+                 }
+                 if (xoff)
+                   LAUNCH(cat_exclude_kernel, nb, kBlock, 0, st, static_cast<const int32_t *>(nullptr), static_cast<int>(done),
+                          dxo.ptr, dxi.ptr, cand ? dcol.ptr : static_cast<const int32_t *>(nullptr), sc, static_cast<size_t>(C));
+                 done += nb;
+               },
+               [&](const TopNDev &dev, EventPair &ev) { then(dev, ev, cand ? dcand.ptr : nullptr, prep_ms); });
+}
+
+// rec_within_device with the result copied to the host and the columns mapped to item ids there.  Without candidates
+// and own lists: rec_run.
+void rec_run_within(mmsbm_hip_ctx *c, const double *x, size_t xs, int64_t n_users, const int32_t *users,
+                    const int32_t *seen_off, const int32_t *seen, const int32_t *cand, int n_cand, const int64_t *xoff,
+                    const int32_t *xit, int n, int32_t *items, double *scores, int32_t *counts) {
+  if (!cand && !xoff) {
+    rec_run(c, x, xs, n_users, users, seen_off, seen, n, items, scores, counts);
+    return;
+  }
+  top_n_blank(n_users, n, items, scores, counts);
+  if ((cand ? n_cand : c->rc->items) == 0 || n_users == 0) {  // (no column to score: every row is empty)
+    c->last_ms[T_RECOMMEND] = 0.f;
+    return;
+  }
+  rec_within_device(c, x, xs, n_users, users, seen_off, seen, cand, n_cand, xoff, xit, n, 0,
+                    [&](const TopNDev &dev, EventPair &ev, const int32_t *, float prep_ms) {
+                      top_n_copy_out(c, dev, ev, n_users, n, T_RECOMMEND, items, scores, counts);
+                      c->last_ms[T_RECOMMEND] += prep_ms;
+                    });
   if (cand)  // columns -> item ids
     for (size_t e = 0; e < static_cast<size_t>(n_users) * n; ++e)
       if (items[e] >= 0) items[e] = cand[items[e]];
@@ -839,6 +886,103 @@ void similar_query(mmsbm_hip_ctx *c, int64_t n_rows, const int32_t *ids, int n, 
             T_SIMILAR, out_ids, distance, counts);
   // the buffer held -D (the selection's order): the distances, +inf behind the last one (a zero leaves as +0.0)
   for (size_t e = 0; distance && e < static_cast<size_t>(n_rows) * n; ++e) distance[e] = -distance[e];
+}
+
+// ---- diversified top-N and the distance of given pairs (diverse.hpp) --------------------------------------------------
+void similar_pairs(mmsbm_hip_ctx *c, int64_t n_pairs, const int32_t *a, const int32_t *b, double *distance) {
+  use_device(c);
+  const SimSession &sm = *c->sm;
+  c->last_ms[T_DIVERSE] = 0.f;
+  if (n_pairs == 0) return;
+  const double denom = static_cast<double>(sm.slots) * static_cast<double>(sm.others);
+  hipStream_t st = c->stream;
+  const int64_t per = std::min<int64_t>(n_pairs, int64_t(1) << 24);  // pairs per launch (16 bytes each)
+  require_free_mem(static_cast<size_t>(per) * 16, "similar_pairs: a batch of pairs");
+  DevBuf<int32_t> da, db;
+  DevBuf<double> dd;
+  da.alloc(static_cast<size_t>(per));
+  db.alloc(static_cast<size_t>(per));
+  dd.alloc(static_cast<size_t>(per));
+  float ms = 0.f;  // device time of the call's kernels (option "diverse_ms")
+  for (int64_t p0 = 0; p0 < n_pairs; p0 += per) {
+    const int64_t np = std::min(per, n_pairs - p0);
+    HIP_CHECK(hipMemcpyAsync(da.ptr, a + p0, sizeof(int32_t) * np, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(db.ptr, b + p0, sizeof(int32_t) * np, hipMemcpyHostToDevice, st));
+    EventPair ev;
+    ev.start(st);
+    LAUNCH(div_pairs_kernel, static_cast<unsigned>((np + kBlock - 1) / kBlock), kBlock, 0, st, sm.q.ptr,
+           static_cast<size_t>(sm.rows) * sm.width, sm.mf.ptr, sm.width, sm.slots, denom, da.ptr, db.ptr, np, dd.ptr);
+    HIP_CHECK(hipGetLastError());
+    ev.stop(st);
+    HIP_CHECK(hipMemcpyAsync(distance + p0, dd.ptr, sizeof(double) * np, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    ms += ev.ms();
+  }
+  c->last_ms[T_DIVERSE] = ms;
+}
+
+void recommend_diverse(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, const int32_t *cand, int n_cand,
+                       const int64_t *xoff, const int32_t *xit, int n, int pool, double trade_off, int32_t *items,
+                       double *scores, double *distances, int32_t *counts) {
+  use_device(c);
+  const RecSession &rc = *c->rc;
+  const SimSession &sm = *c->sm;
+  top_n_blank(n_users, n, items, scores, counts);
+  for (size_t e = 0; distances && e < static_cast<size_t>(n_users) * n; ++e) distances[e] = INFINITY;
+  c->last_ms[T_DIVERSE] = 0.f;
+  if ((cand ? n_cand : rc.items) == 0 || n_users == 0) return;  // (no column to score: every row is empty)
+  hipStream_t st = c->stream;
+  const double denom = static_cast<double>(sm.slots) * static_cast<double>(sm.others);
+  const size_t lds = (static_cast<size_t>(pool) * 21 + 7) / 8 * 8;  // score, m, id, picked flag per place
+  // rows per call: the pool lists (12 bytes a place) and the picks (20 an entry) of all of them unless that is not
+  // free -- then halves of the request until it is (a row's answer does not depend on the other rows)
+  const size_t per_row = static_cast<size_t>(pool) * 12 + static_cast<size_t>(n) * 20 + 16;
+  int64_t rows_per = n_users;
+  if (c->div_rows > 0) {
+    rows_per = std::min<int64_t>(c->div_rows, n_users);
+  } else {
+    size_t free_b = 0, total_b = 0;
+    HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
+    while (rows_per > 1 && static_cast<size_t>(rows_per) * per_row + kRecBatchBytes + (size_t(64) << 20) > free_b)
+      rows_per = (rows_per + 1) / 2;
+  }
+  const size_t xs = static_cast<size_t>(c->ext_users) * rc.rank;
+  float ms = 0.f;  // device time of the query's kernels (option "diverse_ms")
+  std::vector<int64_t> sub;
+  for (int64_t b0 = 0; b0 < n_users; b0 += rows_per) {
+    const int64_t nb = std::min(rows_per, n_users - b0);
+    if (xoff) {  // the rows' own lists, offsets from the first of them
+      sub.resize(static_cast<size_t>(nb) + 1);
+      for (int64_t k = 0; k <= nb; ++k) sub[static_cast<size_t>(k)] = xoff[b0 + k] - xoff[b0];
+    }
+    const size_t outs = static_cast<size_t>(nb) * n;
+    rec_within_device(
+        c, rc.x.ptr, xs, nb, users + b0, rc.excl ? rc.seen_off.ptr : nullptr, rc.seen.ptr, cand, n_cand,
+        xoff ? sub.data() : nullptr, xoff ? xit + xoff[b0] : nullptr, pool, outs * 20 + static_cast<size_t>(nb) * 4,
+        [&](const TopNDev &dev, EventPair &ev, const int32_t *dcand, float prep_ms) {
+          DevBuf<int32_t> ri, rn;
+          DevBuf<double> rs, rd;
+          ri.alloc(outs); rs.alloc(outs); rd.alloc(outs); rn.alloc(static_cast<size_t>(nb));
+          EventPair ev2;
+          ev2.start(st);
+          if (dcand)  // the pool as columns of the compact table -> item ids
+            LAUNCH(div_ids_kernel, static_cast<unsigned>((static_cast<size_t>(nb) * pool + kBlock - 1) / kBlock), kBlock, 0,
+                   st, dcand, n_cand, dev.on, static_cast<int>(nb), pool, dev.oi);
+          LAUNCH(div_greedy_kernel, static_cast<unsigned>(nb), kDivWave, lds, st, sm.q.ptr,
+                 static_cast<size_t>(sm.rows) * sm.width, sm.mf.ptr, sm.width, sm.slots, sm.rows, denom, dev.os,
+                 static_cast<const int32_t *>(dev.oi), dev.on, pool, n, trade_off, ri.ptr, rs.ptr, rd.ptr, rn.ptr);
+          HIP_CHECK(hipGetLastError());
+          ev2.stop(st);
+          const size_t o = static_cast<size_t>(b0) * n;  // (the kernel wrote the padding too: straight into the caller's rows)
+          HIP_CHECK(hipMemcpyAsync(items + o, ri.ptr, sizeof(int32_t) * outs, hipMemcpyDeviceToHost, st));
+          if (scores) HIP_CHECK(hipMemcpyAsync(scores + o, rs.ptr, sizeof(double) * outs, hipMemcpyDeviceToHost, st));
+          if (distances) HIP_CHECK(hipMemcpyAsync(distances + o, rd.ptr, sizeof(double) * outs, hipMemcpyDeviceToHost, st));
+          if (counts) HIP_CHECK(hipMemcpyAsync(counts + b0, rn.ptr, sizeof(int32_t) * nb, hipMemcpyDeviceToHost, st));
+          HIP_CHECK(hipStreamSynchronize(st));
+          ms += ev.ms() + ev2.ms() + prep_ms;
+        });
+  }
+  c->last_ms[T_DIVERSE] = ms;
 }
 
 // ---- the overlap of the restarts' groups (overlap.hpp) ---------------------------------------------------------------

@@ -690,6 +690,21 @@ class MMSBM:
         finally:
             getattr(ctx, kind + "_end")()
 
+    @contextlib.contextmanager
+    def _sessions_of_restarts(self, *sessions):
+        """_session_of_restarts for several kinds at once: ``sessions`` are (kind, *begin_args); every restart the model
+        holds is selected ONCE and added to each of them in that order, so they hold the same slots in the same order.
+        Every session begun is ended however the block ends."""
+        ctx, restarts = self._restarts()
+        with contextlib.ExitStack() as stack:
+            for kind, *begin_args in sessions:
+                getattr(ctx, kind + "_begin")(*begin_args)
+                stack.callback(getattr(ctx, kind + "_end"))
+            for _ in restarts:
+                for kind, *_args in sessions:
+                    getattr(ctx, kind + "_add")()
+            yield ctx
+
     def _top_n_frame(self, query, n, row_labels, item_labels, columns=("users", "items", "score")):
         """The top-``n`` frame (users, items, score, rank) of rows [0, len(row_labels)), fetched in calls of at most
         RECOMMEND_BATCH_ROWS result rows (bounded host memory at a million users): ``query(b, e)`` -> (items, scores,
@@ -798,6 +813,123 @@ class MMSBM:
         with self._session_of_restarts("similar", side) as ctx:
             return self._top_n_frame(lambda b, e: ctx.similar_query(ids[b:e], n), n, labels, side_labels,
                                      columns=(side, "similar", "distance"))
+
+    # ------------------------------------------------------------------ diversified lists (not in the reference)
+    DIVERSE_POOL_MAX = 1024          # largest pool of a diversified query (MMSBM_HIP_RECOMMEND_MAX_N)
+
+    def recommend_diverse(self, users=None, n=10, diversity=..., pool=None, exclude_seen=True, weights=None,
+                          candidates=None, exclude=None):
+        """``recommend`` re-ranked for diversity, on the device: a fitted model puts whole blocks of items on the same
+        memberships, so a user's ``n`` best items are often near-copies of each other.  From the user's ``pool`` best
+        candidates -- ``recommend(n=pool)``'s list, with the same ``exclude_seen``, ``weights``, ``candidates`` and
+        ``exclude`` -- the best one is taken first; then, ``n - 1`` times, the candidate with the largest
+        score + ``diversity`` x (distance to the nearest item taken so far), equal values to the better item of
+        ``recommend``'s order.  The distance is ``similar_items``'s (``distances``).
+
+        ``diversity`` is required: it is in score units per unit of distance, so no default fits every weighting.
+        It must be finite and >= 0; 0 gives ``recommend(n)``'s list, and the larger it is the further apart the items
+        of a list lie.  ``pool``: None means min(1024, 10 n); at least ``n`` and at most 1,024.
+
+        Returns ``recommend``'s frame plus ``distance`` -- to the nearest item ranked above it in the list, +inf at
+        rank 1: columns ``users``, ``items``, ``score``, ``distance``, ``rank``.  ``list_diversity`` summarises a
+        list.  The model's stored predictions and ``score()`` are left as they are."""
+        self._check_whole_model()
+        n, w = self._recommend_args(n, weights)
+        if diversity is ...:
+            raise TypeError("recommend_diverse() needs diversity=: score units per unit of distance (0: plain recommend)")
+        if isinstance(diversity, (bool, np.bool_)) or not isinstance(diversity, (int, float, np.integer, np.floating)) \
+                or not np.isfinite(diversity) or diversity < 0:
+            raise ValueError(f"diversity must be a finite number >= 0, got {diversity!r}")
+        if pool is None:
+            pool = min(self.DIVERSE_POOL_MAX, 10 * n)
+        if isinstance(pool, (bool, np.bool_)) or not isinstance(pool, (int, np.integer)) or pool < 1:
+            raise ValueError(f"pool must be a positive integer, got {pool!r}")
+        if not n <= pool <= self.DIVERSE_POOL_MAX:
+            raise ValueError(f"pool must lie in [n, {self.DIVERSE_POOL_MAX}], got pool={pool} with n={n}")
+        pool, lam = int(pool), float(diversity)
+        enc = self.data_handler
+        ids, labels = self._training_users(users)
+        item_labels = np.asarray(enc.item_labels(), dtype=object) if enc else None
+        cand = None if candidates is None else self._candidate_ids(candidates)
+        dist = []                                                           # the distance column, call by call
+
+        def framed(query, row_labels):
+            df = self._top_n_frame(query, n, row_labels, item_labels)
+            df.insert(3, "distance", np.concatenate(dist) if dist else np.zeros(0))
+            return df
+        if cand is not None and len(cand) == 0:
+            return framed(None, labels[:0])
+        off, its = (None, None) if exclude is None else self._exclusion_lists(exclude, ids)
+        with self._sessions_of_restarts(("recommend", w, exclude_seen), ("similar", "items")) as ctx:
+            def query(b, e):
+                extra = None if off is None else (off[b:e + 1] - off[b], its[off[b]:off[e]])
+                items, scores, distances, counts = ctx.recommend_diverse(ids[b:e], n, pool, lam, cand, extra)
+                dist.append(distances[np.arange(n)[None, :] < counts[:, None]])
+                return items, scores, counts
+            return framed(query, labels)
+
+    def distances(self, pairs, side="items"):
+        """The distance of given pairs of training items (``side="users"``: of training users), on the device:
+        ``similar_items``'s D, the number ``recommend_diverse`` trades against the score.  ``pairs``: a DataFrame whose
+        first two columns hold the two labels of each pair, or an iterable of 2-tuples; a label that is not in the
+        training data: KeyError.  D(a, b) = D(b, a) bit for bit and D(a, a) = 0.
+
+        Returns a DataFrame with columns ``a``, ``b`` (the encoder's labels), ``distance``, rows in request order."""
+        import pandas as pd
+        self._check_whole_model()
+        if side not in ("items", "users"):
+            raise ValueError(f"side must be 'items' or 'users', got {side!r}")
+        left, right = self._pair_columns(pairs)
+        a, a_labels = self._training_ids(left, side)
+        b, b_labels = self._training_ids(right, side)
+        if len(a) == 0:
+            return pd.DataFrame({"a": [], "b": [], "distance": np.zeros(0)})
+        with self._session_of_restarts("similar", side) as ctx:
+            d = self._pair_distances(ctx, a, b)
+        return pd.DataFrame({"a": a_labels, "b": b_labels, "distance": d})
+
+    def _pair_distances(self, ctx, a, b):
+        """ctx.similar_pairs in calls of at most RECOMMEND_BATCH_ROWS pairs."""
+        step = self.RECOMMEND_BATCH_ROWS
+        parts = [ctx.similar_pairs(a[s:s + step], b[s:s + step]) for s in range(0, len(a), step)]
+        return np.concatenate(parts) if parts else np.zeros(0)
+
+    def list_diversity(self, recs):
+        """The intra-list distance of every user's list in a recommend-style frame (``recommend``,
+        ``recommend_diverse``, ``rerank`` ...: the first two columns are users and items): the mean of ``distances``
+        over the unordered pairs of the list's items, on the device -- what ``diversity=`` bought, to be read next to
+        ``ranking_score``.  The items must be in the training data (KeyError); the users are only the lists' names.
+
+        Returns a DataFrame with columns ``users`` (order of first appearance), ``n`` (items in the list) and
+        ``diversity`` (NaN for a list of fewer than two items)."""
+        import pandas as pd
+        self._check_whole_model()
+        us, its = self._pair_columns(recs)
+        iid, _ = self._training_ids(its, "items")
+        names = list(dict.fromkeys(us))
+        place = {u: j for j, u in enumerate(names)}
+        row = np.asarray([place[u] for u in us], dtype=np.int64)
+        order = np.argsort(row, kind="stable")                             # each list's items, in the frame's order
+        sizes = np.bincount(row, minlength=len(names))
+        start = np.concatenate([[0], np.cumsum(sizes)])
+        a, b, owner = [], [], []
+        for j, k in enumerate(sizes.tolist()):
+            if k >= 2:
+                x, y = np.triu_indices(k, 1)
+                mine = iid[order[start[j]:start[j + 1]]]
+                a.append(mine[x])
+                b.append(mine[y])
+                owner.append(np.full(len(x), j, dtype=np.int64))
+        total = np.zeros(len(names))
+        if a:
+            with self._session_of_restarts("similar", "items") as ctx:
+                d = self._pair_distances(ctx, np.concatenate(a).astype(np.int32), np.concatenate(b).astype(np.int32))
+            total = np.bincount(np.concatenate(owner), weights=d, minlength=len(names))
+        pairs = sizes * (sizes - 1) // 2
+        with np.errstate(divide="ignore", invalid="ignore"):
+            mean = np.where(pairs > 0, total / np.maximum(pairs, 1), np.nan)
+        return pd.DataFrame({"users": np.asarray(names, dtype=object) if names else [], "n": sizes.astype(np.int64),
+                             "diversity": mean})
 
     # ------------------------------------------------------------------ matching the restarts' groups (not in the reference)
     def align_restarts(self, reference=None):
