@@ -25,9 +25,17 @@ def _p(a, ctype):
     return a.ctypes.data_as(C.POINTER(ctype))
 
 
-def _csr(offsets, values, rows, name, noun):
-    """(offsets int64, values int32) of a CSR argument over ``rows`` rows, its ``name`` and the ``noun`` of its values
-    in the shape and end checks."""
+def _p_or_null(a, ctype):
+    """_p for an optional array: None is the null pointer."""
+    return None if a is None else _p(a, ctype)
+
+
+def _csr(lists, rows, name, noun):
+    """(offsets int64, values int32) of a CSR argument ``lists`` = (offsets, values) over ``rows`` rows, its ``name``
+    and the ``noun`` of its values in the shape and end checks; (None, None) for None, an optional list left out."""
+    if lists is None:
+        return None, None
+    offsets, values = lists
     off = np.ascontiguousarray(offsets, dtype=np.int64)
     val = _i32(values)
     if off.shape != (rows + 1,):
@@ -382,10 +390,10 @@ class HipEM:
         if t.shape[0] != self._rc_added:
             raise ValueError(f"theta holds {t.shape[0]} blocks, the session {self._rc_added} added slots")
         m, n = t.shape[1], int(n)
-        off, it = (None, None) if seen is None else _csr(seen[0], seen[1], m, "seen offsets", "items")
+        off, it = _csr(seen, m, "seen offsets", "items")
         items, scores, counts = self._query_out(m, n)
-        head = (self._h, m, _p(t, C.c_double), None if off is None else _p(off, C.c_int64),
-                None if it is None else _p(it, C.c_int32))
+        head = (self._h, m, _p(t, C.c_double), _p_or_null(off, C.c_int64),
+                _p_or_null(it, C.c_int32))
         tail = (n, _p(items, C.c_int32), _p(scores, C.c_double), _p(counts, C.c_int32))
         if candidates is None:
             _lib.call("mmsbm_hip_recommend_query_theta", *head, *tail)
@@ -402,11 +410,11 @@ class HipEM:
         recommend_query's: the answer is its row for n = all items, filtered and cut to n."""
         u, n = _i32(users), int(n)
         cand = None if candidates is None else _i32(candidates)
-        off, it = (None, None) if exclude is None else _csr(exclude[0], exclude[1], len(u), "exclude offsets", "items")
+        off, it = _csr(exclude, len(u), "exclude offsets", "items")
         items, scores, counts = self._query_out(len(u), n)
         _lib.call("mmsbm_hip_recommend_query_within", self._h, len(u), _p(u, C.c_int32),
-                  0 if cand is None else len(cand), None if cand is None else _p(cand, C.c_int32),
-                  None if off is None else _p(off, C.c_int64), None if it is None else _p(it, C.c_int32), n,
+                  0 if cand is None else len(cand), _p_or_null(cand, C.c_int32),
+                  _p_or_null(off, C.c_int64), _p_or_null(it, C.c_int32), n,
                   _p(items, C.c_int32), _p(scores, C.c_double), _p(counts, C.c_int32))
         return items, scores, counts
 
@@ -416,7 +424,7 @@ class HipEM:
         users[b].  Returns recommend_query's triple: the n best of each list, without what recommend_query leaves
         out for the user; scores and order are recommend_query's, bit for bit."""
         u, n = _i32(users), int(n)
-        off, it = _csr(offsets, items, len(u), "offsets", "items")
+        off, it = _csr((offsets, items), len(u), "offsets", "items")
         out, scores, counts = self._query_out(len(u), n)
         _lib.call("mmsbm_hip_recommend_rank", self._h, len(u), _p(u, C.c_int32), _p(off, C.c_int64),
                   _p(it, C.c_int32), n, _p(out, C.c_int32), _p(scores, C.c_double), _p(counts, C.c_int32))
@@ -427,7 +435,7 @@ class HipEM:
         order within the open session -- user b's items are items[offsets[b]:offsets[b + 1]] -- and each user's
         number of candidates.  positions: (offsets[-1],) int32; candidates: (len(users),) int32."""
         u = _i32(users)
-        off, it = _csr(offsets, items, len(u), "offsets", "items")
+        off, it = _csr((offsets, items), len(u), "offsets", "items")
         positions = np.empty(len(it), dtype=np.int32)
         candidates = np.empty(len(u), dtype=np.int32)
         _lib.call("mmsbm_hip_recommend_positions", self._h, len(u), _p(u, C.c_int32), _p(off, C.c_int64),
@@ -445,9 +453,9 @@ class HipEM:
         if e.shape[0] != self._rc_added:
             raise ValueError(f"eta holds {e.shape[0]} blocks, the session {self._rc_added} added slots")
         n_new = e.shape[1]
-        off, us = (None, None) if seen is None else _csr(seen[0], seen[1], n_new, "seen offsets", "users")
+        off, us = _csr(seen, n_new, "seen offsets", "users")
         _lib.call("mmsbm_hip_recommend_add_items", self._h, n_new, _p(e, C.c_double),
-                  None if off is None else _p(off, C.c_int64), None if us is None else _p(us, C.c_int32))
+                  _p_or_null(off, C.c_int64), _p_or_null(us, C.c_int32))
 
     MAX_TOP_PAIRS = 1024
 
@@ -461,7 +469,7 @@ class HipEM:
         sc = np.empty(max(m, 0), dtype=np.float64)
         count = C.c_int32(0)
         _lib.call("mmsbm_hip_recommend_top_pairs", self._h, 0 if u is None else len(u),
-                  None if u is None else _p(u, C.c_int32), m, _p(ou, C.c_int32), _p(oi, C.c_int32),
+                  _p_or_null(u, C.c_int32), m, _p(ou, C.c_int32), _p(oi, C.c_int32),
                   _p(sc, C.c_double), C.byref(count))
         return ou, oi, sc, int(count.value)
 
@@ -529,12 +537,12 @@ class HipEM:
         hold the same slots, added in the same order).  distances: to the nearest earlier pick, +inf for the first."""
         u, n, pool = _i32(users), int(n), int(pool)
         cand = None if candidates is None else _i32(candidates)
-        off, it = (None, None) if exclude is None else _csr(exclude[0], exclude[1], len(u), "exclude offsets", "items")
+        off, it = _csr(exclude, len(u), "exclude offsets", "items")
         items, scores, counts = self._query_out(len(u), n)
         distances = np.empty((len(u), max(n, 0)), dtype=np.float64)
         _lib.call("mmsbm_hip_recommend_diverse", self._h, len(u), _p(u, C.c_int32),
-                  0 if cand is None else len(cand), None if cand is None else _p(cand, C.c_int32),
-                  None if off is None else _p(off, C.c_int64), None if it is None else _p(it, C.c_int32), n, pool,
+                  0 if cand is None else len(cand), _p_or_null(cand, C.c_int32),
+                  _p_or_null(off, C.c_int64), _p_or_null(it, C.c_int32), n, pool,
                   float(trade_off), _p(items, C.c_int32), _p(scores, C.c_double), _p(distances, C.c_double),
                   _p(counts, C.c_int32))
         return items, scores, distances, counts
@@ -584,7 +592,7 @@ class HipEM:
         pair's user that carry most of the pair's score, contribution descending, equal ones by ascending item id, then
         rating id; explained: the sum over ALL the user's rows."""
         u, n = _i32(users), int(n)
-        off, it = _csr(offsets, items, len(u), "offsets", "items")
+        off, it = _csr((offsets, items), len(u), "offsets", "items")
         q = len(it)
         hi, hr = np.empty((q, max(n, 0)), dtype=np.int32), np.empty((q, max(n, 0)), dtype=np.int32)
         co = np.empty((q, max(n, 0)), dtype=np.float64)
@@ -666,7 +674,7 @@ class HipEM:
         iters = np.empty(n_new, dtype=np.int32)
         _lib.call(symbol, self._h, len(u), _p(u, C.c_int32), _p(i, C.c_int32), _p(r, C.c_int32),
                   n_new, int(iterations), -1.0 if tol is None else float(tol),
-                  None if start is None else _p(start, C.c_double), _p(out, C.c_double), _p(iters, C.c_int32))
+                  _p_or_null(start, C.c_double), _p(out, C.c_double), _p(iters, C.c_int32))
         return out, iters
 
     # -- measurement -------------------------------------------------------------------------
