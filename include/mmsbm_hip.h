@@ -549,9 +549,15 @@ int mmsbm_hip_time_stage(mmsbm_hip_ctx *ctx, int stage, int reps, float *mean_us
  * of the theta' rows, non-temporal loads of the segments' own rows; 8: whatever the data; results are bitwise the same),
  * "a_units" 0..16 (matrix-core pair stage only: 64-pair units per workgroup of the A launch, which writes rows only and
  * so walks the units in runs of its own length; 0 = the library's choice -- the length that fills its last round of
- * workgroups; the rows are bitwise the same for every value). */
+ * workgroups; the rows are bitwise the same for every value), "pass_dense" -1/0/1 (big problems of small tiles: the
+ * two triple passes and the T + S stage of a committed iteration in one launch, the C rows kept in LDS -- three launches
+ * per iteration; -1 the library's choice by size, 0 off, 1 on wherever the form applies: one restart slot per launch, K
+ * of 17..32, L <= 24, no work lists; results are bitwise the same). */
 int mmsbm_hip_set_option(mmsbm_hip_ctx *ctx, const char *name, double value);
-/* Reads a switch back; also the read-only "launches" (2 or 4: what the next iteration takes), "ranges_pairs" / "ranges_users" (ranges the XCD-local work
+/* Reads a switch back ("pass_dense" reads 1 when the next committed iteration takes that form, else 0); also the
+ * read-only "launches" -- the FAMILY of forms the next iteration takes, not a count: 2 = the two launches of small
+ * problems, 4 = the separate stages, with or without "pass_dense"; a committed iteration really takes
+ * launches - pass_dense launches --, "ranges_pairs" / "ranges_users" (ranges the XCD-local work
  * list of that pass uses, 1 = off), "items_pairs" / "items_users" (work items, 0 = segments as
  * they are), "splits_pairs" / "splits_users" (segments cut into pieces), "fused_split" (bit 0 / 1: whole-segment lists of
  * the two-launch form built for the pair / user side), "item_grid" (1: at least half of the (item, rating) combinations

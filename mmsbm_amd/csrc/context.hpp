@@ -231,7 +231,8 @@ inline void sort_unique_groups(std::vector<int32_t> &off, std::vector<int32_t> &
 enum TimedCall { T_RECOMMEND = 0, T_FOLD_IN, T_POSITIONS, T_TOP_PAIRS, T_AUDIENCE, T_SIMILAR, T_OVERLAP, T_HELDOUT, T_EXPLAIN, T_DIVERSE, T_COUNT };
 
 enum KernelId { K_SEG = 0, K_DENSE, K_ETAP, K_MATVEC_A, K_FUSED_PAIRS, K_FUSED_TAIL, K_COUNT };
-// The four launches of an iteration -- or, for small problems, the two of fused_small.hpp.
+// The four launches of an iteration -- or, for small problems, the two of fused_small.hpp.  With pass_dense.hpp the
+// merged launch (pass_dense_kernel) is timed as stage K_SEG and K_DENSE has no launch: the names stay as they are.
 const char *const kKernelNames[K_COUNT] = {"seg_pass_kernel", "pair_block_kernel(T+S)", "eta_p_kernel",
                                            "pair_block_kernel(A)", "pairs_fused_kernel", "tail_fused_kernel"};
 
@@ -272,6 +273,10 @@ struct mmsbm_hip_ctx {
   DevBuf<mmsbm::WorkItem> fp_items, fu_items;
   DevBuf<mmsbm::FusedSplit> fp_splits, fu_splits;
   int fp_max_parts = 0, fu_max_parts = 0, fu_blocks = 0;
+  // big problems of small tiles: the triple passes and the T + S stage of a committed iteration in one launch, three
+  // launches per iteration (pass_dense.hpp).  Option "pass_dense": -1 the library's choice by size, 0 off, 1 on wherever
+  // the form applies
+  int pass_dense = -1;
   std::vector<char> a_ok;      // per slot: atab[cur] holds A of the CURRENT parameters (the fused form computes A at
                                // the start of an iteration, so after a committed fused iteration it does not)
   int nt_out = 7;          // option "nt_out" (bits: 1 T and A rows, 2 theta' rows as non-temporal stores, 4 the segments' own rows as non-temporal loads) where that pays (nt_on, launch.hpp)

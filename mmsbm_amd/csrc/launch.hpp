@@ -22,6 +22,8 @@ void stage_eta_p(mmsbm_hip_ctx *c, bool commit);
 // tu_fused.hip -- small problems: the iteration in two launches
 void stage_fused_pairs(mmsbm_hip_ctx *c);
 void stage_fused_tail(mmsbm_hip_ctx *c, bool commit);
+// ... and the two triple passes with the T + S stage of a committed iteration in one launch (pass_dense.hpp)
+void stage_pass_dense(mmsbm_hip_ctx *c);
 // tu_once.hip -- once-per-run kernels.  likelihood of the selected slot (the caller holds a OneSlot): kernels onto the
 // context's stream, no wait; returns the number of partial sums in lik_part
 int likelihood_enqueue(mmsbm_hip_ctx *c);

@@ -216,11 +216,33 @@ void mark_a(mmsbm_hip_ctx *c, bool ok) {
 // K = L = 10 38.4 / 31.3 us, 700k 43.8 / 39.8; 300k K = L = 20 45.1 / 41.4, 600k 54.0 / 65.5; 1M x 100k x 20k K = L = 10
 // 77.3 / 92.6) -- up to 18M.
 constexpr long long kFusedWorkMax = 14000000, kFusedWorkMaxSplit = 18000000, kFusedRatingsMax = 1500000;
+
+// ---- big problems of small tiles: the triple passes and the T + S stage in one launch (pass_dense.hpp) ------------
+// Everything but the size: one restart per launch, the small-tile T + S body at 256 threads (its split of a unit's
+// pairs among the slab copies is what the merged kernel mirrors), eight-lane groups on the gathered side, whole
+// segments on both sides (no work lists), every workgroup of the pair stage a single 64-pair unit.
+bool pass_dense_possible(const mmsbm_hip_ctx *c) {
+  return c->launch_slots == 1 && c->code_k == 1 && c->code_l <= 1 && c->n_chunks > 0 && c->pp.pass_dense_shape_ok() &&
+         c->lay.pair_work.items.empty() && c->lay.user_work.items.empty() && c->lay.pair_work.splits.empty() &&
+         c->lay.user_work.splits.empty();
+}
+// ... and the size from which it pays, ratings x (K + L, padded): above the two-launch form's range (kFusedWorkMax), so
+// that no shape goes from two launches to this form (measured per iteration: EXPERIMENTS.md, section C)
+constexpr long long kPassDenseWorkMin = 20000000;
+static_assert(kPassDenseWorkMin > kFusedWorkMaxSplit, "no shape changes from two launches to three");
+
 bool use_fused(const mmsbm_hip_ctx *c) {
   // (fused_possible again: options set after create() -- "mfma", "direct" ... -- change what it depends on)
   const bool cut = !c->lay.pair_work.splits.empty() || !c->lay.user_work.splits.empty();
+  if (c->pass_dense == 1 && !c->fused_forced && pass_dense_possible(c)) return false;  // (option "pass_dense" = 1 asks for that form)
   return c->fused && fused_possible(c) &&
          (c->fused_forced || c->n_obs * c->launch_slots * (c->kp + c->lp) <= (cut ? kFusedWorkMaxSplit : kFusedWorkMax));
+}
+// the next COMMITTED iteration takes the three-launch form (update_coefficients, commit off, needs the raw numerators
+// of the separate launches and keeps them)
+bool use_pass_dense(const mmsbm_hip_ctx *c) {
+  if (c->pass_dense == 0 || use_fused(c) || !pass_dense_possible(c)) return false;
+  return c->pass_dense == 1 || c->n_obs * (c->kp + c->lp) >= kPassDenseWorkMin;
 }
 
 void launch_iteration(mmsbm_hip_ctx *c, bool commit) {
@@ -232,8 +254,12 @@ void launch_iteration(mmsbm_hip_ctx *c, bool commit) {
     return;
   }
   ensure_a(c);
-  stage_seg(c, commit, true, true, c->stream);
-  stage_dense(c);
+  if (commit && use_pass_dense(c)) {
+    stage_pass_dense(c);
+  } else {
+    stage_seg(c, commit, true, true, c->stream);
+    stage_dense(c);
+  }
   stage_eta_p(c, commit);
   if (commit) {
     stage_matvec_a(c, c->cur ^ 1, c->cur ^ 1);
@@ -850,7 +876,16 @@ const Option kOptions[] = {
     // recommend_diverse (diverse.hpp): request rows per call; 0: the library's choice.  It does not change the answer
     {"diverse_rows", [](const Ctx *c) -> double { return static_cast<double>(c->div_rows); },
      [](Ctx *c, double v) { set_audience(c->div_rows, "diverse_rows", v); }},
-    {"launches", [](const Ctx *c) -> double { return use_fused(c) ? 2 : 4; }, nullptr},  // per iteration at the current slot count
+    // the form FAMILY of an iteration at the current slot count: 2 = the two launches of fused_small.hpp, 4 = the separate
+    // stages, with or without "pass_dense" -- the launches a committed iteration really takes are launches - pass_dense
+    {"launches", [](const Ctx *c) -> double { return use_fused(c) ? 2 : 4; }, nullptr},
+    // the triple passes and the T + S stage of a committed iteration in one launch (pass_dense.hpp).  Set: -1 the
+    // library's choice by size, 0 off, 1 on wherever the form applies.  Reads 1 when the next committed iteration takes it
+    {"pass_dense", [](const Ctx *c) -> double { return use_pass_dense(c) ? 1 : 0; },
+     [](Ctx *c, double v) {
+       if (v != -1.0 && v != 0.0 && v != 1.0) throw std::invalid_argument("pass_dense: -1, 0 or 1");
+       c->pass_dense = static_cast<int>(v);
+     }},
     {"wide", [](const Ctx *c) -> double { return c->pp.wide; }, nullptr},
     // 0: a logarithm per element; 1: logarithm tables, a group of lanes per triple; 2: where it applies a wave per pair
     // (lik_fact.hpp), else as 1
@@ -2047,12 +2082,18 @@ int mmsbm_hip_kernel_bytes(const mmsbm_hip_ctx *ctx, int index, int64_t *bytes_r
     const int64_t K = ctx->k, L = ctx->l, Q = ctx->n_pairs;
     const int64_t C = static_cast<int64_t>(ctx->lay.mv_chunks.size());
     int64_t rd = 0, wr = 0;
+    const bool merged = use_pass_dense(ctx);  // K_SEG is the merged launch of pass_dense.hpp, K_DENSE has no launch
     switch (index) {
       case K_SEG:  // two passes: index + one gathered K-row per triple; fixed rows and offsets once
         rd = 2 * N * (4 + 8 * K) + (U + Q) * (8 * K + 4);
         wr = (U + Q) * 8 * K;
+        if (merged) {  // no C rows out; gathered eta rows + item ids + one tile per unit in, T rows + slabs out
+          rd += Q * (8 * L + 4) + C * 8 * K * L;
+          wr += Q * (8 * L - 8 * K) + C * 8 * K * L;
+        }
         break;
       case K_DENSE:  // C rows + gathered eta rows + item ids + one tile per block; T rows + slabs
+        if (merged) break;
         rd = Q * (8 * K + 8 * L + 4) + C * 8 * K * L;
         wr = Q * 8 * L + C * 8 * K * L;
         break;
@@ -2093,9 +2134,18 @@ int mmsbm_hip_time_stage(mmsbm_hip_ctx *ctx, int stage, int reps, float *mean_us
       throw std::invalid_argument("time_stage: the two-launch kernels do not apply to this shape / data");
     use_device(ctx);
     ensure_a(ctx);
+    // (with the triple passes and the T + S stage in one launch, stage K_SEG is that launch and K_DENSE has none: 0 us)
+    const bool merged = use_pass_dense(ctx);
+    if (merged && stage == K_DENSE) {
+      *mean_us = 0.f;
+      return;
+    }
     auto one = [&] {
       switch (stage) {
-        case K_SEG: stage_seg(ctx, true, true, true, ctx->stream); break;
+        case K_SEG:
+          if (merged) stage_pass_dense(ctx);
+          else stage_seg(ctx, true, true, true, ctx->stream);
+          break;
         case K_DENSE: stage_dense(ctx); break;
         case K_ETAP: stage_eta_p(ctx, true); break;
         case K_FUSED_PAIRS: stage_fused_pairs(ctx); break;

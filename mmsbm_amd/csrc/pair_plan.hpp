@@ -79,6 +79,14 @@ struct PairPlan {
            !wide && !mfma && !mfma_big && !direct_out && chunk_pairs == mmsbm::kMvChunkPairs &&
            pairs_fused_lds(kp, lp) <= kLdsBudget;
   }
+  // The plan's share of "the triple passes and the T + S stage run as one launch" (pass_dense.hpp): the T + S launch is
+  // pair_block_kernel<false, true, 1, false, 256, 2, false> over single units -- small tile through scalar loads, one
+  // slot per thread, 256 threads (so rows of up to 24 groups: three double2 of eta rows per thread).  The A launch keeps
+  // its own form whatever it is
+  bool pass_dense_shape_ok() const {
+    return form_t() == PairForm::Block && threads_t == kBlock && !tl_t && nacc == 1 && kt == 2 && spb * nsub <= kBlock &&
+           !direct_out && chunk_pairs == mmsbm::kMvChunkPairs && kUnitPairs * lp <= 3 * 2 * kBlock && lds_t <= kLdsBudget;
+  }
 
   // ---- which kernel the plan selects ----
   PairForm form_t() const {

@@ -7,7 +7,8 @@
 //   tu_pair.hip    the pair stage on the vector ALUs (pair_block.hpp, pair_quad.hpp)
 //   tu_mfma.hip    the pair stage on the matrix cores (pair_mfma.hpp)
 //   tu_etap.hip    eta_p (eta_p.hpp)
-//   tu_fused.hip   the two-launch iteration of small problems (fused_small.hpp)
+//   tu_fused.hip   the two-launch iteration of small problems (fused_small.hpp); the triple passes with the T + S stage
+//                  in one launch (pass_dense.hpp)
 //   tu_once.hip    once-per-run kernels: likelihood, prod_dist / predict, omegas, the random start
 //   tu_layout.hip  the layout's sorts on the device (rocPRIM)
 //   tu_recommend.hip  top-N recommendation (recommend.hpp), nearest items / users (similar.hpp), the m best pairs (top_pairs.hpp),

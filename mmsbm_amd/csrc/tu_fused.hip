@@ -1,10 +1,12 @@
-// tu_fused.hip -- translation unit of the two-launch iteration of small problems: pairs_fused_kernel and
-// tail_fused_kernel (fused_small.hpp; they reuse device code of seg_pass.hpp, pair_block.hpp and eta_p.hpp)
+// tu_fused.hip -- translation unit of the fused forms of the iteration: the two-launch iteration of small problems,
+// pairs_fused_kernel and tail_fused_kernel (fused_small.hpp), and the triple passes with the T + S stage in one launch,
+// pass_dense_kernel (pass_dense.hpp); they reuse device code of seg_pass.hpp, pair_block.hpp and eta_p.hpp
 #include "prelude.hpp"
 #include "seg_pass.hpp"
 #include "pair_block.hpp"
 #include "eta_p.hpp"
 #include "fused_small.hpp"
+#include "pass_dense.hpp"
 
 namespace mmsbm_hip_impl {
 
@@ -60,6 +62,28 @@ void stage_fused_tail(mmsbm_hip_ctx *c, bool commit) {
     default: TAIL(8, 4, 8, 4); break;
   }
 #undef TAIL
+  ls.done();
+}
+
+// The two triple passes and the T + S stage of a committed iteration as one launch (pass_dense.hpp); the caller has
+// checked that the form applies (mmsbm_hip.hip: use_pass_dense).  Timed as stage K_SEG; K_DENSE then has no launch.
+void stage_pass_dense(mmsbm_hip_ctx *c) {
+  LaunchScope ls(c, K_SEG, true);
+  const int s = c->base_slot, cur = c->cur, nt = nt_on(c);
+  PassDenseArgs pa{};
+  pa.a_fixed = a_tab(c, cur); pa.theta = theta_tab(c, cur);
+  pa.pair_off = c->pair_off.ptr; pa.pair_user = c->pair_user.ptr; pa.pair_item = c->pair_item.ptr;
+  pa.chunks = c->mv_chunks.ptr; pa.p_tiles = c->p[cur].at(s); pa.eta = c->eta[cur].at(s);
+  pa.t_out = c->ttab.at(s); pa.partial = c->partial.at(s);
+  pa.kp = c->kp; pa.lp = c->lp; pa.spb = c->pp.spb; pa.nsub = c->pp.nsub;
+  pa.nt = (nt & 1) | ((nt & 4) ? 2 : 0);
+  const SegArgs su = seg_users_args(c, true, c->n_users);
+  const int per = kBlock / group_lanes(c->code_k);
+  pa.n_units = static_cast<int>(c->lay.mv_chunks.size());
+  const int bu = (su.nseg + per - 1) / per;
+  allow_big_lds(pass_dense_kernel<8, 4>, c->pp.lds_t);
+  LAUNCH_IN(ls, (pass_dense_kernel<8, 4>), dim3(static_cast<unsigned>(pa.n_units + bu), 1, 1), kBlock,
+            c->pp.lds_t, c->stream, pa, su, c->kp);
   ls.done();
 }
 
