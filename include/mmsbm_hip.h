@@ -379,6 +379,51 @@ int mmsbm_hip_recommend_diverse(mmsbm_hip_ctx *ctx, int64_t n_users, const int32
                                 int32_t n, int32_t pool, double trade_off, int32_t *items, double *scores,
                                 double *distances, int32_t *counts);
 
+/* ---- the items whose rating tells most about a user: the n largest information gains (mmsbm_amd/csrc/inform.hpp) -- */
+/* A session of its own beside the predict, recommend, similar, overlap, explain and held-out sessions (any of them may
+ * be open meanwhile):
+ *   begin  closes any earlier inform session;
+ *   add    the SELECTED slot joins the session (the slot itself is left unchanged), in external terms: its theta rows,
+ *          the items' rating profiles q_s[i, k, r] = sum_l eta_s[i, l] p_s[k, l, r] (l ascending), their entropies
+ *          h_s[i, k] = sum_r phi(q_s[i, k, r]) (r ascending from +0.0; phi(x) = x > 0 ? -(x log x) : +0.0) and the sums
+ *          sum_u theta_s[u, k] (thread t of 256 adds rows t, t + 256, ... ascending from +0.0, then the 256 partial
+ *          sums are halved 8 times);
+ *   query  for n_users ids of training users (repeats allowed, any order): over the S added slots
+ *            gain_s(u, i) = H( sum_k theta_s[u,k] q_s[i,k,.] ) - sum_k theta_s[u,k] h_s[i,k]         (nats)
+ *            gain(u, i)   = ( sum_s max(gain_s(u, i), +0.0) ) / S,     0 <= gain <= log min(K, R)
+ *          -- the information a rating of item i carries about the group user u acts from -- built as: s ascending; r
+ *          ascending, m_r one fma chain over k ascending from +0.0, H += phi(m_r); lin one fma chain over k of
+ *          theta h; acc += max(H - lin, +0.0); one division by S.  A one-hot theta row gives exactly +0.0 for every
+ *          item.  Per id the n items of largest gain -- gain descending, equal gains (exact fp64 equality) by
+ *          ascending item id -- among cand_items (n_cand strictly ascending item ids; NULL: every item, n_cand
+ *          ignored), without the user's training items when exclude_train is not 0 and without row b's own list
+ *          excl_items[excl_offsets[b] .. excl_offsets[b + 1]) (any order, repeats allowed; excl_offsets NULL: none).
+ *          items / gains: n_users x n, row b holding counts[b] entries followed by item -1 / gain -inf (gains and
+ *          counts may be NULL).  A row's answer depends on that user and the arguments only: bitwise the same whatever
+ *          the other users of the call, the slots the context holds beyond those added, and the side layout;
+ *   query_theta  the same for caller-given users: theta[S][n_users][K], one block per added slot in add order, entries
+ *          finite and >= 0; seen_offsets / seen_items: the items row b leaves out (NULL: none).  A slot's own theta row
+ *          gives the bits query gives for that user;
+ *   mean_theta   out[S][K] = ( sum_u theta_s[u, k] ) / U of the added slots: the membership of a user about whom
+ *          nothing is known;
+ *   end    releases the session's device memory (so does mmsbm_hip_destroy).
+ * mmsbm_hip_get_option(ctx, "inform_ms") reads the device time of the last query's kernels (HIP events).
+ * MMSBM_E_INVALID (before any launch): add, query, query_theta or mean_theta without begin; query, query_theta or
+ * mean_theta before the first add; an id out of range; cand_items not strictly ascending; a bad CSR; n < 1; a theta
+ * entry that is NaN, infinite or negative.  n > MMSBM_HIP_RECOMMEND_MAX_N: MMSBM_E_UNSUPPORTED; MMSBM_E_TOOLARGE where
+ * the device memory of the slots' tables ((U K + I K (R + 1)) doubles per slot) or of a batch is not free.  Touches no
+ * slot, no EM state and no other session. */
+int mmsbm_hip_inform_begin(mmsbm_hip_ctx *ctx);
+int mmsbm_hip_inform_add(mmsbm_hip_ctx *ctx);
+int mmsbm_hip_inform_query(mmsbm_hip_ctx *ctx, int64_t n_users, const int32_t *users, int32_t n_cand,
+                           const int32_t *cand_items, const int64_t *excl_offsets, const int32_t *excl_items,
+                           int exclude_train, int32_t n, int32_t *items, double *gains, int32_t *counts);
+int mmsbm_hip_inform_query_theta(mmsbm_hip_ctx *ctx, int64_t n_users, const double *theta, const int64_t *seen_offsets,
+                                 const int32_t *seen_items, int32_t n_cand, const int32_t *cand_items, int32_t n,
+                                 int32_t *items, double *gains, int32_t *counts);
+int mmsbm_hip_inform_mean_theta(mmsbm_hip_ctx *ctx, double *out);
+int mmsbm_hip_inform_end(mmsbm_hip_ctx *ctx);
+
 /* ---- the overlap of the restarts' groups: the Gram matrix of the membership tables (mmsbm_amd/csrc/overlap.hpp) ---- */
 /* A session of its own beside the predict, recommend, similar and held-out sessions (any of them may be open meanwhile):
  *   begin  side 0: items (eta, G = L groups), 1: users (theta, G = K groups); external sides.  Closes any earlier

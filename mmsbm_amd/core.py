@@ -547,6 +547,61 @@ class HipEM:
                   _p(counts, C.c_int32))
         return items, scores, distances, counts
 
+    # -- the items whose rating tells most about a user (include/mmsbm_hip.h: mmsbm_hip_inform_*) ---------
+    def inform_begin(self):
+        """Open an inform session: the information gain of a rating, averaged over the slots added to it."""
+        _lib.call("mmsbm_hip_inform_begin", self._h)
+        self._inf_added = 0
+
+    def inform_add(self):
+        """Add the selected slot's theta rows, item profiles and their entropies to the session (the slot is left
+        unchanged)."""
+        _lib.call("mmsbm_hip_inform_add", self._h)
+        self._inf_added += 1
+
+    def inform_query(self, users, n, candidates=None, exclude=None, exclude_seen=True):
+        """(items (M,n) int32 padded with -1, gain (M,n) padded with -inf, counts (M,)) for encoded user ids: the n items
+        whose rating would tell most about the group the user acts from -- gain descending, equal gains by ascending
+        item id -- among ``candidates`` (ascending, distinct item ids; None: every item), without the user's training
+        items when ``exclude_seen`` and without ``exclude``: None or (offsets (M+1,) int64, items int32), request row b
+        also leaves out items[offsets[b]:offsets[b + 1]]."""
+        u, n = _i32(users), int(n)
+        cand = None if candidates is None else _i32(candidates)
+        off, it = _csr(exclude, len(u), "exclude offsets", "items")
+        items, gains, counts = self._query_out(len(u), n)
+        _lib.call("mmsbm_hip_inform_query", self._h, len(u), _p(u, C.c_int32), 0 if cand is None else len(cand),
+                  _p_or_null(cand, C.c_int32), _p_or_null(off, C.c_int64), _p_or_null(it, C.c_int32),
+                  int(bool(exclude_seen)), n, _p(items, C.c_int32), _p(gains, C.c_double), _p(counts, C.c_int32))
+        return items, gains, counts
+
+    def inform_query_theta(self, theta, n, seen=None, candidates=None):
+        """inform_query for caller-given users: theta (S, M, K), one (M, K) block per added slot in add order, entries
+        finite and >= 0.  seen: None (nothing excluded) or (offsets (M+1,) int64, items int32): user b leaves out
+        items[offsets[b]:offsets[b + 1]].  candidates as in inform_query."""
+        t = _f64(theta)
+        if t.ndim != 3 or t.shape[2] != self.k:
+            raise ValueError(f"theta has shape {t.shape}, expected (slots, users, {self.k})")
+        if t.shape[0] != getattr(self, "_inf_added", 0):
+            raise ValueError(f"theta holds {t.shape[0]} blocks, the session {getattr(self, '_inf_added', 0)} added slots")
+        m, n = t.shape[1], int(n)
+        cand = None if candidates is None else _i32(candidates)
+        off, it = _csr(seen, m, "seen offsets", "items")
+        items, gains, counts = self._query_out(m, n)
+        _lib.call("mmsbm_hip_inform_query_theta", self._h, m, _p(t, C.c_double), _p_or_null(off, C.c_int64),
+                  _p_or_null(it, C.c_int32), 0 if cand is None else len(cand), _p_or_null(cand, C.c_int32), n,
+                  _p(items, C.c_int32), _p(gains, C.c_double), _p(counts, C.c_int32))
+        return items, gains, counts
+
+    def inform_mean_theta(self):
+        """(S, K): the mean theta row of the training users under each added slot, in add order."""
+        out = np.empty((getattr(self, "_inf_added", 0), self.k), dtype=np.float64)
+        _lib.call("mmsbm_hip_inform_mean_theta", self._h, _p(out, C.c_double) if out.size else None)
+        return out
+
+    def inform_end(self):
+        _lib.call("mmsbm_hip_inform_end", self._h)
+        self._inf_added = 0
+
     # -- the overlap of the restarts' groups on the device (include/mmsbm_hip.h: mmsbm_hip_overlap_*) ----
     def overlap_begin(self, side):
         """Open an overlap session over one side: 0 (or "items") eta's L groups, 1 (or "users") theta's K groups."""

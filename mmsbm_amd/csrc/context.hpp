@@ -176,6 +176,20 @@ struct ExpSession {
   int slots = 0;                        // slots added
 };
 
+// The inform session (mmsbm_hip_inform_begin .. end; inform.hpp): external copies of what the information gain of a
+// (user, item) pair reads, per added slot, and (built by the first query that excludes them) every user's training
+// items.  Created by inform_begin, dropped whole by inform_begin and inform_end; set_slots leaves it alone (it holds
+// copies, nothing of a slot).
+struct InfSession {
+  DevBuf<double> th;                    // [slot][U][K] theta
+  DevBuf<double> q;                     // [slot][I][K R]: the items' rating profiles (sim_profile_kernel)
+  DevBuf<double> h;                     // [slot][I][K]: the entropy of each profile row (inf_entropy_kernel)
+  DevBuf<double> mass;                  // [slot][K]: sum_u theta[u, k] (sim_mass_kernel); theta-bar is this over U
+  DevBuf<int32_t> seen_off, seen;       // per external user: its distinct training items, ascending
+  bool seen_built = false;
+  int slots = 0;                        // slots added
+};
+
 }  // namespace mmsbm_hip_impl
 
 namespace {
@@ -227,8 +241,8 @@ inline void sort_unique_groups(std::vector<int32_t> &off, std::vector<int32_t> &
 // The serving calls whose kernels are timed (mmsbm_hip_ctx::last_ms), in the order of their "<name>_ms" options:
 // recommend_query / recommend_query_items, fold_in / fold_in_items, recommend_positions, recommend_top_pairs,
 // recommend_audience, similar_query, overlap_query, heldout_eval / heldout_add, explain_query, recommend_diverse /
-// similar_pairs
-enum TimedCall { T_RECOMMEND = 0, T_FOLD_IN, T_POSITIONS, T_TOP_PAIRS, T_AUDIENCE, T_SIMILAR, T_OVERLAP, T_HELDOUT, T_EXPLAIN, T_DIVERSE, T_COUNT };
+// similar_pairs, inform_query / inform_query_theta
+enum TimedCall { T_RECOMMEND = 0, T_FOLD_IN, T_POSITIONS, T_TOP_PAIRS, T_AUDIENCE, T_SIMILAR, T_OVERLAP, T_HELDOUT, T_EXPLAIN, T_DIVERSE, T_INFORM, T_COUNT };
 
 enum KernelId { K_SEG = 0, K_DENSE, K_ETAP, K_MATVEC_A, K_FUSED_PAIRS, K_FUSED_TAIL, K_COUNT };
 // The four launches of an iteration -- or, for small problems, the two of fused_small.hpp.  With pass_dense.hpp the
@@ -313,6 +327,7 @@ struct mmsbm_hip_ctx {
   std::unique_ptr<mmsbm_hip_impl::OvlSession> ov;      // overlap
   std::unique_ptr<mmsbm_hip_impl::HoldSession> ho;     // held-out
   std::unique_ptr<mmsbm_hip_impl::ExpSession> ex;      // explain
+  std::unique_ptr<mmsbm_hip_impl::InfSession> inf;     // inform
   float last_ms[T_COUNT] = {};              // device time of the last call's kernels, per TimedCall (options "<name>_ms")
   int top_groups = 0;                       // option "top_pairs_groups": workgroups of gtop_fused_kernel (0: 2 per CU)
   int64_t aud_rows = 0;                     // option "audience_rows": items per COUNT batch (0: the library's choice)

@@ -84,6 +84,17 @@ void recommend_diverse(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, 
 void overlap_begin(mmsbm_hip_ctx *c, int side);
 void overlap_add(mmsbm_hip_ctx *c);  // the selected slot (the caller holds a OneSlot)
 void overlap_query(mmsbm_hip_ctx *c, double *out);
+// ... and the most informative items of a user (inform.hpp): the session of mmsbm_hip_inform_*, arguments checked;
+// cand / excl_* as in recommend_query_within, seen_* as in recommend_query_theta
+void inform_begin(mmsbm_hip_ctx *c);
+void inform_add(mmsbm_hip_ctx *c);  // the selected slot (the caller holds a OneSlot)
+void inform_query(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, const int32_t *cand, int n_cand,
+                  const int64_t *excl_offsets, const int32_t *excl_items, bool exclude_train, int n, int32_t *items,
+                  double *gains, int32_t *counts);
+void inform_query_theta(mmsbm_hip_ctx *c, int64_t n_users, const double *theta, const int64_t *seen_offsets,
+                        const int32_t *seen_items, const int32_t *cand, int n_cand, int n, int32_t *items,
+                        double *gains, int32_t *counts);
+void inform_mean_theta(mmsbm_hip_ctx *c, double *out);
 
 // tu_fold_in.hip -- fold new users (items_side: new items) into the selected slot's fitted eta (theta) and p
 // (fold_in.hpp), arguments checked; x0, x: theta0, theta (eta0, eta); items_side: item[m] in [0, n_new), user[m] in [0, U)

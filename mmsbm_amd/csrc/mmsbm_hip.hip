@@ -858,6 +858,7 @@ const Option kOptions[] = {
     {"audience_ms", [](const Ctx *c) -> double { return c->last_ms[T_AUDIENCE]; }, nullptr},
     {"explain_ms", [](const Ctx *c) -> double { return c->last_ms[T_EXPLAIN]; }, nullptr},
     {"diverse_ms", [](const Ctx *c) -> double { return c->last_ms[T_DIVERSE]; }, nullptr},
+    {"inform_ms", [](const Ctx *c) -> double { return c->last_ms[T_INFORM]; }, nullptr},
     // workgroups of gtop_fused_kernel (top_pairs.hpp); 0: the library's choice
     {"top_pairs_groups", [](const Ctx *c) -> double { return c->top_groups; },
      [](Ctx *c, double v) {
@@ -1852,6 +1853,69 @@ int mmsbm_hip_recommend_diverse(mmsbm_hip_ctx *ctx, int64_t n_users, const int32
                       trade_off, items, scores, distances, counts);
   });
 }
+
+int mmsbm_hip_inform_begin(mmsbm_hip_ctx *ctx) {
+  return guarded([&] {
+    if (!ctx) throw std::invalid_argument("null context");
+    inform_begin(ctx);
+  });
+}
+
+int mmsbm_hip_inform_add(mmsbm_hip_ctx *ctx) {
+  return guarded([&] {
+    require_params(ctx);
+    require_open(ctx, &mmsbm_hip_ctx::inf, "inform");
+    OneSlot one(ctx);
+    inform_add(ctx);
+  });
+}
+
+int mmsbm_hip_inform_query(mmsbm_hip_ctx *ctx, int64_t n_users, const int32_t *users, int32_t n_cand,
+                           const int32_t *cand_items, const int64_t *excl_offsets, const int32_t *excl_items,
+                           int exclude_train, int32_t n, int32_t *items, double *gains, int32_t *counts) {
+  return guarded([&] {
+    require_open(ctx, &mmsbm_hip_ctx::inf, "inform", "inform_query");
+    if (n_users < 0) throw std::invalid_argument("negative n_users");
+    require_n(n, "inform", "items");
+    if (n_users > 0 && (!users || !items)) throw std::invalid_argument("null argument");
+    require_ids(users, n_users, ctx->ext_users, "inform: user");
+    require_subset(cand_items, n_cand, ctx->ext_items, "inform_query");
+    check_csr(excl_offsets, excl_items, n_users, ctx->ext_items, "inform_query", "excl_offsets", "user",
+              "excluded items", "excluded item");
+    inform_query(ctx, n_users, users, cand_items, n_cand, n_users > 0 ? excl_offsets : nullptr, excl_items,
+                 exclude_train != 0, n, items, gains, counts);
+  });
+}
+
+int mmsbm_hip_inform_query_theta(mmsbm_hip_ctx *ctx, int64_t n_users, const double *theta, const int64_t *seen_offsets,
+                                 const int32_t *seen_items, int32_t n_cand, const int32_t *cand_items, int32_t n,
+                                 int32_t *items, double *gains, int32_t *counts) {
+  return guarded([&] {
+    const InfSession &inf = require_open(ctx, &mmsbm_hip_ctx::inf, "inform", "inform_query_theta");
+    if (n_users < 0) throw std::invalid_argument("negative n_users");
+    require_n(n, "inform", "items");
+    if (n_users > 0 && (!theta || !items)) throw std::invalid_argument("null argument");
+    // (a NaN gain has no place in the order, and the entropy of a negative weight is not one)
+    const size_t n_theta = static_cast<size_t>(inf.slots) * static_cast<size_t>(n_users) * ctx->ext_k;
+    for (size_t e = 0; e < n_theta; ++e)
+      if (!std::isfinite(theta[e]) || theta[e] < 0.0)
+        throw std::invalid_argument("inform: theta entry " + std::to_string(e) + " is not a finite number >= 0");
+    require_subset(cand_items, n_cand, ctx->ext_items, "inform_query_theta");
+    check_csr(seen_offsets, seen_items, n_users, ctx->ext_items, "inform", "seen_offsets", "user", "seen items",
+              "seen item");
+    inform_query_theta(ctx, n_users, theta, seen_offsets, seen_items, cand_items, n_cand, n, items, gains, counts);
+  });
+}
+
+int mmsbm_hip_inform_mean_theta(mmsbm_hip_ctx *ctx, double *out) {
+  return guarded([&] {
+    require_open(ctx, &mmsbm_hip_ctx::inf, "inform", "inform_mean_theta");
+    if (!out) throw std::invalid_argument("null out");
+    inform_mean_theta(ctx, out);
+  });
+}
+
+int mmsbm_hip_inform_end(mmsbm_hip_ctx *ctx) { return end_session(ctx, &mmsbm_hip_ctx::inf); }
 
 int mmsbm_hip_overlap_begin(mmsbm_hip_ctx *ctx, int side) {
   return guarded([&] {

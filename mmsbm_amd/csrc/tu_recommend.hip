@@ -8,7 +8,9 @@
 // part of the catalogue (catalogue.hpp): a subset of the items through the same batches and selection over a compact
 // item table, and per-user candidate lists through a kernel of their own; and the diversified top-N (diverse.hpp), the
 // one query that reads the recommend and the similarity session at once: the pool through the same batches and
-// selection, kept on the device, then a greedy kernel of its own
+// selection, kept on the device, then a greedy kernel of its own; and the most informative items of a user
+// (inform.hpp): a session of its own whose prologue borrows the similarity session's two kernels and whose queries go
+// through the same batches, exclusions and selection behind a score kernel of their own
 #include "prelude.hpp"
 #include "recommend.hpp"
 #include "similar.hpp"
@@ -17,6 +19,7 @@
 #include "audience.hpp"
 #include "catalogue.hpp"
 #include "diverse.hpp"
+#include "inform.hpp"
 
 #include <climits>
 
@@ -40,6 +43,29 @@ void require_free_mem(size_t bytes, const std::string &what) {
                                          std::to_string(free_b >> 20) + " MB free");
 }
 
+namespace {
+
+// Every external user's distinct training items, ascending, from the id columns in their original order: the offsets
+// [U + 1] (returned) and the items (`item`)
+std::vector<int32_t> train_item_lists(mmsbm_hip_ctx *c, std::vector<int32_t> &item) {
+  hipStream_t s = c->stream;
+  const size_t n = static_cast<size_t>(c->n_obs);
+  std::vector<int32_t> ou(n), oi(n);
+  if (n > 0) {
+    HIP_CHECK(hipMemcpyAsync(ou.data(), c->orig_u.ptr, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(oi.data(), c->orig_i.ptr, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s));
+  }
+  HIP_CHECK(hipStreamSynchronize(s));
+  const std::vector<int32_t> &eu = c->swapped ? oi : ou, &ei = c->swapped ? ou : oi;  // (internal users = external items)
+  item.assign(n, 0);
+  std::vector<int32_t> off = group_by_key<int32_t>(eu.data(), static_cast<int64_t>(n), c->ext_users,
+                                                   [&](int64_t m, int32_t at) { item[at] = ei[m]; });
+  sort_unique_groups(off, item);  // (duplicate pairs dropped)
+  return off;
+}
+
+}  // namespace
+
 void recommend_begin(mmsbm_hip_ctx *c, const double *weights, int exclude_train) {
   use_device(c);
   c->rc.reset();  // (from here on the previous session is gone)
@@ -49,19 +75,8 @@ void recommend_begin(mmsbm_hip_ctx *c, const double *weights, int exclude_train)
   HIP_CHECK(hipMemcpyAsync(rc->w.ptr, weights, sizeof(double) * c->n_ratings, hipMemcpyHostToDevice, s));
   rc->excl = exclude_train != 0;
   if (rc->excl) {
-    // every external user's distinct training items, ascending: from the id columns in their original order
-    const size_t n = static_cast<size_t>(c->n_obs);
-    std::vector<int32_t> ou(n), oi(n);
-    if (n > 0) {
-      HIP_CHECK(hipMemcpyAsync(ou.data(), c->orig_u.ptr, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s));
-      HIP_CHECK(hipMemcpyAsync(oi.data(), c->orig_i.ptr, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s));
-    }
-    HIP_CHECK(hipStreamSynchronize(s));
-    const std::vector<int32_t> &eu = c->swapped ? oi : ou, &ei = c->swapped ? ou : oi;  // (internal users = external items)
-    std::vector<int32_t> item(n);
-    std::vector<int32_t> off = group_by_key<int32_t>(eu.data(), static_cast<int64_t>(n), c->ext_users,
-                                                     [&](int64_t m, int32_t at) { item[at] = ei[m]; });
-    sort_unique_groups(off, item);  // (duplicate pairs dropped)
+    std::vector<int32_t> item;
+    std::vector<int32_t> off = train_item_lists(c, item);
     rc->seen_off.upload(off, s);
     rc->seen_off_h = off;  // (candidate counts of recommend_positions)
     rc->seen.upload(item, s);
@@ -983,6 +998,159 @@ void recommend_diverse(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, 
         });
   }
   c->last_ms[T_DIVERSE] = ms;
+}
+
+// ---- the most informative items of a user (inform.hpp) ----------------------------------------------------------------
+void inform_begin(mmsbm_hip_ctx *c) {
+  use_device(c);
+  c->inf.reset();  // (from here on the previous session is gone)
+  c->inf = std::make_unique<InfSession>();
+}
+
+void inform_add(mmsbm_hip_ctx *c) {  // the selected slot (the caller holds a OneSlot)
+  use_device(c);
+  InfSession &inf = *c->inf;
+  const int U = c->ext_users, I = c->ext_items, K = c->ext_k, L = c->ext_l, R = c->n_ratings, S = inf.slots;
+  const size_t ths = static_cast<size_t>(U) * K, hs = static_cast<size_t>(I) * K, qs = hs * R;
+  require_free_mem((S + 1) * (ths + qs + hs + K) * sizeof(double), "inform: the slots' profiles");
+  hipStream_t st = c->stream;
+  DevBuf<double> nt, nq, nh, nm;  // the four tables grow by one slot
+  double *to = grow_by_slot(inf.th, ths, S, st, nt), *qo = grow_by_slot(inf.q, qs, S, st, nq);
+  double *ho = grow_by_slot(inf.h, hs, S, st, nh), *mo = grow_by_slot(inf.mass, static_cast<size_t>(K), S, st, nm);
+  const ExtSlot e = ext_slot(c);
+  if (ths > 0)  // the users' rows as they are, external sides (rec_fold_kernel without a matrix)
+    LAUNCH(rec_fold_kernel, static_cast<unsigned>((ths + kBlock - 1) / kBlock), kBlock, 0, st, e.users, K, nullptr, 0, 0,
+           to, U, K);
+  LAUNCH(sim_mass_kernel, static_cast<unsigned>(K), kBlock, 0, st, e.users, U, 1, mo);
+  if (qs > 0) {
+    LAUNCH(sim_profile_kernel, static_cast<unsigned>((qs + kBlock - 1) / kBlock), kBlock, 0, st, e.items, L, e.p, e.rs,
+           e.ks, e.ls, qo, I, K, R);
+    LAUNCH(inf_entropy_kernel, static_cast<unsigned>((hs + kBlock - 1) / kBlock), kBlock, 0, st,
+           static_cast<const double *>(qo), ho, hs, R);
+  }
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipStreamSynchronize(st));
+  inf.th.swap(nt);
+  inf.q.swap(nq);
+  inf.h.swap(nh);
+  inf.mass.swap(nm);
+  inf.slots = S + 1;
+}
+
+namespace {
+
+// An inform query: request rows users[0 .. n_users) (host ids, rows of th: `slots` tables of ts doubles, [row][K])
+// against every item.  seen_off / seen (device, indexed by those ids): the items left out, or null; cand[0 .. n_cand)
+// (host; ascending, distinct item ids; null: every item): the candidate mask; xoff / xit (host, by request row, any
+// order, repeats allowed; null: none): the query's own excluded items.
+void inf_run(mmsbm_hip_ctx *c, const double *th, size_t ts, int64_t n_users, const int32_t *users,
+             const int32_t *seen_off, const int32_t *seen, const int32_t *cand, int n_cand, const int64_t *xoff,
+             const int32_t *xit, int n, int32_t *items, double *gains, int32_t *counts) {
+  const InfSession &inf = *c->inf;
+  const int I = c->ext_items, K = c->ext_k, R = c->n_ratings, S = inf.slots;
+  c->last_ms[T_INFORM] = 0.f;
+  if (I == 0 || n_users == 0 || (cand && n_cand == 0)) {  // (no column to score: every row is empty)
+    top_n_blank(n_users, n, items, gains, counts);
+    return;
+  }
+  hipStream_t st = c->stream;
+  const int64_t n_x = xoff ? xoff[n_users] : 0;  // (checked: below 2^31)
+  require_free_mem((cand ? static_cast<size_t>(I) : 0) + (xoff ? (static_cast<size_t>(n_users) + 1 + n_x) * 4 : 0),
+                   "inform: the candidate mask and the query's excluded items");
+  DevBuf<uint8_t> dmask;
+  DevBuf<int32_t> dxo, dxi;
+  if (cand) {
+    std::vector<uint8_t> hm(static_cast<size_t>(I), 0);
+    for (int e = 0; e < n_cand; ++e) hm[static_cast<size_t>(cand[e])] = 1;
+    dmask.upload(hm, st);
+    HIP_CHECK(hipStreamSynchronize(st));  // (`hm` is a local)
+  }
+  std::vector<int32_t> hxo;
+  if (xoff) {
+    hxo.assign(xoff, xoff + n_users + 1);
+    dxo.upload(hxo, st);
+    dxi.alloc(static_cast<size_t>(n_x));
+    if (n_x > 0) HIP_CHECK(hipMemcpyAsync(dxi.ptr, xit, sizeof(int32_t) * n_x, hipMemcpyHostToDevice, st));
+  }
+  const size_t hs = static_cast<size_t>(I) * K, qs = hs * R;
+  int64_t done = 0;  // rows of the request the earlier batches held (the batches follow each other)
+  top_n_run(c, I, n_users, users, n, "inform: a batch of users",
+            [&](const int32_t *ub, int nb, double *sc) {
+              const dim3 g(static_cast<unsigned>((I + kInfTile - 1) / kInfTile),
+                           static_cast<unsigned>((nb + kInfTile - 1) / kInfTile));
+              LAUNCH(inf_score_kernel, g, kBlock, 0, st, th, ts, static_cast<const double *>(inf.q.ptr), qs,
+                     static_cast<const double *>(inf.h.ptr), hs, ub, nb, I, K, R, S,
+                     static_cast<const uint8_t *>(dmask.ptr), sc, static_cast<size_t>(I));
+              if (seen_off) LAUNCH(rec_exclude_kernel, nb, kBlock, 0, st, ub, seen_off, seen, sc, static_cast<size_t>(I));
+              if (xoff)
+                LAUNCH(cat_exclude_kernel, nb, kBlock, 0, st, static_cast<const int32_t *>(nullptr), static_cast<int>(done),
+                       static_cast<const int32_t *>(dxo.ptr), static_cast<const int32_t *>(dxi.ptr),
+                       static_cast<const int32_t *>(nullptr), sc, static_cast<size_t>(I));
+              done += nb;
+            },
+            T_INFORM, items, gains, counts);
+}
+
+}  // namespace
+
+void inform_query(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, const int32_t *cand, int n_cand,
+                  const int64_t *excl_offsets, const int32_t *excl_items, bool exclude_train, int n, int32_t *items,
+                  double *gains, int32_t *counts) {
+  use_device(c);
+  InfSession &inf = *c->inf;
+  if (exclude_train && !inf.seen_built) {  // every user's training items, built by the first query that leaves them out
+    std::vector<int32_t> item;
+    const std::vector<int32_t> off = train_item_lists(c, item);
+    require_free_mem((off.size() + item.size()) * sizeof(int32_t), "inform: the users' training items");
+    DevBuf<int32_t> d_off, d_item;
+    d_off.upload(off, c->stream);
+    d_item.upload(item, c->stream);
+    HIP_CHECK(hipStreamSynchronize(c->stream));  // (host vectors are locals)
+    inf.seen_off.swap(d_off);
+    inf.seen.swap(d_item);
+    inf.seen_built = true;
+  }
+  inf_run(c, inf.th.ptr, static_cast<size_t>(c->ext_users) * c->ext_k, n_users, users,
+          exclude_train ? inf.seen_off.ptr : nullptr, inf.seen.ptr, cand, n_cand, excl_offsets, excl_items, n, items,
+          gains, counts);
+}
+
+void inform_query_theta(mmsbm_hip_ctx *c, int64_t n_users, const double *theta, const int64_t *seen_offsets,
+                        const int32_t *seen_items, const int32_t *cand, int n_cand, int n, int32_t *items,
+                        double *gains, int32_t *counts) {
+  use_device(c);
+  const int K = c->ext_k, S = c->inf->slots;
+  const size_t tk = static_cast<size_t>(n_users) * K;
+  const int64_t n_seen = seen_offsets && n_users > 0 ? seen_offsets[n_users] : 0;  // (checked: below 2^31)
+  require_free_mem(S * tk * sizeof(double) + (static_cast<size_t>(n_users) + 1 + n_seen) * 4,
+                   "inform: the caller's theta rows");
+  hipStream_t st = c->stream;
+  DevBuf<double> th;  // the caller's rows as they are: request row b is row b of every slot's block
+  DevBuf<int32_t> soff, sit;
+  th.alloc(S * tk);
+  if (S * tk > 0) HIP_CHECK(hipMemcpyAsync(th.ptr, theta, sizeof(double) * S * tk, hipMemcpyHostToDevice, st));
+  std::vector<int32_t> hid(static_cast<size_t>(n_users)), hoff;
+  for (int64_t b = 0; b < n_users; ++b) hid[static_cast<size_t>(b)] = static_cast<int32_t>(b);
+  if (seen_offsets && n_users > 0) {
+    hoff.assign(seen_offsets, seen_offsets + n_users + 1);
+    soff.upload(hoff, st);
+    sit.alloc(static_cast<size_t>(n_seen));
+    if (n_seen > 0)
+      HIP_CHECK(hipMemcpyAsync(sit.ptr, seen_items, sizeof(int32_t) * n_seen, hipMemcpyHostToDevice, st));
+  }
+  inf_run(c, th.ptr, tk, n_users, hid.data(), soff.ptr, sit.ptr, cand, n_cand, nullptr, nullptr, n, items, gains,
+          counts);
+  HIP_CHECK(hipStreamSynchronize(st));  // (`th` and the lists are locals)
+}
+
+void inform_mean_theta(mmsbm_hip_ctx *c, double *out) {
+  use_device(c);
+  const InfSession &inf = *c->inf;
+  const size_t n = static_cast<size_t>(inf.slots) * c->ext_k;
+  HIP_CHECK(hipMemcpyAsync(out, inf.mass.ptr, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
+  HIP_CHECK(hipStreamSynchronize(c->stream));
+  const double users = static_cast<double>(c->ext_users);
+  for (size_t e = 0; e < n; ++e) out[e] /= users;  // (the masses were summed on the device: one division each)
 }
 
 // ---- the overlap of the restarts' groups (overlap.hpp) ---------------------------------------------------------------

@@ -113,8 +113,8 @@ class _Side:
 
 @contextlib.contextmanager
 def session(ctx, kind, *begin_args):
-    """ctx's ``kind`` session ("recommend", "similar", "overlap", "explain", "heldout") begun with ``begin_args`` around
-    the block, ended however the block ends."""
+    """ctx's ``kind`` session ("recommend", "similar", "overlap", "explain", "inform", "heldout") begun with
+    ``begin_args`` around the block, ended however the block ends."""
     getattr(ctx, kind + "_begin")(*begin_args)
     try:
         yield ctx
@@ -920,6 +920,86 @@ class Serving:
         with self._session_with_new_items(rows, labels, w, exclude_seen, iterations, tol) as ctx:
             return self._top_n_frame(lambda b, e: ctx.recommend_query_items(ids[b:e], n), n, labels,
                                      self._side("users"), columns=("items", "users", "score"))
+
+
+    # ------------------------------------------------------------------ which items to ask about (not in the reference)
+    _GAIN_COLUMNS = ("users", "items", "gain")
+
+    def informative_items(self, users=None, n=10, exclude_seen=True, candidates=None, exclude=None):
+        """The ``n`` items whose rating would tell most about each training user, on the device.
+
+        A rating of item i by user u is generated as k ~ theta[u], l ~ eta[i], r ~ p[k, l, .].  With the item's rating
+        profile q[i, k, :] = sum_l eta[i, l] p[k, l, :] the information the rating carries about the group k the user
+        acts from is gain(u, i) = H(sum_k theta[u, k] q[i, k, :]) - sum_k theta[u, k] H(q[i, k, :]) in nats, between 0
+        and log min(K, R), mean over the restarts the model holds: zero for an item every group rates alike and for a
+        user whose theta is one-hot, largest where the groups the user may belong to disagree.  It does not depend on
+        how a restart happens to label its groups.
+
+        Candidates are all training items, without the user's own training items when ``exclude_seen``;
+        ``candidates`` and ``exclude`` as in ``recommend``.  Order: gain descending, equal gains by ascending encoded
+        item id.  Returns a DataFrame with columns ``users``, ``items``, ``gain``, ``rank`` (1 = most informative),
+        users in request order (``users=None``: every training user), labels as ``recommend`` returns them.  The
+        model's stored predictions and ``score()`` are left as they are."""
+        self._check_whole_model()
+        n = check_integer(n, "n", 1)
+        ids, labels = self._side("users").request(users)
+        items = self._side("items")
+        cand = self._candidate_ids(candidates)
+        if cand is not None and len(cand) == 0:
+            return self._top_n_frame(None, n, labels[:0], items, self._GAIN_COLUMNS)
+        extra = self._exclusion_lists(exclude, ids)
+        with self._session_of_restarts("inform") as ctx:
+            return self._top_n_frame(
+                lambda b, e: ctx.inform_query(ids[b:e], n, cand, group_slice(extra, b, e), exclude_seen),
+                n, labels, items, self._GAIN_COLUMNS)
+
+    def ask_next(self, data, n=10, candidates=None, prior=1.0, iterations=100, tol=None):
+        """The ``n`` items to ask each NEW user about next: ``informative_items`` for users that were not in the
+        training data, from the few ratings ``data`` holds of them (users, items, ratings like ``fold_in``'s).
+
+        Each restart's theta comes from ``fold_in`` (same ``iterations`` and ``tol``) and is shrunk towards the
+        population, theta_used = (d_u theta_fold + prior theta_bar) / (d_u + prior), where d_u is the user's number of
+        known rows in ``data``, theta_bar the restart's mean training theta and ``prior`` a pseudo-count >= 0: a
+        maximum-likelihood theta from one or two ratings is close to one-hot, and a one-hot theta has gain 0
+        everywhere.  ``prior=0``: the folded theta itself.  The items a user rated in ``data`` are left out;
+        ``candidates`` as in ``recommend`` -- the items people can be expected to know.
+
+        Returns ``informative_items``'s frame, users in order of first appearance in ``data``.
+        ``self.fold_in_iterations`` as ``fold_in`` leaves it.  The model itself is left as it is."""
+        self._check_whole_model()
+        n = check_integer(n, "n", 1)
+        prior = check_finite(prior, "prior", 0, "a finite number >= 0")
+        cand = self._candidate_ids(candidates)
+        iterations, tol = self._fold_args(iterations, tol)
+        rows, labels = self._encode_new(data, 0)
+        if cand is not None and len(cand) == 0:
+            return self._top_n_frame(None, n, labels[:0], self._side("items"), self._GAIN_COLUMNS)
+        with session(self._ctx(self._device_list()[0]), "inform") as ctx:
+            thetas, iters = self._fold_runs(rows, len(labels), iterations, tol, each=lambda c: c.inform_add())
+            self.fold_in_iterations = pd.DataFrame(np.stack(iters, 1), index=pd.Index(labels, name="users"))
+            theta = np.stack(thetas)                                  # (restarts, new users, K)
+            if prior > 0:
+                d = np.bincount(rows[:, 0], minlength=len(labels)).astype(np.float64)[None, :, None]
+                theta = (d * theta + prior * ctx.inform_mean_theta()[:, None, :]) / (d + prior)
+            seen = grouped(rows[:, 0], rows[:, 1], len(labels), sort=True)
+            return self._top_n_frame(
+                lambda b, e: ctx.inform_query_theta(theta[:, b:e], n, group_slice(seen, b, e), cand),
+                n, labels, self._side("items"), self._GAIN_COLUMNS)
+
+    def interview(self, n=10, candidates=None):
+        """The ``n`` items to ask a user about whom nothing is known: ``informative_items`` under each restart's mean
+        training theta.  ``candidates`` as in ``recommend``.  Returns a DataFrame with columns ``items``, ``gain``,
+        ``rank`` (1 = most informative)."""
+        self._check_whole_model()
+        n = check_integer(n, "n", 1)
+        cand = self._candidate_ids(candidates)
+        if cand is not None and len(cand) == 0:
+            return pd.DataFrame({"items": [], "gain": np.zeros(0), "rank": np.zeros(0, dtype=np.int64)})
+        with self._session_of_restarts("inform") as ctx:
+            items, gains, counts = ctx.inform_query_theta(ctx.inform_mean_theta()[:, None, :], n, None, cand)
+        count = int(counts[0])
+        return pd.DataFrame({"items": self._side("items").label(items[0, :count]), "gain": gains[0, :count],
+                             "rank": np.arange(1, count + 1, dtype=np.int64)})
 
 
 def ranking_metrics(users, items, ratings, position, candidates, ks, relevant=None):
