@@ -379,6 +379,42 @@ int mmsbm_hip_recommend_diverse(mmsbm_hip_ctx *ctx, int64_t n_users, const int32
                                 int32_t n, int32_t pool, double trade_off, int32_t *items, double *scores,
                                 double *distances, int32_t *counts);
 
+/* Group queries of the open recommend session (mmsbm_amd/csrc/group.hpp): what a set of users should get together.
+ * Group g's members are members[offsets[g] .. offsets[g + 1]): ids of training users, in any order, distinct within a
+ * group (a user may be in several groups).  With score(m, i) the score recommend_query gives the pair, bit for bit, the
+ * group's value of item i is
+ *   MMSBM_HIP_GROUP_MIN    least misery:   min_m score(m, i)
+ *   MMSBM_HIP_GROUP_MAX    most pleasure:  max_m score(m, i)
+ *   MMSBM_HIP_GROUP_COUNT  approval:       the number of members with score(m, i) >= bar, as a double (`bar` is
+ *                          compared with the final score, the quotient by S; it is ignored by the other modes)
+ *   MMSBM_HIP_GROUP_MEAN   the score of the group's mean row: per slot xbar[j] = (x[m_0, j] + x[m_1, j] + ...) / |g|,
+ *                          one chain from +0.0 in the member order given, then the fma chain and the division by S of
+ *                          recommend_query.  A group of one gets its member's scores, bit for bit
+ * formed without a buffer of members x items (device memory: groups of a batch x items, the lists, the member ids).
+ * Candidates: cand_items as in recommend_query_within (n_cand strictly ascending ids of the session's catalogue; NULL:
+ * the whole catalogue, the items of recommend_add_items included, n_cand ignored), without every item that ANY member
+ * has in the session's excluded lists (the training pairs while exclude_train is set, the seen lists of
+ * recommend_add_items).  items / scores: n_groups x n, row g holding counts[g] = min(n, candidates left) entries --
+ * value descending, equal values (exact fp64 equality) by ascending item id -- followed by item -1 / value -inf
+ * (scores and counts may be NULL); a group without members has count 0.  The value of (g, i) depends on g's members
+ * and i alone (MEAN: and on their order): bitwise the same wherever g stands in the request, whatever the other groups
+ * are, and in swapped and unswapped contexts.  Touches no slot, no EM state and no other session; the recommend session
+ * stays open and answers as before.  mmsbm_hip_get_option(ctx, "group_ms") reads the device time of the call's kernels.
+ * MIN, MAX and COUNT do not depend on how the member rows are dealt to workgroups (option "group_run_blocks": blocks of
+ * 8 member rows per workgroup and item tile, 0 = the library's choice -- time, never the answer).
+ * MMSBM_E_INVALID (before any launch): no recommend session or no slot added to it, a bad CSR, an id out of range, a
+ * member repeated within a group, an unknown mode, a bar that is not finite in COUNT mode, cand_items not strictly
+ * ascending, n < 1.  n > MMSBM_HIP_RECOMMEND_MAX_N: MMSBM_E_UNSUPPORTED; MMSBM_E_TOOLARGE where the device memory is
+ * not free. */
+#define MMSBM_HIP_GROUP_MIN 0
+#define MMSBM_HIP_GROUP_MAX 1
+#define MMSBM_HIP_GROUP_COUNT 2
+#define MMSBM_HIP_GROUP_MEAN 3
+int mmsbm_hip_recommend_query_groups(mmsbm_hip_ctx *ctx, int64_t n_groups, const int64_t *offsets,
+                                     const int32_t *members, int mode, double bar, int32_t n_cand,
+                                     const int32_t *cand_items, int32_t n, int32_t *items, double *scores,
+                                     int32_t *counts);
+
 /* ---- the items whose rating tells most about a user: the n largest information gains (mmsbm_amd/csrc/inform.hpp) -- */
 /* A session of its own beside the predict, recommend, similar, overlap, explain and held-out sessions (any of them may
  * be open meanwhile):

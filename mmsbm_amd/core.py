@@ -547,6 +547,31 @@ class HipEM:
                   _p(counts, C.c_int32))
         return items, scores, distances, counts
 
+    # -- group queries of the recommend session (include/mmsbm_hip.h: mmsbm_hip_recommend_query_groups) -----
+    GROUP_MODES = {"min": 0, "max": 1, "count": 2, "mean": 3}   # MMSBM_HIP_GROUP_*
+
+    def recommend_query_groups(self, offsets, members, n, mode, bar=0.0, candidates=None):
+        """(items (G,n) int32 padded with -1, scores (G,n) padded with -inf, counts (G,)) for G groups of encoded user
+        ids: group g's members are members[offsets[g]:offsets[g + 1]] (distinct within a group).  ``mode`` (a key of
+        GROUP_MODES or its number): "min" the lowest score a member gives the item, "max" the highest, "count" the
+        number of members whose score is >= ``bar``, "mean" the score of the group's mean row.  Candidates:
+        ``candidates`` (ascending, distinct item ids of the session's catalogue; None: all of it) without every item
+        that recommend_query leaves out for ANY member.  Order: value descending, equal values by ascending item id.
+        The members' scores are recommend_query's, bit for bit."""
+        m, n = _i32(members), int(n)
+        off = np.ascontiguousarray(offsets, dtype=np.int64)
+        if off.ndim != 1 or len(off) < 1:
+            raise ValueError(f"offsets have shape {off.shape}, expected (groups + 1,)")
+        if off[-1] != len(m):
+            raise ValueError(f"offsets end at {int(off[-1])}, members holds {len(m)}")
+        groups = len(off) - 1
+        cand = None if candidates is None else _i32(candidates)
+        items, scores, counts = self._query_out(groups, n)
+        _lib.call("mmsbm_hip_recommend_query_groups", self._h, groups, _p(off, C.c_int64), _p(m, C.c_int32),
+                  int(self.GROUP_MODES.get(mode, mode)), float(bar), 0 if cand is None else len(cand),
+                  _p_or_null(cand, C.c_int32), n, _p(items, C.c_int32), _p(scores, C.c_double), _p(counts, C.c_int32))
+        return items, scores, counts
+
     # -- the items whose rating tells most about a user (include/mmsbm_hip.h: mmsbm_hip_inform_*) ---------
     def inform_begin(self):
         """Open an inform session: the information gain of a rating, averaged over the slots added to it."""

@@ -80,6 +80,11 @@ void similar_pairs(mmsbm_hip_ctx *c, int64_t n_pairs, const int32_t *a, const in
 void recommend_diverse(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, const int32_t *cand, int n_cand,
                        const int64_t *excl_offsets, const int32_t *excl_items, int n, int pool, double trade_off,
                        int32_t *items, double *scores, double *distances, int32_t *counts);
+// ... and the group queries of the recommend session (group.hpp), arguments checked: group g's members are
+// members[offsets[g] .. offsets[g + 1]), distinct; mode: MMSBM_HIP_GROUP_*; cand as in recommend_query_within
+void recommend_query_groups(mmsbm_hip_ctx *c, int64_t n_groups, const int64_t *offsets, const int32_t *members, int mode,
+                            double bar, const int32_t *cand, int n_cand, int n, int32_t *items, double *scores,
+                            int32_t *counts);
 // ... and the overlap of the restarts' groups (overlap.hpp): the session of mmsbm_hip_overlap_*, arguments checked
 void overlap_begin(mmsbm_hip_ctx *c, int side);
 void overlap_add(mmsbm_hip_ctx *c);  // the selected slot (the caller holds a OneSlot)

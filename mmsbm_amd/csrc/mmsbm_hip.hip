@@ -818,7 +818,7 @@ struct Option {
   void (*set)(mmsbm_hip_ctx *, double);
 };
 using Ctx = mmsbm_hip_ctx;
-// "audience_rows" / "audience_entries" / "explain_rows" / "diverse_rows": 0 .. 2^31 - 1, whole
+// "audience_rows" / "audience_entries" / "explain_rows" / "diverse_rows" / "group_run_blocks": 0 .. 2^31 - 1, whole
 void set_audience(int64_t &field, const char *name, double v) {
   if (v < 0 || v > 2147483647.0 || v != std::floor(v)) throw std::invalid_argument(std::string(name) + ": 0 .. 2^31 - 1");
   field = static_cast<int64_t>(v);
@@ -859,6 +859,7 @@ const Option kOptions[] = {
     {"explain_ms", [](const Ctx *c) -> double { return c->last_ms[T_EXPLAIN]; }, nullptr},
     {"diverse_ms", [](const Ctx *c) -> double { return c->last_ms[T_DIVERSE]; }, nullptr},
     {"inform_ms", [](const Ctx *c) -> double { return c->last_ms[T_INFORM]; }, nullptr},
+    {"group_ms", [](const Ctx *c) -> double { return c->last_ms[T_GROUP]; }, nullptr},
     // workgroups of gtop_fused_kernel (top_pairs.hpp); 0: the library's choice
     {"top_pairs_groups", [](const Ctx *c) -> double { return c->top_groups; },
      [](Ctx *c, double v) {
@@ -877,6 +878,10 @@ const Option kOptions[] = {
     // recommend_diverse (diverse.hpp): request rows per call; 0: the library's choice.  It does not change the answer
     {"diverse_rows", [](const Ctx *c) -> double { return static_cast<double>(c->div_rows); },
      [](Ctx *c, double v) { set_audience(c->div_rows, "diverse_rows", v); }},
+    // recommend_query_groups (group.hpp): blocks of 8 member rows per run of groups, rounded up to whole steps of 16; a
+    // longer group is cut into fragments of that length.  0: the library's choice.  It does not change the answer
+    {"group_run_blocks", [](const Ctx *c) -> double { return static_cast<double>(c->grp_run); },
+     [](Ctx *c, double v) { set_audience(c->grp_run, "group_run_blocks", v); }},
     // the form FAMILY of an iteration at the current slot count: 2 = the two launches of fused_small.hpp, 4 = the separate
     // stages, with or without "pass_dense" -- the launches a committed iteration really takes are launches - pass_dense
     {"launches", [](const Ctx *c) -> double { return use_fused(c) ? 2 : 4; }, nullptr},
@@ -1851,6 +1856,36 @@ int mmsbm_hip_recommend_diverse(mmsbm_hip_ctx *ctx, int64_t n_users, const int32
               "excluded item");
     recommend_diverse(ctx, n_users, users, cand_items, n_cand, n_users > 0 ? excl_offsets : nullptr, excl_items, n, pool,
                       trade_off, items, scores, distances, counts);
+  });
+}
+
+int mmsbm_hip_recommend_query_groups(mmsbm_hip_ctx *ctx, int64_t n_groups, const int64_t *offsets,
+                                     const int32_t *members, int mode, double bar, int32_t n_cand,
+                                     const int32_t *cand_items, int32_t n, int32_t *items, double *scores,
+                                     int32_t *counts) {
+  return guarded([&] {
+    const RecSession &rc = require_open(ctx, &mmsbm_hip_ctx::rc, "recommend", "recommend_query_groups");
+    if (n_groups < 0) throw std::invalid_argument("negative n_groups");
+    if (mode != MMSBM_HIP_GROUP_MIN && mode != MMSBM_HIP_GROUP_MAX && mode != MMSBM_HIP_GROUP_COUNT &&
+        mode != MMSBM_HIP_GROUP_MEAN)
+      throw std::invalid_argument("recommend_query_groups: unknown mode " + std::to_string(mode));
+    if (mode == MMSBM_HIP_GROUP_COUNT && !std::isfinite(bar))
+      throw std::invalid_argument("recommend_query_groups: bar must be finite");
+    require_n(n, "recommend_query_groups", "items");
+    if (n_groups > 0 && (!offsets || !items)) throw std::invalid_argument("null argument");
+    check_csr(offsets, members, n_groups, ctx->ext_users, "recommend_query_groups", "offsets", "group", "members",
+              "member");
+    // distinct within a group: last[u] = the last group that named user u
+    std::vector<int64_t> last(static_cast<size_t>(ctx->ext_users), -1);
+    for (int64_t g = 0; g < n_groups; ++g)
+      for (int64_t e = offsets[g]; e < offsets[g + 1]; ++e) {
+        if (last[static_cast<size_t>(members[e])] == g)
+          throw std::invalid_argument("recommend_query_groups: member repeated in group " + std::to_string(g) +
+                                      " at entry " + std::to_string(e));
+        last[static_cast<size_t>(members[e])] = g;
+      }
+    require_subset(cand_items, n_cand, rc.items, "recommend_query_groups");
+    recommend_query_groups(ctx, n_groups, offsets, members, mode, bar, cand_items, n_cand, n, items, scores, counts);
   });
 }
 

@@ -13,8 +13,8 @@
 //   tu_layout.hip  the layout's sorts on the device (rocPRIM)
 //   tu_recommend.hip  top-N recommendation (recommend.hpp), nearest items / users (similar.hpp), the m best pairs (top_pairs.hpp),
 //                     item-side queries (audience.hpp), queries within a part of the catalogue (catalogue.hpp),
-//                     the overlap of the restarts' groups (overlap.hpp), the diversified top-N (diverse.hpp) and the
-//                     most informative items of a user (inform.hpp)
+//                     the overlap of the restarts' groups (overlap.hpp), the diversified top-N (diverse.hpp), the
+//                     most informative items of a user (inform.hpp) and group queries (group.hpp)
 //   tu_fold_in.hip    fold new users into a fitted model (fold_in.hpp)
 //   tu_heldout.hip    held-out log-likelihood of every restart slot (heldout.hpp)
 //   tu_explain.hip    which of a user's training rows carry a recommendation (explain.hpp)

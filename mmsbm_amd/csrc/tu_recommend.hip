@@ -10,7 +10,8 @@
 // one query that reads the recommend and the similarity session at once: the pool through the same batches and
 // selection, kept on the device, then a greedy kernel of its own; and the most informative items of a user
 // (inform.hpp): a session of its own whose prologue borrows the similarity session's two kernels and whose queries go
-// through the same batches, exclusions and selection behind a score kernel of their own
+// through the same batches, exclusions and selection behind a score kernel of their own; and the group queries of the
+// recommend session (group.hpp): the members' score tiles reduced per group in registers and LDS, then the same selection
 #include "prelude.hpp"
 #include "recommend.hpp"
 #include "similar.hpp"
@@ -20,6 +21,7 @@
 #include "catalogue.hpp"
 #include "diverse.hpp"
 #include "inform.hpp"
+#include "group.hpp"
 
 #include <climits>
 
@@ -338,6 +340,35 @@ void rec_run(mmsbm_hip_ctx *c, const double *x, size_t xs, int64_t n_users, cons
             T_RECOMMEND, items, scores, counts);
 }
 
+// The compact item table of a candidate subset (catalogue.hpp): the candidates on the device, every catalogue item's
+// column and the candidates' rows of the session's item table, and the device time of the two kernels that make them
+struct CatTable {
+  DevBuf<int32_t> cand, col;  // [C]; [items of the catalogue]
+  DevBuf<double> y;           // [slot][C][rank]
+  float ms = 0.f;
+};
+
+// cand[0 .. C) (host; ascending, distinct ids of the session's catalogue) -> t (the memory was found free by the caller)
+void cat_table(mmsbm_hip_ctx *c, const int32_t *cand, int C, CatTable &t) {
+  const RecSession &rc = *c->rc;
+  const int NI = rc.items, rank = rc.rank, S = rc.slots;
+  const size_t ycs = static_cast<size_t>(C) * rank;
+  hipStream_t st = c->stream;
+  t.cand.alloc(static_cast<size_t>(C));
+  t.col.alloc(static_cast<size_t>(NI));
+  t.y.alloc(S * ycs);
+  HIP_CHECK(hipMemcpyAsync(t.cand.ptr, cand, sizeof(int32_t) * C, hipMemcpyHostToDevice, st));
+  EventPair ev;
+  ev.start(st);
+  LAUNCH(cat_gather_kernel, static_cast<unsigned>((S * ycs + kBlock - 1) / kBlock), kBlock, 0, st, rc.y.ptr,
+         static_cast<size_t>(NI) * rank, t.cand.ptr, C, rank, S, t.y.ptr);
+  LAUNCH(cat_cols_kernel, static_cast<unsigned>((NI + kBlock - 1) / kBlock), kBlock, 0, st, t.cand.ptr, C, NI, t.col.ptr);
+  HIP_CHECK(hipGetLastError());
+  ev.stop(st);
+  HIP_CHECK(hipStreamSynchronize(st));
+  t.ms = ev.ms();
+}
+
 // The device side of rec_run within the candidates cand[0 .. n_cand) (host; ascending, distinct ids of the session's
 // catalogue; null: the whole catalogue), and with the query's own excluded items: row b of the request also leaves out
 // xit[xoff[b] .. xoff[b + 1]) (host, any order, repeats allowed; null: none).  catalogue.hpp.  Without either: rec_run's
@@ -358,8 +389,8 @@ void rec_within_device(mmsbm_hip_ctx *c, const double *x, size_t xs, int64_t n_u
     require_free_mem((cand ? S * ycs * sizeof(double) + (static_cast<size_t>(C) + NI) * 4 : 0) +
                          (static_cast<size_t>(n_users) + 1 + n_x) * 4,
                      "recommend: the candidates' rows and the query's excluded items");
-  DevBuf<int32_t> dxo, dxi, dcand, dcol;
-  DevBuf<double> yc;
+  DevBuf<int32_t> dxo, dxi;
+  CatTable ct;
   std::vector<int32_t> hxo;
   if (xoff) {
     hxo.assign(xoff, xoff + n_users + 1);
@@ -367,40 +398,28 @@ void rec_within_device(mmsbm_hip_ctx *c, const double *x, size_t xs, int64_t n_u
     dxi.alloc(static_cast<size_t>(n_x));
     if (n_x > 0) HIP_CHECK(hipMemcpyAsync(dxi.ptr, xit, sizeof(int32_t) * n_x, hipMemcpyHostToDevice, st));
   }
-  float prep_ms = 0.f;  // device time of the compact table and the columns (added to "recommend_ms")
-  if (cand) {
-    dcand.alloc(static_cast<size_t>(C));
-    dcol.alloc(static_cast<size_t>(NI));
-    yc.alloc(S * ycs);
-    HIP_CHECK(hipMemcpyAsync(dcand.ptr, cand, sizeof(int32_t) * C, hipMemcpyHostToDevice, st));
-    EventPair ev;
-    ev.start(st);
-    LAUNCH(cat_gather_kernel, static_cast<unsigned>((S * ycs + kBlock - 1) / kBlock), kBlock, 0, st, rc.y.ptr,
-           static_cast<size_t>(NI) * rank, dcand.ptr, C, rank, S, yc.ptr);
-    LAUNCH(cat_cols_kernel, static_cast<unsigned>((NI + kBlock - 1) / kBlock), kBlock, 0, st, dcand.ptr, C, NI, dcol.ptr);
-    HIP_CHECK(hipGetLastError());
-    ev.stop(st);
-    HIP_CHECK(hipStreamSynchronize(st));
-    prep_ms = ev.ms();
-  }
+  if (cand) cat_table(c, cand, C, ct);
+  const float prep_ms = ct.ms;  // device time of the compact table and the columns (added to "recommend_ms")
+  const int32_t *dcand_ptr = ct.cand.ptr, *dcol_ptr = ct.col.ptr;
+  const double *yc_ptr = ct.y.ptr;
   int64_t done = 0;  // rows of the request the earlier batches held (the batches follow each other)
   top_n_device(c, C, n_users, users, n,
                cand || xoff ? "recommend: a batch of users within the candidates" : "recommend: a batch of users", extra,
                [&](const int32_t *ub, int nb, double *sc) {
                  if (cand) {
                    const dim3 g(static_cast<unsigned>((C + kRecTile - 1) / kRecTile), static_cast<unsigned>((nb + kRecTile - 1) / kRecTile));
-                   LAUNCH(rec_score_kernel, g, kBlock, 0, st, x, xs, yc.ptr, ycs, ub, nb, C, rank, S, sc, static_cast<size_t>(C));
+                   LAUNCH(rec_score_kernel, g, kBlock, 0, st, x, xs, yc_ptr, ycs, ub, nb, C, rank, S, sc, static_cast<size_t>(C));
                    if (seen_off)
-                     LAUNCH(cat_exclude_kernel, nb, kBlock, 0, st, ub, 0, seen_off, seen, dcol.ptr, sc, static_cast<size_t>(C));
+                     LAUNCH(cat_exclude_kernel, nb, kBlock, 0, st, ub, 0, seen_off, seen, dcol_ptr, sc, static_cast<size_t>(C));
                  } else {
                    rec_score_batch(c, x, xs, ub, nb, seen_off, seen, sc);
                  }
                  if (xoff)
                    LAUNCH(cat_exclude_kernel, nb, kBlock, 0, st, static_cast<const int32_t *>(nullptr), static_cast<int>(done),
-                          dxo.ptr, dxi.ptr, cand ? dcol.ptr : static_cast<const int32_t *>(nullptr), sc, static_cast<size_t>(C));
+                          dxo.ptr, dxi.ptr, cand ? dcol_ptr : static_cast<const int32_t *>(nullptr), sc, static_cast<size_t>(C));
                  done += nb;
                },
-               [&](const TopNDev &dev, EventPair &ev) { then(dev, ev, cand ? dcand.ptr : nullptr, prep_ms); });
+               [&](const TopNDev &dev, EventPair &ev) { then(dev, ev, cand ? dcand_ptr : nullptr, prep_ms); });
 }
 
 // rec_within_device with the result copied to the host and the columns mapped to item ids there.  Without candidates
@@ -846,6 +865,185 @@ void recommend_audience(mmsbm_hip_ctx *c, int64_t n_items, const int32_t *items,
     }
   }
   c->last_ms[T_AUDIENCE] = ms;
+}
+
+// ---- group queries (group.hpp) ------------------------------------------------------------------------------------------
+void recommend_query_groups(mmsbm_hip_ctx *c, int64_t n_groups, const int64_t *offsets, const int32_t *members, int mode,
+                            double bar, const int32_t *cand, int n_cand, int n, int32_t *items, double *scores,
+                            int32_t *counts) {
+  use_device(c);
+  const RecSession &rc = *c->rc;
+  top_n_blank(n_groups, n, items, scores, counts);
+  c->last_ms[T_GROUP] = 0.f;
+  const int NI = rc.items, rank = rc.rank, S = rc.slots;
+  const int C = cand ? n_cand : NI;
+  // the rows of the device request: the groups that have members (an empty group has no candidate)
+  std::vector<int32_t> ids;
+  std::vector<int64_t> at;  // their places in the caller's request
+  for (int64_t g = 0; g < n_groups; ++g)
+    if (offsets[g + 1] > offsets[g]) {
+      ids.push_back(static_cast<int32_t>(at.size()));
+      at.push_back(g);
+    }
+  const int64_t G = static_cast<int64_t>(at.size());
+  if (G == 0 || C == 0) return;  // (no row or no column to score: every row is empty)
+  // the members in blocks of kGrpBlock rows; a group's last block is filled up with its first member's id (a row that
+  // can be loaded; the kernels never look at it: blk_info holds the number of members)
+  const size_t n_blocks = [&] {
+    size_t b = 0;
+    for (int64_t r = 0; r < G; ++r) b += static_cast<size_t>((offsets[at[r] + 1] - offsets[at[r]] + kGrpBlock - 1) / kGrpBlock);
+    return b;
+  }();
+  if (n_blocks * kGrpBlock > static_cast<size_t>(INT32_MAX))
+    throw ApiError(MMSBM_E_TOOLARGE, "recommend_query_groups: " + std::to_string(n_blocks) + " blocks of member rows in one query");
+  std::vector<int32_t> rows, info, grp, gblk(static_cast<size_t>(G) + 1), gsize(static_cast<size_t>(G));
+  rows.reserve(n_blocks * kGrpBlock);
+  info.reserve(n_blocks);
+  grp.reserve(n_blocks);
+  for (int64_t r = 0; r < G; ++r) {
+    const int32_t *m = members + offsets[at[r]];
+    const int64_t sz = offsets[at[r] + 1] - offsets[at[r]];
+    gblk[static_cast<size_t>(r)] = static_cast<int32_t>(info.size());
+    gsize[static_cast<size_t>(r)] = static_cast<int32_t>(sz);
+    for (int64_t k = 0; k < sz; k += kGrpBlock) {
+      const int in = static_cast<int>(std::min<int64_t>(kGrpBlock, sz - k));
+      for (int a = 0; a < kGrpBlock; ++a) rows.push_back(a < in ? m[k + a] : m[0]);
+      info.push_back(in | (k + kGrpBlock >= sz ? kGrpLast : 0));
+      grp.push_back(static_cast<int32_t>(r));
+    }
+  }
+  gblk[static_cast<size_t>(G)] = static_cast<int32_t>(info.size());
+  // the batches top_n_device will form, and per batch its runs: `want` blocks each -- whole steps of the walk, about 8
+  // workgroups per CU over the item tiles (option "group_run_blocks") -- made of whole groups; a group longer than
+  // that is cut into fragments of `want` blocks, one run each, whose values meet in grp_combine_kernel
+  const bool tiles = mode != MMSBM_HIP_GROUP_MEAN;
+  const int64_t bu = rec_batch_users(C, G);
+  const int64_t item_tiles = (static_cast<int64_t>(C) + kRecTile - 1) / kRecTile;
+  std::vector<int32_t> out = grp;           // per block: the row the tile kernel writes (a group, or a fragment)
+  std::vector<int32_t> run_off, batch_run;  // the runs' first blocks; the batches' first runs
+  std::vector<int32_t> cut_grp, cut_off, batch_cut;  // the cut groups, their first fragments; the batches' first cut groups
+  int32_t n_frag = 0, most_frag = 0;        // fragments so far; of the batch with the most
+  for (int64_t b0 = 0; tiles && b0 < G; b0 += bu) {
+    const int64_t b1 = std::min(G, b0 + bu);
+    const int64_t blocks = gblk[static_cast<size_t>(b1)] - gblk[static_cast<size_t>(b0)];
+    const int64_t most = std::max<int64_t>(1, 8LL * c->n_cus / item_tiles);
+    const int64_t ask = c->grp_run > 0 ? c->grp_run : (blocks + most - 1) / most;
+    const int32_t want = static_cast<int32_t>(std::max<int64_t>(kGrpStep, (std::min<int64_t>(ask, blocks) + kGrpStep - 1) / kGrpStep * kGrpStep));
+    batch_run.push_back(static_cast<int32_t>(run_off.size()));
+    batch_cut.push_back(static_cast<int32_t>(cut_grp.size()));
+    const int32_t frag0 = n_frag;
+    int32_t first = gblk[static_cast<size_t>(b0)];
+    run_off.push_back(first);
+    auto begin_run = [&](int32_t blk) {  // (nothing where a run begins there already)
+      if (blk > first) {
+        first = blk;
+        run_off.push_back(blk);
+      }
+    };
+    for (int64_t r = b0; r < b1; ++r) {
+      const int32_t g_lo = gblk[static_cast<size_t>(r)], g_hi = gblk[static_cast<size_t>(r) + 1];
+      if (g_hi - g_lo > want) {
+        cut_grp.push_back(static_cast<int32_t>(r));
+        cut_off.push_back(n_frag);
+        for (int32_t lo = g_lo; lo < g_hi; lo += want, ++n_frag) {
+          const int32_t hi = std::min(g_hi, lo + want);
+          begin_run(lo);
+          for (int32_t b = lo; b < hi; ++b) {
+            info[static_cast<size_t>(b)] |= kGrpPart;
+            out[static_cast<size_t>(b)] = n_frag;
+          }
+          info[static_cast<size_t>(hi) - 1] |= kGrpLast;
+        }
+        if (r + 1 < b1) begin_run(g_hi);
+      } else if (g_hi - first >= want && r + 1 < b1) {
+        begin_run(g_hi);
+      }
+    }
+    most_frag = std::max(most_frag, n_frag - frag0);
+  }
+  if (tiles) {
+    batch_run.push_back(static_cast<int32_t>(run_off.size()));
+    run_off.push_back(gblk[static_cast<size_t>(G)]);  // (one past the last run; a batch's last run ends where the next batch's first begins)
+    batch_cut.push_back(static_cast<int32_t>(cut_grp.size()));
+    cut_off.push_back(n_frag);
+  }
+  const size_t ycs = static_cast<size_t>(C) * rank, bs = static_cast<size_t>(G) * rank;
+  require_free_mem((cand ? S * ycs * sizeof(double) + (static_cast<size_t>(C) + NI) * 4 : 0) +
+                       (rows.size() + 3 * info.size() + run_off.size() + 2 * cut_off.size() + 2 * static_cast<size_t>(G) + 1) * 4 +
+                       (tiles ? static_cast<size_t>(most_frag) * C : S * bs) * sizeof(double),
+                   "recommend_query_groups: the member rows, the groups' lists and the candidates' rows");
+  hipStream_t st = c->stream;
+  DevBuf<int32_t> d_rows, d_info, d_grp, d_out, d_run, d_cut_grp, d_cut_off, d_gblk, d_size;
+  DevBuf<double> xbar, part;
+  CatTable ct;
+  d_rows.upload(rows, st);
+  d_info.upload(info, st);
+  d_grp.upload(grp, st);
+  if (tiles) {
+    d_out.upload(out, st);
+    d_run.upload(run_off, st);
+    if (most_frag > 0) {
+      d_cut_grp.upload(cut_grp, st);
+      d_cut_off.upload(cut_off, st);
+      part.alloc(static_cast<size_t>(most_frag) * C);
+    }
+  } else {
+    d_gblk.upload(gblk, st);
+    d_size.upload(gsize, st);
+    xbar.alloc(S * bs);
+  }
+  if (cand) cat_table(c, cand, C, ct);
+  const double *y = cand ? ct.y.ptr : rc.y.ptr;
+  const size_t ys = cand ? ycs : static_cast<size_t>(NI) * rank, xs = static_cast<size_t>(c->ext_users) * rank;
+  const int32_t *seen_off = rc.excl ? rc.seen_off.ptr : nullptr, *col_of = cand ? ct.col.ptr : nullptr;
+  std::vector<int32_t> ti(static_cast<size_t>(G) * n), tc(static_cast<size_t>(G));
+  std::vector<double> ts(static_cast<size_t>(G) * n);
+  int64_t done = 0;  // groups the earlier batches held (the batches follow each other)
+  top_n_run(c, C, G, ids.data(), n, "recommend_query_groups: a batch of groups",
+            [&](const int32_t *ub, int nb, double *sc) {
+              const int g0 = static_cast<int>(done);
+              const unsigned it = static_cast<unsigned>(item_tiles);
+              if (tiles) {
+                const size_t k = static_cast<size_t>(done / bu);
+                const dim3 g(it, static_cast<unsigned>(batch_run[k + 1] - batch_run[k]));
+                const int32_t *ro = d_run.ptr + batch_run[k];
+                const int n_cut = batch_cut[k + 1] - batch_cut[k], p0 = cut_off[static_cast<size_t>(batch_cut[k])];
+                auto tile = [&](auto kernel) {
+                  LAUNCH(kernel, g, kBlock, 0, st, rc.x.ptr, xs, y, ys, d_rows.ptr, d_info.ptr, d_out.ptr, ro, g0, p0, C, rank,
+                         S, bar, sc, part.ptr, static_cast<size_t>(C));
+                };
+                if (mode == MMSBM_HIP_GROUP_MIN) tile(grp_tile_kernel<kGrpMin>);
+                else if (mode == MMSBM_HIP_GROUP_MAX) tile(grp_tile_kernel<kGrpMax>);
+                else tile(grp_tile_kernel<kGrpCount>);
+                if (n_cut > 0)
+                  LAUNCH(grp_combine_kernel, dim3(static_cast<unsigned>((C + kBlock - 1) / kBlock), static_cast<unsigned>(n_cut)),
+                         kBlock, 0, st, part.ptr, d_cut_grp.ptr + batch_cut[k], d_cut_off.ptr + batch_cut[k], g0, p0, C, mode, S,
+                         sc, static_cast<size_t>(C));
+              } else {
+                const size_t e = static_cast<size_t>(nb) * rank * S;
+                LAUNCH(grp_mean_kernel, static_cast<unsigned>((e + kBlock - 1) / kBlock), kBlock, 0, st, rc.x.ptr, xs, rank,
+                       S, d_rows.ptr, d_gblk.ptr, d_size.ptr, g0, nb, xbar.ptr, bs);
+                LAUNCH(rec_score_kernel, dim3(it, static_cast<unsigned>((nb + kRecTile - 1) / kRecTile)), kBlock, 0, st,
+                       xbar.ptr, bs, y, ys, ub, nb, C, rank, S, sc, static_cast<size_t>(C));
+              }
+              if (seen_off) {
+                const int blk0 = gblk[static_cast<size_t>(g0)];
+                LAUNCH(grp_exclude_kernel, static_cast<unsigned>(gblk[static_cast<size_t>(g0) + nb] - blk0), kBlock, 0, st,
+                       d_rows.ptr, d_info.ptr, d_grp.ptr, blk0, g0, seen_off, rc.seen.ptr, col_of, sc, static_cast<size_t>(C));
+              }
+              done += nb;
+            },
+            T_GROUP, ti.data(), ts.data(), tc.data());
+  c->last_ms[T_GROUP] += ct.ms;
+  for (int64_t r = 0; r < G; ++r) {  // the rows to their places in the request, columns -> item ids
+    const size_t o = static_cast<size_t>(at[r]) * n, t = static_cast<size_t>(r) * n;
+    const int cnt = tc[static_cast<size_t>(r)];
+    if (counts) counts[at[r]] = cnt;
+    for (int k = 0; k < cnt; ++k) {
+      items[o + k] = cand ? cand[ti[t + k]] : ti[t + k];
+      if (scores) scores[o + k] = ts[t + k];
+    }
+  }
 }
 
 // ---- nearest items / users (similar.hpp) ------------------------------------------------------------------------------

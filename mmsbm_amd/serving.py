@@ -922,6 +922,77 @@ class Serving:
                                      self._side("users"), columns=("items", "users", "score"))
 
 
+    # ------------------------------------------------------------------ recommendation for groups (not in the reference)
+    _GROUP_COLUMNS = ("group", "items", "score")
+    _GROUP_AGGREGATES = {"least_misery": "min", "most_pleasure": "max", "approval": "count", "mean": "mean"}
+
+    def _group_lists(self, groups):
+        """(labels (G,) object, (offsets (G + 1,) int64, members int32)) of a ``groups`` argument: a dict {label:
+        users}, a sequence of user iterables (labels 0, 1, ...) or a DataFrame whose first two columns are group and
+        user (groups in order of first appearance).  A user that is not in the training data: KeyError.  A user
+        repeated within a group counts once; the first appearance fixes the member order."""
+        if hasattr(groups, "iloc") and hasattr(groups, "columns"):
+            if groups.shape[1] < 2:
+                raise ValueError("groups needs two columns: group and user")
+            named = {}
+            for g, u in zip(groups.iloc[:, 0].tolist(), groups.iloc[:, 1].tolist()):
+                named.setdefault(g, []).append(u)
+        elif isinstance(groups, dict):
+            named = {g: list(us) for g, us in groups.items()}
+        else:
+            named = dict(enumerate(list(us) for us in groups))
+        labels = np.empty(len(named), dtype=object)
+        labels[:] = list(named)
+        sizes = [len(us) for us in named.values()]
+        flat = [u for us in named.values() for u in us]
+        ids = self._side("users").request(flat)[0] if flat else np.zeros(0, dtype=np.int32)
+        rows = pd.DataFrame({"g": np.repeat(np.arange(len(named)), sizes), "u": ids}).drop_duplicates()
+        return labels, (_offsets(np.bincount(rows["g"].to_numpy(), minlength=len(named))),
+                        rows["u"].to_numpy().astype(np.int32))
+
+    def recommend_group(self, groups, n=10, aggregate="least_misery", bar=None, exclude_seen=True, weights=None,
+                        candidates=None):
+        """The ``n`` best items for each GROUP of users -- a household choosing a film, a table of friends choosing a
+        restaurant, a campaign that picks one product for a segment -- aggregated on the device without a members x
+        items score matrix.  With score(m, i) ``recommend``'s score of member m for item i (the same numbers, bit for
+        bit), the group's value of an item is, by ``aggregate``:
+
+        ``"least_misery"``   the LOWEST score any member gives it;
+        ``"most_pleasure"``  the HIGHEST;
+        ``"approval"``       how many members score it at or above ``bar`` (required for this aggregate, finite, compared
+                             with the final score; refused for the others);
+        ``"mean"``           the score of the group's mean membership row -- the members' mean score up to rounding.
+
+        ``groups``: a dict {label: iterable of users}, a sequence of iterables (labels 0, 1, ...) or a DataFrame whose
+        first two columns are group and user.  A user that is not in the training data: KeyError; a user repeated
+        within a group counts once.  Candidates are all training items (``candidates`` as in ``recommend``), without
+        every item ANY member has in the training data when ``exclude_seen``.  Order: value descending, equal values
+        by ascending encoded item id.
+
+        Returns a DataFrame with columns ``group``, ``items``, ``score``, ``rank`` (1 = best), groups in request order.
+        The per-member scores behind a line are ``rerank`` of the (member, item) pairs, with ``exclude_seen=False``
+        for the members that have the item.  The model's stored predictions and ``score()`` are left as they are."""
+        self._check_whole_model()
+        n, w = self._recommend_args(n, weights)
+        if aggregate not in self._GROUP_AGGREGATES:
+            raise ValueError(f"aggregate must be one of {list(self._GROUP_AGGREGATES)}, got {aggregate!r}")
+        if aggregate == "approval":
+            if bar is None:
+                raise ValueError('aggregate="approval" needs a bar')
+            bar = check_finite(bar, "bar")
+        elif bar is not None:
+            raise ValueError(f'bar belongs to aggregate="approval", not to {aggregate!r}')
+        mode = self._GROUP_AGGREGATES[aggregate]
+        labels, lists = self._group_lists(groups)
+        items = self._side("items")
+        cand = self._candidate_ids(candidates)
+        if cand is not None and len(cand) == 0:
+            return self._top_n_frame(None, n, labels[:0], items, self._GROUP_COLUMNS)
+        with self._session_of_restarts("recommend", w, exclude_seen) as ctx:
+            return self._top_n_frame(
+                lambda b, e: ctx.recommend_query_groups(*group_slice(lists, b, e), n, mode, bar or 0.0, cand),
+                n, labels, items, self._GROUP_COLUMNS)
+
     # ------------------------------------------------------------------ which items to ask about (not in the reference)
     _GAIN_COLUMNS = ("users", "items", "gain")
 
