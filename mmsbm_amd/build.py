@@ -1,6 +1,6 @@
 """Compile the HIP library in-tree for gfx950 (hipcc cross-compiles without a GPU).
 
-The library is eight translation units (csrc/prelude.hpp lists them) compiled SIDE BY SIDE -- one hipcc per unit, as
+The library is twelve translation units (csrc/prelude.hpp lists them) compiled SIDE BY SIDE -- one hipcc per unit, as
 many at a time as the machine has cores -- and linked into one shared object: about 18 s on eight cores, where the
 single unit of earlier rounds took a minute.  csrc/unity.hip is all of them as one unit, for the diagnostic builds
 (`build_diagnostic`)."""

@@ -102,6 +102,11 @@ struct PinBuf {
   }
 };
 
+// The items a query leaves out per row of the table it scores (device; off indexed by the row's id): null off -- none
+struct SeenLists {
+  const int32_t *off = nullptr, *items = nullptr;
+};
+
 // The recommend session (mmsbm_hip_recommend_begin .. end; recommend.hpp): the slots' folded factors, external sides.
 // Created by recommend_begin, dropped whole by recommend_begin and recommend_end.
 struct RecSession {
@@ -114,7 +119,10 @@ struct RecSession {
   int slots = 0;                        // slots added
   int items = 0;                        // the session's catalogue: I, or I + n_new after recommend_add_items
   int rank = 0;
+  int users = 0;                        // U
   bool excl = false;                    // seen_* in use: exclude_train, or seen lists of recommend_add_items
+  SeenLists seen_lists() const { return {excl ? seen_off.ptr : nullptr, seen.ptr}; }
+  size_t x_stride() const { return static_cast<size_t>(users) * rank; }  // doubles between two slots of x
 };
 
 // The similarity session (mmsbm_hip_similar_begin .. end; similar.hpp): the added slots' profiles and group masses of

@@ -42,11 +42,7 @@
 namespace {
 
 constexpr int kGrpMin = MMSBM_HIP_GROUP_MIN, kGrpMax = MMSBM_HIP_GROUP_MAX, kGrpCount = MMSBM_HIP_GROUP_COUNT;
-constexpr int kGrpBlock = kRecTm;                     // member rows per block: the rows one thread of the tile holds
-constexpr int kGrpStep = kRecTile / kGrpBlock;        // blocks per step of the walk (16)
-constexpr int kGrpLast = 16;                          // blk_info: bit set on the last block of a group (of a fragment
-                                                      // of a cut group); low bits: the block's members
-constexpr int kGrpPart = 32;                          // blk_info: the block belongs to a fragment of a cut group
+// (kGrpBlock, kGrpStep, kGrpLast, kGrpPart: serve_plan.hpp -- plan_groups writes what the kernels here read)
 static_assert(kGrpStep <= kRecKc && kRecTile <= kRecLdsRow, "the blocks' partial values fit the x staging tile");
 
 template <int MODE>

@@ -40,6 +40,9 @@ int score_stats_count();
 // tu_recommend.hip -- top-N recommendation (recommend.hpp): the session of mmsbm_hip_recommend_*, arguments checked
 // MMSBM_E_TOOLARGE "<what> needs ... MB of device memory" unless `bytes` (plus 64 MB) are free (fold-in too)
 void require_free_mem(size_t bytes, const std::string &what);
+// the training rows' external ids in the order they were given, with their ratings on request (null: not wanted)
+void train_id_columns(mmsbm_hip_ctx *c, std::vector<int32_t> &user, std::vector<int32_t> &item,
+                      std::vector<int32_t> *rating);
 void recommend_begin(mmsbm_hip_ctx *c, const double *weights, int exclude_train);
 void recommend_add(mmsbm_hip_ctx *c);  // the selected slot (the caller holds a OneSlot)
 void recommend_query(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, int n, int32_t *items, double *scores,

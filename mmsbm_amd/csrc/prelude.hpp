@@ -11,10 +11,12 @@
 //                  in one launch (pass_dense.hpp)
 //   tu_once.hip    once-per-run kernels: likelihood, prod_dist / predict, omegas, the random start
 //   tu_layout.hip  the layout's sorts on the device (rocPRIM)
-//   tu_recommend.hip  top-N recommendation (recommend.hpp), nearest items / users (similar.hpp), the m best pairs (top_pairs.hpp),
-//                     item-side queries (audience.hpp), queries within a part of the catalogue (catalogue.hpp),
-//                     the overlap of the restarts' groups (overlap.hpp), the diversified top-N (diverse.hpp), the
-//                     most informative items of a user (inform.hpp) and group queries (group.hpp)
+//   tu_recommend.hip  the serving queries, planned by serve_plan.hpp, one header of kernels each:
+//                       recommend.hpp  top-N recommendation        similar.hpp    nearest items / users
+//                       top_pairs.hpp  the m best pairs            overlap.hpp    the overlap of the restarts' groups
+//                       audience.hpp   item-side queries           catalogue.hpp  queries within a part of the catalogue
+//                       diverse.hpp    the diversified top-N       inform.hpp     the most informative items of a user
+//                       group.hpp      group queries
 //   tu_fold_in.hip    fold new users into a fitted model (fold_in.hpp)
 //   tu_heldout.hip    held-out log-likelihood of every restart slot (heldout.hpp)
 //   tu_explain.hip    which of a user's training rows carry a recommendation (explain.hpp)
@@ -44,6 +46,7 @@
 #include "common.hpp"
 #include "shapes.hpp"
 #include "pair_plan.hpp"
+#include "serve_plan.hpp"
 #include "stamps.hpp"
 #include "rowtab.hpp"
 #include "context.hpp"

@@ -37,12 +37,9 @@
 namespace {
 
 constexpr int kRecMaxN = MMSBM_HIP_RECOMMEND_MAX_N;  // largest N a query may ask for (include/mmsbm_hip.h)
-constexpr int kRecTile = 128;       // users x items of one score workgroup
-constexpr int kRecTm = 8;           // outputs per thread along each side (16 x 16 threads)
+// (kRecTile, kRecTm, kRecWave, kRecPerLane: serve_plan.hpp -- the host's plans are made from them too)
 constexpr int kRecKc = 16;          // rank entries staged in LDS per step
 constexpr int kRecLdsRow = kRecTile + 2;  // (padded LDS row: fewer bank conflicts, 16-byte aligned rows)
-constexpr int kRecWave = 64;        // rec_select_kernel: one wave per workgroup
-constexpr int kRecPerLane = 4;      // elements a lane examines per round
 
 // W[k * L + l] = sum_r w[r] p[r][k, l] in external (k, l); p of one slot in the device layout [R][kp][lp], internal
 // (k, l) = external (k, l) or (l, k) when swapped: element (k, l) at p + r * rs + k * ks + l * ls.

@@ -1,0 +1,206 @@
+// serve_plan.hpp -- the launch plans of the serving queries (tu_recommend.hip) as plain values: the batches of a top-N
+// query and its item split, the selection's list, the blocks / runs / fragments of a group query, the COUNT batches and
+// WRITE runs of an audience query, the rows per call of a diversified query.  Host arithmetic on plain numbers only -- no
+// HIP type, no context -- so that the rules a kernel's block index depends on are checked on the CPU over every shape
+// (tests/native/serve_plan_check.cpp).  The shape constants the plans share with the kernels are defined here, once.
+#pragma once
+
+#include <algorithm>
+#include <cstddef>
+#include <cstdint>
+#include <utility>
+#include <vector>
+
+namespace mmsbm_hip_impl {
+
+constexpr int kRecTile = 128;     // users x items of one score workgroup (recommend.hpp)
+constexpr int kRecTm = 8;         // outputs per thread along each side (16 x 16 threads)
+constexpr int kRecWave = 64;      // rec_select_kernel: one wave per workgroup
+constexpr int kRecPerLane = 4;    // elements a lane examines per round
+constexpr int kGrpBlock = kRecTm;               // group.hpp: member rows per block, the rows one thread of the tile holds
+constexpr int kGrpStep = kRecTile / kGrpBlock;  // blocks per step of the walk (16)
+constexpr int kGrpLast = 16;      // blk_info: bit set on the last block of a group (of a fragment of a cut group); low
+                                  // bits: the block's members
+constexpr int kGrpPart = 32;      // blk_info: the block belongs to a fragment of a cut group
+
+constexpr size_t kRecBatchBytes = size_t(128) << 20;  // score buffer of one batch of users (stays in the 256 MB MALL)
+constexpr size_t kAudTableBytes = size_t(64) << 20;   // recommend_audience: the (row, user tile) counts of one batch
+constexpr size_t kFreeMargin = size_t(64) << 20;      // device memory a query leaves free (require_free_mem)
+constexpr int kRecMinPerPart = 1024;                  // items a selecting wave gets at least
+constexpr int kPosMinPerPart = 2048;                  // items a counting workgroup gets at least
+constexpr int64_t kAudEntries = int64_t(16) << 20;    // recommend_audience: the entries of one WRITE batch (12 bytes each)
+
+// ---- the batches of a top-N query and the selection ------------------------------------------------------------------
+// users per batch: a score buffer of ~128 MB, whole 128-user tiles where that allows
+inline int64_t rec_batch_users(int I, int64_t n_users) {
+  int64_t bu = std::max<int64_t>(1, static_cast<int64_t>(kRecBatchBytes / (static_cast<size_t>(I) * sizeof(double))));
+  bu = std::min<int64_t>(bu, 32768);
+  if (bu >= kRecTile) bu = bu / kRecTile * kRecTile;
+  return std::min(bu, n_users);
+}
+
+// (parts, per): the I items split into parts of at least min_per items each until about `target` (batch rows x
+// parts) are in flight; few users: one user over 100k items
+inline std::pair<int, int> item_parts(int I, int64_t bu, int64_t target, int min_per) {
+  int parts = 1;
+  if (bu < target) parts = static_cast<int>(std::min<int64_t>((target + bu - 1) / bu, (I + min_per - 1) / min_per));
+  parts = std::max(parts, 1);
+  const int per = (I + parts - 1) / parts;
+  return {I > 0 ? (I + per - 1) / per : 1, per};
+}
+
+// The sorted list of a selecting wave (rec_select_kernel, cat_rank_kernel): the next power of two >= n + one round of
+// the wave, a score and an id per place in LDS
+inline std::pair<int, size_t> select_list(int n) {  // (places, LDS bytes)
+  int cap = 1;
+  while (cap < n + kRecWave * kRecPerLane) cap <<= 1;
+  return {cap, static_cast<size_t>(cap) * (sizeof(double) + sizeof(int32_t))};
+}
+
+// ---- group queries (group.hpp) -----------------------------------------------------------------------------------------
+// What recommend_query_groups uploads and launches with.  The rows of the device request are the groups that have
+// members (an empty group has no candidate); their members stand in blocks of kGrpBlock rows, a group's last block
+// filled up with its first member's id (a row that can be loaded; the kernels never look at it: `info` holds the number
+// of members).  With `tiles` (every mode but the mean) each batch of `bu` rows is walked in runs of about `want` blocks
+// -- whole steps of the walk, about 8 workgroups per CU over the item tiles (option "group_run_blocks") -- made of whole
+// groups; a group longer than that is cut into fragments of `want` blocks, one run each, whose values meet in
+// grp_combine_kernel.
+struct GroupPlan {
+  std::vector<int64_t> at;    // per row: its place in the caller's request
+  std::vector<int32_t> ids;   // 0 .. G - 1: the rows as top_n_run's request
+  size_t n_blocks = 0;        // more than 2^31 - 1 member rows (too_large): nothing below is filled in
+  bool too_large() const { return n_blocks * kGrpBlock > static_cast<size_t>(INT32_MAX); }
+  std::vector<int32_t> rows, info, grp;  // [block][kGrpBlock] member ids; per block: members | kGrpLast | kGrpPart; its row
+  std::vector<int32_t> out;              // per block: the row the tile kernel writes (a group, or a fragment)
+  std::vector<int32_t> gblk, gsize;      // per row: its first block (G + 1 entries), its members
+  int64_t bu = 0, item_tiles = 0;        // rows per batch (what top_n_device will form); 128-column tiles of the C columns
+  std::vector<int32_t> want;             // per batch: blocks per run
+  std::vector<int32_t> run_off, batch_run;            // the runs' first blocks; the batches' first runs
+  std::vector<int32_t> cut_grp, cut_off, batch_cut;   // the cut groups, their first fragments; the batches' first cut groups
+  int32_t most_frag = 0;                 // fragments of the batch with the most
+  int64_t groups() const { return static_cast<int64_t>(at.size()); }
+};
+
+// force_bu > 0: that many rows per batch instead of rec_batch_users (the CPU check: batches without 128 MB shapes)
+inline GroupPlan plan_groups(const int64_t *offsets, const int32_t *members, int64_t n_groups, int C, int n_cus,
+                             int64_t run_blocks, bool tiles, int64_t force_bu = 0) {
+  GroupPlan p;
+  for (int64_t g = 0; g < n_groups; ++g)
+    if (offsets[g + 1] > offsets[g]) {
+      p.ids.push_back(static_cast<int32_t>(p.at.size()));
+      p.at.push_back(g);
+    }
+  const int64_t G = p.groups();
+  if (G == 0 || C == 0) return p;  // (no row or no column to score)
+  for (int64_t r = 0; r < G; ++r)
+    p.n_blocks += static_cast<size_t>((offsets[p.at[r] + 1] - offsets[p.at[r]] + kGrpBlock - 1) / kGrpBlock);
+  if (p.too_large()) return p;
+  p.gblk.resize(static_cast<size_t>(G) + 1);
+  p.gsize.resize(static_cast<size_t>(G));
+  p.rows.reserve(p.n_blocks * kGrpBlock);
+  for (int64_t r = 0; r < G; ++r) {
+    const int32_t *m = members + offsets[p.at[r]];
+    const int64_t sz = offsets[p.at[r] + 1] - offsets[p.at[r]];
+    p.gblk[static_cast<size_t>(r)] = static_cast<int32_t>(p.info.size());
+    p.gsize[static_cast<size_t>(r)] = static_cast<int32_t>(sz);
+    for (int64_t k = 0; k < sz; k += kGrpBlock) {
+      const int in = static_cast<int>(std::min<int64_t>(kGrpBlock, sz - k));
+      for (int a = 0; a < kGrpBlock; ++a) p.rows.push_back(a < in ? m[k + a] : m[0]);
+      p.info.push_back(in | (k + kGrpBlock >= sz ? kGrpLast : 0));
+      p.grp.push_back(static_cast<int32_t>(r));
+    }
+  }
+  p.gblk[static_cast<size_t>(G)] = static_cast<int32_t>(p.info.size());
+  p.out = p.grp;
+  p.bu = force_bu > 0 ? std::min(force_bu, G) : rec_batch_users(C, G);
+  p.item_tiles = (static_cast<int64_t>(C) + kRecTile - 1) / kRecTile;
+  if (!tiles) return p;
+  int32_t n_frag = 0;  // fragments so far
+  for (int64_t b0 = 0; b0 < G; b0 += p.bu) {
+    const int64_t b1 = std::min(G, b0 + p.bu);
+    const int64_t blocks = p.gblk[static_cast<size_t>(b1)] - p.gblk[static_cast<size_t>(b0)];
+    const int64_t most = std::max<int64_t>(1, 8LL * n_cus / p.item_tiles);
+    const int64_t ask = run_blocks > 0 ? run_blocks : (blocks + most - 1) / most;
+    const int32_t want = static_cast<int32_t>(
+        std::max<int64_t>(kGrpStep, (std::min<int64_t>(ask, blocks) + kGrpStep - 1) / kGrpStep * kGrpStep));
+    p.want.push_back(want);
+    p.batch_run.push_back(static_cast<int32_t>(p.run_off.size()));
+    p.batch_cut.push_back(static_cast<int32_t>(p.cut_grp.size()));
+    const int32_t frag0 = n_frag;
+    int32_t first = p.gblk[static_cast<size_t>(b0)];
+    p.run_off.push_back(first);
+    auto begin_run = [&](int32_t blk) {  // (nothing where a run begins there already)
+      if (blk > first) p.run_off.push_back(first = blk);
+    };
+    for (int64_t r = b0; r < b1; ++r) {
+      const int32_t g_lo = p.gblk[static_cast<size_t>(r)], g_hi = p.gblk[static_cast<size_t>(r) + 1];
+      if (g_hi - g_lo > want) {
+        p.cut_grp.push_back(static_cast<int32_t>(r));
+        p.cut_off.push_back(n_frag);
+        for (int32_t lo = g_lo; lo < g_hi; lo += want, ++n_frag) {
+          const int32_t hi = std::min(g_hi, lo + want);
+          begin_run(lo);
+          for (int32_t b = lo; b < hi; ++b) {
+            p.info[static_cast<size_t>(b)] |= kGrpPart;
+            p.out[static_cast<size_t>(b)] = n_frag;
+          }
+          p.info[static_cast<size_t>(hi) - 1] |= kGrpLast;
+        }
+        if (r + 1 < b1) begin_run(g_hi);
+      } else if (g_hi - first >= want && r + 1 < b1) {
+        begin_run(g_hi);
+      }
+    }
+    p.most_frag = std::max(p.most_frag, n_frag - frag0);
+  }
+  p.batch_run.push_back(static_cast<int32_t>(p.run_off.size()));
+  p.run_off.push_back(p.gblk[static_cast<size_t>(G)]);  // (one past the last run; a batch's last run ends where the next batch's first begins)
+  p.batch_cut.push_back(static_cast<int32_t>(p.cut_grp.size()));
+  p.cut_off.push_back(n_frag);
+  return p;
+}
+
+// ---- item-side queries (audience.hpp) ----------------------------------------------------------------------------------
+// items per COUNT batch of recommend_audience: option "audience_rows", else whole 128-row tiles while the batch's
+// (row, user tile) counts stay within kAudTableBytes
+inline int64_t aud_count_rows(int U, int64_t rows_option, int64_t n_items) {
+  const int64_t n_ut = (static_cast<int64_t>(U) + kRecTile - 1) / kRecTile;
+  int64_t rb = rows_option;
+  if (rb <= 0)
+    rb = std::max<int64_t>(kRecTile, static_cast<int64_t>(kAudTableBytes / sizeof(int32_t)) / n_ut / kRecTile * kRecTile);
+  return std::min(rb, n_items);
+}
+
+// The WRITE runs of one COUNT batch: consecutive rows whose entries stay under the cap (a larger row goes alone).  A
+// run without entries has nothing to write.
+struct AudRun {
+  int first, rows;
+  int64_t entries;
+};
+inline std::vector<AudRun> aud_write_runs(const int32_t *counts, int nb, int64_t cap) {
+  std::vector<AudRun> runs;
+  for (int s0 = 0; s0 < nb;) {
+    int64_t e = counts[s0];
+    int s1 = s0 + 1;
+    while (s1 < nb && e + counts[s1] <= cap) e += counts[s1++];
+    runs.push_back({s0, s1 - s0, e});
+    s0 = s1;
+  }
+  return runs;
+}
+
+// ---- diversified top-N (diverse.hpp) -------------------------------------------------------------------------------------
+// bytes a request row of recommend_diverse holds on the device: the pool list (12 bytes a place) and the picks (20 an entry)
+inline size_t div_row_bytes(int pool, int n) { return static_cast<size_t>(pool) * 12 + static_cast<size_t>(n) * 20 + 16; }
+
+// rows per call: option "diverse_rows", else all of them unless that is not free beside a batch's score buffer -- then
+// halves of the request until it is (a row's answer does not depend on the other rows)
+inline int64_t div_rows_per_call(int64_t rows_option, int64_t n_users, size_t free_bytes, size_t per_row) {
+  if (rows_option > 0) return std::min(rows_option, n_users);
+  int64_t rows_per = n_users;
+  while (rows_per > 1 && static_cast<size_t>(rows_per) * per_row + kRecBatchBytes + kFreeMargin > free_bytes)
+    rows_per = (rows_per + 1) / 2;
+  return rows_per;
+}
+
+}  // namespace mmsbm_hip_impl

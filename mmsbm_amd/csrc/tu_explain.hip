@@ -22,15 +22,9 @@ void explain_begin(mmsbm_hip_ctx *c, const double *weights) {
   ex->w.alloc(c->n_ratings);
   HIP_CHECK(hipMemcpyAsync(ex->w.ptr, weights, sizeof(double) * c->n_ratings, hipMemcpyHostToDevice, s));
   // every external user's training rows in the order they were given: from the id columns in their original order
-  const size_t n = static_cast<size_t>(c->n_obs);
-  std::vector<int32_t> ou(n), oi(n), rt(n);
-  if (n > 0) {
-    HIP_CHECK(hipMemcpyAsync(ou.data(), c->orig_u.ptr, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipMemcpyAsync(oi.data(), c->orig_i.ptr, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipMemcpyAsync(rt.data(), c->orig_r.ptr, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s));
-  }
-  HIP_CHECK(hipStreamSynchronize(s));
-  const std::vector<int32_t> &eu = c->swapped ? oi : ou, &ei = c->swapped ? ou : oi;  // (internal users = external items)
+  std::vector<int32_t> eu, ei, rt;
+  train_id_columns(c, eu, ei, &rt);
+  const size_t n = eu.size();
   std::vector<int32_t> item(n), rating(n);
   ex->off_h = group_by_key<int64_t>(eu.data(), static_cast<int64_t>(n), c->ext_users, [&](int64_t m, int64_t at) {
     item[at] = ei[m];

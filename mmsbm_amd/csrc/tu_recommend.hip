@@ -1,17 +1,15 @@
-// tu_recommend.hip -- translation unit of top-N recommendation (recommend.hpp): the session's host side -- the
-// training items of every user, the per-slot prologue, the batches of a query and the choice of the item split -- and
-// of nearest items / users (similar.hpp), whose queries share the batches and the selection; and the m best pairs of
-// the whole model (top_pairs.hpp), a query of the recommend session with kernels of its own; and the overlap of the
-// restarts' groups (overlap.hpp), whose session copies a slot's rows with the recommend session's rec_fold_kernel; and
-// the item-side queries of the recommend session (audience.hpp): the n best users of an item through the same batches
-// and selection, and the audience of an item above a bar through a fused kernel of its own; and the queries within a
-// part of the catalogue (catalogue.hpp): a subset of the items through the same batches and selection over a compact
-// item table, and per-user candidate lists through a kernel of their own; and the diversified top-N (diverse.hpp), the
-// one query that reads the recommend and the similarity session at once: the pool through the same batches and
-// selection, kept on the device, then a greedy kernel of its own; and the most informative items of a user
-// (inform.hpp): a session of its own whose prologue borrows the similarity session's two kernels and whose queries go
-// through the same batches, exclusions and selection behind a score kernel of their own; and the group queries of the
-// recommend session (group.hpp): the members' score tiles reduced per group in registers and LDS, then the same selection
+// tu_recommend.hip -- translation unit of the serving queries: the host side of the sessions and queries whose kernels
+// live in the headers below.  Every top-N query goes through the same batches and selection (top_n_device); the integer
+// planning of the queries is serve_plan.hpp.
+//   recommend.hpp  the recommend session: training items per user, the per-slot fold, scores, selection, positions
+//   similar.hpp    nearest items / users: a session of its own, the same batches and selection
+//   top_pairs.hpp  the m best pairs of the whole model: a query of the recommend session with kernels of its own
+//   overlap.hpp    the overlap of the restarts' groups: a session that copies a slot's rows with rec_fold_kernel
+//   audience.hpp   item-side queries: the n best users of an item, and an item's audience above a bar (fused kernel)
+//   catalogue.hpp  queries within a part of the catalogue: a compact item table, the query's own exclusions, ranking
+//   diverse.hpp    diversified top-N: the pool kept on the device, then a greedy kernel; reads the similarity session
+//   inform.hpp     the most informative items of a user: a session of its own behind a score kernel of its own
+//   group.hpp      group queries: the members' score tiles reduced per group, then the same selection
 #include "prelude.hpp"
 #include "recommend.hpp"
 #include "similar.hpp"
@@ -23,48 +21,84 @@
 #include "inform.hpp"
 #include "group.hpp"
 
-#include <climits>
-
 namespace mmsbm_hip_impl {
-
-namespace {
-
-constexpr size_t kRecBatchBytes = size_t(128) << 20;  // score buffer of one batch of users (stays in the 256 MB MALL)
-constexpr int kRecMinPerPart = 1024;                   // items a selecting wave gets at least
-constexpr int kPosMinPerPart = 2048;                   // items a counting workgroup gets at least
-constexpr size_t kAudTableBytes = size_t(64) << 20;    // recommend_audience: the (row, user tile) counts of one batch
-constexpr int64_t kAudEntries = int64_t(16) << 20;     // ... and the entries of one WRITE batch (12 bytes each)
-
-}  // namespace
 
 void require_free_mem(size_t bytes, const std::string &what) {
   size_t free_b = 0, total_b = 0;
   HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
-  if (bytes + (size_t(64) << 20) > free_b)
+  if (bytes + kFreeMargin > free_b)
     throw ApiError(MMSBM_E_TOOLARGE, what + " needs " + std::to_string(bytes >> 20) + " MB of device memory, " +
                                          std::to_string(free_b >> 20) + " MB free");
 }
 
-namespace {
-
-// Every external user's distinct training items, ascending, from the id columns in their original order: the offsets
-// [U + 1] (returned) and the items (`item`)
-std::vector<int32_t> train_item_lists(mmsbm_hip_ctx *c, std::vector<int32_t> &item) {
+void train_id_columns(mmsbm_hip_ctx *c, std::vector<int32_t> &user, std::vector<int32_t> &item,
+                      std::vector<int32_t> *rating) {
   hipStream_t s = c->stream;
   const size_t n = static_cast<size_t>(c->n_obs);
-  std::vector<int32_t> ou(n), oi(n);
+  user.resize(n);
+  item.resize(n);
+  if (rating) rating->resize(n);
   if (n > 0) {
-    HIP_CHECK(hipMemcpyAsync(ou.data(), c->orig_u.ptr, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipMemcpyAsync(oi.data(), c->orig_i.ptr, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(user.data(), c->orig_u.ptr, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(item.data(), c->orig_i.ptr, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s));
+    if (rating) HIP_CHECK(hipMemcpyAsync(rating->data(), c->orig_r.ptr, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s));
   }
   HIP_CHECK(hipStreamSynchronize(s));
-  const std::vector<int32_t> &eu = c->swapped ? oi : ou, &ei = c->swapped ? ou : oi;  // (internal users = external items)
-  item.assign(n, 0);
-  std::vector<int32_t> off = group_by_key<int32_t>(eu.data(), static_cast<int64_t>(n), c->ext_users,
+  if (c->swapped) user.swap(item);  // (internal users = external items)
+}
+
+namespace {
+
+// Every external user's distinct training items, ascending, onto the device (off [U + 1], item); returns the offsets.
+// `what`: the memory is checked under that name first (null: no check).  The stream has passed the copies on return.
+std::vector<int32_t> upload_train_lists(mmsbm_hip_ctx *c, DevBuf<int32_t> &d_off, DevBuf<int32_t> &d_item, const char *what) {
+  std::vector<int32_t> eu, ei;
+  train_id_columns(c, eu, ei, nullptr);
+  std::vector<int32_t> item(eu.size(), 0);
+  std::vector<int32_t> off = group_by_key<int32_t>(eu.data(), static_cast<int64_t>(eu.size()), c->ext_users,
                                                    [&](int64_t m, int32_t at) { item[at] = ei[m]; });
   sort_unique_groups(off, item);  // (duplicate pairs dropped)
+  if (what) require_free_mem((off.size() + item.size()) * sizeof(int32_t), what);
+  d_off.upload(off, c->stream);
+  d_item.upload(item, c->stream);
+  HIP_CHECK(hipStreamSynchronize(c->stream));  // (host vectors are locals)
   return off;
 }
+
+// A query's lists by request row on the device: host int64 offsets [n_rows + 1] narrowed to int32 (checked: below
+// 2^31) and the values behind them.  Holds the narrowed offsets for as long as it lives: the copies are asynchronous.
+// Never uploaded: both pointers null ("no list").
+struct DevCsr {
+  DevBuf<int32_t> off, val;
+  std::vector<int32_t> off_h;
+  static int64_t entries(const int64_t *offsets, int64_t n_rows) { return offsets && n_rows > 0 ? offsets[n_rows] : 0; }
+  void upload(const int64_t *offsets, const int32_t *values, int64_t n_rows, hipStream_t st) {
+    const int64_t n = entries(offsets, n_rows);
+    off_h.assign(offsets, offsets + n_rows + 1);
+    off.upload(off_h, st);
+    val.alloc(static_cast<size_t>(n));
+    if (n > 0) HIP_CHECK(hipMemcpyAsync(val.ptr, values, sizeof(int32_t) * n, hipMemcpyHostToDevice, st));
+  }
+  SeenLists lists() const { return {off.ptr, val.ptr}; }
+};
+
+// The rows a caller brings instead of the session's users: theta [S][n_users][K] on the device as it is, the identity
+// ids 0 .. n_users - 1 (request row b is row b of every slot's block) and the caller's seen lists by row (null: none).
+// The caller has checked the memory.
+struct CallerRows {
+  DevBuf<double> th;
+  std::vector<int32_t> ids;
+  DevCsr seen;
+  CallerRows(mmsbm_hip_ctx *c, int S, int64_t n_users, const double *theta, const int64_t *seen_offsets,
+             const int32_t *seen_items)
+      : ids(static_cast<size_t>(n_users)) {
+    const size_t tk = static_cast<size_t>(n_users) * c->ext_k;
+    th.alloc(S * tk);
+    if (S * tk > 0) HIP_CHECK(hipMemcpyAsync(th.ptr, theta, sizeof(double) * S * tk, hipMemcpyHostToDevice, c->stream));
+    for (int64_t b = 0; b < n_users; ++b) ids[static_cast<size_t>(b)] = static_cast<int32_t>(b);
+    if (seen_offsets && n_users > 0) seen.upload(seen_offsets, seen_items, n_users, c->stream);
+  }
+};
 
 }  // namespace
 
@@ -76,16 +110,10 @@ void recommend_begin(mmsbm_hip_ctx *c, const double *weights, int exclude_train)
   rc->w.alloc(c->n_ratings);
   HIP_CHECK(hipMemcpyAsync(rc->w.ptr, weights, sizeof(double) * c->n_ratings, hipMemcpyHostToDevice, s));
   rc->excl = exclude_train != 0;
-  if (rc->excl) {
-    std::vector<int32_t> item;
-    std::vector<int32_t> off = train_item_lists(c, item);
-    rc->seen_off.upload(off, s);
-    rc->seen_off_h = off;  // (candidate counts of recommend_positions)
-    rc->seen.upload(item, s);
-    HIP_CHECK(hipStreamSynchronize(s));  // (host vectors are locals)
-  }
+  if (rc->excl) rc->seen_off_h = upload_train_lists(c, rc->seen_off, rc->seen, nullptr);  // (also the candidate counts of recommend_positions)
   HIP_CHECK(hipStreamSynchronize(s));
   rc->rank = std::min(c->ext_k, c->ext_l);
+  rc->users = c->ext_users;
   rc->items = c->ext_items;
   c->rc = std::move(rc);
 }
@@ -193,35 +221,29 @@ void recommend_add_items(mmsbm_hip_ctx *c, int32_t n_new, const double *eta, con
 
 namespace {
 
-// users per batch: a score buffer of ~128 MB, whole 128-user tiles where that allows
-int64_t rec_batch_users(int I, int64_t n_users) {
-  int64_t bu = std::max<int64_t>(1, static_cast<int64_t>(kRecBatchBytes / (static_cast<size_t>(I) * sizeof(double))));
-  bu = std::min<int64_t>(bu, 32768);
-  if (bu >= kRecTile) bu = bu / kRecTile * kRecTile;
-  return std::min(bu, n_users);
+// sc [nb][n_cols]: the scores of the rows ids[0 .. nb) (device) of table a (`slots` tables as doubles apart, [row][rank])
+// against the rows 0 .. n_cols - 1 of table b; seen (indexed by those ids): the columns set to -inf.  fma is commutative
+// in its factors, so the sides exchanged give (u, i) the same score bit for bit.
+void score_tiles(mmsbm_hip_ctx *c, const double *a, size_t as, const double *b, size_t bs, int n_cols, const int32_t *ids,
+                 int nb, SeenLists seen, double *sc) {
+  if (n_cols == 0) return;
+  const dim3 g(static_cast<unsigned>((n_cols + kRecTile - 1) / kRecTile), static_cast<unsigned>((nb + kRecTile - 1) / kRecTile));
+  LAUNCH(rec_score_kernel, g, kBlock, 0, c->stream, a, as, b, bs, ids, nb, n_cols, c->rc->rank, c->rc->slots, sc,
+         static_cast<size_t>(n_cols));
+  if (seen.off) LAUNCH(rec_exclude_kernel, nb, kBlock, 0, c->stream, ids, seen.off, seen.items, sc, static_cast<size_t>(n_cols));
 }
 
-// (parts, per): the I items split into parts of at least min_per items each until about `target` (batch rows x
-// parts) are in flight; few users: one user over 100k items
-std::pair<int, int> item_parts(int I, int64_t bu, int64_t target, int min_per) {
-  int parts = 1;
-  if (bu < target) parts = static_cast<int>(std::min<int64_t>((target + bu - 1) / bu, (I + min_per - 1) / min_per));
-  parts = std::max(parts, 1);
-  const int per = (I + parts - 1) / parts;
-  return {I > 0 ? (I + per - 1) / per : 1, per};
+// ... of one batch of users ub (rows of x) against the session's catalogue.  Shared by the selection and the positions.
+void rec_score_batch(mmsbm_hip_ctx *c, const double *x, size_t xs, const int32_t *ub, int nb, SeenLists seen, double *sc) {
+  const RecSession &rc = *c->rc;
+  score_tiles(c, x, xs, rc.y.ptr, static_cast<size_t>(rc.items) * rc.rank, rc.items, ub, nb, seen, sc);
 }
 
-// The scores of one batch of nb users ub (device ids, rows of x) into sc [nb][I] (I: the session's catalogue); seen_off / seen (device, indexed by
-// those ids): the items set to -inf, or null.  Shared by the selection (rec_run) and the positions.
-void rec_score_batch(mmsbm_hip_ctx *c, const double *x, size_t xs, const int32_t *ub, int nb, const int32_t *seen_off,
-                     const int32_t *seen, double *sc) {
-  const int I = c->rc->items, rank = c->rc->rank, S = c->rc->slots;
-  if (I == 0) return;
-  hipStream_t st = c->stream;
-  const dim3 g(static_cast<unsigned>((I + kRecTile - 1) / kRecTile), static_cast<unsigned>((nb + kRecTile - 1) / kRecTile));
-  LAUNCH(rec_score_kernel, g, kBlock, 0, st, x, xs, c->rc->y.ptr, static_cast<size_t>(I) * rank, ub, nb, I, rank, S,
-         sc, static_cast<size_t>(I));
-  if (seen_off) LAUNCH(rec_exclude_kernel, nb, kBlock, 0, st, ub, seen_off, seen, sc, static_cast<size_t>(I));
+// The query's own excluded items (catalogue.hpp) of the batch that begins at request row b0: own's lists are by
+// request row; col_of (device): every item's column of sc, or null where the columns are the items
+void own_exclude_batch(hipStream_t st, const DevCsr &own, int64_t b0, int nb, const int32_t *col_of, double *sc, size_t ld) {
+  LAUNCH(cat_exclude_kernel, nb, kBlock, 0, st, static_cast<const int32_t *>(nullptr), static_cast<int>(b0),
+         static_cast<const int32_t *>(own.off.ptr), static_cast<const int32_t *>(own.val.ptr), col_of, sc, ld);
 }
 
 // Every row of a top-N answer as "no candidate": counts 0, ids -1, values -inf
@@ -242,24 +264,21 @@ struct TopNDev {
   const int32_t *on;
 };
 
-// The batches of a top-N query over a buffer of `I` columns: rows ids[0 .. n_rows) (host ids); `fill(ub, nb, sc)`
-// enqueues the kernels that write the batch's values sc [nb][I] for the device ids ub (-inf: no candidate), then the
-// N best of every row are selected (and merged when the columns are split across waves).  `what` names the query in
-// MMSBM_E_TOOLARGE.  Every row's result stays on the device: `then(dev, ev)` is called once the last batch is
-// enqueued, with the result and the event pair around the query's kernels (recorded; not waited for) -- it copies the
-// result out (top_n_copy_out) or enqueues a stage that reads it there (diverse.hpp); `extra` bytes of device memory
-// are what it will allocate.  n_users > 0.
+// The batches of a top-N query over a buffer of `I` columns: rows ids[0 .. n_rows) (host ids); `fill(ub, nb, b0, sc)`
+// enqueues the kernels that write the values sc [nb][I] of the batch of request rows b0 .. b0 + nb, whose device ids
+// are ub (-inf: no candidate), then the N best of every row are selected (and merged when the columns are split across
+// waves).  `what` names the query in MMSBM_E_TOOLARGE.  Every row's result stays on the device: `then(dev, ev)` is
+// called once the last batch is enqueued, with the result and the event pair around the query's kernels (recorded; not
+// waited for) -- it copies the result out (top_n_copy_out) or enqueues a stage that reads it there (diverse.hpp);
+// `extra` bytes of device memory are what it will allocate.  n_users > 0.
 template <class Fill, class Then>
 void top_n_device(mmsbm_hip_ctx *c, int I, int64_t n_users, const int32_t *users, int n, const char *what, size_t extra,
                   Fill &&fill, Then &&then) {
   hipStream_t st = c->stream;
-
   const int64_t bu = rec_batch_users(I, n_users);
   // items split across waves until about 32 selecting waves per CU are in flight (the selection waits on its loads)
   const auto [parts, per] = item_parts(I, bu, 32LL * c->n_cus, kRecMinPerPart);
-  int cap = 1;
-  while (cap < n + kRecWave * kRecPerLane) cap <<= 1;
-  const size_t lds = static_cast<size_t>(cap) * (sizeof(double) + sizeof(int32_t));
+  const auto [cap, lds] = select_list(n);
   const size_t cand = parts > 1 ? static_cast<size_t>(bu) * parts * n : 0;
   const size_t outs = static_cast<size_t>(n_users) * n;
   require_free_mem(static_cast<size_t>(bu) * I * sizeof(double) + cand * 12 + outs * 12 + static_cast<size_t>(n_users) * 8 +
@@ -281,7 +300,7 @@ void top_n_device(mmsbm_hip_ctx *c, int I, int64_t n_users, const int32_t *users
     const int32_t *ub = du.ptr + b0;
     double *obs = os.ptr + b0 * n;
     int32_t *obi = oi.ptr + b0 * n, *obn = on.ptr + b0;
-    fill(ub, nb, sc.ptr);
+    fill(ub, nb, b0, sc.ptr);
     if (parts > 1) {
       LAUNCH(rec_select_kernel<false>, dim3(parts, nb), kRecWave, lds, st, sc.ptr, static_cast<size_t>(I), I, per,
              nullptr, nullptr, nullptr, 0, n, cap, cs.ptr, ci.ptr, cn.ptr);
@@ -332,11 +351,11 @@ void top_n_run(mmsbm_hip_ctx *c, int I, int64_t n_users, const int32_t *users, i
 }
 
 // A recommend query: users users[0 .. n_users) (host ids, rows of x: `slots` tables of xs doubles, [row][rank]),
-// scored against the session's items; seen_off / seen (device, indexed by those ids): the items left out, or null.
-void rec_run(mmsbm_hip_ctx *c, const double *x, size_t xs, int64_t n_users, const int32_t *users,
-             const int32_t *seen_off, const int32_t *seen, int n, int32_t *items, double *scores, int32_t *counts) {
+// scored against the session's items; seen (indexed by those ids): the items left out.
+void rec_run(mmsbm_hip_ctx *c, const double *x, size_t xs, int64_t n_users, const int32_t *users, SeenLists seen, int n,
+             int32_t *items, double *scores, int32_t *counts) {
   top_n_run(c, c->rc->items, n_users, users, n, "recommend: a batch of users",
-            [&](const int32_t *ub, int nb, double *sc) { rec_score_batch(c, x, xs, ub, nb, seen_off, seen, sc); },
+            [&](const int32_t *ub, int nb, int64_t, double *sc) { rec_score_batch(c, x, xs, ub, nb, seen, sc); },
             T_RECOMMEND, items, scores, counts);
 }
 
@@ -377,58 +396,43 @@ void cat_table(mmsbm_hip_ctx *c, const int32_t *cand, int C, CatTable &t) {
 // compact table and the columns.  n_users > 0 and at least one column.
 template <class Then>
 void rec_within_device(mmsbm_hip_ctx *c, const double *x, size_t xs, int64_t n_users, const int32_t *users,
-                       const int32_t *seen_off, const int32_t *seen, const int32_t *cand, int n_cand,
-                       const int64_t *xoff, const int32_t *xit, int n, size_t extra, Then &&then) {
+                       SeenLists seen, const int32_t *cand, int n_cand, const int64_t *xoff, const int32_t *xit, int n,
+                       size_t extra, Then &&then) {
   const RecSession &rc = *c->rc;
   const int NI = rc.items, rank = rc.rank, S = rc.slots;
   const int C = cand ? n_cand : NI;
   hipStream_t st = c->stream;
-  const int64_t n_x = xoff ? xoff[n_users] : 0;  // (checked: below 2^31)
   const size_t ycs = static_cast<size_t>(C) * rank;
   if (cand || xoff)
     require_free_mem((cand ? S * ycs * sizeof(double) + (static_cast<size_t>(C) + NI) * 4 : 0) +
-                         (static_cast<size_t>(n_users) + 1 + n_x) * 4,
+                         (static_cast<size_t>(n_users) + 1 + DevCsr::entries(xoff, n_users)) * 4,
                      "recommend: the candidates' rows and the query's excluded items");
-  DevBuf<int32_t> dxo, dxi;
+  DevCsr own;
   CatTable ct;
-  std::vector<int32_t> hxo;
-  if (xoff) {
-    hxo.assign(xoff, xoff + n_users + 1);
-    dxo.upload(hxo, st);
-    dxi.alloc(static_cast<size_t>(n_x));
-    if (n_x > 0) HIP_CHECK(hipMemcpyAsync(dxi.ptr, xit, sizeof(int32_t) * n_x, hipMemcpyHostToDevice, st));
-  }
+  if (xoff) own.upload(xoff, xit, n_users, st);
   if (cand) cat_table(c, cand, C, ct);
-  const float prep_ms = ct.ms;  // device time of the compact table and the columns (added to "recommend_ms")
-  const int32_t *dcand_ptr = ct.cand.ptr, *dcol_ptr = ct.col.ptr;
-  const double *yc_ptr = ct.y.ptr;
-  int64_t done = 0;  // rows of the request the earlier batches held (the batches follow each other)
   top_n_device(c, C, n_users, users, n,
                cand || xoff ? "recommend: a batch of users within the candidates" : "recommend: a batch of users", extra,
-               [&](const int32_t *ub, int nb, double *sc) {
+               [&](const int32_t *ub, int nb, int64_t b0, double *sc) {
                  if (cand) {
-                   const dim3 g(static_cast<unsigned>((C + kRecTile - 1) / kRecTile), static_cast<unsigned>((nb + kRecTile - 1) / kRecTile));
-                   LAUNCH(rec_score_kernel, g, kBlock, 0, st, x, xs, yc_ptr, ycs, ub, nb, C, rank, S, sc, static_cast<size_t>(C));
-                   if (seen_off)
-                     LAUNCH(cat_exclude_kernel, nb, kBlock, 0, st, ub, 0, seen_off, seen, dcol_ptr, sc, static_cast<size_t>(C));
+                   score_tiles(c, x, xs, ct.y.ptr, ycs, C, ub, nb, SeenLists{}, sc);
+                   if (seen.off)
+                     LAUNCH(cat_exclude_kernel, nb, kBlock, 0, st, ub, 0, seen.off, seen.items, ct.col.ptr, sc, static_cast<size_t>(C));
                  } else {
-                   rec_score_batch(c, x, xs, ub, nb, seen_off, seen, sc);
+                   rec_score_batch(c, x, xs, ub, nb, seen, sc);
                  }
-                 if (xoff)
-                   LAUNCH(cat_exclude_kernel, nb, kBlock, 0, st, static_cast<const int32_t *>(nullptr), static_cast<int>(done),
-                          dxo.ptr, dxi.ptr, cand ? dcol_ptr : static_cast<const int32_t *>(nullptr), sc, static_cast<size_t>(C));
-                 done += nb;
+                 if (xoff) own_exclude_batch(st, own, b0, nb, ct.col.ptr, sc, static_cast<size_t>(C));
                },
-               [&](const TopNDev &dev, EventPair &ev) { then(dev, ev, cand ? dcand_ptr : nullptr, prep_ms); });
+               [&](const TopNDev &dev, EventPair &ev) { then(dev, ev, cand ? ct.cand.ptr : nullptr, ct.ms); });
 }
 
 // rec_within_device with the result copied to the host and the columns mapped to item ids there.  Without candidates
 // and own lists: rec_run.
-void rec_run_within(mmsbm_hip_ctx *c, const double *x, size_t xs, int64_t n_users, const int32_t *users,
-                    const int32_t *seen_off, const int32_t *seen, const int32_t *cand, int n_cand, const int64_t *xoff,
-                    const int32_t *xit, int n, int32_t *items, double *scores, int32_t *counts) {
+void rec_run_within(mmsbm_hip_ctx *c, const double *x, size_t xs, int64_t n_users, const int32_t *users, SeenLists seen,
+                    const int32_t *cand, int n_cand, const int64_t *xoff, const int32_t *xit, int n, int32_t *items,
+                    double *scores, int32_t *counts) {
   if (!cand && !xoff) {
-    rec_run(c, x, xs, n_users, users, seen_off, seen, n, items, scores, counts);
+    rec_run(c, x, xs, n_users, users, seen, n, items, scores, counts);
     return;
   }
   top_n_blank(n_users, n, items, scores, counts);
@@ -436,7 +440,7 @@ void rec_run_within(mmsbm_hip_ctx *c, const double *x, size_t xs, int64_t n_user
     c->last_ms[T_RECOMMEND] = 0.f;
     return;
   }
-  rec_within_device(c, x, xs, n_users, users, seen_off, seen, cand, n_cand, xoff, xit, n, 0,
+  rec_within_device(c, x, xs, n_users, users, seen, cand, n_cand, xoff, xit, n, 0,
                     [&](const TopNDev &dev, EventPair &ev, const int32_t *, float prep_ms) {
                       top_n_copy_out(c, dev, ev, n_users, n, T_RECOMMEND, items, scores, counts);
                       c->last_ms[T_RECOMMEND] += prep_ms;
@@ -453,35 +457,23 @@ void rec_theta_run(mmsbm_hip_ctx *c, int64_t n_users, const double *theta, const
                    int32_t *counts) {
   const int K = c->ext_k, L = c->ext_l, rank = c->rc->rank, S = c->rc->slots;
   const size_t tk = static_cast<size_t>(n_users) * K, xs = static_cast<size_t>(n_users) * rank;
-  const int64_t n_seen = seen_offsets && n_users > 0 ? seen_offsets[n_users] : 0;
-  require_free_mem(S * (tk + xs) * sizeof(double) + (static_cast<size_t>(n_users) + 1 + n_seen) * 4,
+  require_free_mem(S * (tk + xs) * sizeof(double) +
+                       (static_cast<size_t>(n_users) + 1 + DevCsr::entries(seen_offsets, n_users)) * 4,
                    "recommend: the caller's theta rows");
   hipStream_t st = c->stream;
-  // every slot's rows folded exactly as recommend_add folds the slot's own theta: x = theta, or theta W when K > L
-  DevBuf<double> th, x;
-  DevBuf<int32_t> soff, sit;
-  th.alloc(S * tk);
+  CallerRows rows(c, S, n_users, theta, seen_offsets, seen_items);
+  DevBuf<double> x;
   x.alloc(S * xs);
-  if (S * tk > 0) HIP_CHECK(hipMemcpyAsync(th.ptr, theta, sizeof(double) * S * tk, hipMemcpyHostToDevice, st));
-  std::vector<int32_t> hid(static_cast<size_t>(n_users)), hoff;
-  for (int64_t b = 0; b < n_users; ++b) hid[static_cast<size_t>(b)] = static_cast<int32_t>(b);
-  if (seen_offsets) {
-    hoff.assign(seen_offsets, seen_offsets + n_users + 1);  // (checked: below 2^31)
-    soff.upload(hoff, st);
-    sit.alloc(static_cast<size_t>(n_seen));
-    if (n_seen > 0)
-      HIP_CHECK(hipMemcpyAsync(sit.ptr, seen_items, sizeof(int32_t) * n_seen, hipMemcpyHostToDevice, st));
-  }
   const size_t kl = static_cast<size_t>(K) * L;
   for (int s = 0; s < S && xs > 0; ++s) {
-    const RowTab src = plain_tab(th.ptr + s * tk, K);
+    const RowTab src = plain_tab(rows.th.ptr + s * tk, K);
     const double *m = K <= L ? nullptr : c->rc->wk.ptr + s * kl;
     LAUNCH(rec_fold_kernel, static_cast<unsigned>((xs + kBlock - 1) / kBlock), kBlock, 0, st, src, K, m, L, 1,
            x.ptr + s * xs, static_cast<int>(n_users), rank);
   }
   HIP_CHECK(hipGetLastError());
-  rec_run_within(c, x.ptr, xs, n_users, hid.data(), seen_offsets ? soff.ptr : nullptr, sit.ptr, cand, n_cand, nullptr,
-                 nullptr, n, items, scores, counts);
+  rec_run_within(c, x.ptr, xs, n_users, rows.ids.data(), rows.seen.lists(), cand, n_cand, nullptr, nullptr, n, items,
+                 scores, counts);
 }
 
 }  // namespace
@@ -490,8 +482,7 @@ void recommend_query(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, in
                      int32_t *counts) {
   use_device(c);
   const RecSession &rc = *c->rc;
-  rec_run(c, rc.x.ptr, static_cast<size_t>(c->ext_users) * rc.rank, n_users, users, rc.excl ? rc.seen_off.ptr : nullptr,
-          rc.seen.ptr, n, items, scores, counts);
+  rec_run(c, rc.x.ptr, rc.x_stride(), n_users, users, rc.seen_lists(), n, items, scores, counts);
 }
 
 void recommend_query_theta(mmsbm_hip_ctx *c, int64_t n_users, const double *theta, const int64_t *seen_offsets,
@@ -505,9 +496,8 @@ void recommend_query_within(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *us
                             double *scores, int32_t *counts) {
   use_device(c);
   const RecSession &rc = *c->rc;
-  rec_run_within(c, rc.x.ptr, static_cast<size_t>(c->ext_users) * rc.rank, n_users, users,
-                 rc.excl ? rc.seen_off.ptr : nullptr, rc.seen.ptr, cand, n_cand, excl_offsets, excl_items, n, items,
-                 scores, counts);
+  rec_run_within(c, rc.x.ptr, rc.x_stride(), n_users, users, rc.seen_lists(), cand, n_cand, excl_offsets, excl_items, n,
+                 items, scores, counts);
 }
 
 void recommend_query_theta_within(mmsbm_hip_ctx *c, int64_t n_users, const double *theta, const int64_t *seen_offsets,
@@ -521,63 +511,38 @@ void recommend_rank(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, con
                     const int32_t *cand, int n, int32_t *items, double *scores, int32_t *counts) {
   use_device(c);
   const RecSession &rc = *c->rc;
-  for (int64_t b = 0; b < n_users; ++b) {
-    if (counts) counts[b] = 0;
-    for (int k = 0; k < n; ++k) {
-      items[static_cast<size_t>(b) * n + k] = -1;
-      if (scores) scores[static_cast<size_t>(b) * n + k] = -INFINITY;
-    }
-  }
+  top_n_blank(n_users, n, items, scores, counts);
   c->last_ms[T_RECOMMEND] = 0.f;
   if (n_users == 0) return;
   hipStream_t st = c->stream;
-  const int64_t total = offsets[n_users];  // (checked: below 2^31)
-  int cap = 1;
-  while (cap < n + kRecWave * kRecPerLane) cap <<= 1;
-  const size_t lds = static_cast<size_t>(cap) * (sizeof(double) + sizeof(int32_t));
+  const auto [cap, lds] = select_list(n);
   const size_t outs = static_cast<size_t>(n_users) * n;
-  require_free_mem(outs * 12 + (2 * static_cast<size_t>(n_users) + 1 + static_cast<size_t>(total)) * 4 +
+  require_free_mem(outs * 12 + (2 * static_cast<size_t>(n_users) + 1 + static_cast<size_t>(offsets[n_users])) * 4 +
                        static_cast<size_t>(n_users) * 4,
                    "recommend_rank: the users' lists and results");
-  std::vector<int32_t> hoff(offsets, offsets + n_users + 1);
-  DevBuf<int32_t> du, doff, dc, oi, on;
+  DevBuf<int32_t> du, oi, on;
   DevBuf<double> os;
+  DevCsr lists;  // every request row's candidates
   du.alloc(static_cast<size_t>(n_users));
-  doff.upload(hoff, st);
-  dc.alloc(static_cast<size_t>(total));
+  lists.upload(offsets, cand, n_users, st);
   os.alloc(outs); oi.alloc(outs); on.alloc(static_cast<size_t>(n_users));
   HIP_CHECK(hipMemcpyAsync(du.ptr, users, sizeof(int32_t) * n_users, hipMemcpyHostToDevice, st));
-  if (total > 0) HIP_CHECK(hipMemcpyAsync(dc.ptr, cand, sizeof(int32_t) * total, hipMemcpyHostToDevice, st));
+  const SeenLists seen = rc.seen_lists();
   EventPair ev;  // device time of the query's kernel (option "recommend_ms")
   ev.start(st);
-  LAUNCH(cat_rank_kernel, static_cast<unsigned>(n_users), kRecWave, lds, st, rc.x.ptr,
-         static_cast<size_t>(c->ext_users) * rc.rank, rc.y.ptr, static_cast<size_t>(rc.items) * rc.rank, rc.rank, rc.slots,
-         du.ptr, doff.ptr, dc.ptr, rc.excl ? rc.seen_off.ptr : nullptr, rc.seen.ptr, n, cap, os.ptr, oi.ptr, on.ptr);
+  LAUNCH(cat_rank_kernel, static_cast<unsigned>(n_users), kRecWave, lds, st, rc.x.ptr, rc.x_stride(), rc.y.ptr,
+         static_cast<size_t>(rc.items) * rc.rank, rc.rank, rc.slots, du.ptr, lists.off.ptr, lists.val.ptr, seen.off,
+         seen.items, n, cap, os.ptr, oi.ptr, on.ptr);
   HIP_CHECK(hipGetLastError());
   ev.stop(st);
-  std::vector<double> hs(outs);
-  std::vector<int32_t> hi(outs), hn(static_cast<size_t>(n_users));
-  HIP_CHECK(hipMemcpyAsync(hs.data(), os.ptr, sizeof(double) * outs, hipMemcpyDeviceToHost, st));
-  HIP_CHECK(hipMemcpyAsync(hi.data(), oi.ptr, sizeof(int32_t) * outs, hipMemcpyDeviceToHost, st));
-  HIP_CHECK(hipMemcpyAsync(hn.data(), on.ptr, sizeof(int32_t) * n_users, hipMemcpyDeviceToHost, st));
-  HIP_CHECK(hipStreamSynchronize(st));
-  c->last_ms[T_RECOMMEND] = ev.ms();
-  for (int64_t b = 0; b < n_users; ++b) {
-    const size_t o = static_cast<size_t>(b) * n;
-    const int cnt = hn[static_cast<size_t>(b)];
-    if (counts) counts[b] = cnt;
-    for (int k = 0; k < cnt; ++k) {
-      items[o + k] = hi[o + k];
-      if (scores) scores[o + k] = hs[o + k];
-    }
-  }
+  top_n_copy_out(c, TopNDev{os.ptr, oi.ptr, on.ptr}, ev, n_users, n, T_RECOMMEND, items, scores, counts);
 }
 
 void recommend_positions(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, const int64_t *offsets,
                          const int32_t *items, int32_t *positions, int32_t *candidates) {
   use_device(c);
   const RecSession &rc = *c->rc;
-  const int I = rc.items, rank = rc.rank;
+  const int I = rc.items;
   const int64_t total = n_users > 0 ? offsets[n_users] : 0;  // (checked: below 2^31)
   for (int64_t b = 0; b < n_users && candidates; ++b) {
     const int32_t u = users[b];
@@ -618,10 +583,9 @@ void recommend_positions(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users
   HIP_CHECK(hipMemcpyAsync(dit.ptr, items, sizeof(int32_t) * total, hipMemcpyHostToDevice, st));
   EventPair ev;  // device time of the call's kernels (option "position_ms")
   ev.start(st);
-  const size_t xs = static_cast<size_t>(c->ext_users) * rank;
   for (int64_t b0 = 0; b0 < na; b0 += bu) {  // (batches follow each other on the stream)
     const int nb = static_cast<int>(std::min(bu, na - b0));
-    rec_score_batch(c, rc.x.ptr, xs, du.ptr + b0, nb, rc.excl ? rc.seen_off.ptr : nullptr, rc.seen.ptr, sc.ptr);
+    rec_score_batch(c, rc.x.ptr, rc.x_stride(), du.ptr + b0, nb, rc.seen_lists(), sc.ptr);
     LAUNCH(rec_position_kernel, dim3(parts, nb), kBlock, 0, st, sc.ptr, static_cast<size_t>(I), I, per, dto.ptr + b0,
            dit.ptr, pc.ptr);
     LAUNCH(rec_position_sum_kernel, nb, kBlock, 0, st, sc.ptr, static_cast<size_t>(I), dto.ptr + b0, dit.ptr, pc.ptr,
@@ -665,9 +629,9 @@ void recommend_top_pairs(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users
   HIP_CHECK(hipMemcpyAsync(du.ptr, users, sizeof(int32_t) * n_users, hipMemcpyHostToDevice, st));
   EventPair ev;  // device time of the query's kernels (option "top_pairs_ms")
   ev.start(st);
-  LAUNCH(gtop_fused_kernel, G, kBlock, 0, st, rc.x.ptr, static_cast<size_t>(c->ext_users) * rank, rc.y.ptr,
-         static_cast<size_t>(I) * rank, du.ptr, static_cast<int>(n_users), I, rank, rc.slots,
-         rc.excl ? rc.seen_off.ptr : nullptr, rc.seen.ptr, m, sa.ptr, ka.ptr, na.ptr);
+  const SeenLists seen = rc.seen_lists();
+  LAUNCH(gtop_fused_kernel, G, kBlock, 0, st, rc.x.ptr, rc.x_stride(), rc.y.ptr, static_cast<size_t>(I) * rank, du.ptr,
+         static_cast<int>(n_users), I, rank, rc.slots, seen.off, seen.items, m, sa.ptr, ka.ptr, na.ptr);
   // merge levels: a -> b -> a ... until one list is left (G = 1: one level, so that the merge is always part of a query)
   double *is = sa.ptr, *os = sb.ptr;
   uint64_t *ik = ka.ptr, *ok = kb.ptr;
@@ -729,21 +693,6 @@ void rec_item_lists(mmsbm_hip_ctx *c) {
   rc.by_item_built = true;
 }
 
-// rec_score_batch with the sides exchanged: the scores of one batch of nb items ib (device ids, rows of the session's
-// item table) against every user into sc [nb][U]; ex_off / ex (device, indexed by item id): the users set to -inf, or
-// null.  fma is commutative in its factors: sc[b][u] is bit for bit the score rec_score_batch gives (u, ib[b]).
-void rec_score_items_batch(mmsbm_hip_ctx *c, const int32_t *ib, int nb, const int32_t *ex_off, const int32_t *ex,
-                           double *sc) {
-  const RecSession &rc = *c->rc;
-  const int U = c->ext_users, rank = rc.rank, S = rc.slots;
-  if (U == 0) return;
-  hipStream_t st = c->stream;
-  const dim3 g(static_cast<unsigned>((U + kRecTile - 1) / kRecTile), static_cast<unsigned>((nb + kRecTile - 1) / kRecTile));
-  LAUNCH(rec_score_kernel, g, kBlock, 0, st, rc.y.ptr, static_cast<size_t>(rc.items) * rank, rc.x.ptr,
-         static_cast<size_t>(U) * rank, ib, nb, U, rank, S, sc, static_cast<size_t>(U));
-  if (ex_off) LAUNCH(rec_exclude_kernel, nb, kBlock, 0, st, ib, ex_off, ex, sc, static_cast<size_t>(U));
-}
-
 }  // namespace
 
 void recommend_query_items(mmsbm_hip_ctx *c, int64_t n_items, const int32_t *items, int n, int32_t *users,
@@ -751,9 +700,11 @@ void recommend_query_items(mmsbm_hip_ctx *c, int64_t n_items, const int32_t *ite
   use_device(c);
   rec_item_lists(c);
   const RecSession &rc = *c->rc;
-  const int32_t *ex_off = rc.excl ? rc.by_item_off.ptr : nullptr, *ex = rc.by_item.ptr;
-  top_n_run(c, c->ext_users, n_items, items, n, "recommend: a batch of items",
-            [&](const int32_t *ib, int nb, double *sc) { rec_score_items_batch(c, ib, nb, ex_off, ex, sc); },
+  const SeenLists ex{rc.excl ? rc.by_item_off.ptr : nullptr, rc.by_item.ptr};  // (by item id: the users left out)
+  top_n_run(c, rc.users, n_items, items, n, "recommend: a batch of items",
+            [&](const int32_t *ib, int nb, int64_t, double *sc) {  // rec_score_batch with the sides exchanged
+              score_tiles(c, rc.y.ptr, static_cast<size_t>(rc.items) * rc.rank, rc.x.ptr, rc.x_stride(), rc.users, ib, nb, ex, sc);
+            },
             T_RECOMMEND, users, scores, counts);
 }
 
@@ -768,10 +719,7 @@ void recommend_audience(mmsbm_hip_ctx *c, int64_t n_items, const int32_t *items,
   if (n_items == 0 || U == 0) return;
   hipStream_t st = c->stream;
   const int64_t n_ut = (static_cast<int64_t>(U) + kRecTile - 1) / kRecTile;
-  // items per COUNT batch: whole 128-row tiles while the batch's counts stay within kAudTableBytes
-  int64_t rb = c->aud_rows;
-  if (rb <= 0) rb = std::max<int64_t>(kRecTile, static_cast<int64_t>(kAudTableBytes / sizeof(int32_t)) / n_ut / kRecTile * kRecTile);
-  rb = std::min(rb, n_items);
+  const int64_t rb = aud_count_rows(U, c->aud_rows, n_items);  // items per COUNT batch
   const size_t table = static_cast<size_t>(rb) * n_ut;
   require_free_mem(table * 4 + static_cast<size_t>(n_items) * 8 + static_cast<size_t>(rb) * 8,
                    "audience: the counts of a batch of items");
@@ -781,7 +729,7 @@ void recommend_audience(mmsbm_hip_ctx *c, int64_t n_items, const int32_t *items,
   tot.alloc(n_items);
   HIP_CHECK(hipMemcpyAsync(di.ptr, items, sizeof(int32_t) * n_items, hipMemcpyHostToDevice, st));
   const int32_t *ex_off = rc.excl ? rc.by_item_off.ptr : nullptr, *ex = rc.by_item.ptr;
-  const size_t xs = static_cast<size_t>(rc.items) * rank, ys = static_cast<size_t>(U) * rank;
+  const size_t xs = static_cast<size_t>(rc.items) * rank, ys = rc.x_stride();
   // tiles are dealt to at most 8 workgroups per CU (what the staging tiles' LDS allows twice over)
   auto groups = [&](int nb) {
     return static_cast<unsigned>(std::min<int64_t>(n_ut * ((nb + kRecTile - 1) / kRecTile), 8LL * c->n_cus));
@@ -842,32 +790,28 @@ void recommend_audience(mmsbm_hip_ctx *c, int64_t n_items, const int32_t *items,
       HIP_CHECK(hipStreamSynchronize(st));
       ms += ev.ms();
     }
-    for (int s0 = 0; s0 < nb;) {
-      int64_t e = ht[static_cast<size_t>(r0 + s0)];
-      int s1 = s0 + 1;
-      while (s1 < nb && e + ht[static_cast<size_t>(r0 + s1)] <= cap) e += ht[static_cast<size_t>(r0 + s1++)];
-      if (e > 0) {
-        const int ns = s1 - s0;
-        EventPair ev;
-        ev.start(st);
-        LAUNCH(aud_tile_kernel<true>, groups(ns), kBlock, 0, st, rc.y.ptr, xs, rc.x.ptr, ys, di.ptr + r0 + s0, ns, U, rank,
-               S, ex_off, ex, min_score, cnt.ptr + s0, static_cast<size_t>(nb), rbase.ptr + s0, hb[static_cast<size_t>(s0)],
-               ou.ptr, os.ptr, out_cap);
-        HIP_CHECK(hipGetLastError());
-        ev.stop(st);
-        const int64_t o = offsets[r0 + s0];
-        HIP_CHECK(hipMemcpyAsync(users + o, ou.ptr, sizeof(int32_t) * e, hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipMemcpyAsync(scores + o, os.ptr, sizeof(double) * e, hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipStreamSynchronize(st));
-        ms += ev.ms();
-      }
-      s0 = s1;
+    for (const AudRun &run : aud_write_runs(ht.data() + r0, nb, cap)) {
+      if (run.entries == 0) continue;
+      const int s0 = run.first;
+      EventPair ev;
+      ev.start(st);
+      LAUNCH(aud_tile_kernel<true>, groups(run.rows), kBlock, 0, st, rc.y.ptr, xs, rc.x.ptr, ys, di.ptr + r0 + s0, run.rows,
+             U, rank, S, ex_off, ex, min_score, cnt.ptr + s0, static_cast<size_t>(nb), rbase.ptr + s0,
+             hb[static_cast<size_t>(s0)], ou.ptr, os.ptr, out_cap);
+      HIP_CHECK(hipGetLastError());
+      ev.stop(st);
+      const int64_t o = offsets[r0 + s0];
+      HIP_CHECK(hipMemcpyAsync(users + o, ou.ptr, sizeof(int32_t) * run.entries, hipMemcpyDeviceToHost, st));
+      HIP_CHECK(hipMemcpyAsync(scores + o, os.ptr, sizeof(double) * run.entries, hipMemcpyDeviceToHost, st));
+      HIP_CHECK(hipStreamSynchronize(st));
+      ms += ev.ms();
     }
   }
   c->last_ms[T_AUDIENCE] = ms;
 }
 
 // ---- group queries (group.hpp) ------------------------------------------------------------------------------------------
+// plan (plan_groups: the member blocks, the batches' runs and fragments), memory check, uploads, top_n_run, scatter
 void recommend_query_groups(mmsbm_hip_ctx *c, int64_t n_groups, const int64_t *offsets, const int32_t *members, int mode,
                             double bar, const int32_t *cand, int n_cand, int n, int32_t *items, double *scores,
                             int32_t *counts) {
@@ -877,137 +821,53 @@ void recommend_query_groups(mmsbm_hip_ctx *c, int64_t n_groups, const int64_t *o
   c->last_ms[T_GROUP] = 0.f;
   const int NI = rc.items, rank = rc.rank, S = rc.slots;
   const int C = cand ? n_cand : NI;
-  // the rows of the device request: the groups that have members (an empty group has no candidate)
-  std::vector<int32_t> ids;
-  std::vector<int64_t> at;  // their places in the caller's request
-  for (int64_t g = 0; g < n_groups; ++g)
-    if (offsets[g + 1] > offsets[g]) {
-      ids.push_back(static_cast<int32_t>(at.size()));
-      at.push_back(g);
-    }
-  const int64_t G = static_cast<int64_t>(at.size());
-  if (G == 0 || C == 0) return;  // (no row or no column to score: every row is empty)
-  // the members in blocks of kGrpBlock rows; a group's last block is filled up with its first member's id (a row that
-  // can be loaded; the kernels never look at it: blk_info holds the number of members)
-  const size_t n_blocks = [&] {
-    size_t b = 0;
-    for (int64_t r = 0; r < G; ++r) b += static_cast<size_t>((offsets[at[r] + 1] - offsets[at[r]] + kGrpBlock - 1) / kGrpBlock);
-    return b;
-  }();
-  if (n_blocks * kGrpBlock > static_cast<size_t>(INT32_MAX))
-    throw ApiError(MMSBM_E_TOOLARGE, "recommend_query_groups: " + std::to_string(n_blocks) + " blocks of member rows in one query");
-  std::vector<int32_t> rows, info, grp, gblk(static_cast<size_t>(G) + 1), gsize(static_cast<size_t>(G));
-  rows.reserve(n_blocks * kGrpBlock);
-  info.reserve(n_blocks);
-  grp.reserve(n_blocks);
-  for (int64_t r = 0; r < G; ++r) {
-    const int32_t *m = members + offsets[at[r]];
-    const int64_t sz = offsets[at[r] + 1] - offsets[at[r]];
-    gblk[static_cast<size_t>(r)] = static_cast<int32_t>(info.size());
-    gsize[static_cast<size_t>(r)] = static_cast<int32_t>(sz);
-    for (int64_t k = 0; k < sz; k += kGrpBlock) {
-      const int in = static_cast<int>(std::min<int64_t>(kGrpBlock, sz - k));
-      for (int a = 0; a < kGrpBlock; ++a) rows.push_back(a < in ? m[k + a] : m[0]);
-      info.push_back(in | (k + kGrpBlock >= sz ? kGrpLast : 0));
-      grp.push_back(static_cast<int32_t>(r));
-    }
-  }
-  gblk[static_cast<size_t>(G)] = static_cast<int32_t>(info.size());
-  // the batches top_n_device will form, and per batch its runs: `want` blocks each -- whole steps of the walk, about 8
-  // workgroups per CU over the item tiles (option "group_run_blocks") -- made of whole groups; a group longer than
-  // that is cut into fragments of `want` blocks, one run each, whose values meet in grp_combine_kernel
   const bool tiles = mode != MMSBM_HIP_GROUP_MEAN;
-  const int64_t bu = rec_batch_users(C, G);
-  const int64_t item_tiles = (static_cast<int64_t>(C) + kRecTile - 1) / kRecTile;
-  std::vector<int32_t> out = grp;           // per block: the row the tile kernel writes (a group, or a fragment)
-  std::vector<int32_t> run_off, batch_run;  // the runs' first blocks; the batches' first runs
-  std::vector<int32_t> cut_grp, cut_off, batch_cut;  // the cut groups, their first fragments; the batches' first cut groups
-  int32_t n_frag = 0, most_frag = 0;        // fragments so far; of the batch with the most
-  for (int64_t b0 = 0; tiles && b0 < G; b0 += bu) {
-    const int64_t b1 = std::min(G, b0 + bu);
-    const int64_t blocks = gblk[static_cast<size_t>(b1)] - gblk[static_cast<size_t>(b0)];
-    const int64_t most = std::max<int64_t>(1, 8LL * c->n_cus / item_tiles);
-    const int64_t ask = c->grp_run > 0 ? c->grp_run : (blocks + most - 1) / most;
-    const int32_t want = static_cast<int32_t>(std::max<int64_t>(kGrpStep, (std::min<int64_t>(ask, blocks) + kGrpStep - 1) / kGrpStep * kGrpStep));
-    batch_run.push_back(static_cast<int32_t>(run_off.size()));
-    batch_cut.push_back(static_cast<int32_t>(cut_grp.size()));
-    const int32_t frag0 = n_frag;
-    int32_t first = gblk[static_cast<size_t>(b0)];
-    run_off.push_back(first);
-    auto begin_run = [&](int32_t blk) {  // (nothing where a run begins there already)
-      if (blk > first) {
-        first = blk;
-        run_off.push_back(blk);
-      }
-    };
-    for (int64_t r = b0; r < b1; ++r) {
-      const int32_t g_lo = gblk[static_cast<size_t>(r)], g_hi = gblk[static_cast<size_t>(r) + 1];
-      if (g_hi - g_lo > want) {
-        cut_grp.push_back(static_cast<int32_t>(r));
-        cut_off.push_back(n_frag);
-        for (int32_t lo = g_lo; lo < g_hi; lo += want, ++n_frag) {
-          const int32_t hi = std::min(g_hi, lo + want);
-          begin_run(lo);
-          for (int32_t b = lo; b < hi; ++b) {
-            info[static_cast<size_t>(b)] |= kGrpPart;
-            out[static_cast<size_t>(b)] = n_frag;
-          }
-          info[static_cast<size_t>(hi) - 1] |= kGrpLast;
-        }
-        if (r + 1 < b1) begin_run(g_hi);
-      } else if (g_hi - first >= want && r + 1 < b1) {
-        begin_run(g_hi);
-      }
-    }
-    most_frag = std::max(most_frag, n_frag - frag0);
-  }
-  if (tiles) {
-    batch_run.push_back(static_cast<int32_t>(run_off.size()));
-    run_off.push_back(gblk[static_cast<size_t>(G)]);  // (one past the last run; a batch's last run ends where the next batch's first begins)
-    batch_cut.push_back(static_cast<int32_t>(cut_grp.size()));
-    cut_off.push_back(n_frag);
-  }
+  const GroupPlan p = plan_groups(offsets, members, n_groups, C, c->n_cus, c->grp_run, tiles);
+  const int64_t G = p.groups();
+  if (G == 0 || C == 0) return;  // (no row or no column to score: every row is empty)
+  if (p.too_large())
+    throw ApiError(MMSBM_E_TOOLARGE, "recommend_query_groups: " + std::to_string(p.n_blocks) + " blocks of member rows in one query");
   const size_t ycs = static_cast<size_t>(C) * rank, bs = static_cast<size_t>(G) * rank;
   require_free_mem((cand ? S * ycs * sizeof(double) + (static_cast<size_t>(C) + NI) * 4 : 0) +
-                       (rows.size() + 3 * info.size() + run_off.size() + 2 * cut_off.size() + 2 * static_cast<size_t>(G) + 1) * 4 +
-                       (tiles ? static_cast<size_t>(most_frag) * C : S * bs) * sizeof(double),
+                       (p.rows.size() + 3 * p.info.size() + p.run_off.size() + 2 * p.cut_off.size() + 2 * static_cast<size_t>(G) + 1) * 4 +
+                       (tiles ? static_cast<size_t>(p.most_frag) * C : S * bs) * sizeof(double),
                    "recommend_query_groups: the member rows, the groups' lists and the candidates' rows");
   hipStream_t st = c->stream;
   DevBuf<int32_t> d_rows, d_info, d_grp, d_out, d_run, d_cut_grp, d_cut_off, d_gblk, d_size;
   DevBuf<double> xbar, part;
   CatTable ct;
-  d_rows.upload(rows, st);
-  d_info.upload(info, st);
-  d_grp.upload(grp, st);
+  d_rows.upload(p.rows, st);
+  d_info.upload(p.info, st);
+  d_grp.upload(p.grp, st);
   if (tiles) {
-    d_out.upload(out, st);
-    d_run.upload(run_off, st);
-    if (most_frag > 0) {
-      d_cut_grp.upload(cut_grp, st);
-      d_cut_off.upload(cut_off, st);
-      part.alloc(static_cast<size_t>(most_frag) * C);
+    d_out.upload(p.out, st);
+    d_run.upload(p.run_off, st);
+    if (p.most_frag > 0) {
+      d_cut_grp.upload(p.cut_grp, st);
+      d_cut_off.upload(p.cut_off, st);
+      part.alloc(static_cast<size_t>(p.most_frag) * C);
     }
   } else {
-    d_gblk.upload(gblk, st);
-    d_size.upload(gsize, st);
+    d_gblk.upload(p.gblk, st);
+    d_size.upload(p.gsize, st);
     xbar.alloc(S * bs);
   }
   if (cand) cat_table(c, cand, C, ct);
   const double *y = cand ? ct.y.ptr : rc.y.ptr;
-  const size_t ys = cand ? ycs : static_cast<size_t>(NI) * rank, xs = static_cast<size_t>(c->ext_users) * rank;
-  const int32_t *seen_off = rc.excl ? rc.seen_off.ptr : nullptr, *col_of = cand ? ct.col.ptr : nullptr;
+  const size_t ys = cand ? ycs : static_cast<size_t>(NI) * rank, xs = rc.x_stride();
+  const SeenLists seen = rc.seen_lists();
+  const int32_t *col_of = cand ? ct.col.ptr : nullptr;
   std::vector<int32_t> ti(static_cast<size_t>(G) * n), tc(static_cast<size_t>(G));
   std::vector<double> ts(static_cast<size_t>(G) * n);
-  int64_t done = 0;  // groups the earlier batches held (the batches follow each other)
-  top_n_run(c, C, G, ids.data(), n, "recommend_query_groups: a batch of groups",
-            [&](const int32_t *ub, int nb, double *sc) {
-              const int g0 = static_cast<int>(done);
-              const unsigned it = static_cast<unsigned>(item_tiles);
+  top_n_run(c, C, G, p.ids.data(), n, "recommend_query_groups: a batch of groups",
+            [&](const int32_t *ub, int nb, int64_t b0, double *sc) {
+              const int g0 = static_cast<int>(b0);
+              const unsigned it = static_cast<unsigned>(p.item_tiles);
               if (tiles) {
-                const size_t k = static_cast<size_t>(done / bu);
-                const dim3 g(it, static_cast<unsigned>(batch_run[k + 1] - batch_run[k]));
-                const int32_t *ro = d_run.ptr + batch_run[k];
-                const int n_cut = batch_cut[k + 1] - batch_cut[k], p0 = cut_off[static_cast<size_t>(batch_cut[k])];
+                const size_t k = static_cast<size_t>(b0 / p.bu);
+                const dim3 g(it, static_cast<unsigned>(p.batch_run[k + 1] - p.batch_run[k]));
+                const int32_t *ro = d_run.ptr + p.batch_run[k];
+                const int n_cut = p.batch_cut[k + 1] - p.batch_cut[k], p0 = p.cut_off[static_cast<size_t>(p.batch_cut[k])];
                 auto tile = [&](auto kernel) {
                   LAUNCH(kernel, g, kBlock, 0, st, rc.x.ptr, xs, y, ys, d_rows.ptr, d_info.ptr, d_out.ptr, ro, g0, p0, C, rank,
                          S, bar, sc, part.ptr, static_cast<size_t>(C));
@@ -1017,28 +877,26 @@ void recommend_query_groups(mmsbm_hip_ctx *c, int64_t n_groups, const int64_t *o
                 else tile(grp_tile_kernel<kGrpCount>);
                 if (n_cut > 0)
                   LAUNCH(grp_combine_kernel, dim3(static_cast<unsigned>((C + kBlock - 1) / kBlock), static_cast<unsigned>(n_cut)),
-                         kBlock, 0, st, part.ptr, d_cut_grp.ptr + batch_cut[k], d_cut_off.ptr + batch_cut[k], g0, p0, C, mode, S,
+                         kBlock, 0, st, part.ptr, d_cut_grp.ptr + p.batch_cut[k], d_cut_off.ptr + p.batch_cut[k], g0, p0, C, mode, S,
                          sc, static_cast<size_t>(C));
               } else {
                 const size_t e = static_cast<size_t>(nb) * rank * S;
                 LAUNCH(grp_mean_kernel, static_cast<unsigned>((e + kBlock - 1) / kBlock), kBlock, 0, st, rc.x.ptr, xs, rank,
                        S, d_rows.ptr, d_gblk.ptr, d_size.ptr, g0, nb, xbar.ptr, bs);
-                LAUNCH(rec_score_kernel, dim3(it, static_cast<unsigned>((nb + kRecTile - 1) / kRecTile)), kBlock, 0, st,
-                       xbar.ptr, bs, y, ys, ub, nb, C, rank, S, sc, static_cast<size_t>(C));
+                score_tiles(c, xbar.ptr, bs, y, ys, C, ub, nb, SeenLists{}, sc);
               }
-              if (seen_off) {
-                const int blk0 = gblk[static_cast<size_t>(g0)];
-                LAUNCH(grp_exclude_kernel, static_cast<unsigned>(gblk[static_cast<size_t>(g0) + nb] - blk0), kBlock, 0, st,
-                       d_rows.ptr, d_info.ptr, d_grp.ptr, blk0, g0, seen_off, rc.seen.ptr, col_of, sc, static_cast<size_t>(C));
+              if (seen.off) {
+                const int blk0 = p.gblk[static_cast<size_t>(g0)];
+                LAUNCH(grp_exclude_kernel, static_cast<unsigned>(p.gblk[static_cast<size_t>(g0) + nb] - blk0), kBlock, 0, st,
+                       d_rows.ptr, d_info.ptr, d_grp.ptr, blk0, g0, seen.off, seen.items, col_of, sc, static_cast<size_t>(C));
               }
-              done += nb;
             },
             T_GROUP, ti.data(), ts.data(), tc.data());
   c->last_ms[T_GROUP] += ct.ms;
   for (int64_t r = 0; r < G; ++r) {  // the rows to their places in the request, columns -> item ids
-    const size_t o = static_cast<size_t>(at[r]) * n, t = static_cast<size_t>(r) * n;
+    const size_t o = static_cast<size_t>(p.at[r]) * n, t = static_cast<size_t>(r) * n;
     const int cnt = tc[static_cast<size_t>(r)];
-    if (counts) counts[at[r]] = cnt;
+    if (counts) counts[p.at[r]] = cnt;
     for (int k = 0; k < cnt; ++k) {
       items[o + k] = cand ? cand[ti[t + k]] : ti[t + k];
       if (scores) scores[o + k] = ts[t + k];
@@ -1090,7 +948,7 @@ void similar_query(mmsbm_hip_ctx *c, int64_t n_rows, const int32_t *ids, int n, 
   const double denom = static_cast<double>(S) * static_cast<double>(sm.others);
   hipStream_t st = c->stream;
   top_n_run(c, rows, n_rows, ids, n, "similar: a batch of query rows",
-            [&](const int32_t *ub, int nb, double *sc) {
+            [&](const int32_t *ub, int nb, int64_t, double *sc) {
               const dim3 g(static_cast<unsigned>((rows + kSimTile - 1) / kSimTile),
                            static_cast<unsigned>((nb + kSimTile - 1) / kSimTile));
               LAUNCH(sim_dist_kernel, g, kBlock, 0, st, sm.q.ptr, static_cast<size_t>(rows) * W, sm.mf.ptr, ub, nb, rows,
@@ -1147,19 +1005,10 @@ void recommend_diverse(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, 
   hipStream_t st = c->stream;
   const double denom = static_cast<double>(sm.slots) * static_cast<double>(sm.others);
   const size_t lds = (static_cast<size_t>(pool) * 21 + 7) / 8 * 8;  // score, m, id, picked flag per place
-  // rows per call: the pool lists (12 bytes a place) and the picks (20 an entry) of all of them unless that is not
-  // free -- then halves of the request until it is (a row's answer does not depend on the other rows)
-  const size_t per_row = static_cast<size_t>(pool) * 12 + static_cast<size_t>(n) * 20 + 16;
-  int64_t rows_per = n_users;
-  if (c->div_rows > 0) {
-    rows_per = std::min<int64_t>(c->div_rows, n_users);
-  } else {
-    size_t free_b = 0, total_b = 0;
-    HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
-    while (rows_per > 1 && static_cast<size_t>(rows_per) * per_row + kRecBatchBytes + (size_t(64) << 20) > free_b)
-      rows_per = (rows_per + 1) / 2;
-  }
-  const size_t xs = static_cast<size_t>(c->ext_users) * rc.rank;
+  size_t free_b = 0, total_b = 0;
+  if (c->div_rows <= 0) HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
+  const int64_t rows_per = div_rows_per_call(c->div_rows, n_users, free_b, div_row_bytes(pool, n));
+  const SeenLists seen = rc.seen_lists();
   float ms = 0.f;  // device time of the query's kernels (option "diverse_ms")
   std::vector<int64_t> sub;
   for (int64_t b0 = 0; b0 < n_users; b0 += rows_per) {
@@ -1170,8 +1019,7 @@ void recommend_diverse(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, 
     }
     const size_t outs = static_cast<size_t>(nb) * n;
     rec_within_device(
-        c, rc.x.ptr, xs, nb, users + b0, rc.excl ? rc.seen_off.ptr : nullptr, rc.seen.ptr, cand, n_cand,
-        xoff ? sub.data() : nullptr, xoff ? xit + xoff[b0] : nullptr, pool, outs * 20 + static_cast<size_t>(nb) * 4,
+        c, rc.x.ptr, rc.x_stride(), nb, users + b0, seen, cand, n_cand, xoff ? sub.data() : nullptr, xoff ? xit + xoff[b0] : nullptr, pool, outs * 20 + static_cast<size_t>(nb) * 4,
         [&](const TopNDev &dev, EventPair &ev, const int32_t *dcand, float prep_ms) {
           DevBuf<int32_t> ri, rn;
           DevBuf<double> rs, rd;
@@ -1238,12 +1086,12 @@ void inform_add(mmsbm_hip_ctx *c) {  // the selected slot (the caller holds a On
 namespace {
 
 // An inform query: request rows users[0 .. n_users) (host ids, rows of th: `slots` tables of ts doubles, [row][K])
-// against every item.  seen_off / seen (device, indexed by those ids): the items left out, or null; cand[0 .. n_cand)
-// (host; ascending, distinct item ids; null: every item): the candidate mask; xoff / xit (host, by request row, any
-// order, repeats allowed; null: none): the query's own excluded items.
-void inf_run(mmsbm_hip_ctx *c, const double *th, size_t ts, int64_t n_users, const int32_t *users,
-             const int32_t *seen_off, const int32_t *seen, const int32_t *cand, int n_cand, const int64_t *xoff,
-             const int32_t *xit, int n, int32_t *items, double *gains, int32_t *counts) {
+// against every item.  seen (indexed by those ids): the items left out; cand[0 .. n_cand) (host; ascending, distinct
+// item ids; null: every item): the candidate mask; xoff / xit (host, by request row, any order, repeats allowed; null:
+// none): the query's own excluded items.
+void inf_run(mmsbm_hip_ctx *c, const double *th, size_t ts, int64_t n_users, const int32_t *users, SeenLists seen,
+             const int32_t *cand, int n_cand, const int64_t *xoff, const int32_t *xit, int n, int32_t *items,
+             double *gains, int32_t *counts) {
   const InfSession &inf = *c->inf;
   const int I = c->ext_items, K = c->ext_k, R = c->n_ratings, S = inf.slots;
   c->last_ms[T_INFORM] = 0.f;
@@ -1252,39 +1100,28 @@ void inf_run(mmsbm_hip_ctx *c, const double *th, size_t ts, int64_t n_users, con
     return;
   }
   hipStream_t st = c->stream;
-  const int64_t n_x = xoff ? xoff[n_users] : 0;  // (checked: below 2^31)
-  require_free_mem((cand ? static_cast<size_t>(I) : 0) + (xoff ? (static_cast<size_t>(n_users) + 1 + n_x) * 4 : 0),
+  require_free_mem((cand ? static_cast<size_t>(I) : 0) +
+                       (xoff ? (static_cast<size_t>(n_users) + 1 + DevCsr::entries(xoff, n_users)) * 4 : 0),
                    "inform: the candidate mask and the query's excluded items");
   DevBuf<uint8_t> dmask;
-  DevBuf<int32_t> dxo, dxi;
+  DevCsr own;
   if (cand) {
     std::vector<uint8_t> hm(static_cast<size_t>(I), 0);
     for (int e = 0; e < n_cand; ++e) hm[static_cast<size_t>(cand[e])] = 1;
     dmask.upload(hm, st);
     HIP_CHECK(hipStreamSynchronize(st));  // (`hm` is a local)
   }
-  std::vector<int32_t> hxo;
-  if (xoff) {
-    hxo.assign(xoff, xoff + n_users + 1);
-    dxo.upload(hxo, st);
-    dxi.alloc(static_cast<size_t>(n_x));
-    if (n_x > 0) HIP_CHECK(hipMemcpyAsync(dxi.ptr, xit, sizeof(int32_t) * n_x, hipMemcpyHostToDevice, st));
-  }
+  if (xoff) own.upload(xoff, xit, n_users, st);
   const size_t hs = static_cast<size_t>(I) * K, qs = hs * R;
-  int64_t done = 0;  // rows of the request the earlier batches held (the batches follow each other)
   top_n_run(c, I, n_users, users, n, "inform: a batch of users",
-            [&](const int32_t *ub, int nb, double *sc) {
+            [&](const int32_t *ub, int nb, int64_t b0, double *sc) {
               const dim3 g(static_cast<unsigned>((I + kInfTile - 1) / kInfTile),
                            static_cast<unsigned>((nb + kInfTile - 1) / kInfTile));
               LAUNCH(inf_score_kernel, g, kBlock, 0, st, th, ts, static_cast<const double *>(inf.q.ptr), qs,
                      static_cast<const double *>(inf.h.ptr), hs, ub, nb, I, K, R, S,
                      static_cast<const uint8_t *>(dmask.ptr), sc, static_cast<size_t>(I));
-              if (seen_off) LAUNCH(rec_exclude_kernel, nb, kBlock, 0, st, ub, seen_off, seen, sc, static_cast<size_t>(I));
-              if (xoff)
-                LAUNCH(cat_exclude_kernel, nb, kBlock, 0, st, static_cast<const int32_t *>(nullptr), static_cast<int>(done),
-                       static_cast<const int32_t *>(dxo.ptr), static_cast<const int32_t *>(dxi.ptr),
-                       static_cast<const int32_t *>(nullptr), sc, static_cast<size_t>(I));
-              done += nb;
+              if (seen.off) LAUNCH(rec_exclude_kernel, nb, kBlock, 0, st, ub, seen.off, seen.items, sc, static_cast<size_t>(I));
+              if (xoff) own_exclude_batch(st, own, b0, nb, nullptr, sc, static_cast<size_t>(I));
             },
             T_INFORM, items, gains, counts);
 }
@@ -1297,48 +1134,26 @@ void inform_query(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, const
   use_device(c);
   InfSession &inf = *c->inf;
   if (exclude_train && !inf.seen_built) {  // every user's training items, built by the first query that leaves them out
-    std::vector<int32_t> item;
-    const std::vector<int32_t> off = train_item_lists(c, item);
-    require_free_mem((off.size() + item.size()) * sizeof(int32_t), "inform: the users' training items");
-    DevBuf<int32_t> d_off, d_item;
-    d_off.upload(off, c->stream);
-    d_item.upload(item, c->stream);
-    HIP_CHECK(hipStreamSynchronize(c->stream));  // (host vectors are locals)
-    inf.seen_off.swap(d_off);
-    inf.seen.swap(d_item);
+    upload_train_lists(c, inf.seen_off, inf.seen, "inform: the users' training items");
     inf.seen_built = true;
   }
   inf_run(c, inf.th.ptr, static_cast<size_t>(c->ext_users) * c->ext_k, n_users, users,
-          exclude_train ? inf.seen_off.ptr : nullptr, inf.seen.ptr, cand, n_cand, excl_offsets, excl_items, n, items,
-          gains, counts);
+          SeenLists{exclude_train ? inf.seen_off.ptr : nullptr, inf.seen.ptr}, cand, n_cand, excl_offsets, excl_items, n,
+          items, gains, counts);
 }
 
 void inform_query_theta(mmsbm_hip_ctx *c, int64_t n_users, const double *theta, const int64_t *seen_offsets,
                         const int32_t *seen_items, const int32_t *cand, int n_cand, int n, int32_t *items,
                         double *gains, int32_t *counts) {
   use_device(c);
-  const int K = c->ext_k, S = c->inf->slots;
-  const size_t tk = static_cast<size_t>(n_users) * K;
-  const int64_t n_seen = seen_offsets && n_users > 0 ? seen_offsets[n_users] : 0;  // (checked: below 2^31)
-  require_free_mem(S * tk * sizeof(double) + (static_cast<size_t>(n_users) + 1 + n_seen) * 4,
+  const int S = c->inf->slots;
+  const size_t tk = static_cast<size_t>(n_users) * c->ext_k;
+  require_free_mem(S * tk * sizeof(double) + (static_cast<size_t>(n_users) + 1 + DevCsr::entries(seen_offsets, n_users)) * 4,
                    "inform: the caller's theta rows");
-  hipStream_t st = c->stream;
-  DevBuf<double> th;  // the caller's rows as they are: request row b is row b of every slot's block
-  DevBuf<int32_t> soff, sit;
-  th.alloc(S * tk);
-  if (S * tk > 0) HIP_CHECK(hipMemcpyAsync(th.ptr, theta, sizeof(double) * S * tk, hipMemcpyHostToDevice, st));
-  std::vector<int32_t> hid(static_cast<size_t>(n_users)), hoff;
-  for (int64_t b = 0; b < n_users; ++b) hid[static_cast<size_t>(b)] = static_cast<int32_t>(b);
-  if (seen_offsets && n_users > 0) {
-    hoff.assign(seen_offsets, seen_offsets + n_users + 1);
-    soff.upload(hoff, st);
-    sit.alloc(static_cast<size_t>(n_seen));
-    if (n_seen > 0)
-      HIP_CHECK(hipMemcpyAsync(sit.ptr, seen_items, sizeof(int32_t) * n_seen, hipMemcpyHostToDevice, st));
-  }
-  inf_run(c, th.ptr, tk, n_users, hid.data(), soff.ptr, sit.ptr, cand, n_cand, nullptr, nullptr, n, items, gains,
+  CallerRows rows(c, S, n_users, theta, seen_offsets, seen_items);
+  inf_run(c, rows.th.ptr, tk, n_users, rows.ids.data(), rows.seen.lists(), cand, n_cand, nullptr, nullptr, n, items, gains,
           counts);
-  HIP_CHECK(hipStreamSynchronize(st));  // (`th` and the lists are locals)
+  HIP_CHECK(hipStreamSynchronize(c->stream));  // (the rows and the lists are locals)
 }
 
 void inform_mean_theta(mmsbm_hip_ctx *c, double *out) {
