@@ -415,6 +415,49 @@ int mmsbm_hip_recommend_query_groups(mmsbm_hip_ctx *ctx, int64_t n_groups, const
                                      const int32_t *cand_items, int32_t n, int32_t *items, double *scores,
                                      int32_t *counts);
 
+/* Ensemble-aware queries of the open recommend session (mmsbm_amd/csrc/ensemble.hpp): how far the added slots -- the
+ * restarts -- AGREE about a pair.  With x_s / y_s the folded factors the session holds for slot s (add order),
+ *   a_s(u, i) = ONE fma chain over j = 0 .. rank - 1 ascending from +0.0 of x_s[u, j] y_s[i, j]
+ * -- the bits recommend_query returns as the score in a session that holds slot s alone -- and, per pair, every product
+ * and sum rounded on its own (no contraction):
+ *   worst = min_s a_s                       best = max_s a_s
+ *   d_s = a_s - a_0   (s = 1 .. S - 1)      D = ((+0.0 + d_1) + d_2) + ...     Q = ((+0.0 + d_1 d_1) + d_2 d_2) + ...
+ *   mean = a_0 + D / S
+ *   var  = max(S Q - D D, +0.0) / (S S)     std = sqrt(var)                    (population form: divide by S)
+ *   lcb  = mean - risk std                  (product rounded, then the subtraction)
+ * Slots that agree on a pair give std = +0.0 and mean = a_0 exactly; S = 1 gives recommend_query's bits in every mode.
+ *
+ * query_ensemble: recommend_query_within -- the same candidates (cand_items: n_cand strictly ascending ids of the
+ * session's catalogue, the items of recommend_add_items included; NULL: all of it, n_cand ignored), the same exclusions
+ * (the session's lists while exclude_train is set, the seen lists of recommend_add_items, and the query's own
+ * excl_items[excl_offsets[b] .. excl_offsets[b + 1]) by request row, excl_offsets NULL: none), the same output -- with
+ * the value of a pair being, by mode,
+ *   MMSBM_HIP_ENSEMBLE_MIN  worst      MMSBM_HIP_ENSEMBLE_MAX  best      MMSBM_HIP_ENSEMBLE_LCB  lcb
+ * (`risk` is read by LCB alone: > 0 ranks by a lower confidence bound, 0 by the mean, < 0 explores where the slots
+ * disagree).  Order: value descending, equal values (exact fp64 equality) by ascending item id.
+ *
+ * pair_spread: for n_pairs caller-given pairs (users[e], items[e]) -- ids of training users and of the session's
+ * catalogue, any order, repeats allowed -- stats[e * 4 ...] = mean, std, worst, best, and, unless per_slot is NULL,
+ * per_slot[s * n_pairs + e] = a_s.  The same chains as query_ensemble's: a returned pair's worst / best / mean - risk std
+ * are the query's bits.  No row of scores is formed.
+ *
+ * A value depends on its pair alone: bitwise the same whatever the other rows of the call, the candidate set, the slots
+ * the context holds beyond those added, and in swapped and unswapped contexts.  Both touch no slot, no EM state and no
+ * other session; the recommend session stays open and answers as before.  mmsbm_hip_get_option(ctx, "ensemble_ms") reads
+ * the device time of the last call's kernels.
+ * MMSBM_E_INVALID (before any launch): no recommend session or no slot added to it, an id out of range, cand_items not
+ * strictly ascending, a bad CSR, n < 1, an unknown mode, a risk that is not finite in LCB mode.
+ * n > MMSBM_HIP_RECOMMEND_MAX_N: MMSBM_E_UNSUPPORTED; MMSBM_E_TOOLARGE where the device memory is not free. */
+#define MMSBM_HIP_ENSEMBLE_MIN 0
+#define MMSBM_HIP_ENSEMBLE_MAX 1
+#define MMSBM_HIP_ENSEMBLE_LCB 2
+int mmsbm_hip_recommend_query_ensemble(mmsbm_hip_ctx *ctx, int64_t n_users, const int32_t *users, int mode, double risk,
+                                       int32_t n_cand, const int32_t *cand_items, const int64_t *excl_offsets,
+                                       const int32_t *excl_items, int32_t n, int32_t *items, double *scores,
+                                       int32_t *counts);
+int mmsbm_hip_recommend_pair_spread(mmsbm_hip_ctx *ctx, int64_t n_pairs, const int32_t *users, const int32_t *items,
+                                    double *stats, double *per_slot);
+
 /* ---- the items whose rating tells most about a user: the n largest information gains (mmsbm_amd/csrc/inform.hpp) -- */
 /* A session of its own beside the predict, recommend, similar, overlap, explain and held-out sessions (any of them may
  * be open meanwhile):

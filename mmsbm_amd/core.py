@@ -572,6 +572,37 @@ class HipEM:
                   _p_or_null(cand, C.c_int32), n, _p(items, C.c_int32), _p(scores, C.c_double), _p(counts, C.c_int32))
         return items, scores, counts
 
+    # -- ensemble-aware queries of the recommend session (include/mmsbm_hip.h: mmsbm_hip_recommend_query_ensemble) -----
+    ENSEMBLE_MODES = {"min": 0, "max": 1, "lcb": 2}   # MMSBM_HIP_ENSEMBLE_*
+
+    def recommend_query_ensemble(self, users, n, mode, risk=0.0, candidates=None, exclude=None):
+        """recommend_query_within -- the same candidates, exclusions and output -- with a pair valued by how the added
+        slots agree on it.  ``mode`` (a key of ENSEMBLE_MODES or its number): "min" the lowest score a slot alone gives
+        the pair, "max" the highest, "lcb" mean - ``risk`` x std over the slots (population std; ``risk`` 0: the mean,
+        negative: exploration).  With one slot added every mode answers as recommend_query, bit for bit."""
+        u, n = _i32(users), int(n)
+        cand = None if candidates is None else _i32(candidates)
+        off, it = _csr(exclude, len(u), "exclude offsets", "items")
+        items, scores, counts = self._query_out(len(u), n)
+        _lib.call("mmsbm_hip_recommend_query_ensemble", self._h, len(u), _p(u, C.c_int32),
+                  int(self.ENSEMBLE_MODES.get(mode, mode)), float(risk), 0 if cand is None else len(cand),
+                  _p_or_null(cand, C.c_int32), _p_or_null(off, C.c_int64), _p_or_null(it, C.c_int32), n,
+                  _p(items, C.c_int32), _p(scores, C.c_double), _p(counts, C.c_int32))
+        return items, scores, counts
+
+    def recommend_pair_spread(self, users, items, per_slot=False):
+        """stats (M, 4): mean, std, worst, best over the added slots of the score each slot alone gives the pair
+        (users[e], items[e]) -- encoded ids of training users and of the session's catalogue -- the bits
+        recommend_query_ensemble ranks by.  With ``per_slot``: (stats, (S, M) every slot's own score)."""
+        u, i = _i32(users), _i32(items)
+        if u.shape != i.shape or u.ndim != 1:
+            raise ValueError(f"users and items must be two id columns of one length, got shapes {u.shape} and {i.shape}")
+        stats = np.empty((len(u), 4), dtype=np.float64)
+        each = np.empty((self._rc_added, len(u)), dtype=np.float64) if per_slot else None
+        _lib.call("mmsbm_hip_recommend_pair_spread", self._h, len(u), _p(u, C.c_int32), _p(i, C.c_int32),
+                  _p(stats, C.c_double), _p_or_null(each, C.c_double))
+        return (stats, each) if per_slot else stats
+
     # -- the items whose rating tells most about a user (include/mmsbm_hip.h: mmsbm_hip_inform_*) ---------
     def inform_begin(self):
         """Open an inform session: the information gain of a rating, averaged over the slots added to it."""

@@ -249,8 +249,8 @@ inline void sort_unique_groups(std::vector<int32_t> &off, std::vector<int32_t> &
 // The serving calls whose kernels are timed (mmsbm_hip_ctx::last_ms), in the order of their "<name>_ms" options:
 // recommend_query / recommend_query_items, fold_in / fold_in_items, recommend_positions, recommend_top_pairs,
 // recommend_audience, similar_query, overlap_query, heldout_eval / heldout_add, explain_query, recommend_diverse /
-// similar_pairs, inform_query / inform_query_theta, recommend_query_groups
-enum TimedCall { T_RECOMMEND = 0, T_FOLD_IN, T_POSITIONS, T_TOP_PAIRS, T_AUDIENCE, T_SIMILAR, T_OVERLAP, T_HELDOUT, T_EXPLAIN, T_DIVERSE, T_INFORM, T_GROUP, T_COUNT };
+// similar_pairs, inform_query / inform_query_theta, recommend_query_groups, recommend_query_ensemble / recommend_pair_spread
+enum TimedCall { T_RECOMMEND = 0, T_FOLD_IN, T_POSITIONS, T_TOP_PAIRS, T_AUDIENCE, T_SIMILAR, T_OVERLAP, T_HELDOUT, T_EXPLAIN, T_DIVERSE, T_INFORM, T_GROUP, T_ENSEMBLE, T_COUNT };
 
 enum KernelId { K_SEG = 0, K_DENSE, K_ETAP, K_MATVEC_A, K_FUSED_PAIRS, K_FUSED_TAIL, K_COUNT };
 // The four launches of an iteration -- or, for small problems, the two of fused_small.hpp.  With pass_dense.hpp the

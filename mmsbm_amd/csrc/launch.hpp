@@ -88,6 +88,13 @@ void recommend_diverse(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, 
 void recommend_query_groups(mmsbm_hip_ctx *c, int64_t n_groups, const int64_t *offsets, const int32_t *members, int mode,
                             double bar, const int32_t *cand, int n_cand, int n, int32_t *items, double *scores,
                             int32_t *counts);
+// ... and the ensemble-aware queries of the recommend session (ensemble.hpp), arguments checked: mode:
+// MMSBM_HIP_ENSEMBLE_*; cand / excl_* as in recommend_query_within; stats [n_pairs][4], per_slot [S][n_pairs] or null
+void recommend_query_ensemble(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, int mode, double risk,
+                              const int32_t *cand, int n_cand, const int64_t *excl_offsets, const int32_t *excl_items,
+                              int n, int32_t *items, double *scores, int32_t *counts);
+void recommend_pair_spread(mmsbm_hip_ctx *c, int64_t n_pairs, const int32_t *users, const int32_t *items, double *stats,
+                           double *per_slot);
 // ... and the overlap of the restarts' groups (overlap.hpp): the session of mmsbm_hip_overlap_*, arguments checked
 void overlap_begin(mmsbm_hip_ctx *c, int side);
 void overlap_add(mmsbm_hip_ctx *c);  // the selected slot (the caller holds a OneSlot)

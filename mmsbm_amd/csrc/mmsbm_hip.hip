@@ -860,6 +860,7 @@ const Option kOptions[] = {
     {"diverse_ms", [](const Ctx *c) -> double { return c->last_ms[T_DIVERSE]; }, nullptr},
     {"inform_ms", [](const Ctx *c) -> double { return c->last_ms[T_INFORM]; }, nullptr},
     {"group_ms", [](const Ctx *c) -> double { return c->last_ms[T_GROUP]; }, nullptr},
+    {"ensemble_ms", [](const Ctx *c) -> double { return c->last_ms[T_ENSEMBLE]; }, nullptr},
     // workgroups of gtop_fused_kernel (top_pairs.hpp); 0: the library's choice
     {"top_pairs_groups", [](const Ctx *c) -> double { return c->top_groups; },
      [](Ctx *c, double v) {
@@ -1886,6 +1887,40 @@ int mmsbm_hip_recommend_query_groups(mmsbm_hip_ctx *ctx, int64_t n_groups, const
       }
     require_subset(cand_items, n_cand, rc.items, "recommend_query_groups");
     recommend_query_groups(ctx, n_groups, offsets, members, mode, bar, cand_items, n_cand, n, items, scores, counts);
+  });
+}
+
+int mmsbm_hip_recommend_query_ensemble(mmsbm_hip_ctx *ctx, int64_t n_users, const int32_t *users, int mode, double risk,
+                                       int32_t n_cand, const int32_t *cand_items, const int64_t *excl_offsets,
+                                       const int32_t *excl_items, int32_t n, int32_t *items, double *scores,
+                                       int32_t *counts) {
+  return guarded([&] {
+    const RecSession &rc = require_open(ctx, &mmsbm_hip_ctx::rc, "recommend", "recommend_query_ensemble");
+    if (n_users < 0) throw std::invalid_argument("negative n_users");
+    if (mode != MMSBM_HIP_ENSEMBLE_MIN && mode != MMSBM_HIP_ENSEMBLE_MAX && mode != MMSBM_HIP_ENSEMBLE_LCB)
+      throw std::invalid_argument("recommend_query_ensemble: unknown mode " + std::to_string(mode));
+    if (mode == MMSBM_HIP_ENSEMBLE_LCB && !std::isfinite(risk))
+      throw std::invalid_argument("recommend_query_ensemble: risk must be finite");
+    require_n(n, "recommend_query_ensemble", "items");
+    if (n_users > 0 && (!users || !items)) throw std::invalid_argument("null argument");
+    require_ids(users, n_users, ctx->ext_users, "recommend_query_ensemble: user");
+    require_subset(cand_items, n_cand, rc.items, "recommend_query_ensemble");
+    check_csr(excl_offsets, excl_items, n_users, rc.items, "recommend_query_ensemble", "excl_offsets", "user",
+              "excluded items", "excluded item");
+    recommend_query_ensemble(ctx, n_users, users, mode, risk, cand_items, n_cand, n_users > 0 ? excl_offsets : nullptr,
+                             excl_items, n, items, scores, counts);
+  });
+}
+
+int mmsbm_hip_recommend_pair_spread(mmsbm_hip_ctx *ctx, int64_t n_pairs, const int32_t *users, const int32_t *items,
+                                    double *stats, double *per_slot) {
+  return guarded([&] {
+    const RecSession &rc = require_open(ctx, &mmsbm_hip_ctx::rc, "recommend", "recommend_pair_spread");
+    if (n_pairs < 0) throw std::invalid_argument("negative n_pairs");
+    if (n_pairs > 0 && (!users || !items || !stats)) throw std::invalid_argument("null argument");
+    require_ids(users, n_pairs, ctx->ext_users, "recommend_pair_spread: user");
+    require_ids(items, n_pairs, rc.items, "recommend_pair_spread: item");
+    recommend_pair_spread(ctx, n_pairs, users, items, stats, per_slot);
   });
 }
 

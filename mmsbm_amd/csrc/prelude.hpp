@@ -16,7 +16,7 @@
 //                       top_pairs.hpp  the m best pairs            overlap.hpp    the overlap of the restarts' groups
 //                       audience.hpp   item-side queries           catalogue.hpp  queries within a part of the catalogue
 //                       diverse.hpp    the diversified top-N       inform.hpp     the most informative items of a user
-//                       group.hpp      group queries
+//                       group.hpp      group queries               ensemble.hpp   how far the restarts agree on a pair
 //   tu_fold_in.hip    fold new users into a fitted model (fold_in.hpp)
 //   tu_heldout.hip    held-out log-likelihood of every restart slot (heldout.hpp)
 //   tu_explain.hip    which of a user's training rows carry a recommendation (explain.hpp)

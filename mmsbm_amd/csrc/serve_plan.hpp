@@ -160,6 +160,15 @@ inline GroupPlan plan_groups(const int64_t *offsets, const int32_t *members, int
   return p;
 }
 
+// ---- the spread of given pairs (ensemble.hpp) ----------------------------------------------------------------------------
+// pairs per launch of recommend_pair_spread: the batch's ids, four numbers a pair and, when wanted, the S slots' values
+// stay within kEnsPairBytes (at least one pair)
+constexpr size_t kEnsPairBytes = size_t(256) << 20;
+inline size_t ens_pair_bytes(int slots, bool per_slot) { return 8 + 32 + (per_slot ? static_cast<size_t>(slots) * 8 : 0); }
+inline int64_t ens_pairs_per_launch(int64_t n_pairs, int slots, bool per_slot) {
+  return std::min<int64_t>(n_pairs, std::max<int64_t>(1, static_cast<int64_t>(kEnsPairBytes / ens_pair_bytes(slots, per_slot))));
+}
+
 // ---- item-side queries (audience.hpp) ----------------------------------------------------------------------------------
 // items per COUNT batch of recommend_audience: option "audience_rows", else whole 128-row tiles while the batch's
 // (row, user tile) counts stay within kAudTableBytes

@@ -10,6 +10,8 @@
 //   diverse.hpp    diversified top-N: the pool kept on the device, then a greedy kernel; reads the similarity session
 //   inform.hpp     the most informative items of a user: a session of its own behind a score kernel of its own
 //   group.hpp      group queries: the members' score tiles reduced per group, then the same selection
+//   ensemble.hpp   ensemble-aware queries: the restarts' scores reduced per pair (min, max, mean - risk std), then the
+//                  same selection; the spread of given pairs
 #include "prelude.hpp"
 #include "recommend.hpp"
 #include "similar.hpp"
@@ -20,6 +22,7 @@
 #include "diverse.hpp"
 #include "inform.hpp"
 #include "group.hpp"
+#include "ensemble.hpp"
 
 namespace mmsbm_hip_impl {
 
@@ -388,16 +391,19 @@ void cat_table(mmsbm_hip_ctx *c, const int32_t *cand, int C, CatTable &t) {
   t.ms = ev.ms();
 }
 
-// The device side of rec_run within the candidates cand[0 .. n_cand) (host; ascending, distinct ids of the session's
-// catalogue; null: the whole catalogue), and with the query's own excluded items: row b of the request also leaves out
-// xit[xoff[b] .. xoff[b + 1]) (host, any order, repeats allowed; null: none).  catalogue.hpp.  Without either: rec_run's
-// launches.  The result stays on the device (top_n_device): `then(dev, ev, dcand, prep_ms)` gets it -- as COLUMNS of
-// the candidate list when there is one --, the candidate list on the device (or null) and the device time of the
-// compact table and the columns.  n_users > 0 and at least one column.
-template <class Then>
-void rec_within_device(mmsbm_hip_ctx *c, const double *x, size_t xs, int64_t n_users, const int32_t *users,
-                       SeenLists seen, const int32_t *cand, int n_cand, const int64_t *xoff, const int32_t *xit, int n,
-                       size_t extra, Then &&then) {
+// The device side of a recommend query within the candidates cand[0 .. n_cand) (host; ascending, distinct ids of the
+// session's catalogue; null: the whole catalogue), and with the query's own excluded items: row b of the request also
+// leaves out xit[xoff[b] .. xoff[b + 1]) (host, any order, repeats allowed; null: none).  catalogue.hpp.
+// `tiles(y, ys, C, ub, nb, sc)` enqueues the kernel that writes the values sc [nb][C] of the batch's rows ub (device ids)
+// against the C rows of the item table y (slots ys doubles apart: the catalogue's, or the candidates' compact table) --
+// the score tiles of recommend_query (rec_tiles), the aggregate over the restarts (ensemble.hpp); seen (indexed by user
+// id): the items left out after it.  The result stays on the device (top_n_device): `then(dev, ev, dcand, prep_ms)` gets
+// it -- as COLUMNS of the candidate list when there is one --, the candidate list on the device (or null) and the device
+// time of the compact table and the columns.  n_users > 0 and at least one column.
+template <class Tiles, class Then>
+void rec_within_device(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, SeenLists seen, const int32_t *cand,
+                       int n_cand, const int64_t *xoff, const int32_t *xit, int n, size_t extra, Tiles &&tiles,
+                       Then &&then) {
   const RecSession &rc = *c->rc;
   const int NI = rc.items, rank = rc.rank, S = rc.slots;
   const int C = cand ? n_cand : NI;
@@ -411,23 +417,49 @@ void rec_within_device(mmsbm_hip_ctx *c, const double *x, size_t xs, int64_t n_u
   CatTable ct;
   if (xoff) own.upload(xoff, xit, n_users, st);
   if (cand) cat_table(c, cand, C, ct);
+  const double *y = cand ? ct.y.ptr : rc.y.ptr;
+  const size_t ys = cand ? ycs : static_cast<size_t>(NI) * rank;
   top_n_device(c, C, n_users, users, n,
                cand || xoff ? "recommend: a batch of users within the candidates" : "recommend: a batch of users", extra,
                [&](const int32_t *ub, int nb, int64_t b0, double *sc) {
-                 if (cand) {
-                   score_tiles(c, x, xs, ct.y.ptr, ycs, C, ub, nb, SeenLists{}, sc);
-                   if (seen.off)
+                 tiles(y, ys, C, ub, nb, sc);
+                 if (seen.off) {
+                   if (cand)
                      LAUNCH(cat_exclude_kernel, nb, kBlock, 0, st, ub, 0, seen.off, seen.items, ct.col.ptr, sc, static_cast<size_t>(C));
-                 } else {
-                   rec_score_batch(c, x, xs, ub, nb, seen, sc);
+                   else
+                     LAUNCH(rec_exclude_kernel, nb, kBlock, 0, st, ub, seen.off, seen.items, sc, static_cast<size_t>(C));
                  }
                  if (xoff) own_exclude_batch(st, own, b0, nb, ct.col.ptr, sc, static_cast<size_t>(C));
                },
                [&](const TopNDev &dev, EventPair &ev) { then(dev, ev, cand ? ct.cand.ptr : nullptr, ct.ms); });
 }
 
-// rec_within_device with the result copied to the host and the columns mapped to item ids there.  Without candidates
-// and own lists: rec_run.
+// rec_within_device's `tiles` of recommend_query: the scores of the rows of x (`slots` tables xs doubles apart)
+auto rec_tiles(mmsbm_hip_ctx *c, const double *x, size_t xs) {
+  return [=](const double *y, size_t ys, int C, const int32_t *ub, int nb, double *sc) {
+    score_tiles(c, x, xs, y, ys, C, ub, nb, SeenLists{}, sc);
+  };
+}
+
+// rec_within_device with the result copied to the host (top_n_blank done by the caller) and the columns mapped to item
+// ids there; the device time of the query's kernels goes to `timed`.  No column or no row: every row stays empty.
+template <class Tiles>
+void rec_within_run(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, SeenLists seen, const int32_t *cand,
+                    int n_cand, const int64_t *xoff, const int32_t *xit, int n, Tiles &&tiles, TimedCall timed,
+                    int32_t *items, double *scores, int32_t *counts) {
+  c->last_ms[timed] = 0.f;
+  if ((cand ? n_cand : c->rc->items) == 0 || n_users == 0) return;
+  rec_within_device(c, n_users, users, seen, cand, n_cand, xoff, xit, n, 0, tiles,
+                    [&](const TopNDev &dev, EventPair &ev, const int32_t *, float prep_ms) {
+                      top_n_copy_out(c, dev, ev, n_users, n, timed, items, scores, counts);
+                      c->last_ms[timed] += prep_ms;
+                    });
+  if (cand)  // columns -> item ids
+    for (size_t e = 0; e < static_cast<size_t>(n_users) * n; ++e)
+      if (items[e] >= 0) items[e] = cand[items[e]];
+}
+
+// rec_run within the candidates and without the query's own excluded items.  Without candidates and own lists: rec_run.
 void rec_run_within(mmsbm_hip_ctx *c, const double *x, size_t xs, int64_t n_users, const int32_t *users, SeenLists seen,
                     const int32_t *cand, int n_cand, const int64_t *xoff, const int32_t *xit, int n, int32_t *items,
                     double *scores, int32_t *counts) {
@@ -436,18 +468,8 @@ void rec_run_within(mmsbm_hip_ctx *c, const double *x, size_t xs, int64_t n_user
     return;
   }
   top_n_blank(n_users, n, items, scores, counts);
-  if ((cand ? n_cand : c->rc->items) == 0 || n_users == 0) {  // (no column to score: every row is empty)
-    c->last_ms[T_RECOMMEND] = 0.f;
-    return;
-  }
-  rec_within_device(c, x, xs, n_users, users, seen, cand, n_cand, xoff, xit, n, 0,
-                    [&](const TopNDev &dev, EventPair &ev, const int32_t *, float prep_ms) {
-                      top_n_copy_out(c, dev, ev, n_users, n, T_RECOMMEND, items, scores, counts);
-                      c->last_ms[T_RECOMMEND] += prep_ms;
-                    });
-  if (cand)  // columns -> item ids
-    for (size_t e = 0; e < static_cast<size_t>(n_users) * n; ++e)
-      if (items[e] >= 0) items[e] = cand[items[e]];
+  rec_within_run(c, n_users, users, seen, cand, n_cand, xoff, xit, n, rec_tiles(c, x, xs), T_RECOMMEND, items, scores,
+                 counts);
 }
 
 // The caller's theta rows [S][n_users][K] folded exactly as recommend_add folds a slot's own theta (x = theta, or
@@ -904,6 +926,66 @@ void recommend_query_groups(mmsbm_hip_ctx *c, int64_t n_groups, const int64_t *o
   }
 }
 
+// ---- ensemble-aware queries (ensemble.hpp) ------------------------------------------------------------------------------
+// rec_run_within with the score tile replaced by the aggregate over the restarts (rec_within_run: the same candidate
+// table, the same exclusions, the same batches and selection)
+void recommend_query_ensemble(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, int mode, double risk,
+                              const int32_t *cand, int n_cand, const int64_t *xoff, const int32_t *xit, int n,
+                              int32_t *items, double *scores, int32_t *counts) {
+  use_device(c);
+  const RecSession &rc = *c->rc;
+  top_n_blank(n_users, n, items, scores, counts);
+  rec_within_run(c, n_users, users, rc.seen_lists(), cand, n_cand, xoff, xit, n,
+                 [&](const double *y, size_t ys, int C, const int32_t *ub, int nb, double *sc) {
+                   const dim3 g(static_cast<unsigned>((C + kEnsTile - 1) / kEnsTile), static_cast<unsigned>((nb + kEnsTile - 1) / kEnsTile));
+                   auto tile = [&](auto kernel) {
+                     LAUNCH(kernel, g, kBlock, 0, c->stream, rc.x.ptr, rc.x_stride(), y, ys, ub, nb, C, rc.rank, rc.slots, risk, sc,
+                            static_cast<size_t>(C));
+                   };
+                   if (mode == MMSBM_HIP_ENSEMBLE_MIN) tile(ens_tile_kernel<kEnsMin>);
+                   else if (mode == MMSBM_HIP_ENSEMBLE_MAX) tile(ens_tile_kernel<kEnsMax>);
+                   else tile(ens_tile_kernel<kEnsLcb>);
+                 },
+                 T_ENSEMBLE, items, scores, counts);
+}
+
+void recommend_pair_spread(mmsbm_hip_ctx *c, int64_t n_pairs, const int32_t *users, const int32_t *items, double *stats,
+                           double *per_slot) {
+  use_device(c);
+  const RecSession &rc = *c->rc;
+  c->last_ms[T_ENSEMBLE] = 0.f;
+  if (n_pairs == 0) return;
+  const int S = rc.slots;
+  hipStream_t st = c->stream;
+  const int64_t per = ens_pairs_per_launch(n_pairs, S, per_slot != nullptr);
+  require_free_mem(static_cast<size_t>(per) * ens_pair_bytes(S, per_slot != nullptr), "recommend_pair_spread: a batch of pairs");
+  DevBuf<int32_t> du, di;
+  DevBuf<double> ds, dp;
+  du.alloc(static_cast<size_t>(per));
+  di.alloc(static_cast<size_t>(per));
+  ds.alloc(static_cast<size_t>(per) * 4);
+  if (per_slot) dp.alloc(static_cast<size_t>(per) * S);
+  float ms = 0.f;  // device time of the call's kernels (option "ensemble_ms")
+  for (int64_t p0 = 0; p0 < n_pairs; p0 += per) {
+    const int64_t np = std::min(per, n_pairs - p0);
+    HIP_CHECK(hipMemcpyAsync(du.ptr, users + p0, sizeof(int32_t) * np, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(di.ptr, items + p0, sizeof(int32_t) * np, hipMemcpyHostToDevice, st));
+    EventPair ev;
+    ev.start(st);
+    LAUNCH(ens_pairs_kernel, static_cast<unsigned>((np + kBlock - 1) / kBlock), kBlock, 0, st, rc.x.ptr, rc.x_stride(),
+           rc.y.ptr, static_cast<size_t>(rc.items) * rc.rank, rc.rank, S, du.ptr, di.ptr, np, ds.ptr, dp.ptr);
+    HIP_CHECK(hipGetLastError());
+    ev.stop(st);
+    HIP_CHECK(hipMemcpyAsync(stats + p0 * 4, ds.ptr, sizeof(double) * np * 4, hipMemcpyDeviceToHost, st));
+    for (int s = 0; s < S && per_slot; ++s)  // the batch's [S][np] into the caller's [S][n_pairs]
+      HIP_CHECK(hipMemcpyAsync(per_slot + static_cast<size_t>(s) * n_pairs + p0, dp.ptr + static_cast<size_t>(s) * np,
+                               sizeof(double) * np, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    ms += ev.ms();
+  }
+  c->last_ms[T_ENSEMBLE] = ms;
+}
+
 // ---- nearest items / users (similar.hpp) ------------------------------------------------------------------------------
 void similar_begin(mmsbm_hip_ctx *c, int side) {
   use_device(c);
@@ -1019,7 +1101,8 @@ void recommend_diverse(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, 
     }
     const size_t outs = static_cast<size_t>(nb) * n;
     rec_within_device(
-        c, rc.x.ptr, rc.x_stride(), nb, users + b0, seen, cand, n_cand, xoff ? sub.data() : nullptr, xoff ? xit + xoff[b0] : nullptr, pool, outs * 20 + static_cast<size_t>(nb) * 4,
+        c, nb, users + b0, seen, cand, n_cand, xoff ? sub.data() : nullptr, xoff ? xit + xoff[b0] : nullptr, pool,
+        outs * 20 + static_cast<size_t>(nb) * 4, rec_tiles(c, rc.x.ptr, rc.x_stride()),
         [&](const TopNDev &dev, EventPair &ev, const int32_t *dcand, float prep_ms) {
           DevBuf<int32_t> ri, rn;
           DevBuf<double> rs, rd;

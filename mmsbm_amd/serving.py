@@ -993,6 +993,83 @@ class Serving:
                 lambda b, e: ctx.recommend_query_groups(*group_slice(lists, b, e), n, mode, bar or 0.0, cand),
                 n, labels, items, self._GROUP_COLUMNS)
 
+    # ------------------------------------------------------------------ how far the restarts agree (not in the reference)
+    _ROBUST_AGGREGATES = {"lcb": "lcb", "worst": "min", "best": "max"}   # -> HipEM.ENSEMBLE_MODES
+
+    def recommend_robust(self, users=None, n=10, aggregate="lcb", risk=1.0, exclude_seen=True, weights=None,
+                         candidates=None, exclude=None):
+        """``recommend`` that knows the model is an ensemble: ``fit`` keeps every restart, and ``recommend`` ranks by the
+        mean over them -- a pair every restart scores 4.6 and a pair three restarts score 5 and one 3.4 get the same
+        number.  Here the value of a pair is formed on the device from the score each restart ALONE gives it
+        (``recommend``'s score in a model of that one restart), by ``aggregate``:
+
+        ``"lcb"``    mean - ``risk`` x std over the restarts (population std) -- a lower confidence bound: ``risk`` > 0
+                     prefers the items the restarts agree on, 0 ranks by the mean, < 0 explores where they disagree;
+        ``"worst"``  the LOWEST score any restart gives the pair;
+        ``"best"``   the HIGHEST.
+
+        ``risk`` (finite) belongs to ``"lcb"`` and is refused with the others unless left at its default.  Candidates,
+        ``exclude_seen``, ``weights``, ``candidates`` and ``exclude`` as in ``recommend``.  Order: value descending,
+        equal values by ascending encoded item id.  A model of one restart answers as ``recommend``.
+
+        Returns ``recommend``'s frame -- ``score`` is the aggregate -- plus ``mean`` and ``std`` of every returned pair:
+        columns ``users``, ``items``, ``score``, ``mean``, ``std``, ``rank``.  ``score_spread`` gives the same numbers
+        for pairs of the caller's choice.  The model's stored predictions and ``score()`` are left as they are."""
+        self._check_whole_model()
+        n, w = self._recommend_args(n, weights)
+        if aggregate not in self._ROBUST_AGGREGATES:
+            raise ValueError(f"aggregate must be one of {list(self._ROBUST_AGGREGATES)}, got {aggregate!r}")
+        risk = check_finite(risk, "risk")
+        if aggregate != "lcb" and risk != 1.0:
+            raise ValueError(f'risk belongs to aggregate="lcb", not to {aggregate!r}')
+        mode = self._ROBUST_AGGREGATES[aggregate]
+        ids, labels = self._side("users").request(users)
+        items = self._side("items")
+        columns = ("users", "items", "score", "mean", "std")
+        cand = self._candidate_ids(candidates)
+        if cand is not None and len(cand) == 0:
+            return self._top_n_frame(None, n, labels[:0], items, columns)
+        extra = self._exclusion_lists(exclude, ids)
+        with self._session_of_restarts("recommend", w, exclude_seen) as ctx:
+            def query(b, e):
+                its, scores, counts = ctx.recommend_query_ensemble(ids[b:e], n, mode, risk, cand, group_slice(extra, b, e))
+                keep = np.arange(n)[None, :] < counts[:, None]
+                stats = ctx.recommend_pair_spread(np.repeat(ids[b:e], counts), its[keep])   # the returned pairs
+                mean, std = np.full(its.shape, np.nan), np.full(its.shape, np.nan)
+                mean[keep], std[keep] = stats[:, 0], stats[:, 1]
+                return its, scores, mean, std, counts
+            return self._top_n_frame(query, n, labels, items, columns)
+
+    def score_spread(self, pairs, weights=None, per_restart=False):
+        """How far the restarts agree about given (user, item) pairs, on the device: the score each restart alone gives
+        the pair (``recommend``'s score in a model of that one restart), summarised over the restarts.
+
+        ``pairs``: a DataFrame whose first two columns are users and items (further columns are ignored, so
+        ``model.score_spread(model.recommend(users=[...]))`` works as is), or an iterable of (user, item) tuples; both
+        must be in the training data (KeyError).  Returns a DataFrame with columns ``users``, ``items``, ``mean``,
+        ``std`` (population form), ``worst``, ``best`` -- the numbers ``recommend_robust`` ranks by, bit for bit -- and,
+        with ``per_restart``, ``restart_0``, ``restart_1``, ... in ``self.results`` order; pairs in request order,
+        labels as ``recommend`` returns them.  The model's stored predictions and ``score()`` are left as they are."""
+        self._check_whole_model()
+        w = self._rating_weights(weights)
+        us, its = self._pair_columns(pairs)
+        uid, ulab = self._side("users").request(us)
+        iid, ilab = self._side("items").request(its)
+        step = self.RECOMMEND_BATCH_ROWS
+        stats, each = [np.zeros((0, 4))], []
+        with self._session_of_restarts("recommend", w, False) as ctx:
+            for s in range(0, len(uid), step):
+                got = ctx.recommend_pair_spread(uid[s:s + step], iid[s:s + step], per_restart)
+                stats.append(got[0] if per_restart else got)
+                if per_restart:
+                    each.append(got[1])
+        stats = np.concatenate(stats)
+        out = {"users": ulab, "items": ilab, **{c: stats[:, j] for j, c in enumerate(("mean", "std", "worst", "best"))}}
+        if per_restart:
+            rows = np.concatenate(each, axis=1) if each else np.zeros((len(self.results), 0))
+            out.update({f"restart_{s}": rows[s] for s in range(len(rows))})
+        return pd.DataFrame(out)
+
     # ------------------------------------------------------------------ which items to ask about (not in the reference)
     _GAIN_COLUMNS = ("users", "items", "gain")
 
