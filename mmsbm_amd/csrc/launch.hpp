@@ -24,18 +24,21 @@ void stage_fused_pairs(mmsbm_hip_ctx *c);
 void stage_fused_tail(mmsbm_hip_ctx *c, bool commit);
 // ... and the two triple passes with the T + S stage of a committed iteration in one launch (pass_dense.hpp)
 void stage_pass_dense(mmsbm_hip_ctx *c);
-// tu_once.hip -- once-per-run kernels.  likelihood of the selected slot (the caller holds a OneSlot): kernels onto the
-// context's stream, no wait; returns the number of partial sums in lik_part
+// tu_once.hip -- once-per-run kernels, with the host side of the entries that run them.  likelihood of the selected slot
+// (the caller holds a OneSlot): likelihood_enqueue puts the kernels onto the context's stream without waiting and returns
+// the number of partial sums in lik_part; likelihood_finish fetches them and adds them up in workgroup order
 int likelihood_enqueue(mmsbm_hip_ctx *c);
+double likelihood_finish(mmsbm_hip_ctx *c, int n_parts);
 void init_rows_launch(mmsbm_hip_ctx *c, const uint64_t pcg64_state[4]);
-void omegas_launch(mmsbm_hip_ctx *c, double *dev_out, int64_t n_elems);
-void prod_dist_launch(mmsbm_hip_ctx *c, const int32_t *du, const int32_t *di, double *dout, int64_t n_pairs);
-// B = p_r eta_i over every (item, rating) combination, then one group of lanes per row.
-// mode 0: dist[m][r] = P[m, r];  mode 1: dist += P, block_out = the restart's six sums per workgroup
-int rows_launch(mmsbm_hip_ctx *c, int mode, const int32_t *pu, const int32_t *pi, const int32_t *preal,
-                const double *weights, double *dist, double *block_out, int64_t n_rows, int first);
-int score_rows_launch(mmsbm_hip_ctx *c, bool finish);  // the per-row scoring kernels; returns the number of workgroups
-int score_stats_count();
+// ... the selected slot (the caller holds a OneSlot), arguments checked: omega[n,k,l] in the caller's orientation;
+// P[m, r] of n_pairs (user, item) rows; the predict session of mmsbm_hip_predict_* (stats: the six sums of the slot
+// just added / of the mean; mean_dist: null or [rows][R])
+void compute_omegas(mmsbm_hip_ctx *c, double *out, int64_t n_elems);
+void prod_dist(mmsbm_hip_ctx *c, int64_t n_pairs, const int32_t *user, const int32_t *item, double *out);
+void predict_begin(mmsbm_hip_ctx *c, int64_t n_rows, const int32_t *user, const int32_t *item, const int32_t *rating,
+                   const double *rating_weights);
+void predict_add(mmsbm_hip_ctx *c, double *stats);
+void predict_finish(mmsbm_hip_ctx *c, double *mean_dist, double *stats);
 
 // tu_recommend.hip -- top-N recommendation (recommend.hpp): the session of mmsbm_hip_recommend_*, arguments checked
 // MMSBM_E_TOOLARGE "<what> needs ... MB of device memory" unless `bytes` (plus 64 MB) are free (fold-in too)
@@ -131,17 +134,62 @@ void explain_query(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, cons
                    int n, int32_t *hist_items, int32_t *hist_ratings, double *contribution, int32_t *counts,
                    double *explained, double *score, int32_t *degree);
 
-// dispatchers (mmsbm_hip.hip): the form the context's shape and options select
+// tu_iterate.hip -- the EM iteration: the form the context's shape and options select, its order of launches, the
+// cur / a_ok / graph_exec state machine, and the timers.  Dispatchers first:
 void stage_dense(mmsbm_hip_ctx *c);
 void stage_matvec_a(mmsbm_hip_ctx *c, int slot, int a_slot, bool grid = false);
 void ensure_a(mmsbm_hip_ctx *c);  // atab[cur] = A of the current parameters, for every slot the next launches cover
+// the two-launch form of small problems: its kernels exist for the shape; ... and the data's segments are whole inside a
+// workgroup; the size up to which create() builds its lists and turns it on
+bool fused_shape_ok(const mmsbm_hip_ctx *c);
+bool fused_possible(const mmsbm_hip_ctx *c);
+constexpr long long kFusedRatingsMax = 1500000;
+// the form the next (committed) iteration takes: two launches; the triple passes and T + S in one (three launches)
+bool use_fused(const mmsbm_hip_ctx *c);
+bool use_pass_dense(const mmsbm_hip_ctx *c);
+// one iteration of the slots [base_slot, base_slot + launch_slots); commit off: the raw numerators stay in the other
+// buffers and cur does not move (update_coefficients).  run_iterations: n committed ones, replayed from a captured
+// graph two at a time when "graph" is on
+void launch_iteration(mmsbm_hip_ctx *c, bool commit);
+void run_iterations(mmsbm_hip_ctx *c, int n);
+// the matrix-core A launch's own runs of `units` 64-pair units per workgroup (0: balanced against the CUs)
+void build_a_runs(mmsbm_hip_ctx *c, int units);
+// the bodies of mmsbm_hip_time_iterations / profile_iterations / kernel_bytes / time_stage, parameters present
+float time_iterations(mmsbm_hip_ctx *c, int n_iters);
+void profile_iterations(mmsbm_hip_ctx *c, int n_iters, float *mean_us, int *launches_per_iter);
+void kernel_bytes(const mmsbm_hip_ctx *c, int index, int64_t *bytes_read, int64_t *bytes_written);
+void time_stage(mmsbm_hip_ctx *c, int stage, int reps, float *mean_us);
 
-// ---- launch log (MMSBM_HIP_LAUNCH_LOG=<file>; mmsbm_hip.hip) ---------------------------------------------------------
+// tu_create.hip -- building a context (arguments and device index checked), the per-restart state, the index read-back
+mmsbm_hip_ctx *context_create(int device, int64_t n_obs, int32_t n_users, int32_t n_items, int32_t n_ratings,
+                              int32_t k_groups, int32_t l_groups, const int32_t *user, const int32_t *item,
+                              const int32_t *rating, int swap_sides);
+void set_slots(mmsbm_hip_ctx *c, int n_slots);  // drops every slot's parameters and the snapshots, selects slot 0
+// which: 0 .. 18 (mmsbm_hip_index_array); count always, out (of `capacity` int32) when not null
+void index_array(mmsbm_hip_ctx *c, int which, int32_t *out, int64_t capacity, int64_t *count);
+
+// tu_params.hip -- parameters in and out, host layout (K, L, R) / external sides <-> the device's tables; the selected
+// slot (the caller holds a OneSlot where the entry's launches need one), arguments checked
+void set_params(mmsbm_hip_ctx *c, const double *theta, const double *eta, const double *pr);
+void init_params(mmsbm_hip_ctx *c, const uint64_t pcg64_state[4], const double *pr);
+void get_params(mmsbm_hip_ctx *c, double *theta, double *eta, double *pr);
+void update_coefficients(mmsbm_hip_ctx *c, double *n_theta, double *n_eta, double *n_pr);  // one uncommitted iteration
+void fetch_result(mmsbm_hip_ctx *c, double *theta, double *eta, double *pr, double *likelihood);
+void snapshot_save(mmsbm_hip_ctx *c);
+void snapshot_get(mmsbm_hip_ctx *c, double *theta, double *eta, double *pr);
+
+// tu_options.hip -- the option table behind mmsbm_hip_set_option / get_option; an unknown (set: or read-only) name is
+// std::invalid_argument "unknown option: <name>".  A successful set drops the captured graphs
+void set_option(mmsbm_hip_ctx *c, const std::string &name, double value);
+double get_option(const mmsbm_hip_ctx *c, const std::string &name);
+
+// ---- launch log (MMSBM_HIP_LAUNCH_LOG=<file>; tu_iterate.hip) --------------------------------------------------------
 // Host-side only: which kernel instantiations a process launched, how often, and under which test
 // (MMSBM_HIP_LAUNCH_TAG at a kernel's first launch).  Appended to the file when a context is destroyed and at exit;
 // scripts/kernel_coverage.py diffs it against the compiled set.  Nothing in the kernels knows about it.
 extern bool g_launch_log_on;
 void launch_log_note(const void *host_fn);
+void launch_log_flush();
 
 }  // namespace mmsbm_hip_impl
 
@@ -202,6 +250,12 @@ inline RowTab a_tab(const mmsbm_hip_ctx *c, int b) {
 }
 inline dim3 slot_grid(const mmsbm_hip_ctx *c, int blocks) {
   return dim3(static_cast<unsigned>(blocks), static_cast<unsigned>(c->launch_slots), 1);
+}
+// A pair of arguments given by external side, (users' side, items' side) -- theta and eta, the user and the item id
+// column -- as (internal users' side, internal items' side): exchanged in a swapped context
+template <class T>
+inline std::pair<T *, T *> internal_sides(const mmsbm_hip_ctx *c, T *users_side, T *items_side) {
+  return c->swapped ? std::make_pair(items_side, users_side) : std::make_pair(users_side, items_side);
 }
 // Single-restart entry points: launches and copies cover the selected slot only.
 struct OneSlot {

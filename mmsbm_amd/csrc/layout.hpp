@@ -301,7 +301,7 @@ constexpr int32_t kMvChunkPairs = 64;  // default: one 64-pair unit per workgrou
 // lands on the same XCD (workgroups are dealt to the 8 XCDs round-robin), and the rows of an item, which its R (item,
 // rating) pairs all gather, are served to R - 1 of them by that XCD's L2.  (Speed only: an empty chunk's workgroup
 // writes a zero slab and nothing else.)  The ONE statement of the rule: build_mv_chunks builds by it and the cost model
-// of the matrix-core A launch (mmsbm_hip.hip: balanced_run_units) counts by it.
+// of the matrix-core A launch (tu_iterate.hip: balanced_run_units) counts by it.
 inline bool chunk_align_on() { return std::getenv("MMSBM_HIP_NO_CHUNK_ALIGN") == nullptr; }
 inline int64_t padded_chunk_count(int64_t rating_pairs, int32_t pairs, int32_t n_ratings, bool align) {
   const int64_t chunks = (rating_pairs + pairs - 1) / pairs;

@@ -2,14 +2,19 @@
 //
 // The library is built from several translation units compiled side by side (mmsbm_amd/build.py) and linked into one
 // shared object:
-//   mmsbm_hip.hip  the C ABI, the context, the iteration's order of launches
+//   mmsbm_hip.hip  the C ABI: argument checks and one call into the unit that owns the work
+//   tu_create.hip  building a context: the shape plan, the index and its uploads, the per-restart state
+//   tu_params.hip  parameters in and out: the host's arrays <-> the device's padded, split tables; snapshots
+//   tu_iterate.hip the EM iteration: its form, its order of launches, graph replay, the timers; the launch log
+//   tu_options.hip the option table
 //   tu_seg.hip     the two triple passes (seg_pass.hpp)
 //   tu_pair.hip    the pair stage on the vector ALUs (pair_block.hpp, pair_quad.hpp)
 //   tu_mfma.hip    the pair stage on the matrix cores (pair_mfma.hpp)
 //   tu_etap.hip    eta_p (eta_p.hpp)
 //   tu_fused.hip   the two-launch iteration of small problems (fused_small.hpp); the triple passes with the T + S stage
 //                  in one launch (pass_dense.hpp)
-//   tu_once.hip    once-per-run kernels: likelihood, prod_dist / predict, omegas, the random start
+//   tu_once.hip    once-per-run kernels with the host side of their entries: likelihood, prod_dist / predict, omegas,
+//                  the random start
 //   tu_layout.hip  the layout's sorts on the device (rocPRIM)
 //   tu_recommend.hip  the serving queries, planned by serve_plan.hpp, one header of kernels each:
 //                       recommend.hpp  top-N recommendation        similar.hpp    nearest items / users

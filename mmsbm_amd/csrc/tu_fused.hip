@@ -66,7 +66,7 @@ void stage_fused_tail(mmsbm_hip_ctx *c, bool commit) {
 }
 
 // The two triple passes and the T + S stage of a committed iteration as one launch (pass_dense.hpp); the caller has
-// checked that the form applies (mmsbm_hip.hip: use_pass_dense).  Timed as stage K_SEG; K_DENSE then has no launch.
+// checked that the form applies (tu_iterate.hip: use_pass_dense).  Timed as stage K_SEG; K_DENSE then has no launch.
 void stage_pass_dense(mmsbm_hip_ctx *c) {
   LaunchScope ls(c, K_SEG, true);
   const int s = c->base_slot, cur = c->cur, nt = nt_on(c);

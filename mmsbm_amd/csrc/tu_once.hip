@@ -1,5 +1,6 @@
 // tu_once.hip -- translation unit of the once-per-run kernels (once_kernels.hpp, lik_fact.hpp): the likelihood in its
-// forms, prod_dist / predict / score, compute_omegas, the random start -- with the host code that chooses among them
+// forms, prod_dist / predict / score, compute_omegas, the random start -- with the host code that chooses among them and
+// the host side of their entries (uploads, the predict session, the B table of the fast path, results back)
 #include "prelude.hpp"
 #include "pcg64.hpp"
 #include "once_kernels.hpp"
@@ -195,6 +196,39 @@ int likelihood_enqueue(mmsbm_hip_ctx *ctx) {
   return nb;
 }
 
+double likelihood_finish(mmsbm_hip_ctx *ctx, int nb) {  // workgroup sums added in workgroup order
+  std::vector<double> part(nb);
+  HIP_CHECK(hipMemcpyAsync(part.data(), ctx->lik_part.ptr, sizeof(double) * nb, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  double tot = 0.0;
+  for (double v : part) tot += v;
+  return tot;
+}
+
+// theta0 / eta0 of the selected slot drawn on the device from the restart's PCG64 stream (pcg64.hpp)
+void init_rows_launch(mmsbm_hip_ctx *ctx, const uint64_t pcg64_state[4]) {
+  const int cur = ctx->cur;
+  // the reference draws theta (external users x K) first, then eta; internally the two sides
+  // may be swapped, the stream offsets are not
+  const uint64_t n_theta_ext = static_cast<uint64_t>(ctx->ext_users) * ctx->ext_k;
+  const uint64_t off_users = ctx->swapped ? n_theta_ext : 0;  // internal users' table
+  const uint64_t off_items = ctx->swapped ? 0 : n_theta_ext;
+  const RowTab tt = theta_tab(ctx, cur), et = eta_tab(ctx, cur);
+  auto blocks = [](uint64_t total) {
+    return static_cast<unsigned>((total + uint64_t(kBlock) * kDrawsPerThread - 1) / (uint64_t(kBlock) * kDrawsPerThread));
+  };
+  const uint64_t nu = static_cast<uint64_t>(ctx->n_users) * ctx->k, ni = static_cast<uint64_t>(ctx->n_items) * ctx->l;
+  if (nu > 0)
+    LAUNCH(init_rows_kernel, blocks(nu), kBlock, 0, ctx->stream, tt, ctx->user_off.ptr, nullptr, ctx->n_users, ctx->k,
+           pcg64_state[0], pcg64_state[1], pcg64_state[2], pcg64_state[3], off_users);
+  if (ni > 0)
+    LAUNCH(init_rows_kernel, blocks(ni), kBlock, 0, ctx->stream, et, nullptr, ctx->item_deg.ptr, ctx->n_items, ctx->l,
+           pcg64_state[0], pcg64_state[1], pcg64_state[2], pcg64_state[3], off_items);
+  HIP_CHECK(hipGetLastError());
+}
+
+namespace {
+
 // B for the selected slot (the caller holds a OneSlot and rows_fast_prepare said yes), then one group of
 // lanes per row.
 // mode 0: dist[m][r] = P[m, r];  mode 1: dist += P, block_out = the restart's six sums per workgroup
@@ -239,30 +273,6 @@ int score_rows_launch(mmsbm_hip_ctx *ctx, bool finish) {
   HIP_CHECK(hipGetLastError());
   return nb;
 }
-int score_stats_count() { return kScoreStats; }
-
-// theta0 / eta0 of the selected slot drawn on the device from the restart's PCG64 stream (pcg64.hpp)
-void init_rows_launch(mmsbm_hip_ctx *ctx, const uint64_t pcg64_state[4]) {
-  const int cur = ctx->cur;
-  // the reference draws theta (external users x K) first, then eta; internally the two sides
-  // may be swapped, the stream offsets are not
-  const uint64_t n_theta_ext = static_cast<uint64_t>(ctx->ext_users) * ctx->ext_k;
-  const uint64_t off_users = ctx->swapped ? n_theta_ext : 0;  // internal users' table
-  const uint64_t off_items = ctx->swapped ? 0 : n_theta_ext;
-  const RowTab tt = theta_tab(ctx, cur), et = eta_tab(ctx, cur);
-  auto blocks = [](uint64_t total) {
-    return static_cast<unsigned>((total + uint64_t(kBlock) * kDrawsPerThread - 1) / (uint64_t(kBlock) * kDrawsPerThread));
-  };
-  const uint64_t nu = static_cast<uint64_t>(ctx->n_users) * ctx->k, ni = static_cast<uint64_t>(ctx->n_items) * ctx->l;
-  if (nu > 0)
-    LAUNCH(init_rows_kernel, blocks(nu), kBlock, 0, ctx->stream, tt, ctx->user_off.ptr, nullptr, ctx->n_users, ctx->k,
-           pcg64_state[0], pcg64_state[1], pcg64_state[2], pcg64_state[3], off_users);
-  if (ni > 0)
-    LAUNCH(init_rows_kernel, blocks(ni), kBlock, 0, ctx->stream, et, nullptr, ctx->item_deg.ptr, ctx->n_items, ctx->l,
-           pcg64_state[0], pcg64_state[1], pcg64_state[2], pcg64_state[3], off_items);
-  HIP_CHECK(hipGetLastError());
-}
-
 // omega[n,k,l] of the selected slot into dev_out (n_elems = N K L), in the caller's (external) orientation
 void omegas_launch(mmsbm_hip_ctx *ctx, double *dev_out, int64_t n_elems) {
   const int cur = ctx->cur, sl = ctx->sel;
@@ -287,6 +297,134 @@ void prod_dist_launch(mmsbm_hip_ctx *ctx, const int32_t *du, const int32_t *di, 
          du, di, theta_tab(ctx, cur), ctx->eta[cur].at(sl), ctx->p[cur].at(sl), dout,
          n_pairs, ctx->n_ratings, ctx->k, ctx->l, ctx->kp, ctx->lp);
   HIP_CHECK(hipGetLastError());
+}
+
+// ---- prod_dist / predict through B = p_r eta_i over every (item, rating) combination ---------------
+// Worth it when the rows to score are not far fewer than the items (B costs I R K L multiply-adds, a row
+// then R K instead of R K L) and B fits comfortably: otherwise the per-row kernels run.
+bool rows_fast_ok(const mmsbm_hip_ctx *c, int64_t n_rows) {
+  if (!c->predict_fast || n_rows <= 0) return false;
+  const uint64_t combos = static_cast<uint64_t>(c->n_items) * static_cast<uint64_t>(c->n_ratings);
+  if (combos >= (uint64_t(1) << 31) - 2048 || n_rows * 4 < c->n_items) return false;
+  size_t free_b = 0, total_b = 0;
+  if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return false;
+  return combos * static_cast<uint64_t>(c->kp) * sizeof(double) <= (free_b + c->btab.count * sizeof(double)) / 2;
+}
+void ensure_pair_grid(mmsbm_hip_ctx *c) {  // q = r * I + i, chunks of the pair stage's size per rating
+  const size_t combos = static_cast<size_t>(c->n_items) * c->n_ratings;
+  if (c->grid_item.count != combos || c->grid_n_chunks == 0) {
+    std::vector<int32_t> item(combos);
+    std::vector<mmsbm::Chunk> chunks;
+    for (int r = 0; r < c->n_ratings; ++r) {
+      const int32_t base = static_cast<int32_t>(static_cast<size_t>(r) * c->n_items);
+      for (int i = 0; i < c->n_items; ++i) item[static_cast<size_t>(base) + i] = i;
+      for (int i = 0; i < c->n_items; i += c->pp.chunk_pairs)
+        chunks.push_back(mmsbm::Chunk{r, base + i, base + std::min(i + c->pp.chunk_pairs, c->n_items), 0});
+    }
+    c->grid_item.upload(item, c->stream);
+    c->grid_chunks.upload(chunks, c->stream);
+    HIP_CHECK(hipStreamSynchronize(c->stream));  // (host vectors are locals)
+    c->grid_n_chunks = static_cast<int>(chunks.size());
+  }
+  if (c->btab.count < combos * c->kp) c->btab.alloc(combos * c->kp);
+}
+// eligibility + the table's memory; false (and no error left behind) sends the caller to the per-row kernels
+bool rows_fast_prepare(mmsbm_hip_ctx *c, int64_t n_rows) {
+  if (!rows_fast_ok(c, n_rows)) return false;
+  try {
+    ensure_pair_grid(c);
+  } catch (const ApiError &) {  // out of memory after all (another context took it): not an error of this call
+    (void)hipGetLastError();
+    c->btab.release();
+    return false;
+  }
+  return true;
+}
+
+// the open session's rows scored under the selected slot (finish: its mean), the six sums of the workgroups added up
+void score_launch(mmsbm_hip_ctx *ctx, bool finish, double *stats) {
+  const int n_stats = kScoreStats;
+  PredictSession &ps = *ctx->ps;
+  const bool fast = !finish && rows_fast_prepare(ctx, ps.rows);
+  const int per_block = fast ? kBlock / group_lanes(ctx->code_k) : kBlock;
+  const int nb = static_cast<int>((ps.rows + per_block - 1) / per_block);
+  if (ps.part.count < static_cast<size_t>(nb) * n_stats) ps.part.alloc(static_cast<size_t>(nb) * n_stats);
+  if (nb > 0 && fast)
+    rows_launch(ctx, 1, ps.u.ptr, ps.i.ptr, ps.r.ptr, ps.w.ptr, ps.sum.ptr, ps.part.ptr, ps.rows, ps.slots == 0 ? 1 : 0);
+  else if (nb > 0)
+    score_rows_launch(ctx, finish);
+  std::vector<double> part(static_cast<size_t>(nb) * n_stats);
+  if (nb > 0)
+    HIP_CHECK(hipMemcpyAsync(part.data(), ps.part.ptr, sizeof(double) * part.size(), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  for (int j = 0; j < n_stats; ++j) stats[j] = 0.0;
+  for (int b = 0; b < nb; ++b)
+    for (int j = 0; j < n_stats; ++j) stats[j] += part[static_cast<size_t>(b) * n_stats + j];
+}
+
+}  // namespace
+
+void compute_omegas(mmsbm_hip_ctx *ctx, double *out, int64_t n_elems) {
+  DevBuf<double> dev;
+  dev.alloc(static_cast<size_t>(n_elems));
+  omegas_launch(ctx, dev.ptr, n_elems);
+  HIP_CHECK(hipMemcpyAsync(out, dev.ptr, sizeof(double) * n_elems, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_CHECK(hipStreamSynchronize(ctx->stream));
+}
+
+void prod_dist(mmsbm_hip_ctx *ctx, int64_t n_pairs, const int32_t *user, const int32_t *item, double *out) {
+  const int64_t n_elems = n_pairs * ctx->n_ratings;
+  if ((n_elems + kBlock - 1) / kBlock > (int64_t(1) << 31) - 1)
+    throw ApiError(MMSBM_E_TOOLARGE, "prod_dist: too many pairs for one launch");
+  DevBuf<int32_t> du, di;
+  DevBuf<double> dout;
+  du.alloc(n_pairs); di.alloc(n_pairs); dout.alloc(n_elems);
+  const auto [iu, ii] = internal_sides(ctx, user, item);
+  HIP_CHECK(hipMemcpyAsync(du.ptr, iu, sizeof(int32_t) * n_pairs, hipMemcpyHostToDevice, ctx->stream));
+  HIP_CHECK(hipMemcpyAsync(di.ptr, ii, sizeof(int32_t) * n_pairs, hipMemcpyHostToDevice, ctx->stream));
+  if (rows_fast_prepare(ctx, n_pairs)) rows_launch(ctx, 0, du.ptr, di.ptr, nullptr, nullptr, dout.ptr, nullptr, n_pairs, 1);
+  else prod_dist_launch(ctx, du.ptr, di.ptr, dout.ptr, n_pairs);
+  HIP_CHECK(hipMemcpyAsync(out, dout.ptr, sizeof(double) * n_elems, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  ctx->btab.release();  // (the B table is scratch: restart slots are sized from the free memory)
+}
+
+void predict_begin(mmsbm_hip_ctx *ctx, int64_t n_rows, const int32_t *user, const int32_t *item, const int32_t *rating,
+                   const double *rating_weights) {
+  ctx->ps.reset();  // (arguments are fine: from here on the previous session is gone)
+  auto ps = std::make_unique<PredictSession>();
+  const auto [iu, ii] = internal_sides(ctx, user, item);
+  hipStream_t s = ctx->stream;
+  ps->u.alloc(n_rows); ps->i.alloc(n_rows); ps->r.alloc(n_rows);
+  ps->sum.alloc(static_cast<size_t>(n_rows) * ctx->n_ratings);
+  ps->w.alloc(ctx->n_ratings);
+  if (n_rows > 0) {
+    HIP_CHECK(hipMemcpyAsync(ps->u.ptr, iu, sizeof(int32_t) * n_rows, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(ps->i.ptr, ii, sizeof(int32_t) * n_rows, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(ps->r.ptr, rating, sizeof(int32_t) * n_rows, hipMemcpyHostToDevice, s));
+  }
+  HIP_CHECK(hipMemcpyAsync(ps->w.ptr, rating_weights, sizeof(double) * ctx->n_ratings, hipMemcpyHostToDevice, s));
+  HIP_CHECK(hipStreamSynchronize(s));  // the caller's buffers are free again
+  ps->rows = n_rows;
+  ctx->ps = std::move(ps);
+}
+
+void predict_add(mmsbm_hip_ctx *ctx, double *stats) {
+  score_launch(ctx, false, stats);
+  ctx->ps->slots++;
+}
+
+void predict_finish(mmsbm_hip_ctx *ctx, double *mean_dist, double *stats) {
+  // the session is over on every way out of here, and its buffers go back: restart slots are sized from the free memory
+  struct Drop { mmsbm_hip_ctx *c; ~Drop() { c->ps.reset(); } } drop{ctx};
+  const PredictSession &ps = *ctx->ps;
+  score_launch(ctx, true, stats);
+  ctx->btab.release();
+  if (mean_dist && ps.rows > 0) {
+    HIP_CHECK(hipMemcpyAsync(mean_dist, ps.sum.ptr, sizeof(double) * ps.rows * ctx->n_ratings, hipMemcpyDeviceToHost,
+                             ctx->stream));
+    HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  }
 }
 
 }  // namespace mmsbm_hip_impl

@@ -6,6 +6,10 @@
 //
 // The product is NOT built from this file: mmsbm_amd/build.py compiles the units side by side and links them.
 #include "mmsbm_hip.hip"
+#include "tu_create.hip"
+#include "tu_params.hip"
+#include "tu_iterate.hip"
+#include "tu_options.hip"
 #include "tu_seg.hip"
 #include "tu_pair.hip"
 #include "tu_mfma.hip"

@@ -1,5 +1,5 @@
 """The matrix-core A launch on runs of A_UNITS 64-pair units per workgroup (option "a_units"; unset / 0: the library's own
-choice, mmsbm_hip.hip: balanced_run_units): the launch back to back and the whole iteration.
+choice, tu_iterate.hip: balanced_run_units): the launch back to back and the whole iteration.
 usage: [A_UNITS=7] python scripts/a_units_time.py c5 | N,U,I,R,K,L"""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

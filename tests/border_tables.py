@@ -24,7 +24,7 @@ UNIT = 64                  # layout.hpp: kMvChunkPairs / shapes.hpp: kUnitPairs
 XCDS = 8                   # layout.hpp: kXcds -- a populated rating's units are padded to a multiple of it (R > 1)
 SLAB_ROUND = 320           # eta_p.hpp: kRedRows * kRedBatch slabs of one rating per trip of p_update_block's `off` loop
 RED_GROUP = 6              # eta_p.hpp: kRedGroup ratings per LDS pass
-GRID_MAX_R = 16            # mmsbm_hip.hip: upload_item_grid
+GRID_MAX_R = 16            # tu_create.hip: upload_item_grid
 BLOCK = 256                # common.hpp: kBlock
 FUSED_SPLIT_LDS = 96 * 1024   # shapes.hpp: kFusedSplitLds
 

@@ -1,4 +1,4 @@
-"""numpy emulation of the DEVICE algorithm (the factorised form in mmsbm_hip.hip), driven by
+"""numpy emulation of the DEVICE algorithm (the factorised form tu_iterate.hip describes), driven by
 the layout arrays the library builds.  Test infrastructure: it lets the CPU suite check the
 re-association and the sorted layout against the oracle without a GPU."""
 import numpy as np

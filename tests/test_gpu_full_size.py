@@ -147,7 +147,7 @@ def test_c5_shape_with_the_chunk_sizes_full_size_c5_runs(hip, c5_shape, chunk, m
 
 def test_the_a_launch_walks_runs_of_its_own_and_gives_the_same_rows(hip, c5_shape, monkeypatch):
     """The matrix-core A launch writes rows only, so it walks the units in runs of its own length, chosen so that its last
-    round of workgroups is (nearly) full (mmsbm_hip.hip: balanced_run_units; C5: 11 units where the T + S launch takes 8).
+    round of workgroups is (nearly) full (tu_iterate.hip: balanced_run_units; C5: 11 units where the T + S launch takes 8).
     A rows do not depend on which workgroup computes them: theta / eta / p after three iterations are BITWISE the same
     for runs of 1, 3 and 16 units (ragged last runs, empty padding runs) as for the T + S launch's own 4-unit chunks --
     and every entry agrees with the dense oracle as in the tests above."""
