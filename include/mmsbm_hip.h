@@ -571,6 +571,61 @@ int mmsbm_hip_explain_query(mmsbm_hip_ctx *ctx, int64_t n_users, const int32_t *
                             double *contribution, int32_t *counts, double *explained, double *score, int32_t *degree);
 int mmsbm_hip_explain_end(mmsbm_hip_ctx *ctx);
 
+/* ---- which training rows look wrong: leave-one-out reliability (mmsbm_amd/csrc/loo.hpp) ---------------------------- */
+/* The probability of every training row under parameters that never saw it.  The M-step writes theta_u as the average
+ * of its rows' shares (the identity explain rests on) and eta_i likewise, so one EM step without row j is a downdate
+ * of two sums.  Per added slot, in EXTERNAL k, l, r, for training row j = (u, i, r) with that slot's theta, eta, p:
+ *   v_j[k] = sum_l p[k,l,r] eta[i,l]         one fma chain over l ascending from +0.0 (fold-in's v)
+ *   w_j[l] = sum_k p[k,l,r] theta[u,k]       one fma chain over k ascending from +0.0
+ *   fit_j  = sum_k theta[u,k] v_j[k]         one fma chain over k ascending from +0.0 (the in-sample probability: the
+ *                                            P_s(m) of mmsbm_hip_heldout_add, bit for bit)
+ *   inv    = 1 / max(fit_j, eps)             ONE division, eps = DBL_EPSILON
+ *   c_j[k] = (theta[u,k] v_j[k]) inv         e_j[l] = (eta[i,l] w_j[l]) inv
+ *   C_u = sum_{j in u} c_j    E_i = sum_{j in i} e_j    (the n_theta / n_eta of mmsbm_hip_update_coefficients)
+ *   theta-[k] = max(C_u[k] - c_j[k], 0) / (d_u - 1);  d_u = 1: theta-bar[k], the mean theta row over the U users
+ *   eta-[l]   = max(E_i[l] - e_j[l], 0) / (d_i - 1);  d_i = 1: eta-bar[l], the mean eta row over the I items
+ *   rel_j = sum_k theta-[k] (sum_l p[k,l,r] eta-[l])  inner fma chain over l, outer fma chain over k, from +0.0
+ * p stays the fitted p on purpose: a row is one of d_u rows of its user but one of very many soft counts of a block,
+ * and (n - omega) / (N - omega) is ill-conditioned for a block that only this row supports.  Over the S added slots
+ * reliability_j = (sum_s rel_{s,j}) / S and fitted_j = (sum_s fit_{s,j}) / S (slots added ascending from +0.0, one
+ * division), surprise_j = -log(max(reliability_j, eps)); a user's (item's) surprise is the mean of surprise_j over its
+ * rows, fitted_surprise the same built from fitted_j.
+ * Order of every sum over the rows of a user (item): rows in ascending position in the training table, cut into chunks
+ * of 64; a chunk's rows added one after the other from +0.0, then the chunk sums one after the other from +0.0 (the
+ * means: then one division by d) -- a tree fixed by d alone; theta-bar / eta-bar: thread t of 256 adds rows t, t + 256,
+ * ... from +0.0, the 256 sums are halved 8 times, one division.  No atomics.  Every number depends on its row, its
+ * user's rows, its item's rows and the added slots only, bit for bit: not on the other rows asked for, on the side
+ * layout or on slots the context holds beyond those added.
+ * A session of its own beside the others (any of them may be open meanwhile):
+ *   begin   the training table as given to mmsbm_hip_create (duplicate triples are separate rows) by user and by item.
+ *           Closes any earlier loo session;
+ *   add     the SELECTED slot joins: its C and E are formed, then rel and fit of every row are added to the rows'
+ *           running sums (the slot is left unchanged).  Nothing of size n_obs x K exists at any time: device memory of
+ *           a session is O(U K + I L + n_obs);
+ *   rows    fitted and reliability (either may be NULL) at the n_rows positions rows[] of the training table, or of
+ *           every row in training order when rows == NULL (n_rows is then ignored; n_obs doubles each);
+ *   sides   U (I) doubles each, any may be NULL: the users' (items') surprise and fitted_surprise; NaN without rows;
+ *   lowest  the m rows of smallest reliability among the rows whose user is flagged in user_flags (U bytes, non-zero =
+ *           flagged; NULL: every user) AND whose item is flagged in item_flags (I bytes; NULL: every item): rows[] and
+ *           reliability[] (m entries each), reliability ascending, exactly equal doubles by ascending position; *count
+ *           (may be NULL) = how many there are, the rest is (-1, +inf);
+ *   end     releases the session's device memory (so does mmsbm_hip_destroy).
+ * mmsbm_hip_get_option(ctx, "loo_ms") reads the device time of the last add's or query's kernels (HIP events),
+ * "loo_sums_ms" / "loo_rows_ms" those of the last add's sums pass and row pass.
+ * MMSBM_E_INVALID: add or query without begin, a query before the first add, a selected slot without parameters, m < 1
+ * or m > MMSBM_HIP_LOO_MAX_M, a row position outside [0, n_obs), a null pointer where one is needed; K or L >
+ * MMSBM_HIP_FOLD_IN_MAX_K: MMSBM_E_UNSUPPORTED; MMSBM_E_TOOLARGE where the device memory of the session or of a query
+ * is not free.  Touches no slot, no EM state and no other session; set_slots keeps the session's sums. */
+#define MMSBM_HIP_LOO_MAX_M 1024
+int mmsbm_hip_loo_begin(mmsbm_hip_ctx *ctx);
+int mmsbm_hip_loo_add(mmsbm_hip_ctx *ctx);
+int mmsbm_hip_loo_rows(mmsbm_hip_ctx *ctx, int64_t n_rows, const int64_t *rows, double *fitted, double *reliability);
+int mmsbm_hip_loo_sides(mmsbm_hip_ctx *ctx, double *user_surprise, double *user_fitted_surprise,
+                        double *item_surprise, double *item_fitted_surprise);
+int mmsbm_hip_loo_lowest(mmsbm_hip_ctx *ctx, int32_t m, const uint8_t *user_flags, const uint8_t *item_flags,
+                         int64_t *rows, double *reliability, int32_t *count);
+int mmsbm_hip_loo_end(mmsbm_hip_ctx *ctx);
+
 /* ---- held-out log-likelihood of every restart slot, and parameter snapshots (mmsbm_amd/csrc/heldout.hpp) ------------ */
 /* For a row m = (u, i, r) (external ids) and the parameters of slot s:
  *   t_s[k] = sum_l p_s[k, l, r] eta_s[i, l]     one fma chain over l ascending, from +0.0

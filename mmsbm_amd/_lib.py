@@ -16,6 +16,7 @@ c_i64p = C.POINTER(C.c_int64)
 c_f64p = C.POINTER(C.c_double)
 c_f32p = C.POINTER(C.c_float)
 c_intp = C.POINTER(C.c_int)
+c_u8p = C.POINTER(C.c_uint8)
 
 # name -> (restype, argtypes); every symbol include/mmsbm_hip.h declares
 SIGNATURES = {
@@ -97,6 +98,12 @@ SIGNATURES = {
     "mmsbm_hip_explain_query": (C.c_int, [C.c_void_p, C.c_int64, c_i32p, c_i64p, c_i32p, C.c_int32, c_i32p, c_i32p,
                                          c_f64p, c_i32p, c_f64p, c_f64p, c_i32p]),
     "mmsbm_hip_explain_end": (C.c_int, [C.c_void_p]),
+    "mmsbm_hip_loo_begin": (C.c_int, [C.c_void_p]),
+    "mmsbm_hip_loo_add": (C.c_int, [C.c_void_p]),
+    "mmsbm_hip_loo_rows": (C.c_int, [C.c_void_p, C.c_int64, c_i64p, c_f64p, c_f64p]),
+    "mmsbm_hip_loo_sides": (C.c_int, [C.c_void_p, c_f64p, c_f64p, c_f64p, c_f64p]),
+    "mmsbm_hip_loo_lowest": (C.c_int, [C.c_void_p, C.c_int32, c_u8p, c_u8p, c_i64p, c_f64p, c_i32p]),
+    "mmsbm_hip_loo_end": (C.c_int, [C.c_void_p]),
     "mmsbm_hip_heldout_begin": (C.c_int, [C.c_void_p, C.c_int64, c_i32p, c_i32p, c_i32p]),
     "mmsbm_hip_heldout_eval": (C.c_int, [C.c_void_p, c_f64p]),
     "mmsbm_hip_heldout_add": (C.c_int, [C.c_void_p, c_f64p]),

@@ -717,6 +717,62 @@ class HipEM:
     def explain_end(self):
         _lib.call("mmsbm_hip_explain_end", self._h)
 
+    # -- leave-one-out reliability of the training rows (include/mmsbm_hip.h: mmsbm_hip_loo_*) ----
+    MAX_LOO_M = 1024
+
+    def loo_begin(self):
+        """Open a leave-one-out session over the training rows: the probability of each row's rating under parameters
+        that never saw the row, averaged over the slots added to it."""
+        _lib.call("mmsbm_hip_loo_begin", self._h)
+
+    def loo_add(self):
+        """Add the selected slot's current parameters to the session (the slot is left unchanged)."""
+        _lib.call("mmsbm_hip_loo_add", self._h)
+
+    def loo_rows(self, rows=None):
+        """(fitted, reliability) at the positions ``rows`` of the training table (None: every row, in training order):
+        the in-sample and the leave-one-out probability of the row's rating, means over the slots added."""
+        if rows is None:
+            n, pos = self.n_obs, None
+        else:
+            pos = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+            n = len(pos)
+        fitted, rel = np.empty(n, dtype=np.float64), np.empty(n, dtype=np.float64)
+        if pos is not None and n == 0:   # (an empty array has no address to tell from "every row")
+            pos = np.zeros(1, dtype=np.int64)
+        _lib.call("mmsbm_hip_loo_rows", self._h, n, _p_or_null(pos, C.c_int64), _p(fitted, C.c_double),
+                  _p(rel, C.c_double))
+        return fitted, rel
+
+    def loo_sides(self):
+        """(user surprise (U,), user fitted_surprise (U,), item surprise (I,), item fitted_surprise (I,)): the mean of
+        -log(max(reliability, eps)) -- and of the same built from fitted -- over each user's and each item's training
+        rows; NaN where there are none."""
+        out = [np.empty(n, dtype=np.float64) for n in (self.n_users, self.n_users, self.n_items, self.n_items)]
+        _lib.call("mmsbm_hip_loo_sides", self._h, *[_p(a, C.c_double) for a in out])
+        return tuple(out)
+
+    def loo_lowest(self, m, user_flags=None, item_flags=None):
+        """(rows (m,) int64 padded with -1, reliability (m,) padded with +inf, count): the ``m`` training rows of
+        smallest reliability -- ascending, exactly equal ones by ascending position -- among the rows whose user is
+        flagged in ``user_flags`` ((U,) bool; None: every user) and whose item is flagged in ``item_flags``."""
+        m = int(m)
+        flags = []
+        for given, size, name in ((user_flags, self.n_users, "user_flags"), (item_flags, self.n_items, "item_flags")):
+            if given is not None:
+                given = np.ascontiguousarray(np.asarray(given) != 0, dtype=np.uint8)
+                if given.shape != (size,):
+                    raise ValueError(f"{name} has shape {given.shape}, expected ({size},)")
+            flags.append(given)
+        rows, rel = np.empty(max(m, 0), dtype=np.int64), np.empty(max(m, 0), dtype=np.float64)
+        count = C.c_int32(0)
+        _lib.call("mmsbm_hip_loo_lowest", self._h, m, _p_or_null(flags[0], C.c_uint8), _p_or_null(flags[1], C.c_uint8),
+                  _p(rows, C.c_int64), _p(rel, C.c_double), C.byref(count))
+        return rows, rel, int(count.value)
+
+    def loo_end(self):
+        _lib.call("mmsbm_hip_loo_end", self._h)
+
     # -- held-out log-likelihood and snapshots on the device (include/mmsbm_hip.h: mmsbm_hip_heldout_*) ----
     def heldout_begin(self, rows):
         """Open a held-out session over (M,3) triples [user, item, observed rating index] (encoded ids)."""

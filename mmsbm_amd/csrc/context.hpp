@@ -198,6 +198,26 @@ struct InfSession {
   int slots = 0;                        // slots added
 };
 
+// The leave-one-out session (mmsbm_hip_loo_begin .. end; loo.hpp): the training table in the order it was given, its
+// rows by user and by item cut into chunks, the C and E of the slot being added and the rows' running sums.  Created
+// by loo_begin, dropped whole by loo_begin and loo_end; set_slots leaves it alone (it holds sums, nothing of a slot).
+struct LooSession {
+  struct Side {                         // the rows of every user (or item), ascending position in the training table
+    DevBuf<int64_t> off, chunk_off;     // [segments + 1]: first row / first chunk of a segment
+    DevBuf<int32_t> rows, chunk_seg;    // [n_obs] positions in the training table; [chunks] the segment of a chunk
+    DevBuf<double> num, part;           // [segments][groups] C (or E) of the last add; [chunks][max(groups, 2)] chunk sums
+    DevBuf<double> bar, surprise;       // [groups] the mean row of the last add; [segments][2] mean surprises (finish)
+    std::vector<int64_t> off_h;         // off on the host (degrees)
+    int64_t chunks = 0;
+  } by_user, by_item;
+  DevBuf<int32_t> user, item, rating;   // [n_obs] external ids, training order
+  DevBuf<double> fit;                   // [n_obs] fit_j of the slot being added
+  DevBuf<double> rel_sum, fit_sum;      // [n_obs] running sums over the slots added
+  DevBuf<double> rel, fitted, sur, fsur;  // [n_obs] the finished columns of the slots added so far
+  bool finished = false;                // ... are those of `slots`
+  int slots = 0;                        // slots added
+};
+
 }  // namespace mmsbm_hip_impl
 
 namespace {
@@ -249,8 +269,9 @@ inline void sort_unique_groups(std::vector<int32_t> &off, std::vector<int32_t> &
 // The serving calls whose kernels are timed (mmsbm_hip_ctx::last_ms), in the order of their "<name>_ms" options:
 // recommend_query / recommend_query_items, fold_in / fold_in_items, recommend_positions, recommend_top_pairs,
 // recommend_audience, similar_query, overlap_query, heldout_eval / heldout_add, explain_query, recommend_diverse /
-// similar_pairs, inform_query / inform_query_theta, recommend_query_groups, recommend_query_ensemble / recommend_pair_spread
-enum TimedCall { T_RECOMMEND = 0, T_FOLD_IN, T_POSITIONS, T_TOP_PAIRS, T_AUDIENCE, T_SIMILAR, T_OVERLAP, T_HELDOUT, T_EXPLAIN, T_DIVERSE, T_INFORM, T_GROUP, T_ENSEMBLE, T_COUNT };
+// similar_pairs, inform_query / inform_query_theta, recommend_query_groups, recommend_query_ensemble / recommend_pair_spread,
+// loo_add / loo_rows / loo_sides / loo_lowest (and, of the last loo_add alone, its sums pass and its row pass)
+enum TimedCall { T_RECOMMEND = 0, T_FOLD_IN, T_POSITIONS, T_TOP_PAIRS, T_AUDIENCE, T_SIMILAR, T_OVERLAP, T_HELDOUT, T_EXPLAIN, T_DIVERSE, T_INFORM, T_GROUP, T_ENSEMBLE, T_LOO, T_LOO_SUMS, T_LOO_ROWS, T_COUNT };
 
 enum KernelId { K_SEG = 0, K_DENSE, K_ETAP, K_MATVEC_A, K_FUSED_PAIRS, K_FUSED_TAIL, K_COUNT };
 // The four launches of an iteration -- or, for small problems, the two of fused_small.hpp.  With pass_dense.hpp the
@@ -336,6 +357,7 @@ struct mmsbm_hip_ctx {
   std::unique_ptr<mmsbm_hip_impl::HoldSession> ho;     // held-out
   std::unique_ptr<mmsbm_hip_impl::ExpSession> ex;      // explain
   std::unique_ptr<mmsbm_hip_impl::InfSession> inf;     // inform
+  std::unique_ptr<mmsbm_hip_impl::LooSession> loo;     // leave-one-out
   float last_ms[T_COUNT] = {};              // device time of the last call's kernels, per TimedCall (options "<name>_ms")
   int top_groups = 0;                       // option "top_pairs_groups": workgroups of gtop_fused_kernel (0: 2 per CU)
   int64_t aud_rows = 0;                     // option "audience_rows": items per COUNT batch (0: the library's choice)

@@ -134,6 +134,16 @@ void explain_query(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, cons
                    int n, int32_t *hist_items, int32_t *hist_ratings, double *contribution, int32_t *counts,
                    double *explained, double *score, int32_t *degree);
 
+// ... and the leave-one-out reliability of the training rows (loo.hpp): the session of mmsbm_hip_loo_*, arguments
+// checked; rows: positions in the training table (null: every row); flags: per external user / item (null: everyone)
+void loo_begin(mmsbm_hip_ctx *c);
+void loo_add(mmsbm_hip_ctx *c);  // the selected slot (the caller holds a OneSlot)
+void loo_rows(mmsbm_hip_ctx *c, int64_t n_rows, const int64_t *rows, double *fitted, double *reliability);
+void loo_sides(mmsbm_hip_ctx *c, double *user_surprise, double *user_fitted_surprise, double *item_surprise,
+               double *item_fitted_surprise);
+void loo_lowest(mmsbm_hip_ctx *c, int m, const uint8_t *user_flags, const uint8_t *item_flags, int64_t *rows,
+                double *reliability, int32_t *count);
+
 // tu_iterate.hip -- the EM iteration: the form the context's shape and options select, its order of launches, the
 // cur / a_ok / graph_exec state machine, and the timers.  Dispatchers first:
 void stage_dense(mmsbm_hip_ctx *c);

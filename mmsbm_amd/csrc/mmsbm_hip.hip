@@ -952,6 +952,59 @@ int mmsbm_hip_explain_query(mmsbm_hip_ctx *ctx, int64_t n_users, const int32_t *
 
 int mmsbm_hip_explain_end(mmsbm_hip_ctx *ctx) { return end_session(ctx, &mmsbm_hip_ctx::ex); }
 
+int mmsbm_hip_loo_begin(mmsbm_hip_ctx *ctx) {
+  return guarded([&] {
+    if (!ctx) throw std::invalid_argument("null context");
+    if (std::max(ctx->ext_k, ctx->ext_l) > MMSBM_HIP_FOLD_IN_MAX_K)
+      throw ApiError(MMSBM_E_UNSUPPORTED, "loo: K = " + std::to_string(ctx->ext_k) + ", L = " + std::to_string(ctx->ext_l) +
+                                              " is beyond the " + std::to_string(MMSBM_HIP_FOLD_IN_MAX_K) +
+                                              " groups it is built for");
+    if (ctx->n_obs > INT32_MAX) throw ApiError(MMSBM_E_UNSUPPORTED, "loo: n_obs must be below 2^31");
+    loo_begin(ctx);
+  });
+}
+
+int mmsbm_hip_loo_add(mmsbm_hip_ctx *ctx) {
+  return guarded([&] {
+    require_params(ctx);
+    require_open(ctx, &mmsbm_hip_ctx::loo, "loo");
+    OneSlot one(ctx);
+    loo_add(ctx);
+  });
+}
+
+int mmsbm_hip_loo_rows(mmsbm_hip_ctx *ctx, int64_t n_rows, const int64_t *rows, double *fitted, double *reliability) {
+  return guarded([&] {
+    require_open(ctx, &mmsbm_hip_ctx::loo, "loo", "loo_rows");
+    if (rows && n_rows < 0) throw std::invalid_argument("loo: negative n_rows");
+    for (int64_t m = 0; rows && m < n_rows; ++m)
+      if (rows[m] < 0 || rows[m] >= ctx->n_obs)
+        throw std::invalid_argument("loo: row position out of range at entry " + std::to_string(m));
+    loo_rows(ctx, n_rows, rows, fitted, reliability);
+  });
+}
+
+int mmsbm_hip_loo_sides(mmsbm_hip_ctx *ctx, double *user_surprise, double *user_fitted_surprise,
+                        double *item_surprise, double *item_fitted_surprise) {
+  return guarded([&] {
+    require_open(ctx, &mmsbm_hip_ctx::loo, "loo", "loo_sides");
+    loo_sides(ctx, user_surprise, user_fitted_surprise, item_surprise, item_fitted_surprise);
+  });
+}
+
+int mmsbm_hip_loo_lowest(mmsbm_hip_ctx *ctx, int32_t m, const uint8_t *user_flags, const uint8_t *item_flags,
+                         int64_t *rows, double *reliability, int32_t *count) {
+  return guarded([&] {
+    require_open(ctx, &mmsbm_hip_ctx::loo, "loo", "loo_lowest");
+    if (m < 1 || m > MMSBM_HIP_LOO_MAX_M)
+      throw std::invalid_argument("loo: m must be in 1 .. " + std::to_string(MMSBM_HIP_LOO_MAX_M));
+    if (!rows || !reliability) throw std::invalid_argument("null argument");
+    loo_lowest(ctx, m, user_flags, item_flags, rows, reliability, count);
+  });
+}
+
+int mmsbm_hip_loo_end(mmsbm_hip_ctx *ctx) { return end_session(ctx, &mmsbm_hip_ctx::loo); }
+
 int mmsbm_hip_heldout_begin(mmsbm_hip_ctx *ctx, int64_t n_rows, const int32_t *user, const int32_t *item,
                             const int32_t *rating) {
   return guarded([&] {

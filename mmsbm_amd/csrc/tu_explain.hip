@@ -1,10 +1,13 @@
 // tu_explain.hip -- translation unit of the explanation of a recommendation (explain.hpp): the session's host side --
 // the training rows of every external user, the per-slot copies, the batches of a query.  It launches rec_w_kernel and
 // rec_fold_kernel of recommend.hpp for the slots' tables and shares that header's candidate list and fold_in.hpp's v.
+// Also the host side of the leave-one-out reliability of the training rows (loo.hpp), which rests on the same identity
+// and shares the same two headers.
 #include "prelude.hpp"
 #include "recommend.hpp"
 #include "fold_in.hpp"
 #include "explain.hpp"
+#include "loo.hpp"
 
 namespace mmsbm_hip_impl {
 
@@ -163,6 +166,264 @@ void explain_query(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, cons
   fetch(score, osc.ptr, sizeof(double) * total);
   HIP_CHECK(hipStreamSynchronize(st));
   c->last_ms[T_EXPLAIN] = ev.ms();
+}
+
+// ---- leave-one-out reliability of the training rows (loo.hpp) ---------------------------------------------------------
+namespace {
+
+// One side's segments onto the device: the rows of every key (a user, or an item) in ascending position in the training
+// table, and their chunks of kLooChunk rows
+void loo_upload_side(LooSession::Side &sd, const std::vector<int32_t> &key, int segments, int groups, hipStream_t s) {
+  const int64_t n = static_cast<int64_t>(key.size());
+  std::vector<int32_t> rows(key.size());
+  sd.off_h = group_by_key<int64_t>(key.data(), n, segments,
+                                   [&](int64_t m, int64_t at) { rows[at] = static_cast<int32_t>(m); });
+  std::vector<int64_t> chunk_off(static_cast<size_t>(segments) + 1, 0);
+  for (int g = 0; g < segments; ++g)
+    chunk_off[g + 1] = chunk_off[g] + (sd.off_h[g + 1] - sd.off_h[g] + kLooChunk - 1) / kLooChunk;
+  sd.chunks = chunk_off.back();
+  std::vector<int32_t> chunk_seg(static_cast<size_t>(sd.chunks));
+  for (int g = 0; g < segments; ++g)
+    std::fill(chunk_seg.begin() + chunk_off[g], chunk_seg.begin() + chunk_off[g + 1], g);
+  sd.off.upload(sd.off_h, s);
+  sd.chunk_off.upload(chunk_off, s);
+  sd.rows.upload(rows, s);
+  sd.chunk_seg.upload(chunk_seg, s);
+  sd.num.alloc(static_cast<size_t>(segments) * groups);
+  sd.part.alloc(static_cast<size_t>(sd.chunks) * std::max(groups, 2));
+  sd.bar.alloc(static_cast<size_t>(groups));
+  sd.surprise.alloc(static_cast<size_t>(segments) * 2);
+  HIP_CHECK(hipStreamSynchronize(s));  // (host vectors are locals)
+}
+
+LooSide loo_side(const LooSession::Side &sd) {
+  return LooSide{sd.off.ptr, sd.rows.ptr, sd.chunk_seg.ptr, sd.chunk_off.ptr, sd.chunks,
+                 static_cast<int>(sd.off_h.size()) - 1};
+}
+
+unsigned loo_blocks(int64_t n, int per_block) { return static_cast<unsigned>((n + per_block - 1) / per_block); }
+
+// The four columns and the sides' mean surprises of the slots added so far (once per set of added slots)
+void loo_finish(mmsbm_hip_ctx *c, LooSession &lo, hipStream_t st) {
+  if (lo.finished) return;
+  const int64_t n = c->n_obs;
+  if (n > 0)
+    LAUNCH(loo_finish_kernel, loo_blocks(n, kBlock), kBlock, 0, st, lo.rel_sum.ptr, lo.fit_sum.ptr, n,
+           static_cast<double>(lo.slots), lo.rel.ptr, lo.fitted.ptr, lo.sur.ptr, lo.fsur.ptr);
+  for (LooSession::Side *sd : {&lo.by_user, &lo.by_item}) {
+    const LooSide v = loo_side(*sd);
+    if (v.chunks > 0)
+      LAUNCH(loo_agg_kernel, loo_blocks(v.chunks, kBlock), kBlock, 0, st, v, lo.sur.ptr, lo.fsur.ptr, sd->part.ptr);
+    if (v.segments > 0)
+      LAUNCH(loo_comb_kernel, loo_blocks(static_cast<int64_t>(v.segments) * 2, kBlock), kBlock, 0, st, v, 2, 1,
+             sd->part.ptr, sd->surprise.ptr);
+  }
+  HIP_CHECK(hipGetLastError());
+  lo.finished = true;
+}
+
+}  // namespace
+
+void loo_begin(mmsbm_hip_ctx *c) {
+  use_device(c);
+  c->loo.reset();  // (from here on the previous session is gone)
+  auto lo = std::make_unique<LooSession>();
+  hipStream_t s = c->stream;
+  const int U = c->ext_users, I = c->ext_items, K = c->ext_k, L = c->ext_l;
+  const size_t n = static_cast<size_t>(c->n_obs);
+  const size_t chunks = 2 * (n / kLooChunk) + U + I;  // (at most)
+  require_free_mem(n * (5 * sizeof(int32_t) + 7 * sizeof(double)) + chunks * (4 + 8 * std::max({K, L, 2})) +
+                       (static_cast<size_t>(U) * (K + 4) + static_cast<size_t>(I) * (L + 4)) * sizeof(double),
+                   "loo: the training rows, their sums and the sides' numerators");
+  std::vector<int32_t> eu, ei, rt;
+  train_id_columns(c, eu, ei, &rt);
+  loo_upload_side(lo->by_user, eu, U, K, s);
+  loo_upload_side(lo->by_item, ei, I, L, s);
+  lo->user.upload(eu, s);
+  lo->item.upload(ei, s);
+  lo->rating.upload(rt, s);
+  for (DevBuf<double> *b : {&lo->fit, &lo->rel_sum, &lo->fit_sum, &lo->rel, &lo->fitted, &lo->sur, &lo->fsur}) b->alloc(n);
+  if (n > 0) {  // (the running sums start at +0.0)
+    HIP_CHECK(hipMemsetAsync(lo->rel_sum.ptr, 0, sizeof(double) * n, s));
+    HIP_CHECK(hipMemsetAsync(lo->fit_sum.ptr, 0, sizeof(double) * n, s));
+  }
+  HIP_CHECK(hipStreamSynchronize(s));  // (host vectors are locals)
+  c->loo = std::move(lo);
+}
+
+void loo_add(mmsbm_hip_ctx *c) {  // the selected slot (the caller holds a OneSlot)
+  use_device(c);
+  LooSession &lo = *c->loo;
+  hipStream_t st = c->stream;
+  const int U = c->ext_users, I = c->ext_items, K = c->ext_k, L = c->ext_l;
+  const int64_t n = c->n_obs;
+  const ExtSlot e = ext_slot(c);
+  int W = loo_lanes(std::max(K, L));  // (wide rows: fewer rows per workgroup, so that their LDS stays below 96 KB)
+  while (W < kBlock && sizeof(double) * (kBlock / W) * (3 * K + 2 * L) > (size_t(96) << 10)) W <<= 1;
+  const int rows_per = kBlock / W, R = c->n_ratings;
+  // p of every rating goes into LDS where it fits beside the groups' rows (the row pass needs most); the values and the
+  // order of the operations are the same either way
+  const size_t p_lds = sizeof(double) * loo_p_doubles(K, L, R);
+  const size_t fit_rows = sizeof(double) * rows_per * (2 * K + L), row_rows = sizeof(double) * rows_per * (3 * K + 2 * L);
+  const int plds = p_lds + row_rows <= kLooLdsP ? 1 : 0;
+  const size_t fit_lds = fit_rows + (plds ? p_lds : 0), row_lds = row_rows + (plds ? p_lds : 0), sum_lds = plds ? p_lds : 0;
+  const LooArgs a{e.users, e.items, e.p, e.rs, e.ks, e.ls, K, L, R, lo.user.ptr, lo.item.ptr, lo.rating.ptr, n};
+  allow_big_lds(loo_fit_kernel<false>, fit_lds);  // (with p on chip everything stays within the plain budget)
+  allow_big_lds(loo_row_kernel<false>, row_lds);
+  EventPair all, sums, rows;  // device time of the add, of its sums pass and of its row pass (options "loo_*_ms")
+  all.start(st);
+  sums.start(st);
+  LAUNCH(loo_mean_kernel, static_cast<unsigned>(K), kBlock, 0, st, e.users, U, lo.by_user.bar.ptr);
+  LAUNCH(loo_mean_kernel, static_cast<unsigned>(L), kBlock, 0, st, e.items, I, lo.by_item.bar.ptr);
+  const unsigned row_blocks = loo_blocks(n, rows_per * kLooRounds);
+  if (n > 0 && plds) LAUNCH(loo_fit_kernel<true>, row_blocks, kBlock, fit_lds, st, a, W, lo.fit.ptr, lo.fit_sum.ptr);
+  if (n > 0 && !plds) LAUNCH(loo_fit_kernel<false>, row_blocks, kBlock, fit_lds, st, a, W, lo.fit.ptr, lo.fit_sum.ptr);
+  for (int side = 0; side < 2; ++side) {
+    LooSession::Side &sd = side ? lo.by_item : lo.by_user;
+    const LooSide v = loo_side(sd);
+    const int G = side ? L : K, Ws = loo_lanes(G);
+    const unsigned chunk_blocks = loo_blocks(v.chunks, kBlock / Ws);
+    if (v.chunks > 0 && plds)
+      LAUNCH(loo_sum_kernel<true>, chunk_blocks, kBlock, sum_lds, st, a, v, side, Ws, lo.fit.ptr, sd.part.ptr);
+    if (v.chunks > 0 && !plds)
+      LAUNCH(loo_sum_kernel<false>, chunk_blocks, kBlock, sum_lds, st, a, v, side, Ws, lo.fit.ptr, sd.part.ptr);
+    if (v.segments > 0)
+      LAUNCH(loo_comb_kernel, loo_blocks(static_cast<int64_t>(v.segments) * G, kBlock), kBlock, 0, st, v, G, 0,
+             sd.part.ptr, sd.num.ptr);
+  }
+  sums.stop(st);
+  rows.start(st);
+  if (n > 0 && plds)
+    LAUNCH(loo_row_kernel<true>, row_blocks, kBlock, row_lds, st, a, W, lo.fit.ptr, lo.by_user.num.ptr, lo.by_item.num.ptr,
+           lo.by_user.bar.ptr, lo.by_item.bar.ptr, lo.by_user.off.ptr, lo.by_item.off.ptr, lo.rel_sum.ptr);
+  if (n > 0 && !plds)
+    LAUNCH(loo_row_kernel<false>, row_blocks, kBlock, row_lds, st, a, W, lo.fit.ptr, lo.by_user.num.ptr, lo.by_item.num.ptr,
+           lo.by_user.bar.ptr, lo.by_item.bar.ptr, lo.by_user.off.ptr, lo.by_item.off.ptr, lo.rel_sum.ptr);
+  rows.stop(st);
+  all.stop(st);
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipStreamSynchronize(st));
+  lo.slots += 1;
+  lo.finished = false;
+  c->last_ms[T_LOO] = all.ms();
+  c->last_ms[T_LOO_SUMS] = sums.ms();
+  c->last_ms[T_LOO_ROWS] = rows.ms();
+}
+
+void loo_rows(mmsbm_hip_ctx *c, int64_t n_rows, const int64_t *rows, double *fitted, double *reliability) {
+  use_device(c);
+  LooSession &lo = *c->loo;
+  hipStream_t st = c->stream;
+  const int64_t n = rows ? n_rows : c->n_obs;
+  DevBuf<int64_t> dr;
+  DevBuf<double> of, orl;
+  if (rows && n > 0) {
+    require_free_mem(static_cast<size_t>(n) * 24, "loo: the requested rows");
+    dr.alloc(static_cast<size_t>(n));
+    of.alloc(static_cast<size_t>(n));
+    orl.alloc(static_cast<size_t>(n));
+    HIP_CHECK(hipMemcpyAsync(dr.ptr, rows, sizeof(int64_t) * n, hipMemcpyHostToDevice, st));
+  }
+  EventPair ev;
+  ev.start(st);
+  loo_finish(c, lo, st);
+  if (rows && n > 0)
+    LAUNCH(loo_gather_kernel, loo_blocks(n, kBlock), kBlock, 0, st, dr.ptr, n, lo.fitted.ptr, lo.rel.ptr, of.ptr, orl.ptr);
+  HIP_CHECK(hipGetLastError());
+  ev.stop(st);
+  if (n > 0) {
+    if (fitted)
+      HIP_CHECK(hipMemcpyAsync(fitted, rows ? of.ptr : lo.fitted.ptr, sizeof(double) * n, hipMemcpyDeviceToHost, st));
+    if (reliability)
+      HIP_CHECK(hipMemcpyAsync(reliability, rows ? orl.ptr : lo.rel.ptr, sizeof(double) * n, hipMemcpyDeviceToHost, st));
+  }
+  HIP_CHECK(hipStreamSynchronize(st));
+  c->last_ms[T_LOO] = ev.ms();
+}
+
+void loo_sides(mmsbm_hip_ctx *c, double *user_surprise, double *user_fitted_surprise, double *item_surprise,
+               double *item_fitted_surprise) {
+  use_device(c);
+  LooSession &lo = *c->loo;
+  hipStream_t st = c->stream;
+  EventPair ev;
+  ev.start(st);
+  loo_finish(c, lo, st);
+  ev.stop(st);
+  std::vector<double> us(static_cast<size_t>(c->ext_users) * 2), is(static_cast<size_t>(c->ext_items) * 2);
+  HIP_CHECK(hipMemcpyAsync(us.data(), lo.by_user.surprise.ptr, sizeof(double) * us.size(), hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipMemcpyAsync(is.data(), lo.by_item.surprise.ptr, sizeof(double) * is.size(), hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipStreamSynchronize(st));
+  for (size_t u = 0; u < us.size() / 2; ++u) {
+    if (user_surprise) user_surprise[u] = us[2 * u];
+    if (user_fitted_surprise) user_fitted_surprise[u] = us[2 * u + 1];
+  }
+  for (size_t i = 0; i < is.size() / 2; ++i) {
+    if (item_surprise) item_surprise[i] = is[2 * i];
+    if (item_fitted_surprise) item_fitted_surprise[i] = is[2 * i + 1];
+  }
+  c->last_ms[T_LOO] = ev.ms();
+}
+
+void loo_lowest(mmsbm_hip_ctx *c, int m, const uint8_t *user_flags, const uint8_t *item_flags, int64_t *rows,
+                double *reliability, int32_t *count) {
+  use_device(c);
+  LooSession &lo = *c->loo;
+  hipStream_t st = c->stream;
+  const int64_t n = c->n_obs;
+  // ranges of rows: one wave each, at most 256 of them (the split changes no answer)
+  const int64_t per = std::max<int64_t>(4096, (n + 255) / 256);
+  const int parts = static_cast<int>(std::max<int64_t>(1, (n + per - 1) / per));
+  int cap = 1;
+  while (cap < m + kLooWave * kLooPerLane) cap <<= 1;
+  const size_t lds = static_cast<size_t>(cap) * (sizeof(double) + sizeof(int64_t));
+  const size_t list = static_cast<size_t>(parts + 1) * m;
+  require_free_mem(list * 16 + (parts + 1) * 4 + (user_flags ? c->ext_users : 0) + (item_flags ? c->ext_items : 0),
+                   "loo: the ranges' lists and the flags");
+  DevBuf<uint8_t> uf, itf;
+  DevBuf<double> ls;
+  DevBuf<int64_t> lk;
+  DevBuf<int32_t> ln;
+  ls.alloc(list);
+  lk.alloc(list);
+  ln.alloc(static_cast<size_t>(parts) + 1);
+  if (user_flags) {
+    uf.alloc(static_cast<size_t>(c->ext_users));
+    HIP_CHECK(hipMemcpyAsync(uf.ptr, user_flags, static_cast<size_t>(c->ext_users), hipMemcpyHostToDevice, st));
+  }
+  if (item_flags) {
+    itf.alloc(static_cast<size_t>(c->ext_items));
+    HIP_CHECK(hipMemcpyAsync(itf.ptr, item_flags, static_cast<size_t>(c->ext_items), hipMemcpyHostToDevice, st));
+  }
+  const uint8_t *no_flags = nullptr;
+  const double *no_s = nullptr;
+  const int64_t *no_k = nullptr;
+  const int32_t *no_n = nullptr;
+  EventPair ev;
+  ev.start(st);
+  loo_finish(c, lo, st);
+  LAUNCH(loo_low_kernel<false>, static_cast<unsigned>(parts), kLooWave, lds, st, lo.rel.ptr, lo.user.ptr, lo.item.ptr,
+         user_flags ? uf.ptr : no_flags, item_flags ? itf.ptr : no_flags, n, per, no_s, no_k, no_n, 0, m, cap, ls.ptr,
+         lk.ptr, ln.ptr);
+  // the ranges' lists into the one behind them
+  double *fs = ls.ptr + static_cast<size_t>(parts) * m;
+  int64_t *fk = lk.ptr + static_cast<size_t>(parts) * m;
+  LAUNCH(loo_low_kernel<true>, 1u, kLooWave, lds, st, lo.rel.ptr, lo.user.ptr, lo.item.ptr, no_flags, no_flags, n, per,
+         static_cast<const double *>(ls.ptr), static_cast<const int64_t *>(lk.ptr),
+         static_cast<const int32_t *>(ln.ptr), parts, m, cap, fs, fk, ln.ptr + parts);
+  HIP_CHECK(hipGetLastError());
+  ev.stop(st);
+  int32_t got = 0;
+  HIP_CHECK(hipMemcpyAsync(&got, ln.ptr + parts, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipMemcpyAsync(rows, fk, sizeof(int64_t) * m, hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipMemcpyAsync(reliability, fs, sizeof(double) * m, hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipStreamSynchronize(st));
+  for (int k = 0; k < m; ++k) {  // the list held -reliability (the selection's order); behind the last one (-1, +inf)
+    rows[k] = k < got ? rows[k] : -1;
+    reliability[k] = k < got ? -reliability[k] : INFINITY;
+  }
+  if (count) *count = got;
+  c->last_ms[T_LOO] = ev.ms();
 }
 
 }  // namespace mmsbm_hip_impl

@@ -56,6 +56,10 @@ const Option kOptions[] = {
     {"inform_ms", [](const Ctx *c) -> double { return c->last_ms[T_INFORM]; }, nullptr},
     {"group_ms", [](const Ctx *c) -> double { return c->last_ms[T_GROUP]; }, nullptr},
     {"ensemble_ms", [](const Ctx *c) -> double { return c->last_ms[T_ENSEMBLE]; }, nullptr},
+    // ... of the last loo_add or loo query (loo.hpp); of the last loo_add alone: its sums pass and its row pass
+    {"loo_ms", [](const Ctx *c) -> double { return c->last_ms[T_LOO]; }, nullptr},
+    {"loo_sums_ms", [](const Ctx *c) -> double { return c->last_ms[T_LOO_SUMS]; }, nullptr},
+    {"loo_rows_ms", [](const Ctx *c) -> double { return c->last_ms[T_LOO_ROWS]; }, nullptr},
     // workgroups of gtop_fused_kernel (top_pairs.hpp); 0: the library's choice
     {"top_pairs_groups", [](const Ctx *c) -> double { return c->top_groups; },
      [](Ctx *c, double v) {

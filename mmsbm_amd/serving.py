@@ -1,6 +1,6 @@
 """What ``MMSBM`` offers beyond the reference's surface, as the base class it inherits: recommendation from the user's
 and the item's side, nearest neighbours, diversified lists, explanations, the matching of the restarts' groups,
-ranking evaluation and the fold-in of new users and items.  Every method scores on the device, through sessions of the
+ranking evaluation, the fold-in of new users and items and the leave-one-out reliability of the training ratings.  Every method scores on the device, through sessions of the
 model's context (``MMSBM._ctx`` / ``MMSBM._restarts``); this module holds what they share on the host: the label table
 of a side (``_Side``), grouped lists (``grouped`` / ``group_slice``), the argument checks, the session holder and the
 frame assembler.
@@ -113,7 +113,7 @@ class _Side:
 
 @contextlib.contextmanager
 def session(ctx, kind, *begin_args):
-    """ctx's ``kind`` session ("recommend", "similar", "overlap", "explain", "inform", "heldout") begun with
+    """ctx's ``kind`` session ("recommend", "similar", "overlap", "explain", "inform", "heldout", "loo") begun with
     ``begin_args`` around the block, ended however the block ends."""
     getattr(ctx, kind + "_begin")(*begin_args)
     try:
@@ -453,6 +453,122 @@ class Serving:
                 return counts, {"because": hi, "rating": hr, "contribution": co, "score": score[:, None],
                                 "explained": explained[:, None]}
             return self._frame({"users": ulab, "items": ilab}, made, self._row_batches(len(uid), n), query, n)
+
+    # ------------------------------------------------------------------ which ratings look wrong (not in the reference)
+    LOWEST_MAX = 1024                # largest m of spurious_ratings (MMSBM_HIP_LOO_MAX_M)
+
+    def _reliability_frame(self, rows, fitted, reliability):
+        """The frame of the training rows at positions ``rows``: labels, fitted, reliability, surprise."""
+        train = np.asarray(self.train)[rows]
+        return pd.DataFrame({
+            "users": self._side("users").label(train[:, 0]),
+            "items": self._side("items").label(train[:, 1]),
+            "rating": self._side("ratings").label(train[:, 2]),
+            "fitted": fitted,
+            "reliability": reliability,
+            "surprise": -np.log(np.maximum(reliability, np.finfo(np.float64).eps))})
+
+    def _known_labels(self, side, labels):
+        """The ids of ``labels`` on ``side`` ("users" / "items"), -1 where the training data has none: those are named
+        in ``predict``'s warning."""
+        ids = self._side(side).ids(labels)
+        unseen = list(dict.fromkeys(str(x) for x, j in zip(labels, ids.tolist()) if j < 0))
+        if unseen:
+            self.logger.warning(f"The {side} {', '.join(unseen)} are in the test set but weren't in the train set so "
+                                f"I'll remove them.")
+        return ids
+
+    def rating_reliability(self, pairs=None):
+        """How far the model believes each training rating once that rating is taken away -- the other half of network
+        reconstruction: ``top_pairs`` finds the missing links, this the spurious ones.  Computed on the device.
+
+        The in-sample probability of a training row (``fitted``) is bent towards the row: a user with six ratings has
+        a theta that was fitted to explain each of them, so a wrong rating largely vouches for itself.  ``reliability``
+        is the probability of the row's rating under parameters that never saw the row: the M-step writes theta_u as
+        the average of its rows' shares c_j (the identity ``explain`` rests on) and eta_i as that of its rows' shares
+        e_j, so one EM step without row j is a downdate of two sums, theta-_u = (C_u - c_j) / (d_u - 1) and eta-_i =
+        (E_i - e_j) / (d_i - 1), and reliability_j = sum_kl theta-_u[k] eta-_i[l] p[k, l, r_j].  The only row of a user
+        (item) is judged from the mean theta (eta) row.  p stays the fitted p on purpose: a row is one of d_u rows of its
+        user but one of very many soft counts of a block, and removing it from a block that only this row supports is
+        ill-conditioned.  ``surprise`` = -log(max(reliability, eps)).  Everything is the mean over the restarts the
+        model holds.
+
+        ``pairs``: None for every training row in training order, or a DataFrame whose first two columns are users and
+        items, or (user, item) tuples: the training rows of those pairs, in training order (a pair rated twice has two
+        rows; users and items unseen in training are dropped with ``predict``'s warning).  Returns a DataFrame with
+        columns ``users``, ``items``, ``rating``, ``fitted``, ``reliability``, ``surprise``.  The model's stored
+        predictions and ``score()`` are left as they are."""
+        self._check_whole_model()
+        rows = None
+        if pairs is not None:
+            us, its = self._pair_columns(pairs)
+            uid, iid = self._known_labels("users", us), self._known_labels("items", its)
+            keep = (uid >= 0) & (iid >= 0)
+            train = np.asarray(self.train)
+            width = np.int64(self.m + 1)
+            asked = np.unique(uid[keep].astype(np.int64) * width + iid[keep])
+            rows = np.flatnonzero(np.isin(train[:, 0].astype(np.int64) * width + train[:, 1], asked))
+        with self._session_of_restarts("loo") as ctx:
+            fitted, reliability = ctx.loo_rows(rows)
+        return self._reliability_frame(slice(None) if rows is None else rows, fitted, reliability)
+
+    def spurious_ratings(self, m=100, users=None, items=None):
+        """The ``m`` training ratings the model believes least -- a mistyped 1 for a 5, a shared account, a bot, a
+        mislabelled item -- selected on the device: the rows of smallest ``reliability`` (``rating_reliability``
+        defines it), ascending, exactly equal ones in training order.  ``users`` / ``items`` (labels of the training
+        data: KeyError otherwise) restrict the rows to those of the named users and, when both are given, of the named
+        items as well.  ``m`` is at most 1,024: for more, sort ``rating_reliability()``.
+
+        Returns a DataFrame with the columns of ``rating_reliability`` plus ``rank`` (1 = the least reliable), at most
+        ``m`` rows.  The model's stored predictions and ``score()`` are left as they are."""
+        self._check_whole_model()
+        m = check_integer(m, "m", 1)
+        if m > self.LOWEST_MAX:
+            raise ValueError(f"m = {m} is beyond the {self.LOWEST_MAX} rows a query returns at most: "
+                             "sort rating_reliability() instead")
+        flags = []
+        for side, wanted in (("users", users), ("items", items)):
+            if wanted is None:
+                flags.append(None)
+                continue
+            mask = np.zeros(len(self._side(side)), dtype=bool)
+            mask[self._side(side).request(wanted)[0]] = True
+            flags.append(mask)
+        with self._session_of_restarts("loo") as ctx:
+            rows, reliability, count = ctx.loo_lowest(m, *flags)
+            fitted, _ = ctx.loo_rows(rows[:count])
+        frame = self._reliability_frame(rows[:count], fitted, reliability[:count])
+        frame["rank"] = np.arange(1, count + 1, dtype=np.int64)
+        return frame
+
+    def _misfit(self, side, m, min_ratings):
+        self._check_whole_model()
+        if m is not None:
+            m = check_integer(m, "m", 1)
+        min_ratings = check_integer(min_ratings, "min_ratings", 1)
+        with self._session_of_restarts("loo") as ctx:
+            sides = ctx.loo_sides()
+        surprise, fitted = sides[:2] if side == "users" else sides[2:]
+        table = self._side(side)
+        degree = np.bincount(np.asarray(self.train)[:, 0 if side == "users" else 1], minlength=len(table))[:len(table)]
+        ids = np.flatnonzero(degree >= min_ratings)
+        ids = ids[np.lexsort((ids, -surprise[ids]))][:m]
+        return pd.DataFrame({side: table.label(ids), "ratings": degree[ids].astype(np.int64),
+                             "surprise": surprise[ids], "fitted_surprise": fitted[ids]})
+
+    def misfit_users(self, m=None, min_ratings=2):
+        """The users the model explains worst: per user the mean ``surprise`` of its training rows
+        (``rating_reliability``), summed on the device.  Users with fewer than ``min_ratings`` training rows are left
+        out (the only row of a user is judged from the mean theta row, which says little about the user).
+
+        Returns a DataFrame with columns ``users``, ``ratings`` (the user's training rows), ``surprise``,
+        ``fitted_surprise`` (the same mean built from the in-sample ``fitted``), ``surprise`` descending, equal ones by
+        encoded id; ``m``: the first ``m`` rows (None: all)."""
+        return self._misfit("users", m, min_ratings)
+
+    def misfit_items(self, m=None, min_ratings=2):
+        """``misfit_users`` for the items: columns ``items``, ``ratings``, ``surprise``, ``fitted_surprise``."""
+        return self._misfit("items", m, min_ratings)
 
     # ------------------------------------------------------------------ nearest items / users (not in the reference)
     def similar_items(self, items=None, n=10):
