@@ -318,6 +318,32 @@ int mmsbm_hip_recommend_query_theta_within(mmsbm_hip_ctx *ctx, int64_t n_users, 
 int mmsbm_hip_recommend_rank(mmsbm_hip_ctx *ctx, int64_t n_users, const int32_t *users, const int64_t *offsets,
                              const int32_t *cand_items, int32_t n, int32_t *items, double *scores, int32_t *counts);
 
+/* Per-category caps, inside the open recommend session (mmsbm_amd/csrc/quota.hpp): at most cat_caps[g] items of
+ * category g in a row's list -- two per brand, one sponsored item, none of a category that is blocked (cap 0).
+ * Category g holds the catalogue items cat_items[cat_offsets[g] .. cat_offsets[g + 1]) (cat_offsets: int64
+ * [n_cats + 1]; ids of the session's catalogue, those of recommend_add_items included; strictly ascending inside a
+ * category, no item in two categories); an item in no category is uncapped.  The one definition: take query_within's
+ * full order of row b's candidates (score descending, equal scores by ascending item id; what query leaves out,
+ * cand_items and excl_* applied first), walk it, take an item unless cat_caps[g] items of its category were taken
+ * before it, stop after n.  A capped-out or excluded item never counts towards a category; the scores are query's bit
+ * for bit; a cap >= n has no effect; n_cats == 0 IS query_within (query_theta_within).  The answer is exact at any
+ * catalogue size: the walk equals the top n of the items whose rank inside their own category is at most the cap, which
+ * a mask over the batch's scores leaves before the unchanged selection.  Arguments and output otherwise as query_within
+ * / query_theta_within; "recommend_ms" reads the device time of the call's kernels.  MMSBM_E_INVALID (before any
+ * launch): what query_within / query_theta_within refuse, n_cats < 0, a bad CSR, an item id out of range, a category
+ * that is not strictly ascending, an item in two categories, a negative cap; n > MMSBM_HIP_RECOMMEND_MAX_N:
+ * MMSBM_E_UNSUPPORTED; MMSBM_E_TOOLARGE where the device memory is not free. */
+int mmsbm_hip_recommend_query_quota(mmsbm_hip_ctx *ctx, int64_t n_users, const int32_t *users, int32_t n_cand,
+                                    const int32_t *cand_items, const int64_t *excl_offsets, const int32_t *excl_items,
+                                    int64_t n_cats, const int64_t *cat_offsets, const int32_t *cat_items,
+                                    const int32_t *cat_caps, int32_t n, int32_t *items, double *scores,
+                                    int32_t *counts);
+int mmsbm_hip_recommend_query_theta_quota(mmsbm_hip_ctx *ctx, int64_t n_users, const double *theta,
+                                          const int64_t *seen_offsets, const int32_t *seen_items, int32_t n_cand,
+                                          const int32_t *cand_items, int64_t n_cats, const int64_t *cat_offsets,
+                                          const int32_t *cat_items, const int32_t *cat_caps, int32_t n, int32_t *items,
+                                          double *scores, int32_t *counts);
+
 /* ---- nearest items / users: the n most similar rows of one side (mmsbm_amd/csrc/similar.hpp) -------------------- */
 /* A session of its own beside the recommend session (either may be open while the other is):
  *   begin  side 0: items, 1: users (external sides).  Closes any earlier similarity session;

@@ -418,6 +418,50 @@ class HipEM:
                   _p(items, C.c_int32), _p(scores, C.c_double), _p(counts, C.c_int32))
         return items, scores, counts
 
+    @staticmethod
+    def _categories(cat_offsets, cat_items, caps):
+        """(caps int32, offsets int64, items int32) of the capped categories of the two quota queries."""
+        cap = _i32(caps)
+        off, it = _csr((cat_offsets, cat_items), len(cap), "category offsets", "cat_items")
+        return cap, off, it
+
+    def recommend_query_quota(self, users, n, cat_offsets, cat_items, caps, candidates=None, exclude=None):
+        """recommend_query_within with per-category caps: category g holds the catalogue items
+        cat_items[cat_offsets[g]:cat_offsets[g + 1]] (strictly ascending; no item in two categories; an item in none is
+        uncapped) and at most caps[g] >= 0 of them enter a row's list: the row's order is walked and an item taken
+        unless caps[g] items of its category were taken before it, until n are taken.  Scores and order are
+        recommend_query's; without categories the answer is recommend_query_within's.  Returns what it returns."""
+        u, n = _i32(users), int(n)
+        cand = None if candidates is None else _i32(candidates)
+        off, it = _csr(exclude, len(u), "exclude offsets", "items")
+        cap, coff, cit = self._categories(cat_offsets, cat_items, caps)
+        items, scores, counts = self._query_out(len(u), n)
+        _lib.call("mmsbm_hip_recommend_query_quota", self._h, len(u), _p(u, C.c_int32),
+                  0 if cand is None else len(cand), _p_or_null(cand, C.c_int32),
+                  _p_or_null(off, C.c_int64), _p_or_null(it, C.c_int32),
+                  len(cap), _p(coff, C.c_int64), _p(cit, C.c_int32), _p(cap, C.c_int32), n,
+                  _p(items, C.c_int32), _p(scores, C.c_double), _p(counts, C.c_int32))
+        return items, scores, counts
+
+    def recommend_query_theta_quota(self, theta, n, cat_offsets, cat_items, caps, seen=None, candidates=None):
+        """recommend_query_theta (caller-given theta rows (S, M, K), ``seen`` lists per row, ``candidates``) with the
+        per-category caps of recommend_query_quota."""
+        t = _f64(theta)
+        if t.ndim != 3 or t.shape[2] != self.k:
+            raise ValueError(f"theta has shape {t.shape}, expected (slots, users, {self.k})")
+        if t.shape[0] != self._rc_added:
+            raise ValueError(f"theta holds {t.shape[0]} blocks, the session {self._rc_added} added slots")
+        m, n = t.shape[1], int(n)
+        off, it = _csr(seen, m, "seen offsets", "items")
+        cand = None if candidates is None else _i32(candidates)
+        cap, coff, cit = self._categories(cat_offsets, cat_items, caps)
+        items, scores, counts = self._query_out(m, n)
+        _lib.call("mmsbm_hip_recommend_query_theta_quota", self._h, m, _p(t, C.c_double), _p_or_null(off, C.c_int64),
+                  _p_or_null(it, C.c_int32), 0 if cand is None else len(cand), _p_or_null(cand, C.c_int32),
+                  len(cap), _p(coff, C.c_int64), _p(cit, C.c_int32), _p(cap, C.c_int32), n,
+                  _p(items, C.c_int32), _p(scores, C.c_double), _p(counts, C.c_int32))
+        return items, scores, counts
+
     def recommend_rank(self, users, offsets, items, n):
         """The order of caller-given candidates, one list per request row: row b's candidates are
         items[offsets[b]:offsets[b + 1]] (ascending, distinct item ids of the session's catalogue) for encoded user

@@ -75,6 +75,17 @@ void recommend_query_theta_within(mmsbm_hip_ctx *c, int64_t n_users, const doubl
                                   double *scores, int32_t *counts);
 void recommend_rank(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, const int64_t *offsets,
                     const int32_t *cand, int n, int32_t *items, double *scores, int32_t *counts);
+// ... the same two queries with capped categories (quota.hpp): category g holds the catalogue items
+// cat_items[cat_offsets[g] .. cat_offsets[g + 1]) (strictly ascending; the categories disjoint), at most cat_caps[g] of
+// which enter a row's list
+void recommend_query_quota(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, const int32_t *cand, int n_cand,
+                           const int64_t *excl_offsets, const int32_t *excl_items, int64_t n_cats,
+                           const int64_t *cat_offsets, const int32_t *cat_items, const int32_t *cat_caps, int n,
+                           int32_t *items, double *scores, int32_t *counts);
+void recommend_query_theta_quota(mmsbm_hip_ctx *c, int64_t n_users, const double *theta, const int64_t *seen_offsets,
+                                 const int32_t *seen_items, const int32_t *cand, int n_cand, int64_t n_cats,
+                                 const int64_t *cat_offsets, const int32_t *cat_items, const int32_t *cat_caps, int n,
+                                 int32_t *items, double *scores, int32_t *counts);
 // ... and nearest items / users (similar.hpp): the session of mmsbm_hip_similar_*, arguments checked
 void similar_begin(mmsbm_hip_ctx *c, int side);
 void similar_add(mmsbm_hip_ctx *c);  // the selected slot (the caller holds a OneSlot)

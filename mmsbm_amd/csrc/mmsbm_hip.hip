@@ -668,6 +668,71 @@ int mmsbm_hip_recommend_query_theta_within(mmsbm_hip_ctx *ctx, int64_t n_users, 
   });
 }
 
+namespace {
+// The capped categories of the two *_quota entries: a CSR of n_cats categories over the catalogue's `top` items, each
+// strictly ascending, no item in two of them, no negative cap
+void require_categories(int64_t n_cats, const int64_t *cat_offsets, const int32_t *cat_items, const int32_t *cat_caps,
+                        int32_t top, const char *who) {
+  const std::string w = std::string(who) + ": ";
+  if (n_cats < 0) throw std::invalid_argument(w + "negative n_cats");
+  if (n_cats == 0) return;
+  if (!cat_offsets || !cat_caps) throw std::invalid_argument("null argument");
+  check_csr(cat_offsets, cat_items, n_cats, top, who, "cat_offsets", "category", "category items", "category item");
+  std::vector<bool> taken(static_cast<size_t>(top), false);
+  for (int64_t g = 0; g < n_cats; ++g) {
+    if (cat_caps[g] < 0) throw std::invalid_argument(w + "negative cap of category " + std::to_string(g));
+    for (int64_t e = cat_offsets[g]; e < cat_offsets[g + 1]; ++e) {
+      if (e > cat_offsets[g] && cat_items[e] <= cat_items[e - 1])
+        throw std::invalid_argument(w + "the items of a category must be ascending and distinct (entry " +
+                                    std::to_string(e) + ")");
+      if (taken[static_cast<size_t>(cat_items[e])])
+        throw std::invalid_argument(w + "item " + std::to_string(cat_items[e]) + " is in two categories (entry " +
+                                    std::to_string(e) + ")");
+      taken[static_cast<size_t>(cat_items[e])] = true;
+    }
+  }
+}
+}  // namespace
+
+int mmsbm_hip_recommend_query_quota(mmsbm_hip_ctx *ctx, int64_t n_users, const int32_t *users, int32_t n_cand,
+                                    const int32_t *cand_items, const int64_t *excl_offsets, const int32_t *excl_items,
+                                    int64_t n_cats, const int64_t *cat_offsets, const int32_t *cat_items,
+                                    const int32_t *cat_caps, int32_t n, int32_t *items, double *scores,
+                                    int32_t *counts) {
+  return guarded([&] {
+    const RecSession &rc = require_open(ctx, &mmsbm_hip_ctx::rc, "recommend", "recommend_query_quota");
+    if (n_users < 0) throw std::invalid_argument("negative n_users");
+    require_n(n, "recommend", "items");
+    if (n_users > 0 && (!users || !items)) throw std::invalid_argument("null argument");
+    require_ids(users, n_users, ctx->ext_users, "recommend: user");
+    require_subset(cand_items, n_cand, rc.items, "recommend_query_quota");
+    check_csr(excl_offsets, excl_items, n_users, rc.items, "recommend_query_quota", "excl_offsets", "user",
+              "excluded items", "excluded item");
+    require_categories(n_cats, cat_offsets, cat_items, cat_caps, rc.items, "recommend_query_quota");
+    recommend_query_quota(ctx, n_users, users, cand_items, n_cand, n_users > 0 ? excl_offsets : nullptr, excl_items,
+                          n_cats, cat_offsets, cat_items, cat_caps, n, items, scores, counts);
+  });
+}
+
+int mmsbm_hip_recommend_query_theta_quota(mmsbm_hip_ctx *ctx, int64_t n_users, const double *theta,
+                                          const int64_t *seen_offsets, const int32_t *seen_items, int32_t n_cand,
+                                          const int32_t *cand_items, int64_t n_cats, const int64_t *cat_offsets,
+                                          const int32_t *cat_items, const int32_t *cat_caps, int32_t n, int32_t *items,
+                                          double *scores, int32_t *counts) {
+  return guarded([&] {
+    const RecSession &rc = require_open(ctx, &mmsbm_hip_ctx::rc, "recommend", "recommend_query_theta_quota");
+    if (n_users < 0) throw std::invalid_argument("negative n_users");
+    require_n(n, "recommend", "items");
+    if (n_users > 0 && (!theta || !items)) throw std::invalid_argument("null argument");
+    require_subset(cand_items, n_cand, rc.items, "recommend_query_theta_quota");
+    check_csr(seen_offsets, seen_items, n_users, rc.items, "recommend", "seen_offsets", "user", "seen items",
+              "seen item");
+    require_categories(n_cats, cat_offsets, cat_items, cat_caps, rc.items, "recommend_query_theta_quota");
+    recommend_query_theta_quota(ctx, n_users, theta, seen_offsets, seen_items, cand_items, n_cand, n_cats, cat_offsets,
+                                cat_items, cat_caps, n, items, scores, counts);
+  });
+}
+
 int mmsbm_hip_recommend_rank(mmsbm_hip_ctx *ctx, int64_t n_users, const int32_t *users, const int64_t *offsets,
                              const int32_t *cand_items, int32_t n, int32_t *items, double *scores, int32_t *counts) {
   return guarded([&] {

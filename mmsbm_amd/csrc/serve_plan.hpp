@@ -57,6 +57,87 @@ inline std::pair<int, size_t> select_list(int n) {  // (places, LDS bytes)
   return {cap, static_cast<size_t>(cap) * (sizeof(double) + sizeof(int32_t))};
 }
 
+// ---- per-category caps (quota.hpp) -------------------------------------------------------------------------------------
+// What a query with capped categories uploads and launches with.  The categories are the caller's, as catalogue items
+// (each strictly ascending, no item in two of them: checked by the C ABI); here they become COLUMNS of the query's batch
+// buffer -- the item itself, or its place in the ascending candidate list (an item that is no candidate is dropped) --
+// and a category that cannot change the answer is dropped: one with m <= q columns (never full) or with q >= n (never
+// full within n picks).  The form of a kept category follows from (m, q) alone:
+//   short  m <= kQuotaShortMax: a sub-wave group of quota_width(m) lanes, 64 / width categories to a wave.  The short
+//          categories stand first, by ascending width, so that a wave's categories share one width;
+//   long   m >  kQuotaShortMax: one wave per (row, category) with a sorted list of q places.
+constexpr int kQuotaShortMax = kRecWave;  // columns of the largest category that shares a wave with others
+enum QuotaForm { kQuotaDropped = 0, kQuotaShort = 1, kQuotaLong = 2 };
+
+inline int quota_width(int m) {  // lanes of a short category: the next power of two >= m
+  int w = 1;
+  while (w < m) w <<= 1;
+  return w;
+}
+inline QuotaForm quota_form(int m, int q, int n) {
+  if (m <= q || q >= n) return kQuotaDropped;
+  return m <= kQuotaShortMax ? kQuotaShort : kQuotaLong;
+}
+
+struct QuotaPlan {
+  std::vector<int32_t> cat;             // per kept category: its place in the caller's request
+  std::vector<int32_t> off, col, cap;   // the kept categories' columns (CSR, ascending inside a category) and caps
+  int n_short = 0;                      // the first n_short kept categories take the short form, the others the long one
+  std::vector<int32_t> wave_first, wave_info;  // short form, per wave: its first category; width | categories << 8
+  int long_cap = 0;                     // the largest cap of a long category (sizes the waves' list)
+  int kept() const { return static_cast<int>(cat.size()); }
+  int n_long() const { return kept() - n_short; }
+  size_t bytes() const { return (off.size() + col.size() + cap.size() + wave_first.size() + wave_info.size()) * sizeof(int32_t); }
+};
+
+// cand: the query's ascending candidate list (null: the columns are the items)
+inline QuotaPlan plan_quota(const int32_t *cand, int n_cand, int64_t n_cats, const int64_t *cat_off,
+                            const int32_t *cat_items, const int32_t *caps, int n) {
+  QuotaPlan p;
+  std::vector<int32_t> cols;                // every category's columns, in request order
+  std::vector<int64_t> begin(static_cast<size_t>(n_cats) + 1, 0);
+  std::vector<int> form(static_cast<size_t>(n_cats), kQuotaDropped);
+  for (int64_t g = 0; g < n_cats; ++g) {
+    for (int64_t e = cat_off[g]; e < cat_off[g + 1]; ++e) {
+      if (!cand) {
+        cols.push_back(cat_items[e]);
+      } else {
+        const int32_t *at = std::lower_bound(cand, cand + n_cand, cat_items[e]);
+        if (at != cand + n_cand && *at == cat_items[e]) cols.push_back(static_cast<int32_t>(at - cand));
+      }
+    }
+    begin[static_cast<size_t>(g) + 1] = static_cast<int64_t>(cols.size());
+    const int64_t m = begin[static_cast<size_t>(g) + 1] - begin[static_cast<size_t>(g)];
+    form[static_cast<size_t>(g)] = quota_form(static_cast<int>(std::min<int64_t>(m, INT32_MAX)), caps[g], n);
+  }
+  auto keep = [&](int64_t g) {
+    p.cat.push_back(static_cast<int32_t>(g));
+    p.off.push_back(static_cast<int32_t>(p.col.size()));
+    p.col.insert(p.col.end(), cols.begin() + begin[static_cast<size_t>(g)], cols.begin() + begin[static_cast<size_t>(g) + 1]);
+    p.cap.push_back(caps[g]);
+  };
+  for (int w = 1; w <= kQuotaShortMax; w <<= 1) {  // the short categories by ascending width, 64 / w of them to a wave
+    const int first = p.kept();
+    for (int64_t g = 0; g < n_cats; ++g)
+      if (form[static_cast<size_t>(g)] == kQuotaShort &&
+          quota_width(static_cast<int>(begin[static_cast<size_t>(g) + 1] - begin[static_cast<size_t>(g)])) == w)
+        keep(g);
+    const int per = kRecWave / w;
+    for (int g0 = first; g0 < p.kept(); g0 += per) {
+      p.wave_first.push_back(g0);
+      p.wave_info.push_back(w | (std::min(per, p.kept() - g0) << 8));
+    }
+  }
+  p.n_short = p.kept();
+  for (int64_t g = 0; g < n_cats; ++g)
+    if (form[static_cast<size_t>(g)] == kQuotaLong) {
+      keep(g);
+      p.long_cap = std::max(p.long_cap, caps[g]);
+    }
+  p.off.push_back(static_cast<int32_t>(p.col.size()));
+  return p;
+}
+
 // ---- group queries (group.hpp) -----------------------------------------------------------------------------------------
 // What recommend_query_groups uploads and launches with.  The rows of the device request are the groups that have
 // members (an empty group has no candidate); their members stand in blocks of kGrpBlock rows, a group's last block

@@ -12,6 +12,7 @@
 //   group.hpp      group queries: the members' score tiles reduced per group, then the same selection
 //   ensemble.hpp   ensemble-aware queries: the restarts' scores reduced per pair (min, max, mean - risk std), then the
 //                  same selection; the spread of given pairs
+//   quota.hpp      per-category caps: a mask over the batch buffer between the exclusions and the same selection
 #include "prelude.hpp"
 #include "recommend.hpp"
 #include "similar.hpp"
@@ -23,6 +24,7 @@
 #include "inform.hpp"
 #include "group.hpp"
 #include "ensemble.hpp"
+#include "quota.hpp"
 
 namespace mmsbm_hip_impl {
 
@@ -362,6 +364,36 @@ void rec_run(mmsbm_hip_ctx *c, const double *x, size_t xs, int64_t n_users, cons
             T_RECOMMEND, items, scores, counts);
 }
 
+// The capped categories of a query on the device (quota.hpp): the plan of serve_plan.hpp, held for as long as the mask
+// lives (the copies are asynchronous), and the launches that apply it to a batch buffer
+struct QuotaMask {
+  QuotaPlan plan;
+  DevBuf<int32_t> off, col, cap, wave_first, wave_info;
+  void upload(QuotaPlan &&p, hipStream_t st) {
+    plan = std::move(p);
+    off.upload(plan.off, st);
+    col.upload(plan.col, st);
+    cap.upload(plan.cap, st);
+    wave_first.upload(plan.wave_first, st);
+    wave_info.upload(plan.wave_info, st);
+  }
+  // sc [nb][ld]: every row masked, each category by the form its (m, q) selects
+  void apply(hipStream_t st, int nb, double *sc, size_t ld) const {
+    const int waves = static_cast<int>(plan.wave_first.size());
+    if (waves > 0)
+      LAUNCH(quota_short_kernel, dim3(static_cast<unsigned>((waves + kQuotaWaves - 1) / kQuotaWaves), nb), kBlock, 0, st,
+             static_cast<const int32_t *>(wave_first.ptr), static_cast<const int32_t *>(wave_info.ptr), waves,
+             static_cast<const int32_t *>(off.ptr), static_cast<const int32_t *>(col.ptr),
+             static_cast<const int32_t *>(cap.ptr), sc, ld);
+    if (plan.n_long() > 0) {
+      const auto [places, lds] = select_list(plan.long_cap);
+      LAUNCH(quota_long_kernel, dim3(static_cast<unsigned>(plan.n_long()), nb), kRecWave, lds, st,
+             static_cast<const int32_t *>(off.ptr), static_cast<const int32_t *>(col.ptr),
+             static_cast<const int32_t *>(cap.ptr), plan.n_short, places, sc, ld);
+    }
+  }
+};
+
 // The compact item table of a candidate subset (catalogue.hpp): the candidates on the device, every catalogue item's
 // column and the candidates' rows of the session's item table, and the device time of the two kernels that make them
 struct CatTable {
@@ -399,11 +431,12 @@ void cat_table(mmsbm_hip_ctx *c, const int32_t *cand, int C, CatTable &t) {
 // the score tiles of recommend_query (rec_tiles), the aggregate over the restarts (ensemble.hpp); seen (indexed by user
 // id): the items left out after it.  The result stays on the device (top_n_device): `then(dev, ev, dcand, prep_ms)` gets
 // it -- as COLUMNS of the candidate list when there is one --, the candidate list on the device (or null) and the device
-// time of the compact table and the columns.  n_users > 0 and at least one column.
+// time of the compact table and the columns.  n_users > 0 and at least one column.  quota: the capped categories
+// (uploaded; in the buffer's columns), applied after the exclusions; null: none.
 template <class Tiles, class Then>
 void rec_within_device(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, SeenLists seen, const int32_t *cand,
                        int n_cand, const int64_t *xoff, const int32_t *xit, int n, size_t extra, Tiles &&tiles,
-                       Then &&then) {
+                       Then &&then, const QuotaMask *quota = nullptr) {
   const RecSession &rc = *c->rc;
   const int NI = rc.items, rank = rc.rank, S = rc.slots;
   const int C = cand ? n_cand : NI;
@@ -420,7 +453,7 @@ void rec_within_device(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, 
   const double *y = cand ? ct.y.ptr : rc.y.ptr;
   const size_t ys = cand ? ycs : static_cast<size_t>(NI) * rank;
   top_n_device(c, C, n_users, users, n,
-               cand || xoff ? "recommend: a batch of users within the candidates" : "recommend: a batch of users", extra,
+               cand || xoff || quota ? "recommend: a batch of users within the candidates" : "recommend: a batch of users", extra,
                [&](const int32_t *ub, int nb, int64_t b0, double *sc) {
                  tiles(y, ys, C, ub, nb, sc);
                  if (seen.off) {
@@ -430,6 +463,7 @@ void rec_within_device(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, 
                      LAUNCH(rec_exclude_kernel, nb, kBlock, 0, st, ub, seen.off, seen.items, sc, static_cast<size_t>(C));
                  }
                  if (xoff) own_exclude_batch(st, own, b0, nb, ct.col.ptr, sc, static_cast<size_t>(C));
+                 if (quota) quota->apply(st, nb, sc, static_cast<size_t>(C));
                },
                [&](const TopNDev &dev, EventPair &ev) { then(dev, ev, cand ? ct.cand.ptr : nullptr, ct.ms); });
 }
@@ -446,37 +480,56 @@ auto rec_tiles(mmsbm_hip_ctx *c, const double *x, size_t xs) {
 template <class Tiles>
 void rec_within_run(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, SeenLists seen, const int32_t *cand,
                     int n_cand, const int64_t *xoff, const int32_t *xit, int n, Tiles &&tiles, TimedCall timed,
-                    int32_t *items, double *scores, int32_t *counts) {
+                    int32_t *items, double *scores, int32_t *counts, const QuotaMask *quota = nullptr) {
   c->last_ms[timed] = 0.f;
   if ((cand ? n_cand : c->rc->items) == 0 || n_users == 0) return;
   rec_within_device(c, n_users, users, seen, cand, n_cand, xoff, xit, n, 0, tiles,
                     [&](const TopNDev &dev, EventPair &ev, const int32_t *, float prep_ms) {
                       top_n_copy_out(c, dev, ev, n_users, n, timed, items, scores, counts);
                       c->last_ms[timed] += prep_ms;
-                    });
+                    },
+                    quota);
   if (cand)  // columns -> item ids
     for (size_t e = 0; e < static_cast<size_t>(n_users) * n; ++e)
       if (items[e] >= 0) items[e] = cand[items[e]];
 }
 
-// rec_run within the candidates and without the query's own excluded items.  Without candidates and own lists: rec_run.
+// The capped categories of a query (quota.hpp): cat_items[cat_off[g] .. cat_off[g + 1]) (host; catalogue ids, each
+// category strictly ascending, the categories disjoint) with cap caps[g], planned against the candidates (serve_plan.hpp)
+struct QuotaCats {
+  int64_t n_cats = 0;
+  const int64_t *off = nullptr;
+  const int32_t *items = nullptr, *caps = nullptr;
+};
+
+// rec_run within the candidates, without the query's own excluded items and with the capped categories `cats` (null:
+// none).  Without candidates, own lists and a category that can change the answer: rec_run.
 void rec_run_within(mmsbm_hip_ctx *c, const double *x, size_t xs, int64_t n_users, const int32_t *users, SeenLists seen,
                     const int32_t *cand, int n_cand, const int64_t *xoff, const int32_t *xit, int n, int32_t *items,
-                    double *scores, int32_t *counts) {
-  if (!cand && !xoff) {
+                    double *scores, int32_t *counts, const QuotaCats *cats = nullptr) {
+  QuotaMask mask;
+  if (cats && cats->n_cats > 0 && n_users > 0 && (cand ? n_cand : c->rc->items) > 0) {
+    QuotaPlan plan = plan_quota(cand, n_cand, cats->n_cats, cats->off, cats->items, cats->caps, n);
+    if (plan.kept() > 0) {
+      require_free_mem(plan.bytes(), "recommend: the capped categories");
+      mask.upload(std::move(plan), c->stream);
+    }
+  }
+  const bool masked = mask.plan.kept() > 0;
+  if (!cand && !xoff && !masked) {
     rec_run(c, x, xs, n_users, users, seen, n, items, scores, counts);
     return;
   }
   top_n_blank(n_users, n, items, scores, counts);
   rec_within_run(c, n_users, users, seen, cand, n_cand, xoff, xit, n, rec_tiles(c, x, xs), T_RECOMMEND, items, scores,
-                 counts);
+                 counts, masked ? &mask : nullptr);
 }
 
 // The caller's theta rows [S][n_users][K] folded exactly as recommend_add folds a slot's own theta (x = theta, or
 // theta W when K > L), then rec_run_within over the rows 0 .. n_users - 1 with the caller's seen lists
 void rec_theta_run(mmsbm_hip_ctx *c, int64_t n_users, const double *theta, const int64_t *seen_offsets,
                    const int32_t *seen_items, const int32_t *cand, int n_cand, int n, int32_t *items, double *scores,
-                   int32_t *counts) {
+                   int32_t *counts, const QuotaCats *cats = nullptr) {
   const int K = c->ext_k, L = c->ext_l, rank = c->rc->rank, S = c->rc->slots;
   const size_t tk = static_cast<size_t>(n_users) * K, xs = static_cast<size_t>(n_users) * rank;
   require_free_mem(S * (tk + xs) * sizeof(double) +
@@ -495,7 +548,7 @@ void rec_theta_run(mmsbm_hip_ctx *c, int64_t n_users, const double *theta, const
   }
   HIP_CHECK(hipGetLastError());
   rec_run_within(c, x.ptr, xs, n_users, rows.ids.data(), rows.seen.lists(), cand, n_cand, nullptr, nullptr, n, items,
-                 scores, counts);
+                 scores, counts, cats);
 }
 
 }  // namespace
@@ -527,6 +580,26 @@ void recommend_query_theta_within(mmsbm_hip_ctx *c, int64_t n_users, const doubl
                                   double *scores, int32_t *counts) {
   use_device(c);
   rec_theta_run(c, n_users, theta, seen_offsets, seen_items, cand, n_cand, n, items, scores, counts);
+}
+
+void recommend_query_quota(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, const int32_t *cand, int n_cand,
+                           const int64_t *excl_offsets, const int32_t *excl_items, int64_t n_cats,
+                           const int64_t *cat_offsets, const int32_t *cat_items, const int32_t *cat_caps, int n,
+                           int32_t *items, double *scores, int32_t *counts) {
+  use_device(c);
+  const RecSession &rc = *c->rc;
+  const QuotaCats cats{n_cats, cat_offsets, cat_items, cat_caps};
+  rec_run_within(c, rc.x.ptr, rc.x_stride(), n_users, users, rc.seen_lists(), cand, n_cand, excl_offsets, excl_items, n,
+                 items, scores, counts, &cats);
+}
+
+void recommend_query_theta_quota(mmsbm_hip_ctx *c, int64_t n_users, const double *theta, const int64_t *seen_offsets,
+                                 const int32_t *seen_items, const int32_t *cand, int n_cand, int64_t n_cats,
+                                 const int64_t *cat_offsets, const int32_t *cat_items, const int32_t *cat_caps, int n,
+                                 int32_t *items, double *scores, int32_t *counts) {
+  use_device(c);
+  const QuotaCats cats{n_cats, cat_offsets, cat_items, cat_caps};
+  rec_theta_run(c, n_users, theta, seen_offsets, seen_items, cand, n_cand, n, items, scores, counts, &cats);
 }
 
 void recommend_rank(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, const int64_t *offsets,

@@ -58,6 +58,76 @@ def group_slice(lists, b, e):
     return off[b:e + 1] - off[b], values[off[b]:off[e]]
 
 
+# ---------------------------------------------------------------------- capped categories
+class Quota:
+    """The capped categories of ``recommend_quota`` in encoded terms: category g holds the items
+    ``items[offsets[g]:offsets[g + 1]]`` (ascending) with cap ``caps[g]``; ``category_of`` (one per item of the side):
+    the place of the item's category in ``labels`` (the caller's labels, capped or not), or -1."""
+
+    def __init__(self, offsets, items, caps, category_of, labels):
+        self.offsets, self.items, self.caps, self.category_of, self.labels = offsets, items, caps, category_of, labels
+
+    def label(self, ids):
+        """The caller's category label of each encoded item id, None where it has none."""
+        table = np.empty(len(self.labels) + 1, dtype=object)
+        table[:-1] = self.labels
+        table[-1] = None
+        return table[self.category_of[np.asarray(ids, dtype=np.int64)]]
+
+
+def quota_categories(categories, max_per_category, items):
+    """``recommend_quota``'s ``categories`` and ``max_per_category`` against the item table ``items`` (a ``_Side``; no
+    context is needed) -> ``Quota``.
+
+    ``categories``: a dict {item label: category}, a Series indexed by item, or a DataFrame whose first two columns are
+    item and category.  Items the side does not have are ignored, a missing category (None / NaN) leaves the item
+    uncapped, an item given two different categories is a ValueError.  ``max_per_category``: an integer >= 0 for every
+    category, or a dict {category: integer >= 0} -- categories it does not name are uncapped."""
+    if isinstance(categories, dict):
+        labs, cats = list(categories.keys()), list(categories.values())
+    elif isinstance(categories, pd.DataFrame):
+        if categories.shape[1] < 2:
+            raise ValueError("categories needs two columns: items and categories")
+        labs, cats = categories.iloc[:, 0].tolist(), categories.iloc[:, 1].tolist()
+    elif isinstance(categories, pd.Series):
+        labs, cats = categories.index.tolist(), categories.tolist()
+    else:
+        raise ValueError("categories must be a dict {item: category}, a Series indexed by item or a DataFrame of "
+                         f"(item, category) rows, got {type(categories).__name__}")
+    must_be = "an integer >= 0 or a dict {category: integer >= 0}"
+    if isinstance(max_per_category, dict):
+        per = {c: check_integer(v, f"max_per_category[{c!r}]", 0, "an integer >= 0") for c, v in max_per_category.items()}
+        cap_of = lambda c: per.get(c, -1)                                      # noqa: E731  (-1: uncapped)
+    else:
+        every = check_integer(max_per_category, "max_per_category", 0, must_be)
+        cap_of = lambda c: every                                               # noqa: E731
+    ids = items.ids(labs)
+    held = np.empty(len(cats), dtype=object)
+    for j, c in enumerate(cats):
+        held[j] = c
+    keep = (ids >= 0) & ~np.fromiter((c is None or (isinstance(c, (float, np.floating)) and np.isnan(c)) or c is pd.NaT
+                                      or c is pd.NA for c in cats), dtype=bool, count=len(cats))
+    ids, (codes, labels) = ids[keep].astype(np.int64), pd.factorize(held[keep])
+    order = np.lexsort((codes, ids))
+    ids, codes = ids[order], codes[order]
+    clash = np.flatnonzero((ids[1:] == ids[:-1]) & (codes[1:] != codes[:-1]))
+    if len(clash):
+        raise ValueError(f"items given two different categories: {list(dict.fromkeys(items.label(ids[clash]).tolist()))[:10]}")
+    first = np.ones(len(ids), dtype=bool)
+    first[1:] = ids[1:] != ids[:-1]
+    ids, codes = ids[first], codes[first]
+    category_of = np.full(len(items), -1, dtype=np.int64)
+    category_of[ids] = codes
+    labels = list(labels)
+    cap = np.array([cap_of(c) for c in labels], dtype=np.int64)
+    capped = np.flatnonzero(cap >= 0)
+    place = np.full(len(labels), -1, dtype=np.int64)
+    place[capped] = np.arange(len(capped))
+    mine = place[codes] >= 0
+    offsets, members = grouped(place[codes][mine], ids[mine], len(capped), sort=True)
+    return Quota(offsets, members, cap[capped].astype(np.int32), category_of, labels)
+
+
 # ---------------------------------------------------------------------- labels of a side
 class _Side:
     """The users, the items or the ratings of a fitted model: how many there are, the label of an id and the id of a
@@ -253,16 +323,20 @@ class Serving:
                  for c, how in columns.items()}
         return pd.DataFrame({**{c: [] for c in rows}, **empty})
 
-    def _top_n_frame(self, query, n, row_labels, side, columns=("users", "items", "score")):
+    def _top_n_frame(self, query, n, row_labels, side, columns=("users", "items", "score"), derived=None):
         """The top-``n`` frame (users, items, score, rank) of rows [0, len(row_labels)), fetched in calls of at most
         RECOMMEND_BATCH_ROWS result rows: ``query(b, e)`` -> (ids, values, ..., counts) of rows [b, e), each (e - b, n)
         but the counts.  ``side``: the ``_Side`` of the returned ids.  ``columns``: the names of the row, the
-        returned-id and the value columns (similar_items / similar_users; recommend_diverse has two value columns)."""
+        returned-id and the value columns (similar_items / similar_users; recommend_diverse has two value columns).
+        ``derived``: {column: function of the returned ids} of columns behind ``rank`` (recommend_quota's category)."""
         def entries(b, e):
             *padded, counts = query(b, e)
             return counts, dict(zip(columns[1:], padded))
         made = {columns[1]: side, **dict.fromkeys(columns[2:]), "rank": None}
-        return self._frame({columns[0]: row_labels}, made, self._row_batches(len(row_labels), n), entries, n)
+        for name, of_ids in (derived or {}).items():
+            made[name] = lambda got, of_ids=of_ids: of_ids(got[columns[1]])
+        frame = self._frame({columns[0]: row_labels}, made, self._row_batches(len(row_labels), n), entries, n)
+        return frame.astype(dict.fromkeys(derived, object)) if derived and not len(frame) else frame
 
     # ------------------------------------------------------------------ recommendation (not in the reference)
     def recommend(self, users=None, n=10, exclude_seen=True, weights=None, candidates=None, exclude=None):
@@ -295,6 +369,41 @@ class Serving:
         with self._session_of_restarts("recommend", w, exclude_seen) as ctx:
             return self._top_n_frame(
                 lambda b, e: ctx.recommend_query_within(ids[b:e], n, cand, group_slice(extra, b, e)), n, labels, items)
+
+    def recommend_quota(self, users=None, n=10, categories=..., max_per_category=..., exclude_seen=True, weights=None,
+                        candidates=None, exclude=None):
+        """``recommend`` with a hard cap per category: at most ``max_per_category`` items of one category in a user's
+        list -- two per brand, one sponsored item, none of a category that is blocked (cap 0).  The definition: the
+        user's full order of ``recommend`` (score descending, equal scores by ascending encoded item id; the user's own
+        items, ``candidates`` and ``exclude`` applied first) is walked and an item taken unless its category is full,
+        until ``n`` are taken.  Exact at any catalogue size and on the device: nothing is over-fetched or tuned.
+
+        ``categories`` (required): a dict {item label: category}, a Series indexed by item, or a DataFrame whose first
+        two columns are item and category.  Items that are not training items are ignored (a shop's table is larger
+        than the model); an item it does not name, or whose category is None / NaN, is uncapped; an item given two
+        different categories: ValueError.  ``max_per_category`` (required): an integer >= 0 for every category, or a
+        dict {category: integer >= 0} -- categories it does not name are uncapped.  The other arguments are
+        ``recommend``'s.
+
+        Returns ``recommend``'s frame (``users``, ``items``, ``score``, ``rank``) plus ``category``: the caller's label
+        of the item's category, or None.  Scores are ``recommend``'s, bit for bit; users in request order.  The
+        model's stored predictions and ``score()`` are left as they are."""
+        if categories is ... or max_per_category is ...:
+            raise TypeError("recommend_quota needs categories= and max_per_category=")
+        self._check_whole_model()
+        n, w = self._recommend_args(n, weights)
+        ids, labels = self._side("users").request(users)
+        items = self._side("items")
+        quota = quota_categories(categories, max_per_category, items)
+        cand = self._candidate_ids(candidates)
+        derived = {"category": quota.label}
+        if cand is not None and len(cand) == 0:
+            return self._top_n_frame(None, n, labels[:0], items, derived=derived)
+        extra = self._exclusion_lists(exclude, ids)
+        with self._session_of_restarts("recommend", w, exclude_seen) as ctx:
+            return self._top_n_frame(
+                lambda b, e: ctx.recommend_query_quota(ids[b:e], n, quota.offsets, quota.items, quota.caps, cand,
+                                                       group_slice(extra, b, e)), n, labels, items, derived=derived)
 
     def rerank(self, pairs, n=None, exclude_seen=True, weights=None):
         """The order of caller-given candidates per user -- the second stage of a two-stage system: a cheap retriever
@@ -954,6 +1063,20 @@ class Serving:
         the frame ``recommend`` returns (users, items, score, rank), users in order of first appearance in ``data``;
         ``exclude_seen`` leaves out the items a user has in ``data``; ``candidates`` as in ``recommend``: only these
         items are scored and ranked."""
+        return self._recommend_new(data, n, exclude_seen, weights, iterations, tol, candidates, None)
+
+    def recommend_new_quota(self, data, n=10, categories=..., max_per_category=..., exclude_seen=True, weights=None,
+                            iterations=100, tol=None, candidates=None):
+        """``recommend_new`` with ``recommend_quota``'s cap per category (``categories`` and ``max_per_category`` as
+        there, both required): ``recommend_new``'s frame plus the ``category`` column."""
+        if categories is ... or max_per_category is ...:
+            raise TypeError("recommend_new_quota needs categories= and max_per_category=")
+        self._check_whole_model()
+        quota = quota_categories(categories, max_per_category, self._side("items"))
+        return self._recommend_new(data, n, exclude_seen, weights, iterations, tol, candidates, quota)
+
+    def _recommend_new(self, data, n, exclude_seen, weights, iterations, tol, candidates, quota):
+        """recommend_new (``quota`` None) and recommend_new_quota (a ``Quota``)."""
         self._check_whole_model()
         n, w = self._recommend_args(n, weights)
         cand = self._candidate_ids(candidates)
@@ -965,9 +1088,14 @@ class Serving:
             self.fold_in_iterations = pd.DataFrame(np.stack(iters, 1), index=pd.Index(labels, name="users"))
             theta = np.stack(thetas)                                  # (restarts, new users, K)
             seen = grouped(rows[:, 0], rows[:, 1], len(labels), sort=True) if exclude_seen else None
+            if quota is None:
+                return self._top_n_frame(
+                    lambda b, e: ctx.recommend_query_theta(theta[:, b:e], n, group_slice(seen, b, e), **within),
+                    n, labels, self._side("items"))
             return self._top_n_frame(
-                lambda b, e: ctx.recommend_query_theta(theta[:, b:e], n, group_slice(seen, b, e), **within),
-                n, labels, self._side("items"))
+                lambda b, e: ctx.recommend_query_theta_quota(theta[:, b:e], n, quota.offsets, quota.items, quota.caps,
+                                                             group_slice(seen, b, e), **within),
+                n, labels, self._side("items"), derived={"category": quota.label})
 
     def fold_in_items(self, data, iterations=100, tol=None):
         """eta of items that were not in the training data, from their ratings: ``iterations`` steps of the eta half of
