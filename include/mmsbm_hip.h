@@ -344,6 +344,28 @@ int mmsbm_hip_recommend_query_theta_quota(mmsbm_hip_ctx *ctx, int64_t n_users, c
                                           const int32_t *cat_items, const int32_t *cat_caps, int32_t n, int32_t *items,
                                           double *scores, int32_t *counts);
 
+/* Capacity-aware allocation, inside the open recommend session (mmsbm_amd/csrc/allocate.hpp): items run out.  Every
+ * user of the request asks for n items, item i of the session's catalogue (the items of recommend_add_items included)
+ * can be given out caps[i] times: stock, a reviewer's load, coupons per product.  The one definition: take all pairs
+ * (u, i) of the request's users and the catalogue that query does not leave out for u, walk them in top_pairs' order
+ * (score descending, equal scores by ascending user id, then ascending item id) and take a pair iff u holds fewer than n
+ * items and i was given out fewer than caps[i] times.  caps[i] = 0 takes the item out, a negative cap -- and a cap >=
+ * n_users -- is unlimited; with every cap unlimited the answer IS query's, and the scores are always query's bits.
+ * users: DISTINCT ids (the constraint couples users, not request rows), or NULL: all training users, n_users = their
+ * number.  The answer is computed by rounds of user-proposing deferred acceptance, which reach the walk's answer -- the
+ * only stable matching under one strict order of the pairs -- without sorting the pairs; *rounds: the rounds run,
+ * *converged: 1 when the last of them changed nothing.  After max_rounds rounds that still changed a threshold the
+ * answer is cut to a feasible one (rows of at most n, no item beyond its cap; some users may hold fewer items than the
+ * walk gives them) and *converged is 0.  Output otherwise as query: rows padded with -1 / -inf, counts[b] the length of
+ * row b, which may be below n.  Options "allocate_ms" (device time of the whole call, HIP events) and "allocate_rounds".
+ * MMSBM_E_INVALID (before any launch): no session or no slot added, an id out of range, a repeated user id, n < 1,
+ * max_rounds < 1, a null caps, rounds or converged; MMSBM_E_UNSUPPORTED: n > MMSBM_HIP_RECOMMEND_MAX_N, or a cap above
+ * MMSBM_HIP_RECOMMEND_MAX_N and below n_users (it could bind beyond what a selection holds); MMSBM_E_TOOLARGE where the
+ * device memory is not free.  Touches no slot and no other session; later queries of the session answer as before. */
+int mmsbm_hip_recommend_allocate(mmsbm_hip_ctx *ctx, int64_t n_users, const int32_t *users, int32_t n,
+                                 const int32_t *caps, int32_t max_rounds, int32_t *items, double *scores,
+                                 int32_t *counts, int32_t *rounds, int32_t *converged);
+
 /* ---- nearest items / users: the n most similar rows of one side (mmsbm_amd/csrc/similar.hpp) -------------------- */
 /* A session of its own beside the recommend session (either may be open while the other is):
  *   begin  side 0: items, 1: users (external sides).  Closes any earlier similarity session;

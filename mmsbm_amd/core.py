@@ -523,6 +523,24 @@ class HipEM:
         id; the pair (u, i) is left out exactly when recommend_query leaves i out for u."""
         return self._top_n("mmsbm_hip_recommend_query_items", items, n)
 
+    def recommend_allocate(self, users, n, caps, max_rounds=10000):
+        """Capacity-aware allocation inside the open session: every user of ``users`` (distinct encoded ids; None: all
+        training users) asks for n items, item i of the session's catalogue can be given out caps[i] times (0: not at
+        all, negative: unlimited).  The answer is the walk over all candidate pairs in top_pairs' order that takes a
+        pair iff its user holds fewer than n items and its item is not used up.  Returns (items, scores, counts) as
+        recommend_query -- a row may hold fewer than n -- and {"rounds", "converged"}: the rounds of deferred
+        acceptance it took, and whether they reached the fixed point within ``max_rounds`` (if not, the answer is
+        feasible but not the walk's)."""
+        u = None if users is None else _i32(users)
+        m, n = self.n_users if u is None else len(u), int(n)
+        cap = _i32(caps)
+        items, scores, counts = self._query_out(m, n)
+        rounds, converged = C.c_int32(0), C.c_int32(0)
+        _lib.call("mmsbm_hip_recommend_allocate", self._h, m, _p_or_null(u, C.c_int32), n, _p(cap, C.c_int32),
+                  int(max_rounds), _p(items, C.c_int32), _p(scores, C.c_double), _p(counts, C.c_int32),
+                  C.byref(rounds), C.byref(converged))
+        return items, scores, counts, {"rounds": int(rounds.value), "converged": bool(converged.value)}
+
     def recommend_audience(self, items, min_score, count_only=False, total=None):
         """(offsets (M+1,) int64, users int32, scores): for each item id every candidate user whose score is >=
         min_score, in ascending user id -- item b's are [offsets[b]:offsets[b + 1]].  A sizes call followed by a

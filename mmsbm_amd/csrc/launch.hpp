@@ -86,6 +86,11 @@ void recommend_query_theta_quota(mmsbm_hip_ctx *c, int64_t n_users, const double
                                  const int32_t *seen_items, const int32_t *cand, int n_cand, int64_t n_cats,
                                  const int64_t *cat_offsets, const int32_t *cat_items, const int32_t *cat_caps, int n,
                                  int32_t *items, double *scores, int32_t *counts);
+// ... capacity-aware allocation (allocate.hpp): every user of the request (distinct ids) asks for n items, the caps as
+// planned by plan_allocate (serve_plan.hpp); at most max_rounds rounds
+void recommend_allocate(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, int n, const AllocPlan &plan,
+                        int max_rounds, int32_t *items, double *scores, int32_t *counts, int32_t *rounds,
+                        int32_t *converged);
 // ... and nearest items / users (similar.hpp): the session of mmsbm_hip_similar_*, arguments checked
 void similar_begin(mmsbm_hip_ctx *c, int side);
 void similar_add(mmsbm_hip_ctx *c);  // the selected slot (the caller holds a OneSlot)

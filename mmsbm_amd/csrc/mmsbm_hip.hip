@@ -600,6 +600,42 @@ int mmsbm_hip_recommend_query_items(mmsbm_hip_ctx *ctx, int64_t n_items, const i
   });
 }
 
+int mmsbm_hip_recommend_allocate(mmsbm_hip_ctx *ctx, int64_t n_users, const int32_t *users, int32_t n,
+                                 const int32_t *caps, int32_t max_rounds, int32_t *items, double *scores,
+                                 int32_t *counts, int32_t *rounds, int32_t *converged) {
+  return guarded([&] {
+    const RecSession &rc = require_open(ctx, &mmsbm_hip_ctx::rc, "recommend", "recommend_allocate");
+    if (n_users < 0) throw std::invalid_argument("negative n_users");
+    require_n(n, "recommend_allocate", "items");
+    if (max_rounds < 1) throw std::invalid_argument("recommend_allocate: max_rounds must be at least 1");
+    if (!caps || !rounds || !converged || (n_users > 0 && !items)) throw std::invalid_argument("null argument");
+    std::vector<int32_t> all;
+    if (!users) {  // all training users
+      if (n_users != ctx->ext_users)
+        throw std::invalid_argument("recommend_allocate: without users, n_users must be the number of training users");
+      all.resize(static_cast<size_t>(n_users));
+      for (int64_t b = 0; b < n_users; ++b) all[static_cast<size_t>(b)] = static_cast<int32_t>(b);
+      users = all.data();
+    } else {
+      require_ids(users, n_users, ctx->ext_users, "recommend_allocate: user");
+      std::vector<bool> asked(static_cast<size_t>(ctx->ext_users), false);
+      for (int64_t b = 0; b < n_users; ++b) {
+        if (asked[static_cast<size_t>(users[b])])
+          throw std::invalid_argument("recommend_allocate: user " + std::to_string(users[b]) + " is asked twice (row " +
+                                      std::to_string(b) + ")");
+        asked[static_cast<size_t>(users[b])] = true;
+      }
+    }
+    const AllocPlan plan = plan_allocate(caps, rc.items, n_users, ctx->ext_users, MMSBM_HIP_RECOMMEND_MAX_N);
+    if (plan.refused >= 0)
+      throw ApiError(MMSBM_E_UNSUPPORTED, "recommend_allocate: the cap of item " + std::to_string(plan.refused) + ", " +
+                                              std::to_string(caps[plan.refused]) + ", is above " +
+                                              std::to_string(MMSBM_HIP_RECOMMEND_MAX_N) + " and below the " +
+                                              std::to_string(n_users) + " users of the request");
+    recommend_allocate(ctx, n_users, users, n, plan, max_rounds, items, scores, counts, rounds, converged);
+  });
+}
+
 int mmsbm_hip_recommend_audience(mmsbm_hip_ctx *ctx, int64_t n_items, const int32_t *items, double min_score,
                                  int64_t capacity, int64_t *offsets, int32_t *users, double *scores) {
   return guarded([&] {

@@ -138,6 +138,49 @@ inline QuotaPlan plan_quota(const int32_t *cand, int n_cand, int64_t n_cats, con
   return p;
 }
 
+// ---- capacity-aware allocation (allocate.hpp) ----------------------------------------------------------------------------
+// What recommend_allocate makes of the caller's caps, one per catalogue item, for a request of n_users users: a negative
+// cap and a cap >= n_users never bind (every user of the request may hold the item), cap 0 closes the item, and the
+// items in between are the CAPPED ones -- the rows of the item pass, in batches of rec_batch_users over the U user
+// columns, each batch selecting with n = its largest cap.  A cap that binds beyond max_n places is not supported.
+struct AllocPlan {
+  std::vector<int32_t> item, cap;  // the capped items, ascending, and their caps (1 .. min(max_n, n_users - 1))
+  std::vector<int32_t> closed;     // the items with cap 0
+  int64_t refused = -1;            // the first item whose cap lies in (max_n, n_users); nothing below is filled in
+  int64_t bi = 0;                  // capped items per batch of the item pass
+  std::vector<int32_t> batch_n;    // per batch: its largest cap
+  int most_n = 0;                  // the largest cap of all
+  int64_t capped() const { return static_cast<int64_t>(item.size()); }
+};
+
+// force_bi > 0: that many items per batch instead of rec_batch_users (the CPU check: batches without 128 MB shapes)
+inline AllocPlan plan_allocate(const int32_t *caps, int n_items, int64_t n_users, int U, int max_n, int64_t force_bi = 0) {
+  AllocPlan p;
+  for (int i = 0; i < n_items; ++i) {
+    const int64_t q = caps[i];
+    if (q < 0 || q >= n_users) continue;
+    if (q > max_n) {
+      AllocPlan none;
+      none.refused = i;
+      return none;
+    }
+    if (q == 0) {
+      p.closed.push_back(i);
+    } else {
+      p.item.push_back(i);
+      p.cap.push_back(static_cast<int32_t>(q));
+    }
+  }
+  if (p.item.empty()) return p;
+  p.bi = force_bi > 0 ? std::min(force_bi, p.capped()) : rec_batch_users(U, p.capped());
+  for (int64_t r0 = 0; r0 < p.capped(); r0 += p.bi) {
+    const int64_t r1 = std::min(p.capped(), r0 + p.bi);
+    p.batch_n.push_back(*std::max_element(p.cap.begin() + r0, p.cap.begin() + r1));
+    p.most_n = std::max(p.most_n, p.batch_n.back());
+  }
+  return p;
+}
+
 // ---- group queries (group.hpp) -----------------------------------------------------------------------------------------
 // What recommend_query_groups uploads and launches with.  The rows of the device request are the groups that have
 // members (an empty group has no candidate); their members stand in blocks of kGrpBlock rows, a group's last block

@@ -60,6 +60,9 @@ const Option kOptions[] = {
     {"loo_ms", [](const Ctx *c) -> double { return c->last_ms[T_LOO]; }, nullptr},
     {"loo_sums_ms", [](const Ctx *c) -> double { return c->last_ms[T_LOO_SUMS]; }, nullptr},
     {"loo_rows_ms", [](const Ctx *c) -> double { return c->last_ms[T_LOO_ROWS]; }, nullptr},
+    // ... of the last recommend_allocate as a whole (allocate.hpp), and the rounds it took
+    {"allocate_ms", [](const Ctx *c) -> double { return c->last_ms[T_ALLOCATE]; }, nullptr},
+    {"allocate_rounds", [](const Ctx *c) -> double { return c->alloc_rounds; }, nullptr},
     // workgroups of gtop_fused_kernel (top_pairs.hpp); 0: the library's choice
     {"top_pairs_groups", [](const Ctx *c) -> double { return c->top_groups; },
      [](Ctx *c, double v) {

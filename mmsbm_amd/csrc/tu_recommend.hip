@@ -13,6 +13,8 @@
 //   ensemble.hpp   ensemble-aware queries: the restarts' scores reduced per pair (min, max, mean - risk std), then the
 //                  same selection; the spread of given pairs
 //   quota.hpp      per-category caps: a mask over the batch buffer between the exclusions and the same selection
+//   allocate.hpp   capacity-aware allocation: rounds of the user-side and the item-side batches with a threshold epilogue
+//                  on the score tile, the same exclusions and selection; the lists and the keys stay on the device
 #include "prelude.hpp"
 #include "recommend.hpp"
 #include "similar.hpp"
@@ -25,6 +27,7 @@
 #include "group.hpp"
 #include "ensemble.hpp"
 #include "quota.hpp"
+#include "allocate.hpp"
 
 namespace mmsbm_hip_impl {
 
@@ -269,6 +272,22 @@ struct TopNDev {
   const int32_t *on;
 };
 
+// The selection of one batch: the n best of every row of sc [nb][I] to os / oi [row * n + k], k < on[row]; the columns
+// split into `parts` parts of `per` (item_parts) whose lists cs / ci / cn [nb * parts ...] are then merged
+void select_batch(hipStream_t st, const double *sc, int I, int nb, int parts, int per, int n, double *cs, int32_t *ci,
+                  int32_t *cn, double *os, int32_t *oi, int32_t *on) {
+  const auto [cap, lds] = select_list(n);
+  if (parts > 1) {
+    LAUNCH(rec_select_kernel<false>, dim3(parts, nb), kRecWave, lds, st, sc, static_cast<size_t>(I), I, per, nullptr,
+           nullptr, nullptr, 0, n, cap, cs, ci, cn);
+    LAUNCH(rec_select_kernel<true>, dim3(1, nb), kRecWave, lds, st, nullptr, 0, I, 0, cs, ci, cn, parts, n, cap, os, oi,
+           on);
+  } else {
+    LAUNCH(rec_select_kernel<false>, dim3(1, nb), kRecWave, lds, st, sc, static_cast<size_t>(I), I, I, nullptr, nullptr,
+           nullptr, 0, n, cap, os, oi, on);
+  }
+}
+
 // The batches of a top-N query over a buffer of `I` columns: rows ids[0 .. n_rows) (host ids); `fill(ub, nb, b0, sc)`
 // enqueues the kernels that write the values sc [nb][I] of the batch of request rows b0 .. b0 + nb, whose device ids
 // are ub (-inf: no candidate), then the N best of every row are selected (and merged when the columns are split across
@@ -283,7 +302,6 @@ void top_n_device(mmsbm_hip_ctx *c, int I, int64_t n_users, const int32_t *users
   const int64_t bu = rec_batch_users(I, n_users);
   // items split across waves until about 32 selecting waves per CU are in flight (the selection waits on its loads)
   const auto [parts, per] = item_parts(I, bu, 32LL * c->n_cus, kRecMinPerPart);
-  const auto [cap, lds] = select_list(n);
   const size_t cand = parts > 1 ? static_cast<size_t>(bu) * parts * n : 0;
   const size_t outs = static_cast<size_t>(n_users) * n;
   require_free_mem(static_cast<size_t>(bu) * I * sizeof(double) + cand * 12 + outs * 12 + static_cast<size_t>(n_users) * 8 +
@@ -306,15 +324,7 @@ void top_n_device(mmsbm_hip_ctx *c, int I, int64_t n_users, const int32_t *users
     double *obs = os.ptr + b0 * n;
     int32_t *obi = oi.ptr + b0 * n, *obn = on.ptr + b0;
     fill(ub, nb, b0, sc.ptr);
-    if (parts > 1) {
-      LAUNCH(rec_select_kernel<false>, dim3(parts, nb), kRecWave, lds, st, sc.ptr, static_cast<size_t>(I), I, per,
-             nullptr, nullptr, nullptr, 0, n, cap, cs.ptr, ci.ptr, cn.ptr);
-      LAUNCH(rec_select_kernel<true>, dim3(1, nb), kRecWave, lds, st, nullptr, 0, I, 0, cs.ptr, ci.ptr, cn.ptr, parts,
-             n, cap, obs, obi, obn);
-    } else {
-      LAUNCH(rec_select_kernel<false>, dim3(1, nb), kRecWave, lds, st, sc.ptr, static_cast<size_t>(I), I, I, nullptr,
-             nullptr, nullptr, 0, n, cap, obs, obi, obn);
-    }
+    select_batch(st, sc.ptr, I, nb, parts, per, n, cs.ptr, ci.ptr, cn.ptr, obs, obi, obn);
     HIP_CHECK(hipGetLastError());
   }
   ev.stop(st);
@@ -801,6 +811,125 @@ void recommend_query_items(mmsbm_hip_ctx *c, int64_t n_items, const int32_t *ite
               score_tiles(c, rc.y.ptr, static_cast<size_t>(rc.items) * rc.rank, rc.x.ptr, rc.x_stride(), rc.users, ib, nb, ex, sc);
             },
             T_RECOMMEND, users, scores, counts);
+}
+
+// ---- capacity-aware allocation (allocate.hpp) ----------------------------------------------------------------------------
+// The rounds of deferred acceptance: per round the batches of recommend_query (user pass) and of recommend_query_items
+// over the capped items (item pass), both with alloc_score_kernel in place of rec_score_kernel; P, sigma and tau stay on
+// the device, and the host reads one int per round.  users: distinct ids (checked by the C ABI); plan: the caps.
+void recommend_allocate(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, int n, const AllocPlan &plan,
+                        int max_rounds, int32_t *items, double *scores, int32_t *counts, int32_t *rounds,
+                        int32_t *converged) {
+  use_device(c);
+  top_n_blank(n_users, n, items, scores, counts);
+  *rounds = 0;
+  *converged = 1;
+  c->last_ms[T_ALLOCATE] = 0.f;
+  c->alloc_rounds = 0;
+  if (n_users == 0) return;
+  rec_item_lists(c);
+  const RecSession &rc = *c->rc;
+  const int U = rc.users, NI = rc.items, rank = rc.rank;
+  const int64_t NC = plan.capped();
+  hipStream_t st = c->stream;
+  const size_t xs = rc.x_stride(), ys = static_cast<size_t>(NI) * rank;
+  // user pass: batches of bu users over NI columns; item pass: batches of plan.bi capped items over U columns
+  const int64_t bu = rec_batch_users(NI, n_users), bi = plan.bi;
+  const auto [uparts, uper] = item_parts(NI, bu, 32LL * c->n_cus, kRecMinPerPart);
+  const auto [iparts, iper] = NC > 0 ? item_parts(U, bi, 32LL * c->n_cus, kRecMinPerPart) : std::pair<int, int>{1, U};
+  const int nsel = plan.most_n;
+  const size_t cand = std::max(uparts > 1 ? static_cast<size_t>(bu) * uparts * n : 0,
+                               iparts > 1 ? static_cast<size_t>(bi) * iparts * nsel : 0);
+  const size_t cparts = std::max(static_cast<size_t>(bu) * uparts, static_cast<size_t>(bi) * iparts);
+  const size_t buf = std::max(static_cast<size_t>(bu) * NI, static_cast<size_t>(bi) * U);
+  const size_t outs = static_cast<size_t>(n_users) * n, lists = static_cast<size_t>(bi) * nsel;
+  require_free_mem(buf * sizeof(double) + cand * 12 + cparts * 4 + outs * 12 + static_cast<size_t>(n_users) * 8 +
+                       lists * 12 + static_cast<size_t>(bi) * 4 + (static_cast<size_t>(NI) + U) * 12 +
+                       static_cast<size_t>(NC) * 9 + 4,
+                   "recommend_allocate: a batch of scores, the users' lists and the items' keys");
+  // tau by item: -inf (everything is acceptable), +inf for a closed item (nothing is); sigma by user: +inf outside the
+  // request (nothing stands in front of it), written for the request's users by every round
+  std::vector<double> tau_h(static_cast<size_t>(NI), -INFINITY), sig_h(static_cast<size_t>(U), INFINITY);
+  for (int32_t i : plan.closed) tau_h[static_cast<size_t>(i)] = INFINITY;
+  const std::vector<int32_t> tau_uh(static_cast<size_t>(NI), -1), sig_ih(static_cast<size_t>(U), -1);
+  DevBuf<double> sc, cs, ps, ls, tau_s, sig_s;
+  DevBuf<int32_t> du, ci, cn, pi, pn, lu, ln, tau_u, sig_i, d_item, d_cap, d_total;
+  DevBuf<unsigned char> d_changed;
+  sc.alloc(buf);
+  if (cand > 0) {
+    cs.alloc(cand); ci.alloc(cand); cn.alloc(cparts);
+  }
+  ps.alloc(outs); pi.alloc(outs); pn.alloc(static_cast<size_t>(n_users));
+  du.alloc(static_cast<size_t>(n_users));
+  HIP_CHECK(hipMemcpyAsync(du.ptr, users, sizeof(int32_t) * n_users, hipMemcpyHostToDevice, st));
+  tau_s.upload(tau_h, st); tau_u.upload(tau_uh, st);
+  if (NC > 0) {
+    ls.alloc(lists); lu.alloc(lists); ln.alloc(static_cast<size_t>(bi));
+    sig_s.upload(sig_h, st); sig_i.upload(sig_ih, st);
+    d_item.upload(plan.item, st); d_cap.upload(plan.cap, st);
+    d_changed.alloc(static_cast<size_t>(NC));
+    d_total.alloc(1);
+  }
+  const SeenLists seen = rc.seen_lists();
+  const SeenLists by_item{rc.excl ? rc.by_item_off.ptr : nullptr, rc.by_item.ptr};
+  const unsigned row_blocks = static_cast<unsigned>((n_users + kBlock - 1) / kBlock);
+  auto tiles = [](int cols, int nb) {
+    return dim3(static_cast<unsigned>((cols + kRecTile - 1) / kRecTile), static_cast<unsigned>((nb + kRecTile - 1) / kRecTile));
+  };
+  EventPair ev;  // device time of the whole call (option "allocate_ms"): the host's reads between the rounds included
+  ev.start(st);
+  int round = 0;
+  bool done = false;
+  while (!done) {
+    ++round;
+    for (int64_t b0 = 0; b0 < n_users; b0 += bu) {  // the user pass
+      const int nb = static_cast<int>(std::min(bu, n_users - b0));
+      const int32_t *ub = du.ptr + b0;
+      LAUNCH(alloc_score_kernel, tiles(NI, nb), kBlock, 0, st, rc.x.ptr, xs, rc.y.ptr, ys, ub, nb, NI, rank, rc.slots,
+             static_cast<const double *>(nullptr), static_cast<const int32_t *>(nullptr),
+             static_cast<const double *>(tau_s.ptr), static_cast<const int32_t *>(tau_u.ptr), sc.ptr, static_cast<size_t>(NI));
+      if (seen.off) LAUNCH(rec_exclude_kernel, nb, kBlock, 0, st, ub, seen.off, seen.items, sc.ptr, static_cast<size_t>(NI));
+      select_batch(st, sc.ptr, NI, nb, uparts, uper, n, cs.ptr, ci.ptr, cn.ptr, ps.ptr + b0 * n, pi.ptr + b0 * n, pn.ptr + b0);
+    }
+    HIP_CHECK(hipGetLastError());
+    if (NC == 0) break;  // (no cap binds: the answer is the user pass)
+    LAUNCH(alloc_sigma_kernel, row_blocks, kBlock, 0, st, static_cast<const int32_t *>(du.ptr), static_cast<int>(n_users), n,
+           static_cast<const double *>(ps.ptr), static_cast<const int32_t *>(pi.ptr), static_cast<const int32_t *>(pn.ptr),
+           sig_s.ptr, sig_i.ptr);
+    for (int64_t r0 = 0; r0 < NC; r0 += bi) {  // the item pass: the sides exchanged
+      const int nb = static_cast<int>(std::min(bi, NC - r0));
+      const int32_t *ib = d_item.ptr + r0;
+      const int bn = plan.batch_n[static_cast<size_t>(r0 / bi)];
+      LAUNCH(alloc_score_kernel, tiles(U, nb), kBlock, 0, st, rc.y.ptr, ys, rc.x.ptr, xs, ib, nb, U, rank, rc.slots,
+             static_cast<const double *>(tau_s.ptr), static_cast<const int32_t *>(tau_u.ptr),
+             static_cast<const double *>(sig_s.ptr), static_cast<const int32_t *>(sig_i.ptr), sc.ptr, static_cast<size_t>(U));
+      if (by_item.off) LAUNCH(rec_exclude_kernel, nb, kBlock, 0, st, ib, by_item.off, by_item.items, sc.ptr, static_cast<size_t>(U));
+      select_batch(st, sc.ptr, U, nb, iparts, iper, bn, cs.ptr, ci.ptr, cn.ptr, ls.ptr, lu.ptr, ln.ptr);
+      LAUNCH(alloc_tau_kernel, static_cast<unsigned>((nb + kBlock - 1) / kBlock), kBlock, 0, st, ib,
+             static_cast<const int32_t *>(d_cap.ptr + r0), nb, bn, static_cast<const double *>(ls.ptr),
+             static_cast<const int32_t *>(lu.ptr), static_cast<const int32_t *>(ln.ptr), tau_s.ptr, tau_u.ptr,
+             d_changed.ptr + r0);
+    }
+    LAUNCH(alloc_changed_kernel, 1, kBlock, 0, st, static_cast<const unsigned char *>(d_changed.ptr), static_cast<int>(NC),
+           d_total.ptr);
+    HIP_CHECK(hipGetLastError());
+    int32_t changed = 0;
+    HIP_CHECK(hipMemcpyAsync(&changed, d_total.ptr, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));  // (the round's only wait)
+    if (changed == 0) {
+      done = true;
+    } else if (round == max_rounds) {
+      *converged = 0;
+      done = true;
+    }
+  }
+  LAUNCH(alloc_cut_kernel, row_blocks, kBlock, 0, st, static_cast<const int32_t *>(du.ptr), static_cast<int>(n_users), n,
+         static_cast<const double *>(tau_s.ptr), static_cast<const int32_t *>(tau_u.ptr), ps.ptr, pi.ptr, pn.ptr);
+  HIP_CHECK(hipGetLastError());
+  ev.stop(st);
+  top_n_copy_out(c, TopNDev{ps.ptr, pi.ptr, pn.ptr}, ev, n_users, n, T_ALLOCATE, items, scores, counts);
+  *rounds = round;
+  c->alloc_rounds = round;
 }
 
 void recommend_audience(mmsbm_hip_ctx *c, int64_t n_items, const int32_t *items, double min_score, int64_t capacity,

@@ -8,6 +8,7 @@ frame assembler.
 from __future__ import annotations
 
 import contextlib
+import warnings
 
 import numpy as np
 import pandas as pd
@@ -126,6 +127,28 @@ def quota_categories(categories, max_per_category, items):
     mine = place[codes] >= 0
     offsets, members = grouped(place[codes][mine], ids[mine], len(capped), sort=True)
     return Quota(offsets, members, cap[capped].astype(np.int32), category_of, labels)
+
+
+# ---------------------------------------------------------------------- capacities
+def allocate_capacity(capacity, items):
+    """``allocate``'s ``capacity`` against the item table ``items`` (a ``_Side``; no context is needed) -> one int32 per
+    item: how often it can be given out, -1 for unlimited.
+
+    ``capacity``: an integer >= 0 for every item, or a dict / Series {item label: integer >= 0} -- items it does not
+    name are unlimited, labels the side does not have are ignored."""
+    must_be = "an integer >= 0 or a dict {item: integer >= 0}"
+    if isinstance(capacity, pd.Series):
+        capacity = dict(zip(capacity.index.tolist(), capacity.tolist()))
+    if not isinstance(capacity, dict):
+        return np.full(len(items), check_integer(capacity, "capacity", 0, must_be), dtype=np.int32)
+    caps = np.full(len(items), -1, dtype=np.int32)
+    labs = list(capacity.keys())
+    ids = items.ids(labs)
+    for j, lab in zip(ids.tolist(), labs):
+        q = check_integer(capacity[lab], f"capacity[{lab!r}]", 0, "an integer >= 0")
+        if j >= 0:
+            caps[j] = min(q, np.iinfo(np.int32).max)
+    return caps
 
 
 # ---------------------------------------------------------------------- labels of a side
@@ -404,6 +427,67 @@ class Serving:
             return self._top_n_frame(
                 lambda b, e: ctx.recommend_query_quota(ids[b:e], n, quota.offsets, quota.items, quota.caps, cand,
                                                        group_slice(extra, b, e)), n, labels, items, derived=derived)
+
+    def allocate(self, n=1, capacity=..., users=None, exclude_seen=True, weights=None, candidates=None,
+                 max_rounds=10000):
+        """``recommend`` when items run out: every requested user asks for ``n`` items and item i can be given out
+        ``capacity[i]`` times -- units in stock, papers per reviewer, coupons per product, a tutor's free slots.  It is
+        the one constraint that couples the users of a request, so no filter over ``recommend`` emulates it.  The
+        definition: all candidate (user, item) pairs of the request are walked in ``top_pairs``' order (score
+        descending, equal scores by ascending encoded user id, then item id) and a pair is taken iff its user holds fewer
+        than ``n`` items and its item is not used up.  The result is the one stable assignment: no user and item left
+        that would both rather have each other.  On the device it is reached by rounds of deferred acceptance over the
+        user-side and the item-side top-N, without sorting the pairs.
+
+        ``capacity`` (required): an integer >= 0 for every item, or a dict / Series {item label: integer >= 0} -- items
+        it does not name are unlimited, labels that are not training items are ignored; 0 takes an item out.
+        ``users``: distinct labels (None: every training user).  ``candidates``: only these items are given out (every
+        other item gets capacity 0).  ``max_rounds``: the rounds after which the device stops; the answer is then
+        feasible (nobody above ``n``, no item above its capacity) but not the walk's, and a RuntimeWarning says so.
+
+        Returns ``recommend``'s frame (``users``, ``items``, ``score``, ``rank``), users in request order; a user may
+        get fewer than ``n`` rows.  Scores are ``recommend``'s, bit for bit; with nothing capped the frame IS
+        ``recommend``'s.  ``self.allocation_`` = {"rounds", "converged", "filled", "requested"}: the rounds taken,
+        whether they reached the fixed point, the rows returned and users x n.  ``item_load`` counts a frame's items."""
+        if capacity is ...:
+            raise TypeError("allocate needs capacity=")
+        self._check_whole_model()
+        n, w = self._recommend_args(n, weights)
+        max_rounds = check_integer(max_rounds, "max_rounds", 1)
+        ids, labels = self._side("users").request(users)
+        if len(np.unique(ids)) != len(ids):
+            raise ValueError("users must be distinct: capacity couples the users of a request, not its rows")
+        items = self._side("items")
+        caps = allocate_capacity(capacity, items)
+        cand = self._candidate_ids(candidates)
+        if cand is not None:
+            inside = np.zeros(len(items), dtype=bool)
+            inside[cand] = True
+            caps[~inside] = 0
+        self.allocation_ = {"rounds": 0, "converged": True, "filled": 0, "requested": len(ids) * n}
+        if len(ids) == 0:
+            return self._top_n_frame(None, n, labels[:0], items)
+
+        def whole(b, e):   # (one call: the users of a request cannot be split)
+            got_items, scores, counts, info = ctx.recommend_allocate(ids, n, caps, max_rounds)
+            self.allocation_.update(info, filled=int(counts.sum()))
+            return counts, {"items": got_items, "score": scores}
+        with self._session_of_restarts("recommend", w, exclude_seen) as ctx:
+            frame = self._frame({"users": labels}, {"items": items, "score": None, "rank": None}, [(0, len(ids))], whole, n)
+        if not self.allocation_["converged"]:
+            warnings.warn(f"allocate stopped after max_rounds = {max_rounds} rounds before the fixed point: the "
+                          "assignment is feasible but not the stable one", RuntimeWarning, stacklevel=2)
+        return frame
+
+    @staticmethod
+    def item_load(recs):
+        """How often each item appears in a recommend-style frame (any frame with an ``items`` column): a DataFrame
+        ``items``, ``count``, the most used first, equal counts in order of first appearance.  What to look at before
+        and after ``allocate``."""
+        codes, found = pd.factorize(np.asarray(recs["items"], dtype=object))
+        count = np.bincount(codes, minlength=len(found)).astype(np.int64)
+        order = np.argsort(-count, kind="stable")
+        return pd.DataFrame({"items": np.asarray(found, dtype=object)[order], "count": count[order]})
 
     def rerank(self, pairs, n=None, exclude_seen=True, weights=None):
         """The order of caller-given candidates per user -- the second stage of a two-stage system: a cheap retriever
