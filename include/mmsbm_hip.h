@@ -344,6 +344,42 @@ int mmsbm_hip_recommend_query_theta_quota(mmsbm_hip_ctx *ctx, int64_t n_users, c
                                           const int32_t *cat_items, const int32_t *cat_caps, int32_t n, int32_t *items,
                                           double *scores, int32_t *counts);
 
+/* Category-level recommendation, inside the open recommend session (mmsbm_amd/csrc/shelves.hpp): which categories
+ * ("shelves") to show a row -- the rows of a front page -- and each shelf's best items.  The categories are given as the
+ * quota entries give them (cat_offsets int64 [n_cats + 1], cat_items: ids of the session's catalogue, those of
+ * recommend_add_items included; strictly ascending inside a category, no item in two categories); an item in none of
+ * them belongs to no shelf.  The one definition: for row b take query_within's candidates (what query leaves out,
+ * cand_items and excl_* applied) with their scores, query's bit for bit.  For category g let s_1, s_2, ... be its
+ * candidates' scores in query's order (score descending, equal scores by ascending item id) and a their number.
+ * a < min_items: the category is no candidate of the row.  Otherwise t = min(depth, a) and the category's VALUE is
+ * ((..((s_1 + s_2) + s_3) + ..) + s_t) / t: the additions left to right from s_1, one IEEE division (depth 1: the best
+ * item's score, bit for bit; depth >= a: the mean of all).  The row's shelves are the n_shelves categories of largest
+ * value, equal values by ascending category index of the call; the items of a shelf are the first min(per_shelf, a) of
+ * s_1, s_2, ...  A row's answer depends on that row alone.
+ * Output: shelf_cats (category indices of the call) / shelf_values / shelf_available (a) [n_users][n_shelves], row b
+ * holding shelf_counts[b] entries, then -1 / -inf / 0; items / scores [n_users][n_shelves][per_shelf], shelf k of row b
+ * holding item_counts[b * n_shelves + k] entries, then -1 / -inf; with per_shelf == 0 the last three may be NULL.
+ * n_cats == 0, or no category with a candidate item: every row is empty and nothing is launched.  Arguments otherwise
+ * as query_within / query_theta_within; "recommend_ms" reads the device time of the call's kernels.  MMSBM_E_INVALID
+ * (before any launch): what query_within / query_theta_within refuse, n_cats < 0, a bad CSR, an item id out of range, a
+ * category that is not strictly ascending, an item in two categories, depth < 1, min_items < 1, n_shelves < 1,
+ * per_shelf < 0, a null output that is needed; depth, n_shelves or per_shelf > MMSBM_HIP_RECOMMEND_MAX_N:
+ * MMSBM_E_UNSUPPORTED; MMSBM_E_TOOLARGE where the device memory is not free. */
+int mmsbm_hip_recommend_query_shelves(mmsbm_hip_ctx *ctx, int64_t n_users, const int32_t *users, int32_t n_cand,
+                                      const int32_t *cand_items, const int64_t *excl_offsets,
+                                      const int32_t *excl_items, int64_t n_cats, const int64_t *cat_offsets,
+                                      const int32_t *cat_items, int32_t depth, int32_t min_items, int32_t n_shelves,
+                                      int32_t per_shelf, int32_t *shelf_cats, double *shelf_values,
+                                      int32_t *shelf_available, int32_t *shelf_counts, int32_t *items, double *scores,
+                                      int32_t *item_counts);
+int mmsbm_hip_recommend_query_theta_shelves(mmsbm_hip_ctx *ctx, int64_t n_users, const double *theta,
+                                            const int64_t *seen_offsets, const int32_t *seen_items, int32_t n_cand,
+                                            const int32_t *cand_items, int64_t n_cats, const int64_t *cat_offsets,
+                                            const int32_t *cat_items, int32_t depth, int32_t min_items,
+                                            int32_t n_shelves, int32_t per_shelf, int32_t *shelf_cats,
+                                            double *shelf_values, int32_t *shelf_available, int32_t *shelf_counts,
+                                            int32_t *items, double *scores, int32_t *item_counts);
+
 /* Capacity-aware allocation, inside the open recommend session (mmsbm_amd/csrc/allocate.hpp): items run out.  Every
  * user of the request asks for n items, item i of the session's catalogue (the items of recommend_add_items included)
  * can be given out caps[i] times: stock, a reviewer's load, coupons per product.  The one definition: take all pairs

@@ -75,6 +75,13 @@ SIGNATURES = {
     "mmsbm_hip_recommend_query_theta_quota": (C.c_int, [C.c_void_p, C.c_int64, c_f64p, c_i64p, c_i32p, C.c_int32,
                                                         c_i32p, C.c_int64, c_i64p, c_i32p, c_i32p, C.c_int32, c_i32p,
                                                         c_f64p, c_i32p]),
+    "mmsbm_hip_recommend_query_shelves": (C.c_int, [C.c_void_p, C.c_int64, c_i32p, C.c_int32, c_i32p, c_i64p, c_i32p,
+                                                    C.c_int64, c_i64p, c_i32p, C.c_int32, C.c_int32, C.c_int32,
+                                                    C.c_int32, c_i32p, c_f64p, c_i32p, c_i32p, c_i32p, c_f64p, c_i32p]),
+    "mmsbm_hip_recommend_query_theta_shelves": (C.c_int, [C.c_void_p, C.c_int64, c_f64p, c_i64p, c_i32p, C.c_int32,
+                                                          c_i32p, C.c_int64, c_i64p, c_i32p, C.c_int32, C.c_int32,
+                                                          C.c_int32, C.c_int32, c_i32p, c_f64p, c_i32p, c_i32p, c_i32p,
+                                                          c_f64p, c_i32p]),
     "mmsbm_hip_recommend_rank": (C.c_int, [C.c_void_p, C.c_int64, c_i32p, c_i64p, c_i32p, C.c_int32, c_i32p, c_f64p,
                                            c_i32p]),
     "mmsbm_hip_similar_begin": (C.c_int, [C.c_void_p, C.c_int]),

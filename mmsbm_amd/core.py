@@ -462,6 +462,64 @@ class HipEM:
                   _p(items, C.c_int32), _p(scores, C.c_double), _p(counts, C.c_int32))
         return items, scores, counts
 
+    @staticmethod
+    def _shelves_out(m, n_shelves, per_shelf):
+        """The empty outputs of a shelves query of m rows and their pointers (the last three null at per_shelf 0)."""
+        ns, ps = max(int(n_shelves), 0), max(int(per_shelf), 0)
+        out = (np.empty((m, ns), dtype=np.int32), np.empty((m, ns), dtype=np.float64), np.empty((m, ns), dtype=np.int32),
+               np.empty(m, dtype=np.int32), np.empty((m, ns, ps), dtype=np.int32),
+               np.empty((m, ns, ps), dtype=np.float64), np.empty((m, ns), dtype=np.int32))
+        types = (C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_int32)
+        ptrs = [_p(a, t) for a, t in zip(out, types)]
+        if ps == 0:
+            ptrs[4:] = [None, None, None]
+            out[6][:] = 0
+        return out, ptrs
+
+    def recommend_query_shelves(self, users, cat_offsets, cat_items, depth, min_items, n_shelves, per_shelf,
+                                candidates=None, exclude=None):
+        """Category-level recommendation: which categories to show each encoded user id, and each one's best items.
+        Category g holds the catalogue items cat_items[cat_offsets[g]:cat_offsets[g + 1]] (strictly ascending; no item
+        in two categories).  Over recommend_query_within's candidates (``candidates``, ``exclude`` as there) a
+        category's value is the sequential mean of its min(depth, available) best scores; categories with fewer than
+        min_items candidates are left out; the n_shelves best values win, equal values by ascending category index.
+        Returns (categories (M,S) int32 padded with -1, values (M,S) padded with -inf, available (M,S) padded with 0,
+        counts (M,), items (M,S,P) int32 padded with -1, scores (M,S,P) padded with -inf, item_counts (M,S)) for
+        S = n_shelves, P = per_shelf (P = 0: the shelves only)."""
+        u = _i32(users)
+        cand = None if candidates is None else _i32(candidates)
+        off, it = _csr(exclude, len(u), "exclude offsets", "items")
+        coff = np.ascontiguousarray(cat_offsets, dtype=np.int64)
+        coff, cit = _csr((coff, cat_items), len(coff) - 1, "category offsets", "cat_items")
+        out, ptrs = self._shelves_out(len(u), n_shelves, per_shelf)
+        _lib.call("mmsbm_hip_recommend_query_shelves", self._h, len(u), _p(u, C.c_int32),
+                  0 if cand is None else len(cand), _p_or_null(cand, C.c_int32),
+                  _p_or_null(off, C.c_int64), _p_or_null(it, C.c_int32),
+                  len(coff) - 1, _p(coff, C.c_int64), _p(cit, C.c_int32), int(depth), int(min_items), int(n_shelves),
+                  int(per_shelf), *ptrs)
+        return out
+
+    def recommend_query_theta_shelves(self, theta, cat_offsets, cat_items, depth, min_items, n_shelves, per_shelf,
+                                      seen=None, candidates=None):
+        """recommend_query_shelves for caller-given theta rows (S, M, K) with ``seen`` lists per row and ``candidates``,
+        as recommend_query_theta."""
+        t = _f64(theta)
+        if t.ndim != 3 or t.shape[2] != self.k:
+            raise ValueError(f"theta has shape {t.shape}, expected (slots, users, {self.k})")
+        if t.shape[0] != self._rc_added:
+            raise ValueError(f"theta holds {t.shape[0]} blocks, the session {self._rc_added} added slots")
+        m = t.shape[1]
+        off, it = _csr(seen, m, "seen offsets", "items")
+        cand = None if candidates is None else _i32(candidates)
+        coff = np.ascontiguousarray(cat_offsets, dtype=np.int64)
+        coff, cit = _csr((coff, cat_items), len(coff) - 1, "category offsets", "cat_items")
+        out, ptrs = self._shelves_out(m, n_shelves, per_shelf)
+        _lib.call("mmsbm_hip_recommend_query_theta_shelves", self._h, m, _p(t, C.c_double), _p_or_null(off, C.c_int64),
+                  _p_or_null(it, C.c_int32), 0 if cand is None else len(cand), _p_or_null(cand, C.c_int32),
+                  len(coff) - 1, _p(coff, C.c_int64), _p(cit, C.c_int32), int(depth), int(min_items), int(n_shelves),
+                  int(per_shelf), *ptrs)
+        return out
+
     def recommend_rank(self, users, offsets, items, n):
         """The order of caller-given candidates, one list per request row: row b's candidates are
         items[offsets[b]:offsets[b + 1]] (ascending, distinct item ids of the session's catalogue) for encoded user

@@ -706,17 +706,18 @@ int mmsbm_hip_recommend_query_theta_within(mmsbm_hip_ctx *ctx, int64_t n_users, 
 
 namespace {
 // The capped categories of the two *_quota entries: a CSR of n_cats categories over the catalogue's `top` items, each
-// strictly ascending, no item in two of them, no negative cap
+// strictly ascending, no item in two of them, no negative cap.  capped = false (the two *_shelves entries): the same
+// categories without caps, cat_caps is not read.
 void require_categories(int64_t n_cats, const int64_t *cat_offsets, const int32_t *cat_items, const int32_t *cat_caps,
-                        int32_t top, const char *who) {
+                        int32_t top, const char *who, bool capped = true) {
   const std::string w = std::string(who) + ": ";
   if (n_cats < 0) throw std::invalid_argument(w + "negative n_cats");
   if (n_cats == 0) return;
-  if (!cat_offsets || !cat_caps) throw std::invalid_argument("null argument");
+  if (!cat_offsets || (capped && !cat_caps)) throw std::invalid_argument("null argument");
   check_csr(cat_offsets, cat_items, n_cats, top, who, "cat_offsets", "category", "category items", "category item");
   std::vector<bool> taken(static_cast<size_t>(top), false);
   for (int64_t g = 0; g < n_cats; ++g) {
-    if (cat_caps[g] < 0) throw std::invalid_argument(w + "negative cap of category " + std::to_string(g));
+    if (capped && cat_caps[g] < 0) throw std::invalid_argument(w + "negative cap of category " + std::to_string(g));
     for (int64_t e = cat_offsets[g]; e < cat_offsets[g + 1]; ++e) {
       if (e > cat_offsets[g] && cat_items[e] <= cat_items[e - 1])
         throw std::invalid_argument(w + "the items of a category must be ascending and distinct (entry " +
@@ -766,6 +767,76 @@ int mmsbm_hip_recommend_query_theta_quota(mmsbm_hip_ctx *ctx, int64_t n_users, c
     require_categories(n_cats, cat_offsets, cat_items, cat_caps, rc.items, "recommend_query_theta_quota");
     recommend_query_theta_quota(ctx, n_users, theta, seen_offsets, seen_items, cand_items, n_cand, n_cats, cat_offsets,
                                 cat_items, cat_caps, n, items, scores, counts);
+  });
+}
+
+namespace {
+// depth / min_items / n_shelves / per_shelf and the output arrays of the two *_shelves entries
+void require_shelf_ask(int64_t n_users, int64_t n_cats, const ShelfAsk &ask, const ShelfOut &out, const char *who) {
+  const std::string w = std::string(who) + ": ";
+  if (ask.depth < 1) throw std::invalid_argument(w + "depth must be at least 1");
+  if (ask.min_items < 1) throw std::invalid_argument(w + "min_items must be at least 1");
+  if (ask.n_shelves < 1) throw std::invalid_argument(w + "n_shelves must be at least 1");
+  if (ask.per_shelf < 0) throw std::invalid_argument(w + "negative per_shelf");
+  auto within_max = [&](int v, const char *name) {
+    if (v > MMSBM_HIP_RECOMMEND_MAX_N)
+      throw ApiError(MMSBM_E_UNSUPPORTED, w + name + " = " + std::to_string(v) + " is beyond the " +
+                                              std::to_string(MMSBM_HIP_RECOMMEND_MAX_N) + " a query holds");
+  };
+  within_max(ask.depth, "depth");
+  within_max(ask.n_shelves, "n_shelves");
+  within_max(ask.per_shelf, "per_shelf");
+  if (n_cats > INT32_MAX) throw ApiError(MMSBM_E_TOOLARGE, w + "more than 2^31 - 1 categories");
+  if (n_users > 0 && (!out.shelf_cats || !out.shelf_values || !out.shelf_available || !out.shelf_counts ||
+                      (ask.per_shelf > 0 && (!out.items || !out.scores || !out.item_counts))))
+    throw std::invalid_argument("null argument");
+}
+}  // namespace
+
+int mmsbm_hip_recommend_query_shelves(mmsbm_hip_ctx *ctx, int64_t n_users, const int32_t *users, int32_t n_cand,
+                                      const int32_t *cand_items, const int64_t *excl_offsets,
+                                      const int32_t *excl_items, int64_t n_cats, const int64_t *cat_offsets,
+                                      const int32_t *cat_items, int32_t depth, int32_t min_items, int32_t n_shelves,
+                                      int32_t per_shelf, int32_t *shelf_cats, double *shelf_values,
+                                      int32_t *shelf_available, int32_t *shelf_counts, int32_t *items, double *scores,
+                                      int32_t *item_counts) {
+  return guarded([&] {
+    const RecSession &rc = require_open(ctx, &mmsbm_hip_ctx::rc, "recommend", "recommend_query_shelves");
+    if (n_users < 0) throw std::invalid_argument("negative n_users");
+    const ShelfAsk ask{depth, min_items, n_shelves, per_shelf};
+    const ShelfOut out{shelf_cats, shelf_values, shelf_available, shelf_counts, items, scores, item_counts};
+    require_shelf_ask(n_users, n_cats, ask, out, "recommend_query_shelves");
+    if (n_users > 0 && !users) throw std::invalid_argument("null argument");
+    require_ids(users, n_users, ctx->ext_users, "recommend: user");
+    require_subset(cand_items, n_cand, rc.items, "recommend_query_shelves");
+    check_csr(excl_offsets, excl_items, n_users, rc.items, "recommend_query_shelves", "excl_offsets", "user",
+              "excluded items", "excluded item");
+    require_categories(n_cats, cat_offsets, cat_items, nullptr, rc.items, "recommend_query_shelves", false);
+    recommend_query_shelves(ctx, n_users, users, cand_items, n_cand, n_users > 0 ? excl_offsets : nullptr, excl_items,
+                            n_cats, cat_offsets, cat_items, ask, out);
+  });
+}
+
+int mmsbm_hip_recommend_query_theta_shelves(mmsbm_hip_ctx *ctx, int64_t n_users, const double *theta,
+                                            const int64_t *seen_offsets, const int32_t *seen_items, int32_t n_cand,
+                                            const int32_t *cand_items, int64_t n_cats, const int64_t *cat_offsets,
+                                            const int32_t *cat_items, int32_t depth, int32_t min_items,
+                                            int32_t n_shelves, int32_t per_shelf, int32_t *shelf_cats,
+                                            double *shelf_values, int32_t *shelf_available, int32_t *shelf_counts,
+                                            int32_t *items, double *scores, int32_t *item_counts) {
+  return guarded([&] {
+    const RecSession &rc = require_open(ctx, &mmsbm_hip_ctx::rc, "recommend", "recommend_query_theta_shelves");
+    if (n_users < 0) throw std::invalid_argument("negative n_users");
+    const ShelfAsk ask{depth, min_items, n_shelves, per_shelf};
+    const ShelfOut out{shelf_cats, shelf_values, shelf_available, shelf_counts, items, scores, item_counts};
+    require_shelf_ask(n_users, n_cats, ask, out, "recommend_query_theta_shelves");
+    if (n_users > 0 && !theta) throw std::invalid_argument("null argument");
+    require_subset(cand_items, n_cand, rc.items, "recommend_query_theta_shelves");
+    check_csr(seen_offsets, seen_items, n_users, rc.items, "recommend", "seen_offsets", "user", "seen items",
+              "seen item");
+    require_categories(n_cats, cat_offsets, cat_items, nullptr, rc.items, "recommend_query_theta_shelves", false);
+    recommend_query_theta_shelves(ctx, n_users, theta, seen_offsets, seen_items, cand_items, n_cand, n_cats, cat_offsets,
+                                  cat_items, ask, out);
   });
 }
 

@@ -138,6 +138,73 @@ inline QuotaPlan plan_quota(const int32_t *cand, int n_cand, int64_t n_cats, con
   return p;
 }
 
+// ---- category-level recommendation (shelves.hpp) ---------------------------------------------------------------------------
+// What a shelves query uploads and launches with.  The categories are the caller's, as catalogue items (each strictly
+// ascending, no item in two of them: checked by the C ABI); here they become COLUMNS of the query's batch buffer as in
+// plan_quota (an item that is no candidate is dropped), and a category left without a column is dropped: no row can show
+// it.  The kept categories stand in plan_quota's order -- the short ones (m <= kQuotaShortMax) by ascending width,
+// 64 / width to a wave, the long ones behind them -- but their VALUE COLUMNS (slot) follow the caller's order, so that
+// the selection's tie rule over the value buffer, ascending column, is "ascending category index of the call".
+struct ShelfPlan {
+  std::vector<int64_t> cat;             // per kept category: its place in the caller's request
+  std::vector<int32_t> slot;            // per kept category: its column of the value buffer
+  std::vector<int32_t> of_slot;         // per value column: the kept category that writes it
+  std::vector<int32_t> off, col;        // the kept categories' columns (CSR, ascending inside a category)
+  int n_short = 0;                      // the first n_short kept categories take the short form, the others the long one
+  std::vector<int32_t> wave_first, wave_info;  // short form, per wave: its first category; width | categories << 8
+  int kept() const { return static_cast<int>(cat.size()); }
+  int n_long() const { return kept() - n_short; }
+  size_t bytes() const {
+    return (slot.size() + of_slot.size() + off.size() + col.size() + wave_first.size() + wave_info.size()) * sizeof(int32_t);
+  }
+};
+
+// cand: the query's ascending candidate list (null: the columns are the items)
+inline ShelfPlan plan_shelves(const int32_t *cand, int n_cand, int64_t n_cats, const int64_t *cat_off,
+                              const int32_t *cat_items) {
+  ShelfPlan p;
+  std::vector<int32_t> cols;                // every category's columns, in request order
+  std::vector<int64_t> begin(static_cast<size_t>(n_cats) + 1, 0);
+  std::vector<int32_t> rank(static_cast<size_t>(n_cats), -1);  // a category's place among those with a column
+  int32_t n_kept = 0;
+  for (int64_t g = 0; g < n_cats; ++g) {
+    for (int64_t e = cat_off[g]; e < cat_off[g + 1]; ++e) {
+      if (!cand) {
+        cols.push_back(cat_items[e]);
+      } else {
+        const int32_t *at = std::lower_bound(cand, cand + n_cand, cat_items[e]);
+        if (at != cand + n_cand && *at == cat_items[e]) cols.push_back(static_cast<int32_t>(at - cand));
+      }
+    }
+    begin[static_cast<size_t>(g) + 1] = static_cast<int64_t>(cols.size());
+    if (begin[static_cast<size_t>(g) + 1] > begin[static_cast<size_t>(g)]) rank[static_cast<size_t>(g)] = n_kept++;
+  }
+  auto size_of = [&](int64_t g) { return begin[static_cast<size_t>(g) + 1] - begin[static_cast<size_t>(g)]; };
+  p.of_slot.resize(static_cast<size_t>(n_kept));
+  auto keep = [&](int64_t g) {
+    p.of_slot[static_cast<size_t>(rank[static_cast<size_t>(g)])] = p.kept();
+    p.cat.push_back(g);
+    p.slot.push_back(rank[static_cast<size_t>(g)]);
+    p.off.push_back(static_cast<int32_t>(p.col.size()));
+    p.col.insert(p.col.end(), cols.begin() + begin[static_cast<size_t>(g)], cols.begin() + begin[static_cast<size_t>(g) + 1]);
+  };
+  for (int w = 1; w <= kQuotaShortMax; w <<= 1) {  // the short categories by ascending width, 64 / w of them to a wave
+    const int first = p.kept();
+    for (int64_t g = 0; g < n_cats; ++g)
+      if (size_of(g) > 0 && size_of(g) <= kQuotaShortMax && quota_width(static_cast<int>(size_of(g))) == w) keep(g);
+    const int per = kRecWave / w;
+    for (int g0 = first; g0 < p.kept(); g0 += per) {
+      p.wave_first.push_back(g0);
+      p.wave_info.push_back(w | (std::min(per, p.kept() - g0) << 8));
+    }
+  }
+  p.n_short = p.kept();
+  for (int64_t g = 0; g < n_cats; ++g)
+    if (size_of(g) > kQuotaShortMax) keep(g);
+  p.off.push_back(static_cast<int32_t>(p.col.size()));
+  return p;
+}
+
 // ---- capacity-aware allocation (allocate.hpp) ----------------------------------------------------------------------------
 // What recommend_allocate makes of the caller's caps, one per catalogue item, for a request of n_users users: a negative
 // cap and a cap >= n_users never bind (every user of the request may hold the item), cap 0 closes the item, and the

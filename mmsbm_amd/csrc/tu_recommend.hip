@@ -15,6 +15,8 @@
 //   quota.hpp      per-category caps: a mask over the batch buffer between the exclusions and the same selection
 //   allocate.hpp   capacity-aware allocation: rounds of the user-side and the item-side batches with a threshold epilogue
 //                  on the score tile, the same exclusions and selection; the lists and the keys stay on the device
+//   shelves.hpp    category-level recommendation: the batch buffer reduced per (row, category) to a value buffer, the same
+//                  selection over it, then the chosen categories' items
 #include "prelude.hpp"
 #include "recommend.hpp"
 #include "similar.hpp"
@@ -28,6 +30,7 @@
 #include "ensemble.hpp"
 #include "quota.hpp"
 #include "allocate.hpp"
+#include "shelves.hpp"
 
 namespace mmsbm_hip_impl {
 
@@ -433,6 +436,56 @@ void cat_table(mmsbm_hip_ctx *c, const int32_t *cand, int C, CatTable &t) {
   t.ms = ev.ms();
 }
 
+// What a query within the candidates holds on the device beside its batches: the query's own excluded items by request
+// row and the candidates' compact table (cat_table), and from them the item table y (slots ys doubles apart) of C rows
+// that the batches' tiles read
+struct WithinPrep {
+  DevCsr own;
+  CatTable ct;
+  bool has_cand = false, has_own = false;
+  const double *y = nullptr;
+  size_t ys = 0;
+  int C = 0;
+  const int32_t *dcand() const { return has_cand ? ct.cand.ptr : nullptr; }
+};
+
+// cand / n_cand / xoff / xit as rec_within_device's: the memory is checked, the lists uploaded, the compact table made
+void within_prepare(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *cand, int n_cand, const int64_t *xoff,
+                    const int32_t *xit, WithinPrep &w) {
+  const RecSession &rc = *c->rc;
+  const int NI = rc.items, rank = rc.rank, S = rc.slots;
+  w.C = cand ? n_cand : NI;
+  w.has_cand = cand != nullptr;
+  w.has_own = xoff != nullptr;
+  const size_t ycs = static_cast<size_t>(w.C) * rank;
+  if (cand || xoff)
+    require_free_mem((cand ? S * ycs * sizeof(double) + (static_cast<size_t>(w.C) + NI) * 4 : 0) +
+                         (static_cast<size_t>(n_users) + 1 + DevCsr::entries(xoff, n_users)) * 4,
+                     "recommend: the candidates' rows and the query's excluded items");
+  if (xoff) w.own.upload(xoff, xit, n_users, c->stream);
+  if (cand) cat_table(c, cand, w.C, w.ct);
+  w.y = cand ? w.ct.y.ptr : rc.y.ptr;
+  w.ys = cand ? ycs : static_cast<size_t>(NI) * rank;
+}
+
+// The values sc [nb][C] of the batch of request rows b0 .. b0 + nb (device ids ub): `tiles`, then -inf over what `seen`
+// leaves out for the rows' ids and over the query's own excluded items.  The one copy of these launches: the `fill` of
+// rec_within_device and the batch loop of rec_shelves_run both call it.
+template <class Tiles>
+void within_fill(mmsbm_hip_ctx *c, const WithinPrep &w, Tiles &&tiles, SeenLists seen, const int32_t *ub, int nb,
+                 int64_t b0, double *sc) {
+  hipStream_t st = c->stream;
+  const int C = w.C;
+  tiles(w.y, w.ys, C, ub, nb, sc);
+  if (seen.off) {
+    if (w.has_cand)
+      LAUNCH(cat_exclude_kernel, nb, kBlock, 0, st, ub, 0, seen.off, seen.items, w.ct.col.ptr, sc, static_cast<size_t>(C));
+    else
+      LAUNCH(rec_exclude_kernel, nb, kBlock, 0, st, ub, seen.off, seen.items, sc, static_cast<size_t>(C));
+  }
+  if (w.has_own) own_exclude_batch(st, w.own, b0, nb, w.ct.col.ptr, sc, static_cast<size_t>(C));
+}
+
 // The device side of a recommend query within the candidates cand[0 .. n_cand) (host; ascending, distinct ids of the
 // session's catalogue; null: the whole catalogue), and with the query's own excluded items: row b of the request also
 // leaves out xit[xoff[b] .. xoff[b + 1]) (host, any order, repeats allowed; null: none).  catalogue.hpp.
@@ -447,35 +500,15 @@ template <class Tiles, class Then>
 void rec_within_device(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, SeenLists seen, const int32_t *cand,
                        int n_cand, const int64_t *xoff, const int32_t *xit, int n, size_t extra, Tiles &&tiles,
                        Then &&then, const QuotaMask *quota = nullptr) {
-  const RecSession &rc = *c->rc;
-  const int NI = rc.items, rank = rc.rank, S = rc.slots;
-  const int C = cand ? n_cand : NI;
-  hipStream_t st = c->stream;
-  const size_t ycs = static_cast<size_t>(C) * rank;
-  if (cand || xoff)
-    require_free_mem((cand ? S * ycs * sizeof(double) + (static_cast<size_t>(C) + NI) * 4 : 0) +
-                         (static_cast<size_t>(n_users) + 1 + DevCsr::entries(xoff, n_users)) * 4,
-                     "recommend: the candidates' rows and the query's excluded items");
-  DevCsr own;
-  CatTable ct;
-  if (xoff) own.upload(xoff, xit, n_users, st);
-  if (cand) cat_table(c, cand, C, ct);
-  const double *y = cand ? ct.y.ptr : rc.y.ptr;
-  const size_t ys = cand ? ycs : static_cast<size_t>(NI) * rank;
-  top_n_device(c, C, n_users, users, n,
+  WithinPrep w;
+  within_prepare(c, n_users, cand, n_cand, xoff, xit, w);
+  top_n_device(c, w.C, n_users, users, n,
                cand || xoff || quota ? "recommend: a batch of users within the candidates" : "recommend: a batch of users", extra,
                [&](const int32_t *ub, int nb, int64_t b0, double *sc) {
-                 tiles(y, ys, C, ub, nb, sc);
-                 if (seen.off) {
-                   if (cand)
-                     LAUNCH(cat_exclude_kernel, nb, kBlock, 0, st, ub, 0, seen.off, seen.items, ct.col.ptr, sc, static_cast<size_t>(C));
-                   else
-                     LAUNCH(rec_exclude_kernel, nb, kBlock, 0, st, ub, seen.off, seen.items, sc, static_cast<size_t>(C));
-                 }
-                 if (xoff) own_exclude_batch(st, own, b0, nb, ct.col.ptr, sc, static_cast<size_t>(C));
-                 if (quota) quota->apply(st, nb, sc, static_cast<size_t>(C));
+                 within_fill(c, w, tiles, seen, ub, nb, b0, sc);
+                 if (quota) quota->apply(c->stream, nb, sc, static_cast<size_t>(w.C));
                },
-               [&](const TopNDev &dev, EventPair &ev) { then(dev, ev, cand ? ct.cand.ptr : nullptr, ct.ms); });
+               [&](const TopNDev &dev, EventPair &ev) { then(dev, ev, w.dcand(), w.ct.ms); });
 }
 
 // rec_within_device's `tiles` of recommend_query: the scores of the rows of x (`slots` tables xs doubles apart)
@@ -536,10 +569,10 @@ void rec_run_within(mmsbm_hip_ctx *c, const double *x, size_t xs, int64_t n_user
 }
 
 // The caller's theta rows [S][n_users][K] folded exactly as recommend_add folds a slot's own theta (x = theta, or
-// theta W when K > L), then rec_run_within over the rows 0 .. n_users - 1 with the caller's seen lists
-void rec_theta_run(mmsbm_hip_ctx *c, int64_t n_users, const double *theta, const int64_t *seen_offsets,
-                   const int32_t *seen_items, const int32_t *cand, int n_cand, int n, int32_t *items, double *scores,
-                   int32_t *counts, const QuotaCats *cats = nullptr) {
+// theta W when K > L), then `run(x, xs, ids, seen)` over the rows 0 .. n_users - 1 with the caller's seen lists
+template <class Run>
+void rec_theta_fold(mmsbm_hip_ctx *c, int64_t n_users, const double *theta, const int64_t *seen_offsets,
+                    const int32_t *seen_items, Run &&run) {
   const int K = c->ext_k, L = c->ext_l, rank = c->rc->rank, S = c->rc->slots;
   const size_t tk = static_cast<size_t>(n_users) * K, xs = static_cast<size_t>(n_users) * rank;
   require_free_mem(S * (tk + xs) * sizeof(double) +
@@ -557,8 +590,173 @@ void rec_theta_run(mmsbm_hip_ctx *c, int64_t n_users, const double *theta, const
            x.ptr + s * xs, static_cast<int>(n_users), rank);
   }
   HIP_CHECK(hipGetLastError());
-  rec_run_within(c, x.ptr, xs, n_users, rows.ids.data(), rows.seen.lists(), cand, n_cand, nullptr, nullptr, n, items,
-                 scores, counts, cats);
+  run(x.ptr, xs, rows.ids.data(), rows.seen.lists());
+}
+
+// ... then rec_run_within
+void rec_theta_run(mmsbm_hip_ctx *c, int64_t n_users, const double *theta, const int64_t *seen_offsets,
+                   const int32_t *seen_items, const int32_t *cand, int n_cand, int n, int32_t *items, double *scores,
+                   int32_t *counts, const QuotaCats *cats = nullptr) {
+  rec_theta_fold(c, n_users, theta, seen_offsets, seen_items,
+                 [&](const double *x, size_t xs, const int32_t *ids, SeenLists seen) {
+                   rec_run_within(c, x, xs, n_users, ids, seen, cand, n_cand, nullptr, nullptr, n, items, scores, counts,
+                                  cats);
+                 });
+}
+
+// ---- category-level recommendation (shelves.hpp) -------------------------------------------------------------------------
+// The categories of a shelves query on the device: the plan of serve_plan.hpp, held for as long as the query runs (the
+// copies are asynchronous)
+struct ShelfCats {
+  ShelfPlan plan;
+  DevBuf<int32_t> off, col, slot, of_slot, wave_first, wave_info;
+  void upload(ShelfPlan &&p, hipStream_t st) {
+    plan = std::move(p);
+    off.upload(plan.off, st);
+    col.upload(plan.col, st);
+    slot.upload(plan.slot, st);
+    of_slot.upload(plan.of_slot, st);
+    wave_first.upload(plan.wave_first, st);
+    wave_info.upload(plan.wave_info, st);
+  }
+  // val [nb][kept] (and avail, or null) from the batch buffer sc [nb][ld]: each category by the form its size selects
+  void values(hipStream_t st, int nb, const double *sc, size_t ld, int depth, int min_items, double *val,
+              int32_t *avail) const {
+    const int waves = static_cast<int>(plan.wave_first.size());
+    const size_t G = static_cast<size_t>(plan.kept());
+    if (waves > 0)
+      LAUNCH(shelf_value_short_kernel, dim3(static_cast<unsigned>((waves + kQuotaWaves - 1) / kQuotaWaves), nb), kBlock, 0,
+             st, static_cast<const int32_t *>(wave_first.ptr), static_cast<const int32_t *>(wave_info.ptr), waves,
+             static_cast<const int32_t *>(off.ptr), static_cast<const int32_t *>(col.ptr),
+             static_cast<const int32_t *>(slot.ptr), depth, min_items, sc, ld, val, avail, G);
+    if (plan.n_long() > 0) {
+      const auto [places, lds] = select_list(depth);
+      LAUNCH(shelf_value_long_kernel, dim3(static_cast<unsigned>(plan.n_long()), nb), kRecWave, lds, st,
+             static_cast<const int32_t *>(off.ptr), static_cast<const int32_t *>(col.ptr),
+             static_cast<const int32_t *>(slot.ptr), plan.n_short, depth, min_items, places, sc, ld, val, avail, G);
+    }
+  }
+};
+
+// Every row of a shelves answer as "no shelf" (the last three: null when per_shelf = 0)
+void shelves_blank(int64_t n_users, const ShelfAsk &ask, const ShelfOut &out) {
+  const size_t ns = static_cast<size_t>(ask.n_shelves), ps = static_cast<size_t>(ask.per_shelf);
+  for (size_t b = 0; b < static_cast<size_t>(n_users); ++b) {
+    out.shelf_counts[b] = 0;
+    for (size_t k = 0; k < ns; ++k) {
+      out.shelf_cats[b * ns + k] = -1;
+      out.shelf_values[b * ns + k] = -INFINITY;
+      out.shelf_available[b * ns + k] = 0;
+      if (ps > 0) out.item_counts[b * ns + k] = 0;
+      for (size_t e = 0; e < ps; ++e) {
+        out.items[(b * ns + k) * ps + e] = -1;
+        out.scores[(b * ns + k) * ps + e] = -INFINITY;
+      }
+    }
+  }
+}
+
+// The start of both shelves entries, before any launch: every row blanked and the host plan made.  False: no row, no
+// candidate or no category with a column -- every row stays empty and nothing is launched.
+bool shelves_begin(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *cand, int n_cand, int64_t n_cats,
+                   const int64_t *cat_offsets, const int32_t *cat_items, const ShelfAsk &ask, const ShelfOut &out,
+                   ShelfPlan &plan) {
+  shelves_blank(n_users, ask, out);
+  c->last_ms[T_RECOMMEND] = 0.f;
+  if (n_users == 0 || n_cats == 0 || (cand ? n_cand : c->rc->items) == 0) return false;
+  plan = plan_shelves(cand, n_cand, n_cats, cat_offsets, cat_items);
+  return plan.kept() > 0;
+}
+
+// A shelves query: rows users[0 .. n_users) (host ids, rows of x) within cand / xoff / xit as rec_within_device's, the
+// categories cats.  A batch loop of its own: per batch the score tiles and the exclusions (within_fill: the launches of
+// recommend_query_within), the value kernels, the selection over the value buffer and the chosen shelves' items, all
+// before the next batch overwrites the scores; every row's result stays on the device until the end.
+// `plan`: shelves_begin's, with at least one category.
+void rec_shelves_run(mmsbm_hip_ctx *c, const double *x, size_t xs, int64_t n_users, const int32_t *users, SeenLists seen,
+                     const int32_t *cand, int n_cand, const int64_t *xoff, const int32_t *xit, ShelfPlan &&plan,
+                     const ShelfAsk &ask, const ShelfOut &out) {
+  ShelfCats sh;
+  require_free_mem(plan.bytes(), "recommend_shelves: the categories");
+  sh.upload(std::move(plan), c->stream);
+  hipStream_t st = c->stream;
+  const int G = sh.plan.kept(), ns = ask.n_shelves, ps = ask.per_shelf;
+  WithinPrep w;
+  within_prepare(c, n_users, cand, n_cand, xoff, xit, w);
+  const int C = w.C;
+  const int64_t bu = rec_batch_users(C, n_users);  // (the item buffer decides: G <= C)
+  const auto [parts, per] = item_parts(G, bu, 32LL * c->n_cus, kRecMinPerPart);
+  const size_t cands = parts > 1 ? static_cast<size_t>(bu) * parts * ns : 0;
+  const size_t rows_ns = static_cast<size_t>(n_users) * ns, outs = rows_ns * ps;
+  const size_t vals = static_cast<size_t>(bu) * G;
+  require_free_mem(static_cast<size_t>(bu) * C * sizeof(double) + vals * (ps == 0 ? 12 : 8) + cands * 12 +
+                       static_cast<size_t>(bu) * parts * 4 + rows_ns * 20 + outs * 12 + static_cast<size_t>(n_users) * 8,
+                   "recommend_shelves: a batch of users");
+  DevBuf<int32_t> du, ci, cn, oi, on, oa, av, ic, in;
+  DevBuf<double> sc, val, cs, os, is;
+  du.alloc(n_users);
+  sc.alloc(static_cast<size_t>(bu) * C);
+  val.alloc(vals);
+  if (ps == 0) av.alloc(vals);
+  if (parts > 1) {
+    cs.alloc(cands); ci.alloc(cands); cn.alloc(static_cast<size_t>(bu) * parts);
+  }
+  os.alloc(rows_ns); oi.alloc(rows_ns); oa.alloc(rows_ns); on.alloc(n_users);
+  if (ps > 0) {
+    is.alloc(outs); ic.alloc(outs); in.alloc(rows_ns);
+  }
+  HIP_CHECK(hipMemcpyAsync(du.ptr, users, sizeof(int32_t) * n_users, hipMemcpyHostToDevice, st));
+  const auto tiles = rec_tiles(c, x, xs);
+  const auto [places, lds] = select_list(std::max(ps, 1));
+  EventPair ev;  // device time of the query's kernels (option "recommend_ms")
+  ev.start(st);
+  for (int64_t b0 = 0; b0 < n_users; b0 += bu) {  // (batches follow each other on the stream: no host wait in between)
+    const int nb = static_cast<int>(std::min(bu, n_users - b0));
+    int32_t *obi = oi.ptr + b0 * ns, *obn = on.ptr + b0, *oba = oa.ptr + b0 * ns;
+    within_fill(c, w, tiles, seen, du.ptr + b0, nb, b0, sc.ptr);
+    sh.values(st, nb, sc.ptr, static_cast<size_t>(C), ask.depth, ask.min_items, val.ptr, av.ptr);
+    select_batch(st, val.ptr, G, nb, parts, per, ns, cs.ptr, ci.ptr, cn.ptr, os.ptr + b0 * ns, obi, obn);
+    if (ps > 0)
+      LAUNCH(shelf_items_kernel, dim3(static_cast<unsigned>(ns), nb), kRecWave, lds, st, static_cast<const int32_t *>(obi),
+             static_cast<const int32_t *>(obn), static_cast<const int32_t *>(sh.of_slot.ptr),
+             static_cast<const int32_t *>(sh.off.ptr), static_cast<const int32_t *>(sh.col.ptr), ps, places,
+             static_cast<const double *>(sc.ptr), static_cast<size_t>(C), ic.ptr + b0 * ns * ps, is.ptr + b0 * ns * ps,
+             in.ptr + b0 * ns, oba);
+    else
+      LAUNCH(shelf_avail_kernel, nb, kRecWave, 0, st, static_cast<const int32_t *>(obi), static_cast<const int32_t *>(obn),
+             ns, static_cast<const int32_t *>(av.ptr), static_cast<size_t>(G), oba);
+    HIP_CHECK(hipGetLastError());
+  }
+  ev.stop(st);
+  std::vector<double> hs(rows_ns), his(outs);
+  std::vector<int32_t> hi(rows_ns), ha(rows_ns), hn(static_cast<size_t>(n_users)), hic(outs), hin(ps > 0 ? rows_ns : 0);
+  HIP_CHECK(hipMemcpyAsync(hs.data(), os.ptr, sizeof(double) * rows_ns, hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipMemcpyAsync(hi.data(), oi.ptr, sizeof(int32_t) * rows_ns, hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipMemcpyAsync(ha.data(), oa.ptr, sizeof(int32_t) * rows_ns, hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipMemcpyAsync(hn.data(), on.ptr, sizeof(int32_t) * n_users, hipMemcpyDeviceToHost, st));
+  if (ps > 0) {
+    HIP_CHECK(hipMemcpyAsync(his.data(), is.ptr, sizeof(double) * outs, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(hic.data(), ic.ptr, sizeof(int32_t) * outs, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(hin.data(), in.ptr, sizeof(int32_t) * rows_ns, hipMemcpyDeviceToHost, st));
+  }
+  HIP_CHECK(hipStreamSynchronize(st));
+  c->last_ms[T_RECOMMEND] = ev.ms() + w.ct.ms;
+  for (size_t b = 0; b < static_cast<size_t>(n_users); ++b) {
+    const int cnt = hn[b];
+    out.shelf_counts[b] = cnt;
+    for (size_t k = 0; k < static_cast<size_t>(cnt); ++k) {
+      const size_t o = b * ns + k;
+      out.shelf_cats[o] = sh.plan.cat[static_cast<size_t>(sh.plan.of_slot[static_cast<size_t>(hi[o])])];
+      out.shelf_values[o] = hs[o];
+      out.shelf_available[o] = ha[o];
+      if (ps == 0) continue;
+      out.item_counts[o] = hin[o];
+      for (size_t e = 0; e < static_cast<size_t>(hin[o]); ++e) {
+        out.items[o * ps + e] = cand ? cand[hic[o * ps + e]] : hic[o * ps + e];  // columns -> item ids
+        out.scores[o * ps + e] = his[o * ps + e];
+      }
+    }
+  }
 }
 
 }  // namespace
@@ -610,6 +808,32 @@ void recommend_query_theta_quota(mmsbm_hip_ctx *c, int64_t n_users, const double
   use_device(c);
   const QuotaCats cats{n_cats, cat_offsets, cat_items, cat_caps};
   rec_theta_run(c, n_users, theta, seen_offsets, seen_items, cand, n_cand, n, items, scores, counts, &cats);
+}
+
+void recommend_query_shelves(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, const int32_t *cand, int n_cand,
+                             const int64_t *excl_offsets, const int32_t *excl_items, int64_t n_cats,
+                             const int64_t *cat_offsets, const int32_t *cat_items, const ShelfAsk &ask,
+                             const ShelfOut &out) {
+  use_device(c);
+  const RecSession &rc = *c->rc;
+  ShelfPlan plan;
+  if (!shelves_begin(c, n_users, cand, n_cand, n_cats, cat_offsets, cat_items, ask, out, plan)) return;
+  rec_shelves_run(c, rc.x.ptr, rc.x_stride(), n_users, users, rc.seen_lists(), cand, n_cand, excl_offsets, excl_items,
+                  std::move(plan), ask, out);
+}
+
+void recommend_query_theta_shelves(mmsbm_hip_ctx *c, int64_t n_users, const double *theta, const int64_t *seen_offsets,
+                                   const int32_t *seen_items, const int32_t *cand, int n_cand, int64_t n_cats,
+                                   const int64_t *cat_offsets, const int32_t *cat_items, const ShelfAsk &ask,
+                                   const ShelfOut &out) {
+  use_device(c);
+  ShelfPlan plan;
+  if (!shelves_begin(c, n_users, cand, n_cand, n_cats, cat_offsets, cat_items, ask, out, plan)) return;
+  rec_theta_fold(c, n_users, theta, seen_offsets, seen_items,
+                 [&](const double *x, size_t xs, const int32_t *ids, SeenLists seen) {
+                   rec_shelves_run(c, x, xs, n_users, ids, seen, cand, n_cand, nullptr, nullptr, std::move(plan), ask,
+                                   out);
+                 });
 }
 
 void recommend_rank(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, const int64_t *offsets,

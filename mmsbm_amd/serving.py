@@ -76,32 +76,30 @@ class Quota:
         return table[self.category_of[np.asarray(ids, dtype=np.int64)]]
 
 
-def quota_categories(categories, max_per_category, items):
-    """``recommend_quota``'s ``categories`` and ``max_per_category`` against the item table ``items`` (a ``_Side``; no
-    context is needed) -> ``Quota``.
+def _category_columns(categories):
+    """(item labels, categories) of a ``categories`` argument in one of its three forms; anything else: ValueError."""
+    if isinstance(categories, dict):
+        return list(categories.keys()), list(categories.values())
+    if isinstance(categories, pd.DataFrame):
+        if categories.shape[1] < 2:
+            raise ValueError("categories needs two columns: items and categories")
+        return categories.iloc[:, 0].tolist(), categories.iloc[:, 1].tolist()
+    if isinstance(categories, pd.Series):
+        return categories.index.tolist(), categories.tolist()
+    raise ValueError("categories must be a dict {item: category}, a Series indexed by item or a DataFrame of "
+                     f"(item, category) rows, got {type(categories).__name__}")
+
+
+def category_table(categories, items):
+    """A ``categories`` argument against the item table ``items`` (a ``_Side``) -> (ids, codes, labels, category_of):
+    the items that have a category (encoded ids, ascending and distinct) and the place of each one's category in
+    ``labels`` -- the caller's labels in order of first appearance --, and ``category_of``: one per item of the side,
+    that place or -1.
 
     ``categories``: a dict {item label: category}, a Series indexed by item, or a DataFrame whose first two columns are
     item and category.  Items the side does not have are ignored, a missing category (None / NaN) leaves the item
-    uncapped, an item given two different categories is a ValueError.  ``max_per_category``: an integer >= 0 for every
-    category, or a dict {category: integer >= 0} -- categories it does not name are uncapped."""
-    if isinstance(categories, dict):
-        labs, cats = list(categories.keys()), list(categories.values())
-    elif isinstance(categories, pd.DataFrame):
-        if categories.shape[1] < 2:
-            raise ValueError("categories needs two columns: items and categories")
-        labs, cats = categories.iloc[:, 0].tolist(), categories.iloc[:, 1].tolist()
-    elif isinstance(categories, pd.Series):
-        labs, cats = categories.index.tolist(), categories.tolist()
-    else:
-        raise ValueError("categories must be a dict {item: category}, a Series indexed by item or a DataFrame of "
-                         f"(item, category) rows, got {type(categories).__name__}")
-    must_be = "an integer >= 0 or a dict {category: integer >= 0}"
-    if isinstance(max_per_category, dict):
-        per = {c: check_integer(v, f"max_per_category[{c!r}]", 0, "an integer >= 0") for c, v in max_per_category.items()}
-        cap_of = lambda c: per.get(c, -1)                                      # noqa: E731  (-1: uncapped)
-    else:
-        every = check_integer(max_per_category, "max_per_category", 0, must_be)
-        cap_of = lambda c: every                                               # noqa: E731
+    without one, an item given two different categories is a ValueError."""
+    labs, cats = _category_columns(categories)
     ids = items.ids(labs)
     held = np.empty(len(cats), dtype=object)
     for j, c in enumerate(cats):
@@ -119,7 +117,26 @@ def quota_categories(categories, max_per_category, items):
     ids, codes = ids[first], codes[first]
     category_of = np.full(len(items), -1, dtype=np.int64)
     category_of[ids] = codes
-    labels = list(labels)
+    return ids, codes, list(labels), category_of
+
+
+def quota_categories(categories, max_per_category, items):
+    """``recommend_quota``'s ``categories`` and ``max_per_category`` against the item table ``items`` (a ``_Side``; no
+    context is needed) -> ``Quota``.
+
+    ``categories``: a dict {item label: category}, a Series indexed by item, or a DataFrame whose first two columns are
+    item and category.  Items the side does not have are ignored, a missing category (None / NaN) leaves the item
+    uncapped, an item given two different categories is a ValueError.  ``max_per_category``: an integer >= 0 for every
+    category, or a dict {category: integer >= 0} -- categories it does not name are uncapped."""
+    _category_columns(categories)                                              # (its ValueError comes first)
+    must_be = "an integer >= 0 or a dict {category: integer >= 0}"
+    if isinstance(max_per_category, dict):
+        per = {c: check_integer(v, f"max_per_category[{c!r}]", 0, "an integer >= 0") for c, v in max_per_category.items()}
+        cap_of = lambda c: per.get(c, -1)                                      # noqa: E731  (-1: uncapped)
+    else:
+        every = check_integer(max_per_category, "max_per_category", 0, must_be)
+        cap_of = lambda c: every                                               # noqa: E731
+    ids, codes, labels, category_of = category_table(categories, items)
     cap = np.array([cap_of(c) for c in labels], dtype=np.int64)
     capped = np.flatnonzero(cap >= 0)
     place = np.full(len(labels), -1, dtype=np.int64)
@@ -127,6 +144,15 @@ def quota_categories(categories, max_per_category, items):
     mine = place[codes] >= 0
     offsets, members = grouped(place[codes][mine], ids[mine], len(capped), sort=True)
     return Quota(offsets, members, cap[capped].astype(np.int32), category_of, labels)
+
+
+def shelf_categories(categories, items):
+    """``recommend_shelves``' ``categories`` (``category_table``'s forms and rules) against the item table ``items`` ->
+    a ``Quota`` without caps: category g -- the g-th label in order of first appearance, which is the order that decides
+    between equal shelf values -- holds the items ``items[offsets[g]:offsets[g + 1]]``."""
+    ids, codes, labels, category_of = category_table(categories, items)
+    offsets, members = grouped(codes, ids, len(labels), sort=True)
+    return Quota(offsets, members, None, category_of, labels)
 
 
 # ---------------------------------------------------------------------- capacities
@@ -427,6 +453,97 @@ class Serving:
             return self._top_n_frame(
                 lambda b, e: ctx.recommend_query_quota(ids[b:e], n, quota.offsets, quota.items, quota.caps, cand,
                                                        group_slice(extra, b, e)), n, labels, items, derived=derived)
+
+    def _shelves_frame(self, query, shelves, per_shelf, row_labels, cats):
+        """The frame of a shelves query of rows [0, len(row_labels)): ``query(b, e)`` -> HipEM.recommend_query_shelves'
+        tuple for rows [b, e); ``cats``: the ``Quota`` whose labels name the returned category indices.  per_shelf 0:
+        one line per shelf (users, category, score, available, rank), else one per item of a shelf (users, category,
+        shelf, shelf_score, available, items, score, rank)."""
+        table = np.empty(len(cats.labels) + 1, dtype=object)
+        table[:-1] = cats.labels
+
+        def entries(b, e):
+            sc, sv, sa, cnt, it, s, ic = query(b, e)
+            live = np.arange(shelves)[None, :] < cnt[:, None]                        # (rows, shelves)
+            if per_shelf == 0:
+                r, k = np.nonzero(live)
+                return cnt, {"row": r, "category": table[sc[r, k]], "score": sv[r, k], "available": sa[r, k],
+                             "rank": k.astype(np.int64) + 1}
+            r, k, j = np.nonzero(live[:, :, None] & (np.arange(per_shelf)[None, None, :] < ic[:, :, None]))
+            return cnt, {"row": r, "category": table[sc[r, k]], "shelf": k.astype(np.int64) + 1, "shelf_score": sv[r, k],
+                         "available": sa[r, k], "items": it[r, k, j], "score": s[r, k, j], "rank": j.astype(np.int64) + 1}
+        if per_shelf == 0:
+            columns = dict.fromkeys(("category", "score", "available", "rank"))
+        else:
+            columns = {**dict.fromkeys(("category", "shelf", "shelf_score", "available")), "items": self._side("items"),
+                       "score": None, "rank": None}
+        frame = self._frame({"users": row_labels}, columns, self._row_batches(len(row_labels), shelves * max(per_shelf, 1)),
+                            entries)
+        if not len(frame):
+            ints = [c for c in ("shelf", "available", "rank") if c in frame]
+            frame = frame.astype({"category": object, **dict.fromkeys(ints, np.int64)})
+        return frame
+
+    @staticmethod
+    def _shelves_args(shelves, per_shelf, depth, min_items, name="shelves"):
+        """(shelves, per_shelf, depth, min_items) checked as integers >= 1; per_shelf None: no item lists (0 to the
+        device); depth None: per_shelf."""
+        shelves = check_integer(shelves, name, 1)
+        per_shelf = 0 if per_shelf is None else check_integer(per_shelf, "per_shelf", 1)
+        depth = per_shelf if depth is None and per_shelf else check_integer(depth, "depth", 1)
+        return shelves, per_shelf, depth, check_integer(min_items, "min_items", 1)
+
+    def recommend_shelves(self, users=None, shelves=5, per_shelf=10, categories=..., depth=None, min_items=1,
+                          exclude_seen=True, weights=None, candidates=None, exclude=None):
+        """Which categories to show each user, and what to put on them: the rows of a front page ("Thrillers", "Brand
+        X", "New this week"), each holding that user's best items of one category.  Over ``recommend``'s candidates
+        (the user's own items, ``candidates`` and ``exclude`` applied first) and scores, a category's value for a user
+        is the mean of its ``depth`` best candidates' scores (of all of them when it has fewer; ``depth=None``:
+        ``per_shelf``; ``depth=1``: its best item's score), added best first; a category with fewer than ``min_items``
+        candidates is not shown.  The user's shelves are the ``shelves`` categories of largest value -- equal values in
+        the order in which the categories first appear in ``categories`` -- and a shelf's items its ``per_shelf`` best.
+        One query on the device: no users x categories x depth table is formed.
+
+        ``categories`` (required): ``recommend_quota``'s three forms with its rules -- unknown items are ignored, an
+        item it does not name or whose category is None / NaN is on no shelf, an item given two different categories:
+        ValueError.  The other arguments are ``recommend``'s.
+
+        Returns a DataFrame with columns ``users``, ``category``, ``shelf`` (1 = best), ``shelf_score``, ``available``
+        (the category's candidates for the user), ``items``, ``score``, ``rank`` (1 = best inside the shelf): one line
+        per item of a shelf, users in request order.  Scores are ``recommend``'s, bit for bit.  The model's stored
+        predictions and ``score()`` are left as they are."""
+        if categories is ...:
+            raise TypeError("recommend_shelves needs categories=")
+        per_shelf = check_integer(per_shelf, "per_shelf", 1)                   # (no item lists: recommend_categories)
+        shelves, per_shelf, depth, min_items = self._shelves_args(shelves, per_shelf, depth, min_items)
+        return self._recommend_shelves(users, shelves, per_shelf, categories, depth, min_items, exclude_seen, weights,
+                                       candidates, exclude)
+
+    def recommend_categories(self, users=None, n=5, categories=..., depth=10, min_items=1, exclude_seen=True,
+                             weights=None, candidates=None, exclude=None):
+        """The ``n`` best categories per user without their items: ``recommend_shelves`` with no item lists.  Returns a
+        DataFrame with columns ``users``, ``category``, ``score`` (the category's value: the mean of the user's
+        ``depth`` best candidates of it), ``available``, ``rank`` (1 = best)."""
+        if categories is ...:
+            raise TypeError("recommend_categories needs categories=")
+        n, _, depth, min_items = self._shelves_args(n, None, depth, min_items, "n")
+        return self._recommend_shelves(users, n, 0, categories, depth, min_items, exclude_seen, weights, candidates, exclude)
+
+    def _recommend_shelves(self, users, shelves, per_shelf, categories, depth, min_items, exclude_seen, weights,
+                           candidates, exclude):
+        self._check_whole_model()
+        w = self._rating_weights(weights)
+        ids, labels = self._side("users").request(users)
+        cats = shelf_categories(categories, self._side("items"))
+        cand = self._candidate_ids(candidates)
+        if cand is not None and len(cand) == 0:
+            return self._shelves_frame(None, shelves, per_shelf, labels[:0], cats)
+        extra = self._exclusion_lists(exclude, ids)
+        with self._session_of_restarts("recommend", w, exclude_seen) as ctx:
+            return self._shelves_frame(
+                lambda b, e: ctx.recommend_query_shelves(ids[b:e], cats.offsets, cats.items, depth, min_items, shelves,
+                                                         per_shelf, cand, group_slice(extra, b, e)),
+                shelves, per_shelf, labels, cats)
 
     def allocate(self, n=1, capacity=..., users=None, exclude_seen=True, weights=None, candidates=None,
                  max_rounds=10000):
@@ -1158,6 +1275,31 @@ class Serving:
         self._check_whole_model()
         quota = quota_categories(categories, max_per_category, self._side("items"))
         return self._recommend_new(data, n, exclude_seen, weights, iterations, tol, candidates, quota)
+
+    def recommend_new_shelves(self, data, shelves=5, per_shelf=10, categories=..., depth=None, min_items=1,
+                              exclude_seen=True, weights=None, iterations=100, tol=None, candidates=None):
+        """``recommend_shelves`` for users that were not in the training data, folded in as ``recommend_new`` folds
+        them (``iterations``, ``tol``): ``recommend_shelves``' frame, users in order of first appearance in ``data``;
+        ``per_shelf=0``: ``recommend_categories``' frame (then ``depth`` is required)."""
+        if categories is ...:
+            raise TypeError("recommend_new_shelves needs categories=")
+        self._check_whole_model()
+        per_shelf = check_integer(per_shelf, "per_shelf", 0, "a non-negative integer") or None
+        shelves, per_shelf, depth, min_items = self._shelves_args(shelves, per_shelf, depth, min_items)
+        w = self._rating_weights(weights)
+        cats = shelf_categories(categories, self._side("items"))
+        cand = self._candidate_ids(candidates)
+        iterations, tol = self._fold_args(iterations, tol)
+        rows, labels = self._encode_new(data, 0)
+        with session(self._ctx(self._device_list()[0]), "recommend", w, False) as ctx:
+            thetas, iters = self._fold_runs(rows, len(labels), iterations, tol, each=lambda c: c.recommend_add())
+            self.fold_in_iterations = pd.DataFrame(np.stack(iters, 1), index=pd.Index(labels, name="users"))
+            theta = np.stack(thetas)                                  # (restarts, new users, K)
+            seen = grouped(rows[:, 0], rows[:, 1], len(labels), sort=True) if exclude_seen else None
+            return self._shelves_frame(
+                lambda b, e: ctx.recommend_query_theta_shelves(theta[:, b:e], cats.offsets, cats.items, depth, min_items,
+                                                               shelves, per_shelf, group_slice(seen, b, e), cand),
+                shelves, per_shelf, labels, cats)
 
     def _recommend_new(self, data, n, exclude_seen, weights, iterations, tol, candidates, quota):
         """recommend_new (``quota`` None) and recommend_new_quota (a ``Quota``)."""
