@@ -380,6 +380,55 @@ int mmsbm_hip_recommend_query_theta_shelves(mmsbm_hip_ctx *ctx, int64_t n_users,
                                             double *shelf_values, int32_t *shelf_available, int32_t *shelf_counts,
                                             int32_t *items, double *scores, int32_t *item_counts);
 
+/* Randomised top-N with logged propensities, inside the open recommend session (mmsbm_amd/csrc/explore.hpp): every
+ * other query returns the same list on every call, so items just below the cut are never shown and nothing logged can
+ * evaluate another policy.  query_explore draws row b's list WITHOUT replacement from the Plackett-Luce distribution
+ * over query_within's candidates of the row (what query leaves out, cand_items and excl_* applied) with utilities
+ * score / temperature, and returns the probability of every position.  The one definition, for user u = users[b]:
+ *   r(u, i)   the double numpy's Generator.random() returns as draw number u * 2^32 + i (counting from 0) of the PCG64
+ *             stream pcg64_state = { state_hi, state_lo, inc_hi, inc_lo } (as mmsbm_hip_init_params takes it): in numpy,
+ *             bg.advance(u << 32 | i), then one random().  A function of the stream, u and i alone;
+ *   g(u, i)   E = -log(1 - r), E = 2^-54 where r = 0; g = -log(E): always finite;
+ *   key       s(u, i) + temperature * g(u, i): the product rounded, then the sum rounded (no fma); s: query's bits;
+ *   list      the n candidates of largest key, key descending, equal keys by ascending item id;
+ *   propensity of position t = 1 .. counts[b]: with m = the row's largest candidate score and
+ *             e_i = exp((s_i - m) / temperature), e_t / R_t where R_t = the sum of e_i over the candidates not ranked
+ *             above t -- accumulated from those candidates in a fixed order, never as a difference, so the last
+ *             remaining candidate of a row has propensity exactly 1.0.  The product of a row's propensities is the
+ *             probability of its list.
+ * Output as query_within's, scores being the SCORES of the listed items (not the keys), plus propensity [n_users][n],
+ * padded with 0 (scores, propensity, counts may be NULL).  A row depends on its user and the arguments alone, bit for
+ * bit.  The temperature floor: a score lies in [min w, max w] of the session's weights, and (max w - min w) /
+ * temperature > 700 is refused -- below that temperature the policy is query's list to within 1e-300, and no e_i
+ * underflows above it.  "recommend_ms" reads the device time of the call's kernels.  MMSBM_E_INVALID (before any
+ * launch): what query_within refuses, a temperature that is not finite, <= 0 or below the floor, a null pcg64_state;
+ * n > MMSBM_HIP_RECOMMEND_MAX_N: MMSBM_E_UNSUPPORTED; MMSBM_E_TOOLARGE where the device memory is not free (a second
+ * batch buffer holds the unperturbed scores).
+ *
+ * list_propensity: what the policy WOULD have given lists that somebody else logged.  Row b's list is
+ * list_items[list_offsets[b] .. list_offsets[b + 1]) (list_offsets: int64 [n_users + 1]; distinct ids of the session's
+ * catalogue, at most MMSBM_HIP_RECOMMEND_MAX_N, taken in the order given); scores / propensity [list_offsets[n_users]]
+ * (scores may be NULL).  An item that is no candidate of the row gets propensity 0 and score -inf, and the rest of the
+ * list is computed as if it were absent; otherwise the definition above, without noise and seed: applied to
+ * query_explore's own output with the same arguments it returns that call's propensity bits.  MMSBM_E_INVALID: what
+ * query_within refuses, the temperature as above, a bad CSR, an id out of range, an item twice in a list; a list longer
+ * than MMSBM_HIP_RECOMMEND_MAX_N: MMSBM_E_UNSUPPORTED.
+ *
+ * explore_noise: r and g of the definition for n_pairs arbitrary pairs of non-negative int32 ids, computed on the
+ * device by the function the perturbation calls -- the noise of a logged impression can be derived again.  Needs no
+ * session and no parameters. */
+int mmsbm_hip_recommend_query_explore(mmsbm_hip_ctx *ctx, int64_t n_users, const int32_t *users, int32_t n_cand,
+                                      const int32_t *cand_items, const int64_t *excl_offsets,
+                                      const int32_t *excl_items, int32_t n, double temperature,
+                                      const uint64_t pcg64_state[4], int32_t *items, double *scores,
+                                      double *propensity, int32_t *counts);
+int mmsbm_hip_recommend_list_propensity(mmsbm_hip_ctx *ctx, int64_t n_users, const int32_t *users, int32_t n_cand,
+                                        const int32_t *cand_items, const int64_t *excl_offsets,
+                                        const int32_t *excl_items, double temperature, const int64_t *list_offsets,
+                                        const int32_t *list_items, double *scores, double *propensity);
+int mmsbm_hip_explore_noise(mmsbm_hip_ctx *ctx, const uint64_t pcg64_state[4], int64_t n_pairs, const int32_t *users,
+                            const int32_t *items, double *r, double *g);
+
 /* Capacity-aware allocation, inside the open recommend session (mmsbm_amd/csrc/allocate.hpp): items run out.  Every
  * user of the request asks for n items, item i of the session's catalogue (the items of recommend_add_items included)
  * can be given out caps[i] times: stock, a reviewer's load, coupons per product.  The one definition: take all pairs

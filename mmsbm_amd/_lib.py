@@ -82,6 +82,13 @@ SIGNATURES = {
                                                           c_i32p, C.c_int64, c_i64p, c_i32p, C.c_int32, C.c_int32,
                                                           C.c_int32, C.c_int32, c_i32p, c_f64p, c_i32p, c_i32p, c_i32p,
                                                           c_f64p, c_i32p]),
+    "mmsbm_hip_recommend_query_explore": (C.c_int, [C.c_void_p, C.c_int64, c_i32p, C.c_int32, c_i32p, c_i64p, c_i32p,
+                                                    C.c_int32, C.c_double, C.POINTER(C.c_uint64), c_i32p, c_f64p,
+                                                    c_f64p, c_i32p]),
+    "mmsbm_hip_recommend_list_propensity": (C.c_int, [C.c_void_p, C.c_int64, c_i32p, C.c_int32, c_i32p, c_i64p, c_i32p,
+                                                      C.c_double, c_i64p, c_i32p, c_f64p, c_f64p]),
+    "mmsbm_hip_explore_noise": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_int64, c_i32p, c_i32p, c_f64p,
+                                          c_f64p]),
     "mmsbm_hip_recommend_rank": (C.c_int, [C.c_void_p, C.c_int64, c_i32p, c_i64p, c_i32p, C.c_int32, c_i32p, c_f64p,
                                            c_i32p]),
     "mmsbm_hip_similar_begin": (C.c_int, [C.c_void_p, C.c_int]),

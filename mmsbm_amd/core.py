@@ -419,6 +419,59 @@ class HipEM:
         return items, scores, counts
 
     @staticmethod
+    def _pcg64_state(state):
+        """The four state words of the C ABI: ``pcg64_words``' array as it is, or those of a numpy PCG64 bit
+        generator (left where it stands); None: a null pointer, which the library refuses."""
+        return pcg64_words(state) if hasattr(state, "state") else state
+
+    def recommend_query_explore(self, users, n, temperature, state, candidates=None, exclude=None):
+        """recommend_query_within drawn at random: each row's list is sampled without replacement from the
+        Plackett-Luce distribution over the row's candidates with utilities score / ``temperature`` -- the n largest
+        of score + temperature * g(user, item), g the Gumbel noise of draw number (user << 32 | item) of the PCG64
+        stream ``state`` (``pcg64_words``' four words, or the bit generator itself) -- and every position comes with
+        the probability the policy had of showing it there.  Returns (items, scores, propensity (M,n) padded with 0,
+        counts); scores are recommend_query's bits of the listed items, not the perturbed keys."""
+        u, n = _i32(users), int(n)
+        cand = None if candidates is None else _i32(candidates)
+        off, it = _csr(exclude, len(u), "exclude offsets", "items")
+        items, scores, counts = self._query_out(len(u), n)
+        prop = np.empty((len(u), max(n, 0)), dtype=np.float64)
+        _lib.call("mmsbm_hip_recommend_query_explore", self._h, len(u), _p(u, C.c_int32),
+                  0 if cand is None else len(cand), _p_or_null(cand, C.c_int32),
+                  _p_or_null(off, C.c_int64), _p_or_null(it, C.c_int32), n, float(temperature),
+                  self._pcg64_state(state), _p(items, C.c_int32), _p(scores, C.c_double), _p(prop, C.c_double),
+                  _p(counts, C.c_int32))
+        return items, scores, prop, counts
+
+    def recommend_list_propensity(self, users, lists, temperature, candidates=None, exclude=None):
+        """What recommend_query_explore's policy would have given caller-given lists: ``lists`` = (offsets (M+1,)
+        int64, items int32), row b's list is items[offsets[b]:offsets[b + 1]] in the order given (distinct ids, at most
+        MAX_RECOMMEND).  Returns (scores, propensity), one entry per listed item: -inf / 0 where the item is no
+        candidate of its row, and the rest of that list as if the item were absent.  No noise, no seed."""
+        u = _i32(users)
+        cand = None if candidates is None else _i32(candidates)
+        off, it = _csr(exclude, len(u), "exclude offsets", "items")
+        loff, lit = _csr(lists, len(u), "list offsets", "items")
+        scores, prop = np.empty(len(lit), dtype=np.float64), np.empty(len(lit), dtype=np.float64)
+        _lib.call("mmsbm_hip_recommend_list_propensity", self._h, len(u), _p(u, C.c_int32),
+                  0 if cand is None else len(cand), _p_or_null(cand, C.c_int32),
+                  _p_or_null(off, C.c_int64), _p_or_null(it, C.c_int32), float(temperature),
+                  _p(loff, C.c_int64), _p(lit, C.c_int32), _p(scores, C.c_double), _p(prop, C.c_double))
+        return scores, prop
+
+    def explore_noise(self, state, users, items):
+        """(r, g) of recommend_query_explore's noise for the given (user, item) pairs of non-negative int32 ids: r the
+        uniform of draw number (user << 32 | item) of the stream, g = -log(-log(1 - r)) (E = 2^-54 where r = 0),
+        computed on the device by the function the perturbation calls.  Needs no session."""
+        u, i = _i32(users), _i32(items)
+        if u.shape != i.shape or u.ndim != 1:
+            raise ValueError(f"users and items have shapes {u.shape} and {i.shape}: two 1-d arrays of one length expected")
+        r, g = np.empty(len(u), dtype=np.float64), np.empty(len(u), dtype=np.float64)
+        _lib.call("mmsbm_hip_explore_noise", self._h, self._pcg64_state(state), len(u), _p(u, C.c_int32),
+                  _p(i, C.c_int32), _p(r, C.c_double), _p(g, C.c_double))
+        return r, g
+
+    @staticmethod
     def _categories(cat_offsets, cat_items, caps):
         """(caps int32, offsets int64, items int32) of the capped categories of the two quota queries."""
         cap = _i32(caps)

@@ -121,6 +121,7 @@ struct RecSession {
   int rank = 0;
   int users = 0;                        // U
   bool excl = false;                    // seen_* in use: exclude_train, or seen lists of recommend_add_items
+  double w_min = 0.0, w_max = 0.0;      // the smallest and the largest rating weight: every score lies between them
   SeenLists seen_lists() const { return {excl ? seen_off.ptr : nullptr, seen.ptr}; }
   size_t x_stride() const { return static_cast<size_t>(users) * rank; }  // doubles between two slots of x
 };

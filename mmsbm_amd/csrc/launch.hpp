@@ -106,6 +106,19 @@ void recommend_query_theta_shelves(mmsbm_hip_ctx *c, int64_t n_users, const doub
                                    const int32_t *seen_items, const int32_t *cand, int n_cand, int64_t n_cats,
                                    const int64_t *cat_offsets, const int32_t *cat_items, const ShelfAsk &ask,
                                    const ShelfOut &out);
+// ... randomised top-N with propensities (explore.hpp): recommend_query_within's request, a temperature above the
+// session's floor and the four words of a PCG64 stream; the propensities of caller-given lists (list_offsets int64
+// [n_users + 1], distinct items per row); r and g of given (user, item) pairs, no session needed
+void recommend_query_explore(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, const int32_t *cand, int n_cand,
+                             const int64_t *excl_offsets, const int32_t *excl_items, int n, double temperature,
+                             const uint64_t pcg64_state[4], int32_t *items, double *scores, double *propensity,
+                             int32_t *counts);
+void recommend_list_propensity(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, const int32_t *cand, int n_cand,
+                               const int64_t *excl_offsets, const int32_t *excl_items, double temperature,
+                               const int64_t *list_offsets, const int32_t *list_items, double *scores,
+                               double *propensity);
+void explore_noise(mmsbm_hip_ctx *c, const uint64_t pcg64_state[4], int64_t n_pairs, const int32_t *users,
+                   const int32_t *items, double *r, double *g);
 // ... capacity-aware allocation (allocate.hpp): every user of the request (distinct ids) asks for n items, the caps as
 // planned by plan_allocate (serve_plan.hpp); at most max_rounds rounds
 void recommend_allocate(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, int n, const AllocPlan &plan,

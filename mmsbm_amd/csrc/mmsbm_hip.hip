@@ -705,6 +705,85 @@ int mmsbm_hip_recommend_query_theta_within(mmsbm_hip_ctx *ctx, int64_t n_users, 
 }
 
 namespace {
+// The temperature of the two explore entries: finite, > 0 and not below the session's floor (explore.hpp: a score lies
+// in [min w, max w], and no exp((s - m) / T) may underflow)
+void require_temperature(double t, const RecSession &rc, const char *who) {
+  const std::string w = std::string(who) + ": ";
+  if (!std::isfinite(t) || t <= 0.0) throw std::invalid_argument(w + "the temperature must be finite and > 0");
+  if ((rc.w_max - rc.w_min) / t > 700.0)
+    throw std::invalid_argument(w + "temperature " + std::to_string(t) + " is below the floor " +
+                                std::to_string((rc.w_max - rc.w_min) / 700.0) + " of the session's weights ((max w - min w) / 700)");
+}
+}  // namespace
+
+int mmsbm_hip_recommend_query_explore(mmsbm_hip_ctx *ctx, int64_t n_users, const int32_t *users, int32_t n_cand,
+                                      const int32_t *cand_items, const int64_t *excl_offsets,
+                                      const int32_t *excl_items, int32_t n, double temperature,
+                                      const uint64_t pcg64_state[4], int32_t *items, double *scores,
+                                      double *propensity, int32_t *counts) {
+  return guarded([&] {
+    const RecSession &rc = require_open(ctx, &mmsbm_hip_ctx::rc, "recommend", "recommend_query_explore");
+    if (n_users < 0) throw std::invalid_argument("negative n_users");
+    require_n(n, "recommend_explore", "items");
+    require_temperature(temperature, rc, "recommend_query_explore");
+    if (!pcg64_state || (n_users > 0 && (!users || !items))) throw std::invalid_argument("null argument");
+    require_ids(users, n_users, ctx->ext_users, "recommend: user");
+    require_subset(cand_items, n_cand, rc.items, "recommend_query_explore");
+    check_csr(excl_offsets, excl_items, n_users, rc.items, "recommend_query_explore", "excl_offsets", "user",
+              "excluded items", "excluded item");
+    recommend_query_explore(ctx, n_users, users, cand_items, n_cand, n_users > 0 ? excl_offsets : nullptr, excl_items, n,
+                            temperature, pcg64_state, items, scores, propensity, counts);
+  });
+}
+
+int mmsbm_hip_recommend_list_propensity(mmsbm_hip_ctx *ctx, int64_t n_users, const int32_t *users, int32_t n_cand,
+                                        const int32_t *cand_items, const int64_t *excl_offsets,
+                                        const int32_t *excl_items, double temperature, const int64_t *list_offsets,
+                                        const int32_t *list_items, double *scores, double *propensity) {
+  return guarded([&] {
+    const char *who = "recommend_list_propensity";
+    const RecSession &rc = require_open(ctx, &mmsbm_hip_ctx::rc, "recommend", who);
+    if (n_users < 0) throw std::invalid_argument("negative n_users");
+    require_temperature(temperature, rc, who);
+    if (n_users > 0 && (!users || !list_offsets)) throw std::invalid_argument("null argument");
+    require_ids(users, n_users, ctx->ext_users, "recommend: user");
+    require_subset(cand_items, n_cand, rc.items, who);
+    check_csr(excl_offsets, excl_items, n_users, rc.items, who, "excl_offsets", "user", "excluded items", "excluded item");
+    check_csr(list_offsets, list_items, n_users, rc.items, who, "list_offsets", "user", "listed items", "listed item");
+    if (n_users > 0 && list_offsets[n_users] > 0 && !propensity) throw std::invalid_argument("null argument");
+    std::vector<int32_t> row;
+    for (int64_t b = 0; b < n_users; ++b) {
+      const int64_t len = list_offsets[b + 1] - list_offsets[b];
+      if (len > MMSBM_HIP_RECOMMEND_MAX_N)
+        throw ApiError(MMSBM_E_UNSUPPORTED, std::string(who) + ": the list of row " + std::to_string(b) + " holds " +
+                                                std::to_string(len) + " items, beyond the " +
+                                                std::to_string(MMSBM_HIP_RECOMMEND_MAX_N) + " a list holds at most");
+      row.assign(list_items + list_offsets[b], list_items + list_offsets[b + 1]);
+      std::sort(row.begin(), row.end());
+      const auto twice = std::adjacent_find(row.begin(), row.end());
+      if (twice != row.end())
+        throw std::invalid_argument(std::string(who) + ": item " + std::to_string(*twice) + " is twice in the list of row " +
+                                    std::to_string(b));
+    }
+    recommend_list_propensity(ctx, n_users, users, cand_items, n_cand, n_users > 0 ? excl_offsets : nullptr, excl_items,
+                              temperature, n_users > 0 ? list_offsets : nullptr, list_items, scores, propensity);
+  });
+}
+
+int mmsbm_hip_explore_noise(mmsbm_hip_ctx *ctx, const uint64_t pcg64_state[4], int64_t n_pairs, const int32_t *users,
+                            const int32_t *items, double *r, double *g) {
+  return guarded([&] {
+    if (!ctx) throw std::invalid_argument("null context");
+    if (n_pairs < 0) throw std::invalid_argument("negative n_pairs");
+    if (!pcg64_state || (n_pairs > 0 && (!users || !items || !r || !g))) throw std::invalid_argument("null argument");
+    for (int64_t p = 0; p < n_pairs; ++p)
+      if (users[p] < 0 || items[p] < 0)
+        throw std::invalid_argument("explore_noise: negative id at pair " + std::to_string(p));
+    explore_noise(ctx, pcg64_state, n_pairs, users, items, r, g);
+  });
+}
+
+namespace {
 // The capped categories of the two *_quota entries: a CSR of n_cats categories over the catalogue's `top` items, each
 // strictly ascending, no item in two of them, no negative cap.  capped = false (the two *_shelves entries): the same
 // categories without caps, cat_caps is not read.

@@ -17,6 +17,9 @@
 //                  on the score tile, the same exclusions and selection; the lists and the keys stay on the device
 //   shelves.hpp    category-level recommendation: the batch buffer reduced per (row, category) to a value buffer, the same
 //                  selection over it, then the chosen categories' items
+//   explore.hpp    randomised top-N with propensities: the batch buffer moved to a second one and perturbed with Gumbel
+//                  noise from a counter-based PCG64 stream, the same selection over the keys, then each position's
+//                  probability from the unperturbed scores; the propensities of given lists
 #include "prelude.hpp"
 #include "recommend.hpp"
 #include "similar.hpp"
@@ -31,6 +34,7 @@
 #include "quota.hpp"
 #include "allocate.hpp"
 #include "shelves.hpp"
+#include "explore.hpp"
 
 namespace mmsbm_hip_impl {
 
@@ -121,6 +125,8 @@ void recommend_begin(mmsbm_hip_ctx *c, const double *weights, int exclude_train)
   rc->w.alloc(c->n_ratings);
   HIP_CHECK(hipMemcpyAsync(rc->w.ptr, weights, sizeof(double) * c->n_ratings, hipMemcpyHostToDevice, s));
   rc->excl = exclude_train != 0;
+  rc->w_min = *std::min_element(weights, weights + c->n_ratings);  // (the temperature floor of explore.hpp)
+  rc->w_max = *std::max_element(weights, weights + c->n_ratings);
   if (rc->excl) rc->seen_off_h = upload_train_lists(c, rc->seen_off, rc->seen, nullptr);  // (also the candidate counts of recommend_positions)
   HIP_CHECK(hipStreamSynchronize(s));
   rc->rank = std::min(c->ext_k, c->ext_l);
@@ -275,6 +281,16 @@ struct TopNDev {
   const int32_t *on;
 };
 
+// The stages a query may add to its batches and does not: after the exclusions (rec_within_device), after the selection
+// (top_n_device)
+struct NoFillStage {
+  template <class Prep>
+  void operator()(const Prep &, const int32_t *, int, double *) const {}
+};
+struct NoBatchStage {
+  void operator()(const TopNDev &, int, int64_t) const {}
+};
+
 // The selection of one batch: the n best of every row of sc [nb][I] to os / oi [row * n + k], k < on[row]; the columns
 // split into `parts` parts of `per` (item_parts) whose lists cs / ci / cn [nb * parts ...] are then merged
 void select_batch(hipStream_t st, const double *sc, int I, int nb, int parts, int per, int n, double *cs, int32_t *ci,
@@ -297,10 +313,12 @@ void select_batch(hipStream_t st, const double *sc, int I, int nb, int parts, in
 // waves).  `what` names the query in MMSBM_E_TOOLARGE.  Every row's result stays on the device: `then(dev, ev)` is
 // called once the last batch is enqueued, with the result and the event pair around the query's kernels (recorded; not
 // waited for) -- it copies the result out (top_n_copy_out) or enqueues a stage that reads it there (diverse.hpp);
-// `extra` bytes of device memory are what it will allocate.  n_users > 0.
-template <class Fill, class Then>
+// `extra` bytes of device memory are what it will allocate.  n_users > 0.  `each(batch, nb, b0)` (default: nothing) is
+// called once a batch's selection is enqueued, with that batch's part of the result: a stage that needs what `fill` left
+// of the batch before the next batch overwrites it (explore.hpp).
+template <class Fill, class Then, class Each = NoBatchStage>
 void top_n_device(mmsbm_hip_ctx *c, int I, int64_t n_users, const int32_t *users, int n, const char *what, size_t extra,
-                  Fill &&fill, Then &&then) {
+                  Fill &&fill, Then &&then, Each &&each = Each{}) {
   hipStream_t st = c->stream;
   const int64_t bu = rec_batch_users(I, n_users);
   // items split across waves until about 32 selecting waves per CU are in flight (the selection waits on its loads)
@@ -328,6 +346,7 @@ void top_n_device(mmsbm_hip_ctx *c, int I, int64_t n_users, const int32_t *users
     int32_t *obi = oi.ptr + b0 * n, *obn = on.ptr + b0;
     fill(ub, nb, b0, sc.ptr);
     select_batch(st, sc.ptr, I, nb, parts, per, n, cs.ptr, ci.ptr, cn.ptr, obs, obi, obn);
+    each(TopNDev{obs, obi, obn}, nb, b0);
     HIP_CHECK(hipGetLastError());
   }
   ev.stop(st);
@@ -495,11 +514,13 @@ void within_fill(mmsbm_hip_ctx *c, const WithinPrep &w, Tiles &&tiles, SeenLists
 // id): the items left out after it.  The result stays on the device (top_n_device): `then(dev, ev, dcand, prep_ms)` gets
 // it -- as COLUMNS of the candidate list when there is one --, the candidate list on the device (or null) and the device
 // time of the compact table and the columns.  n_users > 0 and at least one column.  quota: the capped categories
-// (uploaded; in the buffer's columns), applied after the exclusions; null: none.
-template <class Tiles, class Then>
+// (uploaded; in the buffer's columns), applied after the exclusions; null: none.  `after(w, ub, nb, sc)` (default:
+// nothing) enqueues a stage of the query's own over the batch buffer behind them, before the selection; `each`:
+// top_n_device's (explore.hpp uses both).
+template <class Tiles, class Then, class After = NoFillStage, class Each = NoBatchStage>
 void rec_within_device(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, SeenLists seen, const int32_t *cand,
                        int n_cand, const int64_t *xoff, const int32_t *xit, int n, size_t extra, Tiles &&tiles,
-                       Then &&then, const QuotaMask *quota = nullptr) {
+                       Then &&then, const QuotaMask *quota = nullptr, After &&after = After{}, Each &&each = Each{}) {
   WithinPrep w;
   within_prepare(c, n_users, cand, n_cand, xoff, xit, w);
   top_n_device(c, w.C, n_users, users, n,
@@ -507,8 +528,9 @@ void rec_within_device(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, 
                [&](const int32_t *ub, int nb, int64_t b0, double *sc) {
                  within_fill(c, w, tiles, seen, ub, nb, b0, sc);
                  if (quota) quota->apply(c->stream, nb, sc, static_cast<size_t>(w.C));
+                 after(w, ub, nb, sc);
                },
-               [&](const TopNDev &dev, EventPair &ev) { then(dev, ev, w.dcand(), w.ct.ms); });
+               [&](const TopNDev &dev, EventPair &ev) { then(dev, ev, w.dcand(), w.ct.ms); }, each);
 }
 
 // rec_within_device's `tiles` of recommend_query: the scores of the rows of x (`slots` tables xs doubles apart)
@@ -834,6 +856,172 @@ void recommend_query_theta_shelves(mmsbm_hip_ctx *c, int64_t n_users, const doub
                    rec_shelves_run(c, x, xs, n_users, ids, seen, cand, n_cand, nullptr, nullptr, std::move(plan), ask,
                                    out);
                  });
+}
+
+// ---- randomised top-N with propensities (explore.hpp) ---------------------------------------------------------------------
+namespace {
+
+// The PCG64 stream of a call: its four words and the jump table on the device (the host copy is held: the upload is
+// asynchronous)
+struct ExploreStream {
+  uint64_t st[4];
+  std::vector<uint64_t> tab_h;
+  DevBuf<uint64_t> tab;
+  ExploreStream(const uint64_t state[4], hipStream_t stream) : tab_h(64 * 4) {
+    std::copy(state, state + 4, st);
+    explore_jump_table(st, tab_h.data());
+    tab.upload(tab_h, stream);
+  }
+};
+
+}  // namespace
+
+// recommend_query_within's batches with two stages of its own around the unchanged selection: behind the exclusions the
+// row maxima and the perturbation (the scores move to `raw`, the keys take their place), behind the selection the
+// propensities from `raw` -- per batch, before the next one overwrites it (top_n_device's `each`).
+void recommend_query_explore(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, const int32_t *cand, int n_cand,
+                             const int64_t *xoff, const int32_t *xit, int n, double temperature,
+                             const uint64_t state[4], int32_t *items, double *scores, double *propensity,
+                             int32_t *counts) {
+  use_device(c);
+  const RecSession &rc = *c->rc;
+  top_n_blank(n_users, n, items, scores, counts);
+  const size_t outs = static_cast<size_t>(n_users) * n;
+  for (size_t e = 0; propensity && e < outs; ++e) propensity[e] = 0.0;
+  c->last_ms[T_RECOMMEND] = 0.f;
+  const int C = cand ? n_cand : rc.items;
+  if (C == 0 || n_users == 0) return;  // (no column to score: every row is empty)
+  hipStream_t st = c->stream;
+  const int64_t bu = rec_batch_users(C, n_users);  // (the batches top_n_device will form)
+  const size_t ld = static_cast<size_t>(C);
+  require_free_mem(static_cast<size_t>(bu) * ld * sizeof(double) + static_cast<size_t>(bu) * 24 + outs * 16 + 2048,
+                   "recommend_explore: the unperturbed scores of a batch of users");
+  ExploreStream rng(state, st);
+  DevBuf<double> raw, mx, ps, pp;
+  DevBuf<uint64_t> base;
+  raw.alloc(static_cast<size_t>(bu) * ld);
+  mx.alloc(static_cast<size_t>(bu));
+  base.alloc(static_cast<size_t>(bu) * 2);
+  ps.alloc(outs);
+  pp.alloc(outs);
+  const unsigned spans = static_cast<unsigned>((C + kExpSpan - 1) / kExpSpan);
+  rec_within_device(
+      c, n_users, users, rc.seen_lists(), cand, n_cand, xoff, xit, n, 0, rec_tiles(c, rc.x.ptr, rc.x_stride()),
+      [&](const TopNDev &dev, EventPair &ev, const int32_t *, float prep_ms) {
+        std::vector<double> hs(outs), hp(outs);
+        std::vector<int32_t> hi(outs), hn(static_cast<size_t>(n_users));
+        HIP_CHECK(hipMemcpyAsync(hs.data(), ps.ptr, sizeof(double) * outs, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipMemcpyAsync(hp.data(), pp.ptr, sizeof(double) * outs, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipMemcpyAsync(hi.data(), dev.oi, sizeof(int32_t) * outs, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipMemcpyAsync(hn.data(), dev.on, sizeof(int32_t) * n_users, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        c->last_ms[T_RECOMMEND] = ev.ms() + prep_ms;
+        for (int64_t b = 0; b < n_users; ++b) {
+          const size_t o = static_cast<size_t>(b) * n;
+          const int cnt = hn[static_cast<size_t>(b)];
+          if (counts) counts[b] = cnt;
+          for (int k = 0; k < cnt; ++k) {
+            items[o + k] = cand ? cand[hi[o + k]] : hi[o + k];  // columns -> item ids
+            if (scores) scores[o + k] = hs[o + k];
+            if (propensity) propensity[o + k] = hp[o + k];
+          }
+        }
+      },
+      nullptr,
+      [&](const WithinPrep &w, const int32_t *ub, int nb, double *sc) {
+        LAUNCH(explore_norm_kernel, nb, kBlock, 0, st, static_cast<const double *>(sc), ld, C, ub,
+               static_cast<const uint64_t *>(rng.tab.ptr), rng.st[0], rng.st[1], mx.ptr, base.ptr);
+        LAUNCH(explore_perturb_kernel, dim3(spans, static_cast<unsigned>(nb)), kBlock, 0, st, sc, raw.ptr, ld, C, w.dcand(),
+               static_cast<const uint64_t *>(rng.tab.ptr), static_cast<const uint64_t *>(base.ptr), rng.st[2], rng.st[3],
+               temperature);
+      },
+      [&](const TopNDev &batch, int nb, int64_t b0) {
+        LAUNCH(explore_finish_kernel, nb, kRecWave, 0, st, raw.ptr, ld, C, static_cast<const double *>(mx.ptr), temperature,
+               static_cast<const int32_t *>(batch.oi), batch.on, n, ps.ptr + b0 * n, pp.ptr + b0 * n);
+      });
+}
+
+// The propensities of caller-given lists: recommend_query_within's score tiles and exclusions per batch (within_fill),
+// the row maxima, then explore_list_kernel over the batch buffer itself -- no noise, no selection.
+void recommend_list_propensity(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, const int32_t *cand, int n_cand,
+                               const int64_t *xoff, const int32_t *xit, double temperature, const int64_t *list_offsets,
+                               const int32_t *list_items, double *scores, double *propensity) {
+  use_device(c);
+  const RecSession &rc = *c->rc;
+  const size_t total = static_cast<size_t>(DevCsr::entries(list_offsets, n_users));  // (checked: below 2^31)
+  for (size_t e = 0; e < total; ++e) {
+    if (scores) scores[e] = -INFINITY;
+    propensity[e] = 0.0;
+  }
+  c->last_ms[T_RECOMMEND] = 0.f;
+  const int C = cand ? n_cand : rc.items;
+  if (C == 0 || total == 0) return;  // (no candidate anywhere, or nothing asked)
+  hipStream_t st = c->stream;
+  WithinPrep w;
+  within_prepare(c, n_users, cand, n_cand, xoff, xit, w);
+  const int64_t bu = rec_batch_users(C, n_users);
+  const size_t ld = static_cast<size_t>(C);
+  require_free_mem(static_cast<size_t>(bu) * ld * sizeof(double) + static_cast<size_t>(bu) * 8 +
+                       (2 * static_cast<size_t>(n_users) + 1) * 4 + total * 20,
+                   "recommend_list_propensity: a batch of users and the lists");
+  DevBuf<int32_t> du;
+  DevBuf<double> sc, mx, os, op;
+  DevCsr lists;
+  du.alloc(static_cast<size_t>(n_users));
+  sc.alloc(static_cast<size_t>(bu) * ld);
+  mx.alloc(static_cast<size_t>(bu));
+  os.alloc(total);
+  op.alloc(total);
+  lists.upload(list_offsets, list_items, n_users, st);
+  HIP_CHECK(hipMemcpyAsync(du.ptr, users, sizeof(int32_t) * n_users, hipMemcpyHostToDevice, st));
+  const auto tiles = rec_tiles(c, rc.x.ptr, rc.x_stride());
+  const int32_t *col_of = w.has_cand ? w.ct.col.ptr : nullptr;
+  EventPair ev;  // device time of the call's kernels (option "recommend_ms")
+  ev.start(st);
+  for (int64_t b0 = 0; b0 < n_users; b0 += bu) {  // (batches follow each other on the stream)
+    const int nb = static_cast<int>(std::min(bu, n_users - b0));
+    within_fill(c, w, tiles, rc.seen_lists(), du.ptr + b0, nb, b0, sc.ptr);
+    LAUNCH(explore_norm_kernel, nb, kBlock, 0, st, static_cast<const double *>(sc.ptr), ld, C,
+           static_cast<const int32_t *>(du.ptr + b0), static_cast<const uint64_t *>(nullptr), uint64_t(0), uint64_t(0),
+           mx.ptr, static_cast<uint64_t *>(nullptr));
+    LAUNCH(explore_list_kernel, nb, kRecWave, 0, st, sc.ptr, ld, C, static_cast<const double *>(mx.ptr), temperature,
+           static_cast<const int32_t *>(lists.off.ptr + b0), static_cast<const int32_t *>(lists.val.ptr), col_of, os.ptr,
+           op.ptr);
+    HIP_CHECK(hipGetLastError());
+  }
+  ev.stop(st);
+  if (scores) HIP_CHECK(hipMemcpyAsync(scores, os.ptr, sizeof(double) * total, hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipMemcpyAsync(propensity, op.ptr, sizeof(double) * total, hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipStreamSynchronize(st));
+  c->last_ms[T_RECOMMEND] = ev.ms() + w.ct.ms;
+}
+
+void explore_noise(mmsbm_hip_ctx *c, const uint64_t state[4], int64_t n_pairs, const int32_t *users, const int32_t *items,
+                   double *r, double *g) {
+  use_device(c);
+  if (n_pairs == 0) return;
+  hipStream_t st = c->stream;
+  const int64_t per = std::min<int64_t>(n_pairs, int64_t(1) << 24);  // pairs per launch (24 bytes each)
+  require_free_mem(static_cast<size_t>(per) * 24 + 2048, "explore_noise: a batch of pairs");
+  ExploreStream rng(state, st);
+  DevBuf<int32_t> du, di;
+  DevBuf<double> dr, dg;
+  du.alloc(static_cast<size_t>(per));
+  di.alloc(static_cast<size_t>(per));
+  dr.alloc(static_cast<size_t>(per));
+  dg.alloc(static_cast<size_t>(per));
+  for (int64_t p0 = 0; p0 < n_pairs; p0 += per) {
+    const int64_t np = std::min(per, n_pairs - p0);
+    HIP_CHECK(hipMemcpyAsync(du.ptr, users + p0, sizeof(int32_t) * np, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(di.ptr, items + p0, sizeof(int32_t) * np, hipMemcpyHostToDevice, st));
+    LAUNCH(explore_noise_kernel, static_cast<unsigned>((np + kBlock - 1) / kBlock), kBlock, 0, st,
+           static_cast<const uint64_t *>(rng.tab.ptr), rng.st[0], rng.st[1], rng.st[2], rng.st[3],
+           static_cast<const int32_t *>(du.ptr), static_cast<const int32_t *>(di.ptr), np, dr.ptr, dg.ptr);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpyAsync(r + p0, dr.ptr, sizeof(double) * np, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(g + p0, dg.ptr, sizeof(double) * np, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+  }
 }
 
 void recommend_rank(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, const int64_t *offsets,

@@ -33,6 +33,31 @@ def check_finite(value, name, lo=None, must_be="a finite number", bool_too=False
     return float(value)
 
 
+EXPLORE_FLOOR = 700.0   # (max w - min w) / temperature beyond this is refused (explore.hpp: no exp underflows below it)
+
+
+def explore_temperature(temperature, weights):
+    """float(temperature) of ``recommend_explore`` / ``propensities``: finite, >= 0 and, unless 0, not below the floor
+    (max w - min w) / 700 of the rating ``weights`` -- the ValueError names the floor."""
+    t = check_finite(temperature, "temperature", 0, "a finite number >= 0")
+    spread = float(np.max(weights) - np.min(weights))
+    if t > 0.0 and spread / t > EXPLORE_FLOOR:
+        raise ValueError(f"temperature must be 0 or at least the floor {spread / EXPLORE_FLOOR!r} of these weights "
+                         f"((max weight - min weight) / {EXPLORE_FLOOR:g}: below it the policy is recommend()'s list), "
+                         f"got {t!r}")
+    return t
+
+
+def explore_stream(seed):
+    """The four PCG64 state words (``core.pcg64_words``) of ``np.random.default_rng(seed)``: the stream that
+    ``recommend_explore`` keys its noise on.  A generator is read where it stands, not advanced."""
+    from .core import pcg64_words
+    bg = np.random.default_rng(seed).bit_generator
+    if not isinstance(bg, np.random.PCG64):
+        raise ValueError(f"seed must give a PCG64 stream, got a generator on {type(bg).__name__}")
+    return pcg64_words(bg)
+
+
 # ---------------------------------------------------------------------- grouped lists
 def _offsets(counts):
     return np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
@@ -453,6 +478,102 @@ class Serving:
             return self._top_n_frame(
                 lambda b, e: ctx.recommend_query_quota(ids[b:e], n, quota.offsets, quota.items, quota.caps, cand,
                                                        group_slice(extra, b, e)), n, labels, items, derived=derived)
+
+    def recommend_explore(self, users=None, n=10, temperature=..., seed=0, exclude_seen=True, weights=None,
+                          candidates=None, exclude=None):
+        """``recommend`` drawn at random, with the probability of what was drawn: every other query returns the same
+        list on every call, so the items just below the cut are never shown and nothing logged under it can evaluate
+        another policy.  Each user's list is sampled WITHOUT replacement from the Plackett-Luce distribution over the
+        user's candidates (``recommend``'s: ``exclude_seen``, ``candidates``, ``exclude``) with utilities
+        score / ``temperature``: the first item with probability proportional to exp(score / temperature), the next
+        one among the rest in the same way, and so on.  On the device: Gumbel noise keyed by (seed, user, item) alone
+        is added to the scores and the n largest are taken, so a user's list does not depend on the other users of the
+        call, the request order, ``n`` of a longer call's head, or the catalogue's size.
+
+        ``temperature`` is required: it is in score units, so no default fits every weighting.  0 gives
+        ``recommend``'s frame with propensity 1.0; it may not lie below (max weight - min weight) / 700 otherwise
+        (ValueError naming that floor: below it the policy IS ``recommend`` to within 1e-300).  ``seed``: anything
+        ``np.random.default_rng`` accepts (a PCG64 stream; a generator is read, not advanced).
+
+        Returns ``recommend``'s frame plus ``propensity`` -- the probability the policy had of putting that item at
+        that rank given the ranks above it; the product over a user's rows is the probability of the list: columns
+        ``users``, ``items``, ``score``, ``propensity``, ``rank``.  ``score`` is ``recommend``'s, bit for bit.
+        ``propensities`` re-derives the column for any logged frame.  The model's stored predictions and ``score()``
+        are left as they are."""
+        if temperature is ...:
+            raise TypeError("recommend_explore() needs temperature=: score units (0: plain recommend)")
+        self._check_whole_model()
+        n, w = self._recommend_args(n, weights)
+        t = explore_temperature(temperature, w)
+        columns = ("users", "items", "score", "propensity")
+        if t == 0.0:
+            frame = self.recommend(users, n, exclude_seen, weights, candidates, exclude)
+            frame.insert(3, "propensity", np.ones(len(frame)))
+            return frame
+        words = explore_stream(seed)
+        ids, labels = self._side("users").request(users)
+        items = self._side("items")
+        cand = self._candidate_ids(candidates)
+        if cand is not None and len(cand) == 0:
+            return self._top_n_frame(None, n, labels[:0], items, columns)
+        extra = self._exclusion_lists(exclude, ids)
+        with self._session_of_restarts("recommend", w, exclude_seen) as ctx:
+            return self._top_n_frame(
+                lambda b, e: ctx.recommend_query_explore(ids[b:e], n, t, words, cand, group_slice(extra, b, e)),
+                n, labels, items, columns)
+
+    def propensities(self, recs, temperature=..., exclude_seen=True, weights=None, candidates=None, exclude=None):
+        """What ``recommend_explore``'s policy at ``temperature`` WOULD have given lists that somebody else logged --
+        another temperature, an older model, a deterministic list: the number inverse-propensity scoring divides by.
+        ``recs``: any recommend-style frame, users and items in its first two columns (both must be in the training
+        data: KeyError); a user's list is its rows in ``rank`` order when the frame has a ``rank`` column, in order of
+        appearance otherwise (at most 1,024 items, none twice).  ``exclude_seen``, ``weights``, ``candidates`` and
+        ``exclude`` describe the policy's candidates as in ``recommend_explore``.
+
+        Returns ``users``, ``items``, ``rank`` (the place in the list as given, from 1), ``score``, ``propensity``,
+        users in order of first appearance.  An item the policy could not have shown that user (seen, excluded, no
+        candidate) has propensity 0 and score -inf, and the rest of the list is computed as if it were absent.  No
+        noise is involved: applied to ``recommend_explore``'s own frame with the same arguments it returns that
+        frame's ``propensity``, bit for bit."""
+        if temperature is ...:
+            raise TypeError("propensities() needs temperature=: the policy's, in score units")
+        self._check_whole_model()
+        w = self._rating_weights(weights)
+        t = explore_temperature(temperature, w)
+        if t == 0.0:
+            raise ValueError("temperature must be > 0: at 0 the policy is recommend()'s list, with propensity 1 on it "
+                             "and 0 elsewhere")
+        if not (hasattr(recs, "iloc") and hasattr(recs, "columns")) or recs.shape[1] < 2:
+            raise ValueError("recs must be a frame whose first two columns are users and items")
+        users_side, items_side = self._side("users"), self._side("items")
+        uid, _ = users_side.request(recs.iloc[:, 0].tolist())
+        iid, _ = items_side.request(recs.iloc[:, 1].tolist())
+        users, first = np.unique(uid, return_index=True)
+        users = users[np.argsort(first, kind="stable")].astype(np.int32)          # order of first appearance
+        place = np.empty(len(users_side), dtype=np.int64)
+        place[users] = np.arange(len(users))
+        row = place[uid]
+        order = (np.lexsort((np.asarray(recs["rank"]), row)) if "rank" in recs.columns
+                 else np.argsort(row, kind="stable"))
+        row, listed = row[order], iid[order].astype(np.int32)
+        offsets = _offsets(np.bincount(row, minlength=len(users)))
+        if len(users) and int(np.diff(offsets).max()) > self.RECOMMEND_MAX:
+            raise ValueError(f"a user's list holds {int(np.diff(offsets).max())} items: at most {self.RECOMMEND_MAX}")
+        pair = np.sort(row * len(items_side) + listed)
+        if (pair[1:] == pair[:-1]).any():
+            raise ValueError("recs names an item twice for one user")
+        rank = np.arange(len(row), dtype=np.int64) - offsets[row] + 1
+        score, prop = np.full(len(row), -np.inf), np.zeros(len(row))
+        cand = self._candidate_ids(candidates)
+        if len(users) and (cand is None or len(cand)):
+            extra = self._exclusion_lists(exclude, users)
+            with self._session_of_restarts("recommend", w, exclude_seen) as ctx:
+                for b, e in self._row_batches(len(users), self.RECOMMEND_MAX):
+                    at = slice(offsets[b], offsets[e])
+                    score[at], prop[at] = ctx.recommend_list_propensity(
+                        users[b:e], group_slice((offsets, listed), b, e), t, cand, group_slice(extra, b, e))
+        return pd.DataFrame({"users": users_side.label(users)[row], "items": items_side.label(listed), "rank": rank,
+                             "score": score, "propensity": prop})
 
     def _shelves_frame(self, query, shelves, per_shelf, row_labels, cats):
         """The frame of a shelves query of rows [0, len(row_labels)): ``query(b, e)`` -> HipEM.recommend_query_shelves'
