@@ -253,6 +253,30 @@ int mmsbm_hip_recommend_add_items(mmsbm_hip_ctx *ctx, int32_t n_new, const doubl
 int mmsbm_hip_recommend_top_pairs(mmsbm_hip_ctx *ctx, int64_t n_users, const int32_t *users, int32_t m,
                                   int32_t *out_users, int32_t *out_items, double *out_scores, int32_t *count);
 
+/* The same question for m beyond MMSBM_HIP_TOP_PAIRS_MAX_M (mmsbm_amd/csrc/pairs_bulk.hpp): candidates, scores and order
+ * are recommend_top_pairs', for 1 <= m <= MMSBM_HIP_TOP_PAIRS_BULK_MAX_M.  The bar -- the score of the last returned
+ * pair -- is found exactly by a radix select over the score tiles, the pairs above it and the ties the order admits are
+ * written by count-then-write, and the entries are sorted on the device; nothing of size n_users x items exists, device
+ * memory is O(m + n_users).  out_users / out_items / out_scores: m entries each, the first *count = min(m, candidates)
+ * hold the answer, the rest -1 / -1 / -inf.  *bar: the score of the last returned pair (+0.0 for a zero of either sign;
+ * -inf without candidates); counts[0]: candidates that score strictly above the bar, counts[1]: exactly the bar (fp64
+ * equality), counts[2]: candidates -- so recommend_audience at min_score = *bar over every item returns counts[0] +
+ * counts[1] pairs of these users.  Options "pairs_bulk_groups" (workgroups, 0 .. 4096), "pairs_bulk_bits" (bits per
+ * digit of the select, 0 .. 12) -- 0: the library's choice -- and "pairs_bulk_collect" (the select stops and sorts a
+ * bin of at most this many keys; 0: never; at most 2^24) change the time only; "pairs_bulk_ms" reads the device time
+ * of the last call, "pairs_bulk_passes" / "pairs_bulk_collected" the passes it ran and the keys it sorted.  Refusals as
+ * recommend_top_pairs: MMSBM_E_INVALID for no session, no slot added, an id out of range, a repeated id, m < 1, a null
+ * pointer; m > MMSBM_HIP_TOP_PAIRS_BULK_MAX_M: MMSBM_E_UNSUPPORTED; MMSBM_E_TOOLARGE where the device memory for
+ * min(m, candidates) entries is not free.  Touches no slot, no EM state and no other session; the recommend session
+ * stays open and answers as before.
+ * recommend_pair_bar: the same request, *bar and counts alone -- the select and one counting pass, no output buffers. */
+#define MMSBM_HIP_TOP_PAIRS_BULK_MAX_M 67108864
+int mmsbm_hip_recommend_top_pairs_bulk(mmsbm_hip_ctx *ctx, int64_t n_users, const int32_t *users, int64_t m,
+                                       int32_t *out_users, int32_t *out_items, double *out_scores, int64_t *count,
+                                       double *bar, int64_t counts[3]);
+int mmsbm_hip_recommend_pair_bar(mmsbm_hip_ctx *ctx, int64_t n_users, const int32_t *users, int64_t m, double *bar,
+                                 int64_t counts[3]);
+
 /* Item-side queries of the open recommend session (mmsbm_amd/csrc/audience.hpp): who should see an item.  items[0 ..
  * n_items): ids in the session's catalogue (training items, and I .. I + n_new - 1 after recommend_add_items), any
  * order, repeats allowed.  score_w(u, i) is bit for bit what query returns for the pair, in swapped and unswapped

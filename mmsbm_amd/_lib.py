@@ -60,6 +60,9 @@ SIGNATURES = {
     "mmsbm_hip_recommend_positions": (C.c_int, [C.c_void_p, C.c_int64, c_i32p, c_i64p, c_i32p, c_i32p, c_i32p]),
     "mmsbm_hip_recommend_add_items": (C.c_int, [C.c_void_p, C.c_int32, c_f64p, c_i64p, c_i32p]),
     "mmsbm_hip_recommend_top_pairs": (C.c_int, [C.c_void_p, C.c_int64, c_i32p, C.c_int32, c_i32p, c_i32p, c_f64p, c_i32p]),
+    "mmsbm_hip_recommend_top_pairs_bulk": (C.c_int, [C.c_void_p, C.c_int64, c_i32p, C.c_int64, c_i32p, c_i32p, c_f64p,
+                                                     c_i64p, c_f64p, c_i64p]),
+    "mmsbm_hip_recommend_pair_bar": (C.c_int, [C.c_void_p, C.c_int64, c_i32p, C.c_int64, c_f64p, c_i64p]),
     "mmsbm_hip_recommend_query_items": (C.c_int, [C.c_void_p, C.c_int64, c_i32p, C.c_int32, c_i32p, c_f64p, c_i32p]),
     "mmsbm_hip_recommend_allocate": (C.c_int, [C.c_void_p, C.c_int64, c_i32p, C.c_int32, c_i32p, C.c_int32, c_i32p,
                                                c_f64p, c_i32p, c_i32p, c_i32p]),

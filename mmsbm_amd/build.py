@@ -1,6 +1,6 @@
 """Compile the HIP library in-tree for gfx950 (hipcc cross-compiles without a GPU).
 
-The library is sixteen translation units (csrc/prelude.hpp lists them) compiled SIDE BY SIDE -- one hipcc per unit, as
+The library is seventeen translation units (csrc/prelude.hpp lists them) compiled SIDE BY SIDE -- one hipcc per unit, as
 many at a time as the machine has cores -- and linked into one shared object: about 18 s on eight cores, where the
 single unit of earlier rounds took a minute.  csrc/unity.hip is all of them as one unit, for the diagnostic builds
 (`build_diagnostic`)."""
@@ -13,9 +13,9 @@ from concurrent.futures import ThreadPoolExecutor
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG_DIR, "csrc")
-# the translation units, longest compile first (tu_layout.hip carries rocPRIM's sorts; the host-only units -- the C ABI,
+# the translation units, longest compile first (tu_layout.hip and tu_pairs_bulk.hip carry rocPRIM's sorts; the host-only units -- the C ABI,
 # tu_create, tu_params, tu_iterate, tu_options -- take a few seconds each and fill the gaps at the end)
-UNITS = ("tu_layout", "tu_fused", "tu_once", "tu_seg", "tu_pair", "tu_etap", "tu_mfma", "tu_recommend", "mmsbm_hip", "tu_create",
+UNITS = ("tu_layout", "tu_pairs_bulk", "tu_fused", "tu_once", "tu_seg", "tu_pair", "tu_etap", "tu_mfma", "tu_recommend", "mmsbm_hip", "tu_create",
          "tu_fold_in", "tu_heldout", "tu_explain", "tu_params", "tu_iterate", "tu_options")
 OBJ_DIR = os.path.join(PKG_DIR, "_build")
 DEPS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".hpp"))) + [

@@ -628,6 +628,34 @@ class HipEM:
                   _p(sc, C.c_double), C.byref(count))
         return ou, oi, sc, int(count.value)
 
+    MAX_TOP_PAIRS_BULK = 1 << 26
+
+    def recommend_top_pairs_bulk(self, m, users=None):
+        """(users (m,) int32, items (m,) int32, scores (m,), count, info): recommend_top_pairs' answer for m up to
+        MAX_TOP_PAIRS_BULK, found by a radix select of the bar over the score tiles.  info: {"bar": the score of the
+        last returned pair, "above" / "ties": candidates that score strictly above / exactly the bar, "candidates"}."""
+        u = None if users is None else _i32(users)
+        m = int(m)
+        ou, oi = np.empty(max(m, 0), dtype=np.int32), np.empty(max(m, 0), dtype=np.int32)
+        sc = np.empty(max(m, 0), dtype=np.float64)
+        count, bar, counts = C.c_int64(0), C.c_double(0.0), np.zeros(3, dtype=np.int64)
+        _lib.call("mmsbm_hip_recommend_top_pairs_bulk", self._h, 0 if u is None else len(u),
+                  _p_or_null(u, C.c_int32), m, _p(ou, C.c_int32), _p(oi, C.c_int32), _p(sc, C.c_double),
+                  C.byref(count), C.byref(bar), _p(counts, C.c_int64))
+        return ou, oi, sc, int(count.value), self._bar_info(bar, counts)
+
+    def recommend_pair_bar(self, m, users=None):
+        """recommend_top_pairs_bulk's info alone: the select and one counting pass, no entries."""
+        u = None if users is None else _i32(users)
+        bar, counts = C.c_double(0.0), np.zeros(3, dtype=np.int64)
+        _lib.call("mmsbm_hip_recommend_pair_bar", self._h, 0 if u is None else len(u), _p_or_null(u, C.c_int32),
+                  int(m), C.byref(bar), _p(counts, C.c_int64))
+        return self._bar_info(bar, counts)
+
+    @staticmethod
+    def _bar_info(bar, counts):
+        return {"bar": float(bar.value), "above": int(counts[0]), "ties": int(counts[1]), "candidates": int(counts[2])}
+
     def recommend_query_items(self, items, n):
         """(users (M,n) int32 padded with -1, scores (M,n) padded with -inf, counts (M,)) for item ids of the open
         session's catalogue: the n best candidate users of each -- score descending, equal scores by ascending user

@@ -273,7 +273,7 @@ inline void sort_unique_groups(std::vector<int32_t> &off, std::vector<int32_t> &
 // similar_pairs, inform_query / inform_query_theta, recommend_query_groups, recommend_query_ensemble / recommend_pair_spread,
 // loo_add / loo_rows / loo_sides / loo_lowest (and, of the last loo_add alone, its sums pass and its row pass),
 // recommend_allocate
-enum TimedCall { T_RECOMMEND = 0, T_FOLD_IN, T_POSITIONS, T_TOP_PAIRS, T_AUDIENCE, T_SIMILAR, T_OVERLAP, T_HELDOUT, T_EXPLAIN, T_DIVERSE, T_INFORM, T_GROUP, T_ENSEMBLE, T_LOO, T_LOO_SUMS, T_LOO_ROWS, T_ALLOCATE, T_COUNT };
+enum TimedCall { T_RECOMMEND = 0, T_FOLD_IN, T_POSITIONS, T_TOP_PAIRS, T_AUDIENCE, T_SIMILAR, T_OVERLAP, T_HELDOUT, T_EXPLAIN, T_DIVERSE, T_INFORM, T_GROUP, T_ENSEMBLE, T_LOO, T_LOO_SUMS, T_LOO_ROWS, T_ALLOCATE, T_TOP_PAIRS_BULK, T_COUNT };
 
 enum KernelId { K_SEG = 0, K_DENSE, K_ETAP, K_MATVEC_A, K_FUSED_PAIRS, K_FUSED_TAIL, K_COUNT };
 // The four launches of an iteration -- or, for small problems, the two of fused_small.hpp.  With pass_dense.hpp the
@@ -362,6 +362,10 @@ struct mmsbm_hip_ctx {
   std::unique_ptr<mmsbm_hip_impl::LooSession> loo;     // leave-one-out
   float last_ms[T_COUNT] = {};              // device time of the last call's kernels, per TimedCall (options "<name>_ms")
   int top_groups = 0;                       // option "top_pairs_groups": workgroups of gtop_fused_kernel (0: 2 per CU)
+  int pb_groups = 0, pb_bits = 0;           // options "pairs_bulk_groups" / "pairs_bulk_bits" (pairs_bulk.hpp; 0: the library's choice)
+  int64_t pb_collect = kPbDefaultCollect;   // option "pairs_bulk_collect": the bin size at which the select stops and sorts
+  int pb_passes = 0;                        // of the last bulk query: histogram passes run, keys collected (0: no early stop)
+  int64_t pb_collected = 0;
   int64_t aud_rows = 0;                     // option "audience_rows": items per COUNT batch (0: the library's choice)
   int64_t aud_entries = 0;                  // option "audience_entries": entries per WRITE batch at most (0: likewise)
   int64_t exp_rows = 0;                     // option "explain_rows": training rows per batch of explain_query (0: likewise)

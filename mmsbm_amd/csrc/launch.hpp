@@ -59,6 +59,14 @@ void recommend_add_items(mmsbm_hip_ctx *c, int32_t n_new, const double *eta, con
 // ... the m best pairs of the whole model (top_pairs.hpp): users ascending and distinct
 void recommend_top_pairs(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, int m, int32_t *out_users,
                          int32_t *out_items, double *out_scores, int32_t *count);
+// ... the same question for m up to MMSBM_HIP_TOP_PAIRS_BULK_MAX_M (pairs_bulk.hpp): users ascending and distinct;
+// out_* null: the bar and the counts alone; counts: above the bar, at the bar, candidates
+void recommend_top_pairs_bulk(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, int64_t m, int32_t *out_users,
+                              int32_t *out_items, double *out_scores, int64_t *count, double *bar, int64_t counts[3]);
+// tu_pairs_bulk.hip -- its device sorts: n keys descending; n (user << 32 | item, score) entries into the query's order
+void pairs_bulk_sort_desc(mmsbm_hip_ctx *c, const uint64_t *keys, uint64_t *sorted, size_t n);
+void pairs_bulk_order(mmsbm_hip_ctx *c, const uint64_t *key, const double *score, size_t n, uint64_t *out_key,
+                      double *out_score);
 // ... item-side queries of the session (audience.hpp): item ids inside the session's catalogue
 void recommend_query_items(mmsbm_hip_ctx *c, int64_t n_items, const int32_t *items, int n, int32_t *users,
                            double *scores, int32_t *counts);

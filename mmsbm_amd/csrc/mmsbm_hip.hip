@@ -588,6 +588,54 @@ int mmsbm_hip_recommend_top_pairs(mmsbm_hip_ctx *ctx, int64_t n_users, const int
   });
 }
 
+namespace {
+
+// The request of top_pairs_bulk / pair_bar checked, and in id order in `ids` (every training user when `users` is null)
+void pairs_bulk_request(mmsbm_hip_ctx *ctx, const char *entry, int64_t n_users, const int32_t *users, int64_t m,
+                        std::vector<int32_t> &ids) {
+  require_open(ctx, &mmsbm_hip_ctx::rc, "recommend", entry);
+  if (n_users < 0) throw std::invalid_argument("negative n_users");
+  if (m < 1) throw std::invalid_argument("top_pairs_bulk: m must be at least 1");
+  if (m > MMSBM_HIP_TOP_PAIRS_BULK_MAX_M)
+    throw ApiError(MMSBM_E_UNSUPPORTED, "top_pairs_bulk: m = " + std::to_string(m) + " is beyond the " +
+                                            std::to_string(MMSBM_HIP_TOP_PAIRS_BULK_MAX_M) + " pairs a query returns at most");
+  if (users) {
+    require_ids(users, n_users, ctx->ext_users, "top_pairs_bulk: user");
+    ids.assign(users, users + n_users);
+    std::sort(ids.begin(), ids.end());
+    const auto twice = std::adjacent_find(ids.begin(), ids.end());
+    if (twice != ids.end()) throw std::invalid_argument("top_pairs_bulk: user id " + std::to_string(*twice) + " is repeated");
+  } else {
+    ids.resize(static_cast<size_t>(ctx->ext_users));
+    for (int32_t u = 0; u < ctx->ext_users; ++u) ids[static_cast<size_t>(u)] = u;
+  }
+}
+
+}  // namespace
+
+int mmsbm_hip_recommend_top_pairs_bulk(mmsbm_hip_ctx *ctx, int64_t n_users, const int32_t *users, int64_t m,
+                                       int32_t *out_users, int32_t *out_items, double *out_scores, int64_t *count,
+                                       double *bar, int64_t counts[3]) {
+  return guarded([&] {
+    std::vector<int32_t> ids;
+    pairs_bulk_request(ctx, "recommend_top_pairs_bulk", n_users, users, m, ids);
+    if (!out_users || !out_items || !out_scores || !count || !bar || !counts) throw std::invalid_argument("null argument");
+    recommend_top_pairs_bulk(ctx, static_cast<int64_t>(ids.size()), ids.data(), m, out_users, out_items, out_scores, count,
+                             bar, counts);
+  });
+}
+
+int mmsbm_hip_recommend_pair_bar(mmsbm_hip_ctx *ctx, int64_t n_users, const int32_t *users, int64_t m, double *bar,
+                                 int64_t counts[3]) {
+  return guarded([&] {
+    std::vector<int32_t> ids;
+    pairs_bulk_request(ctx, "recommend_pair_bar", n_users, users, m, ids);
+    if (!bar || !counts) throw std::invalid_argument("null argument");
+    recommend_top_pairs_bulk(ctx, static_cast<int64_t>(ids.size()), ids.data(), m, nullptr, nullptr, nullptr, nullptr, bar,
+                             counts);
+  });
+}
+
 int mmsbm_hip_recommend_query_items(mmsbm_hip_ctx *ctx, int64_t n_items, const int32_t *items, int32_t n,
                                     int32_t *users, double *scores, int32_t *counts) {
   return guarded([&] {

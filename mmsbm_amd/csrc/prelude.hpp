@@ -22,6 +22,8 @@
 //                       audience.hpp   item-side queries           catalogue.hpp  queries within a part of the catalogue
 //                       diverse.hpp    the diversified top-N       inform.hpp     the most informative items of a user
 //                       group.hpp      group queries               ensemble.hpp   how far the restarts agree on a pair
+//                       pairs_bulk.hpp the m best pairs beyond 1,024, planned by pairs_bulk_plan.hpp
+//   tu_pairs_bulk.hip the device sorts of pairs_bulk.hpp (rocPRIM)
 //   tu_fold_in.hip    fold new users into a fitted model (fold_in.hpp)
 //   tu_heldout.hip    held-out log-likelihood of every restart slot (heldout.hpp)
 //   tu_explain.hip    which of a user's training rows carry a recommendation (explain.hpp)
@@ -52,6 +54,7 @@
 #include "shapes.hpp"
 #include "pair_plan.hpp"
 #include "serve_plan.hpp"
+#include "pairs_bulk_plan.hpp"
 #include "stamps.hpp"
 #include "rowtab.hpp"
 #include "context.hpp"

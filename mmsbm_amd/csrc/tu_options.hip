@@ -62,12 +62,34 @@ const Option kOptions[] = {
     {"loo_rows_ms", [](const Ctx *c) -> double { return c->last_ms[T_LOO_ROWS]; }, nullptr},
     // ... of the last recommend_allocate as a whole (allocate.hpp), and the rounds it took
     {"allocate_ms", [](const Ctx *c) -> double { return c->last_ms[T_ALLOCATE]; }, nullptr},
+    // ... of the last top_pairs_bulk / pair_bar as a whole (pairs_bulk.hpp), the histogram passes it ran and the keys it
+    // collected when it stopped early (0: it did not)
+    {"pairs_bulk_ms", [](const Ctx *c) -> double { return c->last_ms[T_TOP_PAIRS_BULK]; }, nullptr},
+    {"pairs_bulk_passes", [](const Ctx *c) -> double { return c->pb_passes; }, nullptr},
+    {"pairs_bulk_collected", [](const Ctx *c) -> double { return static_cast<double>(c->pb_collected); }, nullptr},
     {"allocate_rounds", [](const Ctx *c) -> double { return c->alloc_rounds; }, nullptr},
     // workgroups of gtop_fused_kernel (top_pairs.hpp); 0: the library's choice
     {"top_pairs_groups", [](const Ctx *c) -> double { return c->top_groups; },
      [](Ctx *c, double v) {
        if (v < 0 || v > 4096 || v != std::floor(v)) throw std::invalid_argument("top_pairs_groups: 0 .. 4096");
        c->top_groups = static_cast<int>(v);
+     }},
+    // top_pairs_bulk (pairs_bulk.hpp): workgroups of its tile launches and bits per digit of the select (0: the library's
+    // choice); the bin size at which the select stops and sorts the bin (0: never).  None changes the answer
+    {"pairs_bulk_groups", [](const Ctx *c) -> double { return c->pb_groups; },
+     [](Ctx *c, double v) {
+       if (v < 0 || v > kPbMaxGroups || v != std::floor(v)) throw std::invalid_argument("pairs_bulk_groups: 0 .. 4096");
+       c->pb_groups = static_cast<int>(v);
+     }},
+    {"pairs_bulk_bits", [](const Ctx *c) -> double { return c->pb_bits; },
+     [](Ctx *c, double v) {
+       if (v < 0 || v > kPbDevMaxBits || v != std::floor(v)) throw std::invalid_argument("pairs_bulk_bits: 0 .. 12");
+       c->pb_bits = static_cast<int>(v);
+     }},
+    {"pairs_bulk_collect", [](const Ctx *c) -> double { return static_cast<double>(c->pb_collect); },
+     [](Ctx *c, double v) {
+       if (v < 0 || v > static_cast<double>(kPbMaxCollect) || v != std::floor(v)) throw std::invalid_argument("pairs_bulk_collect: 0 .. 2^24");
+       c->pb_collect = static_cast<int64_t>(v);
      }},
     // recommend_audience (audience.hpp): items per COUNT batch, entries per WRITE batch at most; 0: the library's choice.
     // Neither changes the answer

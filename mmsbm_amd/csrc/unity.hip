@@ -18,6 +18,7 @@
 #include "tu_once.hip"
 #include "tu_layout.hip"
 #include "tu_recommend.hip"
+#include "tu_pairs_bulk.hip"
 #include "tu_fold_in.hip"
 #include "tu_heldout.hip"
 #include "tu_explain.hip"

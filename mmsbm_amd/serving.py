@@ -846,6 +846,58 @@ class Serving:
             "score": scores[:count],
             "rank": np.arange(1, count + 1, dtype=np.int64)})
 
+    TOP_PAIRS_BULK_MAX = 1 << 26     # largest m of top_pairs_bulk (MMSBM_HIP_TOP_PAIRS_BULK_MAX_M)
+
+    def _pairs_bulk_args(self, m, users, weights):
+        """(m, rating weights, encoded ids or None) of ``top_pairs_bulk`` / ``score_bar``, refused as ``top_pairs``
+        refuses them."""
+        self._check_whole_model()
+        m = check_integer(m, "m", 1)
+        if m > self.TOP_PAIRS_BULK_MAX:
+            raise ValueError(f"m = {m} is beyond the {self.TOP_PAIRS_BULK_MAX} pairs a query returns at most")
+        w = self._rating_weights(weights)
+        ids = None
+        if users is not None:
+            ids, labels = self._side("users").request(users)
+            if len(np.unique(ids)) != len(ids):
+                twice = list(dict.fromkeys(labels[np.isin(ids, ids[np.bincount(ids)[ids] > 1])].tolist()))
+                raise ValueError(f"users named more than once: {twice}")
+        return m, w, ids
+
+    def top_pairs_bulk(self, m, users=None, exclude_seen=True, weights=None):
+        """``top_pairs`` for ``m`` far beyond 1,024 -- up to 2^26 -- : the links a reconstruction adds to a network,
+        the sends of a campaign with a global budget.  Candidates, scores and order are ``top_pairs``'; the score of
+        the ``m``-th pair is found exactly on the device by a radix select over the score tiles, the pairs above it
+        and the ties the order admits are then written and sorted there.  No users x items matrix exists.
+
+        Returns ``top_pairs``' DataFrame: columns ``users``, ``items``, ``score``, ``rank`` (1 = best of all), at most
+        ``m`` rows.  ``self.pairs_bulk_`` then holds ``{"bar", "above", "ties", "candidates"}``: the score of the
+        last returned pair, how many candidate pairs score strictly above it and exactly it, and the number of
+        candidates (see ``score_bar``).  The model's stored predictions and ``score()`` are left as they are."""
+        m, w, ids = self._pairs_bulk_args(m, users, weights)
+        with self._session_of_restarts("recommend", w, exclude_seen) as ctx:
+            us, its, scores, count, info = ctx.recommend_top_pairs_bulk(m, ids)
+        self.pairs_bulk_ = info
+        step = self.RECOMMEND_BATCH_ROWS
+        parts = [pd.DataFrame({
+            "users": self._side("users").label(us[b:min(count, b + step)]),
+            "items": self._side("items").label(its[b:min(count, b + step)]),
+            "score": scores[b:min(count, b + step)],
+            "rank": np.arange(b + 1, min(count, b + step) + 1, dtype=np.int64)}) for b in range(0, max(count, 1), step)]
+        return pd.concat(parts, ignore_index=True) if len(parts) > 1 else parts[0]
+
+    def score_bar(self, m, users=None, exclude_seen=True, weights=None):
+        """The score of the ``m``-th best (user, item) pair without the pairs themselves: what a budget of ``m`` sends
+        sets as the bar.  The request is ``top_pairs_bulk``'s.
+
+        Returns ``{"bar", "above", "ties", "candidates"}``: the bar, the candidate pairs that score strictly above it,
+        those that score exactly it, and all candidates.  ``audience(min_score=bar)`` over the same users returns
+        ``above + ties`` pairs -- ``m`` or, when pairs tie at the bar, more; ``top_pairs_bulk`` cuts the ties by
+        ascending user, then item."""
+        m, w, ids = self._pairs_bulk_args(m, users, weights)
+        with self._session_of_restarts("recommend", w, exclude_seen) as ctx:
+            return ctx.recommend_pair_bar(m, ids)
+
     def explain(self, pairs, n=5, weights=None):
         """Why an item is recommended to a user: the ``n`` training rows of the user that carry most of the pair's
         score -- the "because you rated ..." of a recommendation -- found on the device.
