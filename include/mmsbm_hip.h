@@ -572,6 +572,45 @@ int mmsbm_hip_recommend_query_groups(mmsbm_hip_ctx *ctx, int64_t n_groups, const
                                      const int32_t *cand_items, int32_t n, int32_t *items, double *scores,
                                      int32_t *counts);
 
+/* Greedy assortment selection of the open recommend session (mmsbm_amd/csrc/assortment.hpp): which c items serve a set
+ * of users best TOGETHER.  users: n_users ids of training users, strictly ascending.  With a(u, i) the undivided sum of
+ * recommend_query's fma chain (score = a / S, bit for bit) and a pair ELIGIBLE unless i is in u's excluded list of the
+ * session (the training pairs while exclude_train is set, the seen lists of recommend_add_items), a round's gain of item
+ * i is the sum over the users of
+ *   MMSBM_HIP_ASSORT_BEST   max(0, a(u, i) - best[u]) on eligible pairs; best[u] starts at level x S (`level`: the
+ *                           floor, finite) and rises to a(u, i*) with every item i* taken
+ *   MMSBM_HIP_ASSORT_REACH  1.0 where the pair is eligible, u is not covered yet and score(u, i) >= level (`level`: the
+ *                           bar, finite, compared with the final score); a taken item covers the users it reaches
+ * The given items (n_given ids of the session's catalogue, in the order given) are applied to the state first and are
+ * never chosen; then at most c rounds take the candidate (cand_items as in recommend_query_within; NULL: the whole
+ * catalogue, n_cand ignored) of largest gain, equal gains by the smaller item id, and stop early when that gain is not
+ * > 0 or no candidate is left.  items / gains [c]: the *count items taken in order and each round's gain -- divided by S
+ * once in BEST mode, a whole number of users in REACH mode -- followed by -1 / 0.0.  *stop: MMSBM_HIP_ASSORT_STOP_C
+ * (count == c), _NO_GAIN or _NO_CANDIDATES.  given_gains [n_given]: each given item's gain over the state before it.
+ * served_items / served_scores [n_users]: per user the item that serves them (BEST: the earliest item of their best
+ * score; REACH: the item that covered them first) and its score, or -1 / -inf; read from the state on the device.
+ * The rounds are enqueued without a host wait between them: a stop flag on the device makes the launches behind it
+ * return at once.  REACH depends on nothing but the arguments; BEST sums doubles in an order fixed by the launch plan
+ * (the CU count and option "assortment_run_blocks": blocks of 8 user rows per workgroup and item tile, 0 = the library's
+ * choice): the same bits from call to call, possibly other last bits under another plan.  Option
+ * "assortment_part_bytes" (0 = 64 MB) bounds the runs' partial sums per batch of item tiles -- time, never the answer.
+ * Touches no slot, no EM state
+ * and no other session.  mmsbm_hip_get_option(ctx, "assortment_ms") reads the device time of the call's kernels; with
+ * option "assortment_timing" set, "assortment_gain_ms" / "assortment_pick_ms" / "assortment_update_ms" hold its split.
+ * MMSBM_E_INVALID (before any launch): no recommend session or no slot added to it, an id out of range, users or
+ * cand_items not strictly ascending, an unknown mode, a level that is not finite, c < 0.  c > MMSBM_HIP_ASSORT_MAX_C:
+ * MMSBM_E_UNSUPPORTED; MMSBM_E_TOOLARGE where the device memory is not free. */
+#define MMSBM_HIP_ASSORT_BEST 0
+#define MMSBM_HIP_ASSORT_REACH 1
+#define MMSBM_HIP_ASSORT_MAX_C 1024
+#define MMSBM_HIP_ASSORT_STOP_C 0
+#define MMSBM_HIP_ASSORT_STOP_NO_GAIN 1
+#define MMSBM_HIP_ASSORT_STOP_NO_CANDIDATES 2
+int mmsbm_hip_recommend_assortment(mmsbm_hip_ctx *ctx, int64_t n_users, const int32_t *users, int mode, double level,
+                                   int32_t n_given, const int32_t *given_items, int32_t n_cand,
+                                   const int32_t *cand_items, int32_t c, int32_t *items, double *gains, int32_t *count,
+                                   int32_t *stop, double *given_gains, int32_t *served_items, double *served_scores);
+
 /* Ensemble-aware queries of the open recommend session (mmsbm_amd/csrc/ensemble.hpp): how far the added slots -- the
  * restarts -- AGREE about a pair.  With x_s / y_s the folded factors the session holds for slot s (add order),
  *   a_s(u, i) = ONE fma chain over j = 0 .. rank - 1 ascending from +0.0 of x_s[u, j] y_s[i, j]

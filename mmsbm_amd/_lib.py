@@ -103,6 +103,9 @@ SIGNATURES = {
                                               C.c_int32, C.c_int32, C.c_double, c_i32p, c_f64p, c_f64p, c_i32p]),
     "mmsbm_hip_recommend_query_groups": (C.c_int, [C.c_void_p, C.c_int64, c_i64p, c_i32p, C.c_int, C.c_double,
                                                    C.c_int32, c_i32p, C.c_int32, c_i32p, c_f64p, c_i32p]),
+    "mmsbm_hip_recommend_assortment": (C.c_int, [C.c_void_p, C.c_int64, c_i32p, C.c_int, C.c_double, C.c_int32, c_i32p,
+                                                 C.c_int32, c_i32p, C.c_int32, c_i32p, c_f64p, c_i32p, c_i32p, c_f64p,
+                                                 c_i32p, c_f64p]),
     "mmsbm_hip_recommend_query_ensemble": (C.c_int, [C.c_void_p, C.c_int64, c_i32p, C.c_int, C.c_double, C.c_int32,
                                                      c_i32p, c_i64p, c_i32p, C.c_int32, c_i32p, c_f64p, c_i32p]),
     "mmsbm_hip_recommend_pair_spread": (C.c_int, [C.c_void_p, C.c_int64, c_i32p, c_i32p, c_f64p, c_f64p]),

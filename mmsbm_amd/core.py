@@ -773,6 +773,43 @@ class HipEM:
                   _p_or_null(cand, C.c_int32), n, _p(items, C.c_int32), _p(scores, C.c_double), _p(counts, C.c_int32))
         return items, scores, counts
 
+    # -- greedy assortment selection in the recommend session (include/mmsbm_hip.h: mmsbm_hip_recommend_assortment) -----
+    ASSORT_MODES = {"best_score": 0, "reach": 1}                # MMSBM_HIP_ASSORT_*
+    ASSORT_STOPS = ("c", "no_gain", "no_candidates")            # MMSBM_HIP_ASSORT_STOP_*
+    MAX_ASSORT = 1024                                           # MMSBM_HIP_ASSORT_MAX_C
+
+    def recommend_assortment(self, users, c, mode, level, given=None, candidates=None):
+        """(items (count,) int32, gains (count,), count, stop reason, served items (M,) int32, served scores (M,), start):
+        at most ``c`` greedy rounds over the encoded ``users`` (any order; a user named twice counts once, M of them are
+        distinct) -- each takes the candidate of largest gain, equal gains by the smaller id.  ``mode`` (a key of
+        ASSORT_MODES or its number): "best_score" the gain of an item is the sum over the users of how far its score
+        lies above the best score the user has so far (``level``: the floor that stands for "nothing"), "reach" the number
+        of users not reached yet whose score is >= ``level`` (the bar).  ``given`` (encoded items, in order): applied to
+        the state first and never chosen; ``start``: the gain they had together.  ``candidates`` as in
+        recommend_query_within.  gains: per round, the sum divided by S.  The served arrays stand in the order of the
+        users' first appearance: the item that serves each user (-1: none) and its score (-inf), read from the state on
+        the device.  Stop reason: one of ASSORT_STOPS."""
+        u, c = _i32(users), int(c)
+        uniq, first = np.unique(u, return_index=True)
+        uniq = np.ascontiguousarray(uniq, dtype=np.int32)
+        place = np.searchsorted(uniq, u[np.sort(first)])       # the sorted row of every distinct user, first appearance first
+        g = _i32([] if given is None else given)
+        cand = None if candidates is None else _i32(candidates)
+        items = np.full(max(c, 0), -1, dtype=np.int32)
+        gains = np.zeros(max(c, 0), dtype=np.float64)
+        given_gains = np.zeros(len(g), dtype=np.float64)
+        count, stop = np.zeros(1, dtype=np.int32), np.zeros(1, dtype=np.int32)
+        s_items = np.full(len(uniq), -1, dtype=np.int32)
+        s_scores = np.full(len(uniq), -np.inf, dtype=np.float64)
+        _lib.call("mmsbm_hip_recommend_assortment", self._h, len(uniq), _p(uniq, C.c_int32),
+                  int(self.ASSORT_MODES.get(mode, mode)), float(level), len(g), _p(g, C.c_int32),
+                  0 if cand is None else len(cand), _p_or_null(cand, C.c_int32), c, _p(items, C.c_int32),
+                  _p(gains, C.c_double), _p(count, C.c_int32), _p(stop, C.c_int32), _p(given_gains, C.c_double),
+                  _p(s_items, C.c_int32), _p(s_scores, C.c_double))
+        n = int(count[0])
+        start = float(np.cumsum(given_gains)[-1]) if len(g) else 0.0      # (added in the order given)
+        return items[:n], gains[:n], n, self.ASSORT_STOPS[int(stop[0])], s_items[place], s_scores[place], start
+
     # -- ensemble-aware queries of the recommend session (include/mmsbm_hip.h: mmsbm_hip_recommend_query_ensemble) -----
     ENSEMBLE_MODES = {"min": 0, "max": 1, "lcb": 2}   # MMSBM_HIP_ENSEMBLE_*
 

@@ -148,6 +148,12 @@ void recommend_diverse(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, 
 void recommend_query_groups(mmsbm_hip_ctx *c, int64_t n_groups, const int64_t *offsets, const int32_t *members, int mode,
                             double bar, const int32_t *cand, int n_cand, int n, int32_t *items, double *scores,
                             int32_t *counts);
+// ... and greedy assortment selection in the recommend session (assortment.hpp), arguments checked: users ascending and
+// distinct; mode: MMSBM_HIP_ASSORT_*; level: the floor or the bar; cand as in recommend_query_within
+void recommend_assortment(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, int mode, double level,
+                          const int32_t *given, int n_given, const int32_t *cand, int n_cand, int n_pick, int32_t *items,
+                          double *gains, int32_t *count, int32_t *stop, double *given_gains, int32_t *served_items,
+                          double *served_scores);
 // ... and the ensemble-aware queries of the recommend session (ensemble.hpp), arguments checked: mode:
 // MMSBM_HIP_ENSEMBLE_*; cand / excl_* as in recommend_query_within; stats [n_pairs][4], per_slot [S][n_pairs] or null
 void recommend_query_ensemble(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, int mode, double risk,

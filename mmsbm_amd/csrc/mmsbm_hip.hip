@@ -1085,6 +1085,37 @@ int mmsbm_hip_recommend_query_groups(mmsbm_hip_ctx *ctx, int64_t n_groups, const
   });
 }
 
+int mmsbm_hip_recommend_assortment(mmsbm_hip_ctx *ctx, int64_t n_users, const int32_t *users, int mode, double level,
+                                   int32_t n_given, const int32_t *given_items, int32_t n_cand,
+                                   const int32_t *cand_items, int32_t c, int32_t *items, double *gains, int32_t *count,
+                                   int32_t *stop, double *given_gains, int32_t *served_items, double *served_scores) {
+  return guarded([&] {
+    const RecSession &rc = require_open(ctx, &mmsbm_hip_ctx::rc, "recommend", "recommend_assortment");
+    if (n_users < 0) throw std::invalid_argument("negative n_users");
+    if (n_given < 0) throw std::invalid_argument("recommend_assortment: negative n_given");
+    if (mode != MMSBM_HIP_ASSORT_BEST && mode != MMSBM_HIP_ASSORT_REACH)
+      throw std::invalid_argument("recommend_assortment: unknown mode " + std::to_string(mode));
+    if (!std::isfinite(level))
+      throw std::invalid_argument(mode == MMSBM_HIP_ASSORT_BEST ? "recommend_assortment: floor must be finite"
+                                                                : "recommend_assortment: bar must be finite");
+    if (c < 0) throw std::invalid_argument("recommend_assortment: c must be at least 0");
+    if (c > MMSBM_HIP_ASSORT_MAX_C)
+      throw ApiError(MMSBM_E_UNSUPPORTED, "recommend_assortment: c = " + std::to_string(c) + " is beyond the " +
+                                              std::to_string(MMSBM_HIP_ASSORT_MAX_C) + " items a query takes at most");
+    if (!count || !stop || (n_users > 0 && (!users || !served_items || !served_scores)) ||
+        (c > 0 && (!items || !gains)) || (n_given > 0 && (!given_items || !given_gains)))
+      throw std::invalid_argument("null argument");
+    require_ids(users, n_users, ctx->ext_users, "recommend_assortment: user");
+    for (int64_t m = 1; m < n_users; ++m)
+      if (users[m] <= users[m - 1])
+        throw std::invalid_argument("recommend_assortment: users must be strictly ascending (row " + std::to_string(m) + ")");
+    require_ids(given_items, n_given, rc.items, "recommend_assortment: given item");
+    require_subset(cand_items, n_cand, rc.items, "recommend_assortment");
+    recommend_assortment(ctx, n_users, users, mode, level, given_items, n_given, cand_items, n_cand, c, items, gains, count,
+                         stop, given_gains, served_items, served_scores);
+  });
+}
+
 int mmsbm_hip_recommend_query_ensemble(mmsbm_hip_ctx *ctx, int64_t n_users, const int32_t *users, int mode, double risk,
                                        int32_t n_cand, const int32_t *cand_items, const int64_t *excl_offsets,
                                        const int32_t *excl_items, int32_t n, int32_t *items, double *scores,

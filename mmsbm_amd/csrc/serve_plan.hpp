@@ -351,6 +351,57 @@ inline GroupPlan plan_groups(const int64_t *offsets, const int32_t *members, int
   return p;
 }
 
+// ---- greedy assortment selection (assortment.hpp) --------------------------------------------------------------------------
+// What recommend_assortment launches with.  The request's users stand as ONE list of rows, ascending by id; the gain
+// kernel walks it in runs of `run_rows` rows -- whole 128-row steps, about 8 workgroups per CU over the item tiles
+// (option "assortment_run_blocks": 8-row blocks per run, rounded up to whole steps of 16) -- and never more runs than a
+// grid's second dimension holds.  A run's carry goes to a row of the partial buffer [runs][cols]; where runs x columns
+// is beyond kAsrtPartBytes the item tiles are walked in batches of `batch_tiles`, each joined before the next overwrites
+// the buffer.  The join leaves one entry per 256 columns (n_blk in all), the pick reads them.
+constexpr int kAsrtNoGain = 1, kAsrtNoCand = 2;           // the stop flag (0: running); MMSBM_HIP_ASSORT_STOP_*
+constexpr size_t kAsrtPartBytes = size_t(64) << 20;       // the partial buffer of one batch of item tiles
+constexpr int64_t kAsrtMaxRuns = 65535;                   // gridDim.y
+constexpr int kAsrtJoin = 256;                            // columns per workgroup of asrt_join_kernel (kBlock)
+
+struct AssortPlan {
+  int64_t n_rows = 0, n_blocks = 0, item_tiles = 0;  // users; their 8-row blocks; 128-column tiles of the C columns
+  int64_t run_blocks = 0, run_rows = 0, runs = 0;    // per run: blocks (a multiple of kGrpStep), rows; the runs
+  int64_t batch_tiles = 0, batches = 0;              // item tiles per launch of the gain kernel; launches per round
+  int64_t ld = 0;                                    // columns of the partial buffer: batch_tiles x 128
+  std::vector<int32_t> batch_blk;                    // per batch: its first entry of the join's output (batches + 1)
+  int64_t n_blk() const { return batch_blk.empty() ? 0 : batch_blk.back(); }
+  size_t part_doubles() const { return static_cast<size_t>(runs) * static_cast<size_t>(ld); }
+  // columns of batch b of a table of C columns: [col0, col0 + n)
+  std::pair<int64_t, int64_t> batch_cols(int64_t b, int64_t C) const {
+    const int64_t col0 = b * batch_tiles * kRecTile;
+    return {col0, std::min<int64_t>(C, col0 + batch_tiles * kRecTile) - col0};
+  }
+};
+
+// part_bytes: kAsrtPartBytes (the CPU check: batches without 64 MB shapes).  n_rows == 0 or C == 0: nothing to launch.
+inline AssortPlan plan_assortment(int64_t n_rows, int64_t C, int n_cus, int64_t run_blocks_option,
+                                  size_t part_bytes = kAsrtPartBytes) {
+  AssortPlan p;
+  p.n_rows = n_rows;
+  if (n_rows <= 0 || C <= 0) return p;
+  p.n_blocks = (n_rows + kGrpBlock - 1) / kGrpBlock;
+  p.item_tiles = (C + kRecTile - 1) / kRecTile;
+  const int64_t most = std::max<int64_t>(1, 8LL * n_cus / p.item_tiles);
+  int64_t ask = run_blocks_option > 0 ? run_blocks_option : (p.n_blocks + most - 1) / most;
+  ask = std::max(ask, (p.n_blocks + kAsrtMaxRuns - 1) / kAsrtMaxRuns);
+  p.run_blocks = std::max<int64_t>(kGrpStep, (std::min(ask, p.n_blocks) + kGrpStep - 1) / kGrpStep * kGrpStep);
+  p.run_rows = p.run_blocks * kGrpBlock;
+  p.runs = (p.n_blocks + p.run_blocks - 1) / p.run_blocks;
+  const int64_t fit = static_cast<int64_t>(part_bytes / sizeof(double)) / p.runs / kRecTile;
+  p.batch_tiles = std::min(p.item_tiles, std::max<int64_t>(1, fit));
+  p.batches = (p.item_tiles + p.batch_tiles - 1) / p.batch_tiles;
+  p.ld = p.batch_tiles * kRecTile;
+  p.batch_blk.push_back(0);
+  for (int64_t b = 0; b < p.batches; ++b)
+    p.batch_blk.push_back(p.batch_blk.back() + static_cast<int32_t>((p.batch_cols(b, C).second + kAsrtJoin - 1) / kAsrtJoin));
+  return p;
+}
+
 // ---- the spread of given pairs (ensemble.hpp) ----------------------------------------------------------------------------
 // pairs per launch of recommend_pair_spread: the batch's ids, four numbers a pair and, when wanted, the S slots' values
 // stay within kEnsPairBytes (at least one pair)

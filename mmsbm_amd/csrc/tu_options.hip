@@ -13,7 +13,7 @@ struct Option {
   void (*set)(mmsbm_hip_ctx *, double);
 };
 using Ctx = mmsbm_hip_ctx;
-// "audience_rows" / "audience_entries" / "explain_rows" / "diverse_rows" / "group_run_blocks": 0 .. 2^31 - 1, whole
+// "audience_rows" / "audience_entries" / "explain_rows" / "diverse_rows" / "group_run_blocks" / "assortment_run_blocks" / "assortment_part_bytes": 0 .. 2^31 - 1, whole
 void set_audience(int64_t &field, const char *name, double v) {
   if (v < 0 || v > 2147483647.0 || v != std::floor(v)) throw std::invalid_argument(std::string(name) + ": 0 .. 2^31 - 1");
   field = static_cast<int64_t>(v);
@@ -68,6 +68,13 @@ const Option kOptions[] = {
     {"pairs_bulk_passes", [](const Ctx *c) -> double { return c->pb_passes; }, nullptr},
     {"pairs_bulk_collected", [](const Ctx *c) -> double { return static_cast<double>(c->pb_collected); }, nullptr},
     {"allocate_rounds", [](const Ctx *c) -> double { return c->alloc_rounds; }, nullptr},
+    // ... of the last recommend_assortment as a whole (assortment.hpp) and, of its rounds while "assortment_timing" is
+    // set (events between the phases of every round), of the gain + join, the pick and the update kernels
+    {"assortment_ms", [](const Ctx *c) -> double { return c->last_ms[T_ASSORT]; }, nullptr},
+    {"assortment_gain_ms", [](const Ctx *c) -> double { return c->asrt_ms[0]; }, nullptr},
+    {"assortment_pick_ms", [](const Ctx *c) -> double { return c->asrt_ms[1]; }, nullptr},
+    {"assortment_update_ms", [](const Ctx *c) -> double { return c->asrt_ms[2]; }, nullptr},
+    {"assortment_timing", [](const Ctx *c) -> double { return c->asrt_timing; }, [](Ctx *c, double v) { c->asrt_timing = v != 0.0; }},
     // workgroups of gtop_fused_kernel (top_pairs.hpp); 0: the library's choice
     {"top_pairs_groups", [](const Ctx *c) -> double { return c->top_groups; },
      [](Ctx *c, double v) {
@@ -107,6 +114,13 @@ const Option kOptions[] = {
     // longer group is cut into fragments of that length.  0: the library's choice.  It does not change the answer
     {"group_run_blocks", [](const Ctx *c) -> double { return static_cast<double>(c->grp_run); },
      [](Ctx *c, double v) { set_audience(c->grp_run, "group_run_blocks", v); }},
+    // recommend_assortment (assortment.hpp): blocks of 8 user rows per run, rounded up to whole steps of 16.  0: the
+    // library's choice.  REACH does not depend on it; BEST may differ in the last bits of a gain sum
+    {"assortment_run_blocks", [](const Ctx *c) -> double { return static_cast<double>(c->asrt_run); },
+     [](Ctx *c, double v) { set_audience(c->asrt_run, "assortment_run_blocks", v); }},
+    // ... and the bytes of the runs' partial sums per batch of item tiles (0: 64 MB).  It does not change the answer
+    {"assortment_part_bytes", [](const Ctx *c) -> double { return static_cast<double>(c->asrt_part); },
+     [](Ctx *c, double v) { set_audience(c->asrt_part, "assortment_part_bytes", v); }},
     // the form FAMILY of an iteration at the current slot count: 2 = the two launches of fused_small.hpp, 4 = the separate
     // stages, with or without "pass_dense" -- the launches a committed iteration really takes are launches - pass_dense
     {"launches", [](const Ctx *c) -> double { return use_fused(c) ? 2 : 4; }, nullptr},

@@ -22,6 +22,8 @@
 //   explore.hpp    randomised top-N with propensities: the batch buffer moved to a second one and perturbed with Gumbel
 //                  noise from a counter-based PCG64 stream, the same selection over the keys, then each position's
 //                  probability from the unperturbed scores; the propensities of given lists
+//   assortment.hpp greedy assortment selection: rounds of a gain pass over the score tiles against a per-user state, an
+//                  arg-max over the catalogue and a state update, chained on the stream behind a stop flag
 #include "prelude.hpp"
 #include "recommend.hpp"
 #include "similar.hpp"
@@ -38,6 +40,7 @@
 #include "allocate.hpp"
 #include "shelves.hpp"
 #include "explore.hpp"
+#include "assortment.hpp"
 
 namespace mmsbm_hip_impl {
 
@@ -1710,6 +1713,167 @@ void recommend_query_groups(mmsbm_hip_ctx *c, int64_t n_groups, const int64_t *o
       if (scores) scores[o + k] = ts[t + k];
     }
   }
+}
+
+// ---- greedy assortment selection (assortment.hpp) -------------------------------------------------------------------------
+// plan (plan_assortment: the runs of user rows, the batches of item tiles), memory check, uploads; the given items one
+// by one (their gain over the state before them, then the state); then n_pick rounds of gain / join / pick / update
+// enqueued back to back -- no host wait and no copy between them: once the stop flag is set on the device the launches
+// that follow return at once -- and ONE read-back at the end.  users: ascending, distinct.
+void recommend_assortment(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, int mode, double level,
+                          const int32_t *given, int n_given, const int32_t *cand, int n_cand, int n_pick, int32_t *items,
+                          double *gains, int32_t *count, int32_t *stop, double *given_gains, int32_t *served_items,
+                          double *served_scores) {
+  use_device(c);
+  const RecSession &rc = *c->rc;
+  for (float *t : {&c->last_ms[T_ASSORT], &c->asrt_ms[0], &c->asrt_ms[1], &c->asrt_ms[2]}) *t = 0.f;
+  const int NI = rc.items, rank = rc.rank, S = rc.slots;
+  const int C = cand ? n_cand : NI;
+  for (int k = 0; k < n_pick; ++k) {
+    items[k] = -1;
+    gains[k] = 0.0;
+  }
+  for (int g = 0; g < n_given; ++g) given_gains[g] = 0.0;
+  *count = 0;
+  *stop = n_pick == 0 ? MMSBM_HIP_ASSORT_STOP_C : C == 0 ? MMSBM_HIP_ASSORT_STOP_NO_CANDIDATES : MMSBM_HIP_ASSORT_STOP_NO_GAIN;
+  if (n_users == 0) return;  // (nobody to serve: no item gains anything)
+  const int nu = static_cast<int>(n_users);
+  const AssortPlan p = plan_assortment(n_users, C, c->n_cus, c->asrt_run,
+                                       c->asrt_part > 0 ? static_cast<size_t>(c->asrt_part) : kAsrtPartBytes);
+  // a given item: its one tile of the catalogue, in the runs of the rounds -- a column's sum is the same additions in the
+  // same order whether the item is given or chosen, so a set valued as given items gets the greedy's bits
+  const AssortPlan pg = plan_assortment(n_users, kRecTile, c->n_cus, C > 0 ? p.run_blocks : c->asrt_run);
+  const bool rounds = n_pick > 0 && C > 0;
+  const size_t ycs = static_cast<size_t>(C) * rank;
+  const size_t n_res = static_cast<size_t>(n_pick) + static_cast<size_t>(n_given);
+  require_free_mem((cand ? S * ycs * sizeof(double) + (static_cast<size_t>(C) + NI) * 4 : 0) +
+                       static_cast<size_t>(nu) * (4 + 8 + 4 + 8) + static_cast<size_t>(C) * 4 + n_res * 12 +
+                       (rounds ? p.part_doubles() * sizeof(double) + static_cast<size_t>(p.n_blk()) * 12 : 0) +
+                       (n_given > 0 ? pg.part_doubles() * sizeof(double) : 0),
+                   "recommend_assortment: the users' state, the runs' partial sums and the candidates' rows");
+  hipStream_t st = c->stream;
+  // the state: best[u] = level x S undivided (BEST; REACH fills it when a user is covered), nobody served
+  std::vector<double> h_best(static_cast<size_t>(nu), mode == kAsrtBest ? level * static_cast<double>(S) : 0.0);
+  std::vector<int32_t> h_served(static_cast<size_t>(nu), -1), h_users(users, users + nu);
+  std::vector<int32_t> h_taken(static_cast<size_t>(C), 0);
+  for (int g = 0; g < n_given; ++g) {  // a given item is never chosen: its column, where it has one
+    if (cand) {
+      const int32_t *at = std::lower_bound(cand, cand + n_cand, given[g]);
+      if (at != cand + n_cand && *at == given[g]) h_taken[static_cast<size_t>(at - cand)] = 1;
+    } else {
+      h_taken[static_cast<size_t>(given[g])] = 1;
+    }
+  }
+  DevBuf<double> best, score, part, part_g, blk_v, res_gain;
+  DevBuf<int32_t> rows, served, taken, blk_i, res_col, flags;
+  CatTable ct;
+  rows.upload(h_users, st);
+  best.upload(h_best, st);
+  served.upload(h_served, st);
+  taken.upload(h_taken, st);
+  score.alloc(static_cast<size_t>(nu));
+  res_col.alloc(static_cast<size_t>(n_pick));
+  res_gain.alloc(n_res);
+  flags.alloc(2);  // the stop flag, the count
+  HIP_CHECK(hipMemsetAsync(res_gain.ptr, 0, sizeof(double) * std::max<size_t>(n_res, 1), st));
+  HIP_CHECK(hipMemsetAsync(flags.ptr, 0, sizeof(int32_t) * 2, st));
+  if (rounds) {
+    part.alloc(p.part_doubles());
+    blk_v.alloc(static_cast<size_t>(p.n_blk()));
+    blk_i.alloc(static_cast<size_t>(p.n_blk()));
+    if (cand) cat_table(c, cand, C, ct);
+  }
+  if (n_given > 0) part_g.alloc(pg.part_doubles());
+  const double *y = cand && rounds ? ct.y.ptr : rc.y.ptr;
+  const size_t yfs = static_cast<size_t>(NI) * rank, ys = cand && rounds ? ycs : yfs, xs = rc.x_stride();
+  const SeenLists seen = rc.seen_lists();
+  const int32_t *dcand = cand && rounds ? ct.cand.ptr : nullptr;
+  int32_t *d_stop = flags.ptr, *d_count = flags.ptr + 1;
+  double *d_given = res_gain.ptr + n_pick;
+  const unsigned user_grid = static_cast<unsigned>((nu + kBlock - 1) / kBlock);
+  auto gain = [&](const AssortPlan &pl, const double *yy, size_t yys, int ni, int tile0, unsigned tiles, const int32_t *cols,
+                  double *out) {
+    const dim3 g(tiles, static_cast<unsigned>(pl.runs));
+    auto tile = [&](auto kernel) {
+      LAUNCH(kernel, g, kBlock, 0, st, rc.x.ptr, xs, yy, yys, static_cast<const int32_t *>(rows.ptr), nu,
+             static_cast<int>(pl.run_rows), ni, tile0, rank, S, level, static_cast<const double *>(best.ptr),
+             static_cast<const int32_t *>(served.ptr), seen.off, seen.items, cols, static_cast<const int32_t *>(d_stop), out,
+             static_cast<size_t>(pl.ld));
+    };
+    if (mode == kAsrtBest) tile(asrt_gain_kernel<kAsrtBest>);
+    else tile(asrt_gain_kernel<kAsrtReach>);
+  };
+  auto update = [&](int k, int item) {
+    auto go = [&](auto kernel) {
+      LAUNCH(kernel, user_grid, kBlock, 0, st, rc.x.ptr, xs, rc.y.ptr, yfs, static_cast<const int32_t *>(rows.ptr), nu, rank,
+             S, level, k, item, static_cast<const int32_t *>(res_col.ptr), dcand, seen.off, seen.items,
+             static_cast<const int32_t *>(d_stop), best.ptr, served.ptr);
+    };
+    if (mode == kAsrtBest) go(asrt_update_kernel<kAsrtBest>);
+    else go(asrt_update_kernel<kAsrtReach>);
+  };
+  // the phases' device times (option "assortment_timing"): one event at every border between two phases of a round
+  std::vector<std::unique_ptr<EventPair::Event>> marks;
+  auto mark = [&] {
+    if (!c->asrt_timing) return;
+    marks.push_back(std::make_unique<EventPair::Event>());
+    HIP_CHECK(hipEventRecord(marks.back()->e, st));
+  };
+  EventPair ev;  // device time of the query's kernels (option "assortment_ms")
+  ev.start(st);
+  for (int g = 0; g < n_given; ++g) {
+    gain(pg, rc.y.ptr, yfs, NI, given[g] / kRecTile, 1u, nullptr, part_g.ptr);
+    LAUNCH(asrt_given_kernel, 1, kRecWave, 0, st, static_cast<const double *>(part_g.ptr), static_cast<size_t>(pg.ld),
+           static_cast<int>(pg.runs), given[g] % kRecTile, g, d_given);
+    update(-1, given[g]);
+  }
+  HIP_CHECK(hipGetLastError());
+  for (int k = 0; rounds && k < n_pick; ++k) {  // (rounds follow each other on the stream: no host wait in between)
+    mark();
+    for (int64_t b = 0; b < p.batches; ++b) {
+      const auto [col0, n_cols] = p.batch_cols(b, C);
+      gain(p, y, ys, C, static_cast<int>(b * p.batch_tiles), static_cast<unsigned>((n_cols + kRecTile - 1) / kRecTile), dcand,
+           part.ptr);
+      LAUNCH(asrt_join_kernel, static_cast<unsigned>((n_cols + kAsrtJoin - 1) / kAsrtJoin), kBlock, 0, st,
+             static_cast<const double *>(part.ptr), static_cast<size_t>(p.ld), static_cast<int>(p.runs),
+             static_cast<int>(col0), static_cast<int>(n_cols), static_cast<const int32_t *>(taken.ptr),
+             p.batch_blk[static_cast<size_t>(b)], static_cast<const int32_t *>(d_stop), blk_v.ptr, blk_i.ptr);
+    }
+    mark();
+    LAUNCH(asrt_pick_kernel, 1, kBlock, 0, st, static_cast<const double *>(blk_v.ptr), static_cast<const int32_t *>(blk_i.ptr),
+           static_cast<int>(p.n_blk()), k, taken.ptr, res_col.ptr, res_gain.ptr, d_count, d_stop);
+    mark();
+    update(k, 0);
+    HIP_CHECK(hipGetLastError());
+  }
+  mark();
+  LAUNCH(asrt_finish_kernel, static_cast<unsigned>((std::max<size_t>(n_res, static_cast<size_t>(nu)) + kBlock - 1) / kBlock),
+         kBlock, 0, st, res_gain.ptr, static_cast<int>(n_res), mode == kAsrtBest, static_cast<const double *>(best.ptr),
+         static_cast<const int32_t *>(served.ptr), nu, S, score.ptr);
+  HIP_CHECK(hipGetLastError());
+  ev.stop(st);
+  std::vector<int32_t> h_col(static_cast<size_t>(n_pick)), h_flags(2);
+  std::vector<double> h_gain(n_res);
+  if (n_pick > 0) HIP_CHECK(hipMemcpyAsync(h_col.data(), res_col.ptr, sizeof(int32_t) * n_pick, hipMemcpyDeviceToHost, st));
+  if (n_res > 0) HIP_CHECK(hipMemcpyAsync(h_gain.data(), res_gain.ptr, sizeof(double) * n_res, hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipMemcpyAsync(h_flags.data(), flags.ptr, sizeof(int32_t) * 2, hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipMemcpyAsync(served_items, served.ptr, sizeof(int32_t) * nu, hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipMemcpyAsync(served_scores, score.ptr, sizeof(double) * nu, hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipStreamSynchronize(st));
+  c->last_ms[T_ASSORT] = ev.ms() + ct.ms;
+  for (size_t m = 0; m + 1 < marks.size(); ++m) {  // gain + join, pick, update: in turn
+    float v = 0.f;
+    HIP_CHECK(hipEventElapsedTime(&v, marks[m]->e, marks[m + 1]->e));
+    c->asrt_ms[m % 3] += v;
+  }
+  const int cnt = rounds ? h_flags[1] : 0;
+  *count = cnt;
+  if (rounds) *stop = h_flags[0];  // (0: all n_pick rounds ran)
+  for (int k = 0; k < cnt; ++k) {
+    items[k] = cand ? cand[h_col[static_cast<size_t>(k)]] : h_col[static_cast<size_t>(k)];
+    gains[k] = h_gain[static_cast<size_t>(k)];
+  }
+  for (int g = 0; g < n_given; ++g) given_gains[g] = h_gain[static_cast<size_t>(n_pick) + g];
 }
 
 // ---- ensemble-aware queries (ensemble.hpp) ------------------------------------------------------------------------------

@@ -1636,6 +1636,94 @@ class Serving:
                 lambda b, e: ctx.recommend_query_groups(*group_slice(lists, b, e), n, mode, bar or 0.0, cand),
                 n, labels, items, self._GROUP_COLUMNS)
 
+    # ------------------------------------------------------------------ which items to have at all (not in the reference)
+    ASSORTMENT_MAX = 1024            # largest c of assortment (MMSBM_HIP_ASSORT_MAX_C)
+    _ASSORTMENT_OBJECTIVES = ("best_score", "reach")
+
+    def assortment(self, c=10, objective="best_score", bar=None, floor=None, given=None, users=None, candidates=None,
+                   exclude_seen=True, weights=None):
+        """The ``c`` items to HAVE for a set of users -- the titles a shop stocks, the ten items of a newsletter, the
+        slots of a programme -- chosen greedily on the device.  The value of a set is not the sum of its items' values:
+        a second item that pleases the same users as the first adds almost nothing, so the ``c`` items of highest mean
+        score are ``c`` near-copies.  With score(u, i) ``recommend``'s score (the same numbers, bit for bit) and a pair
+        counted only when it is eligible (``exclude_seen``: i is not a training item of u), the value of a set S is, by
+        ``objective``:
+
+        ``"best_score"``  sum over the users of max(``floor``, the best score an item of S gives them) -- ``floor``
+                          (finite; default min(weights), the lowest value a score can take) is what a user is worth who
+                          finds nothing; ``bar`` is refused;
+        ``"reach"``       the number of users for whom S holds an item they score at or above ``bar`` (required, finite,
+                          compared with the final score); ``floor`` is refused.
+
+        Both are monotone submodular, so the greedy rule -- ``c`` times the item of largest marginal gain, equal gains
+        to the smaller encoded item id -- is within 1 - 1/e of the best set of ``c``.  It stops early when no item gains
+        anything (or none is left), and the frame then has fewer rows.
+
+        ``given``: items already in the assortment ("we stock these, which ``c`` to add"): applied first, in the order
+        given, never chosen; they need not be among ``candidates``.  ``users`` (None: every training user; a user named
+        twice counts once), ``candidates`` and ``weights`` as in ``recommend``.  Unknown labels: KeyError.  0 <= ``c`` <=
+        1,024.
+
+        Returns a DataFrame ``items``, ``gain``, ``total``, ``rank``: each round's item, its gain (in score units; in
+        reach mode a whole number of users), the running sum and 1 for the first item chosen.  ``self.assortment_`` =
+        {"rounds", "stopped" ("c", "no_gain" or "no_candidates"), "users", "floor" or "bar", "start" (what the given
+        items gained over the empty set), "value" (best score: floor + (start + total) / users, the mean best score a
+        user finds; reach: the share of users reached), "served" (a frame ``users``, ``items``, ``score``: per served
+        user the item of their best score -- reach: the item that covered them first -- read from the device state)}.
+        Reach answers depend on the model and the arguments alone; best-score gains are sums of doubles in the launch
+        plan's order -- the same bits from call to call, possibly other last bits on another device."""
+        self._check_whole_model()
+        c = check_integer(c, "c", 0, f"an integer from 0 to {self.ASSORTMENT_MAX}")
+        if c > self.ASSORTMENT_MAX:
+            raise ValueError(f"c must be an integer from 0 to {self.ASSORTMENT_MAX}, got {c}")
+        w = self._rating_weights(weights)
+        if objective not in self._ASSORTMENT_OBJECTIVES:
+            raise ValueError(f"objective must be one of {list(self._ASSORTMENT_OBJECTIVES)}, got {objective!r}")
+        if objective == "reach":
+            if bar is None:
+                raise ValueError('objective="reach" needs a bar')
+            if floor is not None:
+                raise ValueError('floor belongs to objective="best_score", not to "reach"')
+            level = check_finite(bar, "bar")
+        else:
+            if bar is not None:
+                raise ValueError('bar belongs to objective="reach", not to "best_score"')
+            level = float(w.min()) if floor is None else check_finite(floor, "floor")
+        users_side, items = self._side("users"), self._side("items")
+        ids, labels = users_side.request(users)
+        _, first = np.unique(ids, return_index=True)
+        first.sort()
+        ids, labels = ids[first], labels[first]                                # (a user named twice counts once)
+        held = np.zeros(0, dtype=np.int32) if given is None else items.request(list(given))[0]
+        held = held[np.sort(np.unique(held, return_index=True)[1])]
+        cand = self._candidate_ids(candidates)
+        with self._session_of_restarts("recommend", w, exclude_seen) as ctx:
+            chosen, gains, rounds, stopped, s_items, s_scores, start = ctx.recommend_assortment(
+                ids, c, objective, level, held, cand)
+        gains = np.asarray(gains, dtype=np.float64)
+        total = np.cumsum(gains)
+        reached = start + (float(total[-1]) if rounds else 0.0)
+        if objective == "reach":
+            value = reached / len(ids) if len(ids) else 0.0
+        else:
+            value = level + reached / len(ids) if len(ids) else level
+        got = np.asarray(s_items) >= 0
+        served = pd.DataFrame({"users": labels[got], "items": items.label(np.asarray(s_items)[got]),
+                               "score": np.asarray(s_scores, dtype=np.float64)[got]})
+        self.assortment_ = {"rounds": int(rounds), "stopped": stopped, "users": len(ids),
+                            ("bar" if objective == "reach" else "floor"): level, "start": start, "value": value,
+                            "served": served}
+        return pd.DataFrame({"items": items.label(np.asarray(chosen, dtype=np.int64)), "gain": gains, "total": total,
+                             "rank": np.arange(1, rounds + 1, dtype=np.int64)})
+
+    def assortment_value(self, items, objective="best_score", bar=None, floor=None, users=None, exclude_seen=True,
+                         weights=None):
+        """What a set somebody else picked is worth, by ``assortment``'s arithmetic: ``assortment(c=0, given=items,
+        ...)``.  Returns {"value", "start", "served"} of ``self.assortment_`` -- so a hand-made list and the greedy one
+        are compared by the same kernels."""
+        self.assortment(0, objective, bar, floor, items, users, None, exclude_seen, weights)
+        return {k: self.assortment_[k] for k in ("value", "start", "served")}
+
     # ------------------------------------------------------------------ how far the restarts agree (not in the reference)
     _ROBUST_AGGREGATES = {"lcb": "lcb", "worst": "min", "best": "max"}   # -> HipEM.ENSEMBLE_MODES
 
