@@ -475,6 +475,35 @@ int mmsbm_hip_recommend_allocate(mmsbm_hip_ctx *ctx, int64_t n_users, const int3
                                  const int32_t *caps, int32_t max_rounds, int32_t *items, double *scores,
                                  int32_t *counts, int32_t *rounds, int32_t *converged);
 
+/* Welfare-maximising assignment, inside the open recommend session (mmsbm_amd/csrc/assign.hpp): every user of the
+ * request gets AT MOST ONE item, item i of the session's catalogue at most caps[i] users (0: none; negative, or >=
+ * n_users: unlimited), and  sum of the assigned scores + (unassigned users) x reserve  is as large as it can be, within
+ * (assigned users) x epsilon.  allocate above answers the same caps with the one stable assignment; this is the one of
+ * largest total, and it prices the items.  The candidates are query's (the session's exclusions), the scores its bits.
+ * The answer is computed by a forward auction in Jacobi rounds from prices 0 (the definition, step by step, heads
+ * assign.hpp): item i holds caps[i] slots (price, holder); every user without an item bids for its best item at the
+ * items' cheapest slot prices, the bid (p1 + (v1 - v2)) + epsilon, or drops out for good when no candidate is worth more
+ * than reserve; an item takes its k-th highest bid into its k-th cheapest slot while bid > price, and the holder it
+ * displaces bids again.  Doubles are only added, subtracted and compared, so the prices are reproducible bit for bit.
+ * users: DISTINCT ids in any order, or NULL: all training users, n_users = their number.  Output by request row b:
+ * items[b] (-1: unassigned), scores[b] (-inf), paid[b] (the price of the slot it holds; 0: unassigned or an unlimited
+ * item), pi[b] = max(reserve, max over its candidates of score - price[i]) at the final prices; by catalogue item i:
+ * price[i] its cheapest slot (0: unlimited, +inf: caps[i] = 0), price_sum[i] the sum of its slot prices, load[i] the
+ * users that hold it.  sum(pi) + sum(price_sum) bounds the optimum from above whatever the prices, so the caller sees
+ * the gap without solving anything; at convergence the gap is at most (assigned users) x epsilon.  *rounds: the rounds
+ * run; *converged: 0 when max_rounds rounds left somebody bidding (the answer is feasible, the bound still holds).
+ * Options "assign_ms" (device time of the whole call, HIP events), "assign_rounds" and "assign_bids" (the bids of all
+ * rounds).  MMSBM_E_INVALID (before any launch): no session or no slot added, an id out of range, a repeated user id,
+ * epsilon not finite, not positive or below (largest - smallest rating weight) x 2^-40 (a bid could fail to raise a
+ * price by an ulp), reserve NaN or +inf, max_rounds < 1, a null caps or output; MMSBM_E_UNSUPPORTED: a cap above
+ * MMSBM_HIP_RECOMMEND_MAX_N and below n_users; MMSBM_E_TOOLARGE where the device memory is not free (two doubles and
+ * two ints of state and a bid per request user, a price and a holder per slot, one batch of scores).  Touches no slot
+ * and no other session; later queries of the session answer as before. */
+int mmsbm_hip_recommend_assign(mmsbm_hip_ctx *ctx, int64_t n_users, const int32_t *users, const int32_t *caps,
+                               double reserve, double epsilon, int32_t max_rounds, int32_t *items, double *scores,
+                               double *paid, double *pi, double *price, double *price_sum, int32_t *load,
+                               int32_t *rounds, int32_t *converged);
+
 /* ---- nearest items / users: the n most similar rows of one side (mmsbm_amd/csrc/similar.hpp) -------------------- */
 /* A session of its own beside the recommend session (either may be open while the other is):
  *   begin  side 0: items, 1: users (external sides).  Closes any earlier similarity session;

@@ -66,6 +66,8 @@ SIGNATURES = {
     "mmsbm_hip_recommend_query_items": (C.c_int, [C.c_void_p, C.c_int64, c_i32p, C.c_int32, c_i32p, c_f64p, c_i32p]),
     "mmsbm_hip_recommend_allocate": (C.c_int, [C.c_void_p, C.c_int64, c_i32p, C.c_int32, c_i32p, C.c_int32, c_i32p,
                                                c_f64p, c_i32p, c_i32p, c_i32p]),
+    "mmsbm_hip_recommend_assign": (C.c_int, [C.c_void_p, C.c_int64, c_i32p, c_i32p, C.c_double, C.c_double, C.c_int32,
+                                             c_i32p, c_f64p, c_f64p, c_f64p, c_f64p, c_f64p, c_i32p, c_i32p, c_i32p]),
     "mmsbm_hip_recommend_audience": (C.c_int, [C.c_void_p, C.c_int64, c_i32p, C.c_double, C.c_int64, c_i64p, c_i32p,
                                               c_f64p]),
     "mmsbm_hip_recommend_query_within": (C.c_int, [C.c_void_p, C.c_int64, c_i32p, C.c_int32, c_i32p, c_i64p, c_i32p,

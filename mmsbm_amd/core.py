@@ -680,6 +680,32 @@ class HipEM:
                   C.byref(rounds), C.byref(converged))
         return items, scores, counts, {"rounds": int(rounds.value), "converged": bool(converged.value)}
 
+    def recommend_assign(self, users, caps, reserve, epsilon, max_rounds=10000):
+        """Welfare-maximising assignment inside the open session: every user of ``users`` (distinct encoded ids; None:
+        all training users) gets at most one item, item i of the session's catalogue at most caps[i] users (0: none,
+        negative: unlimited), and the sum of the assigned scores plus ``reserve`` per unassigned user is the largest
+        possible within (assigned users) x ``epsilon`` -- a forward auction on the device.  Returns a dict: by request
+        row ``items`` (-1: unassigned), ``scores`` (-inf), ``paid``, ``pi``; by catalogue item ``price`` (its cheapest
+        slot), ``price_sum``, ``load``; and ``rounds``, ``bids``, ``converged``.  sum(pi) + sum(price_sum) bounds the
+        optimum from above."""
+        u = None if users is None else _i32(users)
+        m = self.n_users if u is None else len(u)
+        cap = _i32(caps)
+        if cap.ndim != 1 or len(cap) < self.n_items:
+            raise ValueError(f"caps has shape {cap.shape}, expected one entry per item of the session's catalogue")
+        items = np.full(m, -1, dtype=np.int32)
+        scores, paid, pi = (np.empty(m, dtype=np.float64) for _ in range(3))
+        price, price_sum = np.empty(len(cap), dtype=np.float64), np.empty(len(cap), dtype=np.float64)
+        load = np.zeros(len(cap), dtype=np.int32)
+        rounds, converged = C.c_int32(0), C.c_int32(0)
+        _lib.call("mmsbm_hip_recommend_assign", self._h, m, _p_or_null(u, C.c_int32), _p(cap, C.c_int32), float(reserve),
+                  float(epsilon), int(max_rounds), _p(items, C.c_int32), _p(scores, C.c_double), _p(paid, C.c_double),
+                  _p(pi, C.c_double), _p(price, C.c_double), _p(price_sum, C.c_double), _p(load, C.c_int32),
+                  C.byref(rounds), C.byref(converged))
+        return {"items": items, "scores": scores, "paid": paid, "pi": pi, "price": price, "price_sum": price_sum,
+                "load": load, "rounds": int(rounds.value), "converged": bool(converged.value),
+                "bids": int(self.get_option("assign_bids"))}
+
     def recommend_audience(self, items, min_score, count_only=False, total=None):
         """(offsets (M+1,) int64, users int32, scores): for each item id every candidate user whose score is >=
         min_score, in ascending user id -- item b's are [offsets[b]:offsets[b + 1]].  A sizes call followed by a

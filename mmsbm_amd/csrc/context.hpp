@@ -272,8 +272,8 @@ inline void sort_unique_groups(std::vector<int32_t> &off, std::vector<int32_t> &
 // recommend_audience, similar_query, overlap_query, heldout_eval / heldout_add, explain_query, recommend_diverse /
 // similar_pairs, inform_query / inform_query_theta, recommend_query_groups, recommend_query_ensemble / recommend_pair_spread,
 // loo_add / loo_rows / loo_sides / loo_lowest (and, of the last loo_add alone, its sums pass and its row pass),
-// recommend_allocate, recommend_top_pairs_bulk, recommend_assortment
-enum TimedCall { T_RECOMMEND = 0, T_FOLD_IN, T_POSITIONS, T_TOP_PAIRS, T_AUDIENCE, T_SIMILAR, T_OVERLAP, T_HELDOUT, T_EXPLAIN, T_DIVERSE, T_INFORM, T_GROUP, T_ENSEMBLE, T_LOO, T_LOO_SUMS, T_LOO_ROWS, T_ALLOCATE, T_TOP_PAIRS_BULK, T_ASSORT, T_COUNT };
+// recommend_allocate, recommend_top_pairs_bulk, recommend_assortment, recommend_assign
+enum TimedCall { T_RECOMMEND = 0, T_FOLD_IN, T_POSITIONS, T_TOP_PAIRS, T_AUDIENCE, T_SIMILAR, T_OVERLAP, T_HELDOUT, T_EXPLAIN, T_DIVERSE, T_INFORM, T_GROUP, T_ENSEMBLE, T_LOO, T_LOO_SUMS, T_LOO_ROWS, T_ALLOCATE, T_TOP_PAIRS_BULK, T_ASSORT, T_ASSIGN, T_COUNT };
 
 enum KernelId { K_SEG = 0, K_DENSE, K_ETAP, K_MATVEC_A, K_FUSED_PAIRS, K_FUSED_TAIL, K_COUNT };
 // The four launches of an iteration -- or, for small problems, the two of fused_small.hpp.  With pass_dense.hpp the
@@ -372,6 +372,8 @@ struct mmsbm_hip_ctx {
   int64_t div_rows = 0;                     // option "diverse_rows": request rows per call of recommend_diverse (0: likewise)
   int64_t grp_run = 0;                      // option "group_run_blocks": 8-row blocks of members per run of grp_tile_kernel (0: likewise)
   int alloc_rounds = 0;                     // option "allocate_rounds": the rounds of the last recommend_allocate
+  int asg_rounds = 0;                       // option "assign_rounds": the rounds of the last recommend_assign
+  int64_t asg_bids = 0;                     // option "assign_bids": the bids of all its rounds
   int64_t asrt_run = 0;                     // option "assortment_run_blocks": 8-row blocks of users per run of asrt_gain_kernel (0: likewise)
   int64_t asrt_part = 0;                    // option "assortment_part_bytes": the partial buffer of a batch of item tiles (0: kAsrtPartBytes)
   bool asrt_timing = false;                 // option "assortment_timing": events between the phases of every round

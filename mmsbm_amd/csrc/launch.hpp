@@ -132,6 +132,19 @@ void explore_noise(mmsbm_hip_ctx *c, const uint64_t pcg64_state[4], int64_t n_pa
 void recommend_allocate(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, int n, const AllocPlan &plan,
                         int max_rounds, int32_t *items, double *scores, int32_t *counts, int32_t *rounds,
                         int32_t *converged);
+// ... welfare-maximising assignment (assign.hpp): one item per user of the request (distinct ids) at most, the caps as
+// planned by plan_assign (serve_plan.hpp); the caller's output arrays (mmsbm_hip.h); its sort of a round's bids
+// (tu_pairs_bulk.hip): the places by (item, bid descending, place)
+struct AssignOut {
+  int32_t *items;
+  double *scores, *paid, *pi, *price, *price_sum;
+  int32_t *load, *rounds, *converged;
+};
+void recommend_assign(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, const AssignPlan &plan, double reserve,
+                      double eps, int max_rounds, const AssignOut &out);
+size_t assign_sort_bytes(size_t n);
+void assign_sort_bids(hipStream_t st, void *tmp, size_t bytes, const int32_t *item, const double *bid,
+                      const uint32_t *place, uint32_t *sorted, size_t n);
 // ... and nearest items / users (similar.hpp): the session of mmsbm_hip_similar_*, arguments checked
 void similar_begin(mmsbm_hip_ctx *c, int side);
 void similar_add(mmsbm_hip_ctx *c);  // the selected slot (the caller holds a OneSlot)

@@ -684,6 +684,49 @@ int mmsbm_hip_recommend_allocate(mmsbm_hip_ctx *ctx, int64_t n_users, const int3
   });
 }
 
+int mmsbm_hip_recommend_assign(mmsbm_hip_ctx *ctx, int64_t n_users, const int32_t *users, const int32_t *caps,
+                               double reserve, double epsilon, int32_t max_rounds, int32_t *items, double *scores,
+                               double *paid, double *pi, double *price, double *price_sum, int32_t *load,
+                               int32_t *rounds, int32_t *converged) {
+  return guarded([&] {
+    const RecSession &rc = require_open(ctx, &mmsbm_hip_ctx::rc, "recommend", "recommend_assign");
+    if (n_users < 0) throw std::invalid_argument("negative n_users");
+    if (max_rounds < 1) throw std::invalid_argument("recommend_assign: max_rounds must be at least 1");
+    if (!std::isfinite(epsilon) || !(epsilon > 0.0) || epsilon < (rc.w_max - rc.w_min) * 0x1p-40)
+      throw std::invalid_argument("recommend_assign: epsilon must be finite, positive and at least (largest - smallest "
+                                  "rating weight) x 2^-40");
+    if (std::isnan(reserve) || reserve == INFINITY) throw std::invalid_argument("recommend_assign: reserve is NaN or +inf");
+    if (!caps || !rounds || !converged || !price || !price_sum || !load || (n_users > 0 && (!items || !scores || !paid || !pi)))
+      throw std::invalid_argument("null argument");
+    std::vector<int32_t> all;
+    if (!users) {  // all training users
+      if (n_users != ctx->ext_users)
+        throw std::invalid_argument("recommend_assign: without users, n_users must be the number of training users");
+      all.resize(static_cast<size_t>(n_users));
+      for (int64_t b = 0; b < n_users; ++b) all[static_cast<size_t>(b)] = static_cast<int32_t>(b);
+      users = all.data();
+    } else {
+      require_ids(users, n_users, ctx->ext_users, "recommend_assign: user");
+      std::vector<bool> asked(static_cast<size_t>(ctx->ext_users), false);
+      for (int64_t b = 0; b < n_users; ++b) {
+        if (asked[static_cast<size_t>(users[b])])
+          throw std::invalid_argument("recommend_assign: user " + std::to_string(users[b]) + " is asked twice (row " +
+                                      std::to_string(b) + ")");
+        asked[static_cast<size_t>(users[b])] = true;
+      }
+    }
+    const AssignPlan plan = plan_assign(caps, rc.items, n_users, MMSBM_HIP_RECOMMEND_MAX_N);
+    if (plan.refused >= 0)
+      throw ApiError(MMSBM_E_UNSUPPORTED, "recommend_assign: the cap of item " + std::to_string(plan.refused) + ", " +
+                                              std::to_string(caps[plan.refused]) + ", is above " +
+                                              std::to_string(MMSBM_HIP_RECOMMEND_MAX_N) + " and below the " +
+                                              std::to_string(n_users) + " users of the request (or the slots are "
+                                              "more than 2^31)");
+    recommend_assign(ctx, n_users, users, plan, reserve, epsilon, max_rounds,
+                     AssignOut{items, scores, paid, pi, price, price_sum, load, rounds, converged});
+  });
+}
+
 int mmsbm_hip_recommend_audience(mmsbm_hip_ctx *ctx, int64_t n_items, const int32_t *items, double min_score,
                                  int64_t capacity, int64_t *offsets, int32_t *users, double *scores) {
   return guarded([&] {

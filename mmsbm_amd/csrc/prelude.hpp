@@ -24,7 +24,8 @@
 //                       group.hpp      group queries               ensemble.hpp   how far the restarts agree on a pair
 //                       pairs_bulk.hpp the m best pairs beyond 1,024, planned by pairs_bulk_plan.hpp
 //                       assortment.hpp greedy assortment selection: rounds chained on the stream behind a stop flag
-//   tu_pairs_bulk.hip the device sorts of pairs_bulk.hpp (rocPRIM)
+//                       assign.hpp     welfare-maximising assignment: rounds of a forward auction over the active users
+//   tu_pairs_bulk.hip the device sorts of pairs_bulk.hpp and assign.hpp (rocPRIM)
 //   tu_fold_in.hip    fold new users into a fitted model (fold_in.hpp)
 //   tu_heldout.hip    held-out log-likelihood of every restart slot (heldout.hpp)
 //   tu_explain.hip    which of a user's training rows carry a recommendation (explain.hpp)

@@ -248,6 +248,49 @@ inline AllocPlan plan_allocate(const int32_t *caps, int n_items, int64_t n_users
   return p;
 }
 
+// ---- welfare-maximising assignment (assign.hpp) -------------------------------------------------------------------------
+// What recommend_assign makes of the caller's caps (plan_allocate's reading of them): per item -1 (unlimited: negative
+// or >= n_users), 0 (closed) or its cap, and the binding items' slots one after the other.
+struct AssignPlan {
+  std::vector<int32_t> cap;       // per catalogue item: -1, 0, or 1 .. min(max_n, n_users - 1)
+  std::vector<int32_t> slot_off;  // [items + 1]: the item's slots (none for -1 and 0)
+  int64_t refused = -1;           // the first item whose cap lies in (max_n, n_users); nothing else is filled in
+  int most = 0;                   // the largest binding cap
+  int lds_places() const {        // assign_accept_kernel's list: a power of two >= most, at least 2
+    int p = 2;
+    while (p < most) p <<= 1;
+    return p;
+  }
+  size_t slots() const { return slot_off.empty() ? 0 : static_cast<size_t>(slot_off.back()); }
+};
+
+inline AssignPlan plan_assign(const int32_t *caps, int n_items, int64_t n_users, int max_n) {
+  AssignPlan p;
+  p.cap.assign(static_cast<size_t>(n_items), -1);
+  p.slot_off.assign(static_cast<size_t>(n_items) + 1, 0);
+  int64_t total = 0;
+  for (int i = 0; i < n_items; ++i) {
+    const int64_t q = caps[i];
+    if (q >= 0 && q < n_users) {
+      if (q > max_n) {
+        AssignPlan none;
+        none.refused = i;
+        return none;
+      }
+      p.cap[static_cast<size_t>(i)] = static_cast<int32_t>(q);
+      p.most = std::max(p.most, static_cast<int>(q));
+      total += q;
+    }
+    if (total > INT32_MAX) {  // (n_items x max_n slots: beyond int32 offsets)
+      AssignPlan none;
+      none.refused = i;
+      return none;
+    }
+    p.slot_off[static_cast<size_t>(i) + 1] = static_cast<int32_t>(total);
+  }
+  return p;
+}
+
 // ---- group queries (group.hpp) -----------------------------------------------------------------------------------------
 // What recommend_query_groups uploads and launches with.  The rows of the device request are the groups that have
 // members (an empty group has no candidate); their members stand in blocks of kGrpBlock rows, a group's last block

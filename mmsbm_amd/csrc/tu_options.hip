@@ -75,6 +75,10 @@ const Option kOptions[] = {
     {"assortment_pick_ms", [](const Ctx *c) -> double { return c->asrt_ms[1]; }, nullptr},
     {"assortment_update_ms", [](const Ctx *c) -> double { return c->asrt_ms[2]; }, nullptr},
     {"assortment_timing", [](const Ctx *c) -> double { return c->asrt_timing; }, [](Ctx *c, double v) { c->asrt_timing = v != 0.0; }},
+    // ... of the last recommend_assign as a whole (assign.hpp), its rounds and the bids of all of them
+    {"assign_ms", [](const Ctx *c) -> double { return c->last_ms[T_ASSIGN]; }, nullptr},
+    {"assign_rounds", [](const Ctx *c) -> double { return c->asg_rounds; }, nullptr},
+    {"assign_bids", [](const Ctx *c) -> double { return static_cast<double>(c->asg_bids); }, nullptr},
     // workgroups of gtop_fused_kernel (top_pairs.hpp); 0: the library's choice
     {"top_pairs_groups", [](const Ctx *c) -> double { return c->top_groups; },
      [](Ctx *c, double v) {

@@ -1,6 +1,7 @@
 // tu_pairs_bulk.hip -- translation unit of the device sorts behind mmsbm_hip_recommend_top_pairs_bulk (pairs_bulk.hpp):
 // the collected bin of the radix select, and phase 3, the order of the m entries.  The sorts are rocPRIM's stable radix
-// sorts -- library calls for a library job, as in tu_layout.hip; the two kernels around them are element-wise.
+// sorts -- library calls for a library job, as in tu_layout.hip; the two kernels around them are element-wise.  Also the
+// sort of a round's bids of mmsbm_hip_recommend_assign (assign.hpp): rocPRIM's merge sort under a strict total order.
 #include "prelude.hpp"
 
 #include <rocprim/rocprim.hpp>
@@ -33,7 +34,34 @@ __global__ __launch_bounds__(kBlock) void pbulk_gather_kernel(const uint32_t *__
 
 unsigned blocks_for(size_t n) { return static_cast<unsigned>((n + kBlock - 1) / kBlock); }
 
+// The order of the bids of a round of assign.hpp, over their places: item ascending, bid descending, place ascending
+// -- a strict total order, so the sorted sequence is one whatever the sort's own order of work
+struct AssignBidBefore {
+  const int32_t *item;
+  const double *bid;
+  __device__ bool operator()(uint32_t a, uint32_t b) const {
+    const int32_t ia = item[a], ib = item[b];
+    if (ia != ib) return ia < ib;
+    const double ba = bid[a], bb = bid[b];
+    if (ba != bb) return ba > bb;
+    return a < b;
+  }
+};
+
 }  // namespace
+
+size_t assign_sort_bytes(size_t n) {
+  size_t bytes = 0;
+  HIP_CHECK(rocprim::merge_sort(nullptr, bytes, static_cast<const uint32_t *>(nullptr), static_cast<uint32_t *>(nullptr),
+                                std::max<size_t>(n, 1), AssignBidBefore{nullptr, nullptr}, hipStream_t(nullptr)));
+  return bytes;
+}
+
+void assign_sort_bids(hipStream_t st, void *tmp, size_t bytes, const int32_t *item, const double *bid,
+                      const uint32_t *place, uint32_t *sorted, size_t n) {
+  if (n == 0) return;
+  HIP_CHECK(rocprim::merge_sort(tmp, bytes, place, sorted, n, AssignBidBefore{item, bid}, st));
+}
 
 void pairs_bulk_sort_desc(mmsbm_hip_ctx *c, const uint64_t *keys, uint64_t *sorted, size_t n) {
   if (n == 0) return;

@@ -24,6 +24,9 @@
 //                  probability from the unperturbed scores; the propensities of given lists
 //   assortment.hpp greedy assortment selection: rounds of a gain pass over the score tiles against a per-user state, an
 //                  arg-max over the catalogue and a state update, chained on the stream behind a stop flag
+//   assign.hpp     welfare-maximising assignment: rounds of a forward auction over the compacted active users -- the
+//                  score tile less a price per column, the same exclusions and selection with n = 2, the bids sorted
+//                  (tu_pairs_bulk.hip) and merged into the items' slots by one wave per item
 #include "prelude.hpp"
 #include "recommend.hpp"
 #include "similar.hpp"
@@ -41,6 +44,7 @@
 #include "shelves.hpp"
 #include "explore.hpp"
 #include "assortment.hpp"
+#include "assign.hpp"
 
 namespace mmsbm_hip_impl {
 
@@ -1517,6 +1521,173 @@ void recommend_allocate(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users,
   top_n_copy_out(c, TopNDev{ps.ptr, pi.ptr, pn.ptr}, ev, n_users, n, T_ALLOCATE, items, scores, counts);
   *rounds = round;
   c->alloc_rounds = round;
+}
+
+// ---- welfare-maximising assignment (assign.hpp) -------------------------------------------------------------------------
+// The rounds of the forward auction over the compacted list of active rows, then the certificate pass over all rows; the
+// row state, the slots and the prices stay on the device, and the host reads one int per round: the next round's active
+// rows.  users: distinct ids (checked by the C ABI), any order -- the device works in id order.
+void recommend_assign(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, const AssignPlan &plan, double reserve,
+                      double eps, int max_rounds, const AssignOut &out) {
+  use_device(c);
+  const RecSession &rc = *c->rc;
+  const int NI = rc.items, rank = rc.rank;
+  for (int64_t b = 0; b < n_users; ++b) {
+    out.items[b] = -1;
+    out.scores[b] = -INFINITY;
+    out.paid[b] = 0.0;
+    out.pi[b] = reserve;
+  }
+  for (int i = 0; i < NI; ++i) {
+    const int32_t q = plan.cap[static_cast<size_t>(i)];
+    out.price[i] = q == 0 ? INFINITY : 0.0;
+    out.price_sum[i] = 0.0;
+    out.load[i] = 0;
+  }
+  *out.rounds = 0;
+  *out.converged = 1;
+  c->last_ms[T_ASSIGN] = 0.f;
+  c->asg_rounds = 0;
+  c->asg_bids = 0;
+  if (n_users == 0 || NI == 0) return;
+  hipStream_t st = c->stream;
+  const size_t xs = rc.x_stride(), ys = static_cast<size_t>(NI) * rank;
+  const size_t nu = static_cast<size_t>(n_users), n_slots = plan.slots();
+  // the request in id order: row r is request row at[r]
+  std::vector<int64_t> at(nu);
+  for (size_t b = 0; b < nu; ++b) at[b] = static_cast<int64_t>(b);
+  std::sort(at.begin(), at.end(), [&](int64_t a, int64_t b) { return users[a] < users[b]; });
+  std::vector<int32_t> ids(nu);
+  for (size_t r = 0; r < nu; ++r) ids[r] = users[at[r]];
+  const int64_t bu = rec_batch_users(NI, n_users);
+  const std::pair<int, int> split = item_parts(NI, bu, 32LL * c->n_cus, kRecMinPerPart);
+  const int parts = split.first, per = split.second;
+  const size_t cand = parts > 1 ? static_cast<size_t>(bu) * parts * 2 : 0;
+  const int nblk = static_cast<int>((n_users + kBlock - 1) / kBlock);
+  const size_t sort_bytes = assign_sort_bytes(nu);
+  require_free_mem(static_cast<size_t>(bu) * NI * sizeof(double) + cand * 12 + static_cast<size_t>(bu) * parts * 4 +
+                       nu * (2 * 8 + 2 * 4 + 2 * 12 + 4 + 3 * 4 + 2 * 8 + 2 * 4) + n_slots * 12 +
+                       static_cast<size_t>(NI) * (3 * 8 + 2 * 4) + static_cast<size_t>(nblk) * 8 + sort_bytes + 4,
+                   "recommend_assign: a batch of scores, the users' state, the bids and the items' slots");
+  std::vector<double> p1_h(static_cast<size_t>(NI)), p2_h(static_cast<size_t>(NI));
+  for (int i = 0; i < NI; ++i) {
+    const int32_t q = plan.cap[static_cast<size_t>(i)];
+    p1_h[static_cast<size_t>(i)] = q == 0 ? INFINITY : 0.0;
+    p2_h[static_cast<size_t>(i)] = q < 0 || q >= 2 ? 0.0 : INFINITY;
+  }
+  DevBuf<double> sc, cs, vs, row_paid, row_score, price, p1, p2, bid, bid_score, psum;
+  DevBuf<int32_t> du, ci, cn, vi, vn, row_item, dropped, holder, d_cap, d_off, act_r, act_u, bid_item, blk_cnt, blk_base,
+      d_total;
+  DevBuf<uint32_t> place, ord;
+  DevBuf<char> tmp;
+  sc.alloc(static_cast<size_t>(bu) * NI);
+  if (cand > 0) {
+    cs.alloc(cand); ci.alloc(cand); cn.alloc(static_cast<size_t>(bu) * parts);
+  }
+  vs.alloc(2 * nu); vi.alloc(2 * nu); vn.alloc(nu);
+  du.upload(ids, st);
+  act_u.upload(ids, st);  // the first round: every row is active
+  std::vector<int32_t> iota(nu);
+  for (size_t r = 0; r < nu; ++r) iota[r] = static_cast<int32_t>(r);
+  act_r.upload(iota, st);
+  // nobody holds anything, every slot is free at price 0 (+0.0 and -1 are one byte repeated)
+  const std::vector<double> ninf_d(nu, -INFINITY);
+  row_item.alloc(nu); dropped.alloc(nu); row_paid.alloc(nu); row_score.upload(ninf_d, st);
+  price.alloc(n_slots); holder.alloc(n_slots); psum.alloc(static_cast<size_t>(NI));
+  HIP_CHECK(hipMemsetAsync(row_item.ptr, 0xFF, sizeof(int32_t) * nu, st));
+  HIP_CHECK(hipMemsetAsync(dropped.ptr, 0, sizeof(int32_t) * nu, st));
+  HIP_CHECK(hipMemsetAsync(row_paid.ptr, 0, sizeof(double) * nu, st));
+  if (n_slots > 0) {
+    HIP_CHECK(hipMemsetAsync(price.ptr, 0, sizeof(double) * n_slots, st));
+    HIP_CHECK(hipMemsetAsync(holder.ptr, 0xFF, sizeof(int32_t) * n_slots, st));
+  }
+  p1.upload(p1_h, st); p2.upload(p2_h, st);
+  d_cap.upload(plan.cap, st); d_off.upload(plan.slot_off, st);
+  bid.alloc(nu); bid_score.alloc(nu); bid_item.alloc(nu); place.alloc(nu); ord.alloc(nu);
+  blk_cnt.alloc(static_cast<size_t>(nblk)); blk_base.alloc(static_cast<size_t>(nblk)); d_total.alloc(1);
+  tmp.alloc(sort_bytes);
+  HIP_CHECK(hipStreamSynchronize(st));  // (the uploads' host vectors are temporaries)
+  const SeenLists seen = rc.seen_lists();
+  const size_t accept_lds = static_cast<size_t>(plan.lds_places()) * (sizeof(double) + sizeof(int32_t));
+  // the values of rows ub[0 .. nb) at the prices p1, the exclusions, and the n best of every row to vs / vi / vn
+  auto value_pass = [&](const int32_t *ub, int nb, int n, size_t o0) {
+    const dim3 g(static_cast<unsigned>((NI + kRecTile - 1) / kRecTile), static_cast<unsigned>((nb + kRecTile - 1) / kRecTile));
+    LAUNCH(assign_value_kernel, g, kBlock, 0, st, rc.x.ptr, xs, rc.y.ptr, ys, ub, nb, NI, rank, rc.slots,
+           static_cast<const double *>(p1.ptr), sc.ptr, static_cast<size_t>(NI));
+    if (seen.off) LAUNCH(rec_exclude_kernel, nb, kBlock, 0, st, ub, seen.off, seen.items, sc.ptr, static_cast<size_t>(NI));
+    select_batch(st, sc.ptr, NI, nb, parts, per, n, cs.ptr, ci.ptr, cn.ptr, vs.ptr + o0 * n, vi.ptr + o0 * n, vn.ptr + o0);
+  };
+  EventPair ev;  // device time of the whole call (option "assign_ms"): the host's reads between the rounds included
+  ev.start(st);
+  int round = 0;
+  int64_t na = n_users, active_sum = 0;
+  while (na > 0) {
+    if (round == max_rounds) {
+      *out.converged = 0;
+      break;
+    }
+    ++round;
+    active_sum += na;
+    for (int64_t b0 = 0; b0 < na; b0 += bu)
+      value_pass(act_u.ptr + b0, static_cast<int>(std::min(bu, na - b0)), 2, static_cast<size_t>(b0));
+    const int n_act = static_cast<int>(na);
+    LAUNCH(assign_bid_kernel, static_cast<unsigned>((na + kBlock - 1) / kBlock), kBlock, 0, st, rc.x.ptr, xs, rc.y.ptr, ys,
+           rank, rc.slots, static_cast<const int32_t *>(act_u.ptr), static_cast<const int32_t *>(act_r.ptr), n_act,
+           static_cast<const double *>(vs.ptr), static_cast<const int32_t *>(vi.ptr), static_cast<const int32_t *>(vn.ptr),
+           static_cast<const double *>(p1.ptr), static_cast<const double *>(p2.ptr), reserve, eps, bid_item.ptr, bid.ptr,
+           bid_score.ptr, place.ptr, dropped.ptr);
+    assign_sort_bids(st, tmp.ptr, sort_bytes, bid_item.ptr, bid.ptr, place.ptr, ord.ptr, static_cast<size_t>(na));
+    LAUNCH(assign_accept_kernel, static_cast<unsigned>(NI), kRecWave, accept_lds, st, static_cast<const int32_t *>(d_cap.ptr),
+           static_cast<const int32_t *>(d_off.ptr), plan.lds_places(), static_cast<const int32_t *>(bid_item.ptr),
+           static_cast<const double *>(bid.ptr), static_cast<const double *>(bid_score.ptr),
+           static_cast<const uint32_t *>(ord.ptr), n_act, static_cast<const int32_t *>(act_r.ptr), price.ptr, holder.ptr,
+           p1.ptr, p2.ptr, row_item.ptr, row_paid.ptr, row_score.ptr);
+    LAUNCH(assign_count_kernel, static_cast<unsigned>(nblk), kBlock, 0, st, static_cast<const int32_t *>(row_item.ptr),
+           static_cast<const int32_t *>(dropped.ptr), static_cast<int>(n_users), blk_cnt.ptr);
+    LAUNCH(assign_scan_kernel, 1, kBlock, 0, st, static_cast<const int32_t *>(blk_cnt.ptr), nblk, blk_base.ptr, d_total.ptr);
+    LAUNCH(assign_list_kernel, static_cast<unsigned>(nblk), kBlock, 0, st, static_cast<const int32_t *>(row_item.ptr),
+           static_cast<const int32_t *>(dropped.ptr), static_cast<const int32_t *>(du.ptr), static_cast<int>(n_users),
+           static_cast<const int32_t *>(blk_base.ptr), act_r.ptr, act_u.ptr);
+    HIP_CHECK(hipGetLastError());
+    int32_t next = 0;
+    HIP_CHECK(hipMemcpyAsync(&next, d_total.ptr, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));  // (the round's only wait)
+    na = next;
+  }
+  // the certificate: every row's best value at the final prices
+  for (int64_t b0 = 0; b0 < n_users; b0 += bu)
+    value_pass(du.ptr + b0, static_cast<int>(std::min(bu, n_users - b0)), 1, static_cast<size_t>(b0));
+  LAUNCH(assign_price_sum_kernel, static_cast<unsigned>((NI + kBlock - 1) / kBlock), kBlock, 0, st,
+         static_cast<const int32_t *>(d_off.ptr), static_cast<const double *>(price.ptr), NI, psum.ptr);
+  HIP_CHECK(hipGetLastError());
+  ev.stop(st);
+  std::vector<int32_t> h_item(nu), h_drop(nu), h_vn(nu);
+  std::vector<double> h_paid(nu), h_score(nu), h_vs(nu);
+  HIP_CHECK(hipMemcpyAsync(h_item.data(), row_item.ptr, sizeof(int32_t) * nu, hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipMemcpyAsync(h_drop.data(), dropped.ptr, sizeof(int32_t) * nu, hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipMemcpyAsync(h_vn.data(), vn.ptr, sizeof(int32_t) * nu, hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipMemcpyAsync(h_paid.data(), row_paid.ptr, sizeof(double) * nu, hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipMemcpyAsync(h_score.data(), row_score.ptr, sizeof(double) * nu, hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipMemcpyAsync(h_vs.data(), vs.ptr, sizeof(double) * nu, hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipMemcpyAsync(out.price_sum, psum.ptr, sizeof(double) * NI, hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipMemcpyAsync(out.price, p1.ptr, sizeof(double) * NI, hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipStreamSynchronize(st));
+  c->last_ms[T_ASSIGN] = ev.ms();
+  int64_t n_dropped = 0;
+  for (size_t r = 0; r < nu; ++r) {
+    const size_t b = static_cast<size_t>(at[r]);
+    const double best = h_vn[r] > 0 ? h_vs[r] : -INFINITY;
+    out.pi[b] = best > reserve ? best : reserve;
+    n_dropped += h_drop[r] != 0;
+    if (h_item[r] < 0) continue;
+    out.items[b] = h_item[r];
+    out.scores[b] = h_score[r];
+    out.paid[b] = h_paid[r];
+    ++out.load[h_item[r]];
+  }
+  *out.rounds = round;
+  c->asg_rounds = round;
+  c->asg_bids = active_sum - n_dropped;  // every active row of a round bids or drops out, and drops out once
 }
 
 void recommend_audience(mmsbm_hip_ctx *c, int64_t n_items, const int32_t *items, double min_score, int64_t capacity,

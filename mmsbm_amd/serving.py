@@ -8,6 +8,7 @@ frame assembler.
 from __future__ import annotations
 
 import contextlib
+import math
 import warnings
 
 import numpy as np
@@ -726,6 +727,91 @@ class Serving:
         count = np.bincount(codes, minlength=len(found)).astype(np.int64)
         order = np.argsort(-count, kind="stable")
         return pd.DataFrame({"items": np.asarray(found, dtype=object)[order], "count": count[order]})
+
+    def assign(self, capacity=..., epsilon=None, reserve=None, users=None, exclude_seen=True, weights=None,
+               candidates=None, max_rounds=10000):
+        """The assignment of largest total score under ``allocate``'s capacities: every requested user gets at most one
+        item, item i at most ``capacity[i]`` users, and  sum of the assigned scores + (unassigned users) x ``reserve``
+        is the largest possible, within (assigned users) x ``epsilon``.  Papers to reviewers, coupons to customers,
+        stock to a mailing.  ``allocate`` gives the one stable assignment (nobody envies anybody) and spends the good
+        items on whoever comes first; this one maximises the sum, and prices every item: the price is what one more
+        unit of it is worth in score units.  On the device it is a forward auction: users without an item bid for their
+        best item at the current prices, an item keeps its highest bids, and who is outbid bids again.
+
+        ``capacity`` (required) and ``candidates``: as ``allocate``'s.  ``epsilon`` (required): the bidding step, in
+        score units -- smaller is closer to the optimum and takes more rounds.  ``reserve``: what an unassigned user
+        counts; a user whose every candidate is worth less at the final prices stays out.  None: min(weights) - span
+        (span = max(weights) - min(weights), or 1), below every score, so that any candidate beats staying out.
+        ``users``: distinct labels (None: every training user).  ``max_rounds``: the rounds after which the device stops
+        (RuntimeWarning); the assignment is then feasible and ``bound`` still holds.
+
+        Returns ``recommend``'s frame (``users``, ``items``, ``score``, ``rank`` = 1) plus ``price``, what the user's
+        slot costs; unassigned users have no row.  Scores are ``recommend``'s, bit for bit; with nothing capped the frame
+        is ``recommend(n=1)``'s for every user whose best score exceeds ``reserve``.  ``self.assignment_``: ``rounds``,
+        ``bids``, ``converged``, ``assigned``, ``dropped``, ``total`` (the sum of the scores), ``value`` (with the
+        reserve), ``bound`` (no assignment is worth more), ``gap_limit`` = assigned x epsilon, and ``prices``: a frame
+        ``items``, ``price``, ``load``, ``capacity`` of the capped items.  Not covered: more than one item per user,
+        ``exclude=`` pairs, folded-in users, epsilon-scaling, capacities above 1,024 that bind."""
+        if capacity is ...:
+            raise TypeError("assign needs capacity=")
+        if epsilon is None:
+            raise TypeError("assign needs epsilon=")
+        self._check_whole_model()
+        _, w = self._recommend_args(1, weights)
+        max_rounds = check_integer(max_rounds, "max_rounds", 1)
+        span = float(w.max() - w.min())
+        if isinstance(epsilon, (bool, np.bool_)) or not isinstance(epsilon, (int, float, np.integer, np.floating)) \
+                or not np.isfinite(epsilon) or not epsilon > 0 or epsilon < span * 2.0 ** -40:
+            raise ValueError(f"epsilon must be a finite number > 0 and >= (max - min weight) x 2^-40, got {epsilon!r}")
+        if reserve is None:
+            reserve = float(w.min()) - (span if span > 0 else 1.0)
+        elif isinstance(reserve, (bool, np.bool_)) or not isinstance(reserve, (int, float, np.integer, np.floating)) \
+                or np.isnan(reserve) or reserve == np.inf:
+            raise ValueError(f"reserve must be a number below +inf, got {reserve!r}")
+        epsilon, reserve = float(epsilon), float(reserve)
+        ids, labels = self._side("users").request(users)
+        if len(np.unique(ids)) != len(ids):
+            raise ValueError("users must be distinct: capacity couples the users of a request, not its rows")
+        items = self._side("items")
+        caps = allocate_capacity(capacity, items)
+        cand = self._candidate_ids(candidates)
+        if cand is not None:
+            inside = np.zeros(len(items), dtype=bool)
+            inside[cand] = True
+            caps[~inside] = 0
+        binding = np.flatnonzero((caps >= 0) & (caps < len(ids)))
+        self.assignment_ = {"rounds": 0, "bids": 0, "converged": True, "assigned": 0, "dropped": 0, "total": 0.0,
+                            "value": math.fsum([reserve] * len(ids)) if len(ids) else 0.0,
+                            "bound": math.fsum([reserve] * len(ids)) if len(ids) else 0.0, "gap_limit": 0.0,
+                            "prices": pd.DataFrame({"items": items.label(binding), "price": np.zeros(len(binding)),
+                                                    "load": np.zeros(len(binding), dtype=np.int64),
+                                                    "capacity": caps[binding].astype(np.int64)})}
+        columns = {"items": items, "score": None, "rank": None, "price": None}
+        if len(ids) == 0:
+            return self._frame({"users": labels[:0]}, columns, [], None, 1)
+
+        def whole(b, e):   # (one call: the users of a request cannot be split)
+            got = ctx.recommend_assign(ids, caps, reserve, epsilon, max_rounds)
+            has = got["items"] >= 0
+            scores = got["scores"][has].tolist()
+            self.assignment_.update(
+                rounds=got["rounds"], bids=got["bids"], converged=got["converged"], assigned=int(has.sum()),
+                dropped=int((~has).sum()), total=math.fsum(scores),
+                value=math.fsum(scores + [reserve] * int((~has).sum())),
+                bound=math.fsum(got["pi"].tolist() + got["price_sum"][binding].tolist()),
+                gap_limit=int(has.sum()) * epsilon)
+            self.assignment_["prices"] = pd.DataFrame({
+                "items": items.label(binding), "price": got["price"][binding],
+                "load": got["load"][binding].astype(np.int64), "capacity": caps[binding].astype(np.int64)})
+            return has.astype(np.int64), {"items": got["items"][:, None], "score": got["scores"][:, None],
+                                          "price": got["paid"][:, None]}
+        with self._session_of_restarts("recommend", w, exclude_seen) as ctx:
+            frame = self._frame({"users": labels}, columns, [(0, len(ids))], whole, 1)
+        if not self.assignment_["converged"]:
+            warnings.warn(f"assign stopped after max_rounds = {max_rounds} rounds with users still bidding: the "
+                          "assignment is feasible, and assignment_['bound'] holds, but the gap may exceed gap_limit",
+                          RuntimeWarning, stacklevel=2)
+        return frame
 
     def rerank(self, pairs, n=None, exclude_seen=True, weights=None):
         """The order of caller-given candidates per user -- the second stage of a two-stage system: a cheap retriever
