@@ -22,8 +22,9 @@
 // On the device both passes are the batches of a top-N query (tu_recommend.hip) with ONE change: the score tile's
 // epilogue compares each score with its column's key and its row's key in registers and stores -inf in place of a score
 // that fails either (alloc_score_kernel: rec_tile_acc, then the same single division rec_score_kernel stores).  The
-// exclusions and the selection that follow are recommend's own kernels, so the scores are recommend_query's bits and
-// the orders are its orders.  No atomics; nothing depends on the batch or grid shape.
+// exclusions and the selection that follow are recommend's own kernels (on the host: exclude_seen and one SelectStage
+// whose scratch serves both passes, tu_recommend.hip), so the scores are recommend_query's bits and the orders are its
+// orders.  No atomics; nothing depends on the batch or grid shape.
 //   alloc_score_kernel   user pass: rows = the request's users, column keys = tau (by item), no row keys;
 //                        item pass: the tables exchanged as in recommend_query_items, rows = the capped items, row
 //                        keys = tau (by item), column keys = sigma (by user; +inf for users outside the request)

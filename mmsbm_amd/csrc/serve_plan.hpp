@@ -1,5 +1,5 @@
 // serve_plan.hpp -- the launch plans of the serving queries (tu_recommend.hip) as plain values: the batches of a top-N
-// query and its item split, the selection's list, the blocks / runs / fragments of a group query, the COUNT batches and
+// query and its item split, the selection's list and scratch (SelectPlan), the blocks / runs / fragments of a group query, the COUNT batches and
 // WRITE runs of an audience query, the rows per call of a diversified query.  Host arithmetic on plain numbers only -- no
 // HIP type, no context -- so that the rules a kernel's block index depends on are checked on the CPU over every shape
 // (tests/native/serve_plan_check.cpp).  The shape constants the plans share with the kernels are defined here, once.
@@ -56,6 +56,24 @@ inline std::pair<int, size_t> select_list(int n) {  // (places, LDS bytes)
   while (cap < n + kRecWave * kRecPerLane) cap <<= 1;
   return {cap, static_cast<size_t>(cap) * (sizeof(double) + sizeof(int32_t))};
 }
+
+// The selection of one batch (rec_select_kernel): the n best of every one of `rows` batch rows over `cols` columns.  The
+// columns are split into `parts` parts of `per` (item_parts) until about `target` selecting waves are in flight; with
+// more than one part every (row, part) leaves a list of n places (`entries` in all, a score and an id each) and a count
+// (`lists`) that a second launch merges; one part selects straight into the result and needs no places.
+struct SelectPlan {
+  int cols = 0, parts = 1, per = 0;
+  size_t entries = 0, lists = 0;
+  SelectPlan() = default;  // (a selection that never runs: no scratch)
+  SelectPlan(int cols_, int64_t rows, int n, int min_per, int64_t target) : cols(cols_) {
+    const std::pair<int, int> split = item_parts(cols, rows, target, min_per);
+    parts = split.first;
+    per = split.second;
+    lists = static_cast<size_t>(rows) * parts;
+    entries = parts > 1 ? lists * n : 0;
+  }
+  size_t bytes() const { return entries * (sizeof(double) + sizeof(int32_t)) + lists * sizeof(int32_t); }
+};
 
 // ---- per-category caps (quota.hpp) -------------------------------------------------------------------------------------
 // What a query with capped categories uploads and launches with.  The categories are the caller's, as catalogue items

@@ -9,8 +9,8 @@
 // the n_shelves categories of largest value, equal values by ascending category index of the call; a shelf's items are
 // the first min(per_shelf, a) of s_1, s_2, ...  A row's answer depends on that row alone.
 //
-// Per batch of rows, between the exclusions and the next batch's score tiles (the batch buffer sc [rows][columns] is
-// only read):
+// Per batch of rows (tu_recommend.hip: rec_shelves_run, a BatchFrame over the item columns and a SelectStage over val),
+// between the exclusions and the next batch's score tiles (the batch buffer sc [rows][columns] is only read):
 //   shelf_value_short_kernel  categories of m <= 64 columns, in quota_short_kernel's geometry: a category is a group of
 //                             w = the next power of two >= m lanes, 64 / w categories of one width to a wave.  A lane
 //                             holds one column's (score, column) and finds its rank among the finite ones of its group

@@ -1,6 +1,9 @@
 // tu_recommend.hip -- translation unit of the serving queries: the host side of the sessions and queries whose kernels
-// live in the headers below.  Every top-N query goes through the same batches and selection (top_n_device); the integer
-// planning of the queries is serve_plan.hpp.
+// live in the headers below.  Every batched query runs in one frame (BatchFrame: the ids, the batch buffer, the loop, the
+// event pair) and selects through one stage (SelectStage: the split's scratch and launches); a top-N query is the two
+// together (top_n_device) and ends in one read-back (top_n_copy_out).  The round-based queries keep their round loops and
+// share the loop over a round's batches (for_batches), the tile grid and the seen exclusion (tile_grid, exclude_seen).
+// The integer planning of the queries is serve_plan.hpp.
 //   recommend.hpp  the recommend session: training items per user, the per-slot fold, scores, selection, positions
 //   similar.hpp    nearest items / users: a session of its own, the same batches and selection
 //   top_pairs.hpp  the m best pairs of the whole model: a query of the recommend session with kernels of its own
@@ -248,16 +251,25 @@ void recommend_add_items(mmsbm_hip_ctx *c, int32_t n_new, const double *eta, con
 
 namespace {
 
+// The grid of a kernel that writes a batch buffer in tiles: `cols` columns x `nb` rows, `tile` of each to a workgroup
+dim3 tile_grid(int cols, int nb, int tile = kRecTile) {
+  return dim3(static_cast<unsigned>((cols + tile - 1) / tile), static_cast<unsigned>((nb + tile - 1) / tile));
+}
+
+// -inf over the columns of sc [nb][ld] that `seen` (indexed by the rows' ids, device) leaves out; no lists: nothing
+void exclude_seen(hipStream_t st, const int32_t *ids, int nb, SeenLists seen, double *sc, size_t ld) {
+  if (seen.off) LAUNCH(rec_exclude_kernel, nb, kBlock, 0, st, ids, seen.off, seen.items, sc, ld);
+}
+
 // sc [nb][n_cols]: the scores of the rows ids[0 .. nb) (device) of table a (`slots` tables as doubles apart, [row][rank])
 // against the rows 0 .. n_cols - 1 of table b; seen (indexed by those ids): the columns set to -inf.  fma is commutative
 // in its factors, so the sides exchanged give (u, i) the same score bit for bit.
 void score_tiles(mmsbm_hip_ctx *c, const double *a, size_t as, const double *b, size_t bs, int n_cols, const int32_t *ids,
                  int nb, SeenLists seen, double *sc) {
   if (n_cols == 0) return;
-  const dim3 g(static_cast<unsigned>((n_cols + kRecTile - 1) / kRecTile), static_cast<unsigned>((nb + kRecTile - 1) / kRecTile));
-  LAUNCH(rec_score_kernel, g, kBlock, 0, c->stream, a, as, b, bs, ids, nb, n_cols, c->rc->rank, c->rc->slots, sc,
-         static_cast<size_t>(n_cols));
-  if (seen.off) LAUNCH(rec_exclude_kernel, nb, kBlock, 0, c->stream, ids, seen.off, seen.items, sc, static_cast<size_t>(n_cols));
+  LAUNCH(rec_score_kernel, tile_grid(n_cols, nb), kBlock, 0, c->stream, a, as, b, bs, ids, nb, n_cols, c->rc->rank,
+         c->rc->slots, sc, static_cast<size_t>(n_cols));
+  exclude_seen(c->stream, ids, nb, seen, sc, static_cast<size_t>(n_cols));
 }
 
 // ... of one batch of users ub (rows of x) against the session's catalogue.  Shared by the selection and the positions.
@@ -269,8 +281,7 @@ void rec_score_batch(mmsbm_hip_ctx *c, const double *x, size_t xs, const int32_t
 // The query's own excluded items (catalogue.hpp) of the batch that begins at request row b0: own's lists are by
 // request row; col_of (device): every item's column of sc, or null where the columns are the items
 void own_exclude_batch(hipStream_t st, const DevCsr &own, int64_t b0, int nb, const int32_t *col_of, double *sc, size_t ld) {
-  LAUNCH(cat_exclude_kernel, nb, kBlock, 0, st, static_cast<const int32_t *>(nullptr), static_cast<int>(b0),
-         static_cast<const int32_t *>(own.off.ptr), static_cast<const int32_t *>(own.val.ptr), col_of, sc, ld);
+  LAUNCH(cat_exclude_kernel, nb, kBlock, 0, st, nullptr, static_cast<int>(b0), own.off.ptr, own.val.ptr, col_of, sc, ld);
 }
 
 // Every row of a top-N answer as "no candidate": counts 0, ids -1, values -inf
@@ -301,76 +312,124 @@ struct NoBatchStage {
   void operator()(const TopNDev &, int, int64_t) const {}
 };
 
-// The selection of one batch: the n best of every row of sc [nb][I] to os / oi [row * n + k], k < on[row]; the columns
-// split into `parts` parts of `per` (item_parts) whose lists cs / ci / cn [nb * parts ...] are then merged
-void select_batch(hipStream_t st, const double *sc, int I, int nb, int parts, int per, int n, double *cs, int32_t *ci,
-                  int32_t *cn, double *os, int32_t *oi, int32_t *on) {
-  const auto [cap, lds] = select_list(n);
-  if (parts > 1) {
-    LAUNCH(rec_select_kernel<false>, dim3(parts, nb), kRecWave, lds, st, sc, static_cast<size_t>(I), I, per, nullptr,
-           nullptr, nullptr, 0, n, cap, cs, ci, cn);
-    LAUNCH(rec_select_kernel<true>, dim3(1, nb), kRecWave, lds, st, nullptr, 0, I, 0, cs, ci, cn, parts, n, cap, os, oi,
-           on);
-  } else {
-    LAUNCH(rec_select_kernel<false>, dim3(1, nb), kRecWave, lds, st, sc, static_cast<size_t>(I), I, I, nullptr, nullptr,
-           nullptr, 0, n, cap, os, oi, on);
-  }
+// The selection of a query's batches (serve_plan.hpp: SelectPlan): the items split across waves until about 32 selecting
+// waves per CU are in flight (the selection waits on its loads)
+SelectPlan select_plan(const mmsbm_hip_ctx *c, int cols, int64_t rows, int n) {
+  return SelectPlan(cols, rows, n, kRecMinPerPart, 32LL * c->n_cus);
 }
+
+// The selection stage: the scratch cs / ci / cn of the parts' lists -- sized for one plan, or for two that run in turn
+// over one scratch (recommend_allocate's two passes) -- and the launches of one batch
+struct SelectStage {
+  DevBuf<double> cs;
+  DevBuf<int32_t> ci, cn;
+  static size_t bytes(const SelectPlan &a, const SelectPlan &b = SelectPlan{}) {
+    return std::max(a.entries, b.entries) * 12 + std::max(a.lists, b.lists) * 4;
+  }
+  explicit SelectStage(const SelectPlan &a, const SelectPlan &b = SelectPlan{}) {
+    const size_t entries = std::max(a.entries, b.entries);
+    if (entries == 0) return;  // (one part: it selects straight into the result)
+    cs.alloc(entries);
+    ci.alloc(entries);
+    cn.alloc(std::max(a.lists, b.lists));
+  }
+  // the n best of every row of sc [nb][p.cols] to os / oi [row * n + k], k < on[row]; the lists of the parts, where the
+  // columns are split, are then merged
+  void run(hipStream_t st, const SelectPlan &p, const double *sc, int nb, int n, double *os, int32_t *oi, int32_t *on) const {
+    const auto [cap, lds] = select_list(n);
+    const int I = p.cols;
+    if (p.parts > 1) {
+      LAUNCH(rec_select_kernel<false>, dim3(p.parts, nb), kRecWave, lds, st, sc, static_cast<size_t>(I), I, p.per, nullptr,
+             nullptr, nullptr, 0, n, cap, cs.ptr, ci.ptr, cn.ptr);
+      LAUNCH(rec_select_kernel<true>, dim3(1, nb), kRecWave, lds, st, nullptr, 0, I, 0, cs.ptr, ci.ptr, cn.ptr, p.parts, n,
+             cap, os, oi, on);
+    } else {
+      LAUNCH(rec_select_kernel<false>, dim3(1, nb), kRecWave, lds, st, sc, static_cast<size_t>(I), I, I, nullptr, nullptr,
+             nullptr, 0, n, cap, os, oi, on);
+    }
+  }
+};
+
+// The batches of a request of n rows, bu at a time: body(b0, nb) for each in turn (they follow each other on the stream:
+// no host wait in between)
+template <class Body>
+void for_batches(int64_t n, int64_t bu, Body &&body) {
+  for (int64_t b0 = 0; b0 < n; b0 += bu) body(b0, static_cast<int>(std::min(bu, n - b0)));
+}
+
+// The frame of a batched query over a buffer of `cols` columns: the request's ids on the device, the buffer sc [bu][cols]
+// of one batch (rec_batch_users), and the event pair around the query's kernels
+struct BatchFrame {
+  const int cols;
+  const int64_t n_rows, bu;
+  DevBuf<int32_t> ids;
+  DevBuf<double> sc;
+  EventPair ev;
+  BatchFrame(int cols_, int64_t n_rows_) : cols(cols_), n_rows(n_rows_), bu(rec_batch_users(cols_, n_rows_)) {}
+  size_t bytes() const { return static_cast<size_t>(bu) * cols * sizeof(double) + static_cast<size_t>(n_rows) * 4; }
+  // the ids (host) uploaded and the buffer allocated, then `body(ub, nb, b0, sc)` for every batch -- request rows
+  // b0 .. b0 + nb, whose device ids are ub -- between the event pair's two records (recorded; not waited for)
+  template <class Body>
+  void run(hipStream_t st, const int32_t *host_ids, Body &&body) {
+    ids.alloc(static_cast<size_t>(n_rows));
+    sc.alloc(static_cast<size_t>(bu) * cols);
+    HIP_CHECK(hipMemcpyAsync(ids.ptr, host_ids, sizeof(int32_t) * n_rows, hipMemcpyHostToDevice, st));
+    ev.start(st);
+    for_batches(n_rows, bu, [&](int64_t b0, int nb) {
+      body(ids.ptr + b0, nb, b0, sc.ptr);
+      HIP_CHECK(hipGetLastError());
+    });
+    ev.stop(st);
+  }
+};
 
 // The batches of a top-N query over a buffer of `I` columns: rows ids[0 .. n_rows) (host ids); `fill(ub, nb, b0, sc)`
 // enqueues the kernels that write the values sc [nb][I] of the batch of request rows b0 .. b0 + nb, whose device ids
 // are ub (-inf: no candidate), then the N best of every row are selected (and merged when the columns are split across
 // waves).  `what` names the query in MMSBM_E_TOOLARGE.  Every row's result stays on the device: `then(dev, ev)` is
 // called once the last batch is enqueued, with the result and the event pair around the query's kernels (recorded; not
-// waited for) -- it copies the result out (top_n_copy_out) or enqueues a stage that reads it there (diverse.hpp);
-// `extra` bytes of device memory are what it will allocate.  n_users > 0.  `each(batch, nb, b0)` (default: nothing) is
-// called once a batch's selection is enqueued, with that batch's part of the result: a stage that needs what `fill` left
-// of the batch before the next batch overwrites it (explore.hpp).
+// waited for; options "recommend_ms", "similar_ms", "diverse_ms", ...) -- it copies the result out (top_n_copy_out) or
+// enqueues a stage that reads it there (diverse.hpp); `extra` bytes of device memory are what it will allocate.
+// n_users > 0.  `each(batch, nb, b0)` (default: nothing) is called once a batch's selection is enqueued, with that
+// batch's part of the result: a stage that needs what `fill` left of the batch before the next batch overwrites it
+// (explore.hpp).
 template <class Fill, class Then, class Each = NoBatchStage>
 void top_n_device(mmsbm_hip_ctx *c, int I, int64_t n_users, const int32_t *users, int n, const char *what, size_t extra,
                   Fill &&fill, Then &&then, Each &&each = Each{}) {
   hipStream_t st = c->stream;
-  const int64_t bu = rec_batch_users(I, n_users);
-  // items split across waves until about 32 selecting waves per CU are in flight (the selection waits on its loads)
-  const auto [parts, per] = item_parts(I, bu, 32LL * c->n_cus, kRecMinPerPart);
-  const size_t cand = parts > 1 ? static_cast<size_t>(bu) * parts * n : 0;
+  BatchFrame fr(I, n_users);
+  const SelectPlan sp = select_plan(c, I, fr.bu, n);
   const size_t outs = static_cast<size_t>(n_users) * n;
-  require_free_mem(static_cast<size_t>(bu) * I * sizeof(double) + cand * 12 + outs * 12 + static_cast<size_t>(n_users) * 8 +
-                       extra,
-                   what);
-  DevBuf<int32_t> du, ci, cn, oi, on;
-  DevBuf<double> sc, cs, os;
-  du.alloc(n_users);
-  sc.alloc(static_cast<size_t>(bu) * I);
-  if (parts > 1) {
-    cs.alloc(cand); ci.alloc(cand); cn.alloc(static_cast<size_t>(bu) * parts);
-  }
+  require_free_mem(fr.bytes() + sp.bytes() + outs * 12 + static_cast<size_t>(n_users) * 4 + extra, what);
+  const SelectStage sel(sp);
+  DevBuf<int32_t> oi, on;
+  DevBuf<double> os;
   os.alloc(outs); oi.alloc(outs); on.alloc(n_users);  // every user's result stays on the device until the end
-  HIP_CHECK(hipMemcpyAsync(du.ptr, users, sizeof(int32_t) * n_users, hipMemcpyHostToDevice, st));
-  EventPair ev;  // device time of the query's kernels (options "recommend_ms", "similar_ms", "diverse_ms")
-  ev.start(st);
-  for (int64_t b0 = 0; b0 < n_users; b0 += bu) {  // (batches follow each other on the stream: no host wait in between)
-    const int nb = static_cast<int>(std::min(bu, n_users - b0));
-    const int32_t *ub = du.ptr + b0;
+  fr.run(st, users, [&](const int32_t *ub, int nb, int64_t b0, double *sc) {
     double *obs = os.ptr + b0 * n;
     int32_t *obi = oi.ptr + b0 * n, *obn = on.ptr + b0;
-    fill(ub, nb, b0, sc.ptr);
-    select_batch(st, sc.ptr, I, nb, parts, per, n, cs.ptr, ci.ptr, cn.ptr, obs, obi, obn);
+    fill(ub, nb, b0, sc);
+    sel.run(st, sp, sc, nb, n, obs, obi, obn);
     each(TopNDev{obs, obi, obn}, nb, b0);
-    HIP_CHECK(hipGetLastError());
-  }
-  ev.stop(st);
-  then(TopNDev{os.ptr, oi.ptr, on.ptr}, ev);
+  });
+  then(TopNDev{os.ptr, oi.ptr, on.ptr}, fr.ev);
 }
 
-// The result of top_n_device to the host (rows blanked by top_n_blank), and the device time of its kernels to `timed`
+// A column of a query's buffer as an item id: the candidate list's entry, or (null: the columns are the items) itself
+inline int32_t item_of(const int32_t *cand, int32_t col) { return cand ? cand[col] : col; }
+
+// The result of top_n_device to the host (rows blanked by top_n_blank), and the device time of its kernels to `timed`.
+// cand (host; null: none): the ids are columns of that list and leave as its items.  dev_second / second (null: none): a
+// second value per place, [row * n + k] on the device as dev.os, to the host as the scores (explore.hpp's propensities).
 void top_n_copy_out(mmsbm_hip_ctx *c, const TopNDev &dev, EventPair &ev, int64_t n_users, int n, TimedCall timed,
-                    int32_t *items, double *scores, int32_t *counts) {
+                    int32_t *items, double *scores, int32_t *counts, const int32_t *cand = nullptr,
+                    const double *dev_second = nullptr, double *second = nullptr) {
   hipStream_t st = c->stream;
   const size_t outs = static_cast<size_t>(n_users) * n;
-  std::vector<double> hs(outs);
+  std::vector<double> hs(outs), h2(dev_second ? outs : 0);
   std::vector<int32_t> hi(outs), hn(static_cast<size_t>(n_users));
   HIP_CHECK(hipMemcpyAsync(hs.data(), dev.os, sizeof(double) * outs, hipMemcpyDeviceToHost, st));
+  if (dev_second) HIP_CHECK(hipMemcpyAsync(h2.data(), dev_second, sizeof(double) * outs, hipMemcpyDeviceToHost, st));
   HIP_CHECK(hipMemcpyAsync(hi.data(), dev.oi, sizeof(int32_t) * outs, hipMemcpyDeviceToHost, st));
   HIP_CHECK(hipMemcpyAsync(hn.data(), dev.on, sizeof(int32_t) * n_users, hipMemcpyDeviceToHost, st));
   HIP_CHECK(hipStreamSynchronize(st));
@@ -380,8 +439,9 @@ void top_n_copy_out(mmsbm_hip_ctx *c, const TopNDev &dev, EventPair &ev, int64_t
     const int cnt = hn[static_cast<size_t>(b)];
     if (counts) counts[b] = cnt;
     for (int k = 0; k < cnt; ++k) {
-      items[o + k] = hi[o + k];
+      items[o + k] = item_of(cand, hi[o + k]);
       if (scores) scores[o + k] = hs[o + k];
+      if (dev_second && second) second[o + k] = h2[o + k];
     }
   }
 }
@@ -424,14 +484,11 @@ struct QuotaMask {
     const int waves = static_cast<int>(plan.wave_first.size());
     if (waves > 0)
       LAUNCH(quota_short_kernel, dim3(static_cast<unsigned>((waves + kQuotaWaves - 1) / kQuotaWaves), nb), kBlock, 0, st,
-             static_cast<const int32_t *>(wave_first.ptr), static_cast<const int32_t *>(wave_info.ptr), waves,
-             static_cast<const int32_t *>(off.ptr), static_cast<const int32_t *>(col.ptr),
-             static_cast<const int32_t *>(cap.ptr), sc, ld);
+             wave_first.ptr, wave_info.ptr, waves, off.ptr, col.ptr, cap.ptr, sc, ld);
     if (plan.n_long() > 0) {
       const auto [places, lds] = select_list(plan.long_cap);
-      LAUNCH(quota_long_kernel, dim3(static_cast<unsigned>(plan.n_long()), nb), kRecWave, lds, st,
-             static_cast<const int32_t *>(off.ptr), static_cast<const int32_t *>(col.ptr),
-             static_cast<const int32_t *>(cap.ptr), plan.n_short, places, sc, ld);
+      LAUNCH(quota_long_kernel, dim3(static_cast<unsigned>(plan.n_long()), nb), kRecWave, lds, st, off.ptr, col.ptr, cap.ptr,
+             plan.n_short, places, sc, ld);
     }
   }
 };
@@ -442,6 +499,10 @@ struct CatTable {
   DevBuf<int32_t> cand, col;  // [C]; [items of the catalogue]
   DevBuf<double> y;           // [slot][C][rank]
   float ms = 0.f;
+  // the device memory of the table of cand[0 .. C) (null: no table)
+  static size_t bytes(const RecSession &rc, const int32_t *cand, int C) {
+    return cand ? static_cast<size_t>(rc.slots) * C * rc.rank * sizeof(double) + (static_cast<size_t>(C) + rc.items) * 4 : 0;
+  }
 };
 
 // cand[0 .. C) (host; ascending, distinct ids of the session's catalogue) -> t (the memory was found free by the caller)
@@ -482,14 +543,13 @@ struct WithinPrep {
 void within_prepare(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *cand, int n_cand, const int64_t *xoff,
                     const int32_t *xit, WithinPrep &w) {
   const RecSession &rc = *c->rc;
-  const int NI = rc.items, rank = rc.rank, S = rc.slots;
+  const int NI = rc.items, rank = rc.rank;
   w.C = cand ? n_cand : NI;
   w.has_cand = cand != nullptr;
   w.has_own = xoff != nullptr;
   const size_t ycs = static_cast<size_t>(w.C) * rank;
   if (cand || xoff)
-    require_free_mem((cand ? S * ycs * sizeof(double) + (static_cast<size_t>(w.C) + NI) * 4 : 0) +
-                         (static_cast<size_t>(n_users) + 1 + DevCsr::entries(xoff, n_users)) * 4,
+    require_free_mem(CatTable::bytes(rc, cand, w.C) + (static_cast<size_t>(n_users) + 1 + DevCsr::entries(xoff, n_users)) * 4,
                      "recommend: the candidates' rows and the query's excluded items");
   if (xoff) w.own.upload(xoff, xit, n_users, c->stream);
   if (cand) cat_table(c, cand, w.C, w.ct);
@@ -499,19 +559,17 @@ void within_prepare(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *cand, int 
 
 // The values sc [nb][C] of the batch of request rows b0 .. b0 + nb (device ids ub): `tiles`, then -inf over what `seen`
 // leaves out for the rows' ids and over the query's own excluded items.  The one copy of these launches: the `fill` of
-// rec_within_device and the batch loop of rec_shelves_run both call it.
+// rec_within_device and the batches of rec_shelves_run and recommend_list_propensity call it.
 template <class Tiles>
 void within_fill(mmsbm_hip_ctx *c, const WithinPrep &w, Tiles &&tiles, SeenLists seen, const int32_t *ub, int nb,
                  int64_t b0, double *sc) {
   hipStream_t st = c->stream;
   const int C = w.C;
   tiles(w.y, w.ys, C, ub, nb, sc);
-  if (seen.off) {
-    if (w.has_cand)
-      LAUNCH(cat_exclude_kernel, nb, kBlock, 0, st, ub, 0, seen.off, seen.items, w.ct.col.ptr, sc, static_cast<size_t>(C));
-    else
-      LAUNCH(rec_exclude_kernel, nb, kBlock, 0, st, ub, seen.off, seen.items, sc, static_cast<size_t>(C));
-  }
+  if (!w.has_cand)
+    exclude_seen(st, ub, nb, seen, sc, static_cast<size_t>(C));
+  else if (seen.off)
+    LAUNCH(cat_exclude_kernel, nb, kBlock, 0, st, ub, 0, seen.off, seen.items, w.ct.col.ptr, sc, static_cast<size_t>(C));
   if (w.has_own) own_exclude_batch(st, w.own, b0, nb, w.ct.col.ptr, sc, static_cast<size_t>(C));
 }
 
@@ -550,8 +608,7 @@ auto rec_tiles(mmsbm_hip_ctx *c, const double *x, size_t xs) {
   };
 }
 
-// rec_within_device with the result copied to the host (top_n_blank done by the caller) and the columns mapped to item
-// ids there; the device time of the query's kernels goes to `timed`.  No column or no row: every row stays empty.
+// rec_within_device with the result copied to the host (top_n_blank done by the caller), the columns as item ids; the device time of the query's kernels goes to `timed`.  No column or no row: every row stays empty.
 template <class Tiles>
 void rec_within_run(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, SeenLists seen, const int32_t *cand,
                     int n_cand, const int64_t *xoff, const int32_t *xit, int n, Tiles &&tiles, TimedCall timed,
@@ -560,13 +617,10 @@ void rec_within_run(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, See
   if ((cand ? n_cand : c->rc->items) == 0 || n_users == 0) return;
   rec_within_device(c, n_users, users, seen, cand, n_cand, xoff, xit, n, 0, tiles,
                     [&](const TopNDev &dev, EventPair &ev, const int32_t *, float prep_ms) {
-                      top_n_copy_out(c, dev, ev, n_users, n, timed, items, scores, counts);
+                      top_n_copy_out(c, dev, ev, n_users, n, timed, items, scores, counts, cand);
                       c->last_ms[timed] += prep_ms;
                     },
                     quota);
-  if (cand)  // columns -> item ids
-    for (size_t e = 0; e < static_cast<size_t>(n_users) * n; ++e)
-      if (items[e] >= 0) items[e] = cand[items[e]];
 }
 
 // The capped categories of a query (quota.hpp): cat_items[cat_off[g] .. cat_off[g + 1]) (host; catalogue ids, each
@@ -658,14 +712,11 @@ struct ShelfCats {
     const size_t G = static_cast<size_t>(plan.kept());
     if (waves > 0)
       LAUNCH(shelf_value_short_kernel, dim3(static_cast<unsigned>((waves + kQuotaWaves - 1) / kQuotaWaves), nb), kBlock, 0,
-             st, static_cast<const int32_t *>(wave_first.ptr), static_cast<const int32_t *>(wave_info.ptr), waves,
-             static_cast<const int32_t *>(off.ptr), static_cast<const int32_t *>(col.ptr),
-             static_cast<const int32_t *>(slot.ptr), depth, min_items, sc, ld, val, avail, G);
+             st, wave_first.ptr, wave_info.ptr, waves, off.ptr, col.ptr, slot.ptr, depth, min_items, sc, ld, val, avail, G);
     if (plan.n_long() > 0) {
       const auto [places, lds] = select_list(depth);
-      LAUNCH(shelf_value_long_kernel, dim3(static_cast<unsigned>(plan.n_long()), nb), kRecWave, lds, st,
-             static_cast<const int32_t *>(off.ptr), static_cast<const int32_t *>(col.ptr),
-             static_cast<const int32_t *>(slot.ptr), plan.n_short, depth, min_items, places, sc, ld, val, avail, G);
+      LAUNCH(shelf_value_long_kernel, dim3(static_cast<unsigned>(plan.n_long()), nb), kRecWave, lds, st, off.ptr, col.ptr,
+             slot.ptr, plan.n_short, depth, min_items, places, sc, ld, val, avail, G);
     }
   }
 };
@@ -701,10 +752,10 @@ bool shelves_begin(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *cand, int n
 }
 
 // A shelves query: rows users[0 .. n_users) (host ids, rows of x) within cand / xoff / xit as rec_within_device's, the
-// categories cats.  A batch loop of its own: per batch the score tiles and the exclusions (within_fill: the launches of
-// recommend_query_within), the value kernels, the selection over the value buffer and the chosen shelves' items, all
-// before the next batch overwrites the scores; every row's result stays on the device until the end.
-// `plan`: shelves_begin's, with at least one category.
+// categories cats.  The batches are a BatchFrame over the C item columns, the selection a stage over the G value columns:
+// per batch the score tiles and the exclusions (within_fill: the launches of recommend_query_within), the value kernels,
+// the selection over the value buffer and the chosen shelves' items, all before the next batch overwrites the scores;
+// every row's result stays on the device until the end.  `plan`: shelves_begin's, with at least one category.
 void rec_shelves_run(mmsbm_hip_ctx *c, const double *x, size_t xs, int64_t n_users, const int32_t *users, SeenLists seen,
                      const int32_t *cand, int n_cand, const int64_t *xoff, const int32_t *xit, ShelfPlan &&plan,
                      const ShelfAsk &ask, const ShelfOut &out) {
@@ -716,50 +767,36 @@ void rec_shelves_run(mmsbm_hip_ctx *c, const double *x, size_t xs, int64_t n_use
   WithinPrep w;
   within_prepare(c, n_users, cand, n_cand, xoff, xit, w);
   const int C = w.C;
-  const int64_t bu = rec_batch_users(C, n_users);  // (the item buffer decides: G <= C)
-  const auto [parts, per] = item_parts(G, bu, 32LL * c->n_cus, kRecMinPerPart);
-  const size_t cands = parts > 1 ? static_cast<size_t>(bu) * parts * ns : 0;
+  BatchFrame fr(C, n_users);  // (the item buffer decides the batch: G <= C)
+  const SelectPlan sp = select_plan(c, G, fr.bu, ns);
   const size_t rows_ns = static_cast<size_t>(n_users) * ns, outs = rows_ns * ps;
-  const size_t vals = static_cast<size_t>(bu) * G;
-  require_free_mem(static_cast<size_t>(bu) * C * sizeof(double) + vals * (ps == 0 ? 12 : 8) + cands * 12 +
-                       static_cast<size_t>(bu) * parts * 4 + rows_ns * 20 + outs * 12 + static_cast<size_t>(n_users) * 8,
+  const size_t vals = static_cast<size_t>(fr.bu) * G;
+  require_free_mem(fr.bytes() + vals * (ps == 0 ? 12 : 8) + sp.bytes() + rows_ns * 20 + outs * 12 +
+                       static_cast<size_t>(n_users) * 4,
                    "recommend_shelves: a batch of users");
-  DevBuf<int32_t> du, ci, cn, oi, on, oa, av, ic, in;
-  DevBuf<double> sc, val, cs, os, is;
-  du.alloc(n_users);
-  sc.alloc(static_cast<size_t>(bu) * C);
+  const SelectStage sel(sp);
+  DevBuf<int32_t> oi, on, oa, av, ic, in;
+  DevBuf<double> val, os, is;
   val.alloc(vals);
   if (ps == 0) av.alloc(vals);
-  if (parts > 1) {
-    cs.alloc(cands); ci.alloc(cands); cn.alloc(static_cast<size_t>(bu) * parts);
-  }
   os.alloc(rows_ns); oi.alloc(rows_ns); oa.alloc(rows_ns); on.alloc(n_users);
   if (ps > 0) {
     is.alloc(outs); ic.alloc(outs); in.alloc(rows_ns);
   }
-  HIP_CHECK(hipMemcpyAsync(du.ptr, users, sizeof(int32_t) * n_users, hipMemcpyHostToDevice, st));
   const auto tiles = rec_tiles(c, x, xs);
-  const auto [places, lds] = select_list(std::max(ps, 1));
-  EventPair ev;  // device time of the query's kernels (option "recommend_ms")
-  ev.start(st);
-  for (int64_t b0 = 0; b0 < n_users; b0 += bu) {  // (batches follow each other on the stream: no host wait in between)
-    const int nb = static_cast<int>(std::min(bu, n_users - b0));
+  const std::pair<int, size_t> list = select_list(std::max(ps, 1));  // shelf_items_kernel's places and their LDS bytes
+  fr.run(st, users, [&](const int32_t *ub, int nb, int64_t b0, double *sc) {
     int32_t *obi = oi.ptr + b0 * ns, *obn = on.ptr + b0, *oba = oa.ptr + b0 * ns;
-    within_fill(c, w, tiles, seen, du.ptr + b0, nb, b0, sc.ptr);
-    sh.values(st, nb, sc.ptr, static_cast<size_t>(C), ask.depth, ask.min_items, val.ptr, av.ptr);
-    select_batch(st, val.ptr, G, nb, parts, per, ns, cs.ptr, ci.ptr, cn.ptr, os.ptr + b0 * ns, obi, obn);
+    within_fill(c, w, tiles, seen, ub, nb, b0, sc);
+    sh.values(st, nb, sc, static_cast<size_t>(C), ask.depth, ask.min_items, val.ptr, av.ptr);
+    sel.run(st, sp, val.ptr, nb, ns, os.ptr + b0 * ns, obi, obn);
     if (ps > 0)
-      LAUNCH(shelf_items_kernel, dim3(static_cast<unsigned>(ns), nb), kRecWave, lds, st, static_cast<const int32_t *>(obi),
-             static_cast<const int32_t *>(obn), static_cast<const int32_t *>(sh.of_slot.ptr),
-             static_cast<const int32_t *>(sh.off.ptr), static_cast<const int32_t *>(sh.col.ptr), ps, places,
-             static_cast<const double *>(sc.ptr), static_cast<size_t>(C), ic.ptr + b0 * ns * ps, is.ptr + b0 * ns * ps,
-             in.ptr + b0 * ns, oba);
+      LAUNCH(shelf_items_kernel, dim3(static_cast<unsigned>(ns), nb), kRecWave, list.second, st, obi, obn, sh.of_slot.ptr,
+             sh.off.ptr, sh.col.ptr, ps, list.first, sc, static_cast<size_t>(C), ic.ptr + b0 * ns * ps, is.ptr + b0 * ns * ps, in.ptr + b0 * ns,
+             oba);
     else
-      LAUNCH(shelf_avail_kernel, nb, kRecWave, 0, st, static_cast<const int32_t *>(obi), static_cast<const int32_t *>(obn),
-             ns, static_cast<const int32_t *>(av.ptr), static_cast<size_t>(G), oba);
-    HIP_CHECK(hipGetLastError());
-  }
-  ev.stop(st);
+      LAUNCH(shelf_avail_kernel, nb, kRecWave, 0, st, obi, obn, ns, av.ptr, static_cast<size_t>(G), oba);
+  });
   std::vector<double> hs(rows_ns), his(outs);
   std::vector<int32_t> hi(rows_ns), ha(rows_ns), hn(static_cast<size_t>(n_users)), hic(outs), hin(ps > 0 ? rows_ns : 0);
   HIP_CHECK(hipMemcpyAsync(hs.data(), os.ptr, sizeof(double) * rows_ns, hipMemcpyDeviceToHost, st));
@@ -772,7 +809,7 @@ void rec_shelves_run(mmsbm_hip_ctx *c, const double *x, size_t xs, int64_t n_use
     HIP_CHECK(hipMemcpyAsync(hin.data(), in.ptr, sizeof(int32_t) * rows_ns, hipMemcpyDeviceToHost, st));
   }
   HIP_CHECK(hipStreamSynchronize(st));
-  c->last_ms[T_RECOMMEND] = ev.ms() + w.ct.ms;
+  c->last_ms[T_RECOMMEND] = fr.ev.ms() + w.ct.ms;
   for (size_t b = 0; b < static_cast<size_t>(n_users); ++b) {
     const int cnt = hn[b];
     out.shelf_counts[b] = cnt;
@@ -784,7 +821,7 @@ void rec_shelves_run(mmsbm_hip_ctx *c, const double *x, size_t xs, int64_t n_use
       if (ps == 0) continue;
       out.item_counts[o] = hin[o];
       for (size_t e = 0; e < static_cast<size_t>(hin[o]); ++e) {
-        out.items[o * ps + e] = cand ? cand[hic[o * ps + e]] : hic[o * ps + e];  // columns -> item ids
+        out.items[o * ps + e] = item_of(cand, hic[o * ps + e]);
         out.scores[o * ps + e] = his[o * ps + e];
       }
     }
@@ -917,37 +954,20 @@ void recommend_query_explore(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *u
   const unsigned spans = static_cast<unsigned>((C + kExpSpan - 1) / kExpSpan);
   rec_within_device(
       c, n_users, users, rc.seen_lists(), cand, n_cand, xoff, xit, n, 0, rec_tiles(c, rc.x.ptr, rc.x_stride()),
-      [&](const TopNDev &dev, EventPair &ev, const int32_t *, float prep_ms) {
-        std::vector<double> hs(outs), hp(outs);
-        std::vector<int32_t> hi(outs), hn(static_cast<size_t>(n_users));
-        HIP_CHECK(hipMemcpyAsync(hs.data(), ps.ptr, sizeof(double) * outs, hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipMemcpyAsync(hp.data(), pp.ptr, sizeof(double) * outs, hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipMemcpyAsync(hi.data(), dev.oi, sizeof(int32_t) * outs, hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipMemcpyAsync(hn.data(), dev.on, sizeof(int32_t) * n_users, hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipStreamSynchronize(st));
-        c->last_ms[T_RECOMMEND] = ev.ms() + prep_ms;
-        for (int64_t b = 0; b < n_users; ++b) {
-          const size_t o = static_cast<size_t>(b) * n;
-          const int cnt = hn[static_cast<size_t>(b)];
-          if (counts) counts[b] = cnt;
-          for (int k = 0; k < cnt; ++k) {
-            items[o + k] = cand ? cand[hi[o + k]] : hi[o + k];  // columns -> item ids
-            if (scores) scores[o + k] = hs[o + k];
-            if (propensity) propensity[o + k] = hp[o + k];
-          }
-        }
+      [&](const TopNDev &dev, EventPair &ev, const int32_t *, float prep_ms) {  // the scores are `raw`'s, not the keys
+        top_n_copy_out(c, TopNDev{ps.ptr, dev.oi, dev.on}, ev, n_users, n, T_RECOMMEND, items, scores, counts, cand, pp.ptr,
+                       propensity);
+        c->last_ms[T_RECOMMEND] += prep_ms;
       },
       nullptr,
       [&](const WithinPrep &w, const int32_t *ub, int nb, double *sc) {
-        LAUNCH(explore_norm_kernel, nb, kBlock, 0, st, static_cast<const double *>(sc), ld, C, ub,
-               static_cast<const uint64_t *>(rng.tab.ptr), rng.st[0], rng.st[1], mx.ptr, base.ptr);
+        LAUNCH(explore_norm_kernel, nb, kBlock, 0, st, sc, ld, C, ub, rng.tab.ptr, rng.st[0], rng.st[1], mx.ptr, base.ptr);
         LAUNCH(explore_perturb_kernel, dim3(spans, static_cast<unsigned>(nb)), kBlock, 0, st, sc, raw.ptr, ld, C, w.dcand(),
-               static_cast<const uint64_t *>(rng.tab.ptr), static_cast<const uint64_t *>(base.ptr), rng.st[2], rng.st[3],
-               temperature);
+               rng.tab.ptr, base.ptr, rng.st[2], rng.st[3], temperature);
       },
       [&](const TopNDev &batch, int nb, int64_t b0) {
-        LAUNCH(explore_finish_kernel, nb, kRecWave, 0, st, raw.ptr, ld, C, static_cast<const double *>(mx.ptr), temperature,
-               static_cast<const int32_t *>(batch.oi), batch.on, n, ps.ptr + b0 * n, pp.ptr + b0 * n);
+        LAUNCH(explore_finish_kernel, nb, kRecWave, 0, st, raw.ptr, ld, C, mx.ptr, temperature, batch.oi, batch.on, n,
+               ps.ptr + b0 * n, pp.ptr + b0 * n);
       });
 }
 
@@ -969,41 +989,28 @@ void recommend_list_propensity(mmsbm_hip_ctx *c, int64_t n_users, const int32_t 
   hipStream_t st = c->stream;
   WithinPrep w;
   within_prepare(c, n_users, cand, n_cand, xoff, xit, w);
-  const int64_t bu = rec_batch_users(C, n_users);
+  BatchFrame fr(C, n_users);
   const size_t ld = static_cast<size_t>(C);
-  require_free_mem(static_cast<size_t>(bu) * ld * sizeof(double) + static_cast<size_t>(bu) * 8 +
-                       (2 * static_cast<size_t>(n_users) + 1) * 4 + total * 20,
+  require_free_mem(fr.bytes() + static_cast<size_t>(fr.bu) * 8 + (static_cast<size_t>(n_users) + 1) * 4 + total * 20,
                    "recommend_list_propensity: a batch of users and the lists");
-  DevBuf<int32_t> du;
-  DevBuf<double> sc, mx, os, op;
+  DevBuf<double> mx, os, op;
   DevCsr lists;
-  du.alloc(static_cast<size_t>(n_users));
-  sc.alloc(static_cast<size_t>(bu) * ld);
-  mx.alloc(static_cast<size_t>(bu));
+  mx.alloc(static_cast<size_t>(fr.bu));
   os.alloc(total);
   op.alloc(total);
   lists.upload(list_offsets, list_items, n_users, st);
-  HIP_CHECK(hipMemcpyAsync(du.ptr, users, sizeof(int32_t) * n_users, hipMemcpyHostToDevice, st));
   const auto tiles = rec_tiles(c, rc.x.ptr, rc.x_stride());
   const int32_t *col_of = w.has_cand ? w.ct.col.ptr : nullptr;
-  EventPair ev;  // device time of the call's kernels (option "recommend_ms")
-  ev.start(st);
-  for (int64_t b0 = 0; b0 < n_users; b0 += bu) {  // (batches follow each other on the stream)
-    const int nb = static_cast<int>(std::min(bu, n_users - b0));
-    within_fill(c, w, tiles, rc.seen_lists(), du.ptr + b0, nb, b0, sc.ptr);
-    LAUNCH(explore_norm_kernel, nb, kBlock, 0, st, static_cast<const double *>(sc.ptr), ld, C,
-           static_cast<const int32_t *>(du.ptr + b0), static_cast<const uint64_t *>(nullptr), uint64_t(0), uint64_t(0),
-           mx.ptr, static_cast<uint64_t *>(nullptr));
-    LAUNCH(explore_list_kernel, nb, kRecWave, 0, st, sc.ptr, ld, C, static_cast<const double *>(mx.ptr), temperature,
-           static_cast<const int32_t *>(lists.off.ptr + b0), static_cast<const int32_t *>(lists.val.ptr), col_of, os.ptr,
-           op.ptr);
-    HIP_CHECK(hipGetLastError());
-  }
-  ev.stop(st);
+  fr.run(st, users, [&](const int32_t *ub, int nb, int64_t b0, double *sc) {
+    within_fill(c, w, tiles, rc.seen_lists(), ub, nb, b0, sc);
+    LAUNCH(explore_norm_kernel, nb, kBlock, 0, st, sc, ld, C, ub, nullptr, uint64_t(0), uint64_t(0), mx.ptr, nullptr);
+    LAUNCH(explore_list_kernel, nb, kRecWave, 0, st, sc, ld, C, mx.ptr, temperature, lists.off.ptr + b0, lists.val.ptr, col_of,
+           os.ptr, op.ptr);
+  });
   if (scores) HIP_CHECK(hipMemcpyAsync(scores, os.ptr, sizeof(double) * total, hipMemcpyDeviceToHost, st));
   HIP_CHECK(hipMemcpyAsync(propensity, op.ptr, sizeof(double) * total, hipMemcpyDeviceToHost, st));
   HIP_CHECK(hipStreamSynchronize(st));
-  c->last_ms[T_RECOMMEND] = ev.ms() + w.ct.ms;
+  c->last_ms[T_RECOMMEND] = fr.ev.ms() + w.ct.ms;
 }
 
 void explore_noise(mmsbm_hip_ctx *c, const uint64_t state[4], int64_t n_pairs, const int32_t *users, const int32_t *items,
@@ -1024,9 +1031,8 @@ void explore_noise(mmsbm_hip_ctx *c, const uint64_t state[4], int64_t n_pairs, c
     const int64_t np = std::min(per, n_pairs - p0);
     HIP_CHECK(hipMemcpyAsync(du.ptr, users + p0, sizeof(int32_t) * np, hipMemcpyHostToDevice, st));
     HIP_CHECK(hipMemcpyAsync(di.ptr, items + p0, sizeof(int32_t) * np, hipMemcpyHostToDevice, st));
-    LAUNCH(explore_noise_kernel, static_cast<unsigned>((np + kBlock - 1) / kBlock), kBlock, 0, st,
-           static_cast<const uint64_t *>(rng.tab.ptr), rng.st[0], rng.st[1], rng.st[2], rng.st[3],
-           static_cast<const int32_t *>(du.ptr), static_cast<const int32_t *>(di.ptr), np, dr.ptr, dg.ptr);
+    LAUNCH(explore_noise_kernel, static_cast<unsigned>((np + kBlock - 1) / kBlock), kBlock, 0, st, rng.tab.ptr, rng.st[0],
+           rng.st[1], rng.st[2], rng.st[3], du.ptr, di.ptr, np, dr.ptr, dg.ptr);
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipMemcpyAsync(r + p0, dr.ptr, sizeof(double) * np, hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipMemcpyAsync(g + p0, dg.ptr, sizeof(double) * np, hipMemcpyDeviceToHost, st));
@@ -1249,8 +1255,7 @@ void recommend_top_pairs_bulk(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *
                        static_cast<uint32_t>(bins - 1)};
     HIP_CHECK(hipMemsetAsync(hist.ptr, 0, sizeof(unsigned long long) * 2 * plan.bins, st));
     LAUNCH(pbulk_tile_kernel<false>, G, kBlock, sizeof(uint32_t) * bins, st, rc.x.ptr, xs, rc.y.ptr, ys, du.ptr, nb, I, rank,
-           S, d, hist.ptr, static_cast<const int32_t *>(nullptr), static_cast<const int32_t *>(nullptr),
-           static_cast<uint64_t *>(nullptr), 0ull, static_cast<unsigned long long *>(nullptr));
+           S, d, hist.ptr, nullptr, nullptr, nullptr, 0ull, nullptr);
     if (seen.off)
       LAUNCH(pbulk_seen_kernel, seen_grid, kBlock, sizeof(uint32_t) * bins, st, rc.x.ptr, xs, rc.y.ptr, ys, du.ptr, nb, rank,
              S, d, seen.off, seen.items, hist.ptr + plan.bins);
@@ -1272,9 +1277,8 @@ void recommend_top_pairs_bulk(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *
     sorted.alloc(n);
     const PbulkDigit d{sel.prefix, sel.done_bits == 0 ? 1 : 0, sel.done_bits == 0 ? 0 : 64 - sel.done_bits, 0, 0u};
     HIP_CHECK(hipMemsetAsync(n_buf.ptr, 0, sizeof(unsigned long long), st));
-    LAUNCH(pbulk_tile_kernel<true>, G, kBlock, 0, st, rc.x.ptr, xs, rc.y.ptr, ys, du.ptr, nb, I, rank, S, d,
-           static_cast<unsigned long long *>(nullptr), seen.off, seen.items, buf.ptr, static_cast<unsigned long long>(n),
-           n_buf.ptr);
+    LAUNCH(pbulk_tile_kernel<true>, G, kBlock, 0, st, rc.x.ptr, xs, rc.y.ptr, ys, du.ptr, nb, I, rank, S, d, nullptr, seen.off,
+           seen.items, buf.ptr, static_cast<unsigned long long>(n), n_buf.ptr);
     HIP_CHECK(hipGetLastError());
     unsigned long long got = 0;
     HIP_CHECK(hipMemcpyAsync(&got, n_buf.ptr, sizeof got, hipMemcpyDeviceToHost, st));
@@ -1321,8 +1325,7 @@ void recommend_top_pairs_bulk(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *
       for (int g = 0; g < G; ++g) adm[g] = hg[g] + hg[static_cast<size_t>(G) + g];
     } else {
       LAUNCH(pbulk_emit_kernel<false>, G, kBlock, 0, st, rc.x.ptr, xs, rc.y.ptr, ys, du.ptr, nb, I, rank, S, acc_m, seen.off,
-             seen.items, static_cast<long long>(cut.row), static_cast<const int32_t *>(cut_item.ptr), g_adm,
-             static_cast<const long long *>(nullptr), static_cast<uint64_t *>(nullptr), static_cast<double *>(nullptr), 0ll);
+             seen.items, static_cast<long long>(cut.row), cut_item.ptr, g_adm, nullptr, nullptr, nullptr, 0ll);
       HIP_CHECK(hipGetLastError());
       HIP_CHECK(hipMemcpyAsync(adm.data(), g_adm, sizeof(long long) * G, hipMemcpyDeviceToHost, st));
       HIP_CHECK(hipStreamSynchronize(st));
@@ -1339,8 +1342,7 @@ void recommend_top_pairs_bulk(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *
     ok.alloc(n); os.alloc(n); fk.alloc(n); fs.alloc(n);
     HIP_CHECK(hipMemcpyAsync(g_base, base.data(), sizeof(long long) * G, hipMemcpyHostToDevice, st));
     LAUNCH(pbulk_emit_kernel<true>, G, kBlock, 0, st, rc.x.ptr, xs, rc.y.ptr, ys, du.ptr, nb, I, rank, S, acc_m, seen.off,
-           seen.items, static_cast<long long>(cut.row), static_cast<const int32_t *>(cut_item.ptr), g_adm,
-           static_cast<const long long *>(g_base), ok.ptr, os.ptr, static_cast<long long>(n));
+           seen.items, static_cast<long long>(cut.row), cut_item.ptr, g_adm, g_base, ok.ptr, os.ptr, static_cast<long long>(n));
     HIP_CHECK(hipGetLastError());
     // ---- phase 3: the order ----
     pairs_bulk_order(c, ok.ptr, os.ptr, n, fk.ptr, fs.ptr);
@@ -1426,15 +1428,11 @@ void recommend_allocate(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users,
   const size_t xs = rc.x_stride(), ys = static_cast<size_t>(NI) * rank;
   // user pass: batches of bu users over NI columns; item pass: batches of plan.bi capped items over U columns
   const int64_t bu = rec_batch_users(NI, n_users), bi = plan.bi;
-  const auto [uparts, uper] = item_parts(NI, bu, 32LL * c->n_cus, kRecMinPerPart);
-  const auto [iparts, iper] = NC > 0 ? item_parts(U, bi, 32LL * c->n_cus, kRecMinPerPart) : std::pair<int, int>{1, U};
   const int nsel = plan.most_n;
-  const size_t cand = std::max(uparts > 1 ? static_cast<size_t>(bu) * uparts * n : 0,
-                               iparts > 1 ? static_cast<size_t>(bi) * iparts * nsel : 0);
-  const size_t cparts = std::max(static_cast<size_t>(bu) * uparts, static_cast<size_t>(bi) * iparts);
+  const SelectPlan up = select_plan(c, NI, bu, n), ip = NC > 0 ? select_plan(c, U, bi, nsel) : SelectPlan{};
   const size_t buf = std::max(static_cast<size_t>(bu) * NI, static_cast<size_t>(bi) * U);
   const size_t outs = static_cast<size_t>(n_users) * n, lists = static_cast<size_t>(bi) * nsel;
-  require_free_mem(buf * sizeof(double) + cand * 12 + cparts * 4 + outs * 12 + static_cast<size_t>(n_users) * 8 +
+  require_free_mem(buf * sizeof(double) + SelectStage::bytes(up, ip) + outs * 12 + static_cast<size_t>(n_users) * 8 +
                        lists * 12 + static_cast<size_t>(bi) * 4 + (static_cast<size_t>(NI) + U) * 12 +
                        static_cast<size_t>(NC) * 9 + 4,
                    "recommend_allocate: a batch of scores, the users' lists and the items' keys");
@@ -1443,13 +1441,11 @@ void recommend_allocate(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users,
   std::vector<double> tau_h(static_cast<size_t>(NI), -INFINITY), sig_h(static_cast<size_t>(U), INFINITY);
   for (int32_t i : plan.closed) tau_h[static_cast<size_t>(i)] = INFINITY;
   const std::vector<int32_t> tau_uh(static_cast<size_t>(NI), -1), sig_ih(static_cast<size_t>(U), -1);
-  DevBuf<double> sc, cs, ps, ls, tau_s, sig_s;
-  DevBuf<int32_t> du, ci, cn, pi, pn, lu, ln, tau_u, sig_i, d_item, d_cap, d_total;
+  DevBuf<double> sc, ps, ls, tau_s, sig_s;
+  DevBuf<int32_t> du, pi, pn, lu, ln, tau_u, sig_i, d_item, d_cap, d_total;
   DevBuf<unsigned char> d_changed;
   sc.alloc(buf);
-  if (cand > 0) {
-    cs.alloc(cand); ci.alloc(cand); cn.alloc(cparts);
-  }
+  const SelectStage sel(up, ip);  // (the two passes follow each other: one scratch)
   ps.alloc(outs); pi.alloc(outs); pn.alloc(static_cast<size_t>(n_users));
   du.alloc(static_cast<size_t>(n_users));
   HIP_CHECK(hipMemcpyAsync(du.ptr, users, sizeof(int32_t) * n_users, hipMemcpyHostToDevice, st));
@@ -1464,45 +1460,34 @@ void recommend_allocate(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users,
   const SeenLists seen = rc.seen_lists();
   const SeenLists by_item{rc.excl ? rc.by_item_off.ptr : nullptr, rc.by_item.ptr};
   const unsigned row_blocks = static_cast<unsigned>((n_users + kBlock - 1) / kBlock);
-  auto tiles = [](int cols, int nb) {
-    return dim3(static_cast<unsigned>((cols + kRecTile - 1) / kRecTile), static_cast<unsigned>((nb + kRecTile - 1) / kRecTile));
-  };
   EventPair ev;  // device time of the whole call (option "allocate_ms"): the host's reads between the rounds included
   ev.start(st);
   int round = 0;
   bool done = false;
   while (!done) {
     ++round;
-    for (int64_t b0 = 0; b0 < n_users; b0 += bu) {  // the user pass
-      const int nb = static_cast<int>(std::min(bu, n_users - b0));
+    for_batches(n_users, bu, [&](int64_t b0, int nb) {  // the user pass
       const int32_t *ub = du.ptr + b0;
-      LAUNCH(alloc_score_kernel, tiles(NI, nb), kBlock, 0, st, rc.x.ptr, xs, rc.y.ptr, ys, ub, nb, NI, rank, rc.slots,
-             static_cast<const double *>(nullptr), static_cast<const int32_t *>(nullptr),
-             static_cast<const double *>(tau_s.ptr), static_cast<const int32_t *>(tau_u.ptr), sc.ptr, static_cast<size_t>(NI));
-      if (seen.off) LAUNCH(rec_exclude_kernel, nb, kBlock, 0, st, ub, seen.off, seen.items, sc.ptr, static_cast<size_t>(NI));
-      select_batch(st, sc.ptr, NI, nb, uparts, uper, n, cs.ptr, ci.ptr, cn.ptr, ps.ptr + b0 * n, pi.ptr + b0 * n, pn.ptr + b0);
-    }
+      LAUNCH(alloc_score_kernel, tile_grid(NI, nb), kBlock, 0, st, rc.x.ptr, xs, rc.y.ptr, ys, ub, nb, NI, rank, rc.slots,
+             nullptr, nullptr, tau_s.ptr, tau_u.ptr, sc.ptr, static_cast<size_t>(NI));
+      exclude_seen(st, ub, nb, seen, sc.ptr, static_cast<size_t>(NI));
+      sel.run(st, up, sc.ptr, nb, n, ps.ptr + b0 * n, pi.ptr + b0 * n, pn.ptr + b0);
+    });
     HIP_CHECK(hipGetLastError());
     if (NC == 0) break;  // (no cap binds: the answer is the user pass)
-    LAUNCH(alloc_sigma_kernel, row_blocks, kBlock, 0, st, static_cast<const int32_t *>(du.ptr), static_cast<int>(n_users), n,
-           static_cast<const double *>(ps.ptr), static_cast<const int32_t *>(pi.ptr), static_cast<const int32_t *>(pn.ptr),
+    LAUNCH(alloc_sigma_kernel, row_blocks, kBlock, 0, st, du.ptr, static_cast<int>(n_users), n, ps.ptr, pi.ptr, pn.ptr,
            sig_s.ptr, sig_i.ptr);
-    for (int64_t r0 = 0; r0 < NC; r0 += bi) {  // the item pass: the sides exchanged
-      const int nb = static_cast<int>(std::min(bi, NC - r0));
+    for_batches(NC, bi, [&](int64_t r0, int nb) {  // the item pass: the sides exchanged
       const int32_t *ib = d_item.ptr + r0;
       const int bn = plan.batch_n[static_cast<size_t>(r0 / bi)];
-      LAUNCH(alloc_score_kernel, tiles(U, nb), kBlock, 0, st, rc.y.ptr, ys, rc.x.ptr, xs, ib, nb, U, rank, rc.slots,
-             static_cast<const double *>(tau_s.ptr), static_cast<const int32_t *>(tau_u.ptr),
-             static_cast<const double *>(sig_s.ptr), static_cast<const int32_t *>(sig_i.ptr), sc.ptr, static_cast<size_t>(U));
-      if (by_item.off) LAUNCH(rec_exclude_kernel, nb, kBlock, 0, st, ib, by_item.off, by_item.items, sc.ptr, static_cast<size_t>(U));
-      select_batch(st, sc.ptr, U, nb, iparts, iper, bn, cs.ptr, ci.ptr, cn.ptr, ls.ptr, lu.ptr, ln.ptr);
-      LAUNCH(alloc_tau_kernel, static_cast<unsigned>((nb + kBlock - 1) / kBlock), kBlock, 0, st, ib,
-             static_cast<const int32_t *>(d_cap.ptr + r0), nb, bn, static_cast<const double *>(ls.ptr),
-             static_cast<const int32_t *>(lu.ptr), static_cast<const int32_t *>(ln.ptr), tau_s.ptr, tau_u.ptr,
-             d_changed.ptr + r0);
-    }
-    LAUNCH(alloc_changed_kernel, 1, kBlock, 0, st, static_cast<const unsigned char *>(d_changed.ptr), static_cast<int>(NC),
-           d_total.ptr);
+      LAUNCH(alloc_score_kernel, tile_grid(U, nb), kBlock, 0, st, rc.y.ptr, ys, rc.x.ptr, xs, ib, nb, U, rank, rc.slots,
+             tau_s.ptr, tau_u.ptr, sig_s.ptr, sig_i.ptr, sc.ptr, static_cast<size_t>(U));
+      exclude_seen(st, ib, nb, by_item, sc.ptr, static_cast<size_t>(U));
+      sel.run(st, ip, sc.ptr, nb, bn, ls.ptr, lu.ptr, ln.ptr);
+      LAUNCH(alloc_tau_kernel, static_cast<unsigned>((nb + kBlock - 1) / kBlock), kBlock, 0, st, ib, d_cap.ptr + r0, nb, bn,
+             ls.ptr, lu.ptr, ln.ptr, tau_s.ptr, tau_u.ptr, d_changed.ptr + r0);
+    });
+    LAUNCH(alloc_changed_kernel, 1, kBlock, 0, st, d_changed.ptr, static_cast<int>(NC), d_total.ptr);
     HIP_CHECK(hipGetLastError());
     int32_t changed = 0;
     HIP_CHECK(hipMemcpyAsync(&changed, d_total.ptr, sizeof(int32_t), hipMemcpyDeviceToHost, st));
@@ -1514,8 +1499,8 @@ void recommend_allocate(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users,
       done = true;
     }
   }
-  LAUNCH(alloc_cut_kernel, row_blocks, kBlock, 0, st, static_cast<const int32_t *>(du.ptr), static_cast<int>(n_users), n,
-         static_cast<const double *>(tau_s.ptr), static_cast<const int32_t *>(tau_u.ptr), ps.ptr, pi.ptr, pn.ptr);
+  LAUNCH(alloc_cut_kernel, row_blocks, kBlock, 0, st, du.ptr, static_cast<int>(n_users), n, tau_s.ptr, tau_u.ptr, ps.ptr,
+         pi.ptr, pn.ptr);
   HIP_CHECK(hipGetLastError());
   ev.stop(st);
   top_n_copy_out(c, TopNDev{ps.ptr, pi.ptr, pn.ptr}, ev, n_users, n, T_ALLOCATE, items, scores, counts);
@@ -1560,12 +1545,10 @@ void recommend_assign(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, c
   std::vector<int32_t> ids(nu);
   for (size_t r = 0; r < nu; ++r) ids[r] = users[at[r]];
   const int64_t bu = rec_batch_users(NI, n_users);
-  const std::pair<int, int> split = item_parts(NI, bu, 32LL * c->n_cus, kRecMinPerPart);
-  const int parts = split.first, per = split.second;
-  const size_t cand = parts > 1 ? static_cast<size_t>(bu) * parts * 2 : 0;
+  const SelectPlan sp = select_plan(c, NI, bu, 2);
   const int nblk = static_cast<int>((n_users + kBlock - 1) / kBlock);
   const size_t sort_bytes = assign_sort_bytes(nu);
-  require_free_mem(static_cast<size_t>(bu) * NI * sizeof(double) + cand * 12 + static_cast<size_t>(bu) * parts * 4 +
+  require_free_mem(static_cast<size_t>(bu) * NI * sizeof(double) + sp.bytes() +
                        nu * (2 * 8 + 2 * 4 + 2 * 12 + 4 + 3 * 4 + 2 * 8 + 2 * 4) + n_slots * 12 +
                        static_cast<size_t>(NI) * (3 * 8 + 2 * 4) + static_cast<size_t>(nblk) * 8 + sort_bytes + 4,
                    "recommend_assign: a batch of scores, the users' state, the bids and the items' slots");
@@ -1575,15 +1558,13 @@ void recommend_assign(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, c
     p1_h[static_cast<size_t>(i)] = q == 0 ? INFINITY : 0.0;
     p2_h[static_cast<size_t>(i)] = q < 0 || q >= 2 ? 0.0 : INFINITY;
   }
-  DevBuf<double> sc, cs, vs, row_paid, row_score, price, p1, p2, bid, bid_score, psum;
-  DevBuf<int32_t> du, ci, cn, vi, vn, row_item, dropped, holder, d_cap, d_off, act_r, act_u, bid_item, blk_cnt, blk_base,
+  DevBuf<double> sc, vs, row_paid, row_score, price, p1, p2, bid, bid_score, psum;
+  DevBuf<int32_t> du, vi, vn, row_item, dropped, holder, d_cap, d_off, act_r, act_u, bid_item, blk_cnt, blk_base,
       d_total;
   DevBuf<uint32_t> place, ord;
   DevBuf<char> tmp;
   sc.alloc(static_cast<size_t>(bu) * NI);
-  if (cand > 0) {
-    cs.alloc(cand); ci.alloc(cand); cn.alloc(static_cast<size_t>(bu) * parts);
-  }
+  const SelectStage sel(sp);
   vs.alloc(2 * nu); vi.alloc(2 * nu); vn.alloc(nu);
   du.upload(ids, st);
   act_u.upload(ids, st);  // the first round: every row is active
@@ -1609,13 +1590,16 @@ void recommend_assign(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, c
   HIP_CHECK(hipStreamSynchronize(st));  // (the uploads' host vectors are temporaries)
   const SeenLists seen = rc.seen_lists();
   const size_t accept_lds = static_cast<size_t>(plan.lds_places()) * (sizeof(double) + sizeof(int32_t));
-  // the values of rows ub[0 .. nb) at the prices p1, the exclusions, and the n best of every row to vs / vi / vn
-  auto value_pass = [&](const int32_t *ub, int nb, int n, size_t o0) {
-    const dim3 g(static_cast<unsigned>((NI + kRecTile - 1) / kRecTile), static_cast<unsigned>((nb + kRecTile - 1) / kRecTile));
-    LAUNCH(assign_value_kernel, g, kBlock, 0, st, rc.x.ptr, xs, rc.y.ptr, ys, ub, nb, NI, rank, rc.slots,
-           static_cast<const double *>(p1.ptr), sc.ptr, static_cast<size_t>(NI));
-    if (seen.off) LAUNCH(rec_exclude_kernel, nb, kBlock, 0, st, ub, seen.off, seen.items, sc.ptr, static_cast<size_t>(NI));
-    select_batch(st, sc.ptr, NI, nb, parts, per, n, cs.ptr, ci.ptr, cn.ptr, vs.ptr + o0 * n, vi.ptr + o0 * n, vn.ptr + o0);
+  // the values of the rows ids[0 .. n_rows) (device) at the prices p1, the exclusions, and the n best of every row to
+  // vs / vi / vn, batch by batch
+  auto value_pass = [&](const int32_t *ids, int64_t n_rows, int n) {
+    for_batches(n_rows, bu, [&](int64_t b0, int nb) {
+      const int32_t *ub = ids + b0;
+      LAUNCH(assign_value_kernel, tile_grid(NI, nb), kBlock, 0, st, rc.x.ptr, xs, rc.y.ptr, ys, ub, nb, NI, rank, rc.slots,
+             p1.ptr, sc.ptr, static_cast<size_t>(NI));
+      exclude_seen(st, ub, nb, seen, sc.ptr, static_cast<size_t>(NI));
+      sel.run(st, sp, sc.ptr, nb, n, vs.ptr + b0 * n, vi.ptr + b0 * n, vn.ptr + b0);
+    });
   };
   EventPair ev;  // device time of the whole call (option "assign_ms"): the host's reads between the rounds included
   ev.start(st);
@@ -1628,26 +1612,20 @@ void recommend_assign(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, c
     }
     ++round;
     active_sum += na;
-    for (int64_t b0 = 0; b0 < na; b0 += bu)
-      value_pass(act_u.ptr + b0, static_cast<int>(std::min(bu, na - b0)), 2, static_cast<size_t>(b0));
+    value_pass(act_u.ptr, na, 2);
     const int n_act = static_cast<int>(na);
     LAUNCH(assign_bid_kernel, static_cast<unsigned>((na + kBlock - 1) / kBlock), kBlock, 0, st, rc.x.ptr, xs, rc.y.ptr, ys,
-           rank, rc.slots, static_cast<const int32_t *>(act_u.ptr), static_cast<const int32_t *>(act_r.ptr), n_act,
-           static_cast<const double *>(vs.ptr), static_cast<const int32_t *>(vi.ptr), static_cast<const int32_t *>(vn.ptr),
-           static_cast<const double *>(p1.ptr), static_cast<const double *>(p2.ptr), reserve, eps, bid_item.ptr, bid.ptr,
-           bid_score.ptr, place.ptr, dropped.ptr);
+           rank, rc.slots, act_u.ptr, act_r.ptr, n_act, vs.ptr, vi.ptr, vn.ptr, p1.ptr, p2.ptr, reserve, eps, bid_item.ptr,
+           bid.ptr, bid_score.ptr, place.ptr, dropped.ptr);
     assign_sort_bids(st, tmp.ptr, sort_bytes, bid_item.ptr, bid.ptr, place.ptr, ord.ptr, static_cast<size_t>(na));
-    LAUNCH(assign_accept_kernel, static_cast<unsigned>(NI), kRecWave, accept_lds, st, static_cast<const int32_t *>(d_cap.ptr),
-           static_cast<const int32_t *>(d_off.ptr), plan.lds_places(), static_cast<const int32_t *>(bid_item.ptr),
-           static_cast<const double *>(bid.ptr), static_cast<const double *>(bid_score.ptr),
-           static_cast<const uint32_t *>(ord.ptr), n_act, static_cast<const int32_t *>(act_r.ptr), price.ptr, holder.ptr,
-           p1.ptr, p2.ptr, row_item.ptr, row_paid.ptr, row_score.ptr);
-    LAUNCH(assign_count_kernel, static_cast<unsigned>(nblk), kBlock, 0, st, static_cast<const int32_t *>(row_item.ptr),
-           static_cast<const int32_t *>(dropped.ptr), static_cast<int>(n_users), blk_cnt.ptr);
-    LAUNCH(assign_scan_kernel, 1, kBlock, 0, st, static_cast<const int32_t *>(blk_cnt.ptr), nblk, blk_base.ptr, d_total.ptr);
-    LAUNCH(assign_list_kernel, static_cast<unsigned>(nblk), kBlock, 0, st, static_cast<const int32_t *>(row_item.ptr),
-           static_cast<const int32_t *>(dropped.ptr), static_cast<const int32_t *>(du.ptr), static_cast<int>(n_users),
-           static_cast<const int32_t *>(blk_base.ptr), act_r.ptr, act_u.ptr);
+    LAUNCH(assign_accept_kernel, static_cast<unsigned>(NI), kRecWave, accept_lds, st, d_cap.ptr, d_off.ptr, plan.lds_places(),
+           bid_item.ptr, bid.ptr, bid_score.ptr, ord.ptr, n_act, act_r.ptr, price.ptr, holder.ptr, p1.ptr, p2.ptr,
+           row_item.ptr, row_paid.ptr, row_score.ptr);
+    LAUNCH(assign_count_kernel, static_cast<unsigned>(nblk), kBlock, 0, st, row_item.ptr, dropped.ptr,
+           static_cast<int>(n_users), blk_cnt.ptr);
+    LAUNCH(assign_scan_kernel, 1, kBlock, 0, st, blk_cnt.ptr, nblk, blk_base.ptr, d_total.ptr);
+    LAUNCH(assign_list_kernel, static_cast<unsigned>(nblk), kBlock, 0, st, row_item.ptr, dropped.ptr, du.ptr,
+           static_cast<int>(n_users), blk_base.ptr, act_r.ptr, act_u.ptr);
     HIP_CHECK(hipGetLastError());
     int32_t next = 0;
     HIP_CHECK(hipMemcpyAsync(&next, d_total.ptr, sizeof(int32_t), hipMemcpyDeviceToHost, st));
@@ -1655,10 +1633,9 @@ void recommend_assign(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, c
     na = next;
   }
   // the certificate: every row's best value at the final prices
-  for (int64_t b0 = 0; b0 < n_users; b0 += bu)
-    value_pass(du.ptr + b0, static_cast<int>(std::min(bu, n_users - b0)), 1, static_cast<size_t>(b0));
-  LAUNCH(assign_price_sum_kernel, static_cast<unsigned>((NI + kBlock - 1) / kBlock), kBlock, 0, st,
-         static_cast<const int32_t *>(d_off.ptr), static_cast<const double *>(price.ptr), NI, psum.ptr);
+  value_pass(du.ptr, n_users, 1);
+  LAUNCH(assign_price_sum_kernel, static_cast<unsigned>((NI + kBlock - 1) / kBlock), kBlock, 0, st, d_off.ptr, price.ptr, NI,
+         psum.ptr);
   HIP_CHECK(hipGetLastError());
   ev.stop(st);
   std::vector<int32_t> h_item(nu), h_drop(nu), h_vn(nu);
@@ -1810,7 +1787,7 @@ void recommend_query_groups(mmsbm_hip_ctx *c, int64_t n_groups, const int64_t *o
   if (p.too_large())
     throw ApiError(MMSBM_E_TOOLARGE, "recommend_query_groups: " + std::to_string(p.n_blocks) + " blocks of member rows in one query");
   const size_t ycs = static_cast<size_t>(C) * rank, bs = static_cast<size_t>(G) * rank;
-  require_free_mem((cand ? S * ycs * sizeof(double) + (static_cast<size_t>(C) + NI) * 4 : 0) +
+  require_free_mem(CatTable::bytes(rc, cand, C) +
                        (p.rows.size() + 3 * p.info.size() + p.run_off.size() + 2 * p.cut_off.size() + 2 * static_cast<size_t>(G) + 1) * 4 +
                        (tiles ? static_cast<size_t>(p.most_frag) * C : S * bs) * sizeof(double),
                    "recommend_query_groups: the member rows, the groups' lists and the candidates' rows");
@@ -1880,7 +1857,7 @@ void recommend_query_groups(mmsbm_hip_ctx *c, int64_t n_groups, const int64_t *o
     const int cnt = tc[static_cast<size_t>(r)];
     if (counts) counts[p.at[r]] = cnt;
     for (int k = 0; k < cnt; ++k) {
-      items[o + k] = cand ? cand[ti[t + k]] : ti[t + k];
+      items[o + k] = item_of(cand, ti[t + k]);
       if (scores) scores[o + k] = ts[t + k];
     }
   }
@@ -1917,8 +1894,7 @@ void recommend_assortment(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *user
   const bool rounds = n_pick > 0 && C > 0;
   const size_t ycs = static_cast<size_t>(C) * rank;
   const size_t n_res = static_cast<size_t>(n_pick) + static_cast<size_t>(n_given);
-  require_free_mem((cand ? S * ycs * sizeof(double) + (static_cast<size_t>(C) + NI) * 4 : 0) +
-                       static_cast<size_t>(nu) * (4 + 8 + 4 + 8) + static_cast<size_t>(C) * 4 + n_res * 12 +
+  require_free_mem(CatTable::bytes(rc, cand, C) + static_cast<size_t>(nu) * (4 + 8 + 4 + 8) + static_cast<size_t>(C) * 4 + n_res * 12 +
                        (rounds ? p.part_doubles() * sizeof(double) + static_cast<size_t>(p.n_blk()) * 12 : 0) +
                        (n_given > 0 ? pg.part_doubles() * sizeof(double) : 0),
                    "recommend_assortment: the users' state, the runs' partial sums and the candidates' rows");
@@ -1966,19 +1942,16 @@ void recommend_assortment(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *user
                   double *out) {
     const dim3 g(tiles, static_cast<unsigned>(pl.runs));
     auto tile = [&](auto kernel) {
-      LAUNCH(kernel, g, kBlock, 0, st, rc.x.ptr, xs, yy, yys, static_cast<const int32_t *>(rows.ptr), nu,
-             static_cast<int>(pl.run_rows), ni, tile0, rank, S, level, static_cast<const double *>(best.ptr),
-             static_cast<const int32_t *>(served.ptr), seen.off, seen.items, cols, static_cast<const int32_t *>(d_stop), out,
-             static_cast<size_t>(pl.ld));
+      LAUNCH(kernel, g, kBlock, 0, st, rc.x.ptr, xs, yy, yys, rows.ptr, nu, static_cast<int>(pl.run_rows), ni, tile0, rank, S,
+             level, best.ptr, served.ptr, seen.off, seen.items, cols, d_stop, out, static_cast<size_t>(pl.ld));
     };
     if (mode == kAsrtBest) tile(asrt_gain_kernel<kAsrtBest>);
     else tile(asrt_gain_kernel<kAsrtReach>);
   };
   auto update = [&](int k, int item) {
     auto go = [&](auto kernel) {
-      LAUNCH(kernel, user_grid, kBlock, 0, st, rc.x.ptr, xs, rc.y.ptr, yfs, static_cast<const int32_t *>(rows.ptr), nu, rank,
-             S, level, k, item, static_cast<const int32_t *>(res_col.ptr), dcand, seen.off, seen.items,
-             static_cast<const int32_t *>(d_stop), best.ptr, served.ptr);
+      LAUNCH(kernel, user_grid, kBlock, 0, st, rc.x.ptr, xs, rc.y.ptr, yfs, rows.ptr, nu, rank, S, level, k, item, res_col.ptr,
+             dcand, seen.off, seen.items, d_stop, best.ptr, served.ptr);
     };
     if (mode == kAsrtBest) go(asrt_update_kernel<kAsrtBest>);
     else go(asrt_update_kernel<kAsrtReach>);
@@ -1994,8 +1967,8 @@ void recommend_assortment(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *user
   ev.start(st);
   for (int g = 0; g < n_given; ++g) {
     gain(pg, rc.y.ptr, yfs, NI, given[g] / kRecTile, 1u, nullptr, part_g.ptr);
-    LAUNCH(asrt_given_kernel, 1, kRecWave, 0, st, static_cast<const double *>(part_g.ptr), static_cast<size_t>(pg.ld),
-           static_cast<int>(pg.runs), given[g] % kRecTile, g, d_given);
+    LAUNCH(asrt_given_kernel, 1, kRecWave, 0, st, part_g.ptr, static_cast<size_t>(pg.ld), static_cast<int>(pg.runs),
+           given[g] % kRecTile, g, d_given);
     update(-1, given[g]);
   }
   HIP_CHECK(hipGetLastError());
@@ -2005,22 +1978,20 @@ void recommend_assortment(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *user
       const auto [col0, n_cols] = p.batch_cols(b, C);
       gain(p, y, ys, C, static_cast<int>(b * p.batch_tiles), static_cast<unsigned>((n_cols + kRecTile - 1) / kRecTile), dcand,
            part.ptr);
-      LAUNCH(asrt_join_kernel, static_cast<unsigned>((n_cols + kAsrtJoin - 1) / kAsrtJoin), kBlock, 0, st,
-             static_cast<const double *>(part.ptr), static_cast<size_t>(p.ld), static_cast<int>(p.runs),
-             static_cast<int>(col0), static_cast<int>(n_cols), static_cast<const int32_t *>(taken.ptr),
-             p.batch_blk[static_cast<size_t>(b)], static_cast<const int32_t *>(d_stop), blk_v.ptr, blk_i.ptr);
+      LAUNCH(asrt_join_kernel, static_cast<unsigned>((n_cols + kAsrtJoin - 1) / kAsrtJoin), kBlock, 0, st, part.ptr,
+             static_cast<size_t>(p.ld), static_cast<int>(p.runs), static_cast<int>(col0), static_cast<int>(n_cols), taken.ptr,
+             p.batch_blk[static_cast<size_t>(b)], d_stop, blk_v.ptr, blk_i.ptr);
     }
     mark();
-    LAUNCH(asrt_pick_kernel, 1, kBlock, 0, st, static_cast<const double *>(blk_v.ptr), static_cast<const int32_t *>(blk_i.ptr),
-           static_cast<int>(p.n_blk()), k, taken.ptr, res_col.ptr, res_gain.ptr, d_count, d_stop);
+    LAUNCH(asrt_pick_kernel, 1, kBlock, 0, st, blk_v.ptr, blk_i.ptr, static_cast<int>(p.n_blk()), k, taken.ptr, res_col.ptr,
+           res_gain.ptr, d_count, d_stop);
     mark();
     update(k, 0);
     HIP_CHECK(hipGetLastError());
   }
   mark();
   LAUNCH(asrt_finish_kernel, static_cast<unsigned>((std::max<size_t>(n_res, static_cast<size_t>(nu)) + kBlock - 1) / kBlock),
-         kBlock, 0, st, res_gain.ptr, static_cast<int>(n_res), mode == kAsrtBest, static_cast<const double *>(best.ptr),
-         static_cast<const int32_t *>(served.ptr), nu, S, score.ptr);
+         kBlock, 0, st, res_gain.ptr, static_cast<int>(n_res), mode == kAsrtBest, best.ptr, served.ptr, nu, S, score.ptr);
   HIP_CHECK(hipGetLastError());
   ev.stop(st);
   std::vector<int32_t> h_col(static_cast<size_t>(n_pick)), h_flags(2);
@@ -2041,7 +2012,7 @@ void recommend_assortment(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *user
   *count = cnt;
   if (rounds) *stop = h_flags[0];  // (0: all n_pick rounds ran)
   for (int k = 0; k < cnt; ++k) {
-    items[k] = cand ? cand[h_col[static_cast<size_t>(k)]] : h_col[static_cast<size_t>(k)];
+    items[k] = item_of(cand, h_col[static_cast<size_t>(k)]);
     gains[k] = h_gain[static_cast<size_t>(k)];
   }
   for (int g = 0; g < n_given; ++g) given_gains[g] = h_gain[static_cast<size_t>(n_pick) + g];
@@ -2058,9 +2029,8 @@ void recommend_query_ensemble(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *
   top_n_blank(n_users, n, items, scores, counts);
   rec_within_run(c, n_users, users, rc.seen_lists(), cand, n_cand, xoff, xit, n,
                  [&](const double *y, size_t ys, int C, const int32_t *ub, int nb, double *sc) {
-                   const dim3 g(static_cast<unsigned>((C + kEnsTile - 1) / kEnsTile), static_cast<unsigned>((nb + kEnsTile - 1) / kEnsTile));
                    auto tile = [&](auto kernel) {
-                     LAUNCH(kernel, g, kBlock, 0, c->stream, rc.x.ptr, rc.x_stride(), y, ys, ub, nb, C, rc.rank, rc.slots, risk, sc,
+                     LAUNCH(kernel, tile_grid(C, nb, kEnsTile), kBlock, 0, c->stream, rc.x.ptr, rc.x_stride(), y, ys, ub, nb, C, rc.rank, rc.slots, risk, sc,
                             static_cast<size_t>(C));
                    };
                    if (mode == MMSBM_HIP_ENSEMBLE_MIN) tile(ens_tile_kernel<kEnsMin>);
@@ -2152,9 +2122,7 @@ void similar_query(mmsbm_hip_ctx *c, int64_t n_rows, const int32_t *ids, int n, 
   hipStream_t st = c->stream;
   top_n_run(c, rows, n_rows, ids, n, "similar: a batch of query rows",
             [&](const int32_t *ub, int nb, int64_t, double *sc) {
-              const dim3 g(static_cast<unsigned>((rows + kSimTile - 1) / kSimTile),
-                           static_cast<unsigned>((nb + kSimTile - 1) / kSimTile));
-              LAUNCH(sim_dist_kernel, g, kBlock, 0, st, sm.q.ptr, static_cast<size_t>(rows) * W, sm.mf.ptr, ub, nb, rows,
+              LAUNCH(sim_dist_kernel, tile_grid(rows, nb, kSimTile), kBlock, 0, st, sm.q.ptr, static_cast<size_t>(rows) * W, sm.mf.ptr, ub, nb, rows,
                      W, S, denom, sc, static_cast<size_t>(rows));
             },
             T_SIMILAR, out_ids, distance, counts);
@@ -2234,8 +2202,7 @@ void recommend_diverse(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, 
             LAUNCH(div_ids_kernel, static_cast<unsigned>((static_cast<size_t>(nb) * pool + kBlock - 1) / kBlock), kBlock, 0,
                    st, dcand, n_cand, dev.on, static_cast<int>(nb), pool, dev.oi);
           LAUNCH(div_greedy_kernel, static_cast<unsigned>(nb), kDivWave, lds, st, sm.q.ptr,
-                 static_cast<size_t>(sm.rows) * sm.width, sm.mf.ptr, sm.width, sm.slots, sm.rows, denom, dev.os,
-                 static_cast<const int32_t *>(dev.oi), dev.on, pool, n, trade_off, ri.ptr, rs.ptr, rd.ptr, rn.ptr);
+                 static_cast<size_t>(sm.rows) * sm.width, sm.mf.ptr, sm.width, sm.slots, sm.rows, denom, dev.os, dev.oi, dev.on, pool, n, trade_off, ri.ptr, rs.ptr, rd.ptr, rn.ptr);
           HIP_CHECK(hipGetLastError());
           ev2.stop(st);
           const size_t o = static_cast<size_t>(b0) * n;  // (the kernel wrote the padding too: straight into the caller's rows)
@@ -2275,8 +2242,7 @@ void inform_add(mmsbm_hip_ctx *c) {  // the selected slot (the caller holds a On
   if (qs > 0) {
     LAUNCH(sim_profile_kernel, static_cast<unsigned>((qs + kBlock - 1) / kBlock), kBlock, 0, st, e.items, L, e.p, e.rs,
            e.ks, e.ls, qo, I, K, R);
-    LAUNCH(inf_entropy_kernel, static_cast<unsigned>((hs + kBlock - 1) / kBlock), kBlock, 0, st,
-           static_cast<const double *>(qo), ho, hs, R);
+    LAUNCH(inf_entropy_kernel, static_cast<unsigned>((hs + kBlock - 1) / kBlock), kBlock, 0, st, qo, ho, hs, R);
   }
   HIP_CHECK(hipGetLastError());
   HIP_CHECK(hipStreamSynchronize(st));
@@ -2319,12 +2285,9 @@ void inf_run(mmsbm_hip_ctx *c, const double *th, size_t ts, int64_t n_users, con
   const size_t hs = static_cast<size_t>(I) * K, qs = hs * R;
   top_n_run(c, I, n_users, users, n, "inform: a batch of users",
             [&](const int32_t *ub, int nb, int64_t b0, double *sc) {
-              const dim3 g(static_cast<unsigned>((I + kInfTile - 1) / kInfTile),
-                           static_cast<unsigned>((nb + kInfTile - 1) / kInfTile));
-              LAUNCH(inf_score_kernel, g, kBlock, 0, st, th, ts, static_cast<const double *>(inf.q.ptr), qs,
-                     static_cast<const double *>(inf.h.ptr), hs, ub, nb, I, K, R, S,
-                     static_cast<const uint8_t *>(dmask.ptr), sc, static_cast<size_t>(I));
-              if (seen.off) LAUNCH(rec_exclude_kernel, nb, kBlock, 0, st, ub, seen.off, seen.items, sc, static_cast<size_t>(I));
+              LAUNCH(inf_score_kernel, tile_grid(I, nb, kInfTile), kBlock, 0, st, th, ts, inf.q.ptr, qs, inf.h.ptr, hs, ub, nb, I,
+                     K, R, S, dmask.ptr, sc, static_cast<size_t>(I));
+              exclude_seen(st, ub, nb, seen, sc, static_cast<size_t>(I));
               if (xoff) own_exclude_batch(st, own, b0, nb, nullptr, sc, static_cast<size_t>(I));
             },
             T_INFORM, items, gains, counts);

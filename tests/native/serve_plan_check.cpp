@@ -40,6 +40,16 @@ static void check_batch(int I, int64_t n_users, int n_cus) {
     CHECK(int64_t(parts) * per >= I && int64_t(parts - 1) * per < I);
     if (bu >= targets[t]) CHECK(parts == 1);
     CHECK(parts <= ceil_div(I, min_pers[t]) && parts <= std::max<int64_t>(1, ceil_div(targets[t], bu)));
+    // the selection's plan: item_parts' split, and a scratch of n places per (row, part) exactly when the parts are merged
+    for (int n : {1, 2, 10, 1024}) {
+      const SelectPlan sp(I, bu, n, min_pers[t], targets[t]);
+      CHECK(sp.cols == I && sp.parts == parts && sp.per == per);
+      CHECK(int64_t(sp.parts) * sp.per >= I);
+      CHECK(sp.lists == size_t(bu) * size_t(parts));
+      CHECK((sp.entries == 0) == (sp.parts == 1));
+      if (sp.parts > 1) CHECK(sp.entries == sp.lists * size_t(n));
+      CHECK(sp.bytes() == 12 * sp.entries + 4 * size_t(bu) * size_t(parts));
+    }
   }
 }
 
@@ -66,6 +76,9 @@ static void check_batches() {
   CHECK(item_parts(5000, 3328, 8192, 1024) == std::make_pair(3, 1667));
   CHECK(item_parts(2049, 1, 8192, 1024) == std::make_pair(3, 683));
   CHECK(item_parts(2048, 1, 8192, 1024) == std::make_pair(2, 1024));
+  CHECK(SelectPlan(5000, 3, 10, 1024, 8192).bytes() == size_t(3 * 5 * 10 * 12 + 3 * 5 * 4));  // 5 parts of 1,000
+  CHECK(SelectPlan(129, 32768, 3, 1024, 8192).bytes() == size_t(32768 * 4));                 // one part: the counts alone
+  CHECK(SelectPlan().bytes() == 0 && SelectPlan().parts == 1);
   CHECK(select_list(256) == std::make_pair(512, size_t(6144)));
   CHECK(select_list(257) == std::make_pair(1024, size_t(12288)));
   CHECK(select_list(769) == std::make_pair(2048, size_t(24576)));

@@ -3,8 +3,9 @@ their expected table.
 
 A case opens one context, runs one query and closes the context (the library appends its launch counts to
 MMSBM_HIP_LAUNCH_LOG when a context is destroyed).  Recorded per case: the launch count per kernel name of this process
-since the case began, and a SHA-256 per output array.  The kernels use no atomics, so on one device type both are a
-function of the library alone.  The shapes are the smallest that take every branch of the queries' host side:
+since the case began, and a SHA-256 per output array.  The kernels use no atomics -- top_pairs_bulk's only for counts and
+for places that a sort then orders --, so on one device type both are a function of the library alone (two recordings of
+one commit are equal, case by case).  The shapes are the smallest that take every branch of the queries' host side:
 
   BASIC    exact_models.SPLIT[1]: 3 users over 5,000 items -- the selection splits across waves and merges
   WIDE     129 users over 70,000 items: a batch of the 128 MB score buffer holds 128 rows, so 129 rows are two batches
@@ -17,7 +18,9 @@ The table a commit gives is recorded with
 
 (--tree: the checkout whose mmsbm_amd is imported, e.g. a build of the parent commit; this file's own by default).  The
 committed table is the one of the commit BEFORE the queries' host side moved onto shared helpers and serve_plan.hpp: the
-refactor must not move an entry.
+refactor must not move an entry.  The cases from "quota" on were recorded before the queries added since then (quota,
+shelves, explore, allocate, assign, assortment, top_pairs_bulk, ensemble, the item side) moved onto one selection stage
+and one batch frame, with the library's sources as that commit's.
 """
 import argparse
 import hashlib
@@ -165,6 +168,68 @@ def _rng():
     return np.random.default_rng(21)
 
 
+def _cats(I):
+    """(offsets, items) of six disjoint categories of catalogue items: two long ones (the multiples of 4; 1 mod 4), a
+    short one of 50 and one of 5 even items (2 mod 4), a short one of 4 odd items (3 mod 4: no candidate of _cand) and
+    one of 2 (never full under _CAPS: quota drops it, as it drops the second long one, whose cap is n)."""
+    return csr([np.arange(0, I, 4), np.arange(2, I, I // 50)[:50], np.array([6, 10, 14, 18, 22]),
+                np.array([3, 7, 11, 15]), np.array([26, 30]), np.arange(1, I, 4)], dtype=np.int32)
+
+
+_CAPS = np.array([3, 1, 2, 1, 5, 10], dtype=np.int32)     # (n = 10: the last two never bind, so plan_quota drops them)
+
+
+def _state():
+    return np.random.PCG64(5)                              # the four state words of a fixed stream
+
+
+def _lists(shape):
+    rng = np.random.default_rng(12)
+    return csr([rng.choice(shape[1], s, replace=False) for s in (0, 1, 40)])
+
+
+def _allocate(caps_of, n, max_rounds=10000, rounds_at_least=1):
+    def query(em, shape):
+        items, scores, counts, info = em.recommend_allocate(_users(shape), n, caps_of(shape[1]), max_rounds=max_rounds)
+        assert info["rounds"] >= rounds_at_least and info["rounds"] == em.get_option("allocate_rounds"), info
+        return items, scores, counts, info["rounds"], info["converged"]
+    return query
+
+
+def _assign(max_rounds=10000, rounds_at_least=1):
+    def query(em, shape):
+        U, I = shape[:2]
+        caps = np.array([0, 1, 2, -1], dtype=np.int32)[np.arange(I) % 4]    # p1 / p2 take every initial value
+        out = em.recommend_assign(np.random.default_rng(13).permutation(U), caps, 0.0, 0.05, max_rounds=max_rounds)
+        assert out["rounds"] >= rounds_at_least, out["rounds"]
+        return [out[k] for k in ("items", "scores", "paid", "pi", "price", "price_sum", "load", "rounds", "converged",
+                                 "bids")]
+    return query
+
+
+def _assortment(mode, level):
+    def query(em, shape):
+        U, I = shape[:2]
+        users = np.random.default_rng(14).permutation(U)
+        items, gains, n, stop, s_items, s_scores, start = em.recommend_assortment(
+            users, 6, mode, level, given=[3, 10], candidates=np.arange(0, I, 3, dtype=np.int32))
+        assert n >= 2, (n, stop)
+        return items, gains, n, em.ASSORT_STOPS.index(stop), s_items, s_scores, start
+    return query
+
+
+def _top_pairs_bulk(em, shape):
+    em.set_option("pairs_bulk_collect", 256)               # (15,000 candidates: histogram passes, then a collected bin)
+    users, items, scores, count, info = em.recommend_top_pairs_bulk(2000)
+    return users, items, scores, count, info["bar"], info["above"], info["ties"], info["candidates"]
+
+
+def _pair_bar(em, shape):
+    em.set_option("pairs_bulk_collect", 256)
+    info = em.recommend_pair_bar(2000)
+    return info["bar"], info["above"], info["ties"], info["candidates"]
+
+
 CASES = {
     "recommend": _basic(lambda em, s: em.recommend_query(_users(s), 10)),
     "within-candidates": _basic(lambda em, s: em.recommend_query_within(_users(s), 10, candidates=_cand(s))),
@@ -191,6 +256,38 @@ CASES = {
     **{f"groups-{mode}-three-batches": _groups(mode, True) for mode in GROUP_MODES},
     "audience": (MID, ("recommend",), _audience),
     "diverse": (MID, ("recommend", "similar"), _diverse),
+    "quota": _basic(lambda em, s: em.recommend_query_quota(_users(s), 10, *_cats(s[1]), _CAPS)),
+    "quota-candidates": _basic(lambda em, s: em.recommend_query_quota(_users(s), 10, *_cats(s[1]), _CAPS, candidates=_cand(s),
+                                                                      exclude=own_lists(_rng(), s[0], s[1]))),
+    "theta-quota": _basic(lambda em, s: em.recommend_query_theta_quota(theta_rows(_rng(), s[5], 4, s[2]), 10, *_cats(s[1]),
+                                                                       _CAPS, seen=own_lists(_rng(), 4, s[1]))),
+    "shelves-items": _basic(lambda em, s: em.recommend_query_shelves(_users(s), *_cats(s[1]), 5, 1, 3, 4)),
+    "shelves-values": _basic(lambda em, s: em.recommend_query_shelves(_users(s), *_cats(s[1]), 5, 3, 3, 0, candidates=_cand(s),
+                                                                      exclude=own_lists(_rng(), s[0], s[1]))),
+    "theta-shelves": _basic(lambda em, s: em.recommend_query_theta_shelves(theta_rows(_rng(), s[5], 4, s[2]), *_cats(s[1]), 5,
+                                                                           1, 3, 4, seen=own_lists(_rng(), 4, s[1]))),
+    "two-batches-shelves": (WIDE, ("recommend",), lambda em, s: em.recommend_query_shelves(
+        _users(s), *_cats(s[1]), 5, 1, 3, 4, exclude=own_lists(_rng(), s[0], s[1]))),
+    "explore": _basic(lambda em, s: em.recommend_query_explore(_users(s), 10, 0.1, _state())),
+    "explore-candidates": _basic(lambda em, s: em.recommend_query_explore(_users(s), 10, 0.1, _state(), candidates=_cand(s),
+                                                                          exclude=own_lists(_rng(), s[0], s[1]))),
+    "two-batches-explore": (WIDE, ("recommend",), lambda em, s: em.recommend_query_explore(_users(s), 10, 0.1, _state())),
+    "list-propensity": _basic(lambda em, s: em.recommend_list_propensity(_users(s), _lists(s), 0.1, candidates=_cand(s))),
+    "allocate-free": _basic(_allocate(lambda I: np.full(I, -1, dtype=np.int32), 10)),
+    "allocate": (MID, ("recommend",), _allocate(lambda I: np.array([1, -1, 2, 0, 3, -1], dtype=np.int32)[np.arange(I) % 6], 10,
+                                                rounds_at_least=2)),
+    "allocate-wide": (WIDE, ("recommend",), _allocate(lambda I: (1 + np.arange(I) % 3).astype(np.int32), 10, max_rounds=3)),
+    "assign": (MID, ("recommend",), _assign(rounds_at_least=2)),
+    "assign-wide": (WIDE, ("recommend",), _assign(max_rounds=3)),
+    "assortment-best": (MID, ("recommend",), _assortment("best_score", 1.0)),
+    "assortment-reach": (MID, ("recommend",), _assortment("reach", 2.055)),   # (a bar that each round's item still reaches)
+    "top-pairs-bulk": _basic(_top_pairs_bulk),
+    "pair-bar": _basic(_pair_bar),
+    "ensemble-lcb": _basic(lambda em, s: em.recommend_query_ensemble(_users(s), 10, "lcb", risk=1.0, candidates=_cand(s),
+                                                                     exclude=own_lists(_rng(), s[0], s[1]))),
+    "ensemble-min": _basic(lambda em, s: em.recommend_query_ensemble(_users(s), 10, "min", candidates=_cand(s),
+                                                                     exclude=own_lists(_rng(), s[0], s[1]))),
+    "items": (MID, ("recommend",), lambda em, s: em.recommend_query_items(np.arange(0, s[1], 25, dtype=np.int32), 10)),
 }
 
 
