@@ -18,6 +18,21 @@ c_f32p = C.POINTER(C.c_float)
 c_intp = C.POINTER(C.c_int)
 c_u8p = C.POINTER(C.c_uint8)
 
+# the runs of arguments that travel together, under the header's parameter names
+CTX = [C.c_void_p]
+USERS = [C.c_int64, c_i32p]                  # n_users, users (also n_items, items / n_rows, ids / n_pairs, users)
+SUBSET = [C.c_int32, c_i32p]                 # n_cand, cand_items
+ROW_CSR = [c_i64p, c_i32p]                   # excl_offsets, excl_items (also seen_*, list_*, offsets + items)
+THETA_ROWS = [C.c_int64, c_f64p] + ROW_CSR   # n_users, theta, seen_offsets, seen_items
+TOP_N_OUT = [c_i32p, c_f64p, c_i32p]         # items, scores, counts
+CATEGORIES = [C.c_int64] + ROW_CSR           # n_cats, cat_offsets, cat_items
+SHELF_ASK = [C.c_int32] * 4                  # depth, min_items, n_shelves, per_shelf
+SHELF_OUT = [c_i32p, c_f64p, c_i32p, c_i32p] + TOP_N_OUT   # shelf_cats, shelf_values, shelf_available, shelf_counts,
+                                                           # items, scores, item_counts
+PCG64_STATE = [C.POINTER(C.c_uint64)]
+USER_QUERY = CTX + USERS + SUBSET + ROW_CSR  # the users / candidate subset / exclusion prefix
+THETA_QUERY = CTX + THETA_ROWS + SUBSET      # its counterpart for caller-given theta rows
+
 # name -> (restype, argtypes); every symbol include/mmsbm_hip.h declares
 SIGNATURES = {
     "mmsbm_hip_abi_version": (C.c_int, []),
@@ -53,70 +68,45 @@ SIGNATURES = {
     "mmsbm_hip_predict_finish": (C.c_int, [C.c_void_p, c_f64p, c_f64p]),
     "mmsbm_hip_recommend_begin": (C.c_int, [C.c_void_p, c_f64p, C.c_int]),
     "mmsbm_hip_recommend_add": (C.c_int, [C.c_void_p]),
-    "mmsbm_hip_recommend_query": (C.c_int, [C.c_void_p, C.c_int64, c_i32p, C.c_int32, c_i32p, c_f64p, c_i32p]),
+    "mmsbm_hip_recommend_query": (C.c_int, CTX + USERS + [C.c_int32] + TOP_N_OUT),
     "mmsbm_hip_recommend_end": (C.c_int, [C.c_void_p]),
-    "mmsbm_hip_recommend_query_theta": (C.c_int, [C.c_void_p, C.c_int64, c_f64p, c_i64p, c_i32p, C.c_int32, c_i32p,
-                                                  c_f64p, c_i32p]),
-    "mmsbm_hip_recommend_positions": (C.c_int, [C.c_void_p, C.c_int64, c_i32p, c_i64p, c_i32p, c_i32p, c_i32p]),
-    "mmsbm_hip_recommend_add_items": (C.c_int, [C.c_void_p, C.c_int32, c_f64p, c_i64p, c_i32p]),
-    "mmsbm_hip_recommend_top_pairs": (C.c_int, [C.c_void_p, C.c_int64, c_i32p, C.c_int32, c_i32p, c_i32p, c_f64p, c_i32p]),
-    "mmsbm_hip_recommend_top_pairs_bulk": (C.c_int, [C.c_void_p, C.c_int64, c_i32p, C.c_int64, c_i32p, c_i32p, c_f64p,
-                                                     c_i64p, c_f64p, c_i64p]),
-    "mmsbm_hip_recommend_pair_bar": (C.c_int, [C.c_void_p, C.c_int64, c_i32p, C.c_int64, c_f64p, c_i64p]),
-    "mmsbm_hip_recommend_query_items": (C.c_int, [C.c_void_p, C.c_int64, c_i32p, C.c_int32, c_i32p, c_f64p, c_i32p]),
-    "mmsbm_hip_recommend_allocate": (C.c_int, [C.c_void_p, C.c_int64, c_i32p, C.c_int32, c_i32p, C.c_int32, c_i32p,
-                                               c_f64p, c_i32p, c_i32p, c_i32p]),
+    "mmsbm_hip_recommend_query_theta": (C.c_int, CTX + THETA_ROWS + [C.c_int32] + TOP_N_OUT),
+    "mmsbm_hip_recommend_positions": (C.c_int, CTX + USERS + ROW_CSR + [c_i32p, c_i32p]),
+    "mmsbm_hip_recommend_add_items": (C.c_int, CTX + [C.c_int32, c_f64p] + ROW_CSR),
+    "mmsbm_hip_recommend_top_pairs": (C.c_int, CTX + USERS + [C.c_int32, c_i32p, c_i32p, c_f64p, c_i32p]),
+    "mmsbm_hip_recommend_top_pairs_bulk": (C.c_int, CTX + USERS + [C.c_int64, c_i32p, c_i32p, c_f64p, c_i64p, c_f64p, c_i64p]),
+    "mmsbm_hip_recommend_pair_bar": (C.c_int, CTX + USERS + [C.c_int64, c_f64p, c_i64p]),
+    "mmsbm_hip_recommend_query_items": (C.c_int, CTX + USERS + [C.c_int32] + TOP_N_OUT),
+    "mmsbm_hip_recommend_allocate": (C.c_int, CTX + USERS + [C.c_int32, c_i32p, C.c_int32] + TOP_N_OUT + [c_i32p, c_i32p]),
     "mmsbm_hip_recommend_assign": (C.c_int, [C.c_void_p, C.c_int64, c_i32p, c_i32p, C.c_double, C.c_double, C.c_int32,
                                              c_i32p, c_f64p, c_f64p, c_f64p, c_f64p, c_f64p, c_i32p, c_i32p, c_i32p]),
     "mmsbm_hip_recommend_audience": (C.c_int, [C.c_void_p, C.c_int64, c_i32p, C.c_double, C.c_int64, c_i64p, c_i32p,
                                               c_f64p]),
-    "mmsbm_hip_recommend_query_within": (C.c_int, [C.c_void_p, C.c_int64, c_i32p, C.c_int32, c_i32p, c_i64p, c_i32p,
-                                                   C.c_int32, c_i32p, c_f64p, c_i32p]),
-    "mmsbm_hip_recommend_query_theta_within": (C.c_int, [C.c_void_p, C.c_int64, c_f64p, c_i64p, c_i32p, C.c_int32,
-                                                         c_i32p, C.c_int32, c_i32p, c_f64p, c_i32p]),
-    "mmsbm_hip_recommend_query_quota": (C.c_int, [C.c_void_p, C.c_int64, c_i32p, C.c_int32, c_i32p, c_i64p, c_i32p,
-                                                  C.c_int64, c_i64p, c_i32p, c_i32p, C.c_int32, c_i32p, c_f64p,
-                                                  c_i32p]),
-    "mmsbm_hip_recommend_query_theta_quota": (C.c_int, [C.c_void_p, C.c_int64, c_f64p, c_i64p, c_i32p, C.c_int32,
-                                                        c_i32p, C.c_int64, c_i64p, c_i32p, c_i32p, C.c_int32, c_i32p,
-                                                        c_f64p, c_i32p]),
-    "mmsbm_hip_recommend_query_shelves": (C.c_int, [C.c_void_p, C.c_int64, c_i32p, C.c_int32, c_i32p, c_i64p, c_i32p,
-                                                    C.c_int64, c_i64p, c_i32p, C.c_int32, C.c_int32, C.c_int32,
-                                                    C.c_int32, c_i32p, c_f64p, c_i32p, c_i32p, c_i32p, c_f64p, c_i32p]),
-    "mmsbm_hip_recommend_query_theta_shelves": (C.c_int, [C.c_void_p, C.c_int64, c_f64p, c_i64p, c_i32p, C.c_int32,
-                                                          c_i32p, C.c_int64, c_i64p, c_i32p, C.c_int32, C.c_int32,
-                                                          C.c_int32, C.c_int32, c_i32p, c_f64p, c_i32p, c_i32p, c_i32p,
-                                                          c_f64p, c_i32p]),
-    "mmsbm_hip_recommend_query_explore": (C.c_int, [C.c_void_p, C.c_int64, c_i32p, C.c_int32, c_i32p, c_i64p, c_i32p,
-                                                    C.c_int32, C.c_double, C.POINTER(C.c_uint64), c_i32p, c_f64p,
-                                                    c_f64p, c_i32p]),
-    "mmsbm_hip_recommend_list_propensity": (C.c_int, [C.c_void_p, C.c_int64, c_i32p, C.c_int32, c_i32p, c_i64p, c_i32p,
-                                                      C.c_double, c_i64p, c_i32p, c_f64p, c_f64p]),
-    "mmsbm_hip_explore_noise": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_int64, c_i32p, c_i32p, c_f64p,
-                                          c_f64p]),
-    "mmsbm_hip_recommend_rank": (C.c_int, [C.c_void_p, C.c_int64, c_i32p, c_i64p, c_i32p, C.c_int32, c_i32p, c_f64p,
-                                           c_i32p]),
+    "mmsbm_hip_recommend_query_within": (C.c_int, USER_QUERY + [C.c_int32] + TOP_N_OUT),
+    "mmsbm_hip_recommend_query_theta_within": (C.c_int, THETA_QUERY + [C.c_int32] + TOP_N_OUT),
+    "mmsbm_hip_recommend_query_quota": (C.c_int, USER_QUERY + CATEGORIES + [c_i32p, C.c_int32] + TOP_N_OUT),
+    "mmsbm_hip_recommend_query_theta_quota": (C.c_int, THETA_QUERY + CATEGORIES + [c_i32p, C.c_int32] + TOP_N_OUT),
+    "mmsbm_hip_recommend_query_shelves": (C.c_int, USER_QUERY + CATEGORIES + SHELF_ASK + SHELF_OUT),
+    "mmsbm_hip_recommend_query_theta_shelves": (C.c_int, THETA_QUERY + CATEGORIES + SHELF_ASK + SHELF_OUT),
+    "mmsbm_hip_recommend_query_explore": (C.c_int, USER_QUERY + [C.c_int32, C.c_double] + PCG64_STATE + [c_i32p, c_f64p, c_f64p, c_i32p]),
+    "mmsbm_hip_recommend_list_propensity": (C.c_int, USER_QUERY + [C.c_double] + ROW_CSR + [c_f64p, c_f64p]),
+    "mmsbm_hip_explore_noise": (C.c_int, CTX + PCG64_STATE + USERS + [c_i32p, c_f64p, c_f64p]),
+    "mmsbm_hip_recommend_rank": (C.c_int, CTX + USERS + ROW_CSR + [C.c_int32] + TOP_N_OUT),
     "mmsbm_hip_similar_begin": (C.c_int, [C.c_void_p, C.c_int]),
     "mmsbm_hip_similar_add": (C.c_int, [C.c_void_p]),
-    "mmsbm_hip_similar_query": (C.c_int, [C.c_void_p, C.c_int64, c_i32p, C.c_int32, c_i32p, c_f64p, c_i32p]),
+    "mmsbm_hip_similar_query": (C.c_int, CTX + USERS + [C.c_int32] + TOP_N_OUT),
     "mmsbm_hip_similar_end": (C.c_int, [C.c_void_p]),
     "mmsbm_hip_similar_pairs": (C.c_int, [C.c_void_p, C.c_int64, c_i32p, c_i32p, c_f64p]),
-    "mmsbm_hip_recommend_diverse": (C.c_int, [C.c_void_p, C.c_int64, c_i32p, C.c_int32, c_i32p, c_i64p, c_i32p,
-                                              C.c_int32, C.c_int32, C.c_double, c_i32p, c_f64p, c_f64p, c_i32p]),
-    "mmsbm_hip_recommend_query_groups": (C.c_int, [C.c_void_p, C.c_int64, c_i64p, c_i32p, C.c_int, C.c_double,
-                                                   C.c_int32, c_i32p, C.c_int32, c_i32p, c_f64p, c_i32p]),
-    "mmsbm_hip_recommend_assortment": (C.c_int, [C.c_void_p, C.c_int64, c_i32p, C.c_int, C.c_double, C.c_int32, c_i32p,
-                                                 C.c_int32, c_i32p, C.c_int32, c_i32p, c_f64p, c_i32p, c_i32p, c_f64p,
-                                                 c_i32p, c_f64p]),
-    "mmsbm_hip_recommend_query_ensemble": (C.c_int, [C.c_void_p, C.c_int64, c_i32p, C.c_int, C.c_double, C.c_int32,
-                                                     c_i32p, c_i64p, c_i32p, C.c_int32, c_i32p, c_f64p, c_i32p]),
+    "mmsbm_hip_recommend_diverse": (C.c_int, USER_QUERY + [C.c_int32, C.c_int32, C.c_double, c_i32p, c_f64p, c_f64p, c_i32p]),
+    "mmsbm_hip_recommend_query_groups": (C.c_int, CTX + [C.c_int64] + ROW_CSR + [C.c_int, C.c_double] + SUBSET + [C.c_int32] + TOP_N_OUT),
+    "mmsbm_hip_recommend_assortment": (C.c_int, CTX + USERS + [C.c_int, C.c_double] + SUBSET + SUBSET + [C.c_int32, c_i32p, c_f64p, c_i32p, c_i32p,
+                                                c_f64p, c_i32p, c_f64p]),
+    "mmsbm_hip_recommend_query_ensemble": (C.c_int, CTX + USERS + [C.c_int, C.c_double] + SUBSET + ROW_CSR + [C.c_int32] + TOP_N_OUT),
     "mmsbm_hip_recommend_pair_spread": (C.c_int, [C.c_void_p, C.c_int64, c_i32p, c_i32p, c_f64p, c_f64p]),
     "mmsbm_hip_inform_begin": (C.c_int, [C.c_void_p]),
     "mmsbm_hip_inform_add": (C.c_int, [C.c_void_p]),
-    "mmsbm_hip_inform_query": (C.c_int, [C.c_void_p, C.c_int64, c_i32p, C.c_int32, c_i32p, c_i64p, c_i32p, C.c_int,
-                                         C.c_int32, c_i32p, c_f64p, c_i32p]),
-    "mmsbm_hip_inform_query_theta": (C.c_int, [C.c_void_p, C.c_int64, c_f64p, c_i64p, c_i32p, C.c_int32, c_i32p,
-                                               C.c_int32, c_i32p, c_f64p, c_i32p]),
+    "mmsbm_hip_inform_query": (C.c_int, USER_QUERY + [C.c_int, C.c_int32] + TOP_N_OUT),
+    "mmsbm_hip_inform_query_theta": (C.c_int, THETA_QUERY + [C.c_int32] + TOP_N_OUT),
     "mmsbm_hip_inform_mean_theta": (C.c_int, [C.c_void_p, c_f64p]),
     "mmsbm_hip_inform_end": (C.c_int, [C.c_void_p]),
     "mmsbm_hip_overlap_begin": (C.c_int, [C.c_void_p, C.c_int]),
@@ -125,8 +115,7 @@ SIGNATURES = {
     "mmsbm_hip_overlap_end": (C.c_int, [C.c_void_p]),
     "mmsbm_hip_explain_begin": (C.c_int, [C.c_void_p, c_f64p]),
     "mmsbm_hip_explain_add": (C.c_int, [C.c_void_p]),
-    "mmsbm_hip_explain_query": (C.c_int, [C.c_void_p, C.c_int64, c_i32p, c_i64p, c_i32p, C.c_int32, c_i32p, c_i32p,
-                                         c_f64p, c_i32p, c_f64p, c_f64p, c_i32p]),
+    "mmsbm_hip_explain_query": (C.c_int, CTX + USERS + ROW_CSR + [C.c_int32, c_i32p, c_i32p, c_f64p, c_i32p, c_f64p, c_f64p, c_i32p]),
     "mmsbm_hip_explain_end": (C.c_int, [C.c_void_p]),
     "mmsbm_hip_loo_begin": (C.c_int, [C.c_void_p]),
     "mmsbm_hip_loo_add": (C.c_int, [C.c_void_p]),

@@ -135,7 +135,7 @@ def build_library(force: bool = False, verbose: bool = False) -> str:
 def build_diagnostic(out: str, defines=(), verbose: bool = False) -> str:
     """A diagnostic build of the whole library as ONE translation unit (csrc/unity.hip) with extra -D switches
     (MMSBM_STAMPS: phase stamps; MMSBM_ABLATE: phase ablation through mmsbm_hip_time_stage) -> `out`.  Never the
-    product: load it explicitly (mmsbm_amd._lib.load(path))."""
+    product: a process uses it by naming it in MMSBM_HIP_LIBRARY before mmsbm_amd._lib loads the library."""
     cmd = [hipcc_path(), *_compile_flags(source_id() + "-diag"), *[f"-D{d}" for d in defines], "-shared",
            "-Wl,-rpath,/opt/rocm/lib", "-o", out, os.path.join(CSRC, "unity.hip")]
     if verbose:

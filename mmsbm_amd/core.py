@@ -45,6 +45,35 @@ def _csr(lists, rows, name, noun):
     return off, val
 
 
+def _row_csr(lists, rows, name, noun):
+    """_csr of an optional list as the C ABI takes it: (offsets pointer, values pointer); null, null for None."""
+    off, val = _csr(lists, rows, name, noun)
+    return _p_or_null(off, C.c_int64), _p_or_null(val, C.c_int32)
+
+
+def _subset(candidates):
+    """(n_cand, cand_items) of an optional candidate subset; (0, null) for None, the whole catalogue."""
+    cand = None if candidates is None else _i32(candidates)
+    return 0 if cand is None else len(cand), _p_or_null(cand, C.c_int32)
+
+
+def _user_set(users, when_none):
+    """(n_users, users) of an optional user set; (when_none, null) for None, every training user."""
+    u = None if users is None else _i32(users)
+    return when_none if u is None else len(u), _p_or_null(u, C.c_int32)
+
+
+def _slot_blocks(values, name, expected, width, added):
+    """``values`` as float64 (S, rows, width), one block per slot a session holds ``added`` of; ``expected``: how the
+    refusal of another shape ends."""
+    a = _f64(values)
+    if a.ndim != 3 or a.shape[2] != width:
+        raise ValueError(f"{name} has shape {a.shape}, {expected}")
+    if a.shape[0] != added:
+        raise ValueError(f"{name} holds {a.shape[0]} blocks, the session {added} added slots")
+    return a
+
+
 def _fetch_i32(symbol, *head):
     """The int32 array of count-then-fill entry ``symbol(*head, out, capacity, count)``: asked for its length, then, if
     it has any, filled."""
@@ -379,28 +408,35 @@ class HipEM:
         """(items (M,n) int32 padded with -1, scores (M,n) padded with -inf, counts (M,)) for encoded user ids."""
         return self._top_n("mmsbm_hip_recommend_query", users, n)
 
+    def _theta_rows(self, theta, added):
+        """(theta as float64 (S, M, K), M) of caller-given users for a session that holds ``added`` slots."""
+        t = _slot_blocks(theta, "theta", f"expected (slots, users, {self.k})", self.k, added)
+        return t, t.shape[1]
+
+    def _theta_query(self, t, m, seen, candidates):
+        """The leading arguments of a query over the ``m`` theta rows ``t``: handle, rows, seen lists, candidate subset
+        (left out for None where the entry has none)."""
+        return (self._h, m, _p(t, C.c_double), *_row_csr(seen, m, "seen offsets", "items"), *_subset(candidates))
+
     def recommend_query_theta(self, theta, n, seen=None, candidates=None):
         """recommend_query for caller-given users: theta (S, M, K), one (M, K) block per added slot in add order.
         seen: None (nothing excluded) or (offsets (M+1,) int64, items int32): user b leaves out
         items[offsets[b]:offsets[b + 1]].  candidates: None (the whole catalogue) or ascending, distinct item ids of
         the session's catalogue, as in recommend_query_within."""
-        t = _f64(theta)
-        if t.ndim != 3 or t.shape[2] != self.k:
-            raise ValueError(f"theta has shape {t.shape}, expected (slots, users, {self.k})")
-        if t.shape[0] != self._rc_added:
-            raise ValueError(f"theta holds {t.shape[0]} blocks, the session {self._rc_added} added slots")
-        m, n = t.shape[1], int(n)
-        off, it = _csr(seen, m, "seen offsets", "items")
+        (t, m), n = self._theta_rows(theta, self._rc_added), int(n)
+        head = self._theta_query(t, m, seen, candidates)
         items, scores, counts = self._query_out(m, n)
-        head = (self._h, m, _p(t, C.c_double), _p_or_null(off, C.c_int64),
-                _p_or_null(it, C.c_int32))
         tail = (n, _p(items, C.c_int32), _p(scores, C.c_double), _p(counts, C.c_int32))
         if candidates is None:
-            _lib.call("mmsbm_hip_recommend_query_theta", *head, *tail)
+            _lib.call("mmsbm_hip_recommend_query_theta", *head[:-2], *tail)
         else:
-            cand = _i32(candidates)
-            _lib.call("mmsbm_hip_recommend_query_theta_within", *head, len(cand), _p(cand, C.c_int32), *tail)
+            _lib.call("mmsbm_hip_recommend_query_theta_within", *head, *tail)
         return items, scores, counts
+
+    def _user_query(self, u, candidates, exclude):
+        """The leading arguments of a query over the encoded users ``u``: handle, users, candidate subset, exclusions."""
+        return (self._h, len(u), _p(u, C.c_int32), *_subset(candidates),
+                *_row_csr(exclude, len(u), "exclude offsets", "items"))
 
     def recommend_query_within(self, users, n, candidates=None, exclude=None):
         """recommend_query within a part of the catalogue: the n best of ``candidates`` (ascending, distinct item ids
@@ -409,12 +445,8 @@ class HipEM:
         items[offsets[b]:offsets[b + 1]] (any order; a user asked twice may carry two lists).  Scores and order are
         recommend_query's: the answer is its row for n = all items, filtered and cut to n."""
         u, n = _i32(users), int(n)
-        cand = None if candidates is None else _i32(candidates)
-        off, it = _csr(exclude, len(u), "exclude offsets", "items")
         items, scores, counts = self._query_out(len(u), n)
-        _lib.call("mmsbm_hip_recommend_query_within", self._h, len(u), _p(u, C.c_int32),
-                  0 if cand is None else len(cand), _p_or_null(cand, C.c_int32),
-                  _p_or_null(off, C.c_int64), _p_or_null(it, C.c_int32), n,
+        _lib.call("mmsbm_hip_recommend_query_within", *self._user_query(u, candidates, exclude), n,
                   _p(items, C.c_int32), _p(scores, C.c_double), _p(counts, C.c_int32))
         return items, scores, counts
 
@@ -432,13 +464,9 @@ class HipEM:
         the probability the policy had of showing it there.  Returns (items, scores, propensity (M,n) padded with 0,
         counts); scores are recommend_query's bits of the listed items, not the perturbed keys."""
         u, n = _i32(users), int(n)
-        cand = None if candidates is None else _i32(candidates)
-        off, it = _csr(exclude, len(u), "exclude offsets", "items")
         items, scores, counts = self._query_out(len(u), n)
         prop = np.empty((len(u), max(n, 0)), dtype=np.float64)
-        _lib.call("mmsbm_hip_recommend_query_explore", self._h, len(u), _p(u, C.c_int32),
-                  0 if cand is None else len(cand), _p_or_null(cand, C.c_int32),
-                  _p_or_null(off, C.c_int64), _p_or_null(it, C.c_int32), n, float(temperature),
+        _lib.call("mmsbm_hip_recommend_query_explore", *self._user_query(u, candidates, exclude), n, float(temperature),
                   self._pcg64_state(state), _p(items, C.c_int32), _p(scores, C.c_double), _p(prop, C.c_double),
                   _p(counts, C.c_int32))
         return items, scores, prop, counts
@@ -449,13 +477,10 @@ class HipEM:
         MAX_RECOMMEND).  Returns (scores, propensity), one entry per listed item: -inf / 0 where the item is no
         candidate of its row, and the rest of that list as if the item were absent.  No noise, no seed."""
         u = _i32(users)
-        cand = None if candidates is None else _i32(candidates)
-        off, it = _csr(exclude, len(u), "exclude offsets", "items")
+        head = self._user_query(u, candidates, exclude)
         loff, lit = _csr(lists, len(u), "list offsets", "items")
         scores, prop = np.empty(len(lit), dtype=np.float64), np.empty(len(lit), dtype=np.float64)
-        _lib.call("mmsbm_hip_recommend_list_propensity", self._h, len(u), _p(u, C.c_int32),
-                  0 if cand is None else len(cand), _p_or_null(cand, C.c_int32),
-                  _p_or_null(off, C.c_int64), _p_or_null(it, C.c_int32), float(temperature),
+        _lib.call("mmsbm_hip_recommend_list_propensity", *head, float(temperature),
                   _p(loff, C.c_int64), _p(lit, C.c_int32), _p(scores, C.c_double), _p(prop, C.c_double))
         return scores, prop
 
@@ -485,13 +510,10 @@ class HipEM:
         unless caps[g] items of its category were taken before it, until n are taken.  Scores and order are
         recommend_query's; without categories the answer is recommend_query_within's.  Returns what it returns."""
         u, n = _i32(users), int(n)
-        cand = None if candidates is None else _i32(candidates)
-        off, it = _csr(exclude, len(u), "exclude offsets", "items")
+        head = self._user_query(u, candidates, exclude)
         cap, coff, cit = self._categories(cat_offsets, cat_items, caps)
         items, scores, counts = self._query_out(len(u), n)
-        _lib.call("mmsbm_hip_recommend_query_quota", self._h, len(u), _p(u, C.c_int32),
-                  0 if cand is None else len(cand), _p_or_null(cand, C.c_int32),
-                  _p_or_null(off, C.c_int64), _p_or_null(it, C.c_int32),
+        _lib.call("mmsbm_hip_recommend_query_quota", *head,
                   len(cap), _p(coff, C.c_int64), _p(cit, C.c_int32), _p(cap, C.c_int32), n,
                   _p(items, C.c_int32), _p(scores, C.c_double), _p(counts, C.c_int32))
         return items, scores, counts
@@ -499,20 +521,12 @@ class HipEM:
     def recommend_query_theta_quota(self, theta, n, cat_offsets, cat_items, caps, seen=None, candidates=None):
         """recommend_query_theta (caller-given theta rows (S, M, K), ``seen`` lists per row, ``candidates``) with the
         per-category caps of recommend_query_quota."""
-        t = _f64(theta)
-        if t.ndim != 3 or t.shape[2] != self.k:
-            raise ValueError(f"theta has shape {t.shape}, expected (slots, users, {self.k})")
-        if t.shape[0] != self._rc_added:
-            raise ValueError(f"theta holds {t.shape[0]} blocks, the session {self._rc_added} added slots")
-        m, n = t.shape[1], int(n)
-        off, it = _csr(seen, m, "seen offsets", "items")
-        cand = None if candidates is None else _i32(candidates)
+        (t, m), n = self._theta_rows(theta, self._rc_added), int(n)
+        head = self._theta_query(t, m, seen, candidates)
         cap, coff, cit = self._categories(cat_offsets, cat_items, caps)
         items, scores, counts = self._query_out(m, n)
-        _lib.call("mmsbm_hip_recommend_query_theta_quota", self._h, m, _p(t, C.c_double), _p_or_null(off, C.c_int64),
-                  _p_or_null(it, C.c_int32), 0 if cand is None else len(cand), _p_or_null(cand, C.c_int32),
-                  len(cap), _p(coff, C.c_int64), _p(cit, C.c_int32), _p(cap, C.c_int32), n,
-                  _p(items, C.c_int32), _p(scores, C.c_double), _p(counts, C.c_int32))
+        _lib.call("mmsbm_hip_recommend_query_theta_quota", *head, len(cap), _p(coff, C.c_int64), _p(cit, C.c_int32),
+                  _p(cap, C.c_int32), n, _p(items, C.c_int32), _p(scores, C.c_double), _p(counts, C.c_int32))
         return items, scores, counts
 
     @staticmethod
@@ -540,14 +554,11 @@ class HipEM:
         counts (M,), items (M,S,P) int32 padded with -1, scores (M,S,P) padded with -inf, item_counts (M,S)) for
         S = n_shelves, P = per_shelf (P = 0: the shelves only)."""
         u = _i32(users)
-        cand = None if candidates is None else _i32(candidates)
-        off, it = _csr(exclude, len(u), "exclude offsets", "items")
+        head = self._user_query(u, candidates, exclude)
         coff = np.ascontiguousarray(cat_offsets, dtype=np.int64)
         coff, cit = _csr((coff, cat_items), len(coff) - 1, "category offsets", "cat_items")
         out, ptrs = self._shelves_out(len(u), n_shelves, per_shelf)
-        _lib.call("mmsbm_hip_recommend_query_shelves", self._h, len(u), _p(u, C.c_int32),
-                  0 if cand is None else len(cand), _p_or_null(cand, C.c_int32),
-                  _p_or_null(off, C.c_int64), _p_or_null(it, C.c_int32),
+        _lib.call("mmsbm_hip_recommend_query_shelves", *head,
                   len(coff) - 1, _p(coff, C.c_int64), _p(cit, C.c_int32), int(depth), int(min_items), int(n_shelves),
                   int(per_shelf), *ptrs)
         return out
@@ -556,21 +567,13 @@ class HipEM:
                                       seen=None, candidates=None):
         """recommend_query_shelves for caller-given theta rows (S, M, K) with ``seen`` lists per row and ``candidates``,
         as recommend_query_theta."""
-        t = _f64(theta)
-        if t.ndim != 3 or t.shape[2] != self.k:
-            raise ValueError(f"theta has shape {t.shape}, expected (slots, users, {self.k})")
-        if t.shape[0] != self._rc_added:
-            raise ValueError(f"theta holds {t.shape[0]} blocks, the session {self._rc_added} added slots")
-        m = t.shape[1]
-        off, it = _csr(seen, m, "seen offsets", "items")
-        cand = None if candidates is None else _i32(candidates)
+        t, m = self._theta_rows(theta, self._rc_added)
+        head = self._theta_query(t, m, seen, candidates)
         coff = np.ascontiguousarray(cat_offsets, dtype=np.int64)
         coff, cit = _csr((coff, cat_items), len(coff) - 1, "category offsets", "cat_items")
         out, ptrs = self._shelves_out(m, n_shelves, per_shelf)
-        _lib.call("mmsbm_hip_recommend_query_theta_shelves", self._h, m, _p(t, C.c_double), _p_or_null(off, C.c_int64),
-                  _p_or_null(it, C.c_int32), 0 if cand is None else len(cand), _p_or_null(cand, C.c_int32),
-                  len(coff) - 1, _p(coff, C.c_int64), _p(cit, C.c_int32), int(depth), int(min_items), int(n_shelves),
-                  int(per_shelf), *ptrs)
+        _lib.call("mmsbm_hip_recommend_query_theta_shelves", *head, len(coff) - 1, _p(coff, C.c_int64),
+                  _p(cit, C.c_int32), int(depth), int(min_items), int(n_shelves), int(per_shelf), *ptrs)
         return out
 
     def recommend_rank(self, users, offsets, items, n):
@@ -602,15 +605,10 @@ class HipEM:
         add order; new item j gets id n_items + j.  seen: None or (offsets (n_new+1,) int64, users int32): the training
         users that rated new item j are users[offsets[j]:offsets[j + 1]], and that pair is left out of their lists.
         Once per session, after every recommend_add."""
-        e = _f64(eta)
-        if e.ndim != 3 or e.shape[2] != self.l:
-            raise ValueError(f"eta has shape {e.shape}, expected (slots, items, {self.l})")
-        if e.shape[0] != self._rc_added:
-            raise ValueError(f"eta holds {e.shape[0]} blocks, the session {self._rc_added} added slots")
+        e = _slot_blocks(eta, "eta", f"expected (slots, items, {self.l})", self.l, self._rc_added)
         n_new = e.shape[1]
-        off, us = _csr(seen, n_new, "seen offsets", "users")
         _lib.call("mmsbm_hip_recommend_add_items", self._h, n_new, _p(e, C.c_double),
-                  _p_or_null(off, C.c_int64), _p_or_null(us, C.c_int32))
+                  *_row_csr(seen, n_new, "seen offsets", "users"))
 
     MAX_TOP_PAIRS = 1024
 
@@ -618,13 +616,11 @@ class HipEM:
         """(users (m,) int32, items (m,) int32, scores (m,), count): the m best (user, item) pairs of the open session
         over the encoded user ids ``users`` (distinct; None: every training user) -- score descending, equal scores
         by ascending user id, then item id; entries behind ``count`` are -1 / -1 / -inf."""
-        u = None if users is None else _i32(users)
         m = int(m)
         ou, oi = np.empty(max(m, 0), dtype=np.int32), np.empty(max(m, 0), dtype=np.int32)
         sc = np.empty(max(m, 0), dtype=np.float64)
         count = C.c_int32(0)
-        _lib.call("mmsbm_hip_recommend_top_pairs", self._h, 0 if u is None else len(u),
-                  _p_or_null(u, C.c_int32), m, _p(ou, C.c_int32), _p(oi, C.c_int32),
+        _lib.call("mmsbm_hip_recommend_top_pairs", self._h, *_user_set(users, 0), m, _p(ou, C.c_int32), _p(oi, C.c_int32),
                   _p(sc, C.c_double), C.byref(count))
         return ou, oi, sc, int(count.value)
 
@@ -634,22 +630,18 @@ class HipEM:
         """(users (m,) int32, items (m,) int32, scores (m,), count, info): recommend_top_pairs' answer for m up to
         MAX_TOP_PAIRS_BULK, found by a radix select of the bar over the score tiles.  info: {"bar": the score of the
         last returned pair, "above" / "ties": candidates that score strictly above / exactly the bar, "candidates"}."""
-        u = None if users is None else _i32(users)
         m = int(m)
         ou, oi = np.empty(max(m, 0), dtype=np.int32), np.empty(max(m, 0), dtype=np.int32)
         sc = np.empty(max(m, 0), dtype=np.float64)
         count, bar, counts = C.c_int64(0), C.c_double(0.0), np.zeros(3, dtype=np.int64)
-        _lib.call("mmsbm_hip_recommend_top_pairs_bulk", self._h, 0 if u is None else len(u),
-                  _p_or_null(u, C.c_int32), m, _p(ou, C.c_int32), _p(oi, C.c_int32), _p(sc, C.c_double),
-                  C.byref(count), C.byref(bar), _p(counts, C.c_int64))
+        _lib.call("mmsbm_hip_recommend_top_pairs_bulk", self._h, *_user_set(users, 0), m, _p(ou, C.c_int32),
+                  _p(oi, C.c_int32), _p(sc, C.c_double), C.byref(count), C.byref(bar), _p(counts, C.c_int64))
         return ou, oi, sc, int(count.value), self._bar_info(bar, counts)
 
     def recommend_pair_bar(self, m, users=None):
         """recommend_top_pairs_bulk's info alone: the select and one counting pass, no entries."""
-        u = None if users is None else _i32(users)
         bar, counts = C.c_double(0.0), np.zeros(3, dtype=np.int64)
-        _lib.call("mmsbm_hip_recommend_pair_bar", self._h, 0 if u is None else len(u), _p_or_null(u, C.c_int32),
-                  int(m), C.byref(bar), _p(counts, C.c_int64))
+        _lib.call("mmsbm_hip_recommend_pair_bar", self._h, *_user_set(users, 0), int(m), C.byref(bar), _p(counts, C.c_int64))
         return self._bar_info(bar, counts)
 
     @staticmethod
@@ -670,12 +662,11 @@ class HipEM:
         recommend_query -- a row may hold fewer than n -- and {"rounds", "converged"}: the rounds of deferred
         acceptance it took, and whether they reached the fixed point within ``max_rounds`` (if not, the answer is
         feasible but not the walk's)."""
-        u = None if users is None else _i32(users)
-        m, n = self.n_users if u is None else len(u), int(n)
+        (m, u), n = _user_set(users, self.n_users), int(n)
         cap = _i32(caps)
         items, scores, counts = self._query_out(m, n)
         rounds, converged = C.c_int32(0), C.c_int32(0)
-        _lib.call("mmsbm_hip_recommend_allocate", self._h, m, _p_or_null(u, C.c_int32), n, _p(cap, C.c_int32),
+        _lib.call("mmsbm_hip_recommend_allocate", self._h, m, u, n, _p(cap, C.c_int32),
                   int(max_rounds), _p(items, C.c_int32), _p(scores, C.c_double), _p(counts, C.c_int32),
                   C.byref(rounds), C.byref(converged))
         return items, scores, counts, {"rounds": int(rounds.value), "converged": bool(converged.value)}
@@ -688,8 +679,7 @@ class HipEM:
         row ``items`` (-1: unassigned), ``scores`` (-inf), ``paid``, ``pi``; by catalogue item ``price`` (its cheapest
         slot), ``price_sum``, ``load``; and ``rounds``, ``bids``, ``converged``.  sum(pi) + sum(price_sum) bounds the
         optimum from above."""
-        u = None if users is None else _i32(users)
-        m = self.n_users if u is None else len(u)
+        m, u = _user_set(users, self.n_users)
         cap = _i32(caps)
         if cap.ndim != 1 or len(cap) < self.n_items:
             raise ValueError(f"caps has shape {cap.shape}, expected one entry per item of the session's catalogue")
@@ -698,7 +688,7 @@ class HipEM:
         price, price_sum = np.empty(len(cap), dtype=np.float64), np.empty(len(cap), dtype=np.float64)
         load = np.zeros(len(cap), dtype=np.int32)
         rounds, converged = C.c_int32(0), C.c_int32(0)
-        _lib.call("mmsbm_hip_recommend_assign", self._h, m, _p_or_null(u, C.c_int32), _p(cap, C.c_int32), float(reserve),
+        _lib.call("mmsbm_hip_recommend_assign", self._h, m, u, _p(cap, C.c_int32), float(reserve),
                   float(epsilon), int(max_rounds), _p(items, C.c_int32), _p(scores, C.c_double), _p(paid, C.c_double),
                   _p(pi, C.c_double), _p(price, C.c_double), _p(price_sum, C.c_double), _p(load, C.c_int32),
                   C.byref(rounds), C.byref(converged))
@@ -763,13 +753,9 @@ class HipEM:
         the open recommend session's scores and the distance of the open similarity session over the items (both must
         hold the same slots, added in the same order).  distances: to the nearest earlier pick, +inf for the first."""
         u, n, pool = _i32(users), int(n), int(pool)
-        cand = None if candidates is None else _i32(candidates)
-        off, it = _csr(exclude, len(u), "exclude offsets", "items")
         items, scores, counts = self._query_out(len(u), n)
         distances = np.empty((len(u), max(n, 0)), dtype=np.float64)
-        _lib.call("mmsbm_hip_recommend_diverse", self._h, len(u), _p(u, C.c_int32),
-                  0 if cand is None else len(cand), _p_or_null(cand, C.c_int32),
-                  _p_or_null(off, C.c_int64), _p_or_null(it, C.c_int32), n, pool,
+        _lib.call("mmsbm_hip_recommend_diverse", *self._user_query(u, candidates, exclude), n, pool,
                   float(trade_off), _p(items, C.c_int32), _p(scores, C.c_double), _p(distances, C.c_double),
                   _p(counts, C.c_int32))
         return items, scores, distances, counts
@@ -792,11 +778,10 @@ class HipEM:
         if off[-1] != len(m):
             raise ValueError(f"offsets end at {int(off[-1])}, members holds {len(m)}")
         groups = len(off) - 1
-        cand = None if candidates is None else _i32(candidates)
         items, scores, counts = self._query_out(groups, n)
         _lib.call("mmsbm_hip_recommend_query_groups", self._h, groups, _p(off, C.c_int64), _p(m, C.c_int32),
-                  int(self.GROUP_MODES.get(mode, mode)), float(bar), 0 if cand is None else len(cand),
-                  _p_or_null(cand, C.c_int32), n, _p(items, C.c_int32), _p(scores, C.c_double), _p(counts, C.c_int32))
+                  int(self.GROUP_MODES.get(mode, mode)), float(bar), *_subset(candidates), n,
+                  _p(items, C.c_int32), _p(scores, C.c_double), _p(counts, C.c_int32))
         return items, scores, counts
 
     # -- greedy assortment selection in the recommend session (include/mmsbm_hip.h: mmsbm_hip_recommend_assortment) -----
@@ -820,7 +805,6 @@ class HipEM:
         uniq = np.ascontiguousarray(uniq, dtype=np.int32)
         place = np.searchsorted(uniq, u[np.sort(first)])       # the sorted row of every distinct user, first appearance first
         g = _i32([] if given is None else given)
-        cand = None if candidates is None else _i32(candidates)
         items = np.full(max(c, 0), -1, dtype=np.int32)
         gains = np.zeros(max(c, 0), dtype=np.float64)
         given_gains = np.zeros(len(g), dtype=np.float64)
@@ -829,7 +813,7 @@ class HipEM:
         s_scores = np.full(len(uniq), -np.inf, dtype=np.float64)
         _lib.call("mmsbm_hip_recommend_assortment", self._h, len(uniq), _p(uniq, C.c_int32),
                   int(self.ASSORT_MODES.get(mode, mode)), float(level), len(g), _p(g, C.c_int32),
-                  0 if cand is None else len(cand), _p_or_null(cand, C.c_int32), c, _p(items, C.c_int32),
+                  *_subset(candidates), c, _p(items, C.c_int32),
                   _p(gains, C.c_double), _p(count, C.c_int32), _p(stop, C.c_int32), _p(given_gains, C.c_double),
                   _p(s_items, C.c_int32), _p(s_scores, C.c_double))
         n = int(count[0])
@@ -845,12 +829,10 @@ class HipEM:
         the pair, "max" the highest, "lcb" mean - ``risk`` x std over the slots (population std; ``risk`` 0: the mean,
         negative: exploration).  With one slot added every mode answers as recommend_query, bit for bit."""
         u, n = _i32(users), int(n)
-        cand = None if candidates is None else _i32(candidates)
-        off, it = _csr(exclude, len(u), "exclude offsets", "items")
         items, scores, counts = self._query_out(len(u), n)
-        _lib.call("mmsbm_hip_recommend_query_ensemble", self._h, len(u), _p(u, C.c_int32),
-                  int(self.ENSEMBLE_MODES.get(mode, mode)), float(risk), 0 if cand is None else len(cand),
-                  _p_or_null(cand, C.c_int32), _p_or_null(off, C.c_int64), _p_or_null(it, C.c_int32), n,
+        head = self._user_query(u, candidates, exclude)   # (the mode and the risk stand behind the users)
+        _lib.call("mmsbm_hip_recommend_query_ensemble", *head[:3], int(self.ENSEMBLE_MODES.get(mode, mode)), float(risk),
+                  *head[3:], n,
                   _p(items, C.c_int32), _p(scores, C.c_double), _p(counts, C.c_int32))
         return items, scores, counts
 
@@ -886,29 +868,19 @@ class HipEM:
         items when ``exclude_seen`` and without ``exclude``: None or (offsets (M+1,) int64, items int32), request row b
         also leaves out items[offsets[b]:offsets[b + 1]]."""
         u, n = _i32(users), int(n)
-        cand = None if candidates is None else _i32(candidates)
-        off, it = _csr(exclude, len(u), "exclude offsets", "items")
         items, gains, counts = self._query_out(len(u), n)
-        _lib.call("mmsbm_hip_inform_query", self._h, len(u), _p(u, C.c_int32), 0 if cand is None else len(cand),
-                  _p_or_null(cand, C.c_int32), _p_or_null(off, C.c_int64), _p_or_null(it, C.c_int32),
-                  int(bool(exclude_seen)), n, _p(items, C.c_int32), _p(gains, C.c_double), _p(counts, C.c_int32))
+        _lib.call("mmsbm_hip_inform_query", *self._user_query(u, candidates, exclude), int(bool(exclude_seen)), n,
+                  _p(items, C.c_int32), _p(gains, C.c_double), _p(counts, C.c_int32))
         return items, gains, counts
 
     def inform_query_theta(self, theta, n, seen=None, candidates=None):
         """inform_query for caller-given users: theta (S, M, K), one (M, K) block per added slot in add order, entries
         finite and >= 0.  seen: None (nothing excluded) or (offsets (M+1,) int64, items int32): user b leaves out
         items[offsets[b]:offsets[b + 1]].  candidates as in inform_query."""
-        t = _f64(theta)
-        if t.ndim != 3 or t.shape[2] != self.k:
-            raise ValueError(f"theta has shape {t.shape}, expected (slots, users, {self.k})")
-        if t.shape[0] != getattr(self, "_inf_added", 0):
-            raise ValueError(f"theta holds {t.shape[0]} blocks, the session {getattr(self, '_inf_added', 0)} added slots")
-        m, n = t.shape[1], int(n)
-        cand = None if candidates is None else _i32(candidates)
-        off, it = _csr(seen, m, "seen offsets", "items")
+        (t, m), n = self._theta_rows(theta, getattr(self, "_inf_added", 0)), int(n)
+        head = self._theta_query(t, m, seen, candidates)
         items, gains, counts = self._query_out(m, n)
-        _lib.call("mmsbm_hip_inform_query_theta", self._h, m, _p(t, C.c_double), _p_or_null(off, C.c_int64),
-                  _p_or_null(it, C.c_int32), 0 if cand is None else len(cand), _p_or_null(cand, C.c_int32), n,
+        _lib.call("mmsbm_hip_inform_query_theta", *head, n,
                   _p(items, C.c_int32), _p(gains, C.c_double), _p(counts, C.c_int32))
         return items, gains, counts
 

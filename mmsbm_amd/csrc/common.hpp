@@ -7,14 +7,7 @@
 // unnamed namespace.
 namespace mmsbm_hip_impl {
 
-// ======================================================================================
-// errors
-// ======================================================================================
-struct ApiError : std::runtime_error {
-  int code;
-  ApiError(int c, const std::string &m) : std::runtime_error(m), code(c) {}
-};
-
+// (ApiError, the exception that carries a status code, is abi_request.hpp's: that header stands alone)
 }  // namespace mmsbm_hip_impl
 using namespace mmsbm_hip_impl;
 

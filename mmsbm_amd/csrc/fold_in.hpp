@@ -14,7 +14,7 @@
 //   - RS = 64 / G (one wave per user): the wave's G-lane groups take every RS-th row and the RS partial sums are added by
 //     a butterfly at the end of the iteration; the rows are read from global memory every iteration (long users).
 // Which form a user gets depends on d_u and K only (fold_onchip), so a user's theta is bitwise the same whatever the
-// other users of the request.  All of it is in EXTERNAL terms (a swapped context reads the same numbers).  No atomics.
+// other users asked with it.  All of it is in EXTERNAL terms (a swapped context reads the same numbers).  No atomics.
 #pragma once
 
 namespace {

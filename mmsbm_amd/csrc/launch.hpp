@@ -95,17 +95,7 @@ void recommend_query_theta_quota(mmsbm_hip_ctx *c, int64_t n_users, const double
                                  const int64_t *cat_offsets, const int32_t *cat_items, const int32_t *cat_caps, int n,
                                  int32_t *items, double *scores, int32_t *counts);
 // ... category-level recommendation (shelves.hpp): the categories as the quota queries' (no caps); what is asked of
-// each row, and the caller's output arrays (mmsbm_hip.h; the last three null when per_shelf = 0)
-struct ShelfAsk {
-  int depth, min_items, n_shelves, per_shelf;
-};
-struct ShelfOut {
-  int32_t *shelf_cats;
-  double *shelf_values;
-  int32_t *shelf_available, *shelf_counts, *items;
-  double *scores;
-  int32_t *item_counts;
-};
+// each row, and the caller's output arrays (ShelfAsk, ShelfOut: abi_request.hpp)
 void recommend_query_shelves(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, const int32_t *cand, int n_cand,
                              const int64_t *excl_offsets, const int32_t *excl_items, int64_t n_cats,
                              const int64_t *cat_offsets, const int32_t *cat_items, const ShelfAsk &ask,

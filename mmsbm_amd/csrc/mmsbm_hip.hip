@@ -1,8 +1,10 @@
 // mmsbm_hip.hip -- the C ABI of include/mmsbm_hip.h, and nothing else: every entry is its argument checks, the device
 // and (for the single-restart entries) the selected slot, and ONE call into the unit that owns the work -- launch.hpp
 // declares those calls.  What stays here: the exception-to-status wrapper with the last-error string, the guards the
-// entries share (parameters present, a session open, ids / CSR / candidate lists in range), the device-info entries
-// (they have no context), pcg64_doubles and the host-only layout helpers of the CPU tests.
+// entries share (parameters present, a session open), the device-info entries
+// (they have no context), pcg64_doubles and the host-only layout helpers of the CPU tests.  What a request's users,
+// subsets, lists, categories and user sets must satisfy is abi_request.hpp's, host-only code; an entry opens its session,
+// runs those checks and its own in the order its refusals promise, and makes the call.
 //
 //   tu_create.hip   building a context, restart slots, the index read-back
 //   tu_params.hip   parameters in and out, update_coefficients' fetch, result, snapshots
@@ -82,19 +84,8 @@ int end_session(mmsbm_hip_ctx *ctx, std::unique_ptr<S> mmsbm_hip_ctx::*held, con
   });
 }
 
-// ids[0 .. n) in [0, top), or "<prefix> id out of range at row m"
-void require_ids(const int32_t *ids, int64_t n, int32_t top, const std::string &prefix) {
-  for (int64_t m = 0; m < n; ++m)
-    if (ids[m] < 0 || ids[m] >= top) throw std::invalid_argument(prefix + " id out of range at row " + std::to_string(m));
-}
-
-// The n of a top-N query of `who` ("recommend", "similar"), which returns `noun` ("items", "rows")
-void require_n(int32_t n, const char *who, const char *noun) {
-  if (n < 1) throw std::invalid_argument(std::string(who) + ": n must be at least 1");
-  if (n > MMSBM_HIP_RECOMMEND_MAX_N)
-    throw ApiError(MMSBM_E_UNSUPPORTED, std::string(who) + ": n = " + std::to_string(n) + " is beyond the " +
-                                            std::to_string(MMSBM_HIP_RECOMMEND_MAX_N) + " " + noun + " a query returns at most");
-}
+static_assert(kErrUnsupported == MMSBM_E_UNSUPPORTED && kErrTooLarge == MMSBM_E_TOOLARGE &&
+              kQueryMaxN == MMSBM_HIP_RECOMMEND_MAX_N, "abi_request.hpp stands alone: its copies of the header's numbers");
 
 }  // namespace
 
@@ -431,25 +422,6 @@ int mmsbm_hip_predict_finish(mmsbm_hip_ctx *ctx, double *mean_dist, double stats
 }
 
 namespace {
-// A CSR argument of `rows` ranges (none when off is null): off[0] == 0, never decreasing, a total below 2^31 and
-// val[0 .. total) in [0, top).  Messages "<who>: <off_name>[0] must be 0", "<who>: <off_name> decrease at <row> b",
-// "<who>: more than 2^31 - 1 <vals>", "<who>: <val_name> out of range at entry e".
-void check_csr(const int64_t *off, const int32_t *val, int64_t rows, int32_t top, const char *who,
-               const char *off_name, const char *row, const char *vals, const char *val_name) {
-  if (!off || rows == 0) return;
-  const std::string w = std::string(who) + ": ";
-  if (off[0] != 0) throw std::invalid_argument(w + off_name + "[0] must be 0");
-  for (int64_t b = 0; b < rows; ++b)
-    if (off[b + 1] < off[b])
-      throw std::invalid_argument(w + off_name + " decrease at " + row + " " + std::to_string(b));
-  const int64_t total = off[rows];
-  if (total > INT32_MAX) throw std::invalid_argument(w + "more than 2^31 - 1 " + vals);
-  if (total > 0 && !val) throw std::invalid_argument("null argument");
-  for (int64_t e = 0; e < total; ++e)
-    if (val[e] < 0 || val[e] >= top)
-      throw std::invalid_argument(w + val_name + " out of range at entry " + std::to_string(e));
-}
-
 // Both fold-in entries: new users (user[m] in [0, n_new), K groups) or, items_side, new items (item[m], L groups)
 int fold_entry(mmsbm_hip_ctx *ctx, bool items_side, int64_t n_rows, const int32_t *user, const int32_t *item,
                const int32_t *rating, int32_t n_new, int32_t n_iters, double tol, const double *x0, double *x,
@@ -507,7 +479,7 @@ int mmsbm_hip_recommend_query(mmsbm_hip_ctx *ctx, int64_t n_users, const int32_t
                               double *scores, int32_t *counts) {
   return guarded([&] {
     require_open(ctx, &mmsbm_hip_ctx::rc, "recommend", "recommend_query");
-    if (n_users < 0) throw std::invalid_argument("negative n_users");
+    require_rows(n_users);
     require_n(n, "recommend", "items");
     if (n_users > 0 && (!users || !items)) throw std::invalid_argument("null argument");
     require_ids(users, n_users, ctx->ext_users, "recommend: user");
@@ -522,11 +494,10 @@ int mmsbm_hip_recommend_query_theta(mmsbm_hip_ctx *ctx, int64_t n_users, const d
                                     int32_t *items, double *scores, int32_t *counts) {
   return guarded([&] {
     const RecSession &rc = require_open(ctx, &mmsbm_hip_ctx::rc, "recommend", "recommend_query_theta");
-    if (n_users < 0) throw std::invalid_argument("negative n_users");
+    require_rows(n_users);
     require_n(n, "recommend", "items");
     if (n_users > 0 && (!theta || !items)) throw std::invalid_argument("null argument");
-    check_csr(seen_offsets, seen_items, n_users, rc.items, "recommend", "seen_offsets", "user", "seen items",
-              "seen item");
+    seen_lists(seen_offsets, seen_items).check(n_users, rc.items, "recommend");
     recommend_query_theta(ctx, n_users, theta, seen_offsets, seen_items, n, items, scores, counts);
   });
 }
@@ -536,10 +507,10 @@ int mmsbm_hip_recommend_positions(mmsbm_hip_ctx *ctx, int64_t n_users, const int
                                   int32_t *candidates) {
   return guarded([&] {
     const RecSession &rc = require_open(ctx, &mmsbm_hip_ctx::rc, "recommend", "recommend_positions");
-    if (n_users < 0) throw std::invalid_argument("negative n_users");
+    require_rows(n_users);
     if (n_users > 0 && (!users || !offsets)) throw std::invalid_argument("null argument");
     require_ids(users, n_users, ctx->ext_users, "recommend_positions: user");
-    check_csr(offsets, items, n_users, rc.items, "recommend_positions", "offsets", "user", "items", "item id");
+    RowCsr{offsets, items, "offsets", "user", "items", "item id"}.check(n_users, rc.items, "recommend_positions");
     if (n_users > 0 && offsets[n_users] > 0 && !positions) throw std::invalid_argument("null argument");
     recommend_positions(ctx, n_users, users, offsets, items, positions, candidates);
   });
@@ -555,8 +526,8 @@ int mmsbm_hip_recommend_add_items(mmsbm_hip_ctx *ctx, int32_t n_new, const doubl
     if (static_cast<int64_t>(ctx->ext_items) + n_new > INT32_MAX)
       throw std::invalid_argument("recommend_add_items: more than 2^31 - 1 items in the catalogue");
     if (n_new > 0 && !eta) throw std::invalid_argument("null argument");
-    check_csr(seen_offsets, seen_users, n_new, ctx->ext_users, "recommend_add_items", "seen_offsets", "item",
-              "seen users", "seen user");
+    RowCsr{seen_offsets, seen_users, "seen_offsets", "item", "seen users", "seen user"}.check(n_new, ctx->ext_users,
+                                                                                               "recommend_add_items");
     recommend_add_items(ctx, n_new, eta, seen_offsets, seen_users);
   });
 }
@@ -565,25 +536,13 @@ int mmsbm_hip_recommend_top_pairs(mmsbm_hip_ctx *ctx, int64_t n_users, const int
                                   int32_t *out_users, int32_t *out_items, double *out_scores, int32_t *count) {
   return guarded([&] {
     require_open(ctx, &mmsbm_hip_ctx::rc, "recommend", "recommend_top_pairs");
-    if (n_users < 0) throw std::invalid_argument("negative n_users");
+    require_rows(n_users);
     if (m < 1) throw std::invalid_argument("top_pairs: m must be at least 1");
     if (m > MMSBM_HIP_TOP_PAIRS_MAX_M)
       throw ApiError(MMSBM_E_UNSUPPORTED, "top_pairs: m = " + std::to_string(m) + " is beyond the " +
                                               std::to_string(MMSBM_HIP_TOP_PAIRS_MAX_M) + " pairs a query returns at most");
     if (!out_users || !out_items || !out_scores || !count) throw std::invalid_argument("null argument");
-    // the request in id order (ties go by user id; the kernel walks the users in this order), every training user
-    // when `users` is null; a repeated id would put its pairs into the order twice
-    std::vector<int32_t> ids;
-    if (users) {
-      require_ids(users, n_users, ctx->ext_users, "top_pairs: user");
-      ids.assign(users, users + n_users);
-      std::sort(ids.begin(), ids.end());
-      const auto twice = std::adjacent_find(ids.begin(), ids.end());
-      if (twice != ids.end()) throw std::invalid_argument("top_pairs: user id " + std::to_string(*twice) + " is repeated");
-    } else {
-      ids.resize(static_cast<size_t>(ctx->ext_users));
-      for (int32_t u = 0; u < ctx->ext_users; ++u) ids[static_cast<size_t>(u)] = u;
-    }
+    const std::vector<int32_t> ids = sorted_user_set(users, n_users, ctx->ext_users, "top_pairs");
     recommend_top_pairs(ctx, static_cast<int64_t>(ids.size()), ids.data(), m, out_users, out_items, out_scores, count);
   });
 }
@@ -594,21 +553,12 @@ namespace {
 void pairs_bulk_request(mmsbm_hip_ctx *ctx, const char *entry, int64_t n_users, const int32_t *users, int64_t m,
                         std::vector<int32_t> &ids) {
   require_open(ctx, &mmsbm_hip_ctx::rc, "recommend", entry);
-  if (n_users < 0) throw std::invalid_argument("negative n_users");
+  require_rows(n_users);
   if (m < 1) throw std::invalid_argument("top_pairs_bulk: m must be at least 1");
   if (m > MMSBM_HIP_TOP_PAIRS_BULK_MAX_M)
     throw ApiError(MMSBM_E_UNSUPPORTED, "top_pairs_bulk: m = " + std::to_string(m) + " is beyond the " +
                                             std::to_string(MMSBM_HIP_TOP_PAIRS_BULK_MAX_M) + " pairs a query returns at most");
-  if (users) {
-    require_ids(users, n_users, ctx->ext_users, "top_pairs_bulk: user");
-    ids.assign(users, users + n_users);
-    std::sort(ids.begin(), ids.end());
-    const auto twice = std::adjacent_find(ids.begin(), ids.end());
-    if (twice != ids.end()) throw std::invalid_argument("top_pairs_bulk: user id " + std::to_string(*twice) + " is repeated");
-  } else {
-    ids.resize(static_cast<size_t>(ctx->ext_users));
-    for (int32_t u = 0; u < ctx->ext_users; ++u) ids[static_cast<size_t>(u)] = u;
-  }
+  ids = sorted_user_set(users, n_users, ctx->ext_users, "top_pairs_bulk");
 }
 
 }  // namespace
@@ -653,33 +603,15 @@ int mmsbm_hip_recommend_allocate(mmsbm_hip_ctx *ctx, int64_t n_users, const int3
                                  int32_t *counts, int32_t *rounds, int32_t *converged) {
   return guarded([&] {
     const RecSession &rc = require_open(ctx, &mmsbm_hip_ctx::rc, "recommend", "recommend_allocate");
-    if (n_users < 0) throw std::invalid_argument("negative n_users");
+    require_rows(n_users);
     require_n(n, "recommend_allocate", "items");
     if (max_rounds < 1) throw std::invalid_argument("recommend_allocate: max_rounds must be at least 1");
     if (!caps || !rounds || !converged || (n_users > 0 && !items)) throw std::invalid_argument("null argument");
     std::vector<int32_t> all;
-    if (!users) {  // all training users
-      if (n_users != ctx->ext_users)
-        throw std::invalid_argument("recommend_allocate: without users, n_users must be the number of training users");
-      all.resize(static_cast<size_t>(n_users));
-      for (int64_t b = 0; b < n_users; ++b) all[static_cast<size_t>(b)] = static_cast<int32_t>(b);
-      users = all.data();
-    } else {
-      require_ids(users, n_users, ctx->ext_users, "recommend_allocate: user");
-      std::vector<bool> asked(static_cast<size_t>(ctx->ext_users), false);
-      for (int64_t b = 0; b < n_users; ++b) {
-        if (asked[static_cast<size_t>(users[b])])
-          throw std::invalid_argument("recommend_allocate: user " + std::to_string(users[b]) + " is asked twice (row " +
-                                      std::to_string(b) + ")");
-        asked[static_cast<size_t>(users[b])] = true;
-      }
-    }
+    users = asked_once_user_set(users, n_users, ctx->ext_users, "recommend_allocate", all);
     const AllocPlan plan = plan_allocate(caps, rc.items, n_users, ctx->ext_users, MMSBM_HIP_RECOMMEND_MAX_N);
     if (plan.refused >= 0)
-      throw ApiError(MMSBM_E_UNSUPPORTED, "recommend_allocate: the cap of item " + std::to_string(plan.refused) + ", " +
-                                              std::to_string(caps[plan.refused]) + ", is above " +
-                                              std::to_string(MMSBM_HIP_RECOMMEND_MAX_N) + " and below the " +
-                                              std::to_string(n_users) + " users of the request");
+      throw ApiError(MMSBM_E_UNSUPPORTED, refused_cap("recommend_allocate", plan.refused, caps[plan.refused], n_users));
     recommend_allocate(ctx, n_users, users, n, plan, max_rounds, items, scores, counts, rounds, converged);
   });
 }
@@ -690,7 +622,7 @@ int mmsbm_hip_recommend_assign(mmsbm_hip_ctx *ctx, int64_t n_users, const int32_
                                int32_t *rounds, int32_t *converged) {
   return guarded([&] {
     const RecSession &rc = require_open(ctx, &mmsbm_hip_ctx::rc, "recommend", "recommend_assign");
-    if (n_users < 0) throw std::invalid_argument("negative n_users");
+    require_rows(n_users);
     if (max_rounds < 1) throw std::invalid_argument("recommend_assign: max_rounds must be at least 1");
     if (!std::isfinite(epsilon) || !(epsilon > 0.0) || epsilon < (rc.w_max - rc.w_min) * 0x1p-40)
       throw std::invalid_argument("recommend_assign: epsilon must be finite, positive and at least (largest - smallest "
@@ -699,29 +631,11 @@ int mmsbm_hip_recommend_assign(mmsbm_hip_ctx *ctx, int64_t n_users, const int32_
     if (!caps || !rounds || !converged || !price || !price_sum || !load || (n_users > 0 && (!items || !scores || !paid || !pi)))
       throw std::invalid_argument("null argument");
     std::vector<int32_t> all;
-    if (!users) {  // all training users
-      if (n_users != ctx->ext_users)
-        throw std::invalid_argument("recommend_assign: without users, n_users must be the number of training users");
-      all.resize(static_cast<size_t>(n_users));
-      for (int64_t b = 0; b < n_users; ++b) all[static_cast<size_t>(b)] = static_cast<int32_t>(b);
-      users = all.data();
-    } else {
-      require_ids(users, n_users, ctx->ext_users, "recommend_assign: user");
-      std::vector<bool> asked(static_cast<size_t>(ctx->ext_users), false);
-      for (int64_t b = 0; b < n_users; ++b) {
-        if (asked[static_cast<size_t>(users[b])])
-          throw std::invalid_argument("recommend_assign: user " + std::to_string(users[b]) + " is asked twice (row " +
-                                      std::to_string(b) + ")");
-        asked[static_cast<size_t>(users[b])] = true;
-      }
-    }
+    users = asked_once_user_set(users, n_users, ctx->ext_users, "recommend_assign", all);
     const AssignPlan plan = plan_assign(caps, rc.items, n_users, MMSBM_HIP_RECOMMEND_MAX_N);
     if (plan.refused >= 0)
-      throw ApiError(MMSBM_E_UNSUPPORTED, "recommend_assign: the cap of item " + std::to_string(plan.refused) + ", " +
-                                              std::to_string(caps[plan.refused]) + ", is above " +
-                                              std::to_string(MMSBM_HIP_RECOMMEND_MAX_N) + " and below the " +
-                                              std::to_string(n_users) + " users of the request (or the slots are "
-                                              "more than 2^31)");
+      throw ApiError(MMSBM_E_UNSUPPORTED, refused_cap("recommend_assign", plan.refused, caps[plan.refused], n_users,
+                                                      " (or the slots are more than 2^31)"));
     recommend_assign(ctx, n_users, users, plan, reserve, epsilon, max_rounds,
                      AssignOut{items, scores, paid, pi, price, price_sum, load, rounds, converged});
   });
@@ -740,40 +654,18 @@ int mmsbm_hip_recommend_audience(mmsbm_hip_ctx *ctx, int64_t n_items, const int3
   });
 }
 
-namespace {
-// A candidate list of `who`: v[0 .. n) strictly ascending (so distinct) ids in [0, top)
-void require_candidates(const int32_t *v, int64_t first, int64_t n, int32_t top, const char *who) {
-  for (int64_t e = 0; e < n; ++e) {
-    if (v[e] < 0 || v[e] >= top)
-      throw std::invalid_argument(std::string(who) + ": candidate item id out of range at entry " + std::to_string(first + e));
-    if (e > 0 && v[e] <= v[e - 1])
-      throw std::invalid_argument(std::string(who) + ": candidate items must be ascending and distinct (entry " +
-                                  std::to_string(first + e) + ")");
-  }
-}
-// n_cand / cand_items of the two *_within entries (cand_items null: the whole catalogue, n_cand ignored)
-void require_subset(const int32_t *cand_items, int32_t n_cand, int32_t top, const char *who) {
-  if (!cand_items) return;
-  if (n_cand < 0 || n_cand > top)
-    throw std::invalid_argument(std::string(who) + ": n_cand outside [0, items of the catalogue]");
-  require_candidates(cand_items, 0, n_cand, top, who);
-}
-}  // namespace
-
 int mmsbm_hip_recommend_query_within(mmsbm_hip_ctx *ctx, int64_t n_users, const int32_t *users, int32_t n_cand,
                                      const int32_t *cand_items, const int64_t *excl_offsets,
                                      const int32_t *excl_items, int32_t n, int32_t *items, double *scores,
                                      int32_t *counts) {
   return guarded([&] {
     const RecSession &rc = require_open(ctx, &mmsbm_hip_ctx::rc, "recommend", "recommend_query_within");
-    if (n_users < 0) throw std::invalid_argument("negative n_users");
+    require_rows(n_users);
     require_n(n, "recommend", "items");
     if (n_users > 0 && (!users || !items)) throw std::invalid_argument("null argument");
-    require_ids(users, n_users, ctx->ext_users, "recommend: user");
-    require_subset(cand_items, n_cand, rc.items, "recommend_query_within");
-    check_csr(excl_offsets, excl_items, n_users, rc.items, "recommend_query_within", "excl_offsets", "user",
-              "excluded items", "excluded item");
-    recommend_query_within(ctx, n_users, users, cand_items, n_cand, n_users > 0 ? excl_offsets : nullptr, excl_items, n,
+    const UserQuery q{{n_users, users}, {n_cand, cand_items}, excluded_lists(excl_offsets, excl_items)};
+    q.check(ctx->ext_users, "recommend: user", rc.items, "recommend_query_within");
+    recommend_query_within(ctx, n_users, users, cand_items, n_cand, q.excl.offsets_of(n_users), excl_items, n,
                            items, scores, counts);
   });
 }
@@ -784,28 +676,15 @@ int mmsbm_hip_recommend_query_theta_within(mmsbm_hip_ctx *ctx, int64_t n_users, 
                                            int32_t *counts) {
   return guarded([&] {
     const RecSession &rc = require_open(ctx, &mmsbm_hip_ctx::rc, "recommend", "recommend_query_theta_within");
-    if (n_users < 0) throw std::invalid_argument("negative n_users");
+    require_rows(n_users);
     require_n(n, "recommend", "items");
     if (n_users > 0 && (!theta || !items)) throw std::invalid_argument("null argument");
-    require_subset(cand_items, n_cand, rc.items, "recommend_query_theta_within");
-    check_csr(seen_offsets, seen_items, n_users, rc.items, "recommend", "seen_offsets", "user", "seen items",
-              "seen item");
+    const ThetaQuery q{n_users, {n_cand, cand_items}, seen_lists(seen_offsets, seen_items)};
+    q.check(rc.items, "recommend_query_theta_within", "recommend");
     recommend_query_theta_within(ctx, n_users, theta, seen_offsets, seen_items, cand_items, n_cand, n, items, scores,
                                  counts);
   });
 }
-
-namespace {
-// The temperature of the two explore entries: finite, > 0 and not below the session's floor (explore.hpp: a score lies
-// in [min w, max w], and no exp((s - m) / T) may underflow)
-void require_temperature(double t, const RecSession &rc, const char *who) {
-  const std::string w = std::string(who) + ": ";
-  if (!std::isfinite(t) || t <= 0.0) throw std::invalid_argument(w + "the temperature must be finite and > 0");
-  if ((rc.w_max - rc.w_min) / t > 700.0)
-    throw std::invalid_argument(w + "temperature " + std::to_string(t) + " is below the floor " +
-                                std::to_string((rc.w_max - rc.w_min) / 700.0) + " of the session's weights ((max w - min w) / 700)");
-}
-}  // namespace
 
 int mmsbm_hip_recommend_query_explore(mmsbm_hip_ctx *ctx, int64_t n_users, const int32_t *users, int32_t n_cand,
                                       const int32_t *cand_items, const int64_t *excl_offsets,
@@ -814,15 +693,13 @@ int mmsbm_hip_recommend_query_explore(mmsbm_hip_ctx *ctx, int64_t n_users, const
                                       double *propensity, int32_t *counts) {
   return guarded([&] {
     const RecSession &rc = require_open(ctx, &mmsbm_hip_ctx::rc, "recommend", "recommend_query_explore");
-    if (n_users < 0) throw std::invalid_argument("negative n_users");
+    require_rows(n_users);
     require_n(n, "recommend_explore", "items");
-    require_temperature(temperature, rc, "recommend_query_explore");
+    require_temperature(temperature, rc.w_min, rc.w_max, "recommend_query_explore");
     if (!pcg64_state || (n_users > 0 && (!users || !items))) throw std::invalid_argument("null argument");
-    require_ids(users, n_users, ctx->ext_users, "recommend: user");
-    require_subset(cand_items, n_cand, rc.items, "recommend_query_explore");
-    check_csr(excl_offsets, excl_items, n_users, rc.items, "recommend_query_explore", "excl_offsets", "user",
-              "excluded items", "excluded item");
-    recommend_query_explore(ctx, n_users, users, cand_items, n_cand, n_users > 0 ? excl_offsets : nullptr, excl_items, n,
+    const UserQuery q{{n_users, users}, {n_cand, cand_items}, excluded_lists(excl_offsets, excl_items)};
+    q.check(ctx->ext_users, "recommend: user", rc.items, "recommend_query_explore");
+    recommend_query_explore(ctx, n_users, users, cand_items, n_cand, q.excl.offsets_of(n_users), excl_items, n,
                             temperature, pcg64_state, items, scores, propensity, counts);
   });
 }
@@ -834,30 +711,17 @@ int mmsbm_hip_recommend_list_propensity(mmsbm_hip_ctx *ctx, int64_t n_users, con
   return guarded([&] {
     const char *who = "recommend_list_propensity";
     const RecSession &rc = require_open(ctx, &mmsbm_hip_ctx::rc, "recommend", who);
-    if (n_users < 0) throw std::invalid_argument("negative n_users");
-    require_temperature(temperature, rc, who);
+    require_rows(n_users);
+    require_temperature(temperature, rc.w_min, rc.w_max, who);
     if (n_users > 0 && (!users || !list_offsets)) throw std::invalid_argument("null argument");
-    require_ids(users, n_users, ctx->ext_users, "recommend: user");
-    require_subset(cand_items, n_cand, rc.items, who);
-    check_csr(excl_offsets, excl_items, n_users, rc.items, who, "excl_offsets", "user", "excluded items", "excluded item");
-    check_csr(list_offsets, list_items, n_users, rc.items, who, "list_offsets", "user", "listed items", "listed item");
+    const UserQuery q{{n_users, users}, {n_cand, cand_items}, excluded_lists(excl_offsets, excl_items)};
+    q.check(ctx->ext_users, "recommend: user", rc.items, who);
+    const RowCsr lists{list_offsets, list_items, "list_offsets", "user", "listed items", "listed item"};
+    lists.check(n_users, rc.items, who);
     if (n_users > 0 && list_offsets[n_users] > 0 && !propensity) throw std::invalid_argument("null argument");
-    std::vector<int32_t> row;
-    for (int64_t b = 0; b < n_users; ++b) {
-      const int64_t len = list_offsets[b + 1] - list_offsets[b];
-      if (len > MMSBM_HIP_RECOMMEND_MAX_N)
-        throw ApiError(MMSBM_E_UNSUPPORTED, std::string(who) + ": the list of row " + std::to_string(b) + " holds " +
-                                                std::to_string(len) + " items, beyond the " +
-                                                std::to_string(MMSBM_HIP_RECOMMEND_MAX_N) + " a list holds at most");
-      row.assign(list_items + list_offsets[b], list_items + list_offsets[b + 1]);
-      std::sort(row.begin(), row.end());
-      const auto twice = std::adjacent_find(row.begin(), row.end());
-      if (twice != row.end())
-        throw std::invalid_argument(std::string(who) + ": item " + std::to_string(*twice) + " is twice in the list of row " +
-                                    std::to_string(b));
-    }
-    recommend_list_propensity(ctx, n_users, users, cand_items, n_cand, n_users > 0 ? excl_offsets : nullptr, excl_items,
-                              temperature, n_users > 0 ? list_offsets : nullptr, list_items, scores, propensity);
+    require_lists(list_offsets, list_items, n_users, who);
+    recommend_list_propensity(ctx, n_users, users, cand_items, n_cand, q.excl.offsets_of(n_users), excl_items,
+                              temperature, lists.offsets_of(n_users), list_items, scores, propensity);
   });
 }
 
@@ -874,33 +738,6 @@ int mmsbm_hip_explore_noise(mmsbm_hip_ctx *ctx, const uint64_t pcg64_state[4], i
   });
 }
 
-namespace {
-// The capped categories of the two *_quota entries: a CSR of n_cats categories over the catalogue's `top` items, each
-// strictly ascending, no item in two of them, no negative cap.  capped = false (the two *_shelves entries): the same
-// categories without caps, cat_caps is not read.
-void require_categories(int64_t n_cats, const int64_t *cat_offsets, const int32_t *cat_items, const int32_t *cat_caps,
-                        int32_t top, const char *who, bool capped = true) {
-  const std::string w = std::string(who) + ": ";
-  if (n_cats < 0) throw std::invalid_argument(w + "negative n_cats");
-  if (n_cats == 0) return;
-  if (!cat_offsets || (capped && !cat_caps)) throw std::invalid_argument("null argument");
-  check_csr(cat_offsets, cat_items, n_cats, top, who, "cat_offsets", "category", "category items", "category item");
-  std::vector<bool> taken(static_cast<size_t>(top), false);
-  for (int64_t g = 0; g < n_cats; ++g) {
-    if (capped && cat_caps[g] < 0) throw std::invalid_argument(w + "negative cap of category " + std::to_string(g));
-    for (int64_t e = cat_offsets[g]; e < cat_offsets[g + 1]; ++e) {
-      if (e > cat_offsets[g] && cat_items[e] <= cat_items[e - 1])
-        throw std::invalid_argument(w + "the items of a category must be ascending and distinct (entry " +
-                                    std::to_string(e) + ")");
-      if (taken[static_cast<size_t>(cat_items[e])])
-        throw std::invalid_argument(w + "item " + std::to_string(cat_items[e]) + " is in two categories (entry " +
-                                    std::to_string(e) + ")");
-      taken[static_cast<size_t>(cat_items[e])] = true;
-    }
-  }
-}
-}  // namespace
-
 int mmsbm_hip_recommend_query_quota(mmsbm_hip_ctx *ctx, int64_t n_users, const int32_t *users, int32_t n_cand,
                                     const int32_t *cand_items, const int64_t *excl_offsets, const int32_t *excl_items,
                                     int64_t n_cats, const int64_t *cat_offsets, const int32_t *cat_items,
@@ -908,15 +745,13 @@ int mmsbm_hip_recommend_query_quota(mmsbm_hip_ctx *ctx, int64_t n_users, const i
                                     int32_t *counts) {
   return guarded([&] {
     const RecSession &rc = require_open(ctx, &mmsbm_hip_ctx::rc, "recommend", "recommend_query_quota");
-    if (n_users < 0) throw std::invalid_argument("negative n_users");
+    require_rows(n_users);
     require_n(n, "recommend", "items");
     if (n_users > 0 && (!users || !items)) throw std::invalid_argument("null argument");
-    require_ids(users, n_users, ctx->ext_users, "recommend: user");
-    require_subset(cand_items, n_cand, rc.items, "recommend_query_quota");
-    check_csr(excl_offsets, excl_items, n_users, rc.items, "recommend_query_quota", "excl_offsets", "user",
-              "excluded items", "excluded item");
+    const UserQuery q{{n_users, users}, {n_cand, cand_items}, excluded_lists(excl_offsets, excl_items)};
+    q.check(ctx->ext_users, "recommend: user", rc.items, "recommend_query_quota");
     require_categories(n_cats, cat_offsets, cat_items, cat_caps, rc.items, "recommend_query_quota");
-    recommend_query_quota(ctx, n_users, users, cand_items, n_cand, n_users > 0 ? excl_offsets : nullptr, excl_items,
+    recommend_query_quota(ctx, n_users, users, cand_items, n_cand, q.excl.offsets_of(n_users), excl_items,
                           n_cats, cat_offsets, cat_items, cat_caps, n, items, scores, counts);
   });
 }
@@ -928,40 +763,16 @@ int mmsbm_hip_recommend_query_theta_quota(mmsbm_hip_ctx *ctx, int64_t n_users, c
                                           double *scores, int32_t *counts) {
   return guarded([&] {
     const RecSession &rc = require_open(ctx, &mmsbm_hip_ctx::rc, "recommend", "recommend_query_theta_quota");
-    if (n_users < 0) throw std::invalid_argument("negative n_users");
+    require_rows(n_users);
     require_n(n, "recommend", "items");
     if (n_users > 0 && (!theta || !items)) throw std::invalid_argument("null argument");
-    require_subset(cand_items, n_cand, rc.items, "recommend_query_theta_quota");
-    check_csr(seen_offsets, seen_items, n_users, rc.items, "recommend", "seen_offsets", "user", "seen items",
-              "seen item");
+    const ThetaQuery q{n_users, {n_cand, cand_items}, seen_lists(seen_offsets, seen_items)};
+    q.check(rc.items, "recommend_query_theta_quota", "recommend");
     require_categories(n_cats, cat_offsets, cat_items, cat_caps, rc.items, "recommend_query_theta_quota");
     recommend_query_theta_quota(ctx, n_users, theta, seen_offsets, seen_items, cand_items, n_cand, n_cats, cat_offsets,
                                 cat_items, cat_caps, n, items, scores, counts);
   });
 }
-
-namespace {
-// depth / min_items / n_shelves / per_shelf and the output arrays of the two *_shelves entries
-void require_shelf_ask(int64_t n_users, int64_t n_cats, const ShelfAsk &ask, const ShelfOut &out, const char *who) {
-  const std::string w = std::string(who) + ": ";
-  if (ask.depth < 1) throw std::invalid_argument(w + "depth must be at least 1");
-  if (ask.min_items < 1) throw std::invalid_argument(w + "min_items must be at least 1");
-  if (ask.n_shelves < 1) throw std::invalid_argument(w + "n_shelves must be at least 1");
-  if (ask.per_shelf < 0) throw std::invalid_argument(w + "negative per_shelf");
-  auto within_max = [&](int v, const char *name) {
-    if (v > MMSBM_HIP_RECOMMEND_MAX_N)
-      throw ApiError(MMSBM_E_UNSUPPORTED, w + name + " = " + std::to_string(v) + " is beyond the " +
-                                              std::to_string(MMSBM_HIP_RECOMMEND_MAX_N) + " a query holds");
-  };
-  within_max(ask.depth, "depth");
-  within_max(ask.n_shelves, "n_shelves");
-  within_max(ask.per_shelf, "per_shelf");
-  if (n_cats > INT32_MAX) throw ApiError(MMSBM_E_TOOLARGE, w + "more than 2^31 - 1 categories");
-  if (n_users > 0 && (!out.shelf_cats || !out.shelf_values || !out.shelf_available || !out.shelf_counts ||
-                      (ask.per_shelf > 0 && (!out.items || !out.scores || !out.item_counts))))
-    throw std::invalid_argument("null argument");
-}
-}  // namespace
 
 int mmsbm_hip_recommend_query_shelves(mmsbm_hip_ctx *ctx, int64_t n_users, const int32_t *users, int32_t n_cand,
                                       const int32_t *cand_items, const int64_t *excl_offsets,
@@ -972,17 +783,15 @@ int mmsbm_hip_recommend_query_shelves(mmsbm_hip_ctx *ctx, int64_t n_users, const
                                       int32_t *item_counts) {
   return guarded([&] {
     const RecSession &rc = require_open(ctx, &mmsbm_hip_ctx::rc, "recommend", "recommend_query_shelves");
-    if (n_users < 0) throw std::invalid_argument("negative n_users");
+    require_rows(n_users);
     const ShelfAsk ask{depth, min_items, n_shelves, per_shelf};
     const ShelfOut out{shelf_cats, shelf_values, shelf_available, shelf_counts, items, scores, item_counts};
     require_shelf_ask(n_users, n_cats, ask, out, "recommend_query_shelves");
     if (n_users > 0 && !users) throw std::invalid_argument("null argument");
-    require_ids(users, n_users, ctx->ext_users, "recommend: user");
-    require_subset(cand_items, n_cand, rc.items, "recommend_query_shelves");
-    check_csr(excl_offsets, excl_items, n_users, rc.items, "recommend_query_shelves", "excl_offsets", "user",
-              "excluded items", "excluded item");
+    const UserQuery q{{n_users, users}, {n_cand, cand_items}, excluded_lists(excl_offsets, excl_items)};
+    q.check(ctx->ext_users, "recommend: user", rc.items, "recommend_query_shelves");
     require_categories(n_cats, cat_offsets, cat_items, nullptr, rc.items, "recommend_query_shelves", false);
-    recommend_query_shelves(ctx, n_users, users, cand_items, n_cand, n_users > 0 ? excl_offsets : nullptr, excl_items,
+    recommend_query_shelves(ctx, n_users, users, cand_items, n_cand, q.excl.offsets_of(n_users), excl_items,
                             n_cats, cat_offsets, cat_items, ask, out);
   });
 }
@@ -996,14 +805,13 @@ int mmsbm_hip_recommend_query_theta_shelves(mmsbm_hip_ctx *ctx, int64_t n_users,
                                             int32_t *items, double *scores, int32_t *item_counts) {
   return guarded([&] {
     const RecSession &rc = require_open(ctx, &mmsbm_hip_ctx::rc, "recommend", "recommend_query_theta_shelves");
-    if (n_users < 0) throw std::invalid_argument("negative n_users");
+    require_rows(n_users);
     const ShelfAsk ask{depth, min_items, n_shelves, per_shelf};
     const ShelfOut out{shelf_cats, shelf_values, shelf_available, shelf_counts, items, scores, item_counts};
     require_shelf_ask(n_users, n_cats, ask, out, "recommend_query_theta_shelves");
     if (n_users > 0 && !theta) throw std::invalid_argument("null argument");
-    require_subset(cand_items, n_cand, rc.items, "recommend_query_theta_shelves");
-    check_csr(seen_offsets, seen_items, n_users, rc.items, "recommend", "seen_offsets", "user", "seen items",
-              "seen item");
+    const ThetaQuery q{n_users, {n_cand, cand_items}, seen_lists(seen_offsets, seen_items)};
+    q.check(rc.items, "recommend_query_theta_shelves", "recommend");
     require_categories(n_cats, cat_offsets, cat_items, nullptr, rc.items, "recommend_query_theta_shelves", false);
     recommend_query_theta_shelves(ctx, n_users, theta, seen_offsets, seen_items, cand_items, n_cand, n_cats, cat_offsets,
                                   cat_items, ask, out);
@@ -1014,12 +822,12 @@ int mmsbm_hip_recommend_rank(mmsbm_hip_ctx *ctx, int64_t n_users, const int32_t 
                              const int32_t *cand_items, int32_t n, int32_t *items, double *scores, int32_t *counts) {
   return guarded([&] {
     const RecSession &rc = require_open(ctx, &mmsbm_hip_ctx::rc, "recommend", "recommend_rank");
-    if (n_users < 0) throw std::invalid_argument("negative n_users");
+    require_rows(n_users);
     require_n(n, "recommend", "items");
     if (n_users > 0 && (!users || !offsets || !items)) throw std::invalid_argument("null argument");
     require_ids(users, n_users, ctx->ext_users, "recommend_rank: user");
-    check_csr(offsets, cand_items, n_users, rc.items, "recommend_rank", "offsets", "user", "candidate items",
-              "candidate item id");
+    RowCsr{offsets, cand_items, "offsets", "user", "candidate items", "candidate item id"}.check(n_users, rc.items,
+                                                                                                 "recommend_rank");
     for (int64_t b = 0; b < n_users; ++b)
       require_candidates(cand_items + offsets[b], offsets[b], offsets[b + 1] - offsets[b], rc.items, "recommend_rank");
     recommend_rank(ctx, n_users, users, offsets, cand_items, n, items, scores, counts);
@@ -1082,18 +890,16 @@ int mmsbm_hip_recommend_diverse(mmsbm_hip_ctx *ctx, int64_t n_users, const int32
                                   " slots, the similarity session " + std::to_string(sm.slots));
     if (rc.items != sm.rows)
       throw std::invalid_argument("recommend_diverse: the recommend session's catalogue holds added items");
-    if (n_users < 0) throw std::invalid_argument("negative n_users");
+    require_rows(n_users);
     if (n < 1) throw std::invalid_argument("recommend_diverse: n must be at least 1");
     if (pool < n) throw std::invalid_argument("recommend_diverse: pool must be at least n");
     if (!std::isfinite(trade_off) || trade_off < 0.0)
       throw std::invalid_argument("recommend_diverse: trade_off must be finite and at least 0");
     require_n(pool, "recommend_diverse", "pool entries");
     if (n_users > 0 && (!users || !items)) throw std::invalid_argument("null argument");
-    require_ids(users, n_users, ctx->ext_users, "recommend_diverse: user");
-    require_subset(cand_items, n_cand, rc.items, "recommend_diverse");
-    check_csr(excl_offsets, excl_items, n_users, rc.items, "recommend_diverse", "excl_offsets", "user", "excluded items",
-              "excluded item");
-    recommend_diverse(ctx, n_users, users, cand_items, n_cand, n_users > 0 ? excl_offsets : nullptr, excl_items, n, pool,
+    const UserQuery q{{n_users, users}, {n_cand, cand_items}, excluded_lists(excl_offsets, excl_items)};
+    q.check(ctx->ext_users, "recommend_diverse: user", rc.items, "recommend_diverse");
+    recommend_diverse(ctx, n_users, users, cand_items, n_cand, q.excl.offsets_of(n_users), excl_items, n, pool,
                       trade_off, items, scores, distances, counts);
   });
 }
@@ -1112,17 +918,9 @@ int mmsbm_hip_recommend_query_groups(mmsbm_hip_ctx *ctx, int64_t n_groups, const
       throw std::invalid_argument("recommend_query_groups: bar must be finite");
     require_n(n, "recommend_query_groups", "items");
     if (n_groups > 0 && (!offsets || !items)) throw std::invalid_argument("null argument");
-    check_csr(offsets, members, n_groups, ctx->ext_users, "recommend_query_groups", "offsets", "group", "members",
-              "member");
-    // distinct within a group: last[u] = the last group that named user u
-    std::vector<int64_t> last(static_cast<size_t>(ctx->ext_users), -1);
-    for (int64_t g = 0; g < n_groups; ++g)
-      for (int64_t e = offsets[g]; e < offsets[g + 1]; ++e) {
-        if (last[static_cast<size_t>(members[e])] == g)
-          throw std::invalid_argument("recommend_query_groups: member repeated in group " + std::to_string(g) +
-                                      " at entry " + std::to_string(e));
-        last[static_cast<size_t>(members[e])] = g;
-      }
+    RowCsr{offsets, members, "offsets", "group", "members", "member"}.check(n_groups, ctx->ext_users,
+                                                                           "recommend_query_groups");
+    require_distinct_members(offsets, members, n_groups, ctx->ext_users, "recommend_query_groups");
     require_subset(cand_items, n_cand, rc.items, "recommend_query_groups");
     recommend_query_groups(ctx, n_groups, offsets, members, mode, bar, cand_items, n_cand, n, items, scores, counts);
   });
@@ -1134,7 +932,7 @@ int mmsbm_hip_recommend_assortment(mmsbm_hip_ctx *ctx, int64_t n_users, const in
                                    int32_t *stop, double *given_gains, int32_t *served_items, double *served_scores) {
   return guarded([&] {
     const RecSession &rc = require_open(ctx, &mmsbm_hip_ctx::rc, "recommend", "recommend_assortment");
-    if (n_users < 0) throw std::invalid_argument("negative n_users");
+    require_rows(n_users);
     if (n_given < 0) throw std::invalid_argument("recommend_assortment: negative n_given");
     if (mode != MMSBM_HIP_ASSORT_BEST && mode != MMSBM_HIP_ASSORT_REACH)
       throw std::invalid_argument("recommend_assortment: unknown mode " + std::to_string(mode));
@@ -1165,18 +963,16 @@ int mmsbm_hip_recommend_query_ensemble(mmsbm_hip_ctx *ctx, int64_t n_users, cons
                                        int32_t *counts) {
   return guarded([&] {
     const RecSession &rc = require_open(ctx, &mmsbm_hip_ctx::rc, "recommend", "recommend_query_ensemble");
-    if (n_users < 0) throw std::invalid_argument("negative n_users");
+    require_rows(n_users);
     if (mode != MMSBM_HIP_ENSEMBLE_MIN && mode != MMSBM_HIP_ENSEMBLE_MAX && mode != MMSBM_HIP_ENSEMBLE_LCB)
       throw std::invalid_argument("recommend_query_ensemble: unknown mode " + std::to_string(mode));
     if (mode == MMSBM_HIP_ENSEMBLE_LCB && !std::isfinite(risk))
       throw std::invalid_argument("recommend_query_ensemble: risk must be finite");
     require_n(n, "recommend_query_ensemble", "items");
     if (n_users > 0 && (!users || !items)) throw std::invalid_argument("null argument");
-    require_ids(users, n_users, ctx->ext_users, "recommend_query_ensemble: user");
-    require_subset(cand_items, n_cand, rc.items, "recommend_query_ensemble");
-    check_csr(excl_offsets, excl_items, n_users, rc.items, "recommend_query_ensemble", "excl_offsets", "user",
-              "excluded items", "excluded item");
-    recommend_query_ensemble(ctx, n_users, users, mode, risk, cand_items, n_cand, n_users > 0 ? excl_offsets : nullptr,
+    const UserQuery q{{n_users, users}, {n_cand, cand_items}, excluded_lists(excl_offsets, excl_items)};
+    q.check(ctx->ext_users, "recommend_query_ensemble: user", rc.items, "recommend_query_ensemble");
+    recommend_query_ensemble(ctx, n_users, users, mode, risk, cand_items, n_cand, q.excl.offsets_of(n_users),
                              excl_items, n, items, scores, counts);
   });
 }
@@ -1214,14 +1010,12 @@ int mmsbm_hip_inform_query(mmsbm_hip_ctx *ctx, int64_t n_users, const int32_t *u
                            int exclude_train, int32_t n, int32_t *items, double *gains, int32_t *counts) {
   return guarded([&] {
     require_open(ctx, &mmsbm_hip_ctx::inf, "inform", "inform_query");
-    if (n_users < 0) throw std::invalid_argument("negative n_users");
+    require_rows(n_users);
     require_n(n, "inform", "items");
     if (n_users > 0 && (!users || !items)) throw std::invalid_argument("null argument");
-    require_ids(users, n_users, ctx->ext_users, "inform: user");
-    require_subset(cand_items, n_cand, ctx->ext_items, "inform_query");
-    check_csr(excl_offsets, excl_items, n_users, ctx->ext_items, "inform_query", "excl_offsets", "user",
-              "excluded items", "excluded item");
-    inform_query(ctx, n_users, users, cand_items, n_cand, n_users > 0 ? excl_offsets : nullptr, excl_items,
+    const UserQuery q{{n_users, users}, {n_cand, cand_items}, excluded_lists(excl_offsets, excl_items)};
+    q.check(ctx->ext_users, "inform: user", ctx->ext_items, "inform_query");
+    inform_query(ctx, n_users, users, cand_items, n_cand, q.excl.offsets_of(n_users), excl_items,
                  exclude_train != 0, n, items, gains, counts);
   });
 }
@@ -1231,17 +1025,12 @@ int mmsbm_hip_inform_query_theta(mmsbm_hip_ctx *ctx, int64_t n_users, const doub
                                  int32_t *items, double *gains, int32_t *counts) {
   return guarded([&] {
     const InfSession &inf = require_open(ctx, &mmsbm_hip_ctx::inf, "inform", "inform_query_theta");
-    if (n_users < 0) throw std::invalid_argument("negative n_users");
+    require_rows(n_users);
     require_n(n, "inform", "items");
     if (n_users > 0 && (!theta || !items)) throw std::invalid_argument("null argument");
-    // (a NaN gain has no place in the order, and the entropy of a negative weight is not one)
-    const size_t n_theta = static_cast<size_t>(inf.slots) * static_cast<size_t>(n_users) * ctx->ext_k;
-    for (size_t e = 0; e < n_theta; ++e)
-      if (!std::isfinite(theta[e]) || theta[e] < 0.0)
-        throw std::invalid_argument("inform: theta entry " + std::to_string(e) + " is not a finite number >= 0");
-    require_subset(cand_items, n_cand, ctx->ext_items, "inform_query_theta");
-    check_csr(seen_offsets, seen_items, n_users, ctx->ext_items, "inform", "seen_offsets", "user", "seen items",
-              "seen item");
+    require_theta_entries(theta, static_cast<size_t>(inf.slots) * static_cast<size_t>(n_users) * ctx->ext_k, "inform");
+    const ThetaQuery q{n_users, {n_cand, cand_items}, seen_lists(seen_offsets, seen_items)};
+    q.check(ctx->ext_items, "inform_query_theta", "inform");
     inform_query_theta(ctx, n_users, theta, seen_offsets, seen_items, cand_items, n_cand, n, items, gains, counts);
   });
 }
@@ -1310,11 +1099,11 @@ int mmsbm_hip_explain_query(mmsbm_hip_ctx *ctx, int64_t n_users, const int32_t *
                             double *contribution, int32_t *counts, double *explained, double *score, int32_t *degree) {
   return guarded([&] {
     require_open(ctx, &mmsbm_hip_ctx::ex, "explain", "explain_query");
-    if (n_users < 0) throw std::invalid_argument("negative n_users");
+    require_rows(n_users);
     require_n(n, "explain", "rows");
     if (n_users > 0 && (!users || !offsets)) throw std::invalid_argument("null argument");
     require_ids(users, n_users, ctx->ext_users, "explain: user");
-    check_csr(offsets, items, n_users, ctx->ext_items, "explain", "offsets", "user", "pairs", "item id");
+    RowCsr{offsets, items, "offsets", "user", "pairs", "item id"}.check(n_users, ctx->ext_items, "explain");
     if (n_users > 0 && offsets[n_users] > 0 && !hist_items) throw std::invalid_argument("null argument");
     if (n_users > 0 && offsets[n_users] * static_cast<int64_t>(n) > INT32_MAX)
       throw std::invalid_argument("explain: more than 2^31 - 1 entries in one query");

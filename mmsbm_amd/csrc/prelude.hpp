@@ -52,6 +52,7 @@
 
 #include "../../include/mmsbm_hip.h"
 #include "layout.hpp"
+#include "abi_request.hpp"
 #include "common.hpp"
 #include "shapes.hpp"
 #include "pair_plan.hpp"

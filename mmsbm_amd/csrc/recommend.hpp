@@ -8,7 +8,7 @@
 // rank min(K, L): x_s = theta_s (U x K) and y_s = eta_s W_s^T (I x K) when K <= L, else x_s = theta_s W_s (U x L) and
 // y_s = eta_s.  The slots' factors are concatenated along the rank, f = s * rank + j, and a score is ONE fma chain
 // over f in ascending order, divided by S at the end -- the same operations in the same order whatever the tile, the
-// launch shape or the other users of the request (bitwise request independence; identical eta rows tie exactly).
+// launch shape or the request's other users (bitwise request independence; identical eta rows tie exactly).
 // Everything is stated in EXTERNAL terms (user side = the caller's users, whichever internal side holds them), so a
 // swapped context gives bitwise the same scores as an unswapped one.
 //

@@ -26,6 +26,57 @@ def test_header_symbols_are_exported_and_bound():
     assert sorted(_lib.SIGNATURES) == names
 
 
+C_SCALARS = {"int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "uint64_t": ctypes.c_uint64,
+             "uint8_t": ctypes.c_uint8, "double": ctypes.c_double, "float": ctypes.c_float}
+
+
+def ctype_of(decl):
+    """The ctypes type of one C return or parameter declaration of the header (its name, if any, is dropped)."""
+    decl = re.sub(r"\[\s*\d*\s*\]", " *", decl)                 # T name[k] is T *
+    stars = decl.count("*")
+    words = [w for w in decl.replace("*", " ").split() if w not in ("const", "struct", "unsigned")]
+    base = words[0]
+    if "unsigned" in decl.split():                              # (unsigned long long of the diagnostic build only)
+        raise AssertionError(f"no mapping for {decl!r}")
+    if base.startswith("mmsbm_hip_"):                           # an opaque handle
+        assert stars in (1, 2), decl
+        return ctypes.c_void_p if stars == 1 else ctypes.POINTER(ctypes.c_void_p)
+    if base == "char":
+        assert stars == 1, decl
+        return ctypes.c_char_p
+    assert stars <= 1, decl
+    return ctypes.POINTER(C_SCALARS[base]) if stars else C_SCALARS[base]
+
+
+def declared_prototypes():
+    """{name: (restype, [argtypes])} of every prototype of include/mmsbm_hip.h."""
+    text = open(os.path.join(ROOT, "include", "mmsbm_hip.h")).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    text = re.sub(r"//[^\n]*", "", text)
+    text = re.sub(r"^\s*#[^\n]*(\\\n[^\n]*)*", "", text, flags=re.M)
+    out = {}
+    for ret, name, params in re.findall(r"([A-Za-z_][\w\s\*]*?)\b(mmsbm_hip_[a-z_0-9]+)\s*\(([^()]*)\)\s*;", text):
+        params = " ".join(params.split())
+        args = [] if params == "void" else [ctype_of(p) for p in params.split(",")]
+        assert name not in out, f"{name} is declared twice"
+        out[name] = (ctype_of(ret), args)
+    return out
+
+
+def test_ctypes_signatures_equal_the_header_position_by_position():
+    """Every prototype of the header against _lib.SIGNATURES: the return type and each argument type, in order -- a
+    miscounted or mistyped argument in a long signature shows here, without a GPU."""
+    protos = declared_prototypes()
+    assert sorted(protos) == declared_symbols() == sorted(_lib.SIGNATURES)
+    assert len(protos) >= 106
+    for name, (res, args) in protos.items():
+        got_res, got_args = _lib.SIGNATURES[name]
+        assert got_res is res, (name, "return", got_res, res)
+        assert len(got_args) == len(args), (name, len(got_args), len(args))
+        for pos, (got, want) in enumerate(zip(got_args, args)):
+            assert got is want, (name, pos, got, want)
+
+
 def test_abi_version_and_kernel_names():
     lib = _lib.load()
     assert lib.mmsbm_hip_abi_version() == 1
