@@ -81,11 +81,13 @@ struct PairPlan {
   }
   // The plan's share of "the triple passes and the T + S stage run as one launch" (pass_dense.hpp): the T + S launch is
   // pair_block_kernel<false, true, 1, false, 256, 2, false> over single units -- small tile through scalar loads, one
-  // slot per thread, 256 threads (so rows of up to 24 groups: three double2 of eta rows per thread).  The A launch keeps
-  // its own form whatever it is
+  // slot per thread, 256 threads (so rows of up to 24 groups: three double2 of eta rows per thread).  The pair units
+  // compute their A rows themselves in the multiply-add order of pair_block_kernel's A mode (the same for 256 and 512
+  // threads, tile in scalar loads or in LDS), so the A launch, which still fills the table for the user pass, must be that
+  // kernel too: it is for every small tile, and the condition says so
   bool pass_dense_shape_ok() const {
-    return form_t() == PairForm::Block && threads_t == kBlock && !tl_t && nacc == 1 && kt == 2 && spb * nsub <= kBlock &&
-           !direct_out && chunk_pairs == mmsbm::kMvChunkPairs && kUnitPairs * lp <= 3 * 2 * kBlock && lds_t <= kLdsBudget;
+    return form_t() == PairForm::Block && form_a() == PairForm::Block && threads_t == kBlock && !tl_t && nacc == 1 && kt == 2 && spb * nsub <= kBlock &&
+           !direct_out && chunk_pairs == mmsbm::kMvChunkPairs && kUnitPairs * lp <= 3 * 2 * kBlock && pass_dense_lds(kp, lp) <= kLdsBudget;
   }
 
   // ---- which kernel the plan selects ----

@@ -9,11 +9,17 @@ namespace {
 // T + S launch.  In the four-launch form it goes to memory (16 MB at C3), crosses a launch boundary and is loaded
 // again behind T + S's chain of dependent loads.  Here one grid has two roles, chosen per workgroup from blockIdx.x:
 //
-//   pair unit      one 64-pair unit of one rating (pairs_fused_kernel's mechanism without its A mat-vec: A(t) is in
-//                  the A table and is read as the segments' fixed rows)
-//                    eta rows of the unit -> es (asked for first, landed before the gathers: no register holds them)
+//   pair unit      one 64-pair unit of one rating (pairs_fused_kernel's mechanism; the unit computes the fixed rows A(t)
+//                  of its pairs itself -- it holds the eta rows and the rating's tile anyway -- and does not read the A table)
+//                    eta rows of the unit -> es, and transposed -> cst (asked for first, landed before the gathers: no
+//                             register holds them)
+//                    A[q,:] = pT_r eta[i_q,:]   the A launch's mat-vec (pair_block_kernel's A mode: lane = pair, wave =
+//                             chunk of four outputs, the same multiply-add order), its outputs held in registers until
+//                             every wave has read the eta transpose, then stored over it: cst[d][pair] = A[pair][d];
+//                             the first four theta rows of round 0 are asked for before it and travel under it
 //                    C[q,:] = sum_{n in pair q} theta[u_n,:] / max(theta[u_n,:] . A[q,:], eps)   seg_body's arithmetic,
-//                             two rounds of 32 eight-lane groups, each finished row into cst[d][pair]
+//                             two rounds of 32 eight-lane groups; a group reads column `pair` of cst (A) at the start of
+//                             its round and writes its finished C row into the same column at the end: no region of its own
 //                    barrier; S, T = p_r^T C and the slab exactly as pair_block_body<false, true, 1, false, 256, 2, false>
 //   user segments  seg_body<G, VEC, 4, 1>, unchanged
 //
@@ -24,16 +30,16 @@ namespace {
 // order of every sum are those of the separate launches: results are bitwise identical (tests/test_gpu_pass_dense.py).
 // ======================================================================================
 struct PassDenseArgs {
-  RowTab a_fixed;          // A(t): the pair segments' fixed rows
   RowTab theta;            // gathered by pair_user
   const int32_t *pair_off, *pair_user, *pair_item;
   const mmsbm::Chunk *chunks;  // one 64-pair unit each (empty ones: padding)
-  const double *p_tiles;   // p [R][kp][lp]
+  const double *p_tiles;   // p  [R][kp][lp]  (T mat-vec)
+  const double *pt_tiles;  // pT [R][lp][kp]  (A mat-vec)
   const double *eta;       // [I][lp]
   double *t_out;           // T [Q][lp]
   double *partial;         // one K x L slab per unit
   int kp, lp, spb, nsub;
-  int nt;                  // bit 0: T rows as non-temporal stores, bit 1: the segments' own rows as non-temporal loads
+  int nt;                  // bit 0: T rows as non-temporal stores
   int n_units;             // blocks [0, n_units) are pair units, the rest user workgroups
 };
 
@@ -42,11 +48,13 @@ __device__ __forceinline__ void pass_dense_unit(const PassDenseArgs &pa, int uni
   constexpr int CS = kUnitPairs + 1, KT = 2, TV = KT * 4, B = 4;
   constexpr int NGRP = kBlock / G, ROUNDS = kUnitPairs / NGRP;
   constexpr int CH = (G < 16) ? 2 * G : G;  // seg_body's index chunk
+  static_assert(B <= G, "the rows asked for ahead of the A mat-vec take their ids from a group's first G indices");
   constexpr int NE = 3;  // eta loads per thread (ev0 .. ev2): 64 pairs x <= 24 entries / 2 per load / 256 threads
   const int kp = pa.kp, lp = pa.lp;
   extern __shared__ double lds[];
-  double *cst = lds;                                // [kp][CS]  C rows of the unit, transposed
-  double *es = cst + static_cast<size_t>(kp) * CS;  // [64][lp]  gathered eta rows ...
+  // (shapes.hpp: pass_dense_lds)
+  double *cst = lds;                                // [max(kp, lp)][CS]  transposed: the unit's eta rows, then A, then C rows
+  double *es = cst + static_cast<size_t>(max(kp, lp)) * CS;  // [64][lp]  gathered eta rows ...
   double *tout = es;                                // ... then the T rows
   const mmsbm::Chunk ch = pa.chunks[unit];
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -55,6 +63,8 @@ __device__ __forceinline__ void pass_dense_unit(const PassDenseArgs &pa, int uni
   typedef const double __attribute__((address_space(4))) * const_tile_ptr;
   const const_tile_ptr gtile = (const_tile_ptr)(reinterpret_cast<uintptr_t>(
       pa.p_tiles + static_cast<size_t>(ch.rating) * kp * lp));
+  const const_tile_ptr gpt = (const_tile_ptr)(reinterpret_cast<uintptr_t>(
+      pa.pt_tiles + static_cast<size_t>(ch.rating) * lp * kp));
 
   // ---- level 1: the segments' ranges of both rounds and the item ids of this thread's eta elements ----
   int beg[ROUNDS], end[ROUNDS], ids[NE];
@@ -84,16 +94,81 @@ __device__ __forceinline__ void pass_dense_unit(const PassDenseArgs &pa, int uni
     m1 = (CH > G && cnt > 0) ? pa.pair_user[beg[0] + min(G + gl, cnt - 1)] : 0;
   }
   __builtin_amdgcn_sched_barrier(0);
-  if (tid * 2 < tot) *reinterpret_cast<double2 *>(es + tid * 2) = ev0;
-  if (tid * 2 + kBlock * 2 < tot) *reinterpret_cast<double2 *>(es + tid * 2 + kBlock * 2) = ev1;
-  if (tid * 2 + kBlock * 4 < tot) *reinterpret_cast<double2 *>(es + tid * 2 + kBlock * 4) = ev2;
-
-  // ---- the pair segments (seg_body's arithmetic): a group of G lanes per pair, its C row into cst ----
   const bool act = gl * VEC < kp;
   const int lane_off = act ? gl * VEC : 0;
   const bool g_main = lane_off < pa.theta.mw;
   const double *gbase = g_main ? pa.theta.main + lane_off : pa.theta.tail + (lane_off - pa.theta.mw);
   const size_t gstride = g_main ? pa.theta.rs_m : pa.theta.rs_t;
+  // ---- level 3: the first B theta rows of round 0, asked for ahead of the A mat-vec: they travel under it (the
+  // barriers below wait for LDS traffic only, not for vector loads).  The same rows, clamped the same way, as the first
+  // step of the segment loop would ask for; they land in the loop's own row registers.  Without this the unit gathers
+  // nothing while it multiplies: C3 +1.5 us per iteration, K = 32 with L = 24 slower than reading A from the table.
+  double g[B][VEC];
+  {
+    const int cnt = min(CH, end[0] - beg[0]);
+#pragma unroll
+    for (int b = 0; b < B; ++b) {
+      const int id = __shfl(m0, min(b, max(cnt - 1, 0)), G);
+      if (cnt > 0) load_vec<VEC>(gbase + static_cast<size_t>(id) * gstride, g[b]);  // (whole groups)
+    }
+  }
+  __builtin_amdgcn_sched_barrier(0);
+  const auto eta_put = [&](int j, const double2 &v) {  // row-major for S, transposed for the A mat-vec
+    const int t = tid * 2 + j * kBlock * 2;
+    if (t < tot) {
+      const int pr = t / lp, d = t - pr * lp;
+      *reinterpret_cast<double2 *>(es + t) = v;
+      cst[d * CS + pr] = v.x;
+      cst[(d + 1) * CS + pr] = v.y;
+    }
+  };
+  eta_put(0, ev0); eta_put(1, ev1); eta_put(2, ev2);
+  if (np < kUnitPairs) {  // ragged tail of a rating: the missing pairs are zero columns
+    for (int t = tid; t < (kUnitPairs - np) * lp; t += kBlock)
+      cst[(t / (kUnitPairs - np)) * CS + np + t % (kUnitPairs - np)] = 0.0;
+  }
+  __syncthreads();
+  // ---- A[q,:] = pT_r eta_q: lane = pair, wave = chunk of 4 outputs, the tile through scalar loads (pair_block's A
+  // mode, multiply-add for multiply-add).  kp <= 32: a wave has at most two chunks, eight outputs in named registers ----
+  {
+    const int nck = kp >> 2;
+    const int c0 = __builtin_amdgcn_readfirstlane(wave), c1 = c0 + kBlock / 64;
+    const auto a_chunk = [&](int c, double &a0, double &a1, double &a2, double &a3) {
+      for (int d = 0; d < lp; d += 4) {
+        double x[4];
+        double2 t0[4], t1[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          x[i] = cst[(d + i) * CS + lane];
+          const const_tile_ptr row = gpt + static_cast<size_t>(d + i) * kp + c * 4;  // uniform
+          t0[i].x = row[0]; t0[i].y = row[1];
+          t1[i].x = row[2]; t1[i].y = row[3];
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          a0 = fma(x[i], t0[i].x, a0);
+          a1 = fma(x[i], t0[i].y, a1);
+          a2 = fma(x[i], t1[i].x, a2);
+          a3 = fma(x[i], t1[i].y, a3);
+        }
+      }
+    };
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0, b0 = 0.0, b1 = 0.0, b2 = 0.0, b3 = 0.0;
+    if (c0 < nck) a_chunk(c0, a0, a1, a2, a3);
+    if (c1 < nck) a_chunk(c1, b0, b1, b2, b3);
+    __syncthreads();  // every wave has read the eta transpose: A, transposed, takes its place
+    if (c0 < nck) {
+      double *col = cst + c0 * 4 * CS + lane;
+      col[0] = a0; col[CS] = a1; col[2 * CS] = a2; col[3 * CS] = a3;
+    }
+    if (c1 < nck) {
+      double *col = cst + c1 * 4 * CS + lane;
+      col[0] = b0; col[CS] = b1; col[2 * CS] = b2; col[3 * CS] = b3;
+    }
+    __syncthreads();
+  }
+
+  // ---- the pair segments (seg_body's arithmetic): a group of G lanes per pair, its C row into cst ----
 #pragma unroll
   for (int r = 0; r < ROUNDS; ++r) {
     const int p = grp + r * NGRP;
@@ -101,27 +176,27 @@ __device__ __forceinline__ void pass_dense_unit(const PassDenseArgs &pa, int uni
 #pragma unroll
     for (int v = 0; v < VEC; ++v) acc[v] = 0.0;
     if (p < np) {  // (whole groups)
-      load_vec_in<VEC>(rowtab_ptr(pa.a_fixed, static_cast<size_t>(q0 + p), lane_off), f, (pa.nt & 2) != 0);
-      if (!act) {
 #pragma unroll
-        for (int v = 0; v < VEC; ++v) f[v] = 0.0;
-      }
+      for (int v = 0; v < VEC; ++v) f[v] = act ? cst[(lane_off + v) * CS + p] : 0.0;  // A(t)[q0 + p]: this group's column
       int mine0 = m0, mine1 = m1;
       if (r > 0) {  // (round 0's first indices were asked for beside the eta rows)
         const int cnt = min(CH, end[r] - beg[r]);
         mine0 = cnt > 0 ? pa.pair_user[beg[r] + min(gl, cnt - 1)] : 0;
         mine1 = (CH > G && cnt > 0) ? pa.pair_user[beg[r] + min(G + gl, cnt - 1)] : 0;
       }
+      bool ahead = r == 0;  // (the first step of round 0: its rows were asked for before the A mat-vec and are in g)
       for (int c0 = beg[r]; c0 < end[r]; c0 += CH) {
         const int cnt = min(CH, end[r] - c0);
         for (int n = 0; n < cnt; n += B) {
-          double g[B][VEC];
+          if (!ahead) {
 #pragma unroll
-          for (int b = 0; b < B; ++b) {
-            const int jj = min(n + b, cnt - 1);
-            const int id = __shfl((CH > G && jj >= G) ? mine1 : mine0, jj, G);
-            load_vec<VEC>(gbase + static_cast<size_t>(id) * gstride, g[b]);
+            for (int b = 0; b < B; ++b) {
+              const int jj = min(n + b, cnt - 1);
+              const int id = __shfl((CH > G && jj >= G) ? mine1 : mine0, jj, G);
+              load_vec<VEC>(gbase + static_cast<size_t>(id) * gstride, g[b]);
+            }
           }
+          ahead = false;
 #pragma unroll
           for (int b = 0; b < B; ++b) {
             if (n + b < cnt) {

@@ -53,6 +53,9 @@ inline size_t pair_block_lds(int dinp, int doutp, bool tile_lds) {
                    (tile_lds ? static_cast<size_t>(dinp) * doutp : 0);
   return d * sizeof(double);  // the S hand-over area reuses it (create() bounds the copies by it)
 }
+// dynamic LDS of pass_dense_kernel: pair_block's two regions, the first with max(kp, lp) rows -- it holds the unit's eta
+// rows, transposed (lp rows), before the A rows and then the C rows (kp rows each) take their place
+inline size_t pass_dense_lds(int kp, int lp) { return pair_block_lds(kp > lp ? kp : lp, lp, false); }
 
 // ---- the pair stage on the matrix cores (pair_mfma.hpp) ----
 constexpr int kMfmaMaxDim = 64;       // <= 4 tiles of 16 per side

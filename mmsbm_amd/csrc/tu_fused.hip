@@ -71,19 +71,20 @@ void stage_pass_dense(mmsbm_hip_ctx *c) {
   LaunchScope ls(c, K_SEG, true);
   const int s = c->base_slot, cur = c->cur, nt = nt_on(c);
   PassDenseArgs pa{};
-  pa.a_fixed = a_tab(c, cur); pa.theta = theta_tab(c, cur);
+  pa.theta = theta_tab(c, cur);
   pa.pair_off = c->pair_off.ptr; pa.pair_user = c->pair_user.ptr; pa.pair_item = c->pair_item.ptr;
-  pa.chunks = c->mv_chunks.ptr; pa.p_tiles = c->p[cur].at(s); pa.eta = c->eta[cur].at(s);
+  pa.chunks = c->mv_chunks.ptr; pa.p_tiles = c->p[cur].at(s); pa.pt_tiles = c->pt[cur].at(s); pa.eta = c->eta[cur].at(s);
   pa.t_out = c->ttab.at(s); pa.partial = c->partial.at(s);
   pa.kp = c->kp; pa.lp = c->lp; pa.spb = c->pp.spb; pa.nsub = c->pp.nsub;
-  pa.nt = (nt & 1) | ((nt & 4) ? 2 : 0);
+  pa.nt = nt & 1;
   const SegArgs su = seg_users_args(c, true, c->n_users);
   const int per = kBlock / group_lanes(c->code_k);
   pa.n_units = static_cast<int>(c->lay.mv_chunks.size());
   const int bu = (su.nseg + per - 1) / per;
-  allow_big_lds(pass_dense_kernel<8, 4>, c->pp.lds_t);
+  const size_t lds = pass_dense_lds(c->kp, c->lp);  // (pair_block_lds(kp, lp) unless lp > kp)
+  allow_big_lds(pass_dense_kernel<8, 4>, lds);
   LAUNCH_IN(ls, (pass_dense_kernel<8, 4>), dim3(static_cast<unsigned>(pa.n_units + bu), 1, 1), kBlock,
-            c->pp.lds_t, c->stream, pa, su, c->kp);
+            lds, c->stream, pa, su, c->kp);
   ls.done();
 }
 
