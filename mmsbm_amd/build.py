@@ -1,9 +1,9 @@
 """Compile the HIP library in-tree for gfx950 (hipcc cross-compiles without a GPU).
 
-The library is seventeen translation units (csrc/prelude.hpp lists them) compiled SIDE BY SIDE -- one hipcc per unit, as
-many at a time as the machine has cores -- and linked into one shared object: about 18 s on eight cores, where the
-single unit of earlier rounds took a minute.  csrc/unity.hip is all of them as one unit, for the diagnostic builds
-(`build_diagnostic`)."""
+The library is twenty-two translation units (csrc/prelude.hpp lists them) compiled SIDE BY SIDE -- one hipcc per unit, as
+many at a time as the machine has cores or the job may use (`build_workers`) -- and linked into one shared object: about
+18 s on eight cores at seventeen units, where the single unit of earlier rounds took a minute.  csrc/unity.hip is all of
+them as one unit, for the diagnostic builds (`build_diagnostic`)."""
 from __future__ import annotations
 
 import os
@@ -13,10 +13,11 @@ from concurrent.futures import ThreadPoolExecutor
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG_DIR, "csrc")
-# the translation units, longest compile first (tu_layout.hip and tu_pairs_bulk.hip carry rocPRIM's sorts; the host-only units -- the C ABI,
-# tu_create, tu_params, tu_iterate, tu_options -- take a few seconds each and fill the gaps at the end)
-UNITS = ("tu_layout", "tu_pairs_bulk", "tu_fused", "tu_once", "tu_seg", "tu_pair", "tu_etap", "tu_mfma", "tu_recommend", "mmsbm_hip", "tu_create",
-         "tu_fold_in", "tu_heldout", "tu_explain", "tu_params", "tu_iterate", "tu_options")
+# the translation units, longest compile first, each measured alone on eight cores (tu_pairs_bulk.hip 26 s and tu_layout.hip
+# 17 s carry rocPRIM's sorts, tu_fused.hip 10 s, tu_once.hip 8 s; every other unit takes 3 - 7 s and fills the gaps)
+UNITS = ("tu_pairs_bulk", "tu_layout", "tu_fused", "tu_once", "tu_market", "tu_pairs", "tu_rerank", "mmsbm_hip", "tu_seg",
+         "tu_pair", "tu_etap", "tu_recommend", "tu_create", "tu_explain", "tu_fold_in", "tu_serve_frame", "tu_mfma",
+         "tu_similar", "tu_heldout", "tu_params", "tu_iterate", "tu_options")
 OBJ_DIR = os.path.join(PKG_DIR, "_build")
 DEPS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".hpp"))) + [
     os.path.join(os.path.dirname(PKG_DIR), "include", "mmsbm_hip.h")]
@@ -82,6 +83,14 @@ def _compile_flags(sid: str) -> list:
             f'-DMMSBM_BUILD_ID="{sid}"', *EXTRA_FLAGS]
 
 
+def build_workers(n_units: int) -> int:
+    """Compilers build_library runs side by side: one per unit, but no more than MAX_JOBS, else
+    CMAKE_BUILD_PARALLEL_LEVEL, allows (the first that is a positive integer); neither set: the machine's cores."""
+    asked = (os.environ.get(name, "") for name in ("MAX_JOBS", "CMAKE_BUILD_PARALLEL_LEVEL"))
+    caps = [int(v) for v in asked if v.isdigit() and int(v) > 0]
+    return max(1, min(n_units, caps[0] if caps else os.cpu_count() or 1))
+
+
 def build_library(force: bool = False, verbose: bool = False) -> str:
     """hipcc --offload-arch=gfx950: csrc/<unit>.hip -> _build/<unit>.o side by side, then one link ->
     mmsbm_amd/libmmsbm_hip.so; returns its path."""
@@ -99,8 +108,7 @@ def build_library(force: bool = False, verbose: bool = False) -> str:
             print(" ".join(cmd), flush=True)
         return unit, obj, subprocess.run(cmd, capture_output=True, text=True)
 
-    workers = max(1, min(len(UNITS), os.cpu_count() or 1))
-    with ThreadPoolExecutor(max_workers=workers) as pool:
+    with ThreadPoolExecutor(max_workers=build_workers(len(UNITS))) as pool:
         done = list(pool.map(compile_unit, UNITS))
     objs = [obj for _, obj, _ in done]
     try:

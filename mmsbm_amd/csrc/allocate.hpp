@@ -19,11 +19,11 @@
 //          descending, user ascending); at least cap_i of them: tau_i = the cap_i-th key;
 //   stop   when no tau changed.  tau only rises, so it ends; then no item holds more than cap_i proposers and P is the
 //          answer.
-// On the device both passes are the batches of a top-N query (tu_recommend.hip) with ONE change: the score tile's
+// On the device both passes are the batches of a top-N query (serve_frame.hpp) with ONE change: the score tile's
 // epilogue compares each score with its column's key and its row's key in registers and stores -inf in place of a score
 // that fails either (alloc_score_kernel: rec_tile_acc, then the same single division rec_score_kernel stores).  The
 // exclusions and the selection that follow are recommend's own kernels (on the host: exclude_seen and one SelectStage
-// whose scratch serves both passes, tu_recommend.hip), so the scores are recommend_query's bits and the orders are its
+// whose scratch serves both passes, serve_frame.hpp), so the scores are recommend_query's bits and the orders are its
 // orders.  No atomics; nothing depends on the batch or grid shape.
 //   alloc_score_kernel   user pass: rows = the request's users, column keys = tau (by item), no row keys;
 //                        item pass: the tables exchanged as in recommend_query_items, rows = the capped items, row

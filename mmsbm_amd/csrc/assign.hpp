@@ -21,7 +21,7 @@
 // On the device the request's users stand in id order (row r), and a round runs over the COMPACTED list of active rows:
 //   assign_value_kernel   rec_tile_acc, the single division of rec_score_kernel, then s - p1[column] stored; rows = the
 //                         active users.  recommend's exclusion and selection kernels follow unchanged with n = 2
-//                         (on the host: exclude_seen and the SelectStage of tu_recommend.hip, batch by batch).
+//                         (on the host: exclude_seen and the SelectStage of serve_frame.hpp, batch by batch).
 //   assign_bid_kernel     one thread per active row: score(u, i1) by the tile's own fma chain (the same bits), the
 //                         bid or the drop-out flag, and the row's place for the sort
 //   (rocPRIM merge sort of the places by (item, bid descending, place): tu_pairs_bulk.hip)

@@ -3,7 +3,7 @@
 //   mmsbm_hip_recommend_query_items   the n best users of each requested item.  No kernel of its own: the session's
 //                       item table takes the x side of rec_score_kernel (rows = the requested item ids), the user table
 //                       the y side, the batch buffer has U columns, rec_exclude_kernel runs over the item -> users
-//                       lists, and top_n_run selects (tu_recommend.hip).  fma(a, b, c) is commutative in a, b, so the
+//                       lists, and top_n_run selects (serve_frame.hpp).  fma(a, b, c) is commutative in a, b, so the
 //                       exchanged tables give the bits of recommend_query.
 //   mmsbm_hip_recommend_audience      every candidate user of an item whose score reaches a bar, as a CSR, without a
 //                       score buffer (the answer holds anything from nothing to U x items entries):

@@ -11,7 +11,7 @@
 //     cat_exclude_kernel  -inf at col_of[item] for every listed item that is a candidate: once over the session's seen
 //                       lists (indexed by user id) when the session excludes, once over the query's own lists
 //                       (indexed by the row's place in the request, so a user asked twice may carry two lists);
-//     rec_select_kernel   (recommend.hpp, as it is; top_n_run of tu_recommend.hip) with I = C: the batch size and the
+//     rec_select_kernel   (recommend.hpp, as it is; top_n_run of serve_frame.hpp) with I = C: the batch size and the
 //                       split across waves follow C.  The host maps the returned columns through the candidate list.
 //                       A null candidate list is the whole catalogue: recommend_query's own launches, then
 //                       cat_exclude_kernel without col_of over the query's own lists.

@@ -219,6 +219,14 @@ struct LooSession {
   int slots = 0;                        // slots added
 };
 
+// The serving calls whose kernels are timed (mmsbm_hip_ctx::last_ms), in the order of their "<name>_ms" options:
+// recommend_query / recommend_query_items, fold_in / fold_in_items, recommend_positions, recommend_top_pairs,
+// recommend_audience, similar_query, overlap_query, heldout_eval / heldout_add, explain_query, recommend_diverse /
+// similar_pairs, inform_query / inform_query_theta, recommend_query_groups, recommend_query_ensemble / recommend_pair_spread,
+// loo_add / loo_rows / loo_sides / loo_lowest (and, of the last loo_add alone, its sums pass and its row pass),
+// recommend_allocate, recommend_top_pairs_bulk, recommend_assortment, recommend_assign
+enum TimedCall { T_RECOMMEND = 0, T_FOLD_IN, T_POSITIONS, T_TOP_PAIRS, T_AUDIENCE, T_SIMILAR, T_OVERLAP, T_HELDOUT, T_EXPLAIN, T_DIVERSE, T_INFORM, T_GROUP, T_ENSEMBLE, T_LOO, T_LOO_SUMS, T_LOO_ROWS, T_ALLOCATE, T_TOP_PAIRS_BULK, T_ASSORT, T_ASSIGN, T_COUNT };
+
 }  // namespace mmsbm_hip_impl
 
 namespace {
@@ -266,14 +274,6 @@ inline void sort_unique_groups(std::vector<int32_t> &off, std::vector<int32_t> &
   off.back() = w;
   val.resize(static_cast<size_t>(w));
 }
-
-// The serving calls whose kernels are timed (mmsbm_hip_ctx::last_ms), in the order of their "<name>_ms" options:
-// recommend_query / recommend_query_items, fold_in / fold_in_items, recommend_positions, recommend_top_pairs,
-// recommend_audience, similar_query, overlap_query, heldout_eval / heldout_add, explain_query, recommend_diverse /
-// similar_pairs, inform_query / inform_query_theta, recommend_query_groups, recommend_query_ensemble / recommend_pair_spread,
-// loo_add / loo_rows / loo_sides / loo_lowest (and, of the last loo_add alone, its sums pass and its row pass),
-// recommend_allocate, recommend_top_pairs_bulk, recommend_assortment, recommend_assign
-enum TimedCall { T_RECOMMEND = 0, T_FOLD_IN, T_POSITIONS, T_TOP_PAIRS, T_AUDIENCE, T_SIMILAR, T_OVERLAP, T_HELDOUT, T_EXPLAIN, T_DIVERSE, T_INFORM, T_GROUP, T_ENSEMBLE, T_LOO, T_LOO_SUMS, T_LOO_ROWS, T_ALLOCATE, T_TOP_PAIRS_BULK, T_ASSORT, T_ASSIGN, T_COUNT };
 
 enum KernelId { K_SEG = 0, K_DENSE, K_ETAP, K_MATVEC_A, K_FUSED_PAIRS, K_FUSED_TAIL, K_COUNT };
 // The four launches of an iteration -- or, for small problems, the two of fused_small.hpp.  With pass_dense.hpp the
@@ -446,6 +446,10 @@ struct LaunchScope {
 
 void use_device(const mmsbm_hip_ctx *c) { HIP_CHECK(hipSetDevice(c->device)); }
 
+}  // namespace
+
+namespace mmsbm_hip_impl {  // (an argument of the serving frame, serve_frame.hpp: one type in every translation unit)
+
 // Device time between two points of a stream: start() and stop() record, ms() reads it once the stream has passed
 // stop().  The events are destroyed on every way out of the scope.
 struct EventPair {
@@ -466,5 +470,4 @@ struct EventPair {
   }
 };
 
-
-}  // namespace
+}  // namespace mmsbm_hip_impl

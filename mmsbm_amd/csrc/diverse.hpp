@@ -6,7 +6,7 @@
 // Request row b, user u = users[b]:
 //   pool   P = the row recommend_query_within(n = pool) returns -- ids, score bits and order (score descending, equal
 //          scores by ascending item id); M = |P|.  It is selected by rec_select_kernel as it is (top_n_run's batches,
-//          tu_recommend.hip) and stays on the device;
+//          serve_frame.hpp) and stays on the device;
 //   pick 1 t_1 = P[0];
 //   pick j for j = 2 .. min(n, M): over every i of P not picked yet, m_i = min over a < j of D(t_a, i),
 //          v_i = fma(trade_off, m_i, score_i) -- ONE rounding -- and t_j = the i with the largest v_i, equal v_i (as

@@ -36,7 +36,7 @@
 //   grp_mean_kernel     xbar[s][g][j] = (x_s[m_0, j] + x_s[m_1, j] + ...) / |g|: one chain from +0.0 in the request's
 //                       member order.  rec_score_kernel then runs over xbar (its users are 0 .. G - 1): no new score
 //                       code, and a group of one gets its member's row back (0.0 + x = x, x / 1 = x).
-// Selection and merge: rec_select_kernel through top_n_run (tu_recommend.hip), rows = groups.  No atomics.
+// Selection and merge: rec_select_kernel through top_n_run (serve_frame.hpp), rows = groups.  No atomics.
 #pragma once
 
 namespace {

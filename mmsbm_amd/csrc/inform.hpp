@@ -20,7 +20,7 @@
 //   inf_score_kernel    the gain tile (64 users x 64 items per workgroup, 4 x 4 outputs per thread; theta rows and the
 //                       (k, r) slices of q staged through LDS 16 k at a time) writes gain, or -inf where the candidate
 //                       mask (one byte per item, optional) is 0, into the batch buffer [users][items];
-//   rec_exclude_kernel / cat_exclude_kernel, rec_select_kernel and the merge, as they are (top_n_run, tu_recommend.hip).
+//   rec_exclude_kernel / cat_exclude_kernel, rec_select_kernel and the merge, as they are (top_n_run, serve_frame.hpp).
 // Determinism: an output is built as
 //   for s ascending:  for r ascending:  m_r = ONE fma chain over k ascending from +0.0 of theta[u,k] q[i,k,r];
 //                                        H += phi(m_r)                                        (H from +0.0)

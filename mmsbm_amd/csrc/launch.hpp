@@ -40,12 +40,14 @@ void predict_begin(mmsbm_hip_ctx *c, int64_t n_rows, const int32_t *user, const 
 void predict_add(mmsbm_hip_ctx *c, double *stats);
 void predict_finish(mmsbm_hip_ctx *c, double *mean_dist, double *stats);
 
-// tu_recommend.hip -- top-N recommendation (recommend.hpp): the session of mmsbm_hip_recommend_*, arguments checked
+// tu_serve_frame.hip -- the out-of-line half of the serving frame (serve_frame.hpp declares the rest of it); of use
+// beyond the serving units:
 // MMSBM_E_TOOLARGE "<what> needs ... MB of device memory" unless `bytes` (plus 64 MB) are free (fold-in too)
 void require_free_mem(size_t bytes, const std::string &what);
 // the training rows' external ids in the order they were given, with their ratings on request (null: not wanted)
 void train_id_columns(mmsbm_hip_ctx *c, std::vector<int32_t> &user, std::vector<int32_t> &item,
                       std::vector<int32_t> *rating);
+// tu_recommend.hip -- top-N recommendation (recommend.hpp): the session of mmsbm_hip_recommend_*, arguments checked
 void recommend_begin(mmsbm_hip_ctx *c, const double *weights, int exclude_train);
 void recommend_add(mmsbm_hip_ctx *c);  // the selected slot (the caller holds a OneSlot)
 void recommend_query(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, int n, int32_t *items, double *scores,
@@ -56,22 +58,6 @@ void recommend_positions(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users
                          const int32_t *items, int32_t *positions, int32_t *candidates);
 void recommend_add_items(mmsbm_hip_ctx *c, int32_t n_new, const double *eta, const int64_t *seen_offsets,
                          const int32_t *seen_users);
-// ... the m best pairs of the whole model (top_pairs.hpp): users ascending and distinct
-void recommend_top_pairs(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, int m, int32_t *out_users,
-                         int32_t *out_items, double *out_scores, int32_t *count);
-// ... the same question for m up to MMSBM_HIP_TOP_PAIRS_BULK_MAX_M (pairs_bulk.hpp): users ascending and distinct;
-// out_* null: the bar and the counts alone; counts: above the bar, at the bar, candidates
-void recommend_top_pairs_bulk(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, int64_t m, int32_t *out_users,
-                              int32_t *out_items, double *out_scores, int64_t *count, double *bar, int64_t counts[3]);
-// tu_pairs_bulk.hip -- its device sorts: n keys descending; n (user << 32 | item, score) entries into the query's order
-void pairs_bulk_sort_desc(mmsbm_hip_ctx *c, const uint64_t *keys, uint64_t *sorted, size_t n);
-void pairs_bulk_order(mmsbm_hip_ctx *c, const uint64_t *key, const double *score, size_t n, uint64_t *out_key,
-                      double *out_score);
-// ... item-side queries of the session (audience.hpp): item ids inside the session's catalogue
-void recommend_query_items(mmsbm_hip_ctx *c, int64_t n_items, const int32_t *items, int n, int32_t *users,
-                           double *scores, int32_t *counts);
-void recommend_audience(mmsbm_hip_ctx *c, int64_t n_items, const int32_t *items, double min_score, int64_t capacity,
-                        int64_t *offsets, int32_t *users, double *scores);
 // ... queries within a part of the catalogue (catalogue.hpp): cand ascending, distinct ids of the session's catalogue
 // (null: all of it); excl_*: the query's own excluded items by request row (null: none); recommend_rank: one ascending,
 // distinct candidate list per request row
@@ -104,7 +90,8 @@ void recommend_query_theta_shelves(mmsbm_hip_ctx *c, int64_t n_users, const doub
                                    const int32_t *seen_items, const int32_t *cand, int n_cand, int64_t n_cats,
                                    const int64_t *cat_offsets, const int32_t *cat_items, const ShelfAsk &ask,
                                    const ShelfOut &out);
-// ... randomised top-N with propensities (explore.hpp): recommend_query_within's request, a temperature above the
+// tu_rerank.hip -- the queries of the recommend session that add a stage of their own to the frame, arguments checked.
+// Randomised top-N with propensities (explore.hpp): recommend_query_within's request, a temperature above the
 // session's floor and the four words of a PCG64 stream; the propensities of caller-given lists (list_offsets int64
 // [n_users + 1], distinct items per row); r and g of given (user, item) pairs, no session needed
 void recommend_query_explore(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, const int32_t *cand, int n_cand,
@@ -117,6 +104,41 @@ void recommend_list_propensity(mmsbm_hip_ctx *c, int64_t n_users, const int32_t 
                                double *propensity);
 void explore_noise(mmsbm_hip_ctx *c, const uint64_t pcg64_state[4], int64_t n_pairs, const int32_t *users,
                    const int32_t *items, double *r, double *g);
+// ... and the ensemble-aware queries of the recommend session (ensemble.hpp), arguments checked: mode:
+// MMSBM_HIP_ENSEMBLE_*; cand / excl_* as in recommend_query_within; stats [n_pairs][4], per_slot [S][n_pairs] or null
+void recommend_query_ensemble(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, int mode, double risk,
+                              const int32_t *cand, int n_cand, const int64_t *excl_offsets, const int32_t *excl_items,
+                              int n, int32_t *items, double *scores, int32_t *counts);
+void recommend_pair_spread(mmsbm_hip_ctx *c, int64_t n_pairs, const int32_t *users, const int32_t *items, double *stats,
+                           double *per_slot);
+// ... and the group queries of the recommend session (group.hpp), arguments checked: group g's members are
+// members[offsets[g] .. offsets[g + 1]), distinct; mode: MMSBM_HIP_GROUP_*; cand as in recommend_query_within
+void recommend_query_groups(mmsbm_hip_ctx *c, int64_t n_groups, const int64_t *offsets, const int32_t *members, int mode,
+                            double bar, const int32_t *cand, int n_cand, int n, int32_t *items, double *scores,
+                            int32_t *counts);
+// ... and the two queries of diverse.hpp, arguments checked: the distance of given pairs of the similarity session's
+// side, and the diversified top-N, which reads the recommend session and the similarity session (side items)
+void similar_pairs(mmsbm_hip_ctx *c, int64_t n_pairs, const int32_t *a, const int32_t *b, double *distance);
+void recommend_diverse(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, const int32_t *cand, int n_cand,
+                       const int64_t *excl_offsets, const int32_t *excl_items, int n, int pool, double trade_off,
+                       int32_t *items, double *scores, double *distances, int32_t *counts);
+// tu_pairs.hip -- the m best pairs of the whole model (top_pairs.hpp): users ascending and distinct
+void recommend_top_pairs(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, int m, int32_t *out_users,
+                         int32_t *out_items, double *out_scores, int32_t *count);
+// ... the same question for m up to MMSBM_HIP_TOP_PAIRS_BULK_MAX_M (pairs_bulk.hpp): users ascending and distinct;
+// out_* null: the bar and the counts alone; counts: above the bar, at the bar, candidates
+void recommend_top_pairs_bulk(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, int64_t m, int32_t *out_users,
+                              int32_t *out_items, double *out_scores, int64_t *count, double *bar, int64_t counts[3]);
+// tu_pairs_bulk.hip -- its device sorts: n keys descending; n (user << 32 | item, score) entries into the query's order
+void pairs_bulk_sort_desc(mmsbm_hip_ctx *c, const uint64_t *keys, uint64_t *sorted, size_t n);
+void pairs_bulk_order(mmsbm_hip_ctx *c, const uint64_t *key, const double *score, size_t n, uint64_t *out_key,
+                      double *out_score);
+// tu_market.hip -- the item side and capacity.  Item-side queries of the recommend session (audience.hpp): item ids inside
+// the session's catalogue
+void recommend_query_items(mmsbm_hip_ctx *c, int64_t n_items, const int32_t *items, int n, int32_t *users,
+                           double *scores, int32_t *counts);
+void recommend_audience(mmsbm_hip_ctx *c, int64_t n_items, const int32_t *items, double min_score, int64_t capacity,
+                        int64_t *offsets, int32_t *users, double *scores);
 // ... capacity-aware allocation (allocate.hpp): every user of the request (distinct ids) asks for n items, the caps as
 // planned by plan_allocate (serve_plan.hpp); at most max_rounds rounds
 void recommend_allocate(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, int n, const AllocPlan &plan,
@@ -135,39 +157,17 @@ void recommend_assign(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, c
 size_t assign_sort_bytes(size_t n);
 void assign_sort_bids(hipStream_t st, void *tmp, size_t bytes, const int32_t *item, const double *bid,
                       const uint32_t *place, uint32_t *sorted, size_t n);
-// ... and nearest items / users (similar.hpp): the session of mmsbm_hip_similar_*, arguments checked
-void similar_begin(mmsbm_hip_ctx *c, int side);
-void similar_add(mmsbm_hip_ctx *c);  // the selected slot (the caller holds a OneSlot)
-void similar_query(mmsbm_hip_ctx *c, int64_t n_rows, const int32_t *ids, int n, int32_t *out_ids, double *distance,
-                   int32_t *counts);
-// ... and the two queries of diverse.hpp, arguments checked: the distance of given pairs of the similarity session's
-// side, and the diversified top-N, which reads the recommend session and the similarity session (side items)
-void similar_pairs(mmsbm_hip_ctx *c, int64_t n_pairs, const int32_t *a, const int32_t *b, double *distance);
-void recommend_diverse(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, const int32_t *cand, int n_cand,
-                       const int64_t *excl_offsets, const int32_t *excl_items, int n, int pool, double trade_off,
-                       int32_t *items, double *scores, double *distances, int32_t *counts);
-// ... and the group queries of the recommend session (group.hpp), arguments checked: group g's members are
-// members[offsets[g] .. offsets[g + 1]), distinct; mode: MMSBM_HIP_GROUP_*; cand as in recommend_query_within
-void recommend_query_groups(mmsbm_hip_ctx *c, int64_t n_groups, const int64_t *offsets, const int32_t *members, int mode,
-                            double bar, const int32_t *cand, int n_cand, int n, int32_t *items, double *scores,
-                            int32_t *counts);
 // ... and greedy assortment selection in the recommend session (assortment.hpp), arguments checked: users ascending and
 // distinct; mode: MMSBM_HIP_ASSORT_*; level: the floor or the bar; cand as in recommend_query_within
 void recommend_assortment(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, int mode, double level,
                           const int32_t *given, int n_given, const int32_t *cand, int n_cand, int n_pick, int32_t *items,
                           double *gains, int32_t *count, int32_t *stop, double *given_gains, int32_t *served_items,
                           double *served_scores);
-// ... and the ensemble-aware queries of the recommend session (ensemble.hpp), arguments checked: mode:
-// MMSBM_HIP_ENSEMBLE_*; cand / excl_* as in recommend_query_within; stats [n_pairs][4], per_slot [S][n_pairs] or null
-void recommend_query_ensemble(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, int mode, double risk,
-                              const int32_t *cand, int n_cand, const int64_t *excl_offsets, const int32_t *excl_items,
-                              int n, int32_t *items, double *scores, int32_t *counts);
-void recommend_pair_spread(mmsbm_hip_ctx *c, int64_t n_pairs, const int32_t *users, const int32_t *items, double *stats,
-                           double *per_slot);
-// ... and the overlap of the restarts' groups (overlap.hpp): the session of mmsbm_hip_overlap_*, arguments checked
-void overlap_begin(mmsbm_hip_ctx *c, int side);
-void overlap_add(mmsbm_hip_ctx *c);  // the selected slot (the caller holds a OneSlot)
-void overlap_query(mmsbm_hip_ctx *c, double *out);
+// tu_similar.hip -- nearest items / users (similar.hpp): the session of mmsbm_hip_similar_*, arguments checked
+void similar_begin(mmsbm_hip_ctx *c, int side);
+void similar_add(mmsbm_hip_ctx *c);  // the selected slot (the caller holds a OneSlot)
+void similar_query(mmsbm_hip_ctx *c, int64_t n_rows, const int32_t *ids, int n, int32_t *out_ids, double *distance,
+                   int32_t *counts);
 // ... and the most informative items of a user (inform.hpp): the session of mmsbm_hip_inform_*, arguments checked;
 // cand / excl_* as in recommend_query_within, seen_* as in recommend_query_theta
 void inform_begin(mmsbm_hip_ctx *c);
@@ -179,6 +179,10 @@ void inform_query_theta(mmsbm_hip_ctx *c, int64_t n_users, const double *theta, 
                         const int32_t *seen_items, const int32_t *cand, int n_cand, int n, int32_t *items,
                         double *gains, int32_t *counts);
 void inform_mean_theta(mmsbm_hip_ctx *c, double *out);
+// ... and the overlap of the restarts' groups (overlap.hpp): the session of mmsbm_hip_overlap_*, arguments checked
+void overlap_begin(mmsbm_hip_ctx *c, int side);
+void overlap_add(mmsbm_hip_ctx *c);  // the selected slot (the caller holds a OneSlot)
+void overlap_query(mmsbm_hip_ctx *c, double *out);
 
 // tu_fold_in.hip -- fold new users (items_side: new items) into the selected slot's fitted eta (theta) and p
 // (fold_in.hpp), arguments checked; x0, x: theta0, theta (eta0, eta); items_side: item[m] in [0, n_new), user[m] in [0, U)

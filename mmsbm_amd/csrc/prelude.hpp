@@ -16,15 +16,19 @@
 //   tu_once.hip    once-per-run kernels with the host side of their entries: likelihood, prod_dist / predict, omegas,
 //                  the random start
 //   tu_layout.hip  the layout's sorts on the device (rocPRIM)
-//   tu_recommend.hip  the serving queries, planned by serve_plan.hpp, one header of kernels each:
-//                       recommend.hpp  top-N recommendation        similar.hpp    nearest items / users
-//                       top_pairs.hpp  the m best pairs            overlap.hpp    the overlap of the restarts' groups
-//                       audience.hpp   item-side queries           catalogue.hpp  queries within a part of the catalogue
-//                       diverse.hpp    the diversified top-N       inform.hpp     the most informative items of a user
-//                       group.hpp      group queries               ensemble.hpp   how far the restarts agree on a pair
-//                       pairs_bulk.hpp the m best pairs beyond 1,024, planned by pairs_bulk_plan.hpp
-//                       assortment.hpp greedy assortment selection: rounds chained on the stream behind a stop flag
-//                       assign.hpp     welfare-maximising assignment: rounds of a forward auction over the active users
+// the serving queries, planned by serve_plan.hpp, in the frame of serve_frame.hpp; one unit per query family, one header of
+// kernels per query, and every kernel launched from exactly one unit:
+//   tu_serve_frame.hip the frame's out-of-line half: the kernels several families share (recommend.hpp's weights, fold,
+//                      score tile, seen exclusion and selection; catalogue.hpp's compact table and exclusions by column)
+//   tu_recommend.hip  the recommend session and its plain queries: recommend.hpp (top-N, positions), catalogue.hpp (within
+//                     a part of the catalogue, ranking), quota.hpp (capped categories), shelves.hpp (category level)
+//   tu_rerank.hip     queries with a stage of their own: explore.hpp (randomised top-N), ensemble.hpp (how far the
+//                     restarts agree), group.hpp (group queries), diverse.hpp (the diversified top-N, pair distances)
+//   tu_pairs.hip      top_pairs.hpp (the m best pairs), pairs_bulk.hpp (beyond 1,024, planned by pairs_bulk_plan.hpp)
+//   tu_market.hip     the item side and capacity: audience.hpp (item-side queries), allocate.hpp (capacity-aware
+//                     allocation), assign.hpp (welfare-maximising assignment), assortment.hpp (greedy assortment)
+//   tu_similar.hip    the other sessions: similar.hpp (nearest items / users), inform.hpp (the most informative items of a
+//                     user), overlap.hpp (the overlap of the restarts' groups)
 //   tu_pairs_bulk.hip the device sorts of pairs_bulk.hpp and assign.hpp (rocPRIM)
 //   tu_fold_in.hip    fold new users into a fitted model (fold_in.hpp)
 //   tu_heldout.hip    held-out log-likelihood of every restart slot (heldout.hpp)

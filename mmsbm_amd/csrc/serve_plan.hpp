@@ -1,4 +1,4 @@
-// serve_plan.hpp -- the launch plans of the serving queries (tu_recommend.hip) as plain values: the batches of a top-N
+// serve_plan.hpp -- the launch plans of the serving queries (serve_frame.hpp) as plain values: the batches of a top-N
 // query and its item split, the selection's list and scratch (SelectPlan), the blocks / runs / fragments of a group query, the COUNT batches and
 // WRITE runs of an audience query, the rows per call of a diversified query.  Host arithmetic on plain numbers only -- no
 // HIP type, no context -- so that the rules a kernel's block index depends on are checked on the CPU over every shape

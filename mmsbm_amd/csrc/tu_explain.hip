@@ -1,9 +1,11 @@
 // tu_explain.hip -- translation unit of the explanation of a recommendation (explain.hpp): the session's host side --
-// the training rows of every external user, the per-slot copies, the batches of a query.  It launches rec_w_kernel and
-// rec_fold_kernel of recommend.hpp for the slots' tables and shares that header's candidate list and fold_in.hpp's v.
+// the training rows of every external user, the per-slot copies, the batches of a query.  The slots' tables are folded by
+// the serving frame (serve_frame.hpp: fold_weights, fold_rows); recommend.hpp's candidate list and fold_in.hpp's v are
+// shared as device code.
 // Also the host side of the leave-one-out reliability of the training rows (loo.hpp), which rests on the same identity
 // and shares the same two headers.
 #include "prelude.hpp"
+#include "serve_frame.hpp"
 #include "recommend.hpp"
 #include "fold_in.hpp"
 #include "explain.hpp"
@@ -54,17 +56,10 @@ void explain_add(mmsbm_hip_ctx *c) {  // the selected slot (the caller holds a O
   double *po = grow_by_slot(ex.p, ps, S, st, np), *eo = grow_by_slot(ex.eta, es, S, st, ne);
   wk.alloc(kl);
   const ExtSlot e = ext_slot(c);
-  LAUNCH(rec_w_kernel, static_cast<unsigned>((kl + kBlock - 1) / kBlock), kBlock, 0, st, e.p, ex.w.ptr, wk.ptr, K, L, R,
-         e.rs, e.ks, e.ls);
-  auto fold = [&](const RowTab &src, int d, const double *m, int mt, int mj, double *out, int rows, int rank) {
-    const size_t n = static_cast<size_t>(rows) * rank;
-    if (n == 0) return;
-    LAUNCH(rec_fold_kernel, static_cast<unsigned>((n + kBlock - 1) / kBlock), kBlock, 0, st, src, d, m, mt, mj, out,
-           rows, rank);
-  };
-  fold(e.users, K, nullptr, 0, 0, to, U, K);   // theta as it is
-  fold(e.items, L, wk.ptr, 1, L, go, I, K);    // G[i, k] = sum_l eta[i, l] W[k, l]: recommend_add's y where K <= L
-  fold(e.items, L, nullptr, 0, 0, eo, I, L);   // eta as it is
+  fold_weights(st, e.p, ex.w.ptr, wk.ptr, K, L, R, e.rs, e.ks, e.ls);
+  fold_rows(c, false, nullptr, 0, 0, to, K);   // theta as it is
+  fold_rows(c, true, wk.ptr, 1, L, go, K);     // G[i, k] = sum_l eta[i, l] W[k, l]: recommend_add's y where K <= L
+  fold_rows(c, true, nullptr, 0, 0, eo, L);    // eta as it is
   if (ps > 0)
     LAUNCH(exp_p_kernel, static_cast<unsigned>((ps + kBlock - 1) / kBlock), kBlock, 0, st, e.p, e.rs, e.ks, e.ls, K, L,
            R, po);

@@ -17,7 +17,12 @@
 #include "tu_fused.hip"
 #include "tu_once.hip"
 #include "tu_layout.hip"
+#include "tu_serve_frame.hip"
 #include "tu_recommend.hip"
+#include "tu_rerank.hip"
+#include "tu_pairs.hip"
+#include "tu_market.hip"
+#include "tu_similar.hip"
 #include "tu_pairs_bulk.hip"
 #include "tu_fold_in.hip"
 #include "tu_heldout.hip"

@@ -148,7 +148,7 @@ def bits(a):
     return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
 
 
-# ---- launch shapes of tu_recommend.hip, restated --------------------------------------------------------------------
+# ---- launch shapes of the serving frame (serve_frame.hpp), restated --------------------------------------------------------------------
 REC_MIN_PER, POS_MIN_PER = 1024, 2048     # kRecMinPerPart, kPosMinPerPart
 REC_WAVES_PER_CU, POS_GROUPS_PER_CU = 32, 8
 CU_COUNTS = (64, 104, 110, 120, 128, 208, 220, 228, 240, 256, 304)
