@@ -275,9 +275,7 @@ inline void sort_unique_groups(std::vector<int32_t> &off, std::vector<int32_t> &
   val.resize(static_cast<size_t>(w));
 }
 
-enum KernelId { K_SEG = 0, K_DENSE, K_ETAP, K_MATVEC_A, K_FUSED_PAIRS, K_FUSED_TAIL, K_COUNT };
-// The four launches of an iteration -- or, for small problems, the two of fused_small.hpp.  With pass_dense.hpp the
-// merged launch (pass_dense_kernel) is timed as stage K_SEG and K_DENSE has no launch: the names stay as they are.
+// the stages by KernelId (step_plan.hpp)
 const char *const kKernelNames[K_COUNT] = {"seg_pass_kernel", "pair_block_kernel(T+S)", "eta_p_kernel",
                                            "pair_block_kernel(A)", "pairs_fused_kernel", "tail_fused_kernel"};
 
@@ -309,20 +307,15 @@ struct mmsbm_hip_ctx {
   DevBuf<double> btab;                // [I * R][kp], of the slot being scored
   bool predict_fast = true;
   int seg_batch = 4;  // row gathers a group of seg_pass keeps in flight (4, or 8)
-  bool fused = false;          // small problems: two launches per iteration (fused_small.hpp)
-  bool fused_forced = false;   // option "fused" = 1: whatever the size (else: while ratings x restart slots x (K + L) <= 14M)
-  // ... with segments that are cut into pieces (uneven degrees): every segment's pieces inside one workgroup
-  // (layout.hpp: FusedLists), pair side (the units of pairs_fused_kernel) and / or user side (blocks of tail_fused_kernel)
-  bool fs_pairs = false, fs_users = false;
+  // the iteration's form -- two launches (fused_small.hpp), three (pass_dense.hpp) or four: what was asked for and the
+  // facts about the data that decide it (step_plan.hpp)
+  StepPlan step;
+  // the whole-segment lists of the two-launch form (step.fs_pairs / step.fs_users; layout.hpp: FusedLists)
   DevBuf<mmsbm::FusedUnit> fp_units, fu_units;
   DevBuf<mmsbm::WorkItem> fp_items, fu_items;
   DevBuf<mmsbm::FusedSplit> fp_splits, fu_splits;
   int fp_max_parts = 0, fu_max_parts = 0, fu_blocks = 0;
-  // big problems of small tiles: the triple passes and the T + S stage of a committed iteration in one launch, three
-  // launches per iteration (pass_dense.hpp).  Option "pass_dense": -1 the library's choice by size, 0 off, 1 on wherever
-  // the form applies
-  int pass_dense = -1;
-  std::vector<char> a_ok;      // per slot: atab[cur] holds A of the CURRENT parameters (the fused form computes A at
+  std::vector<char> a_ok;     // per slot: atab[cur] holds A of the CURRENT parameters (the fused form computes A at
                                // the start of an iteration, so after a committed fused iteration it does not)
   int nt_out = 7;          // option "nt_out" (bits: 1 T and A rows, 2 theta' rows as non-temporal stores, 4 the segments' own rows as non-temporal loads) where that pays (nt_on, launch.hpp)
   int ranges_pairs = 1, ranges_users = 1;  // XCD-local work lists: ranges the gathered table is cut into
@@ -391,6 +384,8 @@ struct mmsbm_hip_ctx {
   bool profiling = false;
   std::vector<std::pair<int, std::pair<hipEvent_t, hipEvent_t>>> prof_events;
 
+  // the form of the next iteration of the slots [base_slot, base_slot + launch_slots), under the options in force
+  StepForm form(bool commit) const { return step.form(pp, launch_slots, commit); }
   void drop_graphs() {
     for (auto &g : graph_exec) {
       if (g) (void)hipGraphExecDestroy(g);

@@ -214,19 +214,11 @@ void loo_sides(mmsbm_hip_ctx *c, double *user_surprise, double *user_fitted_surp
 void loo_lowest(mmsbm_hip_ctx *c, int m, const uint8_t *user_flags, const uint8_t *item_flags, int64_t *rows,
                 double *reliability, int32_t *count);
 
-// tu_iterate.hip -- the EM iteration: the form the context's shape and options select, its order of launches, the
+// tu_iterate.hip -- the EM iteration: the launches of the form the context's StepPlan gives (step_plan.hpp), the
 // cur / a_ok / graph_exec state machine, and the timers.  Dispatchers first:
 void stage_dense(mmsbm_hip_ctx *c);
 void stage_matvec_a(mmsbm_hip_ctx *c, int slot, int a_slot, bool grid = false);
 void ensure_a(mmsbm_hip_ctx *c);  // atab[cur] = A of the current parameters, for every slot the next launches cover
-// the two-launch form of small problems: its kernels exist for the shape; ... and the data's segments are whole inside a
-// workgroup; the size up to which create() builds its lists and turns it on
-bool fused_shape_ok(const mmsbm_hip_ctx *c);
-bool fused_possible(const mmsbm_hip_ctx *c);
-constexpr long long kFusedRatingsMax = 1500000;
-// the form the next (committed) iteration takes: two launches; the triple passes and T + S in one (three launches)
-bool use_fused(const mmsbm_hip_ctx *c);
-bool use_pass_dense(const mmsbm_hip_ctx *c);
 // one iteration of the slots [base_slot, base_slot + launch_slots); commit off: the raw numerators stay in the other
 // buffers and cur does not move (update_coefficients).  run_iterations: n committed ones, replayed from a captured
 // graph two at a time when "graph" is on

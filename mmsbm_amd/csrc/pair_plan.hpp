@@ -74,7 +74,7 @@ struct PairPlan {
   // The plan's share of "the two-launch iteration exists for this shape" (fused_small.hpp): rows of up to 24 groups --
   // beyond that the four-launch stage runs 512-thread workgroups, whose split of a unit's pairs among the copies of the
   // slab grid (hence the association order of S) 256 threads cannot mirror
-  bool fused_shape_ok() const {
+  bool two_shape_ok() const {
     return threads_t == kBlock && threads_a == kBlock && !tl_t && !tl_a && nacc == 1 && kt == 2 && spb * nsub <= kBlock &&
            !wide && !mfma && !mfma_big && !direct_out && chunk_pairs == mmsbm::kMvChunkPairs &&
            pairs_fused_lds(kp, lp) <= kLdsBudget;

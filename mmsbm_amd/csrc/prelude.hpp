@@ -60,6 +60,7 @@
 #include "common.hpp"
 #include "shapes.hpp"
 #include "pair_plan.hpp"
+#include "step_plan.hpp"
 #include "serve_plan.hpp"
 #include "pairs_bulk_plan.hpp"
 #include "stamps.hpp"

@@ -193,6 +193,15 @@ void build_range_worklists(mmsbm_hip_ctx *c, const CreateKnobs &knobs, bool gpu_
   c->ranges_users = ru;
 }
 
+// The facts about the data that the form of an iteration is decided by (step_plan.hpp), once the pair stage's plan and
+// the work lists stand; build_fused_lists() adds the whole-segment lists it builds
+void plan_step(mmsbm_hip_ctx *c) {
+  StepPlan &s = c->step;
+  s.n_obs = c->n_obs; s.kp = c->kp; s.lp = c->lp; s.code_k = c->code_k; s.code_l = c->code_l; s.n_chunks = c->n_chunks;
+  s.items_pairs = !c->lay.pair_work.items.empty(); s.items_users = !c->lay.user_work.items.empty();
+  s.cut_pairs = !c->lay.pair_work.splits.empty(); s.cut_users = !c->lay.user_work.splits.empty();
+}
+
 // Whole pair segments for the workgroups of the two-launch form: the 64-pair units rebuilt with at most 64 work items
 // each.  The capped unit list REPLACES the plain one -- both forms of the iteration then run it, so that their S sums
 // associate the same way -- but only once it is certain that the two-launch form can use it: a pair of more than 64
@@ -208,11 +217,11 @@ void build_fused_pair_lists(mmsbm_hip_ctx *c) {
       c->fp_splits.upload(fl.splits, c->stream);
       HIP_CHECK(hipStreamSynchronize(c->stream));  // (`fl` is a local)
       c->fp_max_parts = fl.max_parts;
-      c->fs_pairs = true;
+      c->step.fs_pairs = true;
     }
   }
-  if (!c->fs_pairs) { c->lay.mv_chunks = plain_chunks; c->lay.mv_chunk_off = plain_off; }
-  c->n_chunks = static_cast<int>(c->lay.mv_chunks.size());  // (either list)
+  if (!c->step.fs_pairs) { c->lay.mv_chunks = plain_chunks; c->lay.mv_chunk_off = plain_off; }
+  c->n_chunks = c->step.n_chunks = static_cast<int>(c->lay.mv_chunks.size());  // (either list)
 }
 // ... and whole user segments: a user whose pieces' partial rows exceed the LDS budget leaves the data with the
 // separate launches
@@ -227,16 +236,15 @@ void build_fused_user_lists(mmsbm_hip_ctx *c, const CreateKnobs &knobs) {
   HIP_CHECK(hipStreamSynchronize(c->stream));  // (`fl` is a local)
   c->fu_max_parts = fl.max_parts;
   c->fu_blocks = static_cast<int>(fl.units.size());
-  c->fs_users = true;
+  c->step.fs_users = true;
 }
 // Small problems with uneven degrees (round 4): their segments are cut into pieces by build_range_worklists(); give
 // every workgroup of the two-launch form WHOLE segments (layout.hpp: FusedLists) so that the pieces' partial rows meet
 // in its LDS instead of in a combine launch.
 void build_fused_lists(mmsbm_hip_ctx *c, const CreateKnobs &knobs, CreateLaps &lap) {
-  const bool cut_p = !c->lay.pair_work.splits.empty(), cut_u = !c->lay.user_work.splits.empty();
-  if (c->n_obs > kFusedRatingsMax || !fused_shape_ok(c) || knobs.no_fused_split || !(cut_p || cut_u)) return;
-  if (cut_p) build_fused_pair_lists(c);
-  if (cut_u) build_fused_user_lists(c, knobs);
+  if (!c->step.lists_wanted(c->pp) || knobs.no_fused_split) return;
+  if (c->step.cut_pairs) build_fused_pair_lists(c);
+  if (c->step.cut_users) build_fused_user_lists(c, knobs);
   lap("whole-segment lists (two launches)");
 }
 
@@ -334,9 +342,10 @@ mmsbm_hip_ctx *context_create(int device, int64_t n_obs, int32_t n_users, int32_
       apply_pair_plan(c.get(), plan_pair_forms(shape, c->lay.n_pairs, c->n_cus, knobs.no_mfma, knobs.mfma_chunk));
   build_range_worklists(c.get(), knobs, gpu_layout);
   lap("xcd-local work lists");
+  plan_step(c.get());
   build_fused_lists(c.get(), knobs, lap);
   // small problems (where eight rows in flight pay, plan_sides): two launches per iteration instead of four
-  c->fused = n_obs <= kFusedRatingsMax && fused_possible(c.get()) && !knobs.no_fused;
+  c->step.fused = c->step.fused_default(c->pp, knobs.no_fused);
   upload_index(c.get(), knobs, gpu_layout, units64, iu, ii, rating);
   lap("index uploads");
   alloc_state(c.get(), 1);

@@ -20,7 +20,7 @@ void stage_fused_pairs(mmsbm_hip_ctx *c) {
   fa.chunks = c->mv_chunks.ptr; fa.t_out = c->ttab.at(s); fa.partial = c->partial.at(s);
   fa.kp = c->kp; fa.lp = c->lp; fa.spb = c->pp.spb; fa.nsub = c->pp.nsub; fa.nt = nt_on(c) & 1;
   fa.bs_tiles = c->p[0].stride; fa.bs_eta = c->eta[0].stride; fa.bs_t = c->ttab.stride; fa.bs_partial = c->partial.stride;
-  const bool split = c->fs_pairs && !c->lay.pair_work.splits.empty();
+  const bool split = c->step.fs_pairs && !c->lay.pair_work.splits.empty();
   fa.units = split ? c->fp_units.ptr : nullptr; fa.items = split ? c->fp_items.ptr : nullptr;
   fa.splits = split ? c->fp_splits.ptr : nullptr;
   const size_t lds = pairs_fused_lds(c->kp, c->lp, split ? c->fp_max_parts : 0);
@@ -40,7 +40,7 @@ void stage_fused_tail(mmsbm_hip_ctx *c, bool commit) {
   const SegArgs su = seg_users_args(c, commit, c->n_users);
   const EtaPArgs a = eta_p_args(c, commit, kRedCols);
   const int per_u = kBlock / group_lanes(c->code_k), per_i = kBlock / group_lanes(c->code_l);
-  const bool split = c->fs_users && !c->lay.user_work.splits.empty();
+  const bool split = c->step.fs_users && !c->lay.user_work.splits.empty();
   const int bu = split ? c->fu_blocks : (su.nseg + per_u - 1) / per_u, nb_i = (c->n_items + per_i - 1) / per_i;
   const dim3 grid = slot_grid(c, bu + a.nb_p + nb_i);
   const FusedUserArgs fu{split ? c->fu_units.ptr : nullptr, split ? c->fu_items.ptr : nullptr, split ? c->fu_splits.ptr : nullptr};
@@ -66,7 +66,7 @@ void stage_fused_tail(mmsbm_hip_ctx *c, bool commit) {
 }
 
 // The two triple passes and the T + S stage of a committed iteration as one launch (pass_dense.hpp); the caller has
-// checked that the form applies (tu_iterate.hip: use_pass_dense).  Timed as stage K_SEG; K_DENSE then has no launch.
+// checked that the form applies (StepForm::Three, step_plan.hpp).  Timed as stage K_SEG; K_DENSE then has no launch.
 void stage_pass_dense(mmsbm_hip_ctx *c) {
   LaunchScope ls(c, K_SEG, true);
   const int s = c->base_slot, cur = c->cur, nt = nt_on(c);

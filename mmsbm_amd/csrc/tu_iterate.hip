@@ -1,6 +1,7 @@
-// tu_iterate.hip -- the EM iteration of the Mixed-Membership Stochastic Block Model on the MI355X (gfx950 / CDNA4): which
-// form it takes, the order of its launches, the graph replay, and the timers around them.  Host code only; every
-// kernel lives in the unit of its stage (launch.hpp lists them).
+// tu_iterate.hip -- the EM iteration of the Mixed-Membership Stochastic Block Model on the MI355X (gfx950 / CDNA4): the
+// order of its launches in each of its forms, the graph replay, and the timers around them.  Host code only; every
+// kernel lives in the unit of its stage (launch.hpp lists them), and which form an iteration takes is the context's
+// StepPlan's answer (step_plan.hpp), asked for once per iteration.
 //
 // What the reference computes per EM iteration (src/kernels_numpy.py:43-79 followed by
 // src/mmsbm.py:248-250), for every observed triple n = (u, i, r):
@@ -32,8 +33,11 @@
 //   cur          which of the two parameter buffers is current.  launch_iteration flips it after a committed iteration;
 //                run_iterations puts it back when a capture fails.  Nobody else writes it (tu_create.hip's alloc_state
 //                starts it at 0).
-//   a_ok[slot]   atab[cur] holds A of the slot's current parameters.  Written by ensure_a and by mark_a (called from
-//                launch_iteration, and from run_iterations after a replay).  Outside this unit only where a slot's
+//   step         the iteration's form (step_plan.hpp): the facts are create()'s (tu_create.hip), the ask changes through
+//                set_fused / set_pass_dense (tu_options.hip).  This unit only reads it: form(), and the rules of a form.
+//   a_ok[slot]   atab[cur] holds A of the slot's current parameters.  Written by ensure_a (StepPlan::needs_a_before) and
+//                by mark_a, at the end of launch_iteration and after a replay in run_iterations, both by the one rule
+//                StepPlan::a_valid_after.  Outside this unit only where a slot's
 //                parameters arrive -- set_params / init_params (tu_params.hip) mark the slot they filled -- and where
 //                the state is reset (set_slots, tu_create.hip).
 //   graph_exec   the captured two-iteration graphs, by `cur` at capture time: captured, instantiated and replayed by
@@ -151,6 +155,10 @@ inline int balanced_run_units(const std::vector<int32_t> &rating_off, int slots,
   return best;
 }
 
+void mark_a(mmsbm_hip_ctx *c, bool ok) {
+  for (int s = c->base_slot; s < c->base_slot + c->launch_slots; ++s) c->a_ok[static_cast<size_t>(s)] = ok ? 1 : 0;
+}
+
 }  // namespace
 
 // The A launch of the matrix-core pair stage writes rows only -- nothing ties its workgroups to the T + S launch's
@@ -175,95 +183,30 @@ void build_a_runs(mmsbm_hip_ctx *c, int units) {
   c->n_a_chunks = static_cast<int>(tmp.mv_chunks.size());
 }
 
-// ---- small problems: the iteration in two launches (fused_small.hpp) -------------------------------------
-bool fused_shape_ok(const mmsbm_hip_ctx *c) {  // (everything but the data: the kernels exist for this shape)
-  return c->code_k <= 1 && c->code_l <= 1 && c->n_chunks > 0 && c->pp.fused_shape_ok();
-}
-bool fused_possible(const mmsbm_hip_ctx *c) {
-  // A work list that only ORDERS whole segments is fine (the pair units ignore it -- every segment's result is its
-  // own -- and the user pass follows it as before); segments cut into pieces need all pieces of a segment inside one
-  // workgroup: the lists create() builds for small problems (fs_pairs / fs_users; round 4)
-  return fused_shape_ok(c) && (c->lay.pair_work.splits.empty() || c->fs_pairs) &&
-         (c->lay.user_work.splits.empty() || c->fs_users);
-}
-
-namespace {
-
-void mark_a(mmsbm_hip_ctx *c, bool ok) {
-  for (int s = c->base_slot; s < c->base_slot + c->launch_slots; ++s) c->a_ok[static_cast<size_t>(s)] = ok ? 1 : 0;
-}
-
-// Two launches while the launches' work is small: ratings x restart slots x (K + L, padded) <= 14M (measured per
-// iteration, two / four launches.  One slot, K = L = 10: 100k ratings 20.2 / 29.3 us, 300k 28.7 / 37.0, 500k 37.8 /
-// 43.5; K = L = 16: 400k 36.0 / 41.7; K = L = 20: 100k 28.4 / 37.6, 300k 50.1 / 50.1, 600k 69.4 / 67.5, 1M 105.0 / 95.6.  100k ratings at K = L = 10
-// with 2 / 4 / 8 / 16 slots: 26.5 / 32.4, 40.9 / 42.8, 68.0 / 64.9, 119.9 / 115.9 -- with several slots the four-launch
-// form shares the index stream among them)
-// Data whose segments are cut into pieces pays a combine launch in the separate form (five launches): there the two
-// launches win a little further out (log-normal popularity, separate / two, scripts/fused_split_sweep.py: 400k ratings
-// K = L = 10 38.4 / 31.3 us, 700k 43.8 / 39.8; 300k K = L = 20 45.1 / 41.4, 600k 54.0 / 65.5; 1M x 100k x 20k K = L = 10
-// 77.3 / 92.6) -- up to 18M.  (kFusedRatingsMax, the ratings up to which create() turns the form on: launch.hpp)
-constexpr long long kFusedWorkMax = 14000000, kFusedWorkMaxSplit = 18000000;
-
-// ---- big problems of small tiles: the triple passes and the T + S stage in one launch (pass_dense.hpp) ------------
-// Everything but the size: one restart per launch, the small-tile T + S body at 256 threads (its split of a unit's
-// pairs among the slab copies is what the merged kernel mirrors), eight-lane groups on the gathered side, whole
-// segments on both sides (no work lists), every workgroup of the pair stage a single 64-pair unit.
-bool pass_dense_possible(const mmsbm_hip_ctx *c) {
-  return c->launch_slots == 1 && c->code_k == 1 && c->code_l <= 1 && c->n_chunks > 0 && c->pp.pass_dense_shape_ok() &&
-         c->lay.pair_work.items.empty() && c->lay.user_work.items.empty() && c->lay.pair_work.splits.empty() &&
-         c->lay.user_work.splits.empty();
-}
-// ... and the size from which it pays, ratings x (K + L, padded): above the two-launch form's range (kFusedWorkMax), so
-// that no shape goes from two launches to this form (measured per iteration: EXPERIMENTS.md, section C)
-constexpr long long kPassDenseWorkMin = 20000000;
-static_assert(kPassDenseWorkMin > kFusedWorkMaxSplit, "no shape changes from two launches to three");
-
-}  // namespace
-
-bool use_fused(const mmsbm_hip_ctx *c) {
-  // (fused_possible again: options set after create() -- "mfma", "direct" ... -- change what it depends on)
-  const bool cut = !c->lay.pair_work.splits.empty() || !c->lay.user_work.splits.empty();
-  if (c->pass_dense == 1 && !c->fused_forced && pass_dense_possible(c)) return false;  // (option "pass_dense" = 1 asks for that form)
-  return c->fused && fused_possible(c) &&
-         (c->fused_forced || c->n_obs * c->launch_slots * (c->kp + c->lp) <= (cut ? kFusedWorkMaxSplit : kFusedWorkMax));
-}
-// the next COMMITTED iteration takes the three-launch form (update_coefficients, commit off, needs the raw numerators
-// of the separate launches and keeps them)
-bool use_pass_dense(const mmsbm_hip_ctx *c) {
-  if (c->pass_dense == 0 || use_fused(c) || !pass_dense_possible(c)) return false;
-  return c->pass_dense == 1 || c->n_obs * (c->kp + c->lp) >= kPassDenseWorkMin;
-}
-
+// ---- one iteration in the form the context's plan gives (step_plan.hpp) -------------------------------------------------
 void launch_iteration(mmsbm_hip_ctx *c, bool commit) {
-  if (use_fused(c)) {
-    stage_fused_pairs(c);  // (writes A of the current parameters on its way)
-    stage_fused_tail(c, commit);
-    if (commit) c->cur ^= 1;
-    mark_a(c, !commit);
-    return;
+  const StepForm form = c->form(commit);
+  if (StepPlan::needs_a_before(form)) ensure_a(c);
+  switch (form) {
+    case StepForm::Two: stage_fused_pairs(c); stage_fused_tail(c, commit); break;  // (A of the current parameters on its way)
+    case StepForm::Three: stage_pass_dense(c); stage_eta_p(c, commit); break;
+    case StepForm::Four: stage_seg(c, commit, true, true, c->stream); stage_dense(c); stage_eta_p(c, commit); break;
   }
-  ensure_a(c);
-  if (commit && use_pass_dense(c)) {
-    stage_pass_dense(c);
-  } else {
-    stage_seg(c, commit, true, true, c->stream);
-    stage_dense(c);
-  }
-  stage_eta_p(c, commit);
   if (commit) {
-    stage_matvec_a(c, c->cur ^ 1, c->cur ^ 1);
+    if (form != StepForm::Two) stage_matvec_a(c, c->cur ^ 1, c->cur ^ 1);  // (A of the new parameters: a_valid_after)
     c->cur ^= 1;
-    mark_a(c, true);
   }
+  mark_a(c, StepPlan::a_valid_after(form, commit));
 }
 
 // n committed iterations: graph replays of two iterations each when enabled, the rest eager
 void run_iterations(mmsbm_hip_ctx *c, int n) {
   if (c->graph_mode && !c->profiling) {
+    const StepForm form = c->form(true);  // (of every iteration of this call: nothing it depends on changes in here)
     while (n >= 2) {
       const int slot = c->cur;
       if (!c->graph_exec[slot]) {
-        if (!use_fused(c)) ensure_a(c);  // (outside the capture: a replay must not repeat it)
+        if (StepPlan::needs_a_before(form)) ensure_a(c);  // (outside the capture: a replay must not repeat it)
         hipGraph_t graph = nullptr;
         HIP_CHECK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
         try {
@@ -283,9 +226,8 @@ void run_iterations(mmsbm_hip_ctx *c, int n) {
         // capture only records: cur is back where it started and nothing has run yet
       }
       HIP_CHECK(hipGraphLaunch(c->graph_exec[slot], c->stream));
-      // (a replay runs none of launch_iteration's host code: the bookkeeping of "atab[cur] holds A of the current
-      // parameters" has to be repeated here -- true after the four-launch form, false after the two-launch one)
-      mark_a(c, !use_fused(c));
+      // (a replay runs none of launch_iteration's host code: its last line, by the same rule)
+      mark_a(c, StepPlan::a_valid_after(form, true));
       n -= 2;
     }
   }
@@ -341,7 +283,8 @@ void kernel_bytes(const mmsbm_hip_ctx *ctx, int index, int64_t *bytes_read, int6
   const int64_t K = ctx->k, L = ctx->l, Q = ctx->n_pairs;
   const int64_t C = static_cast<int64_t>(ctx->lay.mv_chunks.size());
   int64_t rd = 0, wr = 0;
-  const bool merged = use_pass_dense(ctx);  // K_SEG is the merged launch of pass_dense.hpp, K_DENSE has no launch
+  const StepForm form = ctx->form(true);
+  const bool merged = form == StepForm::Three;  // K_SEG is the merged launch of pass_dense.hpp
   switch (index) {
     case K_SEG:  // two passes: index + one gathered K-row per triple; fixed rows and offsets once
       rd = 2 * N * (4 + 8 * K) + (U + Q) * (8 * K + 4);
@@ -352,7 +295,7 @@ void kernel_bytes(const mmsbm_hip_ctx *ctx, int index, int64_t *bytes_read, int6
       }
       break;
     case K_DENSE:  // C rows + gathered eta rows + item ids + one tile per block; T rows + slabs
-      if (merged) break;
+      if (!StepPlan::stage_runs(form, K_DENSE)) break;
       rd = Q * (8 * K + 8 * L + 4) + C * 8 * K * L;
       wr = Q * 8 * L + C * 8 * K * L;
       break;
@@ -386,20 +329,20 @@ void time_stage(mmsbm_hip_ctx *ctx, int stage, int reps, float *mean_us) {
 #endif
   if (!mean_us || reps <= 0 || stage < 0 || stage >= K_COUNT)
     throw std::invalid_argument("bad argument");
-  if ((stage == K_FUSED_PAIRS || stage == K_FUSED_TAIL) && !fused_possible(ctx))
+  if ((stage == K_FUSED_PAIRS || stage == K_FUSED_TAIL) && !ctx->step.two_possible(ctx->pp))
     throw std::invalid_argument("time_stage: the two-launch kernels do not apply to this shape / data");
   use_device(ctx);
   ensure_a(ctx);
   // (with the triple passes and the T + S stage in one launch, stage K_SEG is that launch and K_DENSE has none: 0 us)
-  const bool merged = use_pass_dense(ctx);
-  if (merged && stage == K_DENSE) {
+  const StepForm form = ctx->form(true);
+  if (!StepPlan::stage_runs(form, static_cast<KernelId>(stage))) {
     *mean_us = 0.f;
     return;
   }
   auto one = [&] {
     switch (stage) {
       case K_SEG:
-        if (merged) stage_pass_dense(ctx);
+        if (form == StepForm::Three) stage_pass_dense(ctx);
         else stage_seg(ctx, true, true, true, ctx->stream);
         break;
       case K_DENSE: stage_dense(ctx); break;

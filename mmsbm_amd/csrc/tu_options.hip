@@ -31,11 +31,8 @@ const Option kOptions[] = {
     // 0: prod_dist / predict through the per-row kernels (R K L multiply-adds per row)
     {"predict_fast", [](const Ctx *c) -> double { return c->predict_fast; }, [](Ctx *c, double v) { c->predict_fast = v != 0.0; }},
     // two launches per iteration (small tiles, unsplit segments); any problem size
-    {"fused", [](const Ctx *c) -> double { return c->fused; },
-     [](Ctx *c, double v) {
-       if (v != 0.0 && !fused_possible(c)) throw std::invalid_argument("fused: not available for this shape / data");
-       c->fused = c->fused_forced = v != 0.0;
-     }},
+    {"fused", [](const Ctx *c) -> double { return c->step.fused; },
+     [](Ctx *c, double v) { c->step.set_fused(v != 0.0, c->step.two_possible(c->pp)); }},
     // 0: plain stores for every output row; bits: 1 T and A rows, 2 theta' rows, 4 own-row loads.  Reads as what is in use
     {"nt_out", [](const Ctx *c) -> double { return nt_on(c); },
      [](Ctx *c, double v) {
@@ -127,14 +124,11 @@ const Option kOptions[] = {
      [](Ctx *c, double v) { set_audience(c->asrt_part, "assortment_part_bytes", v); }},
     // the form FAMILY of an iteration at the current slot count: 2 = the two launches of fused_small.hpp, 4 = the separate
     // stages, with or without "pass_dense" -- the launches a committed iteration really takes are launches - pass_dense
-    {"launches", [](const Ctx *c) -> double { return use_fused(c) ? 2 : 4; }, nullptr},
+    {"launches", [](const Ctx *c) -> double { return StepPlan::launches_family(c->form(true)); }, nullptr},
     // the triple passes and the T + S stage of a committed iteration in one launch (pass_dense.hpp).  Set: -1 the
     // library's choice by size, 0 off, 1 on wherever the form applies.  Reads 1 when the next committed iteration takes it
-    {"pass_dense", [](const Ctx *c) -> double { return use_pass_dense(c) ? 1 : 0; },
-     [](Ctx *c, double v) {
-       if (v != -1.0 && v != 0.0 && v != 1.0) throw std::invalid_argument("pass_dense: -1, 0 or 1");
-       c->pass_dense = static_cast<int>(v);
-     }},
+    {"pass_dense", [](const Ctx *c) -> double { return c->form(true) == StepForm::Three ? 1 : 0; },
+     [](Ctx *c, double v) { c->step.set_pass_dense(v); }},
     {"wide", [](const Ctx *c) -> double { return c->pp.wide; }, nullptr},
     // 0: a logarithm per element; 1: logarithm tables, a group of lanes per triple; 2: where it applies a wave per pair
     // (lik_fact.hpp), else as 1
@@ -169,7 +163,7 @@ const Option kOptions[] = {
     {"splits_pairs", [](const Ctx *c) -> double { return static_cast<double>(c->lay.pair_work.splits.size()); }, nullptr},
     {"splits_users", [](const Ctx *c) -> double { return static_cast<double>(c->lay.user_work.splits.size()); }, nullptr},
     // whole-segment lists built (1 pair side, 2 user side)
-    {"fused_split", [](const Ctx *c) -> double { return (c->fs_pairs ? 1 : 0) + (c->fs_users ? 2 : 0); }, nullptr},
+    {"fused_split", [](const Ctx *c) -> double { return (c->step.fs_pairs ? 1 : 0) + (c->step.fs_users ? 2 : 0); }, nullptr},
     // item_sum walks the fixed-width grid of pair ids (tu_create.hip: upload_item_grid)
     {"item_grid", [](const Ctx *c) -> double { return c->item_grid.count ? 1 : 0; }, nullptr},
     // the index's sorts ran on the device (tu_create.hip: build_index)

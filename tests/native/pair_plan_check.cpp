@@ -77,7 +77,7 @@ static void check_plan(const PairPlan &p) {
     case PairForm::Mfma: CHECK(ft == PairForm::Mfma && p.lds_ma <= kLdsMax); break;
     case PairForm::MfmaBig: CHECK(ft == PairForm::MfmaBig); break;
   }
-  CHECK(!p.fused_shape_ok() || (ft == PairForm::Block && fa == PairForm::Block && !p.direct_out));
+  CHECK(!p.two_shape_ok() || (ft == PairForm::Block && fa == PairForm::Block && !p.direct_out));
 }
 
 int main() {
