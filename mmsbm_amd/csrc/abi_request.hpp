@@ -1,6 +1,10 @@
 // abi_request.hpp -- the request checks of the C ABI (mmsbm_hip.hip) as host-only code: what a query's users, candidate
 // subset, exclusion lists, theta rows, categories, shelves, temperature and user set must satisfy before a kernel reads
-// them, and the refusal each fault gets.  Plain values only -- counts, tops, pointers, the session's weights' range --
+// them, and the refusal each fault gets -- and the values a checked request crosses into the serving units as (launch.hpp
+// declares the units' entry points over them): UserRows, Subset, RowCsr, UserQuery, ThetaQuery, Categories in; TopNOut,
+// ShelfOut, AssignOut out.  user_query / theta_query are where an empty request loses its offsets, UserQuery::rows where a
+// slice of a request's own lists is re-based: the only arithmetic on the caller's list pointers in front of the uploads.
+// Plain values only -- counts, tops, pointers, the session's weights' range --
 // no HIP type, no context, no session: the checks decide which pointers the kernels will dereference, so they run on
 // the CPU under the sanitizers over faulty and extreme requests (tests/native/abi_request_check.cpp), against the texts
 // recorded from the library (tests/gpu_abi_requests_parent.json).  A fault throws std::invalid_argument (MMSBM_E_INVALID
@@ -70,39 +74,6 @@ inline void require_candidates(const int32_t *v, int64_t first, int64_t n, int32
   }
 }
 
-// n_cand / cand_items of a query within a part of the catalogue (cand_items null: all of it, n_cand ignored)
-inline void require_subset(const int32_t *cand_items, int32_t n_cand, int32_t top, const char *who) {
-  if (!cand_items) return;
-  if (n_cand < 0 || n_cand > top)
-    throw std::invalid_argument(std::string(who) + ": n_cand outside [0, items of the catalogue]");
-  require_candidates(cand_items, 0, n_cand, top, who);
-}
-
-// The capped categories of the two *_quota entries: a CSR of n_cats categories over the catalogue's `top` items, each
-// strictly ascending, no item in two of them, no negative cap.  capped = false (the two *_shelves entries): the same
-// categories without caps, cat_caps is not read.
-inline void require_categories(int64_t n_cats, const int64_t *cat_offsets, const int32_t *cat_items, const int32_t *cat_caps,
-                               int32_t top, const char *who, bool capped = true) {
-  const std::string w = std::string(who) + ": ";
-  if (n_cats < 0) throw std::invalid_argument(w + "negative n_cats");
-  if (n_cats == 0) return;
-  if (!cat_offsets || (capped && !cat_caps)) throw std::invalid_argument("null argument");
-  check_csr(cat_offsets, cat_items, n_cats, top, who, "cat_offsets", "category", "category items", "category item");
-  std::vector<bool> taken(static_cast<size_t>(top), false);
-  for (int64_t g = 0; g < n_cats; ++g) {
-    if (capped && cat_caps[g] < 0) throw std::invalid_argument(w + "negative cap of category " + std::to_string(g));
-    for (int64_t e = cat_offsets[g]; e < cat_offsets[g + 1]; ++e) {
-      if (e > cat_offsets[g] && cat_items[e] <= cat_items[e - 1])
-        throw std::invalid_argument(w + "the items of a category must be ascending and distinct (entry " +
-                                    std::to_string(e) + ")");
-      if (taken[static_cast<size_t>(cat_items[e])])
-        throw std::invalid_argument(w + "item " + std::to_string(cat_items[e]) + " is in two categories (entry " +
-                                    std::to_string(e) + ")");
-      taken[static_cast<size_t>(cat_items[e])] = true;
-    }
-  }
-}
-
 // The temperature of the two explore entries: finite, > 0 and not below the floor of a session whose rating weights
 // span [w_min, w_max] (explore.hpp: a score lies between them, and no exp((s - m) / T) may underflow)
 inline void require_temperature(double t, double w_min, double w_max, const char *who) {
@@ -145,25 +116,6 @@ inline void require_shelf_ask(int64_t n_users, int64_t n_cats, const ShelfAsk &a
     throw std::invalid_argument("null argument");
 }
 
-// The caller-given lists of recommend_list_propensity, a CSR check_csr has passed: no list beyond kQueryMaxN items, no
-// item twice in one
-inline void require_lists(const int64_t *list_offsets, const int32_t *list_items, int64_t rows, const char *who) {
-  std::vector<int32_t> row;
-  for (int64_t b = 0; b < rows; ++b) {
-    const int64_t len = list_offsets[b + 1] - list_offsets[b];
-    if (len > kQueryMaxN)
-      throw ApiError(kErrUnsupported, std::string(who) + ": the list of row " + std::to_string(b) + " holds " +
-                                          std::to_string(len) + " items, beyond the " + std::to_string(kQueryMaxN) +
-                                          " a list holds at most");
-    row.assign(list_items + list_offsets[b], list_items + list_offsets[b + 1]);
-    std::sort(row.begin(), row.end());
-    const auto twice = std::adjacent_find(row.begin(), row.end());
-    if (twice != row.end())
-      throw std::invalid_argument(std::string(who) + ": item " + std::to_string(*twice) + " is twice in the list of row " +
-                                  std::to_string(b));
-  }
-}
-
 // The members of a group query, a CSR check_csr has passed over `top` users: distinct within a group
 inline void require_distinct_members(const int64_t *offsets, const int32_t *members, int64_t n_groups, int32_t top,
                                      const char *who) {
@@ -185,8 +137,8 @@ inline void require_theta_entries(const double *theta, size_t n, const char *who
       throw std::invalid_argument(std::string(who) + ": theta entry " + std::to_string(e) + " is not a finite number >= 0");
 }
 
-// ---- the runs of arguments that travel together -----------------------------------------------------------------------
-// A row CSR: per request row a list of ids, with the names its messages use
+// ---- the values a request crosses into the units as --------------------------------------------------------------------
+// A row CSR: per request row a list of ids, with the names its messages use (null inside the units: checked already)
 struct RowCsr {
   const int64_t *offsets;
   const int32_t *values;
@@ -194,14 +146,40 @@ struct RowCsr {
   void check(int64_t rows, int32_t top, const char *who) const {
     check_csr(offsets, values, rows, top, who, off_name, row, vals, val_name);
   }
-  // what the query is handed: an empty request reads no offsets, given or not
-  const int64_t *offsets_of(int64_t rows) const { return rows > 0 ? offsets : nullptr; }
+  // the lists of a request of `rows` rows: an empty request reads no offsets, given or not
+  RowCsr of_rows(int64_t rows) const {
+    RowCsr r = *this;
+    if (rows <= 0) r.offsets = nullptr;
+    return r;
+  }
 };
 inline RowCsr excluded_lists(const int64_t *off, const int32_t *val) {
   return {off, val, "excl_offsets", "user", "excluded items", "excluded item"};
 }
 inline RowCsr seen_lists(const int64_t *off, const int32_t *val) {
   return {off, val, "seen_offsets", "user", "seen items", "seen item"};
+}
+inline RowCsr listed_items(const int64_t *off, const int32_t *val) {
+  return {off, val, "list_offsets", "user", "listed items", "listed item"};
+}
+
+// The caller-given lists of recommend_list_propensity, a CSR check has passed: no list beyond kQueryMaxN items, no item
+// twice in one
+inline void require_lists(const RowCsr &lists, int64_t rows, const char *who) {
+  std::vector<int32_t> row;
+  for (int64_t b = 0; b < rows; ++b) {
+    const int64_t len = lists.offsets[b + 1] - lists.offsets[b];
+    if (len > kQueryMaxN)
+      throw ApiError(kErrUnsupported, std::string(who) + ": the list of row " + std::to_string(b) + " holds " +
+                                          std::to_string(len) + " items, beyond the " + std::to_string(kQueryMaxN) +
+                                          " a list holds at most");
+    row.assign(lists.values + lists.offsets[b], lists.values + lists.offsets[b + 1]);
+    std::sort(row.begin(), row.end());
+    const auto twice = std::adjacent_find(row.begin(), row.end());
+    if (twice != row.end())
+      throw std::invalid_argument(std::string(who) + ": item " + std::to_string(*twice) + " is twice in the list of row " +
+                                  std::to_string(b));
+  }
 }
 
 // User rows: encoded ids of training users, one per request row
@@ -211,11 +189,17 @@ struct UserRows {
   void check(int32_t top, const std::string &prefix) const { require_ids(ids, n, top, prefix); }
 };
 
-// A candidate subset of the catalogue (items null: all of it)
+// A candidate subset of the catalogue: n ascending, distinct item ids (items null: all of it, n ignored)
 struct Subset {
   int32_t n;
   const int32_t *items;
-  void check(int32_t top, const char *who) const { require_subset(items, n, top, who); }
+  void check(int32_t top, const char *who) const {
+    if (!items) return;
+    if (n < 0 || n > top) throw std::invalid_argument(std::string(who) + ": n_cand outside [0, items of the catalogue]");
+    require_candidates(items, 0, n, top, who);
+  }
+  // the columns a query over it scores, of a catalogue of `catalogue` items
+  int columns(int catalogue) const { return items ? n : catalogue; }
 };
 
 inline void require_rows(int64_t n_users) {
@@ -225,26 +209,90 @@ inline void require_rows(int64_t n_users) {
 // The users / candidate subset / exclusion prefix of a query of `who` over `n_users_top` users and `top` items, after
 // the entry's null checks: ids ("<user_prefix> id ..."), then the subset, then the exclusion lists
 struct UserQuery {
-  UserRows rows;
+  UserRows users;
   Subset cand;
   RowCsr excl;
   void check(int32_t n_users_top, const std::string &user_prefix, int32_t top, const char *who) const {
-    rows.check(n_users_top, user_prefix);
+    users.check(n_users_top, user_prefix);
     cand.check(top, who);
-    excl.check(rows.n, top, who);
+    excl.check(users.n, top, who);
+  }
+  // the query of the request rows [b0, b0 + nb): their ids, the same subset, their own lists with the offsets counted
+  // from the first of them (held by `rebased`)
+  UserQuery rows(int64_t b0, int64_t nb, std::vector<int64_t> &rebased) const {
+    UserQuery q{{nb, users.ids ? users.ids + b0 : nullptr}, cand, excl};
+    if (!excl.offsets) return q;
+    const int64_t first = excl.offsets[b0];
+    rebased.resize(static_cast<size_t>(nb) + 1);
+    for (int64_t k = 0; k <= nb; ++k) rebased[static_cast<size_t>(k)] = excl.offsets[b0 + k] - first;
+    q.excl.offsets = rebased.data();
+    if (excl.values) q.excl.values = excl.values + first;
+    return q;
   }
 };
+inline UserQuery user_query(int64_t n_users, const int32_t *users, int32_t n_cand, const int32_t *cand_items,
+                            const int64_t *excl_offsets, const int32_t *excl_items) {
+  return {{n_users, users}, {n_cand, cand_items}, excluded_lists(excl_offsets, excl_items).of_rows(n_users)};
+}
 
-// Theta rows: caller-given users with their seen lists and the candidate subset; the subset first (under `who`), then
-// the seen lists (under `seen_who`: "recommend", "inform")
+// Theta rows: caller-given users -- theta [slot][n_users][K] -- with their seen lists and the candidate subset; the
+// subset first (under `who`), then the seen lists (under `seen_who`: "recommend", "inform")
 struct ThetaQuery {
   int64_t n_users;
+  const double *theta;
   Subset cand;
   RowCsr seen;
   void check(int32_t top, const char *who, const char *seen_who) const {
     cand.check(top, who);
     seen.check(n_users, top, seen_who);
   }
+};
+inline ThetaQuery theta_query(int64_t n_users, const double *theta, const int64_t *seen_offsets, const int32_t *seen_items,
+                              int32_t n_cand, const int32_t *cand_items) {
+  return {n_users, theta, {n_cand, cand_items}, seen_lists(seen_offsets, seen_items).of_rows(n_users)};
+}
+
+// The categories of the *_quota and *_shelves entries: a CSR of n categories over the catalogue's items with a cap each
+// (caps null: the shelves entries)
+struct Categories {
+  int64_t n;
+  const int64_t *offsets;
+  const int32_t *items, *caps;
+  // over the catalogue's `top` items: each category strictly ascending, no item in two of them, no negative cap.
+  // capped = false (the two *_shelves entries): the same categories without caps, `caps` is not read.
+  void check(int32_t top, const char *who, bool capped = true) const {
+    const std::string w = std::string(who) + ": ";
+    if (n < 0) throw std::invalid_argument(w + "negative n_cats");
+    if (n == 0) return;
+    if (!offsets || (capped && !caps)) throw std::invalid_argument("null argument");
+    check_csr(offsets, items, n, top, who, "cat_offsets", "category", "category items", "category item");
+    std::vector<bool> taken(static_cast<size_t>(top), false);
+    for (int64_t g = 0; g < n; ++g) {
+      if (capped && caps[g] < 0) throw std::invalid_argument(w + "negative cap of category " + std::to_string(g));
+      for (int64_t e = offsets[g]; e < offsets[g + 1]; ++e) {
+        if (e > offsets[g] && items[e] <= items[e - 1])
+          throw std::invalid_argument(w + "the items of a category must be ascending and distinct (entry " +
+                                      std::to_string(e) + ")");
+        if (taken[static_cast<size_t>(items[e])])
+          throw std::invalid_argument(w + "item " + std::to_string(items[e]) + " is in two categories (entry " +
+                                      std::to_string(e) + ")");
+        taken[static_cast<size_t>(items[e])] = true;
+      }
+    }
+  }
+};
+
+// The caller's output arrays of a top-N query: items and scores [rows][n], counts [rows] (scores, counts: null allowed)
+struct TopNOut {
+  int32_t *items;
+  double *scores;
+  int32_t *counts;
+};
+// ... and of recommend_assign (mmsbm_hip.h)
+struct AssignOut {
+  int32_t *items;
+  double *scores, *paid, *pi, *price, *price_sum;
+  int32_t *load, *rounds, *converged;
 };
 
 // ---- user sets ---------------------------------------------------------------------------------------------------------

@@ -47,81 +47,52 @@ void require_free_mem(size_t bytes, const std::string &what);
 // the training rows' external ids in the order they were given, with their ratings on request (null: not wanted)
 void train_id_columns(mmsbm_hip_ctx *c, std::vector<int32_t> &user, std::vector<int32_t> &item,
                       std::vector<int32_t> *rating);
-// tu_recommend.hip -- top-N recommendation (recommend.hpp): the session of mmsbm_hip_recommend_*, arguments checked
+// The serving entry points take a request as the values of abi_request.hpp -- UserQuery (users, candidate subset, the
+// query's own excluded items by request row), ThetaQuery (caller-given theta rows, their seen lists, the subset), Subset,
+// RowCsr, Categories -- and write to its output values (TopNOut, ShelfOut, AssignOut); arguments checked.
+// tu_recommend.hip -- top-N recommendation (recommend.hpp): the session of mmsbm_hip_recommend_*
 void recommend_begin(mmsbm_hip_ctx *c, const double *weights, int exclude_train);
 void recommend_add(mmsbm_hip_ctx *c);  // the selected slot (the caller holds a OneSlot)
-void recommend_query(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, int n, int32_t *items, double *scores,
-                     int32_t *counts);
-void recommend_query_theta(mmsbm_hip_ctx *c, int64_t n_users, const double *theta, const int64_t *seen_offsets,
-                           const int32_t *seen_items, int n, int32_t *items, double *scores, int32_t *counts);
+void recommend_query(mmsbm_hip_ctx *c, const UserRows &users, int n, const TopNOut &out);
 void recommend_positions(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, const int64_t *offsets,
                          const int32_t *items, int32_t *positions, int32_t *candidates);
-void recommend_add_items(mmsbm_hip_ctx *c, int32_t n_new, const double *eta, const int64_t *seen_offsets,
+void recommend_add_items(mmsbm_hip_ctx *c, int32_t n_new, const double *eta, const int64_t *seen_off,
                          const int32_t *seen_users);
-// ... queries within a part of the catalogue (catalogue.hpp): cand ascending, distinct ids of the session's catalogue
-// (null: all of it); excl_*: the query's own excluded items by request row (null: none); recommend_rank: one ascending,
-// distinct candidate list per request row
-void recommend_query_within(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, const int32_t *cand, int n_cand,
-                            const int64_t *excl_offsets, const int32_t *excl_items, int n, int32_t *items,
-                            double *scores, int32_t *counts);
-void recommend_query_theta_within(mmsbm_hip_ctx *c, int64_t n_users, const double *theta, const int64_t *seen_offsets,
-                                  const int32_t *seen_items, const int32_t *cand, int n_cand, int n, int32_t *items,
-                                  double *scores, int32_t *counts);
-void recommend_rank(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, const int64_t *offsets,
-                    const int32_t *cand, int n, int32_t *items, double *scores, int32_t *counts);
-// ... the same two queries with capped categories (quota.hpp): category g holds the catalogue items
-// cat_items[cat_offsets[g] .. cat_offsets[g + 1]) (strictly ascending; the categories disjoint), at most cat_caps[g] of
-// which enter a row's list
-void recommend_query_quota(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, const int32_t *cand, int n_cand,
-                           const int64_t *excl_offsets, const int32_t *excl_items, int64_t n_cats,
-                           const int64_t *cat_offsets, const int32_t *cat_items, const int32_t *cat_caps, int n,
-                           int32_t *items, double *scores, int32_t *counts);
-void recommend_query_theta_quota(mmsbm_hip_ctx *c, int64_t n_users, const double *theta, const int64_t *seen_offsets,
-                                 const int32_t *seen_items, const int32_t *cand, int n_cand, int64_t n_cats,
-                                 const int64_t *cat_offsets, const int32_t *cat_items, const int32_t *cat_caps, int n,
-                                 int32_t *items, double *scores, int32_t *counts);
-// ... category-level recommendation (shelves.hpp): the categories as the quota queries' (no caps); what is asked of
-// each row, and the caller's output arrays (ShelfAsk, ShelfOut: abi_request.hpp)
-void recommend_query_shelves(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, const int32_t *cand, int n_cand,
-                             const int64_t *excl_offsets, const int32_t *excl_items, int64_t n_cats,
-                             const int64_t *cat_offsets, const int32_t *cat_items, const ShelfAsk &ask,
+// ... queries within a part of the catalogue (catalogue.hpp); without a subset and lists: the whole catalogue;
+// recommend_rank: one ascending, distinct candidate list per request row
+void recommend_query_within(mmsbm_hip_ctx *c, const UserQuery &q, int n, const TopNOut &out);
+void recommend_query_theta(mmsbm_hip_ctx *c, const ThetaQuery &q, int n, const TopNOut &out);
+void recommend_rank(mmsbm_hip_ctx *c, const UserRows &users, const RowCsr &lists, int n, const TopNOut &out);
+// ... the same two queries with capped categories (quota.hpp): at most caps[g] items of category g enter a row's list
+void recommend_query_quota(mmsbm_hip_ctx *c, const UserQuery &q, const Categories &cats, int n, const TopNOut &out);
+void recommend_query_theta_quota(mmsbm_hip_ctx *c, const ThetaQuery &q, const Categories &cats, int n, const TopNOut &out);
+// ... category-level recommendation (shelves.hpp): the categories as the quota queries' (no caps)
+void recommend_query_shelves(mmsbm_hip_ctx *c, const UserQuery &q, const Categories &cats, const ShelfAsk &ask,
                              const ShelfOut &out);
-void recommend_query_theta_shelves(mmsbm_hip_ctx *c, int64_t n_users, const double *theta, const int64_t *seen_offsets,
-                                   const int32_t *seen_items, const int32_t *cand, int n_cand, int64_t n_cats,
-                                   const int64_t *cat_offsets, const int32_t *cat_items, const ShelfAsk &ask,
+void recommend_query_theta_shelves(mmsbm_hip_ctx *c, const ThetaQuery &q, const Categories &cats, const ShelfAsk &ask,
                                    const ShelfOut &out);
-// tu_rerank.hip -- the queries of the recommend session that add a stage of their own to the frame, arguments checked.
-// Randomised top-N with propensities (explore.hpp): recommend_query_within's request, a temperature above the
-// session's floor and the four words of a PCG64 stream; the propensities of caller-given lists (list_offsets int64
-// [n_users + 1], distinct items per row); r and g of given (user, item) pairs, no session needed
-void recommend_query_explore(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, const int32_t *cand, int n_cand,
-                             const int64_t *excl_offsets, const int32_t *excl_items, int n, double temperature,
-                             const uint64_t pcg64_state[4], int32_t *items, double *scores, double *propensity,
-                             int32_t *counts);
-void recommend_list_propensity(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, const int32_t *cand, int n_cand,
-                               const int64_t *excl_offsets, const int32_t *excl_items, double temperature,
-                               const int64_t *list_offsets, const int32_t *list_items, double *scores,
+// tu_rerank.hip -- the queries of the recommend session that add a stage of their own to the frame.  Randomised top-N
+// with propensities (explore.hpp): a temperature above the session's floor and the four words of a PCG64 stream; the
+// propensities of caller-given lists (distinct items per row); r and g of given (user, item) pairs, no session needed
+void recommend_query_explore(mmsbm_hip_ctx *c, const UserQuery &q, int n, double temperature, const uint64_t pcg64_state[4],
+                             const TopNOut &out, double *propensity);
+void recommend_list_propensity(mmsbm_hip_ctx *c, const UserQuery &q, double temperature, const RowCsr &lists, double *scores,
                                double *propensity);
 void explore_noise(mmsbm_hip_ctx *c, const uint64_t pcg64_state[4], int64_t n_pairs, const int32_t *users,
                    const int32_t *items, double *r, double *g);
-// ... and the ensemble-aware queries of the recommend session (ensemble.hpp), arguments checked: mode:
-// MMSBM_HIP_ENSEMBLE_*; cand / excl_* as in recommend_query_within; stats [n_pairs][4], per_slot [S][n_pairs] or null
-void recommend_query_ensemble(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, int mode, double risk,
-                              const int32_t *cand, int n_cand, const int64_t *excl_offsets, const int32_t *excl_items,
-                              int n, int32_t *items, double *scores, int32_t *counts);
+// ... and the ensemble-aware queries (ensemble.hpp): mode: MMSBM_HIP_ENSEMBLE_*; stats [n_pairs][4], per_slot
+// [S][n_pairs] or null
+void recommend_query_ensemble(mmsbm_hip_ctx *c, const UserQuery &q, int mode, double risk, int n, const TopNOut &out);
 void recommend_pair_spread(mmsbm_hip_ctx *c, int64_t n_pairs, const int32_t *users, const int32_t *items, double *stats,
                            double *per_slot);
-// ... and the group queries of the recommend session (group.hpp), arguments checked: group g's members are
-// members[offsets[g] .. offsets[g + 1]), distinct; mode: MMSBM_HIP_GROUP_*; cand as in recommend_query_within
-void recommend_query_groups(mmsbm_hip_ctx *c, int64_t n_groups, const int64_t *offsets, const int32_t *members, int mode,
-                            double bar, const int32_t *cand, int n_cand, int n, int32_t *items, double *scores,
-                            int32_t *counts);
-// ... and the two queries of diverse.hpp, arguments checked: the distance of given pairs of the similarity session's
-// side, and the diversified top-N, which reads the recommend session and the similarity session (side items)
+// ... and the group queries (group.hpp): one row of distinct members per group; mode: MMSBM_HIP_GROUP_*
+void recommend_query_groups(mmsbm_hip_ctx *c, int64_t n_groups, const RowCsr &members, int mode, double bar,
+                            const Subset &cand, int n, const TopNOut &out);
+// ... and the two queries of diverse.hpp: the distance of given pairs of the similarity session's side, and the
+// diversified top-N, which reads the recommend session and the similarity session (side items)
 void similar_pairs(mmsbm_hip_ctx *c, int64_t n_pairs, const int32_t *a, const int32_t *b, double *distance);
-void recommend_diverse(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, const int32_t *cand, int n_cand,
-                       const int64_t *excl_offsets, const int32_t *excl_items, int n, int pool, double trade_off,
-                       int32_t *items, double *scores, double *distances, int32_t *counts);
+void recommend_diverse(mmsbm_hip_ctx *c, const UserQuery &q, int n, int pool, double trade_off, const TopNOut &out,
+                       double *distances);
 // tu_pairs.hip -- the m best pairs of the whole model (top_pairs.hpp): users ascending and distinct
 void recommend_top_pairs(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, int m, int32_t *out_users,
                          int32_t *out_items, double *out_scores, int32_t *count);
@@ -134,50 +105,36 @@ void pairs_bulk_sort_desc(mmsbm_hip_ctx *c, const uint64_t *keys, uint64_t *sort
 void pairs_bulk_order(mmsbm_hip_ctx *c, const uint64_t *key, const double *score, size_t n, uint64_t *out_key,
                       double *out_score);
 // tu_market.hip -- the item side and capacity.  Item-side queries of the recommend session (audience.hpp): item ids inside
-// the session's catalogue
-void recommend_query_items(mmsbm_hip_ctx *c, int64_t n_items, const int32_t *items, int n, int32_t *users,
-                           double *scores, int32_t *counts);
+// the session's catalogue; out.items: the users
+void recommend_query_items(mmsbm_hip_ctx *c, int64_t n_items, const int32_t *items, int n, const TopNOut &out);
 void recommend_audience(mmsbm_hip_ctx *c, int64_t n_items, const int32_t *items, double min_score, int64_t capacity,
                         int64_t *offsets, int32_t *users, double *scores);
 // ... capacity-aware allocation (allocate.hpp): every user of the request (distinct ids) asks for n items, the caps as
 // planned by plan_allocate (serve_plan.hpp); at most max_rounds rounds
-void recommend_allocate(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, int n, const AllocPlan &plan,
-                        int max_rounds, int32_t *items, double *scores, int32_t *counts, int32_t *rounds,
-                        int32_t *converged);
+void recommend_allocate(mmsbm_hip_ctx *c, const UserRows &users, int n, const AllocPlan &plan, int max_rounds,
+                        const TopNOut &out, int32_t *rounds, int32_t *converged);
 // ... welfare-maximising assignment (assign.hpp): one item per user of the request (distinct ids) at most, the caps as
-// planned by plan_assign (serve_plan.hpp); the caller's output arrays (mmsbm_hip.h); its sort of a round's bids
-// (tu_pairs_bulk.hip): the places by (item, bid descending, place)
-struct AssignOut {
-  int32_t *items;
-  double *scores, *paid, *pi, *price, *price_sum;
-  int32_t *load, *rounds, *converged;
-};
-void recommend_assign(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, const AssignPlan &plan, double reserve,
-                      double eps, int max_rounds, const AssignOut &out);
+// planned by plan_assign (serve_plan.hpp); its sort of a round's bids (tu_pairs_bulk.hip): the places by (item, bid
+// descending, place)
+void recommend_assign(mmsbm_hip_ctx *c, const UserRows &users, const AssignPlan &plan, double reserve, double eps,
+                      int max_rounds, const AssignOut &out);
 size_t assign_sort_bytes(size_t n);
 void assign_sort_bids(hipStream_t st, void *tmp, size_t bytes, const int32_t *item, const double *bid,
                       const uint32_t *place, uint32_t *sorted, size_t n);
-// ... and greedy assortment selection in the recommend session (assortment.hpp), arguments checked: users ascending and
-// distinct; mode: MMSBM_HIP_ASSORT_*; level: the floor or the bar; cand as in recommend_query_within
-void recommend_assortment(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, int mode, double level,
-                          const int32_t *given, int n_given, const int32_t *cand, int n_cand, int n_pick, int32_t *items,
-                          double *gains, int32_t *count, int32_t *stop, double *given_gains, int32_t *served_items,
-                          double *served_scores);
-// tu_similar.hip -- nearest items / users (similar.hpp): the session of mmsbm_hip_similar_*, arguments checked
+// ... and greedy assortment selection (assortment.hpp): users ascending and distinct; mode: MMSBM_HIP_ASSORT_*; level:
+// the floor or the bar
+void recommend_assortment(mmsbm_hip_ctx *c, const UserRows &users, int mode, double level, const int32_t *given,
+                          int n_given, const Subset &cand, int n_pick, int32_t *items, double *gains, int32_t *count,
+                          int32_t *stop, double *given_gains, int32_t *served_items, double *served_scores);
+// tu_similar.hip -- nearest items / users (similar.hpp): the session of mmsbm_hip_similar_*; out.scores: the distances
 void similar_begin(mmsbm_hip_ctx *c, int side);
 void similar_add(mmsbm_hip_ctx *c);  // the selected slot (the caller holds a OneSlot)
-void similar_query(mmsbm_hip_ctx *c, int64_t n_rows, const int32_t *ids, int n, int32_t *out_ids, double *distance,
-                   int32_t *counts);
-// ... and the most informative items of a user (inform.hpp): the session of mmsbm_hip_inform_*, arguments checked;
-// cand / excl_* as in recommend_query_within, seen_* as in recommend_query_theta
+void similar_query(mmsbm_hip_ctx *c, int64_t n_rows, const int32_t *ids, int n, const TopNOut &out);
+// ... and the most informative items of a user (inform.hpp): the session of mmsbm_hip_inform_*; out.scores: the gains
 void inform_begin(mmsbm_hip_ctx *c);
 void inform_add(mmsbm_hip_ctx *c);  // the selected slot (the caller holds a OneSlot)
-void inform_query(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, const int32_t *cand, int n_cand,
-                  const int64_t *excl_offsets, const int32_t *excl_items, bool exclude_train, int n, int32_t *items,
-                  double *gains, int32_t *counts);
-void inform_query_theta(mmsbm_hip_ctx *c, int64_t n_users, const double *theta, const int64_t *seen_offsets,
-                        const int32_t *seen_items, const int32_t *cand, int n_cand, int n, int32_t *items,
-                        double *gains, int32_t *counts);
+void inform_query(mmsbm_hip_ctx *c, const UserQuery &q, bool exclude_train, int n, const TopNOut &out);
+void inform_query_theta(mmsbm_hip_ctx *c, const ThetaQuery &q, int n, const TopNOut &out);
 void inform_mean_theta(mmsbm_hip_ctx *c, double *out);
 // ... and the overlap of the restarts' groups (overlap.hpp): the session of mmsbm_hip_overlap_*, arguments checked
 void overlap_begin(mmsbm_hip_ctx *c, int side);

@@ -3,8 +3,10 @@
 // declares those calls.  What stays here: the exception-to-status wrapper with the last-error string, the guards the
 // entries share (parameters present, a session open), the device-info entries
 // (they have no context), pcg64_doubles and the host-only layout helpers of the CPU tests.  What a request's users,
-// subsets, lists, categories and user sets must satisfy is abi_request.hpp's, host-only code; an entry opens its session,
-// runs those checks and its own in the order its refusals promise, and makes the call.
+// subsets, lists, categories and user sets must satisfy is abi_request.hpp's, host-only code, and so are the values a
+// request crosses into the units as (UserQuery, ThetaQuery, Subset, RowCsr, Categories; TopNOut, ShelfOut, AssignOut): a
+// serving entry opens its session, runs its own checks, builds the value, checks it -- in the order its refusals
+// promise -- and makes the call with the value.
 //
 //   tu_create.hip   building a context, restart slots, the index read-back
 //   tu_params.hip   parameters in and out, update_coefficients' fetch, result, snapshots
@@ -12,7 +14,12 @@
 //                   algorithm is there)
 //   tu_once.hip     likelihood, prod_dist / predict, compute_omegas, the random start
 //   tu_options.hip  the option table
-//   tu_recommend.hip, tu_fold_in.hip, tu_heldout.hip, tu_explain.hip   the serving queries
+//   the serving queries, behind serve_frame.hpp (tu_serve_frame.hip: what they share):
+//   tu_recommend.hip  the recommend session; within a subset, ranks, positions, quota, shelves
+//   tu_rerank.hip     explore, ensemble, groups, diverse      tu_pairs.hip   top_pairs, top_pairs_bulk
+//   tu_market.hip     the item side, allocate, assign, assortment
+//   tu_similar.hip    similar, inform, overlap
+//   tu_fold_in.hip, tu_heldout.hip, tu_explain.hip (explain, leave-one-out)   sessions outside the frame
 
 #include "prelude.hpp"
 #include "pcg64.hpp"
@@ -483,7 +490,7 @@ int mmsbm_hip_recommend_query(mmsbm_hip_ctx *ctx, int64_t n_users, const int32_t
     require_n(n, "recommend", "items");
     if (n_users > 0 && (!users || !items)) throw std::invalid_argument("null argument");
     require_ids(users, n_users, ctx->ext_users, "recommend: user");
-    recommend_query(ctx, n_users, users, n, items, scores, counts);
+    recommend_query(ctx, {n_users, users}, n, {items, scores, counts});
   });
 }
 
@@ -497,8 +504,9 @@ int mmsbm_hip_recommend_query_theta(mmsbm_hip_ctx *ctx, int64_t n_users, const d
     require_rows(n_users);
     require_n(n, "recommend", "items");
     if (n_users > 0 && (!theta || !items)) throw std::invalid_argument("null argument");
-    seen_lists(seen_offsets, seen_items).check(n_users, rc.items, "recommend");
-    recommend_query_theta(ctx, n_users, theta, seen_offsets, seen_items, n, items, scores, counts);
+    const ThetaQuery q = theta_query(n_users, theta, seen_offsets, seen_items, 0, nullptr);
+    q.check(rc.items, "recommend_query_theta", "recommend");
+    recommend_query_theta(ctx, q, n, {items, scores, counts});
   });
 }
 
@@ -594,7 +602,7 @@ int mmsbm_hip_recommend_query_items(mmsbm_hip_ctx *ctx, int64_t n_items, const i
     require_n(n, "recommend", "items");
     if (n_items > 0 && (!items || !users)) throw std::invalid_argument("null argument");
     require_ids(items, n_items, rc.items, "recommend_query_items: item");
-    recommend_query_items(ctx, n_items, items, n, users, scores, counts);
+    recommend_query_items(ctx, n_items, items, n, {users, scores, counts});
   });
 }
 
@@ -612,7 +620,7 @@ int mmsbm_hip_recommend_allocate(mmsbm_hip_ctx *ctx, int64_t n_users, const int3
     const AllocPlan plan = plan_allocate(caps, rc.items, n_users, ctx->ext_users, MMSBM_HIP_RECOMMEND_MAX_N);
     if (plan.refused >= 0)
       throw ApiError(MMSBM_E_UNSUPPORTED, refused_cap("recommend_allocate", plan.refused, caps[plan.refused], n_users));
-    recommend_allocate(ctx, n_users, users, n, plan, max_rounds, items, scores, counts, rounds, converged);
+    recommend_allocate(ctx, {n_users, users}, n, plan, max_rounds, {items, scores, counts}, rounds, converged);
   });
 }
 
@@ -636,8 +644,8 @@ int mmsbm_hip_recommend_assign(mmsbm_hip_ctx *ctx, int64_t n_users, const int32_
     if (plan.refused >= 0)
       throw ApiError(MMSBM_E_UNSUPPORTED, refused_cap("recommend_assign", plan.refused, caps[plan.refused], n_users,
                                                       " (or the slots are more than 2^31)"));
-    recommend_assign(ctx, n_users, users, plan, reserve, epsilon, max_rounds,
-                     AssignOut{items, scores, paid, pi, price, price_sum, load, rounds, converged});
+    recommend_assign(ctx, {n_users, users}, plan, reserve, epsilon, max_rounds,
+                     {items, scores, paid, pi, price, price_sum, load, rounds, converged});
   });
 }
 
@@ -663,10 +671,9 @@ int mmsbm_hip_recommend_query_within(mmsbm_hip_ctx *ctx, int64_t n_users, const 
     require_rows(n_users);
     require_n(n, "recommend", "items");
     if (n_users > 0 && (!users || !items)) throw std::invalid_argument("null argument");
-    const UserQuery q{{n_users, users}, {n_cand, cand_items}, excluded_lists(excl_offsets, excl_items)};
+    const UserQuery q = user_query(n_users, users, n_cand, cand_items, excl_offsets, excl_items);
     q.check(ctx->ext_users, "recommend: user", rc.items, "recommend_query_within");
-    recommend_query_within(ctx, n_users, users, cand_items, n_cand, q.excl.offsets_of(n_users), excl_items, n,
-                           items, scores, counts);
+    recommend_query_within(ctx, q, n, {items, scores, counts});
   });
 }
 
@@ -679,10 +686,9 @@ int mmsbm_hip_recommend_query_theta_within(mmsbm_hip_ctx *ctx, int64_t n_users, 
     require_rows(n_users);
     require_n(n, "recommend", "items");
     if (n_users > 0 && (!theta || !items)) throw std::invalid_argument("null argument");
-    const ThetaQuery q{n_users, {n_cand, cand_items}, seen_lists(seen_offsets, seen_items)};
+    const ThetaQuery q = theta_query(n_users, theta, seen_offsets, seen_items, n_cand, cand_items);
     q.check(rc.items, "recommend_query_theta_within", "recommend");
-    recommend_query_theta_within(ctx, n_users, theta, seen_offsets, seen_items, cand_items, n_cand, n, items, scores,
-                                 counts);
+    recommend_query_theta(ctx, q, n, {items, scores, counts});
   });
 }
 
@@ -697,10 +703,9 @@ int mmsbm_hip_recommend_query_explore(mmsbm_hip_ctx *ctx, int64_t n_users, const
     require_n(n, "recommend_explore", "items");
     require_temperature(temperature, rc.w_min, rc.w_max, "recommend_query_explore");
     if (!pcg64_state || (n_users > 0 && (!users || !items))) throw std::invalid_argument("null argument");
-    const UserQuery q{{n_users, users}, {n_cand, cand_items}, excluded_lists(excl_offsets, excl_items)};
+    const UserQuery q = user_query(n_users, users, n_cand, cand_items, excl_offsets, excl_items);
     q.check(ctx->ext_users, "recommend: user", rc.items, "recommend_query_explore");
-    recommend_query_explore(ctx, n_users, users, cand_items, n_cand, q.excl.offsets_of(n_users), excl_items, n,
-                            temperature, pcg64_state, items, scores, propensity, counts);
+    recommend_query_explore(ctx, q, n, temperature, pcg64_state, {items, scores, counts}, propensity);
   });
 }
 
@@ -714,14 +719,13 @@ int mmsbm_hip_recommend_list_propensity(mmsbm_hip_ctx *ctx, int64_t n_users, con
     require_rows(n_users);
     require_temperature(temperature, rc.w_min, rc.w_max, who);
     if (n_users > 0 && (!users || !list_offsets)) throw std::invalid_argument("null argument");
-    const UserQuery q{{n_users, users}, {n_cand, cand_items}, excluded_lists(excl_offsets, excl_items)};
+    const UserQuery q = user_query(n_users, users, n_cand, cand_items, excl_offsets, excl_items);
     q.check(ctx->ext_users, "recommend: user", rc.items, who);
-    const RowCsr lists{list_offsets, list_items, "list_offsets", "user", "listed items", "listed item"};
+    const RowCsr lists = listed_items(list_offsets, list_items).of_rows(n_users);
     lists.check(n_users, rc.items, who);
     if (n_users > 0 && list_offsets[n_users] > 0 && !propensity) throw std::invalid_argument("null argument");
-    require_lists(list_offsets, list_items, n_users, who);
-    recommend_list_propensity(ctx, n_users, users, cand_items, n_cand, q.excl.offsets_of(n_users), excl_items,
-                              temperature, lists.offsets_of(n_users), list_items, scores, propensity);
+    require_lists(lists, n_users, who);
+    recommend_list_propensity(ctx, q, temperature, lists, scores, propensity);
   });
 }
 
@@ -748,11 +752,11 @@ int mmsbm_hip_recommend_query_quota(mmsbm_hip_ctx *ctx, int64_t n_users, const i
     require_rows(n_users);
     require_n(n, "recommend", "items");
     if (n_users > 0 && (!users || !items)) throw std::invalid_argument("null argument");
-    const UserQuery q{{n_users, users}, {n_cand, cand_items}, excluded_lists(excl_offsets, excl_items)};
+    const UserQuery q = user_query(n_users, users, n_cand, cand_items, excl_offsets, excl_items);
     q.check(ctx->ext_users, "recommend: user", rc.items, "recommend_query_quota");
-    require_categories(n_cats, cat_offsets, cat_items, cat_caps, rc.items, "recommend_query_quota");
-    recommend_query_quota(ctx, n_users, users, cand_items, n_cand, q.excl.offsets_of(n_users), excl_items,
-                          n_cats, cat_offsets, cat_items, cat_caps, n, items, scores, counts);
+    const Categories cats{n_cats, cat_offsets, cat_items, cat_caps};
+    cats.check(rc.items, "recommend_query_quota");
+    recommend_query_quota(ctx, q, cats, n, {items, scores, counts});
   });
 }
 
@@ -766,11 +770,11 @@ int mmsbm_hip_recommend_query_theta_quota(mmsbm_hip_ctx *ctx, int64_t n_users, c
     require_rows(n_users);
     require_n(n, "recommend", "items");
     if (n_users > 0 && (!theta || !items)) throw std::invalid_argument("null argument");
-    const ThetaQuery q{n_users, {n_cand, cand_items}, seen_lists(seen_offsets, seen_items)};
+    const ThetaQuery q = theta_query(n_users, theta, seen_offsets, seen_items, n_cand, cand_items);
     q.check(rc.items, "recommend_query_theta_quota", "recommend");
-    require_categories(n_cats, cat_offsets, cat_items, cat_caps, rc.items, "recommend_query_theta_quota");
-    recommend_query_theta_quota(ctx, n_users, theta, seen_offsets, seen_items, cand_items, n_cand, n_cats, cat_offsets,
-                                cat_items, cat_caps, n, items, scores, counts);
+    const Categories cats{n_cats, cat_offsets, cat_items, cat_caps};
+    cats.check(rc.items, "recommend_query_theta_quota");
+    recommend_query_theta_quota(ctx, q, cats, n, {items, scores, counts});
   });
 }
 
@@ -788,11 +792,11 @@ int mmsbm_hip_recommend_query_shelves(mmsbm_hip_ctx *ctx, int64_t n_users, const
     const ShelfOut out{shelf_cats, shelf_values, shelf_available, shelf_counts, items, scores, item_counts};
     require_shelf_ask(n_users, n_cats, ask, out, "recommend_query_shelves");
     if (n_users > 0 && !users) throw std::invalid_argument("null argument");
-    const UserQuery q{{n_users, users}, {n_cand, cand_items}, excluded_lists(excl_offsets, excl_items)};
+    const UserQuery q = user_query(n_users, users, n_cand, cand_items, excl_offsets, excl_items);
     q.check(ctx->ext_users, "recommend: user", rc.items, "recommend_query_shelves");
-    require_categories(n_cats, cat_offsets, cat_items, nullptr, rc.items, "recommend_query_shelves", false);
-    recommend_query_shelves(ctx, n_users, users, cand_items, n_cand, q.excl.offsets_of(n_users), excl_items,
-                            n_cats, cat_offsets, cat_items, ask, out);
+    const Categories cats{n_cats, cat_offsets, cat_items, nullptr};
+    cats.check(rc.items, "recommend_query_shelves", false);
+    recommend_query_shelves(ctx, q, cats, ask, out);
   });
 }
 
@@ -810,11 +814,11 @@ int mmsbm_hip_recommend_query_theta_shelves(mmsbm_hip_ctx *ctx, int64_t n_users,
     const ShelfOut out{shelf_cats, shelf_values, shelf_available, shelf_counts, items, scores, item_counts};
     require_shelf_ask(n_users, n_cats, ask, out, "recommend_query_theta_shelves");
     if (n_users > 0 && !theta) throw std::invalid_argument("null argument");
-    const ThetaQuery q{n_users, {n_cand, cand_items}, seen_lists(seen_offsets, seen_items)};
+    const ThetaQuery q = theta_query(n_users, theta, seen_offsets, seen_items, n_cand, cand_items);
     q.check(rc.items, "recommend_query_theta_shelves", "recommend");
-    require_categories(n_cats, cat_offsets, cat_items, nullptr, rc.items, "recommend_query_theta_shelves", false);
-    recommend_query_theta_shelves(ctx, n_users, theta, seen_offsets, seen_items, cand_items, n_cand, n_cats, cat_offsets,
-                                  cat_items, ask, out);
+    const Categories cats{n_cats, cat_offsets, cat_items, nullptr};
+    cats.check(rc.items, "recommend_query_theta_shelves", false);
+    recommend_query_theta_shelves(ctx, q, cats, ask, out);
   });
 }
 
@@ -826,11 +830,11 @@ int mmsbm_hip_recommend_rank(mmsbm_hip_ctx *ctx, int64_t n_users, const int32_t 
     require_n(n, "recommend", "items");
     if (n_users > 0 && (!users || !offsets || !items)) throw std::invalid_argument("null argument");
     require_ids(users, n_users, ctx->ext_users, "recommend_rank: user");
-    RowCsr{offsets, cand_items, "offsets", "user", "candidate items", "candidate item id"}.check(n_users, rc.items,
-                                                                                                 "recommend_rank");
+    const RowCsr lists{offsets, cand_items, "offsets", "user", "candidate items", "candidate item id"};
+    lists.check(n_users, rc.items, "recommend_rank");
     for (int64_t b = 0; b < n_users; ++b)
       require_candidates(cand_items + offsets[b], offsets[b], offsets[b + 1] - offsets[b], rc.items, "recommend_rank");
-    recommend_rank(ctx, n_users, users, offsets, cand_items, n, items, scores, counts);
+    recommend_rank(ctx, {n_users, users}, lists, n, {items, scores, counts});
   });
 }
 
@@ -859,7 +863,7 @@ int mmsbm_hip_similar_query(mmsbm_hip_ctx *ctx, int64_t n_rows, const int32_t *i
     require_n(n, "similar", "rows");
     if (n_rows > 0 && (!ids || !out_ids)) throw std::invalid_argument("null argument");
     require_ids(ids, n_rows, sm.rows, sm.side == 0 ? "similar: item" : "similar: user");
-    similar_query(ctx, n_rows, ids, n, out_ids, distance, counts);
+    similar_query(ctx, n_rows, ids, n, {out_ids, distance, counts});
   });
 }
 
@@ -897,10 +901,9 @@ int mmsbm_hip_recommend_diverse(mmsbm_hip_ctx *ctx, int64_t n_users, const int32
       throw std::invalid_argument("recommend_diverse: trade_off must be finite and at least 0");
     require_n(pool, "recommend_diverse", "pool entries");
     if (n_users > 0 && (!users || !items)) throw std::invalid_argument("null argument");
-    const UserQuery q{{n_users, users}, {n_cand, cand_items}, excluded_lists(excl_offsets, excl_items)};
+    const UserQuery q = user_query(n_users, users, n_cand, cand_items, excl_offsets, excl_items);
     q.check(ctx->ext_users, "recommend_diverse: user", rc.items, "recommend_diverse");
-    recommend_diverse(ctx, n_users, users, cand_items, n_cand, q.excl.offsets_of(n_users), excl_items, n, pool,
-                      trade_off, items, scores, distances, counts);
+    recommend_diverse(ctx, q, n, pool, trade_off, {items, scores, counts}, distances);
   });
 }
 
@@ -918,11 +921,12 @@ int mmsbm_hip_recommend_query_groups(mmsbm_hip_ctx *ctx, int64_t n_groups, const
       throw std::invalid_argument("recommend_query_groups: bar must be finite");
     require_n(n, "recommend_query_groups", "items");
     if (n_groups > 0 && (!offsets || !items)) throw std::invalid_argument("null argument");
-    RowCsr{offsets, members, "offsets", "group", "members", "member"}.check(n_groups, ctx->ext_users,
-                                                                           "recommend_query_groups");
+    const RowCsr groups{offsets, members, "offsets", "group", "members", "member"};
+    groups.check(n_groups, ctx->ext_users, "recommend_query_groups");
     require_distinct_members(offsets, members, n_groups, ctx->ext_users, "recommend_query_groups");
-    require_subset(cand_items, n_cand, rc.items, "recommend_query_groups");
-    recommend_query_groups(ctx, n_groups, offsets, members, mode, bar, cand_items, n_cand, n, items, scores, counts);
+    const Subset cand{n_cand, cand_items};
+    cand.check(rc.items, "recommend_query_groups");
+    recommend_query_groups(ctx, n_groups, groups, mode, bar, cand, n, {items, scores, counts});
   });
 }
 
@@ -951,9 +955,10 @@ int mmsbm_hip_recommend_assortment(mmsbm_hip_ctx *ctx, int64_t n_users, const in
       if (users[m] <= users[m - 1])
         throw std::invalid_argument("recommend_assortment: users must be strictly ascending (row " + std::to_string(m) + ")");
     require_ids(given_items, n_given, rc.items, "recommend_assortment: given item");
-    require_subset(cand_items, n_cand, rc.items, "recommend_assortment");
-    recommend_assortment(ctx, n_users, users, mode, level, given_items, n_given, cand_items, n_cand, c, items, gains, count,
-                         stop, given_gains, served_items, served_scores);
+    const Subset cand{n_cand, cand_items};
+    cand.check(rc.items, "recommend_assortment");
+    recommend_assortment(ctx, {n_users, users}, mode, level, given_items, n_given, cand, c, items, gains, count, stop,
+                         given_gains, served_items, served_scores);
   });
 }
 
@@ -970,10 +975,9 @@ int mmsbm_hip_recommend_query_ensemble(mmsbm_hip_ctx *ctx, int64_t n_users, cons
       throw std::invalid_argument("recommend_query_ensemble: risk must be finite");
     require_n(n, "recommend_query_ensemble", "items");
     if (n_users > 0 && (!users || !items)) throw std::invalid_argument("null argument");
-    const UserQuery q{{n_users, users}, {n_cand, cand_items}, excluded_lists(excl_offsets, excl_items)};
+    const UserQuery q = user_query(n_users, users, n_cand, cand_items, excl_offsets, excl_items);
     q.check(ctx->ext_users, "recommend_query_ensemble: user", rc.items, "recommend_query_ensemble");
-    recommend_query_ensemble(ctx, n_users, users, mode, risk, cand_items, n_cand, q.excl.offsets_of(n_users),
-                             excl_items, n, items, scores, counts);
+    recommend_query_ensemble(ctx, q, mode, risk, n, {items, scores, counts});
   });
 }
 
@@ -1013,10 +1017,9 @@ int mmsbm_hip_inform_query(mmsbm_hip_ctx *ctx, int64_t n_users, const int32_t *u
     require_rows(n_users);
     require_n(n, "inform", "items");
     if (n_users > 0 && (!users || !items)) throw std::invalid_argument("null argument");
-    const UserQuery q{{n_users, users}, {n_cand, cand_items}, excluded_lists(excl_offsets, excl_items)};
+    const UserQuery q = user_query(n_users, users, n_cand, cand_items, excl_offsets, excl_items);
     q.check(ctx->ext_users, "inform: user", ctx->ext_items, "inform_query");
-    inform_query(ctx, n_users, users, cand_items, n_cand, q.excl.offsets_of(n_users), excl_items,
-                 exclude_train != 0, n, items, gains, counts);
+    inform_query(ctx, q, exclude_train != 0, n, {items, gains, counts});
   });
 }
 
@@ -1029,9 +1032,9 @@ int mmsbm_hip_inform_query_theta(mmsbm_hip_ctx *ctx, int64_t n_users, const doub
     require_n(n, "inform", "items");
     if (n_users > 0 && (!theta || !items)) throw std::invalid_argument("null argument");
     require_theta_entries(theta, static_cast<size_t>(inf.slots) * static_cast<size_t>(n_users) * ctx->ext_k, "inform");
-    const ThetaQuery q{n_users, {n_cand, cand_items}, seen_lists(seen_offsets, seen_items)};
+    const ThetaQuery q = theta_query(n_users, theta, seen_offsets, seen_items, n_cand, cand_items);
     q.check(ctx->ext_items, "inform_query_theta", "inform");
-    inform_query_theta(ctx, n_users, theta, seen_offsets, seen_items, cand_items, n_cand, n, items, gains, counts);
+    inform_query_theta(ctx, q, n, {items, gains, counts});
   });
 }
 

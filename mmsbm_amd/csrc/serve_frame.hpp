@@ -24,20 +24,21 @@ std::vector<int32_t> upload_train_lists(mmsbm_hip_ctx *c, DevBuf<int32_t> &d_off
 struct DevCsr {
   DevBuf<int32_t> off, val;
   std::vector<int32_t> off_h;
-  static int64_t entries(const int64_t *offsets, int64_t n_rows) { return offsets && n_rows > 0 ? offsets[n_rows] : 0; }
-  void upload(const int64_t *offsets, const int32_t *values, int64_t n_rows, hipStream_t st);
+  static int64_t entries(const RowCsr &lists, int64_t n_rows) { return lists.offsets && n_rows > 0 ? lists.offsets[n_rows] : 0; }
+  void upload(const RowCsr &lists, int64_t n_rows, hipStream_t st);
   SeenLists lists() const { return {off.ptr, val.ptr}; }
 };
 
-// The rows a caller brings instead of the session's users: theta [S][n_users][K] on the device as it is, the identity
-// ids 0 .. n_users - 1 (request row b is row b of every slot's block) and the caller's seen lists by row (null: none).
-// The caller has checked the memory.
+// The rows a caller brings instead of the session's users: q.theta [S][n_users][K] on the device as it is, the identity
+// ids 0 .. n_users - 1 (request row b is row b of every slot's block) and the caller's seen lists by row (no offsets:
+// none).  The caller has checked the memory.  users(): the rows as a query of their own -- q's subset, no own lists.
 struct CallerRows {
   DevBuf<double> th;
   std::vector<int32_t> ids;
   DevCsr seen;
-  CallerRows(mmsbm_hip_ctx *c, int S, int64_t n_users, const double *theta, const int64_t *seen_offsets,
-             const int32_t *seen_items);
+  Subset cand;
+  CallerRows(mmsbm_hip_ctx *c, int S, const ThetaQuery &q);
+  UserQuery users() const { return {{static_cast<int64_t>(ids.size()), ids.data()}, cand, RowCsr{}}; }
 };
 
 // W [K][L] of a slot from its p (external sides: ExtSlot's p, rs, ks, ls) and the R rating weights w (device): the one
@@ -77,7 +78,7 @@ void rec_score_batch(mmsbm_hip_ctx *c, const double *x, size_t xs, const int32_t
 void own_exclude_batch(hipStream_t st, const DevCsr &own, int64_t b0, int nb, const int32_t *col_of, double *sc, size_t ld);
 
 // Every row of a top-N answer as "no candidate": counts 0, ids -1, values -inf
-void top_n_blank(int64_t n_rows, int n, int32_t *items, double *scores, int32_t *counts);
+void top_n_blank(int64_t n_rows, int n, const TopNOut &out);
 
 // What top_n_device leaves on the device: row b's os / oi [b * n + k], k < on[b] (the entries behind are not written)
 struct TopNDev {
@@ -194,17 +195,17 @@ inline int32_t item_of(const int32_t *cand, int32_t col) { return cand ? cand[co
 // cand (host; null: none): the ids are columns of that list and leave as its items.  dev_second / second (null: none): a
 // second value per place, [row * n + k] on the device as dev.os, to the host as the scores (explore.hpp's propensities).
 void top_n_copy_out(mmsbm_hip_ctx *c, const TopNDev &dev, EventPair &ev, int64_t n_users, int n, TimedCall timed,
-                    int32_t *items, double *scores, int32_t *counts, const int32_t *cand = nullptr,
-                    const double *dev_second = nullptr, double *second = nullptr);
+                    const TopNOut &out, const int32_t *cand = nullptr, const double *dev_second = nullptr,
+                    double *second = nullptr);
 
 // top_n_device with the result copied to the host; `timed`: the timer that takes the device time of the query's kernels
 template <class Fill>
 void top_n_run(mmsbm_hip_ctx *c, int I, int64_t n_users, const int32_t *users, int n, const char *what, Fill &&fill,
-               TimedCall timed, int32_t *items, double *scores, int32_t *counts) {
-  top_n_blank(n_users, n, items, scores, counts);
+               TimedCall timed, const TopNOut &out) {
+  top_n_blank(n_users, n, out);
   if (n_users == 0) return;
   top_n_device(c, I, n_users, users, n, what, 0, fill, [&](const TopNDev &dev, EventPair &ev) {
-    top_n_copy_out(c, dev, ev, n_users, n, timed, items, scores, counts);
+    top_n_copy_out(c, dev, ev, n_users, n, timed, out);
   });
 }
 
@@ -214,14 +215,15 @@ struct CatTable {
   DevBuf<int32_t> cand, col;  // [C]; [items of the catalogue]
   DevBuf<double> y;           // [slot][C][rank]
   float ms = 0.f;
-  // the device memory of the table of cand[0 .. C) (null: no table)
-  static size_t bytes(const RecSession &rc, const int32_t *cand, int C) {
-    return cand ? static_cast<size_t>(rc.slots) * C * rc.rank * sizeof(double) + (static_cast<size_t>(C) + rc.items) * 4 : 0;
+  // the device memory of the table of a subset (the whole catalogue: no table)
+  static size_t bytes(const RecSession &rc, const Subset &cand) {
+    return cand.items ? static_cast<size_t>(rc.slots) * cand.n * rc.rank * sizeof(double) + (static_cast<size_t>(cand.n) + rc.items) * 4 : 0;
   }
 };
 
-// cand[0 .. C) (host; ascending, distinct ids of the session's catalogue) -> t (the memory was found free by the caller)
-void cat_table(mmsbm_hip_ctx *c, const int32_t *cand, int C, CatTable &t);
+// cand (host; its items given: ascending, distinct ids of the session's catalogue) -> t (the memory was found free by
+// the caller)
+void cat_table(mmsbm_hip_ctx *c, const Subset &cand, CatTable &t);
 
 // What a query within the candidates holds on the device beside its batches: the query's own excluded items by request
 // row and the candidates' compact table (cat_table), and from them the item table y (slots ys doubles apart) of C rows
@@ -236,9 +238,8 @@ struct WithinPrep {
   const int32_t *dcand() const { return has_cand ? ct.cand.ptr : nullptr; }
 };
 
-// cand / n_cand / xoff / xit as rec_within_device's: the memory is checked, the lists uploaded, the compact table made
-void within_prepare(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *cand, int n_cand, const int64_t *xoff,
-                    const int32_t *xit, WithinPrep &w);
+// q's subset and own lists as rec_within_device's: the memory is checked, the lists uploaded, the compact table made
+void within_prepare(mmsbm_hip_ctx *c, const UserQuery &q, WithinPrep &w);
 
 // The values sc [nb][C] of the batch of request rows b0 .. b0 + nb (device ids ub): `tiles`, then -inf over what `seen`
 // leaves out for the rows' ids and over the query's own excluded items.  The one copy of these launches: the `fill` of
@@ -256,9 +257,9 @@ void within_fill(mmsbm_hip_ctx *c, const WithinPrep &w, Tiles &&tiles, SeenLists
   if (w.has_own) own_exclude_batch(st, w.own, b0, nb, w.ct.col.ptr, sc, static_cast<size_t>(C));
 }
 
-// The device side of a recommend query within the candidates cand[0 .. n_cand) (host; ascending, distinct ids of the
-// session's catalogue; null: the whole catalogue), and with the query's own excluded items: row b of the request also
-// leaves out xit[xoff[b] .. xoff[b + 1]) (host, any order, repeats allowed; null: none).  catalogue.hpp.
+// The device side of a recommend query q (host): within its candidates (ascending, distinct ids of the session's
+// catalogue; no items: the whole catalogue), and with the query's own excluded items: row b of the request also leaves
+// out q.excl's list b (any order, repeats allowed; no offsets: none).  catalogue.hpp.
 // `tiles(y, ys, C, ub, nb, sc)` enqueues the kernel that writes the values sc [nb][C] of the batch's rows ub (device ids)
 // against the C rows of the item table y (slots ys doubles apart: the catalogue's, or the candidates' compact table) --
 // the score tiles of recommend_query (rec_tiles), the aggregate over the restarts (ensemble.hpp); seen (indexed by user
@@ -269,13 +270,12 @@ void within_fill(mmsbm_hip_ctx *c, const WithinPrep &w, Tiles &&tiles, SeenLists
 // capped categories of quota.hpp (in the buffer's columns; `capped` says so: the memory check then names the query as one
 // within the candidates), the perturbation of explore.hpp; `each`: top_n_device's (explore.hpp uses both).
 template <class Tiles, class Then, class After = NoFillStage, class Each = NoBatchStage>
-void rec_within_device(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, SeenLists seen, const int32_t *cand,
-                       int n_cand, const int64_t *xoff, const int32_t *xit, int n, size_t extra, Tiles &&tiles,
+void rec_within_device(mmsbm_hip_ctx *c, const UserQuery &q, SeenLists seen, int n, size_t extra, Tiles &&tiles,
                        Then &&then, After &&after = After{}, Each &&each = Each{}, bool capped = false) {
   WithinPrep w;
-  within_prepare(c, n_users, cand, n_cand, xoff, xit, w);
-  top_n_device(c, w.C, n_users, users, n,
-               cand || xoff || capped ? "recommend: a batch of users within the candidates" : "recommend: a batch of users", extra,
+  within_prepare(c, q, w);
+  top_n_device(c, w.C, q.users.n, q.users.ids, n,
+               q.cand.items || q.excl.offsets || capped ? "recommend: a batch of users within the candidates" : "recommend: a batch of users", extra,
                [&](const int32_t *ub, int nb, int64_t b0, double *sc) {
                  within_fill(c, w, tiles, seen, ub, nb, b0, sc);
                  after(w, ub, nb, sc);
@@ -293,31 +293,31 @@ inline auto rec_tiles(mmsbm_hip_ctx *c, const double *x, size_t xs) {
 // rec_within_device with the result copied to the host (top_n_blank done by the caller), the columns as item ids; the device time of the query's kernels goes to `timed`.  No column or no row: every row stays empty.
 // `after` / `capped`: rec_within_device's.
 template <class Tiles, class After = NoFillStage>
-void rec_within_run(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, SeenLists seen, const int32_t *cand,
-                    int n_cand, const int64_t *xoff, const int32_t *xit, int n, Tiles &&tiles, TimedCall timed,
-                    int32_t *items, double *scores, int32_t *counts, After &&after = After{}, bool capped = false) {
+void rec_within_run(mmsbm_hip_ctx *c, const UserQuery &q, SeenLists seen, int n, Tiles &&tiles, TimedCall timed,
+                    const TopNOut &out, After &&after = After{}, bool capped = false) {
   c->last_ms[timed] = 0.f;
-  if ((cand ? n_cand : c->rc->items) == 0 || n_users == 0) return;
-  rec_within_device(c, n_users, users, seen, cand, n_cand, xoff, xit, n, 0, tiles,
+  if (q.cand.columns(c->rc->items) == 0 || q.users.n == 0) return;
+  rec_within_device(c, q, seen, n, 0, tiles,
                     [&](const TopNDev &dev, EventPair &ev, const int32_t *, float prep_ms) {
-                      top_n_copy_out(c, dev, ev, n_users, n, timed, items, scores, counts, cand);
+                      top_n_copy_out(c, dev, ev, q.users.n, n, timed, out, q.cand.items);
                       c->last_ms[timed] += prep_ms;
                     },
                     after, NoBatchStage{}, capped);
 }
 
 // The caller's theta rows [S][n_users][K] folded exactly as recommend_add folds a slot's own theta (x = theta, or
-// theta W when K > L), then `run(x, xs, ids, seen)` over the rows 0 .. n_users - 1 with the caller's seen lists
+// theta W when K > L), then `run(x, xs, users, seen)` over the rows 0 .. n_users - 1 as a query of their own
+// (CallerRows::users) with the caller's seen lists
 template <class Run>
-void rec_theta_fold(mmsbm_hip_ctx *c, int64_t n_users, const double *theta, const int64_t *seen_offsets,
-                    const int32_t *seen_items, Run &&run) {
+void rec_theta_fold(mmsbm_hip_ctx *c, const ThetaQuery &q, Run &&run) {
   const int K = c->ext_k, L = c->ext_l, rank = c->rc->rank, S = c->rc->slots;
+  const int64_t n_users = q.n_users;
   const size_t tk = static_cast<size_t>(n_users) * K, xs = static_cast<size_t>(n_users) * rank;
   require_free_mem(S * (tk + xs) * sizeof(double) +
-                       (static_cast<size_t>(n_users) + 1 + DevCsr::entries(seen_offsets, n_users)) * 4,
+                       (static_cast<size_t>(n_users) + 1 + DevCsr::entries(q.seen, n_users)) * 4,
                    "recommend: the caller's theta rows");
   hipStream_t st = c->stream;
-  CallerRows rows(c, S, n_users, theta, seen_offsets, seen_items);
+  CallerRows rows(c, S, q);
   DevBuf<double> x;
   x.alloc(S * xs);
   const size_t kl = static_cast<size_t>(K) * L;
@@ -326,7 +326,7 @@ void rec_theta_fold(mmsbm_hip_ctx *c, int64_t n_users, const double *theta, cons
     fold_rows(st, rows.th.ptr + s * tk, K, m, L, 1, x.ptr + s * xs, static_cast<int>(n_users), rank);
   }
   HIP_CHECK(hipGetLastError());
-  run(x.ptr, xs, rows.ids.data(), rows.seen.lists());
+  run(x.ptr, xs, rows.users(), rows.seen.lists());
 }
 
 }  // namespace mmsbm_hip_impl

@@ -53,8 +53,7 @@ void rec_item_lists(mmsbm_hip_ctx *c) {
 
 }  // namespace
 
-void recommend_query_items(mmsbm_hip_ctx *c, int64_t n_items, const int32_t *items, int n, int32_t *users,
-                           double *scores, int32_t *counts) {
+void recommend_query_items(mmsbm_hip_ctx *c, int64_t n_items, const int32_t *items, int n, const TopNOut &out) {
   use_device(c);
   rec_item_lists(c);
   const RecSession &rc = *c->rc;
@@ -63,7 +62,7 @@ void recommend_query_items(mmsbm_hip_ctx *c, int64_t n_items, const int32_t *ite
             [&](const int32_t *ib, int nb, int64_t, double *sc) {  // rec_score_batch with the sides exchanged
               score_tiles(c, rc.y.ptr, static_cast<size_t>(rc.items) * rc.rank, rc.x.ptr, rc.x_stride(), rc.users, ib, nb, ex, sc);
             },
-            T_RECOMMEND, users, scores, counts);
+            T_RECOMMEND, out);
 }
 
 void recommend_audience(mmsbm_hip_ctx *c, int64_t n_items, const int32_t *items, double min_score, int64_t capacity,
@@ -172,11 +171,11 @@ void recommend_audience(mmsbm_hip_ctx *c, int64_t n_items, const int32_t *items,
 // The rounds of deferred acceptance: per round the batches of recommend_query (user pass) and of recommend_query_items
 // over the capped items (item pass), both with alloc_score_kernel in place of rec_score_kernel; P, sigma and tau stay on
 // the device, and the host reads one int per round.  users: distinct ids (checked by the C ABI); plan: the caps.
-void recommend_allocate(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, int n, const AllocPlan &plan,
-                        int max_rounds, int32_t *items, double *scores, int32_t *counts, int32_t *rounds,
-                        int32_t *converged) {
+void recommend_allocate(mmsbm_hip_ctx *c, const UserRows &users, int n, const AllocPlan &plan, int max_rounds,
+                        const TopNOut &out, int32_t *rounds, int32_t *converged) {
   use_device(c);
-  top_n_blank(n_users, n, items, scores, counts);
+  const int64_t n_users = users.n;
+  top_n_blank(n_users, n, out);
   *rounds = 0;
   *converged = 1;
   c->last_ms[T_ALLOCATE] = 0.f;
@@ -210,7 +209,7 @@ void recommend_allocate(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users,
   const SelectStage sel(up, ip);  // (the two passes follow each other: one scratch)
   ps.alloc(outs); pi.alloc(outs); pn.alloc(static_cast<size_t>(n_users));
   du.alloc(static_cast<size_t>(n_users));
-  HIP_CHECK(hipMemcpyAsync(du.ptr, users, sizeof(int32_t) * n_users, hipMemcpyHostToDevice, st));
+  HIP_CHECK(hipMemcpyAsync(du.ptr, users.ids, sizeof(int32_t) * n_users, hipMemcpyHostToDevice, st));
   tau_s.upload(tau_h, st); tau_u.upload(tau_uh, st);
   if (NC > 0) {
     ls.alloc(lists); lu.alloc(lists); ln.alloc(static_cast<size_t>(bi));
@@ -265,7 +264,7 @@ void recommend_allocate(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users,
          pi.ptr, pn.ptr);
   HIP_CHECK(hipGetLastError());
   ev.stop(st);
-  top_n_copy_out(c, TopNDev{ps.ptr, pi.ptr, pn.ptr}, ev, n_users, n, T_ALLOCATE, items, scores, counts);
+  top_n_copy_out(c, TopNDev{ps.ptr, pi.ptr, pn.ptr}, ev, n_users, n, T_ALLOCATE, out);
   *rounds = round;
   c->alloc_rounds = round;
 }
@@ -274,10 +273,11 @@ void recommend_allocate(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users,
 // The rounds of the forward auction over the compacted list of active rows, then the certificate pass over all rows; the
 // row state, the slots and the prices stay on the device, and the host reads one int per round: the next round's active
 // rows.  users: distinct ids (checked by the C ABI), any order -- the device works in id order.
-void recommend_assign(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, const AssignPlan &plan, double reserve,
-                      double eps, int max_rounds, const AssignOut &out) {
+void recommend_assign(mmsbm_hip_ctx *c, const UserRows &rows, const AssignPlan &plan, double reserve, double eps,
+                      int max_rounds, const AssignOut &out) {
   use_device(c);
   const RecSession &rc = *c->rc;
+  const int64_t n_users = rows.n;
   const int NI = rc.items, rank = rc.rank;
   for (int64_t b = 0; b < n_users; ++b) {
     out.items[b] = -1;
@@ -303,9 +303,9 @@ void recommend_assign(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, c
   // the request in id order: row r is request row at[r]
   std::vector<int64_t> at(nu);
   for (size_t b = 0; b < nu; ++b) at[b] = static_cast<int64_t>(b);
-  std::sort(at.begin(), at.end(), [&](int64_t a, int64_t b) { return users[a] < users[b]; });
+  std::sort(at.begin(), at.end(), [&](int64_t a, int64_t b) { return rows.ids[a] < rows.ids[b]; });
   std::vector<int32_t> ids(nu);
-  for (size_t r = 0; r < nu; ++r) ids[r] = users[at[r]];
+  for (size_t r = 0; r < nu; ++r) ids[r] = rows.ids[at[r]];
   const int64_t bu = rec_batch_users(NI, n_users);
   const SelectPlan sp = select_plan(c, NI, bu, 2);
   const int nblk = static_cast<int>((n_users + kBlock - 1) / kBlock);
@@ -434,15 +434,15 @@ void recommend_assign(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, c
 // by one (their gain over the state before them, then the state); then n_pick rounds of gain / join / pick / update
 // enqueued back to back -- no host wait and no copy between them: once the stop flag is set on the device the launches
 // that follow return at once -- and ONE read-back at the end.  users: ascending, distinct.
-void recommend_assortment(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, int mode, double level,
-                          const int32_t *given, int n_given, const int32_t *cand, int n_cand, int n_pick, int32_t *items,
-                          double *gains, int32_t *count, int32_t *stop, double *given_gains, int32_t *served_items,
-                          double *served_scores) {
+void recommend_assortment(mmsbm_hip_ctx *c, const UserRows &asked, int mode, double level, const int32_t *given,
+                          int n_given, const Subset &sub, int n_pick, int32_t *items, double *gains, int32_t *count,
+                          int32_t *stop, double *given_gains, int32_t *served_items, double *served_scores) {
   use_device(c);
   const RecSession &rc = *c->rc;
+  const int32_t *users = asked.ids, *cand = sub.items;  // (cand null: the columns are the items)
   for (float *t : {&c->last_ms[T_ASSORT], &c->asrt_ms[0], &c->asrt_ms[1], &c->asrt_ms[2]}) *t = 0.f;
   const int NI = rc.items, rank = rc.rank, S = rc.slots;
-  const int C = cand ? n_cand : NI;
+  const int C = sub.columns(NI);
   for (int k = 0; k < n_pick; ++k) {
     items[k] = -1;
     gains[k] = 0.0;
@@ -450,17 +450,17 @@ void recommend_assortment(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *user
   for (int g = 0; g < n_given; ++g) given_gains[g] = 0.0;
   *count = 0;
   *stop = n_pick == 0 ? MMSBM_HIP_ASSORT_STOP_C : C == 0 ? MMSBM_HIP_ASSORT_STOP_NO_CANDIDATES : MMSBM_HIP_ASSORT_STOP_NO_GAIN;
-  if (n_users == 0) return;  // (nobody to serve: no item gains anything)
-  const int nu = static_cast<int>(n_users);
-  const AssortPlan p = plan_assortment(n_users, C, c->n_cus, c->asrt_run,
+  if (asked.n == 0) return;  // (nobody to serve: no item gains anything)
+  const int nu = static_cast<int>(asked.n);
+  const AssortPlan p = plan_assortment(asked.n, C, c->n_cus, c->asrt_run,
                                        c->asrt_part > 0 ? static_cast<size_t>(c->asrt_part) : kAsrtPartBytes);
   // a given item: its one tile of the catalogue, in the runs of the rounds -- a column's sum is the same additions in the
   // same order whether the item is given or chosen, so a set valued as given items gets the greedy's bits
-  const AssortPlan pg = plan_assortment(n_users, kRecTile, c->n_cus, C > 0 ? p.run_blocks : c->asrt_run);
+  const AssortPlan pg = plan_assortment(asked.n, kRecTile, c->n_cus, C > 0 ? p.run_blocks : c->asrt_run);
   const bool rounds = n_pick > 0 && C > 0;
   const size_t ycs = static_cast<size_t>(C) * rank;
   const size_t n_res = static_cast<size_t>(n_pick) + static_cast<size_t>(n_given);
-  require_free_mem(CatTable::bytes(rc, cand, C) + static_cast<size_t>(nu) * (4 + 8 + 4 + 8) + static_cast<size_t>(C) * 4 + n_res * 12 +
+  require_free_mem(CatTable::bytes(rc, sub) + static_cast<size_t>(nu) * (4 + 8 + 4 + 8) + static_cast<size_t>(C) * 4 + n_res * 12 +
                        (rounds ? p.part_doubles() * sizeof(double) + static_cast<size_t>(p.n_blk()) * 12 : 0) +
                        (n_given > 0 ? pg.part_doubles() * sizeof(double) : 0),
                    "recommend_assortment: the users' state, the runs' partial sums and the candidates' rows");
@@ -471,8 +471,8 @@ void recommend_assortment(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *user
   std::vector<int32_t> h_taken(static_cast<size_t>(C), 0);
   for (int g = 0; g < n_given; ++g) {  // a given item is never chosen: its column, where it has one
     if (cand) {
-      const int32_t *at = std::lower_bound(cand, cand + n_cand, given[g]);
-      if (at != cand + n_cand && *at == given[g]) h_taken[static_cast<size_t>(at - cand)] = 1;
+      const int32_t *at = std::lower_bound(cand, cand + C, given[g]);
+      if (at != cand + C && *at == given[g]) h_taken[static_cast<size_t>(at - cand)] = 1;
     } else {
       h_taken[static_cast<size_t>(given[g])] = 1;
     }
@@ -494,7 +494,7 @@ void recommend_assortment(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *user
     part.alloc(p.part_doubles());
     blk_v.alloc(static_cast<size_t>(p.n_blk()));
     blk_i.alloc(static_cast<size_t>(p.n_blk()));
-    if (cand) cat_table(c, cand, C, ct);
+    if (cand) cat_table(c, sub, ct);
   }
   if (n_given > 0) part_g.alloc(pg.part_doubles());
   const double *y = cand && rounds ? ct.y.ptr : rc.y.ptr;

@@ -63,7 +63,7 @@ void recommend_add(mmsbm_hip_ctx *c) {  // the selected slot (the caller holds a
   rc.slots = S + 1;
 }
 
-void recommend_add_items(mmsbm_hip_ctx *c, int32_t n_new, const double *eta, const int64_t *seen_offsets,
+void recommend_add_items(mmsbm_hip_ctx *c, int32_t n_new, const double *eta, const int64_t *seen_off,
                          const int32_t *seen_users) {
   use_device(c);
   if (n_new == 0) return;
@@ -90,7 +90,7 @@ void recommend_add_items(mmsbm_hip_ctx *c, int32_t n_new, const double *eta, con
   HIP_CHECK(hipGetLastError());
   // the seen pairs: user u also leaves out the new items whose list names it.  A user's list stays ascending and
   // distinct: its training items (< I) first, then its new items (>= I), sorted and de-duplicated.
-  const int64_t n_seen = seen_offsets ? seen_offsets[n_new] : 0;  // (checked: below 2^31)
+  const int64_t n_seen = seen_off ? seen_off[n_new] : 0;  // (checked: below 2^31)
   if (n_seen > 0) {
     std::vector<int32_t> old_off = rc.excl ? rc.seen_off_h : std::vector<int32_t>(static_cast<size_t>(U) + 1, 0);
     std::vector<int32_t> old(static_cast<size_t>(old_off[U]));
@@ -98,7 +98,7 @@ void recommend_add_items(mmsbm_hip_ctx *c, int32_t n_new, const double *eta, con
       HIP_CHECK(hipMemcpyAsync(old.data(), rc.seen.ptr, sizeof(int32_t) * old.size(), hipMemcpyDeviceToHost, st));
     // the new pairs (user seen_users[e], item I + j for e in item j's range) grouped by user
     std::vector<int32_t> pit(static_cast<size_t>(n_seen)), nit(static_cast<size_t>(n_seen));
-    for (int32_t j = 0; j < n_new; ++j) std::fill(pit.begin() + seen_offsets[j], pit.begin() + seen_offsets[j + 1], I + j);
+    for (int32_t j = 0; j < n_new; ++j) std::fill(pit.begin() + seen_off[j], pit.begin() + seen_off[j + 1], I + j);
     std::vector<int32_t> noff = group_by_key<int32_t>(seen_users, n_seen, U, [&](int64_t e, int32_t at) { nit[at] = pit[e]; });
     sort_unique_groups(noff, nit);
     HIP_CHECK(hipStreamSynchronize(st));
@@ -128,13 +128,12 @@ void recommend_add_items(mmsbm_hip_ctx *c, int32_t n_new, const double *eta, con
 
 namespace {
 
-// A recommend query: users users[0 .. n_users) (host ids, rows of x: `slots` tables of xs doubles, [row][rank]),
-// scored against the session's items; seen (indexed by those ids): the items left out.
-void rec_run(mmsbm_hip_ctx *c, const double *x, size_t xs, int64_t n_users, const int32_t *users, SeenLists seen, int n,
-             int32_t *items, double *scores, int32_t *counts) {
-  top_n_run(c, c->rc->items, n_users, users, n, "recommend: a batch of users",
+// A recommend query: the users (host ids, rows of x: `slots` tables of xs doubles, [row][rank]) scored against the
+// session's items; seen (indexed by those ids): the items left out.
+void rec_run(mmsbm_hip_ctx *c, const double *x, size_t xs, const UserRows &users, SeenLists seen, int n, const TopNOut &out) {
+  top_n_run(c, c->rc->items, users.n, users.ids, n, "recommend: a batch of users",
             [&](const int32_t *ub, int nb, int64_t, double *sc) { rec_score_batch(c, x, xs, ub, nb, seen, sc); },
-            T_RECOMMEND, items, scores, counts);
+            T_RECOMMEND, out);
 }
 
 // The capped categories of a query on the device (quota.hpp): the plan of serve_plan.hpp, held for as long as the mask
@@ -164,50 +163,37 @@ struct QuotaMask {
   }
 };
 
-// The capped categories of a query (quota.hpp): cat_items[cat_off[g] .. cat_off[g + 1]) (host; catalogue ids, each
-// category strictly ascending, the categories disjoint) with cap caps[g], planned against the candidates (serve_plan.hpp)
-struct QuotaCats {
-  int64_t n_cats = 0;
-  const int64_t *off = nullptr;
-  const int32_t *items = nullptr, *caps = nullptr;
-};
-
-// rec_run within the candidates, without the query's own excluded items and with the capped categories `cats` (null:
-// none).  Without candidates, own lists and a category that can change the answer: rec_run.
-void rec_run_within(mmsbm_hip_ctx *c, const double *x, size_t xs, int64_t n_users, const int32_t *users, SeenLists seen,
-                    const int32_t *cand, int n_cand, const int64_t *xoff, const int32_t *xit, int n, int32_t *items,
-                    double *scores, int32_t *counts, const QuotaCats *cats = nullptr) {
+// rec_run of the query q: within its candidates, without its own excluded items, and with the capped categories
+// `cats` (null: none; quota.hpp), planned against the candidates (serve_plan.hpp).  Without candidates, own lists and a
+// category that can change the answer: rec_run.
+void rec_run_within(mmsbm_hip_ctx *c, const double *x, size_t xs, const UserQuery &q, SeenLists seen, int n,
+                    const TopNOut &out, const Categories *cats = nullptr) {
   QuotaMask mask;
-  if (cats && cats->n_cats > 0 && n_users > 0 && (cand ? n_cand : c->rc->items) > 0) {
-    QuotaPlan plan = plan_quota(cand, n_cand, cats->n_cats, cats->off, cats->items, cats->caps, n);
+  if (cats && cats->n > 0 && q.users.n > 0 && q.cand.columns(c->rc->items) > 0) {
+    QuotaPlan plan = plan_quota(q.cand.items, q.cand.n, cats->n, cats->offsets, cats->items, cats->caps, n);
     if (plan.kept() > 0) {
       require_free_mem(plan.bytes(), "recommend: the capped categories");
       mask.upload(std::move(plan), c->stream);
     }
   }
   const bool masked = mask.plan.kept() > 0;
-  if (!cand && !xoff && !masked) {
-    rec_run(c, x, xs, n_users, users, seen, n, items, scores, counts);
+  if (!q.cand.items && !q.excl.offsets && !masked) {
+    rec_run(c, x, xs, q.users, seen, n, out);
     return;
   }
-  top_n_blank(n_users, n, items, scores, counts);
-  rec_within_run(c, n_users, users, seen, cand, n_cand, xoff, xit, n, rec_tiles(c, x, xs), T_RECOMMEND, items, scores,
-                 counts,
+  top_n_blank(q.users.n, n, out);
+  rec_within_run(c, q, seen, n, rec_tiles(c, x, xs), T_RECOMMEND, out,
                  [&](const WithinPrep &w, const int32_t *, int nb, double *sc) {  // behind the exclusions: the caps
                    if (masked) mask.apply(c->stream, nb, sc, static_cast<size_t>(w.C));
                  },
                  masked);
 }
 
-// ... then rec_run_within
-void rec_theta_run(mmsbm_hip_ctx *c, int64_t n_users, const double *theta, const int64_t *seen_offsets,
-                   const int32_t *seen_items, const int32_t *cand, int n_cand, int n, int32_t *items, double *scores,
-                   int32_t *counts, const QuotaCats *cats = nullptr) {
-  rec_theta_fold(c, n_users, theta, seen_offsets, seen_items,
-                 [&](const double *x, size_t xs, const int32_t *ids, SeenLists seen) {
-                   rec_run_within(c, x, xs, n_users, ids, seen, cand, n_cand, nullptr, nullptr, n, items, scores, counts,
-                                  cats);
-                 });
+// ... of a caller's theta rows, folded first
+void rec_theta_run(mmsbm_hip_ctx *c, const ThetaQuery &t, int n, const TopNOut &out, const Categories *cats = nullptr) {
+  rec_theta_fold(c, t, [&](const double *x, size_t xs, const UserQuery &q, SeenLists seen) {
+    rec_run_within(c, x, xs, q, seen, n, out, cats);
+  });
 }
 
 // ---- category-level recommendation (shelves.hpp) -------------------------------------------------------------------------
@@ -261,31 +247,30 @@ void shelves_blank(int64_t n_users, const ShelfAsk &ask, const ShelfOut &out) {
 
 // The start of both shelves entries, before any launch: every row blanked and the host plan made.  False: no row, no
 // candidate or no category with a column -- every row stays empty and nothing is launched.
-bool shelves_begin(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *cand, int n_cand, int64_t n_cats,
-                   const int64_t *cat_offsets, const int32_t *cat_items, const ShelfAsk &ask, const ShelfOut &out,
-                   ShelfPlan &plan) {
+bool shelves_begin(mmsbm_hip_ctx *c, int64_t n_users, const Subset &cand, const Categories &cats, const ShelfAsk &ask,
+                   const ShelfOut &out, ShelfPlan &plan) {
   shelves_blank(n_users, ask, out);
   c->last_ms[T_RECOMMEND] = 0.f;
-  if (n_users == 0 || n_cats == 0 || (cand ? n_cand : c->rc->items) == 0) return false;
-  plan = plan_shelves(cand, n_cand, n_cats, cat_offsets, cat_items);
+  if (n_users == 0 || cats.n == 0 || cand.columns(c->rc->items) == 0) return false;
+  plan = plan_shelves(cand.items, cand.n, cats.n, cats.offsets, cats.items);
   return plan.kept() > 0;
 }
 
-// A shelves query: rows users[0 .. n_users) (host ids, rows of x) within cand / xoff / xit as rec_within_device's, the
-// categories cats.  The batches are a BatchFrame over the C item columns, the selection a stage over the G value columns:
+// A shelves query: the rows of q (host ids, rows of x) within its subset and own lists as rec_within_device's, the
+// categories of `plan`.  The batches are a BatchFrame over the C item columns, the selection a stage over the G value columns:
 // per batch the score tiles and the exclusions (within_fill: the launches of recommend_query_within), the value kernels,
 // the selection over the value buffer and the chosen shelves' items, all before the next batch overwrites the scores;
 // every row's result stays on the device until the end.  `plan`: shelves_begin's, with at least one category.
-void rec_shelves_run(mmsbm_hip_ctx *c, const double *x, size_t xs, int64_t n_users, const int32_t *users, SeenLists seen,
-                     const int32_t *cand, int n_cand, const int64_t *xoff, const int32_t *xit, ShelfPlan &&plan,
+void rec_shelves_run(mmsbm_hip_ctx *c, const double *x, size_t xs, const UserQuery &q, SeenLists seen, ShelfPlan &&plan,
                      const ShelfAsk &ask, const ShelfOut &out) {
+  const int64_t n_users = q.users.n;
   ShelfCats sh;
   require_free_mem(plan.bytes(), "recommend_shelves: the categories");
   sh.upload(std::move(plan), c->stream);
   hipStream_t st = c->stream;
   const int G = sh.plan.kept(), ns = ask.n_shelves, ps = ask.per_shelf;
   WithinPrep w;
-  within_prepare(c, n_users, cand, n_cand, xoff, xit, w);
+  within_prepare(c, q, w);
   const int C = w.C;
   BatchFrame fr(C, n_users);  // (the item buffer decides the batch: G <= C)
   const SelectPlan sp = select_plan(c, G, fr.bu, ns);
@@ -305,7 +290,7 @@ void rec_shelves_run(mmsbm_hip_ctx *c, const double *x, size_t xs, int64_t n_use
   }
   const auto tiles = rec_tiles(c, x, xs);
   const std::pair<int, size_t> list = select_list(std::max(ps, 1));  // shelf_items_kernel's places and their LDS bytes
-  fr.run(st, users, [&](const int32_t *ub, int nb, int64_t b0, double *sc) {
+  fr.run(st, q.users.ids, [&](const int32_t *ub, int nb, int64_t b0, double *sc) {
     int32_t *obi = oi.ptr + b0 * ns, *obn = on.ptr + b0, *oba = oa.ptr + b0 * ns;
     within_fill(c, w, tiles, seen, ub, nb, b0, sc);
     sh.values(st, nb, sc, static_cast<size_t>(C), ask.depth, ask.min_items, val.ptr, av.ptr);
@@ -341,7 +326,7 @@ void rec_shelves_run(mmsbm_hip_ctx *c, const double *x, size_t xs, int64_t n_use
       if (ps == 0) continue;
       out.item_counts[o] = hin[o];
       for (size_t e = 0; e < static_cast<size_t>(hin[o]); ++e) {
-        out.items[o * ps + e] = item_of(cand, hic[o * ps + e]);
+        out.items[o * ps + e] = item_of(q.cand.items, hic[o * ps + e]);
         out.scores[o * ps + e] = his[o * ps + e];
       }
     }
@@ -350,101 +335,73 @@ void rec_shelves_run(mmsbm_hip_ctx *c, const double *x, size_t xs, int64_t n_use
 
 }  // namespace
 
-void recommend_query(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, int n, int32_t *items, double *scores,
-                     int32_t *counts) {
+void recommend_query(mmsbm_hip_ctx *c, const UserRows &users, int n, const TopNOut &out) {
   use_device(c);
   const RecSession &rc = *c->rc;
-  rec_run(c, rc.x.ptr, rc.x_stride(), n_users, users, rc.seen_lists(), n, items, scores, counts);
+  rec_run(c, rc.x.ptr, rc.x_stride(), users, rc.seen_lists(), n, out);
 }
 
-void recommend_query_theta(mmsbm_hip_ctx *c, int64_t n_users, const double *theta, const int64_t *seen_offsets,
-                           const int32_t *seen_items, int n, int32_t *items, double *scores, int32_t *counts) {
-  use_device(c);
-  rec_theta_run(c, n_users, theta, seen_offsets, seen_items, nullptr, 0, n, items, scores, counts);
-}
-
-void recommend_query_within(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, const int32_t *cand, int n_cand,
-                            const int64_t *excl_offsets, const int32_t *excl_items, int n, int32_t *items,
-                            double *scores, int32_t *counts) {
+void recommend_query_within(mmsbm_hip_ctx *c, const UserQuery &q, int n, const TopNOut &out) {
   use_device(c);
   const RecSession &rc = *c->rc;
-  rec_run_within(c, rc.x.ptr, rc.x_stride(), n_users, users, rc.seen_lists(), cand, n_cand, excl_offsets, excl_items, n,
-                 items, scores, counts);
+  rec_run_within(c, rc.x.ptr, rc.x_stride(), q, rc.seen_lists(), n, out);
 }
 
-void recommend_query_theta_within(mmsbm_hip_ctx *c, int64_t n_users, const double *theta, const int64_t *seen_offsets,
-                                  const int32_t *seen_items, const int32_t *cand, int n_cand, int n, int32_t *items,
-                                  double *scores, int32_t *counts) {
+void recommend_query_theta(mmsbm_hip_ctx *c, const ThetaQuery &q, int n, const TopNOut &out) {
   use_device(c);
-  rec_theta_run(c, n_users, theta, seen_offsets, seen_items, cand, n_cand, n, items, scores, counts);
+  rec_theta_run(c, q, n, out);
 }
 
-void recommend_query_quota(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, const int32_t *cand, int n_cand,
-                           const int64_t *excl_offsets, const int32_t *excl_items, int64_t n_cats,
-                           const int64_t *cat_offsets, const int32_t *cat_items, const int32_t *cat_caps, int n,
-                           int32_t *items, double *scores, int32_t *counts) {
+void recommend_query_quota(mmsbm_hip_ctx *c, const UserQuery &q, const Categories &cats, int n, const TopNOut &out) {
   use_device(c);
   const RecSession &rc = *c->rc;
-  const QuotaCats cats{n_cats, cat_offsets, cat_items, cat_caps};
-  rec_run_within(c, rc.x.ptr, rc.x_stride(), n_users, users, rc.seen_lists(), cand, n_cand, excl_offsets, excl_items, n,
-                 items, scores, counts, &cats);
+  rec_run_within(c, rc.x.ptr, rc.x_stride(), q, rc.seen_lists(), n, out, &cats);
 }
 
-void recommend_query_theta_quota(mmsbm_hip_ctx *c, int64_t n_users, const double *theta, const int64_t *seen_offsets,
-                                 const int32_t *seen_items, const int32_t *cand, int n_cand, int64_t n_cats,
-                                 const int64_t *cat_offsets, const int32_t *cat_items, const int32_t *cat_caps, int n,
-                                 int32_t *items, double *scores, int32_t *counts) {
+void recommend_query_theta_quota(mmsbm_hip_ctx *c, const ThetaQuery &q, const Categories &cats, int n, const TopNOut &out) {
   use_device(c);
-  const QuotaCats cats{n_cats, cat_offsets, cat_items, cat_caps};
-  rec_theta_run(c, n_users, theta, seen_offsets, seen_items, cand, n_cand, n, items, scores, counts, &cats);
+  rec_theta_run(c, q, n, out, &cats);
 }
 
-void recommend_query_shelves(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, const int32_t *cand, int n_cand,
-                             const int64_t *excl_offsets, const int32_t *excl_items, int64_t n_cats,
-                             const int64_t *cat_offsets, const int32_t *cat_items, const ShelfAsk &ask,
+void recommend_query_shelves(mmsbm_hip_ctx *c, const UserQuery &q, const Categories &cats, const ShelfAsk &ask,
                              const ShelfOut &out) {
   use_device(c);
   const RecSession &rc = *c->rc;
   ShelfPlan plan;
-  if (!shelves_begin(c, n_users, cand, n_cand, n_cats, cat_offsets, cat_items, ask, out, plan)) return;
-  rec_shelves_run(c, rc.x.ptr, rc.x_stride(), n_users, users, rc.seen_lists(), cand, n_cand, excl_offsets, excl_items,
-                  std::move(plan), ask, out);
+  if (!shelves_begin(c, q.users.n, q.cand, cats, ask, out, plan)) return;
+  rec_shelves_run(c, rc.x.ptr, rc.x_stride(), q, rc.seen_lists(), std::move(plan), ask, out);
 }
 
-void recommend_query_theta_shelves(mmsbm_hip_ctx *c, int64_t n_users, const double *theta, const int64_t *seen_offsets,
-                                   const int32_t *seen_items, const int32_t *cand, int n_cand, int64_t n_cats,
-                                   const int64_t *cat_offsets, const int32_t *cat_items, const ShelfAsk &ask,
+void recommend_query_theta_shelves(mmsbm_hip_ctx *c, const ThetaQuery &t, const Categories &cats, const ShelfAsk &ask,
                                    const ShelfOut &out) {
   use_device(c);
   ShelfPlan plan;
-  if (!shelves_begin(c, n_users, cand, n_cand, n_cats, cat_offsets, cat_items, ask, out, plan)) return;
-  rec_theta_fold(c, n_users, theta, seen_offsets, seen_items,
-                 [&](const double *x, size_t xs, const int32_t *ids, SeenLists seen) {
-                   rec_shelves_run(c, x, xs, n_users, ids, seen, cand, n_cand, nullptr, nullptr, std::move(plan), ask,
-                                   out);
-                 });
+  if (!shelves_begin(c, t.n_users, t.cand, cats, ask, out, plan)) return;
+  rec_theta_fold(c, t, [&](const double *x, size_t xs, const UserQuery &q, SeenLists seen) {
+    rec_shelves_run(c, x, xs, q, seen, std::move(plan), ask, out);
+  });
 }
 
-void recommend_rank(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, const int64_t *offsets,
-                    const int32_t *cand, int n, int32_t *items, double *scores, int32_t *counts) {
+void recommend_rank(mmsbm_hip_ctx *c, const UserRows &users, const RowCsr &cands, int n, const TopNOut &out) {
+  const int64_t n_users = users.n;
   use_device(c);
   const RecSession &rc = *c->rc;
-  top_n_blank(n_users, n, items, scores, counts);
+  top_n_blank(n_users, n, out);
   c->last_ms[T_RECOMMEND] = 0.f;
   if (n_users == 0) return;
   hipStream_t st = c->stream;
   const auto [cap, lds] = select_list(n);
   const size_t outs = static_cast<size_t>(n_users) * n;
-  require_free_mem(outs * 12 + (2 * static_cast<size_t>(n_users) + 1 + static_cast<size_t>(offsets[n_users])) * 4 +
+  require_free_mem(outs * 12 + (2 * static_cast<size_t>(n_users) + 1 + static_cast<size_t>(cands.offsets[n_users])) * 4 +
                        static_cast<size_t>(n_users) * 4,
                    "recommend_rank: the users' lists and results");
   DevBuf<int32_t> du, oi, on;
   DevBuf<double> os;
   DevCsr lists;  // every request row's candidates
   du.alloc(static_cast<size_t>(n_users));
-  lists.upload(offsets, cand, n_users, st);
+  lists.upload(cands, n_users, st);
   os.alloc(outs); oi.alloc(outs); on.alloc(static_cast<size_t>(n_users));
-  HIP_CHECK(hipMemcpyAsync(du.ptr, users, sizeof(int32_t) * n_users, hipMemcpyHostToDevice, st));
+  HIP_CHECK(hipMemcpyAsync(du.ptr, users.ids, sizeof(int32_t) * n_users, hipMemcpyHostToDevice, st));
   const SeenLists seen = rc.seen_lists();
   EventPair ev;  // device time of the query's kernel (option "recommend_ms")
   ev.start(st);
@@ -453,7 +410,7 @@ void recommend_rank(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, con
          seen.items, n, cap, os.ptr, oi.ptr, on.ptr);
   HIP_CHECK(hipGetLastError());
   ev.stop(st);
-  top_n_copy_out(c, TopNDev{os.ptr, oi.ptr, on.ptr}, ev, n_users, n, T_RECOMMEND, items, scores, counts);
+  top_n_copy_out(c, TopNDev{os.ptr, oi.ptr, on.ptr}, ev, n_users, n, T_RECOMMEND, out);
 }
 
 void recommend_positions(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, const int64_t *offsets,

@@ -43,17 +43,16 @@ struct ExploreStream {
 // recommend_query_within's batches with two stages of its own around the unchanged selection: behind the exclusions the
 // row maxima and the perturbation (the scores move to `raw`, the keys take their place), behind the selection the
 // propensities from `raw` -- per batch, before the next one overwrites it (top_n_device's `each`).
-void recommend_query_explore(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, const int32_t *cand, int n_cand,
-                             const int64_t *xoff, const int32_t *xit, int n, double temperature,
-                             const uint64_t state[4], int32_t *items, double *scores, double *propensity,
-                             int32_t *counts) {
+void recommend_query_explore(mmsbm_hip_ctx *c, const UserQuery &q, int n, double temperature, const uint64_t state[4],
+                             const TopNOut &out, double *propensity) {
   use_device(c);
   const RecSession &rc = *c->rc;
-  top_n_blank(n_users, n, items, scores, counts);
+  const int64_t n_users = q.users.n;
+  top_n_blank(n_users, n, out);
   const size_t outs = static_cast<size_t>(n_users) * n;
   for (size_t e = 0; propensity && e < outs; ++e) propensity[e] = 0.0;
   c->last_ms[T_RECOMMEND] = 0.f;
-  const int C = cand ? n_cand : rc.items;
+  const int C = q.cand.columns(rc.items);
   if (C == 0 || n_users == 0) return;  // (no column to score: every row is empty)
   hipStream_t st = c->stream;
   const int64_t bu = rec_batch_users(C, n_users);  // (the batches top_n_device will form)
@@ -70,10 +69,9 @@ void recommend_query_explore(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *u
   pp.alloc(outs);
   const unsigned spans = static_cast<unsigned>((C + kExpSpan - 1) / kExpSpan);
   rec_within_device(
-      c, n_users, users, rc.seen_lists(), cand, n_cand, xoff, xit, n, 0, rec_tiles(c, rc.x.ptr, rc.x_stride()),
+      c, q, rc.seen_lists(), n, 0, rec_tiles(c, rc.x.ptr, rc.x_stride()),
       [&](const TopNDev &dev, EventPair &ev, const int32_t *, float prep_ms) {  // the scores are `raw`'s, not the keys
-        top_n_copy_out(c, TopNDev{ps.ptr, dev.oi, dev.on}, ev, n_users, n, T_RECOMMEND, items, scores, counts, cand, pp.ptr,
-                       propensity);
+        top_n_copy_out(c, TopNDev{ps.ptr, dev.oi, dev.on}, ev, n_users, n, T_RECOMMEND, out, q.cand.items, pp.ptr, propensity);
         c->last_ms[T_RECOMMEND] += prep_ms;
       },
       [&](const WithinPrep &w, const int32_t *ub, int nb, double *sc) {
@@ -89,22 +87,22 @@ void recommend_query_explore(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *u
 
 // The propensities of caller-given lists: recommend_query_within's score tiles and exclusions per batch (within_fill),
 // the row maxima, then explore_list_kernel over the batch buffer itself -- no noise, no selection.
-void recommend_list_propensity(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, const int32_t *cand, int n_cand,
-                               const int64_t *xoff, const int32_t *xit, double temperature, const int64_t *list_offsets,
-                               const int32_t *list_items, double *scores, double *propensity) {
+void recommend_list_propensity(mmsbm_hip_ctx *c, const UserQuery &q, double temperature, const RowCsr &asked, double *scores,
+                               double *propensity) {
   use_device(c);
   const RecSession &rc = *c->rc;
-  const size_t total = static_cast<size_t>(DevCsr::entries(list_offsets, n_users));  // (checked: below 2^31)
+  const int64_t n_users = q.users.n;
+  const size_t total = static_cast<size_t>(DevCsr::entries(asked, n_users));  // (checked: below 2^31)
   for (size_t e = 0; e < total; ++e) {
     if (scores) scores[e] = -INFINITY;
     propensity[e] = 0.0;
   }
   c->last_ms[T_RECOMMEND] = 0.f;
-  const int C = cand ? n_cand : rc.items;
+  const int C = q.cand.columns(rc.items);
   if (C == 0 || total == 0) return;  // (no candidate anywhere, or nothing asked)
   hipStream_t st = c->stream;
   WithinPrep w;
-  within_prepare(c, n_users, cand, n_cand, xoff, xit, w);
+  within_prepare(c, q, w);
   BatchFrame fr(C, n_users);
   const size_t ld = static_cast<size_t>(C);
   require_free_mem(fr.bytes() + static_cast<size_t>(fr.bu) * 8 + (static_cast<size_t>(n_users) + 1) * 4 + total * 20,
@@ -114,10 +112,10 @@ void recommend_list_propensity(mmsbm_hip_ctx *c, int64_t n_users, const int32_t 
   mx.alloc(static_cast<size_t>(fr.bu));
   os.alloc(total);
   op.alloc(total);
-  lists.upload(list_offsets, list_items, n_users, st);
+  lists.upload(asked, n_users, st);
   const auto tiles = rec_tiles(c, rc.x.ptr, rc.x_stride());
   const int32_t *col_of = w.has_cand ? w.ct.col.ptr : nullptr;
-  fr.run(st, users, [&](const int32_t *ub, int nb, int64_t b0, double *sc) {
+  fr.run(st, q.users.ids, [&](const int32_t *ub, int nb, int64_t b0, double *sc) {
     within_fill(c, w, tiles, rc.seen_lists(), ub, nb, b0, sc);
     LAUNCH(explore_norm_kernel, nb, kBlock, 0, st, sc, ld, C, ub, nullptr, uint64_t(0), uint64_t(0), mx.ptr, nullptr);
     LAUNCH(explore_list_kernel, nb, kRecWave, 0, st, sc, ld, C, mx.ptr, temperature, lists.off.ptr + b0, lists.val.ptr, col_of,
@@ -159,13 +157,11 @@ void explore_noise(mmsbm_hip_ctx *c, const uint64_t state[4], int64_t n_pairs, c
 // ---- ensemble-aware queries (ensemble.hpp) ------------------------------------------------------------------------------
 // rec_run_within with the score tile replaced by the aggregate over the restarts (rec_within_run: the same candidate
 // table, the same exclusions, the same batches and selection)
-void recommend_query_ensemble(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, int mode, double risk,
-                              const int32_t *cand, int n_cand, const int64_t *xoff, const int32_t *xit, int n,
-                              int32_t *items, double *scores, int32_t *counts) {
+void recommend_query_ensemble(mmsbm_hip_ctx *c, const UserQuery &q, int mode, double risk, int n, const TopNOut &out) {
   use_device(c);
   const RecSession &rc = *c->rc;
-  top_n_blank(n_users, n, items, scores, counts);
-  rec_within_run(c, n_users, users, rc.seen_lists(), cand, n_cand, xoff, xit, n,
+  top_n_blank(q.users.n, n, out);
+  rec_within_run(c, q, rc.seen_lists(), n,
                  [&](const double *y, size_t ys, int C, const int32_t *ub, int nb, double *sc) {
                    auto tile = [&](auto kernel) {
                      LAUNCH(kernel, tile_grid(C, nb, kEnsTile), kBlock, 0, c->stream, rc.x.ptr, rc.x_stride(), y, ys, ub, nb, C, rc.rank, rc.slots, risk, sc,
@@ -175,7 +171,7 @@ void recommend_query_ensemble(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *
                    else if (mode == MMSBM_HIP_ENSEMBLE_MAX) tile(ens_tile_kernel<kEnsMax>);
                    else tile(ens_tile_kernel<kEnsLcb>);
                  },
-                 T_ENSEMBLE, items, scores, counts);
+                 T_ENSEMBLE, out);
 }
 
 void recommend_pair_spread(mmsbm_hip_ctx *c, int64_t n_pairs, const int32_t *users, const int32_t *items, double *stats,
@@ -217,23 +213,23 @@ void recommend_pair_spread(mmsbm_hip_ctx *c, int64_t n_pairs, const int32_t *use
 
 // ---- group queries (group.hpp) ------------------------------------------------------------------------------------------
 // plan (plan_groups: the member blocks, the batches' runs and fragments), memory check, uploads, top_n_run, scatter
-void recommend_query_groups(mmsbm_hip_ctx *c, int64_t n_groups, const int64_t *offsets, const int32_t *members, int mode,
-                            double bar, const int32_t *cand, int n_cand, int n, int32_t *items, double *scores,
-                            int32_t *counts) {
+void recommend_query_groups(mmsbm_hip_ctx *c, int64_t n_groups, const RowCsr &members, int mode, double bar,
+                            const Subset &sub, int n, const TopNOut &out) {
   use_device(c);
   const RecSession &rc = *c->rc;
-  top_n_blank(n_groups, n, items, scores, counts);
+  const int32_t *cand = sub.items;  // (null: the columns are the items)
+  top_n_blank(n_groups, n, out);
   c->last_ms[T_GROUP] = 0.f;
   const int NI = rc.items, rank = rc.rank, S = rc.slots;
-  const int C = cand ? n_cand : NI;
+  const int C = sub.columns(NI);
   const bool tiles = mode != MMSBM_HIP_GROUP_MEAN;
-  const GroupPlan p = plan_groups(offsets, members, n_groups, C, c->n_cus, c->grp_run, tiles);
+  const GroupPlan p = plan_groups(members.offsets, members.values, n_groups, C, c->n_cus, c->grp_run, tiles);
   const int64_t G = p.groups();
   if (G == 0 || C == 0) return;  // (no row or no column to score: every row is empty)
   if (p.too_large())
     throw ApiError(MMSBM_E_TOOLARGE, "recommend_query_groups: " + std::to_string(p.n_blocks) + " blocks of member rows in one query");
   const size_t ycs = static_cast<size_t>(C) * rank, bs = static_cast<size_t>(G) * rank;
-  require_free_mem(CatTable::bytes(rc, cand, C) +
+  require_free_mem(CatTable::bytes(rc, sub) +
                        (p.rows.size() + 3 * p.info.size() + p.run_off.size() + 2 * p.cut_off.size() + 2 * static_cast<size_t>(G) + 1) * 4 +
                        (tiles ? static_cast<size_t>(p.most_frag) * C : S * bs) * sizeof(double),
                    "recommend_query_groups: the member rows, the groups' lists and the candidates' rows");
@@ -257,7 +253,7 @@ void recommend_query_groups(mmsbm_hip_ctx *c, int64_t n_groups, const int64_t *o
     d_size.upload(p.gsize, st);
     xbar.alloc(S * bs);
   }
-  if (cand) cat_table(c, cand, C, ct);
+  if (cand) cat_table(c, sub, ct);
   const double *y = cand ? ct.y.ptr : rc.y.ptr;
   const size_t ys = cand ? ycs : static_cast<size_t>(NI) * rank, xs = rc.x_stride();
   const SeenLists seen = rc.seen_lists();
@@ -296,15 +292,15 @@ void recommend_query_groups(mmsbm_hip_ctx *c, int64_t n_groups, const int64_t *o
                        d_rows.ptr, d_info.ptr, d_grp.ptr, blk0, g0, seen.off, seen.items, col_of, sc, static_cast<size_t>(C));
               }
             },
-            T_GROUP, ti.data(), ts.data(), tc.data());
+            T_GROUP, TopNOut{ti.data(), ts.data(), tc.data()});
   c->last_ms[T_GROUP] += ct.ms;
   for (int64_t r = 0; r < G; ++r) {  // the rows to their places in the request, columns -> item ids
     const size_t o = static_cast<size_t>(p.at[r]) * n, t = static_cast<size_t>(r) * n;
     const int cnt = tc[static_cast<size_t>(r)];
-    if (counts) counts[p.at[r]] = cnt;
+    if (out.counts) out.counts[p.at[r]] = cnt;
     for (int k = 0; k < cnt; ++k) {
-      items[o + k] = item_of(cand, ti[t + k]);
-      if (scores) scores[o + k] = ts[t + k];
+      out.items[o + k] = item_of(cand, ti[t + k]);
+      if (out.scores) out.scores[o + k] = ts[t + k];
     }
   }
 }
@@ -342,16 +338,16 @@ void similar_pairs(mmsbm_hip_ctx *c, int64_t n_pairs, const int32_t *a, const in
   c->last_ms[T_DIVERSE] = ms;
 }
 
-void recommend_diverse(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, const int32_t *cand, int n_cand,
-                       const int64_t *xoff, const int32_t *xit, int n, int pool, double trade_off, int32_t *items,
-                       double *scores, double *distances, int32_t *counts) {
+void recommend_diverse(mmsbm_hip_ctx *c, const UserQuery &q, int n, int pool, double trade_off, const TopNOut &out,
+                       double *distances) {
   use_device(c);
   const RecSession &rc = *c->rc;
   const SimSession &sm = *c->sm;
-  top_n_blank(n_users, n, items, scores, counts);
+  const int64_t n_users = q.users.n;
+  top_n_blank(n_users, n, out);
   for (size_t e = 0; distances && e < static_cast<size_t>(n_users) * n; ++e) distances[e] = INFINITY;
   c->last_ms[T_DIVERSE] = 0.f;
-  if ((cand ? n_cand : rc.items) == 0 || n_users == 0) return;  // (no column to score: every row is empty)
+  if (q.cand.columns(rc.items) == 0 || n_users == 0) return;  // (no column to score: every row is empty)
   hipStream_t st = c->stream;
   const double denom = static_cast<double>(sm.slots) * static_cast<double>(sm.others);
   const size_t lds = (static_cast<size_t>(pool) * 21 + 7) / 8 * 8;  // score, m, id, picked flag per place
@@ -360,17 +356,12 @@ void recommend_diverse(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, 
   const int64_t rows_per = div_rows_per_call(c->div_rows, n_users, free_b, div_row_bytes(pool, n));
   const SeenLists seen = rc.seen_lists();
   float ms = 0.f;  // device time of the query's kernels (option "diverse_ms")
-  std::vector<int64_t> sub;
+  std::vector<int64_t> rebased;  // (the rows' own lists, offsets from the first of them)
   for (int64_t b0 = 0; b0 < n_users; b0 += rows_per) {
     const int64_t nb = std::min(rows_per, n_users - b0);
-    if (xoff) {  // the rows' own lists, offsets from the first of them
-      sub.resize(static_cast<size_t>(nb) + 1);
-      for (int64_t k = 0; k <= nb; ++k) sub[static_cast<size_t>(k)] = xoff[b0 + k] - xoff[b0];
-    }
     const size_t outs = static_cast<size_t>(nb) * n;
     rec_within_device(
-        c, nb, users + b0, seen, cand, n_cand, xoff ? sub.data() : nullptr, xoff ? xit + xoff[b0] : nullptr, pool,
-        outs * 20 + static_cast<size_t>(nb) * 4, rec_tiles(c, rc.x.ptr, rc.x_stride()),
+        c, q.rows(b0, nb, rebased), seen, pool, outs * 20 + static_cast<size_t>(nb) * 4, rec_tiles(c, rc.x.ptr, rc.x_stride()),
         [&](const TopNDev &dev, EventPair &ev, const int32_t *dcand, float prep_ms) {
           DevBuf<int32_t> ri, rn;
           DevBuf<double> rs, rd;
@@ -379,16 +370,16 @@ void recommend_diverse(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, 
           ev2.start(st);
           if (dcand)  // the pool as columns of the compact table -> item ids
             LAUNCH(div_ids_kernel, static_cast<unsigned>((static_cast<size_t>(nb) * pool + kBlock - 1) / kBlock), kBlock, 0,
-                   st, dcand, n_cand, dev.on, static_cast<int>(nb), pool, dev.oi);
+                   st, dcand, q.cand.n, dev.on, static_cast<int>(nb), pool, dev.oi);
           LAUNCH(div_greedy_kernel, static_cast<unsigned>(nb), kDivWave, lds, st, sm.q.ptr,
                  static_cast<size_t>(sm.rows) * sm.width, sm.mf.ptr, sm.width, sm.slots, sm.rows, denom, dev.os, dev.oi, dev.on, pool, n, trade_off, ri.ptr, rs.ptr, rd.ptr, rn.ptr);
           HIP_CHECK(hipGetLastError());
           ev2.stop(st);
           const size_t o = static_cast<size_t>(b0) * n;  // (the kernel wrote the padding too: straight into the caller's rows)
-          HIP_CHECK(hipMemcpyAsync(items + o, ri.ptr, sizeof(int32_t) * outs, hipMemcpyDeviceToHost, st));
-          if (scores) HIP_CHECK(hipMemcpyAsync(scores + o, rs.ptr, sizeof(double) * outs, hipMemcpyDeviceToHost, st));
+          HIP_CHECK(hipMemcpyAsync(out.items + o, ri.ptr, sizeof(int32_t) * outs, hipMemcpyDeviceToHost, st));
+          if (out.scores) HIP_CHECK(hipMemcpyAsync(out.scores + o, rs.ptr, sizeof(double) * outs, hipMemcpyDeviceToHost, st));
           if (distances) HIP_CHECK(hipMemcpyAsync(distances + o, rd.ptr, sizeof(double) * outs, hipMemcpyDeviceToHost, st));
-          if (counts) HIP_CHECK(hipMemcpyAsync(counts + b0, rn.ptr, sizeof(int32_t) * nb, hipMemcpyDeviceToHost, st));
+          if (out.counts) HIP_CHECK(hipMemcpyAsync(out.counts + b0, rn.ptr, sizeof(int32_t) * nb, hipMemcpyDeviceToHost, st));
           HIP_CHECK(hipStreamSynchronize(st));
           ms += ev.ms() + ev2.ms() + prep_ms;
         });

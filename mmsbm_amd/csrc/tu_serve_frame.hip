@@ -51,22 +51,20 @@ std::vector<int32_t> upload_train_lists(mmsbm_hip_ctx *c, DevBuf<int32_t> &d_off
   return off;
 }
 
-void DevCsr::upload(const int64_t *offsets, const int32_t *values, int64_t n_rows, hipStream_t st) {
-  const int64_t n = entries(offsets, n_rows);
-  off_h.assign(offsets, offsets + n_rows + 1);
+void DevCsr::upload(const RowCsr &lists, int64_t n_rows, hipStream_t st) {
+  const int64_t n = entries(lists, n_rows);
+  off_h.assign(lists.offsets, lists.offsets + n_rows + 1);
   off.upload(off_h, st);
   val.alloc(static_cast<size_t>(n));
-  if (n > 0) HIP_CHECK(hipMemcpyAsync(val.ptr, values, sizeof(int32_t) * n, hipMemcpyHostToDevice, st));
+  if (n > 0) HIP_CHECK(hipMemcpyAsync(val.ptr, lists.values, sizeof(int32_t) * n, hipMemcpyHostToDevice, st));
 }
 
-CallerRows::CallerRows(mmsbm_hip_ctx *c, int S, int64_t n_users, const double *theta, const int64_t *seen_offsets,
-                       const int32_t *seen_items)
-    : ids(static_cast<size_t>(n_users)) {
-  const size_t tk = static_cast<size_t>(n_users) * c->ext_k;
+CallerRows::CallerRows(mmsbm_hip_ctx *c, int S, const ThetaQuery &q) : ids(static_cast<size_t>(q.n_users)), cand(q.cand) {
+  const size_t tk = static_cast<size_t>(q.n_users) * c->ext_k;
   th.alloc(S * tk);
-  if (S * tk > 0) HIP_CHECK(hipMemcpyAsync(th.ptr, theta, sizeof(double) * S * tk, hipMemcpyHostToDevice, c->stream));
-  for (int64_t b = 0; b < n_users; ++b) ids[static_cast<size_t>(b)] = static_cast<int32_t>(b);
-  if (seen_offsets && n_users > 0) seen.upload(seen_offsets, seen_items, n_users, c->stream);
+  if (S * tk > 0) HIP_CHECK(hipMemcpyAsync(th.ptr, q.theta, sizeof(double) * S * tk, hipMemcpyHostToDevice, c->stream));
+  for (int64_t b = 0; b < q.n_users; ++b) ids[static_cast<size_t>(b)] = static_cast<int32_t>(b);
+  if (q.seen.offsets && q.n_users > 0) seen.upload(q.seen, q.n_users, c->stream);
 }
 
 void fold_weights(hipStream_t st, const double *p, const double *w, double *out, int K, int L, int R, size_t rs, int ks, int ls) {
@@ -120,12 +118,12 @@ void own_exclude_batch(hipStream_t st, const DevCsr &own, int64_t b0, int nb, co
   LAUNCH(cat_exclude_kernel, nb, kBlock, 0, st, nullptr, static_cast<int>(b0), own.off.ptr, own.val.ptr, col_of, sc, ld);
 }
 
-void top_n_blank(int64_t n_rows, int n, int32_t *items, double *scores, int32_t *counts) {
+void top_n_blank(int64_t n_rows, int n, const TopNOut &out) {
   for (int64_t b = 0; b < n_rows; ++b) {
-    if (counts) counts[b] = 0;
+    if (out.counts) out.counts[b] = 0;
     for (int k = 0; k < n; ++k) {
-      items[static_cast<size_t>(b) * n + k] = -1;
-      if (scores) scores[static_cast<size_t>(b) * n + k] = -INFINITY;
+      out.items[static_cast<size_t>(b) * n + k] = -1;
+      if (out.scores) out.scores[static_cast<size_t>(b) * n + k] = -INFINITY;
     }
   }
 }
@@ -146,8 +144,7 @@ void SelectStage::run(hipStream_t st, const SelectPlan &p, const double *sc, int
 }
 
 void top_n_copy_out(mmsbm_hip_ctx *c, const TopNDev &dev, EventPair &ev, int64_t n_users, int n, TimedCall timed,
-                    int32_t *items, double *scores, int32_t *counts, const int32_t *cand, const double *dev_second,
-                    double *second) {
+                    const TopNOut &out, const int32_t *cand, const double *dev_second, double *second) {
   hipStream_t st = c->stream;
   const size_t outs = static_cast<size_t>(n_users) * n;
   std::vector<double> hs(outs), h2(dev_second ? outs : 0);
@@ -161,24 +158,24 @@ void top_n_copy_out(mmsbm_hip_ctx *c, const TopNDev &dev, EventPair &ev, int64_t
   for (int64_t b = 0; b < n_users; ++b) {
     const size_t o = static_cast<size_t>(b) * n;
     const int cnt = hn[static_cast<size_t>(b)];
-    if (counts) counts[b] = cnt;
+    if (out.counts) out.counts[b] = cnt;
     for (int k = 0; k < cnt; ++k) {
-      items[o + k] = item_of(cand, hi[o + k]);
-      if (scores) scores[o + k] = hs[o + k];
+      out.items[o + k] = item_of(cand, hi[o + k]);
+      if (out.scores) out.scores[o + k] = hs[o + k];
       if (dev_second && second) second[o + k] = h2[o + k];
     }
   }
 }
 
-void cat_table(mmsbm_hip_ctx *c, const int32_t *cand, int C, CatTable &t) {
+void cat_table(mmsbm_hip_ctx *c, const Subset &cand, CatTable &t) {
   const RecSession &rc = *c->rc;
-  const int NI = rc.items, rank = rc.rank, S = rc.slots;
+  const int NI = rc.items, rank = rc.rank, S = rc.slots, C = cand.n;
   const size_t ycs = static_cast<size_t>(C) * rank;
   hipStream_t st = c->stream;
   t.cand.alloc(static_cast<size_t>(C));
   t.col.alloc(static_cast<size_t>(NI));
   t.y.alloc(S * ycs);
-  HIP_CHECK(hipMemcpyAsync(t.cand.ptr, cand, sizeof(int32_t) * C, hipMemcpyHostToDevice, st));
+  HIP_CHECK(hipMemcpyAsync(t.cand.ptr, cand.items, sizeof(int32_t) * C, hipMemcpyHostToDevice, st));
   EventPair ev;
   ev.start(st);
   LAUNCH(cat_gather_kernel, static_cast<unsigned>((S * ycs + kBlock - 1) / kBlock), kBlock, 0, st, rc.y.ptr,
@@ -190,21 +187,21 @@ void cat_table(mmsbm_hip_ctx *c, const int32_t *cand, int C, CatTable &t) {
   t.ms = ev.ms();
 }
 
-void within_prepare(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *cand, int n_cand, const int64_t *xoff,
-                    const int32_t *xit, WithinPrep &w) {
+void within_prepare(mmsbm_hip_ctx *c, const UserQuery &q, WithinPrep &w) {
   const RecSession &rc = *c->rc;
   const int NI = rc.items, rank = rc.rank;
-  w.C = cand ? n_cand : NI;
-  w.has_cand = cand != nullptr;
-  w.has_own = xoff != nullptr;
+  const int64_t n_users = q.users.n;
+  w.C = q.cand.columns(NI);
+  w.has_cand = q.cand.items != nullptr;
+  w.has_own = q.excl.offsets != nullptr;
   const size_t ycs = static_cast<size_t>(w.C) * rank;
-  if (cand || xoff)
-    require_free_mem(CatTable::bytes(rc, cand, w.C) + (static_cast<size_t>(n_users) + 1 + DevCsr::entries(xoff, n_users)) * 4,
+  if (w.has_cand || w.has_own)
+    require_free_mem(CatTable::bytes(rc, q.cand) + (static_cast<size_t>(n_users) + 1 + DevCsr::entries(q.excl, n_users)) * 4,
                      "recommend: the candidates' rows and the query's excluded items");
-  if (xoff) w.own.upload(xoff, xit, n_users, c->stream);
-  if (cand) cat_table(c, cand, w.C, w.ct);
-  w.y = cand ? w.ct.y.ptr : rc.y.ptr;
-  w.ys = cand ? ycs : static_cast<size_t>(NI) * rank;
+  if (w.has_own) w.own.upload(q.excl, n_users, c->stream);
+  if (w.has_cand) cat_table(c, q.cand, w.ct);
+  w.y = w.has_cand ? w.ct.y.ptr : rc.y.ptr;
+  w.ys = w.has_cand ? ycs : static_cast<size_t>(NI) * rank;
 }
 
 }  // namespace mmsbm_hip_impl

@@ -48,8 +48,7 @@ void similar_add(mmsbm_hip_ctx *c) {  // the selected slot (the caller holds a O
   sm.slots = S + 1;
 }
 
-void similar_query(mmsbm_hip_ctx *c, int64_t n_rows, const int32_t *ids, int n, int32_t *out_ids, double *distance,
-                   int32_t *counts) {
+void similar_query(mmsbm_hip_ctx *c, int64_t n_rows, const int32_t *ids, int n, const TopNOut &out) {
   use_device(c);
   const SimSession &sm = *c->sm;
   const int rows = sm.rows, W = sm.width, S = sm.slots;
@@ -60,9 +59,9 @@ void similar_query(mmsbm_hip_ctx *c, int64_t n_rows, const int32_t *ids, int n, 
               LAUNCH(sim_dist_kernel, tile_grid(rows, nb, kSimTile), kBlock, 0, st, sm.q.ptr, static_cast<size_t>(rows) * W, sm.mf.ptr, ub, nb, rows,
                      W, S, denom, sc, static_cast<size_t>(rows));
             },
-            T_SIMILAR, out_ids, distance, counts);
+            T_SIMILAR, out);
   // the buffer held -D (the selection's order): the distances, +inf behind the last one (a zero leaves as +0.0)
-  for (size_t e = 0; distance && e < static_cast<size_t>(n_rows) * n; ++e) distance[e] = -distance[e];
+  for (size_t e = 0; out.scores && e < static_cast<size_t>(n_rows) * n; ++e) out.scores[e] = -out.scores[e];
 }
 
 // ---- the most informative items of a user (inform.hpp) ----------------------------------------------------------------
@@ -101,71 +100,65 @@ void inform_add(mmsbm_hip_ctx *c) {  // the selected slot (the caller holds a On
 
 namespace {
 
-// An inform query: request rows users[0 .. n_users) (host ids, rows of th: `slots` tables of ts doubles, [row][K])
-// against every item.  seen (indexed by those ids): the items left out; cand[0 .. n_cand) (host; ascending, distinct
-// item ids; null: every item): the candidate mask; xoff / xit (host, by request row, any order, repeats allowed; null:
-// none): the query's own excluded items.
-void inf_run(mmsbm_hip_ctx *c, const double *th, size_t ts, int64_t n_users, const int32_t *users, SeenLists seen,
-             const int32_t *cand, int n_cand, const int64_t *xoff, const int32_t *xit, int n, int32_t *items,
-             double *gains, int32_t *counts) {
+// An inform query: the request rows of q (host ids, rows of th: `slots` tables of ts doubles, [row][K]) against every
+// item.  seen (indexed by those ids): the items left out; q's subset: the candidate mask; its own lists (by request row,
+// any order, repeats allowed): the query's own excluded items.  out.scores: the gains.
+void inf_run(mmsbm_hip_ctx *c, const double *th, size_t ts, const UserQuery &q, SeenLists seen, int n, const TopNOut &out) {
   const InfSession &inf = *c->inf;
   const int I = c->ext_items, K = c->ext_k, R = c->n_ratings, S = inf.slots;
+  const int64_t n_users = q.users.n;
+  const int32_t *cand = q.cand.items;
+  const bool own_lists = q.excl.offsets != nullptr;
   c->last_ms[T_INFORM] = 0.f;
-  if (I == 0 || n_users == 0 || (cand && n_cand == 0)) {  // (no column to score: every row is empty)
-    top_n_blank(n_users, n, items, gains, counts);
+  if (I == 0 || n_users == 0 || q.cand.columns(I) == 0) {  // (no column to score: every row is empty)
+    top_n_blank(n_users, n, out);
     return;
   }
   hipStream_t st = c->stream;
   require_free_mem((cand ? static_cast<size_t>(I) : 0) +
-                       (xoff ? (static_cast<size_t>(n_users) + 1 + DevCsr::entries(xoff, n_users)) * 4 : 0),
+                       (own_lists ? (static_cast<size_t>(n_users) + 1 + DevCsr::entries(q.excl, n_users)) * 4 : 0),
                    "inform: the candidate mask and the query's excluded items");
   DevBuf<uint8_t> dmask;
   DevCsr own;
   if (cand) {
     std::vector<uint8_t> hm(static_cast<size_t>(I), 0);
-    for (int e = 0; e < n_cand; ++e) hm[static_cast<size_t>(cand[e])] = 1;
+    for (int e = 0; e < q.cand.n; ++e) hm[static_cast<size_t>(cand[e])] = 1;
     dmask.upload(hm, st);
     HIP_CHECK(hipStreamSynchronize(st));  // (`hm` is a local)
   }
-  if (xoff) own.upload(xoff, xit, n_users, st);
+  if (own_lists) own.upload(q.excl, n_users, st);
   const size_t hs = static_cast<size_t>(I) * K, qs = hs * R;
-  top_n_run(c, I, n_users, users, n, "inform: a batch of users",
+  top_n_run(c, I, n_users, q.users.ids, n, "inform: a batch of users",
             [&](const int32_t *ub, int nb, int64_t b0, double *sc) {
               LAUNCH(inf_score_kernel, tile_grid(I, nb, kInfTile), kBlock, 0, st, th, ts, inf.q.ptr, qs, inf.h.ptr, hs, ub, nb, I,
                      K, R, S, dmask.ptr, sc, static_cast<size_t>(I));
               exclude_seen(st, ub, nb, seen, sc, static_cast<size_t>(I));
-              if (xoff) own_exclude_batch(st, own, b0, nb, nullptr, sc, static_cast<size_t>(I));
+              if (own_lists) own_exclude_batch(st, own, b0, nb, nullptr, sc, static_cast<size_t>(I));
             },
-            T_INFORM, items, gains, counts);
+            T_INFORM, out);
 }
 
 }  // namespace
 
-void inform_query(mmsbm_hip_ctx *c, int64_t n_users, const int32_t *users, const int32_t *cand, int n_cand,
-                  const int64_t *excl_offsets, const int32_t *excl_items, bool exclude_train, int n, int32_t *items,
-                  double *gains, int32_t *counts) {
+void inform_query(mmsbm_hip_ctx *c, const UserQuery &q, bool exclude_train, int n, const TopNOut &out) {
   use_device(c);
   InfSession &inf = *c->inf;
   if (exclude_train && !inf.seen_built) {  // every user's training items, built by the first query that leaves them out
     upload_train_lists(c, inf.seen_off, inf.seen, "inform: the users' training items");
     inf.seen_built = true;
   }
-  inf_run(c, inf.th.ptr, static_cast<size_t>(c->ext_users) * c->ext_k, n_users, users,
-          SeenLists{exclude_train ? inf.seen_off.ptr : nullptr, inf.seen.ptr}, cand, n_cand, excl_offsets, excl_items, n,
-          items, gains, counts);
+  inf_run(c, inf.th.ptr, static_cast<size_t>(c->ext_users) * c->ext_k, q,
+          SeenLists{exclude_train ? inf.seen_off.ptr : nullptr, inf.seen.ptr}, n, out);
 }
 
-void inform_query_theta(mmsbm_hip_ctx *c, int64_t n_users, const double *theta, const int64_t *seen_offsets,
-                        const int32_t *seen_items, const int32_t *cand, int n_cand, int n, int32_t *items,
-                        double *gains, int32_t *counts) {
+void inform_query_theta(mmsbm_hip_ctx *c, const ThetaQuery &q, int n, const TopNOut &out) {
   use_device(c);
   const int S = c->inf->slots;
-  const size_t tk = static_cast<size_t>(n_users) * c->ext_k;
-  require_free_mem(S * tk * sizeof(double) + (static_cast<size_t>(n_users) + 1 + DevCsr::entries(seen_offsets, n_users)) * 4,
+  const size_t tk = static_cast<size_t>(q.n_users) * c->ext_k;
+  require_free_mem(S * tk * sizeof(double) + (static_cast<size_t>(q.n_users) + 1 + DevCsr::entries(q.seen, q.n_users)) * 4,
                    "inform: the caller's theta rows");
-  CallerRows rows(c, S, n_users, theta, seen_offsets, seen_items);
-  inf_run(c, rows.th.ptr, tk, n_users, rows.ids.data(), rows.seen.lists(), cand, n_cand, nullptr, nullptr, n, items, gains,
-          counts);
+  CallerRows rows(c, S, q);
+  inf_run(c, rows.th.ptr, tk, rows.users(), rows.seen.lists(), n, out);
   HIP_CHECK(hipStreamSynchronize(c->stream));  // (the rows and the lists are locals)
 }
 

@@ -88,7 +88,7 @@ static void run(const Entry &e, const Request &r) {
   const ShelfOut out{r.has_shelf_cats ? out_i : nullptr, out_d, out_i, out_i, r.has_shelf_items ? out_i : nullptr, out_d, out_i};
   if (e.shelves) require_shelf_ask(r.n_users, r.n_cats, r.ask, out, e.who);
   if (e.explore) require_temperature(r.temperature, kWMin, kWMax, e.who);
-  const Subset cand{r.n_cand, ptr(r.cand, r.has_cand)};
+  const int32_t n_cand = e.subset ? r.n_cand : 0, *cand = e.subset ? ptr(r.cand, r.has_cand) : nullptr;
   if (e.user_prefix) {
     if (r.n_users > 0 && (!r.has_users || (e.vals && !r.has_off))) null_argument();
     if (e.vals) {
@@ -98,18 +98,19 @@ static void run(const Entry &e, const Request &r) {
         require_candidates(r.val.data() + r.off[b], r.off[b], r.off[b + 1] - r.off[b], e.top, e.who);
       return;
     }
-    const UserQuery q{{r.n_users, ptr(r.users, r.has_users)}, e.subset ? cand : Subset{0, nullptr},
-                      e.lists ? excluded_lists(ptr(r.off, r.has_off), ptr(r.val, r.has_val)) : excluded_lists(nullptr, nullptr)};
+    const UserQuery q = user_query(r.n_users, ptr(r.users, r.has_users), n_cand, cand, ptr(r.off, e.lists && r.has_off),
+                                   ptr(r.val, e.lists && r.has_val));
     q.check(kUsers, e.user_prefix, e.top, e.who);
   } else {
     if (r.n_users > 0 && !r.has_theta) null_argument();
     if (std::string(e.seen_who) == "inform") require_theta_entries(r.theta.data(), r.has_theta ? size_t(r.n_users) * kK : 0, "inform");
-    const ThetaQuery q{r.n_users, e.subset ? cand : Subset{0, nullptr}, seen_lists(ptr(r.off, r.has_off), ptr(r.val, r.has_val))};
+    const ThetaQuery q = theta_query(r.n_users, r.has_theta ? r.theta.data() : nullptr, ptr(r.off, r.has_off),
+                                     ptr(r.val, r.has_val), n_cand, cand);
     q.check(e.top, e.who, e.seen_who);
   }
   if (e.quota || e.shelves)
-    require_categories(r.n_cats, ptr(r.cat_off, r.has_cat_off), ptr(r.cat_items, r.has_cat_items), ptr(r.caps, r.has_caps && e.quota),
-                       e.top, e.who, e.quota);
+    Categories{r.n_cats, ptr(r.cat_off, r.has_cat_off), ptr(r.cat_items, r.has_cat_items), ptr(r.caps, r.has_caps && e.quota)}
+        .check(e.top, e.who, e.quota);
 }
 
 struct Named {
@@ -302,9 +303,9 @@ int main() {
     const char *who = "recommend_list_propensity";
     auto lists = [&](const char *label, const I64 &off, const I32 &items) {
       note(std::string(who) + ": " + label, [&] {
-        const RowCsr l{off.data(), items.data(), "list_offsets", "user", "listed items", "listed item"};
+        const RowCsr l = listed_items(off.data(), items.data());
         l.check(2, kItems, who);
-        require_lists(off.data(), items.data(), 2, who);
+        require_lists(l, 2, who);
       });
     };
     lists("an item twice in a list", {0, 2, 2}, {3, 3});
@@ -354,9 +355,13 @@ int main() {
   legal("n_cand = 0, n_cand = top", [] {
     I32 all(kItems);
     for (int i = 0; i < kItems; ++i) all[i] = i;
-    require_subset(all.data(), 0, kItems, "x");
-    require_subset(all.data(), kItems, kItems, "x");
-    require_subset(nullptr, -5, kItems, "x");
+    Subset{0, all.data()}.check(kItems, "x");
+    Subset{kItems, all.data()}.check(kItems, "x");
+    Subset{-5, nullptr}.check(kItems, "x");
+    // the columns of a null subset (the catalogue, whatever n says), an empty one and a full one
+    if (Subset{-5, nullptr}.columns(kItems) != kItems || Subset{0, nullptr}.columns(0) != 0) throw std::runtime_error("null subset");
+    if (Subset{0, all.data()}.columns(kItems) != 0) throw std::runtime_error("empty subset");
+    if (Subset{kItems, all.data()}.columns(kItems) != kItems) throw std::runtime_error("full subset");
   });
   legal("ids at both ends, no ids", [] {
     const I32 ends{0, kUsers - 1};
@@ -368,9 +373,9 @@ int main() {
     I32 items(kItems), caps(kItems, 0);
     for (int i = 0; i <= kItems; ++i) off[i] = i;
     for (int i = 0; i < kItems; ++i) items[i] = i;
-    require_categories(kItems, off.data(), items.data(), caps.data(), kItems, "x");
-    require_categories(kItems, off.data(), items.data(), nullptr, kItems, "x", false);
-    require_categories(0, nullptr, nullptr, nullptr, kItems, "x");
+    Categories{kItems, off.data(), items.data(), caps.data()}.check(kItems, "x");
+    Categories{kItems, off.data(), items.data(), nullptr}.check(kItems, "x", false);
+    Categories{0, nullptr, nullptr, nullptr}.check(kItems, "x");
   });
   legal("a temperature at the floor; equal weights", [] {
     require_temperature(0.00286, kWMin, kWMax, "x");
@@ -387,7 +392,7 @@ int main() {
     I32 items(1024);
     for (int i = 0; i < 1024; ++i) items[i] = i;
     const I64 off{0, 1024};
-    require_lists(off.data(), items.data(), 1, "x");
+    require_lists(listed_items(off.data(), items.data()), 1, "x");
     I32 members(2 * kUsers);
     for (int i = 0; i < 2 * kUsers; ++i) members[i] = i % kUsers;
     const I64 goff{0, kUsers, 2 * kUsers};
@@ -402,6 +407,72 @@ int main() {
     if (asked_once_user_set(rev.data(), kUsers, kUsers, "x", all) != rev.data()) throw std::runtime_error("in order");
     if (asked_once_user_set(nullptr, kUsers, kUsers, "x", all) != all.data() || all != ids) throw std::runtime_error("all");
     if (sorted_user_set(rev.data(), 0, kUsers, "x").size() != 0) throw std::runtime_error("none");
+  });
+  // ---- the request values: the normalising constructors, the rows of a query --------------------------------------------------
+  legal("an empty request loses its offsets, any other keeps them", [] {
+    const I64 off0{0}, off2{0, 1, 2};
+    const I32 ids{0, 1}, val{3, 4};
+    const std::vector<double> theta(2 * kK, 1.0 / kK);
+    const UserQuery none = user_query(0, nullptr, 0, nullptr, off0.data(), nullptr);
+    const ThetaQuery none_t = theta_query(0, nullptr, off0.data(), nullptr, 0, nullptr);
+    if (none.excl.offsets || none_t.seen.offsets) throw std::runtime_error("no rows: offsets kept");
+    none.check(kUsers, "x: user", kItems, "x");
+    none_t.check(kItems, "x", "x");
+    const UserQuery two = user_query(2, ids.data(), 2, val.data(), off2.data(), val.data());
+    const ThetaQuery two_t = theta_query(2, theta.data(), off2.data(), val.data(), 2, val.data());
+    if (two.excl.offsets != off2.data() || two.excl.values != val.data() || two.users.ids != ids.data() || two.users.n != 2 ||
+        two.cand.items != val.data() || two.cand.n != 2)
+      throw std::runtime_error("two rows: the user query moved");
+    if (two_t.seen.offsets != off2.data() || two_t.seen.values != val.data() || two_t.theta != theta.data() || two_t.n_users != 2 ||
+        two_t.cand.items != val.data() || two_t.cand.n != 2)
+      throw std::runtime_error("two rows: the theta query moved");
+    two.check(kUsers, "x: user", kItems, "x");
+    two_t.check(kItems, "x", "x");
+    if (listed_items(off0.data(), nullptr).of_rows(0).offsets || listed_items(off2.data(), val.data()).of_rows(2).offsets != off2.data())
+      throw std::runtime_error("of_rows");
+  });
+  legal("the rows [b0, b0 + nb) of a query: ids from b0, the subset as it is, own lists counted from the first", [] {
+    // requests of 0, 1 and 5 rows: no lists; lists; empty lists at the first and the last row -- each with and without
+    // a subset.  Every array is exactly as long as the request says, so a read beyond one is the sanitizer's.
+    const I32 sub{1, 3, 5};
+    for (int64_t rows : {0, 1, 5})
+      for (int shape = 0; shape < 3; ++shape)
+        for (int with_sub = 0; with_sub < 2; ++with_sub) {
+          I32 ids(static_cast<size_t>(rows));
+          for (int64_t b = 0; b < rows; ++b) ids[static_cast<size_t>(b)] = static_cast<int32_t>(7 * b % kUsers);
+          I64 off(static_cast<size_t>(rows) + 1, 0);
+          for (int64_t b = 0; b < rows; ++b) {
+            const bool hollow = shape == 2 && (b == 0 || b == rows - 1);
+            off[static_cast<size_t>(b) + 1] = off[static_cast<size_t>(b)] + (hollow ? 0 : 1 + b % 3);
+          }
+          I32 val(static_cast<size_t>(off.back()));
+          for (size_t e = 0; e < val.size(); ++e) val[e] = static_cast<int32_t>(5 * e % kItems);
+          const bool lists = shape > 0;
+          const UserQuery q{{rows, ptr(ids, rows > 0)}, {with_sub ? 3 : 0, ptr(sub, with_sub != 0)},
+                            excluded_lists(ptr(off, lists), ptr(val, lists && !val.empty()))};
+          for (int64_t b0 = 0; b0 <= rows; ++b0)
+            for (int64_t nb = 0; b0 + nb <= rows; ++nb) {
+              I64 rebased{-7};   // (a previous call's contents must not show)
+              const UserQuery part = q.rows(b0, nb, rebased);
+              if (part.users.n != nb || part.cand.n != q.cand.n || part.cand.items != q.cand.items)
+                throw std::runtime_error("rows: the users or the subset");
+              for (int64_t k = 0; k < nb; ++k)
+                if (part.users.ids[k] != ids[static_cast<size_t>(b0 + k)]) throw std::runtime_error("rows: an id");
+              if (!lists) {
+                if (part.excl.offsets || part.excl.values) throw std::runtime_error("rows: lists from none");
+                continue;
+              }
+              // the restatement: offsets minus the first, values from the first
+              if (!part.excl.offsets || part.excl.off_name != q.excl.off_name) throw std::runtime_error("rows: no lists");
+              for (int64_t k = 0; k <= nb; ++k)
+                if (part.excl.offsets[k] != off[static_cast<size_t>(b0 + k)] - off[static_cast<size_t>(b0)])
+                  throw std::runtime_error("rows: an offset");
+              for (int64_t e = 0; e < part.excl.offsets[nb]; ++e)
+                if (part.excl.values[e] != val[static_cast<size_t>(off[static_cast<size_t>(b0)] + e)])
+                  throw std::runtime_error("rows: a value");
+              part.check(kUsers, "x: user", kItems, "x");   // (reads every offset and every value to the end)
+            }
+        }
   });
   if (refused_cap("recommend_allocate", 3, 1500, 2000) !=
       "recommend_allocate: the cap of item 3, 1500, is above 1024 and below the 2000 users of the request")

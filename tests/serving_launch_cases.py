@@ -20,7 +20,9 @@ The table a commit gives is recorded with
 committed table is the one of the commit BEFORE the queries' host side moved onto shared helpers and serve_plan.hpp: the
 refactor must not move an entry.  The cases from "quota" on were recorded before the queries added since then (quota,
 shelves, explore, allocate, assign, assortment, top_pairs_bulk, ensemble, the item side) moved onto one selection stage
-and one batch frame, with the library's sources as that commit's.
+and one batch frame, with the library's sources as that commit's.  The four from "theta-quota-candidates" on (the theta
+entries' seen lists and the propensity lists beside a candidate subset) were recorded, twice and equal, from the commit
+before the requests crossed from the C ABI into the units as values (abi_request.hpp).
 """
 import argparse
 import hashlib
@@ -288,6 +290,16 @@ CASES = {
     "ensemble-min": _basic(lambda em, s: em.recommend_query_ensemble(_users(s), 10, "min", candidates=_cand(s),
                                                                      exclude=own_lists(_rng(), s[0], s[1]))),
     "items": (MID, ("recommend",), lambda em, s: em.recommend_query_items(np.arange(0, s[1], 25, dtype=np.int32), 10)),
+    # the theta entries' seen lists and the propensity lists beside a candidate subset (recorded before the requests
+    # crossed into the units as values)
+    "theta-quota-candidates": _basic(lambda em, s: em.recommend_query_theta_quota(
+        theta_rows(_rng(), s[5], 4, s[2]), 10, *_cats(s[1]), _CAPS, seen=own_lists(_rng(), 4, s[1]), candidates=_cand(s))),
+    "theta-shelves-candidates": _basic(lambda em, s: em.recommend_query_theta_shelves(
+        theta_rows(_rng(), s[5], 4, s[2]), *_cats(s[1]), 5, 1, 3, 4, seen=own_lists(_rng(), 4, s[1]), candidates=_cand(s))),
+    "inform-theta-candidates": (BASIC, ("inform",), lambda em, s: em.inform_query_theta(
+        theta_rows(_rng(), s[5], 4, s[2]), 10, seen=own_lists(_rng(), 4, s[1]), candidates=_cand(s))),
+    "list-propensity-own": _basic(lambda em, s: em.recommend_list_propensity(
+        _users(s), _lists(s), 0.1, candidates=_cand(s), exclude=own_lists(_rng(), s[0], s[1]))),
 }
 
 

@@ -70,6 +70,40 @@ def test_the_recommend_unit_includes_only_its_own_kernel_headers():
         assert includes(read(unit + ".hip"))[:2] == ["prelude.hpp", "serve_frame.hpp"], unit
 
 
+def test_a_request_crosses_into_the_units_as_values():
+    """The runs of loose pointers and counts end at the C ABI: as function parameters -- a type, the name,
+    then `,` or `)` -- their spellings occur in mmsbm_hip.hip (the ABI's own signatures) and in the two factory
+    functions of abi_request.hpp (user_query, theta_query), nowhere else under csrc/.  serve_plan.hpp stands alone for
+    its native dump programs and keeps plain arguments (n_cand, cat_off); the kernel headers are not host seams (one
+    kernel of diverse.hpp names an argument n_cand)."""
+    names = r"(?:int(?:32_t)?\s+n_cand|\*\s*(?:excl_offsets|seen_offsets|cat_offsets|list_offsets))\s*[,)]"
+    factories = r"inline \w+Query (?:user|theta)_query\([^)]*\)"
+    found = {}
+    for f in sorted(os.listdir(build.CSRC)):
+        if not f.endswith((".hip", ".hpp")) or f in ("mmsbm_hip.hip", "unity.hip"):
+            continue
+        text = code(read(f))
+        if kernels(read(f)):                     # (a kernel header: device code, where a kernel names its own arguments)
+            continue
+        if f == "abi_request.hpp":
+            assert len(re.findall(factories, text)) == 2
+            text = re.sub(factories, "", text)
+        if f == "serve_plan.hpp":
+            text = re.sub(r"int(?:32_t)?\s+n_cand\s*[,)]", "", text)
+        hits = re.findall(names, text)
+        if hits:
+            found[f] = hits
+    assert not found, found
+    assert re.search(names, code(read("mmsbm_hip.hip")))     # (the pattern does find the ABI's signatures)
+    for f in os.listdir(build.CSRC):
+        if f.endswith(".hip"):
+            assert "offsets_of(" not in code(read(f)), f
+    for f in os.listdir(build.CSRC):
+        assert "QuotaCats" not in read(f), f
+    assert "AssignOut" in code(read("abi_request.hpp"))
+    assert not re.search(r"struct\s+AssignOut", code(read("launch.hpp")))
+
+
 def test_the_build_runs_no_more_compilers_than_the_job_may_use(monkeypatch):
     """MAX_JOBS, then CMAKE_BUILD_PARALLEL_LEVEL, cap the compilers build_library starts side by side when set to a
     positive integer; anything else leaves the machine's core count in charge."""
